@@ -9,7 +9,7 @@ self pairs (default rule minus the removals of _test_rrt.py:38-61) + one Cube(ha
 writing the packed bit mask, and for N > 1 the RCCL all-gather of every rank's mask words.  The timed loop rotates
 over 5 distinct q batches (5 x 56 MB = 280 MB > the 256 MiB Infinity Cache), so no step finds its input in cache.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  `value` is whole-job configurations / wall time of the K timed steps (inputs resident in
@@ -53,6 +53,35 @@ def stats_ms(ms):
             "min_ms": ms[0], "mean_ms": float(np.mean(ms)), "reps": len(ms)}
 
 
+DUMP_MAX_FULL = 8 << 20        # configurations written whole (32 MiB of float32); above that a seeded sample
+DUMP_SAMPLE = 4 << 20          # sampled configurations: 16 MiB of flags + 32 MiB of float64 indices
+
+
+def dump_outputs(out_dir, words, total, world):
+    """--dump-outputs: the packed mask words of the last timed step -> out_dir/in_collision.npy (float32 0/1, one per
+    configuration of the job, rank order).  Above DUMP_MAX_FULL configurations, a fixed seeded sample of them and its indices
+    (in_collision_index.npy, float64).  Returns what was written, for the JSON line."""
+    from numbotics_amd.parallel import shard_bounds, shard_words
+    w = np.ascontiguousarray(words).view(np.uint64).astype("<u8")
+    bits = np.unpackbits(w.view(np.uint8), bitorder="little")          # bit b%64 of word b//64
+    g_words = shard_words(total, world) if world > 1 else w.size
+    parts = []
+    for r in range(world):                                             # every rank's words start on its own word boundary
+        lo, hi = shard_bounds(total, world, r)
+        parts.append(bits[r * g_words * 64:r * g_words * 64 + (hi - lo)])
+    mask = np.concatenate(parts).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"in_collision": {"configurations": int(mask.size)}}
+    if mask.size > DUMP_MAX_FULL:
+        idx = np.sort(np.random.default_rng(0).choice(mask.size, DUMP_SAMPLE, replace=False))
+        mask = mask[idx]
+        np.save(os.path.join(out_dir, "in_collision_index.npy"), idx.astype(np.float64))
+        files["in_collision"]["sampled"] = DUMP_SAMPLE
+        files["in_collision_index"] = {"sampled": DUMP_SAMPLE}
+    np.save(os.path.join(out_dir, "in_collision.npy"), mask)
+    return {"dir": out_dir, "files": files}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -70,7 +99,12 @@ def main():
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="rehearsal on a 1-GPU box: every rank uses cuda:0")
     ap.add_argument("--sync-gather", action="store_true", help="N > 1: wait for every step's mask all-gather before the next step's kernels "
                     "(default: the gather of step k overlaps the kernels of step k+1; everything completes inside the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the mask the last step computed "
+                    "(the whole job's, all-gathered when N > 1) as DIR/in_collision.npy, one float32 0/1 per configuration; the inputs are "
+                    "seeded, so two builds run with the same arguments compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -174,6 +208,11 @@ def main():
     kern = stats_ms(step_ms)
     kern_ms = kern["mean_ms"]
     last_q_host = q_host if (args.steps - 1) % N_ROTATE == 0 else sample_q(chain, B, seed=1 + rank + 1000 * ((args.steps - 1) % N_ROTATE))
+    # the last timed step's packed mask as its caller receives it (N > 1: the gathered words of every rank), copied off the clock
+    dump_words = None
+    if args.dump_outputs and rank == 0:
+        last = words if world == 1 else (bufs[(counter[0] - 1) & 1] if state["overlap"] else gathered)
+        dump_words = last.cpu().numpy()
 
     # ---- BASELINE config 4, whenever N > 1 (no flag needed): a 1e7-q batch strong-scaled over the ranks, packed masks all-gathered ---------
     config4 = None
@@ -574,6 +613,9 @@ def main():
                                "single_thread_value": one_thread}
     else:
         out["cpu_baseline"] = None
+
+    if dump_words is not None:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, dump_words, total, world)
 
     print(json.dumps(out))
     if world > 1:
