@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <mutex>
 #include <algorithm>
 #include <vector>
@@ -127,23 +128,28 @@ namespace nbk {
 // capacity in samples; `stats` is pinned host memory the device writes the true sample count into (read, never waited for, at the
 // start of the NEXT call to grow the capacity).
 struct StreamWs {
-    hipStream_t stream;
-    std::mutex mu;                  // two host threads driving one stream
-    void* ws; size_t ws_bytes;
-    bool ready; double thr; unsigned epoch;
-    bool captured;                  // a call on this stream has been captured into a hipGraph: its nodes reuse this workspace (counter
+    hipStream_t stream = nullptr;
+    std::mutex mu;                  // two host threads driving one stream (also makes the set non-copyable)
+    void* ws = nullptr; size_t ws_bytes = 0;
+    bool ready = false; double thr = 0.0; unsigned epoch = 0;
+    bool captured = false;          // a call on this stream has been captured into a hipGraph: its nodes reuse this workspace (counter
                                     // set 0, the tables for THEIR threshold) whenever the graph is replayed, behind the host's back, so
                                     // direct calls on this stream never trust `ready` again -- each prepares its tables and clears both
                                     // counter sets itself (one more 5 us launch per call)
-    void* ews; size_t ews_bytes;
-    long long ecap_edges; unsigned long long ecap_samples;
-    unsigned long long* stats;      // [4] pinned + mapped: samples needed by the last finished edge call, edges served by the overflow kernel
-    unsigned long long* stats_dev;  // device alias of `stats`
+    void* ews = nullptr; size_t ews_bytes = 0;
+    long long ecap_edges = 0; unsigned long long ecap_samples = 0;
+    unsigned long long* stats = nullptr;      // [4] pinned + mapped: samples needed by the last finished edge call, edges served by the overflow kernel
+    unsigned long long* stats_dev = nullptr;  // device alias of `stats`
     // tile pipelining of batches of several tiles: odd tiles run on `aux_stream` with the scratch set `aux` (forked from / joined
     // to the caller's stream with events), so the latency-bound narrowphase of one tile overlaps the issue-bound broadphase of the next
-    hipStream_t aux_stream;
-    hipEvent_t ev_fork, ev_join;
-    StreamWs* aux;
+    hipStream_t aux_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    StreamWs* aux = nullptr;        // another entry of the descriptor's list, freed as such: not owned here
+    ~StreamWs() {
+        if (ws) (void)hipFree(ws);  if (ews) (void)hipFree(ews);  if (stats) (void)hipHostFree(stats);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);  if (ev_join) (void)hipEventDestroy(ev_join);
+        if (aux_stream) (void)hipStreamDestroy(aux_stream);
+    }
 };
 }  // namespace nbk
 
@@ -196,6 +202,7 @@ static int hip_fail(hipError_t e, const char* what) {
     } while (0)
 
 constexpr int WAVE = 64;
+constexpr size_t LDS_MAX = 160 * 1024;     // LDS per workgroup on gfx950 (MI355X_MICROARCH.md)
 
 NBK_DEV int core_rows(int kind) { return kind == K_POINT ? 3 : ((kind == K_BOX || kind == K_HULL) ? 12 : 6); }
 
@@ -3828,7 +3835,7 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     if (3 * S >= 65536 || W >= 65536) return NBK_ERR_UNSUPPORTED;
     // the LDS broadphase (robots with more than 16 primitives) keeps the pair constants and world cores in LDS; robots the
     // register broadphases serve do not need it, however many world shapes there are
-    const bool lds_broad_ok = (size_t)(d->n_q + 12 * slots + 3 * S) * 64 * sizeof(double) + (4 * (size_t)P + 18 * (size_t)W) * sizeof(double) + BQ_CAP * 4 <= 160 * 1024;
+    const bool lds_broad_ok = (size_t)(d->n_q + 12 * slots + 3 * S) * 64 * sizeof(double) + (4 * (size_t)P + 18 * (size_t)W) * sizeof(double) + BQ_CAP * 4 <= LDS_MAX;
     if (!lds_broad_ok && S > 16) return NBK_ERR_UNSUPPORTED;
     if (P >= (1 << 20)) return NBK_ERR_UNSUPPORTED;
     // LDS budget: q rows + shape rows + saved frames, 512 B each (+ queue and flags of the validity path);
@@ -3836,8 +3843,8 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     const size_t lds_bytes = (size_t)(d->n_q + (rows > d->n_q ? rows : d->n_q) + 12 * slots) * 64 * sizeof(double) + VALIDITY_LDS_EXTRA;
     // robots whose primitives do not fit the LDS-parked layout (some 25+ shapes) keep validity and edges, through the
     // broadphase + narrowphase kernels at every batch size; the per-pair distance entry points report UNSUPPORTED for them
-    const bool parked_ok = lds_bytes <= 160 * 1024;
-    if (S <= 16 && (size_t)d->n_q * 64 * sizeof(double) + 12 * (size_t)slots * 64 * sizeof(float) + 4096 > 160 * 1024) return NBK_ERR_UNSUPPORTED;
+    const bool parked_ok = lds_bytes <= LDS_MAX;
+    if (S <= 16 && (size_t)d->n_q * 64 * sizeof(double) + 12 * (size_t)slots * 64 * sizeof(float) + 4096 > LDS_MAX) return NBK_ERR_UNSUPPORTED;
     if (P >= (1 << 26)) return NBK_ERR_UNSUPPORTED;
 
     Blob B;
@@ -4161,15 +4168,7 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
 void nbk_model_destroy(nbk_model* m) {
     if (m == nullptr) return;
     if (m->blob) (void)hipFree(m->blob);
-    for (StreamWs* w : m->wss) {
-        if (w->ws) (void)hipFree(w->ws);
-        if (w->ews) (void)hipFree(w->ews);
-        if (w->stats) (void)hipHostFree(w->stats);
-        if (w->ev_fork) (void)hipEventDestroy(w->ev_fork);
-        if (w->ev_join) (void)hipEventDestroy(w->ev_join);
-        if (w->aux_stream) (void)hipStreamDestroy(w->aux_stream);
-        delete w;
-    }
+    for (StreamWs* w : m->wss) delete w;
     if (m->scalar_q) (void)hipHostFree(m->scalar_q);
     if (m->scalar_out) (void)hipHostFree(m->scalar_out);
     if (m->scalar_stream) (void)hipStreamDestroy(m->scalar_stream);
@@ -4271,6 +4270,25 @@ static bool stream_capturing(hipStream_t st) {
 
 static inline unsigned blocks_for(int64_t B) { return (unsigned)((B + WAVE - 1) / WAVE); }
 
+// ---- LDS each kernel family asks for, per workgroup (held against LDS_MAX) ----
+// FK: at least 17 q rows; frame sets add a q slab and the saved frames
+static inline size_t fk_lds(const nbk_model* m) { return sizeof(double) * WAVE * (size_t)(m->n_q > 17 ? m->n_q : 17); }
+static inline size_t fk_frames_lds(const nbk_model* m) { return fk_lds(m) + sizeof(double) * WAVE * ((size_t)m->n_q + 12 * (size_t)m->d.frame_slots); }
+// k_jacobian_reg (paths of up to 8 joints): the rows reuse the q area; k_jacobian: q slab + one row of 6 n_q columns (odd stride) per lane
+static inline size_t jacobian_reg_lds(const nbk_model* m) { return sizeof(double) * std::max((size_t)WAVE * m->n_q, (size_t)JAC_ROWS * ((6 * m->n_q) | 1)); }
+static inline size_t jacobian_lds(const nbk_model* m) { return sizeof(double) * WAVE * ((size_t)m->n_q + 6 * (size_t)m->n_q + 1); }
+static inline size_t ik_lds(const nbk_model* m, int path_len) { return sizeof(double) * WAVE * ((size_t)m->n_q * 7 + 6 * (size_t)(path_len > 0 ? path_len : 1)); }
+// the parked robot of 64 configurations: q rows + shape rows + saved frames, + the queue and flags of the validity path
+static inline size_t collide_lds(const nbk_model* m) {
+    return sizeof(double) * WAVE * ((size_t)m->d.n_q + (size_t)m->d.shape_rows + 12 * (size_t)m->d.frame_slots) + VALIDITY_LDS_EXTRA;
+}
+// k_closest: the parked robot without the validity queue, + its branch-and-bound arrays
+static inline size_t closest_lds(const nbk_model* m) { return collide_lds(m) - VALIDITY_LDS_EXTRA + sizeof(double) * CQ_CAP + 12 * WAVE + 6 * CQ_CAP; }
+// the two-wave k_distances<1..3>: room for the second wave's EPA queue; <3> (proximity) also keeps 6 Jacobian rows per joint and lane
+static inline size_t distances_lds(const nbk_model* m) { return collide_lds(m) + 8 * EPAQ_DOUBLES; }
+static inline size_t proximity_lds(const nbk_model* m) { return distances_lds(m) + sizeof(double) * WAVE * 6 * (size_t)m->n_joints; }
+static inline int broad_bucket(int S) { return S <= 8 ? 8 : (S <= 12 ? 12 : 16); }      // template size of the register broadphases
+
 int32_t nbk_fk_batch(const nbk_model* m, const double* q, int64_t B, const int32_t* path, int32_t path_len,
                      const double* local, const double* local_pose, double* T_out, void* stream) {
     if (m == nullptr || B < 0 || (B > 0 && (q == nullptr || T_out == nullptr))) return NBK_ERR_INVALID;
@@ -4279,9 +4297,8 @@ int32_t nbk_fk_batch(const nbk_model* m, const double* q, int64_t B, const int32
     const int st = make_path(m, path, path_len, local, pa);
     if (st != NBK_OK) return st;
     if (B == 0) return NBK_OK;
-    const size_t lds = sizeof(double) * WAVE * ((size_t)(m->n_q > 17 ? m->n_q : 17));
-    if (m->n_q <= 8 && !g_opt.fk_lds_q) hipLaunchKernelGGL(k_fk<true>, dim3(blocks_for(B)), dim3(WAVE), sizeof(double) * WAVE * 17, (hipStream_t)stream, m->d, pa, q, B, local_pose, T_out);
-    else hipLaunchKernelGGL(k_fk<false>, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, pa, q, B, local_pose, T_out);
+    if (m->n_q <= 8 && !g_opt.fk_lds_q) hipLaunchKernelGGL(k_fk<true>, dim3(blocks_for(B)), dim3(WAVE), fk_lds(m), (hipStream_t)stream, m->d, pa, q, B, local_pose, T_out);
+    else hipLaunchKernelGGL(k_fk<false>, dim3(blocks_for(B)), dim3(WAVE), fk_lds(m), (hipStream_t)stream, m->d, pa, q, B, local_pose, T_out);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -4335,10 +4352,8 @@ int32_t nbk_fk_frames_batch(const nbk_model* m, const nbk_frameset* fs, const do
     if (m == nullptr || fs == nullptr || B < 0 || (B > 0 && (q == nullptr || T_out == nullptr))) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     if (B == 0) return NBK_OK;
-    const size_t tr = (size_t)(m->n_q > 17 ? m->n_q : 17);
-    const size_t lds = sizeof(double) * WAVE * ((size_t)m->n_q + 12 * (size_t)m->d.frame_slots + tr);
-    if (lds > 160 * 1024) return NBK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_fk_frames, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, q, B, fs->n, fs->begin, fs->out,
+    if (fk_frames_lds(m) > LDS_MAX) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_fk_frames, dim3(blocks_for(B)), dim3(WAVE), fk_frames_lds(m), (hipStream_t)stream, m->d, q, B, fs->n, fs->begin, fs->out,
                        fs->local, T_out);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
@@ -4362,18 +4377,12 @@ int32_t nbk_jacobian_batch(const nbk_model* m, const double* q, int64_t B, const
     if (st != NBK_OK) return st;
     if (B == 0) return NBK_OK;
     if (pa.len <= 8 && !g_opt.jac_two_sweep) {
-        const int stride = (6 * m->n_q) | 1;
-        const size_t lds_q = (size_t)WAVE * (size_t)m->n_q, lds_rows = (size_t)JAC_ROWS * (size_t)stride;     // the rows reuse the q area
-        const size_t lds = sizeof(double) * (lds_q > lds_rows ? lds_q : lds_rows);
-        hipLaunchKernelGGL(k_jacobian_reg<8>, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, pa, q, B, mode | (g_opt.fk_lds_q ? 256 : 0), pose, J_out);
+        hipLaunchKernelGGL(k_jacobian_reg<8>, dim3(blocks_for(B)), dim3(WAVE), jacobian_reg_lds(m), (hipStream_t)stream, m->d, pa, q, B, mode | (g_opt.fk_lds_q ? 256 : 0), pose, J_out);
         NBK_HIP(hipGetLastError());
         return NBK_OK;
     }
-    const int ncol = 6 * m->n_q;
-    const int stride = ncol + 1 + ((ncol + 1) & 1 ? 0 : 1);
-    const size_t lds = sizeof(double) * WAVE * ((size_t)m->n_q + (size_t)stride);
-    if (lds > 160 * 1024) return NBK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_jacobian, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, pa, q, B, mode, pose, J_out);
+    if (jacobian_lds(m) > LDS_MAX) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_jacobian, dim3(blocks_for(B)), dim3(WAVE), jacobian_lds(m), (hipStream_t)stream, m->d, pa, q, B, mode, pose, J_out);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -4393,16 +4402,11 @@ int32_t nbk_ik_batch(const nbk_model* m, const double* pose, const double* q0, i
     arg.tol = tol; arg.max_iter = max_iter; arg.max_failures = max_failures; arg.use_limits = limits != nullptr ? 1 : 0;
     if (limits != nullptr)
         for (int j = 0; j < m->n_q; ++j) { arg.lo[j] = limits[2 * j]; arg.hi[j] = limits[2 * j + 1]; }
-    const size_t lds = sizeof(double) * WAVE * ((size_t)m->n_q * 7 + 6 * (size_t)(pa.len > 0 ? pa.len : 1));
-    if (lds > 160 * 1024) return NBK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_ik, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, pa, arg, pose, q0, B, q_out, success,
+    if (ik_lds(m, pa.len) > LDS_MAX) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_ik, dim3(blocks_for(B)), dim3(WAVE), ik_lds(m, pa.len), (hipStream_t)stream, m->d, pa, arg, pose, q0, B, q_out, success,
                        diff_norm, iters);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
-}
-
-static inline size_t collide_lds(const nbk_model* m) {
-    return sizeof(double) * WAVE * ((size_t)m->d.n_q + (size_t)m->d.shape_rows + 12 * (size_t)m->d.frame_slots) + VALIDITY_LDS_EXTRA;
 }
 
 // ---- validity: fused kernel for small batches, broadphase + compacted narrowphase for large ones -------
@@ -4491,9 +4495,7 @@ static StreamWs* stream_ws(nbk_model* mm, hipStream_t st) {
     for (StreamWs* w : mm->wss) if (w->stream == st) return w;
     if (mm->wss.size() >= 64) return nullptr;
     StreamWs* w = new StreamWs();
-    w->stream = st; w->ws = nullptr; w->ws_bytes = 0; w->ready = false; w->thr = 0.0; w->epoch = 0; w->captured = false;
-    w->ews = nullptr; w->ews_bytes = 0; w->ecap_edges = 0; w->ecap_samples = 0; w->stats = nullptr; w->stats_dev = nullptr;
-    w->aux_stream = nullptr; w->ev_fork = nullptr; w->ev_join = nullptr; w->aux = nullptr;
+    w->stream = st;
     mm->wss.push_back(w);
     return w;
 }
@@ -4506,6 +4508,16 @@ static int32_t grow_scratch(hipStream_t st, void*& buf, size_t& have, size_t nee
     hipError_t e = hipMalloc(&buf, need);
     if (e != hipSuccess) { hip_fail(e, what); return NBK_ERR_ALLOC; }
     have = need;
+    return NBK_OK;
+}
+
+// grow the validity workspace of a scratch set to `need` bytes: a new buffer has no overflow marks and no tables yet
+static int32_t ensure_validity_ws(const nbk_model* m, StreamWs* w, size_t need, hipStream_t st, const char* what) {
+    if (w->ws_bytes >= need) return NBK_OK;
+    w->ready = false;
+    const int32_t rc = grow_scratch(st, w->ws, w->ws_bytes, need, what);
+    if (rc != NBK_OK) return rc;
+    NBK_HIP(hipMemsetAsync(static_cast<char*>(w->ws) + ws_tables(m), 0, WS_FLAGS, st));
     return NBK_OK;
 }
 
@@ -4561,7 +4573,7 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
     const int narrow_build = narrow_variant(m, threshold);
     const int S = m->d.n_rshapes;
     const bool use_reg = S <= 16 && (!g_opt.no_reg_broad || !m->lds_broad_ok);
-    const bool f32 = !g_opt.f64_broad || broad_reg_lds(m, S <= 8 ? 8 : (S <= 12 ? 12 : 16)) > 160 * 1024;   // the float64 form keeps its tables in LDS
+    const bool f32 = !g_opt.f64_broad || broad_reg_lds(m, broad_bucket(S)) > LDS_MAX;   // the float64 form keeps its tables in LDS
     int tile_no = 0;
     for (int64_t b0 = 0; b0 < B; b0 += tile, ++tile_no) {
         const bool odd = pipe && (tile_no & 1);
@@ -4587,7 +4599,7 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
         uint8_t* my = mask_bytes ? mask_bytes + b0 : nullptr;
         float* ftab = reinterpret_cast<float*>(static_cast<char*>(workspace) + WS_COUNTERS);
         // LDS of the float32 kernel: q slab (later the item queue) + saved frames
-        const size_t qrows_f = (size_t)f32_qrows(m->d.n_q, S <= 8 ? 8 : (S <= 12 ? 12 : 16));
+        const size_t qrows_f = (size_t)f32_qrows(m->d.n_q, broad_bucket(S));
         const size_t lds_f = sizeof(double) * WAVE * qrows_f + sizeof(float) * WAVE * 12 * (size_t)m->d.frame_slots + 16 + sizeof(float) * WAVE * NBK_ZSLOTS;   // (+ the z coordinates of the slots k_broad_f32 keeps in LDS)
         unsigned long long* count_next = nullptr;
         if (use_reg && f32) {
@@ -4654,8 +4666,13 @@ static int32_t launch_two_kernel(const nbk_model* m, const PairCounts& pc, EdgeS
     return rc;
 }
 
+static int64_t two_kernel_workspace_bytes(const nbk_model* m, const PairCounts& pc, int64_t B, bool pipe = false) {
+    const int64_t nblk = (call_tile(m, pc, B, pipe) + WAVE - 1) / WAVE;
+    return (int64_t)ws_header(m) + 8 * (int64_t)NSUB * (int64_t)tile_queue_cap(m, pc, (unsigned long long)nblk);
+}
+
 // the second stream, its events and its scratch set of a pipelined call (created on first use; never while capturing)
-static int32_t pipe_setup(nbk_model* mm, const nbk_model* m, const PairCounts& pc, StreamWs* w, int64_t B, hipStream_t st) {
+static int32_t pipe_setup(nbk_model* mm, const nbk_model* m, const PairCounts& pc, StreamWs* w, int64_t B) {
     if (w->aux_stream == nullptr) {
         NBK_HIP(hipStreamCreateWithFlags(&w->aux_stream, hipStreamNonBlocking));
         NBK_HIP(hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming));
@@ -4663,21 +4680,7 @@ static int32_t pipe_setup(nbk_model* mm, const nbk_model* m, const PairCounts& p
         w->aux = stream_ws(mm, w->aux_stream);
         if (w->aux == nullptr) return NBK_ERR_ALLOC;
     }
-    const int64_t nblk = (call_tile(m, pc, B, true) + WAVE - 1) / WAVE;
-    const size_t need = ws_header(m) + 8 * (size_t)NSUB * (size_t)tile_queue_cap(m, pc, (unsigned long long)nblk);
-    if (w->aux->ws_bytes < need) {
-        w->aux->ready = false;
-        const int32_t rc = grow_scratch(w->aux_stream, w->aux->ws, w->aux->ws_bytes, need, "hipMalloc(workspace, second stream)");
-        if (rc != NBK_OK) return rc;
-        NBK_HIP(hipMemsetAsync(static_cast<char*>(w->aux->ws) + ws_tables(m), 0, WS_FLAGS, w->aux_stream));
-    }
-    (void)st;
-    return NBK_OK;
-}
-
-static int64_t two_kernel_workspace_bytes(const nbk_model* m, const PairCounts& pc, int64_t B, bool pipe = false) {
-    const int64_t nblk = (call_tile(m, pc, B, pipe) + WAVE - 1) / WAVE;
-    return (int64_t)ws_header(m) + 8 * (int64_t)NSUB * (int64_t)tile_queue_cap(m, pc, (unsigned long long)nblk);
+    return ensure_validity_ws(m, w->aux, (size_t)two_kernel_workspace_bytes(m, pc, B, true), w->aux_stream, "hipMalloc(workspace, second stream)");
 }
 
 int64_t nbk_validity_workspace_bytes(const nbk_model* m, int64_t B) {
@@ -4726,21 +4729,16 @@ int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, doubl
     StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
     if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces: pass your own (nbk_validity_batch_ws)"); return NBK_ERR_ALLOC; }
     std::lock_guard<std::mutex> lock(w->mu);
-    if (w->ws_bytes < (size_t)need) {
-        if (capturing) {
-            snprintf(g_err, sizeof(g_err), "graph capture: this stream's internal workspace is not allocated yet -- run the call once "
-                     "outside the capture, or pass a workspace (nbk_validity_batch_ws)");
-            return NBK_ERR_UNSUPPORTED;
-        }
-        w->ready = false;
-        const int32_t rc = grow_scratch(st, w->ws, w->ws_bytes, (size_t)need, "hipMalloc(workspace)");
-        if (rc != NBK_OK) return rc;
-        NBK_HIP(hipMemsetAsync(static_cast<char*>(w->ws) + ws_tables(m), 0, WS_FLAGS, st));      // no overflow marks yet
+    if (capturing && w->ws_bytes < (size_t)need) {
+        snprintf(g_err, sizeof(g_err), "graph capture: this stream's internal workspace is not allocated yet -- run the call once "
+                 "outside the capture, or pass a workspace (nbk_validity_batch_ws)");
+        return NBK_ERR_UNSUPPORTED;
     }
+    { const int32_t rc = ensure_validity_ws(m, w, (size_t)need, st, "hipMalloc(workspace)"); if (rc != NBK_OK) return rc; }
     // a captured call must be self-contained (it is replayed out of order with the host-side state): prepare + clear inside
     // the graph, and the next direct call starts from scratch as well
     if (capturing) { w->ready = false; w->captured = true; }
-    if (pipe) { const int32_t rc = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, B, st); if (rc != NBK_OK) return rc; }
+    if (pipe) { const int32_t rc = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, B); if (rc != NBK_OK) return rc; }
     return launch_two_kernel(m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, w->ws, st, capturing ? nullptr : w, pipe);
 }
 
@@ -4764,12 +4762,11 @@ int32_t nbk_closest_batch(const nbk_model* m, const double* q, int64_t B, double
     if (B == 0) return NBK_OK;
     // branch-and-bound needs its result / best / argmin / queue / EPA-list arrays next to the parked cores; a robot that leaves no room
     // for them gets every pair evaluated (same result)
-    const size_t closest_lds = collide_lds(m) - VALIDITY_LDS_EXTRA + sizeof(double) * CQ_CAP + 8 * WAVE + 4 * WAVE + 4 * CQ_CAP + 2 * CQ_CAP;
-    if (g_opt.closest_brute || closest_lds > 160 * 1024)
+    if (g_opt.closest_brute || closest_lds(m) > LDS_MAX)
         hipLaunchKernelGGL(k_distances<0>, dim3(blocks_for(B)), dim3(WAVE), collide_lds(m), (hipStream_t)stream, m->d, q, B, min_dist,
                            argmin, (double*)nullptr);
     else
-        hipLaunchKernelGGL(k_closest, dim3(blocks_for(B)), dim3(WAVE), closest_lds, (hipStream_t)stream, m->d, q, B, min_dist, argmin);
+        hipLaunchKernelGGL(k_closest, dim3(blocks_for(B)), dim3(WAVE), closest_lds(m), (hipStream_t)stream, m->d, q, B, min_dist, argmin);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -4777,13 +4774,13 @@ int32_t nbk_closest_batch(const nbk_model* m, const double* q, int64_t B, double
 int32_t nbk_pair_distances_batch(const nbk_model* m, const double* q, int64_t B, double* dist, double* witness, void* stream) {
     if (m == nullptr || B < 0 || (B > 0 && (q == nullptr || dist == nullptr))) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
-    if (!m->parked_ok || collide_lds(m) + 8 * EPAQ_DOUBLES > 160 * 1024) return NBK_ERR_UNSUPPORTED;
+    if (!m->parked_ok || distances_lds(m) > LDS_MAX) return NBK_ERR_UNSUPPORTED;
     if (B == 0 || m->n_pairs == 0) return NBK_OK;
     if (witness != nullptr)
-        hipLaunchKernelGGL(k_distances<2>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), collide_lds(m) + 8 * EPAQ_DOUBLES, (hipStream_t)stream, m->d, q, B, dist,
+        hipLaunchKernelGGL(k_distances<2>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), distances_lds(m), (hipStream_t)stream, m->d, q, B, dist,
                            (int32_t*)nullptr, witness);
     else
-        hipLaunchKernelGGL(k_distances<1>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), collide_lds(m) + 8 * EPAQ_DOUBLES, (hipStream_t)stream, m->d, q, B, dist,
+        hipLaunchKernelGGL(k_distances<1>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), distances_lds(m), (hipStream_t)stream, m->d, q, B, dist,
                            (int32_t*)nullptr, (double*)nullptr);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
@@ -4795,9 +4792,8 @@ int32_t nbk_proximity_jacobian_batch(const nbk_model* m, const double* q, int64_
     NBK_DEVICE(m);
     if (!m->parked_ok) return NBK_ERR_UNSUPPORTED;
     if (B == 0 || m->n_pairs == 0) return NBK_OK;
-    const size_t lds = collide_lds(m) + sizeof(double) * WAVE * 6 * (size_t)m->n_joints + 8 * EPAQ_DOUBLES;
-    if (lds > 160 * 1024) return NBK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_distances<3>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), lds, (hipStream_t)stream, m->d, q, B, dist, (int32_t*)nullptr,
+    if (proximity_lds(m) > LDS_MAX) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_distances<3>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), proximity_lds(m), (hipStream_t)stream, m->d, q, B, dist, (int32_t*)nullptr,
                        witness, jrows);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
@@ -4818,6 +4814,16 @@ static inline unsigned long long edge_capacity(int64_t E, double resolution, dou
     if (c > 4.0e9) c = 4.0e9;
     return ((unsigned long long)c + 63ull) & ~63ull;
 }
+
+// a stream's edge scratch for ne edges and nc samples: plan [ne][3] double | cnt [ne + 1] | offs [ne + 1] | overflow flags [ne],
+// then the sample map [nc] and the mask words [nc / 64], each of the three parts rounded up to 4 KiB.  Byte offsets (plan at 0), total
+struct EdgeLayout {
+    size_t cnt, offs, ovf, map, words, bytes;
+    static size_t r4k(size_t n) { return (n + 4095) & ~size_t(4095); }
+    EdgeLayout(long long ne, unsigned long long nc)
+        : cnt((size_t)ne * 3 * 8), offs(cnt + (size_t)(ne + 1) * 8), ovf(offs + (size_t)(ne + 1) * 8), map(r4k(ovf + (size_t)ne)),
+          words(map + r4k((size_t)nc * 8)), bytes(words + r4k(((size_t)nc + 63) / 64 * 8)) {}
+};
 
 int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
                                 double resolution, double max_distance, int32_t mode, double threshold, uint8_t* valid,
@@ -4853,10 +4859,8 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
         if (capturing) { snprintf(g_err, sizeof(g_err), "graph capture of edge batches needs a robot that fits the LDS-parked layout"); return NBK_ERR_UNSUPPORTED; }
     }
     const PairCounts pc = reachable_pairs(m, threshold);
-    double* plan = nullptr;
+    double* plan = nullptr; uint8_t* ovf = nullptr; uint64_t* words = nullptr;
     unsigned long long *cnt = nullptr, *offs = nullptr, *map = nullptr;
-    uint8_t* ovf = nullptr;
-    uint64_t* words = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool fits = w->ecap_edges >= E && w->ecap_samples >= cap && w->stats != nullptr &&
                           w->ws_bytes >= (size_t)two_kernel_workspace_bytes(m, pc, (int64_t)w->ecap_samples);
@@ -4873,29 +4877,21 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
             }
             const long long ne = w->ecap_edges > E ? w->ecap_edges : E;
             const unsigned long long nc = w->ecap_samples > cap ? w->ecap_samples : cap;
-            const size_t head_n = ((size_t)ne * 3 * 8 + (size_t)(ne + 1) * 8 * 2 + (size_t)ne + 4095) & ~size_t(4095);   // plan | cnt | offs | overflow flags
-            const size_t map_n = ((size_t)nc * 8 + 4095) & ~size_t(4095);
-            const size_t words_n = (((size_t)nc + 63) / 64 * 8 + 4095) & ~size_t(4095);
-            int32_t rc = grow_scratch(st, w->ews, w->ews_bytes, head_n + map_n + words_n, "hipMalloc(edge scratch)");
+            int32_t rc = grow_scratch(st, w->ews, w->ews_bytes, EdgeLayout(ne, nc).bytes, "hipMalloc(edge scratch)");
             if (rc != NBK_OK) return rc;
             w->ecap_edges = ne; w->ecap_samples = nc;
-            const size_t need = (size_t)two_kernel_workspace_bytes(m, pc, (int64_t)nc);
-            if (w->ws_bytes < need) {
-                w->ready = false;
-                rc = grow_scratch(st, w->ws, w->ws_bytes, need, "hipMalloc(workspace)");
-                if (rc != NBK_OK) return rc;
-                NBK_HIP(hipMemsetAsync(static_cast<char*>(w->ws) + ws_tables(m), 0, WS_FLAGS, st));
-            }
+            rc = ensure_validity_ws(m, w, (size_t)two_kernel_workspace_bytes(m, pc, (int64_t)nc), st, "hipMalloc(workspace)");
+            if (rc != NBK_OK) return rc;
         }
         cap = w->ecap_samples;                                 // use all of what is there
-        const size_t head_c = ((size_t)w->ecap_edges * 3 * 8 + (size_t)(w->ecap_edges + 1) * 8 * 2 + (size_t)w->ecap_edges + 4095) & ~size_t(4095);
-        const size_t map_c = ((size_t)cap * 8 + 4095) & ~size_t(4095);
-        plan = static_cast<double*>(w->ews);
-        cnt = reinterpret_cast<unsigned long long*>(plan + 3 * w->ecap_edges);
-        offs = cnt + (w->ecap_edges + 1);
-        ovf = reinterpret_cast<uint8_t*>(offs + (w->ecap_edges + 1));
-        map = reinterpret_cast<unsigned long long*>(static_cast<char*>(w->ews) + head_c);
-        words = reinterpret_cast<uint64_t*>(static_cast<char*>(w->ews) + head_c + map_c);
+        const EdgeLayout L(w->ecap_edges, cap);
+        char* ews = static_cast<char*>(w->ews);
+        plan = reinterpret_cast<double*>(ews);
+        cnt = reinterpret_cast<unsigned long long*>(ews + L.cnt);
+        offs = reinterpret_cast<unsigned long long*>(ews + L.offs);
+        ovf = reinterpret_cast<uint8_t*>(ews + L.ovf);
+        map = reinterpret_cast<unsigned long long*>(ews + L.map);
+        words = reinterpret_cast<uint64_t*>(ews + L.words);
         hipLaunchKernelGGL(k_edge_plan, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution,
                            max_distance, mode, plan, cnt, end, n_samples);
         NBK_HIP(hipGetLastError());
@@ -4915,7 +4911,7 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
     EdgeSrc es{starts, goals, plan, map, offs + E, 0, nullptr};
     if (capturing) { w->ready = false; w->captured = true; }
     const bool pipe = pipelined(m, (int64_t)cap) && !capturing;
-    if (pipe) { const int32_t rp = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, (int64_t)cap, st); if (rp != NBK_OK) return rp; }
+    if (pipe) { const int32_t rp = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, (int64_t)cap); if (rp != NBK_OK) return rp; }
     const int32_t rc = launch_two_kernel(m, pc, es, nullptr, (int64_t)cap, threshold, words, nullptr, w->ws, st, capturing ? nullptr : w, pipe);
     if (rc != NBK_OK) return rc;
     hipLaunchKernelGGL(k_edge_reduce, dim3((unsigned)E), dim3(WAVE), 0, st, offs, E, words, ovf, valid, w->stats_dev);
@@ -4996,6 +4992,10 @@ int32_t nbk_selftest_math(const double* a, const double* b, int64_t n, double* s
     return NBK_OK;
 }
 
+// the device staging of the host-memory entry points: freed on every return path
+struct HipFree { void operator()(void* p) const { (void)hipFree(p); } };
+using DevBuf = std::unique_ptr<void, HipFree>;
+
 int32_t nbk_fk_batch_host(const nbk_model* m, const double* q, int64_t B, const int32_t* path, int32_t path_len,
                           const double* local, double* T_out) {
     if (m == nullptr || B < 0 || (B > 0 && (q == nullptr || T_out == nullptr))) return NBK_ERR_INVALID;
@@ -5003,33 +5003,32 @@ int32_t nbk_fk_batch_host(const nbk_model* m, const double* q, int64_t B, const 
     if (B == 0) return NBK_OK;
     double *dq = nullptr, *dT = nullptr;
     NBK_HIP(hipMalloc((void**)&dq, sizeof(double) * B * m->n_q));
+    const DevBuf own_q(dq);
     hipError_t e = hipMalloc((void**)&dT, sizeof(double) * B * 16);
-    if (e != hipSuccess) { (void)hipFree(dq); return hip_fail(e, "hipMalloc"); }
-    int st = NBK_OK;
-    e = hipMemcpy(dq, q, sizeof(double) * B * m->n_q, hipMemcpyHostToDevice);
-    if (e != hipSuccess) st = hip_fail(e, "hipMemcpy H2D");
-    if (st == NBK_OK) st = nbk_fk_batch(m, dq, B, path, path_len, local, nullptr, dT, nullptr);
-    if (st == NBK_OK) { e = hipMemcpy(T_out, dT, sizeof(double) * B * 16, hipMemcpyDeviceToHost); if (e != hipSuccess) st = hip_fail(e, "hipMemcpy D2H"); }
-    (void)hipFree(dq); (void)hipFree(dT);
-    return st;
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+    const DevBuf own_T(dT);
+    if ((e = hipMemcpy(dq, q, sizeof(double) * B * m->n_q, hipMemcpyHostToDevice)) != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
+    const int32_t st = nbk_fk_batch(m, dq, B, path, path_len, local, nullptr, dT, nullptr);
+    if (st != NBK_OK) return st;
+    if ((e = hipMemcpy(T_out, dT, sizeof(double) * B * 16, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
+    return NBK_OK;
 }
 
 int32_t nbk_validity_batch_host(const nbk_model* m, const double* q, int64_t B, double threshold, uint8_t* mask_bytes) {
     if (m == nullptr || B < 0 || (B > 0 && (q == nullptr || mask_bytes == nullptr))) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     if (B == 0) return NBK_OK;
-    double* dq = nullptr;
-    uint8_t* dm = nullptr;
+    double* dq = nullptr; uint8_t* dm = nullptr;
     NBK_HIP(hipMalloc((void**)&dq, sizeof(double) * B * m->n_q));
+    const DevBuf own_q(dq);
     hipError_t e = hipMalloc((void**)&dm, (size_t)B);
-    if (e != hipSuccess) { (void)hipFree(dq); return hip_fail(e, "hipMalloc"); }
-    int st = NBK_OK;
-    e = hipMemcpy(dq, q, sizeof(double) * B * m->n_q, hipMemcpyHostToDevice);
-    if (e != hipSuccess) st = hip_fail(e, "hipMemcpy H2D");
-    if (st == NBK_OK) st = nbk_validity_batch(m, dq, B, threshold, nullptr, dm, nullptr);
-    if (st == NBK_OK) { e = hipMemcpy(mask_bytes, dm, (size_t)B, hipMemcpyDeviceToHost); if (e != hipSuccess) st = hip_fail(e, "hipMemcpy D2H"); }
-    (void)hipFree(dq); (void)hipFree(dm);
-    return st;
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+    const DevBuf own_m(dm);
+    if ((e = hipMemcpy(dq, q, sizeof(double) * B * m->n_q, hipMemcpyHostToDevice)) != hipSuccess) return hip_fail(e, "hipMemcpy H2D");
+    const int32_t st = nbk_validity_batch(m, dq, B, threshold, nullptr, dm, nullptr);
+    if (st != NBK_OK) return st;
+    if ((e = hipMemcpy(mask_bytes, dm, (size_t)B, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
+    return NBK_OK;
 }
 
 }  // extern "C"

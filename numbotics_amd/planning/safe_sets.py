@@ -44,11 +44,10 @@ def counter_example_bisection(arm, centre, points, num_bisections: int = 15, col
     return hi
 
 
-class _BisectionGraph:
-    """One captured bisection round over persistent buffers (lo, hi, mid, mask) on a private stream, for one (scene, M, tolerance):
-    capturing costs more than a whole 15-round search, so the graph is kept on the Arm and replayed by later calls."""
+class _Bisection:
+    """Persistent buffers (lo, hi, mid, mask) of a bisection over M points; ``round()`` runs one round on the current stream."""
 
-    def __init__(self, dev, M, nq, tol, device):
+    def __init__(self, dev, M, nq, tol, device, ws_bytes=0):
         import torch
         from numbotics_amd import _lib
         self.dev, self.M, self.tol = dev, M, float(tol)
@@ -56,19 +55,31 @@ class _BisectionGraph:
         self.hi = torch.empty_like(self.lo)
         self.mid = torch.empty_like(self.lo)
         self.mask = torch.empty((M,), dtype=torch.uint8, device=device)
-        self.stream = torch.cuda.Stream()
+        self.ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device) if ws_bytes > 0 else None
         self._check = _lib.check
-        self.graph = None
 
     def round(self):
         import torch
         torch.add(self.lo, self.hi, out=self.mid)
         self.mid.div_(2.0)                                # (lo + hi) / 2.0, as upstream
-        self._check(self.dev._lib.nbk_validity_batch(self.dev._h, self.mid.data_ptr(), self.M, self.tol, None, self.mask.data_ptr(),
-                                                     self.dev._stream()), "nbk_validity_batch")
+        d = self.dev
+        ws = () if self.ws is None else (self.ws.data_ptr(), self.ws.numel())
+        fn = d._lib.nbk_validity_batch_ws if ws else d._lib.nbk_validity_batch
+        self._check(fn(d._h, self.mid.data_ptr(), self.M, self.tol, None, self.mask.data_ptr(), *ws, d._stream()), fn.__name__)
         hit = self.mask.bool().unsqueeze(1)
         torch.where(hit, self.mid, self.hi, out=self.hi)
         torch.where(hit, self.lo, self.mid, out=self.lo)
+
+
+class _BisectionGraph(_Bisection):
+    """One captured round on a private stream, for one (scene, M, tolerance), kept on the Arm: capturing costs more than a whole
+    15-round search.  Its validity call uses a workspace of its own, never the library's per-stream scratch, which a later call on
+    the same (pooled) stream may regrow; size 0 = the fused kernel, which keeps nothing between calls."""
+
+    def __init__(self, dev, M, nq, tol, device):
+        import torch
+        super().__init__(dev, M, nq, tol, device, dev.validity_workspace_bytes(M))
+        self.stream, self.graph = torch.cuda.Stream(), None
 
     def run(self, centre, pts, rounds):
         import torch
@@ -77,7 +88,7 @@ class _BisectionGraph:
             self.lo.copy_(centre.expand_as(self.lo))
             self.hi.copy_(pts)
             if self.graph is None:
-                self.round()                              # allocates the stream's scratch: a capture cannot
+                self.round()                              # one round outside the capture: lazy initialisation happens here
                 rounds -= 1
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=self.stream):     # records one round, executes nothing
@@ -106,7 +117,7 @@ def _bisection_on_device(arm, centre, points, num_bisections, tol, graph):
                 cache.clear()
             cache[key] = _BisectionGraph(dev, M, nq, tol, pts.device)
         return cache[key].run(c, pts, num_bisections)
-    state = _BisectionGraph(dev, M, nq, tol, pts.device)
+    state = _Bisection(dev, M, nq, tol, pts.device)
     state.lo.copy_(c.expand(M, nq))
     state.hi.copy_(pts)
     for _ in range(num_bisections):

@@ -473,6 +473,54 @@ def test_iris_inner_steps(fresh_world, torch_cuda):
     assert np.array_equal(hi_g.cpu().numpy(), hi)
 
 
+def test_bisection_graphs_own_their_workspace(fresh_world, torch_cuda, monkeypatch):
+    """Cached bisection graphs capture their validity call on a workspace of their own: two graphs of different M on one Arm,
+    direct calls on a larger batch (which regrow the library's per-stream scratch) on the current and on a fresh stream, then
+    a replay of the small graph -- every result bit-equal to the NumPy-input bisection.  graph=False creates no stream."""
+    from numbotics_amd.planning import collision_mask, counter_example_bisection
+    torch = torch_cuda
+    arm, chain, obs = build_scene("c2")
+    _, dev = arm._scene_device()
+    seed_q = np.zeros(7)
+    pts = sample_q(chain, 30000, seed=37)
+    mask = collision_mask(arm, pts, 1e-6)
+    col = pts[mask]
+    assert col.shape[0] > 2000
+    ref = {M: counter_example_bisection(arm, seed_q, col[:M], 15, 1e-6) for M in (400, 2000)}
+
+    def on_device(M, graph=True):
+        return counter_example_bisection(arm, seed_q, torch.from_numpy(col[:M]).cuda(), 15, 1e-6, graph=graph).cpu().numpy()
+
+    assert np.array_equal(on_device(400), ref[400])
+    assert np.array_equal(on_device(2000), ref[2000])
+    graphs = dict(arm._bisection_graphs)
+    assert sorted(g.M for g in graphs.values()) == [400, 2000]
+    for g in graphs.values():
+        need = dev.validity_workspace_bytes(g.M)
+        assert need > 0 and g.ws is not None and g.ws.numel() * g.ws.element_size() >= need, (g.M, need)
+    qd = torch.from_numpy(pts).cuda()                  # larger than either M
+    assert np.array_equal(arm.in_collision(qd, 1e-6).cpu().numpy(), mask)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        got = arm.in_collision(qd, 1e-6)
+    side.synchronize()
+    assert np.array_equal(got.cpu().numpy(), mask)
+    assert np.array_equal(on_device(400), ref[400])    # replays the small graph captured before the direct calls
+    assert arm._bisection_graphs == graphs
+
+    real_stream = torch.cuda.Stream
+
+    def no_new_stream(*args, **kwargs):                # torch.cuda.current_stream() wraps an existing stream by its id
+        if args or "stream_id" not in kwargs:
+            raise AssertionError("graph=False created a stream")
+        return real_stream(*args, **kwargs)
+
+    with monkeypatch.context() as mp:
+        mp.setattr(torch.cuda, "Stream", no_new_stream)
+        hi = on_device(400, graph=False)
+    assert np.array_equal(hi, ref[400])
+
+
 def _tree_scene():
     from numbotics_amd.physics import GraphChain, Cube, Sphere, Capsule
     from numbotics_amd.robots import Arm
