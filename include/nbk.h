@@ -221,6 +221,22 @@ int32_t nbk_proximity_jacobian_batch(const nbk_model *m, const double *q, int64_
                                      double *witness, double *jrows, void *stream);
 
 /*
+ * Proximity records of chosen (configuration, pair) items: the entries of nbk_proximity_jacobian_batch one asks for, bit for bit.
+ * IRIS' counter-example search asks about one body pair per evaluation -- distance_to(x, link, obj)[0].distance and
+ * jacobian_proximity(x, link, obj) for SLSQP, closest_to(q) and its pair for the greedy search (numbotics/planning/safe_sets.py:86-152,
+ * numbotics/robots/arm.py:607-632) -- where the all-pairs entries above compute every allowed pair of every configuration.
+ *   q (device) [B][n_q]; items (device) [N][2] int32 = (configuration b, user pair index p);
+ *   dist (device) [N]; witness (device, optional) [N][9]; jrows (device, optional) [N][n_q] -- the fields of
+ *   nbk_proximity_jacobian_batch at [b][p].
+ * Items outside [0,B) x [0,P) get NaN everywhere (q and the pair tables are not read for them).  One item per lane: items that
+ * name the same pair in runs of 64 (pair-major order) are the fast case for hull shapes.  Unlike the all-pairs entries this one
+ * parks nothing in LDS and serves every descriptor (robots with 30+ primitives included).
+ * Asynchronous: no allocation, no host synchronisation.
+ */
+int32_t nbk_pair_records_items(const nbk_model *m, const double *q, int64_t B, const int32_t *items, int64_t N,
+                               double *dist, double *witness, double *jrows, void *stream);
+
+/*
  * Batched DiscreteConnector.connect / steer (numbotics/planning/sampling_based/connectors.py:57-100)
  * with the default linear trajectory (numbotics/planning/trajectories.py:6-22) and
  * validity_checker = not in_collision(q, threshold).

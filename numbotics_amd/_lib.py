@@ -20,7 +20,7 @@ SYMBOLS = [
     "nbk_model_create", "nbk_model_destroy", "nbk_model_num_pairs",
     "nbk_fk_batch", "nbk_frameset_create", "nbk_frameset_destroy", "nbk_fk_frames_batch", "nbk_jacobian_batch", "nbk_ik_batch", "nbk_validity_batch", "nbk_validity_workspace_bytes",
     "nbk_validity_batch_ws", "nbk_closest_batch",
-    "nbk_pair_distances_batch", "nbk_proximity_jacobian_batch", "nbk_edge_validity_batch", "nbk_selftest_math",
+    "nbk_pair_distances_batch", "nbk_proximity_jacobian_batch", "nbk_pair_records_items", "nbk_edge_validity_batch", "nbk_selftest_math",
     "nbk_fk_batch_host", "nbk_validity_batch_host", "nbk_knn_prefix",
     "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host",
 ]
@@ -89,6 +89,7 @@ def load():
     lib.nbk_closest_batch.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.nbk_pair_distances_batch.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.nbk_proximity_jacobian_batch.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.nbk_pair_records_items.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.nbk_edge_validity_batch.argtypes = [vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, vp, vp, vp]
     lib.nbk_selftest_math.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     lib.nbk_knn_prefix.argtypes = [vp, i32, i32, i32, vp, vp]

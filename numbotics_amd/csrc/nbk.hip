@@ -57,6 +57,7 @@ struct DevModel {
     const int* pair_a;            // [P] index into rs_* (frame order)
     const int* pair_b;            // [P] < S robot (frame order), else S + world
     const int* pair_user;         // [P] index of this pair in the caller's pair list
+    const int* pair_dev;          // [P] the inverse: device index of the caller's pair p (k_pair_items)
     // validity tables: pairs sorted by class (0 plane, 1 closed form, 2 GJK); shape refs: >= 0 robot shape
     // (frame order), < 0 world shape ~ref
     const int* vp_tab;            // [P][4] refA, refB (user order), class, pad
@@ -990,6 +991,17 @@ __global__ __launch_bounds__(64) void k_ik(DevModel m, PathArg path, IkArg arg, 
 }
 
 // ---- collision: sweep the tree, park robot cores in LDS ---------------------------------------------
+// world axis w_k = R_k a_k and origin o_k of joint k, from the joint's frame T_k, into rows[0..5] (stride WAVE): what prox_row reads.
+// sweep_and_park and the FK replay of k_pair_items both write through here, so their rows are the same bits.
+NBK_DEV void joint_frame_rows(const DevModel& m, int k, const Xf& T, double* rows) {
+    const double* a = m.joint_axis + 3 * k;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        rows[r * WAVE] = NBK_FMA(T.R[3 * r + 2], a[2], NBK_FMA(T.R[3 * r + 1], a[1], T.R[3 * r] * a[0]));
+        rows[(3 + r) * WAVE] = T.t[r];
+    }
+}
+
 // LDS rows of 64 doubles: [n_q q rows][shape_rows][frame_slots * 12]
 // lds_jz (optional): [J][6] rows -- world axis w_k = R_k a_k and origin o_k of every joint, for Jacobian rows
 NBK_DEV void sweep_and_park(const DevModel& m, double* lds_q, double* lds_s, double* lds_fr, int lane, double* lds_jz = nullptr) {
@@ -1010,14 +1022,7 @@ NBK_DEV void sweep_and_park(const DevModel& m, double* lds_q, double* lds_s, dou
             }
             const double qk = lds_q[m.joint_qidx[k] * WAVE + lane];
             joint_apply(m, k, P, qk, T);
-            if (lds_jz != nullptr) {
-                const double* a = m.joint_axis + 3 * k;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    lds_jz[(6 * k + r) * WAVE + lane] = NBK_FMA(T.R[3 * r + 2], a[2], NBK_FMA(T.R[3 * r + 1], a[1], T.R[3 * r] * a[0]));
-                    lds_jz[(6 * k + 3 + r) * WAVE + lane] = T.t[r];
-                }
-            }
+            if (lds_jz != nullptr) joint_frame_rows(m, k, T, lds_jz + 6 * k * WAVE + lane);
             const int sv = m.joint_save[k];
             if (sv >= 0) {
 #pragma unroll
@@ -3017,6 +3022,28 @@ NBK_DEV void prox_row(const DevModel& m, const double* lds_jz, int col, int p, c
     }
 }
 
+// the EPA pass of an item that cores_distance<WIT, true> answered with the axis-family depth `fam` (a cylinder or hull core
+// overlapping): where EPA finds a smaller depth, d (and wit) become the record of cores_distance's overlap branch with EPA's depth
+// and direction -- exactly what overlap_depth_exact would have given inline.  Returns whether it replaced them.
+template <bool WIT>
+NBK_DEV bool epa_refine(const Core& A, const Core& Bc, double fam, double& d, double* wit) {
+    double o[4];
+    if (!(epa_depth_copy(A, Bc, o, 0, 0.0) == 1 && o[0] < fam)) return false;
+    const double n[3] = {o[1], o[2], o[3]};
+    const double dc = -o[0];
+    d = (dc - A.margin) - Bc.margin;
+    if constexpr (WIT) {
+        const double neg[3] = {-n[0], -n[1], -n[2]};
+        double pa[3], pb[3];
+        core_support(A, neg, pa);
+        axpy3(dc, n, pa, pb);
+        axpy3(-A.margin, n, pa, wit);
+        axpy3(Bc.margin, n, pb, wit + 3);
+        copy3(n, wit + 6);
+    }
+    return true;
+}
+
 constexpr int EPAQ_CAP = 128;                  // (lane, pair) items waiting for their EPA pass, per wave
 
 // MODE >= 1: TWO waves per workgroup share the parked cores of the block's 64 configurations (lane = configuration in both) and take
@@ -3064,22 +3091,12 @@ __global__ __launch_bounds__(MODE == 0 ? 64 : 128) void k_distances(DevModel m, 
                 const int a = m.pair_a[p], bb = m.pair_b[p];
                 load_core_any(m, lds_s, a, src, A);
                 load_core_any(m, lds_s, bb < m.n_rshapes ? bb : ~(bb - m.n_rshapes), src, Bc);
-                double o[4];
-                if (epa_depth_copy(A, Bc, o, 0, 0.0) == 1 && o[0] < fam) {
-                    // the record of cores_distance's overlap branch, with EPA's depth and direction
-                    const double n[3] = {o[1], o[2], o[3]};
-                    const double dc = -o[0];
+                double d, wit[9];
+                if (epa_refine<(MODE >= 2)>(A, Bc, fam, d, wit)) {
                     const int64_t bs = base + src;
                     const int64_t oo = bs * m.n_pairs + m.pair_user[p];
-                    out_d[oo] = (dc - A.margin) - Bc.margin;
+                    out_d[oo] = d;
                     if constexpr (MODE >= 2) {
-                        const double neg[3] = {-n[0], -n[1], -n[2]};
-                        double pa[3], pb[3], wit[9];
-                        core_support(A, neg, pa);
-                        axpy3(dc, n, pa, pb);
-                        axpy3(-A.margin, n, pa, wit);
-                        axpy3(Bc.margin, n, pb, wit + 3);
-                        copy3(n, wit + 6);
 #pragma unroll
                         for (int e = 0; e < 9; ++e) out_w[oo * 9 + e] = wit[e];
                         if constexpr (MODE == 3) prox_row(m, lds_jz, src, p, wit, out_j + oo * m.n_q);
@@ -3142,6 +3159,95 @@ __global__ __launch_bounds__(MODE == 0 ? 64 : 128) void k_distances(DevModel m, 
             epaq_drain();
         }
     }
+}
+
+// ---- proximity records of chosen (configuration, pair) items ----------------------------------------------------------------
+// ONE ITEM PER LANE over a dense item array (nbk_pair_records_items): the entries of k_distances<3>'s output one asks for, bit for
+// bit, without the sweep of the whole tree and the loop over every pair.  Per lane: read (b, p) and map the caller's pair index to
+// the device order (pair_dev); replay FK of the item's two shapes along their joint masks, as k_narrow does (common ancestors: the
+// same frame, applied once); build the two cores; cores_distance with the EPA depth deferred, then the EPA pass inline on the lanes
+// that need it (epa_refine: the replacement rule of k_distances' queue drain).  A wave holds 64 items, so a per-wave queue would
+// hold the same lanes the inline pass runs on.  The gradient row is prox_row over the axis / origin rows that the replay writes
+// into LDS through joint_frame_rows, the routine sweep_and_park uses -- same frames, same bits.  Nothing is parked, so every
+// descriptor is served, whatever its LDS footprint in the all-pairs kernels.
+// Items outside [0, B) x [0, P) read neither q nor the pair tables and write NaN to every field.
+// LDS: [64][n_q] q rows (the lane's row, staged eight loads at a time) | [J][6][64] joint rows (only when rows are asked for).
+__global__ __launch_bounds__(64) void k_pair_items(DevModel m, const double* __restrict__ q, int64_t B, const int32_t* __restrict__ items,
+                                                   int64_t N, double* __restrict__ out_d, double* __restrict__ out_w,
+                                                   double* __restrict__ out_j) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < N;
+    long long b = -1;
+    int pu = -1;
+    if (live) { b = items[2 * i]; pu = items[2 * i + 1]; }
+    const bool ok = live && b >= 0 && b < B && pu >= 0 && pu < m.n_pairs;
+    const int p = ok ? m.pair_dev[pu] : 0;
+    const int sa = ok ? m.pair_a[p] : 0, sb = ok ? m.pair_b[p] : 0;
+    const int ra = sa, rb = sb < m.n_rshapes ? sb : ~(sb - m.n_rshapes);
+    const unsigned ma = ok ? m.rs_mask[sa] : 0u, mb = (ok && rb >= 0) ? m.rs_mask[rb] : 0u;
+    double* myq = lds + lane * m.n_q;
+    double* lds_jz = out_j != nullptr ? lds + WAVE * m.n_q : nullptr;
+    if (ok) {
+        const double* qrow = q + b * m.n_q;
+        const int nq1 = m.n_q - 1;
+        for (int j0 = 0; j0 < m.n_q; j0 += 8) {
+            double qv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int j = (j0 + u) < nq1 ? (j0 + u) : nq1; qv[u] = qrow[j]; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (j0 + u <= nq1) myq[j0 + u] = qv[u];
+        }
+    }
+    Xf TA, TB;
+    xf_from12(m.base_pose, TA);
+    TB = TA;
+    for (int k = 0; k < m.n_joints; ++k) {
+        const bool in_a = (ma >> k) & 1u, in_b = (mb >> k) & 1u;
+        if (__builtin_amdgcn_ballot_w64(in_a || in_b) == 0ull) continue;
+        if (in_a || in_b) {
+            const double qk = myq[m.joint_qidx[k]];
+            Xf nxt;
+            joint_apply(m, k, in_a ? TA : TB, qk, nxt);     // common ancestors: TA == TB bit for bit
+            if (lds_jz != nullptr) joint_frame_rows(m, k, nxt, lds_jz + 6 * k * WAVE + lane);
+            if (in_a) TA = nxt;
+            if (in_b) TB = nxt;
+        }
+    }
+    // the hull support's scalar-cache path (rad < 0) needs every active lane to hold the same hull: only for pair-uniform waves
+    const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
+    const int p0 = __shfl(p, okm != 0ull ? __builtin_ctzll(okm) : 0);
+    const bool uniform = __builtin_amdgcn_ballot_w64(ok && p != p0) == 0ull;
+    if (!ok) {
+        if (live) {
+            const double nan = __builtin_nan("");
+            out_d[i] = nan;
+            if (out_w != nullptr) for (int e = 0; e < 9; ++e) out_w[i * 9 + e] = nan;
+            if (out_j != nullptr) for (int c = 0; c < m.n_q; ++c) out_j[i * m.n_q + c] = nan;
+        }
+        return;
+    }
+    Core A, Bc;
+    A.kind = K_POINT; Bc.kind = K_POINT;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { A.c[e] = 0.0; Bc.c[e] = 1.0; A.h[e] = 0.0; Bc.h[e] = 0.0; A.ax[0][e] = A.ax[1][e] = A.ax[2][e] = 0.0; Bc.ax[0][e] = Bc.ax[1][e] = Bc.ax[2][e] = 0.0; }
+    A.rad = Bc.rad = A.margin = Bc.margin = A.rho = Bc.rho = 0.0;
+    build_core(m, ra, TA, A);
+    build_core(m, rb, TB, Bc);
+    if (uniform && A.kind == K_HULL) A.rad = -1.0;
+    if (uniform && Bc.kind == K_HULL) Bc.rad = -1.0;
+    double wit[9];
+    double fam = -1.0;
+    double d = cores_distance<true, true>(A, Bc, wit, &fam);
+    if (fam >= 0.0) epa_refine<true>(A, Bc, fam, d, wit);
+    out_d[i] = d;
+    if (out_w != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) out_w[i * 9 + e] = wit[e];
+    }
+    if (out_j != nullptr) prox_row(m, lds_jz, lane, p, wit, out_j + i * m.n_q);
 }
 
 // ---- closest pair with branch-and-bound ----------------------------------------------------------------------
@@ -3905,6 +4011,9 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     o.pa = B.add(pa.data(), sizeof(int) * P);
     o.pb = B.add(pb.data(), sizeof(int) * P);
     o.pu = B.add(pu.data(), sizeof(int) * P);
+    std::vector<int> pdev((size_t)(P > 0 ? P : 1), 0);
+    for (int p = 0; p < P; ++p) pdev[pu[p]] = p;
+    const size_t o_pd = B.add(pdev.data(), sizeof(int) * P);
     o.vt = B.add(vp_tab.data(), sizeof(int) * 4 * P);
     o.vc = B.add(vp_canon.data(), sizeof(int) * 2 * P);
     o.vk = B.add(vp_cst.data(), sizeof(double) * 4 * P);
@@ -4109,6 +4218,7 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     m.pair_a = reinterpret_cast<const int*>(base + o.pa);
     m.pair_b = reinterpret_cast<const int*>(base + o.pb);
     m.pair_user = reinterpret_cast<const int*>(base + o.pu);
+    m.pair_dev = reinterpret_cast<const int*>(base + o_pd);
     m.vp_tab = reinterpret_cast<const int*>(base + o.vt);
     m.vp_canon = reinterpret_cast<const int*>(base + o.vc);
     m.vp_cst = reinterpret_cast<const double*>(base + o.vk);
@@ -4795,6 +4905,22 @@ int32_t nbk_proximity_jacobian_batch(const nbk_model* m, const double* q, int64_
     if (proximity_lds(m) > LDS_MAX) return NBK_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_distances<3>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), proximity_lds(m), (hipStream_t)stream, m->d, q, B, dist, (int32_t*)nullptr,
                        witness, jrows);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+static inline size_t pair_items_lds(const nbk_model* m, bool rows) {
+    return sizeof(double) * WAVE * ((size_t)(m->n_q > 0 ? m->n_q : 1) + (rows ? 6 * (size_t)m->n_joints : 0));
+}
+
+int32_t nbk_pair_records_items(const nbk_model* m, const double* q, int64_t B, const int32_t* items, int64_t N, double* dist,
+                               double* witness, double* jrows, void* stream) {
+    if (m == nullptr || B < 0 || N < 0 || (N > 0 && (q == nullptr || items == nullptr || dist == nullptr))) return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    if (N == 0) return NBK_OK;
+    if ((N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_pair_items, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), pair_items_lds(m, jrows != nullptr),
+                       (hipStream_t)stream, m->d, q, B, items, N, dist, witness, jrows);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

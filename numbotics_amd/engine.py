@@ -290,6 +290,48 @@ class DeviceModel:
                                                           j.data_ptr(), self._stream()), "nbk_proximity_jacobian_batch")
         return qs.out(d), qs.out(w), qs.out(j)
 
+    def _items(self, items, device):
+        torch = _torch()
+        if torch.is_tensor(items):
+            t = items.to(device=device, dtype=torch.int32)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(items, dtype=np.int32))).to(device)
+        return t.contiguous().reshape(-1, 2)
+
+    def _launch_records(self, qt, B, it, witness, jacobian):
+        torch = _torch()
+        N = int(it.shape[0])
+        d = torch.empty((N,), dtype=torch.float64, device=qt.device)
+        w = torch.empty((N, 9), dtype=torch.float64, device=qt.device) if witness else None
+        j = torch.empty((N, self.n_q), dtype=torch.float64, device=qt.device) if jacobian else None
+        _lib.check(self._lib.nbk_pair_records_items(self._h, qt.data_ptr(), B, it.data_ptr(), N, d.data_ptr(),
+                                                    None if w is None else w.data_ptr(), None if j is None else j.data_ptr(),
+                                                    self._stream()), "nbk_pair_records_items")
+        return d, w, j
+
+    def pair_records(self, q, items, witness=True, jacobian=True):
+        """Records of chosen (configuration, pair) items: ``items`` (N, 2) int = (row of q, user pair index) ->
+        dist (N,), witness (N, 9) or None, rows (N, n_q) or None -- the entries of ``proximity_jacobian(q)`` at [b, p], bit for
+        bit; NaN for items outside [0, B) x [0, P)."""
+        _require_gpu()
+        qs = _Staged(q, self.n_q)
+        it = self._items(items, qs.device)
+        d, w, j = self._launch_records(qs.t, qs.B, it, witness, jacobian)
+        return qs.out(d), None if w is None else qs.out(w), None if j is None else qs.out(j)
+
+    def closest_records(self, q):
+        """``closest`` followed by the records of each configuration's closest pair, with no host round trip in between:
+        dist (B,), pair (B,) int32, witness (B, 9), rows (B, n_q)."""
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        d = torch.empty((qs.B,), dtype=torch.float64, device=qs.device)
+        idx = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
+        _lib.check(self._lib.nbk_closest_batch(self._h, qs.t.data_ptr(), qs.B, d.data_ptr(), idx.data_ptr(),
+                                               self._stream()), "nbk_closest_batch")
+        it = torch.stack((torch.arange(qs.B, dtype=torch.int32, device=qs.device), idx), dim=1).contiguous()
+        _, w, j = self._launch_records(qs.t, qs.B, it, True, True)
+        return qs.out(d), qs.out(idx), qs.out(w), qs.out(j)
+
     def edge_validity(self, starts, goals, resolution, max_distance, mode="connect", threshold=0.0, dist=None):
         torch = _require_gpu()
         s = _Staged(starts, self.n_q)

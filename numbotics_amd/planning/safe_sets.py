@@ -11,7 +11,8 @@ cvxpy/MOSEK ellipsoid, SLSQP) are out of scope.
   instead of ``M * num_bisections`` single-configuration PyBullet queries.
 * ``distance_and_gradient(arm, points, link, obj)`` = the constraint value and Jacobian that
   ``counter_ex_search_nlp`` hands to SLSQP (safe_sets.py:86-121: ``distance_to(x, link, obj)[0].distance`` and
-  ``jacobian_proximity(x, link=link, obj=obj)``), for M points in one launch.
+  ``jacobian_proximity(x, link=link, obj=obj)``), for M points in one launch that computes the body pair's primitive pairs
+  only (``Arm.pair_proximity_jacobians``).
 """
 import numpy as np
 
@@ -135,8 +136,8 @@ def distance_and_gradient(arm, points, link, obj):
         raise ValueError(f"Collision pair ({link.name}, {obj.name}) not valid")
     sel = arm._pair_selection(sm, obj, link)
     points = np.asarray(points, dtype=np.float64).reshape(-1, arm.dof)
-    dist, _, rows = arm.proximity_jacobians(points)
-    dist, rows = np.asarray(dist)[:, sel], np.asarray(rows)[:, sel]
+    _, dev = arm._scene_device()
+    dist, _, rows = arm._subset_records(dev, points, np.asarray(sel, dtype=np.int64), witness=False)   # the body pair's columns only
     k = np.argmin(dist, axis=1)
     i = np.arange(points.shape[0])
     return dist[i, k], rows[i, k]

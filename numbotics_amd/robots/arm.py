@@ -420,13 +420,14 @@ class Arm(Robot):
         return ok, q.reshape(*batch_dims, self.dof)
 
     # ---- collision queries ------------------------------------------------------------------------------
-    def _proximities(self, q, sm, dist, wit):
+    def _proximities(self, sm, pairs, dist, wit):
+        """Proximity records of the given pair indices from their (S,) distances and (S, 9) witnesses."""
         out = []
-        for p in range(sm.n_pairs):
+        for i, p in enumerate(pairs):
             subj, targ = sm.pair_members(p)
-            out.append(Proximity(subject=subj, target=targ, position_on_subject=wit[p, 0:3].copy(),
-                                 position_on_target=wit[p, 3:6].copy(), normal_target_to_subject=wit[p, 6:9].copy(),
-                                 distance=float(dist[p])))
+            out.append(Proximity(subject=subj, target=targ, position_on_subject=wit[i, 0:3].copy(),
+                                 position_on_target=wit[i, 3:6].copy(), normal_target_to_subject=wit[i, 6:9].copy(),
+                                 distance=float(dist[i])))
         return out
 
     def collisions(self, q):
@@ -438,7 +439,7 @@ class Arm(Robot):
             return []
         qn = q.detach().cpu().numpy() if _is_tensor(q) else np.asarray(q, dtype=np.float64)
         dist, wit = dev.pair_distances(qn.reshape(1, -1), witness=True)
-        return self._proximities(qn, sm, dist[0], wit[0])
+        return self._proximities(sm, range(sm.n_pairs), dist[0], wit[0])
 
     def self_collisions(self, q):
         if tuple(q.shape) != (self.dof,):
@@ -501,11 +502,19 @@ class Arm(Robot):
         return sel
 
     def distance_to(self, q, obj, link=None):
+        """As upstream: the Proximity records of ``collisions(q)`` that involve ``obj`` (and ``link``) -- computed for those
+        pairs only (the subset path, bit-identical to the all-pairs records)."""
         if link is not None and not self._has(self.collision_pairs(), link, obj):
             raise ValueError(f"Collision pair ({link.name}, {obj.name}) not valid")
-        sm, _ = self._scene_device()
-        prox = self.collisions(q)
-        return [prox[p] for p in self._pair_selection(sm, obj, link)]
+        if tuple(q.shape) != (self.dof,):
+            raise ValueError(f"q must be a 1D array with {self.dof} elements")
+        sm, dev = self._scene_device()
+        sel = self._pair_selection(sm, obj, link)
+        if not sel:
+            return []
+        qn = q.detach().cpu().numpy() if _is_tensor(q) else np.asarray(q, dtype=np.float64)
+        dist, wit, _ = self._subset_records(dev, qn.reshape(1, -1), np.asarray(sel, dtype=np.int64), jacobian=False)
+        return self._proximities(sm, sel, dist[0], wit[0])
 
     def proximity_jacobians(self, q):
         """Batched ``collisions`` + ``jacobian_proximity`` over every allowed primitive pair (additive):
@@ -514,6 +523,98 @@ class Arm(Robot):
         (arm.py:620-632), one launch."""
         sm, dev = self._scene_device()
         return dev.proximity_jacobian(q.reshape(-1, self.dof))
+
+    # ---- records of chosen pairs (additive) ----------------------------------------------------------------
+    # The same records and rows as proximity_jacobians, bit for bit, computed for the (configuration, pair) items asked for
+    # only (nbk_pair_records_items).  Arguments are checked against scene_model() before anything touches the device.
+    def _check_q(self, q):
+        if q.ndim < 1 or q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements in its last dimension")
+
+    @staticmethod
+    def _check_pair_values(a, n_pairs, what):
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= n_pairs):
+            raise ValueError(f"{what}: pair index out of range [0, {n_pairs})")
+
+    def _pair_indices(self, sm, pairs):
+        a = pairs.detach().cpu().numpy() if _is_tensor(pairs) else np.asarray(pairs)
+        if a.ndim != 1:
+            raise ValueError("pairs must be a 1-D sequence of pair indices")
+        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("pairs must hold integer pair indices")
+        self._check_pair_values(a, sm.n_pairs, "pairs")
+        return a.astype(np.int64)
+
+    def _subset_records(self, dev, q, sel, witness=True, jacobian=True):
+        """Records of the pairs ``sel`` for every row of q: (B, S), (B, S, 9), (B, S, dof).  Items go pair-major, so that each
+        wave of 64 items holds one pair."""
+        q2 = q.reshape(-1, self.dof)
+        B, S = int(q2.shape[0]), int(sel.size)
+        if _is_tensor(q2):
+            import torch
+            dv = q2.device if q2.is_cuda else torch.device("cuda")
+            b = torch.arange(B, dtype=torch.int32, device=dv).repeat(S)
+            p = torch.from_numpy(sel.astype(np.int32)).to(dv).repeat_interleave(B)
+            items = torch.stack((b, p), dim=1)
+        else:
+            items = np.stack((np.tile(np.arange(B, dtype=np.int32), S), np.repeat(sel.astype(np.int32), B)), axis=1)
+        d, w, j = dev.pair_records(q2, items, witness=witness, jacobian=jacobian)
+
+        def batch_major(x, tail):
+            if x is None:
+                return None
+            x = x.reshape((S, B) + tail)
+            perm = (1, 0) + tuple(range(2, 2 + len(tail)))
+            return x.permute(*perm).contiguous() if _is_tensor(x) else np.ascontiguousarray(x.transpose(perm))
+        return batch_major(d, ()), batch_major(w, (9,)), batch_major(j, (self.dof,))
+
+    def pair_proximity_jacobians(self, q, pairs):
+        """``proximity_jacobians(q)`` restricted to the columns ``pairs`` (1-D user pair indices, repeats and any order allowed):
+        ``(..., dof)`` -> ``(B, S)``, ``(B, S, 9)``, ``(B, S, dof)``, bit-identical to ``proximity_jacobians(q)[:, pairs]``."""
+        sm = self.scene_model()
+        sel = self._pair_indices(sm, pairs)
+        self._check_q(q)
+        _, dev = self._scene_device()
+        return self._subset_records(dev, q, sel)
+
+    def item_proximity_jacobians(self, q, pair):
+        """One pair per configuration: ``pair`` (B,) user pair indices (NumPy or a CUDA tensor) -> ``(B,)``, ``(B, 9)``,
+        ``(B, dof)``, the records of ``proximity_jacobians(q)`` at [b, pair[b]].  (A CUDA tensor's range check reads its min and
+        max back.)"""
+        sm = self.scene_model()
+        self._check_q(q)
+        B = int(np.prod(q.shape[:-1])) if q.ndim > 1 else 1
+        if _is_tensor(pair):
+            import torch
+            if pair.ndim != 1 or pair.shape[0] != B:
+                raise ValueError(f"pair must have shape ({B},)")
+            if pair.dtype == torch.bool or pair.is_floating_point() or pair.is_complex():
+                raise ValueError("pair must hold integer pair indices")
+            if B:
+                self._check_pair_values(torch.stack((pair.min(), pair.max())).cpu().numpy(), sm.n_pairs, "pair")
+            dv = pair.device if pair.is_cuda else torch.device("cuda")
+            items = torch.stack((torch.arange(B, dtype=torch.int32, device=dv), pair.to(device=dv, dtype=torch.int32)), dim=1)
+        else:
+            a = np.asarray(pair)
+            if a.shape != (B,):
+                raise ValueError(f"pair must have shape ({B},)")
+            if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError("pair must hold integer pair indices")
+            self._check_pair_values(a, sm.n_pairs, "pair")
+            items = np.stack((np.arange(B, dtype=np.int32), a.astype(np.int32)), axis=1)
+        _, dev = self._scene_device()
+        return dev.pair_records(q.reshape(-1, self.dof), items)
+
+    def closest_proximity_jacobians(self, q):
+        """Batched ``closest_to`` + ``jacobian_proximity`` of the closest pair (the greedy counter-example search,
+        safe_sets.py:137-152): ``(..., dof)`` -> dist ``(B,)``, pair ``(B,)`` int32 (first minimum), witness ``(B, 9)``,
+        rows ``(B, dof)``.  The closest-pair kernel and the item kernel run back to back on the device."""
+        sm = self.scene_model()
+        self._check_q(q)
+        if sm.n_pairs == 0:
+            raise ValueError("min() arg is an empty sequence")
+        _, dev = self._scene_device()
+        return dev.closest_records(q.reshape(-1, self.dof))
 
     def jacobian_proximity(self, q, obj, link=None):
         """As upstream (arm.py:620-632): one row per proximity of ``distance_to(q, obj, link)``, a 1-D row when
@@ -527,8 +628,8 @@ class Arm(Robot):
         qn = q.detach().cpu().numpy() if _is_tensor(q) else np.asarray(q, dtype=np.float64)
         if not sel:
             return np.zeros((0, self.dof))
-        _, _, rows = dev.proximity_jacobian(qn.reshape(1, -1))
-        J = np.ascontiguousarray(rows[0][sel])
+        _, _, rows = self._subset_records(dev, qn.reshape(1, -1), np.asarray(sel, dtype=np.int64), witness=False)
+        J = np.ascontiguousarray(rows[0])
         if J.shape[0] == 1:
             return J[0]
         return J
