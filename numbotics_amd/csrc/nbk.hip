@@ -2721,6 +2721,52 @@ NBK_DEV void mark_hit(long long b, uint64_t* mask_bits, uint8_t* mask_bytes) {
     if (mask_bytes != nullptr) mask_bytes[b] = 1;
 }
 
+// phase 2's boolean walk: every lane with `have` steps its own item until the last has its verdict; an inflated walk that gives up
+// (r == 3) leaves its item to the caller in `hard`
+template <int INFL, int KA, int KB>
+NBK_DEV void narrow_walk(GjkBool& gb, const Core& A, const Core& Bc, double tc, bool& have, bool& hard, long long b,
+                         uint64_t* mask_bits, uint8_t* mask_bytes) {
+    while (__builtin_amdgcn_ballot_w64(have) != 0ull) {
+        if (have) {
+            const int r = gjkb_step_k<INFL, KA, KB>(gb, A, Bc, tc);
+            if (r != 0) { if (r == 2) mark_hit(b, mask_bits, mask_bytes); hard = hard || r == 3; have = false; }
+        }
+    }
+}
+
+// The walk with the core kinds and the inflation fixed at compile time where the wave allows it.  A chunk comes from one kind-class
+// sub-queue (flush_items), so in the box-box, box-cylinder and cylinder-cylinder classes every walking lane holds the same two kinds:
+// the kinds are read from the first walking lane and a ballot confirms them for all the others.  INFL 2 decides per item (tc > 0:
+// inflated); when every walking lane makes the same choice the walk is instantiated for it.  Anything else -- the "rest" class,
+// mixed kinds, mixed choices -- takes the generic step.  Each item runs the same statements in the same order either way.
+template <int INFL>
+NBK_DEV void narrow_walk_any(GjkBool& gb, const Core& A, const Core& Bc, double tc, bool& have, bool& hard, long long b,
+                             uint64_t* mask_bits, uint8_t* mask_bytes) {
+    const unsigned long long walkers = __builtin_amdgcn_ballot_w64(have);
+    if (walkers == 0ull) return;
+    const int l0 = __builtin_ctzll(walkers);
+    const int ka = __builtin_amdgcn_readlane(A.kind, l0), kb = __builtin_amdgcn_readlane(Bc.kind, l0);
+    const bool same = __builtin_amdgcn_ballot_w64(have && (A.kind != ka || Bc.kind != kb)) == 0ull;
+    int infl = INFL;
+    if (INFL == 2) {
+        const unsigned long long pos = __builtin_amdgcn_ballot_w64(have && tc > 0.0);
+        infl = pos == walkers ? 1 : (pos == 0ull ? 0 : 2);
+    }
+    const int cls = !same ? 3 : ((ka == K_BOX && kb == K_BOX) ? 0 : ((ka == K_BOX && kb == K_CYL) ? 1 : ((ka == K_CYL && kb == K_CYL) ? 2 : 3)));
+#define NBK_WALK(I, KA_, KB_) narrow_walk<I, KA_, KB_>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes)
+    if (cls == 3 || infl == 2) NBK_WALK(INFL, K_ANY, K_ANY);
+    else if (infl == 1) {
+        if (cls == 0) NBK_WALK(1, K_BOX, K_BOX);
+        else if (cls == 1) NBK_WALK(1, K_BOX, K_CYL);
+        else NBK_WALK(1, K_CYL, K_CYL);
+    } else {
+        if (cls == 0) NBK_WALK(0, K_BOX, K_BOX);
+        else if (cls == 1) NBK_WALK(0, K_BOX, K_CYL);
+        else NBK_WALK(0, K_CYL, K_CYL);
+    }
+#undef NBK_WALK
+}
+
 // BOOL_ONLY: the host has established tc == 0 for every pair that can reach GJK (threshold 0 and no margins on
 // box / cylinder / capsule-vs-solid pairs -- the reference's default in_collision(q) call on sharp shapes); only the
 // boolean GJK state is kept.
@@ -2886,12 +2932,8 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
             if constexpr (MODE == 1) {
                 GjkBool gb;
                 gjkb_init(gb, A, Bc);
-                while (__builtin_amdgcn_ballot_w64(have) != 0ull) {
-                    if (have) {
-                        const int r = gjkb_step(gb, A, Bc);
-                        if (r != 0) { if (r == 2) mark_hit(b, mask_bits, mask_bytes); have = false; }
-                    }
-                }
+                bool hard = false;     // (never set: the plain walk decides every item)
+                narrow_walk_any<0>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes);
             } else if constexpr (MODE == 3) {
                 // tc > 0 everywhere: the boolean walk on the inflated core, then the distance iteration for what it leaves
                 // undecided.  The kernel's time is set by its slowest items: with a cap of 20 steps some 10-2000 items per 1e6
@@ -2902,12 +2944,7 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
                 // hull cores skip the walk: every step scans a vertex list and the distance iteration needs half as many
                 bool hard = have && (A.kind == K_HULL || Bc.kind == K_HULL);
                 have = have && !hard;
-                while (__builtin_amdgcn_ballot_w64(have) != 0ull) {
-                    if (have) {
-                        const int r = gjkb_step<2>(gb, A, Bc, tc);
-                        if (r != 0) { if (r == 2) mark_hit(b, mask_bits, mask_bytes); hard = hard || r == 3; have = false; }
-                    }
-                }
+                narrow_walk_any<2>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes);
                 if (__builtin_amdgcn_ballot_w64(hard) != 0ull) {
                     GjkPred g;
                     gjk_pred_init(g, A, Bc);

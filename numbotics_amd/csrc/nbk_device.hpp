@@ -158,70 +158,81 @@ NBK_DEV void hull_min_max(P hv, int hn, double dl0, double dl1, double dl2, doub
     pos = hi; neg = -lo;
 }
 
-NBK_DEV void core_support(const Core& s, const double* d, double* o) {
-    switch (s.kind) {
-        case K_POINT: copy3(s.c, o); break;
-        case K_SEG: {
-            const double du = dot3(d, s.ax[2]);
-            const double sg = du >= 0.0 ? s.h[0] : -s.h[0];
-            axpy3(sg, s.ax[2], s.c, o);
-        } break;
-        case K_CYL: {
-            const double du = dot3(d, s.ax[2]);
-            const double sg = du >= 0.0 ? s.h[0] : -s.h[0];
-            // w = (u.u) d - (d.u) u, twice: perpendicular to the axis whatever its length (see the oracle: a joint axis given to
-            // five digits leaves the link rotations orthonormal to 1e-6 only)
-            const double uu = dot3(s.ax[2], s.ax[2]);
-            double w[3], t[3];
-            t[0] = uu * d[0]; t[1] = uu * d[1]; t[2] = uu * d[2];
-            axpy3(-du, s.ax[2], t, w);
-            const double wu = dot3(w, s.ax[2]);
-            t[0] = uu * w[0]; t[1] = uu * w[1]; t[2] = uu * w[2];
-            axpy3(-wu, s.ax[2], t, w);
-            const double ww = dot3(w, w);
-            axpy3(sg, s.ax[2], s.c, o);
-            // (a direction axial to 1e-13 has no radial part worth the name: see the oracle)
-            const double u4 = (uu * uu) * (uu * uu);
-            if (ww > (1e-26 * u4) * dot3(d, d)) {
-                const double k = s.rad / nbk_sqrt(ww);
-                axpy3(k, w, o, o);
-            }
-        } break;
-        case K_HULL: {
-            // direction in local coordinates, first maximum over the vertex list, that vertex back to the world
-            const double dl0 = dot3(d, s.ax[0]), dl1 = dot3(d, s.ax[1]), dl2 = dot3(d, s.ax[2]);
-            double v0, v1, v2;
-            if (s.rad < 0.0) {
-                // rad < 0 (set by the pair loop of k_distances): every lane of the wave holds THIS hull, only the poses differ -- the
-                // vertex list is read through the scalar cache (constant address space, uniform pointer and count) instead of sixty-four
-                // identical vector loads per coordinate; same comparisons, same vertex
-                typedef const __attribute__((address_space(4))) double* ConstDoubleP;
-                const unsigned long long pu = __builtin_bit_cast(unsigned long long, s.h[0]);
-                const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pu);
-                const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(pu >> 32));
-                const ConstDoubleP hvu = (ConstDoubleP)(((unsigned long long)hi << 32) | lo);
-                const int hnu = __builtin_amdgcn_readfirstlane(hull_hn(s));
-                hull_first_max(hvu, hnu, dl0, dl1, dl2, v0, v1, v2);
-            } else {
-                const int hn = hull_hn(s);
-                hull_first_max(hull_hv(s), hn, dl0, dl1, dl2, v0, v1, v2);       // (k_narrow*: hv may be a flat address of the LDS copy)
-            }
-            copy3(s.c, o);
-            axpy3(v0, s.ax[0], o, o);
-            axpy3(v1, s.ax[1], o, o);
-            axpy3(v2, s.ax[2], o, o);
-        } break;
-        default: {
-            copy3(s.c, o);
+// support point of one core kind, K fixed at compile time; K_ANY: the kind read at run time (core_support).  The narrowphase walk
+// instantiates the kinds of a kind-homogeneous chunk directly: the run-time form is a per-lane switch over five bodies on both sides
+// of every step, with its exec-mask bookkeeping, where a chunk of box-cylinder items needs one body per side
+constexpr int K_ANY = -1;
+template <int K>
+NBK_DEV void core_support_k(const Core& s, const double* d, double* o) {
+    if constexpr (K == K_ANY) {
+        switch (s.kind) {
+            case K_POINT: core_support_k<K_POINT>(s, d, o); break;
+            case K_SEG: core_support_k<K_SEG>(s, d, o); break;
+            case K_CYL: core_support_k<K_CYL>(s, d, o); break;
+            case K_HULL: core_support_k<K_HULL>(s, d, o); break;
+            default: core_support_k<K_BOX>(s, d, o); break;
+        }
+    } else if constexpr (K == K_POINT) {
+        copy3(s.c, o);
+    } else if constexpr (K == K_SEG) {
+        const double du = dot3(d, s.ax[2]);
+        const double sg = du >= 0.0 ? s.h[0] : -s.h[0];
+        axpy3(sg, s.ax[2], s.c, o);
+    } else if constexpr (K == K_CYL) {
+        const double du = dot3(d, s.ax[2]);
+        const double sg = du >= 0.0 ? s.h[0] : -s.h[0];
+        // w = (u.u) d - (d.u) u, twice: perpendicular to the axis whatever its length (see the oracle: a joint axis given to
+        // five digits leaves the link rotations orthonormal to 1e-6 only)
+        const double uu = dot3(s.ax[2], s.ax[2]);
+        double w[3], t[3];
+        t[0] = uu * d[0]; t[1] = uu * d[1]; t[2] = uu * d[2];
+        axpy3(-du, s.ax[2], t, w);
+        const double wu = dot3(w, s.ax[2]);
+        t[0] = uu * w[0]; t[1] = uu * w[1]; t[2] = uu * w[2];
+        axpy3(-wu, s.ax[2], t, w);
+        const double ww = dot3(w, w);
+        axpy3(sg, s.ax[2], s.c, o);
+        // (a direction axial to 1e-13 has no radial part worth the name: see the oracle)
+        const double u4 = (uu * uu) * (uu * uu);
+        if (ww > (1e-26 * u4) * dot3(d, d)) {
+            const double k = s.rad / nbk_sqrt(ww);
+            axpy3(k, w, o, o);
+        }
+    } else if constexpr (K == K_HULL) {
+        // direction in local coordinates, first maximum over the vertex list, that vertex back to the world
+        const double dl0 = dot3(d, s.ax[0]), dl1 = dot3(d, s.ax[1]), dl2 = dot3(d, s.ax[2]);
+        double v0, v1, v2;
+        if (s.rad < 0.0) {
+            // rad < 0 (set by the pair loop of k_distances): every lane of the wave holds THIS hull, only the poses differ -- the
+            // vertex list is read through the scalar cache (constant address space, uniform pointer and count) instead of sixty-four
+            // identical vector loads per coordinate; same comparisons, same vertex
+            typedef const __attribute__((address_space(4))) double* ConstDoubleP;
+            const unsigned long long pu = __builtin_bit_cast(unsigned long long, s.h[0]);
+            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pu);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(pu >> 32));
+            const ConstDoubleP hvu = (ConstDoubleP)(((unsigned long long)hi << 32) | lo);
+            const int hnu = __builtin_amdgcn_readfirstlane(hull_hn(s));
+            hull_first_max(hvu, hnu, dl0, dl1, dl2, v0, v1, v2);
+        } else {
+            const int hn = hull_hn(s);
+            hull_first_max(hull_hv(s), hn, dl0, dl1, dl2, v0, v1, v2);       // (k_narrow*: hv may be a flat address of the LDS copy)
+        }
+        copy3(s.c, o);
+        axpy3(v0, s.ax[0], o, o);
+        axpy3(v1, s.ax[1], o, o);
+        axpy3(v2, s.ax[2], o, o);
+    } else {
+        static_assert(K == K_BOX, "core_support_k: no such kind");
+        copy3(s.c, o);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double dj = dot3(d, s.ax[j]);
-                const double sj = dj >= 0.0 ? s.h[j] : -s.h[j];
-                axpy3(sj, s.ax[j], o, o);
-            }
-        } break;
+        for (int j = 0; j < 3; ++j) {
+            const double dj = dot3(d, s.ax[j]);
+            const double sj = dj >= 0.0 ? s.h[j] : -s.h[j];
+            axpy3(sj, s.ax[j], o, o);
+        }
     }
 }
+NBK_DEV void core_support(const Core& s, const double* d, double* o) { core_support_k<K_ANY>(s, d, o); }
 
 NBK_DEV double core_halfwidth(const Core& s, const double* n) {
     switch (s.kind) {
@@ -615,13 +626,15 @@ constexpr int GJKB_MAXIT = 32;
 constexpr int GJKB_INFL_MAXIT = 64;     // the inflated walk (tc > 0): then the distance iteration decides (figures: see the oracle)
 struct GjkBool { double p[3][3]; int n; double d[3]; int it; };   // p[0] oldest; at most 3 points are kept between steps
 
-NBK_DEV void mink_support(const Core& A, const Core& Bc, const double* d, double* w) {
+template <int KA, int KB>
+NBK_DEV void mink_support_k(const Core& A, const Core& Bc, const double* d, double* w) {
     const double nd[3] = {-d[0], -d[1], -d[2]};
     double sa[3], sb[3];
-    core_support(A, d, sa);
-    core_support(Bc, nd, sb);
+    core_support_k<KA>(A, d, sa);
+    core_support_k<KB>(Bc, nd, sb);
     sub3(sa, sb, w);
 }
+NBK_DEV void mink_support(const Core& A, const Core& Bc, const double* d, double* w) { mink_support_k<K_ANY, K_ANY>(A, Bc, d, w); }
 NBK_DEV void tri_prod(const double* x, const double* y, double* o) {   // (x cross y) cross x
     double t[3];
     cross3(x, y, t);
@@ -673,12 +686,14 @@ NBK_DEV void gjkb_init(GjkBool& g, const Core& A, const Core& Bc) {
 // tc d/|d| -- so that "A (+) ball(tc) meets B" decides dist(A, B) < tc with the cheap walk instead of the distance iteration;
 // the rounded shape can take long to separate from a near-tangent partner, so the walk gives up after GJKB_INFL_MAXIT steps
 // (or with the origin on the simplex) and the caller falls back to gjk_collides.  INFL 2: per item, inflated iff tc > 0.
-template <int INFL = 0>
-NBK_DEV int gjkb_step(GjkBool& g, const Core& A, const Core& Bc, double tc = 0.0) {
+// KA, KB: the core kinds when the caller knows them at compile time (a kind-homogeneous chunk of k_narrow*), else K_ANY; the
+// arithmetic of an item is the same either way, only the support routine's dispatch goes
+template <int INFL, int KA, int KB>
+NBK_DEV int gjkb_step_k(GjkBool& g, const Core& A, const Core& Bc, double tc = 0.0) {
     const bool infl = INFL == 1 || (INFL == 2 && tc > 0.0);
     if (g.it >= (infl ? GJKB_INFL_MAXIT : GJKB_MAXIT)) return infl ? 3 : 2;
     double a[3];
-    mink_support(A, Bc, g.d, a);
+    mink_support_k<KA, KB>(A, Bc, g.d, a);
     if (infl) {
         const double k = tc / nbk_sqrt(dot3(g.d, g.d));
         axpy3(k, g.d, a, a);
@@ -725,6 +740,8 @@ NBK_DEV int gjkb_step(GjkBool& g, const Core& A, const Core& Bc, double tc = 0.0
     if (dot3(g.d, g.d) == 0.0) return infl ? 3 : 2;
     return 0;
 }
+template <int INFL = 0>
+NBK_DEV int gjkb_step(GjkBool& g, const Core& A, const Core& Bc, double tc = 0.0) { return gjkb_step_k<INFL, K_ANY, K_ANY>(g, A, Bc, tc); }
 NBK_DEV bool gjk_intersect(const Core& A, const Core& Bc) {
     GjkBool g;
     gjkb_init(g, A, Bc);
