@@ -257,6 +257,38 @@ int32_t nbk_edge_validity_batch(const nbk_model *m, const double *starts, const 
                                 int32_t *n_samples, void *stream);
 
 /*
+ * Certified ContinuousConnector (numbotics/planning/sampling_based/connectors.py:108-185 searches each sub-interval with SciPy
+ * SLSQP for a t where the checker is <= 0, a local search that can miss a contact): conservative advancement on the default
+ * linear trajectory q(t) = (1-t)*s + t*g, t in [0, T_f].  One (edge, pair) item per lane; each item repeats, at most max_iter times,
+ *   d = signed distance of the pair at q(t) (the bits of nbk_pair_records_items);
+ *   d <= threshold: COLLISION at t;  gap = (d - threshold) - slack <= 0 (or NaN): UNDECIDED at t;  mu == 0: FREE at T_f;
+ *   t' = t + gap / mu >= T_f: FREE at T_f;  else t = t'
+ * and stops UNDECIDED at t when the iterations run out.  mu (nbk_edge_motion_bounds_host) bounds how fast any point of either
+ * shape moves relative to the deepest common frame, so |d(t) - d(t')| <= mu |t - t'|: an edge reported FREE has no
+ * configuration closer than threshold.  Per edge: t_free = the smallest stop point over the pairs; status = FREE when every pair
+ * is FREE, else the status of the pair that stops at t_free (COLLISION before UNDECIDED on a tie); valid = status == FREE.
+ *   starts, goals [E][n_q]; dist (optional) [E], NULL = Euclidean norm; T_f, the degenerate edge (d <= float32 eps: DEGENERATE,
+ *   invalid, t_free and end NaN) and `end` (optional) [E][n_q] as nbk_edge_validity_batch; there is no resolution.
+ *   valid [E] uint8; t_free [E] double (also the per-edge accumulator while the call runs); status [E] int32 NBK_CA_*.
+ * A descriptor without pairs reports every non-degenerate edge FREE at T_f.  NBK_ERR_INVALID for max_iter < 1, slack < 0, a NaN
+ * slack / threshold / max_distance, and null or size errors.  Asynchronous and capturable: no allocation, no host synchronisation,
+ * three kernels on `stream`; nothing is parked in LDS, so every descriptor is served.
+ */
+enum { NBK_CA_FREE = 0, NBK_CA_COLLISION = 1, NBK_CA_UNDECIDED = 2, NBK_CA_DEGENERATE = 3 };
+int32_t nbk_edge_continuous_batch(const nbk_model *m, const double *starts, const double *goals, const double *dist, int64_t E,
+                                  double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
+                                  uint8_t *valid, double *end, double *t_free, int32_t *status, void *stream);
+/*
+ * The motion bounds mu [E][P] (user pair order) that nbk_edge_continuous_batch advances with, computed on the host by the same
+ * routine from the descriptor alone (no GPU needed).  starts, goals (host) [E][n_q].  For pair p = (shape a, shape or world
+ * shape b), Ja / Jb = the joints on a's / b's path and not on the other's; mu = sum over j in Ja, then Jb (joint index
+ * ascending) of c_j |g - s|_qidx(j), with c_j = |joint_slide_j| for a prismatic joint and, for a revolute one, the bound
+ * sum_{k below j on the path} (|joint_trans_k| + |joint_slide_k| max(|s|, |g|)_qidx(k) [prismatic k]) + |local translation| +
+ * (rho + margin) on the distance from joint j's origin to the shape.
+ */
+int32_t nbk_edge_motion_bounds_host(const nbk_model_desc *desc, const double *starts, const double *goals, int64_t E, double *mu);
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -11,6 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libnbk.so")
 
 NBK_OK = 0
+# status codes of nbk_edge_continuous_batch (NBK_CA_*)
+CA_FREE, CA_COLLISION, CA_UNDECIDED, CA_DEGENERATE = 0, 1, 2, 3
 STATUS = {0: "NBK_OK", -1: "NBK_ERR_INVALID", -2: "NBK_ERR_NO_DEVICE", -3: "NBK_ERR_HIP",
           -4: "NBK_ERR_UNSUPPORTED", -5: "NBK_ERR_ALLOC"}
 
@@ -20,7 +22,8 @@ SYMBOLS = [
     "nbk_model_create", "nbk_model_destroy", "nbk_model_num_pairs",
     "nbk_fk_batch", "nbk_frameset_create", "nbk_frameset_destroy", "nbk_fk_frames_batch", "nbk_jacobian_batch", "nbk_ik_batch", "nbk_validity_batch", "nbk_validity_workspace_bytes",
     "nbk_validity_batch_ws", "nbk_closest_batch",
-    "nbk_pair_distances_batch", "nbk_proximity_jacobian_batch", "nbk_pair_records_items", "nbk_edge_validity_batch", "nbk_selftest_math",
+    "nbk_pair_distances_batch", "nbk_proximity_jacobian_batch", "nbk_pair_records_items", "nbk_edge_validity_batch",
+    "nbk_edge_continuous_batch", "nbk_edge_motion_bounds_host", "nbk_selftest_math",
     "nbk_fk_batch_host", "nbk_validity_batch_host", "nbk_knn_prefix",
     "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host",
 ]
@@ -91,6 +94,8 @@ def load():
     lib.nbk_proximity_jacobian_batch.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.nbk_pair_records_items.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.nbk_edge_validity_batch.argtypes = [vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, vp, vp, vp]
+    lib.nbk_edge_continuous_batch.argtypes = [vp, vp, vp, vp, i64, f64, i32, f64, i32, f64, vp, vp, vp, vp, vp]
+    lib.nbk_edge_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, vp, i64, vp]
     lib.nbk_selftest_math.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     lib.nbk_knn_prefix.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.nbk_fk_batch_host.argtypes = [vp, vp, i64, vp, i32, vp, vp]

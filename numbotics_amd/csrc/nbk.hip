@@ -87,6 +87,7 @@ struct DevModel {
     int bq_count[4];              // pairs per broadphase category
     const int* bq_tab;            // [P][4] broadphase order (category-major): centre row of A (3*shape), centre row of B or world index,
                                   //        index into the vp_* tables, category (0 plane, 1 robot-robot, 2 robot-world, 3 robot-world box)
+    MotionTab mt;                 // motion-bound tables of nbk_edge_continuous_batch (user order; nbk_device.hpp)
     int dbg;                              // ablation switches, ONLY in builds made with -DNBK_ABLATE_BUILD (tools/ablate.py, tools/narrow_prof.py;
                                           // the product library compiles them out: NBK_DBG is the constant 0): 1 = no narrowphase, 2 = no pair
                                           // loop, 4 = no queue appends, 8 = no GJK phase, 16 = no FK replay, 32 = no cores, 64 = no pre-check,
@@ -3209,6 +3210,51 @@ __global__ __launch_bounds__(MODE == 0 ? 64 : 128) void k_distances(DevModel m, 
 // descriptor is served, whatever its LDS footprint in the all-pairs kernels.
 // Items outside [0, B) x [0, P) read neither q nor the pair tables and write NaN to every field.
 // LDS: [64][n_q] q rows (the lane's row, staged eight loads at a time) | [J][6][64] joint rows (only when rows are asked for).
+// The (configuration, pair) item of one lane: FK replay of pair p's two shapes along their joint masks (common ancestors: the same
+// frame, applied once), the two cores, cores_distance with the EPA depth deferred and the EPA pass inline (epa_refine).  k_pair_items
+// and k_edge_ca both call it, so the same statements give the same bits.  qof(c) is the lane's q[c].  Every lane of the wave takes
+// part (the replay and the hull path ballot); lanes with ok == false replay nothing and get NaN.  lds_jz (optional): the replay's
+// joint rows for prox_row.
+template <class QOF>
+NBK_DEV double item_distance(const DevModel& m, const QOF& qof, bool ok, int p, int lane, double* lds_jz, double* wit) {
+    const int sa = ok ? m.pair_a[p] : 0, sb = ok ? m.pair_b[p] : 0;
+    const int ra = sa, rb = sb < m.n_rshapes ? sb : ~(sb - m.n_rshapes);
+    const unsigned ma = ok ? m.rs_mask[sa] : 0u, mb = (ok && rb >= 0) ? m.rs_mask[rb] : 0u;
+    Xf TA, TB;
+    xf_from12(m.base_pose, TA);
+    TB = TA;
+    for (int k = 0; k < m.n_joints; ++k) {
+        const bool in_a = (ma >> k) & 1u, in_b = (mb >> k) & 1u;
+        if (__builtin_amdgcn_ballot_w64(in_a || in_b) == 0ull) continue;
+        if (in_a || in_b) {
+            const double qk = qof(m.joint_qidx[k]);
+            Xf nxt;
+            joint_apply(m, k, in_a ? TA : TB, qk, nxt);     // common ancestors: TA == TB bit for bit
+            if (lds_jz != nullptr) joint_frame_rows(m, k, nxt, lds_jz + 6 * k * WAVE + lane);
+            if (in_a) TA = nxt;
+            if (in_b) TB = nxt;
+        }
+    }
+    // the hull support's scalar-cache path (rad < 0) needs every active lane to hold the same hull: only for pair-uniform waves
+    const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
+    const int p0 = __shfl(p, okm != 0ull ? __builtin_ctzll(okm) : 0);
+    const bool uniform = __builtin_amdgcn_ballot_w64(ok && p != p0) == 0ull;
+    if (!ok) return __builtin_nan("");
+    Core A, Bc;
+    A.kind = K_POINT; Bc.kind = K_POINT;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { A.c[e] = 0.0; Bc.c[e] = 1.0; A.h[e] = 0.0; Bc.h[e] = 0.0; A.ax[0][e] = A.ax[1][e] = A.ax[2][e] = 0.0; Bc.ax[0][e] = Bc.ax[1][e] = Bc.ax[2][e] = 0.0; }
+    A.rad = Bc.rad = A.margin = Bc.margin = A.rho = Bc.rho = 0.0;
+    build_core(m, ra, TA, A);
+    build_core(m, rb, TB, Bc);
+    if (uniform && A.kind == K_HULL) A.rad = -1.0;
+    if (uniform && Bc.kind == K_HULL) Bc.rad = -1.0;
+    double fam = -1.0;
+    double d = cores_distance<true, true>(A, Bc, wit, &fam);
+    if (fam >= 0.0) epa_refine<true>(A, Bc, fam, d, wit);
+    return d;
+}
+
 __global__ __launch_bounds__(64) void k_pair_items(DevModel m, const double* __restrict__ q, int64_t B, const int32_t* __restrict__ items,
                                                    int64_t N, double* __restrict__ out_d, double* __restrict__ out_w,
                                                    double* __restrict__ out_j) {
@@ -3221,9 +3267,6 @@ __global__ __launch_bounds__(64) void k_pair_items(DevModel m, const double* __r
     if (live) { b = items[2 * i]; pu = items[2 * i + 1]; }
     const bool ok = live && b >= 0 && b < B && pu >= 0 && pu < m.n_pairs;
     const int p = ok ? m.pair_dev[pu] : 0;
-    const int sa = ok ? m.pair_a[p] : 0, sb = ok ? m.pair_b[p] : 0;
-    const int ra = sa, rb = sb < m.n_rshapes ? sb : ~(sb - m.n_rshapes);
-    const unsigned ma = ok ? m.rs_mask[sa] : 0u, mb = (ok && rb >= 0) ? m.rs_mask[rb] : 0u;
     double* myq = lds + lane * m.n_q;
     double* lds_jz = out_j != nullptr ? lds + WAVE * m.n_q : nullptr;
     if (ok) {
@@ -3238,25 +3281,8 @@ __global__ __launch_bounds__(64) void k_pair_items(DevModel m, const double* __r
                 if (j0 + u <= nq1) myq[j0 + u] = qv[u];
         }
     }
-    Xf TA, TB;
-    xf_from12(m.base_pose, TA);
-    TB = TA;
-    for (int k = 0; k < m.n_joints; ++k) {
-        const bool in_a = (ma >> k) & 1u, in_b = (mb >> k) & 1u;
-        if (__builtin_amdgcn_ballot_w64(in_a || in_b) == 0ull) continue;
-        if (in_a || in_b) {
-            const double qk = myq[m.joint_qidx[k]];
-            Xf nxt;
-            joint_apply(m, k, in_a ? TA : TB, qk, nxt);     // common ancestors: TA == TB bit for bit
-            if (lds_jz != nullptr) joint_frame_rows(m, k, nxt, lds_jz + 6 * k * WAVE + lane);
-            if (in_a) TA = nxt;
-            if (in_b) TB = nxt;
-        }
-    }
-    // the hull support's scalar-cache path (rad < 0) needs every active lane to hold the same hull: only for pair-uniform waves
-    const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
-    const int p0 = __shfl(p, okm != 0ull ? __builtin_ctzll(okm) : 0);
-    const bool uniform = __builtin_amdgcn_ballot_w64(ok && p != p0) == 0ull;
+    double wit[9];
+    const double d = item_distance(m, [&](int c) { return myq[c]; }, ok, p, lane, lds_jz, wit);
     if (!ok) {
         if (live) {
             const double nan = __builtin_nan("");
@@ -3266,19 +3292,6 @@ __global__ __launch_bounds__(64) void k_pair_items(DevModel m, const double* __r
         }
         return;
     }
-    Core A, Bc;
-    A.kind = K_POINT; Bc.kind = K_POINT;
-#pragma unroll
-    for (int e = 0; e < 3; ++e) { A.c[e] = 0.0; Bc.c[e] = 1.0; A.h[e] = 0.0; Bc.h[e] = 0.0; A.ax[0][e] = A.ax[1][e] = A.ax[2][e] = 0.0; Bc.ax[0][e] = Bc.ax[1][e] = Bc.ax[2][e] = 0.0; }
-    A.rad = Bc.rad = A.margin = Bc.margin = A.rho = Bc.rho = 0.0;
-    build_core(m, ra, TA, A);
-    build_core(m, rb, TB, Bc);
-    if (uniform && A.kind == K_HULL) A.rad = -1.0;
-    if (uniform && Bc.kind == K_HULL) Bc.rad = -1.0;
-    double wit[9];
-    double fam = -1.0;
-    double d = cores_distance<true, true>(A, Bc, wit, &fam);
-    if (fam >= 0.0) epa_refine<true>(A, Bc, fam, d, wit);
     out_d[i] = d;
     if (out_w != nullptr) {
 #pragma unroll
@@ -3578,6 +3591,31 @@ __global__ void k_selftest(const double* __restrict__ a, const double* __restric
 // Every sample of every edge becomes one configuration of a flat batch that goes through k_broad / k_narrow
 // (q is generated on the fly from the edge's end points), so edges run at the batch-validity rate; the
 // one-wave-per-edge kernel above stays for a handful of edges, where its early exit and single launch win.
+// the edge rules of DiscreteConnector.connect / steer: d = dist[e] or |g - s| (fma accumulation in joint order); false for the
+// degenerate edge (d <= float32 eps, or not finite); T_f = max_distance / d when steering further than max_distance, else 1
+NBK_DEV bool edge_span(int nq, const double* s, const double* g, const double* dist, int64_t e, double max_distance, int mode,
+                       double& d, double& Tf) {
+    if (dist != nullptr) d = dist[e];
+    else {
+        double acc = 0.0;
+        for (int i = 0; i < nq; ++i) { const double df = g[i] - s[i]; acc = NBK_FMA(df, df, acc); }
+        d = nbk_sqrt(acc);
+    }
+    if (!(d > 1.1920928955078125e-07 && d <= 1.7976931348623157e308)) return false;
+    Tf = (mode == NBK_STEER && d > max_distance) ? max_distance / d : 1.0;
+    return true;
+}
+
+// end state of a non-degenerate edge: the goal (connect) or traj(T_f) = (1 - T_f) s + T_f g, three roundings (steer)
+NBK_DEV void write_edge_end(int nq, const double* s, const double* g, int64_t e, int mode, double Tf, double* end) {
+    if (end == nullptr) return;
+    if (mode == NBK_CONNECT) for (int i = 0; i < nq; ++i) end[e * nq + i] = g[i];
+    else {
+        const double omt = 1.0 - Tf;
+        for (int i = 0; i < nq; ++i) { const double a = omt * s[i]; const double bb = Tf * g[i]; end[e * nq + i] = a + bb; }
+    }
+}
+
 __global__ void k_edge_plan(int nq, const double* __restrict__ starts, const double* __restrict__ goals,
                             const double* __restrict__ dist, int64_t E, double resolution, double max_distance, int mode,
                             double* __restrict__ plan, unsigned long long* __restrict__ cnt, double* __restrict__ end,
@@ -3586,34 +3624,112 @@ __global__ void k_edge_plan(int nq, const double* __restrict__ starts, const dou
     if (e >= E) return;
     const double* s = starts + e * nq;
     const double* g = goals + e * nq;
-    double d;
-    if (dist != nullptr) d = dist[e];
-    else {
-        double acc = 0.0;
-        for (int i = 0; i < nq; ++i) { const double df = g[i] - s[i]; acc = NBK_FMA(df, df, acc); }
-        d = nbk_sqrt(acc);
-    }
-    if (!(d > 1.1920928955078125e-07 && d <= 1.7976931348623157e308)) {
+    double d, Tf;
+    if (!edge_span(nq, s, g, dist, e, max_distance, mode, d, Tf)) {
         plan[3 * e] = 0.0; plan[3 * e + 1] = 0.0; plan[3 * e + 2] = 0.0;
         cnt[e] = 0ull;
         if (n_samples) n_samples[e] = 0;
         if (end) for (int i = 0; i < nq; ++i) end[e * nq + i] = __builtin_nan("");
         return;
     }
-    const double Tf = (mode == NBK_STEER && d > max_distance) ? max_distance / d : 1.0;
+    write_edge_end(nq, s, g, e, mode, Tf, end);
     const double step = resolution / d;
     const double lenf = __builtin_ceil(Tf / step);
     const long long n = lenf > 0.0 ? (long long)lenf : 0;
     plan[3 * e] = step; plan[3 * e + 1] = Tf; plan[3 * e + 2] = (double)n;
     cnt[e] = (unsigned long long)(n + 1);
     if (n_samples) n_samples[e] = (int32_t)(n + 1);
-    if (end) {
-        if (mode == NBK_CONNECT) for (int i = 0; i < nq; ++i) end[e * nq + i] = g[i];
-        else {
-            const double omt = 1.0 - Tf;
-            for (int i = 0; i < nq; ++i) { const double a = omt * s[i]; const double bb = Tf * g[i]; end[e * nq + i] = a + bb; }
+}
+
+// ==== certified continuous edges (nbk_edge_continuous_batch): conservative advancement, one (edge, pair) item per lane ==========
+// Per edge, while the call runs, t_free holds a 64-bit key = bits(t) << 2 | rank (rank 0 COLLISION, 1 UNDECIDED, 2 FREE): stop points
+// lie in [0, T_f] and T_f <= 1, so bits(t) < 2^62 and the unsigned order of the keys is the order of t, then of the rank -- the
+// smallest stop point, COLLISION winning a tie.  k_edge_ca_init sets each key to "FREE at T_f", every item that stops lowers it
+// with one atomicMin, k_edge_ca_final decodes it.
+constexpr unsigned long long CA_COLLISION = 0ull, CA_UNDECIDED = 1ull, CA_FREE = 2ull;
+
+NBK_DEV unsigned long long ca_key(double t, unsigned long long rank) { return (__builtin_bit_cast(unsigned long long, t) << 2) | rank; }
+
+__global__ void k_edge_ca_init(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
+                               int64_t E, double max_distance, int mode, double* __restrict__ end, unsigned long long* __restrict__ key) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double* s = starts + e * nq;
+    const double* g = goals + e * nq;
+    double d, Tf;
+    if (!edge_span(nq, s, g, dist, e, max_distance, mode, d, Tf)) {
+        key[e] = 0ull;
+        if (end) for (int i = 0; i < nq; ++i) end[e * nq + i] = __builtin_nan("");
+        return;
+    }
+    key[e] = ca_key(Tf, CA_FREE);
+    write_edge_end(nq, s, g, e, mode, Tf, end);
+}
+
+// item i = (user pair pu = i / E, edge e = i % E): pair-major, so a wave holds one pair (the hull support's scalar-cache path) unless
+// it straddles two.  The loop runs while any lane of the wave runs, every lane calling item_distance (those that stopped replay
+// nothing).  An item also stops, without a say in the result, once its t exceeds the edge's current smallest stop point: its own
+// stop point (>= t) can then be neither the minimum nor tied with it.
+__global__ __launch_bounds__(64) void k_edge_ca(DevModel m, const double* __restrict__ starts, const double* __restrict__ goals,
+                                                const double* __restrict__ dist, int64_t E, double max_distance, int mode, double thr,
+                                                int max_iter, double slack, unsigned long long* __restrict__ key) {
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < E * (int64_t)m.n_pairs;
+    const int pu = live ? (int)(i / E) : 0;
+    const int64_t e = live ? i - (int64_t)pu * E : 0;
+    const int p = live ? m.pair_dev[pu] : 0;
+    const double* s = starts + e * m.n_q;
+    const double* g = goals + e * m.n_q;
+    double d_edge = 0.0, Tf = 0.0;
+    bool run = live && edge_span(m.n_q, s, g, dist, e, max_distance, mode, d_edge, Tf);
+    const double mu = run ? pair_motion_bound(m.mt, pu, s, g) : 0.0;
+    double t = 0.0;
+    int it = 0;
+    unsigned long long rank = CA_UNDECIDED;
+    bool post = false;
+    while (__builtin_amdgcn_ballot_w64(run) != 0ull) {
+        if (run) {
+            if (it == max_iter) { rank = CA_UNDECIDED; post = true; run = false; }
+            else if (ca_key(t, 0ull) > __hip_atomic_load(key + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) run = false;
+        }
+        const double omt = 1.0 - t;
+        double wit[9];
+        const double d = item_distance(m, [&](int c) { const double a = omt * s[c]; const double b = t * g[c]; return a + b; },
+                                       run, p, lane, nullptr, wit);
+        if (run) {
+            ++it;
+            if (d <= thr) { rank = CA_COLLISION; post = true; run = false; }
+            else {
+                const double gap = (d - thr) - slack;
+                if (!(gap > 0.0)) { rank = CA_UNDECIDED; post = true; run = false; }
+                else if (mu == 0.0) { t = Tf; rank = CA_FREE; post = true; run = false; }
+                else {
+                    const double tn = t + gap / mu;
+                    if (tn >= Tf) { t = Tf; rank = CA_FREE; post = true; run = false; }
+                    else t = tn;
+                }
+            }
         }
     }
+    if (post) atomicMin(key + e, ca_key(t, rank));
+}
+
+__global__ void k_edge_ca_final(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
+                                int64_t E, double max_distance, int mode, const unsigned long long* __restrict__ key,
+                                uint8_t* __restrict__ valid, double* __restrict__ t_free, int32_t* __restrict__ status) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double d, Tf;
+    if (!edge_span(nq, starts + e * nq, goals + e * nq, dist, e, max_distance, mode, d, Tf)) {
+        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = NBK_CA_DEGENERATE;
+        return;
+    }
+    const unsigned long long k = key[e];          // t_free aliases key: read before the write
+    const unsigned long long r = k & 3ull;
+    valid[e] = r == CA_FREE ? 1 : 0;
+    status[e] = r == CA_FREE ? NBK_CA_FREE : (r == CA_COLLISION ? NBK_CA_COLLISION : NBK_CA_UNDECIDED);
+    t_free[e] = __builtin_bit_cast(double, k >> 2);
 }
 
 // exclusive prefix sum of cnt[0..E) into offs[0..E], one workgroup of 1024 threads
@@ -3714,6 +3830,57 @@ static double hull_bound_radius(const double* v, int n) {
 }
 
 static int host_core_rows(int kind) { return kind == K_POINT ? 3 : ((kind == K_BOX || kind == K_HULL) ? 12 : 6); }
+
+// core parameters of robot shape s as the descriptor stores them: h0 h1 h2 rad margin rho (rho: bounding radius about the centre)
+static void robot_core_host(const nbk_model_desc* d, int s, int& kind, double* cc) {
+    core_params(d->rshape_type[s], d->rshape_param + 4 * s, kind, cc);
+    if (kind == K_HULL) {
+        const int h = (int)d->rshape_param[4 * s];
+        cc[5] = hull_bound_radius(d->hull_verts + 3 * (size_t)d->hull_vert_begin[h], d->hull_vert_begin[h + 1] - d->hull_vert_begin[h]);
+    }
+    cc[5] = host_bound_radius(kind, cc);
+}
+
+static double norm3_host(const double* v) { return sqrt(fma(v[2], v[2], fma(v[1], v[1], v[0] * v[0]))); }
+
+// host copies of the MotionTab tables (nbk_model_create uploads them; nbk_edge_motion_bounds_host uses them in place)
+struct MotionHost {
+    std::vector<int> jtype, jqidx, pa, pb;
+    std::vector<double> jtn, jsn, sloc, sbnd;
+    std::vector<unsigned> smask;
+    MotionTab view(int J, int S) const {
+        return MotionTab{J, S, jtype.data(), jqidx.data(), jtn.data(), jsn.data(), smask.data(), sloc.data(), sbnd.data(), pa.data(), pb.data()};
+    }
+};
+
+// fills h from a descriptor whose joint, shape, hull and pair indices have been checked
+static void motion_tables(const nbk_model_desc* d, MotionHost& h) {
+    const int J = d->n_joints, S = d->n_rshapes, P = d->n_pairs;
+    const size_t J1 = J > 0 ? J : 1, S1 = S > 0 ? S : 1, P1 = P > 0 ? P : 1;
+    h.jtype.assign(J1, 0); h.jqidx.assign(J1, 0); h.jtn.assign(J1, 0.0); h.jsn.assign(J1, 0.0);
+    std::vector<unsigned> fmask(J1, 0u);
+    for (int k = 0; k < J; ++k) {
+        h.jtype[k] = d->joint_type[k];
+        h.jqidx[k] = d->joint_qidx[k];
+        h.jtn[k] = norm3_host(d->joint_trans + 3 * k);
+        h.jsn[k] = norm3_host(d->joint_slide + 3 * k);
+        fmask[k] = (d->joint_parent[k] >= 0 ? fmask[d->joint_parent[k]] : 0u) | (1u << k);
+    }
+    h.smask.assign(S1, 0u); h.sloc.assign(S1, 0.0); h.sbnd.assign(S1, 0.0);
+    for (int x = 0; x < S; ++x) {
+        const int f = d->rshape_frame[x];
+        h.smask[x] = f >= 0 ? fmask[f] : 0u;
+        const double* L = d->rshape_local + 12 * (size_t)x;
+        const double tl[3] = {L[3], L[7], L[11]};
+        h.sloc[x] = norm3_host(tl);
+        int kind;
+        double cc[6];
+        robot_core_host(d, x, kind, cc);
+        h.sbnd[x] = cc[5] + cc[4];
+    }
+    h.pa.assign(d->pair_a, d->pair_a + P); h.pa.resize(P1, 0);
+    h.pb.assign(d->pair_b, d->pair_b + P); h.pb.resize(P1, 0);
+}
 
 }  // namespace nbk
 
@@ -3830,13 +3997,8 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
         const int s = order[i];
         new_index[s] = i;
         int kind;
-        core_params(d->rshape_type[s], d->rshape_param + 4 * s, kind, &rs_core[6 * i]);
-        if (kind == K_HULL) {
-            const int h = (int)d->rshape_param[4 * s];
-            rs_core[6 * i + 5] = hull_bound_radius(d->hull_verts + 3 * (size_t)d->hull_vert_begin[h], d->hull_vert_begin[h + 1] - d->hull_vert_begin[h]);
-            rs_hull[i] = h;
-        }
-        rs_core[6 * i + 5] = host_bound_radius(kind, &rs_core[6 * i]);
+        robot_core_host(d, s, kind, &rs_core[6 * i]);
+        if (kind == K_HULL) rs_hull[i] = (int)d->rshape_param[4 * s];
         rs_kind[i] = kind;
         rs_row[i] = rows;
         rows += host_core_rows(kind);
@@ -4051,6 +4213,13 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     std::vector<int> pdev((size_t)(P > 0 ? P : 1), 0);
     for (int p = 0; p < P; ++p) pdev[pu[p]] = p;
     const size_t o_pd = B.add(pdev.data(), sizeof(int) * P);
+    MotionHost mh;
+    motion_tables(d, mh);
+    const size_t o_mjt = B.add(mh.jtype.data(), sizeof(int) * J), o_mjq = B.add(mh.jqidx.data(), sizeof(int) * J);
+    const size_t o_mtn = B.add(mh.jtn.data(), sizeof(double) * J), o_msn = B.add(mh.jsn.data(), sizeof(double) * J);
+    const size_t o_msm = B.add(mh.smask.data(), sizeof(unsigned) * S), o_msl = B.add(mh.sloc.data(), sizeof(double) * S);
+    const size_t o_msb = B.add(mh.sbnd.data(), sizeof(double) * S);
+    const size_t o_mpa = B.add(mh.pa.data(), sizeof(int) * P), o_mpb = B.add(mh.pb.data(), sizeof(int) * P);
     o.vt = B.add(vp_tab.data(), sizeof(int) * 4 * P);
     o.vc = B.add(vp_canon.data(), sizeof(int) * 2 * P);
     o.vk = B.add(vp_cst.data(), sizeof(double) * 4 * P);
@@ -4256,6 +4425,11 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     m.pair_b = reinterpret_cast<const int*>(base + o.pb);
     m.pair_user = reinterpret_cast<const int*>(base + o.pu);
     m.pair_dev = reinterpret_cast<const int*>(base + o_pd);
+    m.mt = MotionTab{J, S, reinterpret_cast<const int*>(base + o_mjt), reinterpret_cast<const int*>(base + o_mjq),
+                     reinterpret_cast<const double*>(base + o_mtn), reinterpret_cast<const double*>(base + o_msn),
+                     reinterpret_cast<const unsigned*>(base + o_msm), reinterpret_cast<const double*>(base + o_msl),
+                     reinterpret_cast<const double*>(base + o_msb), reinterpret_cast<const int*>(base + o_mpa),
+                     reinterpret_cast<const int*>(base + o_mpb)};
     m.vp_tab = reinterpret_cast<const int*>(base + o.vt);
     m.vp_canon = reinterpret_cast<const int*>(base + o.vc);
     m.vp_cst = reinterpret_cast<const double*>(base + o.vk);
@@ -4959,6 +5133,73 @@ int32_t nbk_pair_records_items(const nbk_model* m, const double* q, int64_t B, c
     hipLaunchKernelGGL(k_pair_items, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), pair_items_lds(m, jrows != nullptr),
                        (hipStream_t)stream, m->d, q, B, items, N, dist, witness, jrows);
     NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
+                                  double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
+                                  uint8_t* valid, double* end, double* t_free, int32_t* status, void* stream) {
+    if (m == nullptr || E < 0 || (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)))
+        return NBK_ERR_INVALID;
+    if (!(max_distance > 0.0) || (mode != NBK_CONNECT && mode != NBK_STEER) || max_iter < 1 || !(slack >= 0.0) || threshold != threshold)
+        return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    if (E == 0) return NBK_OK;
+    const int64_t N = E * (int64_t)m->n_pairs;
+    if (E > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* key = reinterpret_cast<unsigned long long*>(t_free);
+    const unsigned eb = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(k_edge_ca_init, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode, end, key);
+    NBK_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(k_edge_ca, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, m->d, starts, goals, dist, E,
+                           max_distance, (int)mode, threshold, (int)max_iter, slack, key);
+        NBK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_edge_ca_final, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
+                       (const unsigned long long*)key, valid, t_free, status);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* starts, const double* goals, int64_t E, double* mu) {
+    if (d == nullptr || E < 0) return NBK_ERR_INVALID;
+    const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
+    if (d->n_q < 0 || J < 0 || S < 0 || W < 0 || P < 0 || d->n_hulls < 0) return NBK_ERR_INVALID;
+    if (J > NBK_MAX_JOINTS || d->n_q > NBK_MAX_DOF) return NBK_ERR_UNSUPPORTED;
+    if ((J > 0 && (d->joint_parent == nullptr || d->joint_type == nullptr || d->joint_qidx == nullptr || d->joint_trans == nullptr ||
+                   d->joint_slide == nullptr)) ||
+        (S > 0 && (d->rshape_frame == nullptr || d->rshape_type == nullptr || d->rshape_local == nullptr || d->rshape_param == nullptr)) ||
+        (P > 0 && (d->pair_a == nullptr || d->pair_b == nullptr)))
+        return NBK_ERR_INVALID;
+    for (int k = 0; k < J; ++k) {
+        if (d->joint_parent[k] >= k || d->joint_parent[k] < -1) return NBK_ERR_INVALID;
+        if (d->joint_qidx[k] < 0 || d->joint_qidx[k] >= d->n_q) return NBK_ERR_INVALID;
+        if (d->joint_type[k] != NBK_REVOLUTE && d->joint_type[k] != NBK_PRISMATIC) return NBK_ERR_INVALID;
+    }
+    for (int x = 0; x < S; ++x) {
+        if (d->rshape_frame[x] < -1 || d->rshape_frame[x] >= J) return NBK_ERR_INVALID;
+        const int t = d->rshape_type[x];
+        if (!((t >= NBK_SPHERE && t <= NBK_CYLINDER) || t == NBK_HULL)) return NBK_ERR_INVALID;
+        if (t == NBK_HULL) {
+            const double h = d->rshape_param[4 * x];
+            if (!(h >= 0.0 && h < (double)d->n_hulls && h == (double)(int)h) || d->hull_vert_begin == nullptr || d->hull_verts == nullptr)
+                return NBK_ERR_INVALID;
+            const int hi = (int)h;
+            if (d->hull_vert_begin[hi] < 0 || d->hull_vert_begin[hi + 1] <= d->hull_vert_begin[hi]) return NBK_ERR_INVALID;
+        }
+    }
+    for (int p = 0; p < P; ++p)
+        if (d->pair_a[p] < 0 || d->pair_a[p] >= S || d->pair_b[p] < 0 || d->pair_b[p] >= S + W) return NBK_ERR_INVALID;
+    if (E == 0 || P == 0) return NBK_OK;
+    if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
+    MotionHost h;
+    motion_tables(d, h);
+    const MotionTab t = h.view(J, S);
+    for (int64_t e = 0; e < E; ++e)
+        for (int p = 0; p < P; ++p)
+            mu[e * P + p] = pair_motion_bound(t, p, starts + e * d->n_q, goals + e * d->n_q);
     return NBK_OK;
 }
 

@@ -1338,4 +1338,63 @@ NBK_DEV bool cores_collide_exact(const Core& A, const Core& Bc, double tc) {
     return gjk_collides(A, Bc, tc);
 }
 
+// ---- motion bound of a linear edge (nbk_edge_continuous_batch; nbk_edge_motion_bounds_host runs the same routine on the host) ----
+// For pair p = (robot shape a, robot or world shape b) and the edge q(t) = (1-t) s + t g, mu_p bounds the speed (per unit t) of
+// any point of either shape relative to the frame of the deepest joint on both paths, so |d_p(t) - d_p(t')| <= mu_p |t - t'|.
+// Joints on both paths move the two shapes rigidly together and do not count; a world shape has no joints.  A prismatic joint j
+// moves its subtree by |slide_j| |dq_j|; a revolute one rotates it by |dq_j| about joint j's origin, which is at most
+// c_{x,j} |dq_j| for the points of shape x, c_{x,j} bounding their distance from that origin.  Tables in the caller's (user)
+// order, made once by nbk_model_create (device copies) or nbk_edge_motion_bounds_host (host copies) with the same code.
+struct MotionTab {
+    int n_joints, n_rshapes;
+    const int* jtype;            // [J] NBK_REVOLUTE / NBK_PRISMATIC
+    const int* jqidx;            // [J] column of q
+    const double* jtn;           // [J] |joint_trans_k|
+    const double* jsn;           // [J] |joint_slide_k|
+    const unsigned* smask;       // [S] joints on the path from the base to the shape's frame (bit k = joint k)
+    const double* sloc;          // [S] |translation of the shape's local pose|
+    const double* sbnd;          // [S] rho + margin of the shape's core, as the descriptor stores them
+    const int* pa;               // [P] robot shape
+    const int* pb;               // [P] robot shape (< S) or S + world shape
+};
+
+__host__ __device__ inline double motion_abs(double x) { return x < 0.0 ? -x : x; }
+
+// c_{x,j} of a revolute joint j on shape x's path: joints k below j on that path (joint index ascending), their translation and,
+// for a prismatic k, its largest travel on the edge; then the shape's local offset and its bounding radius plus margin
+__host__ __device__ inline double motion_reach(const MotionTab& t, int x, int j, const double* s, const double* g) {
+    const unsigned mx = t.smask[x];
+    double c = 0.0;
+    for (int k = j + 1; k < t.n_joints; ++k) {
+        if (!((mx >> k) & 1u)) continue;
+        c = c + t.jtn[k];
+        if (t.jtype[k] == NBK_PRISMATIC) {
+            const int qk = t.jqidx[k];
+            const double as = motion_abs(s[qk]), ag = motion_abs(g[qk]);
+            c = c + t.jsn[k] * (as > ag ? as : ag);
+        }
+    }
+    c = c + t.sloc[x];
+    return c + t.sbnd[x];
+}
+
+__host__ __device__ inline double motion_terms(const MotionTab& t, int x, unsigned js, const double* s, const double* g, double mu) {
+    for (int j = 0; j < t.n_joints; ++j) {
+        if (!((js >> j) & 1u)) continue;
+        const int qj = t.jqidx[j];
+        const double c = t.jtype[j] == NBK_PRISMATIC ? t.jsn[j] : motion_reach(t, x, j, s, g);
+        mu = mu + c * motion_abs(g[qj] - s[qj]);
+    }
+    return mu;
+}
+
+// mu of user pair p on the edge (s, g): a's terms first, then b's, each joint index ascending
+__host__ __device__ inline double pair_motion_bound(const MotionTab& t, int p, const double* s, const double* g) {
+    const int a = t.pa[p], b = t.pb[p];
+    const unsigned ma = t.smask[a], mb = b < t.n_rshapes ? t.smask[b] : 0u;
+    double mu = motion_terms(t, a, ma & ~mb, s, g, 0.0);
+    if (b < t.n_rshapes) mu = motion_terms(t, b, mb & ~ma, s, g, mu);
+    return mu;
+}
+
 }  // namespace nbk

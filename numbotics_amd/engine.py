@@ -51,6 +51,64 @@ def _host_f64(a, n):
     return a
 
 
+def model_desc(model):
+    """The ``nbk_model_desc`` of a KinematicModel or SceneModel (robots/model.py) -> (desc, arrays it points into).  Keep the
+    second value alive as long as the first is used.  Needs no GPU."""
+    kin = getattr(model, "kin", model)
+    scene = model if hasattr(model, "kin") else None
+    keep = []
+
+    def ptr(a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+    d = _lib.ModelDesc()
+    d.n_q, d.n_joints = kin.n_q, kin.n_joints
+    d.joint_parent = ptr(kin.joint_parent, np.int32)
+    d.joint_type = ptr(kin.joint_type, np.int32)
+    d.joint_qidx = ptr(kin.joint_qidx, np.int32)
+    d.joint_rot = ptr(kin.joint_rot, np.float64)
+    d.joint_trans = ptr(kin.joint_trans, np.float64)
+    d.joint_slide = ptr(kin.joint_slide, np.float64)
+    d.joint_axis = ptr(kin.joint_axis, np.float64)
+    d.base_pose = ptr(kin.base_pose, np.float64)
+    if scene is not None:
+        d.n_rshapes, d.n_wshapes, d.n_pairs = scene.n_rshapes, scene.n_wshapes, scene.n_pairs
+        d.rshape_frame = ptr(scene.rshape_frame, np.int32)
+        d.rshape_type = ptr(scene.rshape_type, np.int32)
+        d.rshape_local = ptr(scene.rshape_local, np.float64)
+        d.rshape_param = ptr(scene.rshape_param, np.float64)
+        d.wshape_type = ptr(scene.wshape_type, np.int32)
+        d.wshape_pose = ptr(scene.wshape_pose, np.float64)
+        d.wshape_param = ptr(scene.wshape_param, np.float64)
+        d.pair_a = ptr(scene.pair_a, np.int32)
+        d.pair_b = ptr(scene.pair_b, np.int32)
+        d.n_hulls = scene.n_hulls
+        d.hull_vert_begin = ptr(scene.hull_vert_begin, np.int32)
+        d.hull_verts = ptr(scene.hull_verts, np.float64)
+        d.hull_face_begin = ptr(scene.hull_face_begin, np.int32)
+        d.hull_planes = ptr(scene.hull_planes, np.float64)
+    return d, keep
+
+
+def edge_motion_bounds(model, starts, goals):
+    """Motion bounds mu (E, P) of the linear edges starts -> goals for every allowed pair of a SceneModel, in its pair order:
+    |d_p(t) - d_p(t')| <= mu[e, p] |t - t'| on q(t) = (1-t) s + t g.  The routine nbk_edge_continuous_batch advances with, run on
+    the host (nbk_edge_motion_bounds_host); no GPU needed."""
+    n_q = getattr(model, "kin", model).n_q
+    s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64)).reshape(-1, n_q)
+    g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64)).reshape(-1, n_q)
+    if s.shape != g.shape:
+        raise ValueError("starts and goals must have the same shape")
+    d, keep = model_desc(model)
+    P = int(d.n_pairs)
+    mu = np.empty((s.shape[0], P), dtype=np.float64)
+    _lib.check(_lib.load().nbk_edge_motion_bounds_host(C.byref(d), s.ctypes.data, g.ctypes.data, s.shape[0], mu.ctypes.data),
+               "nbk_edge_motion_bounds_host")
+    del keep
+    return mu
+
+
 class DeviceModel:
     """Immutable device descriptor built from a KinematicModel or SceneModel (robots/model.py)."""
 
@@ -60,40 +118,10 @@ class DeviceModel:
         kin = getattr(model, "kin", model)
         scene = model if hasattr(model, "kin") else None
         self.kin, self.scene = kin, scene
-        keep = []
-
-        def ptr(a, dt):
-            a = np.ascontiguousarray(a, dtype=dt)
-            keep.append(a)
-            return a.ctypes.data
-        d = _lib.ModelDesc()
-        d.n_q, d.n_joints = kin.n_q, kin.n_joints
-        d.joint_parent = ptr(kin.joint_parent, np.int32)
-        d.joint_type = ptr(kin.joint_type, np.int32)
-        d.joint_qidx = ptr(kin.joint_qidx, np.int32)
-        d.joint_rot = ptr(kin.joint_rot, np.float64)
-        d.joint_trans = ptr(kin.joint_trans, np.float64)
-        d.joint_slide = ptr(kin.joint_slide, np.float64)
-        d.joint_axis = ptr(kin.joint_axis, np.float64)
-        d.base_pose = ptr(kin.base_pose, np.float64)
-        if scene is not None:
-            d.n_rshapes, d.n_wshapes, d.n_pairs = scene.n_rshapes, scene.n_wshapes, scene.n_pairs
-            d.rshape_frame = ptr(scene.rshape_frame, np.int32)
-            d.rshape_type = ptr(scene.rshape_type, np.int32)
-            d.rshape_local = ptr(scene.rshape_local, np.float64)
-            d.rshape_param = ptr(scene.rshape_param, np.float64)
-            d.wshape_type = ptr(scene.wshape_type, np.int32)
-            d.wshape_pose = ptr(scene.wshape_pose, np.float64)
-            d.wshape_param = ptr(scene.wshape_param, np.float64)
-            d.pair_a = ptr(scene.pair_a, np.int32)
-            d.pair_b = ptr(scene.pair_b, np.int32)
-            d.n_hulls = scene.n_hulls
-            d.hull_vert_begin = ptr(scene.hull_vert_begin, np.int32)
-            d.hull_verts = ptr(scene.hull_verts, np.float64)
-            d.hull_face_begin = ptr(scene.hull_face_begin, np.int32)
-            d.hull_planes = ptr(scene.hull_planes, np.float64)
+        d, keep = model_desc(model)
         h = C.c_void_p()
         _lib.check(lib.nbk_model_create(C.byref(d), C.byref(h)), "nbk_model_create")
+        del keep
         self._h = h
         self._lib = lib
         self.n_q = kin.n_q
@@ -351,6 +379,29 @@ class DeviceModel:
             float(resolution), float(max_distance), 0 if mode == "connect" else 1, float(threshold),
             valid.data_ptr(), end.data_ptr(), ns.data_ptr(), self._stream()), "nbk_edge_validity_batch")
         return s.out(valid.bool()), s.out(end), s.out(ns)
+
+    def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
+        """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
+        valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``)."""
+        torch = _require_gpu()
+        s = _Staged(starts, self.n_q)
+        g = _Staged(goals, self.n_q)
+        if s.B != g.B:
+            raise ValueError("starts and goals must have the same number of rows")
+        dd = None
+        if dist is not None:
+            dd = _Staged(dist, 1)
+            if dd.B != s.B:
+                raise ValueError("dist must have one value per edge")
+        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        t_free = torch.empty((s.B,), dtype=torch.float64, device=s.device)
+        status = torch.empty((s.B,), dtype=torch.int32, device=s.device)
+        _lib.check(self._lib.nbk_edge_continuous_batch(
+            self._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
+            0 if mode == "connect" else 1, float(threshold), int(max_iter), float(slack), valid.data_ptr(), end.data_ptr(),
+            t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_edge_continuous_batch")
+        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
 
 
 def selftest_math(a, b):

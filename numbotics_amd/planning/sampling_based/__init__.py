@@ -1,5 +1,5 @@
-__all__ = ["Connector", "ConnectorParams", "DiscreteConnector", "StateSpace", "EuclideanSpace", "PlannerParams", "PRM", "PRMStar", "RRT", "RRTStar",
+__all__ = ["Connector", "ConnectorParams", "DiscreteConnector", "ContinuousConnector", "StateSpace", "EuclideanSpace", "PlannerParams", "PRM", "PRMStar", "RRT", "RRTStar",
            "Node", "knn_prefix"]
 
-from .connectors import Connector, ConnectorParams, DiscreteConnector
+from .connectors import Connector, ConnectorParams, ContinuousConnector, DiscreteConnector
 from .roadmap import StateSpace, EuclideanSpace, PlannerParams, PRM, PRMStar, RRT, RRTStar, Node, knn_prefix

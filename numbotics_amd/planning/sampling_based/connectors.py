@@ -4,7 +4,9 @@
 Additive: when the params carry an ``arm`` (instead of, or next to, a Python ``validity_checker``) the
 whole edge -- every sample ``T = arange(0, T_f, res/d) U {T_f}`` -- is checked by ONE device launch,
 and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per wavefront).
-``ContinuousConnector`` (connectors.py:108-185, SciPy SLSQP per sub-interval) is out of scope.
+``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
+certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
+with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.
 """
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
@@ -133,4 +135,103 @@ class DiscreteConnector(Connector):
         """-> ((E,) bool, (E, dof) end states ``traj(T_f)``); rows of invalid edges are what they would
         have been returned had the edge been free."""
         ok, end, _ = self._batch(starts, goals, "steer", dist)
+        return ok, end
+
+
+class ContinuousConnector(Connector):
+    """Continuous edge checks (reference: numbotics/planning/sampling_based/connectors.py:108-185).
+
+    Device path (``params.arm`` set, no ``validity_checker``, the default linear trajectory): every edge is certified by
+    conservative advancement -- one (edge, pair) item per lane advances t by (d - threshold - slack) / mu, where mu bounds how
+    fast the pair's distance can change along the edge (``nbk_edge_continuous_batch``).  An edge is valid only when every pair
+    reaches T_f: no configuration on it is closer than ``collision_threshold``.  Where the bound cannot prove that within
+    ``max_iter`` steps (a pair stays within ``slack`` of the threshold) the edge is UNDECIDED and rejected, although the
+    reference's local search might have accepted it.  ``params.resolution`` plays no part in the device path.
+
+    Host path (a ``validity_checker`` that returns a signed distance, > 0 free): the reference's behaviour -- the sub-intervals of
+    ``arange(0, T_f, resolution / d) U {T_f}`` are each searched with SciPy SLSQP for a t where the checker is <= 0, and the
+    edge is rejected when a search succeeds.  That search is local and can miss a contact."""
+
+    def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6):
+        if int(max_iter) < 1:
+            raise ValueError("max_iter must be at least 1")
+        if not slack >= 0.0:
+            raise ValueError("slack must be non-negative")
+        self._params = params
+        self.max_iter = int(max_iter)
+        self.slack = float(slack)
+
+    def _device_edge(self):
+        p = self._params
+        return p.arm is not None and p.validity_checker is None and p.trajectory_func is _DEFAULT_TRAJ
+
+    # ---- scalar contract -----------------------------------------------------------------------------
+    def _host_blocked(self, start, goal, distance, T_f):
+        """True when SLSQP finds, in some sub-interval, a t with validity_checker(traj(t)) <= 0."""
+        from scipy.optimize import minimize
+        p = self._params
+        traj = p.trajectory_func(start, goal)
+        knots = np.append(np.arange(0.0, T_f, p.resolution / distance), T_f)
+        cons = [{"type": "ineq", "fun": lambda x: -float(p.validity_checker(traj(x[0])))}]
+        for lo, hi in zip(knots[:-1], knots[1:]):
+            res = minimize(lambda x: x[0], np.array([0.5 * (lo + hi)]), method="SLSQP", bounds=[(lo, hi)], constraints=cons)
+            if res.success:
+                return True
+        return False
+
+    def _one(self, start, goal, mode, distance):
+        ok, end, _, _ = self.certify_batch(np.asarray(start, dtype=np.float64)[None], np.asarray(goal, dtype=np.float64)[None],
+                                           mode, np.array([distance], dtype=np.float64))
+        return bool(ok[0]), np.copy(end[0])
+
+    def connect(self, start, goal, distance_func=_DEFAULT_DIST):
+        distance = distance_func(start, goal)
+        if distance <= np.finfo(np.float32).eps:
+            return None
+        if self._device_edge():
+            ok, _ = self._one(start, goal, "connect", distance)
+            return np.copy(goal) if ok else None
+        if self._params.validity_checker is None:
+            raise ValueError("ContinuousConnector needs a validity_checker, or an arm with the default trajectory")
+        return None if self._host_blocked(start, goal, distance, 1.0) else np.copy(goal)
+
+    def steer(self, start, goal, distance_func=_DEFAULT_DIST):
+        distance = distance_func(start, goal)
+        if distance <= np.finfo(np.float32).eps:
+            return None
+        if self._device_edge():
+            ok, end = self._one(start, goal, "steer", distance)
+            return end if ok else None
+        if self._params.validity_checker is None:
+            raise ValueError("ContinuousConnector needs a validity_checker, or an arm with the default trajectory")
+        T_f = 1.0 if distance <= self._params.max_distance else self._params.max_distance / distance
+        if self._host_blocked(start, goal, distance, T_f):
+            return None
+        return np.copy(self._params.trajectory_func(start, goal)(T_f))
+
+    def is_valid(self, state):
+        p = self._params
+        if p.validity_checker is not None:
+            return p.validity_checker(state) > 0.0
+        return not p.arm.in_collision(state, p.collision_threshold)
+
+    # ---- batched ------------------------------------------------------------------------------------------
+    def certify_batch(self, starts, goals, mode="connect", dist=None):
+        """(E, dof) x (E, dof) -> valid (E,) bool, end (E, dof), t_free (E,), status (E,) int32 (``numbotics_amd._lib.CA_*``:
+        0 free, 1 collision, 2 undecided, 3 degenerate).  t_free: how far along [0, T_f] the edge is certified free."""
+        p = self._params
+        if not self._device_edge():
+            raise ValueError("batched continuous checks need ConnectorParams(arm=...) with the default linear trajectory "
+                             "and no validity_checker")
+        _, dev = p.arm._scene_device()
+        return dev.edge_continuous(starts, goals, p.max_distance, mode=mode, threshold=p.collision_threshold,
+                                   max_iter=self.max_iter, slack=self.slack, dist=dist)
+
+    def connect_batch(self, starts, goals, dist=None):
+        """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
+        return self.certify_batch(starts, goals, "connect", dist)[0]
+
+    def steer_batch(self, starts, goals, dist=None):
+        """-> ((E,) bool, (E, dof) end states ``traj(T_f)``)."""
+        ok, end, _, _ = self.certify_batch(starts, goals, "steer", dist)
         return ok, end

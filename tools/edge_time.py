@@ -1,26 +1,55 @@
+"""Batched DiscreteConnector edges on c3 (nbk_edge_validity_batch).  With --continuous: also the certified continuous check
+(nbk_edge_continuous_batch) on c2 and c3 at the ContinuousConnector defaults, next to the discrete check at resolutions 0.01 and
+0.001, with the fraction of UNDECIDED edges.  Usage: python tools/edge_time.py [E ...] [--continuous]"""
 import os, sys, numpy as np, torch
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT','/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from numbotics_amd.physics import World
+from numbotics_amd.physics.world import _reset_worlds
 from numbotics_amd.scenes import build_scene
-World()
-arm, chain, obs = build_scene('c3')
-sm, dev = arm._scene_device()
-E = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
-rng = np.random.default_rng(3)
-lim = chain.joint_limits
-# end points U(limits); the goal is pulled towards the start so that |dq| <= pi (max_distance of _test_rrt.py:98)
-s = rng.uniform(lim[:,0], lim[:,1], (E, 7)); g = rng.uniform(lim[:,0], lim[:,1], (E, 7))
-d = np.linalg.norm(g - s, axis=1)
-scale = np.minimum(1.0, rng.uniform(0.2, 1.0, E) * np.pi / d)
-g = s + (g - s) * scale[:, None]
-ts, tg = torch.from_numpy(s).cuda(), torch.from_numpy(g).cuda()
-for res in (0.01,):
-    ok, end, ns = dev.edge_validity(ts, tg, res, np.pi)
+
+cont = "--continuous" in sys.argv
+sizes = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([10000, 100000] if cont else [100000])
+
+
+def edges(chain, E):
+    rng = np.random.default_rng(3)
+    lim = chain.joint_limits
+    # end points U(limits); the goal is pulled towards the start so that |dq| <= pi (max_distance of _test_rrt.py:98)
+    s = rng.uniform(lim[:, 0], lim[:, 1], (E, 7)); g = rng.uniform(lim[:, 0], lim[:, 1], (E, 7))
+    d = np.linalg.norm(g - s, axis=1)
+    scale = np.minimum(1.0, rng.uniform(0.2, 1.0, E) * np.pi / d)
+    g = s + (g - s) * scale[:, None]
+    return torch.from_numpy(s).cuda(), torch.from_numpy(g).cuda()
+
+
+def timed(fn, reps=3):
+    out = fn()
     torch.cuda.synchronize()
-    e0,e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    for _ in range(3): ok, end, ns = dev.edge_validity(ts, tg, res, np.pi)
+    for _ in range(reps):
+        out = fn()
     e1.record(); torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1)/3
-    tot = int(ns.sum().item())
-    print('E', E, 'res', res, 'ms %.3f'%ms, 'edges/s %.3e'%(E/ms*1e3), 'samples(len T) %.3e'%tot, 'configs/s (len T) %.3e'%(tot/ms*1e3), 'valid frac %.3f'%ok.float().mean().item())
+    return out, e0.elapsed_time(e1) / reps
+
+
+for scene in (("c2", "c3") if cont else ("c3",)):
+    _reset_worlds(); World()
+    arm, chain, obs = build_scene(scene)
+    sm, dev = arm._scene_device()
+    for E in sizes:
+        ts, tg = edges(chain, E)
+        disc = {}
+        for res in ((0.01, 0.001) if cont else (0.01,)):
+            (ok, end, ns), ms = timed(lambda: dev.edge_validity(ts, tg, res, np.pi))
+            tot = int(ns.sum().item())
+            disc[res] = ok
+            print(scene, 'E', E, 'res', res, 'ms %.3f' % ms, 'edges/s %.3e' % (E / ms * 1e3), 'samples(len T) %.3e' % tot,
+                  'configs/s (len T) %.3e' % (tot / ms * 1e3), 'valid frac %.3f' % ok.float().mean().item(), flush=True)
+        if cont:
+            (ok, end, tf, st), ms = timed(lambda: dev.edge_continuous(ts, tg, np.pi))
+            st = st.cpu().numpy()
+            sub = bool((ok & ~disc[0.001]).any().item())
+            print(scene, 'E', E, 'continuous', 'ms %.3f' % ms, 'edges/s %.3e' % (E / ms * 1e3),
+                  'free %.3f collision %.3f undecided %.3f' % tuple((st == k).mean() for k in (0, 1, 2)),
+                  'free-but-discrete-invalid@1e-3', sub, flush=True)
