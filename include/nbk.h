@@ -22,7 +22,8 @@
  *     made on that stream afterwards (in any order with the replays) do the same -- they no longer
  *     reuse tables between calls.  A graph holds the scratch's address: do not replay it after a
  *     direct call on the same stream with a LARGER batch has regrown the scratch (re-capture).  The *_host
- *     conveniences synchronise by definition.  Batches of 2^21 configurations or more (and edge batches of that many samples)
+ *     conveniences synchronise by definition, and so does nbk_spline_validity_batch (it reads its sample count back; it
+ *     refuses a capturing stream).  Batches of 2^21 configurations or more (and edge batches of that many samples)
  *     run every other 2^20-configuration tile on a second, library-owned stream forked from and joined to `stream` with
  *     events -- the call still begins after, and completes before, its neighbours in `stream`'s order;
  *   - every compute call must be made with the descriptor's device current (hipSetDevice):
@@ -287,6 +288,37 @@ int32_t nbk_edge_continuous_batch(const nbk_model *m, const double *starts, cons
  * (rho + margin) on the distance from joint j's origin to the shape.
  */
 int32_t nbk_edge_motion_bounds_host(const nbk_model_desc *desc, const double *starts, const double *goals, int64_t E, double *mu);
+
+/*
+ * Sampled collision check of clamped B-spline trajectories -- the smoothed references unit_bspline builds from a planner's
+ * waypoints (numbotics/planning/trajectories.py:6-22; numbotics_amd.planning.unit_bspline / UnitBSpline).
+ *   ctrl (device) [S][n_ctrl][n_q]: the control points of S trajectories; degree k, 1 <= k <= NBK_MAX_SPLINE_DEGREE, and
+ *   k < n_ctrl <= 65536; knots (HOST) [n_ctrl + k + 1] = tau, shared by all S: finite, nondecreasing, tau[0..k] = 0 and
+ *   tau[n_ctrl..n_ctrl+k] = 1 (clamped on [0, 1]); resolution > 0 and finite.  Anything else: NBK_ERR_INVALID.
+ * Per trajectory, in float64, every operation in this order (the only fused multiply-add is the one named):
+ *   1. speed bound: for i = 0 .. n-2 with den_i = tau[i+k+1] - tau[i+1] > 0 (others are skipped):
+ *      acc = fma(df, df, acc) over the joints in order, df = ctrl[i+1][c] - ctrl[i][c] (the edge length's accumulation),
+ *      v_i = ((double)k * sqrt(acc)) / den_i;  V = max v_i, NaN when any v_i is NaN.  |q'(t)| <= V.
+ *   2. degenerate when !(V > 2^-23 && V <= DBL_MAX) (the edge rule with d := V): valid 0, n_samples 0, t_hit NaN.
+ *   3. samples: step = resolution / V, m = ceil(1.0 / step), t_j = (double)j * step for j < m, t_m = 1.0; n_samples = m + 1
+ *      (np.append(np.arange(0, 1, step), 1.0)).
+ *   4. q_j = spline(t_j), one joint at a time as the general branch of UnitBSpline.__call__: span ell = (number of knots <= t) - 1
+ *      clamped to [k, n-1]; r = 1..k, j = k down to r: den = tau[j+1+ell-r] - tau[j+ell-k], alpha = 0 when den == 0 else
+ *      (t - tau[j+ell-k]) / den, d[j] = (1 - alpha) * d[j-1] + alpha * d[j] in four separately rounded operations.
+ *   5. hit_j = the nbk_validity_batch verdict for q_j at `threshold` (a non-finite q_j collides); valid [S] uint8 = no hit_j;
+ *      t_hit (optional) [S] = t_j of the smallest colliding j, NaN when valid; n_samples (optional) [S] int32.
+ * With n_ctrl = 2, k = 1, tau = [0, 0, 1, 1] this is nbk_edge_validity_batch in connect mode with dist = NULL, bit for bit.
+ * SYNCHRONOUS by design, an exception like the *_host conveniences: the sample total is read back (8 bytes) to size the mask
+ * words and the tiles; the call returns after that read-back and the launches (plan, scan, then per tile of at most 2^20
+ * samples: de Boor rows into the stream's scratch + the validity pipeline, then one reduction).  Scratch is the stream's own set
+ * (grown as nbk_validity_batch's is); it holds one tile of q rows and one bit per sample.  On a capturing stream the call returns
+ * NBK_ERR_UNSUPPORTED before any synchronisation or allocation (the capture stays usable); S = 0 returns NBK_OK at once; a total
+ * of 2^31 samples or more, or S >= 2^26, returns NBK_ERR_UNSUPPORTED (split the batch).  Every descriptor is served.
+ */
+#define NBK_MAX_SPLINE_DEGREE 5
+int32_t nbk_spline_validity_batch(const nbk_model *m, const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                  const double *knots /* host [n_ctrl + degree + 1] */, double resolution, double threshold,
+                                  uint8_t *valid, double *t_hit /* optional */, int32_t *n_samples /* optional */, void *stream);
 
 /*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists

@@ -25,8 +25,9 @@ SYMBOLS = [
     "nbk_pair_distances_batch", "nbk_proximity_jacobian_batch", "nbk_pair_records_items", "nbk_edge_validity_batch",
     "nbk_edge_continuous_batch", "nbk_edge_motion_bounds_host", "nbk_selftest_math",
     "nbk_fk_batch_host", "nbk_validity_batch_host", "nbk_knn_prefix",
-    "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host",
+    "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host", "nbk_spline_validity_batch",
 ]
+MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
 
 class ModelDesc(C.Structure):
@@ -95,6 +96,7 @@ def load():
     lib.nbk_pair_records_items.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.nbk_edge_validity_batch.argtypes = [vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, vp, vp, vp]
     lib.nbk_edge_continuous_batch.argtypes = [vp, vp, vp, vp, i64, f64, i32, f64, i32, f64, vp, vp, vp, vp, vp]
+    lib.nbk_spline_validity_batch.argtypes = [vp, vp, i64, i32, i32, vp, f64, f64, vp, vp, vp, vp]
     lib.nbk_edge_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, vp, i64, vp]
     lib.nbk_selftest_math.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     lib.nbk_knn_prefix.argtypes = [vp, i32, i32, i32, vp, vp]

@@ -142,6 +142,9 @@ struct StreamWs {
     long long ecap_edges = 0; unsigned long long ecap_samples = 0;
     unsigned long long* stats = nullptr;      // [4] pinned + mapped: samples needed by the last finished edge call, edges served by the overflow kernel
     unsigned long long* stats_dev = nullptr;  // device alias of `stats`
+    // nbk_spline_validity_batch: knots | plan | counts | offsets (sps), mask words | q slab of one tile (spl)
+    void* sps = nullptr; size_t sps_bytes = 0;
+    void* spl = nullptr; size_t spl_bytes = 0;
     // tile pipelining of batches of several tiles: odd tiles run on `aux_stream` with the scratch set `aux` (forked from / joined
     // to the caller's stream with events), so the latency-bound narrowphase of one tile overlaps the issue-bound broadphase of the next
     hipStream_t aux_stream = nullptr;
@@ -149,6 +152,7 @@ struct StreamWs {
     StreamWs* aux = nullptr;        // another entry of the descriptor's list, freed as such: not owned here
     ~StreamWs() {
         if (ws) (void)hipFree(ws);  if (ews) (void)hipFree(ews);  if (stats) (void)hipHostFree(stats);
+        if (sps) (void)hipFree(sps);  if (spl) (void)hipFree(spl);
         if (ev_fork) (void)hipEventDestroy(ev_fork);  if (ev_join) (void)hipEventDestroy(ev_join);
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
     }
@@ -3591,16 +3595,19 @@ __global__ void k_selftest(const double* __restrict__ a, const double* __restric
 // Every sample of every edge becomes one configuration of a flat batch that goes through k_broad / k_narrow
 // (q is generated on the fly from the edge's end points), so edges run at the batch-validity rate; the
 // one-wave-per-edge kernel above stays for a handful of edges, where its early exit and single launch win.
-// the edge rules of DiscreteConnector.connect / steer: d = dist[e] or |g - s| (fma accumulation in joint order); false for the
+// |g - s|: fma accumulation in joint order (edge lengths, and the control-polygon legs of k_spline_plan)
+NBK_DEV double diff_norm(int nq, const double* s, const double* g) {
+    double acc = 0.0;
+    for (int i = 0; i < nq; ++i) { const double df = g[i] - s[i]; acc = NBK_FMA(df, df, acc); }
+    return nbk_sqrt(acc);
+}
+
+// the edge rules of DiscreteConnector.connect / steer: d = dist[e] or |g - s| (diff_norm); false for the
 // degenerate edge (d <= float32 eps, or not finite); T_f = max_distance / d when steering further than max_distance, else 1
 NBK_DEV bool edge_span(int nq, const double* s, const double* g, const double* dist, int64_t e, double max_distance, int mode,
                        double& d, double& Tf) {
     if (dist != nullptr) d = dist[e];
-    else {
-        double acc = 0.0;
-        for (int i = 0; i < nq; ++i) { const double df = g[i] - s[i]; acc = NBK_FMA(df, df, acc); }
-        d = nbk_sqrt(acc);
-    }
+    else d = diff_norm(nq, s, g);
     if (!(d > 1.1920928955078125e-07 && d <= 1.7976931348623157e308)) return false;
     Tf = (mode == NBK_STEER && d > max_distance) ? max_distance / d : 1.0;
     return true;
@@ -3779,6 +3786,117 @@ __global__ __launch_bounds__(64) void k_edge_reduce(const unsigned long long* __
     }
     const unsigned long long any = __builtin_amdgcn_ballot_w64(hit);
     if (threadIdx.x == 0) valid[e] = (n > 0 && any == 0ull) ? 1 : 0;
+}
+
+// ==== clamped B-spline trajectories (nbk_spline_validity_batch): plan -> scan -> per tile (expand -> validity pipeline) -> reduce ===
+// Trajectory s has control points ctrl[s][n][nq] and the shared knots tau[0 .. n+k].  Its derivative lies in the convex hull of
+// k (c[i+1] - c[i]) / (tau[i+k+1] - tau[i+1]), so |q'(t)| <= V = the largest of those norms, and samples resolution / V apart in
+// t are at most `resolution` apart in joint space.  The samples t_j = j * step (j < m), t_m = 1 become q rows of a flat batch,
+// written one tile at a time into a slab that the validity pipeline reads like any batch: no validity kernel knows about splines.
+constexpr double SPLINE_MIN_SPEED = 1.1920928955078125e-07;        // 2^-23: the degenerate-edge rule with d := V
+constexpr unsigned long long SPLINE_TOO_MANY = 1ull << 32;          // a count that stands for "more than the host accepts"
+
+// one wave per trajectory: V = max_i v_i (NaN when any v_i is NaN), step = resolution / V, m = ceil(1 / step); plan[s] = (step, m),
+// cnt[s] = m + 1 samples, 0 for a degenerate trajectory (V outside (2^-23, DBL_MAX])
+__global__ __launch_bounds__(64) void k_spline_plan(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
+                                                   double resolution, double* __restrict__ plan, unsigned long long* __restrict__ cnt) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double* c = ctrl + (size_t)s * (size_t)n * nq;
+    double vmax = 0.0;
+    bool nan = false;
+    for (int i = lane; i < n - 1; i += WAVE) {
+        const double den = knots[i + k + 1] - knots[i + 1];
+        if (den <= 0.0) continue;
+        const double v = ((double)k * diff_norm(nq, c + (size_t)i * nq, c + (size_t)(i + 1) * nq)) / den;
+        if (v != v) nan = true;
+        else if (v > vmax) vmax = v;
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) { const double x = __shfl_xor(vmax, o); vmax = x > vmax ? x : vmax; }
+    if (__builtin_amdgcn_ballot_w64(nan) != 0ull) vmax = __builtin_nan("");
+    if (lane != 0) return;
+    const double V = vmax;
+    if (!(V > SPLINE_MIN_SPEED && V <= 1.7976931348623157e308)) { plan[2 * s] = 0.0; plan[2 * s + 1] = 0.0; cnt[s] = 0ull; return; }
+    const double step = resolution / V;
+    const double mf = __builtin_ceil(1.0 / step);
+    if (!(mf < 4294967296.0)) { plan[2 * s] = step; plan[2 * s + 1] = 0.0; cnt[s] = SPLINE_TOO_MANY; return; }
+    const unsigned long long m = mf > 0.0 ? (unsigned long long)mf : 0ull;
+    plan[2 * s] = step; plan[2 * s + 1] = (double)m;
+    cnt[s] = m + 1ull;
+}
+
+// one thread per row r of the tile (flat sample b0 + r): trajectory by binary search over the offsets, t_j, then the general branch
+// of UnitBSpline.__call__ one joint at a time -- span ell = (knots <= t) - 1 clamped to [K, n-1], de Boor with
+// d[j] = (1 - alpha) * d[j-1] + alpha * d[j] in four roundings (the alphas depend on t only: computed once).  `words` (descriptors
+// without pairs, rows == nullptr): the verdict is the row's finiteness, one mask word per wave (b0 and the block are multiples of 64)
+template <int K>
+__global__ __launch_bounds__(256) void k_spline_expand(int nq, const double* __restrict__ ctrl, int n, const double* __restrict__ knots,
+                                                       const double* __restrict__ plan, const unsigned long long* __restrict__ offs, int64_t S,
+                                                       long long b0, long long nb, double* __restrict__ rows, uint64_t* __restrict__ words) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = r < nb;
+    bool bad = false;
+    if (live) {
+        const unsigned long long g = (unsigned long long)(b0 + r);
+        long long lo = 0, hi = S - 1;                          // the last trajectory whose first sample is <= g
+        while (lo < hi) { const long long mid = (lo + hi + 1) >> 1; if (offs[mid] <= g) lo = mid; else hi = mid - 1; }
+        const double j = (double)(g - offs[lo]);
+        const double t = j < plan[2 * lo + 1] ? j * plan[2 * lo] : 1.0;
+        int a = 0, b = n + K + 1;
+        while (a < b) { const int mid = (a + b) >> 1; if (knots[mid] <= t) a = mid + 1; else b = mid; }
+        const int ell = a - 1 < K ? K : (a - 1 > n - 1 ? n - 1 : a - 1);
+        double al[K * (K + 1) / 2], om[K * (K + 1) / 2];
+        int x = 0;
+#pragma unroll
+        for (int rr = 1; rr <= K; ++rr)
+#pragma unroll
+            for (int jj = K; jj >= rr; --jj, ++x) {
+                const double ta = knots[jj + ell - K];
+                const double den = knots[jj + 1 + ell - rr] - ta;
+                al[x] = den == 0.0 ? 0.0 : (t - ta) / den;
+                om[x] = 1.0 - al[x];
+            }
+        const double* cp = ctrl + ((size_t)lo * (size_t)n + (size_t)(ell - K)) * nq;
+        double* out = rows != nullptr ? rows + (size_t)r * nq : nullptr;
+        for (int c = 0; c < nq; ++c) {
+            double d[K + 1];
+#pragma unroll
+            for (int jj = 0; jj <= K; ++jj) d[jj] = cp[(size_t)jj * nq + c];
+            int y = 0;
+#pragma unroll
+            for (int rr = 1; rr <= K; ++rr)
+#pragma unroll
+                for (int jj = K; jj >= rr; --jj, ++y) { const double u = om[y] * d[jj - 1]; const double v = al[y] * d[jj]; d[jj] = u + v; }
+            if (out != nullptr) out[c] = d[K];
+            bad = bad || !(__builtin_fabs(d[K]) <= 1.7976931348623157e308);
+        }
+    }
+    if (words != nullptr) {
+        const uint64_t word = __builtin_amdgcn_ballot_w64(bad);
+        if ((threadIdx.x & (WAVE - 1)) == 0 && live) words[(b0 + r) >> 6] = word;
+    }
+}
+
+// one wave per trajectory: the first colliding sample in chunks of 64 (ballot), then valid / t_hit / n_samples
+__global__ __launch_bounds__(64) void k_spline_reduce(const double* __restrict__ plan, const unsigned long long* __restrict__ offs,
+                                                     const uint64_t* __restrict__ words, uint8_t* __restrict__ valid,
+                                                     double* __restrict__ t_hit, int32_t* __restrict__ n_samples) {
+    const int64_t s = blockIdx.x;
+    const unsigned long long o = offs[s], n = offs[s + 1] - o;
+    long long first = -1;
+    for (unsigned long long c0 = 0; c0 < n; c0 += WAVE) {
+        const unsigned long long i = c0 + threadIdx.x, b = o + i;
+        const bool hit = i < n && ((words[b >> 6] >> (b & 63)) & 1ull);
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(hit);
+        if (bal != 0ull) { first = (long long)(c0 + (unsigned long long)__builtin_ctzll(bal)); break; }
+    }
+    if (threadIdx.x != 0) return;
+    valid[s] = (n > 0 && first < 0) ? 1 : 0;
+    if (n_samples != nullptr) n_samples[s] = (int32_t)n;
+    if (t_hit != nullptr) {
+        const double j = (double)first;
+        t_hit[s] = first < 0 ? __builtin_nan("") : (j < plan[2 * s + 1] ? j * plan[2 * s] : 1.0);
+    }
 }
 
 // ---- host side --------------------------------------------------------------------------------------
@@ -5325,6 +5443,105 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
                            resolution, max_distance, mode, threshold, valid, (double*)nullptr, (int32_t*)nullptr, (const uint8_t*)ovf, w->stats_dev);
         NBK_HIP(hipGetLastError());
     }
+    return NBK_OK;
+}
+
+// ---- clamped B-spline trajectories: synchronous (one 8-byte read-back of the sample total sizes the mask words and the tiles) ----
+static const int64_t SPLINE_TILE = int64_t(1) << 20;           // q rows written and checked per tile
+static const int32_t SPLINE_MAX_CTRL = 65536;
+
+// the small half of a stream's spline scratch: knots [nk] | plan [S][2] | cnt [S] | offs [S + 1], each part 256-byte aligned
+struct SplineLayout {
+    size_t plan, cnt, offs, bytes;
+    static size_t r256(size_t n) { return (n + 255) & ~size_t(255); }
+    SplineLayout(int nk, int64_t S)
+        : plan(r256((size_t)nk * 8)), cnt(plan + r256((size_t)S * 16)), offs(cnt + r256((size_t)S * 8)), bytes(offs + r256((size_t)(S + 1) * 8)) {}
+};
+
+int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
+                                  double resolution, double threshold, uint8_t* valid, double* t_hit, int32_t* n_samples, void* stream) {
+    if (m == nullptr || S < 0 || knots == nullptr || (S > 0 && (ctrl == nullptr || valid == nullptr))) return NBK_ERR_INVALID;
+    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
+    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308)) return NBK_ERR_INVALID;
+    const int nk = n_ctrl + degree + 1;
+    for (int i = 0; i < nk; ++i) {
+        if (!(fabs(knots[i]) <= 1.7976931348623157e308) || (i > 0 && knots[i] < knots[i - 1])) return NBK_ERR_INVALID;
+    }
+    for (int i = 0; i <= degree; ++i) if (knots[i] != 0.0 || knots[n_ctrl + i] != 1.0) return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    if (S == 0) return NBK_OK;
+    if (S >= (int64_t(1) << 26)) {
+        snprintf(g_err, sizeof(g_err), "spline batch of %lld trajectories (2^26 or more): split the batch", (long long)S);
+        return NBK_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_capturing(st)) {
+        snprintf(g_err, sizeof(g_err), "spline batches read their sample count back to the host and cannot be captured into a graph");
+        return NBK_ERR_UNSUPPORTED;
+    }
+    StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
+    if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces"); return NBK_ERR_ALLOC; }
+    std::lock_guard<std::mutex> lock(w->mu);
+    const SplineLayout L(nk, S);
+    { const int32_t rc = grow_scratch(st, w->sps, w->sps_bytes, L.bytes, "hipMalloc(spline scratch)"); if (rc != NBK_OK) return rc; }
+    char* sp = static_cast<char*>(w->sps);
+    double* kn = reinterpret_cast<double*>(sp);
+    double* plan = reinterpret_cast<double*>(sp + L.plan);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(sp + L.cnt);
+    unsigned long long* offs = reinterpret_cast<unsigned long long*>(sp + L.offs);
+    NBK_HIP(hipMemcpyAsync(kn, knots, (size_t)nk * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, (const double*)kn,
+                       resolution, plan, cnt);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, S, offs);
+    NBK_HIP(hipGetLastError());
+    unsigned long long total = 0;
+    NBK_HIP(hipMemcpyAsync(&total, offs + S, 8, hipMemcpyDeviceToHost, st));
+    NBK_HIP(hipStreamSynchronize(st));
+    if (total >= (1ull << 31)) {
+        snprintf(g_err, sizeof(g_err), "spline batch of %llu samples (2^31 or more): split the batch", total);
+        return NBK_ERR_UNSUPPORTED;
+    }
+    const int64_t T = (int64_t)total;
+    const int64_t tile = std::min<int64_t>((T + WAVE - 1) / WAVE * WAVE, SPLINE_TILE);
+    const bool pairs = m->n_pairs > 0;
+    const size_t words_bytes = ((size_t)(T + 63) / 64 * 8 + 255) & ~size_t(255);
+    const size_t slab_bytes = pairs ? (size_t)tile * (size_t)m->n_q * sizeof(double) : 0;
+    const PairCounts pc = reachable_pairs(m, threshold);
+    if (T > 0) {
+        int32_t rc = grow_scratch(st, w->spl, w->spl_bytes, words_bytes + slab_bytes, "hipMalloc(spline samples)");
+        if (rc != NBK_OK) return rc;
+        if (pairs) {
+            rc = ensure_validity_ws(m, w, (size_t)two_kernel_workspace_bytes(m, pc, tile), st, "hipMalloc(workspace)");
+            if (rc != NBK_OK) return rc;
+        }
+    }
+    uint64_t* words = static_cast<uint64_t*>(w->spl);
+    double* slab = pairs ? reinterpret_cast<double*>(static_cast<char*>(w->spl) + words_bytes) : nullptr;
+    for (int64_t b0 = 0; b0 < T; b0 += tile) {
+        const int64_t nb = std::min<int64_t>(tile, T - b0);
+        const dim3 grid((unsigned)((nb + 255) / 256)), block(256);
+        uint64_t* wx = pairs ? nullptr : words;
+#define NBK_SPLINE_EXPAND(K_) hipLaunchKernelGGL(k_spline_expand<K_>, grid, block, 0, st, m->n_q, ctrl, (int)n_ctrl, (const double*)kn, \
+                                                 (const double*)plan, (const unsigned long long*)offs, S, (long long)b0, (long long)nb, slab, wx)
+        switch (degree) {
+            case 1: NBK_SPLINE_EXPAND(1); break;
+            case 2: NBK_SPLINE_EXPAND(2); break;
+            case 3: NBK_SPLINE_EXPAND(3); break;
+            case 4: NBK_SPLINE_EXPAND(4); break;
+            default: NBK_SPLINE_EXPAND(5); break;
+        }
+#undef NBK_SPLINE_EXPAND
+        NBK_HIP(hipGetLastError());
+        if (pairs) {
+            // the stream's mutex is held: the validity pipeline directly (nbk_validity_batch would take it again); b0 is a multiple of 64
+            const int32_t rc = launch_two_kernel(m, pc, NO_EDGES, slab, nb, threshold, words + b0 / 64, nullptr, w->ws, st, w, false);
+            if (rc != NBK_OK) return rc;
+        }
+    }
+    hipLaunchKernelGGL(k_spline_reduce, dim3((unsigned)S), dim3(WAVE), 0, st, (const double*)plan, (const unsigned long long*)offs,
+                       (const uint64_t*)words, valid, t_hit, n_samples);
+    NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
 

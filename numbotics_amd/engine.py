@@ -403,6 +403,25 @@ class DeviceModel:
             t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_edge_continuous_batch")
         return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
 
+    def spline_validity(self, ctrl, knots, degree, resolution, threshold=0.0):
+        """Sampled check of S clamped B-splines sharing one knot vector (nbk_spline_validity_batch): ctrl (S, n, n_q), knots
+        (host) n + degree + 1 values -> valid (S,) bool, t_hit (S,) (the first colliding sample's t, NaN when valid), n_samples
+        (S,) int32.  Synchronous: the call reads its sample count back."""
+        torch = _require_gpu()
+        shape = tuple(ctrl.shape) if torch.is_tensor(ctrl) else np.shape(ctrl)
+        if len(shape) != 3 or shape[2] != self.n_q:
+            raise ValueError(f"control points must have shape (S, n, {self.n_q}), got {shape}")
+        S, n = int(shape[0]), int(shape[1])
+        kn = _host_f64(knots, n + int(degree) + 1)
+        c = _Staged(ctrl, n * self.n_q, "ctrl")
+        valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
+        t_hit = torch.empty((S,), dtype=torch.float64, device=c.device)
+        ns = torch.empty((S,), dtype=torch.int32, device=c.device)
+        _lib.check(self._lib.nbk_spline_validity_batch(
+            self._h, c.t.data_ptr(), S, n, int(degree), kn.ctypes.data, float(resolution), float(threshold), valid.data_ptr(),
+            t_hit.data_ptr(), ns.data_ptr(), self._stream()), "nbk_spline_validity_batch")
+        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+
 
 def selftest_math(a, b):
     """sincos(a), sqrt(a), a/b as the kernels compute them (arithmetic-contract check)."""

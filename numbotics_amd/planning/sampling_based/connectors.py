@@ -4,6 +4,7 @@
 Additive: when the params carry an ``arm`` (instead of, or next to, a Python ``validity_checker``) the
 whole edge -- every sample ``T = arange(0, T_f, res/d) U {T_f}`` -- is checked by ONE device launch,
 and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per wavefront).
+``validate_trajectories`` / ``validate_trajectory`` check smoothed (clamped B-spline) trajectories sample by sample on the device.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
 certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
 with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.
@@ -14,7 +15,8 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from numbotics_amd.planning import unit_bspline
+from numbotics_amd.planning import unit_bspline, unit_knots
+from numbotics_amd.planning.trajectories import UnitBSpline
 
 _DEFAULT_TRAJ = lambda x, y: unit_bspline(np.array([x, y]))      # noqa: E731
 _DEFAULT_DIST = lambda x, y: np.linalg.norm(x - y)               # noqa: E731
@@ -136,6 +138,46 @@ class DiscreteConnector(Connector):
         have been returned had the edge been free."""
         ok, end, _ = self._batch(starts, goals, "steer", dist)
         return ok, end
+
+    # ---- smoothed trajectories (additive) ----------------------------------------------------------------
+    def _spline_check(self, ctrl, knots, degree):
+        p = self._params
+        _, dev = p.arm._scene_device()
+        return dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
+
+    def _spline_args(self, shape, degree):
+        p = self._params
+        if p.arm is None:
+            raise ValueError("trajectory checks need ConnectorParams(arm=...)")
+        if len(shape) != 3 or shape[2] != p.arm.dof:
+            raise ValueError(f"control points must have shape (S, n, {p.arm.dof}), got {tuple(shape)}")
+        if isinstance(degree, bool) or int(degree) != degree or not 1 <= int(degree) <= 5:
+            raise ValueError("degree must be an integer in 1..5")
+        if shape[1] <= degree:
+            raise ValueError("Degree must be less than the number of control points")
+        return int(degree)
+
+    def validate_trajectories(self, control_points, degree=1):
+        """S clamped B-splines of ``unit_bspline``'s knots, every one sampled at most ``resolution`` apart in joint space and checked
+        on the device (``nbk_spline_validity_batch``): (S, n, dof) -> valid (S,) bool, t_hit (S,) (t of the first colliding
+        sample, NaN when valid), n_samples (S,) int32.  NumPy in, NumPy out; device tensors stay on the device."""
+        shape = tuple(control_points.shape) if hasattr(control_points, "shape") else np.shape(control_points)
+        k = self._spline_args(shape, degree)
+        return self._spline_check(control_points, unit_knots(shape[1], k), k)
+
+    def validate_trajectory(self, spline):
+        """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit)."""
+        if not isinstance(spline, UnitBSpline):
+            raise ValueError("validate_trajectory takes a UnitBSpline (unit_bspline)")
+        c = np.ascontiguousarray(spline.c, dtype=np.float64)
+        k = self._spline_args((1,) + c.shape if c.ndim == 2 else c.shape, spline.k)
+        t = np.asarray(spline.t, dtype=np.float64)
+        n = c.shape[0]
+        if (t.ndim != 1 or t.shape[0] != n + k + 1 or not np.isfinite(t).all() or (np.diff(t) < 0.0).any()
+                or (t[:k + 1] != 0.0).any() or (t[n:] != 1.0).any()):
+            raise ValueError("the spline's knots must be clamped on [0, 1]: nondecreasing, k + 1 zeros first and k + 1 ones last")
+        valid, t_hit, _ = self._spline_check(c[None], t, k)
+        return bool(valid[0]), float(t_hit[0])
 
 
 class ContinuousConnector(Connector):

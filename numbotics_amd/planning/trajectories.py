@@ -33,6 +33,11 @@ class UnitBSpline:
         return d[k]
 
 
+def unit_knots(n: int, degree: int) -> np.ndarray:
+    """The clamped uniform knot vector of ``unit_bspline`` for n control points: n + degree + 1 values."""
+    return np.concatenate((np.zeros(degree), np.linspace(0, 1, n - degree + 1), np.ones(degree)))
+
+
 def unit_bspline(control_points: np.ndarray, degree: int = 1):
     control_points = np.asarray(control_points)
     if control_points.ndim != 2:
@@ -40,5 +45,4 @@ def unit_bspline(control_points: np.ndarray, degree: int = 1):
     B, _ = control_points.shape
     if degree >= B:
         raise ValueError("Degree must be less than the number of control points")
-    knots = np.concatenate((np.zeros(degree), np.linspace(0, 1, B - degree + 1), np.ones(degree)))
-    return UnitBSpline(knots, control_points, degree)
+    return UnitBSpline(unit_knots(B, degree), control_points, degree)

@@ -1,13 +1,16 @@
 """Batched DiscreteConnector edges on c3 (nbk_edge_validity_batch).  With --continuous: also the certified continuous check
 (nbk_edge_continuous_batch) on c2 and c3 at the ContinuousConnector defaults, next to the discrete check at resolutions 0.01 and
-0.001, with the fraction of UNDECIDED edges.  Usage: python tools/edge_time.py [E ...] [--continuous]"""
-import os, sys, numpy as np, torch
+0.001, with the fraction of UNDECIDED edges.  With --spline: S = 1e4 cubic B-splines of 8 control points on c3 at resolution 0.01
+(nbk_spline_validity_batch), the edge batch with the same total sample count, and the latency of S = 1.
+Usage: python tools/edge_time.py [E ...] [--continuous | --spline]"""
+import os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from numbotics_amd.physics import World
 from numbotics_amd.physics.world import _reset_worlds
 from numbotics_amd.scenes import build_scene
 
 cont = "--continuous" in sys.argv
+spline = "--spline" in sys.argv
 sizes = [int(a) for a in sys.argv[1:] if not a.startswith("--")] or ([10000, 100000] if cont else [100000])
 
 
@@ -32,6 +35,47 @@ def timed(fn, reps=3):
     e1.record(); torch.cuda.synchronize()
     return out, e0.elapsed_time(e1) / reps
 
+
+def splines(chain, S, n=8, seed=5):
+    """Smoothings of planner-like paths: n control points along an edge of edges() (|dq| <= pi), each moved by up to 0.1 rad."""
+    s, g = (x.cpu().numpy() for x in edges(chain, S))
+    rng = np.random.default_rng(seed)
+    w = np.linspace(0.0, 1.0, n)[None, :, None]
+    c = (1.0 - w) * s[:, None, :] + w * g[:, None, :] + rng.uniform(-0.1, 0.1, (S, n, s.shape[1]))
+    return torch.from_numpy(c).cuda()
+
+
+if spline:
+    from numbotics_amd.planning import unit_knots
+    _reset_worlds(); World()
+    arm, chain, obs = build_scene("c3")
+    sm, dev = arm._scene_device()
+    S = int(next((a for a in sys.argv[1:] if not a.startswith("--")), 10000))
+    kn = unit_knots(8, 3)
+    tc = splines(chain, S)
+    (ok, th, ns), ms = timed(lambda: dev.spline_validity(tc, kn, 3, 0.01))
+    tot = int(ns.sum().item())
+    print('c3 splines S', S, 'k 3 n 8 res 0.01', 'ms %.3f' % ms, 'samples %.3e' % tot, 'samples/s %.3e' % (tot / ms * 1e3),
+          'valid frac %.3f' % ok.float().mean().item(), flush=True)
+    ts, tg = edges(chain, 100000)
+    per = int(dev.edge_validity(ts, tg, 0.01, np.pi)[2].sum().item()) / 100000
+    E = int(round(tot / per))
+    ts, tg = edges(chain, E)
+    (eok, end, ens), ems = timed(lambda: dev.edge_validity(ts, tg, 0.01, np.pi))
+    etot = int(ens.sum().item())
+    print('c3 edges E', E, 'res 0.01', 'ms %.3f' % ems, 'samples %.3e' % etot, 'samples/s %.3e' % (etot / ems * 1e3),
+          'valid frac %.3f' % eok.float().mean().item(), flush=True)
+    one = tc[:1].clone()
+    for _ in range(20):
+        dev.spline_validity(one, kn, 3, 0.01)
+    torch.cuda.synchronize()
+    reps = 200
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        dev.spline_validity(one, kn, 3, 0.01)
+    torch.cuda.synchronize()
+    print('c3 splines S 1 latency us %.1f' % ((time.perf_counter() - t0) / reps * 1e6), 'samples', int(ns[0].item()), flush=True)
+    sys.exit(0)
 
 for scene in (("c2", "c3") if cont else ("c3",)):
     _reset_worlds(); World()
