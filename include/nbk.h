@@ -23,7 +23,7 @@
  *     reuse tables between calls.  A graph holds the scratch's address: do not replay it after a
  *     direct call on the same stream with a LARGER batch has regrown the scratch (re-capture).  The *_host
  *     conveniences synchronise by definition, and so does nbk_spline_validity_batch (it reads its sample count back; it
- *     refuses a capturing stream).  Batches of 2^21 configurations or more (and edge batches of that many samples)
+ *     refuses a capturing stream; nbk_spline_continuous_batch does not).  Batches of 2^21 configurations or more (and edge batches of that many samples)
  *     run every other 2^20-configuration tile on a second, library-owned stream forked from and joined to `stream` with
  *     events -- the call still begins after, and completes before, its neighbours in `stream`'s order;
  *   - every compute call must be made with the descriptor's device current (hipSetDevice):
@@ -319,6 +319,47 @@ int32_t nbk_edge_motion_bounds_host(const nbk_model_desc *desc, const double *st
 int32_t nbk_spline_validity_batch(const nbk_model *m, const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                   const double *knots /* host [n_ctrl + degree + 1] */, double resolution, double threshold,
                                   uint8_t *valid, double *t_hit /* optional */, int32_t *n_samples /* optional */, void *stream);
+
+/*
+ * Certified continuous check of clamped B-spline trajectories: the loop of nbk_edge_continuous_batch on the spline of
+ * nbk_spline_validity_batch, so that a smoothed plan keeps the certificate its raw edges had.
+ *   ctrl (device) [S][n_ctrl][n_q], degree k and the knots tau [n_ctrl + k + 1] as nbk_spline_validity_batch, except that the knots
+ *   are a DEVICE array (the call reads nothing back).  One (trajectory, pair) item per lane, pair-major; each item starts at t = 0
+ *   and makes at most max_iter distance evaluations:
+ *     d = signed distance of the pair at q(t) (the bits of nbk_pair_records_items), q(t) by de Boor with the span rule and the
+ *       operation order of nbk_spline_validity_batch step 4;
+ *     d <= threshold: COLLISION at t;  gap = (d - threshold) - slack <= 0 (or NaN): UNDECIDED at t;
+ *     else t advances across spans, spending gap: in span ell (the span of t) with hi = tau[ell + 1] and mu = mu[ell]
+ *       (nbk_spline_motion_bounds_host): mu == 0: t = hi;  else tn = t + gap / mu; unless tn >= hi: t = tn and the advance ends;
+ *       else gap = gap - mu * (hi - t) (two roundings) and t = hi.  Once t >= 1 the item stops FREE at 1; else when !(gap > 0) the
+ *       advance ends; else it goes on in the span of the new t.  Crossing a span costs no distance evaluation;
+ *   and stops UNDECIDED at t when the iterations run out.  An item also stops, without a say in the result, once its t passes the
+ *   trajectory's current smallest stop point.  Per trajectory: t_free = the smallest stop point over the pairs; status NBK_CA_* =
+ *   FREE when every pair is FREE, else the status of the pair that stops at t_free (COLLISION before UNDECIDED on a tie); valid =
+ *   status == FREE.  valid [S] uint8; t_free [S] double (also the per-trajectory accumulator while the call runs); status [S] int32.
+ * Degenerate (DEGENERATE, invalid, t_free NaN): V outside (2^-23, DBL_MAX] (nbk_spline_validity_batch steps 1-2), a non-finite
+ * control point, or -- for every trajectory -- knots that are not finite, nondecreasing and clamped on [0, 1] (checked on the
+ * device).  A descriptor without pairs reports every other trajectory FREE at 1.  With n_ctrl = 2, k = 1, tau = [0, 0, 1, 1] this
+ * is nbk_edge_continuous_batch in connect mode with dist = NULL, bit for bit.  NBK_ERR_INVALID for max_iter < 1, slack < 0, a NaN
+ * slack / threshold, degree outside 1 .. NBK_MAX_SPLINE_DEGREE, n_ctrl <= degree or > 65536, and null pointers; S = 0 returns
+ * NBK_OK at once.  Asynchronous and capturable: no allocation, no host synchronisation, three kernels on `stream`; nothing is
+ * parked in LDS, so every descriptor is served.
+ */
+int32_t nbk_spline_continuous_batch(const nbk_model *m, const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                    const double *knots /* DEVICE, n_ctrl + degree + 1 */, double threshold,
+                                    int32_t max_iter, double slack, uint8_t *valid, double *t_free, int32_t *status,
+                                    void *stream);
+/*
+ * The motion bounds mu [S][n_ctrl - degree][P] (span ell at index ell - degree, user pair order) that nbk_spline_continuous_batch
+ * advances with, computed on the host by the same routine (no GPU needed).  ctrl, knots (host); the knots must pass the rules of
+ * nbk_spline_validity_batch (NBK_ERR_INVALID otherwise).  On a non-empty span ell (tau[ell] < tau[ell+1]), with
+ *   V_j = max_{i = ell-k .. ell-1} ((double)k * |c_{i+1} - c_i|_j) / (tau[i+k+1] - tau[i+1])   (three roundings per term)
+ *   A_j = max_{i = ell-k .. ell} |c_i|_j,
+ * mu is the formula of nbk_edge_motion_bounds_host with |g - s|_j replaced by V_j and the prismatic travel max(|s|, |g|)_j by A_j;
+ * then |d_p(t) - d_p(t')| <= mu |t - t'| on the span.  Entries of empty spans are 0 (never used).
+ */
+int32_t nbk_spline_motion_bounds_host(const nbk_model_desc *desc, const double *ctrl /* host */, int64_t S, int32_t n_ctrl,
+                                      int32_t degree, const double *knots /* host */, double *mu /* [S][n_ctrl-degree][P] */);
 
 /*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libnbk.so")
 
 NBK_OK = 0
-# status codes of nbk_edge_continuous_batch (NBK_CA_*)
+# status codes of nbk_edge_continuous_batch / nbk_spline_continuous_batch (NBK_CA_*)
 CA_FREE, CA_COLLISION, CA_UNDECIDED, CA_DEGENERATE = 0, 1, 2, 3
 STATUS = {0: "NBK_OK", -1: "NBK_ERR_INVALID", -2: "NBK_ERR_NO_DEVICE", -3: "NBK_ERR_HIP",
           -4: "NBK_ERR_UNSUPPORTED", -5: "NBK_ERR_ALLOC"}
@@ -26,6 +26,7 @@ SYMBOLS = [
     "nbk_edge_continuous_batch", "nbk_edge_motion_bounds_host", "nbk_selftest_math",
     "nbk_fk_batch_host", "nbk_validity_batch_host", "nbk_knn_prefix",
     "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host", "nbk_spline_validity_batch",
+    "nbk_spline_continuous_batch", "nbk_spline_motion_bounds_host",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -98,6 +99,8 @@ def load():
     lib.nbk_edge_continuous_batch.argtypes = [vp, vp, vp, vp, i64, f64, i32, f64, i32, f64, vp, vp, vp, vp, vp]
     lib.nbk_spline_validity_batch.argtypes = [vp, vp, i64, i32, i32, vp, f64, f64, vp, vp, vp, vp]
     lib.nbk_edge_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, vp, i64, vp]
+    lib.nbk_spline_continuous_batch.argtypes = [vp, vp, i64, i32, i32, vp, f64, i32, f64, vp, vp, vp, vp]
+    lib.nbk_spline_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, i64, i32, i32, vp, vp]
     lib.nbk_selftest_math.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     lib.nbk_knn_prefix.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.nbk_fk_batch_host.argtypes = [vp, vp, i64, vp, i32, vp, vp]

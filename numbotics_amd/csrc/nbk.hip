@@ -3673,10 +3673,72 @@ __global__ void k_edge_ca_init(int nq, const double* __restrict__ starts, const 
     write_edge_end(nq, s, g, e, mode, Tf, end);
 }
 
+// One (trajectory, pair) item per lane: the conservative-advancement loop of nbk_edge_continuous_batch and
+// nbk_spline_continuous_batch, on the trajectory TR (EdgeLane, SplineLane<K>).  TR supplies the stop point T_f (end), the end of the
+// current knot span (span_end; an edge is one span ending at T_f), the span's motion bound on entering the span of t (enter) and
+// the pair's distance at q(t) (distance).  The loop runs while any lane of the wave runs, every lane calling item_distance (those
+// that stopped replay nothing).  An advance spends gap = (d - thr) - slack across spans: within a span t moves by gap / mu; a span
+// it crosses costs mu (hi - t) of the gap and no distance evaluation.  An item also stops, without a say in the result, once its t
+// exceeds the trajectory's current smallest stop point: its own stop point (>= t) can then be neither the minimum nor tied with it.
+template <class TR>
+NBK_DEV void ca_walk(const DevModel& m, TR& tr, bool run, int pu, int p, int lane, double thr, int max_iter, double slack,
+                     unsigned long long* __restrict__ key) {
+    double mu = run ? tr.enter(m, pu, 0.0) : 0.0;
+    const double Tf = tr.end();
+    double t = 0.0;
+    int it = 0;
+    unsigned long long rank = CA_UNDECIDED;
+    bool post = false;
+    while (__builtin_amdgcn_ballot_w64(run) != 0ull) {
+        if (run) {
+            if (it == max_iter) { rank = CA_UNDECIDED; post = true; run = false; }
+            else if (ca_key(t, 0ull) > __hip_atomic_load(key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) run = false;
+        }
+        double wit[9];
+        const double d = tr.distance(m, run, p, lane, t, wit);
+        if (run) {
+            ++it;
+            if (d <= thr) { rank = CA_COLLISION; post = true; run = false; }
+            else {
+                double gap = (d - thr) - slack;
+                if (!(gap > 0.0)) { rank = CA_UNDECIDED; post = true; run = false; }
+                else for (;;) {
+                    const double hi = tr.span_end();
+                    if (mu == 0.0) t = hi;
+                    else {
+                        const double tn = t + gap / mu;
+                        if (!(tn >= hi)) { t = tn; break; }
+                        const double used = mu * (hi - t);
+                        gap = gap - used;
+                        t = hi;
+                    }
+                    if (t >= Tf) { t = Tf; rank = CA_FREE; post = true; run = false; break; }
+                    mu = tr.enter(m, pu, t);
+                    if (!(gap > 0.0)) break;
+                }
+            }
+        }
+    }
+    if (post) atomicMin(key, ca_key(t, rank));
+}
+
+// the linear edge q(t) = (1-t) s + t g on [0, T_f], one span: q(t) in three roundings, mu from the edge's motion bound
+struct EdgeLane {
+    const double* s;
+    const double* g;
+    double Tf;
+    NBK_DEV double end() const { return Tf; }
+    NBK_DEV double span_end() const { return Tf; }
+    NBK_DEV double enter(const DevModel& m, int pu, double) const { return pair_motion_bound(m.mt, pu, EdgeMotion{s, g}); }
+    NBK_DEV double distance(const DevModel& m, bool run, int p, int lane, double t, double* wit) const {
+        const double omt = 1.0 - t;
+        return item_distance(m, [&](int c) { const double a = omt * s[c]; const double b = t * g[c]; return a + b; }, run, p, lane,
+                             nullptr, wit);
+    }
+};
+
 // item i = (user pair pu = i / E, edge e = i % E): pair-major, so a wave holds one pair (the hull support's scalar-cache path) unless
-// it straddles two.  The loop runs while any lane of the wave runs, every lane calling item_distance (those that stopped replay
-// nothing).  An item also stops, without a say in the result, once its t exceeds the edge's current smallest stop point: its own
-// stop point (>= t) can then be neither the minimum nor tied with it.
+// it straddles two
 __global__ __launch_bounds__(64) void k_edge_ca(DevModel m, const double* __restrict__ starts, const double* __restrict__ goals,
                                                 const double* __restrict__ dist, int64_t E, double max_distance, int mode, double thr,
                                                 int max_iter, double slack, unsigned long long* __restrict__ key) {
@@ -3686,40 +3748,10 @@ __global__ __launch_bounds__(64) void k_edge_ca(DevModel m, const double* __rest
     const int pu = live ? (int)(i / E) : 0;
     const int64_t e = live ? i - (int64_t)pu * E : 0;
     const int p = live ? m.pair_dev[pu] : 0;
-    const double* s = starts + e * m.n_q;
-    const double* g = goals + e * m.n_q;
-    double d_edge = 0.0, Tf = 0.0;
-    bool run = live && edge_span(m.n_q, s, g, dist, e, max_distance, mode, d_edge, Tf);
-    const double mu = run ? pair_motion_bound(m.mt, pu, s, g) : 0.0;
-    double t = 0.0;
-    int it = 0;
-    unsigned long long rank = CA_UNDECIDED;
-    bool post = false;
-    while (__builtin_amdgcn_ballot_w64(run) != 0ull) {
-        if (run) {
-            if (it == max_iter) { rank = CA_UNDECIDED; post = true; run = false; }
-            else if (ca_key(t, 0ull) > __hip_atomic_load(key + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) run = false;
-        }
-        const double omt = 1.0 - t;
-        double wit[9];
-        const double d = item_distance(m, [&](int c) { const double a = omt * s[c]; const double b = t * g[c]; return a + b; },
-                                       run, p, lane, nullptr, wit);
-        if (run) {
-            ++it;
-            if (d <= thr) { rank = CA_COLLISION; post = true; run = false; }
-            else {
-                const double gap = (d - thr) - slack;
-                if (!(gap > 0.0)) { rank = CA_UNDECIDED; post = true; run = false; }
-                else if (mu == 0.0) { t = Tf; rank = CA_FREE; post = true; run = false; }
-                else {
-                    const double tn = t + gap / mu;
-                    if (tn >= Tf) { t = Tf; rank = CA_FREE; post = true; run = false; }
-                    else t = tn;
-                }
-            }
-        }
-    }
-    if (post) atomicMin(key + e, ca_key(t, rank));
+    EdgeLane tr{starts + e * m.n_q, goals + e * m.n_q, 0.0};
+    double d_edge = 0.0;
+    const bool run = live && edge_span(m.n_q, tr.s, tr.g, dist, e, max_distance, mode, d_edge, tr.Tf);
+    ca_walk(m, tr, run, pu, p, lane, thr, max_iter, slack, key + e);
 }
 
 __global__ void k_edge_ca_final(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
@@ -3796,13 +3828,9 @@ __global__ __launch_bounds__(64) void k_edge_reduce(const unsigned long long* __
 constexpr double SPLINE_MIN_SPEED = 1.1920928955078125e-07;        // 2^-23: the degenerate-edge rule with d := V
 constexpr unsigned long long SPLINE_TOO_MANY = 1ull << 32;          // a count that stands for "more than the host accepts"
 
-// one wave per trajectory: V = max_i v_i (NaN when any v_i is NaN), step = resolution / V, m = ceil(1 / step); plan[s] = (step, m),
-// cnt[s] = m + 1 samples, 0 for a degenerate trajectory (V outside (2^-23, DBL_MAX])
-__global__ __launch_bounds__(64) void k_spline_plan(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
-                                                   double resolution, double* __restrict__ plan, unsigned long long* __restrict__ cnt) {
-    const int64_t s = blockIdx.x;
-    const int lane = threadIdx.x;
-    const double* c = ctrl + (size_t)s * (size_t)n * nq;
+// V = max_i v_i of trajectory c over one wave (NaN when any v_i is NaN), the same in every lane; k_spline_plan and
+// k_spline_ca_init share it
+NBK_DEV double spline_speed_bound(int nq, const double* c, int n, int k, const double* knots, int lane) {
     double vmax = 0.0;
     bool nan = false;
     for (int i = lane; i < n - 1; i += WAVE) {
@@ -3814,9 +3842,20 @@ __global__ __launch_bounds__(64) void k_spline_plan(int nq, const double* __rest
     }
     for (int o = WAVE / 2; o > 0; o >>= 1) { const double x = __shfl_xor(vmax, o); vmax = x > vmax ? x : vmax; }
     if (__builtin_amdgcn_ballot_w64(nan) != 0ull) vmax = __builtin_nan("");
+    return vmax;
+}
+
+NBK_DEV bool spline_degenerate(double V) { return !(V > SPLINE_MIN_SPEED && V <= 1.7976931348623157e308); }
+
+// one wave per trajectory: V (spline_speed_bound), step = resolution / V, m = ceil(1 / step); plan[s] = (step, m),
+// cnt[s] = m + 1 samples, 0 for a degenerate trajectory (V outside (2^-23, DBL_MAX])
+__global__ __launch_bounds__(64) void k_spline_plan(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
+                                                   double resolution, double* __restrict__ plan, unsigned long long* __restrict__ cnt) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double V = spline_speed_bound(nq, ctrl + (size_t)s * (size_t)n * nq, n, k, knots, lane);
     if (lane != 0) return;
-    const double V = vmax;
-    if (!(V > SPLINE_MIN_SPEED && V <= 1.7976931348623157e308)) { plan[2 * s] = 0.0; plan[2 * s + 1] = 0.0; cnt[s] = 0ull; return; }
+    if (spline_degenerate(V)) { plan[2 * s] = 0.0; plan[2 * s + 1] = 0.0; cnt[s] = 0ull; return; }
     const double step = resolution / V;
     const double mf = __builtin_ceil(1.0 / step);
     if (!(mf < 4294967296.0)) { plan[2 * s] = step; plan[2 * s + 1] = 0.0; cnt[s] = SPLINE_TOO_MANY; return; }
@@ -3825,10 +3864,45 @@ __global__ __launch_bounds__(64) void k_spline_plan(int nq, const double* __rest
     cnt[s] = m + 1ull;
 }
 
-// one thread per row r of the tile (flat sample b0 + r): trajectory by binary search over the offsets, t_j, then the general branch
-// of UnitBSpline.__call__ one joint at a time -- span ell = (knots <= t) - 1 clamped to [K, n-1], de Boor with
-// d[j] = (1 - alpha) * d[j-1] + alpha * d[j] in four roundings (the alphas depend on t only: computed once).  `words` (descriptors
-// without pairs, rows == nullptr): the verdict is the row's finiteness, one mask word per wave (b0 and the block are multiples of 64)
+// the general branch of UnitBSpline.__call__: span ell = (knots <= t) - 1 clamped to [K, n-1]
+template <int K>
+NBK_DEV int spline_span(const double* knots, int n, double t) {
+    int a = 0, b = n + K + 1;
+    while (a < b) { const int mid = (a + b) >> 1; if (knots[mid] <= t) a = mid + 1; else b = mid; }
+    return a - 1 < K ? K : (a - 1 > n - 1 ? n - 1 : a - 1);
+}
+
+// q(t) on span ell one joint at a time, put(c, q_c): de Boor with d[j] = (1 - alpha) * d[j-1] + alpha * d[j] in four roundings (the
+// alphas depend on t only: computed once).  cp = control point ell - K, row stride nq.  k_spline_expand and k_spline_ca share it.
+template <int K, class PUT>
+NBK_DEV void de_boor(int nq, const double* cp, const double* knots, int ell, double t, const PUT& put) {
+    double al[K * (K + 1) / 2], om[K * (K + 1) / 2];
+    int x = 0;
+#pragma unroll
+    for (int rr = 1; rr <= K; ++rr)
+#pragma unroll
+        for (int jj = K; jj >= rr; --jj, ++x) {
+            const double ta = knots[jj + ell - K];
+            const double den = knots[jj + 1 + ell - rr] - ta;
+            al[x] = den == 0.0 ? 0.0 : (t - ta) / den;
+            om[x] = 1.0 - al[x];
+        }
+    for (int c = 0; c < nq; ++c) {
+        double d[K + 1];
+#pragma unroll
+        for (int jj = 0; jj <= K; ++jj) d[jj] = cp[(size_t)jj * nq + c];
+        int y = 0;
+#pragma unroll
+        for (int rr = 1; rr <= K; ++rr)
+#pragma unroll
+            for (int jj = K; jj >= rr; --jj, ++y) { const double u = om[y] * d[jj - 1]; const double v = al[y] * d[jj]; d[jj] = u + v; }
+        put(c, d[K]);
+    }
+}
+
+// one thread per row r of the tile (flat sample b0 + r): trajectory by binary search over the offsets, t_j, then spline_span and
+// de_boor.  `words` (descriptors without pairs, rows == nullptr): the verdict is the row's finiteness, one mask word per wave (b0
+// and the block are multiples of 64)
 template <int K>
 __global__ __launch_bounds__(256) void k_spline_expand(int nq, const double* __restrict__ ctrl, int n, const double* __restrict__ knots,
                                                        const double* __restrict__ plan, const unsigned long long* __restrict__ offs, int64_t S,
@@ -3842,34 +3916,13 @@ __global__ __launch_bounds__(256) void k_spline_expand(int nq, const double* __r
         while (lo < hi) { const long long mid = (lo + hi + 1) >> 1; if (offs[mid] <= g) lo = mid; else hi = mid - 1; }
         const double j = (double)(g - offs[lo]);
         const double t = j < plan[2 * lo + 1] ? j * plan[2 * lo] : 1.0;
-        int a = 0, b = n + K + 1;
-        while (a < b) { const int mid = (a + b) >> 1; if (knots[mid] <= t) a = mid + 1; else b = mid; }
-        const int ell = a - 1 < K ? K : (a - 1 > n - 1 ? n - 1 : a - 1);
-        double al[K * (K + 1) / 2], om[K * (K + 1) / 2];
-        int x = 0;
-#pragma unroll
-        for (int rr = 1; rr <= K; ++rr)
-#pragma unroll
-            for (int jj = K; jj >= rr; --jj, ++x) {
-                const double ta = knots[jj + ell - K];
-                const double den = knots[jj + 1 + ell - rr] - ta;
-                al[x] = den == 0.0 ? 0.0 : (t - ta) / den;
-                om[x] = 1.0 - al[x];
-            }
+        const int ell = spline_span<K>(knots, n, t);
         const double* cp = ctrl + ((size_t)lo * (size_t)n + (size_t)(ell - K)) * nq;
         double* out = rows != nullptr ? rows + (size_t)r * nq : nullptr;
-        for (int c = 0; c < nq; ++c) {
-            double d[K + 1];
-#pragma unroll
-            for (int jj = 0; jj <= K; ++jj) d[jj] = cp[(size_t)jj * nq + c];
-            int y = 0;
-#pragma unroll
-            for (int rr = 1; rr <= K; ++rr)
-#pragma unroll
-                for (int jj = K; jj >= rr; --jj, ++y) { const double u = om[y] * d[jj - 1]; const double v = al[y] * d[jj]; d[jj] = u + v; }
-            if (out != nullptr) out[c] = d[K];
-            bad = bad || !(__builtin_fabs(d[K]) <= 1.7976931348623157e308);
-        }
+        de_boor<K>(nq, cp, knots, ell, t, [&](int c, double v) {
+            if (out != nullptr) out[c] = v;
+            bad = bad || !(__builtin_fabs(v) <= 1.7976931348623157e308);
+        });
     }
     if (words != nullptr) {
         const uint64_t word = __builtin_amdgcn_ballot_w64(bad);
@@ -3897,6 +3950,83 @@ __global__ __launch_bounds__(64) void k_spline_reduce(const double* __restrict__
         const double j = (double)first;
         t_hit[s] = first < 0 ? __builtin_nan("") : (j < plan[2 * s + 1] ? j * plan[2 * s] : 1.0);
     }
+}
+
+// ==== certified continuous B-splines (nbk_spline_continuous_batch): ca_walk on SplineLane<K>, keys as the edge path's ==============
+// A degenerate trajectory (V outside (2^-23, DBL_MAX], a non-finite control point, or knots that are not finite, nondecreasing and
+// clamped on [0, 1]) gets the key CA_DEGENERATE_KEY (rank 3, which no item posts): no item of it runs, and the final kernel reads
+// DEGENERATE from the key alone.
+constexpr unsigned long long CA_DEGENERATE_KEY = 3ull;
+
+// one wave per trajectory: key[s] = "FREE at 1", or CA_DEGENERATE_KEY
+__global__ __launch_bounds__(64) void k_spline_ca_init(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
+                                                      unsigned long long* __restrict__ key) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double* c = ctrl + (size_t)s * (size_t)n * nq;
+    bool bad = false;
+    for (int i = lane; i < n + k + 1; i += WAVE) {
+        const double x = knots[i];
+        bad = bad || !(__builtin_fabs(x) <= 1.7976931348623157e308) || (i > 0 && x < knots[i - 1]) || (i <= k && x != 0.0) ||
+              (i >= n && x != 1.0);
+    }
+    for (size_t i = lane; i < (size_t)n * nq; i += WAVE) bad = bad || !(__builtin_fabs(c[i]) <= 1.7976931348623157e308);
+    const bool deg = __builtin_amdgcn_ballot_w64(bad) != 0ull;
+    const double V = spline_speed_bound(nq, c, n, k, knots, lane);
+    if (lane == 0) key[s] = (deg || spline_degenerate(V)) ? CA_DEGENERATE_KEY : ca_key(1.0, CA_FREE);
+}
+
+// trajectory s of degree K on [0, 1]: spans of the shared knots; entering the span of t finds it (spline_span) and bounds the pair's
+// motion on it (SplineSpanMotion); q(t) is written by de_boor into the lane's LDS row, which item_distance reads -- no de Boor
+// state is live across the distance
+template <int K>
+struct SplineLane {
+    const double* c;            // control points of the trajectory, [n][nq]
+    const double* knots;
+    double* row;                // LDS [nq]
+    int n, nq, ell;
+    NBK_DEV double end() const { return 1.0; }
+    NBK_DEV double span_end() const { return knots[ell + 1]; }
+    NBK_DEV double enter(const DevModel& m, int pu, double t) {
+        ell = spline_span<K>(knots, n, t);
+        return pair_motion_bound(m.mt, pu, SplineSpanMotion{c + (size_t)(ell - K) * nq, knots + (ell - K + 1), nq, K});
+    }
+    NBK_DEV double distance(const DevModel& m, bool run, int p, int lane, double t, double* wit) const {
+        if (run) {
+            double* r = row;
+            de_boor<K>(nq, c + (size_t)(ell - K) * nq, knots, ell, t, [&](int j, double v) { r[j] = v; });
+        }
+        return item_distance(m, [&](int j) { return row[j]; }, run, p, lane, nullptr, wit);
+    }
+};
+
+// item i = (user pair pu = i / S, trajectory s = i % S), pair-major as k_edge_ca.  LDS: [64][n_q] q rows.
+template <int K>
+__global__ __launch_bounds__(64) void k_spline_ca(DevModel m, const double* __restrict__ ctrl, int64_t S, int n,
+                                                  const double* __restrict__ knots, double thr, int max_iter, double slack,
+                                                  unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < S * (int64_t)m.n_pairs;
+    const int pu = live ? (int)(i / S) : 0;
+    const int64_t s = live ? i - (int64_t)pu * S : 0;
+    const int p = live ? m.pair_dev[pu] : 0;
+    SplineLane<K> tr{ctrl + (size_t)s * (size_t)n * m.n_q, knots, lds + lane * m.n_q, n, m.n_q, K};
+    const bool run = live && key[s] != CA_DEGENERATE_KEY;
+    ca_walk(m, tr, run, pu, p, lane, thr, max_iter, slack, key + s);
+}
+
+__global__ void k_spline_ca_final(int64_t S, const unsigned long long* __restrict__ key, uint8_t* __restrict__ valid,
+                                  double* __restrict__ t_free, int32_t* __restrict__ status) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const unsigned long long k = key[s];          // t_free aliases key: read before the write
+    const unsigned long long r = k & 3ull;
+    if (k == CA_DEGENERATE_KEY) { valid[s] = 0; t_free[s] = __builtin_nan(""); status[s] = NBK_CA_DEGENERATE; return; }
+    valid[s] = r == CA_FREE ? 1 : 0;
+    status[s] = r == CA_FREE ? NBK_CA_FREE : (r == CA_COLLISION ? NBK_CA_COLLISION : NBK_CA_UNDECIDED);
+    t_free[s] = __builtin_bit_cast(double, k >> 2);
 }
 
 // ---- host side --------------------------------------------------------------------------------------
@@ -5281,8 +5411,9 @@ int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, cons
     return NBK_OK;
 }
 
-int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* starts, const double* goals, int64_t E, double* mu) {
-    if (d == nullptr || E < 0) return NBK_ERR_INVALID;
+// the descriptor checks of the *_motion_bounds_host entries: the parts MotionTab reads
+static int32_t motion_desc_check(const nbk_model_desc* d) {
+    if (d == nullptr) return NBK_ERR_INVALID;
     const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
     if (d->n_q < 0 || J < 0 || S < 0 || W < 0 || P < 0 || d->n_hulls < 0) return NBK_ERR_INVALID;
     if (J > NBK_MAX_JOINTS || d->n_q > NBK_MAX_DOF) return NBK_ERR_UNSUPPORTED;
@@ -5310,14 +5441,54 @@ int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* start
     }
     for (int p = 0; p < P; ++p)
         if (d->pair_a[p] < 0 || d->pair_a[p] >= S || d->pair_b[p] < 0 || d->pair_b[p] >= S + W) return NBK_ERR_INVALID;
+    return NBK_OK;
+}
+
+int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* starts, const double* goals, int64_t E, double* mu) {
+    if (d == nullptr || E < 0) return NBK_ERR_INVALID;
+    { const int32_t rc = motion_desc_check(d); if (rc != NBK_OK) return rc; }
+    const int P = d->n_pairs;
     if (E == 0 || P == 0) return NBK_OK;
     if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
     MotionHost h;
     motion_tables(d, h);
-    const MotionTab t = h.view(J, S);
+    const MotionTab t = h.view(d->n_joints, d->n_rshapes);
     for (int64_t e = 0; e < E; ++e)
         for (int p = 0; p < P; ++p)
-            mu[e * P + p] = pair_motion_bound(t, p, starts + e * d->n_q, goals + e * d->n_q);
+            mu[e * P + p] = pair_motion_bound(t, p, EdgeMotion{starts + e * d->n_q, goals + e * d->n_q});
+    return NBK_OK;
+}
+
+static const int32_t SPLINE_MAX_CTRL = 65536;
+
+// the knot rules of both spline entries: finite, nondecreasing, clamped on [0, 1]
+static bool spline_knots_ok(const double* knots, int n, int k) {
+    for (int i = 0; i < n + k + 1; ++i)
+        if (!(fabs(knots[i]) <= 1.7976931348623157e308) || (i > 0 && knots[i] < knots[i - 1])) return false;
+    for (int i = 0; i <= k; ++i) if (knots[i] != 0.0 || knots[n + i] != 1.0) return false;
+    return true;
+}
+
+int32_t nbk_spline_motion_bounds_host(const nbk_model_desc* d, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                      const double* knots, double* mu) {
+    if (d == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
+    { const int32_t rc = motion_desc_check(d); if (rc != NBK_OK) return rc; }
+    const int P = d->n_pairs, nq = d->n_q, k = degree, L = n_ctrl - degree;
+    if (S == 0 || P == 0) return NBK_OK;
+    if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_knots_ok(knots, n_ctrl, k)) return NBK_ERR_INVALID;
+    MotionHost h;
+    motion_tables(d, h);
+    const MotionTab t = h.view(d->n_joints, d->n_rshapes);
+    for (int64_t s = 0; s < S; ++s) {
+        const double* c = ctrl + (size_t)s * (size_t)n_ctrl * nq;
+        for (int ell = k; ell < n_ctrl; ++ell) {
+            double* out = mu + ((size_t)s * L + (size_t)(ell - k)) * P;
+            const bool span = knots[ell] < knots[ell + 1];
+            const SplineSpanMotion tr{c + (size_t)(ell - k) * nq, knots + (ell - k + 1), nq, k};
+            for (int p = 0; p < P; ++p) out[p] = span ? pair_motion_bound(t, p, tr) : 0.0;
+        }
+    }
     return NBK_OK;
 }
 
@@ -5448,8 +5619,6 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
 
 // ---- clamped B-spline trajectories: synchronous (one 8-byte read-back of the sample total sizes the mask words and the tiles) ----
 static const int64_t SPLINE_TILE = int64_t(1) << 20;           // q rows written and checked per tile
-static const int32_t SPLINE_MAX_CTRL = 65536;
-
 // the small half of a stream's spline scratch: knots [nk] | plan [S][2] | cnt [S] | offs [S + 1], each part 256-byte aligned
 struct SplineLayout {
     size_t plan, cnt, offs, bytes;
@@ -5464,10 +5633,7 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
     if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
     if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308)) return NBK_ERR_INVALID;
     const int nk = n_ctrl + degree + 1;
-    for (int i = 0; i < nk; ++i) {
-        if (!(fabs(knots[i]) <= 1.7976931348623157e308) || (i > 0 && knots[i] < knots[i - 1])) return NBK_ERR_INVALID;
-    }
-    for (int i = 0; i <= degree; ++i) if (knots[i] != 0.0 || knots[n_ctrl + i] != 1.0) return NBK_ERR_INVALID;
+    if (!spline_knots_ok(knots, n_ctrl, degree)) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     if (S == 0) return NBK_OK;
     if (S >= (int64_t(1) << 26)) {
@@ -5541,6 +5707,44 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
     }
     hipLaunchKernelGGL(k_spline_reduce, dim3((unsigned)S), dim3(WAVE), 0, st, (const double*)plan, (const unsigned long long*)offs,
                        (const uint64_t*)words, valid, t_hit, n_samples);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// ---- certified continuous B-splines: asynchronous and capturable (knots on the device, nothing read back, nothing allocated) ----
+int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
+                                    double threshold, int32_t max_iter, double slack, uint8_t* valid, double* t_free, int32_t* status,
+                                    void* stream) {
+    if (m == nullptr || S < 0 || knots == nullptr ||
+        (S > 0 && (ctrl == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)))
+        return NBK_ERR_INVALID;
+    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
+    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    if (S == 0) return NBK_OK;
+    const int64_t N = S * (int64_t)m->n_pairs;
+    if (S > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* key = reinterpret_cast<unsigned long long*>(t_free);
+    hipLaunchKernelGGL(k_spline_ca_init, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, key);
+    NBK_HIP(hipGetLastError());
+    if (N > 0) {
+        const dim3 grid((unsigned)((N + WAVE - 1) / WAVE)), block(WAVE);
+        const size_t lds = sizeof(double) * WAVE * (size_t)(m->n_q > 0 ? m->n_q : 1);
+#define NBK_SPLINE_CA(K_) hipLaunchKernelGGL(k_spline_ca<K_>, grid, block, lds, st, m->d, ctrl, S, (int)n_ctrl, knots, threshold, \
+                                             (int)max_iter, slack, key)
+        switch (degree) {
+            case 1: NBK_SPLINE_CA(1); break;
+            case 2: NBK_SPLINE_CA(2); break;
+            case 3: NBK_SPLINE_CA(3); break;
+            case 4: NBK_SPLINE_CA(4); break;
+            default: NBK_SPLINE_CA(5); break;
+        }
+#undef NBK_SPLINE_CA
+        NBK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_spline_ca_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const unsigned long long*)key, valid,
+                       t_free, status);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

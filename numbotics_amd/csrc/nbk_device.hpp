@@ -1361,40 +1361,78 @@ struct MotionTab {
 __host__ __device__ inline double motion_abs(double x) { return x < 0.0 ? -x : x; }
 
 // c_{x,j} of a revolute joint j on shape x's path: joints k below j on that path (joint index ascending), their translation and,
-// for a prismatic k, its largest travel on the edge; then the shape's local offset and its bounding radius plus margin
-__host__ __device__ inline double motion_reach(const MotionTab& t, int x, int j, const double* s, const double* g) {
+// for a prismatic k, its largest travel on the trajectory (tr.travel); then the shape's local offset and its bounding radius plus
+// margin.  TR is the trajectory's per-joint speed / travel (EdgeMotion, SplineSpanMotion): a template, not a branch on the caller.
+template <class TR>
+__host__ __device__ inline double motion_reach(const MotionTab& t, int x, int j, const TR& tr) {
     const unsigned mx = t.smask[x];
     double c = 0.0;
     for (int k = j + 1; k < t.n_joints; ++k) {
         if (!((mx >> k) & 1u)) continue;
         c = c + t.jtn[k];
-        if (t.jtype[k] == NBK_PRISMATIC) {
-            const int qk = t.jqidx[k];
-            const double as = motion_abs(s[qk]), ag = motion_abs(g[qk]);
-            c = c + t.jsn[k] * (as > ag ? as : ag);
-        }
+        if (t.jtype[k] == NBK_PRISMATIC) c = c + t.jsn[k] * tr.travel(t.jqidx[k]);
     }
     c = c + t.sloc[x];
     return c + t.sbnd[x];
 }
 
-__host__ __device__ inline double motion_terms(const MotionTab& t, int x, unsigned js, const double* s, const double* g, double mu) {
+template <class TR>
+__host__ __device__ inline double motion_terms(const MotionTab& t, int x, unsigned js, const TR& tr, double mu) {
     for (int j = 0; j < t.n_joints; ++j) {
         if (!((js >> j) & 1u)) continue;
         const int qj = t.jqidx[j];
-        const double c = t.jtype[j] == NBK_PRISMATIC ? t.jsn[j] : motion_reach(t, x, j, s, g);
-        mu = mu + c * motion_abs(g[qj] - s[qj]);
+        const double c = t.jtype[j] == NBK_PRISMATIC ? t.jsn[j] : motion_reach(t, x, j, tr);
+        mu = mu + c * tr.speed(qj);
     }
     return mu;
 }
 
-// mu of user pair p on the edge (s, g): a's terms first, then b's, each joint index ascending
-__host__ __device__ inline double pair_motion_bound(const MotionTab& t, int p, const double* s, const double* g) {
+// mu of user pair p on the trajectory tr: a's terms first, then b's, each joint index ascending
+template <class TR>
+__host__ __device__ inline double pair_motion_bound(const MotionTab& t, int p, const TR& tr) {
     const int a = t.pa[p], b = t.pb[p];
     const unsigned ma = t.smask[a], mb = b < t.n_rshapes ? t.smask[b] : 0u;
-    double mu = motion_terms(t, a, ma & ~mb, s, g, 0.0);
-    if (b < t.n_rshapes) mu = motion_terms(t, b, mb & ~ma, s, g, mu);
+    double mu = motion_terms(t, a, ma & ~mb, tr, 0.0);
+    if (b < t.n_rshapes) mu = motion_terms(t, b, mb & ~ma, tr, mu);
     return mu;
 }
+
+// the linear edge q(t) = (1-t) s + t g: speed |g - s|_c, travel max(|s|, |g|)_c
+struct EdgeMotion {
+    const double* s;
+    const double* g;
+    __host__ __device__ double speed(int c) const { return motion_abs(g[c] - s[c]); }
+    __host__ __device__ double travel(int c) const {
+        const double as = motion_abs(s[c]), ag = motion_abs(g[c]);
+        return as > ag ? as : ag;
+    }
+};
+
+// knot span ell (tau[ell] < tau[ell+1]) of a clamped B-spline of degree k: q(t) lies in the convex hull of c_{ell-k} .. c_ell and
+// q'(t) in that of h_i = k (c_{i+1} - c_i) / (tau[i+k+1] - tau[i+1]), i = ell-k .. ell-1 (every denominator >= tau[ell+1] -
+// tau[ell] > 0).  speed: max_i ((double)k * |c_{i+1} - c_i|_c) / den_i; travel: max_i |c_i|_c.  cp = c_{ell-k}, row stride nq;
+// tau = the knots from tau[ell-k + 1].  For n = 2, k = 1, tau = [0, 0, 1, 1]: (1.0 * |d|) / 1.0 == |d|, EdgeMotion's bits.
+struct SplineSpanMotion {
+    const double* cp;
+    const double* tau;
+    int nq, k;
+    __host__ __device__ double speed(int c) const {
+        double v = 0.0;
+        for (int i = 0; i < k; ++i) {
+            const double den = tau[i + k] - tau[i];
+            const double h = ((double)k * motion_abs(cp[(i + 1) * nq + c] - cp[i * nq + c])) / den;
+            v = i == 0 ? h : (v > h ? v : h);
+        }
+        return v;
+    }
+    __host__ __device__ double travel(int c) const {
+        double a = motion_abs(cp[c]);
+        for (int i = 1; i <= k; ++i) {
+            const double x = motion_abs(cp[i * nq + c]);
+            a = a > x ? a : x;
+        }
+        return a;
+    }
+};
 
 }  // namespace nbk

@@ -109,6 +109,28 @@ def edge_motion_bounds(model, starts, goals):
     return mu
 
 
+def spline_motion_bounds(model, ctrl, knots, degree):
+    """Motion bounds mu (S, n - degree, P) of S clamped B-splines ctrl (S, n, n_q) sharing the knots, per knot span ell (index
+    ell - degree) and allowed pair: |d_p(t) - d_p(t')| <= mu[s, ell - degree, p] |t - t'| for t, t' in [knots[ell], knots[ell+1]].
+    The routine nbk_spline_continuous_batch advances with, run on the host (nbk_spline_motion_bounds_host); no GPU needed.
+    Entries of empty spans are 0."""
+    n_q = getattr(model, "kin", model).n_q
+    c = np.ascontiguousarray(np.asarray(ctrl, dtype=np.float64))
+    if c.ndim != 3 or c.shape[2] != n_q:
+        raise ValueError(f"control points must have shape (S, n, {n_q}), got {c.shape}")
+    S, n = c.shape[:2]
+    k = int(degree)
+    if not 1 <= k < n:
+        raise ValueError("degree must be at least 1 and less than the number of control points")
+    kn = _host_f64(knots, n + k + 1)
+    d, keep = model_desc(model)
+    mu = np.zeros((S, n - k, int(d.n_pairs)), dtype=np.float64)
+    _lib.check(_lib.load().nbk_spline_motion_bounds_host(C.byref(d), c.ctypes.data, S, n, k, kn.ctypes.data, mu.ctypes.data),
+               "nbk_spline_motion_bounds_host")
+    del keep
+    return mu
+
+
 class DeviceModel:
     """Immutable device descriptor built from a KinematicModel or SceneModel (robots/model.py)."""
 
@@ -421,6 +443,31 @@ class DeviceModel:
             self._h, c.t.data_ptr(), S, n, int(degree), kn.ctypes.data, float(resolution), float(threshold), valid.data_ptr(),
             t_hit.data_ptr(), ns.data_ptr(), self._stream()), "nbk_spline_validity_batch")
         return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+
+
+    def spline_continuous(self, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6):
+        """Certified continuous check of S clamped B-splines sharing one knot vector (nbk_spline_continuous_batch): ctrl (S, n,
+        n_q), knots n + degree + 1 values (copied to the device of ctrl) -> valid (S,) bool, t_free (S,) (how far along [0, 1] the
+        trajectory is certified free), status (S,) int32 (``_lib.CA_*``).  Asynchronous on device tensors and capturable."""
+        torch = _require_gpu()
+        shape = tuple(ctrl.shape) if torch.is_tensor(ctrl) else np.shape(ctrl)
+        if len(shape) != 3 or shape[2] != self.n_q:
+            raise ValueError(f"control points must have shape (S, n, {self.n_q}), got {shape}")
+        S, n = int(shape[0]), int(shape[1])
+        c = _Staged(ctrl, n * self.n_q, "ctrl")
+        if torch.is_tensor(knots):
+            kn = knots.to(device=c.device, dtype=torch.float64).contiguous().reshape(-1)
+        else:
+            kn = torch.from_numpy(_host_f64(knots, n + int(degree) + 1)).to(c.device)
+        if kn.numel() != n + int(degree) + 1:
+            raise ValueError(f"expected {n + int(degree) + 1} knots, got {kn.numel()}")
+        valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
+        t_free = torch.empty((S,), dtype=torch.float64, device=c.device)
+        status = torch.empty((S,), dtype=torch.int32, device=c.device)
+        _lib.check(self._lib.nbk_spline_continuous_batch(
+            self._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
+            valid.data_ptr(), t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_continuous_batch")
+        return c.out(valid.bool()), c.out(t_free), c.out(status)
 
 
 def selftest_math(a, b):

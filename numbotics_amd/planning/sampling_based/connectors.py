@@ -7,7 +7,8 @@ and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per w
 ``validate_trajectories`` / ``validate_trajectory`` check smoothed (clamped B-spline) trajectories sample by sample on the device.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
 certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
-with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.
+with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.  Its
+``validate_trajectories`` / ``validate_trajectory`` certify smoothed trajectories the same way (``nbk_spline_continuous_batch``).
 """
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
@@ -145,39 +146,50 @@ class DiscreteConnector(Connector):
         _, dev = p.arm._scene_device()
         return dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
 
-    def _spline_args(self, shape, degree):
-        p = self._params
-        if p.arm is None:
-            raise ValueError("trajectory checks need ConnectorParams(arm=...)")
-        if len(shape) != 3 or shape[2] != p.arm.dof:
-            raise ValueError(f"control points must have shape (S, n, {p.arm.dof}), got {tuple(shape)}")
-        if isinstance(degree, bool) or int(degree) != degree or not 1 <= int(degree) <= 5:
-            raise ValueError("degree must be an integer in 1..5")
-        if shape[1] <= degree:
-            raise ValueError("Degree must be less than the number of control points")
-        return int(degree)
-
     def validate_trajectories(self, control_points, degree=1):
         """S clamped B-splines of ``unit_bspline``'s knots, every one sampled at most ``resolution`` apart in joint space and checked
         on the device (``nbk_spline_validity_batch``): (S, n, dof) -> valid (S,) bool, t_hit (S,) (t of the first colliding
         sample, NaN when valid), n_samples (S,) int32.  NumPy in, NumPy out; device tensors stay on the device."""
-        shape = tuple(control_points.shape) if hasattr(control_points, "shape") else np.shape(control_points)
-        k = self._spline_args(shape, degree)
+        shape = _shape(control_points)
+        k = _spline_args(self._params, shape, degree)
         return self._spline_check(control_points, unit_knots(shape[1], k), k)
 
     def validate_trajectory(self, spline):
         """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit)."""
-        if not isinstance(spline, UnitBSpline):
-            raise ValueError("validate_trajectory takes a UnitBSpline (unit_bspline)")
-        c = np.ascontiguousarray(spline.c, dtype=np.float64)
-        k = self._spline_args((1,) + c.shape if c.ndim == 2 else c.shape, spline.k)
-        t = np.asarray(spline.t, dtype=np.float64)
-        n = c.shape[0]
-        if (t.ndim != 1 or t.shape[0] != n + k + 1 or not np.isfinite(t).all() or (np.diff(t) < 0.0).any()
-                or (t[:k + 1] != 0.0).any() or (t[n:] != 1.0).any()):
-            raise ValueError("the spline's knots must be clamped on [0, 1]: nondecreasing, k + 1 zeros first and k + 1 ones last")
+        c, t, k = _spline_parts(self._params, spline)
         valid, t_hit, _ = self._spline_check(c[None], t, k)
         return bool(valid[0]), float(t_hit[0])
+
+
+def _shape(control_points):
+    return tuple(control_points.shape) if hasattr(control_points, "shape") else np.shape(control_points)
+
+
+def _spline_args(params, shape, degree):
+    """The argument checks of the trajectory methods of both connectors -> the degree."""
+    if params.arm is None:
+        raise ValueError("trajectory checks need ConnectorParams(arm=...)")
+    if len(shape) != 3 or shape[2] != params.arm.dof:
+        raise ValueError(f"control points must have shape (S, n, {params.arm.dof}), got {tuple(shape)}")
+    if isinstance(degree, bool) or int(degree) != degree or not 1 <= int(degree) <= 5:
+        raise ValueError("degree must be an integer in 1..5")
+    if shape[1] <= degree:
+        raise ValueError("Degree must be less than the number of control points")
+    return int(degree)
+
+
+def _spline_parts(params, spline):
+    """(control points (n, dof), knots, degree) of one ``UnitBSpline``, checked as ``validate_trajectory`` needs them."""
+    if not isinstance(spline, UnitBSpline):
+        raise ValueError("validate_trajectory takes a UnitBSpline (unit_bspline)")
+    c = np.ascontiguousarray(spline.c, dtype=np.float64)
+    k = _spline_args(params, (1,) + c.shape if c.ndim == 2 else c.shape, spline.k)
+    t = np.asarray(spline.t, dtype=np.float64)
+    n = c.shape[0]
+    if (t.ndim != 1 or t.shape[0] != n + k + 1 or not np.isfinite(t).all() or (np.diff(t) < 0.0).any()
+            or (t[:k + 1] != 0.0).any() or (t[n:] != 1.0).any()):
+        raise ValueError("the spline's knots must be clamped on [0, 1]: nondecreasing, k + 1 zeros first and k + 1 ones last")
+    return c, t, k
 
 
 class ContinuousConnector(Connector):
@@ -192,7 +204,10 @@ class ContinuousConnector(Connector):
 
     Host path (a ``validity_checker`` that returns a signed distance, > 0 free): the reference's behaviour -- the sub-intervals of
     ``arange(0, T_f, resolution / d) U {T_f}`` are each searched with SciPy SLSQP for a t where the checker is <= 0, and the
-    edge is rejected when a search succeeds.  That search is local and can miss a contact."""
+    edge is rejected when a search succeeds.  That search is local and can miss a contact.
+
+    ``validate_trajectories`` / ``validate_trajectory`` (``params.arm`` required) certify smoothed plans -- clamped B-splines of
+    degree 1-5 -- the same way on the device, across their knot spans (``nbk_spline_continuous_batch``)."""
 
     def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6):
         if int(max_iter) < 1:
@@ -277,3 +292,24 @@ class ContinuousConnector(Connector):
         """-> ((E,) bool, (E, dof) end states ``traj(T_f)``)."""
         ok, end, _, _ = self.certify_batch(starts, goals, "steer", dist)
         return ok, end
+
+    # ---- smoothed trajectories ----------------------------------------------------------------------------
+    def _spline_certify(self, ctrl, knots, degree):
+        p = self._params
+        _, dev = p.arm._scene_device()
+        return dev.spline_continuous(ctrl, knots, degree, threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
+
+    def validate_trajectories(self, control_points, degree=1):
+        """S clamped B-splines of ``unit_bspline``'s knots, each certified on the device by conservative advancement across its knot
+        spans (``nbk_spline_continuous_batch``): (S, n, dof) -> valid (S,) bool, t_free (S,) (how far along [0, 1] the trajectory
+        is certified free; NaN when degenerate), status (S,) int32 (``numbotics_amd._lib.CA_*``).  A trajectory called valid has
+        no configuration closer than ``collision_threshold``.  NumPy in, NumPy out; device tensors stay on the device."""
+        shape = _shape(control_points)
+        k = _spline_args(self._params, shape, degree)
+        return self._spline_certify(control_points, unit_knots(shape[1], k), k)
+
+    def validate_trajectory(self, spline):
+        """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_free)."""
+        c, t, k = _spline_parts(self._params, spline)
+        valid, t_free, _ = self._spline_certify(c[None], t, k)
+        return bool(valid[0]), float(t_free[0])

@@ -1,8 +1,10 @@
 """Batched DiscreteConnector edges on c3 (nbk_edge_validity_batch).  With --continuous: also the certified continuous check
 (nbk_edge_continuous_batch) on c2 and c3 at the ContinuousConnector defaults, next to the discrete check at resolutions 0.01 and
 0.001, with the fraction of UNDECIDED edges.  With --spline: S = 1e4 cubic B-splines of 8 control points on c3 at resolution 0.01
-(nbk_spline_validity_batch), the edge batch with the same total sample count, and the latency of S = 1.
-Usage: python tools/edge_time.py [E ...] [--continuous | --spline]"""
+(nbk_spline_validity_batch), the edge batch with the same total sample count, and the latency of S = 1.  With --spline
+--continuous: S = 1e4 and 1e5 such splines on c2 and c3, certified (nbk_spline_continuous_batch) at the ContinuousConnector
+defaults next to the sampled check at resolutions 0.01 and 0.001, with the FREE / COLLISION / UNDECIDED fractions.
+Usage: python tools/edge_time.py [E ...] [--continuous | --spline | --spline --continuous]"""
 import os, sys, time, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from numbotics_amd.physics import World
@@ -44,6 +46,29 @@ def splines(chain, S, n=8, seed=5):
     c = (1.0 - w) * s[:, None, :] + w * g[:, None, :] + rng.uniform(-0.1, 0.1, (S, n, s.shape[1]))
     return torch.from_numpy(c).cuda()
 
+
+if spline and cont:
+    from numbotics_amd.planning import unit_knots
+    kn = unit_knots(8, 3)
+    for scene in ("c2", "c3"):
+        _reset_worlds(); World()
+        arm, chain, obs = build_scene(scene)
+        sm, dev = arm._scene_device()
+        knd = torch.from_numpy(kn).cuda()
+        for S in sizes:
+            tc = splines(chain, S)
+            samp = {}
+            for res in (0.01, 0.001):
+                (ok, th, ns), ms = timed(lambda: dev.spline_validity(tc, kn, 3, res))
+                samp[res] = ok
+                print(scene, 'splines S', S, 'k 3 n 8 sampled res', res, 'ms %.3f' % ms, 'samples %.3e' % int(ns.sum().item()),
+                      'valid frac %.3f' % ok.float().mean().item(), flush=True)
+            (ok, tf, st), ms = timed(lambda: dev.spline_continuous(tc, knd, 3))
+            st = st.cpu().numpy()
+            print(scene, 'splines S', S, 'k 3 n 8 continuous', 'ms %.3f' % ms, 'splines/s %.3e' % (S / ms * 1e3),
+                  'free %.3f collision %.3f undecided %.3f degenerate %.3f' % tuple((st == k).mean() for k in (0, 1, 2, 3)),
+                  'free-but-sampled-invalid@1e-3', bool((ok & ~samp[0.001]).any().item()), flush=True)
+    sys.exit(0)
 
 if spline:
     from numbotics_amd.planning import unit_knots
