@@ -117,6 +117,21 @@ void nbk_model_destroy(nbk_model *m);
 int32_t nbk_model_num_pairs(const nbk_model *m);
 
 /*
+ * The float32 broadphase compiled for one robot (hipRTC, on the first validity call of a descriptor with B >= 65536 plain q
+ * rows; memoised per process).  Serial chains of at most 8 joints, at most 16 shapes and 2 world shapes with a pair take it;
+ * every other descriptor, NBK_NO_JIT=1, a machine without hipRTC or a failed compile keep the generic kernel (same masks).
+ *   nbk_broad_kernel_used   broadphase of the descriptor's last validity call: 0 none yet, 1 generic k_broad_f32,
+ *                           2 the specialised kernel, 3 another broadphase (float64 / LDS forms)
+ *   nbk_broad_spec_source   (no GPU needed) the complete source the specialised kernel is compiled from for `desc`: its
+ *                           length + 1, 0 when the robot does not take it, < 0 an error; up to cap - 1 bytes + NUL to buf
+ *   nbk_jit_compile         (no GPU needed) compile such a source for `arch` ("gfx950") the way the library does: the size of
+ *                           the code object, or < 0 (nbk_last_error has the compiler's log)
+ */
+int32_t nbk_broad_kernel_used(const nbk_model *m);
+int64_t nbk_broad_spec_source(const nbk_model_desc *desc, char *buf, int64_t cap);
+int64_t nbk_jit_compile(const char *src, const char *arch);
+
+/*
  * Batched forward kinematics of one frame.
  * Replaces nb_compute_transformation + nb_joint_transform (numbotics/robots/helpers.py:33-113) as
  * called by Arm.forward_kinematics (numbotics/robots/arm.py:369-410).

@@ -27,6 +27,7 @@ SYMBOLS = [
     "nbk_fk_batch_host", "nbk_validity_batch_host", "nbk_knn_prefix",
     "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host", "nbk_spline_validity_batch",
     "nbk_spline_continuous_batch", "nbk_spline_motion_bounds_host",
+    "nbk_broad_kernel_used", "nbk_broad_spec_source", "nbk_jit_compile",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -88,6 +89,11 @@ def load():
     lib.nbk_fk_frames_batch.argtypes = [vp, vp, vp, i64, vp, vp]
     lib.nbk_ik_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, f64, i32, i32, vp, vp, vp, vp, vp]
     lib.nbk_validity_batch.argtypes = [vp, vp, i64, f64, vp, vp, vp]
+    lib.nbk_broad_kernel_used.argtypes = [vp]
+    lib.nbk_broad_spec_source.argtypes = [vp, C.c_char_p, i64]
+    lib.nbk_broad_spec_source.restype = i64
+    lib.nbk_jit_compile.argtypes = [C.c_char_p, C.c_char_p]
+    lib.nbk_jit_compile.restype = i64
     lib.nbk_validity_workspace_bytes.argtypes = [vp, i64]
     lib.nbk_validity_workspace_bytes.restype = i64
     lib.nbk_validity_batch_ws.argtypes = [vp, vp, i64, f64, vp, vp, vp, i64, vp]

@@ -20,11 +20,17 @@
 
 #include <memory>
 #include <mutex>
+#include <atomic>
 #include <algorithm>
 #include <vector>
+#include <string>
+#include <map>
+#include <dlfcn.h>
+#include <hip/hiprtc.h>
 
 #include "../../include/nbk.h"
 #include "nbk_device.hpp"
+#include "nbk_bf32_common.hpp"       // WAVE, BQ_CAP, CNT_STRIDE, the float32 broadphase pieces both its kernels share
 
 namespace nbk {
 
@@ -191,6 +197,13 @@ struct nbk_model {
     double* scalar_q_dev;     // device aliases of the two pinned buffers
     unsigned long long* scalar_out_dev;
     hipStream_t scalar_stream;
+    // the broadphase compiled for this robot (nbk_bf32_spec.hpp): the generated Spec text, "" when the robot does not qualify;
+    // the kernel is compiled / looked up on the first large validity call (bf32_mu guards the three fields below)
+    std::string bf32_spec;
+    std::mutex bf32_mu;
+    int bf32_state = 0;            // 0 not tried, 1 bf32_fn is loaded, -1 unavailable (hipRTC missing, compile failed, NBK_NO_JIT)
+    hipFunction_t bf32_fn = nullptr;
+    std::atomic<int> last_broad{0};   // broadphase of the last validity call: 0 none yet, 1 generic k_broad_f32, 2 specialised, 3 another one
 };
 
 namespace nbk {
@@ -207,7 +220,6 @@ static int hip_fail(hipError_t e, const char* what) {
         if (e_ != hipSuccess) return hip_fail(e_, #call);       \
     } while (0)
 
-constexpr int WAVE = 64;
 constexpr size_t LDS_MAX = 160 * 1024;     // LDS per workgroup on gfx950 (MI355X_MICROARCH.md)
 
 NBK_DEV int core_rows(int kind) { return kind == K_POINT ? 3 : ((kind == K_BOX || kind == K_HULL) ? 12 : 6); }
@@ -1288,7 +1300,6 @@ __global__ __launch_bounds__(64) void k_validity_redo(DevModel m, EdgeSrc es, co
 //           from q, runs the exact predicate and ORs the configuration's bit into the mask.
 // Both kernels evaluate exactly the predicate of the fused kernel (and of the oracle), so the masks are
 // bit-identical; the fused kernel stays for small batches and for the edge kernel.
-constexpr int BQ_CAP = 512;             // per-wave LDS staging of queue items before one global append
 // k_broad_f32<S>: rows of 64 doubles its q slab / item queue takes.  The queue must hold one whole row of slots (S x 64 items)
 // beyond what is pending, so that the "queue nearly full" test -- and with it the inlined flush -- exists once per row / world
 // shape instead of once per slot (92 inlined flushes made the kernel 195 KB of code for a 64 KB instruction cache)
@@ -1304,41 +1315,18 @@ NBK_DEV double readlane_f64(double v, int l) {
 // The global queue is sharded into NSUB sub-queues (block b appends to sub-queue b % NSUB): one counter
 // saturates at ~90 appends/us (MI355X_MICROARCH.md, row "dequeue"), which 15k waves would all hit.
 constexpr int NSUB = 256;
-constexpr int CNT_STRIDE = 16;          // one 128-byte line per counter
 constexpr int CNT_TICKET = 1;           // word 1 of a counter's line: the next chunk of that sub-queue the narrowphase hands out
 
-// Items are routed by the kind class of their pair (vp_cls: box-box, box-cylinder, cylinder-cylinder, the rest):
-// class c owns cls_groups[c] of the NSUB sub-queues (in proportion to its pairs), a block appends to the (block % groups)-th.  The chunks k_narrow takes are then kind-homogeneous -- one core layout, one
-// support routine per side -- which is worth 10 % of its time; one atomicAdd per class present, issued together by lanes 0-3.
+// queue routing of the descriptor (flush_items_r, nbk_bf32_common.hpp): vp_cls and the class sub-queue ranges of the model
+struct DevRoute {
+    const DevModel& m;
+    NBK_DEV int cls(unsigned p) const { return m.vp_cls[p]; }
+    NBK_DEV int base(int c) const { return m.cls_base[c]; }
+    NBK_DEV int groups(int c) const { return m.cls_groups[c]; }
+};
 NBK_DEV void flush_items(const DevModel& m, unsigned* lds_queue, int qn, int64_t base_cfg, unsigned long long* q_count,
                          unsigned long long* q_items, unsigned long long cap_sub, int lane, unsigned char* ovf) {
-    __syncthreads();
-    for (int i0 = 0; i0 < qn; i0 += WAVE) {
-        const int i = i0 + lane;
-        const bool has = i < qn;
-        const unsigned it = has ? lds_queue[i] : 0u;
-        const int cls = has ? m.vp_cls[it >> 6] : 0;
-        unsigned long long bc[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) bc[c] = __builtin_amdgcn_ballot_w64(has && cls == c);
-        const unsigned long long mine_cnt = lane == 0 ? bc[0] : (lane == 1 ? bc[1] : (lane == 2 ? bc[2] : bc[3]));
-        unsigned long long off = 0;
-        if (lane < 4 && mine_cnt != 0ull)
-            off = atomicAdd(q_count + (size_t)(m.cls_base[lane] + (int)(blockIdx.x % (unsigned)m.cls_groups[lane])) * CNT_STRIDE,
-                            (unsigned long long)__builtin_popcountll(mine_cnt));
-        const unsigned olo = (unsigned)__builtin_amdgcn_ds_bpermute(cls * 4, (int)(unsigned)off);
-        const unsigned ohi = (unsigned)__builtin_amdgcn_ds_bpermute(cls * 4, (int)(unsigned)(off >> 32));
-        if (has) {
-            const unsigned long long mb_ = cls == 0 ? bc[0] : (cls == 1 ? bc[1] : (cls == 2 ? bc[2] : bc[3]));
-            const unsigned long long slot = (((unsigned long long)ohi << 32) | olo) +
-                                            __builtin_amdgcn_mbcnt_hi((unsigned)(mb_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mb_, 0u));
-            const unsigned sub = (unsigned)(m.cls_base[cls] + (int)(blockIdx.x % (unsigned)m.cls_groups[cls]));
-            const unsigned long long b = (unsigned long long)(base_cfg + (it & 63u));
-            if (slot < cap_sub) q_items[(unsigned long long)sub * cap_sub + slot] = (b << 20) | (unsigned long long)(it >> 6);
-            else if (ovf != nullptr) ovf[blockIdx.x] = 1;          // the sub-queue is full: this block is re-decided without a queue
-        }
-    }
-    __syncthreads();
+    flush_items_r(DevRoute{m}, lds_queue, qn, base_cfg, q_count, q_items, cap_sub, lane, ovf);
 }
 
 // the NSUB queue counters are cleared by a kernel of our own: a hipMemsetAsync node did not reliably clear them
@@ -1374,16 +1362,15 @@ struct FTab {
     const int *rp, *rptri, *wp, *wlist, *n_reach;
 };
 NBK_DEV FTab ftab_view(const float* tab, int W) {
+    const FTabOffsets o = ftab_offsets(W);             // the one layout definition (nbk_bf32_common.hpp)
     FTab t;
-    const size_t w16 = (size_t)W * 16;
-    // every [.][16] table starts on a multiple of 16 floats from `tab` (itself 64-byte aligned): a row is one s_load_dwordx16
-    t.rkey = tab; t.rp = reinterpret_cast<const int*>(tab + 256); t.rcert = tab + 512;
-    t.rptri = reinterpret_cast<const int*>(tab + 768);
-    t.rneg = tab + 896; t.rnd = tab + 1152;
-    t.wkey = tab + 1408; t.wtc = t.wkey + w16; t.wp = reinterpret_cast<const int*>(t.wtc + w16);
-    t.wcert = t.wtc + 2 * w16; t.wcin = t.wcert + w16; t.wkey2 = t.wcin + w16; t.rho = t.wkey2 + w16;
-    t.n_reach = reinterpret_cast<const int*>(t.rho + 32); t.wlist = t.n_reach + 16;
-    t.wbx = reinterpret_cast<const float*>(t.wlist + ((W + 15) & ~15));        // (16-float aligned)
+    t.rkey = tab + o.rkey; t.rp = reinterpret_cast<const int*>(tab + o.rp); t.rcert = tab + o.rcert;
+    t.rptri = reinterpret_cast<const int*>(tab + o.rptri);
+    t.rneg = tab + o.rneg; t.rnd = tab + o.rnd;
+    t.wkey = tab + o.wkey; t.wtc = tab + o.wtc; t.wp = reinterpret_cast<const int*>(tab + o.wp);
+    t.wcert = tab + o.wcert; t.wcin = tab + o.wcin; t.wkey2 = tab + o.wkey2; t.rho = tab + o.rho;
+    t.n_reach = reinterpret_cast<const int*>(tab + o.n_reach); t.wlist = reinterpret_cast<const int*>(tab + o.wlist);
+    t.wbx = tab + o.wbx;
     return t;
 }
 
@@ -1964,16 +1951,7 @@ __global__ __launch_bounds__(64, 3) void k_broad_reg(DevModel m, EdgeSrc es, con
 // Tables in LDS as in k_broad_reg (keys in float32, already including the static part of the slack).
 struct XfF { float R[9]; float t[3]; };
 
-// sin / cos for the conservative float32 sweep: the hardware's v_sin_f32 / v_cos_f32 on the fractional part of x / 2 pi (five
-// instructions where the Cody-Waite + Taylor form took 22).  Measured on the device over |x| <= 64 (tools: profiles/r03_hw_sincos.log):
-// absolute error <= 2.7e-7 for |x| <= 3.2 and <= 2.7e-7 + 4e-8 |x| beyond (the rounding of x / 2 pi) -- inside what the slack
-// charges per joint (16 ulp = 9.5e-7 for the sweep, 2.4e-7 |q| for the angle, both times 50)
-NBK_DEV void sincos_f(float x, float& s, float& c) {
-    const float r = x * 0.15915494309189535f;
-    const float f = r - __builtin_rintf(r);
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
-}
+// sincos_f: nbk_bf32_common.hpp
 
 template <int KZ>
 NBK_DEV void joint_apply_axis_f(const float* M, const float* toff, const XfF& P, float s, float c, XfF& o) {
@@ -2020,45 +1998,7 @@ NBK_DEV void joint_apply_f(const DevModel& m, int k, const XfF& P, float qk, XfF
     }
 }
 
-struct alignas(64) Row16f { float v[16]; };     // one row of a [.][16] slot table: a single s_load_dwordx16
-typedef float V2f __attribute__((ext_vector_type(2)));
-typedef int V2i __attribute__((ext_vector_type(2)));
-// |d|^2 + nk as one fma chain, for two slots at a time (v_pk_fma_f32) and for one: the same operations in the same order, so the
-// one-slot form reproduces the pair form's value bit for bit (the rare enqueue path re-evaluates what the row's sign bits flagged)
-NBK_DEV V2f slot_e2(V2f dx, V2f dy, V2f dz, V2f nk) {
-    return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, __builtin_elementwise_fma(dx, dx, nk)));
-}
-NBK_DEV float slot_e1(float dx, float dy, float dz, float nk) { return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, nk))); }
-
-// ---- the packed float32 sweep of k_broad_f32 --------------------------------------------------------------------------------
-// A frame as rows 0 and 1 of every column in one register PAIR (Rc[k] = (R[0][k], R[1][k]), tc = (t[0], t[1])) and row 2 apart:
-// R x L and R x v then run rows 0 and 1 together on v_pk_fma_f32 (one issue slot for two multiply-adds; plain float32 and packed
-// float32 instructions issue at the same rate on this SIMD, profiles/r03_valu_issue_rate.log): 27 instructions per axis-aligned
-// joint instead of 48, 6 per shape centre instead of 9.
-struct XfP { V2f Rc[3]; float R2[3]; V2f tc; float t2; };
-// host-made constants of one joint (f_tab + f_pk + 20 k): for a joint about coordinate axis KZ of its frame, U = KZ + 1, V = KZ + 2
-struct alignas(16) JPk { float m2p[6]; float m1p[6]; float mk[3]; float pad0; float toff[3]; float pad1; };
-NBK_DEV V2f splat2(float x) { return V2f{x, x}; }
-NBK_DEV V2f fma2(V2f a, V2f b, V2f c) { return __builtin_elementwise_fma(a, b, c); }
-
-template <int KZ>
-NBK_DEV void joint_apply_axis_p(const JPk& jp, const XfP& P, float s, float c, XfP& o) {
-    constexpr int U = (KZ + 1) % 3, V = (KZ + 2) % 3;
-    const V2f s2 = splat2(s), c2 = splat2(c);
-    V2f Lp[3];                                                     // (L[r][U], L[r][V]) = s M2 - c M1
-#pragma unroll
-    for (int r = 0; r < 3; ++r) Lp[r] = fma2(s2, V2f{jp.m2p[2 * r], jp.m2p[2 * r + 1]}, -(c2 * V2f{jp.m1p[2 * r], jp.m1p[2 * r + 1]}));
-    const V2f cu = fma2(P.Rc[2], splat2(Lp[2].x), fma2(P.Rc[1], splat2(Lp[1].x), P.Rc[0] * splat2(Lp[0].x)));
-    const V2f cv = fma2(P.Rc[2], splat2(Lp[2].y), fma2(P.Rc[1], splat2(Lp[1].y), P.Rc[0] * splat2(Lp[0].y)));
-    const V2f ck = fma2(P.Rc[2], splat2(jp.mk[2]), fma2(P.Rc[1], splat2(jp.mk[1]), P.Rc[0] * splat2(jp.mk[0])));
-    const V2f r2 = fma2(splat2(P.R2[2]), Lp[2], fma2(splat2(P.R2[1]), Lp[1], splat2(P.R2[0]) * Lp[0]));        // row 2, columns U and V
-    const float r2k = __builtin_fmaf(P.R2[2], jp.mk[2], __builtin_fmaf(P.R2[1], jp.mk[1], P.R2[0] * jp.mk[0]));
-    const V2f tc = fma2(P.Rc[2], splat2(jp.toff[2]), fma2(P.Rc[1], splat2(jp.toff[1]), fma2(P.Rc[0], splat2(jp.toff[0]), P.tc)));
-    const float t2 = __builtin_fmaf(P.R2[2], jp.toff[2], __builtin_fmaf(P.R2[1], jp.toff[1], __builtin_fmaf(P.R2[0], jp.toff[0], P.t2)));
-    o.Rc[U] = cu; o.Rc[V] = cv; o.Rc[KZ] = ck;
-    o.R2[U] = r2.x; o.R2[V] = r2.y; o.R2[KZ] = r2k;
-    o.tc = tc; o.t2 = t2;
-}
+// Row16f, V2f / V2i, slot_e2, the packed sweep's XfP / JPk / joint_apply_axis_p / joint_apply_gen_p: nbk_bf32_common.hpp
 
 // same case split as joint_apply_f; the error of every form is covered by the slack
 NBK_DEV void joint_apply_p(const DevModel& m, int k, int kind, const JPk& jp, const XfP& P, float qk, XfP& o) {
@@ -2070,23 +2010,7 @@ NBK_DEV void joint_apply_p(const DevModel& m, int k, int kind, const JPk& jp, co
         else joint_apply_axis_p<2>(jp, P, s, c, o);
         return;
     }
-    const float* M = m.f_tab + 27 * k;
-    const float* toff = m.f_tab + m.f_trans + 3 * k;
-    const float* sl = m.f_tab + m.f_slide + 3 * k;
-    float L[9], tl[3];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) L[e] = __builtin_fmaf(s, M[18 + e], __builtin_fmaf(-c, M[9 + e], M[e]));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tl[i] = __builtin_fmaf(qk, sl[i], toff[i]);
-    XfP n;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        n.Rc[j] = fma2(P.Rc[2], splat2(L[6 + j]), fma2(P.Rc[1], splat2(L[3 + j]), P.Rc[0] * splat2(L[j])));
-        n.R2[j] = __builtin_fmaf(P.R2[2], L[6 + j], __builtin_fmaf(P.R2[1], L[3 + j], P.R2[0] * L[j]));
-    }
-    n.tc = fma2(P.Rc[2], splat2(tl[2]), fma2(P.Rc[1], splat2(tl[1]), fma2(P.Rc[0], splat2(tl[0]), P.tc)));
-    n.t2 = __builtin_fmaf(P.R2[2], tl[2], __builtin_fmaf(P.R2[1], tl[1], __builtin_fmaf(P.R2[0], tl[0], P.t2)));
-    o = n;
+    joint_apply_gen_p(m.f_tab + 27 * k, m.f_tab + m.f_trans + 3 * k, m.f_tab + m.f_slide + 3 * k, P, qk, s, c, o);
 }
 
 // in-kernel phase timing of k_broad_f32, only in builds made with -DNBK_BF32_STAMP (tools/build_variant.sh, tools/broad_prof.py):
@@ -4158,10 +4082,245 @@ int32_t nbk_device_count(void) {
     return n;
 }
 
+// ---- the broadphase compiled per robot (nbk_bf32_spec.hpp) ------------------------------------------------------------------
+// The text of nbk_bf32_common.hpp and nbk_bf32_spec.hpp, embedded by build.py (nbk_bf32_spec.inc: kBf32CommonHeader,
+// kBf32SpecHeader as raw string literals).
+#include "nbk_bf32_spec.inc"
+
+// world shapes with a pair that the specialised kernel unrolls at most: every one is a fully unrolled block with its own queue
+// appends (8 cubes made 140 KB of code for a 64 KB instruction cache and an 11 s compile); other scenes keep the generic kernel
+constexpr int SPEC_MAX_WORLD = 2;
+// validity calls smaller than this never pay for a compile
+constexpr int64_t SPEC_MIN_BATCH = 1 << 16;
+
+struct SpecIn {
+    int J, S, W, P, n_q;
+    const int* joint_kind; const int* joint_qidx; const int* begin;    // begin: [J + 2]
+    const int* bq_tab; const int* ws_kind;
+    int f_pk, f_tl, f_base, f_wc, f_wobb, f_trans, f_slide;
+    float f_eps, f_reach, f_e2max;
+    const int* cls_base; const int* cls_groups;
+};
+
+// The `struct Spec` of one descriptor ("" when the robot does not take the specialised kernel: not a serial chain of at most
+// 8 joints, more than 16 shapes, no pairs, too many world shapes)
+static std::string bf32_spec_text(const SpecIn& in) {
+    const int S = in.S, J = in.J;
+    if (in.P == 0 || S < 1 || S > 16 || J < 1 || J > 8) return std::string();
+    std::vector<int> rrp((size_t)S * S, -1), wlist;
+    std::vector<int> wslot_of(in.W > 0 ? in.W : 1, -1);
+    for (int j = 0; j < in.P; ++j) {
+        const int* bt = in.bq_tab + 4 * j;
+        if (bt[3] != 1 && wslot_of[bt[1]] < 0) { wslot_of[bt[1]] = 0; wlist.push_back(bt[1]); }
+    }
+    std::sort(wlist.begin(), wlist.end());
+    if ((int)wlist.size() > SPEC_MAX_WORLD) return std::string();
+    const int NW = (int)wlist.size();
+    for (int i = 0; i < NW; ++i) wslot_of[wlist[i]] = i;
+    std::vector<int> wp((size_t)(NW > 0 ? NW : 1) * S, -1);
+    bool rr_any = false;
+    for (int j = 0; j < in.P; ++j) {
+        const int* bt = in.bq_tab + 4 * j;
+        const int a = bt[0] / 3;
+        if (bt[3] == 1) {
+            const int b = bt[1] / 3, lo = a < b ? a : b, hi = a < b ? b : a;
+            rrp[(size_t)lo * S + hi] = bt[2];
+            rr_any = true;
+        } else {
+            wp[(size_t)wslot_of[bt[1]] * S + a] = bt[2];
+        }
+    }
+    std::string o;
+    char buf[512];
+    auto add = [&](const char* fmt, auto... v) { snprintf(buf, sizeof(buf), fmt, v...); o += buf; };
+    auto arr = [&](const char* name, const std::vector<int>& v) {
+        add("    static constexpr int %s[] = {", name);
+        for (size_t i = 0; i < v.size(); ++i) add(i ? ", %d" : "%d", v[i]);
+        if (v.empty()) o += "-1";
+        o += "};\n";
+    };
+    const int SB = S <= 8 ? 8 : (S <= 12 ? 12 : 16);
+    o += "struct Spec {\n";
+    add("    static constexpr int S = %d, SB = %d, NQ = %d, J = %d, W = %d, NW = %d;\n", S, SB, in.n_q, J, in.W, NW);
+    arr("jkind", std::vector<int>(in.joint_kind, in.joint_kind + J));
+    arr("qcol", std::vector<int>(in.joint_qidx, in.joint_qidx + J));
+    arr("sh_begin", std::vector<int>(in.begin, in.begin + J + 2));
+    add("    static constexpr int f_rot = 0, f_pk = %d, f_tl = %d, f_base = %d, f_wc = %d, f_wobb = %d, f_trans = %d, f_slide = %d;\n",
+        in.f_pk, in.f_tl, in.f_base, in.f_wc, in.f_wobb, in.f_trans, in.f_slide);
+    add("    static constexpr float f_eps = %af, f_reach = %af, f_e2max = %af;\n", (double)in.f_eps, (double)in.f_reach, (double)in.f_e2max);
+    add("    static constexpr bool rr_any = %s;\n", rr_any ? "true" : "false");
+    arr("rrp_", rrp);
+    std::vector<int> wl(wlist), wk;
+    for (int w : wlist) wk.push_back(in.ws_kind[w]);
+    arr("wl", wl);
+    arr("wk", wk);
+    arr("wp_", wp);
+    arr("cls_base", std::vector<int>(in.cls_base, in.cls_base + 4));
+    std::vector<int> groups(in.cls_groups, in.cls_groups + 4);
+    for (int& g : groups) g = g > 0 ? g : 1;             // as DevModel::cls_groups: a divisor, also for a class without pairs
+    arr("cls_groups", groups);
+    o += "    static constexpr int rr_p(int a, int b) { return a >= 0 && b < S && a < b ? rrp_[a * S + b] : -1; }\n"
+         "    static constexpr int wpair(int wi, int a) { return a < S ? wp_[wi * S + a] : -1; }\n"
+         "    static constexpr bool rr_group(int a, int i) { return rr_p(a, 2 * i) >= 0 || rr_p(a, 2 * i + 1) >= 0; }\n"
+         "    static constexpr int row_slots(int a) { int n = 0; for (int b = a + 1; b < S; ++b) n += rr_p(a, b) >= 0 ? 1 : 0; return n; }\n"
+         "};\n";
+    return o;
+}
+
+static std::string bf32_source(const std::string& spec) {
+    return spec + "#line 1 \"nbk_bf32_common.hpp\"\n" + kBf32CommonHeader + "#line 1 \"nbk_bf32_spec.hpp\"\n" + kBf32SpecHeader;
+}
+
+// hipRTC, opened at run time: a machine without it keeps the generic kernel
+struct Rtc {
+    bool ok = false;
+    decltype(&hiprtcCreateProgram) create = nullptr;
+    decltype(&hiprtcCompileProgram) compile = nullptr;
+    decltype(&hiprtcGetProgramLogSize) log_size = nullptr;
+    decltype(&hiprtcGetProgramLog) log = nullptr;
+    decltype(&hiprtcGetCodeSize) code_size = nullptr;
+    decltype(&hiprtcGetCode) code = nullptr;
+    decltype(&hiprtcDestroyProgram) destroy = nullptr;
+};
+static const Rtc& rtc() {
+    static Rtc r;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        void* h = dlopen("libhiprtc.so", RTLD_NOW | RTLD_LOCAL);
+        if (h == nullptr) h = dlopen("libhiprtc.so.7", RTLD_NOW | RTLD_LOCAL);
+        if (h == nullptr) {
+            // next to the HIP runtime this library is linked against
+            Dl_info info;
+            if (dladdr(reinterpret_cast<void*>(&hipModuleLoadData), &info) != 0 && info.dli_fname != nullptr) {
+                std::string dir(info.dli_fname);
+                dir = dir.substr(0, dir.rfind('/') + 1);
+                h = dlopen((dir + "libhiprtc.so").c_str(), RTLD_NOW | RTLD_LOCAL);
+            }
+        }
+        if (h == nullptr) return;
+        r.create = reinterpret_cast<decltype(r.create)>(dlsym(h, "hiprtcCreateProgram"));
+        r.compile = reinterpret_cast<decltype(r.compile)>(dlsym(h, "hiprtcCompileProgram"));
+        r.log_size = reinterpret_cast<decltype(r.log_size)>(dlsym(h, "hiprtcGetProgramLogSize"));
+        r.log = reinterpret_cast<decltype(r.log)>(dlsym(h, "hiprtcGetProgramLog"));
+        r.code_size = reinterpret_cast<decltype(r.code_size)>(dlsym(h, "hiprtcGetCodeSize"));
+        r.code = reinterpret_cast<decltype(r.code)>(dlsym(h, "hiprtcGetCode"));
+        r.destroy = reinterpret_cast<decltype(r.destroy)>(dlsym(h, "hiprtcDestroyProgram"));
+        r.ok = r.create && r.compile && r.log_size && r.log && r.code_size && r.code && r.destroy;
+    });
+    return r;
+}
+
+// compile `src` for `arch` with the library's arithmetic flags; the code object goes to `code`.  NBK_OK, or an error with the
+// compiler's log (truncated) in g_err
+static int32_t bf32_compile(const std::string& src, const std::string& arch, std::vector<char>& code) {
+    const Rtc& r = rtc();
+    if (!r.ok) { snprintf(g_err, sizeof(g_err), "hipRTC is not available"); return NBK_ERR_UNSUPPORTED; }
+    // hipRTC (ROCm 7.2) crashes the process on a target it does not know instead of failing: only known targets are compiled for
+    static const char* const known[] = {"gfx908", "gfx90a", "gfx940", "gfx941", "gfx942", "gfx950", "gfx1030", "gfx1100", "gfx1101",
+                                        "gfx1102", "gfx1200", "gfx1201"};
+    bool known_arch = false;
+    for (const char* k : known) known_arch = known_arch || arch == k;
+    if (!known_arch) { snprintf(g_err, sizeof(g_err), "hipRTC: unsupported target '%.64s'", arch.c_str()); return NBK_ERR_UNSUPPORTED; }
+    hiprtcProgram prog;
+    if (r.create(&prog, src.c_str(), "k_broad_f32_spec.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        snprintf(g_err, sizeof(g_err), "hiprtcCreateProgram failed");
+        return NBK_ERR_UNSUPPORTED;
+    }
+    const std::string arch_opt = "--offload-arch=" + arch;
+    std::vector<const char*> opts = {arch_opt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off"};
+    // NBK_JIT_OPTIONS: one more hipRTC option (diagnostics and tests, e.g. -DNBK_SPEC_WAVES=6); part of the module's memo key
+    const char* extra = getenv("NBK_JIT_OPTIONS");
+    if (extra != nullptr && *extra) opts.push_back(extra);
+    const hiprtcResult cr = r.compile(prog, (int)opts.size(), opts.data());
+    if (cr != HIPRTC_SUCCESS) {
+        size_t n = 0;
+        std::string log;
+        if (r.log_size(prog, &n) == HIPRTC_SUCCESS && n > 1) { log.resize(n); if (r.log(prog, &log[0]) != HIPRTC_SUCCESS) log.clear(); }
+        snprintf(g_err, sizeof(g_err), "hipRTC compile of the specialised broadphase failed: %.200s", log.c_str());
+        r.destroy(&prog);
+        return NBK_ERR_UNSUPPORTED;
+    }
+    size_t n = 0;
+    if (r.code_size(prog, &n) != HIPRTC_SUCCESS || n == 0) { r.destroy(&prog); snprintf(g_err, sizeof(g_err), "hipRTC: no code"); return NBK_ERR_UNSUPPORTED; }
+    code.resize(n);
+    const hiprtcResult gr = r.code(prog, code.data());
+    r.destroy(&prog);
+    return gr == HIPRTC_SUCCESS ? NBK_OK : NBK_ERR_UNSUPPORTED;
+}
+
+// the target of the current device ("gfx950"; the feature suffix dropped), or NBK_JIT_ARCH (a test hook)
+static std::string device_arch() {
+    const char* ov = getenv("NBK_JIT_ARCH");
+    if (ov != nullptr && *ov) return ov;
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return std::string();
+    std::string a(p.gcnArchName);
+    return a.substr(0, a.find(':'));
+}
+
+// One module per (device, arch, source) and process: descriptors of the same robot share it
+static hipFunction_t bf32_function(const std::string& spec) {
+    static std::mutex mu;
+    static std::map<std::string, hipFunction_t> memo;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    const std::string arch = device_arch();
+    if (arch.empty()) return nullptr;
+    const std::string src = bf32_source(spec);
+    const char* extra = getenv("NBK_JIT_OPTIONS");
+    const std::string key = std::to_string(dev) + "|" + arch + "|" + (extra ? extra : "") + "|" + src;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = memo.find(key);
+    if (it != memo.end()) return it->second;
+    std::vector<char> code;
+    hipFunction_t fn = nullptr;
+    if (bf32_compile(src, arch, code) == NBK_OK) {
+        hipModule_t mod = nullptr;
+        if (hipModuleLoadData(&mod, code.data()) == hipSuccess) {
+            if (hipModuleGetFunction(&fn, mod, "k_broad_f32_spec") != hipSuccess) fn = nullptr;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    memo[key] = fn;                 // a failure is remembered too: it is not retried
+    return fn;
+}
+
+static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only);
+
 int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     if (d == nullptr || out == nullptr) return NBK_ERR_INVALID;
     *out = nullptr;
     if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
+    return model_create_impl(d, out, nullptr);
+}
+
+int64_t nbk_broad_spec_source(const nbk_model_desc* d, char* buf, int64_t cap) {
+    if (d == nullptr) return NBK_ERR_INVALID;
+    std::string spec;
+    const int32_t rc = model_create_impl(d, nullptr, &spec);
+    if (rc != NBK_OK) return rc;
+    if (spec.empty()) return 0;
+    const std::string src = bf32_source(spec);
+    if (buf != nullptr && cap > 0) {
+        const size_t n = src.size() < (size_t)(cap - 1) ? src.size() : (size_t)(cap - 1);
+        memcpy(buf, src.data(), n);
+        buf[n] = '\0';
+    }
+    return (int64_t)src.size() + 1;
+}
+
+int64_t nbk_jit_compile(const char* src, const char* arch) {
+    if (src == nullptr || arch == nullptr) return NBK_ERR_INVALID;
+    std::vector<char> code;
+    const int32_t rc = bf32_compile(src, arch, code);
+    return rc == NBK_OK ? (int64_t)code.size() : rc;
+}
+
+int32_t nbk_broad_kernel_used(const nbk_model* m) { return m == nullptr ? NBK_ERR_INVALID : m->last_broad.load(std::memory_order_relaxed); }
+
+static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only) {
     const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
     if (d->n_q < 0 || J < 0 || S < 0 || W < 0 || P < 0) return NBK_ERR_INVALID;
     if (J > NBK_MAX_JOINTS || d->n_q > NBK_MAX_DOF) return NBK_ERR_UNSUPPORTED;
@@ -4583,6 +4742,24 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
         for (int k = 0; k < J && f_chain; ++k) if (load[k] != (k == 0 ? -1 : -2) || save[k] != -1) f_chain = 0;
         if (ftab.empty()) ftab.push_back(0.0f);
     }
+    // slack constants of the float32 broadphase: 50 x the float32 error bound (joints + 2) * 16 ulp of a chain sweep, relative; the
+    // kernel multiplies it by the larger of the static reach and the configuration's own largest coordinate (prismatic travel is
+    // unbounded here)
+    float f_eps_v, f_reach_v, f_e2max_v;
+    {
+        const double rel = 50.0 * (J + 2) * 16.0 * 5.96e-8;
+        f_eps_v = (float)(rel > 1e-4 ? rel : 1e-4);
+        f_reach_v = (float)(reach > 1e-3 ? reach : 1e-3);
+        f_e2max_v = 2.0f * f_reach_v * (f_eps_v + 2.4e-7f * 64.0f) * (1.0f + 1e-6f);
+    }
+    std::string spec;
+    if (f_chain) {
+        const SpecIn si{J, S, W, P, d->n_q, joint_kind.data(), d->joint_qidx, begin.data(), bq_tab.data(), ws_kind.data(),
+                        f_pk, f_tl, f_base, f_wc, f_wobb, f_trans, f_slide, f_eps_v, f_reach_v, f_e2max_v, cls_base, cls_groups};
+        spec = bf32_spec_text(si);
+    }
+    if (spec_only != nullptr) { *spec_only = spec; delete M; return NBK_OK; }
+    M->bf32_spec = spec;
     o.ft = B.add(ftab.data(), sizeof(float) * ftab.size());
     std::vector<int> rs_frame_v(S > 0 ? S : 1, -1);
     for (int i = 0; i < S; ++i) rs_frame_v[i] = d->rshape_frame[order[i]];
@@ -4689,14 +4866,7 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     for (int c = 0; c < 4; ++c) { m.cls_base[c] = cls_base[c]; m.cls_groups[c] = cls_groups[c] > 0 ? cls_groups[c] : 1; }
     m.f_tab = reinterpret_cast<const float*>(base + o.ft);
     m.f_trans = f_trans; m.f_slide = f_slide; m.f_base = f_base; m.f_tl = f_tl; m.f_wc = f_wc; m.f_wobb = f_wobb; m.f_pk = f_pk; m.f_meta = f_meta; m.f_chain = f_chain;
-    // relative slack: 50 x the float32 error bound (joints + 2) * 16 ulp of a chain sweep; the kernel multiplies it by the
-    // larger of the static reach and the configuration's own largest coordinate (prismatic travel is unbounded here)
-    {
-        const double rel = 50.0 * (J + 2) * 16.0 * 5.96e-8;
-        m.f_eps = (float)(rel > 1e-4 ? rel : 1e-4);
-        m.f_reach = (float)(reach > 1e-3 ? reach : 1e-3);
-        m.f_e2max = 2.0f * m.f_reach * (m.f_eps + 2.4e-7f * 64.0f) * (1.0f + 1e-6f);
-    }
+    m.f_eps = f_eps_v; m.f_reach = f_reach_v; m.f_e2max = f_e2max_v;
     m.rs_frame = reinterpret_cast<const int*>(base + o.rf);
     m.bq_tab = reinterpret_cast<const int*>(base + o.bt);
     m.bq_static = reinterpret_cast<const double*>(base + o.bs);
@@ -5143,6 +5313,19 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
     const int S = m->d.n_rshapes;
     const bool use_reg = S <= 16 && (!g_opt.no_reg_broad || !m->lds_broad_ok);
     const bool f32 = !g_opt.f64_broad || broad_reg_lds(m, broad_bucket(S)) > LDS_MAX;   // the float64 form keeps its tables in LDS
+    // the broadphase compiled for this robot (plain q rows, large calls; compiled on the first such call, never inside a capture)
+    hipFunction_t spec_fn = nullptr;
+    if (use_reg && f32 && m->d.f_chain && es.map == nullptr && es.total == nullptr && !m->bf32_spec.empty() && B >= SPEC_MIN_BATCH) {
+        nbk_model* mm = const_cast<nbk_model*>(m);
+        std::lock_guard<std::mutex> lock(mm->bf32_mu);
+        if (mm->bf32_state == 0) {
+            const char* nj = getenv("NBK_NO_JIT");
+            if (nj != nullptr && *nj && strcmp(nj, "0") != 0) mm->bf32_state = -1;
+            else if (!stream_capturing(st0)) { mm->bf32_fn = bf32_function(mm->bf32_spec); mm->bf32_state = mm->bf32_fn != nullptr ? 1 : -1; }
+        }
+        if (mm->bf32_state == 1) spec_fn = mm->bf32_fn;
+    }
+    const_cast<nbk_model*>(m)->last_broad.store(spec_fn != nullptr ? 2 : (use_reg && f32 ? 1 : 3), std::memory_order_relaxed);
     int tile_no = 0;
     for (int64_t b0 = 0; b0 < B; b0 += tile, ++tile_no) {
         const bool odd = pipe && (tile_no & 1);
@@ -5188,7 +5371,16 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
             hipLaunchKernelGGL(k_zero_counters, dim3(1), dim3(NSUB), 0, st, count, flag_words, n_flag_words);
         }
 #define NBK_LAUNCH_BF32(S_, WH_) hipLaunchKernelGGL((k_broad_f32<S_, WH_>), dim3(nblk), dim3(WAVE), lds_f, st, m->d, es_tile, qt, nb, threshold, mb, my, count, items, cap_sub, ftab)
-        if (use_reg && f32 && S <= 8) { if (m->world_hulls) NBK_LAUNCH_BF32(8, true); else NBK_LAUNCH_BF32(8, false); }
+        if (spec_fn != nullptr) {
+            // same arguments as k_broad_f32, flattened; its LDS is the q slab / item queue alone (no saved frames, no parked z)
+            const double* a_q = qt; long long a_b = nb; const float* a_ftb = m->d.f_tab; const float* a_tab = ftab;
+            unsigned long long* a_mb = reinterpret_cast<unsigned long long*>(mb); unsigned char* a_my = my;
+            unsigned long long* a_cnt = count; unsigned long long* a_items = items; unsigned long long a_cap = cap_sub;
+            unsigned char* a_ovf = es_tile.ovf; const int* a_cls = m->d.vp_cls;
+            void* args[] = {&a_q, &a_b, &a_ftb, &a_tab, &a_mb, &a_my, &a_cnt, &a_items, &a_cap, &a_ovf, &a_cls};
+            NBK_HIP(hipModuleLaunchKernel(spec_fn, nblk, 1, 1, WAVE, 1, 1, (unsigned)(sizeof(double) * WAVE * qrows_f), st, args, nullptr));
+        }
+        else if (use_reg && f32 && S <= 8) { if (m->world_hulls) NBK_LAUNCH_BF32(8, true); else NBK_LAUNCH_BF32(8, false); }
         else if (use_reg && f32 && S <= 12) { if (m->world_hulls) NBK_LAUNCH_BF32(12, true); else NBK_LAUNCH_BF32(12, false); }
         else if (use_reg && f32) { if (m->world_hulls) NBK_LAUNCH_BF32(16, true); else NBK_LAUNCH_BF32(16, false); }
 #undef NBK_LAUNCH_BF32

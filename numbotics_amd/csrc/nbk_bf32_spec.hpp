@@ -1,0 +1,340 @@
+// The float32 fast path of k_broad_f32, compiled at run time for ONE robot (hipRTC): k_broad_f32_spec.
+//
+// nbk.hip generates a `struct Spec` from a descriptor's tables (bf32_spec_text) and compiles it in front of this file.  What is
+// fixed for a descriptor becomes a compile-time constant: the joint kinds and q columns of the chain, which shapes hang off
+// which frame, the real robot-robot and robot-world slots and their pair indices, the world shapes and their kinds, the
+// float32 table offsets.  What depends on the threshold stays in the table k_prepare_f32 writes (same layout as for the
+// generic kernel).  With every index a constant, the centres are plain registers: no VGPR indexing, no v_readlane broadcast
+// of the shape offsets, no z coordinates parked in LDS; and groups of two slots (2i, 2i + 1) that hold no pair are not
+// computed at all.
+//
+// The arithmetic of every slot that IS computed is the generic kernel's, operation for operation (same fma chains, same
+// table values), and the float32 stage only culls or certifies with the same conservative thresholds: every survivor is
+// decided again in float64 by k_narrow_*, so the masks are those of the generic kernel.
+//
+// The table layout, the sweep joint, every per-slot test and the queue flush are nbk_bf32_common.hpp's, the very definitions
+// k_broad_f32 uses; what is here is the specialised control flow around them.  nbk.hip hands hipRTC the generated Spec, then
+// nbk_bf32_common.hpp, then this file.  Self-contained for hipRTC: no host headers, nothing beyond what hiprtc supplies.
+
+#define NBK_SPEC_DEV __device__ __forceinline__
+#define NBK_SPEC_INLINE __attribute__((always_inline))      // every lambda of the kernel: its captures must stay registers
+
+namespace nbk_spec {
+
+using namespace nbk;            // nbk_bf32_common.hpp: the table layout, the sweep joint, the slot tests, the queue flush
+enum { K_BOX = 2, K_HULL = 4, K_PLANE = 5 };
+enum { JK_PRISMATIC = 4 };
+
+template <int V> struct IC { static constexpr int value = V; };
+// compile-time loop: f(IC<I>{}) for I = B .. E-1
+template <int B, int E, class F> NBK_SPEC_DEV void sfor(F&& f) {
+    if constexpr (B < E) { f(IC<B>{}); sfor<B + 1, E>(f); }
+}
+
+// queue routing of the descriptor as constants (flush_items_r)
+template <class Spec> struct SpecRoute {
+    const int* __restrict__ vp_cls;
+    NBK_SPEC_DEV int cls(unsigned p) const { return vp_cls[p]; }
+    NBK_SPEC_DEV int base(int c) const { return Spec::cls_base[c]; }
+    NBK_SPEC_DEV int groups(int c) const { return Spec::cls_groups[c]; }
+};
+
+// Spec (generated) provides:
+//   S (robot shapes), SB (even register bucket >= S), NQ, J (<= 8), W (world shapes of the descriptor), NW (world shapes with a pair)
+//   jkind[J], qcol[J]; sh_begin[J + 2] (shapes of frame k - 1 are [sh_begin[k], sh_begin[k + 1]))
+//   f_pk, f_tl, f_base, f_wc, f_wobb, f_trans, f_slide, f_rot (= 0)         float offsets into f_tab
+//   f_eps, f_reach, f_e2max                                                 the descriptor's slack constants
+//   rr_any; rpair(a, b) (a < b), rr_p(a, b): pair index of robot-robot slot (a, b), -1 = none
+//   wl[NW], wk[NW]: world shape and kind; wpair(i, a): pair index of (wl[i], a), -1 = none
+//   cls_base[4], cls_groups[4]
+template <class Spec>
+NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, const float* __restrict__ ftb, const float* __restrict__ tab,
+                                 unsigned long long* __restrict__ mask_bits, unsigned char* __restrict__ mask_bytes,
+                                 unsigned long long* __restrict__ q_count, unsigned long long* __restrict__ q_items, unsigned long long cap,
+                                 unsigned char* ovf, const int* __restrict__ vp_cls) {
+    constexpr int S = Spec::S, SB = Spec::SB, NQ = Spec::NQ, J = Spec::J, W = Spec::W;
+    constexpr FTabOffsets FO = ftab_offsets(W);
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const long long base = (long long)blockIdx.x * WAVE;
+    double* lds_raw = lds;
+    constexpr int qrows = NQ > (SB + 2) / 2 ? NQ : (SB + 2) / 2;
+    constexpr int qcap = qrows * (WAVE * 2);
+    unsigned* lds_queue = reinterpret_cast<unsigned*>(lds_raw);
+    if (base >= B) return;
+    const int rows_i = (int)((B - base) < WAVE ? (B - base) : WAVE);
+    {
+        const int total = rows_i * NQ;
+        const double* src = q + base * NQ;
+        if (rows_i == WAVE && ((reinterpret_cast<unsigned long long>(src) & 15) == 0) && (total % 2 == 0)) {
+            const double2* s2 = reinterpret_cast<const double2*>(src);
+            double2* d2 = reinterpret_cast<double2*>(lds_raw);
+            for (int i = lane; i < total / 2; i += WAVE) d2[i] = s2[i];
+        } else {
+            for (int i = lane; i < total; i += WAVE) lds_raw[i] = src[i];
+            for (int i = total + lane; i < WAVE * NQ; i += WAVE) lds_raw[i] = 0.0;
+        }
+    }
+    __syncthreads();
+    const bool active = lane < rows_i;
+    int hit = 0;                // (an int: a bool captured by the lambdas below was kept in scratch, two bytes per lane)
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) hit = hit || !(__builtin_fabs(lds_raw[lane * NQ + j]) <= 1.7976931348623157e308);
+    // ---- chain sweep: every shape's centre in named registers ------------------------------------------------------------------
+    float cxa[SB], cya[SB], cza[SB];
+#pragma unroll
+    for (int i = 0; i < SB; ++i) { cxa[i] = 0.0f; cya[i] = 0.0f; cza[i] = 0.0f; }
+    float rmax = Spec::f_reach, qabs = 0.0f;
+    float qv[J];
+#pragma unroll
+    for (int k = 0; k < J; ++k) { qv[k] = (float)lds_raw[lane * NQ + Spec::qcol[k]]; qabs += __builtin_fabsf(qv[k]); }
+    XfP T;
+    {
+        const float* bp = ftb + Spec::f_base;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { T.Rc[k] = V2f{bp[k], bp[4 + k]}; T.R2[k] = bp[8 + k]; }
+        T.tc = V2f{bp[3], bp[7]}; T.t2 = bp[11];
+    }
+    auto shapes = [&](auto K) NBK_SPEC_INLINE {                 // the shapes of frame K - 1 from the current frame T
+        constexpr int k = decltype(K)::value;
+        sfor<Spec::sh_begin[k], Spec::sh_begin[k + 1]>([&](auto SH) NBK_SPEC_INLINE {
+            constexpr int sh = decltype(SH)::value;
+            const float tl0 = ftb[Spec::f_tl + 3 * sh], tl1 = ftb[Spec::f_tl + 3 * sh + 1], tl2 = ftb[Spec::f_tl + 3 * sh + 2];
+            const V2f cp = fma2(T.Rc[2], splat2(tl2), fma2(T.Rc[1], splat2(tl1), fma2(T.Rc[0], splat2(tl0), T.tc)));
+            const float c2 = __builtin_fmaf(T.R2[2], tl2, __builtin_fmaf(T.R2[1], tl1, __builtin_fmaf(T.R2[0], tl0, T.t2)));
+            cxa[sh] = cp.x; cya[sh] = cp.y; cza[sh] = c2;
+            rmax = __builtin_fmaxf(rmax, __builtin_fmaxf(__builtin_fabsf(cp.x), __builtin_fmaxf(__builtin_fabsf(cp.y), __builtin_fabsf(c2))));
+        });
+    };
+    shapes(IC<0>{});
+    sfor<0, J>([&](auto K) NBK_SPEC_INLINE {
+        constexpr int k = decltype(K)::value;
+        constexpr int kind = Spec::jkind[k];
+        float s = 0.0f, c = 0.0f;
+        if constexpr (kind != JK_PRISMATIC) sincos_f(qv[k], s, c);
+        if constexpr (kind <= 2) {
+            const JPk jp = *reinterpret_cast<const JPk*>(ftb + Spec::f_pk + 20 * k);
+            joint_apply_axis_p<kind>(jp, T, s, c, T);
+        } else {
+            joint_apply_gen_p(ftb + Spec::f_rot + 27 * k, ftb + Spec::f_trans + 3 * k, ftb + Spec::f_slide + 3 * k, T, qv[k], s, c, T);
+        }
+        shapes(IC<k + 1>{});
+    });
+    const float e2 = 2.0f * rmax * __builtin_fmaf(2.4e-7f, qabs, Spec::f_eps);
+    __syncthreads();            // the q slab is dead from here on: its LDS region becomes the item queue
+    int qn = 0;
+#define NBK_SPEC_ENQUEUE(cond_, pidx_)                                                                                          \
+    {                                                                                                                           \
+        const bool c_ = (cond_);                                                                                                \
+        const unsigned long long cm_ = __builtin_amdgcn_ballot_w64(c_);                                                         \
+        if (cm_ != 0ull) {                                                                                                      \
+            if (c_) {                                                                                                           \
+                const int pos_ = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm_, 0u)); \
+                lds_queue[pos_] = ((unsigned)(pidx_) << 6) | (unsigned)lane;                                                    \
+            }                                                                                                                   \
+            qn += __builtin_popcountll(cm_);                                                                                    \
+        }                                                                                                                       \
+    }
+#define NBK_SPEC_ROOM(slots_)                                                                                                   \
+    if (qn > qcap - (slots_) * WAVE) { flush_items_r(SpecRoute<Spec>{vp_cls}, lds_queue, qn, base, q_count, q_items, cap, lane, ovf); qn = 0; }
+    const float* wbx_all = tab + FO.wbx;
+    if (__builtin_amdgcn_ballot_w64(!(e2 <= Spec::f_e2max)) == 0ull) {
+        // ---- fast stage: world shapes -----------------------------------------------------------------------------------------
+        sfor<0, Spec::NW>([&](auto WI) NBK_SPEC_INLINE {
+            constexpr int wi = decltype(WI)::value;
+            constexpr int w = Spec::wl[wi];
+            constexpr int wk = Spec::wk[wi];
+            const float* wc = ftb + Spec::f_wc + 18 * w;
+            if constexpr (wk == K_BOX || wk == K_HULL) {
+                const float* wb = wbx_all + w * 96;
+                const float* ob = ftb + Spec::f_wobb + 6 * w;
+                int cwv[SB];
+                int acc_c = 0, acc_h = 0;
+                sfor<0, SB / 2>([&](auto I) NBK_SPEC_INLINE {
+                    constexpr int i = decltype(I)::value;
+                    cwv[2 * i] = 0; cwv[2 * i + 1] = 0;
+                    if constexpr (Spec::wpair(wi, 2 * i) >= 0 || Spec::wpair(wi, 2 * i + 1) >= 0) {
+                        const V2f dx = V2f{cxa[2 * i], cxa[2 * i + 1]} - splat2(wc[0]);
+                        const V2f dy = V2f{cya[2 * i], cya[2 * i + 1]} - splat2(wc[1]);
+                        const V2f dz = V2f{cza[2 * i], cza[2 * i + 1]} - splat2(wc[2]);
+                        V2i cand, certh;
+                        if constexpr (wk == K_BOX) box_slot2(dx, dy, dz, wc, wb + 12 * i, cand, certh);
+                        else hull_slot2(dx, dy, dz, wc, ob, wb + 12 * i, cand, certh);
+                        cwv[2 * i] = cand.x; cwv[2 * i + 1] = cand.y;
+                        acc_c |= cand.x | cand.y;
+                        acc_h |= certh.x | certh.y;
+                    }
+                });
+                hit = hit || (acc_h < 0);
+                const bool live = active && !hit;
+                if (__builtin_amdgcn_ballot_w64(acc_c < 0 && live) != 0ull) {
+                    NBK_SPEC_ROOM(S)
+                    sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
+                        constexpr int a = decltype(A)::value;
+                        if constexpr (Spec::wpair(wi, a) >= 0) NBK_SPEC_ENQUEUE(cwv[a] < 0 && live, Spec::wpair(wi, a));
+                    });
+                }
+            } else {
+                // planes and the other kinds: one compare per slot against the table's squared / height thresholds
+                const Row16f wkey2r = *reinterpret_cast<const Row16f*>(tab + FO.wkey2 + w * 16);
+                const Row16f wcertr = *reinterpret_cast<const Row16f*>(tab + FO.wcert + w * 16);
+                const Row16f wkeyr = *reinterpret_cast<const Row16f*>(tab + FO.wkey + w * 16);
+                const int* tab_wp = reinterpret_cast<const int*>(tab + FO.wp);
+                bool c[SB];
+                bool ch = false, anyc = false;
+                sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
+                    constexpr int a = decltype(A)::value;
+                    c[a] = false;
+                    if constexpr (Spec::wpair(wi, a) >= 0) {
+                        if constexpr (wk == K_PLANE) {
+                            if (tab_wp[w * 16 + a] >= 0) plane_slot1(cxa[a] - wc[0], cya[a] - wc[1], cza[a] - wc[2], wc, wkey2r.v[a], wcertr.v[a], c[a], ch);
+                        } else {
+                            if (wkeyr.v[a] >= 0.0f) sphere_slot1(cxa[a] - wc[0], cya[a] - wc[1], cza[a] - wc[2], wkey2r.v[a], wcertr.v[a], c[a], ch);
+                        }
+                        anyc = anyc || c[a];
+                    }
+                });
+                hit = hit || ch;
+                const bool live = active && !hit;
+                if (__builtin_amdgcn_ballot_w64(anyc && live) != 0ull) {
+                    NBK_SPEC_ROOM(S)
+                    sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
+                        constexpr int a = decltype(A)::value;
+                        if constexpr (Spec::wpair(wi, a) >= 0) NBK_SPEC_ENQUEUE(c[a] && live, Spec::wpair(wi, a));
+                    });
+                }
+            }
+        });
+        // ---- fast stage: robot-robot rows, only the groups (2i, 2i + 1) that hold a pair of row a ------------------------------
+        if constexpr (Spec::rr_any) {
+            sfor<0, S - 1>([&](auto A) NBK_SPEC_INLINE {
+                constexpr int a = decltype(A)::value;
+                if constexpr (Spec::row_slots(a) > 0) {
+                    const Row16f nk = *reinterpret_cast<const Row16f*>(tab + FO.rneg + a * 16);
+                    const V2f ax2 = V2f{cxa[a], cxa[a]}, ay2 = V2f{cya[a], cya[a]}, az2 = V2f{cza[a], cza[a]};
+                    V2f ev[SB / 2];
+                    int acc_e = 0;
+                    sfor<(a + 1) / 2, SB / 2>([&](auto I) NBK_SPEC_INLINE {
+                        constexpr int i = decltype(I)::value;
+                        if constexpr (Spec::rr_group(a, i)) {
+                            ev[i] = slot_e2(ax2 - V2f{cxa[2 * i], cxa[2 * i + 1]}, ay2 - V2f{cya[2 * i], cya[2 * i + 1]},
+                                            az2 - V2f{cza[2 * i], cza[2 * i + 1]}, V2f{nk.v[2 * i], nk.v[2 * i + 1]});
+                            const V2i ei = __builtin_bit_cast(V2i, ev[i]);
+                            acc_e |= ei.x | ei.y;
+                        }
+                    });
+                    if (__builtin_amdgcn_ballot_w64(acc_e < 0 && active && !hit) != 0ull) {
+                        const Row16f nd = *reinterpret_cast<const Row16f*>(tab + FO.rnd + a * 16);
+                        int acc_f = 0;
+                        sfor<(a + 1) / 2, SB / 2>([&](auto I) NBK_SPEC_INLINE {
+                            constexpr int i = decltype(I)::value;
+                            if constexpr (Spec::rr_group(a, i)) {
+                                const V2i fi = __builtin_bit_cast(V2i, ev[i] + V2f{nd.v[2 * i], nd.v[2 * i + 1]});
+                                acc_f |= fi.x | fi.y;
+                            }
+                        });
+                        hit = hit || (acc_f < 0);
+                        const bool live = active && !hit;
+                        NBK_SPEC_ROOM(Spec::row_slots(a))
+                        sfor<a + 1, S>([&](auto Bb) NBK_SPEC_INLINE {
+                            constexpr int b = decltype(Bb)::value;
+                            if constexpr (Spec::rr_p(a, b) >= 0) {
+                                const V2i ei = __builtin_bit_cast(V2i, ev[b / 2]);
+                                NBK_SPEC_ENQUEUE(((b % 2) ? ei.y : ei.x) < 0 && live, Spec::rr_p(a, b));
+                            }
+                        });
+                    }
+                }
+            });
+        }
+    } else {
+        // ---- general stage (some lane's slack exceeds the static bound: prismatic travel, huge joint values): the generic
+        // kernel's, over the descriptor's real slots ----------------------------------------------------------------------------
+        const bool cert_ok = e2 <= Spec::f_e2max;
+        bool certh = false;
+        const float* tab_wkey = tab + FO.wkey; const float* tab_wtc = tab + FO.wtc; const float* tab_wcert = tab + FO.wcert;
+        const float* tab_wcin = tab + FO.wcin; const float* tab_rho = tab + FO.rho;
+        const int* tab_wp = reinterpret_cast<const int*>(tab + FO.wp);
+        const int* tab_rp = reinterpret_cast<const int*>(tab + FO.rp);
+        const float* tab_rkey = tab + FO.rkey; const float* tab_rcert = tab + FO.rcert;
+        auto drain = [&](unsigned long long bits, const int* ptab) NBK_SPEC_INLINE {
+            while (true) {
+                const bool has = bits != 0ull;
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
+                if (bal == 0ull) break;
+                if (has) {
+                    const int bit = __builtin_ctzll(bits);
+                    bits &= bits - 1ull;
+                    const unsigned p = (unsigned)ptab[bit];
+                    const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+                    lds_queue[pos] = (p << 6) | (unsigned)lane;
+                }
+                qn += __builtin_popcountll(bal);
+                if (qn > BQ_CAP - WAVE) { flush_items_r(SpecRoute<Spec>{vp_cls}, lds_queue, qn, base, q_count, q_items, cap, lane, ovf); qn = 0; }
+            }
+        };
+        sfor<0, Spec::NW>([&](auto WI) NBK_SPEC_INLINE {
+            constexpr int wi = decltype(WI)::value;
+            constexpr int w = Spec::wl[wi];
+            constexpr int wk = Spec::wk[wi];
+            const float* wc = ftb + Spec::f_wc + 18 * w;
+            unsigned long long bits = 0ull;
+            sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
+                constexpr int a = decltype(A)::value;
+                if constexpr (Spec::wpair(wi, a) >= 0) {
+                    const float dx = cxa[a] - wc[0], dy = cya[a] - wc[1], dz = cza[a] - wc[2];
+                    if constexpr (wk == K_PLANE) {
+                        if (tab_wp[w * 16 + a] >= 0)
+                            bits |= plane_slot_gen(dx, dy, dz, wc, tab_wkey[w * 16 + a], tab_rho[a], e2, tab_wcert[w * 16 + a], certh) ? (1ull << a) : 0ull;
+                    } else if constexpr (wk == K_BOX) {
+                        if (tab_wkey[w * 16 + a] >= 0.0f)
+                            bits |= box_slot_gen(dx, dy, dz, wc, tab_wkey[w * 16 + a], tab_wtc[w * 16 + a], tab_rho[a], e2, tab_wcin[w * 16 + a],
+                                                 certh, hit) ? (1ull << a) : 0ull;
+                    } else {
+                        if (tab_wkey[w * 16 + a] >= 0.0f)
+                            bits |= other_slot_gen(dx, dy, dz, wc, ftb + Spec::f_wobb + 6 * w, wk == K_HULL, tab_wkey[w * 16 + a], tab_wtc[w * 16 + a],
+                                                   tab_rho[a], e2, tab_wcert[w * 16 + a], certh) ? (1ull << a) : 0ull;
+                    }
+                }
+            });
+            hit = hit || (cert_ok && certh);
+            if (!active || hit) bits = 0ull;
+            drain(bits, tab_wp + w * 16);
+        });
+        if constexpr (Spec::rr_any) {
+            sfor<0, S - 1>([&](auto A) NBK_SPEC_INLINE {
+                constexpr int a = decltype(A)::value;
+                unsigned long long bits = 0ull;
+                sfor<a + 1, S>([&](auto Bb) NBK_SPEC_INLINE {
+                    constexpr int b = decltype(Bb)::value;
+                    if constexpr (Spec::rr_p(a, b) >= 0) {
+                        bits |= robot_slot_gen(cxa[a] - cxa[b], cya[a] - cya[b], cza[a] - cza[b], tab_rkey[a * 16 + b], e2, tab_rcert[a * 16 + b], certh)
+                                    ? (1ull << b) : 0ull;
+                    }
+                });
+                hit = hit || (cert_ok && certh);
+                if (!active || hit) bits = 0ull;
+                drain(bits, tab_rp + a * 16);
+            });
+        }
+    }
+#undef NBK_SPEC_ENQUEUE
+#undef NBK_SPEC_ROOM
+    if (qn > 0) flush_items_r(SpecRoute<Spec>{vp_cls}, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
+    const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
+    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
+    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+}
+
+}  // namespace nbk_spec
+
+#ifndef NBK_SPEC_WAVES
+#define NBK_SPEC_WAVES 5
+#endif
+// the generated text defines `struct Spec` before this point
+extern "C" __global__ __launch_bounds__(64, NBK_SPEC_WAVES) void k_broad_f32_spec(
+        const double* __restrict__ q, long long B, const float* __restrict__ ftb, const float* __restrict__ tab,
+        unsigned long long* __restrict__ mask_bits, unsigned char* __restrict__ mask_bytes, unsigned long long* __restrict__ q_count,
+        unsigned long long* __restrict__ q_items, unsigned long long cap, unsigned char* ovf, const int* __restrict__ vp_cls) {
+    nbk_spec::broad_f32_spec<Spec>(q, B, ftb, tab, mask_bits, mask_bytes, q_count, q_items, cap, ovf, vp_cls);
+}
