@@ -60,6 +60,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
     double* lds_raw = lds;
     constexpr int qrows = NQ > (SB + 2) / 2 ? NQ : (SB + 2) / 2;
     constexpr int qcap = qrows * (WAVE * 2);
+    static_assert(qcap >= BQ_CAP && qcap >= S * WAVE, "the q slab must hold the general stage's queue and one unrolled block's items");
     unsigned* lds_queue = reinterpret_cast<unsigned*>(lds_raw);
     if (base >= B) return;
     const int rows_i = (int)((B - base) < WAVE ? (B - base) : WAVE);
