@@ -2652,13 +2652,37 @@ NBK_DEV void mark_hit(long long b, uint64_t* mask_bits, uint8_t* mask_bytes) {
 
 // phase 2's boolean walk: every lane with `have` steps its own item until the last has its verdict; an inflated walk that gives up
 // (r == 3) leaves its item to the caller in `hard`
+// With the kinds (box / cylinder) and the inflation fixed the step is straight-line code (gjkb_step_sl): a trip of the wave is
+// one basic block and one ballot.  Every lane executes it, walker or not -- a lane without `have` steps a state nobody reads, and
+// a step has no memory access -- and the verdict arrives as data; the hits are marked once, after the walk.  gb comes fresh
+// from gjkb_init (both callers), so the first trip is the n == 0 step for every walker.
+// `trips` counts the trips of the wave for the diagnostic build's profile (dead code in the product library).
+#ifndef NBK_WALK_BRANCHED
+#define NBK_WALK_BRANCHED 0            // 1 (A/B builds only): the branched step for every chunk
+#endif
 template <int INFL, int KA, int KB>
 NBK_DEV void narrow_walk(GjkBool& gb, const Core& A, const Core& Bc, double tc, bool& have, bool& hard, long long b,
-                         uint64_t* mask_bits, uint8_t* mask_bytes) {
-    while (__builtin_amdgcn_ballot_w64(have) != 0ull) {
-        if (have) {
-            const int r = gjkb_step_k<INFL, KA, KB>(gb, A, Bc, tc);
-            if (r != 0) { if (r == 2) mark_hit(b, mask_bits, mask_bytes); hard = hard || r == 3; have = false; }
+                         uint64_t* mask_bits, uint8_t* mask_bytes, unsigned& trips) {
+    constexpr bool STRAIGHT = !NBK_WALK_BRANCHED && (INFL == 0 || INFL == 1) && (KA == K_BOX || KA == K_CYL) && (KB == K_BOX || KB == K_CYL);
+    if constexpr (STRAIGHT) {
+        bool hit = false;
+        int r = gjkb_step_sl<INFL, KA, KB, true>(gb, A, Bc, tc);
+        while (true) {
+            trips += 1u;
+            hit = hit || (have && r == 2);
+            hard = hard || (have && r == 3);
+            have = have && r == 0;
+            if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
+            r = gjkb_step_sl<INFL, KA, KB, false>(gb, A, Bc, tc);
+        }
+        if (hit) mark_hit(b, mask_bits, mask_bytes);
+    } else {
+        while (__builtin_amdgcn_ballot_w64(have) != 0ull) {
+            trips += 1u;
+            if (have) {
+                const int r = gjkb_step_k<INFL, KA, KB>(gb, A, Bc, tc);
+                if (r != 0) { if (r == 2) mark_hit(b, mask_bits, mask_bytes); hard = hard || r == 3; have = false; }
+            }
         }
     }
 }
@@ -2670,7 +2694,7 @@ NBK_DEV void narrow_walk(GjkBool& gb, const Core& A, const Core& Bc, double tc, 
 // mixed kinds, mixed choices -- takes the generic step.  Each item runs the same statements in the same order either way.
 template <int INFL>
 NBK_DEV void narrow_walk_any(GjkBool& gb, const Core& A, const Core& Bc, double tc, bool& have, bool& hard, long long b,
-                             uint64_t* mask_bits, uint8_t* mask_bytes) {
+                             uint64_t* mask_bits, uint8_t* mask_bytes, unsigned& trips) {
     const unsigned long long walkers = __builtin_amdgcn_ballot_w64(have);
     if (walkers == 0ull) return;
     const int l0 = __builtin_ctzll(walkers);
@@ -2682,7 +2706,7 @@ NBK_DEV void narrow_walk_any(GjkBool& gb, const Core& A, const Core& Bc, double 
         infl = pos == walkers ? 1 : (pos == 0ull ? 0 : 2);
     }
     const int cls = !same ? 3 : ((ka == K_BOX && kb == K_BOX) ? 0 : ((ka == K_BOX && kb == K_CYL) ? 1 : ((ka == K_CYL && kb == K_CYL) ? 2 : 3)));
-#define NBK_WALK(I, KA_, KB_) narrow_walk<I, KA_, KB_>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes)
+#define NBK_WALK(I, KA_, KB_) narrow_walk<I, KA_, KB_>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes, trips)
     if (cls == 3 || infl == 2) NBK_WALK(INFL, K_ANY, K_ANY);
     else if (infl == 1) {
         if (cls == 0) NBK_WALK(1, K_BOX, K_BOX);
@@ -2747,6 +2771,7 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
     for (unsigned long long chunk = part; chunk * NARROW_T < n; ) {
         const unsigned long long i0 = chunk * NARROW_T;
         unsigned next_ticket = 0u;
+        unsigned trips = 0u;     // trips of this chunk's boolean walk (profile only)
         if (threadIdx.x == 0) next_ticket = (unsigned)atomicAdd(ticket, 1ull);
         chunk = nparts;          // + the ticket, added at the end of the body
         // ---- phase 1 -----------------------------------------------------------------------------------------------
@@ -2862,7 +2887,7 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
                 GjkBool gb;
                 gjkb_init(gb, A, Bc);
                 bool hard = false;     // (never set: the plain walk decides every item)
-                narrow_walk_any<0>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes);
+                narrow_walk_any<0>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes, trips);
             } else if constexpr (MODE == 3) {
                 // tc > 0 everywhere: the boolean walk on the inflated core, then the distance iteration for what it leaves
                 // undecided.  The kernel's time is set by its slowest items: with a cap of 20 steps some 10-2000 items per 1e6
@@ -2873,7 +2898,7 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
                 // hull cores skip the walk: every step scans a vertex list and the distance iteration needs half as many
                 bool hard = have && (A.kind == K_HULL || Bc.kind == K_HULL);
                 have = have && !hard;
-                narrow_walk_any<2>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes);
+                narrow_walk_any<2>(gb, A, Bc, tc, have, hard, b, mask_bits, mask_bytes, trips);
                 if (__builtin_amdgcn_ballot_w64(hard) != 0ull) {
                     GjkPred g;
                     gjk_pred_init(g, A, Bc);
@@ -2914,6 +2939,8 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
             NBK_STAMP(6);
             if (threadIdx.x == 0) {
                 for (int e = 0; e < 6; ++e) atomicAdd(&g_narrow_prof[e], stamp[e + 1] - stamp[e]);
+                atomicAdd(&g_narrow_prof[6], (unsigned long long)trips);
+                atomicMax(&g_narrow_prof[7], (unsigned long long)trips);
                 atomicAdd(&g_narrow_prof[15], 1ull);
                 atomicMax(&g_narrow_prof[14], stamp[6] - stamp[0]);
                 atomicMin(&g_narrow_prof[13], stamp[0]);

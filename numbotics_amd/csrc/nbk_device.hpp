@@ -161,8 +161,10 @@ NBK_DEV void hull_min_max(P hv, int hn, double dl0, double dl1, double dl2, doub
 // support point of one core kind, K fixed at compile time; K_ANY: the kind read at run time (core_support).  The narrowphase walk
 // instantiates the kinds of a kind-homogeneous chunk directly: the run-time form is a per-lane switch over five bodies on both sides
 // of every step, with its exec-mask bookkeeping, where a chunk of box-cylinder items needs one body per side
+// SL (the straight-line walk step, gjkb_step_sl): the cylinder's radial part is computed whatever the direction and the result
+// selected, so that the support is one basic block; the values are the same
 constexpr int K_ANY = -1;
-template <int K>
+template <int K, bool SL = false>
 NBK_DEV void core_support_k(const Core& s, const double* d, double* o) {
     if constexpr (K == K_ANY) {
         switch (s.kind) {
@@ -194,9 +196,14 @@ NBK_DEV void core_support_k(const Core& s, const double* d, double* o) {
         axpy3(sg, s.ax[2], s.c, o);
         // (a direction axial to 1e-13 has no radial part worth the name: see the oracle)
         const double u4 = (uu * uu) * (uu * uu);
-        if (ww > (1e-26 * u4) * dot3(d, d)) {
+        const bool radial = ww > (1e-26 * u4) * dot3(d, d);
+        if (SL || radial) {
+            // (SL: the RESULT is selected, never k -- an infinite k times a zero w must not reach o)
             const double k = s.rad / nbk_sqrt(ww);
-            axpy3(k, w, o, o);
+            double r[3];
+            axpy3(k, w, o, r);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) o[e] = radial ? r[e] : o[e];
         }
     } else if constexpr (K == K_HULL) {
         // direction in local coordinates, first maximum over the vertex list, that vertex back to the world
@@ -626,12 +633,12 @@ constexpr int GJKB_MAXIT = 32;
 constexpr int GJKB_INFL_MAXIT = 64;     // the inflated walk (tc > 0): then the distance iteration decides (figures: see the oracle)
 struct GjkBool { double p[3][3]; int n; double d[3]; int it; };   // p[0] oldest; at most 3 points are kept between steps
 
-template <int KA, int KB>
+template <int KA, int KB, bool SL = false>
 NBK_DEV void mink_support_k(const Core& A, const Core& Bc, const double* d, double* w) {
     const double nd[3] = {-d[0], -d[1], -d[2]};
     double sa[3], sb[3];
-    core_support_k<KA>(A, d, sa);
-    core_support_k<KB>(Bc, nd, sb);
+    core_support_k<KA, SL>(A, d, sa);
+    core_support_k<KB, SL>(Bc, nd, sb);
     sub3(sa, sb, w);
 }
 NBK_DEV void mink_support(const Core& A, const Core& Bc, const double* d, double* w) { mink_support_k<K_ANY, K_ANY>(A, Bc, d, w); }
@@ -673,6 +680,38 @@ NBK_DEV void gjkb_triangle(GjkBool& g, const double* c_in, const double* b_in, c
     }
     g.n = 3;
 }
+// gjkb_triangle as one basic block: every edge normal, dot product and candidate direction is computed, the region flags are
+// derived in the order the nested ifs above test them, and points, n and d are selected.  `line`: the simplex is the segment
+// (b, a) (the n == 1 case of the step, which is the triangle's "star" case on b = p[0]); c is then not looked at.
+// Slots of g.p beyond the new n get a value nobody reads (gjkb_triangle leaves the old one there).
+NBK_DEV void gjkb_triangle_sl(GjkBool& g, const double* c_in, const double* b_in, const double* a_in, bool line) {
+    const double c[3] = {c_in[0], c_in[1], c_in[2]}, b[3] = {b_in[0], b_in[1], b_in[2]}, a[3] = {a_in[0], a_in[1], a_in[2]};
+    double ab[3], ac[3], abc[3], t1[3], t2[3], d_ac[3], d_ab[3];
+    const double ao[3] = {-a[0], -a[1], -a[2]};
+    sub3(b, a, ab); sub3(c, a, ac);
+    cross3(ab, ac, abc);
+    cross3(abc, ac, t1);
+    cross3(ab, abc, t2);
+    tri_prod(ac, ao, d_ac);
+    tri_prod(ab, ao, d_ab);
+    const bool e1 = dot3(t1, ao) > 0.0, f_ac = dot3(ac, ao) > 0.0;
+    const bool e2 = dot3(t2, ao) > 0.0, f_ab = dot3(ab, ao) > 0.0;
+    const bool up = dot3(abc, ao) > 0.0;
+    const bool r_ac = !line && e1 && f_ac;                       // -> (c, a), tri_prod(ac, ao)
+    const bool star = line || (e1 ? !f_ac : e2);
+    const bool r_ab = !r_ac && star && f_ab;                     // -> (b, a), tri_prod(ab, ao)
+    const bool r_a = !r_ac && star && !f_ab;                     // -> (a), ao
+    const bool r_up = !r_ac && !star && up;                      // -> (c, b, a), abc; else (b, c, a), -abc
+    const bool c_first = r_ac || r_up, a_second = r_ac || star;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        g.p[0][e] = c_first ? c[e] : (r_a ? a[e] : b[e]);
+        g.p[1][e] = a_second ? a[e] : (r_up ? b[e] : c[e]);
+        g.p[2][e] = a[e];
+        g.d[e] = r_ac ? d_ac[e] : (r_ab ? d_ab[e] : (r_a ? ao[e] : (r_up ? abc[e] : -abc[e])));
+    }
+    g.n = (r_ac || r_ab) ? 2 : (r_a ? 1 : 3);
+}
 NBK_DEV void gjkb_init(GjkBool& g, const Core& A, const Core& Bc) {
     sub3(A.c, Bc.c, g.d);
     if (dot3(g.d, g.d) == 0.0) { g.d[0] = 1.0; g.d[1] = 0.0; g.d[2] = 0.0; }
@@ -680,6 +719,27 @@ NBK_DEV void gjkb_init(GjkBool& g, const Core& A, const Core& Bc) {
     g.it = 0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) { g.p[i][0] = 0.0; g.p[i][1] = 0.0; g.p[i][2] = 0.0; }
+}
+// the face of the tetrahedron (dd, c, b, a) = (p[0], p[1], p[2], a) that sees the origin, tested in the order abc, acd, adb and
+// picked with selects: x, y = its two older points (the triangle case then takes (x, y, a)).  True: no face sees it, enclosed.
+NBK_DEV bool gjkb_tetra_face(const GjkBool& g, const double* a, double* x, double* y) {
+    double ab[3], ac[3], ad[3], abc[3], acd[3], adb[3];
+    const double ao[3] = {-a[0], -a[1], -a[2]};
+    const double dd[3] = {g.p[0][0], g.p[0][1], g.p[0][2]}, c[3] = {g.p[1][0], g.p[1][1], g.p[1][2]}, b[3] = {g.p[2][0], g.p[2][1], g.p[2][2]};
+    sub3(b, a, ab); sub3(c, a, ac); sub3(dd, a, ad);
+    cross3(ab, ac, abc); cross3(ac, ad, acd); cross3(ad, ab, adb);
+    const double sabc = dot3(abc, ad) > 0.0 ? -1.0 : 1.0;
+    const double sacd = dot3(acd, ab) > 0.0 ? -1.0 : 1.0;
+    const double sadb = dot3(adb, ac) > 0.0 ? -1.0 : 1.0;
+    const bool f0 = sabc * dot3(abc, ao) > 0.0;
+    const bool f1 = !f0 && sacd * dot3(acd, ao) > 0.0;
+    const bool f2 = !f0 && !f1 && sadb * dot3(adb, ao) > 0.0;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        x[e] = f0 ? c[e] : (f1 ? dd[e] : b[e]);
+        y[e] = f0 ? b[e] : (f1 ? c[e] : dd[e]);
+    }
+    return !f0 && !f1 && !f2;
 }
 // one iteration: 0 = continue, 1 = free, 2 = intersecting, 3 = undecided (inflated walk only).
 // INFL 0: the cores as they are (tc == 0).  INFL 1: core A inflated by a ball of radius tc > 0 -- its support point moves by
@@ -715,30 +775,52 @@ NBK_DEV int gjkb_step_k(GjkBool& g, const Core& A, const Core& Bc, double tc = 0
         double x[3], y[3];
         bool enclosed = false;
         if (g.n == 2) { copy3(g.p[0], x); copy3(g.p[1], y); }
-        else {
-            double ab[3], ac[3], ad[3], abc[3], acd[3], adb[3];
-            const double ao[3] = {-a[0], -a[1], -a[2]};
-            const double dd[3] = {g.p[0][0], g.p[0][1], g.p[0][2]}, c[3] = {g.p[1][0], g.p[1][1], g.p[1][2]}, b[3] = {g.p[2][0], g.p[2][1], g.p[2][2]};
-            sub3(b, a, ab); sub3(c, a, ac); sub3(dd, a, ad);
-            cross3(ab, ac, abc); cross3(ac, ad, acd); cross3(ad, ab, adb);
-            const double sabc = dot3(abc, ad) > 0.0 ? -1.0 : 1.0;
-            const double sacd = dot3(acd, ab) > 0.0 ? -1.0 : 1.0;
-            const double sadb = dot3(adb, ac) > 0.0 ? -1.0 : 1.0;
-            const bool f0 = sabc * dot3(abc, ao) > 0.0;
-            const bool f1 = !f0 && sacd * dot3(acd, ao) > 0.0;
-            const bool f2 = !f0 && !f1 && sadb * dot3(adb, ao) > 0.0;
-            enclosed = !f0 && !f1 && !f2;
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                x[e] = f0 ? c[e] : (f1 ? dd[e] : b[e]);
-                y[e] = f0 ? b[e] : (f1 ? c[e] : dd[e]);
-            }
-        }
+        else enclosed = gjkb_tetra_face(g, a, x, y);
         if (enclosed) return 2;
         gjkb_triangle(g, x, y, a);
     }
     if (dot3(g.d, g.d) == 0.0) return infl ? 3 : 2;
     return 0;
+}
+// gjkb_step_k as straight-line code, for the narrowphase walk of a chunk whose kinds (box / cylinder) and inflation (INFL 0 / 1)
+// are fixed: one basic block per trip, so that the independent float64 chains of a step (the two supports, the inflation's
+// square root and division, the face normals, the candidate directions) are scheduled into each other.  Every value an item
+// uses comes from the expression gjkb_step_k evaluates for it (the helpers are shared); what that step decides by a branch is
+// computed here whatever the case and selected.  The verdict is data too, with the precedence of gjkb_step_k's returns.  After
+// a verdict other than 0 the state is not meaningful (gjkb_step_k leaves it as it was; nobody reads it then).
+// FIRST: the step on the state of gjkb_init (n == 0), which every walker of a chunk takes together.  Otherwise n is 1, 2 or 3.
+template <int INFL, int KA, int KB, bool FIRST>
+NBK_DEV int gjkb_step_sl(GjkBool& g, const Core& A, const Core& Bc, double tc) {
+    static_assert(INFL == 0 || INFL == 1, "gjkb_step_sl: the inflation is fixed at compile time");
+    constexpr bool infl = INFL == 1;
+    constexpr int gave_up = infl ? 3 : 2;
+    const bool over = !FIRST && g.it >= (infl ? GJKB_INFL_MAXIT : GJKB_MAXIT);
+    double a[3];
+    mink_support_k<KA, KB, true>(A, Bc, g.d, a);
+    if (infl) {
+        const double k = tc / nbk_sqrt(dot3(g.d, g.d));
+        axpy3(k, g.d, a, a);
+    }
+    const bool free_ = dot3(a, g.d) < 0.0;
+    g.it += 1;
+    bool enclosed = false;
+    if constexpr (FIRST) {
+        copy3(a, g.p[0]); g.n = 1;
+        g.d[0] = -a[0]; g.d[1] = -a[1]; g.d[2] = -a[2];
+    } else {
+        // n == 1: segment (p0, a); n == 2: triangle (p0, p1, a); n == 3: the face of the tetrahedron that sees the origin
+        const bool line = g.n == 1, tetra = g.n == 3;
+        double xt[3], yt[3], x[3], y[3];
+        enclosed = gjkb_tetra_face(g, a, xt, yt) && tetra;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            x[e] = tetra ? xt[e] : g.p[0][e];
+            y[e] = tetra ? yt[e] : (line ? g.p[0][e] : g.p[1][e]);
+        }
+        gjkb_triangle_sl(g, x, y, a, line);
+    }
+    const bool zero = dot3(g.d, g.d) == 0.0;
+    return over ? gave_up : (free_ ? 1 : (enclosed ? 2 : (zero ? gave_up : 0)));
 }
 template <int INFL = 0>
 NBK_DEV int gjkb_step(GjkBool& g, const Core& A, const Core& Bc, double tc = 0.0) { return gjkb_step_k<INFL, K_ANY, K_ANY>(g, A, Bc, tc); }
