@@ -30,7 +30,8 @@
  *     NBK_ERR_INVALID otherwise;
  *   - float64 everywhere (the reference computes in float64); q is row-major (B, n_q);
  *   - return value: NBK_OK or a negative status; no exceptions cross the boundary;
- *   - a descriptor is immutable after creation and may be shared by streams and threads.
+ *   - a descriptor is immutable after creation and may be shared by streams and threads.  One made by nbk_model_create_movable
+ *     is immutable except for its world poses (nbk_model_set_world_poses below).
  */
 #ifndef NBK_H
 #define NBK_H
@@ -115,6 +116,54 @@ int32_t nbk_device_count(void);            /* 0 when no GPU is visible; never fa
 int32_t nbk_model_create(const nbk_model_desc *desc, nbk_model **out);
 void nbk_model_destroy(nbk_model *m);
 int32_t nbk_model_num_pairs(const nbk_model *m);
+
+/*
+ * Moving world bodies (the reference moves an obstacle with one resetBasePositionAndOrientation, numbotics/physics/object.py;
+ * another chain's links move with its configuration).  Additive: nbk_model_create and descriptors made by it behave as before.
+ *
+ * nbk_model_create_movable makes the same descriptor as nbk_model_create -- same pairs, same kernels, accepted by every entry
+ * point -- that is immutable EXCEPT FOR ITS WORLD POSES: the pose-dependent world tables (core frames, centres, the float32
+ * copies of the broadphase, the static reach bounds) are rewritten on the device by an update.  world_radius (finite, >= 0) is the
+ * caller's promise about how far from the origin the centre (pose translation) of a world shape will ever be: the slack of the
+ * float32 broadphase is fixed at creation from max(robot reach, world_radius, the initial centres) and is compiled into the
+ * per-robot broadphase, so poses beyond it are refused, not served.  A larger radius only makes the broadphase more conservative
+ * (more narrowphase items); results stay bit-equal.  NBK_ERR_INVALID for a NaN / negative / infinite radius or an initial pose
+ * that is not finite or lies beyond it.  The library's scratch of such a descriptor is sized for every pair (the host does not
+ * know the poses), not for the pairs within reach.
+ *
+ * nbk_model_set_world_poses: poses (DEVICE) [W][12], 3x4 row-major world poses in the descriptor's world shape order (planes keep
+ * the normal they were created with; only their point moves).  Asynchronous, no allocation, no host synchronisation, capturable:
+ * one memset node and one kernel (k_world_update) in `stream`'s order -- calls issued to that stream afterwards see the new
+ * poses, also the tables the validity path keeps between calls (they are prepared again on every stream of the descriptor).
+ * Checks on OTHER streams are the caller's to order (events), in both directions: an update must not run while another stream
+ * still checks against the descriptor.  The scalar host calls (private stream) wait for the last update issued outside a capture
+ * by themselves; after replaying a graph that holds an update, synchronise before calling them.
+ * Every pose is checked on the device: all 12 values finite and |centre| <= world_radius.  A pose that fails is not applied (its
+ * shape keeps the previous pose) and sets the descriptor's world status; while it is set, EVERY configuration is reported
+ * colliding, every edge and trajectory invalid (status NBK_CA_UNDECIDED unless NBK_CA_DEGENERATE, t_free NaN; a sampled spline
+ * that would have been valid reports t_hit 0), and the distance-valued entry points (closest, pair distances, proximity rows,
+ * records) return NaN everywhere and pair index -1 -- the rule for non-finite joint values, applied to the world, whatever the
+ * geometry is.  The next update whose poses all pass clears it.  NBK_ERR_UNSUPPORTED on a descriptor made by nbk_model_create.
+ *
+ * nbk_model_set_world_poses_host: the same from HOST memory through pinned staging on the private stream of the scalar calls
+ * (nbk_validity_scalar_host, nbk_edge_validity_scalar_host follow it without the caller's help); returns when the update is done.
+ * nbk_model_world_status: synchronous read of the status: 0 ok, 1 a centre beyond world_radius, 2 a non-finite pose.  It waits
+ * for the last update issued outside a capture (not for unrelated streams); after replaying a graph that holds an update,
+ * synchronise that stream first.  Two updates are ordered by the library when one of them is the host entry (it follows the
+ * last direct update); two direct updates on different streams are the caller's to order.
+ * nbk_edge_continuous_batch and nbk_spline_continuous_batch certify against a world that stands still DURING the call.
+ *
+ * nbk_world_reach_bounds_host (no GPU needed): the static reach bounds the update computes, by the same routine on the host.
+ * poses (host) [W][12]; bound (host) [P] in the caller's pair order: a lower bound, over all configurations, of the distance of
+ * the two cores (margins not included) -- |c - b| - reach_a - (rho_a + rho_b), planes n.(b - c) - reach_a - rho_a, with b the base
+ * origin, c the pose's translation, reach_a the sum of |joint_trans| on shape a's path + |its local translation| and rho the
+ * bounding radii -- and -inf for robot-robot pairs and pairs with a prismatic joint on the shape's path.
+ */
+int32_t nbk_model_create_movable(const nbk_model_desc *desc, double world_radius, nbk_model **out);
+int32_t nbk_model_set_world_poses(nbk_model *m, const double *poses /* DEVICE [W][12] */, void *stream);
+int32_t nbk_model_set_world_poses_host(nbk_model *m, const double *poses /* host [W][12] */);
+int32_t nbk_model_world_status(const nbk_model *m, int32_t *status);
+int32_t nbk_world_reach_bounds_host(const nbk_model_desc *desc, const double *poses /* host [W][12] */, double *bound /* [P] */);
 
 /*
  * The float32 broadphase compiled for one robot (hipRTC, on the first validity call of a descriptor with B >= 65536 plain q

@@ -28,6 +28,8 @@ SYMBOLS = [
     "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host", "nbk_spline_validity_batch",
     "nbk_spline_continuous_batch", "nbk_spline_motion_bounds_host",
     "nbk_broad_kernel_used", "nbk_broad_spec_source", "nbk_jit_compile",
+    "nbk_model_create_movable", "nbk_model_set_world_poses", "nbk_model_set_world_poses_host", "nbk_model_world_status",
+    "nbk_world_reach_bounds_host",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -80,6 +82,11 @@ def load():
     lib.nbk_model_destroy.restype = None
     lib.nbk_model_destroy.argtypes = [C.c_void_p]
     lib.nbk_model_create.argtypes = [C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]
+    lib.nbk_model_create_movable.argtypes = [C.POINTER(ModelDesc), C.c_double, C.POINTER(C.c_void_p)]
+    lib.nbk_model_set_world_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.nbk_model_set_world_poses_host.argtypes = [C.c_void_p, C.c_void_p]
+    lib.nbk_model_world_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.nbk_world_reach_bounds_host.argtypes = [C.POINTER(ModelDesc), C.c_void_p, C.c_void_p]
     vp, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
     lib.nbk_fk_batch.argtypes = [vp, vp, i64, vp, i32, vp, vp, vp, vp]
     lib.nbk_jacobian_batch.argtypes = [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp]

@@ -57,7 +57,10 @@ struct DevModel {
     const double* rs_local;       // [S][12]
     const double* rs_core;        // [S][6] h0 h1 h2 rad margin rho
     const int* ws_kind;           // [W]
-    const double* ws_core;        // [W][18] c(3) ax(9: ax0 ax1 ax2) h(3) rad margin rho
+    const double* ws_core;        // [W][18] c(3) ax(9: ax0 ax1 ax2) h(3) rad margin rho.  NOT constant on a movable descriptor
+                                  // (nbk_model_create_movable): k_world_update rewrites [0..11] in place through a const_cast, and
+                                  // likewise ws_center, the [W][18] world cores at f_tab + f_wc and bq_static.  `const` here means
+                                  // "no kernel but k_world_update writes it"; none may keep these four across an update
     const double* hull_blob;      // every hull's [bounding box (6) | vertices (3 n)], back to back: what the HullRef.hv pointers point into
     int hull_blob_n;              // ... in doubles; k_narrow* stage it in LDS when it is at most HULL_LDS_MAX bytes
     const int* pair_a;            // [P] index into rs_* (frame order)
@@ -69,14 +72,14 @@ struct DevModel {
     const int* vp_tab;            // [P][4] refA, refB (user order), class, pad
     const int* vp_canon;          // [P][2] the two refs in canonical (kind-ascending) order
     const double* vp_cst;         // [P][4] mA, mB, rhoA, rhoB (user order)
-    const double* ws_center;      // [W][3]
+    const double* ws_center;      // [W][3]  (rewritten by k_world_update on a movable descriptor, see ws_core)
     int n_plane_pairs, n_closed_pairs;   // class boundaries inside the sorted tables
     const int* rs_frame;          // [S] moving frame of each robot shape (frame order, non-decreasing)
     const unsigned* rs_mask;      // [S] joints on the path from the base to the shape's frame (bit k = joint k)
     // float copies for the conservative float32 broadphase (k_broad_f32): [J][27] rot | [J][3] trans | [J][3] slide |
     // base[12] | [S][3] shape centre offsets | [W][18] world cores; slack = f_eps * max(f_reach, largest |coordinate| of
     // the configuration) covers the float32 error of the sweep 50 times over
-    const float* f_tab;
+    const float* f_tab;           // (the world cores at f_wc are rewritten by k_world_update on a movable descriptor, see ws_core)
     int f_trans, f_slide, f_base, f_tl, f_wc, f_wobb;      // f_wobb: [W][6] local bounding boxes of world hulls (centre, half extents)
     int f_pk;                     // [J][20] per-joint constants of the packed float32 sweep (JPk), 16-byte aligned
     int f_meta;                   // [8] dwords (bit patterns): joint kind | q column << 8 of the first 8 joints
@@ -85,7 +88,8 @@ struct DevModel {
     float f_e2max;                // static bound of the per-lane slack 2e: lanes above it (prismatic travel, |q| sums beyond 64 rad) do not certify hits
     const double* rs_in;          // [S] radius of a ball around the shape's centre that lies inside the shape (margin included)
     const double* ws_in;          // [W] the same for world shapes (0 for planes)
-    const double* bq_static;      // [P] (broadphase order) static lower bound of the pair's centre distance (plane: height) minus the
+    const double* bq_static;      // (rewritten by k_world_update on a movable descriptor, see ws_core)
+                                  // [P] (broadphase order) static lower bound of the pair's centre distance (plane: height) minus the
                                   //     bounding radii, over ALL configurations: reach of the shape's centre from the base; -inf when unknown
     const int* vp_cls;            // [P] kind class of the pair (0 box-box, 1 box-cylinder, 2 cylinder-cylinder, 3 the rest): queue routing
     int cls_base[4], cls_groups[4];   // sub-queues [cls_base[c], cls_base[c] + cls_groups[c]) serve class c, in proportion to its pairs
@@ -140,6 +144,8 @@ struct StreamWs {
     std::mutex mu;                  // two host threads driving one stream (also makes the set non-copyable)
     void* ws = nullptr; size_t ws_bytes = 0;
     bool ready = false; double thr = 0.0; unsigned epoch = 0;
+    unsigned long long world_epoch = 0;   // movable descriptors: the nbk_model::world_epoch the tables were prepared at (an update of the
+                                          // world poses makes them stale)
     bool captured = false;          // a call on this stream has been captured into a hipGraph: its nodes reuse this workspace (counter
                                     // set 0, the tables for THEIR threshold) whenever the graph is replayed, behind the host's back, so
                                     // direct calls on this stream never trust `ready` again -- each prepares its tables and clears both
@@ -204,6 +210,20 @@ struct nbk_model {
     int bf32_state = 0;            // 0 not tried, 1 bf32_fn is loaded, -1 unavailable (hipRTC missing, compile failed, NBK_NO_JIT)
     hipFunction_t bf32_fn = nullptr;
     std::atomic<int> last_broad{0};   // broadphase of the last validity call: 0 none yet, 1 generic k_broad_f32, 2 specialised, 3 another one
+    // nbk_model_create_movable: the world tables (ws_core, ws_center, the float copies at f_tab + f_wc, bq_static) are rewritten in
+    // place by k_world_update; everything else stays immutable.  `world_status` (device) is what the guards of the entry points read.
+    bool movable = false;
+    double world_radius = 0.0;
+    const double* rs_reach = nullptr;         // [S] (device, frame order) reach of each robot shape's centre from the base; inf = unbounded
+    int* world_status = nullptr;              // (device) 0 ok, 1 a centre beyond world_radius, 2 a non-finite pose
+    std::atomic<unsigned long long> world_epoch{0};   // bumped by every update: StreamWs tables prepared before it are stale
+    std::atomic<bool> world_captured{false};  // an update has been captured into a graph: replays move the world behind the host's back,
+                                              // so no stream of this descriptor reuses its tables any more
+    std::mutex world_mu;                      // updates of one descriptor serialise on the host
+    hipEvent_t world_ev = nullptr;            // recorded after the last direct update: the private stream of the scalar calls waits for it
+    bool world_ev_set = false;
+    double* world_stage = nullptr;            // [W][12] pinned + mapped staging of nbk_model_set_world_poses_host
+    double* world_stage_dev = nullptr;
 };
 
 namespace nbk {
@@ -4081,6 +4101,85 @@ static void motion_tables(const nbk_model_desc* d, MotionHost& h) {
     h.pb.assign(d->pair_b, d->pair_b + P); h.pb.resize(P1, 0);
 }
 
+// ---- moving world bodies (nbk_model_create_movable) ------------------------------------------------------------------------------
+// k_world_update rewrites the pose-dependent world tables of a movable descriptor from `poses` [W][12] (3x4 row-major), in stream
+// order: thread t serves world shape t (ws_core[0..11] -- planes keep their normal [9..11] --, ws_center, the float copies at
+// f_tab + f_wc with creation's own casts) and broadphase pair t (bq_static by world_reach_bound, creation's routine, from `poses`
+// directly: no thread reads what another one writes).  A pose that is not finite or whose centre lies beyond the radius promised
+// at creation raises *status and is NOT written (its shape and its pairs keep the last good pose, so every table stays finite and
+// inside the float32 slack the kernels were built for); while *status != 0 the guards below overwrite what the entry points report.
+struct WorldUpd {
+    const double* rs_reach;      // [S] frame order
+    int* status;                 // cleared by a memset node ahead of the kernel
+    double radius;
+};
+
+__global__ void k_world_update(DevModel m, WorldUpd u, const double* __restrict__ poses) {
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t < m.n_wshapes) {
+        const double* T = poses + 12 * (size_t)t;
+        const int bad = world_pose_status(T, u.radius);
+        if (bad != 0) atomicMax(u.status, bad);
+        else {
+            double v[12];
+            v[0] = T[3]; v[1] = T[7]; v[2] = T[11];
+            for (int j = 0; j < 3; ++j) { v[3 + 3 * j] = T[j]; v[4 + 3 * j] = T[4 + j]; v[5 + 3 * j] = T[8 + j]; }
+            double* o = const_cast<double*>(m.ws_core) + 18 * (size_t)t;
+            float* f = const_cast<float*>(m.f_tab) + m.f_wc + 18 * (size_t)t;
+            double* z = const_cast<double*>(m.ws_center) + 3 * (size_t)t;
+            const int n = m.ws_kind[t] == K_PLANE ? 9 : 12;
+            for (int e = 0; e < n; ++e) { o[e] = v[e]; f[e] = (float)v[e]; }
+            z[0] = v[0]; z[1] = v[1]; z[2] = v[2];
+        }
+    }
+    if (t < m.n_pairs) {
+        const int cat = m.bq_tab[4 * t + 3];
+        if (cat != 1) {
+            const int a = m.bq_tab[4 * t] / 3, w = m.bq_tab[4 * t + 1], i = m.bq_tab[4 * t + 2];
+            const double reach = u.rs_reach[a];
+            const double* T = poses + 12 * (size_t)w;
+            if (reach < NBK_INF && world_pose_status(T, u.radius) == 0) {
+                const double c[3] = {T[3], T[7], T[11]};
+                const double b0[3] = {m.base_pose[3], m.base_pose[7], m.base_pose[11]};
+                const_cast<double*>(m.bq_static)[t] = world_reach_bound(cat == 0, c, m.ws_core + 18 * (size_t)w + 9, b0, reach,
+                                                                        m.vp_cst[4 * i + 2], m.vp_cst[4 * i + 3]);
+            }
+        }
+    }
+}
+
+// What an entry point reports while the world status of its movable descriptor is set, whatever the geometry says: every
+// configuration collides, every edge / trajectory is invalid (UNDECIDED unless it was DEGENERATE; a sampled trajectory that was
+// valid is hit at its first sample), every distance-valued output is NaN and every pair index -1.  Launched last on the call's
+// stream; with status 0 it returns at once.
+struct WorldGuard {
+    unsigned long long* bits; unsigned char* bytes; long long n_mask;
+    unsigned char* valid; int* ca_status; double* t_hit; long long n_valid;
+    double* f[3]; long long nf[3];
+    int* idx; long long n_idx;
+};
+
+__global__ void k_world_guard(const int* __restrict__ status, WorldGuard g) {
+    if (*status == 0) return;
+    const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    if (g.bits != nullptr) {
+        const long long nw = (g.n_mask + 63) / 64;
+        for (long long w = t0; w < nw; w += step)
+            g.bits[w] = (w == nw - 1 && (g.n_mask & 63) != 0) ? ((1ull << (g.n_mask & 63)) - 1ull) : ~0ull;
+    }
+    if (g.bytes != nullptr) for (long long b = t0; b < g.n_mask; b += step) g.bytes[b] = 1;
+    for (long long e = t0; e < g.n_valid; e += step) {
+        if (g.valid != nullptr) {
+            if (g.t_hit != nullptr && g.valid[e] != 0) g.t_hit[e] = 0.0;
+            g.valid[e] = 0;
+        }
+        if (g.ca_status != nullptr && g.ca_status[e] != NBK_CA_DEGENERATE) g.ca_status[e] = NBK_CA_UNDECIDED;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (g.f[k] != nullptr) for (long long i = t0; i < g.nf[k]; i += step) g.f[k][i] = __builtin_nan("");
+    if (g.idx != nullptr) for (long long i = t0; i < g.n_idx; i += step) g.idx[i] = -1;
+}
+
 }  // namespace nbk
 
 using namespace nbk;
@@ -4314,7 +4413,10 @@ static hipFunction_t bf32_function(const std::string& spec) {
     return fn;
 }
 
-static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only);
+// what nbk_world_reach_bounds_host needs of a descriptor: per robot-world pair its user index, world shape, reach and radii
+struct ReachOut { std::vector<int> user, w, plane; std::vector<double> reach, rhoA, rhoB; };
+static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only, const double* world_radius = nullptr,
+                                 ReachOut* reach_only = nullptr);
 
 int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     if (d == nullptr || out == nullptr) return NBK_ERR_INVALID;
@@ -4347,7 +4449,8 @@ int64_t nbk_jit_compile(const char* src, const char* arch) {
 
 int32_t nbk_broad_kernel_used(const nbk_model* m) { return m == nullptr ? NBK_ERR_INVALID : m->last_broad.load(std::memory_order_relaxed); }
 
-static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only) {
+static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only, const double* world_radius,
+                                 ReachOut* reach_only) {
     const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
     if (d->n_q < 0 || J < 0 || S < 0 || W < 0 || P < 0) return NBK_ERR_INVALID;
     if (J > NBK_MAX_JOINTS || d->n_q > NBK_MAX_DOF) return NBK_ERR_UNSUPPORTED;
@@ -4538,8 +4641,8 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
     // (sum of the joint offsets on its path + its local offset; unbounded when a prismatic joint is on the path), so a world
     // shape farther than that from the base, radii included, can never be a candidate.  Rigorous by the triangle inequality.
     std::vector<double> bq_static((size_t)(P > 0 ? P : 1), -INFINITY);
+    std::vector<double> reach(S > 0 ? S : 1, 0.0);          // per robot shape (frame order); k_world_update reads a device copy
     {
-        std::vector<double> reach(S > 0 ? S : 1, 0.0);
         for (int i = 0; i < S; ++i) {
             const int f = d->rshape_frame[order[i]];
             double r = 0.0;
@@ -4562,15 +4665,14 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
             const int a = bq_tab[4 * j] / 3, w = bq_tab[4 * j + 1], i = bq_tab[4 * j + 2];
             const double* wc = &ws_core[18 * (size_t)w];
             if (!(reach[a] < INFINITY)) continue;
-            if (cat == 0) {
-                const double hb = wc[9] * (b0[0] - wc[0]) + wc[10] * (b0[1] - wc[1]) + wc[11] * (b0[2] - wc[2]);
-                bq_static[j] = hb - reach[a] - vp_cst[4 * i + 2];
-            } else {
-                const double dx = wc[0] - b0[0], dy = wc[1] - b0[1], dz = wc[2] - b0[2];
-                bq_static[j] = std::sqrt(dx * dx + dy * dy + dz * dz) - reach[a] - (vp_cst[4 * i + 2] + vp_cst[4 * i + 3]);
+            if (reach_only != nullptr) {
+                reach_only->user.push_back(vp_tab[4 * i + 3]); reach_only->w.push_back(w); reach_only->plane.push_back(cat == 0 ? 1 : 0);
+                reach_only->reach.push_back(reach[a]); reach_only->rhoA.push_back(vp_cst[4 * i + 2]); reach_only->rhoB.push_back(vp_cst[4 * i + 3]);
             }
+            bq_static[j] = world_reach_bound(cat == 0, wc, wc + 9, b0, reach[a], vp_cst[4 * i + 2], vp_cst[4 * i + 3]);
         }
     }
+    if (reach_only != nullptr) return NBK_OK;
     if (3 * S >= 65536 || W >= 65536) return NBK_ERR_UNSUPPORTED;
     // the LDS broadphase (robots with more than 16 primitives) keeps the pair constants and world cores in LDS; robots the
     // register broadphases serve do not need it, however many world shapes there are
@@ -4704,14 +4806,14 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
     }
     std::vector<float> ftab;
     int f_trans, f_slide, f_base, f_tl, f_wc, f_wobb = 0, f_pk = 0, f_meta = 0, f_chain = 0;
-    double reach = 0.0;
+    double freach = 0.0;
     {
         for (int k = 0; k < J; ++k) for (int e = 0; e < 27; ++e) ftab.push_back((float)d->joint_rot[27 * k + e]);
         f_trans = (int)ftab.size();
         for (int k = 0; k < J; ++k) {
             double n2 = 0.0;
             for (int e = 0; e < 3; ++e) { ftab.push_back((float)d->joint_trans[3 * k + e]); n2 += d->joint_trans[3 * k + e] * d->joint_trans[3 * k + e]; }
-            reach += std::sqrt(n2);
+            freach += std::sqrt(n2);
         }
         f_slide = (int)ftab.size();
         for (int k = 0; k < J; ++k) for (int e = 0; e < 3; ++e) ftab.push_back((float)d->joint_slide[3 * k + e]);
@@ -4720,7 +4822,7 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
             double n2 = 0.0;
             for (int e = 0; e < 12; ++e) ftab.push_back((float)d->base_pose[e]);
             for (int i = 0; i < 3; ++i) n2 += d->base_pose[4 * i + 3] * d->base_pose[4 * i + 3];
-            reach += std::sqrt(n2);
+            freach += std::sqrt(n2);
         }
         f_tl = (int)ftab.size();
         double lmax = 0.0;
@@ -4729,14 +4831,16 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
             for (int r = 0; r < 3; ++r) { const double v = rs_local[12 * i + 4 * r + 3]; ftab.push_back((float)v); n2 += v * v; }
             if (std::sqrt(n2) > lmax) lmax = std::sqrt(n2);
         }
-        reach += lmax;
+        freach += lmax;
         f_wc = (int)ftab.size();
         for (int w = 0; w < W; ++w) {
             double n2 = 0.0;
             for (int e = 0; e < 18; ++e) ftab.push_back((float)ws_core[18 * w + e]);
             for (int e = 0; e < 3; ++e) n2 += ws_core[18 * w + e] * ws_core[18 * w + e];
-            if (std::sqrt(n2) > reach) reach = std::sqrt(n2);          // world coordinates enter the differences too
+            if (std::sqrt(n2) > freach) freach = std::sqrt(n2);          // world coordinates enter the differences too
         }
+        // a movable descriptor: every centre its poses may ever have (the caller's promise, checked by k_world_update)
+        if (world_radius != nullptr && *world_radius > freach) freach = *world_radius;
         f_wobb = (int)ftab.size();
         for (int w = 0; w < W; ++w)
             for (int e = 0; e < 6; ++e) {
@@ -4776,7 +4880,7 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
     {
         const double rel = 50.0 * (J + 2) * 16.0 * 5.96e-8;
         f_eps_v = (float)(rel > 1e-4 ? rel : 1e-4);
-        f_reach_v = (float)(reach > 1e-3 ? reach : 1e-3);
+        f_reach_v = (float)(freach > 1e-3 ? freach : 1e-3);
         f_e2max_v = 2.0f * f_reach_v * (f_eps_v + 2.4e-7f * 64.0f) * (1.0f + 1e-6f);
     }
     std::string spec;
@@ -4793,6 +4897,9 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
     o.rf = B.add(rs_frame_v.data(), sizeof(int) * S);
     o.bt = B.add(bq_tab.data(), sizeof(int) * 4 * P);
     o.bs = B.add(bq_static.data(), sizeof(double) * P);
+    const size_t o_rch = B.add(reach.data(), sizeof(double) * S);
+    const int status0[4] = {0, 0, 0, 0};
+    const size_t o_wst = B.add(status0, sizeof(status0));
     // radius of a ball around each shape's centre that lies inside the shape (the float32 broadphase certifies a collision when two
     // such balls overlap): margin + the smallest half extent of the core; hulls: the smallest face offset (0 without planes)
     std::vector<double> rs_in(S > 0 ? S : 1, 0.0), ws_in(W > 0 ? W : 1, 0.0);
@@ -4926,6 +5033,9 @@ static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::
     M->world_hulls = world_hulls;
     M->lds_broad_ok = lds_broad_ok;
     M->parked_ok = parked_ok;
+    M->rs_reach = reinterpret_cast<const double*>(base + o_rch);
+    M->world_status = reinterpret_cast<int*>(static_cast<char*>(dev) + o_wst);
+    if (world_radius != nullptr) { M->movable = true; M->world_radius = *world_radius; }
     (void)hipGetDevice(&M->device);
     *out = M;
     return NBK_OK;
@@ -4938,6 +5048,8 @@ void nbk_model_destroy(nbk_model* m) {
     if (m->scalar_q) (void)hipHostFree(m->scalar_q);
     if (m->scalar_out) (void)hipHostFree(m->scalar_out);
     if (m->scalar_stream) (void)hipStreamDestroy(m->scalar_stream);
+    if (m->world_ev) (void)hipEventDestroy(m->world_ev);
+    if (m->world_stage) (void)hipHostFree(m->world_stage);
     delete m;
 }
 
@@ -5211,6 +5323,9 @@ static inline PairCounts reachable_pairs(const nbk_model* m, double thr) {
     }
     return c;
 }
+// what the library's own scratch is sized for: a movable descriptor's poses are the device's business (the host's h_static is
+// creation's), so it sizes for every pair; the budget + k_validity_redo stay the safety net
+static inline PairCounts sized_pairs(const nbk_model* m, double thr) { return m->movable ? all_pairs(m) : reachable_pairs(m, thr); }
 static inline unsigned long long sub_queue_cap(const nbk_model* m, const PairCounts& pc, unsigned long long nblk) {
     unsigned long long cap = WAVE;
     for (int c = 0; c < 4; ++c) {
@@ -5338,6 +5453,9 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
     // the build with everything
     const int narrow_build = narrow_variant(m, threshold);
     const int S = m->d.n_rshapes;
+    // tables prepared before the last update of a movable descriptor's world poses are stale
+    const unsigned long long world_epoch = m->world_epoch.load(std::memory_order_acquire);
+    const bool world_captured = m->world_captured.load(std::memory_order_acquire);
     const bool use_reg = S <= 16 && (!g_opt.no_reg_broad || !m->lds_broad_ok);
     const bool f32 = !g_opt.f64_broad || broad_reg_lds(m, broad_bucket(S)) > LDS_MAX;   // the float64 form keeps its tables in LDS
     // the broadphase compiled for this robot (plain q rows, large calls; compiled on the first such call, never inside a capture)
@@ -5382,14 +5500,14 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
         const size_t lds_f = sizeof(double) * WAVE * qrows_f + sizeof(float) * WAVE * 12 * (size_t)m->d.frame_slots + 16 + sizeof(float) * WAVE * NBK_ZSLOTS;   // (+ the z coordinates of the slots k_broad_f32 keeps in LDS)
         unsigned long long* count_next = nullptr;
         if (use_reg && f32) {
-            if (internal && iw->ready && !iw->captured && iw->thr == threshold) {
+            if (internal && iw->ready && !iw->captured && iw->thr == threshold && iw->world_epoch == world_epoch && !world_captured) {
                 // tables are in place and the previous call's narrowphase cleared this call's counter set: no launch
                 count = count_set0 + (size_t)(iw->epoch & 1u) * NSUB * CNT_STRIDE;
                 count_next = count_set0 + (size_t)((iw->epoch + 1u) & 1u) * NSUB * CNT_STRIDE;
             } else {
                 count = count_set0;
                 hipLaunchKernelGGL(k_prepare_f32, dim3(1), dim3(NSUB), 0, st, m->d, threshold, count_set0, internal ? 2 : 1, ftab, flag_words, n_flag_words);   // clears the counters too
-                if (internal) { iw->ready = true; iw->thr = threshold; iw->epoch = 0; count_next = count_set0 + (size_t)NSUB * CNT_STRIDE; }
+                if (internal) { iw->ready = true; iw->thr = threshold; iw->world_epoch = world_epoch; iw->epoch = 0; count_next = count_set0 + (size_t)NSUB * CNT_STRIDE; }
             }
             if (internal) iw->epoch += 1u;
         } else {
@@ -5471,6 +5589,39 @@ static int32_t pipe_setup(nbk_model* mm, const nbk_model* m, const PairCounts& p
     return ensure_validity_ws(m, w->aux, (size_t)two_kernel_workspace_bytes(m, pc, B, true), w->aux_stream, "hipMalloc(workspace, second stream)");
 }
 
+// the last launch of an entry point on a movable descriptor (k_world_guard); nothing for an ordinary one
+static int32_t world_guard(const nbk_model* m, hipStream_t st, const WorldGuard& g) {
+    if (!m->movable) return NBK_OK;
+    long long n = (g.bits != nullptr || g.bytes != nullptr) ? g.n_mask : 0;
+    if ((g.valid != nullptr || g.ca_status != nullptr) && g.n_valid > n) n = g.n_valid;
+    for (int k = 0; k < 3; ++k) if (g.f[k] != nullptr && g.nf[k] > n) n = g.nf[k];
+    if (g.idx != nullptr && g.n_idx > n) n = g.n_idx;
+    if (n <= 0) return NBK_OK;
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_world_guard, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, (const int*)m->world_status, g);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+static int32_t guard_masks(const nbk_model* m, int32_t rc, uint64_t* bits, uint8_t* bytes, int64_t B, hipStream_t st) {
+    if (rc != NBK_OK || !m->movable) return rc;
+    WorldGuard g = {};
+    g.bits = reinterpret_cast<unsigned long long*>(bits); g.bytes = bytes; g.n_mask = B;
+    return world_guard(m, st, g);
+}
+static int32_t guard_dists(const nbk_model* m, hipStream_t st, double* f0, long long n0, double* f1, long long n1, double* f2, long long n2,
+                           int* idx, long long n_idx) {
+    if (!m->movable) return NBK_OK;
+    WorldGuard g = {};
+    g.f[0] = f0; g.nf[0] = n0; g.f[1] = f1; g.nf[1] = n1; g.f[2] = f2; g.nf[2] = n2; g.idx = idx; g.n_idx = n_idx;
+    return world_guard(m, st, g);
+}
+static int32_t guard_verdicts(const nbk_model* m, hipStream_t st, uint8_t* valid, int32_t* ca_status, double* t_hit, double* t_free, long long n) {
+    if (!m->movable) return NBK_OK;
+    WorldGuard g = {};
+    g.valid = valid; g.ca_status = ca_status; g.t_hit = t_hit; g.n_valid = n; g.f[0] = t_free; g.nf[0] = n;
+    return world_guard(m, st, g);
+}
+
 int64_t nbk_validity_workspace_bytes(const nbk_model* m, int64_t B) {
     if (m == nullptr || B < 0) return NBK_ERR_INVALID;
     if ((B < g_opt.two_kernel_min_b && m->parked_ok) || m->n_pairs == 0 || B == 0) return 0;
@@ -5496,9 +5647,9 @@ int32_t nbk_validity_batch_ws(const nbk_model* m, const double* q, int64_t B, do
         if (!m->parked_ok) return need != 0 ? NBK_ERR_INVALID : NBK_ERR_UNSUPPORTED;   // this robot needs the workspace path
         hipLaunchKernelGGL(k_validity, dim3(blocks_for(B)), dim3(WAVE), collide_lds(m), st, m->d, q, B, threshold, mask_bits, mask_bytes);
         NBK_HIP(hipGetLastError());
-        return NBK_OK;
+        return guard_masks(m, NBK_OK, mask_bits, mask_bytes, B, st);
     }
-    return launch_two_kernel(m, all_pairs(m), NO_EDGES, q, B, threshold, mask_bits, mask_bytes, workspace, st);
+    return guard_masks(m, launch_two_kernel(m, all_pairs(m), NO_EDGES, q, B, threshold, mask_bits, mask_bytes, workspace, st), mask_bits, mask_bytes, B, st);
 }
 
 int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
@@ -5509,7 +5660,7 @@ int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, doubl
     NBK_DEVICE(m);
     // the library's own scratch is sized for the pairs that are within reach at THIS threshold (obstacle-rich scenes: most world
     // shapes are out of the arm's reach for good)
-    const PairCounts pc = reachable_pairs(m, threshold);
+    const PairCounts pc = sized_pairs(m, threshold);
     hipStream_t st = (hipStream_t)stream;
     const bool capturing = stream_capturing(st);
     const bool pipe = pipelined(m, B) && !capturing;
@@ -5527,7 +5678,8 @@ int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, doubl
     // the graph, and the next direct call starts from scratch as well
     if (capturing) { w->ready = false; w->captured = true; }
     if (pipe) { const int32_t rc = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, B); if (rc != NBK_OK) return rc; }
-    return launch_two_kernel(m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, w->ws, st, capturing ? nullptr : w, pipe);
+    return guard_masks(m, launch_two_kernel(m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, w->ws, st, capturing ? nullptr : w, pipe),
+                       mask_bits, mask_bytes, B, st);
 }
 
 // workgroups that share the pair list of one block of configurations in the per-pair distance kernels: enough to put ~8 waves on
@@ -5556,7 +5708,7 @@ int32_t nbk_closest_batch(const nbk_model* m, const double* q, int64_t B, double
     else
         hipLaunchKernelGGL(k_closest, dim3(blocks_for(B)), dim3(WAVE), closest_lds(m), (hipStream_t)stream, m->d, q, B, min_dist, argmin);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_dists(m, (hipStream_t)stream, min_dist, B, nullptr, 0, nullptr, 0, argmin, B);
 }
 
 int32_t nbk_pair_distances_batch(const nbk_model* m, const double* q, int64_t B, double* dist, double* witness, void* stream) {
@@ -5571,7 +5723,7 @@ int32_t nbk_pair_distances_batch(const nbk_model* m, const double* q, int64_t B,
         hipLaunchKernelGGL(k_distances<1>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), distances_lds(m), (hipStream_t)stream, m->d, q, B, dist,
                            (int32_t*)nullptr, (double*)nullptr);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_dists(m, (hipStream_t)stream, dist, B * m->n_pairs, witness, B * m->n_pairs * 9, nullptr, 0, nullptr, 0);
 }
 
 int32_t nbk_proximity_jacobian_batch(const nbk_model* m, const double* q, int64_t B, double* dist, double* witness, double* jrows,
@@ -5584,7 +5736,7 @@ int32_t nbk_proximity_jacobian_batch(const nbk_model* m, const double* q, int64_
     hipLaunchKernelGGL(k_distances<3>, dim3(blocks_for(B), pair_groups2(m, B)), dim3(2 * WAVE), proximity_lds(m), (hipStream_t)stream, m->d, q, B, dist, (int32_t*)nullptr,
                        witness, jrows);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_dists(m, (hipStream_t)stream, dist, B * m->n_pairs, witness, B * m->n_pairs * 9, jrows, B * m->n_pairs * m->n_q, nullptr, 0);
 }
 
 static inline size_t pair_items_lds(const nbk_model* m, bool rows) {
@@ -5600,7 +5752,7 @@ int32_t nbk_pair_records_items(const nbk_model* m, const double* q, int64_t B, c
     hipLaunchKernelGGL(k_pair_items, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), pair_items_lds(m, jrows != nullptr),
                        (hipStream_t)stream, m->d, q, B, items, N, dist, witness, jrows);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_dists(m, (hipStream_t)stream, dist, N, witness, N * 9, jrows, N * m->n_q, nullptr, 0);
 }
 
 int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
@@ -5627,7 +5779,7 @@ int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, cons
     hipLaunchKernelGGL(k_edge_ca_final, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
                        (const unsigned long long*)key, valid, t_free, status);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_verdicts(m, st, valid, status, nullptr, t_free, E);
 }
 
 // the descriptor checks of the *_motion_bounds_host entries: the parts MotionTab reads
@@ -5751,7 +5903,7 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
         hipLaunchKernelGGL(k_edges, dim3((unsigned)E), dim3(WAVE), collide_lds(m), st, m->d, starts, goals, dist, E,
                            resolution, max_distance, mode, threshold, valid, end, n_samples, (const uint8_t*)nullptr, (unsigned long long*)nullptr);
         NBK_HIP(hipGetLastError());
-        return NBK_OK;
+        return guard_verdicts(m, st, valid, nullptr, nullptr, nullptr, E);
     }
     StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
     if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces"); return NBK_ERR_ALLOC; }
@@ -5770,7 +5922,7 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
         // keep a synchronous sizing step (one read-back) and cannot be captured
         if (capturing) { snprintf(g_err, sizeof(g_err), "graph capture of edge batches needs a robot that fits the LDS-parked layout"); return NBK_ERR_UNSUPPORTED; }
     }
-    const PairCounts pc = reachable_pairs(m, threshold);
+    const PairCounts pc = sized_pairs(m, threshold);
     double* plan = nullptr; uint8_t* ovf = nullptr; uint64_t* words = nullptr;
     unsigned long long *cnt = nullptr, *offs = nullptr, *map = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -5833,7 +5985,7 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
                            resolution, max_distance, mode, threshold, valid, (double*)nullptr, (int32_t*)nullptr, (const uint8_t*)ovf, w->stats_dev);
         NBK_HIP(hipGetLastError());
     }
-    return NBK_OK;
+    return guard_verdicts(m, st, valid, nullptr, nullptr, nullptr, E);
 }
 
 // ---- clamped B-spline trajectories: synchronous (one 8-byte read-back of the sample total sizes the mask words and the tiles) ----
@@ -5892,7 +6044,7 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
     const bool pairs = m->n_pairs > 0;
     const size_t words_bytes = ((size_t)(T + 63) / 64 * 8 + 255) & ~size_t(255);
     const size_t slab_bytes = pairs ? (size_t)tile * (size_t)m->n_q * sizeof(double) : 0;
-    const PairCounts pc = reachable_pairs(m, threshold);
+    const PairCounts pc = sized_pairs(m, threshold);
     if (T > 0) {
         int32_t rc = grow_scratch(st, w->spl, w->spl_bytes, words_bytes + slab_bytes, "hipMalloc(spline samples)");
         if (rc != NBK_OK) return rc;
@@ -5927,7 +6079,7 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
     hipLaunchKernelGGL(k_spline_reduce, dim3((unsigned)S), dim3(WAVE), 0, st, (const double*)plan, (const unsigned long long*)offs,
                        (const uint64_t*)words, valid, t_hit, n_samples);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_verdicts(m, st, valid, nullptr, t_hit, nullptr, S);
 }
 
 // ---- certified continuous B-splines: asynchronous and capturable (knots on the device, nothing read back, nothing allocated) ----
@@ -5965,7 +6117,7 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
     hipLaunchKernelGGL(k_spline_ca_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const unsigned long long*)key, valid,
                        t_free, status);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return guard_verdicts(m, st, valid, status, nullptr, t_free, S);
 }
 
 // ---- scalar calls from host memory (Arm.in_collision(q), DiscreteConnector.connect(a, b) on one configuration / one edge) ----
@@ -5989,6 +6141,10 @@ int32_t nbk_validity_scalar_host(const nbk_model* m, const double* q, double thr
     nbk_model* mm = const_cast<nbk_model*>(m);
     std::lock_guard<std::mutex> lock(mm->scalar_mu);
     { const int32_t rc = scalar_setup(mm); if (rc != NBK_OK) return rc; }
+    if (mm->movable) {
+        std::lock_guard<std::mutex> wl(mm->world_mu);
+        if (mm->world_ev_set) NBK_HIP(hipStreamWaitEvent(mm->scalar_stream, mm->world_ev, 0));     // ordered after the last update
+    }
     memcpy(mm->scalar_q, q, sizeof(double) * (size_t)m->n_q);
     double* dq = mm->scalar_q_dev;
     uint64_t* dout = reinterpret_cast<uint64_t*>(mm->scalar_out_dev);
@@ -6008,6 +6164,10 @@ int32_t nbk_edge_validity_scalar_host(const nbk_model* m, const double* start, c
     nbk_model* mm = const_cast<nbk_model*>(m);
     std::lock_guard<std::mutex> lock(mm->scalar_mu);
     { const int32_t rc = scalar_setup(mm); if (rc != NBK_OK) return rc; }
+    if (mm->movable) {
+        std::lock_guard<std::mutex> wl(mm->world_mu);
+        if (mm->world_ev_set) NBK_HIP(hipStreamWaitEvent(mm->scalar_stream, mm->world_ev, 0));     // ordered after the last update
+    }
     const size_t nq = (size_t)m->n_q;
     double* h = mm->scalar_q;                           // start | goal | end | dist
     memcpy(h, start, sizeof(double) * nq);
@@ -6023,6 +6183,114 @@ int32_t nbk_edge_validity_scalar_host(const nbk_model* m, const double* start, c
     *valid = (int32_t)(reinterpret_cast<const uint8_t*>(mm->scalar_out)[0]);
     if (end != nullptr) memcpy(end, h + 2 * nq, sizeof(double) * nq);
     if (n_samples != nullptr) *n_samples = reinterpret_cast<const int32_t*>(mm->scalar_out + 1)[0];
+    return NBK_OK;
+}
+
+// ---- moving world bodies -----------------------------------------------------------------------------------------------------------
+int32_t nbk_model_create_movable(const nbk_model_desc* d, double world_radius, nbk_model** out) {
+    if (d == nullptr || out == nullptr) return NBK_ERR_INVALID;
+    *out = nullptr;
+    if (!(world_radius >= 0.0 && world_radius <= 1.7976931348623157e308)) {
+        snprintf(g_err, sizeof(g_err), "world_radius must be finite and >= 0");
+        return NBK_ERR_INVALID;
+    }
+    if (d->n_wshapes > 0 && d->wshape_pose == nullptr) return NBK_ERR_INVALID;
+    for (int w = 0; w < d->n_wshapes; ++w)
+        if (world_pose_status(d->wshape_pose + 12 * (size_t)w, world_radius) != 0) {
+            snprintf(g_err, sizeof(g_err), "world shape %d: its pose is not finite or its centre lies beyond world_radius", w);
+            return NBK_ERR_INVALID;
+        }
+    if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
+    return model_create_impl(d, out, nullptr, &world_radius);
+}
+
+// the update on `st` (world_mu held): clear the status word, k_world_update; every stream's tables become stale
+static int32_t world_update_launch(nbk_model* mm, const double* poses, hipStream_t st) {
+    const bool capturing = stream_capturing(st);
+    mm->world_epoch.fetch_add(1, std::memory_order_acq_rel);
+    if (capturing) mm->world_captured.store(true, std::memory_order_release);
+    NBK_HIP(hipMemsetAsync(mm->world_status, 0, sizeof(int), st));
+    const int n = mm->d.n_wshapes > mm->d.n_pairs ? mm->d.n_wshapes : mm->d.n_pairs;
+    if (n > 0) {
+        const WorldUpd u{mm->rs_reach, mm->world_status, mm->world_radius};
+        hipLaunchKernelGGL(k_world_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mm->d, u, poses);
+        NBK_HIP(hipGetLastError());
+    }
+    // the scalar calls run on a private stream: they wait for this event (a captured update cannot be waited for from outside its
+    // graph -- nbk.h says so)
+    if (!capturing) {
+        if (mm->world_ev == nullptr) NBK_HIP(hipEventCreateWithFlags(&mm->world_ev, hipEventDisableTiming));
+        NBK_HIP(hipEventRecord(mm->world_ev, st));
+        mm->world_ev_set = true;
+    }
+    return NBK_OK;
+}
+
+int32_t nbk_model_set_world_poses(nbk_model* m, const double* poses, void* stream) {
+    if (m == nullptr) return NBK_ERR_INVALID;
+    if (!m->movable) return NBK_ERR_UNSUPPORTED;
+    if (m->d.n_wshapes > 0 && poses == nullptr) return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(m->world_mu);
+    return world_update_launch(m, poses, st);
+}
+
+int32_t nbk_model_set_world_poses_host(nbk_model* m, const double* poses) {
+    if (m == nullptr) return NBK_ERR_INVALID;
+    if (!m->movable) return NBK_ERR_UNSUPPORTED;
+    const size_t W = (size_t)m->d.n_wshapes;
+    if (W > 0 && poses == nullptr) return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    std::lock_guard<std::mutex> sl(m->scalar_mu);          // the scalar calls' private stream carries the update: they follow it
+    { const int32_t rc = scalar_setup(m); if (rc != NBK_OK) return rc; }
+    std::lock_guard<std::mutex> lock(m->world_mu);
+    if (m->world_stage == nullptr) {
+        NBK_HIP(hipHostMalloc((void**)&m->world_stage, (W > 0 ? W : 1) * 12 * sizeof(double), hipHostMallocMapped));
+        NBK_HIP(hipHostGetDevicePointer((void**)&m->world_stage_dev, m->world_stage, 0));
+    }
+    if (W > 0) memcpy(m->world_stage, poses, W * 12 * sizeof(double));
+    // two updates must not overtake each other: this one follows the last direct update issued on another stream
+    if (m->world_ev_set) NBK_HIP(hipStreamWaitEvent(m->scalar_stream, m->world_ev, 0));
+    const int32_t rc = world_update_launch(m, m->world_stage_dev, m->scalar_stream);
+    if (rc != NBK_OK) return rc;
+    NBK_HIP(hipStreamSynchronize(m->scalar_stream));       // the staging is free again, and work launched from now on sees the poses
+    return NBK_OK;
+}
+
+int32_t nbk_model_world_status(const nbk_model* m, int32_t* status) {
+    if (m == nullptr || status == nullptr) return NBK_ERR_INVALID;
+    NBK_DEVICE(m);
+    // wait for the last update issued outside a capture (its event), not for every stream of the device
+    {
+        nbk_model* mm = const_cast<nbk_model*>(m);
+        std::lock_guard<std::mutex> lock(mm->world_mu);
+        if (mm->world_ev_set) NBK_HIP(hipEventSynchronize(mm->world_ev));
+    }
+    int v = 0;
+    NBK_HIP(hipMemcpy(&v, m->world_status, sizeof(int), hipMemcpyDeviceToHost));
+    *status = v;
+    return NBK_OK;
+}
+
+int32_t nbk_world_reach_bounds_host(const nbk_model_desc* d, const double* poses, double* bound) {
+    if (d == nullptr) return NBK_ERR_INVALID;
+    { const int32_t rc = motion_desc_check(d); if (rc != NBK_OK) return rc; }
+    const int P = d->n_pairs, W = d->n_wshapes;
+    if (P == 0) return NBK_OK;
+    if (bound == nullptr || (W > 0 && (poses == nullptr || d->wshape_type == nullptr || d->wshape_param == nullptr || d->wshape_pose == nullptr)) ||
+        d->base_pose == nullptr)
+        return NBK_ERR_INVALID;
+    ReachOut ro;
+    const int32_t rc = model_create_impl(d, nullptr, nullptr, nullptr, &ro);
+    if (rc != NBK_OK) return rc;
+    for (int p = 0; p < P; ++p) bound[p] = -INFINITY;
+    const double b0[3] = {d->base_pose[3], d->base_pose[7], d->base_pose[11]};
+    for (size_t k = 0; k < ro.user.size(); ++k) {
+        const double* T = poses + 12 * (size_t)ro.w[k];
+        const double c[3] = {T[3], T[7], T[11]};
+        bound[ro.user[k]] = world_reach_bound(ro.plane[k] != 0, c, d->wshape_param + 4 * (size_t)ro.w[k], b0, ro.reach[k], ro.rhoA[k], ro.rhoB[k]);
+    }
     return NBK_OK;
 }
 

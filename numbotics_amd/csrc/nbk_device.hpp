@@ -1517,4 +1517,27 @@ struct SplineSpanMotion {
     }
 };
 
+// ---- static reach bound of a robot-world pair ----------------------------------------------------------------------------------
+// The centre of robot shape a never leaves the ball of radius `reach` around the base origin b0, so over ALL configurations the
+// distance of the two cores is at least |c - b0| - reach - (rhoA + rhoB) (c the world shape's centre, rho the bounding radii), and
+// the height of a's core over a plane (point c, unit normal n) at least n.(b0 - c) - reach - rhoA.  Rigorous by the triangle
+// inequality.  One routine for nbk_model_create, k_world_update and nbk_world_reach_bounds_host (sqrt is correctly rounded on both
+// sides and nothing is contracted, so the three agree to the bit).
+__host__ __device__ inline double world_reach_bound(bool plane, const double* c, const double* n, const double* b0, double reach,
+                                                    double rhoA, double rhoB) {
+    if (plane) {
+        const double hb = n[0] * (b0[0] - c[0]) + n[1] * (b0[1] - c[1]) + n[2] * (b0[2] - c[2]);
+        return hb - reach - rhoA;
+    }
+    const double dx = c[0] - b0[0], dy = c[1] - b0[1], dz = c[2] - b0[2];
+    return __builtin_sqrt(dx * dx + dy * dy + dz * dz) - reach - (rhoA + rhoB);
+}
+
+// is this 3x4 row-major world pose usable?  0 ok, 1 its centre lies beyond `radius` from the origin, 2 a value is not finite
+__host__ __device__ inline int world_pose_status(const double* T, double radius) {
+    for (int e = 0; e < 12; ++e) if (!(motion_abs(T[e]) <= 1.7976931348623157e308)) return 2;
+    const double n2 = T[3] * T[3] + T[7] * T[7] + T[11] * T[11];
+    return __builtin_sqrt(n2) <= radius ? 0 : 1;
+}
+
 }  // namespace nbk

@@ -131,23 +131,124 @@ def spline_motion_bounds(model, ctrl, knots, degree):
     return mu
 
 
-class DeviceModel:
-    """Immutable device descriptor built from a KinematicModel or SceneModel (robots/model.py)."""
+def _world_poses_host(poses, n_wshapes):
+    """(W, 12) float64 C-contiguous from (W, 12) / (W, 3, 4) / (W, 4, 4) host input."""
+    a = np.asarray(poses, dtype=np.float64)
+    if a.ndim == 3 and a.shape[1:] == (4, 4):
+        a = a[:, :3, :]
+    if a.shape not in ((n_wshapes, 12), (n_wshapes, 3, 4)):
+        raise ValueError(f"world poses must have shape ({n_wshapes}, 12) or ({n_wshapes}, 3, 4), got {a.shape}")
+    return np.ascontiguousarray(a).reshape(n_wshapes, 12)
 
-    def __init__(self, model):
-        _require_gpu()
-        lib = _lib.load()
+
+def world_reach_bounds(model, poses=None):
+    """Static reach bounds (P,) of a SceneModel's pairs, in its pair order, at the world poses ``poses`` ((W, 12) / (W, 3, 4),
+    default: the scene's own): a lower bound over ALL configurations of the distance of the two cores (margins not included),
+    -inf for robot-robot pairs and for shapes behind a prismatic joint.  The routine k_world_update and nbk_model_create cull
+    with, run on the host (nbk_world_reach_bounds_host); no GPU needed."""
+    W = model.n_wshapes
+    ps = _world_poses_host(model.wshape_pose if poses is None else poses, W)
+    d, keep = model_desc(model)
+    out = np.full((int(d.n_pairs),), -np.inf, dtype=np.float64)
+    _lib.check(_lib.load().nbk_world_reach_bounds_host(C.byref(d), ps.ctypes.data, out.ctypes.data), "nbk_world_reach_bounds_host")
+    del keep
+    return out
+
+
+class DeviceModel:
+    """Device descriptor built from a KinematicModel or SceneModel (robots/model.py): immutable, or -- ``movable=True`` --
+    immutable except for the poses of its world shapes, which ``set_world_poses`` rewrites on the device without rebuilding
+    anything (nbk_model_create_movable).  ``world_radius``: how far from the origin a world shape's centre may ever be (poses
+    beyond it are refused on the device: see ``world_status``); default ``robots.model.default_world_radius(scene)``."""
+
+    def __init__(self, model, movable=False, world_radius=None):
         kin = getattr(model, "kin", model)
         scene = model if hasattr(model, "kin") else None
+        if world_radius is not None and not movable:
+            raise ValueError("world_radius is meaningful for movable=True only")
+        if movable:
+            if scene is None:
+                raise ValueError("a movable descriptor needs a SceneModel")
+            if world_radius is None:
+                from numbotics_amd.robots.model import default_world_radius
+                world_radius = default_world_radius(scene)
+            world_radius = float(world_radius)
+            if not (0.0 <= world_radius < np.inf):
+                raise ValueError(f"world_radius must be finite and >= 0, got {world_radius}")
+        _require_gpu()
+        lib = _lib.load()
         self.kin, self.scene = kin, scene
+        self.movable, self.world_radius = bool(movable), world_radius
         d, keep = model_desc(model)
         h = C.c_void_p()
-        _lib.check(lib.nbk_model_create(C.byref(d), C.byref(h)), "nbk_model_create")
+        if movable:
+            _lib.check(lib.nbk_model_create_movable(C.byref(d), world_radius, C.byref(h)), "nbk_model_create_movable")
+        else:
+            _lib.check(lib.nbk_model_create(C.byref(d), C.byref(h)), "nbk_model_create")
         del keep
         self._h = h
         self._lib = lib
         self.n_q = kin.n_q
         self.n_pairs = scene.n_pairs if scene is not None else 0
+
+    # ---- moving world bodies --------------------------------------------------------------------
+    def set_world_poses(self, poses, stream_ordered=False):
+        """Move the world shapes of a movable descriptor: ``poses`` (W, 12) or (W, 3, 4) float64 world poses in the scene's world
+        shape order.  A torch CUDA tensor goes to nbk_model_set_world_poses on the current stream: asynchronous, no allocation, no
+        host synchronisation, capturable -- later calls on that stream see the new poses (other streams: order them with events).
+        A NumPy array goes to nbk_model_set_world_poses_host (returns when the update is done; work already queued on the current
+        stream is waited for first), or, with ``stream_ordered=True``, is copied to the device through a pinned
+        staging buffer of the descriptor (non-blocking; before the buffer is reused the host waits for the PREVIOUS update only,
+        never for the checks queued after it) and issued on the current stream like a tensor: no allocation and no stream
+        synchronisation per move.  Poses that are not finite or lie beyond ``world_radius`` are refused on the device: see ``world_status``."""
+        if not getattr(self, "movable", False):
+            raise NbkError("set_world_poses needs a descriptor made with movable=True (NBK_ERR_UNSUPPORTED)")
+        W = self.scene.n_wshapes
+        torch = _torch()
+        if torch.is_tensor(poses):
+            t = poses
+            if not t.is_cuda or t.dtype != torch.float64:
+                raise ValueError("world poses on the device must be a float64 CUDA tensor")
+            if tuple(t.shape) not in ((W, 12), (W, 3, 4)):
+                raise ValueError(f"world poses must have shape ({W}, 12) or ({W}, 3, 4), got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError("world poses on the device must be contiguous")
+        else:
+            a = _world_poses_host(poses, W)
+            if not stream_ordered:
+                torch.cuda.current_stream().synchronize()
+                _lib.check(self._lib.nbk_model_set_world_poses_host(self._h, a.ctypes.data), "nbk_model_set_world_poses_host")
+                return
+            t = self._stage_world_poses(torch, a)
+        _lib.check(self._lib.nbk_model_set_world_poses(self._h, t.data_ptr(), self._stream()), "nbk_model_set_world_poses")
+        if t is self.__dict__.get("_pose_dev"):
+            self._pose_done.record()
+
+    def _stage_world_poses(self, torch, a):
+        """(W, 12) host poses -> the descriptor's device pose buffer, by a non-blocking copy from its pinned staging buffer on the
+        current stream.  `set_world_poses` records ``_pose_done`` behind the update that reads the device buffer."""
+        st = self.__dict__.get("_pose_stage")
+        if st is None:
+            st = self._pose_stage = torch.empty(a.shape, dtype=torch.float64).pin_memory()
+            self._pose_dev = torch.empty(a.shape, dtype=torch.float64, device="cuda")
+            self._pose_done = torch.cuda.Event()
+        else:
+            self._pose_done.synchronize()          # the previous copy and update are through with both buffers
+        st.copy_(torch.from_numpy(a))
+        self._pose_dev.copy_(st, non_blocking=True)
+        return self._pose_dev
+
+    def world_status(self) -> int:
+        """0: the last update's poses were all applied; 1: a centre lay beyond ``world_radius``; 2: a pose was not finite.  While
+        it is not 0 every configuration is reported colliding, every edge / trajectory invalid and every distance NaN.
+        Synchronises."""
+        out = C.c_int32(0)
+        _lib.check(self._lib.nbk_model_world_status(self._h, C.byref(out)), "nbk_model_world_status")
+        return int(out.value)
+
+    def broad_kernel_used(self) -> int:
+        """Diagnostic: the broadphase of the last validity call (nbk_broad_kernel_used)."""
+        return int(self._lib.nbk_broad_kernel_used(self._h))
 
     def __del__(self):
         h = getattr(self, "_h", None)

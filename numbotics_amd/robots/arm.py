@@ -31,14 +31,34 @@ def _is_tensor(x):
 
 class Arm(Robot):
 
-    def __init__(self, chain, weld_filter: bool = False, compound: bool = True, bullet_margins: bool = True):
+    def __init__(self, chain, weld_filter: bool = False, compound: bool = True, bullet_margins: bool = True,
+                 movable_world: bool = False, world_radius=None):
         """``bullet_margins`` (additive, default True): every box / cylinder / mesh hull that has no explicit ``collision_margin``
         gets the margin Bullet itself applies to the shapes ``pybullet.createCollisionShape`` builds for the reference
         (numbotics/utils/shape.py:60-109; robots/model.py ``bullet_margin``: boxes / cylinders are rounded by
         min(0.04, a tenth of the smallest half extent), hulls inflated by 0.001) -- the restatement closest to the reference's
         ``getClosestPoints`` answers.  ``False`` = the sharp analytic shapes (margin 0); can be switched later through the
-        ``bullet_margins`` property."""
+        ``bullet_margins`` property.
+
+        ``movable_world`` (additive, default False): keep the device scene when a world change moved obstacles only --
+        ``obj.pose = T``, ``cube.position = p``, another chain's ``configuration = q``.  The (small) SceneModel is still recompiled
+        on the host, but when everything except the world shapes' poses is unchanged the new poses are written into the existing
+        descriptor on the device (``DeviceModel.set_world_poses``) in stream order: no descriptor build, no scratch reallocation,
+        captured graphs and cached IRIS bisection graphs stay valid.  Any other change (an object added or removed, a shape resized,
+        a plane turned, pair edits, ``bullet_margins``) rebuilds as without the flag, and so does a centre that leaves
+        ``world_radius`` -- how far from the world origin an obstacle's shape centre may go; default
+        ``robots.model.default_world_radius``: twice the larger of the arm's reach and the farthest obstacle centre of the scene
+        the descriptor is built from.  A generous radius costs a little broadphase precision, never a result."""
         super().__init__(chain)
+        self._movable_world = bool(movable_world)
+        if world_radius is not None:
+            world_radius = float(world_radius)
+            if not self._movable_world:
+                raise ValueError("world_radius is meaningful with movable_world=True only")
+            if not (0.0 <= world_radius < np.inf):
+                raise ValueError(f"world_radius must be finite and >= 0, got {world_radius}")
+        self._world_radius = world_radius
+        self._movable_dev = None       # (structure signature, DeviceModel) of the movable device scene
         self._weld_filter = weld_filter
         self._compound = compound
         self._bullet_margins = bool(bullet_margins)
@@ -69,6 +89,7 @@ class Arm(Robot):
         self._pairs_version = 0
         self._kin_dev = None
         self._scene_cache = None       # (key, SceneModel, DeviceModel)
+        self._retired_dev = None
         self.self_collision_pairs()
 
     @staticmethod
@@ -252,7 +273,16 @@ class Arm(Robot):
     @bullet_margins.setter
     def bullet_margins(self, on: bool):
         self._bullet_margins = bool(on)
+        self._retire_scene_cache()
         self._scene_cache = None
+
+    def _retire_scene_cache(self):
+        """Keep the outgoing device scene alive until its successor exists (``_scene_device`` drops it then).  Freed first, its
+        handle can come straight back from the allocator for the new descriptor, and a caller that compares handles across a
+        rebuild (tests/test_broad_spec.py does) would take the new scene for the old one.  The old scratch goes before the
+        new descriptor allocates any of its own."""
+        if self._scene_cache is not None and self._scene_cache[2] is not None:
+            self._retired_dev = self._scene_cache[2]
 
     def scene_model(self, pairs=None):
         """The flat SceneModel (robots/model.py) of the current world and pair set."""
@@ -262,6 +292,7 @@ class Arm(Robot):
         if self._scene_cache is None or self._scene_cache[0] != key:
             sm = compile_scene(self._chain, self._refreshed_kin(), self._sorted_pairs(self.collision_pairs()),
                                self._compound, self._bullet_margins)
+            self._retire_scene_cache()
             self._scene_cache = (key, sm, None)
         return self._scene_cache[1]
 
@@ -284,9 +315,53 @@ class Arm(Robot):
         sm = self.scene_model()
         key, _, dev = self._scene_cache
         if dev is None:
-            dev = DeviceModel(sm)
+            if self._movable_world:
+                dev = self._moved_scene_device(sm, DeviceModel)
+            else:
+                dev = DeviceModel(sm)
             self._scene_cache = (key, sm, dev)
+            self._retired_dev = None
         return sm, dev
+
+    def _moved_scene_device(self, sm, DeviceModel):
+        """The movable device scene for the freshly compiled ``sm``: the existing descriptor with ``sm``'s world poses when only
+        poses changed and every centre is inside its radius, a new one otherwise."""
+        sig = sm.structure_signature()
+        if self._movable_dev is not None and self._movable_dev[0] == sig:
+            dev = self._movable_dev[1]
+            centres = sm.wshape_pose.reshape(-1, 3, 4)[:, :, 3]
+            if np.all(np.isfinite(sm.wshape_pose)) and (sm.n_wshapes == 0 or float(np.max(np.linalg.norm(centres, axis=1))) <= dev.world_radius):
+                dev.set_world_poses(sm.wshape_pose, stream_ordered=True)
+                dev.scene = sm
+                return dev
+        dev = DeviceModel(sm, movable=True, world_radius=self._world_radius)
+        self._movable_dev = (sig, dev)
+        return dev
+
+    # ---- moving obstacles from device data ---------------------------------------------------------------
+    def set_obstacle_poses(self, poses):
+        """Move the obstacles from DEVICE data (perception output, graph replay; ``movable_world=True`` only): ``poses`` a float64
+        CUDA tensor (W, 3, 4) or (W, 12), the world pose of every world SHAPE in ``scene_model()`` order -- rows
+        ``obstacle_shape_index(obj)`` belong to ``obj``; a caller that holds body poses forms ``body_pose @ local`` on the device
+        with ``obstacle_shape_locals()``.  Issued on the current stream (capturable); it does not touch the Python objects'
+        ``pose``.  When both ways are used, the one applied last wins: these poses hold until the next world change made through
+        the Python objects (which writes THEIR poses for every shape), and the other way round."""
+        if not self._movable_world:
+            raise ValueError("set_obstacle_poses needs an Arm made with movable_world=True")
+        _, dev = self._scene_device()
+        dev.set_world_poses(poses)
+
+    def obstacle_shape_index(self, obj):
+        """Rows of ``set_obstacle_poses`` (world shapes of ``scene_model()``) that belong to ``obj`` (an object, a link of another
+        chain, or its name)."""
+        obj = self._resolve(obj)
+        sm = self.scene_model()
+        return np.array([w for w in range(sm.n_wshapes) if sm.objects[sm.wshape_obj[w]] is obj], dtype=np.int64)
+
+    def obstacle_shape_locals(self):
+        """(W, 4, 4) constant shape-in-body transforms of the world shapes (``robots.model.scene_shape_locals``)."""
+        from .model import scene_shape_locals
+        return scene_shape_locals(self.scene_model(), self._compound, self._bullet_margins)
 
     # ---- kinematics -----------------------------------------------------------------------------------
     def _check_frame_q(self, q, frame):

@@ -299,6 +299,27 @@ class SceneModel:
     def n_pairs(self):
         return int(self.pair_a.shape[0])
 
+    def structure_signature(self) -> bytes:
+        """Digest of everything a device descriptor is built from EXCEPT the world poses (``wshape_pose``): kinematics, shape
+        types and parameters (a plane's normal and the margins are parameters), hull tables, which object each world shape
+        belongs to, the pairs.  Two scenes with equal signatures differ by a rigid move of their obstacles at most, which a movable
+        descriptor absorbs with ``set_world_poses``."""
+        import hashlib
+        h = hashlib.sha256()
+        k = self.kin
+        h.update(np.array([k.n_q, k.n_joints, self.n_rshapes, self.n_wshapes, self.n_pairs, self.n_hulls], dtype=np.int64).tobytes())
+        for a, dt in ((k.joint_parent, np.int32), (k.joint_type, np.int32), (k.joint_qidx, np.int32), (k.joint_rot, np.float64),
+                      (k.joint_trans, np.float64), (k.joint_slide, np.float64), (k.joint_axis, np.float64), (k.base_pose, np.float64),
+                      (self.rshape_frame, np.int32), (self.rshape_type, np.int32), (self.rshape_local, np.float64),
+                      (self.rshape_param, np.float64), (self.wshape_type, np.int32), (self.wshape_param, np.float64),
+                      (self.wshape_obj, np.int32), (self.pair_a, np.int32), (self.pair_b, np.int32),
+                      (self.hull_vert_begin, np.int32), (self.hull_verts, np.float64), (self.hull_face_begin, np.int32),
+                      (self.hull_planes, np.float64)):
+            b = np.ascontiguousarray(a, dtype=dt).tobytes()
+            h.update(len(b).to_bytes(8, "little"))
+            h.update(b)
+        return h.digest()
+
     def pair_members(self, p: int):
         """(subject link, target link-or-object) of pair ``p``."""
         a, b = int(self.pair_a[p]), int(self.pair_b[p])
@@ -425,3 +446,38 @@ def compile_scene(chain, kin: KinematicModel, pairs, compound: bool = True, bull
         objects=objects, links=list(links),
         hull_vert_begin=hvb, hull_verts=hv, hull_face_begin=hfb, hull_planes=hp,
     )
+
+
+def default_world_radius(scene: SceneModel) -> float:
+    """The ``world_radius`` a movable descriptor gets when none is given: twice the larger of the robot's reach (the sum of its
+    joint offsets + the base's distance from the origin + the largest shape offset, as the device's float32 slack counts it) and
+    the farthest world shape centre of the scene as compiled -- room to move every obstacle anywhere the arm can touch it and as
+    far out again, at twice the float32 broadphase slack of the immovable scene."""
+    k = scene.kin
+    reach = float(np.sum(np.linalg.norm(np.asarray(k.joint_trans, dtype=np.float64).reshape(-1, 3), axis=1)))
+    reach += float(np.linalg.norm(np.asarray(k.base_pose, dtype=np.float64).reshape(3, 4)[:, 3]))
+    if scene.n_rshapes:
+        reach += float(np.max(np.linalg.norm(scene.rshape_local.reshape(-1, 3, 4)[:, :, 3], axis=1)))
+    far = float(np.max(np.linalg.norm(scene.wshape_pose.reshape(-1, 3, 4)[:, :, 3], axis=1))) if scene.n_wshapes else 0.0
+    return 2.0 * max(reach, far, 1e-3)
+
+
+def scene_shape_locals(scene: SceneModel, compound: bool = True, bullet_margins: bool = True) -> np.ndarray:
+    """(W, 4, 4) constant shape-in-body transform of every world shape of ``scene``: ``cs.offset``, with a hull's centre folded in
+    -- what ``_shape_records`` multiplies onto the body pose (an object's ``pose``, another chain's link pose), so that
+    ``body_pose @ local`` is the ``wshape_pose`` row a fresh compile would produce."""
+    from numbotics_amd.physics import PhysicsObject
+    out = []
+    for obj in scene.objects:
+        if isinstance(obj, PhysicsObject):
+            shapes = [obj._collision_shape]
+        else:
+            shapes = obj._collision_shapes if compound else [obj._collision_shape]
+        for cs in shapes:
+            if cs.shape == Shape.EMPTY:
+                continue
+            for _, T, _ in _shape_records(cs, np.eye(4), HullTable(), bullet_margins):
+                out.append(np.asarray(T, dtype=np.float64).reshape(4, 4))
+    if len(out) != scene.n_wshapes:
+        raise RuntimeError("scene_shape_locals: the scene's objects do not reproduce its world shapes")
+    return np.array(out, dtype=np.float64).reshape(scene.n_wshapes, 4, 4)
