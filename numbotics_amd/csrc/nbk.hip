@@ -4000,106 +4000,33 @@ __global__ void k_spline_ca_final(int64_t S, const unsigned long long* __restric
     t_free[s] = __builtin_bit_cast(double, k >> 2);
 }
 
+}  // namespace nbk
+
 // ---- host side --------------------------------------------------------------------------------------
+#include "nbk_tables.hpp"            // desc_check, ModelTables, compile_tables: the host-only half of descriptor creation
+
+namespace nbk {
+
+// One device allocation per object, tables 16-byte aligned.  bind() adds the table a pointer field is to point at; resolve() fills the fields.
 struct Blob {
     std::vector<unsigned char> bytes;
+    std::vector<std::pair<void*, size_t>> binds;       // (address of the pointer field, offset of its table)
     size_t add(const void* p, size_t n) {
         size_t off = (bytes.size() + 15) & ~size_t(15);
         bytes.resize(off + n);
         if (n) memcpy(bytes.data() + off, p, n);
         return off;
     }
-};
-
-static void core_params(int type, const double* param, int& kind, double* cc) {
-    cc[0] = cc[1] = cc[2] = cc[3] = cc[4] = 0.0;
-    switch (type) {
-        case NBK_SPHERE: kind = K_POINT; cc[4] = param[0]; break;
-        case NBK_CAPSULE: kind = K_SEG; cc[4] = param[0]; cc[0] = param[1]; break;
-        case NBK_BOX:
-            kind = K_BOX; cc[4] = param[3];
-            cc[0] = param[0] - param[3]; cc[1] = param[1] - param[3]; cc[2] = param[2] - param[3];
-            break;
-        case NBK_CYLINDER: kind = K_CYL; cc[4] = param[3]; cc[3] = param[0] - param[3]; cc[0] = param[1] - param[3]; break;
-        case NBK_HULL: kind = K_HULL; cc[4] = param[3]; break;      // cc[0..2] (the HullRef) and the radius are filled in by the caller
-        default: kind = K_PLANE; break;
+    template <class F, class T>
+    size_t bind(F** field, const T* p, size_t count) {
+        const size_t off = add(p, sizeof(T) * count);
+        binds.emplace_back((void*)field, off);
+        return off;
     }
-}
-
-static double host_bound_radius(int kind, const double* cc) {
-    // must round exactly like the oracle's core_bound_radius
-    switch (kind) {
-        case K_POINT: return 0.0;
-        case K_SEG: return cc[0];
-        case K_CYL: return sqrt(fma(cc[3], cc[3], cc[0] * cc[0]));
-        case K_BOX: return sqrt(fma(cc[2], cc[2], fma(cc[1], cc[1], cc[0] * cc[0])));
-        case K_HULL: return cc[5];                 // stored: hull_bound_radius of its vertices
-        default: return HUGE_VAL;
-    }
-}
-
-// largest vertex norm of a hull; must round exactly like the oracle's hull_bound_radius
-static double hull_bound_radius(const double* v, int n) {
-    double best = 0.0;
-    for (int k = 0; k < n; ++k) {
-        const double r2 = fma(v[3 * k + 2], v[3 * k + 2], fma(v[3 * k + 1], v[3 * k + 1], v[3 * k] * v[3 * k]));
-        if (r2 > best) best = r2;
-    }
-    return sqrt(best);
-}
-
-static int host_core_rows(int kind) { return kind == K_POINT ? 3 : ((kind == K_BOX || kind == K_HULL) ? 12 : 6); }
-
-// core parameters of robot shape s as the descriptor stores them: h0 h1 h2 rad margin rho (rho: bounding radius about the centre)
-static void robot_core_host(const nbk_model_desc* d, int s, int& kind, double* cc) {
-    core_params(d->rshape_type[s], d->rshape_param + 4 * s, kind, cc);
-    if (kind == K_HULL) {
-        const int h = (int)d->rshape_param[4 * s];
-        cc[5] = hull_bound_radius(d->hull_verts + 3 * (size_t)d->hull_vert_begin[h], d->hull_vert_begin[h + 1] - d->hull_vert_begin[h]);
-    }
-    cc[5] = host_bound_radius(kind, cc);
-}
-
-static double norm3_host(const double* v) { return sqrt(fma(v[2], v[2], fma(v[1], v[1], v[0] * v[0]))); }
-
-// host copies of the MotionTab tables (nbk_model_create uploads them; nbk_edge_motion_bounds_host uses them in place)
-struct MotionHost {
-    std::vector<int> jtype, jqidx, pa, pb;
-    std::vector<double> jtn, jsn, sloc, sbnd;
-    std::vector<unsigned> smask;
-    MotionTab view(int J, int S) const {
-        return MotionTab{J, S, jtype.data(), jqidx.data(), jtn.data(), jsn.data(), smask.data(), sloc.data(), sbnd.data(), pa.data(), pb.data()};
+    void resolve(void* dev) const {
+        for (const auto& b : binds) { char* a = static_cast<char*>(dev) + b.second; memcpy(b.first, &a, sizeof(a)); }
     }
 };
-
-// fills h from a descriptor whose joint, shape, hull and pair indices have been checked
-static void motion_tables(const nbk_model_desc* d, MotionHost& h) {
-    const int J = d->n_joints, S = d->n_rshapes, P = d->n_pairs;
-    const size_t J1 = J > 0 ? J : 1, S1 = S > 0 ? S : 1, P1 = P > 0 ? P : 1;
-    h.jtype.assign(J1, 0); h.jqidx.assign(J1, 0); h.jtn.assign(J1, 0.0); h.jsn.assign(J1, 0.0);
-    std::vector<unsigned> fmask(J1, 0u);
-    for (int k = 0; k < J; ++k) {
-        h.jtype[k] = d->joint_type[k];
-        h.jqidx[k] = d->joint_qidx[k];
-        h.jtn[k] = norm3_host(d->joint_trans + 3 * k);
-        h.jsn[k] = norm3_host(d->joint_slide + 3 * k);
-        fmask[k] = (d->joint_parent[k] >= 0 ? fmask[d->joint_parent[k]] : 0u) | (1u << k);
-    }
-    h.smask.assign(S1, 0u); h.sloc.assign(S1, 0.0); h.sbnd.assign(S1, 0.0);
-    for (int x = 0; x < S; ++x) {
-        const int f = d->rshape_frame[x];
-        h.smask[x] = f >= 0 ? fmask[f] : 0u;
-        const double* L = d->rshape_local + 12 * (size_t)x;
-        const double tl[3] = {L[3], L[7], L[11]};
-        h.sloc[x] = norm3_host(tl);
-        int kind;
-        double cc[6];
-        robot_core_host(d, x, kind, cc);
-        h.sbnd[x] = cc[5] + cc[4];
-    }
-    h.pa.assign(d->pair_a, d->pair_a + P); h.pa.resize(P1, 0);
-    h.pb.assign(d->pair_b, d->pair_b + P); h.pb.resize(P1, 0);
-}
 
 // ---- moving world bodies (nbk_model_create_movable) ------------------------------------------------------------------------------
 // k_world_update rewrites the pose-dependent world tables of a movable descriptor from `poses` [W][12] (3x4 row-major), in stream
@@ -4213,85 +4140,8 @@ int32_t nbk_device_count(void) {
 // kBf32SpecHeader as raw string literals).
 #include "nbk_bf32_spec.inc"
 
-// world shapes with a pair that the specialised kernel unrolls at most: every one is a fully unrolled block with its own queue
-// appends (8 cubes made 140 KB of code for a 64 KB instruction cache and an 11 s compile); other scenes keep the generic kernel
-constexpr int SPEC_MAX_WORLD = 2;
 // validity calls smaller than this never pay for a compile
 constexpr int64_t SPEC_MIN_BATCH = 1 << 16;
-
-struct SpecIn {
-    int J, S, W, P, n_q;
-    const int* joint_kind; const int* joint_qidx; const int* begin;    // begin: [J + 2]
-    const int* bq_tab; const int* ws_kind;
-    int f_pk, f_tl, f_base, f_wc, f_wobb, f_trans, f_slide;
-    float f_eps, f_reach, f_e2max;
-    const int* cls_base; const int* cls_groups;
-};
-
-// The `struct Spec` of one descriptor ("" when the robot does not take the specialised kernel: not a serial chain of at most
-// 8 joints, more than 16 shapes, no pairs, too many world shapes)
-static std::string bf32_spec_text(const SpecIn& in) {
-    const int S = in.S, J = in.J;
-    if (in.P == 0 || S < 1 || S > 16 || J < 1 || J > 8) return std::string();
-    std::vector<int> rrp((size_t)S * S, -1), wlist;
-    std::vector<int> wslot_of(in.W > 0 ? in.W : 1, -1);
-    for (int j = 0; j < in.P; ++j) {
-        const int* bt = in.bq_tab + 4 * j;
-        if (bt[3] != 1 && wslot_of[bt[1]] < 0) { wslot_of[bt[1]] = 0; wlist.push_back(bt[1]); }
-    }
-    std::sort(wlist.begin(), wlist.end());
-    if ((int)wlist.size() > SPEC_MAX_WORLD) return std::string();
-    const int NW = (int)wlist.size();
-    for (int i = 0; i < NW; ++i) wslot_of[wlist[i]] = i;
-    std::vector<int> wp((size_t)(NW > 0 ? NW : 1) * S, -1);
-    bool rr_any = false;
-    for (int j = 0; j < in.P; ++j) {
-        const int* bt = in.bq_tab + 4 * j;
-        const int a = bt[0] / 3;
-        if (bt[3] == 1) {
-            const int b = bt[1] / 3, lo = a < b ? a : b, hi = a < b ? b : a;
-            rrp[(size_t)lo * S + hi] = bt[2];
-            rr_any = true;
-        } else {
-            wp[(size_t)wslot_of[bt[1]] * S + a] = bt[2];
-        }
-    }
-    std::string o;
-    char buf[512];
-    auto add = [&](const char* fmt, auto... v) { snprintf(buf, sizeof(buf), fmt, v...); o += buf; };
-    auto arr = [&](const char* name, const std::vector<int>& v) {
-        add("    static constexpr int %s[] = {", name);
-        for (size_t i = 0; i < v.size(); ++i) add(i ? ", %d" : "%d", v[i]);
-        if (v.empty()) o += "-1";
-        o += "};\n";
-    };
-    const int SB = S <= 8 ? 8 : (S <= 12 ? 12 : 16);
-    o += "struct Spec {\n";
-    add("    static constexpr int S = %d, SB = %d, NQ = %d, J = %d, W = %d, NW = %d;\n", S, SB, in.n_q, J, in.W, NW);
-    arr("jkind", std::vector<int>(in.joint_kind, in.joint_kind + J));
-    arr("qcol", std::vector<int>(in.joint_qidx, in.joint_qidx + J));
-    arr("sh_begin", std::vector<int>(in.begin, in.begin + J + 2));
-    add("    static constexpr int f_rot = 0, f_pk = %d, f_tl = %d, f_base = %d, f_wc = %d, f_wobb = %d, f_trans = %d, f_slide = %d;\n",
-        in.f_pk, in.f_tl, in.f_base, in.f_wc, in.f_wobb, in.f_trans, in.f_slide);
-    add("    static constexpr float f_eps = %af, f_reach = %af, f_e2max = %af;\n", (double)in.f_eps, (double)in.f_reach, (double)in.f_e2max);
-    add("    static constexpr bool rr_any = %s;\n", rr_any ? "true" : "false");
-    arr("rrp_", rrp);
-    std::vector<int> wl(wlist), wk;
-    for (int w : wlist) wk.push_back(in.ws_kind[w]);
-    arr("wl", wl);
-    arr("wk", wk);
-    arr("wp_", wp);
-    arr("cls_base", std::vector<int>(in.cls_base, in.cls_base + 4));
-    std::vector<int> groups(in.cls_groups, in.cls_groups + 4);
-    for (int& g : groups) g = g > 0 ? g : 1;             // as DevModel::cls_groups: a divisor, also for a class without pairs
-    arr("cls_groups", groups);
-    o += "    static constexpr int rr_p(int a, int b) { return a >= 0 && b < S && a < b ? rrp_[a * S + b] : -1; }\n"
-         "    static constexpr int wpair(int wi, int a) { return a < S ? wp_[wi * S + a] : -1; }\n"
-         "    static constexpr bool rr_group(int a, int i) { return rr_p(a, 2 * i) >= 0 || rr_p(a, 2 * i + 1) >= 0; }\n"
-         "    static constexpr int row_slots(int a) { int n = 0; for (int b = a + 1; b < S; ++b) n += rr_p(a, b) >= 0 ? 1 : 0; return n; }\n"
-         "};\n";
-    return o;
-}
 
 static std::string bf32_source(const std::string& spec) {
     return spec + "#line 1 \"nbk_bf32_common.hpp\"\n" + kBf32CommonHeader + "#line 1 \"nbk_bf32_spec.hpp\"\n" + kBf32SpecHeader;
@@ -4413,25 +4263,127 @@ static hipFunction_t bf32_function(const std::string& spec) {
     return fn;
 }
 
-// what nbk_world_reach_bounds_host needs of a descriptor: per robot-world pair its user index, world shape, reach and radii
-struct ReachOut { std::vector<int> user, w, plane; std::vector<double> reach, rhoA, rhoB; };
-static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only, const double* world_radius = nullptr,
-                                 ReachOut* reach_only = nullptr);
+// ---- descriptor creation: desc_check -> compile_tables (nbk_tables.hpp) -> pack_model -> upload --------------------------------
+struct HullSlots { size_t rs_core, ws_core, verts, planes; };      // blob offsets of the tables patch_hulls writes into / points at
+
+// the device blob of a compiled descriptor (the order of the binds is its layout), then the scalars of DevModel and the host mirrors
+static HullSlots pack_model(const nbk_model_desc* d, const ModelTables& t, Blob& B, nbk_model& M) {
+    const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs, H = d->n_hulls;
+    DevModel& m = M.d;
+    HullSlots hs;
+    B.bind(&m.joint_type, d->joint_type, J);  B.bind(&m.joint_qidx, d->joint_qidx, J);
+    B.bind(&m.joint_load, t.load.data(), J);  B.bind(&m.joint_save, t.save.data(), J);
+    B.bind(&m.joint_shape_begin, t.begin.data(), J + 2);  B.bind(&m.joint_rot, t.jrot.data(), 27 * (size_t)J);
+    B.bind(&m.joint_kind, t.joint_kind.data(), J);  B.bind(&m.joint_trans, t.jtrans.data(), 3 * (size_t)J);
+    B.bind(&m.joint_slide, d->joint_slide, 3 * (size_t)J);  B.bind(&m.joint_pk, t.joint_pk.data(), t.joint_pk.size());
+    B.bind(&m.joint_axis, d->joint_axis, 3 * (size_t)J);  B.bind(&m.base_pose, d->base_pose, 12);
+    B.bind(&m.rs_kind, t.rs_kind.data(), S);  B.bind(&m.rs_row, t.rs_row.data(), S);
+    B.bind(&m.rs_local, t.rs_local.data(), 12 * (size_t)S);  hs.rs_core = B.bind(&m.rs_core, t.rs_core.data(), 6 * (size_t)S);
+    B.bind(&m.ws_kind, t.ws_kind.data(), W);  hs.ws_core = B.bind(&m.ws_core, t.ws_core.data(), 18 * (size_t)W);
+    B.bind(&m.pair_a, t.pa.data(), P);  B.bind(&m.pair_b, t.pb.data(), P);
+    B.bind(&m.pair_user, t.pu.data(), P);  B.bind(&m.pair_dev, t.pdev.data(), P);
+    m.mt.n_joints = J; m.mt.n_rshapes = S;
+    B.bind(&m.mt.jtype, t.mh.jtype.data(), J);  B.bind(&m.mt.jqidx, t.mh.jqidx.data(), J);
+    B.bind(&m.mt.jtn, t.mh.jtn.data(), J);  B.bind(&m.mt.jsn, t.mh.jsn.data(), J);
+    B.bind(&m.mt.smask, t.mh.smask.data(), S);  B.bind(&m.mt.sloc, t.mh.sloc.data(), S);
+    B.bind(&m.mt.sbnd, t.mh.sbnd.data(), S);
+    B.bind(&m.mt.pa, t.mh.pa.data(), P);  B.bind(&m.mt.pb, t.mh.pb.data(), P);
+    B.bind(&m.vp_tab, t.vp_tab.data(), 4 * (size_t)P);  B.bind(&m.vp_canon, t.vp_canon.data(), 2 * (size_t)P);
+    B.bind(&m.vp_cst, t.vp_cst.data(), 4 * (size_t)P);
+    B.bind(&m.ws_center, t.ws_center.data(), 3 * (size_t)W);  B.bind(&m.rs_mask, t.rs_mask.data(), S);
+    B.bind(&m.vp_info, t.vp_info.data(), 4 * (size_t)P);  B.bind(&m.vp_cls, t.vp_cls.data(), P);          // vp_info: four ints per int4 record
+    B.bind(&m.f_tab, t.ftab.data(), t.ftab.size());
+    B.bind(&m.rs_frame, t.rs_frame.data(), S);  B.bind(&m.bq_tab, t.bq_tab.data(), 4 * (size_t)P);
+    B.bind(&m.bq_static, t.bq_static.data(), P);  B.bind(&M.rs_reach, t.reach.data(), S);
+    const int status0[4] = {0, 0, 0, 0};
+    B.bind(&M.world_status, status0, 4);
+    B.bind(&m.rs_in, t.rs_in.data(), S);  B.bind(&m.ws_in, t.ws_in.data(), W);
+    hs.verts = B.bind(&m.hull_blob, t.hull_blob.data(), t.hull_blob.size());
+    hs.planes = B.add(d->hull_planes, sizeof(double) * 4 * (size_t)(H > 0 ? d->hull_face_begin[H] : 0));
+    B.bytes.resize((B.bytes.size() + 255) & ~size_t(255));
+
+    m.n_q = d->n_q; m.n_joints = J; m.n_rshapes = S; m.n_wshapes = W; m.n_pairs = P;
+    m.shape_rows = t.rows > d->n_q ? t.rows : d->n_q;
+    m.frame_slots = t.slots;
+    m.hull_blob_n = (int)t.hull_blob.size();
+    m.n_plane_pairs = t.n_plane; m.n_closed_pairs = t.n_closed;
+    for (int c = 0; c < 4; ++c) { m.cls_base[c] = t.cls_base[c]; m.cls_groups[c] = t.cls_groups[c] > 0 ? t.cls_groups[c] : 1; }
+    m.f_trans = t.f_trans; m.f_slide = t.f_slide; m.f_base = t.f_base; m.f_tl = t.f_tl; m.f_wc = t.f_wc; m.f_wobb = t.f_wobb;
+    m.f_pk = t.f_pk; m.f_meta = t.f_meta; m.f_chain = t.f_chain;
+    m.f_eps = t.f_eps; m.f_reach = t.f_reach; m.f_e2max = t.f_e2max;
+    for (int i = 0; i < P; ++i) m.bq_count[t.bq_tab[4 * i + 3]]++;          // (from zero: the descriptor is value-initialised)
+#ifdef NBK_ABLATE_BUILD
+    { const char* ab = getenv("NBK_ABLATE"); m.dbg = ab ? atoi(ab) : 0; }
+#else
+    m.dbg = 0;
+#endif
+
+    M.blob_bytes = B.bytes.size();
+    M.n_pairs = P; M.n_q = d->n_q; M.n_joints = J;
+    for (int c = 0; c < 4; ++c) M.cls_count[c] = t.cls_count[c];
+    M.h_static.assign(t.bq_static.begin(), t.bq_static.begin() + P);
+    M.h_m0.resize(P); M.h_m1.resize(P); M.h_cat.resize(P); M.h_cls.resize(P);
+    for (int j = 0; j < P; ++j) {
+        const int i = t.bq_tab[4 * j + 2];
+        M.h_m0[j] = t.vp_cst[4 * (size_t)i]; M.h_m1[j] = t.vp_cst[4 * (size_t)i + 1];
+        M.h_cat[j] = t.bq_tab[4 * j + 3]; M.h_cls[j] = t.vp_cls[i];
+    }
+    M.h_joint_qidx.assign(d->joint_qidx, d->joint_qidx + J);
+    M.h_joint_type.assign(d->joint_type, d->joint_type + J);
+    M.h_joint_kind = t.joint_kind;
+    M.gjk_margins = t.gjk_margins; M.gjk_any_hull = t.gjk_any_hull; M.world_hulls = t.world_hulls; M.margins_zero = t.margins_zero;
+    M.lds_broad_ok = t.lds_broad_ok; M.parked_ok = t.parked_ok;
+    M.bf32_spec = t.spec;
+    return hs;
+}
+
+// hull shapes: their 24-byte h[] slots in the shape tables hold the device addresses of the hull's vertices / planes
+static void patch_hulls(const nbk_model_desc* d, const ModelTables& t, const HullSlots& hs, const void* dev, Blob& B) {
+    auto patch = [&](size_t slot, int h) {
+        HullRef r;
+        r.hv = reinterpret_cast<const double*>(static_cast<const char*>(dev) + hs.verts) + t.hull_off[h];
+        r.hp = reinterpret_cast<const double*>(static_cast<const char*>(dev) + hs.planes) + 4 * (size_t)d->hull_face_begin[h];
+        r.hn = d->hull_vert_begin[h + 1] - d->hull_vert_begin[h];
+        r.hf = d->hull_face_begin[h + 1] - d->hull_face_begin[h];
+        static_assert(sizeof(HullRef) == 24, "HullRef must overlay h[3]");
+        memcpy(B.bytes.data() + slot, &r, sizeof(r));
+    };
+    for (int i = 0; i < d->n_rshapes; ++i) if (t.rs_hull[i] >= 0) patch(hs.rs_core + sizeof(double) * 6 * (size_t)i, t.rs_hull[i]);
+    for (int w = 0; w < d->n_wshapes; ++w) if (t.ws_hull[w] >= 0) patch(hs.ws_core + sizeof(double) * (18 * (size_t)w + 12), t.ws_hull[w]);
+}
+
+static int32_t model_create(const nbk_model_desc* d, const double* world_radius, nbk_model** out) {      // world_radius: movable descriptors
+    { const int32_t rc = desc_check(d, D_ALL); if (rc != NBK_OK) return rc; }
+    ModelTables t;
+    { const int32_t rc = compile_tables(d, world_radius, t); if (rc != NBK_OK) return rc; }
+    std::unique_ptr<nbk_model, decltype(&nbk_model_destroy)> M(new nbk_model(), nbk_model_destroy);      // value-initialised: no blob, no scratch yet
+    Blob B;
+    const HullSlots hs = pack_model(d, t, B, *M);
+    hipError_t e = hipMalloc(&M->blob, B.bytes.size());
+    if (e != hipSuccess) { M->blob = nullptr; hip_fail(e, "hipMalloc(model)"); return NBK_ERR_ALLOC; }
+    B.resolve(M->blob);
+    patch_hulls(d, t, hs, M->blob, B);
+    e = hipMemcpy(M->blob, B.bytes.data(), B.bytes.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(model)");
+    if (world_radius != nullptr) { M->movable = true; M->world_radius = *world_radius; }
+    (void)hipGetDevice(&M->device);
+    *out = M.release();
+    return NBK_OK;
+}
 
 int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     if (d == nullptr || out == nullptr) return NBK_ERR_INVALID;
     *out = nullptr;
     if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
-    return model_create_impl(d, out, nullptr);
+    return model_create(d, nullptr, out);
 }
 
 int64_t nbk_broad_spec_source(const nbk_model_desc* d, char* buf, int64_t cap) {
-    if (d == nullptr) return NBK_ERR_INVALID;
-    std::string spec;
-    const int32_t rc = model_create_impl(d, nullptr, &spec);
-    if (rc != NBK_OK) return rc;
-    if (spec.empty()) return 0;
-    const std::string src = bf32_source(spec);
+    { const int32_t rc = desc_check(d, D_ALL); if (rc != NBK_OK) return rc; }
+    ModelTables t;
+    { const int32_t rc = compile_tables(d, nullptr, t); if (rc != NBK_OK) return rc; }
+    if (t.spec.empty()) return 0;
+    const std::string src = bf32_source(t.spec);
     if (buf != nullptr && cap > 0) {
         const size_t n = src.size() < (size_t)(cap - 1) ? src.size() : (size_t)(cap - 1);
         memcpy(buf, src.data(), n);
@@ -4448,598 +4400,6 @@ int64_t nbk_jit_compile(const char* src, const char* arch) {
 }
 
 int32_t nbk_broad_kernel_used(const nbk_model* m) { return m == nullptr ? NBK_ERR_INVALID : m->last_broad.load(std::memory_order_relaxed); }
-
-static int32_t model_create_impl(const nbk_model_desc* d, nbk_model** out, std::string* spec_only, const double* world_radius,
-                                 ReachOut* reach_only) {
-    const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
-    if (d->n_q < 0 || J < 0 || S < 0 || W < 0 || P < 0) return NBK_ERR_INVALID;
-    if (J > NBK_MAX_JOINTS || d->n_q > NBK_MAX_DOF) return NBK_ERR_UNSUPPORTED;
-    const int H = d->n_hulls;
-    if (H < 0 || (H > 0 && (d->hull_vert_begin == nullptr || d->hull_verts == nullptr || d->hull_face_begin == nullptr))) return NBK_ERR_INVALID;
-    for (int h = 0; h < H; ++h) {
-        if (d->hull_vert_begin[h + 1] <= d->hull_vert_begin[h] || d->hull_face_begin[h + 1] < d->hull_face_begin[h]) return NBK_ERR_INVALID;
-        if (h == 0 && (d->hull_vert_begin[0] != 0 || d->hull_face_begin[0] != 0)) return NBK_ERR_INVALID;
-    }
-    if (H > 0 && d->hull_face_begin[H] > 0 && d->hull_planes == nullptr) return NBK_ERR_INVALID;
-    // face planes: unit outward normals that bound the vertex set (n.v <= d for every vertex).  The float32 broadphase certifies
-    // hits from the ball the planes inscribe and the overlap depth walks them: planes that are not what nbk.h asks for would
-    // produce verdicts neither the narrowphase nor the oracle ever re-examines.
-    for (int h = 0; h < H; ++h) {
-        const double* v = d->hull_verts + 3 * (size_t)d->hull_vert_begin[h];
-        const int nv = d->hull_vert_begin[h + 1] - d->hull_vert_begin[h];
-        double vmax = 0.0;
-        for (int i = 0; i < 3 * nv; ++i) { if (!(fabs(v[i]) <= 1e300)) return NBK_ERR_INVALID; vmax = std::max(vmax, fabs(v[i])); }
-        for (int f = d->hull_face_begin[h]; f < d->hull_face_begin[h + 1]; ++f) {
-            const double* pl = d->hull_planes + 4 * (size_t)f;
-            const double n2 = pl[0] * pl[0] + pl[1] * pl[1] + pl[2] * pl[2];
-            if (!(fabs(n2 - 1.0) <= 1e-9) || !(fabs(pl[3]) <= 1e300)) {
-                snprintf(g_err, sizeof(g_err), "hull %d, plane %d: the normal must have unit length (|n|^2 = %.17g)", h, f - d->hull_face_begin[h], n2);
-                return NBK_ERR_INVALID;
-            }
-            const double tol = 1e-9 * (1.0 + fabs(pl[3]) + vmax);
-            for (int i = 0; i < nv; ++i)
-                if (pl[0] * v[3 * i] + pl[1] * v[3 * i + 1] + pl[2] * v[3 * i + 2] > pl[3] + tol) {
-                    snprintf(g_err, sizeof(g_err), "hull %d, plane %d does not bound vertex %d (n.v - d = %.3g)", h, f - d->hull_face_begin[h], i,
-                             pl[0] * v[3 * i] + pl[1] * v[3 * i + 1] + pl[2] * v[3 * i + 2] - pl[3]);
-                    return NBK_ERR_INVALID;
-                }
-        }
-    }
-    auto hull_ok = [&](double idx) { return idx >= 0.0 && idx < (double)H && idx == (double)(int)idx; };
-    for (int k = 0; k < J; ++k) {
-        if (d->joint_parent[k] >= k || d->joint_parent[k] < -1) return NBK_ERR_INVALID;   // parents first
-        if (d->joint_qidx[k] < 0 || d->joint_qidx[k] >= d->n_q) return NBK_ERR_INVALID;
-        if (d->joint_type[k] != NBK_REVOLUTE && d->joint_type[k] != NBK_PRISMATIC) return NBK_ERR_INVALID;
-    }
-    for (int s = 0; s < S; ++s) {
-        if (d->rshape_frame[s] < -1 || d->rshape_frame[s] >= J) return NBK_ERR_INVALID;
-        const int t = d->rshape_type[s];
-        if (!((t >= NBK_SPHERE && t <= NBK_CYLINDER) || t == NBK_HULL)) return NBK_ERR_INVALID;
-        if (t == NBK_HULL && !hull_ok(d->rshape_param[4 * s])) return NBK_ERR_INVALID;
-    }
-    for (int w = 0; w < W; ++w) {
-        if (d->wshape_type[w] < NBK_SPHERE || d->wshape_type[w] > NBK_HULL) return NBK_ERR_INVALID;
-        if (d->wshape_type[w] == NBK_HULL && !hull_ok(d->wshape_param[4 * w])) return NBK_ERR_INVALID;
-    }
-    for (int p = 0; p < P; ++p) {
-        if (d->pair_a[p] < 0 || d->pair_a[p] >= S) return NBK_ERR_INVALID;
-        if (d->pair_b[p] < 0 || d->pair_b[p] >= S + W) return NBK_ERR_INVALID;
-    }
-    // frame load/save plan: a frame stays in registers when its child is the next joint
-    std::vector<int> load(J), save(J, -1);
-    int slots = 0;
-    for (int k = 0; k < J; ++k) {
-        const int par = d->joint_parent[k];
-        if (par == k - 1) load[k] = (par < 0) ? -1 : -2;
-        else if (par < 0) load[k] = -1;
-        else {
-            if (save[par] < 0) save[par] = slots++;
-            load[k] = save[par];
-        }
-    }
-    // robot shapes in frame order
-    std::vector<int> order;
-    std::vector<int> begin(J + 2, 0);
-    for (int f = -1; f < J; ++f) {
-        begin[f + 1] = (int)order.size();
-        for (int s = 0; s < S; ++s) if (d->rshape_frame[s] == f) order.push_back(s);
-    }
-    begin[J + 1] = (int)order.size();
-    std::vector<int> new_index(S);
-    std::vector<int> rs_kind(S), rs_row(S);
-    std::vector<double> rs_local(12 * (size_t)S), rs_core(6 * (size_t)S);
-    std::vector<int> rs_hull(S > 0 ? S : 1, -1), ws_hull(W > 0 ? W : 1, -1);      // hull index of K_HULL shapes
-    int rows = 0;
-    for (int i = 0; i < S; ++i) {
-        const int s = order[i];
-        new_index[s] = i;
-        int kind;
-        robot_core_host(d, s, kind, &rs_core[6 * i]);
-        if (kind == K_HULL) rs_hull[i] = (int)d->rshape_param[4 * s];
-        rs_kind[i] = kind;
-        rs_row[i] = rows;
-        rows += host_core_rows(kind);
-        memcpy(&rs_local[12 * i], d->rshape_local + 12 * s, 12 * sizeof(double));
-    }
-    std::vector<int> ws_kind(W);
-    bool world_hulls = false;
-    std::vector<double> ws_core(18 * (size_t)W);
-    for (int w = 0; w < W; ++w) {
-        double cc[6];
-        int kind;
-        core_params(d->wshape_type[w], d->wshape_param + 4 * w, kind, cc);
-        cc[5] = 0.0;
-        if (kind == K_HULL) {
-            const int h = (int)d->wshape_param[4 * w];
-            cc[5] = hull_bound_radius(d->hull_verts + 3 * (size_t)d->hull_vert_begin[h], d->hull_vert_begin[h + 1] - d->hull_vert_begin[h]);
-            ws_hull[w] = h;
-        }
-        ws_kind[w] = kind;
-        world_hulls = world_hulls || kind == K_HULL;
-        const double* T = d->wshape_pose + 12 * w;
-        double* o = &ws_core[18 * w];
-        o[0] = T[3]; o[1] = T[7]; o[2] = T[11];
-        for (int j = 0; j < 3; ++j) { o[3 + 3 * j] = T[j]; o[4 + 3 * j] = T[4 + j]; o[5 + 3 * j] = T[8 + j]; }
-        if (kind == K_PLANE) { o[9] = d->wshape_param[4 * w]; o[10] = d->wshape_param[4 * w + 1]; o[11] = d->wshape_param[4 * w + 2]; }
-        o[12] = cc[0]; o[13] = cc[1]; o[14] = cc[2]; o[15] = cc[3]; o[16] = cc[4];
-        o[17] = host_bound_radius(kind, cc);
-    }
-    std::vector<int> pa(P), pb(P), pu(P);
-    for (int p = 0; p < P; ++p) {
-        pa[p] = new_index[d->pair_a[p]];
-        pb[p] = d->pair_b[p] < S ? new_index[d->pair_b[p]] : d->pair_b[p];
-        pu[p] = p;
-    }
-    // validity tables: pairs stably sorted by class, refs (>= 0 robot shape in frame order, < 0 world ~ref)
-    std::vector<int> vcls(P), vorder(P);
-    auto kind_of = [&](int ref) { return ref >= 0 ? rs_kind[ref] : ws_kind[~ref]; };
-    auto core_of = [&](int ref) -> const double* { return ref >= 0 ? &rs_core[6 * ref] : &ws_core[18 * (~ref) + 12]; };
-    std::vector<int> refA(P), refB(P);
-    for (int p = 0; p < P; ++p) {
-        refA[p] = pa[p];
-        refB[p] = pb[p] < S ? pb[p] : ~(pb[p] - S);
-        const int ka = kind_of(refA[p]), kb = kind_of(refB[p]);
-        const bool a_ps = (ka == K_POINT || ka == K_SEG), b_ps = (kb == K_POINT || kb == K_SEG);
-        if (kb == K_PLANE) vcls[p] = 0;
-        else if (ka == K_HULL || kb == K_HULL) vcls[p] = 2;           // hulls have no closed forms: GJK, also against a point
-        else if ((a_ps && b_ps) || ka == K_POINT || kb == K_POINT) vcls[p] = 1;
-        else vcls[p] = 2;
-    }
-    int n_plane = 0, n_closed = 0, cur = 0;
-    for (int c = 0; c < 3; ++c)
-        for (int p = 0; p < P; ++p)
-            if (vcls[p] == c) { vorder[cur++] = p; if (c == 0) ++n_plane; if (c == 1) ++n_closed; }
-    std::vector<int> vp_tab(4 * (size_t)P), vp_canon(2 * (size_t)P);
-    std::vector<double> vp_cst(4 * (size_t)P), ws_center(3 * (size_t)W);
-    bool margins_zero = true;
-    std::vector<double> gjk_margins;
-    bool gjk_any_hull = false;
-    for (int i = 0; i < P; ++i) {
-        const int p = vorder[i];
-        const int ka = kind_of(refA[p]), kb = kind_of(refB[p]);
-        vp_tab[4 * i] = refA[p]; vp_tab[4 * i + 1] = refB[p]; vp_tab[4 * i + 2] = vcls[p]; vp_tab[4 * i + 3] = p;
-        const bool swap = ka > kb;
-        vp_canon[2 * i] = swap ? refB[p] : refA[p];
-        vp_canon[2 * i + 1] = swap ? refA[p] : refB[p];
-        const double* ca = core_of(refA[p]);
-        const double* cb = core_of(refB[p]);
-        vp_cst[4 * i] = ca[4]; vp_cst[4 * i + 1] = cb[4];
-        vp_cst[4 * i + 2] = host_bound_radius(ka, ca);
-        vp_cst[4 * i + 3] = host_bound_radius(kb, cb);
-        {
-            const int k0 = ka < kb ? ka : kb, k1 = ka < kb ? kb : ka;          // canonical order
-            const bool closed = k1 != K_HULL && (k0 == K_POINT || ((k0 == K_POINT || k0 == K_SEG) && (k1 == K_POINT || k1 == K_SEG)));
-            if (k1 != K_PLANE && !closed && (ca[4] != 0.0 || cb[4] != 0.0)) margins_zero = false;
-            if (k1 != K_PLANE && !closed) { gjk_margins.push_back(ca[4]); gjk_margins.push_back(cb[4]); if (k1 == K_HULL) gjk_any_hull = true; }
-        }
-    }
-    for (int w = 0; w < W; ++w) { ws_center[3 * w] = ws_core[18 * w]; ws_center[3 * w + 1] = ws_core[18 * w + 1]; ws_center[3 * w + 2] = ws_core[18 * w + 2]; }
-    std::vector<unsigned> frame_mask(J > 0 ? J : 1, 0u), rs_mask(S > 0 ? S : 1, 0u);
-    for (int k = 0; k < J; ++k) frame_mask[k] = (d->joint_parent[k] >= 0 ? frame_mask[d->joint_parent[k]] : 0u) | (1u << k);
-    for (int i = 0; i < S; ++i) { const int f = d->rshape_frame[order[i]]; rs_mask[i] = f >= 0 ? frame_mask[f] : 0u; }
-    // broadphase order: category-major (0 plane, 1 robot-robot, 2 robot-world, 3 robot-world box), then by pair
-    std::vector<int> bq_tab(4 * (size_t)(P > 0 ? P : 1), 0);
-    {
-        int cur_b = 0;
-        for (int cat = 0; cat < 4; ++cat)
-            for (int i = 0; i < P; ++i) {
-                const int p = vorder[i];
-                int c;
-                if (refB[p] >= 0) c = 1;
-                else if (ws_kind[~refB[p]] == K_PLANE) c = 0;
-                else if (ws_kind[~refB[p]] == K_BOX) c = 3;
-                else c = 2;
-                if (c != cat) continue;
-                bq_tab[4 * cur_b] = 3 * refA[p];
-                bq_tab[4 * cur_b + 1] = refB[p] >= 0 ? 3 * refB[p] : ~refB[p];
-                bq_tab[4 * cur_b + 2] = i;
-                bq_tab[4 * cur_b + 3] = cat;
-                ++cur_b;
-            }
-    }
-    // static reach culling: the centre of robot shape a never leaves the ball of radius reach_a around the base origin
-    // (sum of the joint offsets on its path + its local offset; unbounded when a prismatic joint is on the path), so a world
-    // shape farther than that from the base, radii included, can never be a candidate.  Rigorous by the triangle inequality.
-    std::vector<double> bq_static((size_t)(P > 0 ? P : 1), -INFINITY);
-    std::vector<double> reach(S > 0 ? S : 1, 0.0);          // per robot shape (frame order); k_world_update reads a device copy
-    {
-        for (int i = 0; i < S; ++i) {
-            const int f = d->rshape_frame[order[i]];
-            double r = 0.0;
-            bool unbounded = false;
-            if (f >= 0)
-                for (int k = 0; k < J; ++k)
-                    if ((frame_mask[f] >> k) & 1u) {
-                        if (d->joint_type[k] == NBK_PRISMATIC) unbounded = true;
-                        r += std::sqrt(d->joint_trans[3 * k] * d->joint_trans[3 * k] + d->joint_trans[3 * k + 1] * d->joint_trans[3 * k + 1] +
-                                       d->joint_trans[3 * k + 2] * d->joint_trans[3 * k + 2]);
-                    }
-            const double lx = rs_local[12 * i + 3], ly = rs_local[12 * i + 7], lz = rs_local[12 * i + 11];
-            r += std::sqrt(lx * lx + ly * ly + lz * lz);
-            reach[i] = unbounded ? INFINITY : r * (1.0 + 1e-12) + 1e-12;
-        }
-        const double b0[3] = {d->base_pose[3], d->base_pose[7], d->base_pose[11]};
-        for (int j = 0; j < P; ++j) {
-            const int cat = bq_tab[4 * j + 3];
-            if (cat == 1) continue;
-            const int a = bq_tab[4 * j] / 3, w = bq_tab[4 * j + 1], i = bq_tab[4 * j + 2];
-            const double* wc = &ws_core[18 * (size_t)w];
-            if (!(reach[a] < INFINITY)) continue;
-            if (reach_only != nullptr) {
-                reach_only->user.push_back(vp_tab[4 * i + 3]); reach_only->w.push_back(w); reach_only->plane.push_back(cat == 0 ? 1 : 0);
-                reach_only->reach.push_back(reach[a]); reach_only->rhoA.push_back(vp_cst[4 * i + 2]); reach_only->rhoB.push_back(vp_cst[4 * i + 3]);
-            }
-            bq_static[j] = world_reach_bound(cat == 0, wc, wc + 9, b0, reach[a], vp_cst[4 * i + 2], vp_cst[4 * i + 3]);
-        }
-    }
-    if (reach_only != nullptr) return NBK_OK;
-    if (3 * S >= 65536 || W >= 65536) return NBK_ERR_UNSUPPORTED;
-    // the LDS broadphase (robots with more than 16 primitives) keeps the pair constants and world cores in LDS; robots the
-    // register broadphases serve do not need it, however many world shapes there are
-    const bool lds_broad_ok = (size_t)(d->n_q + 12 * slots + 3 * S) * 64 * sizeof(double) + (4 * (size_t)P + 18 * (size_t)W) * sizeof(double) + BQ_CAP * 4 <= LDS_MAX;
-    if (!lds_broad_ok && S > 16) return NBK_ERR_UNSUPPORTED;
-    if (P >= (1 << 20)) return NBK_ERR_UNSUPPORTED;
-    // LDS budget: q rows + shape rows + saved frames, 512 B each (+ queue and flags of the validity path);
-    // the raw q slab reuses the shape area
-    const size_t lds_bytes = (size_t)(d->n_q + (rows > d->n_q ? rows : d->n_q) + 12 * slots) * 64 * sizeof(double) + VALIDITY_LDS_EXTRA;
-    // robots whose primitives do not fit the LDS-parked layout (some 25+ shapes) keep validity and edges, through the
-    // broadphase + narrowphase kernels at every batch size; the per-pair distance entry points report UNSUPPORTED for them
-    const bool parked_ok = lds_bytes <= LDS_MAX;
-    if (S <= 16 && (size_t)d->n_q * 64 * sizeof(double) + 12 * (size_t)slots * 64 * sizeof(float) + 4096 > LDS_MAX) return NBK_ERR_UNSUPPORTED;
-    if (P >= (1 << 26)) return NBK_ERR_UNSUPPORTED;
-
-    Blob B;
-    nbk_model* M = new nbk_model();
-    memset(&M->d, 0, sizeof(M->d));
-    struct Off { size_t jt, jq, jl, js, jb, jr, jtr, jsl, jax, bp, rk, rr, rl, rc, wk, wc, pa, pb, pu, vt, vc, vk, wz, rm, bt, rf, vi, ft, bs, vcl; } o;
-    o.jt = B.add(d->joint_type, sizeof(int) * J);
-    o.jq = B.add(d->joint_qidx, sizeof(int) * J);
-    o.jl = B.add(load.data(), sizeof(int) * J);
-    o.js = B.add(save.data(), sizeof(int) * J);
-    o.jb = B.add(begin.data(), sizeof(int) * (J + 2));
-    // exact zeros of the joint tables are stored as +0 (so that a literal 0.0 in the axis-aligned fast paths is the same operand),
-    // and every joint is classified: which coordinate axis of the joint frame it turns about, if any
-    std::vector<double> jrot(d->joint_rot, d->joint_rot + 27 * (size_t)J), jtrans(d->joint_trans, d->joint_trans + 3 * (size_t)J);
-    for (double& v : jrot) v += 0.0;
-    for (double& v : jtrans) v += 0.0;
-    std::vector<int> joint_kind(J > 0 ? J : 1, JK_GENERIC);
-    for (int k = 0; k < J; ++k) {
-        const double* Mk = &jrot[27 * (size_t)k];
-        if (d->joint_type[k] == NBK_PRISMATIC) {
-            bool zero = true;
-            for (int e = 9; e < 27; ++e) zero = zero && Mk[e] == 0.0;
-            if (!zero) { delete M; snprintf(g_err, sizeof(g_err), "prismatic joint %d: M1 / M2 of joint_rot must be zero", k); return NBK_ERR_INVALID; }
-            joint_kind[k] = JK_PRISMATIC;
-            continue;
-        }
-        for (int kz = 0; kz < 3; ++kz) {
-            const int u = (kz + 1) % 3, v = (kz + 2) % 3;
-            bool ok = d->joint_slide[3 * k] == 0.0 && d->joint_slide[3 * k + 1] == 0.0 && d->joint_slide[3 * k + 2] == 0.0;
-            for (int r = 0; r < 3; ++r)
-                ok = ok && Mk[9 + 3 * r + kz] == 0.0 && Mk[18 + 3 * r + kz] == 0.0 && Mk[3 * r + u] == 0.0 && Mk[3 * r + v] == 0.0;
-            if (ok) { joint_kind[k] = kz; break; }
-        }
-    }
-    o.jr = B.add(jrot.data(), sizeof(double) * 27 * J);
-    const size_t o_jk = B.add(joint_kind.data(), sizeof(int) * J);
-    o.jtr = B.add(jtrans.data(), sizeof(double) * 3 * J);
-    o.jsl = B.add(d->joint_slide, sizeof(double) * 3 * J);
-    std::vector<double> joint_pk(22 * (size_t)(J > 0 ? J : 1), 0.0);
-    for (int k = 0; k < J; ++k) {
-        const double* Mk = &jrot[27 * (size_t)k];
-        const int kz = joint_kind[k] <= 2 ? joint_kind[k] : 0;
-        const int u = (kz + 1) % 3, v = (kz + 2) % 3;
-        double* jp = &joint_pk[22 * (size_t)k];
-        for (int r = 0; r < 3; ++r) jp[18 + r] = d->joint_axis[3 * k + r];
-        for (int r = 0; r < 3; ++r) { jp[2 * r] = Mk[18 + 3 * r + u]; jp[2 * r + 1] = Mk[18 + 3 * r + v]; jp[6 + 2 * r] = Mk[9 + 3 * r + u]; jp[6 + 2 * r + 1] = Mk[9 + 3 * r + v]; jp[12 + r] = Mk[3 * r + kz]; jp[15 + r] = jtrans[3 * k + r]; }
-    }
-    const size_t o_jpk = B.add(joint_pk.data(), sizeof(double) * joint_pk.size());
-    M->h_joint_kind.assign(joint_kind.begin(), joint_kind.end());
-    o.jax = B.add(d->joint_axis, sizeof(double) * 3 * J);
-    o.bp = B.add(d->base_pose, sizeof(double) * 12);
-    o.rk = B.add(rs_kind.data(), sizeof(int) * S);
-    o.rr = B.add(rs_row.data(), sizeof(int) * S);
-    o.rl = B.add(rs_local.data(), sizeof(double) * 12 * S);
-    o.rc = B.add(rs_core.data(), sizeof(double) * 6 * S);
-    o.wk = B.add(ws_kind.data(), sizeof(int) * W);
-    o.wc = B.add(ws_core.data(), sizeof(double) * 18 * W);
-    o.pa = B.add(pa.data(), sizeof(int) * P);
-    o.pb = B.add(pb.data(), sizeof(int) * P);
-    o.pu = B.add(pu.data(), sizeof(int) * P);
-    std::vector<int> pdev((size_t)(P > 0 ? P : 1), 0);
-    for (int p = 0; p < P; ++p) pdev[pu[p]] = p;
-    const size_t o_pd = B.add(pdev.data(), sizeof(int) * P);
-    MotionHost mh;
-    motion_tables(d, mh);
-    const size_t o_mjt = B.add(mh.jtype.data(), sizeof(int) * J), o_mjq = B.add(mh.jqidx.data(), sizeof(int) * J);
-    const size_t o_mtn = B.add(mh.jtn.data(), sizeof(double) * J), o_msn = B.add(mh.jsn.data(), sizeof(double) * J);
-    const size_t o_msm = B.add(mh.smask.data(), sizeof(unsigned) * S), o_msl = B.add(mh.sloc.data(), sizeof(double) * S);
-    const size_t o_msb = B.add(mh.sbnd.data(), sizeof(double) * S);
-    const size_t o_mpa = B.add(mh.pa.data(), sizeof(int) * P), o_mpb = B.add(mh.pb.data(), sizeof(int) * P);
-    o.vt = B.add(vp_tab.data(), sizeof(int) * 4 * P);
-    o.vc = B.add(vp_canon.data(), sizeof(int) * 2 * P);
-    o.vk = B.add(vp_cst.data(), sizeof(double) * 4 * P);
-    o.wz = B.add(ws_center.data(), sizeof(double) * 3 * W);
-    o.rm = B.add(rs_mask.data(), sizeof(unsigned) * S);
-    std::vector<int> vp_info(4 * (size_t)(P > 0 ? P : 1), 0);
-    for (int i = 0; i < P; ++i) {
-        const int ra = vp_canon[2 * i], rb = vp_canon[2 * i + 1];
-        vp_info[4 * i] = ra; vp_info[4 * i + 1] = rb;
-        vp_info[4 * i + 2] = ra >= 0 ? (int)rs_mask[ra] : 0;
-        vp_info[4 * i + 3] = rb >= 0 ? (int)rs_mask[rb] : 0;
-    }
-    o.vi = B.add(vp_info.data(), sizeof(int) * 4 * P);
-    std::vector<int> vp_cls((size_t)(P > 0 ? P : 1), 3);
-    int cls_count[4] = {0, 0, 0, 0};
-    for (int i = 0; i < P; ++i) {
-        const int ra = vp_canon[2 * i], rb = vp_canon[2 * i + 1];
-        const int ka = ra >= 0 ? rs_kind[ra] : ws_kind[~ra], kb = rb >= 0 ? rs_kind[rb] : ws_kind[~rb];
-        vp_cls[i] = (ka == K_BOX && kb == K_BOX) ? 0 : ((ka == K_BOX && kb == K_CYL) ? 1 : ((ka == K_CYL && kb == K_CYL) ? 2 : 3));
-        cls_count[vp_cls[i]] += 1;
-    }
-    // sub-queues per class in proportion to its pairs (at least one for a class that has pairs)
-    int cls_groups[4] = {0, 0, 0, 0}, cls_base[4] = {0, 0, 0, 0};
-    {
-        int used = 0, nonempty = 0;
-        for (int c = 0; c < 4; ++c) if (cls_count[c] > 0) ++nonempty;
-        const int spare = NSUB - nonempty;
-        for (int c = 0; c < 4; ++c)
-            if (cls_count[c] > 0) { cls_groups[c] = 1 + (int)((long long)spare * cls_count[c] / (P > 0 ? P : 1)); used += cls_groups[c]; }
-        // hand what rounding left over to the largest class
-        int big = 0;
-        for (int c = 1; c < 4; ++c) if (cls_count[c] > cls_count[big]) big = c;
-        if (P > 0) cls_groups[big] += NSUB - used;
-        for (int c = 1; c < 4; ++c) cls_base[c] = cls_base[c - 1] + cls_groups[c - 1];
-    }
-    o.vcl = B.add(vp_cls.data(), sizeof(int) * P);
-    // float32 tables + error slack of the conservative broadphase.  Position error of a float32 chain sweep is below
-    // (joints + 2) * 16 ulp(float) * reach; the slack is 50x that, never below 1e-4 of the reach.
-    // local bounding box of every hull (centre, half extents rounded outwards): the hull midphase culls against it
-    std::vector<double> hull_obb(6 * (size_t)(H > 0 ? H : 1), 0.0);
-    for (int h = 0; h < H; ++h) {
-        const double* v = d->hull_verts + 3 * (size_t)d->hull_vert_begin[h];
-        const int n = d->hull_vert_begin[h + 1] - d->hull_vert_begin[h];
-        double lo[3] = {v[0], v[1], v[2]}, hi[3] = {v[0], v[1], v[2]};
-        for (int k = 1; k < n; ++k)
-            for (int j = 0; j < 3; ++j) { lo[j] = std::min(lo[j], v[3 * k + j]); hi[j] = std::max(hi[j], v[3 * k + j]); }
-        for (int j = 0; j < 3; ++j) { hull_obb[6 * h + j] = 0.5 * (lo[j] + hi[j]); hull_obb[6 * h + 3 + j] = 0.5 * (hi[j] - lo[j]) * (1.0 + 1e-12) + 1e-300; }
-    }
-    std::vector<float> ftab;
-    int f_trans, f_slide, f_base, f_tl, f_wc, f_wobb = 0, f_pk = 0, f_meta = 0, f_chain = 0;
-    double freach = 0.0;
-    {
-        for (int k = 0; k < J; ++k) for (int e = 0; e < 27; ++e) ftab.push_back((float)d->joint_rot[27 * k + e]);
-        f_trans = (int)ftab.size();
-        for (int k = 0; k < J; ++k) {
-            double n2 = 0.0;
-            for (int e = 0; e < 3; ++e) { ftab.push_back((float)d->joint_trans[3 * k + e]); n2 += d->joint_trans[3 * k + e] * d->joint_trans[3 * k + e]; }
-            freach += std::sqrt(n2);
-        }
-        f_slide = (int)ftab.size();
-        for (int k = 0; k < J; ++k) for (int e = 0; e < 3; ++e) ftab.push_back((float)d->joint_slide[3 * k + e]);
-        f_base = (int)ftab.size();
-        {
-            double n2 = 0.0;
-            for (int e = 0; e < 12; ++e) ftab.push_back((float)d->base_pose[e]);
-            for (int i = 0; i < 3; ++i) n2 += d->base_pose[4 * i + 3] * d->base_pose[4 * i + 3];
-            freach += std::sqrt(n2);
-        }
-        f_tl = (int)ftab.size();
-        double lmax = 0.0;
-        for (int i = 0; i < S; ++i) {
-            double n2 = 0.0;
-            for (int r = 0; r < 3; ++r) { const double v = rs_local[12 * i + 4 * r + 3]; ftab.push_back((float)v); n2 += v * v; }
-            if (std::sqrt(n2) > lmax) lmax = std::sqrt(n2);
-        }
-        freach += lmax;
-        f_wc = (int)ftab.size();
-        for (int w = 0; w < W; ++w) {
-            double n2 = 0.0;
-            for (int e = 0; e < 18; ++e) ftab.push_back((float)ws_core[18 * w + e]);
-            for (int e = 0; e < 3; ++e) n2 += ws_core[18 * w + e] * ws_core[18 * w + e];
-            if (std::sqrt(n2) > freach) freach = std::sqrt(n2);          // world coordinates enter the differences too
-        }
-        // a movable descriptor: every centre its poses may ever have (the caller's promise, checked by k_world_update)
-        if (world_radius != nullptr && *world_radius > freach) freach = *world_radius;
-        f_wobb = (int)ftab.size();
-        for (int w = 0; w < W; ++w)
-            for (int e = 0; e < 6; ++e) {
-                const double v = ws_hull[w] >= 0 ? hull_obb[6 * (size_t)ws_hull[w] + e] : 0.0;
-                ftab.push_back(e < 3 ? (float)v : (float)v * (1.0f + 2.4e-7f));          // half extents rounded up
-            }
-        // per-joint constants of the packed sweep (k_broad_f32): for a joint about coordinate axis KZ of its frame (U, V = the two
-        // other axes) the pairs (M2[r][U], M2[r][V]) and (M1[r][U], M1[r][V]), r = 0..2, column KZ of M0, the offset translation
-        while (ftab.size() % 4 != 0) ftab.push_back(0.0f);
-        f_pk = (int)ftab.size();
-        for (int k = 0; k < (J > 8 ? J : 8); ++k) {
-            if (k >= J) { for (int e = 0; e < 20; ++e) ftab.push_back(0.0f); continue; }      // (the chain sweep prefetches entry k + 1 <= 7)
-            const double* M = d->joint_rot + 27 * (size_t)k;
-            const int kz = joint_kind[k] <= 2 ? joint_kind[k] : 0;
-            const int u = (kz + 1) % 3, v = (kz + 2) % 3;
-            for (int r = 0; r < 3; ++r) { ftab.push_back((float)M[18 + 3 * r + u]); ftab.push_back((float)M[18 + 3 * r + v]); }
-            for (int r = 0; r < 3; ++r) { ftab.push_back((float)M[9 + 3 * r + u]); ftab.push_back((float)M[9 + 3 * r + v]); }
-            for (int r = 0; r < 3; ++r) ftab.push_back((float)M[3 * r + kz]);
-            ftab.push_back(0.0f);
-            for (int e = 0; e < 3; ++e) ftab.push_back((float)d->joint_trans[3 * k + e]);
-            ftab.push_back(0.0f);
-        }
-        f_meta = (int)ftab.size();
-        for (int k = 0; k < 8; ++k) {
-            const unsigned v = k < J ? ((unsigned)joint_kind[k] | ((unsigned)d->joint_qidx[k] << 8)) : 0u;
-            float fv; memcpy(&fv, &v, 4);
-            ftab.push_back(fv);
-        }
-        f_chain = (J >= 1 && J <= 8 && S <= 16) ? 1 : 0;
-        for (int k = 0; k < J && f_chain; ++k) if (load[k] != (k == 0 ? -1 : -2) || save[k] != -1) f_chain = 0;
-        if (ftab.empty()) ftab.push_back(0.0f);
-    }
-    // slack constants of the float32 broadphase: 50 x the float32 error bound (joints + 2) * 16 ulp of a chain sweep, relative; the
-    // kernel multiplies it by the larger of the static reach and the configuration's own largest coordinate (prismatic travel is
-    // unbounded here)
-    float f_eps_v, f_reach_v, f_e2max_v;
-    {
-        const double rel = 50.0 * (J + 2) * 16.0 * 5.96e-8;
-        f_eps_v = (float)(rel > 1e-4 ? rel : 1e-4);
-        f_reach_v = (float)(freach > 1e-3 ? freach : 1e-3);
-        f_e2max_v = 2.0f * f_reach_v * (f_eps_v + 2.4e-7f * 64.0f) * (1.0f + 1e-6f);
-    }
-    std::string spec;
-    if (f_chain) {
-        const SpecIn si{J, S, W, P, d->n_q, joint_kind.data(), d->joint_qidx, begin.data(), bq_tab.data(), ws_kind.data(),
-                        f_pk, f_tl, f_base, f_wc, f_wobb, f_trans, f_slide, f_eps_v, f_reach_v, f_e2max_v, cls_base, cls_groups};
-        spec = bf32_spec_text(si);
-    }
-    if (spec_only != nullptr) { *spec_only = spec; delete M; return NBK_OK; }
-    M->bf32_spec = spec;
-    o.ft = B.add(ftab.data(), sizeof(float) * ftab.size());
-    std::vector<int> rs_frame_v(S > 0 ? S : 1, -1);
-    for (int i = 0; i < S; ++i) rs_frame_v[i] = d->rshape_frame[order[i]];
-    o.rf = B.add(rs_frame_v.data(), sizeof(int) * S);
-    o.bt = B.add(bq_tab.data(), sizeof(int) * 4 * P);
-    o.bs = B.add(bq_static.data(), sizeof(double) * P);
-    const size_t o_rch = B.add(reach.data(), sizeof(double) * S);
-    const int status0[4] = {0, 0, 0, 0};
-    const size_t o_wst = B.add(status0, sizeof(status0));
-    // radius of a ball around each shape's centre that lies inside the shape (the float32 broadphase certifies a collision when two
-    // such balls overlap): margin + the smallest half extent of the core; hulls: the smallest face offset (0 without planes)
-    std::vector<double> rs_in(S > 0 ? S : 1, 0.0), ws_in(W > 0 ? W : 1, 0.0);
-    {
-        auto inscribed = [&](int kind, const double* cc, int hull) {
-            double r = 0.0;
-            if (kind == K_BOX) r = std::min(cc[0], std::min(cc[1], cc[2]));
-            else if (kind == K_CYL) r = std::min(cc[3], cc[0]);
-            else if (kind == K_HULL) {
-                const int f0 = d->hull_face_begin[hull], f1 = d->hull_face_begin[hull + 1];
-                r = f1 > f0 ? INFINITY : 0.0;
-                for (int f = f0; f < f1; ++f) r = std::min(r, d->hull_planes[4 * (size_t)f + 3]);
-                r *= (1.0 - 1e-9);             // the planes come from a float64 hull computation: stay inside them
-            } else if (kind == K_PLANE) return 0.0;
-            if (!(r > 0.0)) r = 0.0;
-            return r + cc[4];
-        };
-        for (int i = 0; i < S; ++i) rs_in[i] = inscribed(rs_kind[i], &rs_core[6 * (size_t)i], rs_hull[i]);
-        for (int w = 0; w < W; ++w) ws_in[w] = inscribed(ws_kind[w], &ws_core[18 * (size_t)w + 12], ws_hull[w]);
-    }
-    const size_t o_rin = B.add(rs_in.data(), sizeof(double) * S);
-    const size_t o_win = B.add(ws_in.data(), sizeof(double) * W);
-    // hull vertices, each hull's list preceded by its local bounding box (centre, half extents): 6 + 3 n doubles per hull
-    std::vector<double> hull_blob;
-    std::vector<size_t> hull_off(H > 0 ? H : 1, 0);           // offset (in doubles) of hull h's first vertex inside hull_blob
-    for (int h = 0; h < H; ++h) {
-        const double* v = d->hull_verts + 3 * (size_t)d->hull_vert_begin[h];
-        const int n = d->hull_vert_begin[h + 1] - d->hull_vert_begin[h];
-        hull_blob.insert(hull_blob.end(), &hull_obb[6 * h], &hull_obb[6 * h] + 6);
-        hull_off[h] = hull_blob.size();
-        hull_blob.insert(hull_blob.end(), v, v + 3 * (size_t)n);
-    }
-    const size_t o_hv = B.add(hull_blob.data(), sizeof(double) * hull_blob.size());
-    const size_t o_hp = B.add(d->hull_planes, sizeof(double) * 4 * (size_t)(H > 0 ? d->hull_face_begin[H] : 0));
-    B.bytes.resize((B.bytes.size() + 255) & ~size_t(255));
-
-    void* dev = nullptr;
-    hipError_t e = hipMalloc(&dev, B.bytes.size());
-    if (e != hipSuccess) { delete M; hip_fail(e, "hipMalloc(model)"); return NBK_ERR_ALLOC; }
-    // hull shapes: their 24-byte h[] slots in the shape tables hold the device addresses of the hull's vertices / planes
-    {
-        auto patch = [&](size_t slot, int h) {
-            HullRef r;
-            r.hv = reinterpret_cast<const double*>(static_cast<const char*>(dev) + o_hv) + hull_off[h];
-            r.hp = reinterpret_cast<const double*>(static_cast<const char*>(dev) + o_hp) + 4 * (size_t)d->hull_face_begin[h];
-            r.hn = d->hull_vert_begin[h + 1] - d->hull_vert_begin[h];
-            r.hf = d->hull_face_begin[h + 1] - d->hull_face_begin[h];
-            static_assert(sizeof(HullRef) == 24, "HullRef must overlay h[3]");
-            memcpy(B.bytes.data() + slot, &r, sizeof(r));
-        };
-        for (int i = 0; i < S; ++i) if (rs_hull[i] >= 0) patch(o.rc + sizeof(double) * 6 * (size_t)i, rs_hull[i]);
-        for (int w = 0; w < W; ++w) if (ws_hull[w] >= 0) patch(o.wc + sizeof(double) * (18 * (size_t)w + 12), ws_hull[w]);
-    }
-    e = hipMemcpy(dev, B.bytes.data(), B.bytes.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(dev); delete M; return hip_fail(e, "hipMemcpy(model)"); }
-    const char* base = static_cast<const char*>(dev);
-    DevModel& m = M->d;
-    m.n_q = d->n_q; m.n_joints = J; m.n_rshapes = S; m.n_wshapes = W; m.n_pairs = P;
-    m.shape_rows = rows > d->n_q ? rows : d->n_q;
-    m.frame_slots = slots;
-    m.joint_type = reinterpret_cast<const int*>(base + o.jt);
-    m.joint_qidx = reinterpret_cast<const int*>(base + o.jq);
-    m.joint_load = reinterpret_cast<const int*>(base + o.jl);
-    m.joint_save = reinterpret_cast<const int*>(base + o.js);
-    m.joint_shape_begin = reinterpret_cast<const int*>(base + o.jb);
-    m.joint_rot = reinterpret_cast<const double*>(base + o.jr);
-    m.joint_kind = reinterpret_cast<const int*>(base + o_jk);
-    m.joint_trans = reinterpret_cast<const double*>(base + o.jtr);
-    m.joint_slide = reinterpret_cast<const double*>(base + o.jsl);
-    m.joint_axis = reinterpret_cast<const double*>(base + o.jax);
-    m.joint_pk = reinterpret_cast<const double*>(base + o_jpk);
-    m.base_pose = reinterpret_cast<const double*>(base + o.bp);
-    m.rs_kind = reinterpret_cast<const int*>(base + o.rk);
-    m.rs_row = reinterpret_cast<const int*>(base + o.rr);
-    m.rs_local = reinterpret_cast<const double*>(base + o.rl);
-    m.rs_core = reinterpret_cast<const double*>(base + o.rc);
-    m.ws_kind = reinterpret_cast<const int*>(base + o.wk);
-    m.ws_core = reinterpret_cast<const double*>(base + o.wc);
-    m.hull_blob = reinterpret_cast<const double*>(base + o_hv);
-    m.hull_blob_n = (int)hull_blob.size();
-    m.pair_a = reinterpret_cast<const int*>(base + o.pa);
-    m.pair_b = reinterpret_cast<const int*>(base + o.pb);
-    m.pair_user = reinterpret_cast<const int*>(base + o.pu);
-    m.pair_dev = reinterpret_cast<const int*>(base + o_pd);
-    m.mt = MotionTab{J, S, reinterpret_cast<const int*>(base + o_mjt), reinterpret_cast<const int*>(base + o_mjq),
-                     reinterpret_cast<const double*>(base + o_mtn), reinterpret_cast<const double*>(base + o_msn),
-                     reinterpret_cast<const unsigned*>(base + o_msm), reinterpret_cast<const double*>(base + o_msl),
-                     reinterpret_cast<const double*>(base + o_msb), reinterpret_cast<const int*>(base + o_mpa),
-                     reinterpret_cast<const int*>(base + o_mpb)};
-    m.vp_tab = reinterpret_cast<const int*>(base + o.vt);
-    m.vp_canon = reinterpret_cast<const int*>(base + o.vc);
-    m.vp_cst = reinterpret_cast<const double*>(base + o.vk);
-    m.ws_center = reinterpret_cast<const double*>(base + o.wz);
-    m.n_plane_pairs = n_plane; m.n_closed_pairs = n_closed;
-    m.rs_mask = reinterpret_cast<const unsigned*>(base + o.rm);
-    m.vp_info = reinterpret_cast<const int4*>(base + o.vi);
-    m.vp_cls = reinterpret_cast<const int*>(base + o.vcl);
-    for (int c = 0; c < 4; ++c) { m.cls_base[c] = cls_base[c]; m.cls_groups[c] = cls_groups[c] > 0 ? cls_groups[c] : 1; }
-    m.f_tab = reinterpret_cast<const float*>(base + o.ft);
-    m.f_trans = f_trans; m.f_slide = f_slide; m.f_base = f_base; m.f_tl = f_tl; m.f_wc = f_wc; m.f_wobb = f_wobb; m.f_pk = f_pk; m.f_meta = f_meta; m.f_chain = f_chain;
-    m.f_eps = f_eps_v; m.f_reach = f_reach_v; m.f_e2max = f_e2max_v;
-    m.rs_frame = reinterpret_cast<const int*>(base + o.rf);
-    m.bq_tab = reinterpret_cast<const int*>(base + o.bt);
-    m.bq_static = reinterpret_cast<const double*>(base + o.bs);
-    m.rs_in = reinterpret_cast<const double*>(base + o_rin);
-    m.ws_in = reinterpret_cast<const double*>(base + o_win);
-    for (int c = 0; c < 4; ++c) { m.bq_count[c] = 0; }
-    for (int i = 0; i < P; ++i) m.bq_count[bq_tab[4 * i + 3]]++;
-#ifdef NBK_ABLATE_BUILD
-    { const char* ab = getenv("NBK_ABLATE"); m.dbg = ab ? atoi(ab) : 0; }
-#else
-    m.dbg = 0;
-#endif
-    M->blob = dev;
-    M->scalar_q = nullptr; M->scalar_out = nullptr; M->scalar_stream = nullptr;
-    M->blob_bytes = B.bytes.size();
-    M->n_pairs = P; M->n_q = d->n_q; M->n_joints = J;
-    M->h_joint_qidx.assign(d->joint_qidx, d->joint_qidx + J);
-    M->h_joint_type.assign(d->joint_type, d->joint_type + J);
-    M->margins_zero = margins_zero;
-    for (int c = 0; c < 4; ++c) M->cls_count[c] = cls_count[c];
-    M->h_static = bq_static; M->h_static.resize(P > 0 ? P : 0);
-    M->h_m0.resize(P); M->h_m1.resize(P); M->h_cat.resize(P); M->h_cls.resize(P);
-    for (int j = 0; j < P; ++j) {
-        const int i = bq_tab[4 * j + 2];
-        M->h_m0[j] = vp_cst[4 * (size_t)i]; M->h_m1[j] = vp_cst[4 * (size_t)i + 1];
-        M->h_cat[j] = bq_tab[4 * j + 3]; M->h_cls[j] = vp_cls[i];
-    }
-    M->gjk_margins = gjk_margins;
-    M->gjk_any_hull = gjk_any_hull;
-    M->world_hulls = world_hulls;
-    M->lds_broad_ok = lds_broad_ok;
-    M->parked_ok = parked_ok;
-    M->rs_reach = reinterpret_cast<const double*>(base + o_rch);
-    M->world_status = reinterpret_cast<int*>(static_cast<char*>(dev) + o_wst);
-    if (world_radius != nullptr) { M->movable = true; M->world_radius = *world_radius; }
-    (void)hipGetDevice(&M->device);
-    *out = M;
-    return NBK_OK;
-}
 
 void nbk_model_destroy(nbk_model* m) {
     if (m == nullptr) return;
@@ -5202,21 +4562,18 @@ int32_t nbk_frameset_create(const nbk_model* m, int32_t n_frames, const int32_t*
     for (int k = 1; k < J + 2; ++k) begin[k] += begin[k - 1];
     std::vector<double> local(12 * (size_t)n_frames);
     for (int i = 0; i < n_frames; ++i) { outv[i] = order[i]; memcpy(&local[12 * i], frame_local + 12 * order[i], 12 * sizeof(double)); }
+    std::unique_ptr<nbk_frameset, decltype(&nbk_frameset_destroy)> fs(new nbk_frameset(), nbk_frameset_destroy);      // value-initialised: no blob yet
+    fs->n = n_frames;
     Blob Bb;
-    const size_t ob = Bb.add(begin.data(), sizeof(int) * (J + 2));
-    const size_t oo = Bb.add(outv.data(), sizeof(int) * n_frames);
-    const size_t ol = Bb.add(local.data(), sizeof(double) * 12 * n_frames);
-    nbk_frameset* fs = new nbk_frameset();
-    fs->n = n_frames; fs->blob = nullptr;
+    Bb.bind(&fs->begin, begin.data(), J + 2);
+    Bb.bind(&fs->out, outv.data(), n_frames);
+    Bb.bind(&fs->local, local.data(), 12 * (size_t)n_frames);
     hipError_t e = hipMalloc(&fs->blob, Bb.bytes.size());
-    if (e != hipSuccess) { delete fs; hip_fail(e, "hipMalloc(frameset)"); return NBK_ERR_ALLOC; }
+    if (e != hipSuccess) { fs->blob = nullptr; hip_fail(e, "hipMalloc(frameset)"); return NBK_ERR_ALLOC; }
+    Bb.resolve(fs->blob);
     e = hipMemcpy(fs->blob, Bb.bytes.data(), Bb.bytes.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(fs->blob); delete fs; return hip_fail(e, "hipMemcpy(frameset)"); }
-    const char* b = static_cast<const char*>(fs->blob);
-    fs->begin = reinterpret_cast<const int*>(b + ob);
-    fs->out = reinterpret_cast<const int*>(b + oo);
-    fs->local = reinterpret_cast<const double*>(b + ol);
-    *out = fs;
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(frameset)");
+    *out = fs.release();
     return NBK_OK;
 }
 
@@ -5782,47 +5139,14 @@ int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, cons
     return guard_verdicts(m, st, valid, status, nullptr, t_free, E);
 }
 
-// the descriptor checks of the *_motion_bounds_host entries: the parts MotionTab reads
-static int32_t motion_desc_check(const nbk_model_desc* d) {
-    if (d == nullptr) return NBK_ERR_INVALID;
-    const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
-    if (d->n_q < 0 || J < 0 || S < 0 || W < 0 || P < 0 || d->n_hulls < 0) return NBK_ERR_INVALID;
-    if (J > NBK_MAX_JOINTS || d->n_q > NBK_MAX_DOF) return NBK_ERR_UNSUPPORTED;
-    if ((J > 0 && (d->joint_parent == nullptr || d->joint_type == nullptr || d->joint_qidx == nullptr || d->joint_trans == nullptr ||
-                   d->joint_slide == nullptr)) ||
-        (S > 0 && (d->rshape_frame == nullptr || d->rshape_type == nullptr || d->rshape_local == nullptr || d->rshape_param == nullptr)) ||
-        (P > 0 && (d->pair_a == nullptr || d->pair_b == nullptr)))
-        return NBK_ERR_INVALID;
-    for (int k = 0; k < J; ++k) {
-        if (d->joint_parent[k] >= k || d->joint_parent[k] < -1) return NBK_ERR_INVALID;
-        if (d->joint_qidx[k] < 0 || d->joint_qidx[k] >= d->n_q) return NBK_ERR_INVALID;
-        if (d->joint_type[k] != NBK_REVOLUTE && d->joint_type[k] != NBK_PRISMATIC) return NBK_ERR_INVALID;
-    }
-    for (int x = 0; x < S; ++x) {
-        if (d->rshape_frame[x] < -1 || d->rshape_frame[x] >= J) return NBK_ERR_INVALID;
-        const int t = d->rshape_type[x];
-        if (!((t >= NBK_SPHERE && t <= NBK_CYLINDER) || t == NBK_HULL)) return NBK_ERR_INVALID;
-        if (t == NBK_HULL) {
-            const double h = d->rshape_param[4 * x];
-            if (!(h >= 0.0 && h < (double)d->n_hulls && h == (double)(int)h) || d->hull_vert_begin == nullptr || d->hull_verts == nullptr)
-                return NBK_ERR_INVALID;
-            const int hi = (int)h;
-            if (d->hull_vert_begin[hi] < 0 || d->hull_vert_begin[hi + 1] <= d->hull_vert_begin[hi]) return NBK_ERR_INVALID;
-        }
-    }
-    for (int p = 0; p < P; ++p)
-        if (d->pair_a[p] < 0 || d->pair_a[p] >= S || d->pair_b[p] < 0 || d->pair_b[p] >= S + W) return NBK_ERR_INVALID;
-    return NBK_OK;
-}
-
 int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* starts, const double* goals, int64_t E, double* mu) {
     if (d == nullptr || E < 0) return NBK_ERR_INVALID;
-    { const int32_t rc = motion_desc_check(d); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
     const int P = d->n_pairs;
     if (E == 0 || P == 0) return NBK_OK;
     if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
     MotionHost h;
-    motion_tables(d, h);
+    motion_tables(d, frame_masks(d), h);
     const MotionTab t = h.view(d->n_joints, d->n_rshapes);
     for (int64_t e = 0; e < E; ++e)
         for (int p = 0; p < P; ++p)
@@ -5844,12 +5168,12 @@ int32_t nbk_spline_motion_bounds_host(const nbk_model_desc* d, const double* ctr
                                       const double* knots, double* mu) {
     if (d == nullptr || S < 0) return NBK_ERR_INVALID;
     if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
-    { const int32_t rc = motion_desc_check(d); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
     const int P = d->n_pairs, nq = d->n_q, k = degree, L = n_ctrl - degree;
     if (S == 0 || P == 0) return NBK_OK;
     if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_knots_ok(knots, n_ctrl, k)) return NBK_ERR_INVALID;
     MotionHost h;
-    motion_tables(d, h);
+    motion_tables(d, frame_masks(d), h);
     const MotionTab t = h.view(d->n_joints, d->n_rshapes);
     for (int64_t s = 0; s < S; ++s) {
         const double* c = ctrl + (size_t)s * (size_t)n_ctrl * nq;
@@ -6201,7 +5525,7 @@ int32_t nbk_model_create_movable(const nbk_model_desc* d, double world_radius, n
             return NBK_ERR_INVALID;
         }
     if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
-    return model_create_impl(d, out, nullptr, &world_radius);
+    return model_create(d, &world_radius, out);
 }
 
 // the update on `st` (world_mu held): clear the status word, k_world_update; every stream's tables become stale
@@ -6274,23 +5598,16 @@ int32_t nbk_model_world_status(const nbk_model* m, int32_t* status) {
 }
 
 int32_t nbk_world_reach_bounds_host(const nbk_model_desc* d, const double* poses, double* bound) {
-    if (d == nullptr) return NBK_ERR_INVALID;
-    { const int32_t rc = motion_desc_check(d); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
     const int P = d->n_pairs, W = d->n_wshapes;
     if (P == 0) return NBK_OK;
     if (bound == nullptr || (W > 0 && (poses == nullptr || d->wshape_type == nullptr || d->wshape_param == nullptr || d->wshape_pose == nullptr)) ||
         d->base_pose == nullptr)
         return NBK_ERR_INVALID;
-    ReachOut ro;
-    const int32_t rc = model_create_impl(d, nullptr, nullptr, nullptr, &ro);
-    if (rc != NBK_OK) return rc;
-    for (int p = 0; p < P; ++p) bound[p] = -INFINITY;
-    const double b0[3] = {d->base_pose[3], d->base_pose[7], d->base_pose[11]};
-    for (size_t k = 0; k < ro.user.size(); ++k) {
-        const double* T = poses + 12 * (size_t)ro.w[k];
-        const double c[3] = {T[3], T[7], T[11]};
-        bound[ro.user[k]] = world_reach_bound(ro.plane[k] != 0, c, d->wshape_param + 4 * (size_t)ro.w[k], b0, ro.reach[k], ro.rhoA[k], ro.rhoB[k]);
-    }
+    { const int32_t rc = desc_check(d, D_WSHAPES | D_HULL_PLANES); if (rc != NBK_OK) return rc; }
+    ModelTables t;
+    compile_geometry(d, t);              // creation's shape order, pair tables and reach, ahead of its compiled-in limits
+    for (int j = 0; j < P; ++j) bound[t.vp_tab[4 * t.bq_tab[4 * j + 2] + 3]] = pair_reach_bound(d, t, j, poses);      // broadphase -> user order
     return NBK_OK;
 }
 

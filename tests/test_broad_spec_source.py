@@ -1,4 +1,4 @@
-"""CPU tier of the per-robot broadphase tests: the ``struct Spec`` that ``bf32_spec_text`` (csrc/nbk.hip) generates for a robot against
+"""CPU tier of the per-robot broadphase tests: the ``struct Spec`` that ``bf32_spec_text`` (csrc/nbk_tables.hpp) generates for a robot against
 an independent restatement from the scene model (spec_cases.expected_spec), over a fixed list of generated robots that spans the Spec
 space; which robots get a source at all; and hipRTC compiling every one of them for gfx950.  No device is needed: the masks of the
 same robots are tests/test_broad_spec.py."""
