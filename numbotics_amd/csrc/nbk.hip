@@ -290,6 +290,65 @@ NBK_DEV bool row_nonfinite(const double* row, int n, int stride) {
     return bad;
 }
 
+// ---- configuration source of the validity kernels ------------------------------------------------------------------------
+// sample `mp` (edge_t) of an edge, to dst[j * stride]: q = (1-t)*start + t*goal in three roundings, as the oracle (and SciPy's
+// degree-1 de Boor) computes it -- never fused
+NBK_DEV void edge_sample_row(const EdgeSrc& es, unsigned long long mp, int nq, double* dst, int stride) {
+    unsigned e;
+    const double t = edge_t(es, mp, e);
+    const double omt = 1.0 - t;
+    const double* s = es.starts + (size_t)e * nq;
+    const double* g = es.goals + (size_t)e * nq;
+    // four joints' loads in flight at a time: an index past the row clamps to its last joint and is not stored
+    const int last = nq - 1;
+    for (int j0 = 0; j0 < nq; j0 += 4) {
+        double sv[4], gv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const int j = (j0 + u) < last ? (j0 + u) : last; sv[u] = s[j]; gv[u] = g[j]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (j0 + u <= last) { const double a = omt * sv[u]; const double b = t * gv[u]; dst[(j0 + u) * stride] = a + b; }
+    }
+}
+// the block's configurations into the row-major slab lds_raw[64][nq] of the broadphases (lane reads lds_raw[lane * nq + j]; no
+// transposed copy): edge samples (es.map) or plain rows of q; rows past the batch are zeros.  The caller synchronises.
+NBK_DEV void stage_rows(const EdgeSrc& es, const double* __restrict__ q, int64_t base, int rows_i, int nq, double* lds_raw, int lane) {
+    if (es.map != nullptr) {
+        if (lane < rows_i) edge_sample_row(es, es.map[base + lane], nq, lds_raw + lane * nq, 1);
+        else for (int j = 0; j < nq; ++j) lds_raw[lane * nq + j] = 0.0;
+        return;
+    }
+#if defined(NBK_BF32_ABL) && NBK_BF32_ABL == 3      // timing experiment: no global read of q
+    for (int i = lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.001 * (double)(i + (int)blockIdx.x);
+#else
+    stage_plain_rows(q, base, rows_i, nq, lds_raw, lane);
+#endif
+}
+
+// ---- one step of the tree sweep (joint_load / joint_save plan of the descriptor) -------------------------------------------
+// parent frame of a joint: the frame in registers (ld == -2), the base (-1) or saved slot ld of lds_fr ([12 * slots][64])
+template <class F, class E>
+NBK_DEV F frame_parent(int ld, const F& T, const F& base, const E* lds_fr, int lane) {
+    F P;
+    if (ld == -2) P = T;
+    else if (ld == -1) P = base;
+    else {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) P.R[e] = lds_fr[(ld * 12 + e) * WAVE + lane];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) P.t[e] = lds_fr[(ld * 12 + 9 + e) * WAVE + lane];
+    }
+    return P;
+}
+template <class F, class E>
+NBK_DEV void frame_save(int sv, const F& T, E* lds_fr, int lane) {
+    if (sv < 0) return;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) lds_fr[(sv * 12 + e) * WAVE + lane] = T.R[e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) lds_fr[(sv * 12 + 9 + e) * WAVE + lane] = T.t[e];
+}
+
 // child frame of joint k (robots/helpers.py:43-55 restated with the host-made M0/M1/M2):
 //   L = M0 - cos(q) M1 + sin(q) M2 (each element fma(s, M2, fma(-c, M1, M0))),  tl = fma(q, slide, trans),  out = parent * (L, tl).
 // Joints whose axis is a coordinate axis of the joint frame (every joint of the usual URDFs) have known zeros in the tables:
@@ -745,24 +804,9 @@ __global__ __launch_bounds__(64) void k_fk_frames(DevModel m, const double* __re
     Xf T = bpose;
     for (int k = -1; k < m.n_joints; ++k) {
         if (k >= 0) {
-            const int ld = m.joint_load[k];
-            Xf P;
-            if (ld == -2) P = T;
-            else if (ld == -1) P = bpose;
-            else {
-#pragma unroll
-                for (int e = 0; e < 9; ++e) P.R[e] = lds_fr[(ld * 12 + e) * WAVE + lane];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) P.t[e] = lds_fr[(ld * 12 + 9 + e) * WAVE + lane];
-            }
+            const Xf P = frame_parent(m.joint_load[k], T, bpose, lds_fr, lane);
             joint_apply(m, k, P, lds_q[m.joint_qidx[k] * WAVE + lane], T);
-            const int sv = m.joint_save[k];
-            if (sv >= 0) {
-#pragma unroll
-                for (int e = 0; e < 9; ++e) lds_fr[(sv * 12 + e) * WAVE + lane] = T.R[e];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) lds_fr[(sv * 12 + 9 + e) * WAVE + lane] = T.t[e];
-            }
+            frame_save(m.joint_save[k], T, lds_fr, lane);
         }
         const int f0 = fs_begin[k + 1], f1 = fs_begin[k + 2];
         for (int f = f0; f < f1; ++f) {
@@ -1047,26 +1091,11 @@ NBK_DEV void sweep_and_park(const DevModel& m, double* lds_q, double* lds_s, dou
     Xf T = base;
     for (int k = -1; k < m.n_joints; ++k) {
         if (k >= 0) {
-            const int ld = m.joint_load[k];
-            Xf P;
-            if (ld == -2) P = T;
-            else if (ld == -1) P = base;
-            else {
-#pragma unroll
-                for (int e = 0; e < 9; ++e) P.R[e] = lds_fr[(ld * 12 + e) * WAVE + lane];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) P.t[e] = lds_fr[(ld * 12 + 9 + e) * WAVE + lane];
-            }
+            const Xf P = frame_parent(m.joint_load[k], T, base, lds_fr, lane);
             const double qk = lds_q[m.joint_qidx[k] * WAVE + lane];
             joint_apply(m, k, P, qk, T);
             if (lds_jz != nullptr) joint_frame_rows(m, k, T, lds_jz + 6 * k * WAVE + lane);
-            const int sv = m.joint_save[k];
-            if (sv >= 0) {
-#pragma unroll
-                for (int e = 0; e < 9; ++e) lds_fr[(sv * 12 + e) * WAVE + lane] = T.R[e];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) lds_fr[(sv * 12 + 9 + e) * WAVE + lane] = T.t[e];
-            }
+            frame_save(m.joint_save[k], T, lds_fr, lane);
         }
         const int s0 = m.joint_shape_begin[k + 1], s1 = m.joint_shape_begin[k + 2];
         for (int s = s0; s < s1; ++s) {
@@ -1262,9 +1291,7 @@ __global__ __launch_bounds__(64) void k_validity(DevModel m, const double* __res
     sweep_and_park(m, lds_q, lds_s, lds_fr, lane);
     const bool bad = row_nonfinite(lds_q + lane, m.n_q, WAVE);
     const bool hit = wave_collides(m, lds_s, lds_x, lane, thr, active) || bad;
-    const uint64_t word = __builtin_amdgcn_ballot_w64(hit && active);
-    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
-    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+    write_mask(hit, active, base, lane, mask_bits, mask_bytes);
 }
 
 // The queues of the broadphase + narrowphase pipeline are sized for a BUDGET (1 GiB), not for the worst case of every pair of every
@@ -1287,17 +1314,8 @@ __global__ __launch_bounds__(64) void k_validity_redo(DevModel m, EdgeSrc es, co
     unsigned* lds_x = reinterpret_cast<unsigned*>(lds_fr + WAVE * 12 * m.frame_slots);
     const bool active = (base + lane) < Beff;
     if (es.map != nullptr) {
-        const int nq = m.n_q;
-        if (active) {
-            unsigned e;
-            const double t = edge_t(es, es.map[base + lane], e);
-            const double omt = 1.0 - t;
-            const double* sp = es.starts + (size_t)e * nq;
-            const double* gp = es.goals + (size_t)e * nq;
-            for (int j = 0; j < nq; ++j) { const double a = omt * sp[j]; const double bb = t * gp[j]; lds_q[j * WAVE + lane] = a + bb; }
-        } else {
-            for (int j = 0; j < nq; ++j) lds_q[j * WAVE + lane] = 0.0;
-        }
+        if (active) edge_sample_row(es, es.map[base + lane], m.n_q, lds_q + lane, WAVE);
+        else for (int j = 0; j < m.n_q; ++j) lds_q[j * WAVE + lane] = 0.0;
         __syncthreads();
     } else {
         stage_q(q, base, Beff, m.n_q, lds_s, lds_q, lane);
@@ -1528,25 +1546,11 @@ __global__ __launch_bounds__(256) void k_prepare_f32(DevModel m, double thr, uns
 // back with wave-uniform addresses (broadcast reads), so the pair loop touches no scalar or vector memory
 // and is a straight line per category.  Survivors are collected as one bit per (lane, pair) and turned into
 // queue items 64 pairs at a time.
-NBK_DEV void enqueue_bits(const DevModel& m, unsigned long long bits, int jbase, const double* lds_pc, unsigned* lds_queue, int& qn, int lane,
-                          int64_t base, unsigned long long* q_count, unsigned long long* q_items, unsigned long long cap, const EdgeSrc& es) {
-    while (true) {
-        const bool has = bits != 0ull;
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
-        if (bal == 0ull) break;
-        if (has) {
-            const int bit = __builtin_ctzll(bits);
-            bits &= bits - 1ull;
-            const unsigned long long e0 = __builtin_bit_cast(unsigned long long, lds_pc[4 * (jbase + bit)]);
-            const unsigned p = (unsigned)(e0 >> 32) & 0xFFFFFu;
-            const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-            lds_queue[pos] = (p << 6) | (unsigned)lane;
-        }
-        qn += __builtin_popcountll(bal);
-        if (qn > BQ_CAP - WAVE) { flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf); qn = 0; }
-    }
-}
-
+// (drain_bits, nbk_bf32_common.hpp; the pair index of entry jbase + bit sits in word 0 of its lds_pc record)
+struct PcPairs {
+    const double* pc;
+    NBK_DEV unsigned operator()(int bit) const { return (unsigned)(__builtin_bit_cast(unsigned long long, pc[4 * bit]) >> 32) & 0xFFFFFu; }
+};
 
 __global__ __launch_bounds__(64) void k_broad(DevModel m, EdgeSrc es, const double* __restrict__ q, int64_t B, double thr,
                                                uint64_t* __restrict__ mask_bits, uint8_t* __restrict__ mask_bytes,
@@ -1569,33 +1573,7 @@ __global__ __launch_bounds__(64) void k_broad(DevModel m, EdgeSrc es, const doub
     if (base >= Beff) return;               // edge mode: the launch covers the scratch's capacity, this block lies beyond the samples
     const int rows_i = (int)((Beff - base) < WAVE ? (Beff - base) : WAVE);
     // ---- stage q (coalesced), no transposed copy: lane reads lds_raw[lane*nq + j] -------------------------
-    if (es.map != nullptr) {
-        // edge mode: this lane's configuration is an interpolation sample
-        if (lane < rows_i) {
-            unsigned e;
-            const double t = edge_t(es, es.map[base + lane], e);
-            const double omt = 1.0 - t;
-            const double* sp = es.starts + (size_t)e * nq;
-            const double* gp = es.goals + (size_t)e * nq;
-            for (int j = 0; j < nq; ++j) { const double a = omt * sp[j]; const double bb = t * gp[j]; lds_raw[lane * nq + j] = a + bb; }
-        } else {
-            for (int j = 0; j < nq; ++j) lds_raw[lane * nq + j] = 0.0;
-        }
-    } else {
-        const int total = rows_i * nq;
-        const double* src = q + base * nq;
-#if defined(NBK_BF32_ABL) && NBK_BF32_ABL == 3      // timing experiment: no global read of q
-        if (true) { for (int i = lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.001 * (double)(i + (int)blockIdx.x); } else
-#endif
-        if (rows_i == WAVE && ((reinterpret_cast<uintptr_t>(src) & 15) == 0) && (total % 2 == 0)) {
-            const double2* s2 = reinterpret_cast<const double2*>(src);
-            double2* d2 = reinterpret_cast<double2*>(lds_raw);
-            for (int i = lane; i < total / 2; i += WAVE) d2[i] = s2[i];
-        } else {
-            for (int i = lane; i < total; i += WAVE) lds_raw[i] = src[i];
-            for (int i = total + lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.0;
-        }
-    }
+    stage_rows(es, q, base, rows_i, nq, lds_raw, lane);
     // ---- per-wave constants: lane j prepares pair j ------------------------------------------------------------
     for (int j = lane; j < P; j += WAVE) {
         const int* t = m.bq_tab + 4 * j;
@@ -1626,25 +1604,10 @@ __global__ __launch_bounds__(64) void k_broad(DevModel m, EdgeSrc es, const doub
         Xf T = bpose;
         for (int k = -1; k < m.n_joints; ++k) {
             if (k >= 0) {
-                const int ld = m.joint_load[k];
-                Xf Pf;
-                if (ld == -2) Pf = T;
-                else if (ld == -1) Pf = bpose;
-                else {
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) Pf.R[e] = lds_fr[(ld * 12 + e) * WAVE + lane];
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) Pf.t[e] = lds_fr[(ld * 12 + 9 + e) * WAVE + lane];
-                }
+                const Xf Pf = frame_parent(m.joint_load[k], T, bpose, lds_fr, lane);
                 const double qk = lds_raw[lane * nq + m.joint_qidx[k]];
                 joint_apply(m, k, Pf, qk, T);
-                const int sv = m.joint_save[k];
-                if (sv >= 0) {
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) lds_fr[(sv * 12 + e) * WAVE + lane] = T.R[e];
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) lds_fr[(sv * 12 + 9 + e) * WAVE + lane] = T.t[e];
-                }
+                frame_save(m.joint_save[k], T, lds_fr, lane);
             }
             const int s0 = m.joint_shape_begin[k + 1], s1 = m.joint_shape_begin[k + 2];
             for (int s = s0; s < s1; ++s) {
@@ -1720,15 +1683,13 @@ __global__ __launch_bounds__(64) void k_broad(DevModel m, EdgeSrc es, const doub
                 }
             }
             if (!active || hit || (NBK_DBG(m) & 4)) bits = 0ull;
-            enqueue_bits(m, bits, j0 + c0, lds_pc, lds_queue, qn, lane, base, q_count, q_items, cap, es);
+            drain_bits(bits, PcPairs{pc0}, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
         }
         j0 += ncat;
     }
     if (qn > 0) flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
     // the mask starts from the hits certified here; k_narrow ORs the rest in
-    const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
-    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
-    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+    write_mask(hit, active, base, lane, mask_bits, mask_bytes);
 }
 
 // ---- k_broad_reg<S>: the same broadphase with the centres of up to S robot shapes in REGISTERS ---------------
@@ -1759,32 +1720,7 @@ __global__ __launch_bounds__(64, 3) void k_broad_reg(DevModel m, EdgeSrc es, con
     if (base >= Beff) return;               // edge mode: the launch covers the scratch's capacity, this block lies beyond the samples
     const int rows_i = (int)((Beff - base) < WAVE ? (Beff - base) : WAVE);
     // ---- stage q ------------------------------------------------------------------------------------------------------
-    if (es.map != nullptr) {
-        if (lane < rows_i) {
-            unsigned e;
-            const double t = edge_t(es, es.map[base + lane], e);
-            const double omt = 1.0 - t;
-            const double* sp = es.starts + (size_t)e * nq;
-            const double* gp = es.goals + (size_t)e * nq;
-            for (int j = 0; j < nq; ++j) { const double a = omt * sp[j]; const double bb = t * gp[j]; lds_raw[lane * nq + j] = a + bb; }
-        } else {
-            for (int j = 0; j < nq; ++j) lds_raw[lane * nq + j] = 0.0;
-        }
-    } else {
-        const int total = rows_i * nq;
-        const double* src = q + base * nq;
-#if defined(NBK_BF32_ABL) && NBK_BF32_ABL == 3      // timing experiment: no global read of q
-        if (true) { for (int i = lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.001 * (double)(i + (int)blockIdx.x); } else
-#endif
-        if (rows_i == WAVE && ((reinterpret_cast<uintptr_t>(src) & 15) == 0) && (total % 2 == 0)) {
-            const double2* s2 = reinterpret_cast<const double2*>(src);
-            double2* d2 = reinterpret_cast<double2*>(lds_raw);
-            for (int i = lane; i < total / 2; i += WAVE) d2[i] = s2[i];
-        } else {
-            for (int i = lane; i < total; i += WAVE) lds_raw[i] = src[i];
-            for (int i = total + lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.0;
-        }
-    }
+    stage_rows(es, q, base, rows_i, nq, lds_raw, lane);
     // ---- per-wave tables: slot (a,b) -> key for THIS threshold and pair index ------------------------------------------------
     for (int i = lane; i < S * S; i += WAVE) { lds_rkey[i] = -1.0; lds_rp[i] = -1; }
     for (int i = lane; i < W * S; i += WAVE) { lds_wkey[i] = -1.0; lds_wtc[i] = 0.0; lds_wp[i] = -1; }
@@ -1833,25 +1769,10 @@ __global__ __launch_bounds__(64, 3) void k_broad_reg(DevModel m, EdgeSrc es, con
                 while (kcur < f) {
                     ++kcur;
                     const int k = kcur;
-                    const int ld = m.joint_load[k];
-                    Xf Pf;
-                    if (ld == -2) Pf = T;
-                    else if (ld == -1) Pf = bpose;
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 9; ++e) Pf.R[e] = lds_fr[(ld * 12 + e) * WAVE + lane];
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) Pf.t[e] = lds_fr[(ld * 12 + 9 + e) * WAVE + lane];
-                    }
+                    const Xf Pf = frame_parent(m.joint_load[k], T, bpose, lds_fr, lane);
                     const double qk = lds_raw[lane * nq + m.joint_qidx[k]];
                     joint_apply(m, k, Pf, qk, T);
-                    const int sv = m.joint_save[k];
-                    if (sv >= 0) {
-#pragma unroll
-                        for (int e = 0; e < 9; ++e) lds_fr[(sv * 12 + e) * WAVE + lane] = T.R[e];
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) lds_fr[(sv * 12 + 9 + e) * WAVE + lane] = T.t[e];
-                    }
+                    frame_save(m.joint_save[k], T, lds_fr, lane);
                 }
                 const double* loc = m.rs_local + 12 * sidx;
                 const double tl[3] = {loc[3], loc[7], loc[11]};
@@ -1875,21 +1796,7 @@ __global__ __launch_bounds__(64, 3) void k_broad_reg(DevModel m, EdgeSrc es, con
                 bits |= (dot3(d, d) < key) ? (1ull << b) : 0ull;
             }
             if (!active || hit) bits = 0ull;
-            // enqueue this row's survivors
-            while (true) {
-                const bool has = bits != 0ull;
-                const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
-                if (bal == 0ull) break;
-                if (has) {
-                    const int bit = __builtin_ctzll(bits);
-                    bits &= bits - 1ull;
-                    const unsigned p = (unsigned)lds_rp[a * S + bit];
-                    const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                    lds_queue[pos] = (p << 6) | (unsigned)lane;
-                }
-                qn += __builtin_popcountll(bal);
-                if (qn > BQ_CAP - WAVE) { flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf); qn = 0; }
-            }
+            drain_bits(bits, PairTab{lds_rp + a * S}, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
         }
     }
     // ---- world shapes (run-time loop) against the static robot shapes -------------------------------------------------------------
@@ -1938,25 +1845,10 @@ __global__ __launch_bounds__(64, 3) void k_broad_reg(DevModel m, EdgeSrc es, con
             }
         }
         if (!active || hit || (NBK_DBG(m) & 4)) bits = 0ull;
-        while (true) {
-            const bool has = bits != 0ull;
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
-            if (bal == 0ull) break;
-            if (has) {
-                const int bit = __builtin_ctzll(bits);
-                bits &= bits - 1ull;
-                const unsigned p = (unsigned)lds_wp[w * S + bit];
-                const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                lds_queue[pos] = (p << 6) | (unsigned)lane;
-            }
-            qn += __builtin_popcountll(bal);
-            if (qn > BQ_CAP - WAVE) { flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf); qn = 0; }
-        }
+        drain_bits(bits, PairTab{lds_wp + w * S}, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
     }
     if (qn > 0) flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
-    const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
-    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
-    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+    write_mask(hit, active, base, lane, mask_bits, mask_bytes);
 }
 
 // ---- k_broad_f32<S>: the register broadphase in float32, conservative -----------------------------------------------
@@ -2075,7 +1967,6 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
     const float* tab_rkey = ft.rkey; const float* tab_rcert = ft.rcert;
     const float* tab_wkey = ft.wkey; const float* tab_wtc = ft.wtc; const int* tab_wp = ft.wp;
     const float* tab_wcert = ft.wcert; const float* tab_wcin = ft.wcin; const float* tab_rho = ft.rho;
-    const float up = 1.0f + 2.4e-7f;
     const int64_t Beff = effective_batch(es, B);
     if (base >= Beff) return;               // edge mode: the launch covers the scratch's capacity, this block lies beyond the samples
 #ifdef NBK_BF32_STAMP
@@ -2083,32 +1974,7 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
 #endif
     NBK_BSTAMP(0);
     const int rows_i = (int)((Beff - base) < WAVE ? (Beff - base) : WAVE);
-    if (es.map != nullptr) {
-        if (lane < rows_i) {
-            unsigned e;
-            const double t = edge_t(es, es.map[base + lane], e);
-            const double omt = 1.0 - t;
-            const double* sp = es.starts + (size_t)e * nq;
-            const double* gp = es.goals + (size_t)e * nq;
-            for (int j = 0; j < nq; ++j) { const double a = omt * sp[j]; const double bb = t * gp[j]; lds_raw[lane * nq + j] = a + bb; }
-        } else {
-            for (int j = 0; j < nq; ++j) lds_raw[lane * nq + j] = 0.0;
-        }
-    } else {
-        const int total = rows_i * nq;
-        const double* src = q + base * nq;
-#if defined(NBK_BF32_ABL) && NBK_BF32_ABL == 3      // timing experiment: no global read of q
-        if (true) { for (int i = lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.001 * (double)(i + (int)blockIdx.x); } else
-#endif
-        if (rows_i == WAVE && ((reinterpret_cast<uintptr_t>(src) & 15) == 0) && (total % 2 == 0)) {
-            const double2* s2 = reinterpret_cast<const double2*>(src);
-            double2* d2 = reinterpret_cast<double2*>(lds_raw);
-            for (int i = lane; i < total / 2; i += WAVE) d2[i] = s2[i];
-        } else {
-            for (int i = lane; i < total; i += WAVE) lds_raw[i] = src[i];
-            for (int i = total + lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.0;
-        }
-    }
+    stage_rows(es, q, base, rows_i, nq, lds_raw, lane);
     __syncthreads();
     const bool active = lane < rows_i;
     NBK_BSTAMP(1);
@@ -2205,26 +2071,11 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
                 while (kcur < f) {
                     ++kcur;
                     const int k = kcur;
-                    const int ld = m.joint_load[k];
-                    XfF Pf;
-                    if (ld == -2) Pf = T;
-                    else if (ld == -1) Pf = bpose;
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 9; ++e) Pf.R[e] = lds_fr[(ld * 12 + e) * WAVE + lane];
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) Pf.t[e] = lds_fr[(ld * 12 + 9 + e) * WAVE + lane];
-                    }
+                    const XfF Pf = frame_parent(m.joint_load[k], T, bpose, lds_fr, lane);
                     const float qk = (float)lds_raw[lane * nq + m.joint_qidx[k]];
                     qabs += __builtin_fabsf(qk);
                     joint_apply_f(m, k, Pf, qk, T);
-                    const int sv = m.joint_save[k];
-                    if (sv >= 0) {
-#pragma unroll
-                        for (int e = 0; e < 9; ++e) lds_fr[(sv * 12 + e) * WAVE + lane] = T.R[e];
-#pragma unroll
-                        for (int e = 0; e < 3; ++e) lds_fr[(sv * 12 + 9 + e) * WAVE + lane] = T.t[e];
-                    }
+                    frame_save(m.joint_save[k], T, lds_fr, lane);
                 }
                 const float* tl = m.f_tab + m.f_tl + 3 * sidx;
                 const XfF& F = f < 0 ? bpose : T;
@@ -2266,22 +2117,7 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
         const float* tab_rneg = ft.rneg;
         const float* tab_rnd = ft.rnd;
         const float* tab_wkey2 = ft.wkey2;
-        // one queue append: lanes with `cond_` get consecutive slots behind the pending items.  No "nearly full" test here:
-        // NBK_ROOM makes room for a whole row of slots before the row's appends start
-#define NBK_ENQUEUE(cond_, pidx_)                                                                                               \
-        {                                                                                                                       \
-            const bool c_ = (cond_);                                                                                            \
-            const unsigned long long cm_ = __builtin_amdgcn_ballot_w64(c_);                                                     \
-            if (cm_ != 0ull) {                                                                                                  \
-                if (c_) {                                                                                                       \
-                    const int pos_ = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm_, 0u)); \
-                    lds_queue[pos_] = ((unsigned)(pidx_) << 6) | (unsigned)lane;                                                \
-                }                                                                                                               \
-                qn += __builtin_popcountll(cm_);                                                                                \
-            }                                                                                                                   \
-        }
-#define NBK_ROOM(slots_)                                                                                                        \
-        if (qn > qcap - (slots_) * WAVE) { flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf); qn = 0; }
+        // (appends: enqueue_lanes; queue_room makes room for a whole row of S slots before the row's appends start)
 #if defined(NBK_BF32_ABL) && NBK_BF32_ABL == 5
         for (int wi = 0; wi < (e2 == 12345.0f ? n_reach : 0); ++wi) {
 #else
@@ -2349,10 +2185,10 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
                 hit = hit || (acc_h < 0);
                 const bool live = active && !hit && !(NBK_DBG(m) & 4);
                 if (__builtin_amdgcn_ballot_w64(acc_c < 0 && live) != 0ull) {
-                    NBK_ROOM(S)
+                    queue_room(S * WAVE, qcap, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
 #pragma unroll
                     for (int a = 0; a < S; ++a)
-                        if (a < m.n_rshapes) NBK_ENQUEUE(cwv[a] < 0 && live, tab_wp[w * 16 + a]);
+                        if (a < m.n_rshapes) enqueue_lanes(cwv[a] < 0 && live, (unsigned)tab_wp[w * 16 + a], lds_queue, qn, lane);
                 }
                 continue;
             } else if (WH && wk == K_HULL) {
@@ -2385,10 +2221,10 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
                 hit = hit || (acc_h < 0);
                 const bool live = active && !hit && !(NBK_DBG(m) & 4);
                 if (__builtin_amdgcn_ballot_w64(acc_c < 0 && live) != 0ull) {
-                    NBK_ROOM(S)
+                    queue_room(S * WAVE, qcap, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
 #pragma unroll
                     for (int a = 0; a < S; ++a)
-                        if (a < m.n_rshapes) NBK_ENQUEUE(cwv[a] < 0 && live, tab_wp[w * 16 + a]);
+                        if (a < m.n_rshapes) enqueue_lanes(cwv[a] < 0 && live, (unsigned)tab_wp[w * 16 + a], lds_queue, qn, lane);
                 }
                 continue;
             } else {
@@ -2408,10 +2244,10 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
 #pragma unroll
             for (int a = 0; a < S; ++a) anyc = anyc || c[a];
             if (__builtin_amdgcn_ballot_w64(anyc && live) != 0ull) {          // one branch per world shape; most have no candidate
-                NBK_ROOM(S)
+                queue_room(S * WAVE, qcap, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
 #pragma unroll
                 for (int a = 0; a < S; ++a)
-                    if (a < m.n_rshapes) NBK_ENQUEUE(c[a] && live, tab_wp[w * 16 + a]);
+                    if (a < m.n_rshapes) enqueue_lanes(c[a] && live, (unsigned)tab_wp[w * 16 + a], lds_queue, qn, lane);
             }
         }
         NBK_BSTAMP(3);
@@ -2450,22 +2286,18 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
                     }
                     hit = hit || (acc_f < 0);
                     const bool live = active && !hit;
-                    NBK_ROOM(S)
+                    queue_room(S * WAVE, qcap, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
 #pragma unroll
                     for (int b = a + 1; b < S; ++b) {
                         const V2i ei = __builtin_bit_cast(V2i, ev[b / 2]);
-                        NBK_ENQUEUE(((b % 2) ? ei.y : ei.x) < 0 && live, ft.rp[a * 16 + b]);
+                        enqueue_lanes(((b % 2) ? ei.y : ei.x) < 0 && live, (unsigned)ft.rp[a * 16 + b], lds_queue, qn, lane);
                     }
                 }
             }
         }
-#undef NBK_ENQUEUE
-#undef NBK_ROOM
         NBK_BSTAMP(4);
         if (qn > 0) flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
-        const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
-        if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
-        if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+        write_mask(hit, active, base, lane, mask_bits, mask_bytes);
 #ifdef NBK_BF32_STAMP
         NBK_BSTAMP(5);
         if (lane == 0) { unsigned long long* pr_ = g_broad_prof + 8 * (blockIdx.x & 16383u); for (int e_ = 0; e_ < 5; ++e_) pr_[e_] += bstamp[e_ + 1] - bstamp[e_]; pr_[7] += 1ull; }
@@ -2473,6 +2305,7 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
         return;
     }
     // ---- general pair stage (some lane's slack exceeds the static bound: prismatic travel, huge joint values) ----------------------
+    const float up = 1.0f + 2.4e-7f;
     const bool cert_ok = e2 <= m.f_e2max;
     bool certh = false;
     for (int wi = 0; wi < n_reach; ++wi) {
@@ -2559,20 +2392,7 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
         }
         hit = hit || (cert_ok && certh);
         if (!active || hit || (NBK_DBG(m) & 4)) bits = 0ull;
-        while (true) {
-            const bool has = bits != 0ull;
-            const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
-            if (bal == 0ull) break;
-            if (has) {
-                const int bit = __builtin_ctzll(bits);
-                bits &= bits - 1ull;
-                const unsigned p = (unsigned)tab_wp[w * 16 + bit];
-                const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                lds_queue[pos] = (p << 6) | (unsigned)lane;
-            }
-            qn += __builtin_popcountll(bal);
-            if (qn > BQ_CAP - WAVE) { flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf); qn = 0; }
-        }
+        drain_bits(bits, PairTab{tab_wp + w * 16}, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
     }
     if (m.bq_count[1] > 0) {
 #pragma unroll
@@ -2589,26 +2409,11 @@ __global__ __launch_bounds__(64, NBK_BF32_WAVES) void k_broad_f32(DevModel m, Ed
             }
             hit = hit || (cert_ok && certh);
             if (!active || hit) bits = 0ull;
-            while (true) {
-                const bool has = bits != 0ull;
-                const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
-                if (bal == 0ull) break;
-                if (has) {
-                    const int bit = __builtin_ctzll(bits);
-                    bits &= bits - 1ull;
-                    const unsigned p = (unsigned)ft.rp[a * 16 + bit];
-                    const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                    lds_queue[pos] = (p << 6) | (unsigned)lane;
-                }
-                qn += __builtin_popcountll(bal);
-                if (qn > BQ_CAP - WAVE) { flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf); qn = 0; }
-            }
+            drain_bits(bits, PairTab{ft.rp + a * 16}, DevRoute{m}, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
         }
     }
     if (qn > 0) flush_items(m, lds_queue, qn, base, q_count, q_items, cap, lane, es.ovf);
-    const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
-    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
-    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+    write_mask(hit, active, base, lane, mask_bits, mask_bytes);
 }
 #undef cx
 #undef cy
@@ -2817,19 +2622,7 @@ NBK_DEV void narrow_body(const DevModel& m, const EdgeSrc& es, const double* __r
             double* myq = qstage + threadIdx.x * m.n_q;
             const int nq1 = m.n_q - 1;
             if (es.map != nullptr) {
-                unsigned e;
-                const double et = edge_t(es, es.map[b], e);
-                const double eomt = 1.0 - et;
-                const double* sp = es.starts + (size_t)e * m.n_q;
-                const double* gp = es.goals + (size_t)e * m.n_q;
-                for (int j0 = 0; j0 < m.n_q; j0 += 4) {
-                    double sv[4], gv[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) { const int j = (j0 + u) < nq1 ? (j0 + u) : nq1; sv[u] = sp[j]; gv[u] = gp[j]; }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (j0 + u <= nq1) { const double a = eomt * sv[u]; const double bb = et * gv[u]; myq[j0 + u] = a + bb; }
-                }
+                edge_sample_row(es, es.map[b], m.n_q, myq, 1);
             } else {
                 const double* qrow = q + b * m.n_q;
                 for (int j0 = 0; j0 < m.n_q; j0 += 8) {

@@ -1,11 +1,15 @@
 // Pieces of the float32 broadphase that the ahead-of-time k_broad_f32<S, WH> (nbk.hip) and the per-robot k_broad_f32_spec
 // (nbk_bf32_spec.hpp, compiled with hipRTC) share: ONE definition of the slot-table layout k_prepare_f32 writes (ftab_offsets),
-// of the packed chain-sweep joints, of sincos_f and of the queue flush -- both kernels compile these.
+// of the packed chain-sweep joints, of sincos_f, of slot_e2, of the plain-row q staging, of the queue appends (enqueue_lanes,
+// queue_room, drain_bits), of the queue flush and of the mask epilogue -- both kernels compile these.  The float64 broadphases
+// of nbk.hip (k_broad, k_broad_reg) take drain_bits and write_mask from here as well.
 //
 // The per-slot tests below (box_slot2 ... robot_slot_gen) are the specialised kernel's; k_broad_f32 keeps the same statements
-// inline.  Calling them from k_broad_f32 changed its register allocation at the 5-waves-per-SIMD bound (VGPR spills 52 -> 71
-// with the general stage through them, 52 -> 80 with the fast stage through them; 68 -> 74 us on c2), so a change to a slot
-// test is made here AND in k_broad_f32, and tests/test_broad_spec.py compares the two kernels' masks over both stages.
+// inline.  Calling them from k_broad_f32 changes its register allocation at the 5-waves-per-SIMD bound: with the general stage
+// through them every instance spills more (scratch bytes <12, false> 108 -> 124, <16, false> 176 -> 224, <16, true> 176 -> 208;
+// with the fast stage alone 108 -> 116) and <12, false> runs 0.9-2.3 us of 121 us slower on 1e6 plain rows of c2, also with the
+// results returned by value (the same code) or the stages apart (profiles/r11_a_broad_dedupe.log).  So a change to a slot test
+// is made here AND in k_broad_f32, and tests/test_broad_spec.py compares the two kernels' masks over both stages.
 //
 // Self-contained for hipRTC: no includes, nothing beyond what hiprtc supplies.  nbk.hip includes it at file scope; build.py
 // embeds it into libnbk.so next to nbk_bf32_spec.hpp, and source_digest() covers it.
@@ -229,6 +233,22 @@ NBK_BF32_DEV bool robot_slot_gen(float dx, float dy, float dz, float rs, float e
     return rs >= 0.0f && dd < r * r * up;
 }
 
+// ---- plain q rows ---------------------------------------------------------------------------------------------------------------
+// rows [base, base + rows_i) of q[.][nq] into the block's row-major slab lds_raw[64][nq] (lane reads lds_raw[lane * nq + j]): 16-byte
+// loads where the slab is full, else scalar ones and zeros for the rows past the batch
+NBK_BF32_DEV void stage_plain_rows(const double* __restrict__ q, long long base, int rows_i, int nq, double* lds_raw, int lane) {
+    const int total = rows_i * nq;
+    const double* src = q + base * nq;
+    if (rows_i == WAVE && ((reinterpret_cast<unsigned long long>(src) & 15) == 0) && (total % 2 == 0)) {
+        const double2* s2 = reinterpret_cast<const double2*>(src);
+        double2* d2 = reinterpret_cast<double2*>(lds_raw);
+        for (int i = lane; i < total / 2; i += WAVE) d2[i] = s2[i];
+    } else {
+        for (int i = lane; i < total; i += WAVE) lds_raw[i] = src[i];
+        for (int i = total + lane; i < WAVE * nq; i += WAVE) lds_raw[i] = 0.0;
+    }
+}
+
 // ---- queue flush ------------------------------------------------------------------------------------------------------------------
 // Items are routed by the kind class of their pair (vp_cls: box-box, box-cylinder, cylinder-cylinder, the rest): class c owns
 // `groups(c)` (at least 1) of the sub-queues from `base(c)` on, in proportion to its pairs; a block appends to the (block %
@@ -264,6 +284,59 @@ NBK_BF32_DEV void flush_items_r(const Route& rt, unsigned* lds_queue, int qn, lo
         }
     }
     __syncthreads();
+}
+
+// ---- queue appends ----------------------------------------------------------------------------------------------------------------
+// One append: the lanes with `cond` get consecutive slots behind the pending items.  No "nearly full" test here: queue_room makes
+// room for a whole row of slots before the row's appends start.
+NBK_BF32_DEV void enqueue_lanes(bool cond, unsigned pair, unsigned* lds_queue, int& qn, int lane) {
+    const unsigned long long cm = __builtin_amdgcn_ballot_w64(cond);
+    if (cm != 0ull) {
+        if (cond) {
+            const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
+            lds_queue[pos] = (pair << 6) | (unsigned)lane;
+        }
+        qn += __builtin_popcountll(cm);
+    }
+}
+// flush unless `need` more items fit a staging area of `qcap` items
+template <class Route>
+NBK_BF32_DEV void queue_room(int need, int qcap, const Route& rt, unsigned* lds_queue, int& qn, long long base_cfg, unsigned long long* q_count,
+                             unsigned long long* q_items, unsigned long long cap_sub, int lane, unsigned char* ovf) {
+    if (qn > qcap - need) { flush_items_r(rt, lds_queue, qn, base_cfg, q_count, q_items, cap_sub, lane, ovf); qn = 0; }
+}
+// Survivor bits -> items: every lane holds one bit per surviving slot of a row; each trip takes the lowest bit of every lane that
+// has one left, so a trip appends at most WAVE items and the staging area (BQ_CAP) is flushed once fewer than WAVE are free.
+// pair_of(bit): the pair index of that slot (PairTab: a row of a pair-index table).
+struct PairTab {
+    const int* t;
+    NBK_BF32_DEV unsigned operator()(int bit) const { return (unsigned)t[bit]; }
+};
+template <class PairOf, class Route>
+NBK_BF32_DEV void drain_bits(unsigned long long bits, const PairOf& pair_of, const Route& rt, unsigned* lds_queue, int& qn, long long base_cfg,
+                             unsigned long long* q_count, unsigned long long* q_items, unsigned long long cap_sub, int lane, unsigned char* ovf) {
+    while (true) {
+        const bool has = bits != 0ull;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
+        if (bal == 0ull) break;
+        if (has) {
+            const int bit = __builtin_ctzll(bits);
+            bits &= bits - 1ull;
+            const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+            lds_queue[pos] = (pair_of(bit) << 6) | (unsigned)lane;
+        }
+        qn += __builtin_popcountll(bal);
+        queue_room(WAVE, BQ_CAP, rt, lds_queue, qn, base_cfg, q_count, q_items, cap_sub, lane, ovf);
+    }
+}
+
+// ---- mask epilogue ----------------------------------------------------------------------------------------------------------------
+// one bit per configuration of the block (and / or one byte): the hits decided so far; the narrowphase ORs the rest in
+template <class Word>
+NBK_BF32_DEV void write_mask(bool hit, bool active, long long base, int lane, Word* mask_bits, unsigned char* mask_bytes) {
+    const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
+    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
+    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
 }
 
 }  // namespace nbk

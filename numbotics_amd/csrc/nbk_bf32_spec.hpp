@@ -12,16 +12,17 @@
 // table values), and the float32 stage only culls or certifies with the same conservative thresholds: every survivor is
 // decided again in float64 by k_narrow_*, so the masks are those of the generic kernel.
 //
-// The table layout, the sweep joint, every per-slot test and the queue flush are nbk_bf32_common.hpp's, the very definitions
-// k_broad_f32 uses; what is here is the specialised control flow around them.  nbk.hip hands hipRTC the generated Spec, then
-// nbk_bf32_common.hpp, then this file.  Self-contained for hipRTC: no host headers, nothing beyond what hiprtc supplies.
+// The table layout, the sweep joint, the plain-row q staging, the queue appends and flush and the mask epilogue are
+// nbk_bf32_common.hpp's: the functions k_broad_f32 calls as well.  The per-slot tests are that header's too; k_broad_f32 keeps
+// the same statements inline (see the header for why).  What is here is the specialised control flow around them.  nbk.hip hands hipRTC the generated Spec, then nbk_bf32_common.hpp, then this file.  Self-contained for hipRTC:
+// no host headers, nothing beyond what hiprtc supplies.
 
 #define NBK_SPEC_DEV __device__ __forceinline__
 #define NBK_SPEC_INLINE __attribute__((always_inline))      // every lambda of the kernel: its captures must stay registers
 
 namespace nbk_spec {
 
-using namespace nbk;            // nbk_bf32_common.hpp: the table layout, the sweep joint, the slot tests, the queue flush
+using namespace nbk;            // nbk_bf32_common.hpp: the table layout, the sweep joint, the slot tests, the queue appends and flush
 enum { K_BOX = 2, K_HULL = 4, K_PLANE = 5 };
 enum { JK_PRISMATIC = 4 };
 
@@ -64,18 +65,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
     unsigned* lds_queue = reinterpret_cast<unsigned*>(lds_raw);
     if (base >= B) return;
     const int rows_i = (int)((B - base) < WAVE ? (B - base) : WAVE);
-    {
-        const int total = rows_i * NQ;
-        const double* src = q + base * NQ;
-        if (rows_i == WAVE && ((reinterpret_cast<unsigned long long>(src) & 15) == 0) && (total % 2 == 0)) {
-            const double2* s2 = reinterpret_cast<const double2*>(src);
-            double2* d2 = reinterpret_cast<double2*>(lds_raw);
-            for (int i = lane; i < total / 2; i += WAVE) d2[i] = s2[i];
-        } else {
-            for (int i = lane; i < total; i += WAVE) lds_raw[i] = src[i];
-            for (int i = total + lane; i < WAVE * NQ; i += WAVE) lds_raw[i] = 0.0;
-        }
-    }
+    stage_plain_rows(q, base, rows_i, NQ, lds_raw, lane);
     __syncthreads();
     const bool active = lane < rows_i;
     int hit = 0;                // (an int: a bool captured by the lambdas below was kept in scratch, two bytes per lane)
@@ -124,20 +114,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
     const float e2 = 2.0f * rmax * __builtin_fmaf(2.4e-7f, qabs, Spec::f_eps);
     __syncthreads();            // the q slab is dead from here on: its LDS region becomes the item queue
     int qn = 0;
-#define NBK_SPEC_ENQUEUE(cond_, pidx_)                                                                                          \
-    {                                                                                                                           \
-        const bool c_ = (cond_);                                                                                                \
-        const unsigned long long cm_ = __builtin_amdgcn_ballot_w64(c_);                                                         \
-        if (cm_ != 0ull) {                                                                                                      \
-            if (c_) {                                                                                                           \
-                const int pos_ = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm_, 0u)); \
-                lds_queue[pos_] = ((unsigned)(pidx_) << 6) | (unsigned)lane;                                                    \
-            }                                                                                                                   \
-            qn += __builtin_popcountll(cm_);                                                                                    \
-        }                                                                                                                       \
-    }
-#define NBK_SPEC_ROOM(slots_)                                                                                                   \
-    if (qn > qcap - (slots_) * WAVE) { flush_items_r(SpecRoute<Spec>{vp_cls}, lds_queue, qn, base, q_count, q_items, cap, lane, ovf); qn = 0; }
+    const SpecRoute<Spec> route{vp_cls};
     const float* wbx_all = tab + FO.wbx;
     if (__builtin_amdgcn_ballot_w64(!(e2 <= Spec::f_e2max)) == 0ull) {
         // ---- fast stage: world shapes -----------------------------------------------------------------------------------------
@@ -169,10 +146,10 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                 hit = hit || (acc_h < 0);
                 const bool live = active && !hit;
                 if (__builtin_amdgcn_ballot_w64(acc_c < 0 && live) != 0ull) {
-                    NBK_SPEC_ROOM(S)
+                    queue_room(S * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
                     sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
                         constexpr int a = decltype(A)::value;
-                        if constexpr (Spec::wpair(wi, a) >= 0) NBK_SPEC_ENQUEUE(cwv[a] < 0 && live, Spec::wpair(wi, a));
+                        if constexpr (Spec::wpair(wi, a) >= 0) enqueue_lanes(cwv[a] < 0 && live, (unsigned)Spec::wpair(wi, a), lds_queue, qn, lane);
                     });
                 }
             } else {
@@ -198,10 +175,10 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                 hit = hit || ch;
                 const bool live = active && !hit;
                 if (__builtin_amdgcn_ballot_w64(anyc && live) != 0ull) {
-                    NBK_SPEC_ROOM(S)
+                    queue_room(S * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
                     sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
                         constexpr int a = decltype(A)::value;
-                        if constexpr (Spec::wpair(wi, a) >= 0) NBK_SPEC_ENQUEUE(c[a] && live, Spec::wpair(wi, a));
+                        if constexpr (Spec::wpair(wi, a) >= 0) enqueue_lanes(c[a] && live, (unsigned)Spec::wpair(wi, a), lds_queue, qn, lane);
                     });
                 }
             }
@@ -236,12 +213,12 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                         });
                         hit = hit || (acc_f < 0);
                         const bool live = active && !hit;
-                        NBK_SPEC_ROOM(Spec::row_slots(a))
+                        queue_room(Spec::row_slots(a) * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
                         sfor<a + 1, S>([&](auto Bb) NBK_SPEC_INLINE {
                             constexpr int b = decltype(Bb)::value;
                             if constexpr (Spec::rr_p(a, b) >= 0) {
                                 const V2i ei = __builtin_bit_cast(V2i, ev[b / 2]);
-                                NBK_SPEC_ENQUEUE(((b % 2) ? ei.y : ei.x) < 0 && live, Spec::rr_p(a, b));
+                                enqueue_lanes(((b % 2) ? ei.y : ei.x) < 0 && live, (unsigned)Spec::rr_p(a, b), lds_queue, qn, lane);
                             }
                         });
                     }
@@ -258,22 +235,6 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
         const int* tab_wp = reinterpret_cast<const int*>(tab + FO.wp);
         const int* tab_rp = reinterpret_cast<const int*>(tab + FO.rp);
         const float* tab_rkey = tab + FO.rkey; const float* tab_rcert = tab + FO.rcert;
-        auto drain = [&](unsigned long long bits, const int* ptab) NBK_SPEC_INLINE {
-            while (true) {
-                const bool has = bits != 0ull;
-                const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);
-                if (bal == 0ull) break;
-                if (has) {
-                    const int bit = __builtin_ctzll(bits);
-                    bits &= bits - 1ull;
-                    const unsigned p = (unsigned)ptab[bit];
-                    const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                    lds_queue[pos] = (p << 6) | (unsigned)lane;
-                }
-                qn += __builtin_popcountll(bal);
-                if (qn > BQ_CAP - WAVE) { flush_items_r(SpecRoute<Spec>{vp_cls}, lds_queue, qn, base, q_count, q_items, cap, lane, ovf); qn = 0; }
-            }
-        };
         sfor<0, Spec::NW>([&](auto WI) NBK_SPEC_INLINE {
             constexpr int wi = decltype(WI)::value;
             constexpr int w = Spec::wl[wi];
@@ -300,7 +261,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
             });
             hit = hit || (cert_ok && certh);
             if (!active || hit) bits = 0ull;
-            drain(bits, tab_wp + w * 16);
+            drain_bits(bits, PairTab{tab_wp + w * 16}, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
         });
         if constexpr (Spec::rr_any) {
             sfor<0, S - 1>([&](auto A) NBK_SPEC_INLINE {
@@ -315,16 +276,12 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                 });
                 hit = hit || (cert_ok && certh);
                 if (!active || hit) bits = 0ull;
-                drain(bits, tab_rp + a * 16);
+                drain_bits(bits, PairTab{tab_rp + a * 16}, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
             });
         }
     }
-#undef NBK_SPEC_ENQUEUE
-#undef NBK_SPEC_ROOM
-    if (qn > 0) flush_items_r(SpecRoute<Spec>{vp_cls}, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
-    const unsigned long long word = __builtin_amdgcn_ballot_w64(hit && active);
-    if (mask_bits != nullptr && lane == 0) mask_bits[blockIdx.x] = word;
-    if (mask_bytes != nullptr && active) mask_bytes[base + lane] = hit ? 1 : 0;
+    if (qn > 0) flush_items_r(route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
+    write_mask(hit != 0, active, base, lane, mask_bits, mask_bytes);
 }
 
 }  // namespace nbk_spec

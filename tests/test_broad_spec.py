@@ -395,6 +395,35 @@ def test_spec_waves_with_one_bad_or_wide_lane(key, tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("key", EDGE_SCENES, ids=str)
+def test_generic_waves_with_one_wide_lane(key, tmp_path):
+    """The generic k_broad_f32 (a batch below SPEC_MIN_BATCH) through its general stage against plane, box and hull world shapes:
+    row 17 of every wave of 4096 + 37 rows is far outside the limits (see _moved) and takes its 63 neighbours through the general
+    stage with it.  The moved rows and the neighbours equal the oracle, and the neighbours equal the oracle's verdicts of the batch
+    without a wide lane.  Not trivial, by the oracle alone: at least 5 of the 65 moved rows collide and at least 5 are free, and
+    between 5 % and 95 % of the neighbours collide."""
+    arm, chain, obs, sm, dev, orc = _edge_scene(key, str(tmp_path))
+    B = 4096 + 37
+    assert B < sc.SPEC_MIN_BATCH
+    q = sc.sample(chain, B, 41)
+    rows = np.arange(17, B, 64)
+    wide = _moved(sm, q, rows, np.random.default_rng(42))
+    others = np.setdiff1d(np.arange(B), rows)
+    assert rows.size == 65 and np.array_equal(wide[others], q[others])
+    for thr in (0.0, 0.01):
+        ref = orc.validity(wide, thr, nthreads=8)
+        plain = orc.validity(q, thr, nthreads=8)
+        print(f"{key} at {thr}: {int(ref[rows].sum())} of {rows.size} moved rows collide, {ref[others].mean():.3f} of the others")
+        assert 5 <= int(ref[rows].sum()) <= rows.size - 5, (key, thr, int(ref[rows].sum()))
+        assert 0.05 <= ref[others].mean() <= 0.95, (key, thr, ref[others].mean())
+        got = dev.validity(wide, thr)
+        assert sc.used_kernel(dev) == sc.GENERIC, (key, thr, sc.used_kernel(dev))
+        assert np.array_equal(got[rows], ref[rows]), (key, thr, "moved rows", rows[got[rows] != ref[rows]][:8])
+        assert np.array_equal(got[others], ref[others]), (key, thr, "neighbours", others[got[others] != ref[others]][:8])
+        assert np.array_equal(got[others], plain[others]), (key, thr, "neighbours against the batch without a wide lane")
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("key", ("c2", sc.EDGE_CASE), ids=str)
 def test_spec_queue_overflow_is_redecided(key, tmp_path):
     """The item queue shrunk to a few KB (as test_queue_overflow_is_redecided_without_a_queue does for the generic kernel): blocks
