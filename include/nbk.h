@@ -25,7 +25,11 @@
  *     conveniences synchronise by definition, and so does nbk_spline_validity_batch (it reads its sample count back; it
  *     refuses a capturing stream; nbk_spline_continuous_batch does not).  Batches of 2^21 configurations or more (and edge batches of that many samples)
  *     run every other 2^20-configuration tile on a second, library-owned stream forked from and joined to `stream` with
- *     events -- the call still begins after, and completes before, its neighbours in `stream`'s order;
+ *     events -- the call still begins after, and completes before, its neighbours in `stream`'s order.  A captured call never
+ *     uses the second stream.  A captured nbk_validity_batch that finds on `stream` the scratch a tiled direct call left there
+ *     (sized for 2^20-configuration tiles, whatever that call's batch) runs such tiles one after the other on `stream`, so "once
+ *     outside the capture" holds for these batches as for smaller ones; a captured edge batch runs its tiles without the second stream in its own
+ *     scratch, which direct edge calls always size for that;
  *   - every compute call must be made with the descriptor's device current (hipSetDevice):
  *     NBK_ERR_INVALID otherwise;
  *   - float64 everywhere (the reference computes in float64); q is row-major (B, n_q);

@@ -210,6 +210,7 @@ struct nbk_model {
     int bf32_state = 0;            // 0 not tried, 1 bf32_fn is loaded, -1 unavailable (hipRTC missing, compile failed, NBK_NO_JIT)
     hipFunction_t bf32_fn = nullptr;
     std::atomic<int> last_broad{0};   // broadphase of the last validity call: 0 none yet, 1 generic k_broad_f32, 2 specialised, 3 another one
+    std::atomic<long long> last_tiling[3] = {{0}, {0}, {0}};   // the last two-kernel launch: tiles, configurations per tile, 1 = odd tiles on the second stream
     // nbk_model_create_movable: the world tables (ws_core, ws_center, the float copies at f_tab + f_wc, bq_static) are rewritten in
     // place by k_world_update; everything else stays immutable.  `world_status` (device) is what the guards of the entry points read.
     bool movable = false;
@@ -4589,11 +4590,19 @@ static int narrow_variant(const nbk_model* m, double threshold) {
 }
 // diagnostic (not part of include/nbk.h): the narrowphase build nbk_validity_batch picks for this descriptor at this threshold
 extern "C" int32_t nbk_debug_narrow_variant(const nbk_model* m, double threshold) { return m == nullptr ? NBK_ERR_INVALID : narrow_variant(m, threshold); }
+// diagnostic (not part of include/nbk.h): how the descriptor's last broadphase + narrowphase launch (plain rows or edge samples) was
+// tiled -- out[0] tiles, out[1] configurations per tile, out[2] 1 when odd tiles ran on the second stream; zeros before the first
+extern "C" int32_t nbk_debug_last_tiling(const nbk_model* m, int64_t out[3]) {
+    if (m == nullptr || out == nullptr) return NBK_ERR_INVALID;
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)m->last_tiling[i].load(std::memory_order_relaxed);
+    return NBK_OK;
+}
 
-// `pipe` (the library's own scratch only): odd tiles run on iw0->aux_stream with the scratch set iw0->aux
+// `pipe` (the library's own scratch only): odd tiles run on iw0->aux_stream with the scratch set iw0->aux.  `pipe_sized`: the tiles
+// of a pipelined call, all on st0 (a captured call on a stream whose scratch a pipelined call sized)
 static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, EdgeSrc es, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
-                                      uint8_t* mask_bytes, void* workspace0, hipStream_t st0, StreamWs* iw0, bool pipe) {
-    const int64_t tile = call_tile(m, pc, B, pipe);
+                                      uint8_t* mask_bytes, void* workspace0, hipStream_t st0, StreamWs* iw0, bool pipe, bool pipe_sized) {
+    const int64_t tile = call_tile(m, pc, B, pipe || pipe_sized);
     if (pipe) {
         NBK_HIP(hipEventRecord(iw0->ev_fork, st0));                          // the odd tiles' inputs are whatever the caller's stream has produced
         NBK_HIP(hipStreamWaitEvent(iw0->aux_stream, iw0->ev_fork, 0));
@@ -4621,6 +4630,12 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
         if (mm->bf32_state == 1) spec_fn = mm->bf32_fn;
     }
     const_cast<nbk_model*>(m)->last_broad.store(spec_fn != nullptr ? 2 : (use_reg && f32 ? 1 : 3), std::memory_order_relaxed);
+    {
+        std::atomic<long long>* lt = const_cast<nbk_model*>(m)->last_tiling;
+        lt[0].store((long long)((B + tile - 1) / tile), std::memory_order_relaxed);
+        lt[1].store((long long)tile, std::memory_order_relaxed);
+        lt[2].store(pipe ? 1 : 0, std::memory_order_relaxed);
+    }
     int tile_no = 0;
     for (int64_t b0 = 0; b0 < B; b0 += tile, ++tile_no) {
         const bool odd = pipe && (tile_no & 1);
@@ -4716,8 +4731,8 @@ static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, 
 }
 
 static int32_t launch_two_kernel(const nbk_model* m, const PairCounts& pc, EdgeSrc es, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
-                                 uint8_t* mask_bytes, void* workspace, hipStream_t st, StreamWs* iw = nullptr, bool pipe = false) {
-    const int32_t rc = launch_two_kernel_impl(m, pc, es, q, B, threshold, mask_bits, mask_bytes, workspace, st, iw, pipe);
+                                 uint8_t* mask_bytes, void* workspace, hipStream_t st, StreamWs* iw = nullptr, bool pipe = false, bool pipe_sized = false) {
+    const int32_t rc = launch_two_kernel_impl(m, pc, es, q, B, threshold, mask_bits, mask_bytes, workspace, st, iw, pipe, pipe_sized);
     if (rc != NBK_OK && iw != nullptr) { iw->ready = false; if (iw->aux) iw->aux->ready = false; }      // whatever state the queues are in: start over
     return rc;
 }
@@ -4814,10 +4829,17 @@ int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, doubl
     hipStream_t st = (hipStream_t)stream;
     const bool capturing = stream_capturing(st);
     const bool pipe = pipelined(m, B) && !capturing;
-    const int64_t need = two_kernel_workspace_bytes(m, pc, B, pipe);
+    int64_t need = two_kernel_workspace_bytes(m, pc, B, pipe);
     StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
     if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces: pass your own (nbk_validity_batch_ws)"); return NBK_ERR_ALLOC; }
     std::lock_guard<std::mutex> lock(w->mu);
+    // a direct call of this size is pipelined and sizes the scratch for ITS tiles: a capture that finds such a scratch runs the same
+    // tiles, one after the other on the caller's stream (no second stream inside a graph); tiling never changes a result
+    bool pipe_sized = false;
+    if (capturing && w->ws_bytes < (size_t)need && pipelined(m, B)) {
+        const int64_t need_tiles = two_kernel_workspace_bytes(m, pc, B, true);
+        if (w->ws_bytes >= (size_t)need_tiles) { pipe_sized = true; need = need_tiles; }
+    }
     if (capturing && w->ws_bytes < (size_t)need) {
         snprintf(g_err, sizeof(g_err), "graph capture: this stream's internal workspace is not allocated yet -- run the call once "
                  "outside the capture, or pass a workspace (nbk_validity_batch_ws)");
@@ -4828,7 +4850,7 @@ int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, doubl
     // the graph, and the next direct call starts from scratch as well
     if (capturing) { w->ready = false; w->captured = true; }
     if (pipe) { const int32_t rc = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, B); if (rc != NBK_OK) return rc; }
-    return guard_masks(m, launch_two_kernel(m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, w->ws, st, capturing ? nullptr : w, pipe),
+    return guard_masks(m, launch_two_kernel(m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, w->ws, st, capturing ? nullptr : w, pipe, pipe_sized),
                        mask_bits, mask_bytes, B, st);
 }
 

@@ -386,6 +386,14 @@ class DeviceModel:
         """Diagnostic: the narrowphase build ``validity`` launches for this scene at this threshold (bench.py reports it)."""
         return self.NARROW_BUILDS[int(self._lib.nbk_debug_narrow_variant(self._h, float(threshold)))]
 
+    def last_tiling(self):
+        """Diagnostic: (tiles, configurations per tile, pipelined) of this descriptor's last broadphase + narrowphase launch, a
+        validity batch or the flat sample batch of an edge call (nbk_debug_last_tiling); ``pipelined`` is 1 when the odd tiles ran
+        on the library's second stream.  (0, 0, 0) before the first such launch."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self._lib.nbk_debug_last_tiling(self._h, out), "nbk_debug_last_tiling")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def validity_scalar(self, q, threshold=0.0) -> bool:
         """One configuration from host memory (the reference's scalar ``in_collision(q)``): pinned, device-mapped staging
         inside the library, one wait -- no torch tensors on the way."""
