@@ -17,11 +17,13 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <ctype.h>
 
 #include <memory>
 #include <mutex>
 #include <atomic>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 #include <string>
 #include <map>
@@ -31,6 +33,13 @@
 #include "../../include/nbk.h"
 #include "nbk_device.hpp"
 #include "nbk_bf32_common.hpp"       // WAVE, BQ_CAP, CNT_STRIDE, the float32 broadphase pieces both its kernels share
+namespace nbk {
+// The global queue is sharded into NSUB sub-queues (block b appends to sub-queue b % NSUB): one counter
+// saturates at ~90 appends/us (MI355X_MICROARCH.md, row "dequeue"), which 15k waves would all hit.
+constexpr int NSUB = 256;
+}
+#include "nbk_plan.hpp"              // WsLayout, TilePlan, TableCache, EdgeLayout, SplineLayout: the host arithmetic of the validity launch path
+static_assert(nbk::PLAN_WAVE == nbk::WAVE && nbk::PLAN_CNT_STRIDE == nbk::CNT_STRIDE && nbk::PLAN_NSUB == nbk::NSUB, "nbk_plan.hpp's stand-alone constants");
 
 namespace nbk {
 
@@ -134,22 +143,14 @@ NBK_DEV int64_t effective_batch(const EdgeSrc& es, int64_t B) {
 }  // namespace nbk
 
 namespace nbk {
-// per-(descriptor, stream) scratch.  The float32 broadphase tables stay valid while the threshold does not change and the queue
-// counters exist twice -- a call uses set (epoch & 1), its narrowphase clears the other set for the next call -- so steady-state
-// calls launch two kernels, not three.  The edge path keeps plan / counts / offsets / sample map / mask words here, sized for a
-// capacity in samples; `stats` is pinned host memory the device writes the true sample count into (read, never waited for, at the
-// start of the NEXT call to grow the capacity).
+// per-(descriptor, stream) scratch.  `tables`: what of the validity workspace the next call may reuse (TableCache, nbk_plan.hpp).
+// The edge path keeps plan / counts / offsets / sample map / mask words here, sized for a capacity in samples; `stats` is pinned
+// host memory the device writes the true sample count into (read, never waited for, at the start of the NEXT call to grow the capacity).
 struct StreamWs {
     hipStream_t stream = nullptr;
     std::mutex mu;                  // two host threads driving one stream (also makes the set non-copyable)
     void* ws = nullptr; size_t ws_bytes = 0;
-    bool ready = false; double thr = 0.0; unsigned epoch = 0;
-    unsigned long long world_epoch = 0;   // movable descriptors: the nbk_model::world_epoch the tables were prepared at (an update of the
-                                          // world poses makes them stale)
-    bool captured = false;          // a call on this stream has been captured into a hipGraph: its nodes reuse this workspace (counter
-                                    // set 0, the tables for THEIR threshold) whenever the graph is replayed, behind the host's back, so
-                                    // direct calls on this stream never trust `ready` again -- each prepares its tables and clears both
-                                    // counter sets itself (one more 5 us launch per call)
+    TableCache tables;
     void* ews = nullptr; size_t ews_bytes = 0;
     long long ecap_edges = 0; unsigned long long ecap_samples = 0;
     unsigned long long* stats = nullptr;      // [4] pinned + mapped: samples needed by the last finished edge call, edges served by the overflow kernel
@@ -179,7 +180,8 @@ struct nbk_model {
     int n_pairs;
     int n_q;
     int n_joints;
-    int cls_count[4];          // pairs per kind class; cls_groups (in d) sub-queues serve each
+    nbk::PlanModel pm;         // the numbers workspace sizing and tiling read (nbk_plan.hpp), and the workspace layout made from them
+    nbk::WsLayout ws;
     // per pair, in broadphase order: what the per-call static reach test (k_prepare_f32) needs, so that the host can count the
     // pairs a call can produce items for at ITS threshold and size queues / tiles for those instead of for every pair
     std::vector<double> h_static, h_m0, h_m1;
@@ -192,39 +194,43 @@ struct nbk_model {
     bool lds_broad_ok;        // the LDS broadphase k_broad fits this scene (else only the register broadphases are used)
     bool margins_zero;        // every pair that can reach GJK (no point core, not point/segment x point/segment) has mA = mB = 0:
                               // with threshold 0 its contact threshold tc is exactly 0 and the boolean walk decides it
-    // Internal scratch of nbk_validity_batch / nbk_edge_validity_batch: ONE SET PER STREAM (created on a stream's first call), so
-    // calls on different streams share nothing mutable and overlap on the device; `mu` only guards the list itself.
-    std::mutex mu;
-    std::vector<nbk::StreamWs*> wss;
-    // nbk_validity_scalar_host: pinned, device-mapped staging for one configuration + its private stream
-    std::mutex scalar_mu;
-    double* scalar_q;         // [n_q] host-pinned, read by the kernel through its device alias
-    unsigned long long* scalar_out;
-    double* scalar_q_dev;     // device aliases of the two pinned buffers
-    unsigned long long* scalar_out_dev;
-    hipStream_t scalar_stream;
-    // the broadphase compiled for this robot (nbk_bf32_spec.hpp): the generated Spec text, "" when the robot does not qualify;
-    // the kernel is compiled / looked up on the first large validity call (bf32_mu guards the three fields below)
+    // the broadphase compiled for this robot (nbk_bf32_spec.hpp): the generated Spec text, "" when the robot does not qualify
     std::string bf32_spec;
-    std::mutex bf32_mu;
-    int bf32_state = 0;            // 0 not tried, 1 bf32_fn is loaded, -1 unavailable (hipRTC missing, compile failed, NBK_NO_JIT)
-    hipFunction_t bf32_fn = nullptr;
-    std::atomic<int> last_broad{0};   // broadphase of the last validity call: 0 none yet, 1 generic k_broad_f32, 2 specialised, 3 another one
-    std::atomic<long long> last_tiling[3] = {{0}, {0}, {0}};   // the last two-kernel launch: tiles, configurations per tile, 1 = odd tiles on the second stream
     // nbk_model_create_movable: the world tables (ws_core, ws_center, the float copies at f_tab + f_wc, bq_static) are rewritten in
     // place by k_world_update; everything else stays immutable.  `world_status` (device) is what the guards of the entry points read.
     bool movable = false;
     double world_radius = 0.0;
     const double* rs_reach = nullptr;         // [S] (device, frame order) reach of each robot shape's centre from the base; inf = unbounded
     int* world_status = nullptr;              // (device) 0 ok, 1 a centre beyond world_radius, 2 a non-finite pose
-    std::atomic<unsigned long long> world_epoch{0};   // bumped by every update: StreamWs tables prepared before it are stale
-    std::atomic<bool> world_captured{false};  // an update has been captured into a graph: replays move the world behind the host's back,
-                                              // so no stream of this descriptor reuses its tables any more
-    std::mutex world_mu;                      // updates of one descriptor serialise on the host
-    hipEvent_t world_ev = nullptr;            // recorded after the last direct update: the private stream of the scalar calls waits for it
-    bool world_ev_set = false;
-    double* world_stage = nullptr;            // [W][12] pinned + mapped staging of nbk_model_set_world_poses_host
-    double* world_stage_dev = nullptr;
+    // Everything above is fixed at creation.  What calls change on the host lives in `host`, which a const nbk_model* may write.
+    struct Host {
+        // Internal scratch of nbk_validity_batch / nbk_edge_validity_batch: ONE SET PER STREAM (created on a stream's first call), so
+        // calls on different streams share nothing mutable and overlap on the device; `mu` only guards the list itself.
+        std::mutex mu;
+        std::vector<nbk::StreamWs*> wss;
+        // nbk_validity_scalar_host: pinned, device-mapped staging for one configuration + its private stream
+        std::mutex scalar_mu;
+        double* scalar_q;         // [n_q] host-pinned, read by the kernel through its device alias
+        unsigned long long* scalar_out;
+        double* scalar_q_dev;     // device aliases of the two pinned buffers
+        unsigned long long* scalar_out_dev;
+        hipStream_t scalar_stream;
+        // the per-robot broadphase is compiled / looked up on the first large validity call (bf32_mu guards the two fields below)
+        std::mutex bf32_mu;
+        int bf32_state = 0;            // 0 not tried, 1 bf32_fn is loaded, -1 unavailable (hipRTC missing, compile failed, NBK_NO_JIT)
+        hipFunction_t bf32_fn = nullptr;
+        std::atomic<int> last_broad{0};   // broadphase of the last validity call: 0 none yet, 1 generic k_broad_f32, 2 specialised, 3 another one
+        std::atomic<long long> last_tiling[3] = {{0}, {0}, {0}};   // the last two-kernel launch: tiles, configurations per tile, 1 = odd tiles on the second stream
+        std::atomic<unsigned long long> world_epoch{0};   // bumped by every update: StreamWs tables prepared before it are stale
+        std::atomic<bool> world_captured{false};  // an update has been captured into a graph: replays move the world behind the host's back,
+                                                  // so no stream of this descriptor reuses its tables any more
+        std::mutex world_mu;                      // updates of one descriptor serialise on the host
+        hipEvent_t world_ev = nullptr;            // recorded after the last direct update: the private stream of the scalar calls waits for it
+        bool world_ev_set = false;
+        double* world_stage = nullptr;            // [W][12] pinned + mapped staging of nbk_model_set_world_poses_host
+        double* world_stage_dev = nullptr;
+    };
+    mutable Host host;
 };
 
 namespace nbk {
@@ -1351,9 +1357,6 @@ NBK_DEV double readlane_f64(double v, int l) {
     return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
-// The global queue is sharded into NSUB sub-queues (block b appends to sub-queue b % NSUB): one counter
-// saturates at ~90 appends/us (MI355X_MICROARCH.md, row "dequeue"), which 15k waves would all hit.
-constexpr int NSUB = 256;
 constexpr int CNT_TICKET = 1;           // word 1 of a counter's line: the next chunk of that sub-queue the narrowphase hands out
 
 // queue routing of the descriptor (flush_items_r, nbk_bf32_common.hpp): vp_cls and the class sub-queue ranges of the model
@@ -3901,6 +3904,18 @@ __global__ void k_world_guard(const int* __restrict__ status, WorldGuard g) {
     if (g.idx != nullptr) for (long long i = t0; i < g.n_idx; i += step) g.idx[i] = -1;
 }
 
+// both spline entries: f(std::integral_constant<int, K>) for K = degree, 1 .. NBK_MAX_SPLINE_DEGREE (checked by the callers)
+template <class F>
+static void with_degree(int degree, F&& f) {
+    switch (degree) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 5>{}); break;
+    }
+}
+
 }  // namespace nbk
 
 using namespace nbk;
@@ -4114,7 +4129,9 @@ static HullSlots pack_model(const nbk_model_desc* d, const ModelTables& t, Blob&
 
     M.blob_bytes = B.bytes.size();
     M.n_pairs = P; M.n_q = d->n_q; M.n_joints = J;
-    for (int c = 0; c < 4; ++c) M.cls_count[c] = t.cls_count[c];
+    M.pm = PlanModel{d->n_q, P, d->n_rshapes, d->n_wshapes, t.slots, {}, {}, t.parked_ok, false};
+    for (int c = 0; c < 4; ++c) { M.pm.cls_count[c] = t.cls_count[c]; M.pm.cls_groups[c] = m.cls_groups[c]; }
+    M.ws = WsLayout(d->n_wshapes);
     M.h_static.assign(t.bq_static.begin(), t.bq_static.begin() + P);
     M.h_m0.resize(P); M.h_m1.resize(P); M.h_cat.resize(P); M.h_cls.resize(P);
     for (int j = 0; j < P; ++j) {
@@ -4159,7 +4176,7 @@ static int32_t model_create(const nbk_model_desc* d, const double* world_radius,
     patch_hulls(d, t, hs, M->blob, B);
     e = hipMemcpy(M->blob, B.bytes.data(), B.bytes.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy(model)");
-    if (world_radius != nullptr) { M->movable = true; M->world_radius = *world_radius; }
+    if (world_radius != nullptr) { M->movable = M->pm.movable = true; M->world_radius = *world_radius; }
     (void)hipGetDevice(&M->device);
     *out = M.release();
     return NBK_OK;
@@ -4193,17 +4210,17 @@ int64_t nbk_jit_compile(const char* src, const char* arch) {
     return rc == NBK_OK ? (int64_t)code.size() : rc;
 }
 
-int32_t nbk_broad_kernel_used(const nbk_model* m) { return m == nullptr ? NBK_ERR_INVALID : m->last_broad.load(std::memory_order_relaxed); }
+int32_t nbk_broad_kernel_used(const nbk_model* m) { return m == nullptr ? NBK_ERR_INVALID : m->host.last_broad.load(std::memory_order_relaxed); }
 
 void nbk_model_destroy(nbk_model* m) {
     if (m == nullptr) return;
     if (m->blob) (void)hipFree(m->blob);
-    for (StreamWs* w : m->wss) delete w;
-    if (m->scalar_q) (void)hipHostFree(m->scalar_q);
-    if (m->scalar_out) (void)hipHostFree(m->scalar_out);
-    if (m->scalar_stream) (void)hipStreamDestroy(m->scalar_stream);
-    if (m->world_ev) (void)hipEventDestroy(m->world_ev);
-    if (m->world_stage) (void)hipHostFree(m->world_stage);
+    for (StreamWs* w : m->host.wss) delete w;
+    if (m->host.scalar_q) (void)hipHostFree(m->host.scalar_q);
+    if (m->host.scalar_out) (void)hipHostFree(m->host.scalar_out);
+    if (m->host.scalar_stream) (void)hipStreamDestroy(m->host.scalar_stream);
+    if (m->host.world_ev) (void)hipEventDestroy(m->host.world_ev);
+    if (m->host.world_stage) (void)hipHostFree(m->host.world_stage);
     delete m;
 }
 
@@ -4253,33 +4270,37 @@ static int make_path(const nbk_model* m, const int32_t* path, int32_t path_len, 
 
 // ---- tuning / diagnostic switches: process-wide, seeded ONCE from the environment when the library is loaded -------
 // (no getenv on any call path).  nbk_debug_set_option changes them at run time (tests, tools); none of them changes a result.
-struct Options {
-    long long two_kernel_min_b;     // NBK_TWO_KERNEL_MIN_B: batches below this size run the fused kernel k_validity.  The broadphase +
-                                    // narrowphase pair measured faster at every size (0.040 vs 0.050 ms for 64 configurations), so: 1
-    long long edge_batch_min_e;     // NBK_EDGE_BATCH_MIN_E: edge batches below this size run one wave per edge (k_edges); default 1
-    long long no_reg_broad;         // NBK_NO_REG_BROAD: the LDS broadphase k_broad instead of the register broadphases
-    long long f64_broad;            // NBK_F64_BROAD: the float64 register broadphase instead of the conservative float32 one
-    long long jac_two_sweep;        // NBK_JAC_TWO_SWEEP: the general Jacobian kernel also for short paths
-    long long closest_brute;        // NBK_CLOSEST_BRUTE: every pair instead of branch-and-bound
-    long long narrow_parts_max;     // NBK_NARROW_PARTS_MAX: cap of the narrowphase workgroups per sub-queue
-    long long pipeline_tiles;       // NBK_PIPELINE_TILES: batches of >= 2 x 2^20 configurations run their tiles alternately on two streams (default 1)
-    long long pipe_tile;            // NBK_PIPE_TILE: configurations per tile of a pipelined batch (default 2^20)
-    long long queue_budget;         // NBK_QUEUE_BUDGET: bytes the item queues of one tile may take (default 1 GiB); tests shrink it to force
-                                    // the overflow path (k_validity_redo)
-    long long fk_lds_q;             // NBK_FK_LDS_Q=1: k_fk stages q in LDS also for n_q <= 8 (A/B switch)
+struct Options : PlanOptions { long long edge_batch_min_e, no_reg_broad, f64_broad, jac_two_sweep, closest_brute, fk_lds_q; };      // PlanOptions: what sizing and tiling read
+// name (the environment variable is NBK_ + the name in upper case), field, default
+static const struct { const char* name; long long Options::*field; long long dflt; } OPTION_TABLE[] = {
+    {"two_kernel_min_b", &Options::two_kernel_min_b, 1},      // batches below this size run the fused kernel k_validity (the pair measured faster at every size: 0.040 vs 0.050 ms for 64 configurations)
+    {"edge_batch_min_e", &Options::edge_batch_min_e, 1},      // edge batches below this size run one wave per edge (k_edges)
+    {"no_reg_broad", &Options::no_reg_broad, 0},              // the LDS broadphase k_broad instead of the register broadphases
+    {"f64_broad", &Options::f64_broad, 0},                    // the float64 register broadphase instead of the conservative float32 one
+    {"jac_two_sweep", &Options::jac_two_sweep, 0},            // the general Jacobian kernel also for short paths
+    {"closest_brute", &Options::closest_brute, 0},            // every pair instead of branch-and-bound
+    {"narrow_parts_max", &Options::narrow_parts_max, 16},     // cap of the narrowphase workgroups per sub-queue
+    {"pipeline_tiles", &Options::pipeline_tiles, 1},          // batches of >= 2 x pipe_tile configurations run their tiles alternately on two streams
+    {"pipe_tile", &Options::pipe_tile, 1ll << 20},            // configurations per tile of a pipelined batch
+    {"queue_budget", &Options::queue_budget, 1ll << 30},      // bytes the item queues of one tile may take; tests shrink it to force the overflow path (k_validity_redo)
+    {"fk_lds_q", &Options::fk_lds_q, 0},                      // 1: k_fk stages q in LDS also for n_q <= 8 (A/B switch)
 };
-static long long env_ll(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
-static Options g_opt = {env_ll("NBK_TWO_KERNEL_MIN_B", 1), env_ll("NBK_EDGE_BATCH_MIN_E", 1), env_ll("NBK_NO_REG_BROAD", 0),
-                        env_ll("NBK_F64_BROAD", 0), env_ll("NBK_JAC_TWO_SWEEP", 0), env_ll("NBK_CLOSEST_BRUTE", 0), env_ll("NBK_NARROW_PARTS_MAX", 16), env_ll("NBK_PIPELINE_TILES", 1), env_ll("NBK_PIPE_TILE", 1ll << 20), env_ll("NBK_QUEUE_BUDGET", 1ll << 30), env_ll("NBK_FK_LDS_Q", 0)};
+static Options options_from_env() {
+    Options o;
+    for (const auto& t : OPTION_TABLE) {
+        std::string env = "NBK_";
+        for (const char* c = t.name; *c; ++c) env += (char)toupper((unsigned char)*c);
+        const char* e = getenv(env.c_str());
+        o.*t.field = e ? atoll(e) : t.dflt;
+    }
+    return o;
+}
+static Options g_opt = options_from_env();
 
 // diagnostic (not part of include/nbk.h): set one of the switches above by name; returns NBK_ERR_INVALID for an unknown name
 extern "C" int32_t nbk_debug_set_option(const char* name, int64_t value) {
     if (name == nullptr) return NBK_ERR_INVALID;
-    struct { const char* n; long long* v; } tab[] = {
-        {"two_kernel_min_b", &g_opt.two_kernel_min_b}, {"edge_batch_min_e", &g_opt.edge_batch_min_e}, {"no_reg_broad", &g_opt.no_reg_broad},
-        {"f64_broad", &g_opt.f64_broad}, {"jac_two_sweep", &g_opt.jac_two_sweep}, {"closest_brute", &g_opt.closest_brute},
-        {"narrow_parts_max", &g_opt.narrow_parts_max}, {"queue_budget", &g_opt.queue_budget}, {"pipeline_tiles", &g_opt.pipeline_tiles}, {"pipe_tile", &g_opt.pipe_tile}, {"fk_lds_q", &g_opt.fk_lds_q}};
-    for (auto& t : tab) if (strcmp(t.n, name) == 0) { *t.v = (long long)value; return NBK_OK; }
+    for (const auto& t : OPTION_TABLE) if (strcmp(t.name, name) == 0) { g_opt.*t.field = (long long)value; return NBK_OK; }
     return NBK_ERR_INVALID;
 }
 
@@ -4439,25 +4460,12 @@ int32_t nbk_ik_batch(const nbk_model* m, const double* pose, const double* q0, i
 }
 
 // ---- validity: fused kernel for small batches, broadphase + compacted narrowphase for large ones -------
-static const size_t WS_MAX_BYTES = size_t(1) << 30;
-static const int64_t TILE_MAX = int64_t(1) << 22;               // configurations per queue tile at most (65 536 blocks)
-static const size_t WS_FLAGS = (size_t)(TILE_MAX / WAVE);       // one overflow mark per block of a tile
-static const size_t WS_COUNTER_SET = NSUB * CNT_STRIDE * 8;    // NSUB counters, one cache line each
-static const size_t WS_COUNTERS = 2 * WS_COUNTER_SET;          // two sets (see StreamWs::epoch)
-static inline size_t ws_tables(const nbk_model* m) {           // counters | per-call float32 broadphase tables
-    return (WS_COUNTERS + 4 * (5 * 256 + 128 + 6 * (size_t)m->d.n_wshapes * 16 + 32 + (size_t)m->d.n_wshapes + 16 + 96 * (size_t)m->d.n_wshapes + 16) + 255) & ~size_t(255);
-}
-static inline size_t ws_header(const nbk_model* m) { return ws_tables(m) + WS_FLAGS; }      // ... | overflow marks | items follow
-
+// (the workspace layout, the tiling of a call and the reuse of its tables are host arithmetic: nbk_plan.hpp)
 static inline size_t broad_lds(const nbk_model* m) {
     const size_t qrows = ((size_t)WAVE * m->d.n_q * 8 >= (size_t)BQ_CAP * 4) ? (size_t)m->d.n_q : ((size_t)BQ_CAP * 4 + WAVE * 8 - 1) / (WAVE * 8);
     return sizeof(double) * (WAVE * (qrows + 12 * (size_t)m->d.frame_slots + 3 * (size_t)m->d.n_rshapes) + 4 * (size_t)m->d.n_pairs + 18 * (size_t)m->d.n_wshapes);
 }
 
-// capacity (items) of one sub-queue for a tile of nblk 64-configuration blocks: the blocks that feed it times 64 times
-// the pairs of its class, maximised over the classes (all sub-queues get the same stride)
-struct PairCounts { int n[4]; };      // pairs per kind class that can produce queue items
-static inline PairCounts all_pairs(const nbk_model* m) { PairCounts c; for (int i = 0; i < 4; ++i) c.n[i] = m->cls_count[i]; return c; }
 // the pairs the static reach test leaves at this threshold (the very test k_prepare_f32 applies: a pair it drops can never pass
 // the bounding-sphere test of any broadphase, so it can never own a queue item)
 static inline PairCounts reachable_pairs(const nbk_model* m, double thr) {
@@ -4476,44 +4484,7 @@ static inline PairCounts reachable_pairs(const nbk_model* m, double thr) {
 }
 // what the library's own scratch is sized for: a movable descriptor's poses are the device's business (the host's h_static is
 // creation's), so it sizes for every pair; the budget + k_validity_redo stay the safety net
-static inline PairCounts sized_pairs(const nbk_model* m, double thr) { return m->movable ? all_pairs(m) : reachable_pairs(m, thr); }
-static inline unsigned long long sub_queue_cap(const nbk_model* m, const PairCounts& pc, unsigned long long nblk) {
-    unsigned long long cap = WAVE;
-    for (int c = 0; c < 4; ++c) {
-        if (pc.n[c] == 0) continue;
-        const unsigned long long g = (unsigned long long)m->d.cls_groups[c];
-        const unsigned long long v = ((nblk + g - 1) / g) * WAVE * (unsigned long long)pc.n[c];
-        if (v > cap) cap = v;
-    }
-    return cap;
-}
-
-// Queue sizing.  Robots that fit the LDS-parked layout (the queue-less kernel can re-decide a block): one tile of up to TILE_MAX
-// configurations, every sub-queue as large as the worst case needs but at most its share of WS_MAX_BYTES -- blocks whose items do
-// not fit are re-decided by k_validity_redo.  Larger robots: tiles small enough for the worst case (every pair of every
-// configuration), as nothing can catch an overflow for them.
-static inline int64_t tile_configs(const nbk_model* m, const PairCounts& pc, int64_t B) {
-    const int64_t Bp = ((B + WAVE - 1) / WAVE) * WAVE;
-    if (m->parked_ok) return Bp < TILE_MAX ? Bp : TILE_MAX;
-    double per_cfg = 1.0;
-    for (int c = 0; c < 4; ++c) if (pc.n[c] > 0) { const double v = (double)NSUB * pc.n[c] / m->d.cls_groups[c]; if (v > per_cfg) per_cfg = v; }
-    const int64_t P = (int64_t)per_cfg + 1;
-    const size_t ws_max = size_t(8) << 30;
-    int64_t t = (int64_t)((ws_max - ws_header(m)) / (8 * (size_t)P)) - (int64_t)NSUB * WAVE;
-    t = (t / WAVE) * WAVE;
-    if (t < 2 * (int64_t)NSUB * WAVE) t = 2 * (int64_t)NSUB * WAVE;
-    if (t > TILE_MAX) t = TILE_MAX;
-    return Bp < t ? Bp : t;
-}
-static inline unsigned long long tile_queue_cap(const nbk_model* m, const PairCounts& pc, unsigned long long nblk) {
-    const unsigned long long worst = sub_queue_cap(m, pc, nblk);
-    if (!m->parked_ok) return worst;
-    size_t bytes = g_opt.queue_budget > 0 ? (size_t)g_opt.queue_budget : WS_MAX_BYTES;
-    if (bytes > 2 * ws_header(m)) bytes -= ws_header(m);           // the whole workspace, tables included, stays within the budget
-    unsigned long long budget = (unsigned long long)(bytes / (8 * (size_t)NSUB));
-    if (budget < (unsigned long long)WAVE) budget = WAVE;
-    return worst < budget ? worst : budget;
-}
+static inline PairCounts sized_pairs(const nbk_model* m, double thr) { return m->movable ? all_pairs(m->pm) : reachable_pairs(m, thr); }
 
 static inline size_t broad_reg_lds(const nbk_model* m, int S) {
     const size_t qrows = ((size_t)WAVE * m->d.n_q * 8 >= (size_t)BQ_CAP * 4) ? (size_t)m->d.n_q : ((size_t)BQ_CAP * 4 + WAVE * 8 - 1) / (WAVE * 8);
@@ -4522,13 +4493,13 @@ static inline size_t broad_reg_lds(const nbk_model* m, int S) {
 }
 
 // the scratch set of (descriptor, stream); created on the stream's first call.  nullptr: too many streams (use the _ws variant)
-static StreamWs* stream_ws(nbk_model* mm, hipStream_t st) {
-    std::lock_guard<std::mutex> lock(mm->mu);
-    for (StreamWs* w : mm->wss) if (w->stream == st) return w;
-    if (mm->wss.size() >= 64) return nullptr;
+static StreamWs* stream_ws(const nbk_model* m, hipStream_t st) {
+    std::lock_guard<std::mutex> lock(m->host.mu);
+    for (StreamWs* w : m->host.wss) if (w->stream == st) return w;
+    if (m->host.wss.size() >= 64) return nullptr;
     StreamWs* w = new StreamWs();
     w->stream = st;
-    mm->wss.push_back(w);
+    m->host.wss.push_back(w);
     return w;
 }
 
@@ -4546,30 +4517,11 @@ static int32_t grow_scratch(hipStream_t st, void*& buf, size_t& have, size_t nee
 // grow the validity workspace of a scratch set to `need` bytes: a new buffer has no overflow marks and no tables yet
 static int32_t ensure_validity_ws(const nbk_model* m, StreamWs* w, size_t need, hipStream_t st, const char* what) {
     if (w->ws_bytes >= need) return NBK_OK;
-    w->ready = false;
+    w->tables.invalidate();
     const int32_t rc = grow_scratch(st, w->ws, w->ws_bytes, need, what);
     if (rc != NBK_OK) return rc;
-    NBK_HIP(hipMemsetAsync(static_cast<char*>(w->ws) + ws_tables(m), 0, WS_FLAGS, st));
+    NBK_HIP(hipMemsetAsync(static_cast<char*>(w->ws) + m->ws.flags, 0, WsLayout::FLAGS, st));
     return NBK_OK;
-}
-
-// broadphase + narrowphase over B configurations (plain q rows, or the samples described by `es`), tiled so that the worst-case
-// queue fits the workspace.  `iw`: the workspace is this stream's own set and keeps state between calls (tables, counter epoch);
-// nullptr: caller-owned workspace, or a call being captured into a graph -- self-contained: every call prepares its tables
-// and clears its counters itself.
-// tile size of pipelined batches (NBK_PIPE_TILE): whole 64-configuration blocks (tiles on the two streams must not share a mask word
-// or a block), at least one block per sub-queue; anything else is rounded / clamped here, so no value of the switch changes a result
-static inline int64_t pipe_tile_configs() {
-    int64_t t = g_opt.pipe_tile > 0 ? (int64_t)g_opt.pipe_tile : (int64_t(1) << 20);
-    t &= ~int64_t(WAVE - 1);
-    const int64_t lo = (int64_t)NSUB * WAVE;
-    return t < lo ? lo : t;
-}
-#define PIPE_TILE pipe_tile_configs()
-static inline bool pipelined(const nbk_model* m, int64_t B) { return g_opt.pipeline_tiles != 0 && m->parked_ok && B >= 2 * PIPE_TILE; }
-static inline int64_t call_tile(const nbk_model* m, const PairCounts& pc, int64_t B, bool pipe) {
-    const int64_t t = tile_configs(m, pc, B);
-    return pipe && t > PIPE_TILE ? PIPE_TILE : t;
 }
 
 // which GJK walks can a call at this threshold need?  tc = (thr + mA) + mB per pair that can reach GJK: all zero and no hull -> the
@@ -4588,170 +4540,183 @@ static int narrow_variant(const nbk_model* m, double threshold) {
     if (!any_zero && !any_positive) return 2;
     return 3;
 }
+static constexpr decltype(&k_narrow) NARROW_BUILD[4] = {k_narrow_bool, k_narrow_pos, k_narrow_pred, k_narrow};
 // diagnostic (not part of include/nbk.h): the narrowphase build nbk_validity_batch picks for this descriptor at this threshold
 extern "C" int32_t nbk_debug_narrow_variant(const nbk_model* m, double threshold) { return m == nullptr ? NBK_ERR_INVALID : narrow_variant(m, threshold); }
 // diagnostic (not part of include/nbk.h): how the descriptor's last broadphase + narrowphase launch (plain rows or edge samples) was
 // tiled -- out[0] tiles, out[1] configurations per tile, out[2] 1 when odd tiles ran on the second stream; zeros before the first
 extern "C" int32_t nbk_debug_last_tiling(const nbk_model* m, int64_t out[3]) {
     if (m == nullptr || out == nullptr) return NBK_ERR_INVALID;
-    for (int i = 0; i < 3; ++i) out[i] = (int64_t)m->last_tiling[i].load(std::memory_order_relaxed);
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)m->host.last_tiling[i].load(std::memory_order_relaxed);
     return NBK_OK;
 }
 
-// `pipe` (the library's own scratch only): odd tiles run on iw0->aux_stream with the scratch set iw0->aux.  `pipe_sized`: the tiles
-// of a pipelined call, all on st0 (a captured call on a stream whose scratch a pipelined call sized)
-static int32_t launch_two_kernel_impl(const nbk_model* m, const PairCounts& pc, EdgeSrc es, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
-                                      uint8_t* mask_bytes, void* workspace0, hipStream_t st0, StreamWs* iw0, bool pipe, bool pipe_sized) {
-    const int64_t tile = call_tile(m, pc, B, pipe || pipe_sized);
-    if (pipe) {
-        NBK_HIP(hipEventRecord(iw0->ev_fork, st0));                          // the odd tiles' inputs are whatever the caller's stream has produced
-        NBK_HIP(hipStreamWaitEvent(iw0->aux_stream, iw0->ev_fork, 0));
-    }
-    // which GJK walks can this call need?  tc = (thr + mA) + mB per pair: all zero and no hull -> boolean walk only, none negative ->
-    // the (inflated) walk + the distance iteration for hulls and undecided walks, all negative -> distance predicate only, else
-    // the build with everything
-    const int narrow_build = narrow_variant(m, threshold);
+// one broadphase + narrowphase call over B configurations: plain q rows, or the samples described by `es`
+struct ValidityCall { const nbk_model* m; PairCounts pc; EdgeSrc es; const double* q; int64_t B; double threshold; uint64_t* mask_bits; uint8_t* mask_bytes; hipStream_t st; };
+// ... and the workspace it runs on.  `own`: this stream's own set, which keeps state between calls (TableCache); nullptr: a caller's workspace
+// or a call being captured -- self-contained, every tile prepares its tables and clears its counters.  TwoStreams needs `own`.
+struct WsBinding { void* ws; StreamWs* own; TileMode mode; };
+static const EdgeSrc NO_EDGES = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+
+enum class Broad { Spec, F32, Reg, Lds };      // the kernel compiled for this robot | k_broad_f32<S, WH> | k_broad_reg<S> | k_broad
+// what the tiles of one call share: its kernels, and the descriptor's world state the cached tables are held against
+struct CallSetup { Broad broad; hipFunction_t spec_fn; int narrow; unsigned long long world_epoch; bool world_captured; };
+static CallSetup call_setup(const ValidityCall& c) {
+    const nbk_model* m = c.m;
     const int S = m->d.n_rshapes;
-    // tables prepared before the last update of a movable descriptor's world poses are stale
-    const unsigned long long world_epoch = m->world_epoch.load(std::memory_order_acquire);
-    const bool world_captured = m->world_captured.load(std::memory_order_acquire);
-    const bool use_reg = S <= 16 && (!g_opt.no_reg_broad || !m->lds_broad_ok);
-    const bool f32 = !g_opt.f64_broad || broad_reg_lds(m, broad_bucket(S)) > LDS_MAX;   // the float64 form keeps its tables in LDS
+    nbk_model::Host& h = m->host;
+    CallSetup x = {Broad::Lds, nullptr, narrow_variant(m, c.threshold), h.world_epoch.load(std::memory_order_acquire), h.world_captured.load(std::memory_order_acquire)};
+    if (S <= 16 && (!g_opt.no_reg_broad || !m->lds_broad_ok))      // the float64 form keeps its tables in LDS
+        x.broad = !g_opt.f64_broad || broad_reg_lds(m, broad_bucket(S)) > LDS_MAX ? Broad::F32 : Broad::Reg;
     // the broadphase compiled for this robot (plain q rows, large calls; compiled on the first such call, never inside a capture)
-    hipFunction_t spec_fn = nullptr;
-    if (use_reg && f32 && m->d.f_chain && es.map == nullptr && es.total == nullptr && !m->bf32_spec.empty() && B >= SPEC_MIN_BATCH) {
-        nbk_model* mm = const_cast<nbk_model*>(m);
-        std::lock_guard<std::mutex> lock(mm->bf32_mu);
-        if (mm->bf32_state == 0) {
+    if (x.broad == Broad::F32 && m->d.f_chain && c.es.map == nullptr && c.es.total == nullptr && !m->bf32_spec.empty() && c.B >= SPEC_MIN_BATCH) {
+        std::lock_guard<std::mutex> lock(h.bf32_mu);
+        if (h.bf32_state == 0) {
             const char* nj = getenv("NBK_NO_JIT");
-            if (nj != nullptr && *nj && strcmp(nj, "0") != 0) mm->bf32_state = -1;
-            else if (!stream_capturing(st0)) { mm->bf32_fn = bf32_function(mm->bf32_spec); mm->bf32_state = mm->bf32_fn != nullptr ? 1 : -1; }
+            if (nj != nullptr && *nj && strcmp(nj, "0") != 0) h.bf32_state = -1;
+            else if (!stream_capturing(c.st)) { h.bf32_fn = bf32_function(m->bf32_spec); h.bf32_state = h.bf32_fn != nullptr ? 1 : -1; }
         }
-        if (mm->bf32_state == 1) spec_fn = mm->bf32_fn;
+        if (h.bf32_state == 1) { x.spec_fn = h.bf32_fn; x.broad = Broad::Spec; }
     }
-    const_cast<nbk_model*>(m)->last_broad.store(spec_fn != nullptr ? 2 : (use_reg && f32 ? 1 : 3), std::memory_order_relaxed);
-    {
-        std::atomic<long long>* lt = const_cast<nbk_model*>(m)->last_tiling;
-        lt[0].store((long long)((B + tile - 1) / tile), std::memory_order_relaxed);
-        lt[1].store((long long)tile, std::memory_order_relaxed);
-        lt[2].store(pipe ? 1 : 0, std::memory_order_relaxed);
+    return x;
+}
+
+// one tile on stream `st`: [k_prepare_f32 | k_zero_counters,] broadphase, narrowphase [, k_validity_redo]
+static int32_t launch_tile(const ValidityCall& c, const CallSetup& x, const Tile& t, const WsBinding& b, hipStream_t st) {
+    const nbk_model* m = c.m;
+    using ull = unsigned long long;
+    char* const ws = static_cast<char*>(b.ws);      // the one place that turns the offsets of WsLayout into pointers
+    const struct { ull* counters; float* ftab; ull* flag_words; ull* items; } p = {reinterpret_cast<ull*>(ws), reinterpret_cast<float*>(ws + m->ws.tables),
+                                                                                 reinterpret_cast<ull*>(ws + m->ws.flags), reinterpret_cast<ull*>(ws + m->ws.items)};
+    EdgeSrc es = c.es;
+    if (es.map != nullptr) { es.map += t.b0; es.b0 = t.b0; }
+    es.ovf = m->parked_ok ? reinterpret_cast<unsigned char*>(p.flag_words) : nullptr;
+    const int n_flag_words = m->parked_ok ? (int)((t.nblk + 7) / 8) : 0;
+    // tiles start on a multiple of 64 configurations, so mask words never straddle tiles
+    const double* qt = c.q ? c.q + t.b0 * m->n_q : nullptr;
+    uint64_t* mb = c.mask_bits ? c.mask_bits + t.b0 / 64 : nullptr;
+    uint8_t* my = c.mask_bytes ? c.mask_bytes + t.b0 : nullptr;
+    const int bucket = broad_bucket(m->d.n_rshapes);
+    // LDS of the float32 kernel: q slab (later the item queue) + saved frames
+    const size_t qrows_f = (size_t)f32_qrows(m->d.n_q, bucket);
+    const size_t lds_f = sizeof(double) * WAVE * qrows_f + sizeof(float) * WAVE * 12 * (size_t)m->d.frame_slots + 16 + sizeof(float) * WAVE * NBK_ZSLOTS;   // (+ the z coordinates of the slots k_broad_f32 keeps in LDS)
+    unsigned long long *count = p.counters, *count_next = nullptr;
+    if (x.broad == Broad::Spec || x.broad == Broad::F32) {
+        // tables in place and this call's counter set cleared by the previous call's narrowphase: no launch
+        const TableCache::Use u = b.own != nullptr ? b.own->tables.begin(c.threshold, x.world_epoch, x.world_captured) : TableCache::Use{true, 0, -1};
+        if (u.prepare) hipLaunchKernelGGL(k_prepare_f32, dim3(1), dim3(NSUB), 0, st, m->d, c.threshold, p.counters, b.own != nullptr ? 2 : 1, p.ftab, p.flag_words, n_flag_words);   // clears the counters too
+        count = p.counters + (size_t)u.set * NSUB * CNT_STRIDE;
+        if (u.clear >= 0) count_next = p.counters + (size_t)u.clear * NSUB * CNT_STRIDE;
+    } else {
+        if (b.own != nullptr) b.own->tables.invalidate();
+        hipLaunchKernelGGL(k_zero_counters, dim3(1), dim3(NSUB), 0, st, count, p.flag_words, n_flag_words);
     }
-    int tile_no = 0;
-    for (int64_t b0 = 0; b0 < B; b0 += tile, ++tile_no) {
-        const bool odd = pipe && (tile_no & 1);
-        StreamWs* iw = odd ? iw0->aux : iw0;
-        hipStream_t st = odd ? iw0->aux_stream : st0;
-        void* workspace = odd ? iw0->aux->ws : workspace0;
-        const bool internal = iw != nullptr;
-        unsigned long long* count_set0 = static_cast<unsigned long long*>(workspace);
-        unsigned long long* count = count_set0;
-        unsigned long long* items = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + ws_header(m));
-        const int64_t nb = (B - b0) < tile ? (B - b0) : tile;
-        const unsigned nblk = blocks_for(nb);
-        // a sub-queue takes one kind class of the blocks of one group (every 64th block): worst case all pairs of that class
-        const unsigned long long cap_sub = tile_queue_cap(m, pc, nblk);
-        EdgeSrc es_tile = es;
-        if (es.map != nullptr) { es_tile.map = es.map + b0; es_tile.b0 = b0; }
-        es_tile.ovf = m->parked_ok ? reinterpret_cast<unsigned char*>(workspace) + ws_tables(m) : nullptr;
-        unsigned long long* flag_words = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + ws_tables(m));
-        const int n_flag_words = m->parked_ok ? (int)((nblk + 7) / 8) : 0;
-        // tiles start on a multiple of 64 configurations, so mask words never straddle tiles
-        const double* qt = q ? q + b0 * m->n_q : nullptr;
-        uint64_t* mb = mask_bits ? mask_bits + b0 / 64 : nullptr;
-        uint8_t* my = mask_bytes ? mask_bytes + b0 : nullptr;
-        float* ftab = reinterpret_cast<float*>(static_cast<char*>(workspace) + WS_COUNTERS);
-        // LDS of the float32 kernel: q slab (later the item queue) + saved frames
-        const size_t qrows_f = (size_t)f32_qrows(m->d.n_q, broad_bucket(S));
-        const size_t lds_f = sizeof(double) * WAVE * qrows_f + sizeof(float) * WAVE * 12 * (size_t)m->d.frame_slots + 16 + sizeof(float) * WAVE * NBK_ZSLOTS;   // (+ the z coordinates of the slots k_broad_f32 keeps in LDS)
-        unsigned long long* count_next = nullptr;
-        if (use_reg && f32) {
-            if (internal && iw->ready && !iw->captured && iw->thr == threshold && iw->world_epoch == world_epoch && !world_captured) {
-                // tables are in place and the previous call's narrowphase cleared this call's counter set: no launch
-                count = count_set0 + (size_t)(iw->epoch & 1u) * NSUB * CNT_STRIDE;
-                count_next = count_set0 + (size_t)((iw->epoch + 1u) & 1u) * NSUB * CNT_STRIDE;
-            } else {
-                count = count_set0;
-                hipLaunchKernelGGL(k_prepare_f32, dim3(1), dim3(NSUB), 0, st, m->d, threshold, count_set0, internal ? 2 : 1, ftab, flag_words, n_flag_words);   // clears the counters too
-                if (internal) { iw->ready = true; iw->thr = threshold; iw->world_epoch = world_epoch; iw->epoch = 0; count_next = count_set0 + (size_t)NSUB * CNT_STRIDE; }
-            }
-            if (internal) iw->epoch += 1u;
-        } else {
-            count = count_set0;
-            if (internal) iw->ready = false;
-            hipLaunchKernelGGL(k_zero_counters, dim3(1), dim3(NSUB), 0, st, count, flag_words, n_flag_words);
-        }
-#define NBK_LAUNCH_BF32(S_, WH_) hipLaunchKernelGGL((k_broad_f32<S_, WH_>), dim3(nblk), dim3(WAVE), lds_f, st, m->d, es_tile, qt, nb, threshold, mb, my, count, items, cap_sub, ftab)
-        if (spec_fn != nullptr) {
-            // same arguments as k_broad_f32, flattened; its LDS is the q slab / item queue alone (no saved frames, no parked z)
-            const double* a_q = qt; long long a_b = nb; const float* a_ftb = m->d.f_tab; const float* a_tab = ftab;
-            unsigned long long* a_mb = reinterpret_cast<unsigned long long*>(mb); unsigned char* a_my = my;
-            unsigned long long* a_cnt = count; unsigned long long* a_items = items; unsigned long long a_cap = cap_sub;
-            unsigned char* a_ovf = es_tile.ovf; const int* a_cls = m->d.vp_cls;
-            void* args[] = {&a_q, &a_b, &a_ftb, &a_tab, &a_mb, &a_my, &a_cnt, &a_items, &a_cap, &a_ovf, &a_cls};
-            NBK_HIP(hipModuleLaunchKernel(spec_fn, nblk, 1, 1, WAVE, 1, 1, (unsigned)(sizeof(double) * WAVE * qrows_f), st, args, nullptr));
-        }
-        else if (use_reg && f32 && S <= 8) { if (m->world_hulls) NBK_LAUNCH_BF32(8, true); else NBK_LAUNCH_BF32(8, false); }
-        else if (use_reg && f32 && S <= 12) { if (m->world_hulls) NBK_LAUNCH_BF32(12, true); else NBK_LAUNCH_BF32(12, false); }
-        else if (use_reg && f32) { if (m->world_hulls) NBK_LAUNCH_BF32(16, true); else NBK_LAUNCH_BF32(16, false); }
+#define NBK_LAUNCH_BF32(S_, WH_) hipLaunchKernelGGL((k_broad_f32<S_, WH_>), dim3(t.nblk), dim3(WAVE), lds_f, st, m->d, es, qt, t.nb, c.threshold, mb, my, count, p.items, t.cap_sub, p.ftab)
+#define NBK_LAUNCH_REG(S_) hipLaunchKernelGGL(k_broad_reg<S_>, dim3(t.nblk), dim3(WAVE), broad_reg_lds(m, S_), st, m->d, es, qt, t.nb, c.threshold, mb, my, count, p.items, t.cap_sub)
+    if (x.broad == Broad::Spec) {
+        // same arguments as k_broad_f32, flattened; its LDS is the q slab / item queue alone (no saved frames, no parked z)
+        const double* a_q = qt; long long a_b = t.nb; const float* a_ftb = m->d.f_tab; const float* a_tab = p.ftab;
+        unsigned long long* a_mb = reinterpret_cast<unsigned long long*>(mb); unsigned char* a_my = my;
+        unsigned long long* a_cnt = count; unsigned long long* a_items = p.items; unsigned long long a_cap = t.cap_sub;
+        unsigned char* a_ovf = es.ovf; const int* a_cls = m->d.vp_cls;
+        void* args[] = {&a_q, &a_b, &a_ftb, &a_tab, &a_mb, &a_my, &a_cnt, &a_items, &a_cap, &a_ovf, &a_cls};
+        NBK_HIP(hipModuleLaunchKernel(x.spec_fn, t.nblk, 1, 1, WAVE, 1, 1, (unsigned)(sizeof(double) * WAVE * qrows_f), st, args, nullptr));
+    }
+    else if (x.broad == Broad::F32 && bucket == 8) { if (m->world_hulls) NBK_LAUNCH_BF32(8, true); else NBK_LAUNCH_BF32(8, false); }
+    else if (x.broad == Broad::F32 && bucket == 12) { if (m->world_hulls) NBK_LAUNCH_BF32(12, true); else NBK_LAUNCH_BF32(12, false); }
+    else if (x.broad == Broad::F32) { if (m->world_hulls) NBK_LAUNCH_BF32(16, true); else NBK_LAUNCH_BF32(16, false); }
+    else if (x.broad == Broad::Reg) { if (bucket == 8) NBK_LAUNCH_REG(8); else if (bucket == 12) NBK_LAUNCH_REG(12); else NBK_LAUNCH_REG(16); }
+    else hipLaunchKernelGGL(k_broad, dim3(t.nblk), dim3(WAVE), broad_lds(m), st, m->d, es, qt, t.nb, c.threshold, mb, my, count, p.items, t.cap_sub);
 #undef NBK_LAUNCH_BF32
-        else if (use_reg && S <= 8)
-            hipLaunchKernelGGL(k_broad_reg<8>, dim3(nblk), dim3(WAVE), broad_reg_lds(m, 8), st, m->d, es_tile, qt, nb, threshold, mb, my, count, items, cap_sub);
-        else if (use_reg && S <= 12)
-            hipLaunchKernelGGL(k_broad_reg<12>, dim3(nblk), dim3(WAVE), broad_reg_lds(m, 12), st, m->d, es_tile, qt, nb, threshold, mb, my, count, items, cap_sub);
-        else if (use_reg)
-            hipLaunchKernelGGL(k_broad_reg<16>, dim3(nblk), dim3(WAVE), broad_reg_lds(m, 16), st, m->d, es_tile, qt, nb, threshold, mb, my, count, items, cap_sub);
-        else
-            hipLaunchKernelGGL(k_broad, dim3(nblk), dim3(WAVE), broad_lds(m), st, m->d, es_tile, qt, nb, threshold, mb, my, count, items, cap_sub);
+#undef NBK_LAUNCH_REG
+    NBK_HIP(hipGetLastError());
+    const size_t nlds = sizeof(double) * NARROW_T * (size_t)m->n_q + narrow_hull_lds(m->d.hull_blob_n);
+    hipLaunchKernelGGL(NARROW_BUILD[x.narrow], dim3(NSUB * t.parts), dim3(NARROW_T), nlds, st, m->d, es, qt, c.threshold, p.items, count, t.cap_sub, mb, my, count_next);
+    NBK_HIP(hipGetLastError());
+    // blocks whose items overflowed their sub-queue (possible only when the budget, not the worst case, sized the queue)
+    if (t.redo) {
+        hipLaunchKernelGGL(k_validity_redo, dim3(t.nblk), dim3(WAVE), collide_lds(m), st, m->d, es, qt, t.nb, c.threshold, mb, my);
         NBK_HIP(hipGetLastError());
-        const size_t nlds = sizeof(double) * NARROW_T * (size_t)m->n_q + narrow_hull_lds(m->d.hull_blob_n);
-        // workgroups per sub-queue: one 64-item chunk each at a few survivors per configuration; more chunks are strided over
-        unsigned parts = 4u * nblk / NSUB;
-        { const unsigned pmax = g_opt.narrow_parts_max > 0 ? (unsigned)g_opt.narrow_parts_max : 16u; parts = parts < 4u ? 4u : parts; parts = parts > pmax ? pmax : parts; }
-        if (nblk <= 4u) parts = 1u;                      // a handful of configurations (the scalar calls): 256 workgroups are plenty
-        if (narrow_build == 0)
-            hipLaunchKernelGGL(k_narrow_bool, dim3(NSUB * parts), dim3(NARROW_T), nlds, st, m->d, es_tile, qt, threshold, items, count, cap_sub, mb, my, count_next);
-        else if (narrow_build == 1)
-            hipLaunchKernelGGL(k_narrow_pos, dim3(NSUB * parts), dim3(NARROW_T), nlds, st, m->d, es_tile, qt, threshold, items, count, cap_sub, mb, my, count_next);
-        else if (narrow_build == 2)
-            hipLaunchKernelGGL(k_narrow_pred, dim3(NSUB * parts), dim3(NARROW_T), nlds, st, m->d, es_tile, qt, threshold, items, count, cap_sub, mb, my, count_next);
-        else
-            hipLaunchKernelGGL(k_narrow, dim3(NSUB * parts), dim3(NARROW_T), nlds, st, m->d, es_tile, qt, threshold, items, count, cap_sub, mb, my, count_next);
-        NBK_HIP(hipGetLastError());
-        // blocks whose items overflowed their sub-queue (possible only when the budget, not the worst case, sized the queue)
-        if (m->parked_ok && cap_sub < sub_queue_cap(m, pc, nblk)) {
-            hipLaunchKernelGGL(k_validity_redo, dim3(nblk), dim3(WAVE), collide_lds(m), st, m->d, es_tile, qt, nb, threshold, mb, my);
-            NBK_HIP(hipGetLastError());
-        }
-    }
-    if (pipe) {
-        NBK_HIP(hipEventRecord(iw0->ev_join, iw0->aux_stream));              // the caller's stream continues when the odd tiles are done too
-        NBK_HIP(hipStreamWaitEvent(st0, iw0->ev_join, 0));
     }
     return NBK_OK;
 }
 
-static int32_t launch_two_kernel(const nbk_model* m, const PairCounts& pc, EdgeSrc es, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
-                                 uint8_t* mask_bytes, void* workspace, hipStream_t st, StreamWs* iw = nullptr, bool pipe = false, bool pipe_sized = false) {
-    const int32_t rc = launch_two_kernel_impl(m, pc, es, q, B, threshold, mask_bits, mask_bytes, workspace, st, iw, pipe, pipe_sized);
-    if (rc != NBK_OK && iw != nullptr) { iw->ready = false; if (iw->aux) iw->aux->ready = false; }      // whatever state the queues are in: start over
+// the tiles of the call's TilePlan, each sized so that its queue fits the workspace
+static int32_t launch_tiles(const ValidityCall& c, const WsBinding& b) {
+    nbk_model::Host& h = c.m->host;
+    const TilePlan plan(c.m->pm, g_opt, c.pc, c.B, b.mode);
+    const bool two = b.mode == TileMode::TwoStreams;
+    if (two) {
+        NBK_HIP(hipEventRecord(b.own->ev_fork, c.st));                         // the odd tiles' inputs are whatever the caller's stream has produced
+        NBK_HIP(hipStreamWaitEvent(b.own->aux_stream, b.own->ev_fork, 0));
+    }
+    const CallSetup x = call_setup(c);
+    h.last_broad.store(x.broad == Broad::Spec ? 2 : (x.broad == Broad::F32 ? 1 : 3), std::memory_order_relaxed);
+    const long long tiling[3] = {(long long)plan.tiles, (long long)plan.tile, two ? 1 : 0};
+    for (int i = 0; i < 3; ++i) h.last_tiling[i].store(tiling[i], std::memory_order_relaxed);
+    for (int64_t i = 0; i < plan.tiles; ++i) {
+        const bool odd = two && (i & 1);
+        const int32_t rc = odd ? launch_tile(c, x, plan.at(i), WsBinding{b.own->aux->ws, b.own->aux, b.mode}, b.own->aux_stream) : launch_tile(c, x, plan.at(i), b, c.st);
+        if (rc != NBK_OK) return rc;
+    }
+    if (two) {
+        NBK_HIP(hipEventRecord(b.own->ev_join, b.own->aux_stream));            // the caller's stream continues when the odd tiles are done too
+        NBK_HIP(hipStreamWaitEvent(c.st, b.own->ev_join, 0));
+    }
+    return NBK_OK;
+}
+static int32_t launch_validity(const ValidityCall& c, const WsBinding& b) {
+    const int32_t rc = launch_tiles(c, b);
+    if (rc != NBK_OK && b.own != nullptr) { b.own->tables.invalidate(); if (b.own->aux) b.own->aux->tables.invalidate(); }      // whatever state the queues are in: start over
     return rc;
 }
 
-static int64_t two_kernel_workspace_bytes(const nbk_model* m, const PairCounts& pc, int64_t B, bool pipe = false) {
-    const int64_t nblk = (call_tile(m, pc, B, pipe) + WAVE - 1) / WAVE;
-    return (int64_t)ws_header(m) + 8 * (int64_t)NSUB * (int64_t)tile_queue_cap(m, pc, (unsigned long long)nblk);
-}
-
 // the second stream, its events and its scratch set of a pipelined call (created on first use; never while capturing)
-static int32_t pipe_setup(nbk_model* mm, const nbk_model* m, const PairCounts& pc, StreamWs* w, int64_t B) {
+static int32_t pipe_setup(const nbk_model* m, const PairCounts& pc, StreamWs* w, int64_t B) {
     if (w->aux_stream == nullptr) {
         NBK_HIP(hipStreamCreateWithFlags(&w->aux_stream, hipStreamNonBlocking));
         NBK_HIP(hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming));
         NBK_HIP(hipEventCreateWithFlags(&w->ev_join, hipEventDisableTiming));
-        w->aux = stream_ws(mm, w->aux_stream);
+        w->aux = stream_ws(m, w->aux_stream);
         if (w->aux == nullptr) return NBK_ERR_ALLOC;
     }
-    return ensure_validity_ws(m, w->aux, (size_t)two_kernel_workspace_bytes(m, pc, B, true), w->aux_stream, "hipMalloc(workspace, second stream)");
+    return ensure_validity_ws(m, w->aux, TilePlan(m->pm, g_opt, pc, B, TileMode::TwoStreams).bytes, w->aux_stream, "hipMalloc(workspace, second stream)");
+}
+
+// What a call on the library's own scratch does before it launches.  own_scratch: the scratch set of (descriptor, stream), locked for the
+// length of the call, and whether the stream is being captured (`advice` ends the error text of a descriptor that serves 64 streams).
+struct OwnScratch { hipStream_t st = nullptr; StreamWs* w = nullptr; std::unique_lock<std::mutex> lock; bool capturing = false; };
+static int32_t own_scratch(const nbk_model* m, hipStream_t st, const char* advice, OwnScratch& s) {
+    s.st = st; s.w = stream_ws(m, st);
+    if (s.w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces%s", advice); return NBK_ERR_ALLOC; }
+    s.lock = std::unique_lock<std::mutex>(s.w->mu); s.capturing = stream_capturing(st);
+    return NBK_OK;
+}
+// bind_own: the tile mode (batches of two pipe tiles or more alternate on two streams, never inside a capture); with `grow` the
+// workspace for it, which a capture cannot allocate; the mark a capture leaves on the stream's tables; the second stream's set.
+static int32_t bind_own(const nbk_model* m, const PairCounts& pc, int64_t B, bool grow, OwnScratch& s, WsBinding& b) {
+    StreamWs* w = s.w;
+    const bool pipe = pipelined(m->pm, g_opt, B);
+    TileMode mode = pipe && !s.capturing ? TileMode::TwoStreams : TileMode::Plain;
+    if (grow) {
+        size_t need = TilePlan(m->pm, g_opt, pc, B, mode).bytes;
+        // a direct call of this size is pipelined and sizes the scratch for ITS tiles: a capture that finds such a scratch runs the same
+        // tiles, one after the other on the caller's stream (no second stream inside a graph); tiling never changes a result
+        if (s.capturing && pipe && w->ws_bytes < need) {
+            const size_t need_tiles = TilePlan(m->pm, g_opt, pc, B, TileMode::PipeSerial).bytes;
+            if (w->ws_bytes >= need_tiles) { mode = TileMode::PipeSerial; need = need_tiles; }
+        }
+        if (s.capturing && w->ws_bytes < need) {
+            snprintf(g_err, sizeof(g_err), "graph capture: this stream's internal workspace is not allocated yet -- run the call once outside the capture, or pass a workspace (nbk_validity_batch_ws)");
+            return NBK_ERR_UNSUPPORTED;
+        }
+        { const int32_t rc = ensure_validity_ws(m, w, need, s.st, "hipMalloc(workspace)"); if (rc != NBK_OK) return rc; }
+    }
+    // a captured call is replayed out of order with the host-side state: it prepares + clears inside the graph, and so does the next direct call
+    if (s.capturing) w->tables.mark_captured();
+    if (mode == TileMode::TwoStreams) { const int32_t rc = pipe_setup(m, pc, w, B); if (rc != NBK_OK) return rc; }
+    b = WsBinding{w->ws, s.capturing ? nullptr : w, mode};
+    return NBK_OK;
 }
 
 // the last launch of an entry point on a movable descriptor (k_world_guard); nothing for an ordinary one
@@ -4788,13 +4753,8 @@ static int32_t guard_verdicts(const nbk_model* m, hipStream_t st, uint8_t* valid
 }
 
 int64_t nbk_validity_workspace_bytes(const nbk_model* m, int64_t B) {
-    if (m == nullptr || B < 0) return NBK_ERR_INVALID;
-    if ((B < g_opt.two_kernel_min_b && m->parked_ok) || m->n_pairs == 0 || B == 0) return 0;
-    // NSUB sub-queues, each sized for the blocks that map to it (rounded up)
-    return two_kernel_workspace_bytes(m, all_pairs(m), B);        // the caller's workspace serves every threshold
+    return m == nullptr || B < 0 ? NBK_ERR_INVALID : caller_workspace_bytes(m->pm, g_opt, B);
 }
-
-static const EdgeSrc NO_EDGES = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
 
 int32_t nbk_validity_batch_ws(const nbk_model* m, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
                               uint8_t* mask_bytes, void* workspace, int64_t workspace_bytes, void* stream) {
@@ -4814,7 +4774,8 @@ int32_t nbk_validity_batch_ws(const nbk_model* m, const double* q, int64_t B, do
         NBK_HIP(hipGetLastError());
         return guard_masks(m, NBK_OK, mask_bits, mask_bytes, B, st);
     }
-    return guard_masks(m, launch_two_kernel(m, all_pairs(m), NO_EDGES, q, B, threshold, mask_bits, mask_bytes, workspace, st), mask_bits, mask_bytes, B, st);
+    return guard_masks(m, launch_validity({m, all_pairs(m->pm), NO_EDGES, q, B, threshold, mask_bits, mask_bytes, st}, {workspace, nullptr, TileMode::Plain}),
+                       mask_bits, mask_bytes, B, st);
 }
 
 int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, double threshold, uint64_t* mask_bits,
@@ -4827,31 +4788,11 @@ int32_t nbk_validity_batch(const nbk_model* m, const double* q, int64_t B, doubl
     // shapes are out of the arm's reach for good)
     const PairCounts pc = sized_pairs(m, threshold);
     hipStream_t st = (hipStream_t)stream;
-    const bool capturing = stream_capturing(st);
-    const bool pipe = pipelined(m, B) && !capturing;
-    int64_t need = two_kernel_workspace_bytes(m, pc, B, pipe);
-    StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
-    if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces: pass your own (nbk_validity_batch_ws)"); return NBK_ERR_ALLOC; }
-    std::lock_guard<std::mutex> lock(w->mu);
-    // a direct call of this size is pipelined and sizes the scratch for ITS tiles: a capture that finds such a scratch runs the same
-    // tiles, one after the other on the caller's stream (no second stream inside a graph); tiling never changes a result
-    bool pipe_sized = false;
-    if (capturing && w->ws_bytes < (size_t)need && pipelined(m, B)) {
-        const int64_t need_tiles = two_kernel_workspace_bytes(m, pc, B, true);
-        if (w->ws_bytes >= (size_t)need_tiles) { pipe_sized = true; need = need_tiles; }
-    }
-    if (capturing && w->ws_bytes < (size_t)need) {
-        snprintf(g_err, sizeof(g_err), "graph capture: this stream's internal workspace is not allocated yet -- run the call once "
-                 "outside the capture, or pass a workspace (nbk_validity_batch_ws)");
-        return NBK_ERR_UNSUPPORTED;
-    }
-    { const int32_t rc = ensure_validity_ws(m, w, (size_t)need, st, "hipMalloc(workspace)"); if (rc != NBK_OK) return rc; }
-    // a captured call must be self-contained (it is replayed out of order with the host-side state): prepare + clear inside
-    // the graph, and the next direct call starts from scratch as well
-    if (capturing) { w->ready = false; w->captured = true; }
-    if (pipe) { const int32_t rc = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, B); if (rc != NBK_OK) return rc; }
-    return guard_masks(m, launch_two_kernel(m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, w->ws, st, capturing ? nullptr : w, pipe, pipe_sized),
-                       mask_bits, mask_bytes, B, st);
+    OwnScratch s;
+    WsBinding b;
+    { const int32_t rc = own_scratch(m, st, ": pass your own (nbk_validity_batch_ws)", s); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = bind_own(m, pc, B, true, s, b); if (rc != NBK_OK) return rc; }
+    return guard_masks(m, launch_validity({m, pc, NO_EDGES, q, B, threshold, mask_bits, mask_bytes, st}, b), mask_bits, mask_bytes, B, st);
 }
 
 // workgroups that share the pair list of one block of configurations in the per-pair distance kernels: enough to put ~8 waves on
@@ -5009,25 +4950,6 @@ int32_t nbk_spline_motion_bounds_host(const nbk_model_desc* d, const double* ctr
 // steer, and for connect whenever the caller's edges respect the connector's max_distance (planners do) -- and at least 1.25 x
 // the count the previous call reported through pinned memory (`stats`, read here without waiting).  Edges that do not fit
 // anyway are marked and walked by one wave each (k_edges_overflow): always correct, only slower.
-static inline unsigned long long edge_capacity(int64_t E, double resolution, double max_distance) {
-    double per = ceil(max_distance / resolution) + 2.0;
-    if (!(per < 4096.0)) per = 4096.0;                    // an unbounded max_distance: start from 4096 samples per edge
-    double c = (double)E * per;
-    if (c < 4096.0) c = 4096.0;
-    if (c > 4.0e9) c = 4.0e9;
-    return ((unsigned long long)c + 63ull) & ~63ull;
-}
-
-// a stream's edge scratch for ne edges and nc samples: plan [ne][3] double | cnt [ne + 1] | offs [ne + 1] | overflow flags [ne],
-// then the sample map [nc] and the mask words [nc / 64], each of the three parts rounded up to 4 KiB.  Byte offsets (plan at 0), total
-struct EdgeLayout {
-    size_t cnt, offs, ovf, map, words, bytes;
-    static size_t r4k(size_t n) { return (n + 4095) & ~size_t(4095); }
-    EdgeLayout(long long ne, unsigned long long nc)
-        : cnt((size_t)ne * 3 * 8), offs(cnt + (size_t)(ne + 1) * 8), ovf(offs + (size_t)(ne + 1) * 8), map(r4k(ovf + (size_t)ne)),
-          words(map + r4k((size_t)nc * 8)), bytes(words + r4k(((size_t)nc + 63) / 64 * 8)) {}
-};
-
 int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
                                 double resolution, double max_distance, int32_t mode, double threshold, uint8_t* valid,
                                 double* end, int32_t* n_samples, void* stream) {
@@ -5044,10 +4966,10 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
         NBK_HIP(hipGetLastError());
         return guard_verdicts(m, st, valid, nullptr, nullptr, nullptr, E);
     }
-    StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
-    if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces"); return NBK_ERR_ALLOC; }
-    std::lock_guard<std::mutex> lock(w->mu);
-    const bool capturing = stream_capturing(st);
+    OwnScratch s;
+    { const int32_t rc = own_scratch(m, st, "", s); if (rc != NBK_OK) return rc; }
+    StreamWs* const w = s.w;
+    const bool capturing = s.capturing;
     // capacity: the static bound, and what earlier calls on this stream turned out to need (pinned memory, not waited for)
     unsigned long long cap = edge_capacity(E, resolution, max_distance);
     if (w->stats != nullptr && __atomic_load_n(&w->stats[1], __ATOMIC_RELAXED) != 0ull) {
@@ -5066,7 +4988,7 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
     unsigned long long *cnt = nullptr, *offs = nullptr, *map = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool fits = w->ecap_edges >= E && w->ecap_samples >= cap && w->stats != nullptr &&
-                          w->ws_bytes >= (size_t)two_kernel_workspace_bytes(m, pc, (int64_t)w->ecap_samples);
+                          w->ws_bytes >= TilePlan(m->pm, g_opt, pc, (int64_t)w->ecap_samples, TileMode::Plain).bytes;
         if (!fits) {
             if (capturing) {
                 snprintf(g_err, sizeof(g_err), "graph capture: this stream's edge scratch is not allocated for %lld edges yet -- run the "
@@ -5083,7 +5005,7 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
             int32_t rc = grow_scratch(st, w->ews, w->ews_bytes, EdgeLayout(ne, nc).bytes, "hipMalloc(edge scratch)");
             if (rc != NBK_OK) return rc;
             w->ecap_edges = ne; w->ecap_samples = nc;
-            rc = ensure_validity_ws(m, w, (size_t)two_kernel_workspace_bytes(m, pc, (int64_t)nc), st, "hipMalloc(workspace)");
+            rc = ensure_validity_ws(m, w, TilePlan(m->pm, g_opt, pc, (int64_t)nc, TileMode::Plain).bytes, st, "hipMalloc(workspace)");
             if (rc != NBK_OK) return rc;
         }
         cap = w->ecap_samples;                                 // use all of what is there
@@ -5112,11 +5034,9 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
     hipLaunchKernelGGL(k_edge_expand, dim3((unsigned)E), dim3(WAVE), 0, st, offs, E, map, cap, ovf);
     NBK_HIP(hipGetLastError());
     EdgeSrc es{starts, goals, plan, map, offs + E, 0, nullptr};
-    if (capturing) { w->ready = false; w->captured = true; }
-    const bool pipe = pipelined(m, (int64_t)cap) && !capturing;
-    if (pipe) { const int32_t rp = pipe_setup(const_cast<nbk_model*>(m), m, pc, w, (int64_t)cap); if (rp != NBK_OK) return rp; }
-    const int32_t rc = launch_two_kernel(m, pc, es, nullptr, (int64_t)cap, threshold, words, nullptr, w->ws, st, capturing ? nullptr : w, pipe);
-    if (rc != NBK_OK) return rc;
+    WsBinding b;                          // (the loop above sized the main workspace, for the unpipelined tiling)
+    { const int32_t rc = bind_own(m, pc, (int64_t)cap, false, s, b); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_validity({m, pc, es, nullptr, (int64_t)cap, threshold, words, nullptr, st}, b); if (rc != NBK_OK) return rc; }
     hipLaunchKernelGGL(k_edge_reduce, dim3((unsigned)E), dim3(WAVE), 0, st, offs, E, words, ovf, valid, w->stats_dev);
     NBK_HIP(hipGetLastError());
     if (m->parked_ok) {
@@ -5128,15 +5048,6 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
 }
 
 // ---- clamped B-spline trajectories: synchronous (one 8-byte read-back of the sample total sizes the mask words and the tiles) ----
-static const int64_t SPLINE_TILE = int64_t(1) << 20;           // q rows written and checked per tile
-// the small half of a stream's spline scratch: knots [nk] | plan [S][2] | cnt [S] | offs [S + 1], each part 256-byte aligned
-struct SplineLayout {
-    size_t plan, cnt, offs, bytes;
-    static size_t r256(size_t n) { return (n + 255) & ~size_t(255); }
-    SplineLayout(int nk, int64_t S)
-        : plan(r256((size_t)nk * 8)), cnt(plan + r256((size_t)S * 16)), offs(cnt + r256((size_t)S * 8)), bytes(offs + r256((size_t)(S + 1) * 8)) {}
-};
-
 int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
                                   double resolution, double threshold, uint8_t* valid, double* t_hit, int32_t* n_samples, void* stream) {
     if (m == nullptr || S < 0 || knots == nullptr || (S > 0 && (ctrl == nullptr || valid == nullptr))) return NBK_ERR_INVALID;
@@ -5155,9 +5066,9 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
         snprintf(g_err, sizeof(g_err), "spline batches read their sample count back to the host and cannot be captured into a graph");
         return NBK_ERR_UNSUPPORTED;
     }
-    StreamWs* w = stream_ws(const_cast<nbk_model*>(m), st);
-    if (w == nullptr) { snprintf(g_err, sizeof(g_err), "more than 64 streams use this descriptor's internal workspaces"); return NBK_ERR_ALLOC; }
-    std::lock_guard<std::mutex> lock(w->mu);
+    OwnScratch s;
+    { const int32_t rc = own_scratch(m, st, "", s); if (rc != NBK_OK) return rc; }
+    StreamWs* const w = s.w;
     const SplineLayout L(nk, S);
     { const int32_t rc = grow_scratch(st, w->sps, w->sps_bytes, L.bytes, "hipMalloc(spline scratch)"); if (rc != NBK_OK) return rc; }
     char* sp = static_cast<char*>(w->sps);
@@ -5188,7 +5099,7 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
         int32_t rc = grow_scratch(st, w->spl, w->spl_bytes, words_bytes + slab_bytes, "hipMalloc(spline samples)");
         if (rc != NBK_OK) return rc;
         if (pairs) {
-            rc = ensure_validity_ws(m, w, (size_t)two_kernel_workspace_bytes(m, pc, tile), st, "hipMalloc(workspace)");
+            rc = ensure_validity_ws(m, w, TilePlan(m->pm, g_opt, pc, tile, TileMode::Plain).bytes, st, "hipMalloc(workspace)");
             if (rc != NBK_OK) return rc;
         }
     }
@@ -5198,20 +5109,14 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
         const int64_t nb = std::min<int64_t>(tile, T - b0);
         const dim3 grid((unsigned)((nb + 255) / 256)), block(256);
         uint64_t* wx = pairs ? nullptr : words;
-#define NBK_SPLINE_EXPAND(K_) hipLaunchKernelGGL(k_spline_expand<K_>, grid, block, 0, st, m->n_q, ctrl, (int)n_ctrl, (const double*)kn, \
-                                                 (const double*)plan, (const unsigned long long*)offs, S, (long long)b0, (long long)nb, slab, wx)
-        switch (degree) {
-            case 1: NBK_SPLINE_EXPAND(1); break;
-            case 2: NBK_SPLINE_EXPAND(2); break;
-            case 3: NBK_SPLINE_EXPAND(3); break;
-            case 4: NBK_SPLINE_EXPAND(4); break;
-            default: NBK_SPLINE_EXPAND(5); break;
-        }
-#undef NBK_SPLINE_EXPAND
+        with_degree(degree, [&](auto K) {
+            hipLaunchKernelGGL(k_spline_expand<decltype(K)::value>, grid, block, 0, st, m->n_q, ctrl, (int)n_ctrl, (const double*)kn,
+                               (const double*)plan, (const unsigned long long*)offs, S, (long long)b0, (long long)nb, slab, wx);
+        });
         NBK_HIP(hipGetLastError());
         if (pairs) {
             // the stream's mutex is held: the validity pipeline directly (nbk_validity_batch would take it again); b0 is a multiple of 64
-            const int32_t rc = launch_two_kernel(m, pc, NO_EDGES, slab, nb, threshold, words + b0 / 64, nullptr, w->ws, st, w, false);
+            const int32_t rc = launch_validity({m, pc, NO_EDGES, slab, nb, threshold, words + b0 / 64, nullptr, st}, {w->ws, w, TileMode::Plain});
             if (rc != NBK_OK) return rc;
         }
     }
@@ -5241,16 +5146,9 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
     if (N > 0) {
         const dim3 grid((unsigned)((N + WAVE - 1) / WAVE)), block(WAVE);
         const size_t lds = sizeof(double) * WAVE * (size_t)(m->n_q > 0 ? m->n_q : 1);
-#define NBK_SPLINE_CA(K_) hipLaunchKernelGGL(k_spline_ca<K_>, grid, block, lds, st, m->d, ctrl, S, (int)n_ctrl, knots, threshold, \
-                                             (int)max_iter, slack, key)
-        switch (degree) {
-            case 1: NBK_SPLINE_CA(1); break;
-            case 2: NBK_SPLINE_CA(2); break;
-            case 3: NBK_SPLINE_CA(3); break;
-            case 4: NBK_SPLINE_CA(4); break;
-            default: NBK_SPLINE_CA(5); break;
-        }
-#undef NBK_SPLINE_CA
+        with_degree(degree, [&](auto K) {
+            hipLaunchKernelGGL(k_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, ctrl, S, (int)n_ctrl, knots, threshold, (int)max_iter, slack, key);
+        });
         NBK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_spline_ca_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const unsigned long long*)key, valid,
@@ -5263,35 +5161,34 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
 // The reference's planners call these once per sample / per edge (numbotics/planning/sampling_based/prm.py:40,
 // connectors.py:57-100), so what counts is latency: inputs and results travel through pinned host memory that the kernels
 // read and write directly (no staging copies), on a private stream with its own scratch set; one wait at the end.
-static int32_t scalar_setup(nbk_model* mm) {
-    if (mm->scalar_q != nullptr) return NBK_OK;
-    const size_t nd = 4 * (size_t)mm->n_q + 8;
-    NBK_HIP(hipHostMalloc((void**)&mm->scalar_q, nd * sizeof(double), hipHostMallocMapped));
-    NBK_HIP(hipHostMalloc((void**)&mm->scalar_out, 8 * sizeof(unsigned long long), hipHostMallocMapped));
-    NBK_HIP(hipStreamCreateWithFlags(&mm->scalar_stream, hipStreamNonBlocking));
-    NBK_HIP(hipHostGetDevicePointer((void**)&mm->scalar_q_dev, mm->scalar_q, 0));
-    NBK_HIP(hipHostGetDevicePointer((void**)&mm->scalar_out_dev, mm->scalar_out, 0));
+static int32_t scalar_setup(const nbk_model* m) {
+    if (m->host.scalar_q != nullptr) return NBK_OK;
+    const size_t nd = 4 * (size_t)m->n_q + 8;
+    NBK_HIP(hipHostMalloc((void**)&m->host.scalar_q, nd * sizeof(double), hipHostMallocMapped));
+    NBK_HIP(hipHostMalloc((void**)&m->host.scalar_out, 8 * sizeof(unsigned long long), hipHostMallocMapped));
+    NBK_HIP(hipStreamCreateWithFlags(&m->host.scalar_stream, hipStreamNonBlocking));
+    NBK_HIP(hipHostGetDevicePointer((void**)&m->host.scalar_q_dev, m->host.scalar_q, 0));
+    NBK_HIP(hipHostGetDevicePointer((void**)&m->host.scalar_out_dev, m->host.scalar_out, 0));
     return NBK_OK;
 }
 
 int32_t nbk_validity_scalar_host(const nbk_model* m, const double* q, double threshold, int32_t* in_collision) {
     if (m == nullptr || q == nullptr || in_collision == nullptr) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
-    nbk_model* mm = const_cast<nbk_model*>(m);
-    std::lock_guard<std::mutex> lock(mm->scalar_mu);
-    { const int32_t rc = scalar_setup(mm); if (rc != NBK_OK) return rc; }
-    if (mm->movable) {
-        std::lock_guard<std::mutex> wl(mm->world_mu);
-        if (mm->world_ev_set) NBK_HIP(hipStreamWaitEvent(mm->scalar_stream, mm->world_ev, 0));     // ordered after the last update
+    std::lock_guard<std::mutex> lock(m->host.scalar_mu);
+    { const int32_t rc = scalar_setup(m); if (rc != NBK_OK) return rc; }
+    if (m->movable) {
+        std::lock_guard<std::mutex> wl(m->host.world_mu);
+        if (m->host.world_ev_set) NBK_HIP(hipStreamWaitEvent(m->host.scalar_stream, m->host.world_ev, 0));     // ordered after the last update
     }
-    memcpy(mm->scalar_q, q, sizeof(double) * (size_t)m->n_q);
-    double* dq = mm->scalar_q_dev;
-    uint64_t* dout = reinterpret_cast<uint64_t*>(mm->scalar_out_dev);
-    mm->scalar_out[0] = 0ull;
-    const int32_t rc = nbk_validity_batch(m, dq, 1, threshold, dout, nullptr, mm->scalar_stream);
+    memcpy(m->host.scalar_q, q, sizeof(double) * (size_t)m->n_q);
+    double* dq = m->host.scalar_q_dev;
+    uint64_t* dout = reinterpret_cast<uint64_t*>(m->host.scalar_out_dev);
+    m->host.scalar_out[0] = 0ull;
+    const int32_t rc = nbk_validity_batch(m, dq, 1, threshold, dout, nullptr, m->host.scalar_stream);
     if (rc != NBK_OK) return rc;
-    NBK_HIP(hipStreamSynchronize(mm->scalar_stream));
-    *in_collision = (int32_t)(mm->scalar_out[0] & 1ull);
+    NBK_HIP(hipStreamSynchronize(m->host.scalar_stream));
+    *in_collision = (int32_t)(m->host.scalar_out[0] & 1ull);
     return NBK_OK;
 }
 
@@ -5300,28 +5197,27 @@ int32_t nbk_edge_validity_scalar_host(const nbk_model* m, const double* start, c
                                       int32_t* n_samples) {
     if (m == nullptr || start == nullptr || goal == nullptr || valid == nullptr) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
-    nbk_model* mm = const_cast<nbk_model*>(m);
-    std::lock_guard<std::mutex> lock(mm->scalar_mu);
-    { const int32_t rc = scalar_setup(mm); if (rc != NBK_OK) return rc; }
-    if (mm->movable) {
-        std::lock_guard<std::mutex> wl(mm->world_mu);
-        if (mm->world_ev_set) NBK_HIP(hipStreamWaitEvent(mm->scalar_stream, mm->world_ev, 0));     // ordered after the last update
+    std::lock_guard<std::mutex> lock(m->host.scalar_mu);
+    { const int32_t rc = scalar_setup(m); if (rc != NBK_OK) return rc; }
+    if (m->movable) {
+        std::lock_guard<std::mutex> wl(m->host.world_mu);
+        if (m->host.world_ev_set) NBK_HIP(hipStreamWaitEvent(m->host.scalar_stream, m->host.world_ev, 0));     // ordered after the last update
     }
     const size_t nq = (size_t)m->n_q;
-    double* h = mm->scalar_q;                           // start | goal | end | dist
+    double* h = m->host.scalar_q;                           // start | goal | end | dist
     memcpy(h, start, sizeof(double) * nq);
     memcpy(h + nq, goal, sizeof(double) * nq);
     h[3 * nq] = dist;
-    double* d = mm->scalar_q_dev;
-    unsigned long long* dout = mm->scalar_out_dev;
+    double* d = m->host.scalar_q_dev;
+    unsigned long long* dout = m->host.scalar_out_dev;
     const bool has_dist = dist >= 0.0 || dist != dist;      // a negative value = "Euclidean norm" (a NaN length is a given length)
     const int32_t rc = nbk_edge_validity_batch(m, d, d + nq, has_dist ? d + 3 * nq : nullptr, 1, resolution, max_distance, mode, threshold,
-                                               reinterpret_cast<uint8_t*>(dout), d + 2 * nq, reinterpret_cast<int32_t*>(dout + 1), mm->scalar_stream);
+                                               reinterpret_cast<uint8_t*>(dout), d + 2 * nq, reinterpret_cast<int32_t*>(dout + 1), m->host.scalar_stream);
     if (rc != NBK_OK) return rc;
-    NBK_HIP(hipStreamSynchronize(mm->scalar_stream));
-    *valid = (int32_t)(reinterpret_cast<const uint8_t*>(mm->scalar_out)[0]);
+    NBK_HIP(hipStreamSynchronize(m->host.scalar_stream));
+    *valid = (int32_t)(reinterpret_cast<const uint8_t*>(m->host.scalar_out)[0]);
     if (end != nullptr) memcpy(end, h + 2 * nq, sizeof(double) * nq);
-    if (n_samples != nullptr) *n_samples = reinterpret_cast<const int32_t*>(mm->scalar_out + 1)[0];
+    if (n_samples != nullptr) *n_samples = reinterpret_cast<const int32_t*>(m->host.scalar_out + 1)[0];
     return NBK_OK;
 }
 
@@ -5344,23 +5240,23 @@ int32_t nbk_model_create_movable(const nbk_model_desc* d, double world_radius, n
 }
 
 // the update on `st` (world_mu held): clear the status word, k_world_update; every stream's tables become stale
-static int32_t world_update_launch(nbk_model* mm, const double* poses, hipStream_t st) {
+static int32_t world_update_launch(nbk_model* m, const double* poses, hipStream_t st) {
     const bool capturing = stream_capturing(st);
-    mm->world_epoch.fetch_add(1, std::memory_order_acq_rel);
-    if (capturing) mm->world_captured.store(true, std::memory_order_release);
-    NBK_HIP(hipMemsetAsync(mm->world_status, 0, sizeof(int), st));
-    const int n = mm->d.n_wshapes > mm->d.n_pairs ? mm->d.n_wshapes : mm->d.n_pairs;
+    m->host.world_epoch.fetch_add(1, std::memory_order_acq_rel);
+    if (capturing) m->host.world_captured.store(true, std::memory_order_release);
+    NBK_HIP(hipMemsetAsync(m->world_status, 0, sizeof(int), st));
+    const int n = m->d.n_wshapes > m->d.n_pairs ? m->d.n_wshapes : m->d.n_pairs;
     if (n > 0) {
-        const WorldUpd u{mm->rs_reach, mm->world_status, mm->world_radius};
-        hipLaunchKernelGGL(k_world_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mm->d, u, poses);
+        const WorldUpd u{m->rs_reach, m->world_status, m->world_radius};
+        hipLaunchKernelGGL(k_world_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->d, u, poses);
         NBK_HIP(hipGetLastError());
     }
     // the scalar calls run on a private stream: they wait for this event (a captured update cannot be waited for from outside its
     // graph -- nbk.h says so)
     if (!capturing) {
-        if (mm->world_ev == nullptr) NBK_HIP(hipEventCreateWithFlags(&mm->world_ev, hipEventDisableTiming));
-        NBK_HIP(hipEventRecord(mm->world_ev, st));
-        mm->world_ev_set = true;
+        if (m->host.world_ev == nullptr) NBK_HIP(hipEventCreateWithFlags(&m->host.world_ev, hipEventDisableTiming));
+        NBK_HIP(hipEventRecord(m->host.world_ev, st));
+        m->host.world_ev_set = true;
     }
     return NBK_OK;
 }
@@ -5371,7 +5267,7 @@ int32_t nbk_model_set_world_poses(nbk_model* m, const double* poses, void* strea
     if (m->d.n_wshapes > 0 && poses == nullptr) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(m->world_mu);
+    std::lock_guard<std::mutex> lock(m->host.world_mu);
     return world_update_launch(m, poses, st);
 }
 
@@ -5381,19 +5277,19 @@ int32_t nbk_model_set_world_poses_host(nbk_model* m, const double* poses) {
     const size_t W = (size_t)m->d.n_wshapes;
     if (W > 0 && poses == nullptr) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
-    std::lock_guard<std::mutex> sl(m->scalar_mu);          // the scalar calls' private stream carries the update: they follow it
+    std::lock_guard<std::mutex> sl(m->host.scalar_mu);          // the scalar calls' private stream carries the update: they follow it
     { const int32_t rc = scalar_setup(m); if (rc != NBK_OK) return rc; }
-    std::lock_guard<std::mutex> lock(m->world_mu);
-    if (m->world_stage == nullptr) {
-        NBK_HIP(hipHostMalloc((void**)&m->world_stage, (W > 0 ? W : 1) * 12 * sizeof(double), hipHostMallocMapped));
-        NBK_HIP(hipHostGetDevicePointer((void**)&m->world_stage_dev, m->world_stage, 0));
+    std::lock_guard<std::mutex> lock(m->host.world_mu);
+    if (m->host.world_stage == nullptr) {
+        NBK_HIP(hipHostMalloc((void**)&m->host.world_stage, (W > 0 ? W : 1) * 12 * sizeof(double), hipHostMallocMapped));
+        NBK_HIP(hipHostGetDevicePointer((void**)&m->host.world_stage_dev, m->host.world_stage, 0));
     }
-    if (W > 0) memcpy(m->world_stage, poses, W * 12 * sizeof(double));
+    if (W > 0) memcpy(m->host.world_stage, poses, W * 12 * sizeof(double));
     // two updates must not overtake each other: this one follows the last direct update issued on another stream
-    if (m->world_ev_set) NBK_HIP(hipStreamWaitEvent(m->scalar_stream, m->world_ev, 0));
-    const int32_t rc = world_update_launch(m, m->world_stage_dev, m->scalar_stream);
+    if (m->host.world_ev_set) NBK_HIP(hipStreamWaitEvent(m->host.scalar_stream, m->host.world_ev, 0));
+    const int32_t rc = world_update_launch(m, m->host.world_stage_dev, m->host.scalar_stream);
     if (rc != NBK_OK) return rc;
-    NBK_HIP(hipStreamSynchronize(m->scalar_stream));       // the staging is free again, and work launched from now on sees the poses
+    NBK_HIP(hipStreamSynchronize(m->host.scalar_stream));       // the staging is free again, and work launched from now on sees the poses
     return NBK_OK;
 }
 
@@ -5402,9 +5298,8 @@ int32_t nbk_model_world_status(const nbk_model* m, int32_t* status) {
     NBK_DEVICE(m);
     // wait for the last update issued outside a capture (its event), not for every stream of the device
     {
-        nbk_model* mm = const_cast<nbk_model*>(m);
-        std::lock_guard<std::mutex> lock(mm->world_mu);
-        if (mm->world_ev_set) NBK_HIP(hipEventSynchronize(mm->world_ev));
+            std::lock_guard<std::mutex> lock(m->host.world_mu);
+        if (m->host.world_ev_set) NBK_HIP(hipEventSynchronize(m->host.world_ev));
     }
     int v = 0;
     NBK_HIP(hipMemcpy(&v, m->world_status, sizeof(int), hipMemcpyDeviceToHost));

@@ -1388,7 +1388,7 @@ def test_internal_workspace_calls_are_capturable_once_allocated(fresh_world, tor
 def test_graph_replays_interleaved_with_direct_calls(fresh_world, torch_cuda):
     """capture, direct, direct, replay, direct -- with another threshold and a SMALLER batch in the direct calls.  A replayed graph
     rewrites the stream's float32 tables for its own threshold and leaves counter set 0 non-empty behind the host's back; direct
-    calls on a stream that has captured therefore never reuse cached tables / counter sets (StreamWs::captured).  Every mask
+    calls on a stream that has captured therefore never reuse cached tables / counter sets (TableCache::captured).  Every mask
     against the oracle."""
     import ctypes as C
     torch = torch_cuda

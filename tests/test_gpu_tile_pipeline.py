@@ -1,4 +1,4 @@
-"""The scheduling layer above the validity kernels (launch_two_kernel_impl, nbk_validity_batch, nbk_edge_validity_batch): batch
+"""The scheduling layer above the validity kernels (launch_validity, nbk_validity_batch, nbk_edge_validity_batch): batch
 tiling, odd tiles on the library's second stream with its own scratch set (cached tables, two counter sets, overflow marks, world
 epoch), and narrowphase chunks handed out by ticket.  ``pipe_tile = 16384`` brings the two-stream pipeline down from 2^21 rows to
 32 768, so every row of every call is compared with the oracle -- exactly, there is no tolerance in this file -- and
