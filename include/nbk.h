@@ -430,6 +430,59 @@ int32_t nbk_spline_motion_bounds_host(const nbk_model_desc *desc, const double *
                                       int32_t degree, const double *knots /* host */, double *mu /* [S][n_ctrl-degree][P] */);
 
 /*
+ * Point-cloud obstacles (additive; the reference has no such obstacle: a depth camera's scan would be one sphere body per point).
+ * A cloud is N points of ONE radius in a uniform grid on the device.  It belongs to no descriptor -- one cloud serves many robots --
+ * and the entry points below look at the cloud ALONE: the descriptor's own pairs and world shapes play no part (full validity is
+ * nbk_validity_batch, then nbk_cloud_validity_batch with accumulate on the same mask).
+ *
+ * nbk_cloud_create: the grid is lo[3], cell > 0 and dims[3] (each >= 1, product <= 2^22); the cell coordinate of x on an axis is
+ * floor((x - lo) / cell) in float64 clamped to [0, dim - 1], so points outside the box land in border cells and none is dropped
+ * (a box that is too small costs time, never a result).  It allocates everything the object will ever need, for up to `capacity`
+ * points (1 .. 2^24).  NBK_ERR_INVALID -- before any device is looked for -- for a null pointer, a capacity out of range, a NaN or
+ * non-positive cell, a non-finite lo, a dim below 1 or more than 2^22 cells.
+ *
+ * nbk_cloud_set_points: pts (DEVICE) [N][3].  Asynchronous, no allocation, no host synchronisation, capturable: a memset, then
+ * count, scan and scatter kernels in `stream`'s order; queries issued to that stream afterwards see the new points and radius
+ * (both live on the device: a replayed graph that holds an update sets them for the queries behind it).  Queries on OTHER streams
+ * are the caller's to order, in both directions, as for nbk_model_set_world_poses.  N = 0 empties the cloud.  NBK_ERR_INVALID for
+ * N > capacity, a NaN or negative radius, or null pts with N > 0.  A non-finite coordinate sets the cloud's status (2); while it is
+ * set every configuration is reported colliding and the clearance outputs are NaN / -1 / -1, whatever the other points are; the
+ * next update whose points are all finite clears it.  nbk_cloud_status: synchronous read (it waits for the last update issued outside a
+ * capture, by an event of the cloud's own: that update's stream may be gone by then; after replaying a graph that holds an update, synchronise that stream first).
+ *
+ * nbk_cloud_validity_batch: bit b is the OR, over the selected robot shapes s and the points i, of the pair predicate of
+ * nbk_validity_batch for (shape s, a sphere world shape of radius `radius` at p_i) -- bit for bit what a descriptor with those N
+ * spheres as world shapes and those pairs reports.  A configuration with a non-finite joint value collides.
+ *   shape_bits (HOST, optional) ceil(S / 64) words, bit s = robot shape s of the descriptor as it was given to nbk_model_create;
+ *   NULL = every robot shape.  With a selection S must be at most 256 (NBK_ERR_UNSUPPORTED otherwise).
+ *   accumulate != 0: OR into the caller's mask instead of overwriting it (bits beyond B in the last word: written 0 when
+ *   overwriting, left alone when accumulating).  At least one of mask_bits / mask_bytes must be given.
+ * nbk_cloud_clearance_batch: per configuration the minimum over the selected (s, i) of the signed distance of that pair (the bits of
+ * nbk_pair_distances_batch for it), reported if and only if it is < d_max (finite: NBK_ERR_INVALID otherwise), with its shape
+ * (the caller's index) and the point's index in the array given to the last update; on equal distances the smallest shape, then the
+ * smallest point index.  Otherwise +inf, -1, -1 (an empty cloud, an empty selection).  A non-finite configuration or a set status:
+ * NaN, -1, -1.  shape / point are optional.
+ * Both are asynchronous and capturable (no allocation, no synchronisation, one kernel); nothing is parked in LDS beyond the staged
+ * q rows, so every descriptor is served.  The descriptor's and the cloud's device must be current.
+ *
+ * nbk_cloud_cells_host (no GPU needed): the cell index ((z * dims[1] + y) * dims[0] + x) of each of N HOST points, by the routine
+ * the device uses.
+ */
+typedef struct nbk_cloud nbk_cloud;
+int32_t nbk_cloud_create(int64_t capacity, const double lo[3], double cell, const int32_t dims[3], nbk_cloud **out);
+void nbk_cloud_destroy(nbk_cloud *c);
+int32_t nbk_cloud_set_points(nbk_cloud *c, const double *pts /* DEVICE [N][3] */, int64_t N, double radius, void *stream);
+int32_t nbk_cloud_status(const nbk_cloud *c, int32_t *status);   /* synchronous: 0 ok, 2 a non-finite point */
+int32_t nbk_cloud_validity_batch(const nbk_model *m, const nbk_cloud *c, const double *q, int64_t B, double threshold,
+                                 const uint64_t *shape_bits /* host, ceil(S/64) words, NULL = every robot shape */,
+                                 int32_t accumulate, uint64_t *mask_bits, uint8_t *mask_bytes, void *stream);
+int32_t nbk_cloud_clearance_batch(const nbk_model *m, const nbk_cloud *c, const double *q, int64_t B, double d_max,
+                                  const uint64_t *shape_bits, double *min_dist /* [B] */, int32_t *shape /* [B] */,
+                                  int32_t *point /* [B] */, void *stream);
+int32_t nbk_cloud_cells_host(const double lo[3], double cell, const int32_t dims[3], const double *pts, int64_t N,
+                             int32_t *cell_out);                 /* no GPU: the same routine, for tests */
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -30,6 +30,8 @@ SYMBOLS = [
     "nbk_broad_kernel_used", "nbk_broad_spec_source", "nbk_jit_compile",
     "nbk_model_create_movable", "nbk_model_set_world_poses", "nbk_model_set_world_poses_host", "nbk_model_world_status",
     "nbk_world_reach_bounds_host",
+    "nbk_cloud_create", "nbk_cloud_destroy", "nbk_cloud_set_points", "nbk_cloud_status", "nbk_cloud_validity_batch",
+    "nbk_cloud_clearance_batch", "nbk_cloud_cells_host",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -121,6 +123,14 @@ def load():
     lib.nbk_model_num_pairs.argtypes = [vp]
     lib.nbk_validity_scalar_host.argtypes = [vp, vp, f64, vp]
     lib.nbk_edge_validity_scalar_host.argtypes = [vp, vp, vp, f64, f64, f64, i32, f64, vp, vp, vp]
+    lib.nbk_cloud_create.argtypes = [i64, vp, f64, vp, C.POINTER(C.c_void_p)]
+    lib.nbk_cloud_destroy.argtypes = [vp]
+    lib.nbk_cloud_destroy.restype = None
+    lib.nbk_cloud_set_points.argtypes = [vp, vp, i64, f64, vp]
+    lib.nbk_cloud_status.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.nbk_cloud_validity_batch.argtypes = [vp, vp, vp, i64, f64, vp, i32, vp, vp, vp]
+    lib.nbk_cloud_clearance_batch.argtypes = [vp, vp, vp, i64, f64, vp, vp, vp, vp, vp]
+    lib.nbk_cloud_cells_host.argtypes = [vp, f64, vp, vp, i64, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

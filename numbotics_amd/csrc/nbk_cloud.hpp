@@ -1,0 +1,482 @@
+// nbk_cloud.hpp -- point-cloud obstacles (include/nbk.h: nbk_cloud_*; DESIGN.md 3, "Point clouds").  Included once by nbk.hip, after
+// its own entry points: the kernels here use DevModel, joint_apply, build_core and epa_refine of nbk.hip and the predicate / distance
+// routines of nbk_device.hpp, and nothing of the validity launch path (no queue, no table, no scratch of a descriptor).
+//
+// A cloud is N points of one radius, sorted into a uniform grid (nbk_cloud_grid.hpp) on the device:
+//   hdr            status (0 ok, 2 a non-finite point), N and the radius of the last update -- written on the device, in stream order,
+//                  so that a query sees what the update ahead of it in its stream (or in its graph) set, not what the host last asked for
+//   fill  [cells]  points per cell while counting; the scatter's cursors afterwards
+//   start [cells+1] first sorted slot of each cell (exclusive scan of the counts); start[cells] = N
+//   cell_of [cap]  cell of each original point (count -> scatter)
+//   idx   [cap]    original index of each sorted point
+//   pts   [cap][3] sorted points
+// nbk_cloud_set_points: one memset (hdr + fill) | k_cloud_count | k_cloud_scan | k_cloud_scatter.  The order of the points of one
+// cell depends on the arrival of the scatter's atomics; no result does (a verdict is an OR; the clearance breaks ties by the original
+// index).
+//
+// Queries: one configuration per lane, 64 per workgroup; the wave takes the selected robot shapes one after the other (Core.kind and
+// the hull a core names are wave-uniform this way), replays FK along the shape's joint mask from the lane's staged q row, builds the
+// shape's core and walks the cells cloud_cell_range gives for the ball the pair predicate's bounding-sphere step can pass.  Cells are
+// numbered x fastest, so one (y, z) row of the range is one contiguous run of sorted points.
+#pragma once
+#define NBK_GRID_FN __host__ __device__ inline
+#include "nbk_cloud_grid.hpp"
+
+namespace nbk {
+
+struct CloudHdr { int status; int n; double radius; };
+static_assert(sizeof(CloudHdr) == 16, "the update's memset covers the header and the counters in one piece");
+
+struct CloudDev {                 // what the query kernels read (by value)
+    CloudGrid g;
+    const CloudHdr* hdr;
+    const double* pts;
+    const int* idx;
+    const unsigned* start;
+};
+
+// robot shapes a query looks at, in the descriptor's device (frame) order
+struct CloudSel { unsigned long long w[4]; int all; };
+NBK_DEV bool cloud_selected(const CloudSel& s, int i) { return s.all != 0 || ((s.w[(i >> 6) & 3] >> (i & 63)) & 1ull) != 0ull; }
+
+// ---- the update ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cloud_count(CloudGrid g, const double* __restrict__ pts, int n, int* __restrict__ cell_of,
+                                                     unsigned* __restrict__ fill, int* __restrict__ status) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const double p[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+    const bool finite = (p[0] - p[0] == 0.0) && (p[1] - p[1] == 0.0) && (p[2] - p[2] == 0.0);
+    if (!finite) atomicMax(status, 2);
+    const int c = finite ? cloud_cell(g, p) : 0;
+    cell_of[i] = c;
+    atomicAdd(&fill[c], 1u);
+}
+
+// one workgroup: thread t owns the cells [t * per, (t + 1) * per); counts -> exclusive offsets in `start` and the scatter's cursors in `fill`
+__global__ __launch_bounds__(1024) void k_cloud_scan(unsigned* __restrict__ fill, unsigned* __restrict__ start, int cells,
+                                                     CloudHdr* __restrict__ hdr, int n, double radius) {
+    __shared__ unsigned part[1024];
+    const int t = (int)threadIdx.x;
+    const int per = (cells + 1023) / 1024;
+    const int lo = t * per < cells ? t * per : cells;
+    const int hi = lo + per < cells ? lo + per : cells;
+    unsigned sum = 0u;
+    for (int c = lo; c < hi; ++c) sum += fill[c];
+    part[t] = sum;
+    __syncthreads();
+    // inclusive scan of the 1024 partial sums (Hillis-Steele)
+    for (int d = 1; d < 1024; d <<= 1) {
+        const unsigned v = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    unsigned run = part[t] - sum;
+    for (int c = lo; c < hi; ++c) {
+        const unsigned v = fill[c];
+        start[c] = run;
+        fill[c] = run;
+        run += v;
+    }
+    if (t == 0) { start[cells] = (unsigned)n; hdr->n = n; hdr->radius = radius; }
+}
+
+__global__ __launch_bounds__(256) void k_cloud_scatter(const double* __restrict__ pts, int n, const int* __restrict__ cell_of,
+                                                       unsigned* __restrict__ fill, double* __restrict__ sorted, int* __restrict__ idx,
+                                                       unsigned cap) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const unsigned pos = atomicAdd(&fill[cell_of[i]], 1u);
+    if (pos >= cap) return;            // (cannot happen: the cursors start at the scan of these very counts)
+    sorted[3 * (size_t)pos] = pts[3 * (size_t)i];
+    sorted[3 * (size_t)pos + 1] = pts[3 * (size_t)i + 1];
+    sorted[3 * (size_t)pos + 2] = pts[3 * (size_t)i + 2];
+    idx[pos] = i;
+}
+
+// ---- the walk of one lane over the cells of a ball ----------------------------------------------------------------------------
+struct CloudWalk { int x0, x1, y0, y1, z1, y, z; unsigned cur, end; bool more; };
+
+NBK_DEV void cloud_walk_begin(const CloudDev& c, bool on, const double* centre, double R, CloudWalk& w) {
+    int lo[3], hi[3];
+    w.more = cloud_cell_range(c.g, centre, R, lo, hi) && on;
+    w.x0 = lo[0]; w.x1 = hi[0]; w.y0 = lo[1]; w.y1 = hi[1]; w.z1 = hi[2];
+    w.y = lo[1] - 1; w.z = lo[2];
+    w.cur = w.end = 0u;
+}
+// true: sorted point w.cur is the next one (the caller consumes it with ++w.cur)
+NBK_DEV bool cloud_walk_next(const CloudDev& c, CloudWalk& w) {
+    while (w.cur == w.end) {
+        if (!w.more) return false;
+        if (++w.y > w.y1) {
+            w.y = w.y0;
+            if (++w.z > w.z1) { w.more = false; return false; }
+        }
+        const int row = (w.z * c.g.dims[1] + w.y) * c.g.dims[0];
+        w.cur = c.start[row + w.x0];
+        w.end = c.start[row + w.x1 + 1];
+    }
+    return true;
+}
+
+// the lane's q row into its LDS row (eight loads in flight, as k_pair_items stages it); returns whether every value is finite
+NBK_DEV bool cloud_stage_q(const double* __restrict__ q, int64_t b, int nq, double* myq) {
+    const double* qrow = q + b * nq;
+    const int nq1 = nq - 1;
+    bool fin = true;
+    for (int j0 = 0; j0 < nq; j0 += 8) {
+        double qv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { const int j = (j0 + u) < nq1 ? (j0 + u) : nq1; qv[u] = qrow[j]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (j0 + u <= nq1) { myq[j0 + u] = qv[u]; fin = fin && (qv[u] - qv[u] == 0.0); }
+    }
+    return fin;
+}
+
+// frame of robot shape s (device order) for the lane's q: the joints of the shape's mask, base first
+NBK_DEV void cloud_shape_frame(const DevModel& m, int s, const double* myq, Xf& T) {
+    const unsigned mask = m.rs_mask[s];
+    xf_from12(m.base_pose, T);
+    for (int k = 0; k < m.n_joints; ++k) {
+        if (((mask >> k) & 1u) == 0u) continue;
+        Xf nxt;
+        joint_apply(m, k, T, myq[m.joint_qidx[k]], nxt);
+        T = nxt;
+    }
+}
+
+NBK_DEV void cloud_core_init(Core& A) {
+    A.kind = K_POINT;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { A.c[e] = 0.0; A.h[e] = 0.0; A.ax[0][e] = A.ax[1][e] = A.ax[2][e] = 0.0; }
+    A.rad = A.margin = A.rho = 0.0;
+}
+// the core of a sphere world shape of radius r with identity rotation: a point core with margin r
+NBK_DEV void cloud_point_core(double r, Core& P) {
+    cloud_core_init(P);
+    P.ax[0][0] = 1.0; P.ax[1][1] = 1.0; P.ax[2][2] = 1.0;
+    P.margin = r;
+}
+
+// ---- validity -----------------------------------------------------------------------------------------------------------------
+// The pair predicate for (point core P, shape core A), canonical order (the point first).  cores_collide_exact as it is, except that a
+// hull core at tc <= 0 skips that routine's device-only cull: hull_box_far compares the point's distance from the hull's local box
+// with max(tc, 0) + the point's bounding radius = 0 and answers "free" for EVERY point there, also one inside the box (its sibling
+// box_far_negative asks for d2 > 0).  For a point against a hull cores_collide_pre decides nothing else, and the predicate ends in
+// the distance iteration either way: call it directly.
+NBK_DEV bool cloud_collides(const Core& P, const Core& A, double tc) {
+    if (A.kind == K_HULL && !(tc > 0.0)) return gjk_collides(P, A, tc);
+    return cores_collide_exact(P, A, tc);
+}
+
+// verdict of row b = OR over the selected shapes s and the points i of the pair predicate for (s, sphere of the cloud's radius at
+// p_i): tc = (thr + margin_s) + radius; bounding spheres |cA - p|^2 >= ((tc + rhoA) + 0)^2 or a non-positive sum => free; else the exact
+// test with the cores in canonical order (cloud_collides; the point first: a point-point pair computes the same bits either way).
+// A workgroup owns one mask word, so the word and the bytes have one writer each.
+__global__ __launch_bounds__(64) void k_cloud_validity(DevModel m, CloudDev cd, CloudSel sel, const double* __restrict__ q, int64_t B,
+                                                       double thr, int accumulate, unsigned long long* __restrict__ mask_bits,
+                                                       uint8_t* __restrict__ mask_bytes) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    double* myq = lds + lane * m.n_q;
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool hit = false;
+    if (active) hit = !cloud_stage_q(q, b, m.n_q, myq) || status != 0;
+    if (n > 0 && status == 0) {
+        Core P;
+        cloud_point_core(radius, P);
+        Xf T;
+        int cur_frame = -2;
+        for (int s = 0; s < m.n_rshapes; ++s) {
+            if (!cloud_selected(sel, s)) continue;
+            const bool work = active && !hit;
+            if (__builtin_amdgcn_ballot_w64(work) == 0ull) break;
+            Core A;
+            cloud_core_init(A);
+            double tc = 0.0, rs = 0.0;
+            if (work) {
+                // (a lane that drops out keeps a stale frame and never comes back)
+                if (m.rs_frame[s] != cur_frame) cloud_shape_frame(m, s, myq, T);
+                build_core(m, s, T, A);
+                if (A.kind == K_HULL) A.rad = -1.0;          // every working lane holds this hull: its vertices go through the scalar cache
+                tc = (thr + A.margin) + radius;
+                rs = (tc + A.rho) + 0.0;
+            }
+            cur_frame = m.rs_frame[s];
+            CloudWalk w;
+            cloud_walk_begin(cd, work, A.c, rs, w);
+            const double rs2 = rs * rs;
+            while (true) {
+                // each lane runs ahead to its next point that passes the bounding spheres (a short loop: three loads, one
+                // comparison), then the lanes that hold one decide theirs side by side: the exact test is the long part, and inline
+                // in the walk it would run for one lane's candidate at a time
+                bool cand = false;
+                while (!hit && !cand && cloud_walk_next(cd, w)) {
+                    const double* p = cd.pts + 3 * (size_t)w.cur;
+                    ++w.cur;
+                    P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+                    double dc[3];
+                    sub3(A.c, P.c, dc);
+                    cand = dot3(dc, dc) < rs2;
+                }
+                if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+                if (cand && cloud_collides(P, A, tc)) hit = true;
+            }
+        }
+    }
+    const unsigned long long word = __builtin_amdgcn_ballot_w64(active && hit);
+    if (mask_bits != nullptr && lane == 0) {
+        if (accumulate) { if (word != 0ull) mask_bits[blockIdx.x] |= word; }
+        else mask_bits[blockIdx.x] = word;
+    }
+    if (mask_bytes != nullptr && active) {
+        if (!accumulate) mask_bytes[b] = hit ? 1 : 0;
+        else if (hit) mask_bytes[b] = 1;
+    }
+}
+
+// ---- clearance ----------------------------------------------------------------------------------------------------------------
+// per row the minimum over the selected (s, i) of the signed distance (cores_distance, EPA's depth where a point lies inside a hull
+// core), reported when it is < d_max with the shape (caller's index) and the original point index; ties go to the smallest shape, then
+// to the smallest point index, whatever order the walk meets them in.  d >= |cA - p| - rhoA - margin_s - radius, so only points with
+// |cA - p| < ((D + margin_s) + radius) + rhoA can reach below D: the walk covers that ball for D = d_max, and the running best shrinks
+// the ball a candidate must lie in before its distance is evaluated.  Both radii are widened by 1e-6 relative + 1e-7: the bound holds
+// for exact distances, and the iterative ones (GJK to 1e-10, EPA to 1e-8 relative) must not lose a point to their last digits.
+NBK_DEV double cloud_search_radius(double D, const Core& A, double radius) {
+    const double R = ((D + A.margin) + radius) + A.rho;
+    return R + (1e-6 * __builtin_fabs(R) + 1e-7);
+}
+
+__global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd, CloudSel sel, const int* __restrict__ rs_user,
+                                                        const double* __restrict__ q, int64_t B, double d_max,
+                                                        double* __restrict__ out_d, int32_t* __restrict__ out_s, int32_t* __restrict__ out_p) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    double* myq = lds + lane * m.n_q;
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool ok = false;
+    if (active) ok = cloud_stage_q(q, b, m.n_q, myq) && status == 0;
+    double best = NBK_INF;
+    int bs = -1, bi = -1;
+    if (n > 0 && status == 0 && __builtin_amdgcn_ballot_w64(ok) != 0ull) {
+        Core P;
+        cloud_point_core(radius, P);
+        Xf T;
+        int cur_frame = -2;
+        for (int s = 0; s < m.n_rshapes; ++s) {
+            if (!cloud_selected(sel, s)) continue;
+            Core A;
+            cloud_core_init(A);
+            double R = 0.0;
+            const int su = rs_user[s];
+            if (ok) {
+                if (m.rs_frame[s] != cur_frame) cloud_shape_frame(m, s, myq, T);
+                build_core(m, s, T, A);
+                if (A.kind == K_HULL) A.rad = -1.0;
+                R = cloud_search_radius(best < d_max ? best : d_max, A, radius);
+            }
+            cur_frame = m.rs_frame[s];
+            CloudWalk w;
+            cloud_walk_begin(cd, ok, A.c, R, w);
+            double R2 = R * R;
+            while (true) {
+                // as in k_cloud_validity: run ahead to the next point inside the current ball, then evaluate side by side
+                bool cand = false;
+                int oi = -1;
+                while (!cand && R > 0.0 && cloud_walk_next(cd, w)) {
+                    const double* p = cd.pts + 3 * (size_t)w.cur;
+                    oi = cd.idx[w.cur];
+                    ++w.cur;
+                    P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+                    double dc[3];
+                    sub3(A.c, P.c, dc);
+                    cand = dot3(dc, dc) < R2;
+                }
+                if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+                if (cand) {
+                    double fam = -1.0;
+                    double d = cores_distance<false, true>(A, P, nullptr, &fam);
+                    if (fam >= 0.0) epa_refine<false>(A, P, fam, d, nullptr);
+                    if (d < d_max && (d < best || (d == best && (su < bs || (su == bs && oi < bi))))) {
+                        best = d; bs = su; bi = oi;
+                        R = cloud_search_radius(best, A, radius);
+                        R2 = R * R;
+                    }
+                }
+            }
+        }
+    }
+    if (active) {
+        out_d[b] = ok ? best : __builtin_nan("");
+        if (out_s != nullptr) out_s[b] = ok ? bs : -1;
+        if (out_p != nullptr) out_p[b] = ok ? bi : -1;
+    }
+}
+
+}  // namespace nbk
+
+struct nbk_cloud {
+    nbk::CloudGrid g;
+    int64_t capacity;
+    int cells;
+    int device;
+    void* blob;
+    nbk::CloudHdr* hdr;
+    unsigned* fill;
+    unsigned* start;
+    int* cell_of;
+    int* idx;
+    double* pts;
+    hipEvent_t updated;            // recorded after each update issued outside a capture: nbk_cloud_status waits for it (an event of
+    bool last_set;                 // the cloud's own, so a caller may destroy the stream of an update before asking for the status)
+};
+
+namespace nbk {
+
+static int32_t cloud_check_device(const nbk_cloud* c) {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != c->device) {
+        snprintf(g_err, sizeof(g_err), "cloud belongs to device %d, the current device is %d", c->device, dev);
+        return NBK_ERR_INVALID;
+    }
+    return NBK_OK;
+}
+
+static CloudDev cloud_dev(const nbk_cloud* c) { return CloudDev{c->g, c->hdr, c->pts, c->idx, c->start}; }
+
+// the caller's selection (bit s of shape_bits = robot shape s of the descriptor it passed to nbk_model_create) in device order
+static CloudSel cloud_selection(const nbk_model* m, const uint64_t* shape_bits) {
+    CloudSel sel{{0ull, 0ull, 0ull, 0ull}, shape_bits == nullptr ? 1 : 0};
+    if (shape_bits != nullptr)
+        for (size_t i = 0; i < m->h_rs_user.size(); ++i) {
+            const int u = m->h_rs_user[i];
+            if ((shape_bits[u >> 6] >> (u & 63)) & 1ull) sel.w[i >> 6] |= 1ull << (i & 63);
+        }
+    return sel;
+}
+
+}  // namespace nbk
+
+extern "C" {
+
+int32_t nbk_cloud_cells_host(const double lo[3], double cell, const int32_t dims[3], const double* pts, int64_t N, int32_t* cell_out) {
+    if (!cloud_grid_valid(lo, cell, dims) || N < 0 || (N > 0 && (pts == nullptr || cell_out == nullptr))) return NBK_ERR_INVALID;
+    const CloudGrid g{{lo[0], lo[1], lo[2]}, cell, {dims[0], dims[1], dims[2]}};
+    for (int64_t i = 0; i < N; ++i) cell_out[i] = cloud_cell(g, pts + 3 * i);
+    return NBK_OK;
+}
+
+int32_t nbk_cloud_create(int64_t capacity, const double lo[3], double cell, const int32_t dims[3], nbk_cloud** out) {
+    if (out == nullptr) return NBK_ERR_INVALID;
+    *out = nullptr;
+    if (capacity < 1 || capacity > CLOUD_MAX_POINTS || !cloud_grid_valid(lo, cell, dims)) return NBK_ERR_INVALID;
+    if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
+    std::unique_ptr<nbk_cloud> c(new nbk_cloud());
+    c->g = CloudGrid{{lo[0], lo[1], lo[2]}, cell, {dims[0], dims[1], dims[2]}};
+    c->capacity = capacity;
+    c->cells = dims[0] * dims[1] * dims[2];
+    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+    const size_t o_fill = sizeof(CloudHdr);
+    const size_t o_start = up(o_fill + sizeof(unsigned) * (size_t)c->cells);
+    const size_t o_cell = up(o_start + sizeof(unsigned) * ((size_t)c->cells + 1));
+    const size_t o_idx = up(o_cell + sizeof(int) * (size_t)capacity);
+    const size_t o_pts = up(o_idx + sizeof(int) * (size_t)capacity);
+    const size_t bytes = o_pts + sizeof(double) * 3 * (size_t)capacity;
+    hipError_t e = hipMalloc(&c->blob, bytes);
+    if (e != hipSuccess) { hip_fail(e, "hipMalloc(cloud)"); return NBK_ERR_ALLOC; }
+    char* base = static_cast<char*>(c->blob);
+    c->hdr = reinterpret_cast<CloudHdr*>(base);
+    c->fill = reinterpret_cast<unsigned*>(base + o_fill);
+    c->start = reinterpret_cast<unsigned*>(base + o_start);
+    c->cell_of = reinterpret_cast<int*>(base + o_cell);
+    c->idx = reinterpret_cast<int*>(base + o_idx);
+    c->pts = reinterpret_cast<double*>(base + o_pts);
+    // an empty cloud until the first update: status 0, N 0, every cell empty
+    e = hipMemset(c->blob, 0, o_cell);
+    if (e != hipSuccess) { (void)hipFree(c->blob); return hip_fail(e, "hipMemset(cloud)"); }
+    e = hipEventCreateWithFlags(&c->updated, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipFree(c->blob); return hip_fail(e, "hipEventCreate(cloud)"); }
+    (void)hipGetDevice(&c->device);
+    c->last_set = false;
+    *out = c.release();
+    return NBK_OK;
+}
+
+void nbk_cloud_destroy(nbk_cloud* c) {
+    if (c == nullptr) return;
+    if (c->blob) (void)hipFree(c->blob);
+    (void)hipEventDestroy(c->updated);
+    delete c;
+}
+
+int32_t nbk_cloud_set_points(nbk_cloud* c, const double* pts, int64_t N, double radius, void* stream) {
+    if (c == nullptr || N < 0 || N > c->capacity || !(radius >= 0.0) || (N > 0 && pts == nullptr)) return NBK_ERR_INVALID;
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    NBK_HIP(hipMemsetAsync(c->hdr, 0, sizeof(CloudHdr) + sizeof(unsigned) * (size_t)c->cells, st));
+    const unsigned blocks = (unsigned)((N + 255) / 256);
+    if (N > 0) {
+        hipLaunchKernelGGL(k_cloud_count, dim3(blocks), dim3(256), 0, st, c->g, pts, (int)N, c->cell_of, c->fill, &c->hdr->status);
+        NBK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, c->fill, c->start, c->cells, c->hdr, (int)N, radius);
+    NBK_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(k_cloud_scatter, dim3(blocks), dim3(256), 0, st, pts, (int)N, (const int*)c->cell_of, c->fill, c->pts, c->idx,
+                           (unsigned)c->capacity);
+        NBK_HIP(hipGetLastError());
+    }
+    if (!stream_capturing(st)) { NBK_HIP(hipEventRecord(c->updated, st)); c->last_set = true; }
+    return NBK_OK;
+}
+
+int32_t nbk_cloud_status(const nbk_cloud* c, int32_t* status) {
+    if (c == nullptr || status == nullptr) return NBK_ERR_INVALID;
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    if (c->last_set) NBK_HIP(hipEventSynchronize(c->updated));
+    int v = 0;
+    NBK_HIP(hipMemcpy(&v, &c->hdr->status, sizeof(int), hipMemcpyDeviceToHost));
+    *status = v;
+    return NBK_OK;
+}
+
+int32_t nbk_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* q, int64_t B, double threshold,
+                                 const uint64_t* shape_bits, int32_t accumulate, uint64_t* mask_bits, uint8_t* mask_bytes, void* stream) {
+    if (m == nullptr || c == nullptr || B < 0 || (B > 0 && (q == nullptr || (mask_bits == nullptr && mask_bytes == nullptr)))) return NBK_ERR_INVALID;
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    if (B == 0) return NBK_OK;
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_cloud_validity, dim3(blocks_for(B)), dim3(WAVE), sizeof(double) * WAVE * (size_t)m->n_q, (hipStream_t)stream, m->d,
+                       cloud_dev(c), cloud_selection(m, shape_bits), q, B, threshold, (int)accumulate,
+                       reinterpret_cast<unsigned long long*>(mask_bits), mask_bytes);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_cloud_clearance_batch(const nbk_model* m, const nbk_cloud* c, const double* q, int64_t B, double d_max,
+                                  const uint64_t* shape_bits, double* min_dist, int32_t* shape, int32_t* point, void* stream) {
+    if (m == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0) || (B > 0 && (q == nullptr || min_dist == nullptr))) return NBK_ERR_INVALID;
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    if (B == 0) return NBK_OK;
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), sizeof(double) * WAVE * (size_t)m->n_q, (hipStream_t)stream, m->d,
+                       cloud_dev(c), cloud_selection(m, shape_bits), m->rs_user, q, B, d_max, min_dist, shape, point);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+}  // extern "C"

@@ -428,6 +428,64 @@ class DeviceModel:
                                                self._stream()), "nbk_closest_batch")
         return qs.out(d), qs.out(idx)
 
+    # ---- point-cloud obstacles (physics/pointcloud.py) -------------------------------------------------
+    def _shape_bits(self, shapes):
+        """``shapes``: None (every robot shape) or an iterable of robot shape indices (``SceneModel`` order) -> host words."""
+        if shapes is None:
+            return None
+        if self.scene is None:
+            raise ValueError("a shape selection needs a SceneModel")
+        S = self.scene.n_rshapes
+        words = np.zeros((max((S + 63) // 64, 1),), dtype=np.uint64)
+        for s in shapes:
+            s = int(s)
+            if not 0 <= s < S:
+                raise ValueError(f"robot shape {s} out of range (0..{S - 1})")
+            words[s >> 6] |= np.uint64(1) << np.uint64(s & 63)
+        return words
+
+    def cloud_validity(self, cloud, q, threshold=0.0, packed=False, shapes=None, out=None):
+        """In-collision flags of q against ``cloud`` ALONE (a ``PointCloud``): this descriptor's own pairs and world shapes play no
+        part.  Bit for bit the verdict of a descriptor that holds the cloud's points as sphere world shapes paired with the selected
+        robot shapes.  ``shapes``: robot shape indices to check (default: all).  ``out``: a CUDA mask of the form ``validity``
+        returns for this ``packed`` (uint8 / bool (B,), or int64 words) to OR the verdicts INTO -- ``validity`` then
+        ``cloud_validity(..., out=mask)`` gives full validity; it is returned.  Without ``out`` the result is as ``validity``'s."""
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        bits = self._shape_bits(shapes)
+        if out is not None:
+            want = ((qs.B + 63) // 64,) if packed else (qs.B,)
+            if not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == want
+                    and (out.dtype == torch.int64 if packed else out.dtype in (torch.uint8, torch.bool))):
+                raise ValueError(f"out must be a contiguous CUDA tensor of shape {want} ({'int64' if packed else 'uint8 / bool'})")
+            words, mask = (out, None) if packed else (None, out)
+        elif packed:
+            words, mask = torch.empty(((qs.B + 63) // 64,), dtype=torch.int64, device=qs.device), None
+        else:
+            words, mask = None, torch.empty((qs.B,), dtype=torch.uint8, device=qs.device)
+        _lib.check(self._lib.nbk_cloud_validity_batch(
+            self._h, cloud._h, qs.t.data_ptr(), qs.B, float(threshold), None if bits is None else bits.ctypes.data,
+            0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
+            self._stream()), "nbk_cloud_validity_batch")
+        if out is not None:
+            return out
+        return qs.out(words) if packed else qs.out(mask.bool())
+
+    def cloud_clearance(self, cloud, q, d_max, shapes=None):
+        """Per configuration the smallest signed distance to ``cloud`` over the selected robot shapes when it is below ``d_max``
+        -> (distance (B,), robot shape (B,) int32, point index (B,) int32); +inf, -1, -1 where nothing is closer than ``d_max``;
+        NaN, -1, -1 for a non-finite configuration or while the cloud's status is set.  Ties: smallest shape, then smallest point."""
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        bits = self._shape_bits(shapes)
+        d = torch.empty((qs.B,), dtype=torch.float64, device=qs.device)
+        sh = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
+        pt = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
+        _lib.check(self._lib.nbk_cloud_clearance_batch(
+            self._h, cloud._h, qs.t.data_ptr(), qs.B, float(d_max), None if bits is None else bits.ctypes.data,
+            d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._stream()), "nbk_cloud_clearance_batch")
+        return qs.out(d), qs.out(sh), qs.out(pt)
+
     def pair_distances(self, q, witness=False):
         torch = _require_gpu()
         qs = _Staged(q, self.n_q)

@@ -551,6 +551,46 @@ class Arm(Robot):
         mask = dev.validity(q.reshape(-1, self.dof), threshold)
         return mask.reshape(tuple(q.shape[:-1]))
 
+    # ---- point-cloud obstacles ---------------------------------------------------------------------------
+    def _cloud_shapes(self, sm, ignore_links):
+        """Robot shape indices of ``sm`` without the shapes of ``ignore_links`` (Link objects or link names); None = all."""
+        names = {getattr(l, "_name", l) for l in ignore_links}
+        if not names:
+            return None
+        known = {l._name for l in sm.links}
+        for n in names:
+            if n not in known:
+                raise ValueError(f"Link {n} not found in chain")
+        return [s for s in range(sm.n_rshapes) if sm.links[sm.rshape_link[s]]._name not in names]
+
+    def in_collision_with_cloud(self, q, cloud, threshold: float = 0.0, ignore_links=()):
+        """Is the arm closer than ``threshold`` to a point of ``cloud`` (``numbotics_amd.physics.PointCloud``: every point a sphere
+        of the cloud's radius)?  ``(dof,)`` -> bool, ``(..., dof)`` -> bool array / tensor, like ``in_collision``.  This is the
+        cloud's verdict ONLY -- self-collision and the world's objects are ``in_collision``'s; full validity is
+        ``arm.in_collision(q) | arm.in_collision_with_cloud(q, cloud)``.  ``ignore_links``: links (or their names) whose shapes are
+        left out, e.g. the base standing on a scanned table."""
+        if q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        sm, dev = self._scene_device()
+        shapes = self._cloud_shapes(sm, ignore_links)
+        if q.ndim == 1:
+            return bool(dev.cloud_validity(cloud, q.reshape(1, -1), threshold, shapes=shapes)[0])
+        mask = dev.cloud_validity(cloud, q.reshape(-1, self.dof), threshold, shapes=shapes)
+        return mask.reshape(tuple(q.shape[:-1]))
+
+    def cloud_clearance(self, q, cloud, d_max: float, ignore_links=()):
+        """(distance, link name, point index) per configuration: the smallest signed distance between a link shape and a point of
+        ``cloud`` when it is below ``d_max`` (else inf, None, -1; NaN, None, -1 for a non-finite configuration).  ``q`` is
+        ``(dof,)`` or ``(B, dof)``; distances and point indices come back as arrays (or tensors, for a tensor ``q``), the link
+        names as an object array."""
+        if q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        sm, dev = self._scene_device()
+        d, sh, pt = dev.cloud_clearance(cloud, q.reshape(-1, self.dof), d_max, shapes=self._cloud_shapes(sm, ignore_links))
+        shn = sh.cpu().numpy() if _is_tensor(sh) else sh
+        names = np.array([sm.links[sm.rshape_link[s]]._name if s >= 0 else None for s in shn], dtype=object)
+        return d, names, pt
+
     def pair_distances(self, q):
         """(B, P) signed distances of every allowed primitive pair (additive, batched ``collisions``)."""
         sm, dev = self._scene_device()
