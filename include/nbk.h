@@ -483,6 +483,41 @@ int32_t nbk_cloud_cells_host(const double lo[3], double cell, const int32_t dims
                              int32_t *cell_out);                 /* no GPU: the same routine, for tests */
 
 /*
+ * Sampled straight-line edges against a cloud: nbk_edge_validity_batch's edges, nbk_cloud_validity_batch's verdict per sample -- what
+ * a planner's connector asks about a scan.  The samples are generated on the device and never written down as q rows.
+ *   starts, goals (device) [E][n_q]; dist (device, optional) [E]; the edge rule is nbk_edge_validity_batch's, word for word:
+ *   d = dist[e] or the fma-accumulated norm; degenerate when !(d > 2^-23 && d <= DBL_MAX); T_f = max_distance / d when steering
+ *   further than max_distance, else 1; step = resolution / d, n = ceil(T_f / step); samples t_i = i * step for i < n and t_n = T_f;
+ *   q = (1 - t) * s + t * g in three separately rounded operations per joint.  end (optional) [E][n_q] and n_samples (optional) [E]
+ *   get the bits that function writes: NaN / 0 for the degenerate edge, the goal or traj(T_f) and n + 1 otherwise.
+ *   valid [E] uint8 = 1 iff the edge is not degenerate and no sample's nbk_cloud_validity_batch verdict (same cloud, threshold and
+ *   shape_bits: NULL = every robot shape, a selection needs S <= 256) is 1 -- bit for bit what a descriptor reports through
+ *   nbk_edge_validity_batch when it holds the points as sphere world shapes paired with the selected robot shapes.  A non-finite
+ *   sample collides; a set cloud status makes every non-degenerate edge invalid; an empty cloud or an empty selection leaves every
+ *   non-degenerate edge valid.  (An edge of 2^32 samples or more is reported invalid.)
+ *   accumulate != 0: valid is only ever lowered -- an entry that is 0 on entry stays 0 and its samples are not looked at (the fast
+ *   path after the scene has rejected the edge), a non-zero entry ends as 1 or 0 by the rule above: nbk_edge_validity_batch followed
+ *   by this call on the same `valid` is full edge validity.  accumulate == 0 overwrites.
+ *   workspace: caller-owned device memory of at least nbk_edge_cloud_workspace_bytes(E) bytes (no GPU needed; < 0 for E < 0), 64-byte
+ *   aligned: the plan, the counts and the offsets, 40 bytes per edge whatever the sample count.  The descriptor's per-stream
+ *   scratch is not touched.
+ * Asynchronous, no allocation, no host synchronisation, capturable for every descriptor (nothing is parked in LDS beyond the staged
+ * q rows): four kernels on `stream` -- plan, scan, the initial valid, then one sample per lane, flat across the edges, over a grid
+ * sized from the static bound E * (ceil(max_distance / resolution) + 2); a batch with more samples than that is served completely
+ * by the same kernel's stride (the host never learns the count).
+ * NBK_ERR_INVALID -- before any device is looked for -- for null m / c, E < 0, null starts / goals / valid / workspace with E > 0,
+ * !(resolution > 0), !(max_distance > 0), a mode other than connect / steer, a NaN threshold, a workspace that is too small or
+ * misaligned.  E = 0 returns NBK_OK at once.  NBK_ERR_UNSUPPORTED for E > 2^31 - 1 and for a selection with S > 256.  The
+ * descriptor's and the cloud's device must be current.
+ */
+int64_t nbk_edge_cloud_workspace_bytes(int64_t E);
+int32_t nbk_edge_cloud_validity_batch(const nbk_model *m, const nbk_cloud *c, const double *starts, const double *goals,
+                                      const double *dist /* optional */, int64_t E, double resolution, double max_distance,
+                                      int32_t mode, double threshold, const uint64_t *shape_bits /* host, optional */,
+                                      int32_t accumulate, uint8_t *valid, double *end /* optional */,
+                                      int32_t *n_samples /* optional */, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

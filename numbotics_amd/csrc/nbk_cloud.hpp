@@ -18,6 +18,10 @@
 // the hull a core names are wave-uniform this way), replays FK along the shape's joint mask from the lane's staged q row, builds the
 // shape's core and walks the cells cloud_cell_range gives for the ball the pair predicate's bounding-sphere step can pass.  Cells are
 // numbered x fastest, so one (y, z) row of the range is one contiguous run of sorted points.
+//
+// Sampled edges (nbk_edge_cloud_validity_batch): the edge rule is nbk.hip's own (k_edge_plan, k_scan, edge_sample_row); the samples of
+// all edges form one flat range that k_cloud_edges walks one sample per lane with the walk of k_cloud_validity (cloud_row_hits).  Plan,
+// counts and offsets live in the caller's workspace (EdgeCloudLayout).
 #pragma once
 #define NBK_GRID_FN __host__ __device__ inline
 #include "nbk_cloud_grid.hpp"
@@ -171,10 +175,58 @@ NBK_DEV bool cloud_collides(const Core& P, const Core& A, double tc) {
     return cores_collide_exact(P, A, tc);
 }
 
-// verdict of row b = OR over the selected shapes s and the points i of the pair predicate for (s, sphere of the cloud's radius at
-// p_i): tc = (thr + margin_s) + radius; bounding spheres |cA - p|^2 >= ((tc + rhoA) + 0)^2 or a non-positive sum => free; else the exact
-// test with the cores in canonical order (cloud_collides; the point first: a point-point pair computes the same bits either way).
-// A workgroup owns one mask word, so the word and the bytes have one writer each.
+// The walk: does the lane's staged row `myq` touch the cloud?  OR over the selected shapes s and the points i of the pair predicate
+// for (s, sphere of the cloud's radius at p_i): tc = (thr + margin_s) + radius; bounding spheres |cA - p|^2 >= ((tc + rhoA) + 0)^2 or a
+// non-positive sum => free; else the exact test with the cores in canonical order (cloud_collides; the point first: a point-point pair
+// computes the same bits either way).  Called by every lane of the wave (`active`: this lane has a row; `hit`: its verdict so far,
+// raised here -- a lane that comes in with a hit, or without a row, only keeps the ballots company); the caller has checked that
+// the cloud holds points and that its status is clear.
+NBK_DEV void cloud_row_hits(const DevModel& m, const CloudDev& cd, const CloudSel& sel, double radius, double thr, const double* myq,
+                            bool active, bool& hit) {
+    Core P;
+    cloud_point_core(radius, P);
+    Xf T;
+    int cur_frame = -2;
+    for (int s = 0; s < m.n_rshapes; ++s) {
+        if (!cloud_selected(sel, s)) continue;
+        const bool work = active && !hit;
+        if (__builtin_amdgcn_ballot_w64(work) == 0ull) break;
+        Core A;
+        cloud_core_init(A);
+        double tc = 0.0, rs = 0.0;
+        if (work) {
+            // (a lane that drops out keeps a stale frame and never comes back)
+            if (m.rs_frame[s] != cur_frame) cloud_shape_frame(m, s, myq, T);
+            build_core(m, s, T, A);
+            if (A.kind == K_HULL) A.rad = -1.0;          // every working lane holds this hull: its vertices go through the scalar cache
+            tc = (thr + A.margin) + radius;
+            rs = (tc + A.rho) + 0.0;
+        }
+        cur_frame = m.rs_frame[s];
+        CloudWalk w;
+        cloud_walk_begin(cd, work, A.c, rs, w);
+        const double rs2 = rs * rs;
+        while (true) {
+            // each lane runs ahead to its next point that passes the bounding spheres (a short loop: three loads, one
+            // comparison), then the lanes that hold one decide theirs side by side: the exact test is the long part, and inline
+            // in the walk it would run for one lane's candidate at a time
+            bool cand = false;
+            while (!hit && !cand && cloud_walk_next(cd, w)) {
+                const double* p = cd.pts + 3 * (size_t)w.cur;
+                ++w.cur;
+                P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+                double dc[3];
+                sub3(A.c, P.c, dc);
+                cand = dot3(dc, dc) < rs2;
+            }
+            if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+            if (cand && cloud_collides(P, A, tc)) hit = true;
+        }
+    }
+}
+
+// verdict of row b = the walk's, or 1 for a non-finite row or a set status.  A workgroup owns one mask word, so the word and the
+// bytes have one writer each.
 __global__ __launch_bounds__(64) void k_cloud_validity(DevModel m, CloudDev cd, CloudSel sel, const double* __restrict__ q, int64_t B,
                                                        double thr, int accumulate, unsigned long long* __restrict__ mask_bits,
                                                        uint8_t* __restrict__ mask_bytes) {
@@ -188,48 +240,7 @@ __global__ __launch_bounds__(64) void k_cloud_validity(DevModel m, CloudDev cd, 
     const double radius = cd.hdr->radius;
     bool hit = false;
     if (active) hit = !cloud_stage_q(q, b, m.n_q, myq) || status != 0;
-    if (n > 0 && status == 0) {
-        Core P;
-        cloud_point_core(radius, P);
-        Xf T;
-        int cur_frame = -2;
-        for (int s = 0; s < m.n_rshapes; ++s) {
-            if (!cloud_selected(sel, s)) continue;
-            const bool work = active && !hit;
-            if (__builtin_amdgcn_ballot_w64(work) == 0ull) break;
-            Core A;
-            cloud_core_init(A);
-            double tc = 0.0, rs = 0.0;
-            if (work) {
-                // (a lane that drops out keeps a stale frame and never comes back)
-                if (m.rs_frame[s] != cur_frame) cloud_shape_frame(m, s, myq, T);
-                build_core(m, s, T, A);
-                if (A.kind == K_HULL) A.rad = -1.0;          // every working lane holds this hull: its vertices go through the scalar cache
-                tc = (thr + A.margin) + radius;
-                rs = (tc + A.rho) + 0.0;
-            }
-            cur_frame = m.rs_frame[s];
-            CloudWalk w;
-            cloud_walk_begin(cd, work, A.c, rs, w);
-            const double rs2 = rs * rs;
-            while (true) {
-                // each lane runs ahead to its next point that passes the bounding spheres (a short loop: three loads, one
-                // comparison), then the lanes that hold one decide theirs side by side: the exact test is the long part, and inline
-                // in the walk it would run for one lane's candidate at a time
-                bool cand = false;
-                while (!hit && !cand && cloud_walk_next(cd, w)) {
-                    const double* p = cd.pts + 3 * (size_t)w.cur;
-                    ++w.cur;
-                    P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
-                    double dc[3];
-                    sub3(A.c, P.c, dc);
-                    cand = dot3(dc, dc) < rs2;
-                }
-                if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
-                if (cand && cloud_collides(P, A, tc)) hit = true;
-            }
-        }
-    }
+    if (n > 0 && status == 0) cloud_row_hits(m, cd, sel, radius, thr, myq, active, hit);
     const unsigned long long word = __builtin_amdgcn_ballot_w64(active && hit);
     if (mask_bits != nullptr && lane == 0) {
         if (accumulate) { if (word != 0ull) mask_bits[blockIdx.x] |= word; }
@@ -238,6 +249,53 @@ __global__ __launch_bounds__(64) void k_cloud_validity(DevModel m, CloudDev cd, 
     if (mask_bytes != nullptr && active) {
         if (!accumulate) mask_bytes[b] = hit ? 1 : 0;
         else if (hit) mask_bytes[b] = 1;
+    }
+}
+
+// ---- sampled edges against the cloud (nbk_edge_cloud_validity_batch) -----------------------------------------------------------
+// valid[e] before the walk: an edge without samples (the degenerate edge) is invalid; accumulating, an entry only ever goes down.
+// An edge of 2^32 samples or more (its sample index no longer fits the packed (edge, sample) word of edge_t) is invalid as well.
+__global__ __launch_bounds__(256) void k_cloud_edges_init(const unsigned long long* __restrict__ cnt, int64_t E, int accumulate,
+                                                          uint8_t* __restrict__ valid) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const bool ok = cnt[e] != 0ull && cnt[e] <= 0xffffffffull;
+    valid[e] = (ok && (!accumulate || valid[e] != 0)) ? 1 : 0;
+}
+
+// One sample per lane, FLAT across the edges: sample f of [0, total) belongs to the largest edge e with offs[e] <= f (edges without
+// samples fall out by themselves) and is sample f - offs[e] of it, by the expression of the validity kernels (edge_sample_row).  The
+// grid covers the static bound edge_capacity; a workgroup strides over 64-sample blocks until `total` (read here, never by the host),
+// so a batch longer than the bound is served all the same.  valid[e] is an AND: a lane whose edge already reads 0 skips its sample,
+// a lane that finds a hit (or a non-finite sample, or a set status) stores 0 -- several lanes may store the same 0, in any order.
+__global__ __launch_bounds__(64) void k_cloud_edges(DevModel m, CloudDev cd, CloudSel sel, EdgeSrc es,
+                                                    const unsigned long long* __restrict__ offs, int64_t E, double thr, uint8_t* valid) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    double* myq = lds + lane * m.n_q;
+    const unsigned long long total = offs[E];
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * WAVE; base < total; base += (unsigned long long)gridDim.x * WAVE) {
+        const unsigned long long f = base + (unsigned long long)lane;
+        int64_t e = 0;
+        bool work = false;
+        if (f < total) {
+            int64_t hi = E;                                  // offs[e] <= f < offs[hi]
+            while (hi - e > 1) {
+                const int64_t mid = e + ((hi - e) >> 1);
+                if (offs[mid] <= f) e = mid; else hi = mid;
+            }
+            if (__hip_atomic_load(valid + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+                edge_sample_row(es, ((unsigned long long)e << 32) | (f - offs[e]), m.n_q, myq, 1);
+                work = !row_nonfinite(myq, m.n_q, 1) && status == 0;
+                if (!work) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        bool hit = false;
+        if (n > 0 && status == 0) cloud_row_hits(m, cd, sel, radius, thr, myq, work, hit);
+        if (hit) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -351,6 +409,14 @@ static int32_t cloud_check_device(const nbk_cloud* c) {
     }
     return NBK_OK;
 }
+
+// the workspace of nbk_edge_cloud_validity_batch: plan [E][3] double | cnt [E] | offs [E + 1], each part rounded up to 64 bytes
+struct EdgeCloudLayout {
+    size_t cnt, offs, bytes;
+    static size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
+    explicit EdgeCloudLayout(int64_t E) : cnt(r64((size_t)E * 24)), offs(cnt + r64((size_t)E * 8)), bytes(offs + r64(((size_t)E + 1) * 8)) {}
+};
+constexpr int64_t EDGE_CLOUD_MAX_E = int64_t(1) << 56;      // the layout's 40 bytes per edge stay far inside int64
 
 static CloudDev cloud_dev(const nbk_cloud* c) { return CloudDev{c->g, c->hdr, c->pts, c->idx, c->start}; }
 
@@ -475,6 +541,49 @@ int32_t nbk_cloud_clearance_batch(const nbk_model* m, const nbk_cloud* c, const 
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), sizeof(double) * WAVE * (size_t)m->n_q, (hipStream_t)stream, m->d,
                        cloud_dev(c), cloud_selection(m, shape_bits), m->rs_user, q, B, d_max, min_dist, shape, point);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_edge_cloud_workspace_bytes(int64_t E) {
+    if (E < 0 || E > EDGE_CLOUD_MAX_E) return -1;
+    return (int64_t)EdgeCloudLayout(E).bytes;
+}
+
+int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* starts, const double* goals, const double* dist,
+                                      int64_t E, double resolution, double max_distance, int32_t mode, double threshold,
+                                      const uint64_t* shape_bits, int32_t accumulate, uint8_t* valid, double* end, int32_t* n_samples,
+                                      void* workspace, int64_t workspace_bytes, void* stream) {
+    // (nothing below dereferences m or c before the argument rules are through: they are answered without a device)
+    if (m == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!(resolution > 0.0) || !(max_distance > 0.0) || (mode != NBK_CONNECT && mode != NBK_STEER) || threshold != threshold) return NBK_ERR_INVALID;
+    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
+        (workspace_bytes < (int64_t)EdgeCloudLayout(E).bytes || (reinterpret_cast<uintptr_t>(workspace) & 63) != 0)) return NBK_ERR_INVALID;
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    const EdgeCloudLayout L(E);
+    char* ws = static_cast<char*>(workspace);
+    double* plan = reinterpret_cast<double*>(ws);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(ws + L.cnt);
+    unsigned long long* offs = reinterpret_cast<unsigned long long*>(ws + L.offs);
+    const unsigned eblocks = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
+                       plan, cnt, end, n_samples);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_edges_init, dim3(eblocks), dim3(256), 0, st, cnt, E, (int)accumulate, valid);
+    NBK_HIP(hipGetLastError());
+    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
+    const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
+    hipLaunchKernelGGL(k_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
+                       sizeof(double) * WAVE * (size_t)m->n_q, st, m->d, cloud_dev(c), cloud_selection(m, shape_bits), es, offs, E, threshold,
+                       valid);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

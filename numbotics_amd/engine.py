@@ -549,8 +549,8 @@ class DeviceModel:
         _, w, j = self._launch_records(qs.t, qs.B, it, True, True)
         return qs.out(d), qs.out(idx), qs.out(w), qs.out(j)
 
-    def edge_validity(self, starts, goals, resolution, max_distance, mode="connect", threshold=0.0, dist=None):
-        torch = _require_gpu()
+    def _stage_edges(self, starts, goals, dist):
+        """The end points (and the optional lengths) of E edges on the device -> (starts, goals, dist or None), each ``_Staged``."""
         s = _Staged(starts, self.n_q)
         g = _Staged(goals, self.n_q)
         if s.B != g.B:
@@ -560,6 +560,11 @@ class DeviceModel:
             dd = _Staged(dist, 1)
             if dd.B != s.B:
                 raise ValueError("dist must have one value per edge")
+        return s, g, dd
+
+    def edge_validity(self, starts, goals, resolution, max_distance, mode="connect", threshold=0.0, dist=None):
+        torch = _require_gpu()
+        s, g, dd = self._stage_edges(starts, goals, dist)
         valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
         end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
         ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
@@ -569,19 +574,44 @@ class DeviceModel:
             valid.data_ptr(), end.data_ptr(), ns.data_ptr(), self._stream()), "nbk_edge_validity_batch")
         return s.out(valid.bool()), s.out(end), s.out(ns)
 
+    @staticmethod
+    def cloud_edge_workspace_bytes(E: int) -> int:
+        return int(_lib.load().nbk_edge_cloud_workspace_bytes(int(E)))
+
+    def cloud_edge_validity(self, cloud, starts, goals, resolution, max_distance, mode="connect", threshold=0.0, dist=None, shapes=None,
+                            out=None, workspace=None):
+        """``edge_validity``'s edges against ``cloud`` ALONE (a ``PointCloud``): an edge is valid when it is not degenerate and
+        ``cloud_validity`` clears every one of its samples (generated on the device, never stored) -> (valid (E,) bool, end (E, n_q),
+        n_samples (E,) int32), ``end`` and ``n_samples`` bit for bit ``edge_validity``'s.  ``shapes``: as ``cloud_validity``.
+        ``out``: a contiguous CUDA uint8 / bool (E,) tensor to AND the verdicts INTO -- entries that are already 0 stay 0 and cost
+        nothing, so ``edge_validity`` then ``cloud_edge_validity(..., out=valid)`` is full edge validity; it is returned as the
+        first element.  ``workspace``: optional torch uint8 CUDA tensor of at least ``cloud_edge_workspace_bytes(E)`` bytes; by
+        default one is taken from torch's caching allocator (inside a graph capture: from the capture's pool)."""
+        torch = _require_gpu()
+        s, g, dd = self._stage_edges(starts, goals, dist)
+        bits = self._shape_bits(shapes)
+        if out is None:
+            valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
+        else:
+            if not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (s.B,)
+                    and out.dtype in (torch.uint8, torch.bool)):
+                raise ValueError(f"out must be a contiguous CUDA tensor of shape {(s.B,)} (uint8 / bool)")
+            valid = out
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
+        ws = torch.empty((self.cloud_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device) if workspace is None else workspace
+        _lib.check(self._lib.nbk_edge_cloud_validity_batch(
+            self._h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
+            float(max_distance), 0 if mode == "connect" else 1, float(threshold), None if bits is None else bits.ctypes.data,
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            self._stream()), "nbk_edge_cloud_validity_batch")
+        return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
+
     def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
         """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
         valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``)."""
         torch = _require_gpu()
-        s = _Staged(starts, self.n_q)
-        g = _Staged(goals, self.n_q)
-        if s.B != g.B:
-            raise ValueError("starts and goals must have the same number of rows")
-        dd = None
-        if dist is not None:
-            dd = _Staged(dist, 1)
-            if dd.B != s.B:
-                raise ValueError("dist must have one value per edge")
+        s, g, dd = self._stage_edges(starts, goals, dist)
         valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
         end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
         t_free = torch.empty((s.B,), dtype=torch.float64, device=s.device)

@@ -5,6 +5,9 @@ Additive: when the params carry an ``arm`` (instead of, or next to, a Python ``v
 whole edge -- every sample ``T = arange(0, T_f, res/d) U {T_f}`` -- is checked by ONE device launch,
 and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per wavefront).
 ``validate_trajectories`` / ``validate_trajectory`` check smoothed (clamped B-spline) trajectories sample by sample on the device.
+``ConnectorParams(cloud=...)`` (a ``PointCloud``, with an ``arm``) adds a scan to what the sampled edges and ``is_valid`` respect:
+the device path ANDs ``nbk_edge_cloud_validity_batch`` into the scene's verdict.  Smoothed trajectories and the certified continuous
+checks do not see point clouds yet: with a cloud set they refuse instead of ignoring it.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
 certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
 with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.  Its
@@ -32,6 +35,10 @@ class ConnectorParams:
     # additive: device-side validity = not arm.in_collision(q, collision_threshold)
     arm: object = None
     collision_threshold: float = 0.0
+    # additive: a PointCloud the arm must also stay clear of (at collision_threshold), without the shapes of cloud_ignore_links
+    # (Link objects or names, e.g. the base standing on a scanned table)
+    cloud: object = None
+    cloud_ignore_links: tuple = ()
 
     def __post_init__(self):
         if self.resolution <= 0:
@@ -44,6 +51,13 @@ class ConnectorParams:
             raise ValueError("Validity checker must be provided")
         if self.trajectory_func is None:
             raise ValueError("Trajectory conversion function must be provided")
+        if self.cloud is not None and self.arm is None:
+            raise ValueError("A point cloud needs ConnectorParams(arm=...)")
+
+
+def _no_cloud(params, what):
+    if params.cloud is not None:
+        raise ValueError(f"{what} do not see point clouds yet")
 
 
 class Connector(ABC):
@@ -107,13 +121,16 @@ class DiscreteConnector(Connector):
         p = self._params
         if p.validity_checker is not None:
             return p.validity_checker(state)
-        return not p.arm.in_collision(state, p.collision_threshold)
+        if p.cloud is None:
+            return not p.arm.in_collision(state, p.collision_threshold)
+        return not (p.arm.in_collision(state, p.collision_threshold)
+                    or p.arm.in_collision_with_cloud(state, p.cloud, p.collision_threshold, p.cloud_ignore_links))
 
     def _scalar(self, start, goal, mode, distance):
         """One edge, every sample in one device call (host arrays through the library's pinned staging)."""
         p = self._params
         _, dev = p.arm._scene_device()
-        if isinstance(start, np.ndarray) and isinstance(goal, np.ndarray):
+        if p.cloud is None and isinstance(start, np.ndarray) and isinstance(goal, np.ndarray):
             return dev.edge_validity_scalar(start, goal, p.resolution, p.max_distance, mode=mode,
                                             threshold=p.collision_threshold, dist=float(distance))
         ok, end, ns = self._batch(start[None], goal[None], mode, np.array([distance], dtype=np.float64))
@@ -126,9 +143,20 @@ class DiscreteConnector(Connector):
             raise ValueError("batched edge checks need ConnectorParams(arm=...)")
         if p.trajectory_func is not _DEFAULT_TRAJ:
             raise ValueError("batched edge checks support the default linear trajectory only")
-        _, dev = p.arm._scene_device()
-        return dev.edge_validity(starts, goals, p.resolution, p.max_distance, mode=mode,
-                                 threshold=p.collision_threshold, dist=dist)
+        sm, dev = p.arm._scene_device()
+        if p.cloud is None:
+            return dev.edge_validity(starts, goals, p.resolution, p.max_distance, mode=mode,
+                                     threshold=p.collision_threshold, dist=dist)
+        # the scene's verdict, then the cloud's ANDed into it on the device: edges the scene rejected cost the second call nothing
+        import torch
+        host = not torch.is_tensor(starts)
+        on_dev = lambda x: x if x is None or torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()  # noqa: E731
+        starts, goals, dist = on_dev(starts), on_dev(goals), on_dev(dist)
+        valid, end, ns = dev.edge_validity(starts, goals, p.resolution, p.max_distance, mode=mode,
+                                           threshold=p.collision_threshold, dist=dist)
+        dev.cloud_edge_validity(p.cloud, starts, goals, p.resolution, p.max_distance, mode=mode, threshold=p.collision_threshold,
+                                dist=dist, shapes=p.arm._cloud_shapes(sm, p.cloud_ignore_links), out=valid)
+        return (valid.cpu().numpy(), end.cpu().numpy(), ns.cpu().numpy()) if host else (valid, end, ns)
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -150,12 +178,14 @@ class DiscreteConnector(Connector):
         """S clamped B-splines of ``unit_bspline``'s knots, every one sampled at most ``resolution`` apart in joint space and checked
         on the device (``nbk_spline_validity_batch``): (S, n, dof) -> valid (S,) bool, t_hit (S,) (t of the first colliding
         sample, NaN when valid), n_samples (S,) int32.  NumPy in, NumPy out; device tensors stay on the device."""
+        _no_cloud(self._params, "sampled trajectory checks")
         shape = _shape(control_points)
         k = _spline_args(self._params, shape, degree)
         return self._spline_check(control_points, unit_knots(shape[1], k), k)
 
     def validate_trajectory(self, spline):
         """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit)."""
+        _no_cloud(self._params, "sampled trajectory checks")
         c, t, k = _spline_parts(self._params, spline)
         valid, t_hit, _ = self._spline_check(c[None], t, k)
         return bool(valid[0]), float(t_hit[0])
@@ -207,13 +237,16 @@ class ContinuousConnector(Connector):
     edge is rejected when a search succeeds.  That search is local and can miss a contact.
 
     ``validate_trajectories`` / ``validate_trajectory`` (``params.arm`` required) certify smoothed plans -- clamped B-splines of
-    degree 1-5 -- the same way on the device, across their knot spans (``nbk_spline_continuous_batch``)."""
+    degree 1-5 -- the same way on the device, across their knot spans (``nbk_spline_continuous_batch``).
+
+    Params that carry a ``cloud`` are refused: a certificate that ignores an obstacle would be worse than none."""
 
     def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6):
         if int(max_iter) < 1:
             raise ValueError("max_iter must be at least 1")
         if not slack >= 0.0:
             raise ValueError("slack must be non-negative")
+        _no_cloud(params, "certified continuous checks")
         self._params = params
         self.max_iter = int(max_iter)
         self.slack = float(slack)

@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--only update,validity,clearance,sweep,baseline] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -15,6 +15,12 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
     baseline    N = 1e3: nbk_validity_batch on a descriptor that holds the same points as sphere world shapes with the same pairs
                 (the only route without this entry), same process, same q, the windows of the two alternating; the two masks
                 must be equal
+    edges       DeviceModel.cloud_edge_validity at N = 1e3 and 1e5: E = 1e5 edges from the first configurations, up to 1.0 long, at
+                resolution 0.05 and 0.01, max_distance 1.0, connect mode (the lengths are passed as `dist`, so that the rows below
+                are the same samples).  Against it, windows alternating: cloud_validity on the same samples written out as q rows
+                ahead of time (what had to be done without this entry, less its costs of writing the rows and reducing the mask),
+                whose per-edge AND must equal `valid`.  Then, at N = 1e5, the connector's sequence on the c2 scene -- edge_validity,
+                then the cloud call ANDed into its result -- next to its two parts alone
 """
 import argparse
 import os
@@ -95,10 +101,76 @@ def fmt(t):
     return f"{t[0]:9.3f} ms (min {t[1]:.3f}, max {t[2]:.3f}; {t[3]} calls/window)"
 
 
+def edges(q, E, seed, length):
+    """E edges from the first rows of q: a random direction, a length drawn from U(0.02, length)."""
+    rng = np.random.default_rng(seed); s = q[:E].copy()
+    d = rng.standard_normal(s.shape); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return s, s + d * rng.uniform(0.02, length, (E, 1))
+
+
+def sample_rows(st, gt, d, resolution, ns):
+    """The samples of the connect-mode edges st -> gt of lengths d as q rows, by the rule of nbk_edge_validity_batch (step =
+    resolution / d, n = ceil(1 / step), t_i = i * step for i < n, t_n = 1; q in three roundings) -> rows, edge of each row."""
+    E = st.shape[0]
+    step = resolution / d
+    n = torch.ceil(1.0 / step).to(torch.int64)
+    assert torch.equal(n + 1, ns.to(torch.int64)), "the sample counts restated here differ from the library's"
+    offs = torch.cumsum(n + 1, 0) - (n + 1)
+    e_of = torch.repeat_interleave(torch.arange(E, device=st.device), n + 1)
+    i = torch.arange(e_of.shape[0], device=st.device) - offs[e_of]
+    t = torch.where(i < n[e_of], i.to(torch.float64) * step[e_of], torch.ones((), dtype=torch.float64, device=st.device))
+    a = (1.0 - t)[:, None] * st[e_of]
+    b = t[:, None] * gt[e_of]
+    return (a + b).contiguous(), e_of
+
+
+def edges_part(dev, sm, chain, shapes, reps):
+    E = 10 ** 5
+    s, g = edges(sample_q(chain, E, seed=1), E, 7, 1.0)
+    st, gt = torch.from_numpy(s).cuda(), torch.from_numpy(g).cuda()
+    d = torch.linalg.norm(gt - st, dim=1)
+    say(f"edges: E = {E}, lengths U(0.02, 1.0), max_distance 1.0, connect; workspace {dev.cloud_edge_workspace_bytes(E)} bytes")
+    for N in (10 ** 3, 10 ** 5):
+        cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), RADIUS, bounds=BOX)
+        for res in (0.05, 0.01):
+            call = lambda: dev.cloud_edge_validity(cloud, st, gt, res, 1.0, dist=d, shapes=shapes)      # noqa: E731
+            valid, _, ns = call()
+            total = int(ns.sum())
+            rows, e_of = sample_rows(st, gt, d, res, ns)
+            hit = dev.cloud_validity(cloud, rows, 0.0, shapes=shapes)
+            blocked = torch.zeros((E,), dtype=torch.bool, device="cuda")
+            blocked[e_of[hit]] = True
+            assert torch.equal(valid, ~blocked), "the per-edge AND of the rows' mask differs from cloud_edge_validity"
+            te, tr = timed_pair(call, lambda: dev.cloud_validity(cloud, rows, 0.0, packed=True, shapes=shapes), reps)
+            say(f"  N = {N:6d} resolution {res}: {total} samples, valid {float(valid.float().mean()):.3f}   edges {fmt(te)}  "
+                f"{total / te[0] / 1e6:.2f} G samples/s   rows written out ({rows.numel() * 8 / 1e6:.0f} MB) {fmt(tr)}   "
+                f"ratio {tr[0] / te[0]:.2f}x   verdicts equal")
+            del rows, e_of, hit
+    # the connector's sequence on the c2 scene (its cube rejects part of the edges before the cloud is asked)
+    N, res = 10 ** 5, 0.05
+    cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), RADIUS, bounds=BOX)
+
+    def scene():
+        return dev.edge_validity(st, gt, res, 1.0, dist=d)[0]
+
+    def both():
+        v = scene()
+        dev.cloud_edge_validity(cloud, st, gt, res, 1.0, dist=d, shapes=shapes, out=v)
+        return v
+    own, full = scene(), both()
+    alone = dev.cloud_edge_validity(cloud, st, gt, res, 1.0, dist=d, shapes=shapes)[0]
+    assert torch.equal(full, own & alone)
+    say(f"  N = {N:6d} resolution {res}, c2 scene: valid {float(own.float().mean()):.3f} after the scene, {float(full.float().mean()):.3f} after both")
+    say(f"    edge_validity                          {fmt(timed(scene, reps))}")
+    say(f"    cloud_edge_validity alone              {fmt(timed(lambda: dev.cloud_edge_validity(cloud, st, gt, res, 1.0, dist=d, shapes=shapes), reps))}")
+    say(f"    edge_validity, cloud_edge_validity(out) {fmt(timed(both, reps))}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default="update,validity,clearance,sweep,baseline")
+    ap.add_argument("--append", action="store_true", help="add to --out instead of starting it anew")
+    ap.add_argument("--only", default="update,validity,clearance,sweep,baseline,edges")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-n", type=int, default=10 ** 6)
     a = ap.parse_args()
@@ -106,7 +178,7 @@ def main():
     global OUT
     OUT = a.out
     if OUT:
-        open(OUT, "w").close()
+        open(OUT, "a" if a.append else "w").close()
     if not torch.cuda.is_available():
         raise SystemExit("cloud_time.py measures on the GPU: none visible")
     arm, chain, obs = build_scene("c2")
@@ -157,6 +229,8 @@ def main():
             tc, tb = timed_pair(lambda: dev.cloud_validity(cloud, q, 0.0, packed=True, shapes=shapes),
                                 lambda: base.validity(q, 0.0, packed=True), a.reps)
             say(f"  B = {name}: cloud {fmt(tc)}   sphere descriptor {fmt(tb)}   ratio {tb[0] / tc[0]:.2f}x   masks equal")
+    if "edges" in only:
+        edges_part(dev, sm, chain, shapes, a.reps)
 
 
 if __name__ == "__main__":
