@@ -177,11 +177,13 @@ int32_t nbk_world_reach_bounds_host(const nbk_model_desc *desc, const double *po
  *                           2 the specialised kernel, 3 another broadphase (float64 / LDS forms)
  *   nbk_broad_spec_source   (no GPU needed) the complete source the specialised kernel is compiled from for `desc`: its
  *                           length + 1, 0 when the robot does not take it, < 0 an error; up to cap - 1 bytes + NUL to buf
+ *   nbk_broad_spec_source_movable   the same for the descriptor nbk_model_create_movable(desc, world_radius) makes
  *   nbk_jit_compile         (no GPU needed) compile such a source for `arch` ("gfx950") the way the library does: the size of
  *                           the code object, or < 0 (nbk_last_error has the compiler's log)
  */
 int32_t nbk_broad_kernel_used(const nbk_model *m);
 int64_t nbk_broad_spec_source(const nbk_model_desc *desc, char *buf, int64_t cap);
+int64_t nbk_broad_spec_source_movable(const nbk_model_desc *desc, double world_radius, char *buf, int64_t cap);
 int64_t nbk_jit_compile(const char *src, const char *arch);
 
 /*

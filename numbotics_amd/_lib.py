@@ -27,7 +27,7 @@ SYMBOLS = [
     "nbk_fk_batch_host", "nbk_validity_batch_host", "nbk_knn_prefix",
     "nbk_validity_scalar_host", "nbk_edge_validity_scalar_host", "nbk_spline_validity_batch",
     "nbk_spline_continuous_batch", "nbk_spline_motion_bounds_host",
-    "nbk_broad_kernel_used", "nbk_broad_spec_source", "nbk_jit_compile",
+    "nbk_broad_kernel_used", "nbk_broad_spec_source", "nbk_broad_spec_source_movable", "nbk_jit_compile",
     "nbk_model_create_movable", "nbk_model_set_world_poses", "nbk_model_set_world_poses_host", "nbk_model_world_status",
     "nbk_world_reach_bounds_host",
     "nbk_cloud_create", "nbk_cloud_destroy", "nbk_cloud_set_points", "nbk_cloud_status", "nbk_cloud_validity_batch",

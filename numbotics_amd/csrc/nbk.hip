@@ -4016,9 +4016,18 @@ static int32_t bf32_compile(const std::string& src, const std::string& arch, std
     }
     const std::string arch_opt = "--offload-arch=" + arch;
     std::vector<const char*> opts = {arch_opt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off"};
-    // NBK_JIT_OPTIONS: one more hipRTC option (diagnostics and tests, e.g. -DNBK_SPEC_WAVES=6); part of the module's memo key
+    // NBK_JIT_OPTIONS: more hipRTC options, separated by blanks (diagnostics and tests, e.g. "-DNBK_SPEC_WAVES=6 -DNBK_SPEC_NO_QREG");
+    // part of the module's memo key
     const char* extra = getenv("NBK_JIT_OPTIONS");
-    if (extra != nullptr && *extra) opts.push_back(extra);
+    std::vector<std::string> extras;
+    if (extra != nullptr) {
+        std::string cur;
+        for (const char* c = extra; ; ++c) {
+            if (*c == ' ' || *c == '\0') { if (!cur.empty()) extras.push_back(cur); cur.clear(); if (*c == '\0') break; }
+            else cur.push_back(*c);
+        }
+    }
+    for (const std::string& e : extras) opts.push_back(e.c_str());
     const hiprtcResult cr = r.compile(prog, (int)opts.size(), opts.data());
     if (cr != HIPRTC_SUCCESS) {
         size_t n = 0;
@@ -4193,10 +4202,10 @@ int32_t nbk_model_create(const nbk_model_desc* d, nbk_model** out) {
     return model_create(d, nullptr, out);
 }
 
-int64_t nbk_broad_spec_source(const nbk_model_desc* d, char* buf, int64_t cap) {
+static int64_t spec_source(const nbk_model_desc* d, const double* world_radius, char* buf, int64_t cap) {
     { const int32_t rc = desc_check(d, D_ALL); if (rc != NBK_OK) return rc; }
     ModelTables t;
-    { const int32_t rc = compile_tables(d, nullptr, t); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = compile_tables(d, world_radius, t); if (rc != NBK_OK) return rc; }
     if (t.spec.empty()) return 0;
     const std::string src = bf32_source(t.spec);
     if (buf != nullptr && cap > 0) {
@@ -4205,6 +4214,11 @@ int64_t nbk_broad_spec_source(const nbk_model_desc* d, char* buf, int64_t cap) {
         buf[n] = '\0';
     }
     return (int64_t)src.size() + 1;
+}
+int64_t nbk_broad_spec_source(const nbk_model_desc* d, char* buf, int64_t cap) { return spec_source(d, nullptr, buf, cap); }
+int64_t nbk_broad_spec_source_movable(const nbk_model_desc* d, double world_radius, char* buf, int64_t cap) {
+    if (!(world_radius >= 0.0 && world_radius <= 1.7976931348623157e308)) return NBK_ERR_INVALID;
+    return spec_source(d, &world_radius, buf, cap);
 }
 
 int64_t nbk_jit_compile(const char* src, const char* arch) {

@@ -112,12 +112,19 @@ NBK_BF32_DEV void joint_apply_gen_p(const float* M, const float* toff, const flo
 //   candidate  dd < wkey2 (bounding spheres) and ex2 < cull2 (closer to the box than tc+ + rho + slack)
 //   certain hit, outside  candidate, ex2 > 0 and ex2 < cin (inside the ball inscribed in the shape, slack taken off)
 //   certain hit, inside   candidate, mx < 0, mx < -g (deeper than -tc + slack) and dd < kin
+// ALIGNED: the box's axes at wc[3..11] are exactly (1,0,0), (0,1,0), (0,0,1) and can never change (an immovable descriptor; the
+// generated Spec says so), and the projections are the differences themselves.  For finite differences that is the value of the
+// fma chain -- dx * 1 = dx, fma(dy, 0, dx) and fma(dz, 0, .) round to their addend -- up to the sign of a zero, which fabs
+// removes; a row with a non-finite q is `hit` before any slot.
+template <bool ALIGNED = false>
 NBK_BF32_DEV void box_slot2(V2f dx, V2f dy, V2f dz, const float* wc, const float* tb, V2i& cand, V2i& certh) {
     const V2f dd = fma2(dz, dz, fma2(dy, dy, dx * dx));
     V2f ex[3], ex2 = V2f{0.0f, 0.0f};
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        const V2f pj = fma2(dz, splat2(wc[5 + 3 * j]), fma2(dy, splat2(wc[4 + 3 * j]), dx * splat2(wc[3 + 3 * j])));
+        V2f pj;
+        if constexpr (ALIGNED) pj = j == 0 ? dx : (j == 1 ? dy : dz);
+        else pj = fma2(dz, splat2(wc[5 + 3 * j]), fma2(dy, splat2(wc[4 + 3 * j]), dx * splat2(wc[3 + 3 * j])));
         ex[j] = V2f{__builtin_fabsf(pj.x) - wc[12 + j], __builtin_fabsf(pj.y) - wc[12 + j]};
         const V2f cl = V2f{__builtin_fmaxf(ex[j].x, 0.0f), __builtin_fmaxf(ex[j].y, 0.0f)};
         ex2 = fma2(cl, cl, ex2);

@@ -17,6 +17,37 @@
 // the same statements inline (see the header for why).  What is here is the specialised control flow around them.  nbk.hip hands hipRTC the generated Spec, then nbk_bf32_common.hpp, then this file.  Self-contained for hipRTC:
 // no host headers, nothing beyond what hiprtc supplies.
 
+// Compile-time switches, reachable through NBK_JIT_OPTIONS (diagnostics; the product path defines none):
+//   NBK_SPEC_NO_ALIGNED, NBK_SPEC_NO_QREG   one of the two trims below off (same masks): the axis-aligned box slot, the q rows
+//       loaded straight into registers
+//   NBK_SPEC_DIAG_NO_WORLD, NBK_SPEC_DIAG_NO_RR, NBK_SPEC_DIAG_NO_ENQUEUE   the fast stage without its world blocks / its robot-robot
+//       rows / its queue appends: WRONG masks, for attributing instructions and time only (tools/spec_variant.sh)
+#ifdef NBK_SPEC_NO_ALIGNED
+#define NBK_SPEC_ALIGNED 0
+#else
+#define NBK_SPEC_ALIGNED 1
+#endif
+#ifdef NBK_SPEC_NO_QREG
+#define NBK_SPEC_QREG 0
+#else
+#define NBK_SPEC_QREG 1
+#endif
+#ifdef NBK_SPEC_DIAG_NO_WORLD
+#define NBK_SPEC_WORLD 0
+#else
+#define NBK_SPEC_WORLD 1
+#endif
+#ifdef NBK_SPEC_DIAG_NO_RR
+#define NBK_SPEC_RR 0
+#else
+#define NBK_SPEC_RR 1
+#endif
+#ifdef NBK_SPEC_DIAG_NO_ENQUEUE
+#define NBK_SPEC_ENQUEUE 0
+#else
+#define NBK_SPEC_ENQUEUE 1
+#endif
+
 #define NBK_SPEC_DEV __device__ __forceinline__
 #define NBK_SPEC_INLINE __attribute__((always_inline))      // every lambda of the kernel: its captures must stay registers
 
@@ -47,6 +78,7 @@ template <class Spec> struct SpecRoute {
 //   f_eps, f_reach, f_e2max                                                 the descriptor's slack constants
 //   rr_any; rpair(a, b) (a < b), rr_p(a, b): pair index of robot-robot slot (a, b), -1 = none
 //   wl[NW], wk[NW]: world shape and kind; wpair(i, a): pair index of (wl[i], a), -1 = none
+//   wbox_aligned[NW]: 1 = a box of a descriptor that cannot move whose axes at f_wc are exactly the coordinate axes
 //   cls_base[4], cls_groups[4]
 template <class Spec>
 NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, const float* __restrict__ ftb, const float* __restrict__ tab,
@@ -65,12 +97,25 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
     unsigned* lds_queue = reinterpret_cast<unsigned*>(lds_raw);
     if (base >= B) return;
     const int rows_i = (int)((B - base) < WAVE ? (B - base) : WAVE);
-    stage_plain_rows(q, base, rows_i, NQ, lds_raw, lane);
-    __syncthreads();
     const bool active = lane < rows_i;
+    // NQ <= 8: every lane loads its own row straight into registers, as k_fk<true> does (eight-byte loads at an 8 NQ-byte stride:
+    // the wave's NQ instructions hit the same lines); no LDS pass and no barrier before the sweep.  A lane past the batch takes
+    // row `base`, lane 0's: it is inactive, and its slack is lane 0's, so the wave's choice of stage is that of its real rows.
+    // Longer rows go through the LDS slab.
+    constexpr bool QREG = NBK_SPEC_QREG != 0 && NQ <= 8;
+    double qd[QREG ? NQ : 1];
+    if constexpr (QREG) {
+        const double* row = q + (base + (active ? lane : 0)) * NQ;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) qd[j] = row[j];
+    } else {
+        stage_plain_rows(q, base, rows_i, NQ, lds_raw, lane);
+        __syncthreads();
+    }
+    auto qat = [&](int j) NBK_SPEC_INLINE { if constexpr (QREG) return qd[j]; else return lds_raw[lane * NQ + j]; };
     int hit = 0;                // (an int: a bool captured by the lambdas below was kept in scratch, two bytes per lane)
 #pragma unroll
-    for (int j = 0; j < NQ; ++j) hit = hit || !(__builtin_fabs(lds_raw[lane * NQ + j]) <= 1.7976931348623157e308);
+    for (int j = 0; j < NQ; ++j) hit = hit || !(__builtin_fabs(qat(j)) <= 1.7976931348623157e308);
     // ---- chain sweep: every shape's centre in named registers ------------------------------------------------------------------
     float cxa[SB], cya[SB], cza[SB];
 #pragma unroll
@@ -78,7 +123,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
     float rmax = Spec::f_reach, qabs = 0.0f;
     float qv[J];
 #pragma unroll
-    for (int k = 0; k < J; ++k) { qv[k] = (float)lds_raw[lane * NQ + Spec::qcol[k]]; qabs += __builtin_fabsf(qv[k]); }
+    for (int k = 0; k < J; ++k) { qv[k] = (float)qat(Spec::qcol[k]); qabs += __builtin_fabsf(qv[k]); }
     XfP T;
     {
         const float* bp = ftb + Spec::f_base;
@@ -112,13 +157,15 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
         shapes(IC<k + 1>{});
     });
     const float e2 = 2.0f * rmax * __builtin_fmaf(2.4e-7f, qabs, Spec::f_eps);
-    __syncthreads();            // the q slab is dead from here on: its LDS region becomes the item queue
+    if constexpr (!QREG) __syncthreads();            // the q slab is dead from here on: its LDS region becomes the item queue
     int qn = 0;
     const SpecRoute<Spec> route{vp_cls};
     const float* wbx_all = tab + FO.wbx;
     if (__builtin_amdgcn_ballot_w64(!(e2 <= Spec::f_e2max)) == 0ull) {
         // ---- fast stage: world shapes -----------------------------------------------------------------------------------------
-        sfor<0, Spec::NW>([&](auto WI) NBK_SPEC_INLINE {
+        // (A group both of whose slots k_prepare_f32 left at the "never" defaults -- out of static reach at this threshold -- is
+        // computed all the same: a scalar branch around it took 16 VALU off the wave and added 54 SALU, for no time: DESIGN.md §6.)
+        sfor<0, NBK_SPEC_WORLD ? Spec::NW : 0>([&](auto WI) NBK_SPEC_INLINE {
             constexpr int wi = decltype(WI)::value;
             constexpr int w = Spec::wl[wi];
             constexpr int wk = Spec::wk[wi];
@@ -136,7 +183,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                         const V2f dy = V2f{cya[2 * i], cya[2 * i + 1]} - splat2(wc[1]);
                         const V2f dz = V2f{cza[2 * i], cza[2 * i + 1]} - splat2(wc[2]);
                         V2i cand, certh;
-                        if constexpr (wk == K_BOX) box_slot2(dx, dy, dz, wc, wb + 12 * i, cand, certh);
+                        if constexpr (wk == K_BOX) box_slot2<NBK_SPEC_ALIGNED != 0 && Spec::wbox_aligned[wi] != 0>(dx, dy, dz, wc, wb + 12 * i, cand, certh);
                         else hull_slot2(dx, dy, dz, wc, ob, wb + 12 * i, cand, certh);
                         cwv[2 * i] = cand.x; cwv[2 * i + 1] = cand.y;
                         acc_c |= cand.x | cand.y;
@@ -145,7 +192,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                 });
                 hit = hit || (acc_h < 0);
                 const bool live = active && !hit;
-                if (__builtin_amdgcn_ballot_w64(acc_c < 0 && live) != 0ull) {
+                if (NBK_SPEC_ENQUEUE && __builtin_amdgcn_ballot_w64(acc_c < 0 && live) != 0ull) {
                     queue_room(S * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
                     sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
                         constexpr int a = decltype(A)::value;
@@ -174,7 +221,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                 });
                 hit = hit || ch;
                 const bool live = active && !hit;
-                if (__builtin_amdgcn_ballot_w64(anyc && live) != 0ull) {
+                if (NBK_SPEC_ENQUEUE && __builtin_amdgcn_ballot_w64(anyc && live) != 0ull) {
                     queue_room(S * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
                     sfor<0, S>([&](auto A) NBK_SPEC_INLINE {
                         constexpr int a = decltype(A)::value;
@@ -184,7 +231,7 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
             }
         });
         // ---- fast stage: robot-robot rows, only the groups (2i, 2i + 1) that hold a pair of row a ------------------------------
-        if constexpr (Spec::rr_any) {
+        if constexpr (Spec::rr_any && NBK_SPEC_RR != 0) {
             sfor<0, S - 1>([&](auto A) NBK_SPEC_INLINE {
                 constexpr int a = decltype(A)::value;
                 if constexpr (Spec::row_slots(a) > 0) {
@@ -213,8 +260,8 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
                         });
                         hit = hit || (acc_f < 0);
                         const bool live = active && !hit;
-                        queue_room(Spec::row_slots(a) * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
-                        sfor<a + 1, S>([&](auto Bb) NBK_SPEC_INLINE {
+                        if (NBK_SPEC_ENQUEUE) queue_room(Spec::row_slots(a) * WAVE, qcap, route, lds_queue, qn, base, q_count, q_items, cap, lane, ovf);
+                        sfor<NBK_SPEC_ENQUEUE ? a + 1 : S, S>([&](auto Bb) NBK_SPEC_INLINE {
                             constexpr int b = decltype(Bb)::value;
                             if constexpr (Spec::rr_p(a, b) >= 0) {
                                 const V2i ei = __builtin_bit_cast(V2i, ev[b / 2]);

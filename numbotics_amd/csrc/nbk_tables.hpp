@@ -570,8 +570,9 @@ static void float_tables(const nbk_model_desc* d, const double* world_radius, Mo
 constexpr int SPEC_MAX_WORLD = 2;
 
 // The `struct Spec` of one descriptor ("" when the robot does not take the specialised kernel: not a serial chain of at most
-// 8 joints, more than 16 shapes, no pairs, too many world shapes)
-static std::string bf32_spec_text(const nbk_model_desc* d, const ModelTables& t) {
+// 8 joints, more than 16 shapes, no pairs, too many world shapes).  movable: the world cores at f_wc may be rewritten later
+// (k_world_update), so nothing about a world shape's pose is built in
+static std::string bf32_spec_text(const nbk_model_desc* d, const ModelTables& t, bool movable) {
     const int S = d->n_rshapes, J = d->n_joints, W = d->n_wshapes, P = d->n_pairs;
     if (!t.f_chain || P == 0 || S < 1 || S > 16 || J < 1 || J > 8) return std::string();
     std::vector<int> rrp((size_t)S * S, -1), wlist;
@@ -622,6 +623,15 @@ static std::string bf32_spec_text(const nbk_model_desc* d, const ModelTables& t)
     arr("wl", wlist);
     arr("wk", wk);
     arr("wp_", wp);
+    // a world BOX that can never move and whose axes (the nine floats behind its centre at f_wc) are exactly the coordinate
+    // axes: the kernel takes the centre differences as its axis projections (box_slot2<true>)
+    std::vector<int> aligned;
+    for (int w : wlist) {
+        bool id = !movable && t.ws_kind[w] == K_BOX;
+        for (int e = 0; e < 9 && id; ++e) id = t.ftab[t.f_wc + 18 * (size_t)w + 3 + e] == (e % 4 == 0 ? 1.0f : 0.0f);
+        aligned.push_back(id ? 1 : 0);
+    }
+    arr("wbox_aligned", aligned);
     arr("cls_base", std::vector<int>(t.cls_base, t.cls_base + 4));
     std::vector<int> groups(t.cls_groups, t.cls_groups + 4);
     for (int& g : groups) g = g > 0 ? g : 1;             // as DevModel::cls_groups: a divisor, also for a class without pairs
@@ -674,7 +684,7 @@ static int32_t compile_tables(const nbk_model_desc* d, const double* world_radiu
     { const int32_t rc = joint_tables(d, t); if (rc != NBK_OK) return rc; }
     queue_groups(d, t);
     float_tables(d, world_radius, t);
-    t.spec = bf32_spec_text(d, t);
+    t.spec = bf32_spec_text(d, t, world_radius != nullptr);
     hull_tables(d, t);
     return NBK_OK;
 }

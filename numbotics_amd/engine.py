@@ -155,6 +155,31 @@ def world_reach_bounds(model, poses=None):
     return out
 
 
+def broad_spec_source(model, movable=False, world_radius=None):
+    """The source the per-robot broadphase is compiled from for a SceneModel (bytes), or None when the robot does not take it;
+    ``movable`` / ``world_radius`` as for DeviceModel.  Runs on the host (nbk_broad_spec_source[_movable]); no GPU needed."""
+    lib = _lib.load()
+    d, keep = model_desc(model)
+    if movable:
+        if world_radius is None:
+            from numbotics_amd.robots.model import default_world_radius
+            world_radius = default_world_radius(model)
+        fn = lib.nbk_broad_spec_source_movable
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_double, C.c_char_p, C.c_int64], C.c_int64
+        call = lambda buf, cap: fn(C.byref(d), float(world_radius), buf, cap)
+    else:
+        call = lambda buf, cap: lib.nbk_broad_spec_source(C.byref(d), buf, cap)
+    n = call(None, 0)
+    if n < 0:
+        _lib.check(int(n), "nbk_broad_spec_source")
+    if n == 0:
+        return None
+    buf = C.create_string_buffer(int(n))
+    call(buf, n)
+    del keep
+    return buf.value
+
+
 class DeviceModel:
     """Device descriptor built from a KinematicModel or SceneModel (robots/model.py): immutable, or -- ``movable=True`` --
     immutable except for the poses of its world shapes, which ``set_world_poses`` rewrites on the device without rebuilding
