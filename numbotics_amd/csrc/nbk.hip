@@ -38,7 +38,7 @@ namespace nbk {
 // saturates at ~90 appends/us (MI355X_MICROARCH.md, row "dequeue"), which 15k waves would all hit.
 constexpr int NSUB = 256;
 }
-#include "nbk_plan.hpp"              // WsLayout, TilePlan, TableCache, EdgeLayout, SplineLayout: the host arithmetic of the validity launch path
+#include "nbk_plan.hpp"              // WsLayout, TilePlan, TableCache, the edge capacity rules, SplinePlan, Edge / EdgeCloud / SplineLayout: the host arithmetic of the launch paths
 static_assert(nbk::PLAN_WAVE == nbk::WAVE && nbk::PLAN_CNT_STRIDE == nbk::CNT_STRIDE && nbk::PLAN_NSUB == nbk::NSUB, "nbk_plan.hpp's stand-alone constants");
 
 namespace nbk {
@@ -144,28 +144,36 @@ NBK_DEV int64_t effective_batch(const EdgeSrc& es, int64_t B) {
 
 namespace nbk {
 // per-(descriptor, stream) scratch.  `tables`: what of the validity workspace the next call may reuse (TableCache, nbk_plan.hpp).
-// The edge path keeps plan / counts / offsets / sample map / mask words here, sized for a capacity in samples; `stats` is pinned
+// The edge path keeps plan / counts / offsets / sample map / mask words in `edge.buf` (EdgeLayout), sized for `edge.cap`; `stats` is pinned
 // host memory the device writes the true sample count into (read, never waited for, at the start of the NEXT call to grow the capacity).
+struct EdgeWs {
+    void* buf = nullptr; size_t bytes = 0;
+    EdgeCap cap;
+    unsigned long long* stats = nullptr;      // [4] pinned + mapped: samples needed by the last finished edge call, edges served by the overflow kernel
+    unsigned long long* stats_dev = nullptr;  // device alias of `stats`
+    unsigned long long word(int i) const { return stats ? __atomic_load_n(&stats[i], __ATOMIC_RELAXED) : 0ull; }      // read, not waited for; 0 before the first call
+    ~EdgeWs() { if (buf) (void)hipFree(buf);  if (stats) (void)hipHostFree(stats); }
+};
+// nbk_spline_validity_batch: knots | plan | counts | offsets (SplineLayout), mask words | q slab of one tile (SplinePlan)
+struct SplineWs {
+    void* small = nullptr; size_t small_bytes = 0;
+    void* large = nullptr; size_t large_bytes = 0;
+    ~SplineWs() { if (small) (void)hipFree(small);  if (large) (void)hipFree(large); }
+};
 struct StreamWs {
     hipStream_t stream = nullptr;
     std::mutex mu;                  // two host threads driving one stream (also makes the set non-copyable)
     void* ws = nullptr; size_t ws_bytes = 0;
     TableCache tables;
-    void* ews = nullptr; size_t ews_bytes = 0;
-    long long ecap_edges = 0; unsigned long long ecap_samples = 0;
-    unsigned long long* stats = nullptr;      // [4] pinned + mapped: samples needed by the last finished edge call, edges served by the overflow kernel
-    unsigned long long* stats_dev = nullptr;  // device alias of `stats`
-    // nbk_spline_validity_batch: knots | plan | counts | offsets (sps), mask words | q slab of one tile (spl)
-    void* sps = nullptr; size_t sps_bytes = 0;
-    void* spl = nullptr; size_t spl_bytes = 0;
+    EdgeWs edge;
+    SplineWs spline;
     // tile pipelining of batches of several tiles: odd tiles run on `aux_stream` with the scratch set `aux` (forked from / joined
     // to the caller's stream with events), so the latency-bound narrowphase of one tile overlaps the issue-bound broadphase of the next
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     StreamWs* aux = nullptr;        // another entry of the descriptor's list, freed as such: not owned here
     ~StreamWs() {
-        if (ws) (void)hipFree(ws);  if (ews) (void)hipFree(ews);  if (stats) (void)hipHostFree(stats);
-        if (sps) (void)hipFree(sps);  if (spl) (void)hipFree(spl);
+        if (ws) (void)hipFree(ws);
         if (ev_fork) (void)hipEventDestroy(ev_fork);  if (ev_join) (void)hipEventDestroy(ev_join);
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
     }
@@ -4886,13 +4894,22 @@ int32_t nbk_pair_records_items(const nbk_model* m, const double* q, int64_t B, c
     return guard_dists(m, (hipStream_t)stream, dist, N, witness, N * 9, jrows, N * m->n_q, nullptr, 0);
 }
 
+// The argument rules the edge entries share (sampled, certified continuous, against a point cloud): max_distance > 0 and the mode
+// always; what else an entry checks, it names -- the certified entry has no resolution, the sampled one takes a NaN threshold.
+enum EdgeRule : unsigned { RULE_RESOLUTION = 1u, RULE_THRESHOLD = 2u, RULE_CERTIFIED = 4u };      // resolution > 0 | threshold not NaN | max_iter >= 1, slack >= 0
+static bool edge_args_ok(unsigned rules, double resolution, double max_distance, int32_t mode, double threshold = 0.0, int32_t max_iter = 1, double slack = 0.0) {
+    if ((rules & RULE_RESOLUTION) && !(resolution > 0.0)) return false;
+    if (!(max_distance > 0.0) || (mode != NBK_CONNECT && mode != NBK_STEER)) return false;
+    if ((rules & RULE_CERTIFIED) && (max_iter < 1 || !(slack >= 0.0))) return false;
+    return !((rules & RULE_THRESHOLD) && threshold != threshold);
+}
+
 int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
                                   double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
                                   uint8_t* valid, double* end, double* t_free, int32_t* status, void* stream) {
     if (m == nullptr || E < 0 || (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)))
         return NBK_ERR_INVALID;
-    if (!(max_distance > 0.0) || (mode != NBK_CONNECT && mode != NBK_STEER) || max_iter < 1 || !(slack >= 0.0) || threshold != threshold)
-        return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     if (E == 0) return NBK_OK;
     const int64_t N = E * (int64_t)m->n_pairs;
@@ -4930,7 +4947,7 @@ int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* start
 
 static const int32_t SPLINE_MAX_CTRL = 65536;
 
-// the knot rules of both spline entries: finite, nondecreasing, clamped on [0, 1]
+// the knot rules of the spline entries: finite, nondecreasing, clamped on [0, 1]
 static bool spline_knots_ok(const double* knots, int n, int k) {
     for (int i = 0; i < n + k + 1; ++i)
         if (!(fabs(knots[i]) <= 1.7976931348623157e308) || (i > 0 && knots[i] < knots[i - 1])) return false;
@@ -4938,14 +4955,20 @@ static bool spline_knots_ok(const double* knots, int n, int k) {
     return true;
 }
 
+// The argument rules the spline entries share: degree, control count, and the knots where the host can read them (host_knots ==
+// nullptr: they are on the device, as for the certified entry, or the caller has not got to them yet)
+static bool spline_args_ok(int32_t n_ctrl, int32_t degree, const double* host_knots) {
+    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return false;
+    return host_knots == nullptr || spline_knots_ok(host_knots, n_ctrl, degree);
+}
+
 int32_t nbk_spline_motion_bounds_host(const nbk_model_desc* d, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                       const double* knots, double* mu) {
-    if (d == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
+    if (d == nullptr || S < 0 || !spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;
     { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
     const int P = d->n_pairs, nq = d->n_q, k = degree, L = n_ctrl - degree;
     if (S == 0 || P == 0) return NBK_OK;
-    if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_knots_ok(knots, n_ctrl, k)) return NBK_ERR_INVALID;
+    if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_args_ok(n_ctrl, degree, knots)) return NBK_ERR_INVALID;
     MotionHost h;
     motion_tables(d, frame_masks(d), h);
     const MotionTab t = h.view(d->n_joints, d->n_rshapes);
@@ -4961,18 +4984,52 @@ int32_t nbk_spline_motion_bounds_host(const nbk_model_desc* d, const double* ctr
     return NBK_OK;
 }
 
+// Size this stream's edge scratch for E edges and `cap` samples and bind it: the capture refusals, the pinned `stats`, the growth of the
+// scratch and of the validity workspace that serves its capacity (edge_scratch_fits / edge_scratch_grown, nbk_plan.hpp).  Answers the
+// typed view of the scratch and the capacity the launches cover: all of what is there.
+struct EdgeScratch { EdgeLayout::View v; unsigned long long cap; };
+static int32_t edge_scratch(const nbk_model* m, const PairCounts& pc, int64_t E, unsigned long long cap, OwnScratch& s, EdgeScratch& out) {
+    StreamWs* const w = s.w;
+    EdgeWs& e = w->edge;
+    // robots whose primitives do not fit the one-wave-per-edge kernel cannot serve overflowing edges: such descriptors
+    // keep a synchronous sizing step (one read-back) and cannot be captured
+    if (!m->parked_ok && s.capturing) { snprintf(g_err, sizeof(g_err), "graph capture of edge batches needs a robot that fits the LDS-parked layout"); return NBK_ERR_UNSUPPORTED; }
+    if (e.stats == nullptr || !edge_scratch_fits(m->pm, g_opt, pc, e.cap, w->ws_bytes, E, cap)) {
+        if (s.capturing) {
+            snprintf(g_err, sizeof(g_err), "graph capture: this stream's edge scratch is not allocated for %lld edges yet -- run the "
+                     "call once outside the capture", (long long)E);
+            return NBK_ERR_UNSUPPORTED;
+        }
+        if (e.stats == nullptr) {
+            NBK_HIP(hipHostMalloc((void**)&e.stats, 4 * sizeof(unsigned long long), hipHostMallocMapped));
+            memset(e.stats, 0, 4 * sizeof(unsigned long long));
+            NBK_HIP(hipHostGetDevicePointer((void**)&e.stats_dev, e.stats, 0));
+        }
+        const EdgeCap grown = edge_scratch_grown(e.cap, E, cap);
+        { const int32_t rc = grow_scratch(s.st, e.buf, e.bytes, EdgeLayout(grown.edges, grown.samples).bytes, "hipMalloc(edge scratch)"); if (rc != NBK_OK) return rc; }
+        e.cap = grown;
+        const size_t ws_need = TilePlan(m->pm, g_opt, pc, (int64_t)grown.samples, TileMode::Plain).bytes;
+        { const int32_t rc = ensure_validity_ws(m, w, ws_need, s.st, "hipMalloc(workspace)"); if (rc != NBK_OK) return rc; }
+    }
+    out = EdgeScratch{EdgeLayout(e.cap.edges, e.cap.samples).view(e.buf), e.cap.samples};
+    return NBK_OK;
+}
+static int32_t edge_too_large(unsigned long long total) { snprintf(g_err, sizeof(g_err), "edge batch of %llu samples is too large", total); return NBK_ERR_UNSUPPORTED; }
+
 // ---- batched DiscreteConnector: fully asynchronous -----------------------------------------------------------------------------
 // The sample count of an edge batch is only known on the device (the lengths come from device arrays), so nothing here waits
 // for it: the stream's edge scratch has a CAPACITY in samples, every launch covers the capacity and blocks beyond the true
 // count exit at once (EdgeSrc::total).  Capacity = E x (ceil(max_distance / resolution) + 2) samples at least -- exact for
 // steer, and for connect whenever the caller's edges respect the connector's max_distance (planners do) -- and at least 1.25 x
 // the count the previous call reported through pinned memory (`stats`, read here without waiting).  Edges that do not fit
-// anyway are marked and walked by one wave each (k_edges_overflow): always correct, only slower.
+// anyway are marked and walked by one wave each (k_edges_overflow): always correct, only slower.  Every number here is nbk_plan.hpp's
+// (edge_call_capacity, edge_scratch_fits / _grown, edge_exact_capacity, EdgeLayout): edge_scratch above sizes and binds the stream's
+// scratch, the entry is the launch sequence over it -- plan, scan, expand, validity, reduce, overflow walk.
 int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
                                 double resolution, double max_distance, int32_t mode, double threshold, uint8_t* valid,
                                 double* end, int32_t* n_samples, void* stream) {
     if (m == nullptr || E < 0 || (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr))) return NBK_ERR_INVALID;
-    if (!(resolution > 0.0) || !(max_distance > 0.0) || (mode != NBK_CONNECT && mode != NBK_STEER)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_RESOLUTION, resolution, max_distance, mode)) return NBK_ERR_INVALID;      // (a NaN threshold is served)
     NBK_DEVICE(m);
     if (E == 0) return NBK_OK;
     if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
@@ -4986,80 +5043,46 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
     }
     OwnScratch s;
     { const int32_t rc = own_scratch(m, st, "", s); if (rc != NBK_OK) return rc; }
-    StreamWs* const w = s.w;
-    const bool capturing = s.capturing;
-    // capacity: the static bound, and what earlier calls on this stream turned out to need (pinned memory, not waited for)
-    unsigned long long cap = edge_capacity(E, resolution, max_distance);
-    if (w->stats != nullptr && __atomic_load_n(&w->stats[1], __ATOMIC_RELAXED) != 0ull) {
-        // the last finished call had edges that did not fit: leave headroom over what it needed
-        const unsigned long long seen = __atomic_load_n(&w->stats[0], __ATOMIC_RELAXED);
-        const unsigned long long want = seen + seen / 4;
-        if (want > cap && want < 4000000000ull) cap = (want + 63ull) & ~63ull;
-    }
-    if (!m->parked_ok) {
-        // robots whose primitives do not fit the one-wave-per-edge kernel cannot serve overflowing edges: such descriptors
-        // keep a synchronous sizing step (one read-back) and cannot be captured
-        if (capturing) { snprintf(g_err, sizeof(g_err), "graph capture of edge batches needs a robot that fits the LDS-parked layout"); return NBK_ERR_UNSUPPORTED; }
-    }
     const PairCounts pc = sized_pairs(m, threshold);
-    double* plan = nullptr; uint8_t* ovf = nullptr; uint64_t* words = nullptr;
-    unsigned long long *cnt = nullptr, *offs = nullptr, *map = nullptr;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const bool fits = w->ecap_edges >= E && w->ecap_samples >= cap && w->stats != nullptr &&
-                          w->ws_bytes >= TilePlan(m->pm, g_opt, pc, (int64_t)w->ecap_samples, TileMode::Plain).bytes;
-        if (!fits) {
-            if (capturing) {
-                snprintf(g_err, sizeof(g_err), "graph capture: this stream's edge scratch is not allocated for %lld edges yet -- run the "
-                         "call once outside the capture", (long long)E);
-                return NBK_ERR_UNSUPPORTED;
-            }
-            if (w->stats == nullptr) {
-                NBK_HIP(hipHostMalloc((void**)&w->stats, 4 * sizeof(unsigned long long), hipHostMallocMapped));
-                memset(w->stats, 0, 4 * sizeof(unsigned long long));
-                NBK_HIP(hipHostGetDevicePointer((void**)&w->stats_dev, w->stats, 0));
-            }
-            const long long ne = w->ecap_edges > E ? w->ecap_edges : E;
-            const unsigned long long nc = w->ecap_samples > cap ? w->ecap_samples : cap;
-            int32_t rc = grow_scratch(st, w->ews, w->ews_bytes, EdgeLayout(ne, nc).bytes, "hipMalloc(edge scratch)");
-            if (rc != NBK_OK) return rc;
-            w->ecap_edges = ne; w->ecap_samples = nc;
-            rc = ensure_validity_ws(m, w, TilePlan(m->pm, g_opt, pc, (int64_t)nc, TileMode::Plain).bytes, st, "hipMalloc(workspace)");
-            if (rc != NBK_OK) return rc;
-        }
-        cap = w->ecap_samples;                                 // use all of what is there
-        const EdgeLayout L(w->ecap_edges, cap);
-        char* ews = static_cast<char*>(w->ews);
-        plan = reinterpret_cast<double*>(ews);
-        cnt = reinterpret_cast<unsigned long long*>(ews + L.cnt);
-        offs = reinterpret_cast<unsigned long long*>(ews + L.offs);
-        ovf = reinterpret_cast<uint8_t*>(ews + L.ovf);
-        map = reinterpret_cast<unsigned long long*>(ews + L.map);
-        words = reinterpret_cast<uint64_t*>(ews + L.words);
+    // the capacity to ask for: the static bound, and what earlier calls on this stream turned out to need (the two pinned words)
+    const unsigned long long want = edge_call_capacity(E, resolution, max_distance, s.w->edge.word(0), s.w->edge.word(1));
+    EdgeScratch x;
+    unsigned long long total = 0;
+    // One pass: bind a scratch of `cap` samples or more, plan and scan the edges into it.  A robot with the parked layout goes on at once
+    // (edges beyond the capacity are the overflow walk's, below); any other waits for the total here, the one read-back of this entry.
+    auto pass = [&](unsigned long long cap) -> int32_t {
+        { const int32_t rc = edge_scratch(m, pc, E, cap, s, x); if (rc != NBK_OK) return rc; }
         hipLaunchKernelGGL(k_edge_plan, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution,
-                           max_distance, mode, plan, cnt, end, n_samples);
+                           max_distance, mode, x.v.plan, x.v.cnt, end, n_samples);
         NBK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, x.v.cnt, E, x.v.offs);
         NBK_HIP(hipGetLastError());
-        if (m->parked_ok) break;
-        // (see above) no overflow kernel for this robot: size exactly, with one read-back
-        unsigned long long total = 0;
-        NBK_HIP(hipMemcpyAsync(&total, offs + E, 8, hipMemcpyDeviceToHost, st));
+        if (m->parked_ok) return NBK_OK;
+        NBK_HIP(hipMemcpyAsync(&total, x.v.offs + E, 8, hipMemcpyDeviceToHost, st));
         NBK_HIP(hipStreamSynchronize(st));
-        if (total <= cap) break;
-        if (attempt == 1 || total >= 4000000000ull) { snprintf(g_err, sizeof(g_err), "edge batch of %llu samples is too large", total); return NBK_ERR_UNSUPPORTED; }
-        cap = (total + 63ull) & ~63ull;
+        return NBK_OK;
+    };
+    { const int32_t rc = pass(want); if (rc != NBK_OK) return rc; }
+    if (!m->parked_ok && total > x.cap) {
+        // nothing serves this robot's overflowing edges: a second pass at exactly what the batch needs, and no third
+        unsigned long long exact = 0;
+        if (!edge_exact_capacity(total, exact)) return edge_too_large(total);
+        { const int32_t rc = pass(exact); if (rc != NBK_OK) return rc; }
+        if (total > x.cap) return edge_too_large(total);
     }
-    hipLaunchKernelGGL(k_edge_expand, dim3((unsigned)E), dim3(WAVE), 0, st, offs, E, map, cap, ovf);
+    const EdgeLayout::View& v = x.v;
+    unsigned long long* const stats_dev = s.w->edge.stats_dev;
+    hipLaunchKernelGGL(k_edge_expand, dim3((unsigned)E), dim3(WAVE), 0, st, v.offs, E, v.map, x.cap, v.ovf);
     NBK_HIP(hipGetLastError());
-    EdgeSrc es{starts, goals, plan, map, offs + E, 0, nullptr};
-    WsBinding b;                          // (the loop above sized the main workspace, for the unpipelined tiling)
-    { const int32_t rc = bind_own(m, pc, (int64_t)cap, false, s, b); if (rc != NBK_OK) return rc; }
-    { const int32_t rc = launch_validity({m, pc, es, nullptr, (int64_t)cap, threshold, words, nullptr, st}, b); if (rc != NBK_OK) return rc; }
-    hipLaunchKernelGGL(k_edge_reduce, dim3((unsigned)E), dim3(WAVE), 0, st, offs, E, words, ovf, valid, w->stats_dev);
+    EdgeSrc es{starts, goals, v.plan, v.map, v.offs + E, 0, nullptr};
+    WsBinding b;                          // (edge_scratch sized the main workspace, for the unpipelined tiling)
+    { const int32_t rc = bind_own(m, pc, (int64_t)x.cap, false, s, b); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_validity({m, pc, es, nullptr, (int64_t)x.cap, threshold, v.words, nullptr, st}, b); if (rc != NBK_OK) return rc; }
+    hipLaunchKernelGGL(k_edge_reduce, dim3((unsigned)E), dim3(WAVE), 0, st, v.offs, E, v.words, v.ovf, valid, stats_dev);
     NBK_HIP(hipGetLastError());
     if (m->parked_ok) {
         hipLaunchKernelGGL(k_edges, dim3((unsigned)E), dim3(WAVE), collide_lds(m), st, m->d, starts, goals, dist, E,
-                           resolution, max_distance, mode, threshold, valid, (double*)nullptr, (int32_t*)nullptr, (const uint8_t*)ovf, w->stats_dev);
+                           resolution, max_distance, mode, threshold, valid, (double*)nullptr, (int32_t*)nullptr, (const uint8_t*)v.ovf, stats_dev);
         NBK_HIP(hipGetLastError());
     }
     return guard_verdicts(m, st, valid, nullptr, nullptr, nullptr, E);
@@ -5069,13 +5092,12 @@ int32_t nbk_edge_validity_batch(const nbk_model* m, const double* starts, const 
 int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
                                   double resolution, double threshold, uint8_t* valid, double* t_hit, int32_t* n_samples, void* stream) {
     if (m == nullptr || S < 0 || knots == nullptr || (S > 0 && (ctrl == nullptr || valid == nullptr))) return NBK_ERR_INVALID;
-    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, knots)) return NBK_ERR_INVALID;
     if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308)) return NBK_ERR_INVALID;
     const int nk = n_ctrl + degree + 1;
-    if (!spline_knots_ok(knots, n_ctrl, degree)) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     if (S == 0) return NBK_OK;
-    if (S >= (int64_t(1) << 26)) {
+    if (S >= SPLINE_MAX_S) {
         snprintf(g_err, sizeof(g_err), "spline batch of %lld trajectories (2^26 or more): split the batch", (long long)S);
         return NBK_ERR_UNSUPPORTED;
     }
@@ -5088,58 +5110,45 @@ int32_t nbk_spline_validity_batch(const nbk_model* m, const double* ctrl, int64_
     { const int32_t rc = own_scratch(m, st, "", s); if (rc != NBK_OK) return rc; }
     StreamWs* const w = s.w;
     const SplineLayout L(nk, S);
-    { const int32_t rc = grow_scratch(st, w->sps, w->sps_bytes, L.bytes, "hipMalloc(spline scratch)"); if (rc != NBK_OK) return rc; }
-    char* sp = static_cast<char*>(w->sps);
-    double* kn = reinterpret_cast<double*>(sp);
-    double* plan = reinterpret_cast<double*>(sp + L.plan);
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(sp + L.cnt);
-    unsigned long long* offs = reinterpret_cast<unsigned long long*>(sp + L.offs);
-    NBK_HIP(hipMemcpyAsync(kn, knots, (size_t)nk * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, (const double*)kn,
-                       resolution, plan, cnt);
+    { const int32_t rc = grow_scratch(st, w->spline.small, w->spline.small_bytes, L.bytes, "hipMalloc(spline scratch)"); if (rc != NBK_OK) return rc; }
+    const SplineLayout::View v = L.view(w->spline.small);
+    NBK_HIP(hipMemcpyAsync(v.knots, knots, (size_t)nk * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, v.knots, resolution, v.plan, v.cnt);
     NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, S, offs);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
     NBK_HIP(hipGetLastError());
     unsigned long long total = 0;
-    NBK_HIP(hipMemcpyAsync(&total, offs + S, 8, hipMemcpyDeviceToHost, st));
+    NBK_HIP(hipMemcpyAsync(&total, v.offs + S, 8, hipMemcpyDeviceToHost, st));
     NBK_HIP(hipStreamSynchronize(st));
-    if (total >= (1ull << 31)) {
+    if (total >= SPLINE_MAX_T) {
         snprintf(g_err, sizeof(g_err), "spline batch of %llu samples (2^31 or more): split the batch", total);
         return NBK_ERR_UNSUPPORTED;
     }
-    const int64_t T = (int64_t)total;
-    const int64_t tile = std::min<int64_t>((T + WAVE - 1) / WAVE * WAVE, SPLINE_TILE);
-    const bool pairs = m->n_pairs > 0;
-    const size_t words_bytes = ((size_t)(T + 63) / 64 * 8 + 255) & ~size_t(255);
-    const size_t slab_bytes = pairs ? (size_t)tile * (size_t)m->n_q * sizeof(double) : 0;
+    const SplinePlan P((int64_t)total, m->n_q, m->n_pairs > 0);
     const PairCounts pc = sized_pairs(m, threshold);
-    if (T > 0) {
-        int32_t rc = grow_scratch(st, w->spl, w->spl_bytes, words_bytes + slab_bytes, "hipMalloc(spline samples)");
+    if (P.T > 0) { const int32_t rc = grow_scratch(st, w->spline.large, w->spline.large_bytes, P.bytes, "hipMalloc(spline samples)"); if (rc != NBK_OK) return rc; }
+    if (P.T > 0 && P.pairs) {
+        const int32_t rc = ensure_validity_ws(m, w, TilePlan(m->pm, g_opt, pc, P.tile, TileMode::Plain).bytes, st, "hipMalloc(workspace)");
         if (rc != NBK_OK) return rc;
-        if (pairs) {
-            rc = ensure_validity_ws(m, w, TilePlan(m->pm, g_opt, pc, tile, TileMode::Plain).bytes, st, "hipMalloc(workspace)");
-            if (rc != NBK_OK) return rc;
-        }
     }
-    uint64_t* words = static_cast<uint64_t*>(w->spl);
-    double* slab = pairs ? reinterpret_cast<double*>(static_cast<char*>(w->spl) + words_bytes) : nullptr;
-    for (int64_t b0 = 0; b0 < T; b0 += tile) {
-        const int64_t nb = std::min<int64_t>(tile, T - b0);
-        const dim3 grid((unsigned)((nb + 255) / 256)), block(256);
-        uint64_t* wx = pairs ? nullptr : words;
+    const SplinePlan::View x = P.view(w->spline.large);
+    for (int64_t i = 0; i < P.tiles; ++i) {
+        const SplinePlan::Tile t = P.at(i);
+        const dim3 grid((unsigned)((t.nb + 255) / 256)), block(256);
+        uint64_t* wx = P.pairs ? nullptr : x.words;
         with_degree(degree, [&](auto K) {
-            hipLaunchKernelGGL(k_spline_expand<decltype(K)::value>, grid, block, 0, st, m->n_q, ctrl, (int)n_ctrl, (const double*)kn,
-                               (const double*)plan, (const unsigned long long*)offs, S, (long long)b0, (long long)nb, slab, wx);
+            hipLaunchKernelGGL(k_spline_expand<decltype(K)::value>, grid, block, 0, st, m->n_q, ctrl, (int)n_ctrl, v.knots,
+                               (const double*)v.plan, (const unsigned long long*)v.offs, S, (long long)t.b0, (long long)t.nb, x.slab, wx);
         });
         NBK_HIP(hipGetLastError());
-        if (pairs) {
+        if (P.pairs) {
             // the stream's mutex is held: the validity pipeline directly (nbk_validity_batch would take it again); b0 is a multiple of 64
-            const int32_t rc = launch_validity({m, pc, NO_EDGES, slab, nb, threshold, words + b0 / 64, nullptr, st}, {w->ws, w, TileMode::Plain});
+            const int32_t rc = launch_validity({m, pc, NO_EDGES, x.slab, t.nb, threshold, x.words + t.b0 / 64, nullptr, st}, {w->ws, w, TileMode::Plain});
             if (rc != NBK_OK) return rc;
         }
     }
-    hipLaunchKernelGGL(k_spline_reduce, dim3((unsigned)S), dim3(WAVE), 0, st, (const double*)plan, (const unsigned long long*)offs,
-                       (const uint64_t*)words, valid, t_hit, n_samples);
+    hipLaunchKernelGGL(k_spline_reduce, dim3((unsigned)S), dim3(WAVE), 0, st, (const double*)v.plan, (const unsigned long long*)v.offs,
+                       (const uint64_t*)x.words, valid, t_hit, n_samples);
     NBK_HIP(hipGetLastError());
     return guard_verdicts(m, st, valid, nullptr, t_hit, nullptr, S);
 }
@@ -5151,7 +5160,7 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
     if (m == nullptr || S < 0 || knots == nullptr ||
         (S > 0 && (ctrl == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)))
         return NBK_ERR_INVALID;
-    if (degree < 1 || degree > NBK_MAX_SPLINE_DEGREE || n_ctrl <= degree || n_ctrl > SPLINE_MAX_CTRL) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
     if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
     NBK_DEVICE(m);
     if (S == 0) return NBK_OK;

@@ -21,7 +21,7 @@
 //
 // Sampled edges (nbk_edge_cloud_validity_batch): the edge rule is nbk.hip's own (k_edge_plan, k_scan, edge_sample_row); the samples of
 // all edges form one flat range that k_cloud_edges walks one sample per lane with the walk of k_cloud_validity (cloud_row_hits).  Plan,
-// counts and offsets live in the caller's workspace (EdgeCloudLayout).
+// counts and offsets live in the caller's workspace (EdgeCloudLayout, nbk_plan.hpp).
 #pragma once
 #define NBK_GRID_FN __host__ __device__ inline
 #include "nbk_cloud_grid.hpp"
@@ -410,14 +410,6 @@ static int32_t cloud_check_device(const nbk_cloud* c) {
     return NBK_OK;
 }
 
-// the workspace of nbk_edge_cloud_validity_batch: plan [E][3] double | cnt [E] | offs [E + 1], each part rounded up to 64 bytes
-struct EdgeCloudLayout {
-    size_t cnt, offs, bytes;
-    static size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
-    explicit EdgeCloudLayout(int64_t E) : cnt(r64((size_t)E * 24)), offs(cnt + r64((size_t)E * 8)), bytes(offs + r64(((size_t)E + 1) * 8)) {}
-};
-constexpr int64_t EDGE_CLOUD_MAX_E = int64_t(1) << 56;      // the layout's 40 bytes per edge stay far inside int64
-
 static CloudDev cloud_dev(const nbk_cloud* c) { return CloudDev{c->g, c->hdr, c->pts, c->idx, c->start}; }
 
 // the caller's selection (bit s of shape_bits = robot shape s of the descriptor it passed to nbk_model_create) in device order
@@ -557,7 +549,7 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, co
     // (nothing below dereferences m or c before the argument rules are through: they are answered without a device)
     if (m == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
     if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!(resolution > 0.0) || !(max_distance > 0.0) || (mode != NBK_CONNECT && mode != NBK_STEER) || threshold != threshold) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
     if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
         (workspace_bytes < (int64_t)EdgeCloudLayout(E).bytes || (reinterpret_cast<uintptr_t>(workspace) & 63) != 0)) return NBK_ERR_INVALID;
     if (E == 0) return NBK_OK;
@@ -566,11 +558,9 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, co
     NBK_DEVICE(m);
     { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
     hipStream_t st = (hipStream_t)stream;
-    const EdgeCloudLayout L(E);
-    char* ws = static_cast<char*>(workspace);
-    double* plan = reinterpret_cast<double*>(ws);
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(ws + L.cnt);
-    unsigned long long* offs = reinterpret_cast<unsigned long long*>(ws + L.offs);
+    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
+    double* const plan = v.plan;
+    unsigned long long *const cnt = v.cnt, *const offs = v.offs;
     const unsigned eblocks = (unsigned)((E + 255) / 256);
     hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
                        plan, cnt, end, n_samples);

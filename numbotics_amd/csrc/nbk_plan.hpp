@@ -1,7 +1,8 @@
 // nbk_plan.hpp -- host only: the arithmetic of the validity launch path of nbk.hip ("The launch plan"): WsLayout, the
 // parts of a validity workspace; TilePlan, how a call is cut into tiles and the bytes it needs; TableCache, when a stream's tables and
-// counter sets may be reused; the scratch layouts of the edge and spline entries.  No kernel, no HIP type or call, no global: g++
-// -std=c++17 compiles this file alone (tests/plan_check.cpp sweeps it under the host sanitizers).
+// counter sets may be reused; the capacity and scratch rules of the edge entry, the spline plan, and the scratch layouts of the edge,
+// cloud-edge and spline entries with their typed views.  No kernel, no HIP type or call, no global: g++ -std=c++17 compiles this file
+// alone (tests/plan_check.cpp sweeps it under the host sanitizers).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -159,16 +160,38 @@ struct TableCache {
     void mark_captured() { ready = false; captured = true; }
 };
 
-// ---- scratch of the edge and spline entries ------------------------------------------------------------------------------------
+// ---- the sample-generating entries: edge capacity and scratch, the spline plan, the scratch layouts and their typed views ---------
+constexpr unsigned long long EDGE_SAMPLES_MAX = 4000000000ull;      // an edge batch stays below this many samples (just under 2^32)
+
 // Capacity = E x (ceil(max_distance / resolution) + 2) samples at least (see nbk_edge_validity_batch), in whole 64-sample blocks
 inline unsigned long long edge_capacity(int64_t E, double resolution, double max_distance) {
     double per = ceil(max_distance / resolution) + 2.0;
     if (!(per < 4096.0)) per = 4096.0;                    // an unbounded max_distance: start from 4096 samples per edge
     double c = (double)E * per;
     if (c < 4096.0) c = 4096.0;
-    if (c > 4.0e9) c = 4.0e9;
+    if (c > (double)EDGE_SAMPLES_MAX) c = (double)EDGE_SAMPLES_MAX;
     return ((unsigned long long)c + 63ull) & ~63ull;
 }
+inline unsigned long long round64(unsigned long long n) { return (n + 63ull) & ~63ull; }
+
+struct EdgeCap { long long edges = 0; unsigned long long samples = 0; };      // what a stream's edge scratch holds
+
+// the capacity a call asks for: the static bound, and 1.25 x the samples the last finished call on the stream needed (`seen`) when it
+// had edges that did not fit (`overflowed`: edges its overflow kernel served) -- the two pinned words, 0 before the first call
+inline unsigned long long edge_call_capacity(int64_t E, double resolution, double max_distance, unsigned long long seen, unsigned long long overflowed) {
+    const unsigned long long cap = edge_capacity(E, resolution, max_distance), want = seen + seen / 4;
+    return overflowed != 0ull && want > cap && want < EDGE_SAMPLES_MAX ? round64(want) : cap;
+}
+// does a scratch of `have` with a validity workspace of ws_bytes serve E edges at capacity `cap`?  The call uses all of have.samples,
+// so the workspace has to hold the plain plan of that
+inline bool edge_scratch_fits(const PlanModel& m, const PlanOptions& o, const PairCounts& pc, const EdgeCap& have, size_t ws_bytes, int64_t E, unsigned long long cap) {
+    return have.edges >= E && have.samples >= cap && ws_bytes >= TilePlan(m, o, pc, (int64_t)have.samples, TileMode::Plain).bytes;
+}
+inline EdgeCap edge_scratch_grown(const EdgeCap& have, int64_t E, unsigned long long cap) {      // never shrinks
+    return {have.edges > E ? have.edges : (long long)E, have.samples > cap ? have.samples : cap};
+}
+// robots without the parked layout (no overflow kernel) read the exact sample total T back: the capacity it asks for; false = refused
+inline bool edge_exact_capacity(unsigned long long T, unsigned long long& cap) { cap = round64(T); return T < EDGE_SAMPLES_MAX; }
 
 // a stream's edge scratch for ne edges and nc samples: plan [ne][3] double | cnt [ne + 1] | offs [ne + 1] | overflow flags [ne],
 // then the sample map [nc] and the mask words [nc / 64], each of the three parts rounded up to 4 KiB.  Byte offsets (plan at 0), total
@@ -178,15 +201,57 @@ struct EdgeLayout {
     EdgeLayout(long long ne, unsigned long long nc)
         : cnt((size_t)ne * 3 * 8), offs(cnt + (size_t)(ne + 1) * 8), ovf(offs + (size_t)(ne + 1) * 8), map(r4k(ovf + (size_t)ne)),
           words(map + r4k((size_t)nc * 8)), bytes(words + r4k(((size_t)nc + 63) / 64 * 8)) {}
+    struct View { double* plan; unsigned long long *cnt, *offs; uint8_t* ovf; unsigned long long* map; uint64_t* words; };
+    View view(void* base) const {
+        char* p = static_cast<char*>(base);
+        return {reinterpret_cast<double*>(p), reinterpret_cast<unsigned long long*>(p + cnt), reinterpret_cast<unsigned long long*>(p + offs),
+                reinterpret_cast<uint8_t*>(p + ovf), reinterpret_cast<unsigned long long*>(p + map), reinterpret_cast<uint64_t*>(p + words)};
+    }
 };
 
+// the caller's workspace of nbk_edge_cloud_validity_batch: plan [E][3] double | cnt [E] | offs [E + 1], each part rounded up to 64 bytes
+struct EdgeCloudLayout {
+    size_t cnt, offs, bytes;
+    static size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
+    explicit EdgeCloudLayout(int64_t E) : cnt(r64((size_t)E * 24)), offs(cnt + r64((size_t)E * 8)), bytes(offs + r64(((size_t)E + 1) * 8)) {}
+    struct View { double* plan; unsigned long long *cnt, *offs; };
+    View view(void* base) const {
+        char* p = static_cast<char*>(base);
+        return {reinterpret_cast<double*>(p), reinterpret_cast<unsigned long long*>(p + cnt), reinterpret_cast<unsigned long long*>(p + offs)};
+    }
+};
+constexpr int64_t EDGE_CLOUD_MAX_E = int64_t(1) << 56;      // the layout's 40 bytes per edge stay far inside int64
+
 constexpr int64_t SPLINE_TILE = int64_t(1) << 20;           // q rows written and checked per tile of nbk_spline_validity_batch
+constexpr int64_t SPLINE_MAX_S = int64_t(1) << 26;          // a spline batch has fewer trajectories than this ...
+constexpr unsigned long long SPLINE_MAX_T = 1ull << 31;     // ... and fewer samples than this
 // the small half of a stream's spline scratch: knots [nk] | plan [S][2] | cnt [S] | offs [S + 1], each part 256-byte aligned
 struct SplineLayout {
     size_t plan, cnt, offs, bytes;
     static size_t r256(size_t n) { return (n + 255) & ~size_t(255); }
     SplineLayout(int nk, int64_t S)
         : plan(r256((size_t)nk * 8)), cnt(plan + r256((size_t)S * 16)), offs(cnt + r256((size_t)S * 8)), bytes(offs + r256((size_t)(S + 1) * 8)) {}
+    struct View { double *knots, *plan; unsigned long long *cnt, *offs; };
+    View view(void* base) const {
+        char* p = static_cast<char*>(base);
+        return {reinterpret_cast<double*>(p), reinterpret_cast<double*>(p + plan), reinterpret_cast<unsigned long long*>(p + cnt),
+                reinterpret_cast<unsigned long long*>(p + offs)};
+    }
+};
+// the large half, known once the sample total T (< SPLINE_MAX_T) is read back: mask words [T / 64], rounded up to 256 bytes | the q
+// slab [tile][n_q] of one tile, only for a robot with pairs.  Tiles of min(T in whole 64-row blocks, SPLINE_TILE) rows: at(0 .. tiles - 1)
+struct SplinePlan {
+    int64_t T, tile, tiles;
+    bool pairs;
+    size_t words_bytes, slab_bytes, bytes;
+    SplinePlan(int64_t T_, int n_q, bool pairs_)
+        : T(T_), tile((T_ + WAVE - 1) / WAVE * WAVE < SPLINE_TILE ? (T_ + WAVE - 1) / WAVE * WAVE : SPLINE_TILE), tiles(tile > 0 ? (T_ + tile - 1) / tile : 0),
+          pairs(pairs_), words_bytes(((size_t)(T_ + 63) / 64 * 8 + 255) & ~size_t(255)), slab_bytes(pairs_ ? (size_t)tile * (size_t)n_q * sizeof(double) : 0),
+          bytes(words_bytes + slab_bytes) {}
+    struct Tile { int64_t b0, nb; };
+    Tile at(int64_t i) const { return {i * tile, T - i * tile < tile ? T - i * tile : tile}; }
+    struct View { uint64_t* words; double* slab; };      // slab: nullptr for a robot without pairs
+    View view(void* base) const { return {static_cast<uint64_t*>(base), pairs ? reinterpret_cast<double*>(static_cast<char*>(base) + words_bytes) : nullptr}; }
 };
 
 }  // namespace nbk

@@ -1,13 +1,15 @@
 // plan_check.cpp -- stand-alone check of numbotics_amd/csrc/nbk_plan.hpp (tests/test_plan_host.py builds it with the host sanitizers and
 // runs it): sweeps the tiling / sizing arithmetic of the validity launch path and holds it against the properties the launcher
-// relies on, the scratch layouts against their comments, TableCache against the reuse condition written out, and three plans against
-// values read from the library on an MI355X.  Includes nothing of the project but that header; exits 0 and prints the counts, or
+// relies on, the scratch layouts and their typed views against their comments, TableCache against the reuse condition written out, the
+// capacity and scratch rules of the edge entry and the spline plan against the statements the entry points held before, and three plans
+// against values read from the library on an MI355X.  Includes nothing of the project but that header; exits 0 and prints the counts, or
 // prints every failed check and exits 1.
 #define NBK_PLAN_STANDALONE
 #include "../numbotics_amd/csrc/nbk_plan.hpp"
 
 #include <stdio.h>
 #include <initializer_list>
+#include <utility>
 
 using namespace nbk;
 
@@ -123,15 +125,192 @@ static void check_layouts() {
             CHECK(L.words >= L.map + c * 8 && L.words % 4096 == 0, "words");
             CHECK(L.bytes >= L.words + (c + 63) / 64 * 8 && L.bytes % 4096 == 0 && L.bytes < L.words + (c + 63) / 64 * 8 + 4096, "bytes");
         }
+    for (int64_t E : {int64_t(1), int64_t(2), int64_t(7), int64_t(8), int64_t(9), int64_t(1000), int64_t(0x7fffffff), EDGE_CLOUD_MAX_E}) {
+        const EdgeCloudLayout L(E);
+        const size_t e = (size_t)E;
+        CHECK(L.cnt >= e * 24 && L.offs >= L.cnt + e * 8 && L.bytes >= L.offs + (e + 1) * 8 && L.bytes <= e * 40 + 8 + 3 * 63, "plan | cnt | offs, E=%lld", (long long)E);
+        CHECK(L.cnt % 64 == 0 && L.offs % 64 == 0 && L.bytes % 64 == 0, "64-byte parts");
+    }
     for (int nk : {3, 8, 70, 65536 + 6})
         for (int64_t S : {int64_t(1), int64_t(31), int64_t(10000), (int64_t(1) << 26) - 1}) {
             const SplineLayout L(nk, S);
             CHECK(L.plan >= (size_t)nk * 8 && L.cnt >= L.plan + (size_t)S * 16 && L.offs >= L.cnt + (size_t)S * 8 && L.bytes >= L.offs + (size_t)(S + 1) * 8, "ordered");
             CHECK(L.plan % 256 == 0 && L.cnt % 256 == 0 && L.offs % 256 == 0 && L.bytes % 256 == 0, "256-byte parts");
         }
-    CHECK(SPLINE_TILE == 1 << 20, "SPLINE_TILE");
+    CHECK(SPLINE_TILE == 1 << 20 && SPLINE_MAX_S == 1 << 26 && SPLINE_MAX_T == 2147483648ull && EDGE_SAMPLES_MAX == 4000000000ull, "the limits of the entries");
     CHECK(edge_capacity(1, 0.05, 1.5) == 4096 && edge_capacity(1500, 0.02, 1.0) == 78016 && edge_capacity(1300, 0.01, 0.25) == 35136, "edge_capacity");
     CHECK(edge_capacity(10, 0.01, INFINITY) == 40960 && edge_capacity(int64_t(1) << 31, 1.0, 100.0) == 4000000000ull, "edge_capacity at its limits");
+}
+
+// The typed views: every part where its layout's offset says, inside `bytes`, at the alignment the layout's comment states, and no part
+// reaching into the next (checked on a real buffer, for the sizes that fit it)
+alignas(4096) static char g_arena[1 << 20];
+struct Part { const void* p; size_t size, align; };
+static void check_parts(const char* what, std::initializer_list<Part> parts, size_t bytes) {
+    size_t end = 0;
+    for (const Part& x : parts) {
+        const size_t at = (size_t)(static_cast<const char*>(x.p) - g_arena);
+        CHECK(x.p != nullptr && at >= end && at % x.align == 0 && at + x.size <= bytes, "%s: a part of %zu bytes at %zu, the one before ends at %zu, %zu in all", what, x.size, at, end, bytes);
+        end = at + x.size;
+    }
+}
+static void check_views() {
+    for (long long ne : {1ll, 2ll, 500ll, 1300ll})
+        for (unsigned long long nc : {64ull, 4096ull, 35136ull, 78016ull}) {
+            const EdgeLayout L(ne, nc);
+            if (L.bytes > sizeof(g_arena)) continue;
+            const EdgeLayout::View v = L.view(g_arena);
+            const size_t e = (size_t)ne, c = (size_t)nc;
+            check_parts("edge scratch", {{v.plan, e * 24, 8}, {v.cnt, (e + 1) * 8, 8}, {v.offs, (e + 1) * 8, 8}, {v.ovf, e, 1}, {v.map, c * 8, 4096}, {v.words, (c + 63) / 64 * 8, 4096}}, L.bytes);
+            CHECK((char*)v.plan == g_arena && (char*)v.cnt == g_arena + L.cnt && (char*)v.offs == g_arena + L.offs && (char*)v.ovf == g_arena + L.ovf &&
+                  (char*)v.map == g_arena + L.map && (char*)v.words == g_arena + L.words, "the view follows the offsets");
+        }
+    for (int64_t E : {int64_t(1), int64_t(2), int64_t(7), int64_t(8), int64_t(9), int64_t(1000), int64_t(26000)}) {
+        const EdgeCloudLayout L(E);
+        const EdgeCloudLayout::View v = L.view(g_arena);
+        const size_t e = (size_t)E;
+        CHECK(L.bytes <= sizeof(g_arena), "E=%lld fits the buffer", (long long)E);
+        check_parts("cloud edge workspace", {{v.plan, e * 24, 64}, {v.cnt, e * 8, 64}, {v.offs, (e + 1) * 8, 64}}, L.bytes);
+        CHECK((char*)v.plan == g_arena && (char*)v.cnt == g_arena + L.cnt && (char*)v.offs == g_arena + L.offs, "the view follows the offsets");
+    }
+    for (int nk : {3, 8, 70, 65536 + 6})
+        for (int64_t S : {int64_t(1), int64_t(31), int64_t(10000)}) {
+            const SplineLayout L(nk, S);
+            const SplineLayout::View v = L.view(g_arena);
+            CHECK(L.bytes <= sizeof(g_arena), "nk=%d S=%lld fits the buffer", nk, (long long)S);
+            check_parts("spline scratch", {{v.knots, (size_t)nk * 8, 256}, {v.plan, (size_t)S * 16, 256}, {v.cnt, (size_t)S * 8, 256}, {v.offs, (size_t)(S + 1) * 8, 256}}, L.bytes);
+            CHECK((char*)v.knots == g_arena && (char*)v.plan == g_arena + L.plan && (char*)v.cnt == g_arena + L.cnt && (char*)v.offs == g_arena + L.offs, "the view follows the offsets");
+        }
+}
+
+// ---- the edge and spline entries of nbk.hip before this arithmetic moved into the header (commit 820f3000): their inline statements,
+// one by one, as the old rules the header's functions are held equal to -------------------------------------------------------------
+static unsigned long long old_edge_capacity(int64_t E, double resolution, double max_distance) {
+    double per = ceil(max_distance / resolution) + 2.0;
+    if (!(per < 4096.0)) per = 4096.0;
+    double c = (double)E * per;
+    if (c < 4096.0) c = 4096.0;
+    if (c > 4.0e9) c = 4.0e9;
+    return ((unsigned long long)c + 63ull) & ~63ull;
+}
+struct OldEdge {
+    long long ecap_edges = 0; unsigned long long ecap_samples = 0; size_t ws_bytes = 0; bool stats = false;
+    unsigned long long stats0 = 0, stats1 = 0;          // the pinned words
+    unsigned long long capacity(int64_t E, double resolution, double max_distance) const {
+        unsigned long long cap = old_edge_capacity(E, resolution, max_distance);
+        if (stats && stats1 != 0ull) {
+            const unsigned long long seen = stats0;
+            const unsigned long long want = seen + seen / 4;
+            if (want > cap && want < 4000000000ull) cap = (want + 63ull) & ~63ull;
+        }
+        return cap;
+    }
+    bool fits(const PlanModel& m, const PlanOptions& o, const PairCounts& pc, int64_t E, unsigned long long cap) const {
+        const bool fits = ecap_edges >= E && ecap_samples >= cap && stats &&
+                          ws_bytes >= TilePlan(m, o, pc, (int64_t)ecap_samples, TileMode::Plain).bytes;
+        return fits;
+    }
+    void grow(const PlanModel& m, const PlanOptions& o, const PairCounts& pc, int64_t E, unsigned long long cap) {
+        stats = true;
+        const long long ne = ecap_edges > E ? ecap_edges : E;
+        const unsigned long long nc = ecap_samples > cap ? ecap_samples : cap;
+        ecap_edges = ne; ecap_samples = nc;
+        const size_t need = TilePlan(m, o, pc, (int64_t)nc, TileMode::Plain).bytes;
+        if (ws_bytes < need) ws_bytes = need;                // ensure_validity_ws
+    }
+    // the read-back of a robot without the parked layout: 0 go on, 1 resize to `cap` and go round again, 2 refused
+    static int exact(unsigned long long total, unsigned long long& cap, int attempt) {
+        if (total <= cap) return 0;
+        if (attempt == 1 || total >= 4000000000ull) return 2;
+        cap = (total + 63ull) & ~63ull;
+        return 1;
+    }
+};
+
+static void check_edge_rules() {
+    const int count[4] = {16, 74, 18, 13}, groups[4] = {34, 156, 38, 28};
+    const std::pair<double, double> steps[] = {{0.05, 1.5}, {0.02, 1.0}, {0.01, 0.25}, {0.01, (double)INFINITY}};
+    for (int parked = 0; parked < 2; ++parked) {
+        const PlanModel m = model(parked != 0, count, groups, 8);
+        const PairCounts pc = all_pairs(m);
+        for (int64_t E : {int64_t(1), int64_t(2), int64_t(400), int64_t(1300), int64_t(1500), int64_t(0x7fffffff)})
+            for (const auto& rd : steps) {
+                const unsigned long long bound = edge_capacity(E, rd.first, rd.second);
+                CHECK(bound == old_edge_capacity(E, rd.first, rd.second) && bound % 64 == 0 && bound >= 4096 && bound <= EDGE_SAMPLES_MAX, "E=%lld: static bound %llu", (long long)E, bound);
+                for (unsigned long long seen : {0ull, 1ull, bound - 1, bound, 5 * bound, 3990000000ull, 4000000000ull})
+                    for (unsigned long long overflowed : {0ull, 1ull}) {
+                        OldEdge old;
+                        old.stats = true; old.stats0 = seen; old.stats1 = overflowed;
+                        const unsigned long long cap = edge_call_capacity(E, rd.first, rd.second, seen, overflowed);
+                        CHECK(cap == old.capacity(E, rd.first, rd.second), "E=%lld seen=%llu overflowed=%llu: capacity %llu, before %llu", (long long)E, seen, overflowed, cap, old.capacity(E, rd.first, rd.second));
+                        CHECK(cap % 64 == 0 && cap >= bound && cap <= EDGE_SAMPLES_MAX + 63, "capacity %llu over the bound %llu", cap, bound);
+                        if (overflowed && seen + seen / 4 < EDGE_SAMPLES_MAX) CHECK(cap >= seen + seen / 4, "headroom over the %llu samples seen: %llu", seen, cap);
+                        // scratch sizes below, at and above what is asked, workspaces one byte short of, at and above what they serve
+                        for (long long he : {(long long)E - 1, (long long)E, (long long)E + 1})
+                            for (unsigned long long hs : {cap - 64, cap, cap + 64}) {
+                                const EdgeCap have = {he, hs};
+                                const size_t serve = TilePlan(m, DEFAULTS, pc, (int64_t)hs, TileMode::Plain).bytes;
+                                for (size_t ws : {serve - 1, serve, serve + 4096}) {
+                                    old.ecap_edges = he; old.ecap_samples = hs; old.ws_bytes = ws;
+                                    const bool fits = edge_scratch_fits(m, DEFAULTS, pc, have, ws, E, cap);
+                                    CHECK(fits == old.fits(m, DEFAULTS, pc, E, cap), "fits: %lld edges %llu samples %zu bytes for E=%lld cap=%llu", he, hs, ws, (long long)E, cap);
+                                    CHECK(fits == (he >= E && hs >= cap && ws >= serve), "fits, written out");
+                                    // the call then covers all of have.samples: its plan is what the workspace has to hold
+                                    if (fits) CHECK(have.samples >= cap && have.edges >= E && ws >= TilePlan(m, DEFAULTS, pc, (int64_t)have.samples, TileMode::Plain).bytes, "fits and cannot serve");
+                                    const EdgeCap g = edge_scratch_grown(have, E, cap);
+                                    OldEdge after = old;
+                                    after.grow(m, DEFAULTS, pc, E, cap);
+                                    CHECK(g.edges == after.ecap_edges && g.samples == after.ecap_samples, "growth to %lld edges %llu samples, before %lld and %llu", g.edges, g.samples, after.ecap_edges, after.ecap_samples);
+                                    CHECK(g.edges >= have.edges && g.samples >= have.samples && g.edges >= E && g.samples >= cap && g.samples % 64 == 0, "growth never shrinks and serves the call");
+                                    CHECK(edge_scratch_fits(m, DEFAULTS, pc, g, after.ws_bytes, E, cap), "a grown scratch fits");
+                                }
+                            }
+                    }
+                // the exact resize of a robot without the parked layout: one read-back, one more pass at the most
+                for (unsigned long long T : {0ull, 1ull, 63ull, 64ull, 65ull, (1ull << 20) - 1, 1ull << 20, (1ull << 20) + 1, (1ull << 31) - 1, 3990000000ull, 3999999999ull, 4000000000ull, 1ull << 40}) {
+                    unsigned long long old_cap = bound, exact = 0;
+                    const int verdict = OldEdge::exact(T, old_cap, 0);
+                    const bool ok = edge_exact_capacity(T, exact);
+                    CHECK(ok == (T < EDGE_SAMPLES_MAX), "T=%llu refused at the limit only", T);
+                    if (T > bound) {                  // (the launcher asks only then)
+                        CHECK((verdict == 2) == !ok && (verdict != 1 || exact == old_cap), "T=%llu over %llu: exact %llu ok %d, before %llu verdict %d", T, bound, exact, (int)ok, old_cap, verdict);
+                        if (ok) CHECK(exact % 64 == 0 && exact >= T && exact < T + 64 && OldEdge::exact(T, exact, 1) == 0, "the second pass holds T=%llu: %llu", T, exact);
+                    } else {
+                        CHECK(verdict == 0, "T=%llu fits %llu", T, bound);
+                    }
+                }
+            }
+    }
+}
+
+static void check_spline_plan() {
+    for (int64_t T : {int64_t(0), int64_t(1), int64_t(63), int64_t(64), int64_t(65), (int64_t(1) << 20) - 1, int64_t(1) << 20, (int64_t(1) << 20) + 1, (int64_t(1) << 31) - 1})
+        for (int n_q : {1, 7, 32})
+            for (bool pairs : {false, true}) {
+                // nbk_spline_validity_batch before SplinePlan
+                const int64_t a = (T + WAVE - 1) / WAVE * WAVE;
+                const int64_t tile = a < SPLINE_TILE ? a : SPLINE_TILE;                        // std::min<int64_t>(.., SPLINE_TILE)
+                const size_t words_bytes = ((size_t)(T + 63) / 64 * 8 + 255) & ~size_t(255);
+                const size_t slab_bytes = pairs ? (size_t)tile * (size_t)n_q * sizeof(double) : 0;
+                const SplinePlan p(T, n_q, pairs);
+                CHECK(p.T == T && p.pairs == pairs && p.tile == tile && p.words_bytes == words_bytes && p.slab_bytes == slab_bytes && p.bytes == words_bytes + slab_bytes,
+                      "T=%lld n_q=%d pairs=%d: tile %lld words %zu slab %zu", (long long)T, n_q, (int)pairs, (long long)p.tile, p.words_bytes, p.slab_bytes);
+                CHECK(p.tile % 64 == 0 && p.tile <= SPLINE_TILE && (T == 0) == (p.tile == 0) && p.words_bytes % 256 == 0 && p.words_bytes >= (size_t)(T + 63) / 64 * 8, "tile %lld", (long long)p.tile);
+                int64_t next = 0, i = 0;
+                for (int64_t b0 = 0; b0 < T; b0 += tile, ++i) {                                 // the loop of the entry point, before
+                    const int64_t nb = tile < T - b0 ? tile : T - b0;
+                    const SplinePlan::Tile t = p.at(i);
+                    CHECK(i < p.tiles && t.b0 == b0 && t.nb == nb, "tile %lld: rows %lld + %lld, before %lld + %lld", (long long)i, (long long)t.b0, (long long)t.nb, (long long)b0, (long long)nb);
+                    CHECK(t.b0 == next && t.b0 % 64 == 0 && t.nb > 0 && t.nb <= p.tile, "tile %lld starts at %lld", (long long)i, (long long)t.b0);
+                    CHECK(((size_t)t.b0 / 64 + (size_t)(t.nb + 63) / 64) * 8 <= p.words_bytes && (!pairs || (size_t)t.nb * (size_t)n_q * 8 <= p.slab_bytes), "tile %lld stays inside its buffer", (long long)i);
+                    next += t.nb;
+                }
+                CHECK(i == p.tiles && next == T, "%lld tiles cover %lld of %lld rows", (long long)p.tiles, (long long)next, (long long)T);
+                if (p.bytes <= sizeof(g_arena) && T > 0) {
+                    const SplinePlan::View v = p.view(g_arena);
+                    CHECK((char*)v.words == g_arena && (pairs ? (char*)v.slab == g_arena + p.words_bytes : v.slab == nullptr), "words | slab");
+                }
+            }
 }
 
 // the reuse condition and the state updates of the launcher before TableCache, statement by statement
@@ -203,6 +382,9 @@ static void check_pinned() {
 int main() {
     sweep();
     check_layouts();
+    check_views();
+    check_edge_rules();
+    check_spline_plan();
     check_table_cache();
     check_pinned();
     printf("%ld checks, %ld failed\n", g_checks, g_failed);
