@@ -516,7 +516,7 @@ int32_t nbk_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const d
     { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_cloud_validity, dim3(blocks_for(B)), dim3(WAVE), sizeof(double) * WAVE * (size_t)m->n_q, (hipStream_t)stream, m->d,
+    hipLaunchKernelGGL(k_cloud_validity, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
                        cloud_dev(c), cloud_selection(m, shape_bits), q, B, threshold, (int)accumulate,
                        reinterpret_cast<unsigned long long*>(mask_bits), mask_bytes);
     NBK_HIP(hipGetLastError());
@@ -531,7 +531,7 @@ int32_t nbk_cloud_clearance_batch(const nbk_model* m, const nbk_cloud* c, const 
     { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), sizeof(double) * WAVE * (size_t)m->n_q, (hipStream_t)stream, m->d,
+    hipLaunchKernelGGL(k_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
                        cloud_dev(c), cloud_selection(m, shape_bits), m->rs_user, q, B, d_max, min_dist, shape, point);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
@@ -572,7 +572,7 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, co
     // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
     const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
     hipLaunchKernelGGL(k_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
-                       sizeof(double) * WAVE * (size_t)m->n_q, st, m->d, cloud_dev(c), cloud_selection(m, shape_bits), es, offs, E, threshold,
+                       QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c), cloud_selection(m, shape_bits), es, offs, E, threshold,
                        valid);
     NBK_HIP(hipGetLastError());
     return NBK_OK;

@@ -3,8 +3,8 @@
 //   compile_tables  turns a checked descriptor into ModelTables: every table of the device blob, the host mirrors of nbk_model and the
 //                   Spec text of the per-robot broadphase, stage by stage (compile_geometry is its first half).
 // No kernel and no HIP runtime call in this file: the host-only entry points run it on machines without a device.  nbk.hip includes it
-// after what it uses: the K_* kinds, MotionTab and world_reach_bound (nbk_device.hpp), BQ_CAP (nbk_bf32_common.hpp), JK_*, NSUB,
-// LDS_MAX, VALIDITY_LDS_EXTRA and g_err.  Every expression here feeds a table the kernels and the oracle agree on bit for bit.
+// after what it uses: the K_* kinds, MotionTab and world_reach_bound (nbk_device.hpp), the LDS layouts (nbk_lds.hpp), JK_*, NSUB
+// and g_err.  Every expression here feeds a table the kernels and the oracle agree on bit for bit.
 #pragma once
 
 namespace nbk {
@@ -398,19 +398,15 @@ static void compile_geometry(const nbk_model_desc* d, ModelTables& t) {
 // the compiled-in limits; sets the two LDS verdicts
 static int32_t check_limits(const nbk_model_desc* d, ModelTables& t) {
     const int S = d->n_rshapes, W = d->n_wshapes, P = d->n_pairs;
-    if (3 * S >= 65536 || W >= 65536) return NBK_ERR_UNSUPPORTED;
+    if (3 * S >= 65536 || W >= 65536 || P >= (1 << 20)) return NBK_ERR_UNSUPPORTED;      // (the layouts below count in int)
     // the LDS broadphase (robots with more than 16 primitives) keeps the pair constants and world cores in LDS; robots the
     // register broadphases serve do not need it, however many world shapes there are
-    t.lds_broad_ok = (size_t)(d->n_q + 12 * t.slots + 3 * S) * 64 * sizeof(double) + (4 * (size_t)P + 18 * (size_t)W) * sizeof(double) + BQ_CAP * 4 <= LDS_MAX;
+    t.lds_broad_ok = lds_broad_ok(d->n_q, t.slots, S, P, W);
     if (!t.lds_broad_ok && S > 16) return NBK_ERR_UNSUPPORTED;
-    if (P >= (1 << 20)) return NBK_ERR_UNSUPPORTED;
-    // LDS budget: q rows + shape rows + saved frames, 512 B each (+ queue and flags of the validity path);
-    // the raw q slab reuses the shape area
-    const size_t lds_bytes = (size_t)(d->n_q + (t.rows > d->n_q ? t.rows : d->n_q) + 12 * t.slots) * 64 * sizeof(double) + VALIDITY_LDS_EXTRA;
     // robots whose primitives do not fit the LDS-parked layout (some 25+ shapes) keep validity and edges, through the
     // broadphase + narrowphase kernels at every batch size; the per-pair distance entry points report UNSUPPORTED for them
-    t.parked_ok = lds_bytes <= LDS_MAX;
-    if (S <= 16 && (size_t)d->n_q * 64 * sizeof(double) + 12 * (size_t)t.slots * 64 * sizeof(float) + 4096 > LDS_MAX) return NBK_ERR_UNSUPPORTED;
+    t.parked_ok = ValidityLds(d->n_q, t.rows > d->n_q ? t.rows : d->n_q, t.slots).fits();
+    if (S <= 16 && !broad_f32_ok(d->n_q, t.slots, S)) return NBK_ERR_UNSUPPORTED;
     if (P >= (1 << 26)) return NBK_ERR_UNSUPPORTED;
     return NBK_OK;
 }
