@@ -520,6 +520,45 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model *m, const nbk_cloud *c, co
                                       int32_t *n_samples /* optional */, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Certified continuous edges against a cloud: nbk_edge_continuous_batch's edges (T_f, the degenerate rule, `end`, the keys in
+ * t_free while the call runs) and its loop, unchanged, on one (edge e, selected robot shape s) item per lane; the cloud ALONE is
+ * looked at.  shape_bits as nbk_cloud_validity_batch (caller's numbering, NULL = every robot shape, a selection needs S <= 256).
+ *   mu_s (nbk_edge_shape_motion_bounds_host) bounds how fast any point of shape s moves in the world, which stands still.
+ *   The item's distance at t: q(t) = (1 - t) * s + t * g in three roundings per joint; a non-finite q(t) gives NaN (UNDECIDED at t);
+ *   else with  D_end = (threshold + slack) + mu_s * (T_f - t),  D_cap = (threshold + slack) + look_ahead,  D = D_end < D_cap ? D_end : D_cap:
+ *     some point i has signed distance (shape s, sphere of the cloud's radius at p_i) < D: d = the smallest one (the bits of
+ *     nbk_cloud_clearance_batch for shape s alone with d_max = D);  else D == D_end: d = +inf (the item stops FREE at T_f);  else d = D_cap.
+ *   Sound: every point of shape s moves at most mu_s |t' - t| and the cloud's points stand still, so no point within D_end at t means
+ *   the distance stays above threshold + slack up to T_f; a distance >= D_cap replaced by D_cap is a lower bound, hence conservative.
+ *   look_ahead > 0 (+inf allowed) bounds the ball one step searches; it changes how many steps an edge takes, never whether a
+ *   reported FREE is free.
+ *   Per edge the smallest stop point over the items, COLLISION before UNDECIDED on a tie, as nbk_edge_continuous_batch.
+ *   accumulate == 0: an empty cloud (N = 0 on the device) or an empty selection reports every non-degenerate edge FREE at T_f.
+ *   accumulate != 0: valid / t_free / status hold on entry what nbk_edge_continuous_batch wrote for the same edges with the same mode,
+ *   max_distance and dist; the result is bit for bit that of ONE conservative-advancement call over the scene's pairs and the
+ *   cloud's items together (items of an edge the scene stopped at t0 stop once past t0).  A non-degenerate edge that comes in with
+ *   a NaN t_free (a movable world whose status is set) keeps 0 / UNDECIDED / NaN.  Degenerate edges are DEGENERATE either way.
+ *   While the cloud's status is set every non-degenerate edge is invalid, UNDECIDED, t_free NaN; nothing of the grid is read.  N, the
+ *   radius and the status are read from the cloud on the device, in stream order.
+ * Asynchronous, no allocation, no host synchronisation, no workspace, capturable for every descriptor (LDS holds the q rows only):
+ * three kernels on `stream`, the middle one on a grid of (ceil(E / 64), selected shapes).  NBK_ERR_INVALID -- before any device is
+ * looked for -- for null m / c, E < 0, null starts / goals / valid / t_free / status with E > 0, max_iter < 1, slack < 0,
+ * !(max_distance > 0), a mode other than connect / steer, a NaN slack / threshold, and look_ahead NaN or <= 0.  E = 0 returns NBK_OK
+ * at once.  NBK_ERR_UNSUPPORTED for E > 2^31 - 1, a selection with S > 256, more than 65535 selected shapes.
+ */
+int32_t nbk_edge_cloud_continuous_batch(const nbk_model *m, const nbk_cloud *c, const double *starts, const double *goals,
+                                        const double *dist /* optional */, int64_t E, double max_distance, int32_t mode,
+                                        double threshold, int32_t max_iter, double slack, double look_ahead,
+                                        const uint64_t *shape_bits /* host, optional */, int32_t accumulate, uint8_t *valid,
+                                        double *end /* optional */, double *t_free, int32_t *status, void *stream);
+/*
+ * The motion bounds mu [E][S] (caller's robot shape order) that nbk_edge_cloud_continuous_batch advances with, on the host by the
+ * same routine (no GPU needed): the formula of nbk_edge_motion_bounds_host for a pair of (shape s, a world shape) -- every joint on
+ * the shape's path counts.  starts, goals (host) [E][n_q].
+ */
+int32_t nbk_edge_shape_motion_bounds_host(const nbk_model_desc *desc, const double *starts, const double *goals, int64_t E, double *mu);
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -4913,6 +4913,21 @@ int32_t nbk_edge_motion_bounds_host(const nbk_model_desc* d, const double* start
     return NBK_OK;
 }
 
+int32_t nbk_edge_shape_motion_bounds_host(const nbk_model_desc* d, const double* starts, const double* goals, int64_t E, double* mu) {
+    if (d == nullptr || E < 0) return NBK_ERR_INVALID;
+    { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
+    const int S = d->n_rshapes;
+    if (E == 0 || S == 0) return NBK_OK;
+    if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
+    MotionHost h;
+    motion_tables(d, frame_masks(d), h);
+    const MotionTab t = h.view(d->n_joints, S);
+    for (int64_t e = 0; e < E; ++e)
+        for (int x = 0; x < S; ++x)
+            mu[e * S + x] = shape_motion_bound(t, x, EdgeMotion{starts + e * d->n_q, goals + e * d->n_q});
+    return NBK_OK;
+}
+
 static const int32_t SPLINE_MAX_CTRL = 65536;
 
 // the knot rules of the spline entries: finite, nondecreasing, clamped on [0, 1]

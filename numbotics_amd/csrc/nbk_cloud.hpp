@@ -311,6 +311,42 @@ NBK_DEV double cloud_search_radius(double D, const Core& A, double radius) {
     return R + (1e-6 * __builtin_fabs(R) + 1e-7);
 }
 
+// The per-shape body of the clearance (k_cloud_clearance, CloudEdgeLane): core A of the robot shape with the caller's index su, built
+// by the caller (`ok`: this lane holds one), against every point of the cloud; best / bs / bi come in as the row's running minimum
+// and go out lowered.  Called by every lane of the wave.
+NBK_DEV void cloud_core_clearance(const CloudDev& cd, const Core& A, Core& P, double radius, bool ok, int su, double d_max,
+                                  double& best, int& bs, int& bi) {
+    double R = ok ? cloud_search_radius(best < d_max ? best : d_max, A, radius) : 0.0;
+    CloudWalk w;
+    cloud_walk_begin(cd, ok, A.c, R, w);
+    double R2 = R * R;
+    while (true) {
+        // as in k_cloud_validity: run ahead to the next point inside the current ball, then evaluate side by side
+        bool cand = false;
+        int oi = -1;
+        while (!cand && R > 0.0 && cloud_walk_next(cd, w)) {
+            const double* p = cd.pts + 3 * (size_t)w.cur;
+            oi = cd.idx[w.cur];
+            ++w.cur;
+            P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+            double dc[3];
+            sub3(A.c, P.c, dc);
+            cand = dot3(dc, dc) < R2;
+        }
+        if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+        if (cand) {
+            double fam = -1.0;
+            double d = cores_distance<false, true>(A, P, nullptr, &fam);
+            if (fam >= 0.0) epa_refine<false>(A, P, fam, d, nullptr);
+            if (d < d_max && (d < best || (d == best && (su < bs || (su == bs && oi < bi))))) {
+                best = d; bs = su; bi = oi;
+                R = cloud_search_radius(best, A, radius);
+                R2 = R * R;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd, CloudSel sel, const int* __restrict__ rs_user,
                                                         const double* __restrict__ q, int64_t B, double d_max,
                                                         double* __restrict__ out_d, int32_t* __restrict__ out_s, int32_t* __restrict__ out_p) {
@@ -335,43 +371,13 @@ __global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd,
             if (!cloud_selected(sel, s)) continue;
             Core A;
             cloud_core_init(A);
-            double R = 0.0;
-            const int su = rs_user[s];
             if (ok) {
                 if (m.rs_frame[s] != cur_frame) cloud_shape_frame(m, s, myq, T);
                 build_core(m, s, T, A);
                 if (A.kind == K_HULL) A.rad = -1.0;
-                R = cloud_search_radius(best < d_max ? best : d_max, A, radius);
             }
             cur_frame = m.rs_frame[s];
-            CloudWalk w;
-            cloud_walk_begin(cd, ok, A.c, R, w);
-            double R2 = R * R;
-            while (true) {
-                // as in k_cloud_validity: run ahead to the next point inside the current ball, then evaluate side by side
-                bool cand = false;
-                int oi = -1;
-                while (!cand && R > 0.0 && cloud_walk_next(cd, w)) {
-                    const double* p = cd.pts + 3 * (size_t)w.cur;
-                    oi = cd.idx[w.cur];
-                    ++w.cur;
-                    P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
-                    double dc[3];
-                    sub3(A.c, P.c, dc);
-                    cand = dot3(dc, dc) < R2;
-                }
-                if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
-                if (cand) {
-                    double fam = -1.0;
-                    double d = cores_distance<false, true>(A, P, nullptr, &fam);
-                    if (fam >= 0.0) epa_refine<false>(A, P, fam, d, nullptr);
-                    if (d < d_max && (d < best || (d == best && (su < bs || (su == bs && oi < bi))))) {
-                        best = d; bs = su; bi = oi;
-                        R = cloud_search_radius(best, A, radius);
-                        R2 = R * R;
-                    }
-                }
-            }
+            cloud_core_clearance(cd, A, P, radius, ok, rs_user[s], d_max, best, bs, bi);
         }
     }
     if (active) {
@@ -379,6 +385,139 @@ __global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd,
         if (out_s != nullptr) out_s[b] = ok ? bs : -1;
         if (out_p != nullptr) out_p[b] = ok ? bi : -1;
     }
+}
+
+// ---- certified continuous edges against the cloud (nbk_edge_cloud_continuous_batch) --------------------------------------------
+// ca_walk (nbk.hip) as it is, on one (edge e, selected robot shape s) item per lane; keys, ranks and the per-edge reduction are those
+// of nbk_edge_continuous_batch.  The grid is (ceil(E / 64), selected shapes): a wave holds ONE shape, so Core.kind and the hull are
+// wave-uniform as the cloud routines above need them (a pair-major flat index would straddle shapes).  LDS: [64][n_q] q rows.
+//
+// The item's motion bound is mu_s = shape_motion_bound (every joint on the shape's path counts: the cloud stands still), and its
+// distance at t the clearance of shape s ALONE against the cloud at q(t), cut at
+//     D = min(D_end, D_cap),   D_end = (thr + slack) + mu_s (T_f - t),   D_cap = (thr + slack) + look_ahead:
+// the smallest distance below D where there is one; else +inf when D == D_end, else D_cap.  Soundness:
+//   * every point of shape s moves at most mu_s |t' - t| between q(t) and q(t'), and the points of the cloud stand still;
+//   * so no point within D_end at t means that the distance stays above thr + slack up to T_f: the item may stop FREE at T_f, which
+//     is what ca_walk makes of +inf (gap is infinite, the advance reaches hi = T_f) -- no new branch;
+//   * a distance >= D_cap reported as D_cap is a lower bound of it, and advancing on a lower bound is conservative.
+// look_ahead bounds the ball a step walks, and so the points a lane meets: without it the first step of a long edge walks the whole
+// cloud.  A reserved key (real keys are < 2^64 - 4) marks the edges whose items do not run and whose result is 0 / UNDECIDED / NaN:
+// every non-degenerate edge while the cloud's status is set, and -- accumulating -- those that come in with a NaN t_free.
+constexpr unsigned long long CA_KEEP_KEY = ~0ull;
+
+// accumulate: valid / t_free (= key) / status hold what nbk_edge_continuous_batch wrote for these edges; the key is re-encoded from them
+__global__ void k_cloud_ca_init(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
+                                int64_t E, double max_distance, int mode, const CloudHdr* __restrict__ hdr, int accumulate,
+                                const int32_t* __restrict__ status, double* __restrict__ end, unsigned long long* __restrict__ key) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double* s = starts + e * nq;
+    const double* g = goals + e * nq;
+    double d, Tf;
+    if (!edge_span(nq, s, g, dist, e, max_distance, mode, d, Tf)) {
+        key[e] = 0ull;
+        if (end) for (int i = 0; i < nq; ++i) end[e * nq + i] = __builtin_nan("");
+        return;
+    }
+    unsigned long long k = ca_key(Tf, CA_FREE);
+    if (accumulate) {
+        const double t0 = __builtin_bit_cast(double, key[e]);
+        const int32_t st = status[e];
+        k = t0 != t0 ? CA_KEEP_KEY : ca_key(t0, st == NBK_CA_FREE ? CA_FREE : (st == NBK_CA_COLLISION ? CA_COLLISION : CA_UNDECIDED));
+    }
+    if (hdr->status != 0) k = CA_KEEP_KEY;
+    key[e] = k;
+    write_edge_end(nq, s, g, e, mode, Tf, end);
+}
+
+// the linear edge of EdgeLane for one robot shape against the cloud (pu: the shape's caller's index, p: its device index)
+struct CloudEdgeLane {
+    const double* s;
+    const double* g;
+    double Tf;
+    const CloudDev& cd;
+    double radius;            // of the cloud's points
+    double* myq;              // the lane's LDS row
+    double d_base, d_cap;     // thr + slack; (thr + slack) + look_ahead
+    double mu;
+    NBK_DEV double end() const { return Tf; }
+    NBK_DEV double span_end() const { return Tf; }
+    NBK_DEV double enter(const DevModel& m, int pu, double) { mu = shape_motion_bound(m.mt, pu, EdgeMotion{s, g}); return mu; }
+    NBK_DEV double distance(const DevModel& m, bool run, int p, int, double t, double*) {
+        bool ok = false;
+        if (run) {
+            const double omt = 1.0 - t;
+            for (int c = 0; c < m.n_q; ++c) { const double a = omt * s[c]; const double b = t * g[c]; myq[c] = a + b; }
+            ok = !row_nonfinite(myq, m.n_q, 1);
+        }
+        Core P;
+        cloud_point_core(radius, P);
+        Core A;
+        cloud_core_init(A);
+        double D_end = 0.0, D = 0.0;
+        if (ok) {
+            Xf T;
+            cloud_shape_frame(m, p, myq, T);
+            build_core(m, p, T, A);
+            if (A.kind == K_HULL) A.rad = -1.0;
+            D_end = d_base + mu * (Tf - t);
+            D = D_end < d_cap ? D_end : d_cap;
+        }
+        double best = NBK_INF;
+        int bs = -1, bi = -1;
+        cloud_core_clearance(cd, A, P, radius, ok, 0, D, best, bs, bi);
+        if (!ok) return __builtin_nan("");
+        if (best < D) return best;
+        return D == D_end ? NBK_INF : d_cap;
+    }
+};
+
+__global__ __launch_bounds__(64) void k_cloud_edge_ca(DevModel m, CloudDev cd, CloudSel sel, const int* __restrict__ rs_user,
+                                                      const double* __restrict__ starts, const double* __restrict__ goals,
+                                                      const double* __restrict__ dist, int64_t E, double max_distance, int mode, double thr,
+                                                      int max_iter, double slack, double look_ahead, unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    // the blockIdx.y-th selected shape, device order
+    int p = -1;
+    for (int i = 0, k = 0; i < m.n_rshapes; ++i) {
+        if (!cloud_selected(sel, i)) continue;
+        if (k == (int)blockIdx.y) { p = i; break; }
+        ++k;
+    }
+    if (p < 0) return;
+    const int n = cd.hdr->n;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < E;
+    const int64_t e = live ? i : 0;
+    const double base = thr + slack;
+    CloudEdgeLane tr{starts + e * m.n_q, goals + e * m.n_q, 0.0, cd, cd.hdr->radius, lds + lane * m.n_q, base, base + look_ahead, 0.0};
+    double d_edge = 0.0;
+    // (an empty cloud stops every item FREE at T_f, which is where its key stands; the keys of a cloud whose status is set are all reserved)
+    const bool run = live && n > 0 && edge_span(m.n_q, tr.s, tr.g, dist, e, max_distance, mode, d_edge, tr.Tf) &&
+                     __hip_atomic_load(key + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != CA_KEEP_KEY;
+    ca_walk(m, tr, run, rs_user[p], p, lane, thr, max_iter, slack, key + e);
+}
+
+__global__ void k_cloud_ca_final(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
+                                 int64_t E, double max_distance, int mode, const unsigned long long* __restrict__ key,
+                                 uint8_t* __restrict__ valid, double* __restrict__ t_free, int32_t* __restrict__ status) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double d, Tf;
+    if (!edge_span(nq, starts + e * nq, goals + e * nq, dist, e, max_distance, mode, d, Tf)) {
+        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = NBK_CA_DEGENERATE;
+        return;
+    }
+    const unsigned long long k = key[e];          // t_free aliases key: read before the write
+    if (k == CA_KEEP_KEY) {
+        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = NBK_CA_UNDECIDED;
+        return;
+    }
+    const unsigned long long r = k & 3ull;
+    valid[e] = r == CA_FREE ? 1 : 0;
+    status[e] = r == CA_FREE ? NBK_CA_FREE : (r == CA_COLLISION ? NBK_CA_COLLISION : NBK_CA_UNDECIDED);
+    t_free[e] = __builtin_bit_cast(double, k >> 2);
 }
 
 }  // namespace nbk
@@ -574,6 +713,41 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, co
     hipLaunchKernelGGL(k_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
                        QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c), cloud_selection(m, shape_bits), es, offs, E, threshold,
                        valid);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_edge_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, const double* starts, const double* goals, const double* dist,
+                                        int64_t E, double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
+                                        double look_ahead, const uint64_t* shape_bits, int32_t accumulate, uint8_t* valid, double* end,
+                                        double* t_free, int32_t* status, void* stream) {
+    // (as nbk_edge_cloud_validity_batch: the argument rules are answered without a device)
+    if (m == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
+    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    const CloudSel sel = cloud_selection(m, shape_bits);
+    int n_sel = m->d.n_rshapes;
+    if (!sel.all) { n_sel = 0; for (int k = 0; k < 4; ++k) n_sel += __builtin_popcountll(sel.w[k]); }
+    if (n_sel > 65535) return NBK_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* key = reinterpret_cast<unsigned long long*>(t_free);
+    const unsigned eb = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(k_cloud_ca_init, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
+                       (const CloudHdr*)c->hdr, (int)accumulate, (const int32_t*)status, end, key);
+    NBK_HIP(hipGetLastError());
+    if (n_sel > 0) {
+        hipLaunchKernelGGL(k_cloud_edge_ca, dim3(blocks_for(E), (unsigned)n_sel), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c),
+                           sel, m->rs_user, starts, goals, dist, E, max_distance, (int)mode, threshold, (int)max_iter, slack, look_ahead, key);
+        NBK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cloud_ca_final, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
+                       (const unsigned long long*)key, valid, t_free, status);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

@@ -1479,6 +1479,13 @@ __host__ __device__ inline double pair_motion_bound(const MotionTab& t, int p, c
     return mu;
 }
 
+// mu of robot shape x (user order) against a world that stands still: every joint on its path counts.  The bits pair_motion_bound
+// gives for a pair of (x, any world shape); what nbk_edge_cloud_continuous_batch advances with (nbk_edge_shape_motion_bounds_host).
+template <class TR>
+__host__ __device__ inline double shape_motion_bound(const MotionTab& t, int x, const TR& tr) {
+    return motion_terms(t, x, t.smask[x], tr, 0.0);
+}
+
 // the linear edge q(t) = (1-t) s + t g: speed |g - s|_c, travel max(|s|, |g|)_c
 struct EdgeMotion {
     const double* s;

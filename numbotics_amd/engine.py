@@ -109,6 +109,23 @@ def edge_motion_bounds(model, starts, goals):
     return mu
 
 
+def edge_shape_motion_bounds(model, starts, goals):
+    """Motion bounds mu (E, S) of the linear edges starts -> goals for every robot shape of a SceneModel, in its shape order, against
+    a world that stands still: no point of shape s moves further than mu[e, s] |t - t'| between q(t) and q(t').  The routine
+    nbk_edge_cloud_continuous_batch advances with, run on the host (nbk_edge_shape_motion_bounds_host); no GPU needed."""
+    n_q = getattr(model, "kin", model).n_q
+    s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64)).reshape(-1, n_q)
+    g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64)).reshape(-1, n_q)
+    if s.shape != g.shape:
+        raise ValueError("starts and goals must have the same shape")
+    d, keep = model_desc(model)
+    mu = np.empty((s.shape[0], int(d.n_rshapes)), dtype=np.float64)
+    _lib.check(_lib.load().nbk_edge_shape_motion_bounds_host(C.byref(d), s.ctypes.data, g.ctypes.data, s.shape[0], mu.ctypes.data),
+               "nbk_edge_shape_motion_bounds_host")
+    del keep
+    return mu
+
+
 def spline_motion_bounds(model, ctrl, knots, degree):
     """Motion bounds mu (S, n - degree, P) of S clamped B-splines ctrl (S, n, n_q) sharing the knots, per knot span ell (index
     ell - degree) and allowed pair: |d_p(t) - d_p(t')| <= mu[s, ell - degree, p] |t - t'| for t, t' in [knots[ell], knots[ell+1]].
@@ -178,6 +195,12 @@ def broad_spec_source(model, movable=False, world_radius=None):
     call(buf, n)
     del keep
     return buf.value
+
+
+# default ``look_ahead`` of DeviceModel.cloud_edge_continuous and ContinuousConnector(cloud=...): the fastest value measured whose UNDECIDED
+# count is no higher than without a cut (tools/cloud_time.py --only certified).  Until that table has its figures
+# the default is no cut at all, the one value that meets the rule unmeasured.
+CLOUD_LOOK_AHEAD = float("inf")
 
 
 class DeviceModel:
@@ -645,6 +668,39 @@ class DeviceModel:
             self._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
             0 if mode == "connect" else 1, float(threshold), int(max_iter), float(slack), valid.data_ptr(), end.data_ptr(),
             t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_edge_continuous_batch")
+        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
+
+    def cloud_edge_continuous(self, cloud, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6,
+                              look_ahead=CLOUD_LOOK_AHEAD, dist=None, shapes=None, out=None):
+        """``edge_continuous``'s edges certified against ``cloud`` ALONE (a ``PointCloud``; nbk_edge_cloud_continuous_batch): one
+        (edge, robot shape) item per lane advances by conservative advancement on the shape's clearance from the cloud -> valid (E,)
+        bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``).  ``shapes``: as ``cloud_validity``.  ``look_ahead`` (> 0,
+        ``inf`` allowed): how far beyond threshold + slack one step searches the cloud; it changes the number of steps, never the
+        soundness of FREE.  ``out``: the CUDA tensors (valid (E,) uint8 / bool, t_free (E,) float64, status (E,) int32) that
+        ``edge_continuous`` returned for the same edges, mode, max_distance and dist: the cloud's items are reduced INTO them -- the
+        result is that of one certified call over the scene's pairs and the cloud together; they are returned, with this call's end."""
+        torch = _require_gpu()
+        s, g, dd = self._stage_edges(starts, goals, dist)
+        bits = self._shape_bits(shapes)
+        if out is None:
+            valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
+            t_free = torch.empty((s.B,), dtype=torch.float64, device=s.device)
+            status = torch.empty((s.B,), dtype=torch.int32, device=s.device)
+        else:
+            want = ((torch.uint8, torch.bool), (torch.float64,), (torch.int32,))
+            if not (isinstance(out, (tuple, list)) and len(out) == 3 and
+                    all(torch.is_tensor(o) and o.is_cuda and o.is_contiguous() and tuple(o.shape) == (s.B,) and o.dtype in w
+                        for o, w in zip(out, want))):
+                raise ValueError(f"out must be (valid, t_free, status): contiguous CUDA tensors of shape {(s.B,)} (uint8 / bool, float64, int32)")
+            valid, t_free, status = out
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.nbk_edge_cloud_continuous_batch(
+            self._h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
+            0 if mode == "connect" else 1, float(threshold), int(max_iter), float(slack), float(look_ahead),
+            None if bits is None else bits.ctypes.data, 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
+            status.data_ptr(), self._stream()), "nbk_edge_cloud_continuous_batch")
+        if out is not None:
+            return valid, s.out(end), t_free, status
         return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
 
     def spline_validity(self, ctrl, knots, degree, resolution, threshold=0.0):

@@ -6,8 +6,10 @@ whole edge -- every sample ``T = arange(0, T_f, res/d) U {T_f}`` -- is checked b
 and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per wavefront).
 ``validate_trajectories`` / ``validate_trajectory`` check smoothed (clamped B-spline) trajectories sample by sample on the device.
 ``ConnectorParams(cloud=...)`` (a ``PointCloud``, with an ``arm``) adds a scan to what the sampled edges and ``is_valid`` respect:
-the device path ANDs ``nbk_edge_cloud_validity_batch`` into the scene's verdict.  Smoothed trajectories and the certified continuous
-checks do not see point clouds yet: with a cloud set they refuse instead of ignoring it.
+the device path ANDs ``nbk_edge_cloud_validity_batch`` into the scene's verdict.  Smoothed trajectories do not see point clouds yet:
+with a cloud set they refuse instead of ignoring it.  ``ContinuousConnector`` takes its cloud as a constructor argument
+(``ContinuousConnector(params, cloud=...)``: certified straight edges, ``nbk_edge_cloud_continuous_batch``) and still refuses params
+that carry one.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
 certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
 with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.  Its
@@ -21,6 +23,7 @@ import numpy as np
 
 from numbotics_amd.planning import unit_bspline, unit_knots
 from numbotics_amd.planning.trajectories import UnitBSpline
+from numbotics_amd.engine import CLOUD_LOOK_AHEAD
 
 _DEFAULT_TRAJ = lambda x, y: unit_bspline(np.array([x, y]))      # noqa: E731
 _DEFAULT_DIST = lambda x, y: np.linalg.norm(x - y)               # noqa: E731
@@ -239,17 +242,34 @@ class ContinuousConnector(Connector):
     ``validate_trajectories`` / ``validate_trajectory`` (``params.arm`` required) certify smoothed plans -- clamped B-splines of
     degree 1-5 -- the same way on the device, across their knot spans (``nbk_spline_continuous_batch``).
 
-    Params that carry a ``cloud`` are refused: a certificate that ignores an obstacle would be worse than none."""
+    ``cloud`` (a ``PointCloud``; ``cloud_ignore_links``: links, or their names, whose shapes are left out, e.g. the base standing on
+    a scanned table): the straight edges are certified against the scan as well -- ``certify_batch`` runs ``edge_continuous``, then
+    ``cloud_edge_continuous`` reduces one (edge, robot shape) item per lane into the same result
+    (``nbk_edge_cloud_continuous_batch``), which is that of one certified call over the scene and the cloud together; ``is_valid``
+    asks both.  ``look_ahead`` bounds how far one step searches the cloud (it changes the number of steps, never whether an edge
+    called free is free).  It needs ``params.arm``, the default trajectory and no ``validity_checker``.  The cloud is an argument of
+    THIS constructor because ``ConnectorParams(cloud=...)`` keeps being refused here -- a certificate that ignores an obstacle would
+    be worse than none, and callers rely on that refusal; lifting it is a later change.  With a cloud the trajectory methods raise:
+    certified splines do not see point clouds yet."""
 
-    def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6):
+    def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6, cloud=None, cloud_ignore_links=(),
+                 look_ahead: float = CLOUD_LOOK_AHEAD):
         if int(max_iter) < 1:
             raise ValueError("max_iter must be at least 1")
         if not slack >= 0.0:
             raise ValueError("slack must be non-negative")
         _no_cloud(params, "certified continuous checks")
+        if cloud is not None:
+            if params.arm is None or params.validity_checker is not None or params.trajectory_func is not _DEFAULT_TRAJ:
+                raise ValueError("a point cloud needs ConnectorParams(arm=...) with the default linear trajectory and no validity_checker")
+            if not look_ahead > 0.0:
+                raise ValueError("look_ahead must be positive")
         self._params = params
         self.max_iter = int(max_iter)
         self.slack = float(slack)
+        self.cloud = cloud
+        self.cloud_ignore_links = tuple(cloud_ignore_links)
+        self.look_ahead = float(look_ahead)
 
     def _device_edge(self):
         p = self._params
@@ -303,7 +323,10 @@ class ContinuousConnector(Connector):
         p = self._params
         if p.validity_checker is not None:
             return p.validity_checker(state) > 0.0
-        return not p.arm.in_collision(state, p.collision_threshold)
+        if self.cloud is None:
+            return not p.arm.in_collision(state, p.collision_threshold)
+        return not (p.arm.in_collision(state, p.collision_threshold)
+                    or p.arm.in_collision_with_cloud(state, self.cloud, p.collision_threshold, self.cloud_ignore_links))
 
     # ---- batched ------------------------------------------------------------------------------------------
     def certify_batch(self, starts, goals, mode="connect", dist=None):
@@ -313,9 +336,20 @@ class ContinuousConnector(Connector):
         if not self._device_edge():
             raise ValueError("batched continuous checks need ConnectorParams(arm=...) with the default linear trajectory "
                              "and no validity_checker")
-        _, dev = p.arm._scene_device()
-        return dev.edge_continuous(starts, goals, p.max_distance, mode=mode, threshold=p.collision_threshold,
-                                   max_iter=self.max_iter, slack=self.slack, dist=dist)
+        sm, dev = p.arm._scene_device()
+        kw = dict(mode=mode, threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
+        if self.cloud is None:
+            return dev.edge_continuous(starts, goals, p.max_distance, dist=dist, **kw)
+        # the scene's result, then the cloud's items reduced into it on the device: items of an edge the scene stopped early stop there
+        import torch
+        host = not torch.is_tensor(starts)
+        on_dev = lambda x: x if x is None or torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()  # noqa: E731
+        starts, goals, dist = on_dev(starts), on_dev(goals), on_dev(dist)
+        valid, end, t_free, status = dev.edge_continuous(starts, goals, p.max_distance, dist=dist, **kw)
+        dev.cloud_edge_continuous(self.cloud, starts, goals, p.max_distance, look_ahead=self.look_ahead, dist=dist,
+                                  shapes=p.arm._cloud_shapes(sm, self.cloud_ignore_links), out=(valid, t_free, status), **kw)
+        out = (valid, end, t_free, status)
+        return tuple(x.cpu().numpy() for x in out) if host else out
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -327,6 +361,10 @@ class ContinuousConnector(Connector):
         return ok, end
 
     # ---- smoothed trajectories ----------------------------------------------------------------------------
+    def _no_cloud_splines(self):
+        if self.cloud is not None:
+            raise ValueError("certified trajectory checks do not see point clouds yet")
+
     def _spline_certify(self, ctrl, knots, degree):
         p = self._params
         _, dev = p.arm._scene_device()
@@ -337,12 +375,14 @@ class ContinuousConnector(Connector):
         spans (``nbk_spline_continuous_batch``): (S, n, dof) -> valid (S,) bool, t_free (S,) (how far along [0, 1] the trajectory
         is certified free; NaN when degenerate), status (S,) int32 (``numbotics_amd._lib.CA_*``).  A trajectory called valid has
         no configuration closer than ``collision_threshold``.  NumPy in, NumPy out; device tensors stay on the device."""
+        self._no_cloud_splines()
         shape = _shape(control_points)
         k = _spline_args(self._params, shape, degree)
         return self._spline_certify(control_points, unit_knots(shape[1], k), k)
 
     def validate_trajectory(self, spline):
         """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_free)."""
+        self._no_cloud_splines()
         c, t, k = _spline_parts(self._params, spline)
         valid, t_free, _ = self._spline_certify(c[None], t, k)
         return bool(valid[0]), float(t_free[0])

@@ -1,0 +1,158 @@
+"""NumPy + CPU-oracle restatement of nbk_edge_cloud_continuous_batch (DeviceModel.cloud_edge_continuous, ContinuousConnector(cloud=...)),
+for the tests.
+
+One item per (edge, selected robot shape): mu from nbk_edge_shape_motion_bounds_host, the shape's clearance from the oracle on
+``cloud_model(sm, pts, r, [shape])`` (the cloud's points as sphere world shapes: the bits the device computes), q(t) in three
+roundings, the cut D = min(D_end, D_cap) and the three-way rule of include/nbk.h in its operation order.  The loop and the per-edge
+reduction are those of tests/continuous_ref.py; the accumulate form reduces over the scene's items and the cloud's together."""
+import numpy as np
+
+from numbotics_amd.engine import edge_shape_motion_bounds
+from cloud_cases import cloud_model
+from continuous_ref import edge_span, pair_distances, reference_continuous, FREE, COLLISION, UNDECIDED, DEGENERATE
+
+EXIT_POINT, EXIT_INF, EXIT_CAP, EXIT_NAN = 0, 1, 2, 3       # how a distance evaluation ended
+
+
+def selection(sm, shapes):
+    return np.arange(sm.n_rshapes, dtype=np.int32) if shapes is None else np.asarray(sorted(shapes), dtype=np.int32)
+
+
+class CloudDistance:
+    """d of the items (edge, k-th selected shape) at t, by the rule of the header; counts the exits it takes."""
+
+    def __init__(self, sm, pts, r, shapes, starts, goals, Tf, threshold, slack, look_ahead):
+        from oracle.cpu_oracle import Oracle
+        self.sel = selection(sm, shapes)
+        self.pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+        self.orc = [Oracle(cloud_model(sm, self.pts, r, [int(x)])) for x in self.sel] if self.pts.shape[0] else []
+        self.s, self.g, self.Tf = starts, goals, Tf
+        self.mu = edge_shape_motion_bounds(sm, starts, goals)[:, self.sel]
+        self.base = threshold + slack
+        self.d_cap = self.base + look_ahead
+        self.exits = np.zeros(4, dtype=np.int64)
+
+    def __call__(self, ee, kk, tt):
+        with np.errstate(invalid="ignore"):
+            q = (1.0 - tt)[:, None] * self.s[ee] + tt[:, None] * self.g[ee]
+        fin = np.isfinite(q).all(axis=1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            d_end = self.base + self.mu[ee, kk] * (self.Tf[ee] - tt)
+        D = np.where(d_end < self.d_cap, d_end, self.d_cap)
+        d = np.full(ee.shape, np.nan)
+        how = np.full(ee.shape, EXIT_NAN)
+        for k in np.unique(kk):
+            rows = np.nonzero((kk == k) & fin)[0]
+            if rows.shape[0] == 0:
+                continue
+            dmin = pair_distances(self.orc[k], q[rows]).min(axis=1)
+            near = dmin < D[rows]
+            at_end = D[rows] == d_end[rows]
+            d[rows] = np.where(near, dmin, np.where(at_end, np.inf, self.d_cap))
+            how[rows] = np.where(near, EXIT_POINT, np.where(at_end, EXIT_INF, EXIT_CAP))
+        self.exits += np.bincount(how, minlength=4)
+        return d
+
+
+def advance_items(distance, mu, Tf, live, threshold, max_iter, slack):
+    """The loop of continuous_ref.reference_continuous on items (E, K) with ``distance(ee, kk, tt)`` -> stop (E, K), status (E, K)
+    (-1 / NaN for the items of edges that are not ``live``)."""
+    E, K = mu.shape
+    t = np.zeros((E, K))
+    stop = np.full((E, K), np.nan)
+    st = np.full((E, K), -1, dtype=np.int32)
+    active = np.zeros((E, K), dtype=bool)
+    active[live, :] = True
+    for _ in range(max_iter):
+        ee, kk = np.nonzero(active)
+        if ee.shape[0] == 0:
+            break
+        tt = t[ee, kk]
+        d = distance(ee, kk, tt)
+        m = mu[ee, kk]
+        col = d <= threshold
+        with np.errstate(invalid="ignore"):
+            gap = (d - threshold) - slack
+        und = ~col & ~(gap > 0.0)
+        rest = ~col & ~und
+        free0 = rest & (m == 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tn = tt + gap / m
+        free1 = rest & ~free0 & (tn >= Tf[ee])
+        adv = rest & ~free0 & ~free1
+        for mask, code in ((col, COLLISION), (und, UNDECIDED)):
+            stop[ee[mask], kk[mask]] = tt[mask]
+            st[ee[mask], kk[mask]] = code
+        fr = free0 | free1
+        stop[ee[fr], kk[fr]] = Tf[ee[fr]]
+        st[ee[fr], kk[fr]] = FREE
+        active[ee[~adv], kk[~adv]] = False
+        t[ee[adv], kk[adv]] = tn[adv]
+    ee, kk = np.nonzero(active)
+    stop[ee, kk] = t[ee, kk]
+    st[ee, kk] = UNDECIDED
+    return stop, st
+
+
+def reduce_edges(stop, st, Tf, live, starts, goals, mode):
+    """Per edge the smallest stop point over its items, COLLISION before UNDECIDED before FREE on a tie (explicit loops)."""
+    E, nq = starts.shape
+    valid = np.zeros(E, dtype=bool)
+    t_free = np.full(E, np.nan)
+    status = np.full(E, DEGENERATE, dtype=np.int32)
+    end = np.full((E, nq), np.nan)
+    rank = {COLLISION: 0, UNDECIDED: 1, FREE: 2}
+    for e in range(E):
+        if not live[e]:
+            continue
+        tf = Tf[e]
+        best_t, best_s = tf, FREE
+        for p in range(stop.shape[1]):
+            tp, sp = stop[e, p], st[e, p]
+            if tp < best_t or (tp == best_t and rank[sp] < rank[best_s]):
+                best_t, best_s = tp, sp
+        t_free[e], status[e] = best_t, best_s
+        valid[e] = best_s == FREE
+        end[e] = goals[e] if mode == "connect" else (1.0 - tf) * starts[e] + tf * goals[e]
+    return valid, end, t_free, status
+
+
+def reference_cloud_continuous(sm, pts, r, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6,
+                               look_ahead=np.inf, dist=None, shapes=None, scene_orc=None):
+    """-> valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32, the cloud items' stop points and statuses (E, S_sel), and the
+    count of distance evaluations by exit (EXIT_*).  ``scene_orc`` (the Oracle of ``sm``): the accumulate form -- the reduction runs
+    over the scene's (edge, pair) items (continuous_ref.reference_continuous) and the cloud's together."""
+    starts = np.ascontiguousarray(starts, dtype=np.float64)
+    goals = np.ascontiguousarray(goals, dtype=np.float64)
+    E = starts.shape[0]
+    spans = [edge_span(starts[e], goals[e], None if dist is None else dist[e], max_distance, mode) for e in range(E)]
+    live = np.array([sp is not None for sp in spans], dtype=bool)
+    Tf = np.array([sp[1] if sp is not None else np.nan for sp in spans])
+    dist_fn = CloudDistance(sm, pts, r, shapes, starts, goals, Tf, threshold, slack, look_ahead)
+    K = dist_fn.sel.shape[0]
+    if K == 0 or dist_fn.pts.shape[0] == 0:                     # nothing to hit: no items
+        stop, st = np.zeros((E, 0)), np.zeros((E, 0), dtype=np.int32)
+    else:
+        stop, st = advance_items(dist_fn, dist_fn.mu, Tf, live, threshold, max_iter, slack)
+    all_stop, all_st = stop, st
+    if scene_orc is not None:
+        ref = reference_continuous(sm, scene_orc, starts, goals, max_distance, mode=mode, threshold=threshold, max_iter=max_iter,
+                                   slack=slack, dist=dist)
+        all_stop, all_st = np.concatenate((ref[4], stop), axis=1), np.concatenate((ref[5], st), axis=1)
+    return reduce_edges(all_stop, all_st, Tf, live, starts, goals, mode) + (stop, st, dist_fn.exits)
+
+
+def dense_cloud_min_distance(sm, pts, r, shapes, s, g, T_f=1.0, n=2000):
+    """min over n + 1 samples t in [0, T_f], the selected shapes and the points of the signed distance on the edge s -> g."""
+    from oracle.cpu_oracle import Oracle
+    t = np.linspace(0.0, T_f, n + 1)
+    q = (1.0 - t)[:, None] * s[None] + t[:, None] * g[None]
+    return min(pair_distances(Oracle(cloud_model(sm, pts, r, [int(x)])), q).min() for x in selection(sm, shapes))
+
+
+def plate_wall(spacing, half=0.35, x=0.45, z0=0.45):
+    """Points on the plane of continuous_ref.PLATE, a square lattice `spacing` apart over the plate's face."""
+    k = int(np.floor(half / spacing))
+    a = np.arange(-k, k + 1) * spacing
+    yy, zz = np.meshgrid(a, a, indexing="ij")
+    return np.stack((np.full(yy.size, x), yy.reshape(-1), z0 + zz.reshape(-1)), axis=1)

@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -21,6 +21,11 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
                 ahead of time (what had to be done without this entry, less its costs of writing the rows and reducing the mask),
                 whose per-edge AND must equal `valid`.  Then, at N = 1e5, the connector's sequence on the c2 scene -- edge_validity,
                 then the cloud call ANDed into its result -- next to its two parts alone
+    certified   (only when asked for) DeviceModel.cloud_edge_continuous on the c2 scene against scan(100 000) of radius 0.005: E = 1e4
+                of the edges above, ContinuousConnector's defaults (max_iter 64, slack 1e-6), at look_ahead 0.02, 0.05, 0.1, 0.2 and
+                inf: the time of the cloud call alone and of the connector's sequence (edge_continuous, then the cloud's items reduced
+                into its result), with the FREE / COLLISION / UNDECIDED counts of both.  The default look_ahead is the fastest value
+                whose UNDECIDED count is no higher than at inf
 """
 import argparse
 import os
@@ -166,6 +171,28 @@ def edges_part(dev, sm, chain, shapes, reps):
     say(f"    edge_validity, cloud_edge_validity(out) {fmt(timed(both, reps))}")
 
 
+def certified_part(dev, chain, shapes, reps):
+    E, N, radius = 10 ** 4, 10 ** 5, 0.005
+    s, g = edges(sample_q(chain, E, seed=1), E, 7, 1.0)
+    st, gt = torch.from_numpy(s).cuda(), torch.from_numpy(g).cuda()
+    d = torch.linalg.norm(gt - st, dim=1)
+    cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), radius, bounds=BOX)
+    say(f"certified: E = {E}, lengths U(0.02, 1.0), max_distance 1.0, connect, max_iter 64, slack 1e-6; N = {N}, radius {radius}")
+    counts = lambda status: " ".join(f"{name} {int((status == k).sum()):5d}" for k, name in enumerate(("FREE", "COLLISION", "UNDECIDED")))   # noqa: E731
+    own = dev.edge_continuous(st, gt, 1.0, dist=d)
+    say(f"  edge_continuous alone (the scene)   {fmt(timed(lambda: dev.edge_continuous(st, gt, 1.0, dist=d), reps))}   {counts(own[3])}")
+    for la in (0.02, 0.05, 0.1, 0.2, float("inf")):
+        alone = lambda: dev.cloud_edge_continuous(cloud, st, gt, 1.0, look_ahead=la, dist=d, shapes=shapes)      # noqa: E731
+
+        def both():
+            v, _, tf, status = dev.edge_continuous(st, gt, 1.0, dist=d)
+            dev.cloud_edge_continuous(cloud, st, gt, 1.0, look_ahead=la, dist=d, shapes=shapes, out=(v, tf, status))
+            return status
+        sa, sb = alone()[3], both()
+        say(f"  look_ahead {la:5.2f}: cloud alone {fmt(timed(alone, reps))}   {counts(sa)}")
+        say(f"                    scene + cloud {fmt(timed(both, reps))}   {counts(sb)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -189,7 +216,7 @@ def main():
     say(f"# cloud_time.py  kernels {source_digest()}  device {torch.cuda.get_device_name(0)}  robot c2 ({sm.n_rshapes} shapes, base left out)  radius {RADIUS}")
     q5 = torch.from_numpy(sample_q(chain, 10 ** 5, seed=1)).cuda()
     q6 = torch.from_numpy(sample_q(chain, 10 ** 6, seed=2)).cuda()
-    sizes = [n for n in (10 ** 3, 10 ** 4, 10 ** 5, 10 ** 6) if n <= a.max_n]
+    sizes = [n for n in (10 ** 3, 10 ** 4, 10 ** 5, 10 ** 6) if n <= a.max_n] if only & {"update", "validity", "clearance"} else []
     for N in sizes:
         pts = torch.from_numpy(scan(N, seed=N)).cuda()
         cloud = PointCloud(pts, RADIUS, bounds=BOX)
@@ -231,6 +258,8 @@ def main():
             say(f"  B = {name}: cloud {fmt(tc)}   sphere descriptor {fmt(tb)}   ratio {tb[0] / tc[0]:.2f}x   masks equal")
     if "edges" in only:
         edges_part(dev, sm, chain, shapes, a.reps)
+    if "certified" in only:
+        certified_part(dev, chain, shapes, a.reps)
 
 
 if __name__ == "__main__":
