@@ -2,7 +2,8 @@
 generated robots with 9 to 32 joints, built identically in every process; plain ``np.longdouble`` restatements of FK and of the
 Jacobian written from the KinematicModel tables alone (they share no code with the oracle); and a restatement of the LDS byte
 formulas by which the library decides whether an entry point serves a descriptor (csrc/nbk.hip ``*_lds()``, csrc/nbk_tables.hpp
-``check_limits``).  No test functions here."""
+``check_limits``).  The point-cloud ladder (tests/cloud_ladder_cases.py) reuses the cases k9, k16, k25, k32d and tree as they are.  No
+test functions here."""
 import os
 
 import numpy as np
