@@ -3427,25 +3427,41 @@ __global__ void k_edge_plan(int nq, const double* __restrict__ starts, const dou
 // ==== certified continuous edges (nbk_edge_continuous_batch): conservative advancement, one (edge, pair) item per lane ==========
 // Per edge, while the call runs, t_free holds a 64-bit key = bits(t) << 2 | rank (rank 0 COLLISION, 1 UNDECIDED, 2 FREE): stop points
 // lie in [0, T_f] and T_f <= 1, so bits(t) < 2^62 and the unsigned order of the keys is the order of t, then of the rank -- the
-// smallest stop point, COLLISION winning a tie.  k_edge_ca_init sets each key to "FREE at T_f", every item that stops lowers it
-// with one atomicMin, k_edge_ca_final decodes it.
+// smallest stop point, COLLISION winning a tie.  The entry's init kernel (k_edge_ca_init, k_spline_ca_init) sets each key to "FREE
+// at T_f", every item that stops lowers it with one atomicMin, k_ca_final decodes it -- for every certified entry, the spline's and
+// the cloud's (nbk_cloud.hpp) included.
 constexpr unsigned long long CA_COLLISION = 0ull, CA_UNDECIDED = 1ull, CA_FREE = 2ull;
+// The init kernel marks a trajectory none of whose items run with a reserved key.  No item can post either: posted ranks are 0..2,
+// and real keys are below 2^64 - 4.
+constexpr unsigned long long CA_DEGENERATE_KEY = 3ull;          // the result is 0 / NaN / DEGENERATE
+constexpr unsigned long long CA_KEEP_KEY = ~0ull;               // the result is 0 / NaN / UNDECIDED
 
 NBK_DEV unsigned long long ca_key(double t, unsigned long long rank) { return (__builtin_bit_cast(unsigned long long, t) << 2) | rank; }
 
+// hold (nullable): a status word that, when set, makes CA_KEEP_KEY of every non-degenerate edge (a cloud's hdr->status).
+// prev (nullable): accumulating -- the status array of the certified call whose t_free the keys alias; each key is re-encoded from
+// the two, and an edge that comes in with a NaN t_free keeps CA_KEEP_KEY.
 __global__ void k_edge_ca_init(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
-                               int64_t E, double max_distance, int mode, double* __restrict__ end, unsigned long long* __restrict__ key) {
+                               int64_t E, double max_distance, int mode, const int* __restrict__ hold, const int32_t* __restrict__ prev,
+                               double* __restrict__ end, unsigned long long* __restrict__ key) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
     const double* s = starts + e * nq;
     const double* g = goals + e * nq;
     double d, Tf;
     if (!edge_span(nq, s, g, dist, e, max_distance, mode, d, Tf)) {
-        key[e] = 0ull;
+        key[e] = CA_DEGENERATE_KEY;
         if (end) for (int i = 0; i < nq; ++i) end[e * nq + i] = __builtin_nan("");
         return;
     }
-    key[e] = ca_key(Tf, CA_FREE);
+    unsigned long long k = ca_key(Tf, CA_FREE);
+    if (prev) {
+        const double t0 = __builtin_bit_cast(double, key[e]);
+        const int32_t st = prev[e];
+        k = t0 != t0 ? CA_KEEP_KEY : ca_key(t0, st == NBK_CA_FREE ? CA_FREE : (st == NBK_CA_COLLISION ? CA_COLLISION : CA_UNDECIDED));
+    }
+    if (hold && *hold != 0) k = CA_KEEP_KEY;
+    key[e] = k;
     write_edge_end(nq, s, g, e, mode, Tf, end);
 }
 
@@ -3530,17 +3546,16 @@ __global__ __launch_bounds__(64) void k_edge_ca(DevModel m, const double* __rest
     ca_walk(m, tr, run, pu, p, lane, thr, max_iter, slack, key + e);
 }
 
-__global__ void k_edge_ca_final(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
-                                int64_t E, double max_distance, int mode, const unsigned long long* __restrict__ key,
-                                uint8_t* __restrict__ valid, double* __restrict__ t_free, int32_t* __restrict__ status) {
+// key -> valid / t_free / status of the n trajectories of any certified entry, from the key alone
+__global__ void k_ca_final(int64_t n, const unsigned long long* __restrict__ key, uint8_t* __restrict__ valid, double* __restrict__ t_free,
+                           int32_t* __restrict__ status) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    double d, Tf;
-    if (!edge_span(nq, starts + e * nq, goals + e * nq, dist, e, max_distance, mode, d, Tf)) {
-        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = NBK_CA_DEGENERATE;
+    if (e >= n) return;
+    const unsigned long long k = key[e];          // t_free aliases key: read before the write
+    if (k == CA_DEGENERATE_KEY || k == CA_KEEP_KEY) {
+        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = k == CA_KEEP_KEY ? NBK_CA_UNDECIDED : NBK_CA_DEGENERATE;
         return;
     }
-    const unsigned long long k = key[e];          // t_free aliases key: read before the write
     const unsigned long long r = k & 3ull;
     valid[e] = r == CA_FREE ? 1 : 0;
     status[e] = r == CA_FREE ? NBK_CA_FREE : (r == CA_COLLISION ? NBK_CA_COLLISION : NBK_CA_UNDECIDED);
@@ -3730,9 +3745,7 @@ __global__ __launch_bounds__(64) void k_spline_reduce(const double* __restrict__
 
 // ==== certified continuous B-splines (nbk_spline_continuous_batch): ca_walk on SplineLane<K>, keys as the edge path's ==============
 // A degenerate trajectory (V outside (2^-23, DBL_MAX], a non-finite control point, or knots that are not finite, nondecreasing and
-// clamped on [0, 1]) gets the key CA_DEGENERATE_KEY (rank 3, which no item posts): no item of it runs, and the final kernel reads
-// DEGENERATE from the key alone.
-constexpr unsigned long long CA_DEGENERATE_KEY = 3ull;
+// clamped on [0, 1]) gets the key CA_DEGENERATE_KEY: no item of it runs.
 
 // one wave per trajectory: key[s] = "FREE at 1", or CA_DEGENERATE_KEY
 __global__ __launch_bounds__(64) void k_spline_ca_init(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
@@ -3791,18 +3804,6 @@ __global__ __launch_bounds__(64) void k_spline_ca(DevModel m, const double* __re
     SplineLane<K> tr{ctrl + (size_t)s * (size_t)n * m.n_q, knots, lds + lane * m.n_q, n, m.n_q, K};
     const bool run = live && key[s] != CA_DEGENERATE_KEY;
     ca_walk(m, tr, run, pu, p, lane, thr, max_iter, slack, key + s);
-}
-
-__global__ void k_spline_ca_final(int64_t S, const unsigned long long* __restrict__ key, uint8_t* __restrict__ valid,
-                                  double* __restrict__ t_free, int32_t* __restrict__ status) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    const unsigned long long k = key[s];          // t_free aliases key: read before the write
-    const unsigned long long r = k & 3ull;
-    if (k == CA_DEGENERATE_KEY) { valid[s] = 0; t_free[s] = __builtin_nan(""); status[s] = NBK_CA_DEGENERATE; return; }
-    valid[s] = r == CA_FREE ? 1 : 0;
-    status[s] = r == CA_FREE ? NBK_CA_FREE : (r == CA_COLLISION ? NBK_CA_COLLISION : NBK_CA_UNDECIDED);
-    t_free[s] = __builtin_bit_cast(double, k >> 2);
 }
 
 }  // namespace nbk
@@ -4872,6 +4873,26 @@ static bool edge_args_ok(unsigned rules, double resolution, double max_distance,
     return !((rules & RULE_THRESHOLD) && threshold != threshold);
 }
 
+// What the certified entries share (edges, splines, edges against a cloud): init -> walk -> final, with the keys held in the
+// caller's t_free while the call runs.
+static unsigned long long* ca_keys(double* t_free) { return reinterpret_cast<unsigned long long*>(t_free); }
+
+// hold, prev: as k_edge_ca_init (both null for the scene's own edges)
+static int32_t launch_edge_ca_init(const nbk_model* m, hipStream_t st, const double* starts, const double* goals, const double* dist, int64_t E,
+                                   double max_distance, int32_t mode, const int* hold, const int32_t* prev, double* end, double* t_free) {
+    hipLaunchKernelGGL(k_edge_ca_init, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance,
+                       (int)mode, hold, prev, end, ca_keys(t_free));
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+static int32_t launch_ca_final(hipStream_t st, int64_t n, uint8_t* valid, double* t_free, int32_t* status) {
+    hipLaunchKernelGGL(k_ca_final, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const unsigned long long*)ca_keys(t_free), valid,
+                       t_free, status);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
 int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
                                   double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
                                   uint8_t* valid, double* end, double* t_free, int32_t* status, void* stream) {
@@ -4883,18 +4904,13 @@ int32_t nbk_edge_continuous_batch(const nbk_model* m, const double* starts, cons
     const int64_t N = E * (int64_t)m->n_pairs;
     if (E > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(t_free);
-    const unsigned eb = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(k_edge_ca_init, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode, end, key);
-    NBK_HIP(hipGetLastError());
+    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, nullptr, nullptr, end, t_free); if (rc != NBK_OK) return rc; }
     if (N > 0) {
         hipLaunchKernelGGL(k_edge_ca, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), 0, st, m->d, starts, goals, dist, E,
-                           max_distance, (int)mode, threshold, (int)max_iter, slack, key);
+                           max_distance, (int)mode, threshold, (int)max_iter, slack, ca_keys(t_free));
         NBK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_edge_ca_final, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
-                       (const unsigned long long*)key, valid, t_free, status);
-    NBK_HIP(hipGetLastError());
+    { const int32_t rc = launch_ca_final(st, E, valid, t_free, status); if (rc != NBK_OK) return rc; }
     return guard_verdicts(m, st, valid, status, nullptr, t_free, E);
 }
 
@@ -5152,7 +5168,7 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
     const int64_t N = S * (int64_t)m->n_pairs;
     if (S > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(t_free);
+    unsigned long long* key = ca_keys(t_free);
     hipLaunchKernelGGL(k_spline_ca_init, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, key);
     NBK_HIP(hipGetLastError());
     if (N > 0) {
@@ -5163,9 +5179,7 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
         });
         NBK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_spline_ca_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const unsigned long long*)key, valid,
-                       t_free, status);
-    NBK_HIP(hipGetLastError());
+    { const int32_t rc = launch_ca_final(st, S, valid, t_free, status); if (rc != NBK_OK) return rc; }
     return guard_verdicts(m, st, valid, status, nullptr, t_free, S);
 }
 

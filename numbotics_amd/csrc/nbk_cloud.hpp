@@ -22,6 +22,9 @@
 // Sampled edges (nbk_edge_cloud_validity_batch): the edge rule is nbk.hip's own (k_edge_plan, k_scan, edge_sample_row); the samples of
 // all edges form one flat range that k_cloud_edges walks one sample per lane with the walk of k_cloud_validity (cloud_row_hits).  Plan,
 // counts and offsets live in the caller's workspace (EdgeCloudLayout, nbk_plan.hpp).
+//
+// Certified edges (nbk_edge_cloud_continuous_batch): nbk.hip's k_edge_ca_init -> k_cloud_edge_ca (ca_walk on CloudEdgeLane) -> nbk.hip's
+// k_ca_final; the keys and their reserved values are defined once, beside ca_key.
 #pragma once
 #define NBK_GRID_FN __host__ __device__ inline
 #include "nbk_cloud_grid.hpp"
@@ -388,8 +391,8 @@ __global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd,
 }
 
 // ---- certified continuous edges against the cloud (nbk_edge_cloud_continuous_batch) --------------------------------------------
-// ca_walk (nbk.hip) as it is, on one (edge e, selected robot shape s) item per lane; keys, ranks and the per-edge reduction are those
-// of nbk_edge_continuous_batch.  The grid is (ceil(E / 64), selected shapes): a wave holds ONE shape, so Core.kind and the hull are
+// ca_walk (nbk.hip) as it is, on one (edge e, selected robot shape s) item per lane; keys, ranks, the per-edge reduction and the
+// kernels around the walk (k_edge_ca_init, k_ca_final) are those of nbk_edge_continuous_batch.  The grid is (ceil(E / 64), selected shapes): a wave holds ONE shape, so Core.kind and the hull are
 // wave-uniform as the cloud routines above need them (a pair-major flat index would straddle shapes).  LDS: [64][n_q] q rows.
 //
 // The item's motion bound is mu_s = shape_motion_bound (every joint on the shape's path counts: the cloud stands still), and its
@@ -401,34 +404,9 @@ __global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd,
 //     is what ca_walk makes of +inf (gap is infinite, the advance reaches hi = T_f) -- no new branch;
 //   * a distance >= D_cap reported as D_cap is a lower bound of it, and advancing on a lower bound is conservative.
 // look_ahead bounds the ball a step walks, and so the points a lane meets: without it the first step of a long edge walks the whole
-// cloud.  A reserved key (real keys are < 2^64 - 4) marks the edges whose items do not run and whose result is 0 / UNDECIDED / NaN:
-// every non-degenerate edge while the cloud's status is set, and -- accumulating -- those that come in with a NaN t_free.
-constexpr unsigned long long CA_KEEP_KEY = ~0ull;
-
-// accumulate: valid / t_free (= key) / status hold what nbk_edge_continuous_batch wrote for these edges; the key is re-encoded from them
-__global__ void k_cloud_ca_init(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
-                                int64_t E, double max_distance, int mode, const CloudHdr* __restrict__ hdr, int accumulate,
-                                const int32_t* __restrict__ status, double* __restrict__ end, unsigned long long* __restrict__ key) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double* s = starts + e * nq;
-    const double* g = goals + e * nq;
-    double d, Tf;
-    if (!edge_span(nq, s, g, dist, e, max_distance, mode, d, Tf)) {
-        key[e] = 0ull;
-        if (end) for (int i = 0; i < nq; ++i) end[e * nq + i] = __builtin_nan("");
-        return;
-    }
-    unsigned long long k = ca_key(Tf, CA_FREE);
-    if (accumulate) {
-        const double t0 = __builtin_bit_cast(double, key[e]);
-        const int32_t st = status[e];
-        k = t0 != t0 ? CA_KEEP_KEY : ca_key(t0, st == NBK_CA_FREE ? CA_FREE : (st == NBK_CA_COLLISION ? CA_COLLISION : CA_UNDECIDED));
-    }
-    if (hdr->status != 0) k = CA_KEEP_KEY;
-    key[e] = k;
-    write_edge_end(nq, s, g, e, mode, Tf, end);
-}
+// cloud.  k_edge_ca_init (nbk.hip) gives CA_KEEP_KEY to the edges whose items do not run and whose result is 0 / UNDECIDED / NaN:
+// every non-degenerate edge while the cloud's status is set, and -- accumulating into what nbk_edge_continuous_batch wrote for these
+// edges -- those that come in with a NaN t_free.
 
 // the linear edge of EdgeLane for one robot shape against the cloud (pu: the shape's caller's index, p: its device index)
 struct CloudEdgeLane {
@@ -497,27 +475,6 @@ __global__ __launch_bounds__(64) void k_cloud_edge_ca(DevModel m, CloudDev cd, C
     const bool run = live && n > 0 && edge_span(m.n_q, tr.s, tr.g, dist, e, max_distance, mode, d_edge, tr.Tf) &&
                      __hip_atomic_load(key + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != CA_KEEP_KEY;
     ca_walk(m, tr, run, rs_user[p], p, lane, thr, max_iter, slack, key + e);
-}
-
-__global__ void k_cloud_ca_final(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
-                                 int64_t E, double max_distance, int mode, const unsigned long long* __restrict__ key,
-                                 uint8_t* __restrict__ valid, double* __restrict__ t_free, int32_t* __restrict__ status) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    double d, Tf;
-    if (!edge_span(nq, starts + e * nq, goals + e * nq, dist, e, max_distance, mode, d, Tf)) {
-        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = NBK_CA_DEGENERATE;
-        return;
-    }
-    const unsigned long long k = key[e];          // t_free aliases key: read before the write
-    if (k == CA_KEEP_KEY) {
-        valid[e] = 0; t_free[e] = __builtin_nan(""); status[e] = NBK_CA_UNDECIDED;
-        return;
-    }
-    const unsigned long long r = k & 3ull;
-    valid[e] = r == CA_FREE ? 1 : 0;
-    status[e] = r == CA_FREE ? NBK_CA_FREE : (r == CA_COLLISION ? NBK_CA_COLLISION : NBK_CA_UNDECIDED);
-    t_free[e] = __builtin_bit_cast(double, k >> 2);
 }
 
 }  // namespace nbk
@@ -736,20 +693,15 @@ int32_t nbk_edge_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, 
     if (!sel.all) { n_sel = 0; for (int k = 0; k < 4; ++k) n_sel += __builtin_popcountll(sel.w[k]); }
     if (n_sel > 65535) return NBK_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(t_free);
-    const unsigned eb = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(k_cloud_ca_init, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
-                       (const CloudHdr*)c->hdr, (int)accumulate, (const int32_t*)status, end, key);
-    NBK_HIP(hipGetLastError());
+    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, &c->hdr->status, accumulate ? status : nullptr, end, t_free);
+      if (rc != NBK_OK) return rc; }
     if (n_sel > 0) {
         hipLaunchKernelGGL(k_cloud_edge_ca, dim3(blocks_for(E), (unsigned)n_sel), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c),
-                           sel, m->rs_user, starts, goals, dist, E, max_distance, (int)mode, threshold, (int)max_iter, slack, look_ahead, key);
+                           sel, m->rs_user, starts, goals, dist, E, max_distance, (int)mode, threshold, (int)max_iter, slack, look_ahead,
+                           ca_keys(t_free));
         NBK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_cloud_ca_final, dim3(eb), dim3(256), 0, st, m->n_q, starts, goals, dist, E, max_distance, (int)mode,
-                       (const unsigned long long*)key, valid, t_free, status);
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return launch_ca_final(st, E, valid, t_free, status);
 }
 
 }  // extern "C"

@@ -4,12 +4,13 @@ for the tests.
 One item per (edge, selected robot shape): mu from nbk_edge_shape_motion_bounds_host, the shape's clearance from the oracle on
 ``cloud_model(sm, pts, r, [shape])`` (the cloud's points as sphere world shapes: the bits the device computes), q(t) in three
 roundings, the cut D = min(D_end, D_cap) and the three-way rule of include/nbk.h in its operation order.  The loop and the per-edge
-reduction are those of tests/continuous_ref.py; the accumulate form reduces over the scene's items and the cloud's together."""
+reduction are those of tests/ca_ref.py; the accumulate form reduces over the scene's items and the cloud's together."""
 import numpy as np
 
 from numbotics_amd.engine import edge_shape_motion_bounds
 from cloud_cases import cloud_model
-from continuous_ref import edge_span, pair_distances, reference_continuous, FREE, COLLISION, UNDECIDED, DEGENERATE
+from ca_ref import advance_items, reduce_items
+from continuous_ref import edge_ends, edge_span, pair_distances, reference_continuous
 
 EXIT_POINT, EXIT_INF, EXIT_CAP, EXIT_NAN = 0, 1, 2, 3       # how a distance evaluation ended
 
@@ -54,69 +55,6 @@ class CloudDistance:
         return d
 
 
-def advance_items(distance, mu, Tf, live, threshold, max_iter, slack):
-    """The loop of continuous_ref.reference_continuous on items (E, K) with ``distance(ee, kk, tt)`` -> stop (E, K), status (E, K)
-    (-1 / NaN for the items of edges that are not ``live``)."""
-    E, K = mu.shape
-    t = np.zeros((E, K))
-    stop = np.full((E, K), np.nan)
-    st = np.full((E, K), -1, dtype=np.int32)
-    active = np.zeros((E, K), dtype=bool)
-    active[live, :] = True
-    for _ in range(max_iter):
-        ee, kk = np.nonzero(active)
-        if ee.shape[0] == 0:
-            break
-        tt = t[ee, kk]
-        d = distance(ee, kk, tt)
-        m = mu[ee, kk]
-        col = d <= threshold
-        with np.errstate(invalid="ignore"):
-            gap = (d - threshold) - slack
-        und = ~col & ~(gap > 0.0)
-        rest = ~col & ~und
-        free0 = rest & (m == 0.0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            tn = tt + gap / m
-        free1 = rest & ~free0 & (tn >= Tf[ee])
-        adv = rest & ~free0 & ~free1
-        for mask, code in ((col, COLLISION), (und, UNDECIDED)):
-            stop[ee[mask], kk[mask]] = tt[mask]
-            st[ee[mask], kk[mask]] = code
-        fr = free0 | free1
-        stop[ee[fr], kk[fr]] = Tf[ee[fr]]
-        st[ee[fr], kk[fr]] = FREE
-        active[ee[~adv], kk[~adv]] = False
-        t[ee[adv], kk[adv]] = tn[adv]
-    ee, kk = np.nonzero(active)
-    stop[ee, kk] = t[ee, kk]
-    st[ee, kk] = UNDECIDED
-    return stop, st
-
-
-def reduce_edges(stop, st, Tf, live, starts, goals, mode):
-    """Per edge the smallest stop point over its items, COLLISION before UNDECIDED before FREE on a tie (explicit loops)."""
-    E, nq = starts.shape
-    valid = np.zeros(E, dtype=bool)
-    t_free = np.full(E, np.nan)
-    status = np.full(E, DEGENERATE, dtype=np.int32)
-    end = np.full((E, nq), np.nan)
-    rank = {COLLISION: 0, UNDECIDED: 1, FREE: 2}
-    for e in range(E):
-        if not live[e]:
-            continue
-        tf = Tf[e]
-        best_t, best_s = tf, FREE
-        for p in range(stop.shape[1]):
-            tp, sp = stop[e, p], st[e, p]
-            if tp < best_t or (tp == best_t and rank[sp] < rank[best_s]):
-                best_t, best_s = tp, sp
-        t_free[e], status[e] = best_t, best_s
-        valid[e] = best_s == FREE
-        end[e] = goals[e] if mode == "connect" else (1.0 - tf) * starts[e] + tf * goals[e]
-    return valid, end, t_free, status
-
-
 def reference_cloud_continuous(sm, pts, r, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6,
                                look_ahead=np.inf, dist=None, shapes=None, scene_orc=None):
     """-> valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32, the cloud items' stop points and statuses (E, S_sel), and the
@@ -139,7 +77,8 @@ def reference_cloud_continuous(sm, pts, r, starts, goals, max_distance, mode="co
         ref = reference_continuous(sm, scene_orc, starts, goals, max_distance, mode=mode, threshold=threshold, max_iter=max_iter,
                                    slack=slack, dist=dist)
         all_stop, all_st = np.concatenate((ref[4], stop), axis=1), np.concatenate((ref[5], st), axis=1)
-    return reduce_edges(all_stop, all_st, Tf, live, starts, goals, mode) + (stop, st, dist_fn.exits)
+    valid, t_free, status = reduce_items(all_stop, all_st, Tf, live)
+    return valid, edge_ends(starts, goals, Tf, live, mode), t_free, status, stop, st, dist_fn.exits
 
 
 def dense_cloud_min_distance(sm, pts, r, shapes, s, g, T_f=1.0, n=2000):

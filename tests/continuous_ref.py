@@ -1,9 +1,8 @@
 """NumPy + CPU-oracle restatement of nbk_edge_continuous_batch (ContinuousConnector's device path), for the tests.
 
 Conservative advancement per (edge, pair) item: mu from nbk_edge_motion_bounds_host, distances from ``Oracle.pair_distances``
-(the bits the device computes), q(t) = (1 - t) * s + t * g with three roundings, the loop of include/nbk.h.  Per-edge
-reductions run in explicit loops.  The items of one iteration are evaluated together; the oracle runs in a few threads (ctypes
-releases the GIL)."""
+(the bits the device computes), q(t) = (1 - t) * s + t * g with three roundings; the loop of include/nbk.h and the per-edge
+reduction are those of tests/ca_ref.py.  The oracle runs in a few threads (ctypes releases the GIL)."""
 import math
 from concurrent.futures import ThreadPoolExecutor
 from fractions import Fraction
@@ -11,8 +10,8 @@ from fractions import Fraction
 import numpy as np
 
 from numbotics_amd.engine import edge_motion_bounds
+from ca_ref import advance_items, reduce_items, FREE, COLLISION, UNDECIDED, DEGENERATE      # noqa: F401  (the codes: for the tests)
 
-FREE, COLLISION, UNDECIDED, DEGENERATE = 0, 1, 2, 3
 F32_EPS = 1.1920928955078125e-07
 DBL_MAX = 1.7976931348623157e308
 
@@ -45,69 +44,31 @@ def pair_distances(orc, q, threads=8):
         return np.concatenate(list(ex.map(orc.pair_distances, chunks)), axis=0)
 
 
+def edge_ends(starts, goals, Tf, live, mode):
+    """end (E, n_q): the goal, or q(T_f) in three roundings under "steer"; NaN rows where not ``live``."""
+    end = np.full(starts.shape, np.nan)
+    for e in np.nonzero(live)[0]:
+        end[e] = goals[e] if mode == "connect" else (1.0 - Tf[e]) * starts[e] + Tf[e] * goals[e]
+    return end
+
+
 def reference_continuous(sm, orc, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
     """-> valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32, and the per-item stop points / statuses (E, P)."""
     starts = np.ascontiguousarray(starts, dtype=np.float64)
     goals = np.ascontiguousarray(goals, dtype=np.float64)
-    E, nq = starts.shape
+    E = starts.shape[0]
     P = sm.n_pairs
     mu = edge_motion_bounds(sm, starts, goals) if P > 0 else np.zeros((E, 0))
     spans = [edge_span(starts[e], goals[e], None if dist is None else dist[e], max_distance, mode) for e in range(E)]
     Tf = np.array([sp[1] if sp is not None else np.nan for sp in spans])
-    t = np.zeros((E, P))
-    stop = np.full((E, P), np.nan)
-    st = np.full((E, P), -1, dtype=np.int32)
-    active = np.zeros((E, P), dtype=bool)
-    for e in range(E):
-        if spans[e] is not None:
-            active[e, :] = True
-    for _ in range(max_iter):
-        ee, pp = np.nonzero(active)
-        n = ee.shape[0]
-        if n == 0:
-            break
-        tt = t[ee, pp]
+    live = np.array([sp is not None for sp in spans], dtype=bool)
+
+    def distance(ee, pp, tt):
         q = (1.0 - tt)[:, None] * starts[ee] + tt[:, None] * goals[ee]
-        d = pair_distances(orc, q)[np.arange(n), pp]
-        m = mu[ee, pp]
-        col = d <= threshold
-        gap = (d - threshold) - slack
-        und = ~col & ~(gap > 0.0)
-        rest = ~col & ~und
-        free0 = rest & (m == 0.0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            tn = tt + gap / m
-        free1 = rest & ~free0 & (tn >= Tf[ee])
-        adv = rest & ~free0 & ~free1
-        for mask, code in ((col, COLLISION), (und, UNDECIDED)):
-            stop[ee[mask], pp[mask]] = tt[mask]
-            st[ee[mask], pp[mask]] = code
-        fr = free0 | free1
-        stop[ee[fr], pp[fr]] = Tf[ee[fr]]
-        st[ee[fr], pp[fr]] = FREE
-        active[ee[~adv], pp[~adv]] = False
-        t[ee[adv], pp[adv]] = tn[adv]
-    ee, pp = np.nonzero(active)
-    stop[ee, pp] = t[ee, pp]
-    st[ee, pp] = UNDECIDED
-    # per edge, explicit loops
-    valid = np.zeros(E, dtype=bool)
-    t_free = np.full(E, np.nan)
-    status = np.full(E, DEGENERATE, dtype=np.int32)
-    end = np.full((E, nq), np.nan)
-    for e in range(E):
-        if spans[e] is None:
-            continue
-        tf = Tf[e]
-        best_t, best_s = tf, FREE
-        rank = {COLLISION: 0, UNDECIDED: 1, FREE: 2}
-        for p in range(P):
-            tp, sp = stop[e, p], st[e, p]
-            if tp < best_t or (tp == best_t and rank[sp] < rank[best_s]):
-                best_t, best_s = tp, sp
-        t_free[e], status[e] = best_t, best_s
-        valid[e] = best_s == FREE
-        end[e] = goals[e] if mode == "connect" else (1.0 - tf) * starts[e] + tf * goals[e]
+        return pair_distances(orc, q)[np.arange(ee.shape[0]), pp]
+    stop, st = advance_items(distance, mu, Tf, live, threshold, max_iter, slack)
+    valid, t_free, status = reduce_items(stop, st, Tf, live)
+    end = edge_ends(starts, goals, Tf, live, mode)
     return valid, end, t_free, status, stop, st
 
 

@@ -3,13 +3,14 @@
 Conservative advancement per (trajectory, pair) item across the knot spans: q(t) from ``spline_ref.de_boor`` (the bits of
 ``UnitBSpline.__call__``), distances from ``Oracle.pair_distances``, mu per span from ``spline_motion_bounds``, the loop of
 include/nbk.h.  The advance runs per item in plain Python floats (every operation separately rounded, as the device's); the
-per-trajectory reductions run in explicit loops, as in ``continuous_ref.reference_continuous``."""
+per-trajectory reduction is ``ca_ref.reduce_items``."""
 import math
 
 import numpy as np
 
 from numbotics_amd.engine import spline_motion_bounds
-from continuous_ref import pair_distances, FREE, COLLISION, UNDECIDED, DEGENERATE
+from ca_ref import reduce_items, FREE, COLLISION, UNDECIDED
+from continuous_ref import pair_distances
 from spline_ref import de_boor, speed_bound, MIN_SPEED, DBL_MAX
 
 
@@ -91,22 +92,7 @@ def reference_spline_continuous(sm, orc, ctrl, knots, k, threshold=0.0, max_iter
     ss, pp = np.nonzero(active)
     stop[ss, pp] = t[ss, pp]
     st[ss, pp] = UNDECIDED
-    # per trajectory, explicit loops
-    valid = np.zeros(S, dtype=bool)
-    t_free = np.full(S, np.nan)
-    status = np.full(S, DEGENERATE, dtype=np.int32)
-    rank = {COLLISION: 0, UNDECIDED: 1, FREE: 2}
-    for s in range(S):
-        if deg[s]:
-            continue
-        best_t, best_s = 1.0, FREE
-        for p in range(P):
-            tp, sp = stop[s, p], st[s, p]
-            if tp < best_t or (tp == best_t and rank[sp] < rank[best_s]):
-                best_t, best_s = tp, sp
-        t_free[s], status[s] = best_t, best_s
-        valid[s] = best_s == FREE
-    return valid, t_free, status, stop, st
+    return reduce_items(stop, st, np.ones(S), ~deg) + (stop, st)
 
 
 def motion_bounds_numpy(sm, ctrl, knots, k):

@@ -1,5 +1,5 @@
 """Certified continuous B-spline checks on the device (nbk_spline_continuous_batch: k_spline_ca_init, k_spline_ca<K>,
-k_spline_ca_final): valid / t_free / status bit-identical to the NumPy + oracle restatement (tests/spline_continuous_ref.py), the
+k_ca_final): valid / t_free / status bit-identical to the NumPy + oracle restatement (tests/spline_continuous_ref.py), the
 two-point linear spline against the edge path, soundness on the thin plate and against the sampled check, graph capture, degenerate
 input, other descriptors and the C layer's error codes.  Needs a real MI355X."""
 import numpy as np

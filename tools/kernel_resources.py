@@ -3,7 +3,8 @@ summary comments (hipcc -S).  Usage: python tools/kernel_resources.py [substring
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from numbotics_amd.csrc.build import FLAGS, hipcc
+from numbotics_amd.csrc.build import FLAGS, hipcc, write_spec_inc
+write_spec_inc()                 # nbk.hip includes the generated header text
 flags = [f for f in FLAGS if f not in ("-shared", "-fPIC")]
 with tempfile.TemporaryDirectory() as d:
     out = os.path.join(d, "nbk.s")
