@@ -35,15 +35,15 @@ constexpr int HULL_LDS_MAX = 16 * 1024;    // k_narrow*: the scene's hull vertic
                                            // times faster than the vector memory path)
 
 // Every layout lists its regions in the order they lie in LDS.  Its members are the regions' lengths, `<region>_len`, in elements of the
-// region's own type (double unless the comment says otherwise); `<region>_at()` is the region's byte offset, the sum of what lies before
-// it.  A kernel steps through the regions by their lengths (next = previous + L.previous_len, re-typed where the element type changes):
-// the same chain of pointer additions it always had.  bytes() is what the launch asks for, fits() whether a workgroup can have it.  A
-// constructor computes the lengths and nothing else (the kernels run it); what only the byte count needs is kept as given and worked
-// out in bytes().  An argument that only sizes the last region comes last and has a default: the kernel, which needs no end, leaves it out.
-// What this does NOT make single: the order of the regions and the element type each is re-typed to are written here, in the chain of
-// <region>_at() that bytes() sums and tests/lds_check.cpp proves bounds, overlap and alignment over, AND in the kernel's chain of pointer
-// additions over the same lengths.  The two are held equal by reading them side by side, not by a check.  (Kernels that add <region>_at()
-// to the base would close that gap, but compile to other code in some 20 kernels: DESIGN.md 2.)
+// region's own type (double unless the comment says otherwise); `<region>(base)` is the region's pointer, of its own element type, in
+// the dynamic LDS that starts at `base`: the previous region's pointer plus the previous region's length, re-typed inside the accessor
+// where the type changes -- the chain of pointer additions the kernels always had, written once.  Order and types stand nowhere else:
+// every kernel of nbk.hip takes its region pointers from the accessors of a named `const ...Lds L(...)`, and tests/lds_check.cpp proves
+// its properties over what the same accessors return for a host buffer (begin = pointer - base, element size = sizeof(*pointer)).
+// bytes() is what the launch asks for, a sum over the lengths, fits() whether a workgroup can have it.  A constructor computes the
+// lengths and nothing else (the kernels run it); what only the byte count needs is kept as given and worked out in bytes().  An argument
+// that only sizes the last region comes last and has a default: the kernel, which needs no end, leaves it out.  Out of scope: the kernel
+// compiled per robot (nbk_bf32_spec.hpp) travels to hipRTC as text and carves its slab for itself.
 #define NBK_LDS_TOTAL(expr) NBK_HD size_t bytes() const { return (expr); } NBK_HD bool fits() const { return bytes() <= LDS_MAX; }
 
 // ---- kinematics ---------------------------------------------------------------------------------------------------------------------
@@ -58,18 +58,20 @@ struct FkLds {
 struct FkFramesLds {
     int q_len, fr_len, n_q;
     NBK_HD FkFramesLds(int n_q_, int frame_slots) : q_len(LDS_WAVE * n_q_), fr_len(LDS_WAVE * 12 * frame_slots), n_q(n_q_) {}
-    NBK_HD size_t fr_at() const { return sizeof(double) * (size_t)q_len; }
-    NBK_HD size_t t_at() const { return fr_at() + sizeof(double) * (size_t)fr_len; }
+    NBK_HD double* q(double* base) const { return base; }
+    NBK_HD double* fr(double* base) const { return q(base) + q_len; }
+    NBK_HD double* t(double* base) const { return fr(base) + fr_len; }
     NBK_HD size_t t_len() const { return (size_t)LDS_WAVE * FkLds(n_q).rows(); }
-    NBK_LDS_TOTAL(t_at() + sizeof(double) * t_len())
+    NBK_LDS_TOTAL(sizeof(double) * ((size_t)q_len + (size_t)fr_len + t_len()))
 };
 // k_jacobian: raw q slab [64][n_q] | output rows [64][stride], stride = 6 n_q | 1 (odd: conflict-free)
 struct JacobianLds {
     int q_len, n_q;
     NBK_HD explicit JacobianLds(int n_q_) : q_len(LDS_WAVE * n_q_), n_q(n_q_) {}
     NBK_HD int stride() const { return (6 * n_q) | 1; }
-    NBK_HD size_t o_at() const { return sizeof(double) * (size_t)q_len; }
-    NBK_LDS_TOTAL(o_at() + sizeof(double) * LDS_WAVE * (size_t)(6 * n_q + 1))
+    NBK_HD double* q(double* base) const { return base; }
+    NBK_HD double* o(double* base) const { return q(base) + q_len; }
+    NBK_LDS_TOTAL(sizeof(double) * ((size_t)q_len + LDS_WAVE * (size_t)(6 * n_q + 1)))
 };
 // k_jacobian_reg (paths of up to 8 joints): raw q slab [64][n_q]; the output rows [JAC_ROWS][stride] reuse it from 0 once q is read
 struct JacobianRegLds {
@@ -78,22 +80,25 @@ struct JacobianRegLds {
     NBK_HD int stride() const { return (6 * n_q) | 1; }
     NBK_HD size_t q_len() const { return (size_t)LDS_WAVE * n_q; }
     NBK_HD size_t o_len() const { return (size_t)JAC_ROWS * stride(); }
+    NBK_HD double* q(double* base) const { return base; }   NBK_HD double* o(double* base) const { return q(base); }
     NBK_LDS_TOTAL(sizeof(double) * (q_len() > o_len() ? q_len() : o_len()))
 };
 // k_ik: q rows [n_q][64] | Jacobian [6 n_q][64] | joint axes and origins [6 path_len][64] (one joint at least)
 struct IkLds {
     int q_len, J_len, path_len;
     NBK_HD explicit IkLds(int n_q, int path_len_ = 1) : q_len(LDS_WAVE * n_q), J_len(LDS_WAVE * 6 * n_q), path_len(path_len_) {}
-    NBK_HD size_t J_at() const { return sizeof(double) * (size_t)q_len; }
-    NBK_HD size_t jz_at() const { return J_at() + sizeof(double) * (size_t)J_len; }
+    NBK_HD double* q(double* base) const { return base; }
+    NBK_HD double* J(double* base) const { return q(base) + q_len; }
+    NBK_HD double* jz(double* base) const { return J(base) + J_len; }
     NBK_HD size_t jz_len() const { return (size_t)LDS_WAVE * 6 * (size_t)(path_len > 0 ? path_len : 1); }
-    NBK_LDS_TOTAL(jz_at() + sizeof(double) * jz_len())
+    NBK_LDS_TOTAL(sizeof(double) * ((size_t)q_len + (size_t)J_len + jz_len()))
 };
 // k_pair_items: q rows [64][n_q] (room for one row at least) | with gradient rows: joint axes and origins [6 n_joints][64]
 struct PairItemsLds {
     int q_len, n_q, jz_joints;             // jz_joints: n_joints, 0 without gradient rows
     NBK_HD explicit PairItemsLds(int n_q_, int jz_joints_ = 0) : q_len(LDS_WAVE * n_q_), n_q(n_q_), jz_joints(jz_joints_) {}
-    NBK_HD size_t jz_at() const { return sizeof(double) * (size_t)q_len; }
+    NBK_HD double* q(double* base) const { return base; }
+    NBK_HD double* jz(double* base) const { return q(base) + q_len; }
     NBK_HD size_t jz_len() const { return (size_t)LDS_WAVE * 6 * (size_t)jz_joints; }
     NBK_LDS_TOTAL(sizeof(double) * ((size_t)LDS_WAVE * (n_q > 0 ? n_q : 1) + jz_len()))
 };
@@ -108,9 +113,10 @@ struct NarrowLds {
     int q_len, hull_blob_n;
     NBK_HD NarrowLds(int n_q, int hull_blob_n_) : q_len(NARROW_T * n_q), hull_blob_n(hull_blob_n_) {}
     NBK_HD bool hull_staged() const { return hull_blob_n > 0 && hull_blob_n <= HULL_LDS_MAX / 8; }      // else the cores keep reading global memory
-    NBK_HD size_t hull_at() const { return sizeof(double) * (size_t)q_len; }
+    NBK_HD double* q(double* base) const { return base; }
+    NBK_HD double* hull(double* base) const { return q(base) + q_len; }
     NBK_HD size_t hull_len() const { return hull_staged() ? (size_t)hull_blob_n : 0; }
-    NBK_LDS_TOTAL(hull_at() + sizeof(double) * hull_len())
+    NBK_LDS_TOTAL(sizeof(double) * ((size_t)q_len + hull_len()))
 };
 
 // ---- the parked robot of 64 configurations -------------------------------------------------------------------------------------------
@@ -119,9 +125,11 @@ struct NarrowLds {
 struct ParkedLds {
     int q_len, s_len, fr_len;
     NBK_HD ParkedLds(int n_q, int shape_rows, int frame_slots) : q_len(LDS_WAVE * n_q), s_len(LDS_WAVE * shape_rows), fr_len(LDS_WAVE * 12 * frame_slots) {}
-    NBK_HD size_t s_at() const { return sizeof(double) * (size_t)q_len; }
-    NBK_HD size_t fr_at() const { return s_at() + sizeof(double) * (size_t)s_len; }
-    NBK_HD size_t tail_at() const { return fr_at() + sizeof(double) * (size_t)fr_len; }
+    NBK_HD double* q(double* base) const { return base; }
+    NBK_HD double* s(double* base) const { return q(base) + q_len; }
+    NBK_HD double* fr(double* base) const { return s(base) + s_len; }
+    NBK_HD double* tail(double* base) const { return fr(base) + fr_len; }
+    NBK_HD size_t parked_bytes() const { return sizeof(double) * ((size_t)q_len + (size_t)s_len + (size_t)fr_len); }      // what lies before the tail
 };
 // tail of k_validity, k_validity_redo, k_edges and k_distances<0>: queue [QUEUE_CAP] unsigned | hit flags [64] unsigned.
 // k_distances<0> keeps its one EPA queue (EPAQ_DOUBLES doubles) in it
@@ -129,8 +137,9 @@ struct ValidityLds : ParkedLds {
     static constexpr int QUEUE_LEN = QUEUE_CAP, HIT_LEN = LDS_WAVE;      // unsigned
     static constexpr int TAIL_BYTES = QUEUE_LEN * 4 + HIT_LEN * 4;
     NBK_HD ValidityLds(int n_q, int shape_rows, int frame_slots) : ParkedLds(n_q, shape_rows, frame_slots) {}
-    NBK_HD size_t hit_at() const { return tail_at() + sizeof(unsigned) * QUEUE_LEN; }
-    NBK_LDS_TOTAL(tail_at() + TAIL_BYTES)
+    NBK_HD unsigned* queue(double* base) const { return reinterpret_cast<unsigned*>(tail(base)); }
+    NBK_HD unsigned* hit(double* base) const { return queue(base) + QUEUE_LEN; }
+    NBK_LDS_TOTAL(parked_bytes() + TAIL_BYTES)
 };
 // tail of k_distances<MODE>: for MODE 3 the joint axes and origins [6 n_joints][64], then one EPA queue per wave (MODE 0: one wave,
 // else two), each depths [EPAQ_CAP] double | items [EPAQ_CAP] unsigned.  The first wave's queue is paid for by the validity tail, which
@@ -140,18 +149,21 @@ struct DistancesLds : ParkedLds {
     NBK_HD DistancesLds(int n_q, int shape_rows, int frame_slots, int n_joints, int mode_)
         : ParkedLds(n_q, shape_rows, frame_slots), jz_len(mode_ == 3 ? LDS_WAVE * 6 * n_joints : 0), mode(mode_) {}
     NBK_HD int nwave() const { return mode == 0 ? 1 : 2; }
-    NBK_HD size_t epaq_at(int wave) const { return tail_at() + sizeof(double) * ((size_t)jz_len + (size_t)wave * EPAQ_DOUBLES); }
-    NBK_LDS_TOTAL(epaq_at(0) + ValidityLds::TAIL_BYTES + sizeof(double) * (size_t)(nwave() - 1) * EPAQ_DOUBLES)
+    NBK_HD double* jz(double* base) const { return tail(base); }
+    NBK_HD double* epaq_depth(double* base, int wave) const { return jz(base) + jz_len + wave * EPAQ_DOUBLES; }
+    NBK_HD unsigned* epaq_item(double* base, int wave) const { return reinterpret_cast<unsigned*>(epaq_depth(base, wave) + EPAQ_CAP); }
+    NBK_LDS_TOTAL(parked_bytes() + sizeof(double) * (size_t)jz_len + ValidityLds::TAIL_BYTES + sizeof(double) * (size_t)(nwave() - 1) * EPAQ_DOUBLES)
 };
 // tail of k_closest: results [CQ_CAP] double | best [64] u64 | argmin [64] unsigned | queue [CQ_CAP] unsigned | EPA list [CQ_CAP] u16
 struct ClosestLds : ParkedLds {
     static constexpr int RES_LEN = CQ_CAP, BEST_LEN = LDS_WAVE, ARG_LEN = LDS_WAVE, QUEUE_LEN = CQ_CAP, ELIST_LEN = CQ_CAP;
     NBK_HD ClosestLds(int n_q, int shape_rows, int frame_slots) : ParkedLds(n_q, shape_rows, frame_slots) {}
-    NBK_HD size_t best_at() const { return tail_at() + sizeof(double) * RES_LEN; }
-    NBK_HD size_t arg_at() const { return best_at() + sizeof(unsigned long long) * BEST_LEN; }
-    NBK_HD size_t queue_at() const { return arg_at() + sizeof(unsigned) * ARG_LEN; }
-    NBK_HD size_t elist_at() const { return queue_at() + sizeof(unsigned) * QUEUE_LEN; }
-    NBK_LDS_TOTAL(elist_at() + sizeof(unsigned short) * ELIST_LEN)
+    NBK_HD double* res(double* base) const { return tail(base); }
+    NBK_HD unsigned long long* best(double* base) const { return reinterpret_cast<unsigned long long*>(res(base) + RES_LEN); }
+    NBK_HD unsigned* arg(double* base) const { return reinterpret_cast<unsigned*>(best(base) + BEST_LEN); }
+    NBK_HD unsigned* queue(double* base) const { return arg(base) + ARG_LEN; }
+    NBK_HD unsigned short* elist(double* base) const { return reinterpret_cast<unsigned short*>(queue(base) + QUEUE_LEN); }
+    NBK_LDS_TOTAL(parked_bytes() + sizeof(double) * RES_LEN + sizeof(unsigned long long) * BEST_LEN + sizeof(unsigned) * (ARG_LEN + QUEUE_LEN) + sizeof(unsigned short) * ELIST_LEN)
 };
 
 // ---- the broadphases -------------------------------------------------------------------------------------------------------------------
@@ -170,11 +182,12 @@ struct BroadLds {
     NBK_HD BroadLds(int n_q, int frame_slots, int n_rshapes, int n_pairs, int n_wshapes = 0)
         : qrows(broad_qrows(n_q)), slab_len(LDS_WAVE * qrows), fr_len(LDS_WAVE * 12 * frame_slots), c_len(LDS_WAVE * 3 * n_rshapes), pc_len(4 * n_pairs), w_len(18 * n_wshapes) {}
     NBK_HD int qcap() const { return qrows * (LDS_WAVE * 2); }      // queue entries the slab holds
-    NBK_HD size_t fr_at() const { return sizeof(double) * (size_t)slab_len; }
-    NBK_HD size_t c_at() const { return fr_at() + sizeof(double) * (size_t)fr_len; }
-    NBK_HD size_t pc_at() const { return c_at() + sizeof(double) * (size_t)c_len; }
-    NBK_HD size_t w_at() const { return pc_at() + sizeof(double) * (size_t)pc_len; }
-    NBK_LDS_TOTAL(w_at() + sizeof(double) * (size_t)w_len)
+    NBK_HD double* slab(double* base) const { return base; }   NBK_HD unsigned* queue(double* base) const { return reinterpret_cast<unsigned*>(slab(base)); }
+    NBK_HD double* fr(double* base) const { return slab(base) + slab_len; }
+    NBK_HD double* c(double* base) const { return fr(base) + fr_len; }
+    NBK_HD double* pc(double* base) const { return c(base) + c_len; }
+    NBK_HD double* w(double* base) const { return pc(base) + pc_len; }
+    NBK_LDS_TOTAL(sizeof(double) * ((size_t)slab_len + (size_t)fr_len + (size_t)c_len + (size_t)pc_len + (size_t)w_len))
 };
 // k_broad_reg<S>: q slab / queue | saved frames | keys [S*S] | world keys [W*S] | world tc [W*S] | pair index [S*S] int | [W*S] int.
 // The launch asks for 16 bytes more than the last region ends at
@@ -183,13 +196,14 @@ struct BroadRegLds {
     NBK_HD BroadRegLds(int n_q, int frame_slots, int S, int W)
         : qrows(broad_qrows(n_q)), slab_len(LDS_WAVE * qrows), fr_len(LDS_WAVE * 12 * frame_slots), rkey_len(S * S), wkey_len(W * S), wtc_len(W * S), rp_len(S * S), wp_len(W * S) {}
     NBK_HD int qcap() const { return qrows * (LDS_WAVE * 2); }
-    NBK_HD size_t fr_at() const { return sizeof(double) * (size_t)slab_len; }
-    NBK_HD size_t rkey_at() const { return fr_at() + sizeof(double) * (size_t)fr_len; }
-    NBK_HD size_t wkey_at() const { return rkey_at() + sizeof(double) * (size_t)rkey_len; }
-    NBK_HD size_t wtc_at() const { return wkey_at() + sizeof(double) * (size_t)wkey_len; }
-    NBK_HD size_t rp_at() const { return wtc_at() + sizeof(double) * (size_t)wtc_len; }
-    NBK_HD size_t wp_at() const { return rp_at() + sizeof(int) * (size_t)rp_len; }
-    NBK_LDS_TOTAL(wp_at() + sizeof(int) * (size_t)wp_len + 16)
+    NBK_HD double* slab(double* base) const { return base; }   NBK_HD unsigned* queue(double* base) const { return reinterpret_cast<unsigned*>(slab(base)); }
+    NBK_HD double* fr(double* base) const { return slab(base) + slab_len; }
+    NBK_HD double* rkey(double* base) const { return fr(base) + fr_len; }
+    NBK_HD double* wkey(double* base) const { return rkey(base) + rkey_len; }
+    NBK_HD double* wtc(double* base) const { return wkey(base) + wkey_len; }
+    NBK_HD int* rp(double* base) const { return reinterpret_cast<int*>(wtc(base) + wtc_len); }
+    NBK_HD int* wp(double* base) const { return rp(base) + rp_len; }
+    NBK_LDS_TOTAL(sizeof(double) * ((size_t)slab_len + (size_t)fr_len + (size_t)rkey_len + (size_t)wkey_len + (size_t)wtc_len) + sizeof(int) * ((size_t)rp_len + (size_t)wp_len) + 16)
 };
 // k_broad_f32<S, WH>: q slab / queue / centre z rows | saved frames [12 slots][64] float | Z_PAD floats | z rows [NBK_ZSLOTS][64] float:
 // the z of slots NBK_ZFIRST .., which the kernel indexes by slot (its pointer starts NBK_ZFIRST rows before them).  The kernel compiled
@@ -201,9 +215,11 @@ struct BroadF32Lds {
     NBK_HD BroadF32Lds(int n_q, int frame_slots, int S) : qrows(f32_qrows(n_q, S)), slab_len(LDS_WAVE * qrows), fr_len(LDS_WAVE * 12 * frame_slots) {}
     NBK_HD int qcap() const { return qrows * (LDS_WAVE * 2); }      // queue entries the slab holds
     NBK_HD size_t slab_bytes() const { return sizeof(double) * (size_t)slab_len; }
-    NBK_HD size_t fr_at() const { return slab_bytes(); }
-    NBK_HD size_t z_at() const { return fr_at() + sizeof(float) * ((size_t)fr_len + Z_PAD); }
-    NBK_LDS_TOTAL(fr_at() + sizeof(float) * (size_t)fr_len + TAIL_BYTES)
+    NBK_HD double* slab(double* base) const { return base; }   NBK_HD unsigned* queue(double* base) const { return reinterpret_cast<unsigned*>(slab(base)); }
+    NBK_HD float* czrows(double* base) const { return reinterpret_cast<float*>(slab(base)); }      // the centre z rows
+    NBK_HD float* fr(double* base) const { return reinterpret_cast<float*>(slab(base) + slab_len); }
+    NBK_HD float* zp(double* base) const { return fr(base) + fr_len + Z_PAD - LDS_ZFIRST * LDS_WAVE; }      // indexed by slot: row LDS_ZFIRST is the first stored
+    NBK_LDS_TOTAL(slab_bytes() + sizeof(float) * (size_t)fr_len + TAIL_BYTES)
 };
 
 // ---- creation (check_limits) ----------------------------------------------------------------------------------------------------------

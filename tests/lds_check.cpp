@@ -1,10 +1,10 @@
 // lds_check.cpp -- stand-alone check of numbotics_amd/csrc/nbk_lds.hpp (tests/test_lds_host.py builds it with the host sanitizers and runs
 // it).  Sweeps n_q 1..32, n_joints 1..32, frame_slots 0..32, path_len 0..32, shape_rows from 0 to beyond the parked limit, S 0..40 (the
 // three buckets), W and P over small values, the boundaries and the descriptor limits, hull_blob_n around HULL_LDS_MAX / 8, the four
-// k_distances modes, and holds for every layout:
+// k_distances modes, and holds for every layout, over the pointers its accessors (the kernels' own carve) return for a host buffer:
 //   parent equality      bytes() and every served / refused verdict equal the host expressions this header replaced (the *_lds helpers,
 //                        lds_f, nlds, the cloud launches and the three rules of check_limits), transcribed below as they stood;
-//   in bounds            every region ends at or before bytes();
+//   in bounds            every region ends at or before bytes(), the last one at it (two exceptions, stated where they are checked);
 //   no overlap           regions that are live at the same time do not overlap;
 //   aliases covered      each region that reuses another fits into it (named at its check);
 //   alignment            every region starts on a multiple of its element size, what stage_q / stage_rows read as double2 on 16 bytes;
@@ -98,27 +98,30 @@ static parent::Limits check_limits_now(int n_q, int rows, int slots, int S, int 
 }
 
 // ---- regions ------------------------------------------------------------------------------------------------------------------------------
-struct Region { const char* name; size_t begin, bytes, elem; bool d2; };      // d2: read or written as double2
-// `count` elements of `elem` bytes from byte `begin`
-static Region region(const char* name, size_t begin, size_t count, size_t elem, bool d2 = false) { return {name, begin, count * elem, elem, d2}; }
+struct Region { const char* name; size_t begin, bytes, elem; bool d2; size_t end() const { return begin + bytes; } };      // d2: read or written as double2
+// The host buffer the accessors are called on in place of the dynamic LDS: it holds the largest layout of the sweep (check_regions holds that)
+static std::vector<double> g_buf((size_t)6 << 20);
+static double* const lds = g_buf.data();
+// `count` elements from `p`, a pointer an accessor returned: the begin is its distance from the base, the element size its type's
+template <class T> static Region region(const char* name, T* p, size_t count, bool d2 = false) { return {name, (size_t)((const char*)p - (const char*)lds), count * sizeof(T), sizeof(T), d2}; }
 
-// in bounds, aligned, pairwise disjoint (the regions given are live at the same time)
-static void check_regions(const char* what, const std::vector<Region>& rs, size_t total) {
+// in bounds, aligned, pairwise disjoint (the regions given are live at the same time); end_slack >= 0: the last one ends that many bytes before bytes()
+static void check_regions(const char* what, const std::vector<Region>& rs, size_t total, long end_slack = -1) {
+    CHECK(total <= g_buf.size() * sizeof(double), "%s: %zu bytes beyond the host buffer", what, total);
+    if (end_slack >= 0) CHECK(rs.back().end() + (size_t)end_slack == total, "%s: %s ends at %zu, bytes() = %zu", what, rs.back().name, rs.back().end(), total);
     for (size_t i = 0; i < rs.size(); ++i) {
         const Region& r = rs[i];
-        CHECK(r.begin + r.bytes <= total, "%s: %s ends at %zu of %zu", what, r.name, r.begin + r.bytes, total);
+        CHECK(r.end() <= total, "%s: %s ends at %zu of %zu", what, r.name, r.end(), total);
         CHECK(r.begin % r.elem == 0 && (!r.d2 || r.begin % 16 == 0), "%s: %s starts at byte %zu", what, r.name, r.begin);
         for (size_t j = i + 1; j < rs.size(); ++j) {
             const Region& o = rs[j];
-            CHECK(r.bytes == 0 || o.bytes == 0 || r.begin + r.bytes <= o.begin || o.begin + o.bytes <= r.begin, "%s: %s [%zu, %zu) and %s [%zu, %zu)", what, r.name,
-                  r.begin, r.begin + r.bytes, o.name, o.begin, o.begin + o.bytes);
+            CHECK(r.bytes == 0 || o.bytes == 0 || r.end() <= o.begin || o.end() <= r.begin, "%s: %s [%zu, %zu) and %s [%zu, %zu)", what, r.name, r.begin, r.end(), o.name, o.begin, o.end());
         }
     }
 }
 // `alias` lies inside `host`
 static void check_alias(const char* what, const Region& alias, const Region& host) {
-    CHECK(alias.begin >= host.begin && alias.begin + alias.bytes <= host.begin + host.bytes, "%s: %s [%zu, %zu) outside %s [%zu, %zu)", what, alias.name, alias.begin,
-          alias.begin + alias.bytes, host.name, host.begin, host.begin + host.bytes);
+    CHECK(alias.begin >= host.begin && alias.end() <= host.end(), "%s: %s [%zu, %zu) outside %s [%zu, %zu)", what, alias.name, alias.begin, alias.end(), host.name, host.begin, host.end());
     CHECK(alias.begin % alias.elem == 0 && (!alias.d2 || alias.begin % 16 == 0), "%s: %s starts at byte %zu", what, alias.name, alias.begin);
 }
 
@@ -131,48 +134,49 @@ static void check_kinematics(int n_q, int n_joints, int slots, int path_len) {
     {
         const FkLds L(n_q);
         CHECK(L.bytes() == parent::fk_lds(&pm) && L.fits(), "fk n_q=%d", n_q);
-        check_regions("k_fk q", {region("raw q", 0, slab, 8, true)}, L.bytes());
-        check_regions("k_fk out", {region("poses", 0, (size_t)WAVE * 17, 8)}, L.bytes());
+        check_regions("k_fk q", {region("raw q", lds, slab, true)}, L.bytes());      // one region, no accessor: the base itself
+        check_regions("k_fk out", {region("poses", lds, (size_t)WAVE * 17)}, L.bytes());
     }
     {
         const FkFramesLds L(n_q, slots);
         CHECK(L.bytes() == parent::fk_frames_lds(&pm) && L.fits() == (parent::fk_frames_lds(&pm) <= LDS_MAX), "fk_frames n_q=%d slots=%d", n_q, slots);
-        const Region t = region("transpose", L.t_at(), L.t_len(), 8);
-        check_regions("k_fk_frames", {region("q rows", 0, (size_t)L.q_len, 8), region("frames", L.fr_at(), (size_t)L.fr_len, 8), t}, L.bytes());
+        const Region t = region("transpose", L.t(lds), L.t_len());
+        check_regions("k_fk_frames", {region("q rows", L.q(lds), (size_t)L.q_len), region("frames", L.fr(lds), (size_t)L.fr_len), t}, L.bytes(), 0);
         CHECK((size_t)L.q_len == slab && L.fr_len == WAVE * 12 * slots, "k_fk_frames lengths");
-        check_alias("k_fk_frames", region("raw q", L.t_at(), slab, 8, true), t);
-        check_alias("k_fk_frames", region("poses", L.t_at(), (size_t)WAVE * 17, 8), t);
+        check_alias("k_fk_frames", region("raw q", L.t(lds), slab, true), t);
+        check_alias("k_fk_frames", region("poses", L.t(lds), (size_t)WAVE * 17), t);
     }
     {
         const JacobianLds L(n_q);
         CHECK(L.bytes() == parent::jacobian_lds(&pm) && L.fits() == (parent::jacobian_lds(&pm) <= LDS_MAX), "jacobian n_q=%d", n_q);
         CHECK(L.stride() == ((6 * n_q) | 1), "jacobian stride");
-        check_regions("k_jacobian", {region("raw q", 0, (size_t)L.q_len, 8, true), region("rows", L.o_at(), (size_t)WAVE * L.stride(), 8)}, L.bytes());
+        check_regions("k_jacobian", {region("raw q", L.q(lds), (size_t)L.q_len, true), region("rows", L.o(lds), (size_t)WAVE * L.stride())}, L.bytes(), 0);
     }
     {
         const JacobianRegLds L(n_q);
         CHECK(L.bytes() == parent::jacobian_reg_lds(&pm) && L.fits(), "jacobian_reg n_q=%d", n_q);
-        const Region all = region("LDS", 0, L.bytes() / 8, 8);
-        check_alias("k_jacobian_reg", region("raw q", 0, L.q_len(), 8, true), all);
-        check_alias("k_jacobian_reg", region("rows", 0, L.o_len(), 8), all);      // the rows reuse the q area
-        CHECK(L.q_len() == slab && L.o_len() == (size_t)JAC_ROWS * ((6 * n_q) | 1), "k_jacobian_reg lengths");
+        const Region all = region("LDS", lds, L.bytes() / 8), q = region("raw q", L.q(lds), L.q_len(), true), o = region("rows", L.o(lds), L.o_len());
+        check_alias("k_jacobian_reg", q, all);
+        check_alias("k_jacobian_reg", o, all);      // the rows reuse the q area
+        CHECK(L.q_len() == slab && L.o_len() == (size_t)JAC_ROWS * ((6 * n_q) | 1) && o.begin == q.begin, "k_jacobian_reg lengths; the rows start where q starts");
+        CHECK(std::max(q.end(), o.end()) == L.bytes(), "k_jacobian_reg: the longer of the two ends where the launch's bytes end");
     }
     {
         const IkLds L(n_q, path_len);
         CHECK(L.bytes() == parent::ik_lds(&pm, path_len) && L.fits() == (parent::ik_lds(&pm, path_len) <= LDS_MAX), "ik n_q=%d len=%d", n_q, path_len);
         CHECK(L.jz_len() >= (size_t)WAVE * 6 * path_len, "k_ik: jz holds 6 rows per joint of the path");
-        check_regions("k_ik", {region("q rows", 0, (size_t)L.q_len, 8), region("J", L.J_at(), (size_t)L.J_len, 8), region("jz", L.jz_at(), L.jz_len(), 8)}, L.bytes());
+        check_regions("k_ik", {region("q rows", L.q(lds), (size_t)L.q_len), region("J", L.J(lds), (size_t)L.J_len), region("jz", L.jz(lds), L.jz_len())}, L.bytes(), 0);
         CHECK(IkLds(n_q).q_len == L.q_len && IkLds(n_q).J_len == L.J_len, "k_ik: the kernel's construction, without the path length");
     }
     for (int rows = 0; rows < 2; ++rows) {
         const PairItemsLds L(n_q, rows ? n_joints : 0);
         CHECK(L.bytes() == parent::pair_items_lds(&pm, rows != 0) && L.fits(), "pair_items n_q=%d J=%d", n_q, n_joints);
-        check_regions("k_pair_items", {region("q rows", 0, (size_t)L.q_len, 8), region("jz", L.jz_at(), L.jz_len(), 8)}, L.bytes());
+        check_regions("k_pair_items", {region("q rows", L.q(lds), (size_t)L.q_len), region("jz", L.jz(lds), L.jz_len())}, L.bytes(), 0);
         CHECK(L.jz_len() == (rows ? (size_t)WAVE * 6 * n_joints : 0) && PairItemsLds(n_q).q_len == L.q_len, "k_pair_items lengths");
     }
     CHECK(QSlabLds(n_q).bytes() == parent::cloud_lds(&pm) && QSlabLds(n_q).fits(), "cloud n_q=%d", n_q);
     CHECK(QSlabLds(n_q, 1).bytes() == parent::spline_ca_lds(&pm) && QSlabLds(n_q, 1).fits(), "spline_ca n_q=%d", n_q);
-    check_regions("q slab", {region("q rows", 0, slab, 8)}, QSlabLds(n_q).bytes());
+    check_regions("q slab", {region("q rows", lds, slab)}, QSlabLds(n_q).bytes(), 0);
 }
 
 static void check_narrow(int n_q, int hull_blob_n) {
@@ -180,7 +184,7 @@ static void check_narrow(int n_q, int hull_blob_n) {
     const NarrowLds L(n_q, hull_blob_n);
     CHECK(L.bytes() == parent::nlds(&pm) && L.fits(), "narrow n_q=%d hull=%d", n_q, hull_blob_n);
     CHECK(L.hull_staged() == (hull_blob_n > 0 && (size_t)hull_blob_n * 8 <= (size_t)HULL_LDS_MAX) && L.hull_len() == (L.hull_staged() ? (size_t)hull_blob_n : 0), "hull_staged(%d)", hull_blob_n);
-    check_regions("k_narrow", {region("q rows", 0, (size_t)L.q_len, 8), region("hull", L.hull_at(), L.hull_len(), 8)}, L.bytes());
+    check_regions("k_narrow", {region("q rows", L.q(lds), (size_t)L.q_len), region("hull", L.hull(lds), L.hull_len())}, L.bytes(), 0);
     CHECK(L.q_len == NARROW_T * n_q, "k_narrow q rows");
 }
 
@@ -189,18 +193,17 @@ static void check_parked(int n_q, int n_joints, int shape_rows, int slots) {
     const size_t slab = (size_t)WAVE * n_q;
     auto body = [&](const ParkedLds& L) {
         CHECK((size_t)L.q_len == slab && L.s_len == WAVE * shape_rows && L.fr_len == WAVE * 12 * slots, "parked lengths");
-        return std::vector<Region>{region("q rows", 0, (size_t)L.q_len, 8), region("shape rows", L.s_at(), (size_t)L.s_len, 8), region("frames", L.fr_at(), (size_t)L.fr_len, 8)};
+        return std::vector<Region>{region("q rows", L.q(lds), (size_t)L.q_len), region("shape rows", L.s(lds), (size_t)L.s_len), region("frames", L.fr(lds), (size_t)L.fr_len)};
     };
     {
         const ValidityLds L(n_q, shape_rows, slots);
         CHECK(L.bytes() == parent::collide_lds(&pm) && L.fits() == (parent::collide_lds(&pm) <= LDS_MAX), "validity n_q=%d rows=%d slots=%d", n_q, shape_rows, slots);
         CHECK(ValidityLds::TAIL_BYTES == parent::VALIDITY_LDS_EXTRA, "VALIDITY_LDS_EXTRA");
         std::vector<Region> rs = body(L);
-        rs.push_back(region("queue", L.tail_at(), ValidityLds::QUEUE_LEN, 4));
-        rs.push_back(region("hit flags", L.hit_at(), ValidityLds::HIT_LEN, 4));
-        check_regions("validity", rs, L.bytes());
+        rs.insert(rs.end(), {region("queue", L.queue(lds), ValidityLds::QUEUE_LEN), region("hit flags", L.hit(lds), ValidityLds::HIT_LEN)});
+        check_regions("validity", rs, L.bytes(), 0);
         // the raw q slab is staged in the shape area: holds for every descriptor, whose shape_rows is max(rows, n_q)
-        if (shape_rows >= n_q) check_alias("validity", region("raw q", L.s_at(), slab, 8, true), rs[1]);
+        if (shape_rows >= n_q) check_alias("validity", region("raw q", L.s(lds), slab, true), rs[1]);
     }
     for (int mode = 0; mode < 4; ++mode) {
         const DistancesLds L(n_q, shape_rows, slots, n_joints, mode);
@@ -208,12 +211,12 @@ static void check_parked(int n_q, int n_joints, int shape_rows, int slots) {
         CHECK(L.bytes() == was && L.fits() == (was <= LDS_MAX), "distances<%d> n_q=%d rows=%d slots=%d J=%d", mode, n_q, shape_rows, slots, n_joints);
         CHECK(L.nwave() == (mode == 0 ? 1 : 2) && L.jz_len == (mode == 3 ? WAVE * 6 * n_joints : 0), "distances<%d> waves, jz", mode);
         std::vector<Region> rs = body(L);
-        rs.push_back(region("jz", L.tail_at(), (size_t)L.jz_len, 8));
+        rs.push_back(region("jz", L.jz(lds), (size_t)L.jz_len));
         for (int w = 0; w < L.nwave(); ++w) {
-            rs.push_back(region(w ? "EPA depths 1" : "EPA depths 0", L.epaq_at(w), EPAQ_CAP, 8));
-            rs.push_back(region(w ? "EPA items 1" : "EPA items 0", L.epaq_at(w) + 8 * (size_t)EPAQ_CAP, EPAQ_CAP, 4));
+            rs.push_back(region(w ? "EPA depths 1" : "EPA depths 0", L.epaq_depth(lds, w), EPAQ_CAP));
+            rs.push_back(region(w ? "EPA items 1" : "EPA items 0", L.epaq_item(lds, w), EPAQ_CAP));
         }
-        check_regions("distances", rs, L.bytes());
+        check_regions("distances", rs, L.bytes(), ValidityLds::TAIL_BYTES - 8 * EPAQ_DOUBLES);      // bytes() keeps the whole validity tail where the first wave's EPA queue lies
         // the first wave's EPA queue lives in the tail the validity path sized for its own queue
         CHECK((size_t)EPAQ_DOUBLES * 8 <= (size_t)ValidityLds::TAIL_BYTES && EPAQ_DOUBLES * 8 == EPAQ_CAP * (8 + 4), "the validity tail holds one EPA queue");
     }
@@ -221,13 +224,9 @@ static void check_parked(int n_q, int n_joints, int shape_rows, int slots) {
         const ClosestLds L(n_q, shape_rows, slots);
         CHECK(L.bytes() == parent::closest_lds(&pm) && L.fits() == (parent::closest_lds(&pm) <= LDS_MAX), "closest n_q=%d rows=%d slots=%d", n_q, shape_rows, slots);
         std::vector<Region> rs = body(L);
-        rs.push_back(region("results", L.tail_at(), ClosestLds::RES_LEN, 8));
-        rs.push_back(region("best", L.best_at(), ClosestLds::BEST_LEN, 8));
-        rs.push_back(region("argmin", L.arg_at(), ClosestLds::ARG_LEN, 4));
-        rs.push_back(region("queue", L.queue_at(), ClosestLds::QUEUE_LEN, 4));
-        rs.push_back(region("EPA list", L.elist_at(), ClosestLds::ELIST_LEN, 2));
-        check_regions("closest", rs, L.bytes());
-        CHECK(rs.back().begin + rs.back().bytes == L.bytes(), "closest: the unsigned short list ends where the launch's bytes end");
+        rs.insert(rs.end(), {region("results", L.res(lds), ClosestLds::RES_LEN), region("best", L.best(lds), ClosestLds::BEST_LEN), region("argmin", L.arg(lds), ClosestLds::ARG_LEN),
+                             region("queue", L.queue(lds), ClosestLds::QUEUE_LEN), region("EPA list", L.elist(lds), ClosestLds::ELIST_LEN)});
+        check_regions("closest", rs, L.bytes(), 0);      // the unsigned short list ends where the launch's bytes end
     }
 }
 
@@ -237,14 +236,14 @@ static void check_broad(int n_q, int slots, int S, int W, int P) {
     {
         const BroadLds L(n_q, slots, S, P, W);
         CHECK(L.bytes() == parent::broad_lds(&pm) && L.fits() == (parent::broad_lds(&pm) <= LDS_MAX), "broad n_q=%d slots=%d S=%d W=%d P=%d", n_q, slots, S, W, P);
-        const Region q = region("q slab", 0, (size_t)L.slab_len, 8, true);
-        check_regions("k_broad", {q, region("frames", L.fr_at(), (size_t)L.fr_len, 8), region("centres", L.c_at(), (size_t)L.c_len, 8),
-                                  region("pair constants", L.pc_at(), (size_t)L.pc_len, 8), region("world cores", L.w_at(), (size_t)L.w_len, 8)}, L.bytes());
+        const Region q = region("q slab", L.slab(lds), (size_t)L.slab_len, true);
+        check_regions("k_broad", {q, region("frames", L.fr(lds), (size_t)L.fr_len), region("centres", L.c(lds), (size_t)L.c_len),
+                                  region("pair constants", L.pc(lds), (size_t)L.pc_len), region("world cores", L.w(lds), (size_t)L.w_len)}, L.bytes(), 0);
         CHECK(L.slab_len == WAVE * L.qrows && L.fr_len == WAVE * 12 * slots && L.c_len == WAVE * 3 * S && L.pc_len == 4 * P && L.w_len == 18 * W, "k_broad lengths");
         const BroadLds K(n_q, slots, S, P);      // the kernel's construction, without the world shapes
         CHECK(K.slab_len == L.slab_len && K.fr_len == L.fr_len && K.c_len == L.c_len && K.pc_len == L.pc_len, "k_broad: the kernel's construction");
-        check_alias("k_broad", region("raw q", 0, slab, 8, true), q);
-        check_alias("k_broad", region("item queue", 0, BQ_CAP, 4), q);
+        check_alias("k_broad", region("raw q", L.slab(lds), slab, true), q);
+        check_alias("k_broad", region("item queue", L.queue(lds), BQ_CAP), q);
         CHECK(L.qcap() >= BQ_CAP && (size_t)L.qcap() * 4 == q.bytes, "k_broad qcap %d", L.qcap());
     }
     if (S <= 16) {
@@ -253,26 +252,26 @@ static void check_broad(int n_q, int slots, int S, int W, int P) {
         {
             const BroadRegLds L(n_q, slots, b, W);
             CHECK(L.bytes() == parent::broad_reg_lds(&pm, b) && L.fits() == (parent::broad_reg_lds(&pm, b) <= LDS_MAX), "broad_reg n_q=%d slots=%d S=%d W=%d", n_q, slots, b, W);
-            const Region q = region("q slab", 0, (size_t)L.slab_len, 8, true);
-            check_regions("k_broad_reg", {q, region("frames", L.fr_at(), (size_t)L.fr_len, 8), region("rkey", L.rkey_at(), (size_t)L.rkey_len, 8), region("wkey", L.wkey_at(), (size_t)L.wkey_len, 8),
-                                          region("wtc", L.wtc_at(), (size_t)L.wtc_len, 8), region("rp", L.rp_at(), (size_t)L.rp_len, 4), region("wp", L.wp_at(), (size_t)L.wp_len, 4)}, L.bytes());
+            const Region q = region("q slab", L.slab(lds), (size_t)L.slab_len, true);
+            check_regions("k_broad_reg", {q, region("frames", L.fr(lds), (size_t)L.fr_len), region("rkey", L.rkey(lds), (size_t)L.rkey_len), region("wkey", L.wkey(lds), (size_t)L.wkey_len),
+                                          region("wtc", L.wtc(lds), (size_t)L.wtc_len), region("rp", L.rp(lds), (size_t)L.rp_len), region("wp", L.wp(lds), (size_t)L.wp_len)}, L.bytes(), 16);      // the launch asks for 16 bytes more
             CHECK(L.slab_len == WAVE * L.qrows && L.rkey_len == b * b && L.wkey_len == W * b && L.wtc_len == W * b && L.rp_len == b * b && L.wp_len == W * b, "k_broad_reg lengths");
-            check_alias("k_broad_reg", region("raw q", 0, slab, 8, true), q);
-            check_alias("k_broad_reg", region("item queue", 0, BQ_CAP, 4), q);
+            check_alias("k_broad_reg", region("raw q", L.slab(lds), slab, true), q);
+            check_alias("k_broad_reg", region("item queue", L.queue(lds), BQ_CAP), q);
             CHECK(L.qcap() >= BQ_CAP, "k_broad_reg qcap %d", L.qcap());
         }
         {
             const BroadF32Lds L(n_q, slots, b);
             CHECK(L.bytes() == parent::lds_f(&pm, b) && L.slab_bytes() == parent::spec_lds(&pm, b), "broad_f32 n_q=%d slots=%d S=%d", n_q, slots, b);
-            const Region q = region("q slab", 0, (size_t)L.slab_len, 8, true);
-            check_regions("k_broad_f32", {q, region("frames", L.fr_at(), (size_t)L.fr_len, 4), region("z", L.z_at(), (size_t)WAVE * LDS_ZSLOTS, 4)}, L.bytes());
-            CHECK(L.z_at() % 16 == 0 && L.z_at() - (L.fr_at() + 4 * (size_t)L.fr_len) == 16, "z starts 16 bytes behind the frames, on 16 bytes");
-            CHECK(L.bytes() == L.fr_at() + 4 * (size_t)L.fr_len + BroadF32Lds::TAIL_BYTES && L.fr_len == WAVE * 12 * slots, "TAIL_BYTES");
-            // the kernel's z pointer, indexed by slot: frames + fr_len + Z_PAD - NBK_ZFIRST * WAVE floats; slot NBK_ZFIRST is where z starts
-            CHECK(L.fr_at() + 4 * ((size_t)L.fr_len + BroadF32Lds::Z_PAD) == L.z_at(), "the z row of slot NBK_ZFIRST");
-            check_alias("k_broad_f32", region("raw q", 0, slab, 8, true), q);
-            check_alias("k_broad_f32", region("item queue", 0, (size_t)L.qcap(), 4), q);
-            check_alias("k_broad_f32", region("centre z rows", 0, (size_t)b * WAVE, 4), q);
+            const Region q = region("q slab", L.slab(lds), (size_t)L.slab_len, true), fr = region("frames", L.fr(lds), (size_t)L.fr_len);
+            const Region z = region("z", L.zp(lds) + LDS_ZFIRST * WAVE, (size_t)WAVE * LDS_ZSLOTS);      // the kernel's pointer is indexed by slot: row NBK_ZFIRST is the first stored
+            check_regions("k_broad_f32", {q, fr, z}, L.bytes(), 0);
+            CHECK(z.begin % 16 == 0 && z.begin - (fr.begin + fr.bytes) == 16, "z starts 16 bytes behind the frames, on 16 bytes");
+            CHECK(L.bytes() == fr.begin + fr.bytes + BroadF32Lds::TAIL_BYTES && L.fr_len == WAVE * 12 * slots, "TAIL_BYTES");
+            CHECK(fr.begin == L.slab_bytes() && fr.begin + 4 * ((size_t)L.fr_len + BroadF32Lds::Z_PAD) == z.begin, "the z row of slot NBK_ZFIRST");
+            check_alias("k_broad_f32", region("raw q", L.slab(lds), slab, true), q);
+            check_alias("k_broad_f32", region("item queue", L.queue(lds), (size_t)L.qcap()), q);
+            check_alias("k_broad_f32", region("centre z rows", L.czrows(lds), (size_t)b * WAVE), q);
             CHECK(L.qcap() >= BQ_CAP && L.qcap() >= b * WAVE, "qcap %d: the general stage's queue and one unrolled block's items", L.qcap());
             CHECK(L.slab_bytes() == q.bytes, "the per-robot kernel's LDS is the slab");
         }
