@@ -559,6 +559,87 @@ int32_t nbk_edge_cloud_continuous_batch(const nbk_model *m, const nbk_cloud *c, 
 int32_t nbk_edge_shape_motion_bounds_host(const nbk_model_desc *desc, const double *starts, const double *goals, int64_t E, double *mu);
 
 /*
+ * Sampled B-spline trajectories against a cloud: nbk_spline_validity_batch's trajectories, nbk_cloud_validity_batch's verdict per
+ * sample -- re-checking a smoothed plan against the scan it was planned in.  The samples are generated on the device and never
+ * written down as q rows.
+ *   ctrl (device) [S][n_ctrl][n_q], degree k (1 .. NBK_MAX_SPLINE_DEGREE, k < n_ctrl <= 65536) and the knots tau [n_ctrl + k + 1], a
+ *   DEVICE array here (the call reads nothing back).  The trajectory rule is nbk_spline_validity_batch steps 1-4, word for word: V,
+ *   the degenerate rule, step, m, t_j, the span rule and de Boor in its operation order.
+ *   hit_j = the nbk_cloud_validity_batch verdict of q_j (same cloud, threshold and shape_bits: NULL = every robot shape, a selection
+ *   needs at most 256 robot shapes); a non-finite q_j collides.  valid [S] uint8 = no hit_j; t_hit (optional) [S] = t_j of the
+ *   SMALLEST colliding j, NaN when valid; n_samples (optional) [S] int32 -- bit for bit what a descriptor reports through
+ *   nbk_spline_validity_batch when it holds the points as sphere world shapes paired with the selected robot shapes.  A set cloud
+ *   status makes every non-degenerate trajectory invalid with t_hit = 0.0 (its first sample); an empty cloud or an empty selection
+ *   leaves every non-degenerate trajectory valid.
+ *   Knots that are not finite, nondecreasing and clamped on [0, 1] are found on the device (the rule of
+ *   nbk_spline_continuous_batch) and make every trajectory invalid, n_samples 0, t_hit NaN.  A trajectory of more than 2^31 - 1
+ *   samples is invalid, t_hit NaN, n_samples -1; none of its samples is looked at.
+ *   accumulate != 0: valid, and t_hit when given, hold on entry what nbk_spline_validity_batch wrote for the same arguments.  An
+ *   entry that is 0 on entry stays 0; with t_hit given only its samples with t_j < t_hit[s] are looked at and t_hit ends as the
+ *   smaller of the two, without t_hit none of its samples is looked at.  The scene's call followed by this one is then, bit for
+ *   bit, nbk_spline_validity_batch on the descriptor that holds scene and points together.  accumulate == 0 overwrites.
+ *   workspace: caller-owned device memory of at least nbk_spline_cloud_workspace_bytes(S) bytes (no GPU needed; < 0 for S < 0 and for S >= 2^26),
+ *   64-byte aligned: the plan, the counts, the offsets and one first-hit word per trajectory, 40 bytes per trajectory whatever the
+ *   sample count.  The descriptor's per-stream scratch is not touched.
+ * Asynchronous, no allocation, no host synchronisation, capturable for every descriptor (LDS holds the q rows only): five kernels on
+ * `stream` -- plan, the starting first-hit words (trajectories without samples to look at, or with too many, leave the flat range), scan, then one sample per lane, flat across the trajectories, on a grid of fixed
+ * size (8 workgroups of 64 lanes per compute unit) that strides to the sample total, which the host never learns; a hit lowers its
+ * trajectory's first-hit sample index with one 64-bit atomic minimum, and a lane whose index lies above it skips its sample; a last
+ * kernel decodes valid / t_hit / n_samples.
+ * NBK_ERR_INVALID -- before any device is looked for -- for null m / c, S < 0, null ctrl / knots / valid / workspace with S > 0, a
+ * degree outside 1 .. NBK_MAX_SPLINE_DEGREE, n_ctrl <= degree or > 65536, a resolution that is not positive and finite, a NaN
+ * threshold, a workspace that is too small or misaligned.  S = 0 returns NBK_OK at once.  NBK_ERR_UNSUPPORTED for S >= 2^26 and for a
+ * selection on a descriptor of more than 256 robot shapes.  The descriptor's and the cloud's device must be current.
+ */
+int64_t nbk_spline_cloud_workspace_bytes(int64_t S);
+int32_t nbk_spline_cloud_validity_batch(const nbk_model *m, const nbk_cloud *c, const double *ctrl, int64_t S, int32_t n_ctrl,
+                                        int32_t degree, const double *knots /* DEVICE, n_ctrl + degree + 1 */, double resolution,
+                                        double threshold, const uint64_t *shape_bits /* host, optional */, int32_t accumulate,
+                                        uint8_t *valid, double *t_hit /* optional */, int32_t *n_samples /* optional */,
+                                        void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Certified continuous B-spline trajectories against a cloud: nbk_spline_continuous_batch's trajectories (the degenerate rule, the
+ * knot check on the device, the keys in t_free while the call runs) and its loop, unchanged, on one (trajectory, selected robot
+ * shape s) item per lane; the cloud ALONE is looked at.  shape_bits as nbk_cloud_validity_batch.
+ *   Entering span ell gives mu = mu[ell][s] (nbk_spline_shape_motion_bounds_host), which bounds how fast any point of shape s moves
+ *   on that span; mu_max[s] is the largest of them over the trajectory's non-empty spans.
+ *   The item's distance at t: q(t) by de Boor (nbk_spline_validity_batch step 4); a non-finite q(t) gives NaN (UNDECIDED at t); else
+ *   with  D_end = (threshold + slack) + mu_max * (1 - t),  D_cap = (threshold + slack) + look_ahead,  D = D_end < D_cap ? D_end : D_cap:
+ *     some point i has signed distance (shape s, sphere of the cloud's radius at p_i) < D: d = the smallest one (the bits of
+ *     nbk_cloud_clearance_batch for shape s alone with d_max = D);  else D == D_end: d = +inf (the item stops FREE at 1);  else d = D_cap.
+ *   Sound: the loop carries an infinite gap across ALL remaining spans without another evaluation, so +inf may only be reported when
+ *   no point can be reached on the whole remainder [t, 1].  Each span's mu bounds the speed of the shape's points on that span, so
+ *   mu_max * (1 - t) bounds their travel from t to 1 and no point within D_end at t means the distance stays above threshold + slack
+ *   up to 1.  (The current span's mu in D_end would NOT be sound: a later span may be faster.)  A distance >= D_cap replaced by D_cap
+ *   is a lower bound, hence conservative, and is spent span by span with each span's own mu.
+ *   accumulate == 0: an empty cloud or an empty selection reports every non-degenerate trajectory FREE at 1.
+ *   accumulate != 0: valid / t_free / status hold on entry what nbk_spline_continuous_batch wrote for the same trajectories; the
+ *   result is bit for bit that of ONE conservative-advancement call over the scene's pairs and the cloud's items together.  A
+ *   non-degenerate trajectory that comes in with a NaN t_free keeps 0 / UNDECIDED / NaN.  Degenerate ones are DEGENERATE either way.
+ *   While the cloud's status is set every non-degenerate trajectory is invalid, UNDECIDED, t_free NaN.
+ * With n_ctrl = 2, k = 1, tau = [0, 0, 1, 1] this is nbk_edge_cloud_continuous_batch in connect mode with dist = NULL, bit for bit.
+ * Asynchronous, no allocation, no host synchronisation, no workspace, capturable for every descriptor: three kernels on `stream`,
+ * the middle one on a grid of (ceil(S / 64), selected shapes).  NBK_ERR_INVALID -- before any device is looked for -- for null m / c,
+ * S < 0, null ctrl / knots / valid / t_free / status with S > 0, a degree outside 1 .. NBK_MAX_SPLINE_DEGREE, n_ctrl <= degree or
+ * > 65536, max_iter < 1, slack < 0, a NaN slack / threshold, and look_ahead NaN or <= 0.  S = 0 returns NBK_OK at once.
+ * NBK_ERR_UNSUPPORTED for S > 2^31 - 1, a selection on more than 256 robot shapes, more than 65535 selected shapes.
+ */
+int32_t nbk_spline_cloud_continuous_batch(const nbk_model *m, const nbk_cloud *c, const double *ctrl, int64_t S, int32_t n_ctrl,
+                                          int32_t degree, const double *knots /* DEVICE, n_ctrl + degree + 1 */, double threshold,
+                                          int32_t max_iter, double slack, double look_ahead,
+                                          const uint64_t *shape_bits /* host, optional */, int32_t accumulate, uint8_t *valid,
+                                          double *t_free, int32_t *status, void *stream);
+/*
+ * The motion bounds mu [S][n_ctrl - degree][R] (span ell at index ell - degree, R robot shapes in the caller's order) that
+ * nbk_spline_cloud_continuous_batch advances with, on the host by the same routine (no GPU needed): the formula of
+ * nbk_spline_motion_bounds_host for a pair of (shape s, a world shape) -- every joint on the shape's path counts.  ctrl, knots (host);
+ * the knots must pass the rules of nbk_spline_validity_batch (NBK_ERR_INVALID otherwise).  Entries of empty spans are 0.
+ */
+int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const double *ctrl /* host */, int64_t S, int32_t n_ctrl,
+                                            int32_t degree, const double *knots /* host */, double *mu /* [S][n_ctrl-degree][R] */);
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -34,6 +34,8 @@ SYMBOLS = [
     "nbk_cloud_clearance_batch", "nbk_cloud_cells_host",
     "nbk_edge_cloud_workspace_bytes", "nbk_edge_cloud_validity_batch",
     "nbk_edge_cloud_continuous_batch", "nbk_edge_shape_motion_bounds_host",
+    "nbk_spline_cloud_workspace_bytes", "nbk_spline_cloud_validity_batch",
+    "nbk_spline_cloud_continuous_batch", "nbk_spline_shape_motion_bounds_host",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -138,6 +140,11 @@ def load():
     lib.nbk_edge_cloud_validity_batch.argtypes = [vp, vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, i32, vp, vp, vp, vp, i64, vp]
     lib.nbk_edge_cloud_continuous_batch.argtypes = [vp, vp, vp, vp, vp, i64, f64, i32, f64, i32, f64, f64, vp, i32, vp, vp, vp, vp, vp]
     lib.nbk_edge_shape_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, vp, i64, vp]
+    lib.nbk_spline_cloud_workspace_bytes.argtypes = [i64]
+    lib.nbk_spline_cloud_workspace_bytes.restype = i64
+    lib.nbk_spline_cloud_validity_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, f64, f64, vp, i32, vp, vp, vp, vp, i64, vp]
+    lib.nbk_spline_cloud_continuous_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, f64, i32, f64, f64, vp, i32, vp, vp, vp, vp]
+    lib.nbk_spline_shape_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, i64, i32, i32, vp, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

@@ -38,7 +38,7 @@ namespace nbk {
 // saturates at ~90 appends/us (MI355X_MICROARCH.md, row "dequeue"), which 15k waves would all hit.
 constexpr int NSUB = 256;
 }
-#include "nbk_plan.hpp"              // WsLayout, TilePlan, TableCache, the edge capacity rules, SplinePlan, Edge / EdgeCloud / SplineLayout: the host arithmetic of the launch paths
+#include "nbk_plan.hpp"              // WsLayout, TilePlan, TableCache, the edge capacity rules, SplinePlan, Edge / EdgeCloud / Spline / SplineCloudLayout: the host arithmetic of the launch paths
 static_assert(nbk::PLAN_WAVE == nbk::WAVE && nbk::PLAN_CNT_STRIDE == nbk::CNT_STRIDE && nbk::PLAN_NSUB == nbk::NSUB, "nbk_plan.hpp's stand-alone constants");
 #include "nbk_lds.hpp"               // the dynamic LDS of every kernel family: region pointers for the kernels' carves, bytes() and fits() for the launches; LDS_MAX and the queue capacities
 static_assert(nbk::LDS_WAVE == nbk::WAVE && nbk::LDS_BQ_CAP == nbk::BQ_CAP, "nbk_lds.hpp's stand-alone constants");
@@ -3438,9 +3438,22 @@ constexpr unsigned long long CA_KEEP_KEY = ~0ull;               // the result is
 
 NBK_DEV unsigned long long ca_key(double t, unsigned long long rank) { return (__builtin_bit_cast(unsigned long long, t) << 2) | rank; }
 
-// hold (nullable): a status word that, when set, makes CA_KEEP_KEY of every non-degenerate edge (a cloud's hdr->status).
+// The starting key of non-degenerate trajectory e, whose stop point is Tf (k_edge_ca_init, k_spline_ca_init).
+// hold (nullable): a status word that, when set, makes CA_KEEP_KEY of every non-degenerate trajectory (a cloud's hdr->status).
 // prev (nullable): accumulating -- the status array of the certified call whose t_free the keys alias; each key is re-encoded from
-// the two, and an edge that comes in with a NaN t_free keeps CA_KEEP_KEY.
+// the two, and a trajectory that comes in with a NaN t_free keeps CA_KEEP_KEY.
+NBK_DEV unsigned long long ca_start_key(double Tf, const int* hold, const int32_t* prev, const unsigned long long* key, int64_t e) {
+    unsigned long long k = ca_key(Tf, CA_FREE);
+    if (prev) {
+        const double t0 = __builtin_bit_cast(double, key[e]);
+        const int32_t st = prev[e];
+        k = t0 != t0 ? CA_KEEP_KEY : ca_key(t0, st == NBK_CA_FREE ? CA_FREE : (st == NBK_CA_COLLISION ? CA_COLLISION : CA_UNDECIDED));
+    }
+    if (hold && *hold != 0) k = CA_KEEP_KEY;
+    return k;
+}
+
+// hold, prev: as ca_start_key
 __global__ void k_edge_ca_init(int nq, const double* __restrict__ starts, const double* __restrict__ goals, const double* __restrict__ dist,
                                int64_t E, double max_distance, int mode, const int* __restrict__ hold, const int32_t* __restrict__ prev,
                                double* __restrict__ end, unsigned long long* __restrict__ key) {
@@ -3454,14 +3467,7 @@ __global__ void k_edge_ca_init(int nq, const double* __restrict__ starts, const 
         if (end) for (int i = 0; i < nq; ++i) end[e * nq + i] = __builtin_nan("");
         return;
     }
-    unsigned long long k = ca_key(Tf, CA_FREE);
-    if (prev) {
-        const double t0 = __builtin_bit_cast(double, key[e]);
-        const int32_t st = prev[e];
-        k = t0 != t0 ? CA_KEEP_KEY : ca_key(t0, st == NBK_CA_FREE ? CA_FREE : (st == NBK_CA_COLLISION ? CA_COLLISION : CA_UNDECIDED));
-    }
-    if (hold && *hold != 0) k = CA_KEEP_KEY;
-    key[e] = k;
+    key[e] = ca_start_key(Tf, hold, prev, key, e);
     write_edge_end(nq, s, g, e, mode, Tf, end);
 }
 
@@ -3747,22 +3753,30 @@ __global__ __launch_bounds__(64) void k_spline_reduce(const double* __restrict__
 // A degenerate trajectory (V outside (2^-23, DBL_MAX], a non-finite control point, or knots that are not finite, nondecreasing and
 // clamped on [0, 1]) gets the key CA_DEGENERATE_KEY: no item of it runs.
 
-// one wave per trajectory: key[s] = "FREE at 1", or CA_DEGENERATE_KEY
-__global__ __launch_bounds__(64) void k_spline_ca_init(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
-                                                      unsigned long long* __restrict__ key) {
-    const int64_t s = blockIdx.x;
-    const int lane = threadIdx.x;
-    const double* c = ctrl + (size_t)s * (size_t)n * nq;
+// the knot rules on the device, over one wave: are the knots finite, nondecreasing and clamped on [0, 1]?  The same in every lane.
+NBK_DEV bool spline_knots_bad(const double* __restrict__ knots, int n, int k, int lane) {
     bool bad = false;
     for (int i = lane; i < n + k + 1; i += WAVE) {
         const double x = knots[i];
         bad = bad || !(__builtin_fabs(x) <= 1.7976931348623157e308) || (i > 0 && x < knots[i - 1]) || (i <= k && x != 0.0) ||
               (i >= n && x != 1.0);
     }
+    return __builtin_amdgcn_ballot_w64(bad) != 0ull;
+}
+
+// one wave per trajectory: key[s] = "FREE at 1" (hold, prev: as ca_start_key; both null for the scene's own splines), or
+// CA_DEGENERATE_KEY
+__global__ __launch_bounds__(64) void k_spline_ca_init(int nq, const double* __restrict__ ctrl, int n, int k, const double* __restrict__ knots,
+                                                      const int* __restrict__ hold, const int32_t* __restrict__ prev,
+                                                      unsigned long long* __restrict__ key) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const double* c = ctrl + (size_t)s * (size_t)n * nq;
+    bool bad = false;
     for (size_t i = lane; i < (size_t)n * nq; i += WAVE) bad = bad || !(__builtin_fabs(c[i]) <= 1.7976931348623157e308);
-    const bool deg = __builtin_amdgcn_ballot_w64(bad) != 0ull;
+    const bool deg = spline_knots_bad(knots, n, k, lane) || __builtin_amdgcn_ballot_w64(bad) != 0ull;
     const double V = spline_speed_bound(nq, c, n, k, knots, lane);
-    if (lane == 0) key[s] = (deg || spline_degenerate(V)) ? CA_DEGENERATE_KEY : ca_key(1.0, CA_FREE);
+    if (lane == 0) key[s] = (deg || spline_degenerate(V)) ? CA_DEGENERATE_KEY : ca_start_key(1.0, hold, prev, key, s);
 }
 
 // trajectory s of degree K on [0, 1]: spans of the shared knots; entering the span of t finds it (spline_span) and bounds the pair's
@@ -4886,6 +4900,14 @@ static int32_t launch_edge_ca_init(const nbk_model* m, hipStream_t st, const dou
     return NBK_OK;
 }
 
+static int32_t launch_spline_ca_init(const nbk_model* m, hipStream_t st, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                     const double* knots, const int* hold, const int32_t* prev, double* t_free) {
+    hipLaunchKernelGGL(k_spline_ca_init, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, hold, prev,
+                       ca_keys(t_free));
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
 static int32_t launch_ca_final(hipStream_t st, int64_t n, uint8_t* valid, double* t_free, int32_t* status) {
     hipLaunchKernelGGL(k_ca_final, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const unsigned long long*)ca_keys(t_free), valid,
                        t_free, status);
@@ -4978,6 +5000,28 @@ int32_t nbk_spline_motion_bounds_host(const nbk_model_desc* d, const double* ctr
             const bool span = knots[ell] < knots[ell + 1];
             const SplineSpanMotion tr{c + (size_t)(ell - k) * nq, knots + (ell - k + 1), nq, k};
             for (int p = 0; p < P; ++p) out[p] = span ? pair_motion_bound(t, p, tr) : 0.0;
+        }
+    }
+    return NBK_OK;
+}
+
+int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc* d, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                            const double* knots, double* mu) {
+    if (d == nullptr || S < 0 || !spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;
+    { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
+    const int R = d->n_rshapes, nq = d->n_q, k = degree, L = n_ctrl - degree;
+    if (S == 0 || R == 0) return NBK_OK;
+    if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_args_ok(n_ctrl, degree, knots)) return NBK_ERR_INVALID;
+    MotionHost h;
+    motion_tables(d, frame_masks(d), h);
+    const MotionTab t = h.view(d->n_joints, R);
+    for (int64_t s = 0; s < S; ++s) {
+        const double* c = ctrl + (size_t)s * (size_t)n_ctrl * nq;
+        for (int ell = k; ell < n_ctrl; ++ell) {
+            double* out = mu + ((size_t)s * L + (size_t)(ell - k)) * R;
+            const bool span = knots[ell] < knots[ell + 1];
+            const SplineSpanMotion tr{c + (size_t)(ell - k) * nq, knots + (ell - k + 1), nq, k};
+            for (int x = 0; x < R; ++x) out[x] = span ? shape_motion_bound(t, x, tr) : 0.0;
         }
     }
     return NBK_OK;
@@ -5169,8 +5213,7 @@ int32_t nbk_spline_continuous_batch(const nbk_model* m, const double* ctrl, int6
     if (S > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* key = ca_keys(t_free);
-    hipLaunchKernelGGL(k_spline_ca_init, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, key);
-    NBK_HIP(hipGetLastError());
+    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, nullptr, nullptr, t_free); if (rc != NBK_OK) return rc; }
     if (N > 0) {
         const dim3 grid((unsigned)((N + WAVE - 1) / WAVE)), block(WAVE);
         const size_t lds = QSlabLds(m->n_q, 1).bytes();

@@ -25,6 +25,11 @@
 //
 // Certified edges (nbk_edge_cloud_continuous_batch): nbk.hip's k_edge_ca_init -> k_cloud_edge_ca (ca_walk on CloudEdgeLane) -> nbk.hip's
 // k_ca_final; the keys and their reserved values are defined once, beside ca_key.
+//
+// B-spline trajectories (nbk_spline_cloud_validity_batch, nbk_spline_cloud_continuous_batch): the trajectory rule is nbk.hip's own
+// (k_spline_plan, k_scan, spline_span, de_boor, k_spline_ca_init, SplineSpanMotion); k_cloud_spline walks one sample per lane on a grid
+// of fixed size with a first-hit word per trajectory in the caller's workspace (SplineCloudLayout, nbk_plan.hpp), k_cloud_spline_ca is
+// ca_walk on CloudSplineLane.
 #pragma once
 #define NBK_GRID_FN __host__ __device__ inline
 #include "nbk_cloud_grid.hpp"
@@ -477,6 +482,219 @@ __global__ __launch_bounds__(64) void k_cloud_edge_ca(DevModel m, CloudDev cd, C
     ca_walk(m, tr, run, rs_user[p], p, lane, thr, max_iter, slack, key + e);
 }
 
+// ---- sampled B-spline trajectories against the cloud (nbk_spline_cloud_validity_batch) -------------------------------------------
+// Per trajectory s the workspace holds a 64-bit first-hit key, lowered with atomicMin while the sample kernel runs:
+//   j + 1 (1 .. 2^31)   sample j collides and no smaller colliding sample is known: only samples below j are still looked at
+//   SPC_NONE            open: every sample is looked at, none has collided
+//   above SPC_NONE      closed: no sample is looked at, and k_cloud_spline_final reports what the code says
+constexpr unsigned long long SPC_NONE = 1ull << 62;
+constexpr unsigned long long SPC_KEEP = SPC_NONE + 1ull;          // accumulating: the entry came in 0 without a t_hit to lower; it stays as it is
+constexpr unsigned long long SPC_EMPTY = SPC_NONE + 2ull;         // no samples (the degenerate trajectory; bad knots): 0 / NaN / 0
+constexpr unsigned long long SPC_TOO_MANY = SPC_NONE + 3ull;      // more than 2^31 - 1 samples: 0 / NaN / -1
+constexpr unsigned long long SPC_MAX_SAMPLES = 0x7fffffffull;
+
+// one wave per trajectory, BEFORE the scan: the starting key.  Knots that break the rules (spline_knots_bad, the rule of
+// k_spline_ca_init) close every trajectory; a set cloud status hits every trajectory that has samples at its first one; accumulating,
+// an entry that is 0 and has no finite t_hit to lower is closed (t_prev: the caller's t_hit, null when it gave none or does not
+// accumulate).  A trajectory closed as SPC_EMPTY or SPC_TOO_MANY gets the count 0, so the flat sample range holds no sample of it
+// and the sample kernel's run time is bounded by the samples that can be looked at (k_cloud_spline_final reads 0 / -1 off the key).
+__global__ __launch_bounds__(64) void k_cloud_spline_init(int n, int k, const double* __restrict__ knots,
+                                                          unsigned long long* __restrict__ cnt, const int* __restrict__ hold,
+                                                          int accumulate, const uint8_t* __restrict__ valid,
+                                                          const double* __restrict__ t_prev, unsigned long long* __restrict__ first) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const bool bad = spline_knots_bad(knots, n, k, lane);
+    if (lane != 0) return;
+    const unsigned long long c = cnt[s];
+    unsigned long long key = SPC_NONE;
+    if (bad || c == 0ull) key = SPC_EMPTY;
+    else if (c > SPC_MAX_SAMPLES) key = SPC_TOO_MANY;
+    else if (*hold != 0) key = 1ull;
+    else if (accumulate && valid[s] == 0 && (t_prev == nullptr || t_prev[s] != t_prev[s])) key = SPC_KEEP;
+    if (key == SPC_EMPTY || key == SPC_TOO_MANY) cnt[s] = 0ull;
+    first[s] = key;
+}
+
+// One sample per lane, FLAT across the trajectories, as k_cloud_edges: sample f of [0, total) belongs to the largest trajectory s with
+// offs[s] <= f (trajectories without samples fall out by themselves: equal offsets) and is sample j = f - offs[s] of it; t_j, the
+// span and de Boor are k_spline_expand's expressions, with the row going to the lane's LDS row instead of a slab.  The grid has a
+// fixed size (SPLINE_CLOUD_WAVES_PER_CU); a workgroup strides over 64-sample blocks until `total`, read here, never by the host.
+// A lane skips its sample when the trajectory's key says so (closed, or a hit at or below j is known), or -- accumulating with a
+// t_hit -- when t_j is not below the t_hit the entry came in with (a NaN there: the entry came in valid, every sample counts).
+template <int K>
+__global__ __launch_bounds__(64) void k_cloud_spline(DevModel m, CloudDev cd, CloudSel sel, const double* __restrict__ ctrl, int n,
+                                                     const double* __restrict__ knots, const double* __restrict__ plan,
+                                                     const unsigned long long* __restrict__ offs, int64_t S, double thr,
+                                                     const double* __restrict__ t_prev, unsigned long long* first) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    double* myq = lds + lane * m.n_q;
+    const unsigned long long total = offs[S];
+    const int ncl = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * WAVE; base < total; base += (unsigned long long)gridDim.x * WAVE) {
+        const unsigned long long f = base + (unsigned long long)lane;
+        int64_t s = 0;
+        unsigned long long j = 0ull;
+        bool work = false, hit = false;
+        if (f < total) {
+            int64_t hi = S;                                  // offs[s] <= f < offs[hi]
+            while (hi - s > 1) {
+                const int64_t mid = s + ((hi - s) >> 1);
+                if (offs[mid] <= f) s = mid; else hi = mid;
+            }
+            j = f - offs[s];
+            const unsigned long long key = __hip_atomic_load(first + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (key <= SPC_NONE && j + 1ull < key) {
+                const double jd = (double)j;
+                const double t = jd < plan[2 * s + 1] ? jd * plan[2 * s] : 1.0;
+                if (t_prev == nullptr || !(t >= t_prev[s])) {
+                    const int ell = spline_span<K>(knots, n, t);
+                    const double* cp = ctrl + ((size_t)s * (size_t)n + (size_t)(ell - K)) * m.n_q;
+                    de_boor<K>(m.n_q, cp, knots, ell, t, [&](int c, double v) { myq[c] = v; });
+                    work = !row_nonfinite(myq, m.n_q, 1);
+                    hit = !work;                             // a non-finite sample collides
+                }
+            }
+        }
+        if (ncl > 0 && __builtin_amdgcn_ballot_w64(work) != 0ull) cloud_row_hits(m, cd, sel, radius, thr, myq, work, hit);
+        if (hit) atomicMin(first + s, j + 1ull);
+    }
+}
+
+// key -> valid / t_hit / n_samples.  Accumulating, an open trajectory without a hit keeps what it came in with (1 / NaN, or 0 and
+// the scene's t_hit); t_j by the expression of k_spline_reduce.
+__global__ __launch_bounds__(256) void k_cloud_spline_final(int64_t S, const double* __restrict__ plan, const unsigned long long* __restrict__ cnt,
+                                                            const unsigned long long* __restrict__ first, int accumulate,
+                                                            uint8_t* __restrict__ valid, double* __restrict__ t_hit,
+                                                            int32_t* __restrict__ n_samples) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const unsigned long long key = first[s];
+    if (n_samples != nullptr) n_samples[s] = key == SPC_EMPTY ? 0 : (key == SPC_TOO_MANY ? -1 : (int32_t)cnt[s]);
+    if (key == SPC_EMPTY || key == SPC_TOO_MANY) {
+        valid[s] = 0;
+        if (t_hit != nullptr) t_hit[s] = __builtin_nan("");
+    } else if (key == SPC_KEEP) valid[s] = 0;
+    else if (key == SPC_NONE) {
+        if (!accumulate) { valid[s] = 1; if (t_hit != nullptr) t_hit[s] = __builtin_nan(""); }
+    } else {
+        valid[s] = 0;
+        const double j = (double)(key - 1ull);
+        if (t_hit != nullptr) t_hit[s] = j < plan[2 * s + 1] ? j * plan[2 * s] : 1.0;
+    }
+}
+
+// ---- certified continuous B-splines against the cloud (nbk_spline_cloud_continuous_batch) ----------------------------------------
+// ca_walk as it is, on one (trajectory, selected robot shape) item per lane, grid (ceil(S / 64), selected shapes) as k_cloud_edge_ca;
+// init is nbk.hip's k_spline_ca_init (hold = the cloud's status, prev when accumulating), final its k_ca_final.  The lane is
+// SplineLane's trajectory with CloudEdgeLane's distance: entering a span gives mu = shape_motion_bound on that span, q(t) goes by
+// de_boor into the lane's LDS row, and the distance is the shape's clearance from the cloud cut at
+//     D = min(D_end, D_cap),   D_end = (thr + slack) + mu_max (1 - t),   D_cap = (thr + slack) + look_ahead,
+// the smallest distance below D where there is one; else +inf when D == D_end; else D_cap.  mu_max is the LARGEST span bound of the
+// trajectory over its non-empty spans, not the current span's.  Soundness of the +inf:
+//   * ca_walk carries an infinite gap across ALL remaining spans without another evaluation (gap - mu (hi - t) stays infinite), so
+//     +inf at t stops the item FREE at 1: it may only be reported when no point can be reached on the whole remainder [t, 1];
+//   * each span's mu bounds the speed of every point of the shape on that span, so mu_max bounds it on every span, and no point of
+//     the shape travels further than mu_max (1 - t) between q(t) and any q(t'), t' in [t, 1]; the cloud stands still;
+//   * so no point within D_end at t means that the distance stays above thr + slack up to 1;
+//   * D_cap is a lower bound of a distance that is not below it, and advancing on a lower bound is conservative, span by span with
+//     each span's own mu, as for the scene's pairs.
+// With n = 2, K = 1 and the knots [0, 0, 1, 1] there is one span, mu_max = mu and T_f = 1: CloudEdgeLane's bits in connect mode.
+template <int K>
+struct CloudSplineLane {
+    const double* c;          // control points of the trajectory, [n][nq]
+    const double* knots;
+    int n, nq, ell;
+    const CloudDev& cd;
+    double radius;            // of the cloud's points
+    double* myq;              // the lane's LDS row
+    double d_base, d_cap;     // thr + slack; (thr + slack) + look_ahead
+    double mu_max;
+    NBK_DEV double end() const { return 1.0; }
+    NBK_DEV double span_end() const { return knots[ell + 1]; }
+    NBK_DEV double span_bound(const DevModel& m, int pu, int span) const {
+        return shape_motion_bound(m.mt, pu, SplineSpanMotion{c + (size_t)(span - K) * nq, knots + (span - K + 1), nq, K});
+    }
+    NBK_DEV double enter(const DevModel& m, int pu, double t) {
+        ell = spline_span<K>(knots, n, t);
+        return span_bound(m, pu, ell);
+    }
+    // the largest bound over the non-empty spans: what D_end may use (see above)
+    NBK_DEV void bound_all(const DevModel& m, int pu) {
+        mu_max = 0.0;
+        for (int span = K; span < n; ++span) {
+            if (!(knots[span] < knots[span + 1])) continue;
+            const double mu = span_bound(m, pu, span);
+            mu_max = mu > mu_max ? mu : mu_max;
+        }
+    }
+    NBK_DEV double distance(const DevModel& m, bool run, int p, int, double t, double*) {
+        bool ok = false;
+        if (run) {
+            double* r = myq;
+            de_boor<K>(nq, c + (size_t)(ell - K) * nq, knots, ell, t, [&](int j, double v) { r[j] = v; });
+            ok = !row_nonfinite(myq, nq, 1);
+        }
+        Core P;
+        cloud_point_core(radius, P);
+        Core A;
+        cloud_core_init(A);
+        double D_end = 0.0, D = 0.0;
+        if (ok) {
+            Xf T;
+            cloud_shape_frame(m, p, myq, T);
+            build_core(m, p, T, A);
+            if (A.kind == K_HULL) A.rad = -1.0;
+            // mu_max, NOT the current span's mu: +inf frees the item up to 1 across every later span (ca_walk evaluates nothing
+            // there), and a later span may be faster than this one -- a per-span D_end would free a trajectory that sweeps into a
+            // point after a slow start
+            D_end = d_base + mu_max * (1.0 - t);
+            D = D_end < d_cap ? D_end : d_cap;
+        }
+        double best = NBK_INF;
+        int bs = -1, bi = -1;
+        cloud_core_clearance(cd, A, P, radius, ok, 0, D, best, bs, bi);
+        if (!ok) return __builtin_nan("");
+        if (best < D) return best;
+        return D == D_end ? NBK_INF : d_cap;
+    }
+};
+
+template <int K>
+__global__ __launch_bounds__(64) void k_cloud_spline_ca(DevModel m, CloudDev cd, CloudSel sel, const int* __restrict__ rs_user,
+                                                        const double* __restrict__ ctrl, int64_t S, int n,
+                                                        const double* __restrict__ knots, double thr, int max_iter, double slack,
+                                                        double look_ahead, unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    // the blockIdx.y-th selected shape, device order
+    int p = -1;
+    for (int i = 0, k = 0; i < m.n_rshapes; ++i) {
+        if (!cloud_selected(sel, i)) continue;
+        if (k == (int)blockIdx.y) { p = i; break; }
+        ++k;
+    }
+    if (p < 0) return;
+    const int ncl = cd.hdr->n;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < S;
+    const int64_t s = live ? i : 0;
+    const double base = thr + slack;
+    CloudSplineLane<K> tr{ctrl + (size_t)s * (size_t)n * m.n_q, knots, n, m.n_q, K, cd, cd.hdr->radius, lds + lane * m.n_q, base,
+                          base + look_ahead, 0.0};
+    // (an empty cloud stops every item FREE at 1, which is where its key stands; the keys of a cloud whose status is set are all reserved)
+    bool run = false;
+    if (live && ncl > 0) {
+        const unsigned long long k0 = __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        run = k0 != CA_DEGENERATE_KEY && k0 != CA_KEEP_KEY;
+    }
+    const int pu = rs_user[p];
+    if (run) tr.bound_all(m, pu);
+    ca_walk(m, tr, run, pu, p, lane, thr, max_iter, slack, key + s);
+}
+
 }  // namespace nbk
 
 struct nbk_cloud {
@@ -702,6 +920,95 @@ int32_t nbk_edge_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, 
         NBK_HIP(hipGetLastError());
     }
     return launch_ca_final(st, E, valid, t_free, status);
+}
+
+int64_t nbk_spline_cloud_workspace_bytes(int64_t S) {
+    if (S < 0 || S >= SPLINE_MAX_S) return -1;              // (the entry takes fewer than SPLINE_MAX_S trajectories)
+    return (int64_t)SplineCloudLayout(S).bytes;
+}
+
+// the selected shapes of a call, counted
+static int cloud_selected_count(const nbk_model* m, const CloudSel& sel) {
+    if (sel.all) return m->d.n_rshapes;
+    int n_sel = 0;
+    for (int k = 0; k < 4; ++k) n_sel += __builtin_popcountll(sel.w[k]);
+    return n_sel;
+}
+
+int32_t nbk_spline_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                        const double* knots, double resolution, double threshold, const uint64_t* shape_bits,
+                                        int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+    // (as nbk_edge_cloud_validity_batch: the argument rules are answered without a device)
+    if (m == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
+    if (S > 0 && S < SPLINE_MAX_S &&
+        (workspace_bytes < (int64_t)SplineCloudLayout(S).bytes || (reinterpret_cast<uintptr_t>(workspace) & 63) != 0)) return NBK_ERR_INVALID;
+    if (S == 0) return NBK_OK;
+    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    int cus = 0;
+    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
+    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
+    NBK_HIP(hipGetLastError());
+    const double* t_prev = accumulate ? t_hit : nullptr;
+    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt,
+                       (const int*)&c->hdr->status, (int)accumulate, (const uint8_t*)valid, t_prev, v.first);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
+    NBK_HIP(hipGetLastError());
+    const CloudSel sel = cloud_selection(m, shape_bits);
+    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
+    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
+    const size_t lds = QSlabLds(m->n_q).bytes();
+    with_degree(degree, [&](auto K) {
+        hipLaunchKernelGGL(k_cloud_spline<decltype(K)::value>, grid, block, lds, st, m->d, cloud_dev(c), sel, ctrl, (int)n_ctrl, knots,
+                           (const double*)v.plan, (const unsigned long long*)v.offs, S, threshold, t_prev, v.first);
+    });
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
+                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_spline_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, const double* ctrl, int64_t S, int32_t n_ctrl,
+                                          int32_t degree, const double* knots, double threshold, int32_t max_iter, double slack,
+                                          double look_ahead, const uint64_t* shape_bits, int32_t accumulate, uint8_t* valid,
+                                          double* t_free, int32_t* status, void* stream) {
+    // (the argument rules are answered without a device)
+    if (m == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
+    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
+    if (S == 0) return NBK_OK;
+    if (S > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    const CloudSel sel = cloud_selection(m, shape_bits);
+    const int n_sel = cloud_selected_count(m, sel);
+    if (n_sel > 65535) return NBK_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, &c->hdr->status, accumulate ? status : nullptr, t_free);
+      if (rc != NBK_OK) return rc; }
+    if (n_sel > 0) {
+        const dim3 grid(blocks_for(S), (unsigned)n_sel), block(WAVE);
+        const size_t lds = QSlabLds(m->n_q).bytes();
+        with_degree(degree, [&](auto K) {
+            hipLaunchKernelGGL(k_cloud_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, cloud_dev(c), sel, m->rs_user, ctrl, S,
+                               (int)n_ctrl, knots, threshold, (int)max_iter, slack, look_ahead, ca_keys(t_free));
+        });
+        NBK_HIP(hipGetLastError());
+    }
+    return launch_ca_final(st, S, valid, t_free, status);
 }
 
 }  // extern "C"

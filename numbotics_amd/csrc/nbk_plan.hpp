@@ -238,6 +238,26 @@ struct SplineLayout {
                 reinterpret_cast<unsigned long long*>(p + offs)};
     }
 };
+// the caller's workspace of nbk_spline_cloud_validity_batch: plan [S][2] double | cnt [S] | offs [S + 1] | first [S] (the first-hit
+// keys), each part rounded up to 64 bytes: 40 bytes per trajectory whatever the sample count
+struct SplineCloudLayout {
+    size_t cnt, offs, first, bytes;
+    static size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
+    explicit SplineCloudLayout(int64_t S)
+        : cnt(r64((size_t)S * 16)), offs(cnt + r64((size_t)S * 8)), first(offs + r64(((size_t)S + 1) * 8)), bytes(first + r64((size_t)S * 8)) {}
+    struct View { double* plan; unsigned long long *cnt, *offs, *first; };
+    View view(void* base) const {
+        char* p = static_cast<char*>(base);
+        return {reinterpret_cast<double*>(p), reinterpret_cast<unsigned long long*>(p + cnt), reinterpret_cast<unsigned long long*>(p + offs),
+                reinterpret_cast<unsigned long long*>(p + first)};
+    }
+};
+// The sample kernel of that entry runs on a grid of fixed size, CUs x this many 64-lane workgroups, and strides to the sample total,
+// which only the device knows.  The kernel takes 256 + 162 registers, so ONE wave fits a SIMD and four workgroups are resident per
+// CU; 8 per CU is two rounds of them, so that a workgroup whose samples are mostly skipped (behind a first hit) ends early and its
+// SIMD takes another instead of idling to the end of the launch.  A guess until it is measured against 4 and 16.
+constexpr int SPLINE_CLOUD_WAVES_PER_CU = 8;
+
 // the large half, known once the sample total T (< SPLINE_MAX_T) is read back: mask words [T / 64], rounded up to 256 bytes | the q
 // slab [tile][n_q] of one tile, only for a robot with pairs.  Tiles of min(T in whole 64-row blocks, SPLINE_TILE) rows: at(0 .. tiles - 1)
 struct SplinePlan {

@@ -148,6 +148,29 @@ def spline_motion_bounds(model, ctrl, knots, degree):
     return mu
 
 
+def spline_shape_motion_bounds(model, ctrl, knots, degree):
+    """Motion bounds mu (S, n - degree, R) of S clamped B-splines ctrl (S, n, n_q) sharing the knots, per knot span ell (index
+    ell - degree) and robot shape of a SceneModel, in its shape order, against a world that stands still: no point of shape x moves
+    further than mu[s, ell - degree, x] |t - t'| between q(t) and q(t') for t, t' in [knots[ell], knots[ell+1]].  The routine
+    nbk_spline_cloud_continuous_batch advances with, run on the host (nbk_spline_shape_motion_bounds_host); no GPU needed.
+    Entries of empty spans are 0."""
+    n_q = getattr(model, "kin", model).n_q
+    c = np.ascontiguousarray(np.asarray(ctrl, dtype=np.float64))
+    if c.ndim != 3 or c.shape[2] != n_q:
+        raise ValueError(f"control points must have shape (S, n, {n_q}), got {c.shape}")
+    S, n = c.shape[:2]
+    k = int(degree)
+    if not 1 <= k < n:
+        raise ValueError("degree must be at least 1 and less than the number of control points")
+    kn = _host_f64(knots, n + k + 1)
+    d, keep = model_desc(model)
+    mu = np.zeros((S, n - k, int(d.n_rshapes)), dtype=np.float64)
+    _lib.check(_lib.load().nbk_spline_shape_motion_bounds_host(C.byref(d), c.ctypes.data, S, n, k, kn.ctypes.data, mu.ctypes.data),
+               "nbk_spline_shape_motion_bounds_host")
+    del keep
+    return mu
+
+
 def _world_poses_host(poses, n_wshapes):
     """(W, 12) float64 C-contiguous from (W, 12) / (W, 3, 4) / (W, 4, 4) host input."""
     a = np.asarray(poses, dtype=np.float64)
@@ -687,12 +710,7 @@ class DeviceModel:
             t_free = torch.empty((s.B,), dtype=torch.float64, device=s.device)
             status = torch.empty((s.B,), dtype=torch.int32, device=s.device)
         else:
-            want = ((torch.uint8, torch.bool), (torch.float64,), (torch.int32,))
-            if not (isinstance(out, (tuple, list)) and len(out) == 3 and
-                    all(torch.is_tensor(o) and o.is_cuda and o.is_contiguous() and tuple(o.shape) == (s.B,) and o.dtype in w
-                        for o, w in zip(out, want))):
-                raise ValueError(f"out must be (valid, t_free, status): contiguous CUDA tensors of shape {(s.B,)} (uint8 / bool, float64, int32)")
-            valid, t_free, status = out
+            valid, t_free, status = self._out_tensors(torch, out, s.B, "(valid, t_free, status)")
         end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
         _lib.check(self._lib.nbk_edge_cloud_continuous_batch(
             self._h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
@@ -728,6 +746,18 @@ class DeviceModel:
         n_q), knots n + degree + 1 values (copied to the device of ctrl) -> valid (S,) bool, t_free (S,) (how far along [0, 1] the
         trajectory is certified free), status (S,) int32 (``_lib.CA_*``).  Asynchronous on device tensors and capturable."""
         torch = _require_gpu()
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
+        t_free = torch.empty((S,), dtype=torch.float64, device=c.device)
+        status = torch.empty((S,), dtype=torch.int32, device=c.device)
+        _lib.check(self._lib.nbk_spline_continuous_batch(
+            self._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
+            valid.data_ptr(), t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_continuous_batch")
+        return c.out(valid.bool()), c.out(t_free), c.out(status)
+
+    def _stage_splines(self, ctrl, knots, degree):
+        """The control points and the knots of S splines on one device -> (ctrl ``_Staged``, knots tensor, S, n)."""
+        torch = _require_gpu()
         shape = tuple(ctrl.shape) if torch.is_tensor(ctrl) else np.shape(ctrl)
         if len(shape) != 3 or shape[2] != self.n_q:
             raise ValueError(f"control points must have shape (S, n, {self.n_q}), got {shape}")
@@ -739,12 +769,74 @@ class DeviceModel:
             kn = torch.from_numpy(_host_f64(knots, n + int(degree) + 1)).to(c.device)
         if kn.numel() != n + int(degree) + 1:
             raise ValueError(f"expected {n + int(degree) + 1} knots, got {kn.numel()}")
-        valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
-        t_free = torch.empty((S,), dtype=torch.float64, device=c.device)
-        status = torch.empty((S,), dtype=torch.int32, device=c.device)
-        _lib.check(self._lib.nbk_spline_continuous_batch(
-            self._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
-            valid.data_ptr(), t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_continuous_batch")
+        return c, kn, S, n
+
+    @staticmethod
+    def _out_tensors(torch, out, S, names):
+        """``out`` of the accumulating cloud calls over edges and splines: three contiguous CUDA tensors of shape (S,), uint8 / bool,
+        float64 and int32."""
+        want = ((torch.uint8, torch.bool), (torch.float64,), (torch.int32,))
+        if not (isinstance(out, (tuple, list)) and len(out) == 3 and
+                all(torch.is_tensor(o) and o.is_cuda and o.is_contiguous() and tuple(o.shape) == (S,) and o.dtype in w
+                    for o, w in zip(out, want))):
+            raise ValueError(f"out must be {names}: contiguous CUDA tensors of shape {(S,)} (uint8 / bool, float64, int32)")
+        return tuple(out)
+
+    @staticmethod
+    def cloud_spline_workspace_bytes(S: int) -> int:
+        return int(_lib.load().nbk_spline_cloud_workspace_bytes(int(S)))
+
+    def cloud_spline_validity(self, cloud, ctrl, knots, degree, resolution, threshold=0.0, shapes=None, out=None, workspace=None):
+        """``spline_validity``'s trajectories against ``cloud`` ALONE (a ``PointCloud``; nbk_spline_cloud_validity_batch): a
+        trajectory is valid when it is not degenerate and ``cloud_validity`` clears every one of its samples (generated on the
+        device, never stored) -> (valid (S,) bool, t_hit (S,) (t of the first colliding sample, NaN when valid), n_samples (S,)
+        int32).  The knots are copied to the device of ctrl; the call is asynchronous on device tensors and capturable.
+        ``shapes``: as ``cloud_validity``.  ``out``: the CUDA tensors (valid (S,) uint8 / bool, t_hit (S,) float64, n_samples (S,)
+        int32) that ``spline_validity`` returned for the same trajectories and resolution: the cloud's verdict is reduced INTO them
+        -- an invalid entry stays invalid, only samples before its t_hit are looked at, and t_hit ends as the smaller of the two;
+        they are returned.  ``workspace``: optional torch uint8 CUDA tensor of at least ``cloud_spline_workspace_bytes(S)`` bytes;
+        by default one is taken from torch's caching allocator (inside a graph capture: from the capture's pool)."""
+        torch = _require_gpu()
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        bits = self._shape_bits(shapes)
+        if out is None:
+            valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
+            t_hit = torch.empty((S,), dtype=torch.float64, device=c.device)
+            ns = torch.empty((S,), dtype=torch.int32, device=c.device)
+        else:
+            valid, t_hit, ns = self._out_tensors(torch, out, S, "(valid, t_hit, n_samples)")
+        ws = torch.empty((self.cloud_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device) if workspace is None else workspace
+        _lib.check(self._lib.nbk_spline_cloud_validity_batch(
+            self._h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
+            None if bits is None else bits.ctypes.data, 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
+            ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_cloud_validity_batch")
+        if out is not None:
+            return valid, t_hit, ns
+        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+
+    def cloud_spline_continuous(self, cloud, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6, look_ahead=CLOUD_LOOK_AHEAD,
+                                shapes=None, out=None):
+        """``spline_continuous``'s trajectories certified against ``cloud`` ALONE (a ``PointCloud``;
+        nbk_spline_cloud_continuous_batch): one (trajectory, robot shape) item per lane advances by conservative advancement on the
+        shape's clearance from the cloud -> valid (S,) bool, t_free (S,), status (S,) int32 (``_lib.CA_*``).  ``shapes``: as
+        ``cloud_validity``; ``look_ahead``: as ``cloud_edge_continuous``.  ``out``: the CUDA tensors (valid (S,) uint8 / bool, t_free
+        (S,) float64, status (S,) int32) that ``spline_continuous`` returned for the same trajectories: the cloud's items are reduced
+        INTO them -- the result is that of one certified call over the scene's pairs and the cloud together; they are returned."""
+        torch = _require_gpu()
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        bits = self._shape_bits(shapes)
+        if out is None:
+            valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
+            t_free = torch.empty((S,), dtype=torch.float64, device=c.device)
+            status = torch.empty((S,), dtype=torch.int32, device=c.device)
+        else:
+            valid, t_free, status = self._out_tensors(torch, out, S, "(valid, t_free, status)")
+        _lib.check(self._lib.nbk_spline_cloud_continuous_batch(
+            self._h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
+            float(look_ahead), None if bits is None else bits.ctypes.data, 0 if out is None else 1, valid.data_ptr(),
+            t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_cloud_continuous_batch")
+        if out is not None:
+            return valid, t_free, status
         return c.out(valid.bool()), c.out(t_free), c.out(status)
 
 

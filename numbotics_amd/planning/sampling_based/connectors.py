@@ -6,8 +6,10 @@ whole edge -- every sample ``T = arange(0, T_f, res/d) U {T_f}`` -- is checked b
 and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per wavefront).
 ``validate_trajectories`` / ``validate_trajectory`` check smoothed (clamped B-spline) trajectories sample by sample on the device.
 ``ConnectorParams(cloud=...)`` (a ``PointCloud``, with an ``arm``) adds a scan to what the sampled edges and ``is_valid`` respect:
-the device path ANDs ``nbk_edge_cloud_validity_batch`` into the scene's verdict.  Smoothed trajectories do not see point clouds yet:
-with a cloud set they refuse instead of ignoring it.  ``ContinuousConnector`` takes its cloud as a constructor argument
+the device path ANDs ``nbk_edge_cloud_validity_batch`` into the scene's verdict.  Smoothed trajectories see a scan through a per-call
+keyword, ``validate_trajectories(..., cloud=scan)`` on both connectors (``nbk_spline_cloud_validity_batch`` /
+``nbk_spline_cloud_continuous_batch`` accumulating into the scene's result); a call that names no cloud while the params or the
+connector carry one still refuses ("do not see point clouds yet") instead of ignoring it.  ``ContinuousConnector`` takes its cloud as a constructor argument
 (``ContinuousConnector(params, cloud=...)``: certified straight edges, ``nbk_edge_cloud_continuous_batch``) and still refuses params
 that carry one.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
@@ -172,25 +174,42 @@ class DiscreteConnector(Connector):
         return ok, end
 
     # ---- smoothed trajectories (additive) ----------------------------------------------------------------
-    def _spline_check(self, ctrl, knots, degree):
+    def _spline_check(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None):
         p = self._params
-        _, dev = p.arm._scene_device()
-        return dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
+        sm, dev = p.arm._scene_device()
+        if cloud is None:
+            return dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
+        # the scene's verdict, then the cloud's reduced into it on the device: only samples before the scene's first hit are looked at
+        import torch
+        host = not torch.is_tensor(ctrl)
+        if host:
+            ctrl = torch.from_numpy(np.ascontiguousarray(ctrl, dtype=np.float64)).cuda()
+        links = p.cloud_ignore_links if cloud_ignore_links is None else tuple(cloud_ignore_links)
+        out = dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
+        dev.cloud_spline_validity(cloud, ctrl, knots, degree, p.resolution, threshold=p.collision_threshold,
+                                  shapes=p.arm._cloud_shapes(sm, links), out=out)
+        return tuple(x.cpu().numpy() for x in out) if host else out
 
-    def validate_trajectories(self, control_points, degree=1):
+    def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None):
         """S clamped B-splines of ``unit_bspline``'s knots, every one sampled at most ``resolution`` apart in joint space and checked
         on the device (``nbk_spline_validity_batch``): (S, n, dof) -> valid (S,) bool, t_hit (S,) (t of the first colliding
-        sample, NaN when valid), n_samples (S,) int32.  NumPy in, NumPy out; device tensors stay on the device."""
-        _no_cloud(self._params, "sampled trajectory checks")
+        sample, NaN when valid), n_samples (S,) int32.  NumPy in, NumPy out; device tensors stay on the device.
+        ``cloud`` (a ``PointCloud``): the samples are checked against the scan as well (``nbk_spline_cloud_validity_batch``
+        accumulating into the scene's result: t_hit is the first sample either of them rejects), without the shapes of
+        ``cloud_ignore_links`` (default: the params' own tuple).  A call that names no cloud is refused when the params carry one."""
+        if cloud is None:
+            _no_cloud(self._params, "sampled trajectory checks")
         shape = _shape(control_points)
         k = _spline_args(self._params, shape, degree)
-        return self._spline_check(control_points, unit_knots(shape[1], k), k)
+        return self._spline_check(control_points, unit_knots(shape[1], k), k, cloud, cloud_ignore_links)
 
-    def validate_trajectory(self, spline):
-        """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit)."""
-        _no_cloud(self._params, "sampled trajectory checks")
+    def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None):
+        """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit).  ``cloud``,
+        ``cloud_ignore_links``: as ``validate_trajectories``."""
+        if cloud is None:
+            _no_cloud(self._params, "sampled trajectory checks")
         c, t, k = _spline_parts(self._params, spline)
-        valid, t_hit, _ = self._spline_check(c[None], t, k)
+        valid, t_hit, _ = self._spline_check(c[None], t, k, cloud, cloud_ignore_links)
         return bool(valid[0]), float(t_hit[0])
 
 
@@ -249,8 +268,9 @@ class ContinuousConnector(Connector):
     asks both.  ``look_ahead`` bounds how far one step searches the cloud (it changes the number of steps, never whether an edge
     called free is free).  It needs ``params.arm``, the default trajectory and no ``validity_checker``.  The cloud is an argument of
     THIS constructor because ``ConnectorParams(cloud=...)`` keeps being refused here -- a certificate that ignores an obstacle would
-    be worse than none, and callers rely on that refusal; lifting it is a later change.  With a cloud the trajectory methods raise:
-    certified splines do not see point clouds yet."""
+    be worse than none, and callers rely on that refusal; lifting it is a later change.  The trajectory methods take their scan per
+    call, ``validate_trajectories(..., cloud=scan)`` (``nbk_spline_cloud_continuous_batch``, with this connector's ``look_ahead``
+    and, by default, its ``cloud_ignore_links``); a call that names no cloud still raises when the connector carries one."""
 
     def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6, cloud=None, cloud_ignore_links=(),
                  look_ahead: float = CLOUD_LOOK_AHEAD):
@@ -365,24 +385,43 @@ class ContinuousConnector(Connector):
         if self.cloud is not None:
             raise ValueError("certified trajectory checks do not see point clouds yet")
 
-    def _spline_certify(self, ctrl, knots, degree):
+    def _spline_certify(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None):
         p = self._params
-        _, dev = p.arm._scene_device()
-        return dev.spline_continuous(ctrl, knots, degree, threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
+        sm, dev = p.arm._scene_device()
+        kw = dict(threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
+        if cloud is None:
+            return dev.spline_continuous(ctrl, knots, degree, **kw)
+        # the scene's result, then the cloud's items reduced into it on the device, as certify_batch does for edges
+        import torch
+        host = not torch.is_tensor(ctrl)
+        if host:
+            ctrl = torch.from_numpy(np.ascontiguousarray(ctrl, dtype=np.float64)).cuda()
+        links = self.cloud_ignore_links if cloud_ignore_links is None else tuple(cloud_ignore_links)
+        out = dev.spline_continuous(ctrl, knots, degree, **kw)
+        dev.cloud_spline_continuous(cloud, ctrl, knots, degree, look_ahead=self.look_ahead, shapes=p.arm._cloud_shapes(sm, links),
+                                    out=out, **kw)
+        return tuple(x.cpu().numpy() for x in out) if host else out
 
-    def validate_trajectories(self, control_points, degree=1):
+    def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None):
         """S clamped B-splines of ``unit_bspline``'s knots, each certified on the device by conservative advancement across its knot
         spans (``nbk_spline_continuous_batch``): (S, n, dof) -> valid (S,) bool, t_free (S,) (how far along [0, 1] the trajectory
         is certified free; NaN when degenerate), status (S,) int32 (``numbotics_amd._lib.CA_*``).  A trajectory called valid has
-        no configuration closer than ``collision_threshold``.  NumPy in, NumPy out; device tensors stay on the device."""
-        self._no_cloud_splines()
+        no configuration closer than ``collision_threshold``.  NumPy in, NumPy out; device tensors stay on the device.
+        ``cloud`` (a ``PointCloud``): the trajectories are certified against the scan as well
+        (``nbk_spline_cloud_continuous_batch`` accumulating into the scene's result, with this connector's ``look_ahead``), without
+        the shapes of ``cloud_ignore_links`` (default: the connector's own tuple).  A call that names no cloud is refused when the
+        connector carries one."""
+        if cloud is None:
+            self._no_cloud_splines()
         shape = _shape(control_points)
         k = _spline_args(self._params, shape, degree)
-        return self._spline_certify(control_points, unit_knots(shape[1], k), k)
+        return self._spline_certify(control_points, unit_knots(shape[1], k), k, cloud, cloud_ignore_links)
 
-    def validate_trajectory(self, spline):
-        """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_free)."""
-        self._no_cloud_splines()
+    def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None):
+        """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_free).  ``cloud``,
+        ``cloud_ignore_links``: as ``validate_trajectories``."""
+        if cloud is None:
+            self._no_cloud_splines()
         c, t, k = _spline_parts(self._params, spline)
-        valid, t_free, _ = self._spline_certify(c[None], t, k)
+        valid, t_free, _ = self._spline_certify(c[None], t, k, cloud, cloud_ignore_links)
         return bool(valid[0]), float(t_free[0])

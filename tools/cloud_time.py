@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -26,6 +26,12 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
                 inf: the time of the cloud call alone and of the connector's sequence (edge_continuous, then the cloud's items reduced
                 into its result), with the FREE / COLLISION / UNDECIDED counts of both.  The default look_ahead is the fastest value
                 whose UNDECIDED count is no higher than at inf
+    splines     (only when asked for) S = 1e3 B-spline trajectories of 8 control points, degree 3 (a random walk of legs 0.05 to 0.25
+                long from the first configurations) against the scans of N = 1e3 and 1e5 points: DeviceModel.cloud_spline_validity at
+                resolution 0.01 (radius 0.01) per sample, and DeviceModel.cloud_spline_continuous (radius 0.005, max_iter 64, slack
+                1e-6) per (trajectory, shape) item at each look_ahead of the certified table; next to each, windows alternating, the
+                straight-edge entry on E = 1e3 of the edges above against the same cloud: cloud_edge_validity per sample,
+                cloud_edge_continuous per (edge, shape) item
 """
 import argparse
 import os
@@ -193,6 +199,41 @@ def certified_part(dev, chain, shapes, reps):
         say(f"                    scene + cloud {fmt(timed(both, reps))}   {counts(sb)}")
 
 
+def splines_part(dev, chain, shapes, reps):
+    from numbotics_amd.planning import unit_knots
+    S, n, k, res = 10 ** 3, 8, 3, 0.01
+    q = sample_q(chain, S, seed=1)
+    rng = np.random.default_rng(11)
+    legs = rng.standard_normal((S, n - 1, q.shape[1]))
+    legs *= rng.uniform(0.05, 0.25, (S, n - 1, 1)) / np.linalg.norm(legs, axis=2, keepdims=True)
+    ct = torch.from_numpy(np.concatenate((q[:, None], q[:, None] + np.cumsum(legs, axis=1)), axis=1)).cuda()
+    kn = torch.from_numpy(unit_knots(n, k)).cuda()
+    s, g = edges(q, S, 7, 1.0)
+    st, gt = torch.from_numpy(s).cuda(), torch.from_numpy(g).cuda()
+    d = torch.linalg.norm(gt - st, dim=1)
+    K = len(shapes)
+    say(f"splines: S = {S} trajectories of {n} control points, degree {k}; edges: E = {S}, lengths U(0.02, 1.0), connect; {K} shapes")
+    for N in (10 ** 3, 10 ** 5):
+        cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), RADIUS, bounds=BOX)
+        spl = lambda: dev.cloud_spline_validity(cloud, ct, kn, k, res, shapes=shapes)                     # noqa: E731
+        edg = lambda: dev.cloud_edge_validity(cloud, st, gt, res, 1.0, dist=d, shapes=shapes)              # noqa: E731
+        (v, _, ns), (ve, _, nse) = spl(), edg()
+        ts, te = timed_pair(spl, edg, reps)
+        say(f"  sampled   N = {N:6d} resolution {res}: splines {int(ns.sum())} samples, valid {float(v.float().mean()):.3f}  {fmt(ts)}  "
+            f"{ts[0] * 1e6 / int(ns.sum()):.2f} ns/sample   edges {int(nse.sum())} samples, valid {float(ve.float().mean()):.3f}  {fmt(te)}  "
+            f"{te[0] * 1e6 / int(nse.sum()):.2f} ns/sample")
+    counts = lambda status: " ".join(f"{name} {int((status == j).sum()):4d}" for j, name in enumerate(("FREE", "COLLISION", "UNDECIDED")))   # noqa: E731
+    for N in (10 ** 3, 10 ** 5):
+        cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), 0.005, bounds=BOX)
+        for la in (0.02, 0.05, 0.1, 0.2, float("inf")):
+            spl = lambda: dev.cloud_spline_continuous(cloud, ct, kn, k, look_ahead=la, shapes=shapes)      # noqa: E731
+            edg = lambda: dev.cloud_edge_continuous(cloud, st, gt, 1.0, look_ahead=la, dist=d, shapes=shapes)   # noqa: E731
+            ss, se = spl()[2], edg()[3]
+            ts, te = timed_pair(spl, edg, reps)
+            say(f"  certified N = {N:6d} radius 0.005 look_ahead {la:5.2f}: splines {fmt(ts)}  {ts[0] * 1e3 / (S * K):.2f} us/item  {counts(ss)}   "
+                f"edges {fmt(te)}  {te[0] * 1e3 / (S * K):.2f} us/item  {counts(se)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -260,6 +301,8 @@ def main():
         edges_part(dev, sm, chain, shapes, a.reps)
     if "certified" in only:
         certified_part(dev, chain, shapes, a.reps)
+    if "splines" in only:
+        splines_part(dev, chain, shapes, a.reps)
 
 
 if __name__ == "__main__":
