@@ -20,6 +20,9 @@
 // Compile-time switches, reachable through NBK_JIT_OPTIONS (diagnostics; the product path defines none):
 //   NBK_SPEC_NO_ALIGNED, NBK_SPEC_NO_QREG   one of the two trims below off (same masks): the axis-aligned box slot, the q rows
 //       loaded straight into registers
+//   NBK_SPEC_NO_FOLD   the chain sweep without the folded tables (same masks): the unfolded sweep alone
+//   NBK_SPEC_FOLD_PARTS=<bits>   the folded sweep with only one of its parts (same masks; for measuring them apart): 1 the
+//       axis-aligned joints, 2 the shape centres
 //   NBK_SPEC_DIAG_NO_WORLD, NBK_SPEC_DIAG_NO_RR, NBK_SPEC_DIAG_NO_ENQUEUE   the fast stage without its world blocks / its robot-robot
 //       rows / its queue appends: WRONG masks, for attributing instructions and time only (tools/spec_variant.sh)
 #ifdef NBK_SPEC_NO_ALIGNED
@@ -31,6 +34,14 @@
 #define NBK_SPEC_QREG 0
 #else
 #define NBK_SPEC_QREG 1
+#endif
+#ifdef NBK_SPEC_NO_FOLD
+#define NBK_SPEC_FOLD 0
+#else
+#define NBK_SPEC_FOLD 1
+#endif
+#ifndef NBK_SPEC_FOLD_PARTS
+#define NBK_SPEC_FOLD_PARTS 3
 #endif
 #ifdef NBK_SPEC_DIAG_NO_WORLD
 #define NBK_SPEC_WORLD 0
@@ -71,6 +82,82 @@ template <class Spec> struct SpecRoute {
     NBK_SPEC_DEV int groups(int c) const { return Spec::cls_groups[c]; }
 };
 
+// ---- folded tables ------------------------------------------------------------------------------------------------------------------
+// The generated Spec classes every float32 table value of the robot that the sweep multiplies by (fc_pk, fc_tl; the
+// classes: nbk_tables.hpp, fold_class).  In the folded sweep a term whose constant is FC_ZERO is not issued, a term whose constant
+// is +-1 is an add, a subtract or a negation, and everything else is the unfolded sweep's fma chain in its order.  For finite
+// operands an exact zero or +-1 folds to the unfolded value bit for bit up to the sign of a zero (fma(a, 0, x) = x,
+// fma(a, 1, x) = a + x); a residue classed zero moves a centre by less than the slack charges.
+//
+// A wave takes the folded sweep only when every lane's sum of |q_k| (float32) is below FOLD_QMAX; any other wave (a NaN fails the
+// compare) runs the unfolded sweep, whose fma(inf, 0, .) terms make the NaN the generic kernel has.  Below the bound nothing of
+// the sweep overflows, so neither arm sees an inf or a NaN and the folds are exact.  The argument, with the ranges the generator
+// checks before it classes anything (rotation-type table entries at most 2, lengths and slides at most 2^20): |sin|, |cos| <= 1,
+// so an entry of L = M0 + s M2 - c M1 is at most 6 and a frame entry grows by at most 3 * 6 = 18 per joint, to 2 * 18^8 < 2^35
+// after eight; a joint's own translation is at most 2^20 + 2^20 * 2^20 < 2^41 and a shape offset at most 2^20; a frame
+// translation is at most 2^20 + 8 * 3 * 2^35 * 2^41 < 2^81 and a centre at most that + 3 * 2^35 * 2^20 -- every product and
+// partial sum far below 2^127.
+constexpr float FOLD_QMAX = 0x1p20f;
+enum { FC_GEN = 0, FC_ZERO = 1, FC_ONE = 2, FC_NEG = 3 };
+
+NBK_SPEC_DEV V2f fold_mul(V2f a, float k) { return a * splat2(k); }
+NBK_SPEC_DEV V2f fold_mul(V2f a, V2f k) { return a * k; }
+NBK_SPEC_DEV float fold_mul(float a, float k) { return a * k; }
+NBK_SPEC_DEV V2f fold_fma(V2f a, float k, V2f acc) { return fma2(a, splat2(k), acc); }
+NBK_SPEC_DEV V2f fold_fma(V2f a, V2f k, V2f acc) { return fma2(a, k, acc); }
+NBK_SPEC_DEV float fold_fma(float a, float k, float acc) { return __builtin_fmaf(a, k, acc); }
+
+// acc + a * k for a k of class CL; EMPTY: the chain has issued no term yet and acc holds nothing
+template <int CL, bool EMPTY, class T, class K> NBK_SPEC_DEV T fold_term(T a, K k, T acc) {
+    if constexpr (CL == FC_ZERO) return acc;
+    else if constexpr (CL == FC_ONE) { if constexpr (EMPTY) return a; else return a + acc; }
+    else if constexpr (CL == FC_NEG) { if constexpr (EMPTY) return -a; else return acc - a; }
+    else { if constexpr (EMPTY) return fold_mul(a, k); else return fold_fma(a, k, acc); }
+}
+// the sweep's three-term chains: fma(a2, k2, fma(a1, k1, fma(a0, k0, init))) with HAS, fma(a2, k2, fma(a1, k1, a0 * k0)) without (init = 0)
+template <int C0, int C1, int C2, bool HAS, class T, class K> NBK_SPEC_DEV T fold_dot3(T a0, T a1, T a2, K k0, K k1, K k2, T init) {
+    constexpr bool e0 = !HAS, e1 = e0 && C0 == FC_ZERO, e2 = e1 && C1 == FC_ZERO;
+    return fold_term<C2, e2>(a2, k2, fold_term<C1, e1>(a1, k1, fold_term<C0, e0>(a0, k0, init)));
+}
+// one entry of L = s M2 - c M1 (columns U and V hold no M0) from the classes of its M2 and M1 entries
+template <int C2, int C1> NBK_SPEC_DEV float fold_l(float s, float c, float m2, float m1) {
+    if constexpr (C2 == FC_ZERO && C1 == FC_ZERO) return 0.0f;
+    else if constexpr (C2 == FC_ZERO) return -fold_term<C1, true>(c, m1, 0.0f);
+    else if constexpr (C1 == FC_ZERO) return fold_term<C2, true>(s, m2, 0.0f);
+    else return __builtin_fmaf(s, m2, -(c * m1));
+}
+// C::at(i): the class of float i of a joint's packed block, in the order m2p[6], m1p[6], mk[3], toff[3]
+template <class C> struct FoldL {
+    float x[3], y[3];                       // L[r][U], L[r][V]
+    static constexpr int z(int i) { return C::at(i) == FC_ZERO && C::at(6 + i) == FC_ZERO ? FC_ZERO : FC_GEN; }       // i = 2 r + (0: U, 1: V)
+    static constexpr int pz(int r) { return z(2 * r) == FC_ZERO && z(2 * r + 1) == FC_ZERO ? FC_ZERO : FC_GEN; }     // the pair of row r
+    NBK_SPEC_DEV FoldL(const JPk& jp, float s, float c) {
+        x[0] = fold_l<C::at(0), C::at(6)>(s, c, jp.m2p[0], jp.m1p[0]);  y[0] = fold_l<C::at(1), C::at(7)>(s, c, jp.m2p[1], jp.m1p[1]);
+        x[1] = fold_l<C::at(2), C::at(8)>(s, c, jp.m2p[2], jp.m1p[2]);  y[1] = fold_l<C::at(3), C::at(9)>(s, c, jp.m2p[3], jp.m1p[3]);
+        x[2] = fold_l<C::at(4), C::at(10)>(s, c, jp.m2p[4], jp.m1p[4]); y[2] = fold_l<C::at(5), C::at(11)>(s, c, jp.m2p[5], jp.m1p[5]);
+    }
+};
+// joint_apply_axis_p with the joint's classes: the same chains in the same order, less the folded terms
+template <int KZ, class C>
+NBK_SPEC_DEV void joint_apply_axis_fold(const JPk& jp, const XfP& P, float s, float c, XfP& o) {
+    constexpr int U = (KZ + 1) % 3, V = (KZ + 2) % 3;
+    using Z = FoldL<C>;
+    const Z L(jp, s, c);
+    const V2f z2 = V2f{0.0f, 0.0f};
+    const V2f cu = fold_dot3<Z::z(0), Z::z(2), Z::z(4), false>(P.Rc[0], P.Rc[1], P.Rc[2], L.x[0], L.x[1], L.x[2], z2);
+    const V2f cv = fold_dot3<Z::z(1), Z::z(3), Z::z(5), false>(P.Rc[0], P.Rc[1], P.Rc[2], L.y[0], L.y[1], L.y[2], z2);
+    const V2f ck = fold_dot3<C::at(12), C::at(13), C::at(14), false>(P.Rc[0], P.Rc[1], P.Rc[2], jp.mk[0], jp.mk[1], jp.mk[2], z2);
+    const V2f r2 = fold_dot3<Z::pz(0), Z::pz(1), Z::pz(2), false>(splat2(P.R2[0]), splat2(P.R2[1]), splat2(P.R2[2]), V2f{L.x[0], L.y[0]},
+                                                                  V2f{L.x[1], L.y[1]}, V2f{L.x[2], L.y[2]}, z2);
+    const float r2k = fold_dot3<C::at(12), C::at(13), C::at(14), false>(P.R2[0], P.R2[1], P.R2[2], jp.mk[0], jp.mk[1], jp.mk[2], 0.0f);
+    const V2f tc = fold_dot3<C::at(15), C::at(16), C::at(17), true>(P.Rc[0], P.Rc[1], P.Rc[2], jp.toff[0], jp.toff[1], jp.toff[2], P.tc);
+    const float t2 = fold_dot3<C::at(15), C::at(16), C::at(17), true>(P.R2[0], P.R2[1], P.R2[2], jp.toff[0], jp.toff[1], jp.toff[2], P.t2);
+    o.Rc[U] = cu; o.Rc[V] = cv; o.Rc[KZ] = ck;
+    o.R2[U] = r2.x; o.R2[V] = r2.y; o.R2[KZ] = r2k;
+    o.tc = tc; o.t2 = t2;
+}
+template <class Spec, int K> struct PkClass { static constexpr int at(int i) { return Spec::fc_pk[18 * K + i]; } };
+
 // Spec (generated) provides:
 //   S (robot shapes), SB (even register bucket >= S), NQ, J (<= 8), W (world shapes of the descriptor), NW (world shapes with a pair)
 //   jkind[J], qcol[J]; sh_begin[J + 2] (shapes of frame k - 1 are [sh_begin[k], sh_begin[k + 1]))
@@ -79,6 +166,7 @@ template <class Spec> struct SpecRoute {
 //   rr_any; rpair(a, b) (a < b), rr_p(a, b): pair index of robot-robot slot (a, b), -1 = none
 //   wl[NW], wk[NW]: world shape and kind; wpair(i, a): pair index of (wl[i], a), -1 = none
 //   wbox_aligned[NW]: 1 = a box of a descriptor that cannot move whose axes at f_wc are exactly the coordinate axes
+//   fc_any, fc_pk[18 J], fc_tl[3 S]: the classes of the robot's table values for the folded sweep (fc_any = 0: none)
 //   cls_base[4], cls_groups[4]
 template <class Spec>
 NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, const float* __restrict__ ftb, const float* __restrict__ tab,
@@ -124,38 +212,58 @@ NBK_SPEC_DEV void broad_f32_spec(const double* __restrict__ q, long long B, cons
     float qv[J];
 #pragma unroll
     for (int k = 0; k < J; ++k) { qv[k] = (float)qat(Spec::qcol[k]); qabs += __builtin_fabsf(qv[k]); }
-    XfP T;
-    {
-        const float* bp = ftb + Spec::f_base;
+    // FOLD = 1: the sweep with the robot's folded tables (above); FOLD = 0: the unfolded one, the generic kernel's operation for operation
+    auto sweep = [&](auto FOLD) NBK_SPEC_INLINE {
+        constexpr bool fold = decltype(FOLD)::value != 0;
+        constexpr bool fold_joints = fold && (NBK_SPEC_FOLD_PARTS & 1) != 0, fold_shapes = fold && (NBK_SPEC_FOLD_PARTS & 2) != 0;
+        XfP T;
+        {
+            const float* bp = ftb + Spec::f_base;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { T.Rc[k] = V2f{bp[k], bp[4 + k]}; T.R2[k] = bp[8 + k]; }
-        T.tc = V2f{bp[3], bp[7]}; T.t2 = bp[11];
-    }
-    auto shapes = [&](auto K) NBK_SPEC_INLINE {                 // the shapes of frame K - 1 from the current frame T
-        constexpr int k = decltype(K)::value;
-        sfor<Spec::sh_begin[k], Spec::sh_begin[k + 1]>([&](auto SH) NBK_SPEC_INLINE {
-            constexpr int sh = decltype(SH)::value;
-            const float tl0 = ftb[Spec::f_tl + 3 * sh], tl1 = ftb[Spec::f_tl + 3 * sh + 1], tl2 = ftb[Spec::f_tl + 3 * sh + 2];
-            const V2f cp = fma2(T.Rc[2], splat2(tl2), fma2(T.Rc[1], splat2(tl1), fma2(T.Rc[0], splat2(tl0), T.tc)));
-            const float c2 = __builtin_fmaf(T.R2[2], tl2, __builtin_fmaf(T.R2[1], tl1, __builtin_fmaf(T.R2[0], tl0, T.t2)));
-            cxa[sh] = cp.x; cya[sh] = cp.y; cza[sh] = c2;
-            rmax = __builtin_fmaxf(rmax, __builtin_fmaxf(__builtin_fabsf(cp.x), __builtin_fmaxf(__builtin_fabsf(cp.y), __builtin_fabsf(c2))));
+            for (int k = 0; k < 3; ++k) { T.Rc[k] = V2f{bp[k], bp[4 + k]}; T.R2[k] = bp[8 + k]; }
+            T.tc = V2f{bp[3], bp[7]}; T.t2 = bp[11];
+        }
+        auto shapes = [&](auto K) NBK_SPEC_INLINE {                 // the shapes of frame K - 1 from the current frame T
+            constexpr int k = decltype(K)::value;
+            sfor<Spec::sh_begin[k], Spec::sh_begin[k + 1]>([&](auto SH) NBK_SPEC_INLINE {
+                constexpr int sh = decltype(SH)::value;
+                const float tl0 = ftb[Spec::f_tl + 3 * sh], tl1 = ftb[Spec::f_tl + 3 * sh + 1], tl2 = ftb[Spec::f_tl + 3 * sh + 2];
+                V2f cp;
+                float c2;
+                if constexpr (fold_shapes) {
+                    constexpr int c0 = Spec::fc_tl[3 * sh], c1 = Spec::fc_tl[3 * sh + 1], c2c = Spec::fc_tl[3 * sh + 2];
+                    cp = fold_dot3<c0, c1, c2c, true>(T.Rc[0], T.Rc[1], T.Rc[2], tl0, tl1, tl2, T.tc);
+                    c2 = fold_dot3<c0, c1, c2c, true>(T.R2[0], T.R2[1], T.R2[2], tl0, tl1, tl2, T.t2);
+                } else {
+                    cp = fma2(T.Rc[2], splat2(tl2), fma2(T.Rc[1], splat2(tl1), fma2(T.Rc[0], splat2(tl0), T.tc)));
+                    c2 = __builtin_fmaf(T.R2[2], tl2, __builtin_fmaf(T.R2[1], tl1, __builtin_fmaf(T.R2[0], tl0, T.t2)));
+                }
+                cxa[sh] = cp.x; cya[sh] = cp.y; cza[sh] = c2;
+                rmax = __builtin_fmaxf(rmax, __builtin_fmaxf(__builtin_fabsf(cp.x), __builtin_fmaxf(__builtin_fabsf(cp.y), __builtin_fabsf(c2))));
+            });
+        };
+        shapes(IC<0>{});
+        sfor<0, J>([&](auto K) NBK_SPEC_INLINE {
+            constexpr int k = decltype(K)::value;
+            constexpr int kind = Spec::jkind[k];
+            float s = 0.0f, c = 0.0f;
+            if constexpr (kind != JK_PRISMATIC) sincos_f(qv[k], s, c);
+            if constexpr (kind <= 2) {
+                const JPk jp = *reinterpret_cast<const JPk*>(ftb + Spec::f_pk + 20 * k);
+                if constexpr (fold_joints) joint_apply_axis_fold<kind, PkClass<Spec, k>>(jp, T, s, c, T);
+                else joint_apply_axis_p<kind>(jp, T, s, c, T);
+            } else {
+                joint_apply_gen_p(ftb + Spec::f_rot + 27 * k, ftb + Spec::f_trans + 3 * k, ftb + Spec::f_slide + 3 * k, T, qv[k], s, c, T);
+            }
+            shapes(IC<k + 1>{});
         });
     };
-    shapes(IC<0>{});
-    sfor<0, J>([&](auto K) NBK_SPEC_INLINE {
-        constexpr int k = decltype(K)::value;
-        constexpr int kind = Spec::jkind[k];
-        float s = 0.0f, c = 0.0f;
-        if constexpr (kind != JK_PRISMATIC) sincos_f(qv[k], s, c);
-        if constexpr (kind <= 2) {
-            const JPk jp = *reinterpret_cast<const JPk*>(ftb + Spec::f_pk + 20 * k);
-            joint_apply_axis_p<kind>(jp, T, s, c, T);
-        } else {
-            joint_apply_gen_p(ftb + Spec::f_rot + 27 * k, ftb + Spec::f_trans + 3 * k, ftb + Spec::f_slide + 3 * k, T, qv[k], s, c, T);
-        }
-        shapes(IC<k + 1>{});
-    });
+    if constexpr (NBK_SPEC_FOLD != 0 && (NBK_SPEC_FOLD_PARTS & 3) != 0 && Spec::fc_any != 0) {
+        if (__builtin_amdgcn_ballot_w64(!(qabs < FOLD_QMAX)) == 0ull) sweep(IC<1>{});
+        else sweep(IC<0>{});
+    } else {
+        sweep(IC<0>{});
+    }
     const float e2 = 2.0f * rmax * __builtin_fmaf(2.4e-7f, qabs, Spec::f_eps);
     if constexpr (!QREG) __syncthreads();            // the q slab is dead from here on: its LDS region becomes the item queue
     int qn = 0;

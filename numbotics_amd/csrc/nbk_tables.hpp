@@ -565,6 +565,15 @@ static void float_tables(const nbk_model_desc* d, const double* world_radius, Mo
 // appends (8 cubes made 140 KB of code for a 64 KB instruction cache and an 11 s compile); other scenes keep the generic kernel
 constexpr int SPEC_MAX_WORLD = 2;
 
+// Class of a float32 table value for the folded sweep of the specialised kernel (Spec::fc_*): 0 general, 1 zero, 2 exactly +1,
+// 3 exactly -1.  Zero covers the residues that multiples of pi / 2 leave in a URDF's origins (cos(pi / 2) = 6.1e-17): a rotation
+// entry up to 2^-40, a length up to 2^-40 of the static reach (`zero_below`).  DESIGN.md §3 charges them to the slack.
+constexpr float FOLD_ZERO_REL = 0x1p-40f;
+static int fold_class(float v, float zero_below) {
+    if (std::fabs(v) <= zero_below) return 1;
+    return v == 1.0f ? 2 : (v == -1.0f ? 3 : 0);
+}
+
 // The `struct Spec` of one descriptor ("" when the robot does not take the specialised kernel: not a serial chain of at most
 // 8 joints, more than 16 shapes, no pairs, too many world shapes).  movable: the world cores at f_wc may be rewritten later
 // (k_world_update), so nothing about a world shape's pose is built in
@@ -628,6 +637,29 @@ static std::string bf32_spec_text(const nbk_model_desc* d, const ModelTables& t,
         aligned.push_back(id ? 1 : 0);
     }
     arr("wbox_aligned", aligned);
+    // Classes of the robot's own float32 table values, which no call ever rewrites (a movable descriptor's neither), for the folded
+    // sweep of the kernel: per joint the 18 used floats of its block at f_pk (m2p, m1p, mk, toff), per shape its offset at f_tl.  (The
+    // base pose is not classed: folding an identity base was measured and did not pay)  The tables keep their
+    // values: the generic kernel and k_prepare_f32 read the same floats.
+    // fc_any = 0 (and every class general) when a table value is outside the range FOLD_QMAX's argument in nbk_bf32_spec.hpp
+    // assumes -- a rotation-type entry above 2, a length above 2^20 -- or when no value the folded sweep reads has a class.
+    bool fold_ok = t.f_reach <= 0x1p20f;
+    for (int e = 0; e < 27 * J; ++e) fold_ok = fold_ok && std::fabs(t.ftab[e]) <= 2.0f;
+    for (int e = 0; e < 3 * J; ++e) fold_ok = fold_ok && std::fabs(t.ftab[t.f_trans + e]) <= 0x1p20f && std::fabs(t.ftab[t.f_slide + e]) <= 0x1p20f;
+    for (int e = 0; e < 12; ++e) fold_ok = fold_ok && std::fabs(t.ftab[t.f_base + e]) <= (e % 4 == 3 ? 0x1p20f : 2.0f);
+    for (int e = 0; e < 3 * S; ++e) fold_ok = fold_ok && std::fabs(t.ftab[t.f_tl + e]) <= 0x1p20f;
+    const float zr = FOLD_ZERO_REL, zt = FOLD_ZERO_REL * t.f_reach;
+    std::vector<int> fc_pk, fc_tl;
+    bool fold_any = false;
+    for (int k = 0; k < J; ++k)
+        for (int e = 0; e < 18; ++e) {
+            fc_pk.push_back(fold_ok ? (e < 15 ? fold_class(t.ftab[t.f_pk + 20 * (size_t)k + e], zr) : fold_class(t.ftab[t.f_pk + 20 * (size_t)k + e + 1], zt)) : 0);
+            fold_any = fold_any || (t.joint_kind[k] <= 2 && fc_pk.back() != 0);
+        }
+    for (int e = 0; e < 3 * S; ++e) { fc_tl.push_back(fold_ok ? fold_class(t.ftab[t.f_tl + e], zt) : 0); fold_any = fold_any || fc_tl.back() != 0; }
+    add("    static constexpr int fc_any = %d;\n", fold_any ? 1 : 0);
+    arr("fc_pk", fc_pk);
+    arr("fc_tl", fc_tl);
     arr("cls_base", std::vector<int>(t.cls_base, t.cls_base + 4));
     std::vector<int> groups(t.cls_groups, t.cls_groups + 4);
     for (int& g : groups) g = g > 0 ? g : 1;             // as DevModel::cls_groups: a divisor, also for a class without pairs
