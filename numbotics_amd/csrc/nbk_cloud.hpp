@@ -20,8 +20,8 @@
 // numbered x fastest, so one (y, z) row of the range is one contiguous run of sorted points.
 //
 // Sampled edges (nbk_edge_cloud_validity_batch): the edge rule is nbk.hip's own (k_edge_plan, k_scan, edge_sample_row); the samples of
-// all edges form one flat range that k_cloud_edges walks one sample per lane with the walk of k_cloud_validity (cloud_row_hits).  Plan,
-// counts and offsets live in the caller's workspace (EdgeCloudLayout, nbk_plan.hpp).
+// all edges form one flat range (cloud_flat_owner: whose sample a lane holds) that k_cloud_edges walks one sample per lane with the
+// walk of k_cloud_validity (cloud_row_hits).  Plan, counts and offsets live in the caller's workspace (EdgeCloudLayout, nbk_plan.hpp).
 //
 // Certified edges (nbk_edge_cloud_continuous_batch): nbk.hip's k_edge_ca_init -> k_cloud_edge_ca (ca_walk on CloudEdgeLane) -> nbk.hip's
 // k_ca_final; the keys and their reserved values are defined once, beside ca_key.
@@ -30,6 +30,9 @@
 // (k_spline_plan, k_scan, spline_span, de_boor, k_spline_ca_init, SplineSpanMotion); k_cloud_spline walks one sample per lane on a grid
 // of fixed size with a first-hit word per trajectory in the caller's workspace (SplineCloudLayout, nbk_plan.hpp), k_cloud_spline_ca is
 // ca_walk on CloudSplineLane.
+//
+// Entry points: each states its own argument rules, then cloud_call_begin (selection limit, devices, selection, selected count); the
+// sampled entries check their workspace with cloud_workspace_ok.
 #pragma once
 #define NBK_GRID_FN __host__ __device__ inline
 #include "nbk_cloud_grid.hpp"
@@ -172,6 +175,17 @@ NBK_DEV void cloud_point_core(double r, Core& P) {
     P.margin = r;
 }
 
+// the owner of flat sample f < offs[n]: the largest e in [0, n) with offs[e] <= f (owners without samples fall out by themselves:
+// equal offsets); f is sample f - offs[e] of it
+NBK_DEV int64_t cloud_flat_owner(const unsigned long long* __restrict__ offs, int64_t n, unsigned long long f) {
+    int64_t e = 0, hi = n;                               // offs[e] <= f < offs[hi]
+    while (hi - e > 1) {
+        const int64_t mid = e + ((hi - e) >> 1);
+        if (offs[mid] <= f) e = mid; else hi = mid;
+    }
+    return e;
+}
+
 // ---- validity -----------------------------------------------------------------------------------------------------------------
 // The pair predicate for (point core P, shape core A), canonical order (the point first).  cores_collide_exact as it is, except that a
 // hull core at tc <= 0 skips that routine's device-only cull: hull_box_far compares the point's distance from the hull's local box
@@ -290,11 +304,7 @@ __global__ __launch_bounds__(64) void k_cloud_edges(DevModel m, CloudDev cd, Clo
         int64_t e = 0;
         bool work = false;
         if (f < total) {
-            int64_t hi = E;                                  // offs[e] <= f < offs[hi]
-            while (hi - e > 1) {
-                const int64_t mid = e + ((hi - e) >> 1);
-                if (offs[mid] <= f) e = mid; else hi = mid;
-            }
+            e = cloud_flat_owner(offs, E, f);
             if (__hip_atomic_load(valid + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
                 edge_sample_row(es, ((unsigned long long)e << 32) | (f - offs[e]), m.n_q, myq, 1);
                 work = !row_nonfinite(myq, m.n_q, 1) && status == 0;
@@ -539,11 +549,7 @@ __global__ __launch_bounds__(64) void k_cloud_spline(DevModel m, CloudDev cd, Cl
         unsigned long long j = 0ull;
         bool work = false, hit = false;
         if (f < total) {
-            int64_t hi = S;                                  // offs[s] <= f < offs[hi]
-            while (hi - s > 1) {
-                const int64_t mid = s + ((hi - s) >> 1);
-                if (offs[mid] <= f) s = mid; else hi = mid;
-            }
+            s = cloud_flat_owner(offs, S, f);
             j = f - offs[s];
             const unsigned long long key = __hip_atomic_load(first + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (key <= SPC_NONE && j + 1ull < key) {
@@ -737,6 +743,32 @@ static CloudSel cloud_selection(const nbk_model* m, const uint64_t* shape_bits) 
     return sel;
 }
 
+// the selected shapes of a call, counted
+static int cloud_selected_count(const nbk_model* m, const CloudSel& sel) {
+    if (sel.all) return m->d.n_rshapes;
+    int n_sel = 0;
+    for (int k = 0; k < 4; ++k) n_sel += __builtin_popcountll(sel.w[k]);
+    return n_sel;
+}
+
+// What every query entry answers once its own argument rules are through (they come first: INVALID is answered without a device), in
+// this order: a selection on a model of more than 256 robot shapes is UNSUPPORTED (CloudSel holds 256 bits); the model's device and
+// the cloud's must be the current one; then `sel` is the selection.  n_sel (the certified entries, whose grid has one row of
+// workgroups per selected shape): their count, UNSUPPORTED above the 65535 rows a grid has.  -> the first code that fails
+static int32_t cloud_call_begin(const nbk_model* m, const nbk_cloud* c, const uint64_t* shape_bits, CloudSel& sel, int* n_sel = nullptr) {
+    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    sel = cloud_selection(m, shape_bits);
+    if (n_sel != nullptr && (*n_sel = cloud_selected_count(m, sel)) > 65535) return NBK_ERR_UNSUPPORTED;
+    return NBK_OK;
+}
+
+// the caller's workspace of the sampled entries: at least `need` bytes (a layout's) at a 64-byte boundary
+static bool cloud_workspace_ok(const void* workspace, int64_t workspace_bytes, size_t need) {
+    return workspace_bytes >= (int64_t)need && (reinterpret_cast<uintptr_t>(workspace) & 63) == 0;
+}
+
 }  // namespace nbk
 
 extern "C" {
@@ -825,13 +857,12 @@ int32_t nbk_cloud_status(const nbk_cloud* c, int32_t* status) {
 int32_t nbk_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* q, int64_t B, double threshold,
                                  const uint64_t* shape_bits, int32_t accumulate, uint64_t* mask_bits, uint8_t* mask_bytes, void* stream) {
     if (m == nullptr || c == nullptr || B < 0 || (B > 0 && (q == nullptr || (mask_bits == nullptr && mask_bytes == nullptr)))) return NBK_ERR_INVALID;
-    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
-    NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    CloudSel sel;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_cloud_validity, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
-                       cloud_dev(c), cloud_selection(m, shape_bits), q, B, threshold, (int)accumulate,
+                       cloud_dev(c), sel, q, B, threshold, (int)accumulate,
                        reinterpret_cast<unsigned long long*>(mask_bits), mask_bytes);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
@@ -840,13 +871,12 @@ int32_t nbk_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const d
 int32_t nbk_cloud_clearance_batch(const nbk_model* m, const nbk_cloud* c, const double* q, int64_t B, double d_max,
                                   const uint64_t* shape_bits, double* min_dist, int32_t* shape, int32_t* point, void* stream) {
     if (m == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0) || (B > 0 && (q == nullptr || min_dist == nullptr))) return NBK_ERR_INVALID;
-    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
-    NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    CloudSel sel;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
-                       cloud_dev(c), cloud_selection(m, shape_bits), m->rs_user, q, B, d_max, min_dist, shape, point);
+                       cloud_dev(c), sel, m->rs_user, q, B, d_max, min_dist, shape, point);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -865,12 +895,11 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, co
     if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
     if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
     if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
-        (workspace_bytes < (int64_t)EdgeCloudLayout(E).bytes || (reinterpret_cast<uintptr_t>(workspace) & 63) != 0)) return NBK_ERR_INVALID;
+        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
     if (E == 0) return NBK_OK;
     if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
-    NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    CloudSel sel;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel); if (rc != NBK_OK) return rc; }
     hipStream_t st = (hipStream_t)stream;
     const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
     double* const plan = v.plan;
@@ -886,7 +915,7 @@ int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, co
     // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
     const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
     hipLaunchKernelGGL(k_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
-                       QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c), cloud_selection(m, shape_bits), es, offs, E, threshold,
+                       QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c), sel, es, offs, E, threshold,
                        valid);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
@@ -903,13 +932,9 @@ int32_t nbk_edge_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, 
     if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
     if (E == 0) return NBK_OK;
     if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
-    NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
-    const CloudSel sel = cloud_selection(m, shape_bits);
-    int n_sel = m->d.n_rshapes;
-    if (!sel.all) { n_sel = 0; for (int k = 0; k < 4; ++k) n_sel += __builtin_popcountll(sel.w[k]); }
-    if (n_sel > 65535) return NBK_ERR_UNSUPPORTED;
+    CloudSel sel;
+    int n_sel = 0;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel, &n_sel); if (rc != NBK_OK) return rc; }
     hipStream_t st = (hipStream_t)stream;
     { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, &c->hdr->status, accumulate ? status : nullptr, end, t_free);
       if (rc != NBK_OK) return rc; }
@@ -927,14 +952,6 @@ int64_t nbk_spline_cloud_workspace_bytes(int64_t S) {
     return (int64_t)SplineCloudLayout(S).bytes;
 }
 
-// the selected shapes of a call, counted
-static int cloud_selected_count(const nbk_model* m, const CloudSel& sel) {
-    if (sel.all) return m->d.n_rshapes;
-    int n_sel = 0;
-    for (int k = 0; k < 4; ++k) n_sel += __builtin_popcountll(sel.w[k]);
-    return n_sel;
-}
-
 int32_t nbk_spline_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                         const double* knots, double resolution, double threshold, const uint64_t* shape_bits,
                                         int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples, void* workspace,
@@ -945,12 +962,11 @@ int32_t nbk_spline_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, 
     if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
     if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
     if (S > 0 && S < SPLINE_MAX_S &&
-        (workspace_bytes < (int64_t)SplineCloudLayout(S).bytes || (reinterpret_cast<uintptr_t>(workspace) & 63) != 0)) return NBK_ERR_INVALID;
+        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
     if (S == 0) return NBK_OK;
     if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
-    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
-    NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    CloudSel sel;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel); if (rc != NBK_OK) return rc; }
     int cus = 0;
     NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     hipStream_t st = (hipStream_t)stream;
@@ -963,7 +979,6 @@ int32_t nbk_spline_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, 
     NBK_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
     NBK_HIP(hipGetLastError());
-    const CloudSel sel = cloud_selection(m, shape_bits);
     // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
     const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
     const size_t lds = QSlabLds(m->n_q).bytes();
@@ -990,12 +1005,9 @@ int32_t nbk_spline_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c
     if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
     if (S == 0) return NBK_OK;
     if (S > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
-    NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
-    const CloudSel sel = cloud_selection(m, shape_bits);
-    const int n_sel = cloud_selected_count(m, sel);
-    if (n_sel > 65535) return NBK_ERR_UNSUPPORTED;
+    CloudSel sel;
+    int n_sel = 0;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel, &n_sel); if (rc != NBK_OK) return rc; }
     hipStream_t st = (hipStream_t)stream;
     { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, &c->hdr->status, accumulate ? status : nullptr, t_free);
       if (rc != NBK_OK) return rc; }

@@ -51,6 +51,16 @@ def _host_f64(a, n):
     return a
 
 
+def _host_ptr(a):
+    """The address of an optional host array (None stays None)."""
+    return None if a is None else a.ctypes.data
+
+
+def _mode_int(mode):
+    """``mode`` of the edge entries as the library takes it: 0 connect, 1 steer."""
+    return 0 if mode == "connect" else 1
+
+
 def model_desc(model):
     """The ``nbk_model_desc`` of a KinematicModel or SceneModel (robots/model.py) -> (desc, arrays it points into).  Keep the
     second value alive as long as the first is used.  Needs no GPU."""
@@ -486,7 +496,7 @@ class DeviceModel:
         ok, ns = C.c_int32(0), C.c_int32(0)
         _lib.check(self._lib.nbk_edge_validity_scalar_host(
             self._h, s.ctypes.data, g.ctypes.data, -1.0 if dist is None else float(dist), float(resolution), float(max_distance),
-            0 if mode == "connect" else 1, float(threshold), C.byref(ok), end.ctypes.data, C.byref(ns)),
+            _mode_int(mode), float(threshold), C.byref(ok), end.ctypes.data, C.byref(ns)),
             "nbk_edge_validity_scalar_host")
         return bool(ok.value), end, int(ns.value)
 
@@ -515,6 +525,15 @@ class DeviceModel:
             words[s >> 6] |= np.uint64(1) << np.uint64(s & 63)
         return words
 
+    @staticmethod
+    def _mask_out(torch, out, want, packed=False):
+        """``out`` of the cloud calls that OR / AND into a mask: a contiguous CUDA tensor of shape ``want``, uint8 / bool, or int64
+        words when ``packed`` -> out."""
+        if not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == want
+                and (out.dtype == torch.int64 if packed else out.dtype in (torch.uint8, torch.bool))):
+            raise ValueError(f"out must be a contiguous CUDA tensor of shape {want} ({'int64' if packed else 'uint8 / bool'})")
+        return out
+
     def cloud_validity(self, cloud, q, threshold=0.0, packed=False, shapes=None, out=None):
         """In-collision flags of q against ``cloud`` ALONE (a ``PointCloud``): this descriptor's own pairs and world shapes play no
         part.  Bit for bit the verdict of a descriptor that holds the cloud's points as sphere world shapes paired with the selected
@@ -524,18 +543,14 @@ class DeviceModel:
         torch = _require_gpu()
         qs = _Staged(q, self.n_q)
         bits = self._shape_bits(shapes)
+        want = ((qs.B + 63) // 64,) if packed else (qs.B,)
         if out is not None:
-            want = ((qs.B + 63) // 64,) if packed else (qs.B,)
-            if not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == want
-                    and (out.dtype == torch.int64 if packed else out.dtype in (torch.uint8, torch.bool))):
-                raise ValueError(f"out must be a contiguous CUDA tensor of shape {want} ({'int64' if packed else 'uint8 / bool'})")
-            words, mask = (out, None) if packed else (None, out)
-        elif packed:
-            words, mask = torch.empty(((qs.B + 63) // 64,), dtype=torch.int64, device=qs.device), None
+            res = self._mask_out(torch, out, want, packed)
         else:
-            words, mask = None, torch.empty((qs.B,), dtype=torch.uint8, device=qs.device)
+            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=qs.device)
+        words, mask = (res, None) if packed else (None, res)
         _lib.check(self._lib.nbk_cloud_validity_batch(
-            self._h, cloud._h, qs.t.data_ptr(), qs.B, float(threshold), None if bits is None else bits.ctypes.data,
+            self._h, cloud._h, qs.t.data_ptr(), qs.B, float(threshold), _host_ptr(bits),
             0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
             self._stream()), "nbk_cloud_validity_batch")
         if out is not None:
@@ -553,7 +568,7 @@ class DeviceModel:
         sh = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
         pt = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
         _lib.check(self._lib.nbk_cloud_clearance_batch(
-            self._h, cloud._h, qs.t.data_ptr(), qs.B, float(d_max), None if bits is None else bits.ctypes.data,
+            self._h, cloud._h, qs.t.data_ptr(), qs.B, float(d_max), _host_ptr(bits),
             d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._stream()), "nbk_cloud_clearance_batch")
         return qs.out(d), qs.out(sh), qs.out(pt)
 
@@ -641,7 +656,7 @@ class DeviceModel:
         ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
         _lib.check(self._lib.nbk_edge_validity_batch(
             self._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B,
-            float(resolution), float(max_distance), 0 if mode == "connect" else 1, float(threshold),
+            float(resolution), float(max_distance), _mode_int(mode), float(threshold),
             valid.data_ptr(), end.data_ptr(), ns.data_ptr(), self._stream()), "nbk_edge_validity_batch")
         return s.out(valid.bool()), s.out(end), s.out(ns)
 
@@ -661,19 +676,13 @@ class DeviceModel:
         torch = _require_gpu()
         s, g, dd = self._stage_edges(starts, goals, dist)
         bits = self._shape_bits(shapes)
-        if out is None:
-            valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
-        else:
-            if not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (s.B,)
-                    and out.dtype in (torch.uint8, torch.bool)):
-                raise ValueError(f"out must be a contiguous CUDA tensor of shape {(s.B,)} (uint8 / bool)")
-            valid = out
+        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
         end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
         ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
         ws = torch.empty((self.cloud_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device) if workspace is None else workspace
         _lib.check(self._lib.nbk_edge_cloud_validity_batch(
             self._h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
-            float(max_distance), 0 if mode == "connect" else 1, float(threshold), None if bits is None else bits.ctypes.data,
+            float(max_distance), _mode_int(mode), float(threshold), _host_ptr(bits),
             0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
             self._stream()), "nbk_edge_cloud_validity_batch")
         return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
@@ -689,7 +698,7 @@ class DeviceModel:
         status = torch.empty((s.B,), dtype=torch.int32, device=s.device)
         _lib.check(self._lib.nbk_edge_continuous_batch(
             self._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
-            0 if mode == "connect" else 1, float(threshold), int(max_iter), float(slack), valid.data_ptr(), end.data_ptr(),
+            _mode_int(mode), float(threshold), int(max_iter), float(slack), valid.data_ptr(), end.data_ptr(),
             t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_edge_continuous_batch")
         return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
 
@@ -705,17 +714,12 @@ class DeviceModel:
         torch = _require_gpu()
         s, g, dd = self._stage_edges(starts, goals, dist)
         bits = self._shape_bits(shapes)
-        if out is None:
-            valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device)
-            t_free = torch.empty((s.B,), dtype=torch.float64, device=s.device)
-            status = torch.empty((s.B,), dtype=torch.int32, device=s.device)
-        else:
-            valid, t_free, status = self._out_tensors(torch, out, s.B, "(valid, t_free, status)")
+        valid, t_free, status = self._result_triple(torch, out, s.B, s.device, "(valid, t_free, status)")
         end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
         _lib.check(self._lib.nbk_edge_cloud_continuous_batch(
             self._h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
-            0 if mode == "connect" else 1, float(threshold), int(max_iter), float(slack), float(look_ahead),
-            None if bits is None else bits.ctypes.data, 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
+            _mode_int(mode), float(threshold), int(max_iter), float(slack), float(look_ahead),
+            _host_ptr(bits), 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
             status.data_ptr(), self._stream()), "nbk_edge_cloud_continuous_batch")
         if out is not None:
             return valid, s.out(end), t_free, status
@@ -726,10 +730,7 @@ class DeviceModel:
         (host) n + degree + 1 values -> valid (S,) bool, t_hit (S,) (the first colliding sample's t, NaN when valid), n_samples
         (S,) int32.  Synchronous: the call reads its sample count back."""
         torch = _require_gpu()
-        shape = tuple(ctrl.shape) if torch.is_tensor(ctrl) else np.shape(ctrl)
-        if len(shape) != 3 or shape[2] != self.n_q:
-            raise ValueError(f"control points must have shape (S, n, {self.n_q}), got {shape}")
-        S, n = int(shape[0]), int(shape[1])
+        S, n = self._spline_dims(ctrl)
         kn = _host_f64(knots, n + int(degree) + 1)
         c = _Staged(ctrl, n * self.n_q, "ctrl")
         valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
@@ -755,13 +756,17 @@ class DeviceModel:
             valid.data_ptr(), t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_continuous_batch")
         return c.out(valid.bool()), c.out(t_free), c.out(status)
 
+    def _spline_dims(self, ctrl):
+        """(S, n) of control points (S, n, n_q), a tensor or anything NumPy takes."""
+        shape = tuple(ctrl.shape) if _torch().is_tensor(ctrl) else np.shape(ctrl)
+        if len(shape) != 3 or shape[2] != self.n_q:
+            raise ValueError(f"control points must have shape (S, n, {self.n_q}), got {shape}")
+        return int(shape[0]), int(shape[1])
+
     def _stage_splines(self, ctrl, knots, degree):
         """The control points and the knots of S splines on one device -> (ctrl ``_Staged``, knots tensor, S, n)."""
         torch = _require_gpu()
-        shape = tuple(ctrl.shape) if torch.is_tensor(ctrl) else np.shape(ctrl)
-        if len(shape) != 3 or shape[2] != self.n_q:
-            raise ValueError(f"control points must have shape (S, n, {self.n_q}), got {shape}")
-        S, n = int(shape[0]), int(shape[1])
+        S, n = self._spline_dims(ctrl)
         c = _Staged(ctrl, n * self.n_q, "ctrl")
         if torch.is_tensor(knots):
             kn = knots.to(device=c.device, dtype=torch.float64).contiguous().reshape(-1)
@@ -772,10 +777,12 @@ class DeviceModel:
         return c, kn, S, n
 
     @staticmethod
-    def _out_tensors(torch, out, S, names):
-        """``out`` of the accumulating cloud calls over edges and splines: three contiguous CUDA tensors of shape (S,), uint8 / bool,
-        float64 and int32."""
+    def _result_triple(torch, out, S, device, names):
+        """The result triple of the cloud calls over edges and splines, shape (S,), uint8 / bool, float64 and int32: fresh on
+        ``device``, or -- accumulating -- the caller's ``out``, three contiguous CUDA tensors of that form."""
         want = ((torch.uint8, torch.bool), (torch.float64,), (torch.int32,))
+        if out is None:
+            return tuple(torch.empty((S,), dtype=w[0], device=device) for w in want)
         if not (isinstance(out, (tuple, list)) and len(out) == 3 and
                 all(torch.is_tensor(o) and o.is_cuda and o.is_contiguous() and tuple(o.shape) == (S,) and o.dtype in w
                     for o, w in zip(out, want))):
@@ -799,16 +806,11 @@ class DeviceModel:
         torch = _require_gpu()
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         bits = self._shape_bits(shapes)
-        if out is None:
-            valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
-            t_hit = torch.empty((S,), dtype=torch.float64, device=c.device)
-            ns = torch.empty((S,), dtype=torch.int32, device=c.device)
-        else:
-            valid, t_hit, ns = self._out_tensors(torch, out, S, "(valid, t_hit, n_samples)")
+        valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
         ws = torch.empty((self.cloud_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device) if workspace is None else workspace
         _lib.check(self._lib.nbk_spline_cloud_validity_batch(
             self._h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
-            None if bits is None else bits.ctypes.data, 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
+            _host_ptr(bits), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
             ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_cloud_validity_batch")
         if out is not None:
             return valid, t_hit, ns
@@ -825,15 +827,10 @@ class DeviceModel:
         torch = _require_gpu()
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         bits = self._shape_bits(shapes)
-        if out is None:
-            valid = torch.empty((S,), dtype=torch.uint8, device=c.device)
-            t_free = torch.empty((S,), dtype=torch.float64, device=c.device)
-            status = torch.empty((S,), dtype=torch.int32, device=c.device)
-        else:
-            valid, t_free, status = self._out_tensors(torch, out, S, "(valid, t_free, status)")
+        valid, t_free, status = self._result_triple(torch, out, S, c.device, "(valid, t_free, status)")
         _lib.check(self._lib.nbk_spline_cloud_continuous_batch(
             self._h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
-            float(look_ahead), None if bits is None else bits.ctypes.data, 0 if out is None else 1, valid.data_ptr(),
+            float(look_ahead), _host_ptr(bits), 0 if out is None else 1, valid.data_ptr(),
             t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_cloud_continuous_batch")
         if out is not None:
             return valid, t_free, status

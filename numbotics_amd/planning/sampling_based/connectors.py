@@ -60,6 +60,20 @@ class ConnectorParams:
             raise ValueError("A point cloud needs ConnectorParams(arm=...)")
 
 
+def _scene_then_cloud(inputs, scene, cloud):
+    """A scene check, then the cloud's reduced INTO its result on the device, so that what the scene already rejected costs the second
+    call nothing.  ``inputs``: the arrays both calls take (None allowed), put on the device first when they come from the host -- the
+    result then goes back to NumPy; device tensors stay where they are.  ``scene(*inputs)`` -> the result tuple, which
+    ``cloud(*inputs, result)`` accumulates into through its ``out=``."""
+    import torch
+    host = not torch.is_tensor(inputs[0])
+    on_dev = lambda x: x if x is None or torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()  # noqa: E731
+    inputs = tuple(on_dev(x) for x in inputs)
+    result = scene(*inputs)
+    cloud(*inputs, result)
+    return tuple(x.cpu().numpy() for x in result) if host else result
+
+
 def _no_cloud(params, what):
     if params.cloud is not None:
         raise ValueError(f"{what} do not see point clouds yet")
@@ -149,19 +163,14 @@ class DiscreteConnector(Connector):
         if p.trajectory_func is not _DEFAULT_TRAJ:
             raise ValueError("batched edge checks support the default linear trajectory only")
         sm, dev = p.arm._scene_device()
+        kw = dict(mode=mode, threshold=p.collision_threshold)
         if p.cloud is None:
-            return dev.edge_validity(starts, goals, p.resolution, p.max_distance, mode=mode,
-                                     threshold=p.collision_threshold, dist=dist)
-        # the scene's verdict, then the cloud's ANDed into it on the device: edges the scene rejected cost the second call nothing
-        import torch
-        host = not torch.is_tensor(starts)
-        on_dev = lambda x: x if x is None or torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()  # noqa: E731
-        starts, goals, dist = on_dev(starts), on_dev(goals), on_dev(dist)
-        valid, end, ns = dev.edge_validity(starts, goals, p.resolution, p.max_distance, mode=mode,
-                                           threshold=p.collision_threshold, dist=dist)
-        dev.cloud_edge_validity(p.cloud, starts, goals, p.resolution, p.max_distance, mode=mode, threshold=p.collision_threshold,
-                                dist=dist, shapes=p.arm._cloud_shapes(sm, p.cloud_ignore_links), out=valid)
-        return (valid.cpu().numpy(), end.cpu().numpy(), ns.cpu().numpy()) if host else (valid, end, ns)
+            return dev.edge_validity(starts, goals, p.resolution, p.max_distance, dist=dist, **kw)
+        # the cloud's verdict is ANDed into the scene's `valid`
+        return _scene_then_cloud(
+            (starts, goals, dist), lambda s, g, d: dev.edge_validity(s, g, p.resolution, p.max_distance, dist=d, **kw),
+            lambda s, g, d, res: dev.cloud_edge_validity(p.cloud, s, g, p.resolution, p.max_distance, dist=d,
+                                                         shapes=p.arm._cloud_shapes(sm, p.cloud_ignore_links), out=res[0], **kw))
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -177,18 +186,14 @@ class DiscreteConnector(Connector):
     def _spline_check(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None):
         p = self._params
         sm, dev = p.arm._scene_device()
+        scene = lambda c: dev.spline_validity(c, knots, degree, p.resolution, threshold=p.collision_threshold)      # noqa: E731
         if cloud is None:
-            return dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
-        # the scene's verdict, then the cloud's reduced into it on the device: only samples before the scene's first hit are looked at
-        import torch
-        host = not torch.is_tensor(ctrl)
-        if host:
-            ctrl = torch.from_numpy(np.ascontiguousarray(ctrl, dtype=np.float64)).cuda()
+            return scene(ctrl)
+        # only samples before the scene's first hit are looked at
         links = p.cloud_ignore_links if cloud_ignore_links is None else tuple(cloud_ignore_links)
-        out = dev.spline_validity(ctrl, knots, degree, p.resolution, threshold=p.collision_threshold)
-        dev.cloud_spline_validity(cloud, ctrl, knots, degree, p.resolution, threshold=p.collision_threshold,
-                                  shapes=p.arm._cloud_shapes(sm, links), out=out)
-        return tuple(x.cpu().numpy() for x in out) if host else out
+        return _scene_then_cloud(
+            (ctrl,), scene, lambda c, res: dev.cloud_spline_validity(cloud, c, knots, degree, p.resolution, threshold=p.collision_threshold,
+                                                                     shapes=p.arm._cloud_shapes(sm, links), out=res))
 
     def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None):
         """S clamped B-splines of ``unit_bspline``'s knots, every one sampled at most ``resolution`` apart in joint space and checked
@@ -360,16 +365,12 @@ class ContinuousConnector(Connector):
         kw = dict(mode=mode, threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
         if self.cloud is None:
             return dev.edge_continuous(starts, goals, p.max_distance, dist=dist, **kw)
-        # the scene's result, then the cloud's items reduced into it on the device: items of an edge the scene stopped early stop there
-        import torch
-        host = not torch.is_tensor(starts)
-        on_dev = lambda x: x if x is None or torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).cuda()  # noqa: E731
-        starts, goals, dist = on_dev(starts), on_dev(goals), on_dev(dist)
-        valid, end, t_free, status = dev.edge_continuous(starts, goals, p.max_distance, dist=dist, **kw)
-        dev.cloud_edge_continuous(self.cloud, starts, goals, p.max_distance, look_ahead=self.look_ahead, dist=dist,
-                                  shapes=p.arm._cloud_shapes(sm, self.cloud_ignore_links), out=(valid, t_free, status), **kw)
-        out = (valid, end, t_free, status)
-        return tuple(x.cpu().numpy() for x in out) if host else out
+        # items of an edge the scene stopped early stop there; `end` is the scene's
+        return _scene_then_cloud(
+            (starts, goals, dist), lambda s, g, d: dev.edge_continuous(s, g, p.max_distance, dist=d, **kw),
+            lambda s, g, d, res: dev.cloud_edge_continuous(self.cloud, s, g, p.max_distance, look_ahead=self.look_ahead, dist=d,
+                                                           shapes=p.arm._cloud_shapes(sm, self.cloud_ignore_links),
+                                                           out=(res[0], res[2], res[3]), **kw))
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -391,16 +392,11 @@ class ContinuousConnector(Connector):
         kw = dict(threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
         if cloud is None:
             return dev.spline_continuous(ctrl, knots, degree, **kw)
-        # the scene's result, then the cloud's items reduced into it on the device, as certify_batch does for edges
-        import torch
-        host = not torch.is_tensor(ctrl)
-        if host:
-            ctrl = torch.from_numpy(np.ascontiguousarray(ctrl, dtype=np.float64)).cuda()
         links = self.cloud_ignore_links if cloud_ignore_links is None else tuple(cloud_ignore_links)
-        out = dev.spline_continuous(ctrl, knots, degree, **kw)
-        dev.cloud_spline_continuous(cloud, ctrl, knots, degree, look_ahead=self.look_ahead, shapes=p.arm._cloud_shapes(sm, links),
-                                    out=out, **kw)
-        return tuple(x.cpu().numpy() for x in out) if host else out
+        return _scene_then_cloud(
+            (ctrl,), lambda c: dev.spline_continuous(c, knots, degree, **kw),
+            lambda c, res: dev.cloud_spline_continuous(cloud, c, knots, degree, look_ahead=self.look_ahead,
+                                                       shapes=p.arm._cloud_shapes(sm, links), out=res, **kw))
 
     def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None):
         """S clamped B-splines of ``unit_bspline``'s knots, each certified on the device by conservative advancement across its knot
