@@ -485,6 +485,35 @@ int32_t nbk_cloud_cells_host(const double lo[3], double cell, const int32_t dims
                              int32_t *cell_out);                 /* no GPU: the same routine, for tests */
 
 /*
+ * Proximity records against a cloud: nbk_cloud_clearance_batch's record with WHERE the contact is and WHICH WAY to move -- what
+ * nbk_proximity_jacobian_batch / nbk_pair_records_items give for the scene's pairs.  (Named like its siblings over edges and splines,
+ * nbk_<what>_cloud_*: the nbk_cloud_* names are the cloud object's own set.)
+ *   q (device) [B][n_q]; d_max finite; shape_bits (HOST, optional) as nbk_cloud_clearance_batch.
+ *   per_shape == 0, one record per configuration: dist [B], shape [B], point [B], witness [B][9], jrows [B][n_q] (all device);
+ *     dist, shape and point are the bits of nbk_cloud_clearance_batch for the same arguments, its tie rule included (smallest shape,
+ *     then smallest point index).
+ *   per_shape != 0, one record per (configuration, selected shape): [B][n_sel], [B][n_sel][9], [B][n_sel][n_q]; column j is the j-th
+ *     selected shape in ascending caller's index, and each entry is what nbk_cloud_clearance_batch reports for that shape selected
+ *     alone with the same d_max -- the form a per-link constraint takes.
+ *   witness and jrows belong to the winning (shape s, point i): the witness and jrows bits of nbk_proximity_jacobian_batch on a
+ *     descriptor that holds point i as a sphere world shape of the cloud's radius (identity rotation), paired with s.  witness =
+ *     position on the robot shape, position on the point's sphere, unit normal from target to subject; jrows = n . Jv_subject(position
+ *     on subject) -- the cloud is a world target, so there is no target term.
+ *   nothing nearer than d_max (an empty cloud and an empty selection included): +inf, -1, -1, witness NaN, jrows all +0.0 -- the
+ *     gradient of a hinge cost, so rows can be weighted without a mask.  per_shape with an empty selection writes nothing.
+ *   a non-finite configuration or a set cloud status: NaN, -1, -1, NaN, NaN.
+ *   shape, point, witness and jrows are each optional.
+ * NBK_ERR_INVALID -- before any device is looked for -- for a null m or c, B < 0, a non-finite d_max, or null q / dist with B > 0;
+ * B == 0 returns NBK_OK at once.  NBK_ERR_UNSUPPORTED for a selection on a descriptor of more than 256 robot shapes.
+ * Asynchronous and capturable: no allocation, no host synchronisation, one kernel on `stream`.  Nothing is parked in LDS beyond the
+ * q rows and (with jrows) the joint rows, 8 * 64 * (n_q + 6 n_joints) bytes, so every descriptor is served.
+ */
+int32_t nbk_records_cloud_batch(const nbk_model *m, const nbk_cloud *c, const double *q, int64_t B, double d_max,
+                                const uint64_t *shape_bits /* host, as nbk_cloud_clearance_batch */, int32_t per_shape,
+                                double *dist, int32_t *shape, int32_t *point, double *witness /* optional */,
+                                double *jrows /* optional */, void *stream);
+
+/*
  * Sampled straight-line edges against a cloud: nbk_edge_validity_batch's edges, nbk_cloud_validity_batch's verdict per sample -- what
  * a planner's connector asks about a scan.  The samples are generated on the device and never written down as q rows.
  *   starts, goals (device) [E][n_q]; dist (device, optional) [E]; the edge rule is nbk_edge_validity_batch's, word for word:

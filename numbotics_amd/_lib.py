@@ -31,7 +31,7 @@ SYMBOLS = [
     "nbk_model_create_movable", "nbk_model_set_world_poses", "nbk_model_set_world_poses_host", "nbk_model_world_status",
     "nbk_world_reach_bounds_host",
     "nbk_cloud_create", "nbk_cloud_destroy", "nbk_cloud_set_points", "nbk_cloud_status", "nbk_cloud_validity_batch",
-    "nbk_cloud_clearance_batch", "nbk_cloud_cells_host",
+    "nbk_cloud_clearance_batch", "nbk_cloud_cells_host", "nbk_records_cloud_batch",
     "nbk_edge_cloud_workspace_bytes", "nbk_edge_cloud_validity_batch",
     "nbk_edge_cloud_continuous_batch", "nbk_edge_shape_motion_bounds_host",
     "nbk_spline_cloud_workspace_bytes", "nbk_spline_cloud_validity_batch",
@@ -135,6 +135,7 @@ def load():
     lib.nbk_cloud_validity_batch.argtypes = [vp, vp, vp, i64, f64, vp, i32, vp, vp, vp]
     lib.nbk_cloud_clearance_batch.argtypes = [vp, vp, vp, i64, f64, vp, vp, vp, vp, vp]
     lib.nbk_cloud_cells_host.argtypes = [vp, f64, vp, vp, i64, vp]
+    lib.nbk_records_cloud_batch.argtypes = [vp, vp, vp, i64, f64, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.nbk_edge_cloud_workspace_bytes.argtypes = [i64]
     lib.nbk_edge_cloud_workspace_bytes.restype = i64
     lib.nbk_edge_cloud_validity_batch.argtypes = [vp, vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, i32, vp, vp, vp, vp, i64, vp]

@@ -2816,12 +2816,10 @@ __global__ __launch_bounds__(NARROW_T, 2) void k_narrow_pos(DevModel m, EdgeSrc 
 // MODE 3: distances + witnesses + proximity-Jacobian rows (Arm.jacobian_proximity, arm.py:620-632):
 //         row[col(k)] = n . Jv_subject,k(p_s) - n . Jv_target,k(p_t) over the joints k above each shape, with
 //         Jv_k(r) = w_k x (r - o_k) (revolute) or w_k (prismatic); world targets contribute nothing.
-// one row of the proximity Jacobian (MODE 3) of pair p for the configuration parked in LDS column `col`
-NBK_DEV void prox_row(const DevModel& m, const double* lds_jz, int col, int p, const double* wit, double* row) {
+// one row of the proximity Jacobian for the configuration parked in LDS column `col`, from the joint masks of the subject (ma) and
+// of the target (mb; 0 for a world target)
+NBK_DEV void prox_row_masks(const DevModel& m, const double* lds_jz, int col, unsigned ma, unsigned mb, const double* wit, double* row) {
     for (int c = 0; c < m.n_q; ++c) row[c] = 0.0;
-    const int sa = m.pair_a[p], sb = m.pair_b[p];
-    const unsigned ma = m.rs_mask[sa];
-    const unsigned mb = sb < m.n_rshapes ? m.rs_mask[sb] : 0u;
     for (int k = 0; k < m.n_joints; ++k) {
         const bool in_a = (ma >> k) & 1u, in_b = (mb >> k) & 1u;
         if (!in_a && !in_b) continue;
@@ -2839,6 +2837,11 @@ NBK_DEV void prox_row(const DevModel& m, const double* lds_jz, int col, int p, c
         }
         row[m.joint_qidx[k]] = va - vb;
     }
+}
+// the row (MODE 3) of pair p
+NBK_DEV void prox_row(const DevModel& m, const double* lds_jz, int col, int p, const double* wit, double* row) {
+    const int sa = m.pair_a[p], sb = m.pair_b[p];
+    prox_row_masks(m, lds_jz, col, m.rs_mask[sa], sb < m.n_rshapes ? m.rs_mask[sb] : 0u, wit, row);
 }
 
 // the EPA pass of an item that cores_distance<WIT, true> answered with the axis-family depth `fam` (a cylinder or hull core

@@ -331,9 +331,10 @@ NBK_DEV double cloud_search_radius(double D, const Core& A, double radius) {
 
 // The per-shape body of the clearance (k_cloud_clearance, CloudEdgeLane): core A of the robot shape with the caller's index su, built
 // by the caller (`ok`: this lane holds one), against every point of the cloud; best / bs / bi come in as the row's running minimum
-// and go out lowered.  Called by every lane of the wave.
+// and go out lowered.  Called by every lane of the wave.  bslot (optional; k_cloud_records): where a point that lowers the minimum
+// stands in the SORTED arrays -- cd.idx maps sorted to original only, and the record needs the winner's coordinates again.
 NBK_DEV void cloud_core_clearance(const CloudDev& cd, const Core& A, Core& P, double radius, bool ok, int su, double d_max,
-                                  double& best, int& bs, int& bi) {
+                                  double& best, int& bs, int& bi, unsigned* bslot = nullptr) {
     double R = ok ? cloud_search_radius(best < d_max ? best : d_max, A, radius) : 0.0;
     CloudWalk w;
     cloud_walk_begin(cd, ok, A.c, R, w);
@@ -358,6 +359,7 @@ NBK_DEV void cloud_core_clearance(const CloudDev& cd, const Core& A, Core& P, do
             if (fam >= 0.0) epa_refine<false>(A, P, fam, d, nullptr);
             if (d < d_max && (d < best || (d == best && (su < bs || (su == bs && oi < bi))))) {
                 best = d; bs = su; bi = oi;
+                if (bslot != nullptr) *bslot = w.cur - 1u;       // (the run-ahead loop stops behind its candidate)
                 R = cloud_search_radius(best, A, radius);
                 R2 = R * R;
             }
@@ -402,6 +404,117 @@ __global__ __launch_bounds__(64) void k_cloud_clearance(DevModel m, CloudDev cd,
         out_d[b] = ok ? best : __builtin_nan("");
         if (out_s != nullptr) out_s[b] = ok ? bs : -1;
         if (out_p != nullptr) out_p[b] = ok ? bi : -1;
+    }
+}
+
+// ---- proximity records (nbk_records_cloud_batch) -----------------------------------------------------------------------------------
+// The clearance's winner with its witness and gradient row, one configuration per lane, in two phases.
+//   1. the winner: cloud_core_clearance as k_cloud_clearance calls it, which also keeps the winner's slot in the sorted arrays and
+//      (here) the device index of its shape.  PER_SHAPE = false runs k_cloud_clearance's shape loop; PER_SHAPE = true has the grid
+//      (ceil(B / 64), selected shapes) of k_cloud_edge_ca -- a wave holds ONE shape, every item starts from a fresh `best` -- and
+//      writes column `col` of [B][n_sel]: the rank of the shape's caller's index among the selected ones.
+//   2. the record, for the lanes that hold a winner and only when a witness or a row is asked for: the winner shape's joint chain
+//      once more (the joint_apply sequence of cloud_shape_frame, so the same frame bits), with joint_frame_rows into the
+//      [J][6][64] LDS rows when rows are asked for; build_core; cores_distance<true, true> and epa_refine<true> on (shape core,
+//      point core) -- item_distance's statements for a (robot shape, sphere world shape) pair; prox_row_masks with the shape's mask
+//      and 0.  The hull's scalar-cache path only where every lane with a winner holds the same shape.  The distance this phase
+//      finds is the one reported where it runs: the bits of phase 1, as tests/test_gpu_cloud_records.py checks against both.
+// Nothing nearer than d_max: +inf, -1, -1, NaN witness, a row of +0.0 (the gradient of a hinge cost).  A non-finite configuration
+// or a set status: NaN, -1, -1, NaN, NaN.  LDS: PairItemsLds -- [64][n_q] q rows | [J][6][64] joint rows when rows are asked for.
+template <bool PER_SHAPE>
+__global__ __launch_bounds__(64) void k_cloud_records(DevModel m, CloudDev cd, CloudSel sel, const int* __restrict__ rs_user,
+                                                      const double* __restrict__ q, int64_t B, double d_max, int n_sel,
+                                                      double* __restrict__ out_d, int32_t* __restrict__ out_s, int32_t* __restrict__ out_p,
+                                                      double* __restrict__ out_w, double* __restrict__ out_j) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    const PairItemsLds L(m.n_q);
+    double* myq = L.q(lds) + lane * m.n_q;
+    double* lds_jz = out_j != nullptr ? L.jz(lds) : nullptr;
+    // per shape: the blockIdx.y-th selected shape, device order, and its column
+    int only = -1, col = 0;
+    if constexpr (PER_SHAPE) {
+        for (int i = 0, k = 0; i < m.n_rshapes; ++i) {
+            if (!cloud_selected(sel, i)) continue;
+            if (k == (int)blockIdx.y) { only = i; break; }
+            ++k;
+        }
+        if (only < 0) return;
+        for (int i = 0; i < m.n_rshapes; ++i)
+            if (cloud_selected(sel, i) && rs_user[i] < rs_user[only]) ++col;
+    }
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool ok = false;
+    if (active) ok = cloud_stage_q(q, b, m.n_q, myq) && status == 0;
+    double best = NBK_INF;
+    int bs = -1, bi = -1, bdev = 0;
+    unsigned slot = 0u;
+    Core P;
+    cloud_point_core(radius, P);
+    if (n > 0 && status == 0 && __builtin_amdgcn_ballot_w64(ok) != 0ull) {
+        Xf T;
+        int cur_frame = -2;
+        for (int s = PER_SHAPE ? only : 0; s < (PER_SHAPE ? only + 1 : m.n_rshapes); ++s) {
+            if (!cloud_selected(sel, s)) continue;
+            Core A;
+            cloud_core_init(A);
+            if (ok) {
+                if (m.rs_frame[s] != cur_frame) cloud_shape_frame(m, s, myq, T);
+                build_core(m, s, T, A);
+                if (A.kind == K_HULL) A.rad = -1.0;
+            }
+            cur_frame = m.rs_frame[s];
+            cloud_core_clearance(cd, A, P, radius, ok, rs_user[s], d_max, best, bs, bi, &slot);
+            if (bs == rs_user[s]) bdev = s;              // (a caller's index names one shape: bs equals it only once set here)
+        }
+    }
+    const bool win = ok && bs >= 0;
+    double wit[9];
+    if ((out_w != nullptr || out_j != nullptr) && __builtin_amdgcn_ballot_w64(win) != 0ull) {
+        const unsigned mask = win ? m.rs_mask[bdev] : 0u;
+        Xf T;
+        xf_from12(m.base_pose, T);
+        for (int k = 0; k < m.n_joints; ++k) {
+            if (((mask >> k) & 1u) == 0u) continue;
+            Xf nxt;
+            joint_apply(m, k, T, myq[m.joint_qidx[k]], nxt);
+            if (lds_jz != nullptr) joint_frame_rows(m, k, nxt, lds_jz + 6 * k * WAVE + lane);
+            T = nxt;
+        }
+        // the hull support's scalar-cache path (rad < 0) needs every working lane to hold the same hull, as item_distance has it
+        const unsigned long long wm = __builtin_amdgcn_ballot_w64(win);
+        const int s0 = __shfl(bdev, __builtin_ctzll(wm));
+        const bool uniform = __builtin_amdgcn_ballot_w64(win && bdev != s0) == 0ull;
+        if (win) {
+            Core A;
+            cloud_core_init(A);
+            build_core(m, bdev, T, A);
+            if (uniform && A.kind == K_HULL) A.rad = -1.0;
+            const double* p = cd.pts + 3 * (size_t)slot;
+            P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+            double fam = -1.0;
+            double d = cores_distance<true, true>(A, P, wit, &fam);
+            if (fam >= 0.0) epa_refine<true>(A, P, fam, d, wit);
+            best = d;
+        }
+    }
+    if (!active) return;
+    const int64_t o = PER_SHAPE ? b * n_sel + col : b;
+    const double nan = __builtin_nan("");
+    out_d[o] = ok ? best : nan;
+    if (out_s != nullptr) out_s[o] = ok ? bs : -1;
+    if (out_p != nullptr) out_p[o] = ok ? bi : -1;
+    if (out_w != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) out_w[o * 9 + e] = win ? wit[e] : nan;
+    }
+    if (out_j != nullptr) {
+        if (win) prox_row_masks(m, lds_jz, lane, m.rs_mask[bdev], 0u, wit, out_j + o * m.n_q);
+        else for (int c = 0; c < m.n_q; ++c) out_j[o * m.n_q + c] = ok ? 0.0 : nan;
     }
 }
 
@@ -877,6 +990,29 @@ int32_t nbk_cloud_clearance_batch(const nbk_model* m, const nbk_cloud* c, const 
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
                        cloud_dev(c), sel, m->rs_user, q, B, d_max, min_dist, shape, point);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_records_cloud_batch(const nbk_model* m, const nbk_cloud* c, const double* q, int64_t B, double d_max,
+                                const uint64_t* shape_bits, int32_t per_shape, double* dist, int32_t* shape, int32_t* point,
+                                double* witness, double* jrows, void* stream) {
+    // (nothing below dereferences m or c before the argument rules are through and B is known to be positive)
+    if (m == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0) || (B > 0 && (q == nullptr || dist == nullptr))) return NBK_ERR_INVALID;
+    if (B == 0) return NBK_OK;
+    CloudSel sel;
+    int n_sel = 0;
+    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel, &n_sel); if (rc != NBK_OK) return rc; }
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const size_t lds = PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes();
+    if (per_shape) {
+        if (n_sel == 0) return NBK_OK;                       // no column: nothing is written
+        hipLaunchKernelGGL(k_cloud_records<true>, dim3(blocks_for(B), (unsigned)n_sel), dim3(WAVE), lds, (hipStream_t)stream, m->d,
+                           cloud_dev(c), sel, m->rs_user, q, B, d_max, n_sel, dist, shape, point, witness, jrows);
+    } else {
+        hipLaunchKernelGGL(k_cloud_records<false>, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, cloud_dev(c), sel,
+                           m->rs_user, q, B, d_max, n_sel, dist, shape, point, witness, jrows);
+    }
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

@@ -572,6 +572,34 @@ class DeviceModel:
             d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._stream()), "nbk_cloud_clearance_batch")
         return qs.out(d), qs.out(sh), qs.out(pt)
 
+    def cloud_records(self, cloud, q, d_max, shapes=None, per_shape=False, witness=True, jacobian=True):
+        """``cloud_clearance``'s record with the contact and the way out of it (nbk_records_cloud_batch) -> (dist, shape, point,
+        witness or None, rows or None).  ``per_shape=False``: one record per configuration, (B,), (B,), (B,), (B, 9), (B, n_q);
+        dist, shape and point are ``cloud_clearance``'s bits.  ``per_shape=True``: one per (configuration, selected shape),
+        (B, n_sel) ..., column j the j-th selected shape in ascending index, each entry ``cloud_clearance`` with that shape
+        selected alone.  witness = point on the robot shape, point on the cloud point's sphere, unit normal from the point to the
+        shape; rows = n . Jv_shape(point on the shape), the gradient of the distance.  Nothing nearer than ``d_max``: inf, -1, -1,
+        NaN witness, a row of zeros; a non-finite configuration or a set cloud status: NaN, -1, -1, NaN, NaN."""
+        bits = self._shape_bits(shapes)                 # (argument errors come before the device is touched)
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        if per_shape:
+            n_sel = len({int(s) for s in shapes}) if shapes is not None else (0 if self.scene is None else self.scene.n_rshapes)
+            lead = (qs.B, n_sel)
+        else:
+            lead = (qs.B,)
+        d = torch.empty(lead, dtype=torch.float64, device=qs.device)
+        sh = torch.empty(lead, dtype=torch.int32, device=qs.device)
+        pt = torch.empty(lead, dtype=torch.int32, device=qs.device)
+        w = torch.empty(lead + (9,), dtype=torch.float64, device=qs.device) if witness else None
+        j = torch.empty(lead + (self.n_q,), dtype=torch.float64, device=qs.device) if jacobian else None
+        if d.numel() > 0:
+            _lib.check(self._lib.nbk_records_cloud_batch(
+                self._h, cloud._h, qs.t.data_ptr(), qs.B, float(d_max), _host_ptr(bits), 1 if per_shape else 0,
+                d.data_ptr(), sh.data_ptr(), pt.data_ptr(), None if w is None else w.data_ptr(),
+                None if j is None else j.data_ptr(), self._stream()), "nbk_records_cloud_batch")
+        return qs.out(d), qs.out(sh), qs.out(pt), None if w is None else qs.out(w), None if j is None else qs.out(j)
+
     def pair_distances(self, q, witness=False):
         torch = _require_gpu()
         qs = _Staged(q, self.n_q)

@@ -13,6 +13,8 @@ cvxpy/MOSEK ellipsoid, SLSQP) are out of scope.
   ``counter_ex_search_nlp`` hands to SLSQP (safe_sets.py:86-121: ``distance_to(x, link, obj)[0].distance`` and
   ``jacobian_proximity(x, link=link, obj=obj)``), for M points in one launch that computes the body pair's primitive pairs
   only (``Arm.pair_proximity_jacobians``).
+* ``cloud_distance_and_gradient(arm, points, cloud, d_max, link)``: the same constraint value and gradient against a point cloud
+  (``DeviceModel.cloud_records``), one launch.
 """
 import numpy as np
 
@@ -141,3 +143,21 @@ def distance_and_gradient(arm, points, link, obj):
     k = np.argmin(dist, axis=1)
     i = np.arange(points.shape[0])
     return dist[i, k], rows[i, k]
+
+
+def cloud_distance_and_gradient(arm, points, cloud, d_max, link=None, ignore_links=()):
+    """``distance_and_gradient`` against a point cloud: (M, dof) -> the signed distance (M,) between the arm and ``cloud`` (a
+    ``PointCloud``) where it is below ``d_max`` and its gradient rows (M, dof); inf and a row of zeros where nothing is that near
+    (the value and gradient of a hinge constraint), NaN for a non-finite point.  ``link`` (a Link or its name): that link's shapes
+    only, the minimum over them; otherwise every shape but those of ``ignore_links``."""
+    sm = arm.scene_model()
+    if link is not None:
+        name = getattr(link, "_name", link)
+        arm._cloud_shapes(sm, [name])                                    # an unknown link: its error
+        shapes = [s for s in range(sm.n_rshapes) if sm.links[sm.rshape_link[s]]._name == name]
+    else:
+        shapes = arm._cloud_shapes(sm, ignore_links)
+    points = np.asarray(points, dtype=np.float64).reshape(-1, arm.dof)
+    _, dev = arm._scene_device()
+    dist, _, _, _, rows = dev.cloud_records(cloud, points, d_max, shapes=shapes, witness=False)
+    return dist, rows

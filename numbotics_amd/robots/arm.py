@@ -591,6 +591,45 @@ class Arm(Robot):
         names = np.array([sm.links[sm.rshape_link[s]]._name if s >= 0 else None for s in shn], dtype=object)
         return d, names, pt
 
+    def _link_names(self, sm, sh):
+        shn = sh.cpu().numpy() if _is_tensor(sh) else sh
+        flat = [sm.links[sm.rshape_link[s]]._name if s >= 0 else None for s in shn.reshape(-1)]
+        out = np.empty((len(flat),), dtype=object)
+        out[:] = flat
+        return out.reshape(shn.shape)
+
+    def cloud_proximity_jacobians(self, q, cloud, d_max: float, ignore_links=(), per_shape: bool = False):
+        """``cloud_clearance`` with the contact and the gradient: (distance, link names, point index, witness, rows) per
+        configuration of ``q`` (``(dof,)`` or ``(..., dof)``, flattened to B rows) -- witness ``(B, 9)`` = point on the link's
+        shape, point on the cloud point's sphere, unit normal from the point to the shape; rows ``(B, dof)`` = n . Jv_link(point on
+        the shape), the gradient of the distance.  Nothing nearer than ``d_max``: inf, None, -1, NaN, a row of zeros (a hinge
+        cost's gradient).  ``per_shape=True``: one record per (configuration, link shape left after ``ignore_links``), ``(B, S)``,
+        ``(B, S)``, ``(B, S)``, ``(B, S, 9)``, ``(B, S, dof)``, and a sixth value: the link names of the S columns."""
+        sm = self.scene_model()
+        self._check_q(q)
+        shapes = self._cloud_shapes(sm, ignore_links)
+        _, dev = self._scene_device()
+        d, sh, pt, w, j = dev.cloud_records(cloud, q.reshape(-1, self.dof), d_max, shapes=shapes, per_shape=per_shape)
+        if not per_shape:
+            return d, self._link_names(sm, sh), pt, w, j
+        cols = range(sm.n_rshapes) if shapes is None else shapes
+        return d, self._link_names(sm, sh), pt, w, j, np.array([sm.links[sm.rshape_link[s]]._name for s in cols], dtype=object)
+
+    def cloud_closest_to(self, q, cloud, d_max: float, ignore_links=()):
+        """``closest_to`` for a cloud: the ``Proximity`` of the closest (link shape, point) when it is nearer than ``d_max`` --
+        subject = the link, target = ``cloud`` -- else None (also for a non-finite ``q``)."""
+        if tuple(q.shape) != (self.dof,):
+            raise ValueError(f"q must be a 1D array with {self.dof} elements")
+        sm = self.scene_model()
+        shapes = self._cloud_shapes(sm, ignore_links)
+        _, dev = self._scene_device()
+        qn = q.detach().cpu().numpy() if _is_tensor(q) else np.asarray(q, dtype=np.float64)
+        d, sh, _, w, _ = dev.cloud_records(cloud, qn.reshape(1, -1), d_max, shapes=shapes, jacobian=False)
+        if sh[0] < 0:
+            return None
+        return Proximity(subject=sm.links[sm.rshape_link[sh[0]]], target=cloud, position_on_subject=w[0, 0:3].copy(),
+                         position_on_target=w[0, 3:6].copy(), normal_target_to_subject=w[0, 6:9].copy(), distance=float(d[0]))
+
     def pair_distances(self, q):
         """(B, P) signed distances of every allowed primitive pair (additive, batched ``collisions``)."""
         sm, dev = self._scene_device()

@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -32,6 +32,10 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
                 1e-6) per (trajectory, shape) item at each look_ahead of the certified table; next to each, windows alternating, the
                 straight-edge entry on E = 1e3 of the edges above against the same cloud: cloud_edge_validity per sample,
                 cloud_edge_continuous per (edge, shape) item
+    records     (only when asked for) c2 against scan(100 000), B = 1e5 configurations, d_max = 0.05: DeviceModel.cloud_clearance, then
+                DeviceModel.cloud_records per configuration with witness and rows, with the witness alone and with neither, windows
+                alternating with the clearance call's; then per (configuration, shape) with rows.  Each line has the ratio to the
+                clearance windows it alternated with.  (profiles/cloud_records_time.log)
 """
 import argparse
 import os
@@ -234,6 +238,27 @@ def splines_part(dev, chain, shapes, reps):
                 f"edges {fmt(te)}  {te[0] * 1e3 / (S * K):.2f} us/item  {counts(se)}")
 
 
+def records_part(dev, sm, shapes, q5, reps):
+    N, d_max = 10 ** 5, 0.05
+    cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), RADIUS, bounds=BOX)
+    clr = lambda: dev.cloud_clearance(cloud, q5, d_max, shapes=shapes)                                  # noqa: E731
+    d, s, p = clr()
+    near = torch.isfinite(d)
+    say(f"records: N = {N}, B = {q5.shape[0]}, d_max {d_max}, {len(shapes)} shapes; below d_max {float(near.float().mean()):.3f}")
+    say(f"  cloud_clearance alone                    {fmt(timed(clr, reps))}")
+    for name, kw in (("per configuration, witness + rows", {}), ("per configuration, witness", dict(jacobian=False)),
+                     ("per configuration, neither", dict(witness=False, jacobian=False)), ("per shape, witness + rows", dict(per_shape=True))):
+        rec = lambda: dev.cloud_records(cloud, q5, d_max, shapes=shapes, **kw)                          # noqa: E731
+        r = rec()
+        if not kw.get("per_shape"):
+            assert torch.equal(r[0][near], d[near]) and torch.equal(r[1], s) and torch.equal(r[2], p), "records and clearance differ"
+            share = ""
+        else:
+            share = f"   items below d_max {float(torch.isfinite(r[0]).float().mean()):.3f}"
+        tr, tc = timed_pair(rec, clr, reps)
+        say(f"  {name:36s} {fmt(tr)}   clearance beside it {fmt(tc)}   ratio {tr[0] / tc[0]:.2f}x{share}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -303,6 +328,8 @@ def main():
         certified_part(dev, chain, shapes, a.reps)
     if "splines" in only:
         splines_part(dev, chain, shapes, a.reps)
+    if "records" in only:
+        records_part(dev, sm, shapes, q5, a.reps)
 
 
 if __name__ == "__main__":
