@@ -485,6 +485,50 @@ int32_t nbk_cloud_cells_host(const double lo[3], double cell, const int32_t dims
                              int32_t *cell_out);                 /* no GPU: the same routine, for tests */
 
 /*
+ * Depth frames to a cloud (additive): back-projection, the robot's own image taken out, and an update that honours the mask.  Three
+ * stream-ordered steps in caller memory: no allocation, no host synchronisation, capturable; point i of a frame is pixel
+ * i = v * W + u all the way, so the `point` of a clearance record names a pixel.  (Named nbk_frame_cloud_*, like the siblings over
+ * edges, splines and records: the nbk_cloud_* names are the cloud object's own first set.)
+ *
+ * nbk_frame_cloud_backproject: depth (DEVICE) [H][W], depth_type 0 = float32, 1 = uint16 raw units; a pinhole fx, fy, cx, cy in the OPTICAL
+ * frame (z forward, x right, y down) whose world pose is T (DEVICE, [3][4] row-major: read when the kernel runs, so a replayed graph
+ * follows a pose rewritten in place).  Depth is metric along the view axis.  In float64, every operation rounded once, in this order:
+ *     z  = (double)d * depth_scale;   xc = (((double)u - cx) * z) / fx;   yc = (((double)v - cy) * z) / fy;
+ *     pts[i][e] = ((T[e][0] * xc + T[e][1] * yc) + T[e][2] * z) + T[e][3]
+ * keep[i] = 1 iff z is finite, z > z_min and z <= z_max; otherwise keep[i] = 0 and pts[i] = (0, 0, 0) (a hole: 0, NaN, out of range).
+ * NBK_ERR_INVALID -- before any device is looked for -- for H or W < 0, H * W > 2^24, an unknown depth_type, fx, fy or depth_scale
+ * not positive (NaN included), a null T, or null depth / pts / keep with H * W > 0.  nbk_frame_cloud_backproject_host (no GPU needed): the
+ * same routine on HOST arrays, T included.
+ *
+ * nbk_frame_cloud_self_filter: q0 (DEVICE) [n_q], pts (DEVICE) [N][3], keep (DEVICE) [N] read and written.  keep[i] stays 0 where it is 0;
+ * else it becomes 0 iff for some selected robot shape s the predicate of nbk_cloud_validity_batch holds for (s, a sphere of `radius`
+ * at pts[i]) at q0 with threshold = padding -- the same statements in the same order, so a cloud of the points kept reads free at
+ * (q0, padding, the same selection), exactly.  A non-finite q0 removes nothing; a non-finite point is left as it is (the masked
+ * update raises the status for it).  shape_bits as nbk_cloud_validity_batch.  One kernel: the selected shapes' cores at q0 are built
+ * once per workgroup into LDS (168 bytes a shape); NBK_ERR_UNSUPPORTED when they do not fit 160 KB.  NBK_ERR_INVALID -- before any
+ * device is looked for -- for a null m or q0, N < 0 or > 2^24, a NaN or negative radius, a NaN padding, null pts / keep with N > 0.
+ * nbk_frame_cloud_self_filter_lds_bytes (no GPU needed): that kernel's LDS for n_shapes selected shapes, -1 when the entry refuses them.
+ *
+ * nbk_frame_cloud_set_points: nbk_cloud_set_points with keep (DEVICE) [N]; NULL = nbk_cloud_set_points, which is this call.  A
+ * point with keep[i] == 0 is neither counted, nor stored, nor checked for finiteness; the cloud holds the others under their
+ * ORIGINAL indices i (what nbk_cloud_clearance_batch reports).  `capacity` bounds N, the points submitted.
+ * nbk_frame_cloud_count: the points the cloud holds (those kept); synchronous, as nbk_cloud_status.
+ */
+int32_t nbk_frame_cloud_backproject(const void *depth /* DEVICE [H][W] */, int32_t depth_type, int32_t H, int32_t W, double depth_scale,
+                              double fx, double fy, double cx, double cy, const double *T /* DEVICE [3][4] */, double z_min,
+                              double z_max, double *pts /* DEVICE [H*W][3] */, uint8_t *keep /* DEVICE [H*W] */, void *stream);
+int32_t nbk_frame_cloud_backproject_host(const void *depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx,
+                                   double fy, double cx, double cy, const double *T, double z_min, double z_max, double *pts,
+                                   uint8_t *keep);               /* no GPU: the same routine on host arrays */
+int32_t nbk_frame_cloud_self_filter(const nbk_model *m, const double *q0 /* DEVICE [n_q] */, const double *pts /* DEVICE [N][3] */,
+                              int64_t N, double radius, double padding, const uint64_t *shape_bits /* host */,
+                              uint8_t *keep /* DEVICE [N], in and out */, void *stream);
+int64_t nbk_frame_cloud_self_filter_lds_bytes(int32_t n_shapes);       /* no GPU */
+int32_t nbk_frame_cloud_set_points(nbk_cloud *c, const double *pts /* DEVICE [N][3] */, const uint8_t *keep /* DEVICE [N] or NULL */,
+                                    int64_t N, double radius, void *stream);
+int32_t nbk_frame_cloud_count(const nbk_cloud *c, int64_t *n);         /* synchronous: the points held */
+
+/*
  * Proximity records against a cloud: nbk_cloud_clearance_batch's record with WHERE the contact is and WHICH WAY to move -- what
  * nbk_proximity_jacobian_batch / nbk_pair_records_items give for the scene's pairs.  (Named like its siblings over edges and splines,
  * nbk_<what>_cloud_*: the nbk_cloud_* names are the cloud object's own set.)

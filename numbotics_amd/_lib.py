@@ -36,6 +36,8 @@ SYMBOLS = [
     "nbk_edge_cloud_continuous_batch", "nbk_edge_shape_motion_bounds_host",
     "nbk_spline_cloud_workspace_bytes", "nbk_spline_cloud_validity_batch",
     "nbk_spline_cloud_continuous_batch", "nbk_spline_shape_motion_bounds_host",
+    "nbk_frame_cloud_backproject", "nbk_frame_cloud_backproject_host", "nbk_frame_cloud_self_filter", "nbk_frame_cloud_self_filter_lds_bytes",
+    "nbk_frame_cloud_set_points", "nbk_frame_cloud_count",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -146,6 +148,13 @@ def load():
     lib.nbk_spline_cloud_validity_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, f64, f64, vp, i32, vp, vp, vp, vp, i64, vp]
     lib.nbk_spline_cloud_continuous_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, f64, i32, f64, f64, vp, i32, vp, vp, vp, vp]
     lib.nbk_spline_shape_motion_bounds_host.argtypes = [C.POINTER(ModelDesc), vp, i64, i32, i32, vp, vp]
+    lib.nbk_frame_cloud_backproject.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, f64, vp, f64, f64, vp, vp, vp]
+    lib.nbk_frame_cloud_backproject_host.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, f64, vp, f64, f64, vp, vp]
+    lib.nbk_frame_cloud_self_filter.argtypes = [vp, vp, vp, i64, f64, f64, vp, vp, vp]
+    lib.nbk_frame_cloud_self_filter_lds_bytes.argtypes = [i32]
+    lib.nbk_frame_cloud_self_filter_lds_bytes.restype = i64
+    lib.nbk_frame_cloud_set_points.argtypes = [vp, vp, vp, i64, f64, vp]
+    lib.nbk_frame_cloud_count.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

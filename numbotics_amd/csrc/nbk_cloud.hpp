@@ -12,7 +12,12 @@
 //   pts   [cap][3] sorted points
 // nbk_cloud_set_points: one memset (hdr + fill) | k_cloud_count | k_cloud_scan | k_cloud_scatter.  The order of the points of one
 // cell depends on the arrival of the scatter's atomics; no result does (a verdict is an OR; the clearance breaks ties by the original
-// index).
+// index).  With a mask (nbk_frame_cloud_set_points; the plain update is that call without one) N is the number of points kept: the
+// others are neither counted nor stored, and idx keeps the indices the caller's array has.
+//
+// Depth frames: k_cloud_backproject (one pixel per lane, the arithmetic of nbk_cloud_depth.hpp) and k_cloud_self_filter (the query
+// predicate at ONE configuration against many points, the selected shapes' cores once per workgroup in LDS) write the points and the
+// mask such an update takes.
 //
 // Queries: one configuration per lane, 64 per workgroup; the wave takes the selected robot shapes one after the other (Core.kind and
 // the hull a core names are wave-uniform this way), replays FK along the shape's joint mask from the lane's staged q row, builds the
@@ -36,8 +41,11 @@
 #pragma once
 #define NBK_GRID_FN __host__ __device__ inline
 #include "nbk_cloud_grid.hpp"
+#include "nbk_cloud_depth.hpp"
 
 namespace nbk {
+
+constexpr int SELF_FILTER_WGS_PER_CU = 4;      // k_cloud_self_filter: workgroups per CU of its bounded grid
 
 struct CloudHdr { int status; int n; double radius; };
 static_assert(sizeof(CloudHdr) == 16, "the update's memset covers the header and the counters in one piece");
@@ -55,10 +63,13 @@ struct CloudSel { unsigned long long w[4]; int all; };
 NBK_DEV bool cloud_selected(const CloudSel& s, int i) { return s.all != 0 || ((s.w[(i >> 6) & 3] >> (i & 63)) & 1ull) != 0ull; }
 
 // ---- the update ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_cloud_count(CloudGrid g, const double* __restrict__ pts, int n, int* __restrict__ cell_of,
-                                                     unsigned* __restrict__ fill, int* __restrict__ status) {
+// keep (optional, nbk_frame_cloud_set_points): point i takes part iff keep[i] != 0 -- a point that does not is neither counted nor
+// looked at (its coordinates may be anything), and k_cloud_scatter leaves it out by the same test
+__global__ __launch_bounds__(256) void k_cloud_count(CloudGrid g, const double* __restrict__ pts, int n, const uint8_t* __restrict__ keep,
+                                                     int* __restrict__ cell_of, unsigned* __restrict__ fill, int* __restrict__ status) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
+    if (keep != nullptr && keep[i] == 0) return;
     const double p[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
     const bool finite = (p[0] - p[0] == 0.0) && (p[1] - p[1] == 0.0) && (p[2] - p[2] == 0.0);
     if (!finite) atomicMax(status, 2);
@@ -67,9 +78,10 @@ __global__ __launch_bounds__(256) void k_cloud_count(CloudGrid g, const double* 
     atomicAdd(&fill[c], 1u);
 }
 
-// one workgroup: thread t owns the cells [t * per, (t + 1) * per); counts -> exclusive offsets in `start` and the scatter's cursors in `fill`
+// one workgroup: thread t owns the cells [t * per, (t + 1) * per); counts -> exclusive offsets in `start` and the scatter's cursors in `fill`.
+// The points the cloud holds are the points counted (all that were submitted, or those a mask kept): the scan's own total
 __global__ __launch_bounds__(1024) void k_cloud_scan(unsigned* __restrict__ fill, unsigned* __restrict__ start, int cells,
-                                                     CloudHdr* __restrict__ hdr, int n, double radius) {
+                                                     CloudHdr* __restrict__ hdr, double radius) {
     __shared__ unsigned part[1024];
     const int t = (int)threadIdx.x;
     const int per = (cells + 1023) / 1024;
@@ -93,20 +105,40 @@ __global__ __launch_bounds__(1024) void k_cloud_scan(unsigned* __restrict__ fill
         fill[c] = run;
         run += v;
     }
-    if (t == 0) { start[cells] = (unsigned)n; hdr->n = n; hdr->radius = radius; }
+    if (t == 0) { const unsigned total = part[1023]; start[cells] = total; hdr->n = (int)total; hdr->radius = radius; }
 }
 
-__global__ __launch_bounds__(256) void k_cloud_scatter(const double* __restrict__ pts, int n, const int* __restrict__ cell_of,
-                                                       unsigned* __restrict__ fill, double* __restrict__ sorted, int* __restrict__ idx,
-                                                       unsigned cap) {
+__global__ __launch_bounds__(256) void k_cloud_scatter(const double* __restrict__ pts, int n, const uint8_t* __restrict__ keep,
+                                                       const int* __restrict__ cell_of, unsigned* __restrict__ fill,
+                                                       double* __restrict__ sorted, int* __restrict__ idx, unsigned cap) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
+    if (keep != nullptr && keep[i] == 0) return;
     const unsigned pos = atomicAdd(&fill[cell_of[i]], 1u);
     if (pos >= cap) return;            // (cannot happen: the cursors start at the scan of these very counts)
     sorted[3 * (size_t)pos] = pts[3 * (size_t)i];
     sorted[3 * (size_t)pos + 1] = pts[3 * (size_t)i + 1];
     sorted[3 * (size_t)pos + 2] = pts[3 * (size_t)i + 2];
     idx[pos] = i;
+}
+
+// ---- depth frames (nbk_frame_cloud_backproject) -------------------------------------------------------------------------------------------
+// One pixel per lane, i = v * W + u its point; the arithmetic is depth_backproject_pixel's (nbk_cloud_depth.hpp).  T: the optical
+// frame's pose [3][4] in DEVICE memory, read when the kernel runs: a replayed graph follows a camera whose pose is rewritten in place.
+__global__ __launch_bounds__(256) void k_cloud_backproject(const void* __restrict__ depth, int depth_type, int W, int n, DepthCam cam,
+                                                           const double* __restrict__ T, double* __restrict__ pts,
+                                                           uint8_t* __restrict__ keep) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    double Tm[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) Tm[e] = T[e];
+    double w[3];
+    const bool valid = depth_backproject_pixel(cam, Tm, i % W, i / W, depth_pixel_value(depth, depth_type, i), w);
+    pts[3 * (size_t)i] = w[0];
+    pts[3 * (size_t)i + 1] = w[1];
+    pts[3 * (size_t)i + 2] = w[2];
+    keep[i] = valid ? 1 : 0;
 }
 
 // ---- the walk of one lane over the cells of a ball ----------------------------------------------------------------------------
@@ -271,6 +303,84 @@ __global__ __launch_bounds__(64) void k_cloud_validity(DevModel m, CloudDev cd, 
     if (mask_bytes != nullptr && active) {
         if (!accumulate) mask_bytes[b] = hit ? 1 : 0;
         else if (hit) mask_bytes[b] = 1;
+    }
+}
+
+// ---- the robot's own image in a frame (nbk_frame_cloud_self_filter) ----------------------------------------------------------------------
+// k_cloud_validity with the roles of the batch swapped: ONE configuration q0 and many points.  keep[i] goes from 1 to 0 iff, for some
+// selected shape s, the query predicate holds for (s, sphere of `radius` at p_i) with thr = padding -- cloud_row_hits' statements
+// in cloud_row_hits' operand order: tc = (padding + margin_s) + radius; rs = (tc + rho_s) + 0, free unless rs > 0 and
+// |c_s - p|^2 < rs^2; then cloud_collides(P, A, tc), the point first.  So a cloud of the points kept reads free at (q0, padding).
+//   preamble  one selected shape per lane (a stride of 256 over the shapes): the shape's frame at q0 (cloud_shape_frame: q0 is read
+//             from global memory, every lane the same addresses), build_core, the record into LDS (SelfFilterLds).  Divergent, and
+//             once per workgroup: the grid is bounded so that a workgroup serves many points
+//   loop      256 points per trip, a stride of the grid over the points.  Two stages, as in cloud_row_hits: each lane runs ahead
+//             over the records to its next shape that passes the bounding spheres (while the lanes agree on the record this is an
+//             LDS broadcast: four doubles), then the lanes that hold a candidate decide theirs side by side under one ballot.  The
+//             candidates of a trip may be DIFFERENT shapes: the hull support's scalar-cache path (rad < 0: every working lane
+//             holds that hull) is taken only when the ballot shows one shape, as k_cloud_records' second phase has it; the bits
+//             are the same either way.
+// A non-finite q0 removes nothing; a non-finite point never passes the bounding spheres and stays as it came.
+__global__ __launch_bounds__(256) void k_cloud_self_filter(DevModel m, CloudSel sel, int n_sel, const double* __restrict__ q0,
+                                                           const double* __restrict__ pts, int n, double radius, double padding,
+                                                           uint8_t* __restrict__ keep) {
+    extern __shared__ double lds[];
+    static_assert(sizeof(Core) == sizeof(double) * SelfFilterLds::CORE_LEN, "SelfFilterLds holds a Core per record");
+    const int tid = (int)threadIdx.x;
+    double* const rec = SelfFilterLds(0).rec(lds);
+    for (int c = 0; c < m.n_q; ++c)
+        if (!(q0[c] - q0[c] == 0.0)) return;                 // (every thread reads the same row: the whole grid leaves)
+    // the records, in device order: record k is the k-th selected shape (a selection has at most 256 shapes: four words)
+    for (int s = tid; s < m.n_rshapes; s += 256) {
+        if (!cloud_selected(sel, s)) continue;
+        int k = s;
+        if (sel.all == 0) {
+            k = __builtin_popcountll(sel.w[(s >> 6) & 3] & ((1ull << (s & 63)) - 1ull));
+            for (int w = 0; w < ((s >> 6) & 3); ++w) k += __builtin_popcountll(sel.w[w]);
+        }
+        Xf T;
+        cloud_shape_frame(m, s, q0, T);
+        Core A;
+        cloud_core_init(A);
+        build_core(m, s, T, A);
+        const double tc = (padding + A.margin) + radius;
+        const double rs = (tc + A.rho) + 0.0;
+        double* r = rec + (size_t)k * SelfFilterLds::REC_LEN;
+        *reinterpret_cast<Core*>(r) = A;
+        r[SelfFilterLds::TC_AT] = tc;
+        r[SelfFilterLds::RS2_AT] = rs > 0.0 ? rs * rs : -1.0;      // (a sum that is not positive: free, as the empty cell range of the queries)
+    }
+    __syncthreads();
+    Core P;
+    cloud_point_core(radius, P);
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < (int64_t)n; base += (int64_t)gridDim.x * 256) {
+        const int64_t i = base + tid;
+        const bool live = i < (int64_t)n && keep[i] != 0;
+        if (live) { P.c[0] = pts[3 * i]; P.c[1] = pts[3 * i + 1]; P.c[2] = pts[3 * i + 2]; }
+        bool hit = false;
+        int k = 0;
+        while (true) {
+            bool cand = false;
+            int kc = 0;
+            while (live && !hit && !cand && k < n_sel) {
+                const double* r = rec + (size_t)k * SelfFilterLds::REC_LEN;
+                double dc[3];
+                sub3(reinterpret_cast<const Core*>(r)->c, P.c, dc);
+                cand = dot3(dc, dc) < r[SelfFilterLds::RS2_AT];
+                kc = k++;
+            }
+            const unsigned long long cm = __builtin_amdgcn_ballot_w64(cand);
+            if (cm == 0ull) break;
+            const int k0 = __shfl(kc, __builtin_ctzll(cm));
+            const bool uniform = __builtin_amdgcn_ballot_w64(cand && kc != k0) == 0ull;
+            if (cand) {
+                const double* r = rec + (size_t)kc * SelfFilterLds::REC_LEN;
+                Core A = *reinterpret_cast<const Core*>(r);
+                if (uniform && A.kind == K_HULL) A.rad = -1.0;
+                if (cloud_collides(P, A, r[SelfFilterLds::TC_AT])) hit = true;
+            }
+        }
+        if (hit) keep[i] = 0;
     }
 }
 
@@ -868,11 +978,17 @@ static int cloud_selected_count(const nbk_model* m, const CloudSel& sel) {
 // this order: a selection on a model of more than 256 robot shapes is UNSUPPORTED (CloudSel holds 256 bits); the model's device and
 // the cloud's must be the current one; then `sel` is the selection.  n_sel (the certified entries, whose grid has one row of
 // workgroups per selected shape): their count, UNSUPPORTED above the 65535 rows a grid has.  -> the first code that fails
-static int32_t cloud_call_begin(const nbk_model* m, const nbk_cloud* c, const uint64_t* shape_bits, CloudSel& sel, int* n_sel = nullptr) {
+// Its sibling for a call that has a descriptor and no cloud (nbk_frame_cloud_self_filter) is the same without the cloud's device:
+// cloud_model_begin.
+static int32_t cloud_model_begin(const nbk_model* m, const uint64_t* shape_bits, CloudSel& sel) {
     if (shape_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
     NBK_DEVICE(m);
-    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
     sel = cloud_selection(m, shape_bits);
+    return NBK_OK;
+}
+static int32_t cloud_call_begin(const nbk_model* m, const nbk_cloud* c, const uint64_t* shape_bits, CloudSel& sel, int* n_sel = nullptr) {
+    { const int32_t rc = cloud_model_begin(m, shape_bits, sel); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
     if (n_sel != nullptr && (*n_sel = cloud_selected_count(m, sel)) > 65535) return NBK_ERR_UNSUPPORTED;
     return NBK_OK;
 }
@@ -936,24 +1052,38 @@ void nbk_cloud_destroy(nbk_cloud* c) {
     delete c;
 }
 
-int32_t nbk_cloud_set_points(nbk_cloud* c, const double* pts, int64_t N, double radius, void* stream) {
+int32_t nbk_frame_cloud_set_points(nbk_cloud* c, const double* pts, const uint8_t* keep, int64_t N, double radius, void* stream) {
     if (c == nullptr || N < 0 || N > c->capacity || !(radius >= 0.0) || (N > 0 && pts == nullptr)) return NBK_ERR_INVALID;
     { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
     hipStream_t st = (hipStream_t)stream;
     NBK_HIP(hipMemsetAsync(c->hdr, 0, sizeof(CloudHdr) + sizeof(unsigned) * (size_t)c->cells, st));
     const unsigned blocks = (unsigned)((N + 255) / 256);
     if (N > 0) {
-        hipLaunchKernelGGL(k_cloud_count, dim3(blocks), dim3(256), 0, st, c->g, pts, (int)N, c->cell_of, c->fill, &c->hdr->status);
+        hipLaunchKernelGGL(k_cloud_count, dim3(blocks), dim3(256), 0, st, c->g, pts, (int)N, keep, c->cell_of, c->fill, &c->hdr->status);
         NBK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, c->fill, c->start, c->cells, c->hdr, (int)N, radius);
+    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(1024), 0, st, c->fill, c->start, c->cells, c->hdr, radius);
     NBK_HIP(hipGetLastError());
     if (N > 0) {
-        hipLaunchKernelGGL(k_cloud_scatter, dim3(blocks), dim3(256), 0, st, pts, (int)N, (const int*)c->cell_of, c->fill, c->pts, c->idx,
-                           (unsigned)c->capacity);
+        hipLaunchKernelGGL(k_cloud_scatter, dim3(blocks), dim3(256), 0, st, pts, (int)N, keep, (const int*)c->cell_of, c->fill, c->pts,
+                           c->idx, (unsigned)c->capacity);
         NBK_HIP(hipGetLastError());
     }
     if (!stream_capturing(st)) { NBK_HIP(hipEventRecord(c->updated, st)); c->last_set = true; }
+    return NBK_OK;
+}
+
+int32_t nbk_cloud_set_points(nbk_cloud* c, const double* pts, int64_t N, double radius, void* stream) {
+    return nbk_frame_cloud_set_points(c, pts, nullptr, N, radius, stream);
+}
+
+int32_t nbk_frame_cloud_count(const nbk_cloud* c, int64_t* n) {
+    if (c == nullptr || n == nullptr) return NBK_ERR_INVALID;
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    if (c->last_set) NBK_HIP(hipEventSynchronize(c->updated));
+    int v = 0;
+    NBK_HIP(hipMemcpy(&v, &c->hdr->n, sizeof(int), hipMemcpyDeviceToHost));
+    *n = v;
     return NBK_OK;
 }
 
@@ -964,6 +1094,64 @@ int32_t nbk_cloud_status(const nbk_cloud* c, int32_t* status) {
     int v = 0;
     NBK_HIP(hipMemcpy(&v, &c->hdr->status, sizeof(int), hipMemcpyDeviceToHost));
     *status = v;
+    return NBK_OK;
+}
+
+// the argument rules the two back-projection entries share
+static bool backproject_args_ok(const void* depth, int32_t depth_type, int32_t H, int32_t W, const DepthCam& cam, const double* T,
+                                const double* pts, const uint8_t* keep) {
+    if (H < 0 || W < 0 || (int64_t)H * (int64_t)W > CLOUD_MAX_POINTS) return false;
+    if ((depth_type != 0 && depth_type != 1) || !depth_cam_valid(cam) || T == nullptr) return false;
+    return (int64_t)H * (int64_t)W == 0 || (depth != nullptr && pts != nullptr && keep != nullptr);
+}
+
+int32_t nbk_frame_cloud_backproject_host(const void* depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx, double fy,
+                                   double cx, double cy, const double* T, double z_min, double z_max, double* pts, uint8_t* keep) {
+    const DepthCam cam{depth_scale, fx, fy, cx, cy, z_min, z_max};
+    if (!backproject_args_ok(depth, depth_type, H, W, cam, T, pts, keep)) return NBK_ERR_INVALID;
+    const int64_t n = (int64_t)H * (int64_t)W;
+    for (int64_t i = 0; i < n; ++i)
+        keep[i] = depth_backproject_pixel(cam, T, (int)(i % W), (int)(i / W), depth_pixel_value(depth, depth_type, i), pts + 3 * i) ? 1 : 0;
+    return NBK_OK;
+}
+
+int32_t nbk_frame_cloud_backproject(const void* depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx, double fy,
+                              double cx, double cy, const double* T, double z_min, double z_max, double* pts, uint8_t* keep,
+                              void* stream) {
+    const DepthCam cam{depth_scale, fx, fy, cx, cy, z_min, z_max};
+    if (!backproject_args_ok(depth, depth_type, H, W, cam, T, pts, keep)) return NBK_ERR_INVALID;
+    if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
+    const int n = H * W;
+    if (n == 0) return NBK_OK;
+    hipLaunchKernelGGL(k_cloud_backproject, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, depth, (int)depth_type,
+                       (int)W, n, cam, T, pts, keep);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_frame_cloud_self_filter_lds_bytes(int32_t n_shapes) {
+    if (n_shapes < 0 || !SelfFilterLds(n_shapes).fits()) return -1;
+    return (int64_t)SelfFilterLds(n_shapes).bytes();
+}
+
+int32_t nbk_frame_cloud_self_filter(const nbk_model* m, const double* q0, const double* pts, int64_t N, double radius, double padding,
+                              const uint64_t* shape_bits, uint8_t* keep, void* stream) {
+    if (m == nullptr || q0 == nullptr || N < 0 || N > CLOUD_MAX_POINTS || !(radius >= 0.0) || padding != padding ||
+        (N > 0 && (pts == nullptr || keep == nullptr))) return NBK_ERR_INVALID;
+    CloudSel sel;
+    { const int32_t rc = cloud_model_begin(m, shape_bits, sel); if (rc != NBK_OK) return rc; }
+    const int n_sel = cloud_selected_count(m, sel);
+    const SelfFilterLds L(n_sel);
+    if (!L.fits()) return NBK_ERR_UNSUPPORTED;
+    if (N == 0 || n_sel == 0) return NBK_OK;
+    int dev = 0, cus = 0;
+    NBK_HIP(hipGetDevice(&dev));
+    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // a bounded grid: every workgroup pays the preamble (the selected shapes' cores at q0) once and then strides over the points
+    const int64_t want = (N + 255) / 256, most = (int64_t)(cus > 0 ? cus : 1) * SELF_FILTER_WGS_PER_CU;
+    hipLaunchKernelGGL(k_cloud_self_filter, dim3((unsigned)(want < most ? want : most)), dim3(256), L.bytes(), (hipStream_t)stream, m->d, sel,
+                       n_sel, q0, pts, (int)N, radius, padding, keep);
+    NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
 

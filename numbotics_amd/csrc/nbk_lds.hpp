@@ -108,6 +108,16 @@ struct QSlabLds {
     NBK_HD explicit QSlabLds(int n_q, int min_rows = 0) : rows(n_q > min_rows ? n_q : min_rows) {}
     NBK_LDS_TOTAL(sizeof(double) * LDS_WAVE * (size_t)rows)
 };
+// k_cloud_self_filter: one record per selected robot shape, [n_sel][REC_LEN]: the shape's core at q0 as the kernel's Core struct
+// (CORE_LEN doubles: nbk_cloud.hpp holds sizeof(Core) against it) | tc | the squared bounding-sphere sum (-1: the sum is not positive).
+// A model whose selected shapes do not fit is refused by the entry (room for one record at least)
+struct SelfFilterLds {
+    static constexpr int CORE_LEN = 19, REC_LEN = CORE_LEN + 2, TC_AT = CORE_LEN, RS2_AT = CORE_LEN + 1;
+    int rec_len;
+    NBK_HD explicit SelfFilterLds(int n_sel) : rec_len(REC_LEN * (n_sel > 0 ? n_sel : 1)) {}
+    NBK_HD double* rec(double* base) const { return base; }
+    NBK_LDS_TOTAL(sizeof(double) * (size_t)rec_len)
+};
 // k_narrow*: q rows [NARROW_T][n_q] | the scene's hull vertices [hull_blob_n] when they fit HULL_LDS_MAX
 struct NarrowLds {
     int q_len, hull_blob_n;

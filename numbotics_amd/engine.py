@@ -557,6 +557,33 @@ class DeviceModel:
             return out
         return qs.out(words) if packed else qs.out(mask.bool())
 
+    def cloud_self_filter(self, points, q0, radius, padding=0.0, keep=None, shapes=None):
+        """Take the robot's own image out of a frame's points (nbk_frame_cloud_self_filter): ``keep[i]`` goes to 0 iff point i, as a
+        sphere of ``radius``, is closer than ``padding`` to a selected robot shape at the ONE configuration ``q0`` -- the
+        predicate of ``cloud_validity`` with threshold = padding, so a cloud of the points kept reads free there, exactly.
+        ``points``: (N, 3) float64, NumPy or a CUDA tensor; ``q0``: (n_q,), NumPy or a float64 CUDA tensor (read when the kernel
+        runs).  ``keep``: an (N,) uint8 CUDA tensor to work on in place (zeros stay zeros) -- it is returned; without it every
+        point starts kept and the result is a fresh uint8 tensor, or a NumPy bool array for NumPy ``points``.  ``shapes``: as
+        ``cloud_validity``.  A non-finite ``q0`` removes nothing.  No allocation and capturable when everything is a CUDA tensor."""
+        bits = self._shape_bits(shapes)                 # (argument errors come before the device is touched)
+        torch = _require_gpu()
+        ps = _Staged(points, 3, "points")
+        qs = _Staged(q0, self.n_q)
+        if qs.B != 1:
+            raise ValueError(f"q0 must be one configuration of {self.n_q} values")
+        if keep is None:
+            k = torch.ones((ps.B,), dtype=torch.uint8, device=ps.device)
+        else:
+            k = keep
+            if not (torch.is_tensor(k) and k.is_cuda and k.dtype == torch.uint8 and k.is_contiguous() and tuple(k.shape) == (ps.B,)):
+                raise ValueError(f"keep must be a contiguous uint8 CUDA tensor of shape ({ps.B},)")
+        _lib.check(self._lib.nbk_frame_cloud_self_filter(
+            self._h, qs.t.data_ptr(), ps.t.data_ptr() if ps.B > 0 else None, ps.B, float(radius), float(padding), _host_ptr(bits),
+            k.data_ptr() if ps.B > 0 else None, self._stream()), "nbk_frame_cloud_self_filter")
+        if keep is not None:
+            return keep
+        return k.cpu().numpy().astype(bool) if ps.numpy else k
+
     def cloud_clearance(self, cloud, q, d_max, shapes=None):
         """Per configuration the smallest signed distance to ``cloud`` over the selected robot shapes when it is below ``d_max``
         -> (distance (B,), robot shape (B,) int32, point index (B,) int32); +inf, -1, -1 where nothing is closer than ``d_max``;

@@ -578,6 +578,27 @@ class Arm(Robot):
         mask = dev.cloud_validity(cloud, q.reshape(-1, self.dof), threshold, shapes=shapes)
         return mask.reshape(tuple(q.shape[:-1]))
 
+    def cloud_self_filter(self, points, q, radius: float, padding: float = 0.0, keep=None, links=None, ignore_links=()):
+        """Which of a depth frame's ``points`` (N, 3) are NOT the arm's own image at the configuration ``q`` the frame was taken at:
+        ``keep[i]`` goes to 0 iff point i, a sphere of ``radius``, is closer than ``padding`` to a link shape -- the verdict
+        ``in_collision_with_cloud(q, cloud, padding)`` would give for that point alone, so a cloud updated with
+        ``update(points, keep=keep)`` reads free at ``q``, exactly.  ``links``: only these links (objects or names; default: all);
+        ``ignore_links``: links left out of the filter, whose image stays in the cloud.  ``keep``, the return value and the array
+        kinds: as ``DeviceModel.cloud_self_filter``."""
+        sm, dev = self._scene_device()
+        shapes = self._cloud_shapes(sm, ignore_links)
+        if links is not None:
+            names = {getattr(l, "_name", l) for l in links}
+            known = {l._name for l in sm.links}
+            for n in names:
+                if n not in known:
+                    raise ValueError(f"Link {n} not found in chain")
+            shapes = [s for s in (range(sm.n_rshapes) if shapes is None else shapes) if sm.links[sm.rshape_link[s]]._name in names]
+        q = q.reshape(-1) if hasattr(q, "reshape") else np.asarray(q, dtype=np.float64).reshape(-1)
+        if q.shape[0] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        return dev.cloud_self_filter(points, q, radius, padding, keep=keep, shapes=shapes)
+
     def cloud_clearance(self, q, cloud, d_max: float, ignore_links=()):
         """(distance, link name, point index) per configuration: the smallest signed distance between a link shape and a point of
         ``cloud`` when it is below ``d_max`` (else inf, None, -1; NaN, None, -1 for a non-finite configuration).  ``q`` is

@@ -1,0 +1,149 @@
+"""Inputs and references of the depth-frame tests (tests/test_cloud_depth_host.py, tests/test_gpu_cloud_depth.py).
+
+Back-projection: ``backproject_ref`` restates the arithmetic contract of include/nbk.h in NumPy, one rounded float64 operation per
+step, in the contract's order.  Self-filter: ``filter_ref`` is the CPU oracle as it is -- point i is removed iff the oracle reports a
+collision for the robot against that ONE point as a sphere world shape (tests/cloud_cases.py, ``cloud_model``) at (q0, padding)."""
+import os
+
+import numpy as np
+
+from cloud_cases import scan, cloud_model
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TREE_URDF = os.path.join(ROOT, "tests", "models", "tree_gripper.urdf")
+# the robots of tests/test_gpu_cloud.py
+ROBOTS = [("c1", True), ("c1", False), ("c2m", True), ("c2m", False), ("tree", True), ("tree", False), ("k9", True)]
+ROBOT_IDS = [f"{n}-{'bullet' if m else 'sharp'}" for n, m in ROBOTS]
+# (radius, padding): the three pairs the band was drawn for, and one negative padding
+FILTER_PARAMS = ((0.01, 0.02), (0.0, 0.0), (0.005, 0.05), (0.01, -0.005))
+# half width of the box around each link frame the points near the robot are drawn in
+BOX = {"c1": 0.07, "c2m": 0.07, "tree": 0.07, "k9": 0.07}
+PER_SHAPE = 12
+SHAPES = ((1, 1), (1, 64), (5, 7), (17, 33))        # (H, W): 1x1, 64x1, 7x5 and 33x17 images (width x height)
+
+
+def robot(name, margins, tmp):
+    """-> (arm, chain, things to keep alive, q0): the robot of tests/test_gpu_cloud.py and the configuration the frame is taken at."""
+    from numbotics_amd.scenes import build_scene, sample_q
+    if name == "k9":
+        import long_chain_cases as lc
+        arm, chain, obs = lc.case("k9", tmp)
+        return arm, chain, obs, lc.sample(chain, 4, 5)[2]
+    if name == "tree":
+        from numbotics_amd.physics import GraphChain
+        from numbotics_amd.robots import Arm
+        chain = GraphChain.from_urdf(TREE_URDF)
+        return Arm(chain, bullet_margins=margins), chain, [], sample_q(chain, 4, seed=5)[2]
+    arm, chain, obs = build_scene(name, bullet_margins=margins)
+    return arm, chain, obs, sample_q(chain, 4, seed=5)[2]
+
+
+def frame_points(name, sm, q0):
+    """For each robot shape PER_SHAPE points uniform in a +-BOX[name] box around the frame origin of the shape's link at q0 (the
+    oracle's FK), then the 64 points of ``scan(64, seed=1)``."""
+    from oracle.cpu_oracle import Oracle
+    rng = np.random.default_rng(11)
+    orc = Oracle(sm)
+    out = []
+    for s in range(sm.n_rshapes):
+        o = orc.fk(np.asarray(q0, dtype=np.float64).reshape(1, -1), sm.links[sm.rshape_link[s]]._name)[0, :3, 3]
+        out.append(o + rng.uniform(-BOX[name], BOX[name], (PER_SHAPE, 3)))
+    out.append(scan(64, seed=1))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def filter_ref(sm, pts, r, q0, pad, shapes=None):
+    """keep (N,) bool by the oracle: point i stays iff the robot at q0 is NOT closer than ``pad`` to the sphere of radius r at it."""
+    from oracle.cpu_oracle import Oracle
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    q0 = np.asarray(q0, dtype=np.float64).reshape(1, -1)
+    keep = np.ones((pts.shape[0],), dtype=bool)
+    if shapes is not None and len(shapes) == 0:
+        return keep
+    for i in range(pts.shape[0]):
+        keep[i] = not Oracle(cloud_model(sm, pts[i:i + 1], r, shapes)).validity(q0, pad)[0]
+    return keep
+
+
+def in_band(keep_ref, what):
+    """The condition on the reference: it removes between 5 % and 70 % of the points."""
+    f = 1.0 - float(np.mean(keep_ref))
+    assert 0.05 <= f <= 0.70, f"{what}: the reference removes {f:.3f} of the points -- not a mixed case"
+    return f
+
+
+# ---- back-projection ---------------------------------------------------------------------------------------------------------------
+def backproject_ref(depth, intr, T, depth_scale=1.0, z_min=0.0, z_max=np.inf):
+    """(points (H * W, 3), keep (H * W,) uint8) by the contract: z = (double)d * scale; xc = (((double)u - cx) * z) / fx; yc likewise;
+    w[e] = ((T[e][0] * xc + T[e][1] * yc) + T[e][2] * z) + T[e][3]; valid iff z - z == 0, z > z_min, z <= z_max; a hole is (0, 0, 0)."""
+    d = np.asarray(depth)
+    if d.dtype == np.int16:
+        d = d.view(np.uint16)
+    H, W = d.shape
+    fx, fy, cx, cy = (np.float64(x) for x in intr)
+    T = np.asarray(T, dtype=np.float64)[:3, :4]
+    with np.errstate(all="ignore"):
+        z = d.astype(np.float64).reshape(-1) * np.float64(depth_scale)
+        u = np.tile(np.arange(W, dtype=np.float64), H)
+        v = np.repeat(np.arange(H, dtype=np.float64), W)
+        xc = ((u - cx) * z) / fx
+        yc = ((v - cy) * z) / fy
+        w = np.stack([((T[e, 0] * xc + T[e, 1] * yc) + T[e, 2] * z) + T[e, 3] for e in range(3)], axis=1)
+        keep = ((z - z) == 0.0) & (z > np.float64(z_min)) & (z <= np.float64(z_max))
+    w[~keep] = 0.0
+    return np.ascontiguousarray(w), keep.astype(np.uint8)
+
+
+def camera_pose():
+    """A rotated, translated optical pose (4, 4): rotations about all three axes by angles that are no multiple of anything."""
+    a, b, c = 0.3, -0.7, 1.1
+    Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+    Ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
+    Rz = np.array([[np.cos(c), -np.sin(c), 0], [np.sin(c), np.cos(c), 0], [0, 0, 1]])
+    T = np.eye(4)
+    T[:3, :3] = Rz @ Ry @ Rx
+    T[:3, 3] = [0.31, -0.42, 0.87]
+    return T
+
+
+Z_MIN, Z_MAX = 0.25, 3.0
+
+
+def depth_image(H, W, kind, seed=0):
+    """An (H, W) image with holes of every kind at fixed places (as far as the image has pixels for them): 0, z == z_min exactly,
+    z > z_max and -- float32 -- NaN and +inf; the rest valid depths.  kind "f32": metres; "u16": millimetres (depth_scale 0.001 --
+    250 raw units times 0.001 is the double 0.25 exactly: z == z_min)."""
+    rng = np.random.default_rng(seed + 7 * H + W)
+    n = H * W
+    z = rng.uniform(0.3, 2.9, n)
+    if kind == "f32":
+        d = z.astype(np.float32)
+        holes = [np.float32(0.0), np.float32(Z_MIN), np.float32(3.5), np.float32(np.nan), np.float32(np.inf), np.float32(-1.0)]
+    else:
+        d = np.round(z * 1000.0).astype(np.uint16)
+        holes = [np.uint16(0), np.uint16(250), np.uint16(3001), np.uint16(65535)]
+    for k, h in enumerate(holes):
+        if 1 + k < n:
+            d[1 + k] = h
+    return np.ascontiguousarray(d.reshape(H, W))
+
+
+def intrinsics(H, W):
+    return (0.9 * W + 1.5, 1.1 * W + 0.25, (W - 1) / 2.0 + 0.125, (H - 1) / 2.0 - 0.375)
+
+
+def project_points(pts, T, intr, H, W):
+    """A synthetic float32 frame of world points: each point that falls on a pixel of the (H, W) optical camera at pose T writes its
+    z there (the nearest wins); the other pixels stay 0."""
+    T = np.asarray(T, dtype=np.float64)
+    R, t = T[:3, :3], T[:3, 3]
+    pc = (np.asarray(pts, dtype=np.float64) - t) @ R
+    fx, fy, cx, cy = intr
+    d = np.zeros((H, W), dtype=np.float32)
+    for x, y, z in pc:
+        if z <= 0.05:
+            continue
+        u, v = int(np.round(fx * x / z + cx)), int(np.round(fy * y / z + cy))
+        if 0 <= u < W and 0 <= v < H and (d[v, u] == 0 or z < d[v, u]):
+            d[v, u] = np.float32(z)
+    return d

@@ -1,0 +1,154 @@
+"""Depth frames to point clouds, the part that needs no device (include/nbk.h: nbk_frame_cloud_backproject*, nbk_frame_cloud_self_filter*,
+nbk_frame_cloud_set_points, nbk_frame_cloud_count): the back-projection's arithmetic on the host against its NumPy restatement, bit for
+bit; the camera conventions; the argument rules of every new entry; the self-filter's LDS layout against its limit; and the condition
+the GPU tests put on their reference (tests/test_gpu_cloud_depth.py), checked here for every robot they use."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import cloud_depth_cases as dc
+from numbotics_amd import _lib
+from numbotics_amd.physics import intrinsics_from_fov
+from numbotics_amd.physics.pointcloud import backproject_host, optical_pose
+
+INVALID, UNSUPPORTED = -1, -4
+
+
+def _bits_equal(a, b, what):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, f"{what}: {a.shape} {a.dtype} vs {b.shape} {b.dtype}"
+    assert a.tobytes() == b.tobytes(), f"{what}: bits differ at {np.flatnonzero((a != b) & ~((a != a) & (b != b)))[:8]}"
+
+
+@pytest.mark.parametrize("kind", ["f32", "u16"])
+@pytest.mark.parametrize("H,W", dc.SHAPES, ids=[f"{w}x{h}" for h, w in dc.SHAPES])
+def test_backproject_host_is_the_restatement(H, W, kind):
+    d = dc.depth_image(H, W, kind)
+    scale = 1.0 if kind == "f32" else 0.001
+    intr, T = dc.intrinsics(H, W), dc.camera_pose()
+    pts, keep = backproject_host(d, intr, T, depth_scale=scale, z_min=dc.Z_MIN, z_max=dc.Z_MAX)
+    rp, rk = dc.backproject_ref(d, intr, T, scale, dc.Z_MIN, dc.Z_MAX)
+    _bits_equal(keep, rk, f"{W}x{H} {kind}: keep")
+    _bits_equal(pts, rp, f"{W}x{H} {kind}: points")
+    assert np.all(pts[keep == 0] == 0.0) and not np.any(np.signbit(pts[keep == 0])), "a hole comes back as +0.0 three times"
+    if H * W > 8:
+        # every kind of hole is in the image and is a hole; the pixel before them is none
+        n_holes = 6 if kind == "f32" else 3           # (65535 mm is beyond z_max too)
+        assert keep[0] == 1 and not keep[1:1 + n_holes].any() and 0 < keep.sum() < H * W
+        if kind == "f32":
+            flat = d.reshape(-1)
+            assert flat[1] == 0 and flat[2] == np.float32(dc.Z_MIN) and flat[3] > dc.Z_MAX and np.isnan(flat[4]) and np.isposinf(flat[5])
+        else:
+            assert np.float64(250) * np.float64(0.001) == dc.Z_MIN, "250 raw units are z_min exactly"
+
+
+def test_backproject_host_signed_sixteen_bits_and_a_lone_hole():
+    """int16 carries the same raw bits as uint16 (a value above 32767 is NOT negative); a 1x1 image that is a hole."""
+    d = np.array([[40000, 1200, 0]], dtype=np.uint16)
+    intr, T = dc.intrinsics(1, 3), dc.camera_pose()
+    a = backproject_host(d, intr, T, depth_scale=0.0001)
+    b = backproject_host(d.view(np.int16), intr, T, depth_scale=0.0001)
+    _bits_equal(a[0], b[0], "int16 view: points")
+    _bits_equal(a[1], b[1], "int16 view: keep")
+    _bits_equal(a[0], dc.backproject_ref(d, intr, T, 0.0001)[0], "uint16 above 32767")
+    assert list(a[1]) == [1, 1, 0] and a[0][0, :].any()
+    pts, keep = backproject_host(np.zeros((1, 1), dtype=np.float32), (1.0, 1.0, 0.0, 0.0), np.eye(4))
+    assert keep.tolist() == [0] and pts.tolist() == [[0.0, 0.0, 0.0]]
+    # z_max = +inf by default: a large finite depth counts, +inf never does
+    pts, keep = backproject_host(np.array([[1e30, np.inf]], dtype=np.float32), (1.0, 1.0, 0.0, 0.0), np.eye(4))
+    assert keep.tolist() == [1, 0]
+
+
+def test_numbotics_frame_is_the_permuted_optical_pose():
+    """frame="numbotics": x forward, z up.  The optical axes are x = -y_cam, y = -z_cam, z = x_cam: the pose's columns moved and
+    negated, exactly."""
+    T = dc.camera_pose()
+    P = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])       # columns: the optical axes in camera coordinates
+    To = optical_pose(T, "numbotics")
+    expect = np.concatenate((np.stack((-T[:3, 1], -T[:3, 2], T[:3, 0]), axis=1), T[:3, 3:4]), axis=1)
+    _bits_equal(To, expect, "the permuted pose")
+    assert np.allclose(To[:, :3], T[:3, :3] @ P) and abs(np.linalg.det(To[:, :3]) - 1.0) < 1e-12
+    d = dc.depth_image(17, 33, "f32")
+    intr = dc.intrinsics(17, 33)
+    a = backproject_host(d, intr, T, z_min=dc.Z_MIN, z_max=dc.Z_MAX, frame="numbotics")
+    b = backproject_host(d, intr, To, z_min=dc.Z_MIN, z_max=dc.Z_MAX, frame="optical")
+    _bits_equal(a[0], b[0], "numbotics frame: points")
+    _bits_equal(a[1], b[1], "numbotics frame: keep")
+    # the centre pixel of a camera at the origin looking along world x lands on the x axis
+    pts, keep = backproject_host(np.full((3, 3), 2.0, dtype=np.float32), intrinsics_from_fov(3, 3, 60.0), np.eye(4), frame="numbotics")
+    assert keep.all() and pts[4].tolist() == [2.0, 0.0, 0.0]
+    assert pts[0][1] > 0 and pts[0][2] > 0, "the first pixel is up (z) and to the left (+y) of a camera that looks along x"
+    with pytest.raises(ValueError):
+        optical_pose(T, "opengl")
+
+
+def test_intrinsics_from_fov():
+    fx, fy, cx, cy = intrinsics_from_fov(640, 480, 60.0)
+    assert fy == 240.0 / np.tan(np.deg2rad(60.0) / 2.0) and fx == fy
+    assert (cx, cy) == (319.5, 239.5)
+    fx, fy, cx, cy = intrinsics_from_fov(33, 17, 90.0)
+    assert abs(fy - 8.5) < 1e-12 and fx == fy and (cx, cy) == (16.0, 8.0)
+    # the top edge of the image is fov / 2 above the axis: pixel row -0.5
+    assert abs(np.arctan((8.0 + 0.5) / fy) - np.deg2rad(45.0)) < 1e-12
+
+
+def test_argument_rules_need_no_device():
+    lib = _lib.load()
+    buf = np.zeros((64,), dtype=np.float64)            # stands for any non-null pointer: no rule below reads through one
+    p = buf.ctypes.data
+    ok = dict(depth=p, depth_type=0, H=2, W=3, scale=1.0, fx=1.0, fy=1.0, cx=0.0, cy=0.0, T=p, z_min=0.0, z_max=1.0, pts=p, keep=p)
+
+    def bp(host, **kw):
+        a = dict(ok, **kw)
+        args = [a["depth"], a["depth_type"], a["H"], a["W"], a["scale"], a["fx"], a["fy"], a["cx"], a["cy"], a["T"], a["z_min"], a["z_max"],
+                a["pts"], a["keep"]]
+        return lib.nbk_frame_cloud_backproject_host(*args) if host else lib.nbk_frame_cloud_backproject(*(args + [None]))
+
+    bad = [dict(depth=None), dict(T=None), dict(pts=None), dict(keep=None), dict(H=-1), dict(W=-1), dict(H=4097, W=4096),
+           dict(depth_type=2), dict(depth_type=-1), dict(fx=0.0), dict(fx=-1.0), dict(fx=float("nan")), dict(fy=0.0), dict(fy=float("nan")),
+           dict(scale=0.0), dict(scale=-0.001), dict(scale=float("nan"))]
+    for host in (True, False):
+        for kw in bad:
+            assert bp(host, **kw) == INVALID, (host, kw)
+    assert bp(True) == 0 and bp(True, H=0, depth=None, pts=None, keep=None) == 0
+    assert bp(True, H=4096, W=4096, depth=None) == INVALID, "2^24 pixels pass the size rule and fall to the next one"
+    # the self-filter: m, q0, pts, N, radius, padding, shape_bits, keep, stream
+    sf = lib.nbk_frame_cloud_self_filter
+    nan = float("nan")
+    for args in ((None, p, p, 4, 0.01, 0.0, None, p, None), (p, None, p, 4, 0.01, 0.0, None, p, None), (p, p, None, 4, 0.01, 0.0, None, p, None),
+                 (p, p, p, 4, 0.01, 0.0, None, None, None), (p, p, p, -1, 0.01, 0.0, None, p, None), (p, p, p, (1 << 24) + 1, 0.01, 0.0, None, p, None),
+                 (p, p, p, 4, -0.01, 0.0, None, p, None), (p, p, p, 4, nan, 0.0, None, p, None), (p, p, p, 4, 0.01, nan, None, p, None)):
+        assert sf(*args) == INVALID, args
+    # the masked update and the count
+    assert lib.nbk_frame_cloud_set_points(None, p, p, 4, 0.01, None) == INVALID
+    assert lib.nbk_frame_cloud_set_points(p, p, p, -1, 0.01, None) == INVALID
+    n = C.c_int64(7)
+    assert lib.nbk_frame_cloud_count(None, C.byref(n)) == INVALID and lib.nbk_frame_cloud_count(p, None) == INVALID and n.value == 7
+
+
+def test_self_filter_lds_layout_against_its_limit():
+    """One record of 21 doubles per selected shape (the core's 19, tc, the squared bounding-sphere sum); 160 KB hold 975 of them."""
+    f = _lib.load().nbk_frame_cloud_self_filter_lds_bytes
+    LDS_MAX = 160 * 1024
+    assert f(0) == 168 and f(1) == 168, "room for one record at least"
+    for n in (2, 11, 72, 256, 257, 975):
+        assert f(n) == 168 * n <= LDS_MAX, n
+    assert 168 * 976 > LDS_MAX
+    for n in (976, 1024, 1 << 20, -1):
+        assert f(n) == -1, n
+
+
+@pytest.mark.parametrize("name,margins", dc.ROBOTS, ids=dc.ROBOT_IDS)
+def test_reference_band(fresh_world, tmp_path, name, margins):
+    """The condition tests/test_gpu_cloud_depth.py asserts before it compares: the oracle removes between 5 % and 70 % of the frame's
+    points for every (radius, padding), so no comparison passes on an all-kept or all-removed mask."""
+    arm, chain, alive, q0 = dc.robot(name, margins, tmp_path)
+    sm = arm.scene_model()
+    pts = dc.frame_points(name, sm, q0)
+    assert pts.shape == (sm.n_rshapes * dc.PER_SHAPE + 64, 3)
+    seen = set()
+    for r, pad in dc.FILTER_PARAMS:
+        keep = dc.filter_ref(sm, pts, r, q0, pad)
+        seen.add(round(dc.in_band(keep, f"{name} r={r} pad={pad}"), 6))
+    assert len(seen) >= 3, f"radius and padding matter: {seen}"

@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records,depth] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -36,6 +36,13 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
                 DeviceModel.cloud_records per configuration with witness and rows, with the witness alone and with neither, windows
                 alternating with the clearance call's; then per (configuration, shape) with rows.  Each line has the ratio to the
                 clearance windows it alternated with.  (profiles/cloud_records_time.log)
+    depth       (only when asked for) c2 and synthetic float32 frames of 640x480 and 1280x720 pixels from a camera 1.6 m in front of
+                the arm, looking along x (vertical field of view 50 degrees): a wall behind the arm, a column of pixels on the arm
+                itself at the configuration the frame is taken at, about 15 % holes (zeros).  At least 10 windows each:
+                backproject; DeviceModel.cloud_self_filter at the cloud's radius and padding 0.02, every shape (with its grid, and
+                beside it the same launch for one workgroup's 256 points: the preamble and the launch, little else);
+                PointCloud.update(points, keep); the whole update_from_depth; and PointCloud.update on the surviving points as a
+                ready array -- the yardstick.  (profiles/cloud_depth_time.log)
 """
 import argparse
 import os
@@ -259,6 +266,53 @@ def records_part(dev, sm, shapes, q5, reps):
         say(f"  {name:36s} {fmt(tr)}   clearance beside it {fmt(tc)}   ratio {tr[0] / tc[0]:.2f}x{share}")
 
 
+def depth_part(arm, dev, sm, chain, reps):
+    from numbotics_amd.physics import backproject, intrinsics_from_fov
+    reps = max(reps, 10)
+    pad = 0.02
+    q0 = sample_q(chain, 4, seed=5)[2]
+    qt = torch.from_numpy(q0).cuda()
+    cam = np.array([[1.0, 0.0, 0.0, -1.6], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.55], [0.0, 0.0, 0.0, 1.0]])
+    Tt = torch.from_numpy(cam).cuda()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    say(f"depth: c2 ({sm.n_rshapes} shapes, all filtered), radius {RADIUS}, padding {pad}, camera at (-1.6, 0, 0.55) looking along x; {cus} CUs; >= {reps} windows")
+    for W, H in ((640, 480), (1280, 720)):
+        rng = np.random.default_rng(W)
+        intr = intrinsics_from_fov(W, H, 50.0)
+        u, v = np.meshgrid(np.arange(W), np.arange(H))
+        z = np.full((H, W), 2.05) + rng.uniform(-0.01, 0.01, (H, W))                 # the wall
+        col = np.abs((u - intr[2]) / intr[0]) < 0.06                                   # the arm's column: 0.1 m either side at 1.6 m
+        z[col] = 1.6 + rng.uniform(-0.06, 0.06, int(col.sum()))
+        z[rng.uniform(size=(H, W)) < 0.15] = 0.0
+        dt = torch.from_numpy(z.astype(np.float32)).cuda()
+        n = H * W
+        pts, keep = backproject(dt, intr, Tt, frame="numbotics")
+        valid = int(keep.sum())
+        lo, hi = pts[keep.bool()].min(0).values.cpu().numpy(), pts[keep.bool()].max(0).values.cpu().numpy()
+        cloud = PointCloud(np.zeros((0, 3)), RADIUS, bounds=(lo, hi), capacity=n)
+        k2 = keep.clone()
+        dev.cloud_self_filter(pts, qt, RADIUS, pad, keep=k2)
+        left = int(k2.sum())
+        surv = pts[k2.bool()].contiguous()
+        grid = min((n + 255) // 256, 4 * cus)
+        say(f"  {W}x{H}: {n} pixels, {valid} valid ({1 - valid / n:.3f} holes), the filter removes {valid - left} ({(valid - left) / valid:.3f}); "
+            f"cell {cloud.cell:.4f}, grid {tuple(int(d) for d in cloud.dims)}; filter grid {grid} workgroups of 256")
+        say(f"    backproject                         {fmt(timed(lambda: backproject(dt, intr, Tt, frame='numbotics', out=(pts, keep)), reps))}")
+
+        def filt():
+            k2.copy_(keep)
+            dev.cloud_self_filter(pts, qt, RADIUS, pad, keep=k2)
+        say(f"    self-filter (with the mask's copy)  {fmt(timed(filt, reps))}")
+        say(f"    the mask's copy alone               {fmt(timed(lambda: k2.copy_(keep), reps))}")
+        k1, p1 = torch.ones((256,), dtype=torch.uint8, device='cuda'), pts[:256].contiguous()
+        say(f"    self-filter, 256 points (1 workgroup) {fmt(timed(lambda: dev.cloud_self_filter(p1, qt, RADIUS, pad, keep=k1), reps))}")
+        say(f"    update(points, keep)                {fmt(timed(lambda: cloud.update(pts, keep=k2), reps))}")
+        say(f"    update_from_depth, all three        {fmt(timed(lambda: cloud.update_from_depth(dt, intr, Tt, arm=arm, q=qt, padding=pad, frame='numbotics'), reps))}")
+        assert cloud.count() == left
+        say(f"    update({left} surviving points)      {fmt(timed(lambda: cloud.update(surv), reps))}")
+        say(f"    update(all {n} pixels, no mask)     {fmt(timed(lambda: cloud.update(pts), reps))}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -330,6 +384,8 @@ def main():
         splines_part(dev, chain, shapes, a.reps)
     if "records" in only:
         records_part(dev, sm, shapes, q5, a.reps)
+    if "depth" in only:
+        depth_part(arm, dev, sm, chain, a.reps)
 
 
 if __name__ == "__main__":
