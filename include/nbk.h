@@ -529,6 +529,62 @@ int32_t nbk_frame_cloud_set_points(nbk_cloud *c, const double *pts /* DEVICE [N]
 int32_t nbk_frame_cloud_count(const nbk_cloud *c, int64_t *n);         /* synchronous: the points held */
 
 /*
+ * Fused frames (additive): several depth frames in one cloud.  The caller keeps a STORE of M point slots in device memory -- store_pts
+ * [M][3], store_keep [M]: slot j is held iff store_keep[j] != 0 -- and makes the cloud of it with nbk_frame_cloud_set_points at
+ * N = M.  That update files a point under its index in the submitted array, so the `point` of every clearance or proximity record
+ * is a SLOT, and a point keeps its slot for as long as it lives.  Three stream-ordered steps maintain the store; like the entries
+ * above they allocate nothing, synchronise nothing and may be captured.  They write masks, indices and copies of doubles: every
+ * result is exact.  One frame: backproject | self_filter on the frame | carve | (self_filter on the store) | novel | append | set_points.
+ *
+ * nbk_frame_cloud_carve: a held slot the new frame sees THROUGH is released.  The image and the camera as nbk_frame_cloud_backproject
+ * takes them (T in DEVICE memory); store_pts (DEVICE) [M][3], store_keep (DEVICE) [M], the only thing written.  In float64, every
+ * operation rounded once, in this order, for the point p of slot i:
+ *     d[e] = p[e] - T[e][3]
+ *     xc = (T[0][0] * d[0] + T[1][0] * d[1]) + T[2][0] * d[2];   yc, zc: the same with columns 1 and 2 of T   (R^T d: the rotation
+ *                                                                 of T is taken to be orthonormal and is not checked)
+ *     u = floor(((xc * fx) / zc + cx) + 0.5);   v = floor(((yc * fy) / zc + cy) + 0.5)                          (kept as doubles)
+ * store_keep[i] becomes 0 iff it was not 0, and zc > z_min, and u - window >= 0, u + window <= W - 1, v - window >= 0,
+ * v + window <= H - 1 (compared as doubles: NaN and huge values fall out), and EVERY pixel of the (2 window + 1)^2 window around
+ * (u, v) is valid by the back-projection's test with (z_m - zc) > margin, z_m = (double)raw * depth_scale.  A hole anywhere in the
+ * window is no evidence: the point stays; so does a point behind the surface, outside the image, or non-finite.  NBK_ERR_INVALID --
+ * before any device is looked for -- by the image and camera rules of nbk_frame_cloud_backproject, for a NaN or infinite margin, window
+ * < 0 or > 8, M < 0 or > 2^24, null store_pts / store_keep with M > 0.  nbk_frame_cloud_carve_host (no GPU needed): the same routine on
+ * HOST arrays, T included.
+ *
+ * nbk_frame_cloud_novel: pts (DEVICE) [N][3], keep (DEVICE) [N] read and written: keep[i] becomes 0 iff it was not 0 and the cloud
+ * holds a sorted point s with (held == NULL or held[original index of s] != 0) and
+ *     ((dx * dx + dy * dy) + dz * dz) < merge * merge,   dx = pts[i][0] - cloud point s [0], ...      (strict; float64, rounded once each)
+ * held (DEVICE, optional): one byte per point SUBMITTED to the cloud's last update -- the store's mask: the cloud as that update
+ * left it, less the slots released since.  The cloud's N, status and grid are read on the device, so in a graph this step sees the
+ * update before it; while the status is set or the cloud is empty nothing is read and keep stays.  merge <= 0 drops nothing; a
+ * non-finite point keeps its 1 (the update raises the status for it).  Frame points are not thinned against each other.
+ * NBK_ERR_INVALID for a null c, N < 0 or > 2^24, a NaN merge, null pts / keep with N > 0.
+ *
+ * nbk_frame_cloud_append: F = the ascending slots j < M with store_keep[j] == 0, A = the ascending i < N with new_keep[i] != 0; for
+ * k < min(|F|, |A|): store_pts[F[k]] = new_pts[A[k]] (three doubles copied) and store_keep[F[k]] = 1.  counts (DEVICE) int64[3] =
+ * (slots held afterwards, appended, dropped = |A| - appended); slot_of (DEVICE, optional) int32[N] = F[k] for A[k], -1 for a point
+ * not kept or dropped; new_pts and new_keep are not modified; untouched slots keep their bytes.  Deterministic: ranks of a two-level
+ * scan, no atomics; both lists' ranks are complete in the workspace before a slot is written.  workspace (DEVICE): at least
+ * nbk_frame_cloud_append_workspace_bytes (no GPU needed; -1 for M < 1, N < 0 or either > 2^24) bytes at a 64-byte boundary.
+ * NBK_ERR_INVALID for those sizes, a null store_pts / store_keep / counts / workspace, null new_pts / new_keep with N > 0, a workspace
+ * too small or misaligned.
+ */
+int32_t nbk_frame_cloud_carve(const void *depth /* DEVICE [H][W] */, int32_t depth_type, int32_t H, int32_t W, double depth_scale,
+                              double fx, double fy, double cx, double cy, const double *T /* DEVICE [3][4] */, double z_min,
+                              double z_max, double margin, int32_t window, const double *store_pts /* DEVICE [M][3] */, int64_t M,
+                              uint8_t *store_keep /* DEVICE [M], in and out */, void *stream);
+int32_t nbk_frame_cloud_carve_host(const void *depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx, double fy,
+                                   double cx, double cy, const double *T, double z_min, double z_max, double margin, int32_t window,
+                                   const double *store_pts, int64_t M, uint8_t *store_keep);     /* no GPU: the same routine */
+int32_t nbk_frame_cloud_novel(const nbk_cloud *c, const double *pts /* DEVICE [N][3] */, int64_t N, double merge,
+                              const uint8_t *held /* DEVICE or NULL */, uint8_t *keep /* DEVICE [N], in and out */, void *stream);
+int64_t nbk_frame_cloud_append_workspace_bytes(int64_t M, int64_t N);  /* no GPU */
+int32_t nbk_frame_cloud_append(double *store_pts /* DEVICE [M][3] */, uint8_t *store_keep /* DEVICE [M] */, int64_t M,
+                               const double *new_pts /* DEVICE [N][3] */, const uint8_t *new_keep /* DEVICE [N] */, int64_t N,
+                               int64_t *counts /* DEVICE [3] */, int32_t *slot_of /* DEVICE [N] or NULL */, void *workspace,
+                               int64_t workspace_bytes, void *stream);
+
+/*
  * Proximity records against a cloud: nbk_cloud_clearance_batch's record with WHERE the contact is and WHICH WAY to move -- what
  * nbk_proximity_jacobian_batch / nbk_pair_records_items give for the scene's pairs.  (Named like its siblings over edges and splines,
  * nbk_<what>_cloud_*: the nbk_cloud_* names are the cloud object's own set.)

@@ -38,6 +38,8 @@ SYMBOLS = [
     "nbk_spline_cloud_continuous_batch", "nbk_spline_shape_motion_bounds_host",
     "nbk_frame_cloud_backproject", "nbk_frame_cloud_backproject_host", "nbk_frame_cloud_self_filter", "nbk_frame_cloud_self_filter_lds_bytes",
     "nbk_frame_cloud_set_points", "nbk_frame_cloud_count",
+    "nbk_frame_cloud_carve", "nbk_frame_cloud_carve_host", "nbk_frame_cloud_novel", "nbk_frame_cloud_append_workspace_bytes",
+    "nbk_frame_cloud_append",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -155,6 +157,12 @@ def load():
     lib.nbk_frame_cloud_self_filter_lds_bytes.restype = i64
     lib.nbk_frame_cloud_set_points.argtypes = [vp, vp, vp, i64, f64, vp]
     lib.nbk_frame_cloud_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.nbk_frame_cloud_carve.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, f64, vp, f64, f64, f64, i32, vp, i64, vp, vp]
+    lib.nbk_frame_cloud_carve_host.argtypes = [vp, i32, i32, i32, f64, f64, f64, f64, f64, vp, f64, f64, f64, i32, vp, i64, vp]
+    lib.nbk_frame_cloud_novel.argtypes = [vp, vp, i64, f64, vp, vp, vp]
+    lib.nbk_frame_cloud_append_workspace_bytes.argtypes = [i64, i64]
+    lib.nbk_frame_cloud_append_workspace_bytes.restype = i64
+    lib.nbk_frame_cloud_append.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

@@ -19,6 +19,12 @@
 // predicate at ONE configuration against many points, the selected shapes' cores once per workgroup in LDS) write the points and the
 // mask such an update takes.
 //
+// Fused frames (several frames in one cloud): the caller's store of point slots is the array an update with a mask takes, so a point's
+// index in a record is its slot.  k_cloud_carve releases the slots a new frame sees through (depth_carve_point, nbk_cloud_depth.hpp),
+// k_cloud_novel drops the frame points the cloud of the previous update still holds within a merge distance (the walk of the queries),
+// k_cloud_append_count | nbk.hip's k_scan | k_cloud_append_slots | k_cloud_append_write move the rest into free slots by the ranks of
+// a two-level scan (CloudAppendLayout, nbk_plan.hpp: the caller's workspace).
+//
 // Queries: one configuration per lane, 64 per workgroup; the wave takes the selected robot shapes one after the other (Core.kind and
 // the hull a core names are wave-uniform this way), replays FK along the shape's joint mask from the lane's staged q row, builds the
 // shape's core and walks the cells cloud_cell_range gives for the ball the pair predicate's bounding-sphere step can pass.  Cells are
@@ -141,6 +147,22 @@ __global__ __launch_bounds__(256) void k_cloud_backproject(const void* __restric
     keep[i] = valid ? 1 : 0;
 }
 
+// ---- fused frames: carving (nbk_frame_cloud_carve) ------------------------------------------------------------------------------------
+// One stored point per lane: a slot that is held and that the frame sees through (depth_carve_point, nbk_cloud_depth.hpp) is released.
+// Only store_keep is written, and only 1 -> 0; T as k_cloud_backproject takes it.
+__global__ __launch_bounds__(256) void k_cloud_carve(const void* __restrict__ depth, int depth_type, int H, int W, DepthCam cam,
+                                                     const double* __restrict__ T, double margin, int window,
+                                                     const double* __restrict__ store_pts, int m, uint8_t* __restrict__ store_keep) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= m) return;
+    if (store_keep[i] == 0) return;
+    double Tm[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) Tm[e] = T[e];
+    const double p[3] = {store_pts[3 * (size_t)i], store_pts[3 * (size_t)i + 1], store_pts[3 * (size_t)i + 2]};
+    if (depth_carve_point(cam, Tm, depth, depth_type, H, W, p, margin, window)) store_keep[i] = 0;
+}
+
 // ---- the walk of one lane over the cells of a ball ----------------------------------------------------------------------------
 struct CloudWalk { int x0, x1, y0, y1, z1, y, z; unsigned cur, end; bool more; };
 
@@ -164,6 +186,116 @@ NBK_DEV bool cloud_walk_next(const CloudDev& c, CloudWalk& w) {
         w.end = c.start[row + w.x1 + 1];
     }
     return true;
+}
+
+// ---- fused frames: novelty (nbk_frame_cloud_novel) -------------------------------------------------------------------------------------
+// One frame point per lane: keep[i] goes 1 -> 0 iff the cloud holds a point s -- counted only while held[idx[s]] != 0, when a `held`
+// mask is given: the cloud of the last update less what has been released since -- with
+//     ((dx * dx + dy * dy) + dz * dz) < merge * merge,   dx = p[0] - pts[s][0], ...          (strict; plain products and sums)
+// The walk is the ball of radius merge around the point (nbk_cloud_grid.hpp: the range is sound for exactly this predicate form).
+// N, status and the grid are the device's: while the status is set or N is 0 nothing of the grid is read.  An OR: the order of the
+// points of a cell plays no part.  A non-finite frame point satisfies the predicate for no s and stays; it is not walked.
+__global__ __launch_bounds__(256) void k_cloud_novel(CloudDev cd, const uint8_t* __restrict__ held, const double* __restrict__ pts, int n,
+                                                     double merge, uint8_t* __restrict__ keep) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    if (keep[i] == 0) return;
+    if (cd.hdr->status != 0 || cd.hdr->n == 0) return;
+    const double p[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+    if (!((p[0] - p[0] == 0.0) && (p[1] - p[1] == 0.0) && (p[2] - p[2] == 0.0))) return;
+    const double m2 = merge * merge;
+    CloudWalk w;
+    cloud_walk_begin(cd, true, p, merge, w);
+    while (cloud_walk_next(cd, w)) {
+        const unsigned s = w.cur++;
+        if (held != nullptr && held[cd.idx[s]] == 0) continue;
+        const double dx = p[0] - cd.pts[3 * (size_t)s], dy = p[1] - cd.pts[3 * (size_t)s + 1], dz = p[2] - cd.pts[3 * (size_t)s + 2];
+        if (((dx * dx + dy * dy) + dz * dz) < m2) { keep[i] = 0; return; }
+    }
+}
+
+// ---- fused frames: append (nbk_frame_cloud_append) -------------------------------------------------------------------------------------
+// F: the free slots of the store (store_keep == 0), A: the new points kept (keep != 0), both ascending; the k-th of A goes to the k-th
+// of F.  Ranks come from a two-level scan, never from atomics: k_cloud_append_count (per-256 block counts of F, then of A, one list) |
+// nbk.hip's k_scan over that list | k_cloud_append_slots (slot[k] = F[k] for k < N, into the workspace) | k_cloud_append_write.  The
+// store is written by the last kernel alone, after both lists' ranks are complete.
+
+// the rank of this thread among the threads of its 256-thread workgroup whose flag is set (by ballot and the four waves' totals),
+// and their number; every thread of the workgroup calls it, once per kernel
+NBK_DEV unsigned cloud_block_rank(bool flag, unsigned& total) {
+    __shared__ unsigned wave_sum[4];
+    const unsigned long long b = __ballot(flag);
+    const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+    if (lane == 0) wave_sum[wv] = (unsigned)__popcll(b);
+    __syncthreads();
+    unsigned base = 0u;
+    total = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned v = wave_sum[k];
+        if (k < wv) base += v;
+        total += v;
+    }
+    return base + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+}
+
+// blocks 0 .. bf - 1: the free slots of their 256 store slots; blocks bf .. bf + ba - 1: the kept ones of their 256 new points
+__global__ __launch_bounds__(256) void k_cloud_append_count(const uint8_t* __restrict__ store_keep, int m, const uint8_t* __restrict__ keep,
+                                                            int n, int bf, unsigned long long* __restrict__ cnt) {
+    const int b = (int)blockIdx.x;
+    bool flag;
+    if (b < bf) {
+        const int j = b * 256 + (int)threadIdx.x;
+        flag = j < m && store_keep[j] == 0;
+    } else {
+        const int i = (b - bf) * 256 + (int)threadIdx.x;
+        flag = i < n && keep[i] != 0;
+    }
+    unsigned total;
+    (void)cloud_block_rank(flag, total);
+    if (threadIdx.x == 0) cnt[b] = total;
+}
+
+// one block per 256 store slots: free slot j of rank k < n -> slot[k] = j
+__global__ __launch_bounds__(256) void k_cloud_append_slots(const uint8_t* __restrict__ store_keep, int m, int n,
+                                                            const unsigned long long* __restrict__ offs, int* __restrict__ slot) {
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool flag = j < m && store_keep[j] == 0;
+    unsigned total;
+    const unsigned long long k = offs[blockIdx.x] + cloud_block_rank(flag, total);
+    if (flag && k < (unsigned long long)n) slot[k] = j;
+}
+
+// one block per 256 new points (one block at least: it writes the counts): the kept point i of rank k < |F| moves to slot[k]
+__global__ __launch_bounds__(256) void k_cloud_append_write(const double* __restrict__ new_pts, const uint8_t* __restrict__ keep, int n, int m,
+                                                            int bf, int ba, const unsigned long long* __restrict__ offs,
+                                                            const int* __restrict__ slot, double* __restrict__ store_pts,
+                                                            uint8_t* __restrict__ store_keep, int* __restrict__ slot_of,
+                                                            long long* __restrict__ counts) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool flag = i < n && keep[i] != 0;
+    const unsigned long long n_free = offs[bf], n_new = offs[bf + ba] - n_free;
+    const unsigned long long appended = n_free < n_new ? n_free : n_new;
+    unsigned total;
+    const unsigned r = cloud_block_rank(flag, total);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counts[0] = (long long)((unsigned long long)m - n_free + appended);
+        counts[1] = (long long)appended;
+        counts[2] = (long long)(n_new - appended);
+    }
+    if (i >= n) return;
+    int to = -1;
+    if (flag) {
+        const unsigned long long k = (offs[bf + (int)blockIdx.x] - n_free) + r;
+        if (k < appended) {
+            to = slot[k];
+            store_pts[3 * (size_t)to] = new_pts[3 * (size_t)i];
+            store_pts[3 * (size_t)to + 1] = new_pts[3 * (size_t)i + 1];
+            store_pts[3 * (size_t)to + 2] = new_pts[3 * (size_t)i + 2];
+            store_keep[to] = 1;
+        }
+    }
+    if (slot_of != nullptr) slot_of[i] = to;
 }
 
 // the lane's q row into its LDS row (eight loads in flight, as k_pair_items stages it); returns whether every value is finite
@@ -1151,6 +1283,82 @@ int32_t nbk_frame_cloud_self_filter(const nbk_model* m, const double* q0, const 
     const int64_t want = (N + 255) / 256, most = (int64_t)(cus > 0 ? cus : 1) * SELF_FILTER_WGS_PER_CU;
     hipLaunchKernelGGL(k_cloud_self_filter, dim3((unsigned)(want < most ? want : most)), dim3(256), L.bytes(), (hipStream_t)stream, m->d, sel,
                        n_sel, q0, pts, (int)N, radius, padding, keep);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// the argument rules the two carving entries share: those of the back-projection for the image and the camera, the store and the
+// two parameters of the test
+static bool carve_args_ok(const void* depth, int32_t depth_type, int32_t H, int32_t W, const DepthCam& cam, const double* T, double margin,
+                          int32_t window, const double* store_pts, int64_t M, const uint8_t* store_keep) {
+    if (H < 0 || W < 0 || (int64_t)H * (int64_t)W > CLOUD_MAX_POINTS) return false;
+    if ((depth_type != 0 && depth_type != 1) || !depth_cam_valid(cam) || T == nullptr) return false;
+    if ((int64_t)H * (int64_t)W > 0 && depth == nullptr) return false;
+    if (!(margin - margin == 0.0) || window < 0 || window > DEPTH_CARVE_MAX_WINDOW) return false;
+    return M >= 0 && M <= CLOUD_MAX_POINTS && (M == 0 || (store_pts != nullptr && store_keep != nullptr));
+}
+
+int32_t nbk_frame_cloud_carve_host(const void* depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx, double fy,
+                                   double cx, double cy, const double* T, double z_min, double z_max, double margin, int32_t window,
+                                   const double* store_pts, int64_t M, uint8_t* store_keep) {
+    const DepthCam cam{depth_scale, fx, fy, cx, cy, z_min, z_max};
+    if (!carve_args_ok(depth, depth_type, H, W, cam, T, margin, window, store_pts, M, store_keep)) return NBK_ERR_INVALID;
+    for (int64_t i = 0; i < M; ++i)
+        if (store_keep[i] != 0 && depth_carve_point(cam, T, depth, depth_type, H, W, store_pts + 3 * i, margin, window)) store_keep[i] = 0;
+    return NBK_OK;
+}
+
+int32_t nbk_frame_cloud_carve(const void* depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx, double fy,
+                              double cx, double cy, const double* T, double z_min, double z_max, double margin, int32_t window,
+                              const double* store_pts, int64_t M, uint8_t* store_keep, void* stream) {
+    const DepthCam cam{depth_scale, fx, fy, cx, cy, z_min, z_max};
+    if (!carve_args_ok(depth, depth_type, H, W, cam, T, margin, window, store_pts, M, store_keep)) return NBK_ERR_INVALID;
+    if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
+    if (M == 0 || (int64_t)H * (int64_t)W == 0) return NBK_OK;           // (no image: no window fits, nothing is seen through)
+    hipLaunchKernelGGL(k_cloud_carve, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, depth, (int)depth_type, (int)H,
+                       (int)W, cam, T, margin, (int)window, store_pts, (int)M, store_keep);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_frame_cloud_novel(const nbk_cloud* c, const double* pts, int64_t N, double merge, const uint8_t* held, uint8_t* keep,
+                              void* stream) {
+    if (c == nullptr || N < 0 || N > CLOUD_MAX_POINTS || merge != merge || (N > 0 && (pts == nullptr || keep == nullptr))) return NBK_ERR_INVALID;
+    { const int32_t rc = cloud_check_device(c); if (rc != NBK_OK) return rc; }
+    if (N == 0 || !(merge > 0.0)) return NBK_OK;
+    hipLaunchKernelGGL(k_cloud_novel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cloud_dev(c), held, pts, (int)N,
+                       merge, keep);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_frame_cloud_append_workspace_bytes(int64_t M, int64_t N) {
+    if (M < 1 || M > CLOUD_MAX_POINTS || N < 0 || N > CLOUD_MAX_POINTS) return -1;
+    return (int64_t)CloudAppendLayout(M, N).bytes;
+}
+
+int32_t nbk_frame_cloud_append(double* store_pts, uint8_t* store_keep, int64_t M, const double* new_pts, const uint8_t* new_keep, int64_t N,
+                               int64_t* counts, int32_t* slot_of, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (store_pts == nullptr || store_keep == nullptr || counts == nullptr || workspace == nullptr) return NBK_ERR_INVALID;
+    if (M < 1 || M > CLOUD_MAX_POINTS || N < 0 || N > CLOUD_MAX_POINTS || (N > 0 && (new_pts == nullptr || new_keep == nullptr))) return NBK_ERR_INVALID;
+    const CloudAppendLayout L(M, N);
+    if (!cloud_workspace_ok(workspace, workspace_bytes, L.bytes)) return NBK_ERR_INVALID;
+    if (nbk_device_count() <= 0) return NBK_ERR_NO_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    const CloudAppendLayout::View v = L.view(workspace);
+    const int bf = (int)L.bf, ba = (int)L.ba;
+    hipLaunchKernelGGL(k_cloud_append_count, dim3((unsigned)(bf + ba)), dim3(256), 0, st, (const uint8_t*)store_keep, (int)M, new_keep, (int)N,
+                       bf, v.cnt);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, (const unsigned long long*)v.cnt, (int64_t)(bf + ba), v.offs);
+    NBK_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(k_cloud_append_slots, dim3((unsigned)bf), dim3(256), 0, st, (const uint8_t*)store_keep, (int)M, (int)N,
+                           (const unsigned long long*)v.offs, v.slot);
+        NBK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cloud_append_write, dim3((unsigned)(ba > 0 ? ba : 1)), dim3(256), 0, st, new_pts, new_keep, (int)N, (int)M, bf, ba,
+                       (const unsigned long long*)v.offs, (const int*)v.slot, store_pts, store_keep, slot_of, reinterpret_cast<long long*>(counts));
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

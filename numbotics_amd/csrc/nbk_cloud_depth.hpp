@@ -11,8 +11,18 @@
 //     yc = (((double)v - cy) * z) / fy
 //     w[e] = ((T[e][0] * xc + T[e][1] * yc) + T[e][2] * z) + T[e][3]
 // A pixel is valid iff z - z == 0 (finite), z > z_min and z <= z_max; an invalid pixel (a hole: 0, NaN, out of range) has no point.
+//
+// The way back, for free-space carving (k_cloud_carve, nbk_frame_cloud_carve_host; DESIGN.md 3, "Fused frames"): a stored world point p
+// is SEEN THROUGH by a frame when the frame measures a surface behind it at every pixel around its projection.  Same contract:
+//     d[e] = p[e] - T[e][3]
+//     xc = (T[0][0] * d[0] + T[1][0] * d[1]) + T[2][0] * d[2]       (R^T d: T's rotation is taken to be orthonormal, not checked;
+//     yc, zc likewise with columns 1 and 2                            columns 0, 1, 2 of T give xc, yc, zc)
+//     u = floor(((xc * fx) / zc + cx) + 0.5)      v = floor(((yc * fy) / zc + cy) + 0.5)                   (kept as doubles)
+// p is seen through iff zc > z_min, the window u - w .. u + w, v - w .. v + w lies in the image (compared as doubles: NaN and huge
+// values fall out) and every pixel of it is valid by the test above with (z - zc) > margin.  A hole in the window is no evidence.
 #ifndef NBK_CLOUD_DEPTH_HPP
 #define NBK_CLOUD_DEPTH_HPP
+#include <math.h>
 #include <stdint.h>
 
 #ifndef NBK_GRID_FN
@@ -31,10 +41,13 @@ NBK_GRID_FN double depth_pixel_value(const void* depth, int depth_type, int64_t 
     return depth_type == 0 ? (double)static_cast<const float*>(depth)[i] : (double)static_cast<const uint16_t*>(depth)[i];
 }
 
+// the validity test of a metric depth z: finite and in (z_min, z_max]
+NBK_GRID_FN bool depth_z_valid(const DepthCam& k, double z) { return (z - z == 0.0) && z > k.z_min && z <= k.z_max; }
+
 // pixel (u, v) of raw depth d -> its world point in w and true, or (0, 0, 0) and false for a hole
 NBK_GRID_FN bool depth_backproject_pixel(const DepthCam& k, const double* T, int u, int v, double d, double* w) {
     const double z = d * k.depth_scale;
-    const bool valid = (z - z == 0.0) && z > k.z_min && z <= k.z_max;
+    const bool valid = depth_z_valid(k, z);
     if (!valid) {
         w[0] = 0.0; w[1] = 0.0; w[2] = 0.0;
         return false;
@@ -42,6 +55,30 @@ NBK_GRID_FN bool depth_backproject_pixel(const DepthCam& k, const double* T, int
     const double xc = (((double)u - k.cx) * z) / k.fx;
     const double yc = (((double)v - k.cy) * z) / k.fy;
     for (int e = 0; e < 3; ++e) w[e] = ((T[4 * e] * xc + T[4 * e + 1] * yc) + T[4 * e + 2] * z) + T[4 * e + 3];
+    return true;
+}
+
+constexpr int DEPTH_CARVE_MAX_WINDOW = 8;
+
+// is the world point p seen through by the (H, W) image at pose T?  (0 <= window <= DEPTH_CARVE_MAX_WINDOW: the caller's rule; every
+// pixel read lies in the image by the window test, whatever p holds)
+NBK_GRID_FN bool depth_carve_point(const DepthCam& k, const double* T, const void* depth, int depth_type, int H, int W, const double* p,
+                                   double margin, int window) {
+    const double d0 = p[0] - T[3], d1 = p[1] - T[7], d2 = p[2] - T[11];
+    const double xc = (T[0] * d0 + T[4] * d1) + T[8] * d2;
+    const double yc = (T[1] * d0 + T[5] * d1) + T[9] * d2;
+    const double zc = (T[2] * d0 + T[6] * d1) + T[10] * d2;
+    if (!(zc > k.z_min)) return false;
+    const double u = floor(((xc * k.fx) / zc + k.cx) + 0.5);
+    const double v = floor(((yc * k.fy) / zc + k.cy) + 0.5);
+    const double w = (double)window;
+    if (!(u - w >= 0.0 && u + w <= (double)(W - 1) && v - w >= 0.0 && v + w <= (double)(H - 1))) return false;
+    const int u0 = (int)u - window, v0 = (int)v - window, side = 2 * window + 1;
+    for (int b = 0; b < side; ++b)
+        for (int a = 0; a < side; ++a) {
+            const double z = depth_pixel_value(depth, depth_type, (int64_t)(v0 + b) * W + (u0 + a)) * k.depth_scale;
+            if (!depth_z_valid(k, z) || !((z - zc) > margin)) return false;
+        }
     return true;
 }
 

@@ -222,6 +222,23 @@ struct EdgeCloudLayout {
 };
 constexpr int64_t EDGE_CLOUD_MAX_E = int64_t(1) << 56;      // the layout's 40 bytes per edge stay far inside int64
 
+// the caller's workspace of nbk_frame_cloud_append for a store of M slots and N new points: the per-256 block counts of the free
+// slots (bf blocks) and then of the points kept (ba blocks) as one list cnt [bf + ba] | its exclusive scan offs [bf + ba + 1] |
+// slot [N]: the k-th free slot, for k < N (more are never taken).  Each part rounded up to 64 bytes
+struct CloudAppendLayout {
+    int64_t bf, ba;
+    size_t offs, slot, bytes;
+    static size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
+    CloudAppendLayout(int64_t M, int64_t N)
+        : bf((M + 255) / 256), ba((N + 255) / 256), offs(r64((size_t)(bf + ba) * 8)), slot(offs + r64((size_t)(bf + ba + 1) * 8)),
+          bytes(slot + r64((size_t)N * 4)) {}
+    struct View { unsigned long long *cnt, *offs; int* slot; };
+    View view(void* base) const {
+        char* p = static_cast<char*>(base);
+        return {reinterpret_cast<unsigned long long*>(p), reinterpret_cast<unsigned long long*>(p + offs), reinterpret_cast<int*>(p + slot)};
+    }
+};
+
 constexpr int64_t SPLINE_TILE = int64_t(1) << 20;           // q rows written and checked per tile of nbk_spline_validity_batch
 constexpr int64_t SPLINE_MAX_S = int64_t(1) << 26;          // a spline batch has fewer trajectories than this ...
 constexpr unsigned long long SPLINE_MAX_T = 1ull << 31;     // ... and fewer samples than this

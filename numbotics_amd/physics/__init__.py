@@ -2,7 +2,7 @@
 __all__ = [
     "CollisionShape", "PhysicsObject", "Cube", "Cuboid", "Sphere", "Mesh", "Plane", "Capsule", "Cylinder",
     "World", "get_world", "Link", "Chain", "GraphChain", "Constraint", "Joint", "Proximity",
-    "PointCloud", "backproject", "intrinsics_from_fov",
+    "PointCloud", "backproject", "carve", "intrinsics_from_fov",
 ]
 
 from .constraint import Constraint, Joint
@@ -10,4 +10,4 @@ from .collision import Proximity, CollisionShape
 from .world import World, get_world
 from .object import PhysicsObject, Cube, Cuboid, Sphere, Mesh, Plane, Capsule, Cylinder
 from .chain import Link, Chain, GraphChain
-from .pointcloud import PointCloud, backproject, intrinsics_from_fov
+from .pointcloud import PointCloud, backproject, carve, intrinsics_from_fov

@@ -8,6 +8,10 @@ each and never a new descriptor.  Like the rest of the device path it has no CPU
 From a camera's frame to that update: ``backproject`` (a depth image to world points and a validity mask, one pixel per point),
 ``Arm.cloud_self_filter`` (the arm's own image out of the mask) and ``update(points, keep=mask)``; ``update_from_depth`` is the
 three on the current stream.
+
+Several frames in one cloud: ``PointCloud.integrate_depth`` keeps a store of ``capacity`` point slots on the device and, per frame,
+releases the stored points the frame sees through (``carve``), drops the frame points the cloud holds already (``novel``), moves the
+rest into free slots (``append``) and updates the cloud from the store -- a point's index in a record is its slot.
 """
 import ctypes as C
 
@@ -118,6 +122,32 @@ def _device_keep(torch, keep, n):
     return k
 
 
+def _device_pose(torch, camera_pose, frame, stage=None):
+    """The optical pose as a float64 CUDA tensor the kernels read rows 0 .. 2 of: a device ``camera_pose`` in the optical frame as it
+    is, anything else through ``stage`` (a (3, 4) float64 CUDA tensor; a new one when there is none) -- a device pose in the
+    reference's frame by device copies, a host pose by ``optical_pose`` and one copy."""
+    if torch.is_tensor(camera_pose):
+        T = camera_pose
+        if not T.is_cuda or T.dtype != torch.float64 or tuple(T.shape) not in ((4, 4), (3, 4)) or not T.is_contiguous():
+            raise ValueError("camera_pose on the device must be a contiguous float64 (4, 4) or (3, 4) CUDA tensor")
+        if frame == "numbotics":
+            stage = stage if stage is not None else torch.empty((3, 4), dtype=torch.float64, device=T.device)
+            torch.neg(T[:3, 1], out=stage[:, 0])
+            torch.neg(T[:3, 2], out=stage[:, 1])
+            stage[:, 2].copy_(T[:3, 0])
+            stage[:, 3].copy_(T[:3, 3])
+            T = stage
+        elif frame != "optical":
+            raise ValueError(f"frame must be 'optical' or 'numbotics', got {frame!r}")
+    else:
+        host = torch.from_numpy(optical_pose(camera_pose, frame))
+        if stage is not None:
+            T = stage.copy_(host)
+        else:
+            T = host.to("cuda")
+    return T
+
+
 def backproject_host(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical"):
     """``backproject`` by the library's own routine on the host (nbk_frame_cloud_backproject_host; no GPU needed): NumPy in, NumPy
     (points (H * W, 3), keep (H * W,) uint8) out, the bits of the device's."""
@@ -152,25 +182,7 @@ def backproject(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_ma
         d = d.to("cuda")
     H, W = int(d.shape[0]), int(d.shape[1])
     fx, fy, cx, cy = _intrinsics(intrinsics)
-    if torch.is_tensor(camera_pose):
-        T = camera_pose
-        if not T.is_cuda or T.dtype != torch.float64 or tuple(T.shape) not in ((4, 4), (3, 4)) or not T.is_contiguous():
-            raise ValueError("camera_pose on the device must be a contiguous float64 (4, 4) or (3, 4) CUDA tensor")
-        if frame == "numbotics":
-            stage = _pose_stage if _pose_stage is not None else torch.empty((3, 4), dtype=torch.float64, device=T.device)
-            torch.neg(T[:3, 1], out=stage[:, 0])
-            torch.neg(T[:3, 2], out=stage[:, 1])
-            stage[:, 2].copy_(T[:3, 0])
-            stage[:, 3].copy_(T[:3, 3])
-            T = stage
-        elif frame != "optical":
-            raise ValueError(f"frame must be 'optical' or 'numbotics', got {frame!r}")
-    else:
-        host = torch.from_numpy(optical_pose(camera_pose, frame))
-        if _pose_stage is not None:
-            T = _pose_stage.copy_(host)
-        else:
-            T = host.to("cuda")
+    T = _device_pose(torch, camera_pose, frame, _pose_stage)
     if out is None:
         pts = torch.empty((H * W, 3), dtype=torch.float64, device=d.device)
         keep = torch.empty((H * W,), dtype=torch.uint8, device=d.device)
@@ -185,6 +197,92 @@ def backproject(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_ma
                                                  pts.data_ptr() if n > 0 else None, keep.data_ptr() if n > 0 else None,
                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_backproject")
     return pts, keep
+
+
+def carve_host(points, keep, depth, intrinsics, camera_pose, margin, window=1, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical"):
+    """``carve`` by the library's own routine on the host (nbk_frame_cloud_carve_host; no GPU needed): NumPy in, the new mask (M,)
+    uint8 out (``keep`` itself is not modified), the bits of the device's."""
+    a = np.asarray(depth)
+    if a.ndim != 2 or a.dtype not in (np.float32, np.uint16, np.int16):
+        raise ValueError("depth must be a (H, W) float32 or 16-bit image")
+    a = np.ascontiguousarray(a)
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64)).reshape(-1, 3)
+    out = np.ascontiguousarray(np.asarray(keep)).astype(np.uint8)
+    M = pts.shape[0]
+    if out.shape != (M,):
+        raise ValueError(f"keep must have shape ({M},), got {out.shape}")
+    fx, fy, cx, cy = _intrinsics(intrinsics)
+    T = optical_pose(camera_pose, frame)
+    H, W = a.shape
+    _lib.check(_lib.load().nbk_frame_cloud_carve_host(a.ctypes.data, 0 if a.dtype == np.float32 else 1, H, W, float(depth_scale), fx, fy, cx, cy,
+                                                      T.ctypes.data, float(z_min), float(z_max), float(margin), int(window),
+                                                      pts.ctypes.data, M, out.ctypes.data), "nbk_frame_cloud_carve_host")
+    return out
+
+
+def carve(points, keep, depth, intrinsics, camera_pose, margin, window=1, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical",
+          _pose_stage=None):
+    """Free-space carving on the current stream (nbk_frame_cloud_carve): a stored point the frame sees THROUGH is released.
+    ``points`` (M, 3) float64 and ``keep`` (M,) uint8 -- CUDA tensors: ``keep`` is worked on in place and returned; NumPy: a new
+    device mask is returned.  ``depth``, ``intrinsics``, ``camera_pose`` and the options are ``backproject``'s.  ``keep[i]`` goes to
+    0 iff it was set, point i lies in front of the camera (beyond ``z_min``), its pixel and the ``window`` pixels around it on every
+    side lie in the image, and every one of those (2 * window + 1)^2 pixels is a valid depth more than ``margin`` BEHIND the point.
+    A hole in the window, a point behind the measured surface (occluded) or outside the image: no evidence, the point stays."""
+    from numbotics_amd.engine import _require_gpu
+    torch = _require_gpu()
+    d = _depth_array(torch, depth)
+    if not d.is_cuda:
+        d = d.to("cuda")
+    H, W = int(d.shape[0]), int(d.shape[1])
+    fx, fy, cx, cy = _intrinsics(intrinsics)
+    T = _device_pose(torch, camera_pose, frame, _pose_stage)
+    pts = PointCloud._device_points(torch, points)
+    M = int(pts.shape[0])
+    k = _device_keep(torch, keep, M)
+    _lib.check(_lib.load().nbk_frame_cloud_carve(d.data_ptr() if H * W > 0 else None, 0 if d.dtype == torch.float32 else 1, H, W,
+                                                 float(depth_scale), fx, fy, cx, cy, T.data_ptr(), float(z_min), float(z_max), float(margin),
+                                                 int(window), pts.data_ptr() if M > 0 else None, M, k.data_ptr() if M > 0 else None,
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_carve")
+    return k
+
+
+def append_workspace_bytes(capacity, n):
+    """Bytes of workspace ``append`` needs for a store of ``capacity`` slots and ``n`` new points (no GPU needed)."""
+    b = int(_lib.load().nbk_frame_cloud_append_workspace_bytes(int(capacity), int(n)))
+    if b < 0:
+        raise ValueError(f"a store of {capacity} slots and {n} new points: sizes out of range")
+    return b
+
+
+def append(store_points, store_keep, points, keep, counts=None, slot_of=None, workspace=None):
+    """The kept ``points`` into the free slots of a store on the current stream (nbk_frame_cloud_append), all CUDA tensors: the k-th
+    point with ``keep != 0`` goes to the k-th slot with ``store_keep == 0`` (both ascending) until either list ends.  ``counts``
+    (3,) int64 receives (slots held afterwards, appended, dropped); ``slot_of`` (N,) int32, optional, the slot of each new point
+    or -1.  ``workspace``: a uint8 CUDA tensor of ``append_workspace_bytes`` bytes (allocated when not given).  Deterministic: ranks
+    by prefix sums, no atomics.  -> counts."""
+    import torch
+    sp = PointCloud._device_points(torch, store_points)
+    M = int(sp.shape[0])
+    sk = _device_keep(torch, store_keep, M)
+    if not (torch.is_tensor(store_keep) and store_keep.dtype == torch.uint8):
+        raise ValueError("store_keep must be a uint8 CUDA tensor: it is written in place")
+    p = PointCloud._device_points(torch, points)
+    N = int(p.shape[0])
+    k = _device_keep(torch, keep, N)
+    if counts is None:
+        counts = torch.empty((3,), dtype=torch.int64, device="cuda")
+    need = append_workspace_bytes(M, N)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device="cuda")
+    if slot_of is not None and not (slot_of.is_cuda and slot_of.dtype == torch.int32 and tuple(slot_of.shape) == (N,) and slot_of.is_contiguous()):
+        raise ValueError(f"slot_of must be a contiguous int32 CUDA tensor of shape ({N},)")
+    if not (counts.is_cuda and counts.dtype == torch.int64 and tuple(counts.shape) == (3,) and counts.is_contiguous()):
+        raise ValueError("counts must be a contiguous int64 CUDA tensor of shape (3,)")
+    _lib.check(_lib.load().nbk_frame_cloud_append(sp.data_ptr(), sk.data_ptr(), M, p.data_ptr() if N > 0 else None, k.data_ptr() if N > 0 else None,
+                                                  N, counts.data_ptr(), slot_of.data_ptr() if slot_of is not None and N > 0 else None,
+                                                  workspace.data_ptr(), int(workspace.numel()),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_append")
+    return counts
 
 
 class PointCloud:
@@ -274,6 +372,7 @@ class PointCloud:
         self.radius = radius             # (only now: a refused update leaves the object as the device has it)
         self._points = t
         self.n = n
+        self._map_live = False           # (a plain update ends a map: integrate_depth sets the flag again after its own)
 
     def count(self) -> int:
         """The points the cloud holds: those of the last update that its ``keep`` let through (all of them without one).
@@ -281,6 +380,32 @@ class PointCloud:
         out = C.c_int64(0)
         _lib.check(self._lib.nbk_frame_cloud_count(self._h, C.byref(out)), "nbk_frame_cloud_count")
         return int(out.value)
+
+    def _frame_stage(self, torch, d):
+        """The staging tensors of a frame of d's size and type (allocated on the first call with that size and type), and d on the
+        device: a host image is copied into the stage's."""
+        H, W = int(d.shape[0]), int(d.shape[1])
+        st = self.__dict__.get("_stage")
+        if st is None or st["key"] != (H * W, d.dtype):
+            st = self._stage = {"key": (H * W, d.dtype), "pts": torch.empty((H * W, 3), dtype=torch.float64, device="cuda"),
+                                "keep": torch.empty((H * W,), dtype=torch.uint8, device="cuda"),
+                                "pose": torch.empty((3, 4), dtype=torch.float64, device="cuda"),
+                                "depth": torch.empty((H, W), dtype=d.dtype, device="cuda"), "q": None}
+        if not d.is_cuda:
+            st["depth"].copy_(d.reshape(H, W))
+            d = st["depth"]
+        return st, d
+
+    def _stage_q(self, torch, st, arm, q):
+        """q as a device tensor: a host q goes through the stage's."""
+        if q is None:
+            raise ValueError("the self-filter needs the configuration q the frame was taken at")
+        if torch.is_tensor(q):
+            return q
+        if st["q"] is None:
+            st["q"] = torch.empty((arm.dof,), dtype=torch.float64, device="cuda")
+        st["q"].copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(q, dtype=np.float64)).reshape(arm.dof)))
+        return st["q"]
 
     def update_from_depth(self, depth, intrinsics, camera_pose, arm=None, q=None, padding=0.0, ignore_links=(), **options):
         """A depth frame to the cloud's points on the current stream, in three steps: ``backproject`` (``options``: its
@@ -296,27 +421,105 @@ class PointCloud:
         import torch
         d = _depth_array(torch, depth)
         H, W = int(d.shape[0]), int(d.shape[1])
-        st = self.__dict__.get("_stage")
-        if st is None or st["key"] != (H * W, d.dtype):
-            st = self._stage = {"key": (H * W, d.dtype), "pts": torch.empty((H * W, 3), dtype=torch.float64, device="cuda"),
-                                "keep": torch.empty((H * W,), dtype=torch.uint8, device="cuda"),
-                                "pose": torch.empty((3, 4), dtype=torch.float64, device="cuda"),
-                                "depth": torch.empty((H, W), dtype=d.dtype, device="cuda"), "q": None}
-        if not d.is_cuda:
-            st["depth"].copy_(d.reshape(H, W))
-            d = st["depth"]
+        st, d = self._frame_stage(torch, d)
         pts, keep = backproject(d, intrinsics, camera_pose, out=(st["pts"], st["keep"]), _pose_stage=st["pose"], **options)
         if arm is not None:
-            if q is None:
-                raise ValueError("the self-filter needs the configuration q the frame was taken at")
-            if not torch.is_tensor(q):
-                if st["q"] is None:
-                    st["q"] = torch.empty((arm.dof,), dtype=torch.float64, device="cuda")
-                st["q"].copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(q, dtype=np.float64)).reshape(arm.dof)))
-                q = st["q"]
+            q = self._stage_q(torch, st, arm, q)
             arm.cloud_self_filter(pts, q, self.radius, padding, keep=keep, ignore_links=ignore_links)
         self.update(pts, keep=keep)
         return pts, keep
+
+    def novel(self, points, keep, merge_distance, held=None):
+        """Which of ``points`` (N, 3) the cloud does not hold yet, on the current stream (nbk_frame_cloud_novel): ``keep[i]`` goes to
+        0 iff it was set and a point of the cloud lies closer than ``merge_distance`` (squared distance, strictly below the
+        square).  ``held``: an optional uint8 / bool CUDA mask over the points SUBMITTED to the last update (``n`` of them): cloud
+        points whose byte is 0 do not count -- a store's mask after slots were released.  ``keep`` as a CUDA tensor is worked on
+        in place and returned; NumPy: a new device mask.  ``merge_distance <= 0`` drops nothing.  The cloud's size, status and grid
+        are read when the work runs: an empty cloud, or one whose status is set, leaves ``keep`` as it is.  The points are not
+        thinned against each other."""
+        import torch
+        p = self._device_points(torch, points)
+        n = int(p.shape[0])
+        k = _device_keep(torch, keep, n)
+        h = None if held is None else _device_keep(torch, held, self.n)
+        _lib.check(self._lib.nbk_frame_cloud_novel(self._h, p.data_ptr() if n > 0 else None, n, float(merge_distance),
+                                                   h.data_ptr() if h is not None and self.n > 0 else None, k.data_ptr() if n > 0 else None,
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_novel")
+        return k
+
+    def reset_map(self):
+        """Forget the map: the next ``integrate_depth`` starts from an empty store.  (Issues nothing; the cloud keeps its points
+        until then.)"""
+        self._map_live = False
+
+    def integrate_depth(self, depth, intrinsics, camera_pose, arm=None, q=None, padding=0.0, ignore_links=(), carve_margin=0.05,
+                        carve_window=1, merge_distance=None, clear_robot=True, **options):
+        """ADD a depth frame to the cloud, on the current stream -- where ``update_from_depth`` replaces the cloud by the frame.  The
+        cloud becomes a MAP: a store of ``capacity`` point slots on the device, the cloud built from it with the masked update, so
+        a point's index in every clearance or proximity record is its slot and stays that for as long as the point lives.  Seven
+        steps: ``backproject`` (``options``: its ``depth_scale``, ``z_min``, ``z_max``, ``frame``); with ``arm`` and ``q``, the
+        arm's own image out of the frame (``padding``, ``ignore_links``: as ``update_from_depth``); ``carve``: stored points the
+        frame sees through are released (``carve_margin``, ``carve_window``); with ``arm`` and ``clear_robot``, the stored points
+        the arm now touches are released as well (the arm is where it is: no obstacle is there); ``novel``: frame points the map
+        already holds within ``merge_distance`` (default: the cloud's radius, which then must not be 0) are dropped; ``append``: the
+        rest moves into free slots, and what finds none is dropped and counted; then the update from the store.
+
+        The first call, and the first after ``reset_map`` or after a plain ``update`` / ``update_from_depth`` (which end the
+        map), starts from an empty store.  Store, staging and workspace are allocated once (at ``capacity`` and H * W); after that the
+        call allocates nothing and, given CUDA tensors for ``depth``, ``camera_pose`` and ``q``, may be captured in a graph.  The
+        frame may have fewer or more pixels than ``capacity``.  Returns (store_points (capacity, 3), store_keep (capacity,)), the
+        store's own tensors; ``map_counts()`` tells what the call did.
+
+        What carving cannot know: there is no notion of unknown space and no confidence per point -- one frame that sees through a
+        point releases it --, and the world is taken to stand still while a frame is taken."""
+        import torch
+        merge = self.radius if merge_distance is None else float(merge_distance)
+        if merge_distance is None and not merge > 0.0:
+            raise ValueError("a cloud of radius 0 needs merge_distance")
+        if merge != merge:
+            raise ValueError("merge_distance is NaN")
+        unknown = set(options) - {"depth_scale", "z_min", "z_max", "frame"}
+        if unknown:
+            raise TypeError(f"integrate_depth got unexpected options {sorted(unknown)}")
+        d = _depth_array(torch, depth)
+        H, W = int(d.shape[0]), int(d.shape[1])
+        n = H * W
+        st, d = self._frame_stage(torch, d)
+        mp = self.__dict__.get("_map")
+        if mp is None or mp["n"] != n:
+            old = mp
+            mp = self._map = {"n": n, "counts": torch.zeros((3,), dtype=torch.int64, device="cuda"),
+                              "ws": torch.empty((append_workspace_bytes(self.capacity, n),), dtype=torch.uint8, device="cuda")}
+            mp["pts"] = old["pts"] if old is not None else torch.zeros((self.capacity, 3), dtype=torch.float64, device="cuda")
+            mp["keep"] = old["keep"] if old is not None else torch.zeros((self.capacity,), dtype=torch.uint8, device="cuda")
+        sp, sk = mp["pts"], mp["keep"]
+        if not self.__dict__.get("_map_live", False):
+            sk.zero_()
+            self.update(sp, keep=sk)
+        cam = {k: options[k] for k in ("depth_scale", "z_min", "z_max") if k in options}
+        T = _device_pose(torch, camera_pose, options.get("frame", "optical"), st["pose"])
+        pts, keep = backproject(d, intrinsics, T, out=(st["pts"], st["keep"]), **cam)
+        if arm is not None:
+            q = self._stage_q(torch, st, arm, q)
+            arm.cloud_self_filter(pts, q, self.radius, padding, keep=keep, ignore_links=ignore_links)
+        carve(sp, sk, d, intrinsics, T, carve_margin, carve_window, **cam)
+        if arm is not None and clear_robot:
+            arm.cloud_self_filter(sp, q, self.radius, padding, keep=sk, ignore_links=ignore_links)
+        self.novel(pts, keep, merge, held=sk)
+        append(sp, sk, pts, keep, counts=mp["counts"], workspace=mp["ws"])
+        self.update(sp, keep=sk)
+        self._map_live = True
+        return sp, sk
+
+    def map_counts(self):
+        """{"held", "appended", "dropped"} of the last ``integrate_depth``: the slots held after it, the frame points it filed and
+        the ones that found no free slot.  Synchronises, like ``count``."""
+        mp = self.__dict__.get("_map")
+        if mp is None:
+            raise ValueError("no frame has been integrated")
+        self.count()
+        held, appended, dropped = (int(x) for x in mp["counts"].cpu().numpy())
+        return {"held": held, "appended": appended, "dropped": dropped}
 
     def status(self) -> int:
         """0: the last update's points were all finite; 2: one was not -- until a clean update every configuration is reported

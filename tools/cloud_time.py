@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records,depth] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records,depth,fuse] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -43,6 +43,13 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
                 beside it the same launch for one workgroup's 256 points: the preamble and the launch, little else);
                 PointCloud.update(points, keep); the whole update_from_depth; and PointCloud.update on the surviving points as a
                 ready array -- the yardstick.  (profiles/cloud_depth_time.log)
+    fuse        (only when asked for) c2 and 640x480 float32 frames of the analytic scene of tests/cloud_fuse_cases.py (a wall and a
+                sphere in front of it, rendered by ray casting) from a ring of 8 camera poses around it, integrated into a map of
+                capacity 2^20 (radius 0.01, merge distance = the radius, carve margin 0.05, window 1, the arm's filter on the frame
+                and on the store).  The ring is integrated twice first (the counts of every call are printed); then, in that steady
+                state, at least 10 windows each: PointCloud.integrate_depth cycling over the ring; the prefixes 1, 1..2, ... 1..7 of its
+                seven steps on the last frame, a step's time being the difference of two (the steps that write are idempotent there);
+                and update_from_depth of the same frame on a cloud of its own.  (profiles/cloud_fuse_time.log)
 """
 import argparse
 import os
@@ -313,6 +320,72 @@ def depth_part(arm, dev, sm, chain, reps):
         say(f"    update(all {n} pixels, no mask)     {fmt(timed(lambda: cloud.update(pts), reps))}")
 
 
+def fuse_part(arm, dev, sm, chain, reps):
+    from numbotics_amd.physics import backproject, intrinsics_from_fov
+    from numbotics_amd.physics.pointcloud import append, carve
+    import cloud_fuse_cases as fc
+    reps = max(reps, 10)
+    W, H, cap, pad, margin, window = 640, 480, 1 << 20, 0.02, 0.05, 1
+    intr = intrinsics_from_fov(W, H, 50.0)
+    q0 = sample_q(chain, 4, seed=5)[2]
+    qt = torch.from_numpy(q0).cuda()
+    centre = np.array([0.3, 0.0, 0.5])
+    poses = []
+    for k in range(8):
+        a = -0.6 + 1.2 * k / 7.0                                                     # the ring: an arc of 1.7 m around the scene
+        pos = centre + 1.7 * np.array([-np.cos(a), np.sin(a), 0.0]) + [0.0, 0.0, 0.1 * (k % 3 - 1)]
+        poses.append(fc.look_along_x(pos, yaw=-a, pitch=0.06 * (k % 3 - 1)))
+    frames = [torch.from_numpy(fc.render(T, intr, H, W)).cuda() for T in poses]
+    Ts = [torch.from_numpy(np.ascontiguousarray(T)).cuda() for T in poses]
+    box = ([-0.1, -3.2, -1.3], [0.7, 3.2, 2.5])                                       # what the eight frames see of the wall
+    cloud = PointCloud(np.zeros((0, 3)), RADIUS, bounds=box, capacity=cap)
+    kw = dict(arm=arm, q=qt, padding=pad, carve_margin=margin, carve_window=window)
+    say(f"fuse: c2 ({sm.n_rshapes} shapes, all filtered), {W}x{H} float32 frames, ring of {len(poses)} poses, capacity {cap}, radius = merge {RADIUS}, "
+        f"carve margin {margin} window {window}, padding {pad}; cell {cloud.cell:.4f}, grid {tuple(int(d) for d in cloud.dims)}; >= {reps} windows")
+    for lap in range(2):
+        for k in range(len(poses)):
+            cloud.integrate_depth(frames[k], intr, Ts[k], **kw)
+            say(f"  lap {lap} pose {k}: {cloud.map_counts()}")
+    ring = [0]
+
+    def whole():
+        k = ring[0] = (ring[0] + 1) % len(poses)
+        cloud.integrate_depth(frames[k], intr, Ts[k], **kw)
+    say(f"    integrate_depth, over the ring      {fmt(timed(whole, reps))}")
+    k = len(poses) - 1
+    sp, sk = cloud.integrate_depth(frames[k], intr, Ts[k], **kw)
+    say(f"    steady state at the last pose: {cloud.map_counts()}")
+    say(f"    integrate_depth, the last frame     {fmt(timed(lambda: cloud.integrate_depth(frames[k], intr, Ts[k], **kw), reps))}")
+    st, mp = cloud._stage, cloud._map
+    pts, keep = st["pts"], st["keep"]
+    # a step's time is the difference of two prefixes of the sequence: each prefix starts from the back-projection, so that the
+    # frame's mask is the one the step sees inside the call (alone, after the call, steps 2 and 5 would find it all zeros)
+    def prefix(n):
+        backproject(frames[k], intr, Ts[k], out=(pts, keep))
+        if n >= 2:
+            dev.cloud_self_filter(pts, qt, RADIUS, pad, keep=keep)
+        if n >= 3:
+            carve(sp, sk, frames[k], intr, Ts[k], margin, window)
+        if n >= 4:
+            dev.cloud_self_filter(sp, qt, RADIUS, pad, keep=sk)
+        if n >= 5:
+            cloud.novel(pts, keep, RADIUS, held=sk)
+        if n >= 6:
+            append(sp, sk, pts, keep, counts=mp["counts"], workspace=mp["ws"])
+        if n >= 7:
+            cloud.update(sp, keep=sk)
+    before = 0.0
+    for n, name in enumerate(("backproject", "self-filter, the frame", "carve", "self-filter, the store", "novel", "append",
+                              f"update(store, keep), N = {cap}"), 1):
+        t = timed(lambda: prefix(n), reps)
+        say(f"    steps 1..{n} {fmt(t)}   step {n}, {name}: {t[0] - before:.3f} ms")
+        before = t[0]
+    held = cloud.count()
+    one = PointCloud(np.zeros((0, 3)), RADIUS, bounds=box, capacity=H * W)
+    say(f"    update_from_depth, the same frame   {fmt(timed(lambda: one.update_from_depth(frames[k], intr, Ts[k], arm=arm, q=qt, padding=pad), reps))}")
+    say(f"    the map holds {held} points, the single frame's cloud {one.count()}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -386,6 +459,8 @@ def main():
         records_part(dev, sm, shapes, q5, a.reps)
     if "depth" in only:
         depth_part(arm, dev, sm, chain, a.reps)
+    if "fuse" in only:
+        fuse_part(arm, dev, sm, chain, a.reps)
 
 
 if __name__ == "__main__":
