@@ -1229,12 +1229,17 @@ int32_t nbk_cloud_status(const nbk_cloud* c, int32_t* status) {
     return NBK_OK;
 }
 
-// the argument rules the two back-projection entries share
-static bool backproject_args_ok(const void* depth, int32_t depth_type, int32_t H, int32_t W, const DepthCam& cam, const double* T,
-                                const double* pts, const uint8_t* keep) {
+// the image and camera rules every entry that takes a frame shares
+static bool frame_args_ok(const void* depth, int32_t depth_type, int32_t H, int32_t W, const DepthCam& cam, const double* T) {
     if (H < 0 || W < 0 || (int64_t)H * (int64_t)W > CLOUD_MAX_POINTS) return false;
     if ((depth_type != 0 && depth_type != 1) || !depth_cam_valid(cam) || T == nullptr) return false;
-    return (int64_t)H * (int64_t)W == 0 || (depth != nullptr && pts != nullptr && keep != nullptr);
+    return (int64_t)H * (int64_t)W == 0 || depth != nullptr;
+}
+
+// the argument rules the two back-projection entries share: the frame's and the two outputs
+static bool backproject_args_ok(const void* depth, int32_t depth_type, int32_t H, int32_t W, const DepthCam& cam, const double* T,
+                                const double* pts, const uint8_t* keep) {
+    return frame_args_ok(depth, depth_type, H, W, cam, T) && ((int64_t)H * (int64_t)W == 0 || (pts != nullptr && keep != nullptr));
 }
 
 int32_t nbk_frame_cloud_backproject_host(const void* depth, int32_t depth_type, int32_t H, int32_t W, double depth_scale, double fx, double fy,
@@ -1287,13 +1292,10 @@ int32_t nbk_frame_cloud_self_filter(const nbk_model* m, const double* q0, const 
     return NBK_OK;
 }
 
-// the argument rules the two carving entries share: those of the back-projection for the image and the camera, the store and the
-// two parameters of the test
+// the argument rules the two carving entries share: the frame's, the store and the two parameters of the test
 static bool carve_args_ok(const void* depth, int32_t depth_type, int32_t H, int32_t W, const DepthCam& cam, const double* T, double margin,
                           int32_t window, const double* store_pts, int64_t M, const uint8_t* store_keep) {
-    if (H < 0 || W < 0 || (int64_t)H * (int64_t)W > CLOUD_MAX_POINTS) return false;
-    if ((depth_type != 0 && depth_type != 1) || !depth_cam_valid(cam) || T == nullptr) return false;
-    if ((int64_t)H * (int64_t)W > 0 && depth == nullptr) return false;
+    if (!frame_args_ok(depth, depth_type, H, W, cam, T)) return false;
     if (!(margin - margin == 0.0) || window < 0 || window > DEPTH_CARVE_MAX_WINDOW) return false;
     return M >= 0 && M <= CLOUD_MAX_POINTS && (M == 0 || (store_pts != nullptr && store_keep != nullptr));
 }

@@ -108,6 +108,19 @@ def _depth_array(torch, depth):
     return t
 
 
+def _device_points(torch, points):
+    """``points`` as a contiguous (N, 3) float64 CUDA tensor: one on the device as it is, anything else by one copy."""
+    if torch.is_tensor(points):
+        t = points
+        if not t.is_cuda or t.dtype != torch.float64:
+            raise ValueError("points on the device must be a float64 CUDA tensor")
+        if t.ndim != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError(f"points must be a contiguous (N, 3) tensor, got {tuple(t.shape)}")
+        return t
+    a = np.ascontiguousarray(np.asarray(points, dtype=np.float64)).reshape(-1, 3)
+    return torch.from_numpy(a).to("cuda")
+
+
 def _device_keep(torch, keep, n):
     """``keep`` as a contiguous (n,) uint8 CUDA tensor (a bool tensor is read as it is: one byte each)."""
     if torch.is_tensor(keep):
@@ -141,32 +154,59 @@ def _device_pose(torch, camera_pose, frame, stage=None):
             raise ValueError(f"frame must be 'optical' or 'numbotics', got {frame!r}")
     else:
         host = torch.from_numpy(optical_pose(camera_pose, frame))
-        if stage is not None:
-            T = stage.copy_(host)
-        else:
-            T = host.to("cuda")
+        T = host.to("cuda") if stage is None else stage.copy_(host)
     return T
+
+
+class _Frame:
+    """One depth frame as every nbk_frame_cloud_* image entry takes it, built once per call: ``depth`` by ``_depth_array`` (the one depth
+    rule), ``H``, ``W``, ``pose`` (the optical pose) and ``args``, the twelve arguments those entries start with: depth, depth_type
+    (0: float32, 1: 16 bits), H, W, depth_scale, fx, fy, cx, cy, T, z_min, z_max.  ``device=False``, for the host entries: the image
+    stays in host memory, the pose is ``optical_pose``'s.  Else a host image goes to the device -- through ``stage.depth`` when a
+    ``_FrameStage`` is given, which is fitted to the frame first -- and the pose is ``_device_pose``'s (through ``stage.pose``)."""
+
+    __slots__ = ("depth", "H", "W", "pose", "args")
+
+    def __init__(self, torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, device=True, stage=None):
+        d = _depth_array(torch, depth)
+        self.H, self.W = H, W = int(d.shape[0]), int(d.shape[1])
+        fx, fy, cx, cy = _intrinsics(intrinsics)
+        if not device:
+            T = torch.from_numpy(optical_pose(camera_pose, frame))
+        else:
+            if stage is not None:
+                stage.fit(torch, H, W, d.dtype)
+            if not d.is_cuda:
+                d = d.to("cuda") if stage is None else stage.depth.copy_(d)
+            T = _device_pose(torch, camera_pose, frame, None if stage is None else stage.pose)
+        self.depth, self.pose = d, T
+        self.args = (d.data_ptr() if H * W > 0 else None, 0 if d.dtype == torch.float32 else 1, H, W, float(depth_scale), fx, fy, cx, cy,
+                     T.data_ptr(), float(z_min), float(z_max))
+
+
+def _stream(torch):
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def backproject_host(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical"):
     """``backproject`` by the library's own routine on the host (nbk_frame_cloud_backproject_host; no GPU needed): NumPy in, NumPy
     (points (H * W, 3), keep (H * W,) uint8) out, the bits of the device's."""
-    a = np.asarray(depth)
-    if a.ndim != 2 or a.dtype not in (np.float32, np.uint16, np.int16):
-        raise ValueError("depth must be a (H, W) float32 or 16-bit image")
-    a = np.ascontiguousarray(a)
-    fx, fy, cx, cy = _intrinsics(intrinsics)
-    T = optical_pose(camera_pose, frame)
-    H, W = a.shape
-    pts = np.empty((H * W, 3), dtype=np.float64)
-    keep = np.empty((H * W,), dtype=np.uint8)
-    _lib.check(_lib.load().nbk_frame_cloud_backproject_host(a.ctypes.data, 0 if a.dtype == np.float32 else 1, H, W, float(depth_scale), fx, fy,
-                                                      cx, cy, T.ctypes.data, float(z_min), float(z_max), pts.ctypes.data, keep.ctypes.data),
-               "nbk_frame_cloud_backproject_host")
+    import torch
+    f = _Frame(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, device=False)
+    pts = np.empty((f.H * f.W, 3), dtype=np.float64)
+    keep = np.empty((f.H * f.W,), dtype=np.uint8)
+    _lib.check(_lib.load().nbk_frame_cloud_backproject_host(*f.args, pts.ctypes.data, keep.ctypes.data), "nbk_frame_cloud_backproject_host")
     return pts, keep
 
 
-def backproject(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical", out=None, _pose_stage=None):
+def _backproject(torch, f, pts, keep):
+    n = f.H * f.W
+    _lib.check(_lib.load().nbk_frame_cloud_backproject(*f.args, pts.data_ptr() if n > 0 else None, keep.data_ptr() if n > 0 else None,
+                                                       _stream(torch)), "nbk_frame_cloud_backproject")
+    return pts, keep
+
+
+def backproject(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical", out=None):
     """A depth image to world points on the current stream (nbk_frame_cloud_backproject) -> (points (H * W, 3) float64, keep (H * W,)
     uint8), CUDA tensors; point ``v * W + u`` is pixel (u, v).  ``depth``: (H, W), NumPy or a CUDA tensor, float32 (times
     ``depth_scale``: metres) or 16-bit raw units (a torch int16 / uint16 tensor is read as unsigned bits); the metric depth along
@@ -177,51 +217,42 @@ def backproject(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0, z_ma
     holes -- get keep 0 and the point (0, 0, 0).  ``out``: (points, keep) tensors to write into."""
     from numbotics_amd.engine import _require_gpu
     torch = _require_gpu()
-    d = _depth_array(torch, depth)
-    if not d.is_cuda:
-        d = d.to("cuda")
-    H, W = int(d.shape[0]), int(d.shape[1])
-    fx, fy, cx, cy = _intrinsics(intrinsics)
-    T = _device_pose(torch, camera_pose, frame, _pose_stage)
+    f = _Frame(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame)
+    n = f.H * f.W
     if out is None:
-        pts = torch.empty((H * W, 3), dtype=torch.float64, device=d.device)
-        keep = torch.empty((H * W,), dtype=torch.uint8, device=d.device)
+        pts = torch.empty((n, 3), dtype=torch.float64, device=f.depth.device)
+        keep = torch.empty((n,), dtype=torch.uint8, device=f.depth.device)
     else:
         pts, keep = out
-        if not (torch.is_tensor(pts) and pts.is_cuda and pts.dtype == torch.float64 and tuple(pts.shape) == (H * W, 3) and pts.is_contiguous()
-                and torch.is_tensor(keep) and keep.is_cuda and keep.dtype == torch.uint8 and tuple(keep.shape) == (H * W,) and keep.is_contiguous()):
-            raise ValueError(f"out must be contiguous CUDA tensors: float64 ({H * W}, 3) and uint8 ({H * W},)")
-    n = H * W
-    _lib.check(_lib.load().nbk_frame_cloud_backproject(d.data_ptr() if n > 0 else None, 0 if d.dtype == torch.float32 else 1, H, W,
-                                                 float(depth_scale), fx, fy, cx, cy, T.data_ptr(), float(z_min), float(z_max),
-                                                 pts.data_ptr() if n > 0 else None, keep.data_ptr() if n > 0 else None,
-                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_backproject")
-    return pts, keep
+        if not (torch.is_tensor(pts) and pts.is_cuda and pts.dtype == torch.float64 and tuple(pts.shape) == (n, 3) and pts.is_contiguous()
+                and torch.is_tensor(keep) and keep.is_cuda and keep.dtype == torch.uint8 and tuple(keep.shape) == (n,) and keep.is_contiguous()):
+            raise ValueError(f"out must be contiguous CUDA tensors: float64 ({n}, 3) and uint8 ({n},)")
+    return _backproject(torch, f, pts, keep)
 
 
 def carve_host(points, keep, depth, intrinsics, camera_pose, margin, window=1, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical"):
     """``carve`` by the library's own routine on the host (nbk_frame_cloud_carve_host; no GPU needed): NumPy in, the new mask (M,)
     uint8 out (``keep`` itself is not modified), the bits of the device's."""
-    a = np.asarray(depth)
-    if a.ndim != 2 or a.dtype not in (np.float32, np.uint16, np.int16):
-        raise ValueError("depth must be a (H, W) float32 or 16-bit image")
-    a = np.ascontiguousarray(a)
+    import torch
+    f = _Frame(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, device=False)
     pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64)).reshape(-1, 3)
     out = np.ascontiguousarray(np.asarray(keep)).astype(np.uint8)
     M = pts.shape[0]
     if out.shape != (M,):
         raise ValueError(f"keep must have shape ({M},), got {out.shape}")
-    fx, fy, cx, cy = _intrinsics(intrinsics)
-    T = optical_pose(camera_pose, frame)
-    H, W = a.shape
-    _lib.check(_lib.load().nbk_frame_cloud_carve_host(a.ctypes.data, 0 if a.dtype == np.float32 else 1, H, W, float(depth_scale), fx, fy, cx, cy,
-                                                      T.ctypes.data, float(z_min), float(z_max), float(margin), int(window),
-                                                      pts.ctypes.data, M, out.ctypes.data), "nbk_frame_cloud_carve_host")
+    _lib.check(_lib.load().nbk_frame_cloud_carve_host(*f.args, float(margin), int(window), pts.ctypes.data, M, out.ctypes.data),
+               "nbk_frame_cloud_carve_host")
     return out
 
 
-def carve(points, keep, depth, intrinsics, camera_pose, margin, window=1, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical",
-          _pose_stage=None):
+def _carve(torch, f, margin, window, pts, k):
+    M = int(pts.shape[0])
+    _lib.check(_lib.load().nbk_frame_cloud_carve(*f.args, float(margin), int(window), pts.data_ptr() if M > 0 else None, M,
+                                                 k.data_ptr() if M > 0 else None, _stream(torch)), "nbk_frame_cloud_carve")
+    return k
+
+
+def carve(points, keep, depth, intrinsics, camera_pose, margin, window=1, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical"):
     """Free-space carving on the current stream (nbk_frame_cloud_carve): a stored point the frame sees THROUGH is released.
     ``points`` (M, 3) float64 and ``keep`` (M,) uint8 -- CUDA tensors: ``keep`` is worked on in place and returned; NumPy: a new
     device mask is returned.  ``depth``, ``intrinsics``, ``camera_pose`` and the options are ``backproject``'s.  ``keep[i]`` goes to
@@ -230,20 +261,9 @@ def carve(points, keep, depth, intrinsics, camera_pose, margin, window=1, depth_
     A hole in the window, a point behind the measured surface (occluded) or outside the image: no evidence, the point stays."""
     from numbotics_amd.engine import _require_gpu
     torch = _require_gpu()
-    d = _depth_array(torch, depth)
-    if not d.is_cuda:
-        d = d.to("cuda")
-    H, W = int(d.shape[0]), int(d.shape[1])
-    fx, fy, cx, cy = _intrinsics(intrinsics)
-    T = _device_pose(torch, camera_pose, frame, _pose_stage)
-    pts = PointCloud._device_points(torch, points)
-    M = int(pts.shape[0])
-    k = _device_keep(torch, keep, M)
-    _lib.check(_lib.load().nbk_frame_cloud_carve(d.data_ptr() if H * W > 0 else None, 0 if d.dtype == torch.float32 else 1, H, W,
-                                                 float(depth_scale), fx, fy, cx, cy, T.data_ptr(), float(z_min), float(z_max), float(margin),
-                                                 int(window), pts.data_ptr() if M > 0 else None, M, k.data_ptr() if M > 0 else None,
-                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_carve")
-    return k
+    f = _Frame(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame)
+    pts = _device_points(torch, points)
+    return _carve(torch, f, margin, window, pts, _device_keep(torch, keep, int(pts.shape[0])))
 
 
 def append_workspace_bytes(capacity, n):
@@ -260,29 +280,77 @@ def append(store_points, store_keep, points, keep, counts=None, slot_of=None, wo
     (3,) int64 receives (slots held afterwards, appended, dropped); ``slot_of`` (N,) int32, optional, the slot of each new point
     or -1.  ``workspace``: a uint8 CUDA tensor of ``append_workspace_bytes`` bytes (allocated when not given).  Deterministic: ranks
     by prefix sums, no atomics.  -> counts."""
-    import torch
-    sp = PointCloud._device_points(torch, store_points)
+    from numbotics_amd.engine import _require_gpu
+    torch = _require_gpu()
+    sp = _device_points(torch, store_points)
     M = int(sp.shape[0])
     sk = _device_keep(torch, store_keep, M)
     if not (torch.is_tensor(store_keep) and store_keep.dtype == torch.uint8):
         raise ValueError("store_keep must be a uint8 CUDA tensor: it is written in place")
-    p = PointCloud._device_points(torch, points)
+    p = _device_points(torch, points)
     N = int(p.shape[0])
     k = _device_keep(torch, keep, N)
     if counts is None:
         counts = torch.empty((3,), dtype=torch.int64, device="cuda")
-    need = append_workspace_bytes(M, N)
     if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device="cuda")
+        workspace = torch.empty((append_workspace_bytes(M, N),), dtype=torch.uint8, device="cuda")
     if slot_of is not None and not (slot_of.is_cuda and slot_of.dtype == torch.int32 and tuple(slot_of.shape) == (N,) and slot_of.is_contiguous()):
         raise ValueError(f"slot_of must be a contiguous int32 CUDA tensor of shape ({N},)")
     if not (counts.is_cuda and counts.dtype == torch.int64 and tuple(counts.shape) == (3,) and counts.is_contiguous()):
         raise ValueError("counts must be a contiguous int64 CUDA tensor of shape (3,)")
     _lib.check(_lib.load().nbk_frame_cloud_append(sp.data_ptr(), sk.data_ptr(), M, p.data_ptr() if N > 0 else None, k.data_ptr() if N > 0 else None,
                                                   N, counts.data_ptr(), slot_of.data_ptr() if slot_of is not None and N > 0 else None,
-                                                  workspace.data_ptr(), int(workspace.numel()),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_append")
+                                                  workspace.data_ptr(), int(workspace.numel()), _stream(torch)), "nbk_frame_cloud_append")
     return counts
+
+
+class _FrameStage:
+    """The tensors a frame passes through on its way into a cloud: ``pts`` (H * W, 3), ``keep`` (H * W,) and ``depth`` (H, W), re-made
+    when H, W or the depth type change; ``pose`` (3, 4); ``q`` (dof,), re-made when the arm's dof changes."""
+
+    def __init__(self):
+        self.key = self.pts = self.keep = self.depth = self.pose = self.q = None
+
+    def fit(self, torch, H, W, dtype):
+        if self.key != (H, W, dtype):
+            self.key = (H, W, dtype)
+            self.pts = torch.empty((H * W, 3), dtype=torch.float64, device="cuda")
+            self.keep = torch.empty((H * W,), dtype=torch.uint8, device="cuda")
+            self.depth = torch.empty((H, W), dtype=dtype, device="cuda")
+            self.pose = torch.empty((3, 4), dtype=torch.float64, device="cuda")
+
+    def device_q(self, torch, dof, q):
+        """q as a device tensor: a host q goes through the stage's."""
+        if q is None:
+            raise ValueError("the self-filter needs the configuration q the frame was taken at")
+        if torch.is_tensor(q):
+            return q
+        if self.q is None or self.q.shape[0] != dof:
+            self.q = torch.empty((dof,), dtype=torch.float64, device="cuda")
+        return self.q.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(q, dtype=np.float64)).reshape(dof)))
+
+
+class _Map:
+    """What ``integrate_depth`` keeps between frames: the store ``pts`` (capacity, 3) and ``keep`` (capacity,) and ``counts`` (3,),
+    allocated once; the append workspace ``ws``, sized for frames of ``n`` pixels and re-made when ``n`` changes; and ``live``: the
+    cloud's points are the store's."""
+
+    def __init__(self):
+        self.pts = self.keep = self.counts = self.ws = self.n = None
+        self.live = False
+
+    def end(self):
+        """What a plain update and ``reset_map`` do to the map: the tensors stay, the next integration starts from an empty store."""
+        self.live = False
+
+    def fit(self, torch, capacity, n):
+        if self.pts is None:
+            self.pts = torch.zeros((capacity, 3), dtype=torch.float64, device="cuda")
+            self.keep = torch.zeros((capacity,), dtype=torch.uint8, device="cuda")
+            self.counts = torch.zeros((3,), dtype=torch.int64, device="cuda")
+        if self.n != n:
+            self.n, self.ws = n, torch.empty((append_workspace_bytes(capacity, n),), dtype=torch.uint8, device="cuda")
+        return self
 
 
 class PointCloud:
@@ -299,7 +367,7 @@ class PointCloud:
         radius = float(radius)
         if not radius >= 0.0:
             raise ValueError(f"radius must be >= 0, got {radius}")
-        t = self._device_points(torch, points)
+        t = _device_points(torch, points)
         n = int(t.shape[0])
         if bounds is None:
             if n == 0:
@@ -333,20 +401,9 @@ class PointCloud:
                    "nbk_cloud_create")
         self._h = h
         self.n = 0
-        self._points = None
+        self._points = self._keep = None      # the tensors of the last update: held so that they outlive the asynchronous work
+        self._stage, self._map = _FrameStage(), _Map()
         self.update(t)
-
-    @staticmethod
-    def _device_points(torch, points):
-        if torch.is_tensor(points):
-            t = points
-            if not t.is_cuda or t.dtype != torch.float64:
-                raise ValueError("points on the device must be a float64 CUDA tensor")
-            if t.ndim != 2 or t.shape[1] != 3 or not t.is_contiguous():
-                raise ValueError(f"points must be a contiguous (N, 3) tensor, got {tuple(t.shape)}")
-            return t
-        a = np.ascontiguousarray(np.asarray(points, dtype=np.float64)).reshape(-1, 3)
-        return torch.from_numpy(a).to("cuda")
 
     def update(self, points, radius=None, keep=None):
         """Replace the points (and, optionally, the radius) on the current stream: nbk_cloud_set_points.  A CUDA tensor is read in
@@ -356,23 +413,23 @@ class PointCloud:
         it holds under their indices in ``points``.  ``n`` is the number submitted (what ``capacity`` bounds); ``count()`` the
         number held."""
         import torch
-        t = self._device_points(torch, points)
-        n = int(t.shape[0])              # (more than `capacity` points: the library refuses the update, NBK_ERR_INVALID)
         radius = self.radius if radius is None else float(radius)
         if not radius >= 0.0:
             raise ValueError(f"radius must be >= 0, got {radius}")
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if keep is None:
-            _lib.check(self._lib.nbk_cloud_set_points(self._h, t.data_ptr() if n > 0 else None, n, radius, stream), "nbk_cloud_set_points")
+        t = _device_points(torch, points)
+        self._set_points(torch, t, None if keep is None else _device_keep(torch, keep, int(t.shape[0])), radius)
+        self._map.end()
+
+    def _set_points(self, torch, t, k, radius):
+        """The update itself, from device tensors: what ``update`` issues, and ``integrate_depth`` from its store."""
+        n = int(t.shape[0])              # (more than `capacity` points: the library refuses the update, NBK_ERR_INVALID)
+        if k is None:
+            _lib.check(self._lib.nbk_cloud_set_points(self._h, t.data_ptr() if n > 0 else None, n, radius, _stream(torch)), "nbk_cloud_set_points")
         else:
-            k = _device_keep(torch, keep, n)
             _lib.check(self._lib.nbk_frame_cloud_set_points(self._h, t.data_ptr() if n > 0 else None, k.data_ptr() if n > 0 else None,
-                                                             n, radius, stream), "nbk_frame_cloud_set_points")
-            self._keep = k
+                                                             n, radius, _stream(torch)), "nbk_frame_cloud_set_points")
         self.radius = radius             # (only now: a refused update leaves the object as the device has it)
-        self._points = t
-        self.n = n
-        self._map_live = False           # (a plain update ends a map: integrate_depth sets the flag again after its own)
+        self._points, self._keep, self.n = t, k, n
 
     def count(self) -> int:
         """The points the cloud holds: those of the last update that its ``keep`` let through (all of them without one).
@@ -381,52 +438,34 @@ class PointCloud:
         _lib.check(self._lib.nbk_frame_cloud_count(self._h, C.byref(out)), "nbk_frame_cloud_count")
         return int(out.value)
 
-    def _frame_stage(self, torch, d):
-        """The staging tensors of a frame of d's size and type (allocated on the first call with that size and type), and d on the
-        device: a host image is copied into the stage's."""
-        H, W = int(d.shape[0]), int(d.shape[1])
-        st = self.__dict__.get("_stage")
-        if st is None or st["key"] != (H * W, d.dtype):
-            st = self._stage = {"key": (H * W, d.dtype), "pts": torch.empty((H * W, 3), dtype=torch.float64, device="cuda"),
-                                "keep": torch.empty((H * W,), dtype=torch.uint8, device="cuda"),
-                                "pose": torch.empty((3, 4), dtype=torch.float64, device="cuda"),
-                                "depth": torch.empty((H, W), dtype=d.dtype, device="cuda"), "q": None}
-        if not d.is_cuda:
-            st["depth"].copy_(d.reshape(H, W))
-            d = st["depth"]
-        return st, d
+    def _frame_points(self, torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, arm, q, padding, ignore_links):
+        """The common start of ``update_from_depth`` and ``integrate_depth``: the frame's description, a host image, pose or q
+        through the stage, the back-projection into the stage's tensors and, with ``arm``, its image out of the mask.
+        -> (the frame on the device, points, keep, q on the device)."""
+        st = self._stage
+        f = _Frame(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, stage=st)
+        pts, keep = _backproject(torch, f, st.pts, st.keep)
+        if arm is not None:
+            q = st.device_q(torch, arm.dof, q)
+            arm.cloud_self_filter(pts, q, self.radius, padding, keep=keep, ignore_links=ignore_links)
+        return f, pts, keep, q
 
-    def _stage_q(self, torch, st, arm, q):
-        """q as a device tensor: a host q goes through the stage's."""
-        if q is None:
-            raise ValueError("the self-filter needs the configuration q the frame was taken at")
-        if torch.is_tensor(q):
-            return q
-        if st["q"] is None:
-            st["q"] = torch.empty((arm.dof,), dtype=torch.float64, device="cuda")
-        st["q"].copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(q, dtype=np.float64)).reshape(arm.dof)))
-        return st["q"]
-
-    def update_from_depth(self, depth, intrinsics, camera_pose, arm=None, q=None, padding=0.0, ignore_links=(), **options):
-        """A depth frame to the cloud's points on the current stream, in three steps: ``backproject`` (``options``: its
-        ``depth_scale``, ``z_min``, ``z_max``, ``frame``), then -- with ``arm`` and its configuration ``q`` when the frame was
+    def update_from_depth(self, depth, intrinsics, camera_pose, arm=None, q=None, padding=0.0, ignore_links=(), depth_scale=1.0, z_min=0.0,
+                          z_max=np.inf, frame="optical"):
+        """A depth frame to the cloud's points on the current stream, in three steps: ``backproject`` (with its ``depth_scale``,
+        ``z_min``, ``z_max``, ``frame``), then -- with ``arm`` and its configuration ``q`` when the frame was
         taken -- ``arm.cloud_self_filter`` at the cloud's radius and ``padding`` (``ignore_links``: links whose image stays in),
         then ``update(points, keep=keep)``.  Point i is pixel ``v * W + u``; ``in_collision_with_cloud(q, cloud, padding)`` is
         False afterwards for the links that were filtered, exactly.  H * W must not exceed ``capacity``.
 
         The staging tensors (points, mask, pose, q and the frame itself) are allocated once, on the first call with a given
-        H * W and depth type; after that the call allocates nothing and -- given CUDA tensors for ``depth``, ``camera_pose`` and
+        H, W and depth type; after that the call allocates nothing and -- given CUDA tensors for ``depth``, ``camera_pose`` and
         ``q``, which are read when the work runs -- issues no host copy, so it may be captured in a graph that is replayed with
         those tensors rewritten in place.  Returns (points, keep), the staging tensors themselves."""
         import torch
-        d = _depth_array(torch, depth)
-        H, W = int(d.shape[0]), int(d.shape[1])
-        st, d = self._frame_stage(torch, d)
-        pts, keep = backproject(d, intrinsics, camera_pose, out=(st["pts"], st["keep"]), _pose_stage=st["pose"], **options)
-        if arm is not None:
-            q = self._stage_q(torch, st, arm, q)
-            arm.cloud_self_filter(pts, q, self.radius, padding, keep=keep, ignore_links=ignore_links)
-        self.update(pts, keep=keep)
+        _, pts, keep, _ = self._frame_points(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, arm, q, padding, ignore_links)
+        self._set_points(torch, pts, keep, self.radius)
+        self._map.end()
         return pts, keep
 
     def novel(self, points, keep, merge_distance, held=None):
@@ -438,26 +477,26 @@ class PointCloud:
         are read when the work runs: an empty cloud, or one whose status is set, leaves ``keep`` as it is.  The points are not
         thinned against each other."""
         import torch
-        p = self._device_points(torch, points)
+        p = _device_points(torch, points)
         n = int(p.shape[0])
         k = _device_keep(torch, keep, n)
         h = None if held is None else _device_keep(torch, held, self.n)
         _lib.check(self._lib.nbk_frame_cloud_novel(self._h, p.data_ptr() if n > 0 else None, n, float(merge_distance),
                                                    h.data_ptr() if h is not None and self.n > 0 else None, k.data_ptr() if n > 0 else None,
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "nbk_frame_cloud_novel")
+                                                   _stream(torch)), "nbk_frame_cloud_novel")
         return k
 
     def reset_map(self):
         """Forget the map: the next ``integrate_depth`` starts from an empty store.  (Issues nothing; the cloud keeps its points
         until then.)"""
-        self._map_live = False
+        self._map.end()
 
     def integrate_depth(self, depth, intrinsics, camera_pose, arm=None, q=None, padding=0.0, ignore_links=(), carve_margin=0.05,
-                        carve_window=1, merge_distance=None, clear_robot=True, **options):
+                        carve_window=1, merge_distance=None, clear_robot=True, depth_scale=1.0, z_min=0.0, z_max=np.inf, frame="optical"):
         """ADD a depth frame to the cloud, on the current stream -- where ``update_from_depth`` replaces the cloud by the frame.  The
         cloud becomes a MAP: a store of ``capacity`` point slots on the device, the cloud built from it with the masked update, so
         a point's index in every clearance or proximity record is its slot and stays that for as long as the point lives.  Seven
-        steps: ``backproject`` (``options``: its ``depth_scale``, ``z_min``, ``z_max``, ``frame``); with ``arm`` and ``q``, the
+        steps: ``backproject`` (with its ``depth_scale``, ``z_min``, ``z_max``, ``frame``); with ``arm`` and ``q``, the
         arm's own image out of the frame (``padding``, ``ignore_links``: as ``update_from_depth``); ``carve``: stored points the
         frame sees through are released (``carve_margin``, ``carve_window``); with ``arm`` and ``clear_robot``, the stored points
         the arm now touches are released as well (the arm is where it is: no obstacle is there); ``novel``: frame points the map
@@ -478,47 +517,28 @@ class PointCloud:
             raise ValueError("a cloud of radius 0 needs merge_distance")
         if merge != merge:
             raise ValueError("merge_distance is NaN")
-        unknown = set(options) - {"depth_scale", "z_min", "z_max", "frame"}
-        if unknown:
-            raise TypeError(f"integrate_depth got unexpected options {sorted(unknown)}")
-        d = _depth_array(torch, depth)
-        H, W = int(d.shape[0]), int(d.shape[1])
-        n = H * W
-        st, d = self._frame_stage(torch, d)
-        mp = self.__dict__.get("_map")
-        if mp is None or mp["n"] != n:
-            old = mp
-            mp = self._map = {"n": n, "counts": torch.zeros((3,), dtype=torch.int64, device="cuda"),
-                              "ws": torch.empty((append_workspace_bytes(self.capacity, n),), dtype=torch.uint8, device="cuda")}
-            mp["pts"] = old["pts"] if old is not None else torch.zeros((self.capacity, 3), dtype=torch.float64, device="cuda")
-            mp["keep"] = old["keep"] if old is not None else torch.zeros((self.capacity,), dtype=torch.uint8, device="cuda")
-        sp, sk = mp["pts"], mp["keep"]
-        if not self.__dict__.get("_map_live", False):
+        f, pts, keep, q = self._frame_points(torch, depth, intrinsics, camera_pose, depth_scale, z_min, z_max, frame, arm, q, padding, ignore_links)
+        mp = self._map.fit(torch, self.capacity, f.H * f.W)
+        sp, sk = mp.pts, mp.keep
+        if not mp.live:
             sk.zero_()
-            self.update(sp, keep=sk)
-        cam = {k: options[k] for k in ("depth_scale", "z_min", "z_max") if k in options}
-        T = _device_pose(torch, camera_pose, options.get("frame", "optical"), st["pose"])
-        pts, keep = backproject(d, intrinsics, T, out=(st["pts"], st["keep"]), **cam)
-        if arm is not None:
-            q = self._stage_q(torch, st, arm, q)
-            arm.cloud_self_filter(pts, q, self.radius, padding, keep=keep, ignore_links=ignore_links)
-        carve(sp, sk, d, intrinsics, T, carve_margin, carve_window, **cam)
+            self._set_points(torch, sp, sk, self.radius)
+            mp.live = True
+        _carve(torch, f, carve_margin, carve_window, sp, sk)
         if arm is not None and clear_robot:
             arm.cloud_self_filter(sp, q, self.radius, padding, keep=sk, ignore_links=ignore_links)
         self.novel(pts, keep, merge, held=sk)
-        append(sp, sk, pts, keep, counts=mp["counts"], workspace=mp["ws"])
-        self.update(sp, keep=sk)
-        self._map_live = True
+        append(sp, sk, pts, keep, counts=mp.counts, workspace=mp.ws)
+        self._set_points(torch, sp, sk, self.radius)
         return sp, sk
 
     def map_counts(self):
         """{"held", "appended", "dropped"} of the last ``integrate_depth``: the slots held after it, the frame points it filed and
         the ones that found no free slot.  Synchronises, like ``count``."""
-        mp = self.__dict__.get("_map")
-        if mp is None:
+        if self._map.counts is None:
             raise ValueError("no frame has been integrated")
         self.count()
-        held, appended, dropped = (int(x) for x in mp["counts"].cpu().numpy())
+        held, appended, dropped = (int(x) for x in self._map.counts.cpu().numpy())
         return {"held": held, "appended": appended, "dropped": dropped}
 
     def status(self) -> int:

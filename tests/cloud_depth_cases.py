@@ -17,7 +17,7 @@ ROBOT_IDS = [f"{n}-{'bullet' if m else 'sharp'}" for n, m in ROBOTS]
 # (radius, padding): the three pairs the band was drawn for, and one negative padding
 FILTER_PARAMS = ((0.01, 0.02), (0.0, 0.0), (0.005, 0.05), (0.01, -0.005))
 # half width of the box around each link frame the points near the robot are drawn in
-BOX = {"c1": 0.07, "c2m": 0.07, "tree": 0.07, "k9": 0.07}
+BOX = {"c1": 0.07, "c2m": 0.07, "tree": 0.07, "k9": 0.07, "k16": 0.07}
 PER_SHAPE = 12
 SHAPES = ((1, 1), (1, 64), (5, 7), (17, 33))        # (H, W): 1x1, 64x1, 7x5 and 33x17 images (width x height)
 

@@ -10,7 +10,7 @@ import pytest
 import cloud_depth_cases as dc
 from numbotics_amd import _lib
 from numbotics_amd.physics import intrinsics_from_fov
-from numbotics_amd.physics.pointcloud import backproject_host, optical_pose
+from numbotics_amd.physics.pointcloud import _depth_array, backproject_host, carve_host, optical_pose
 
 INVALID, UNSUPPORTED = -1, -4
 
@@ -58,6 +58,54 @@ def test_backproject_host_signed_sixteen_bits_and_a_lone_hole():
     # z_max = +inf by default: a large finite depth counts, +inf never does
     pts, keep = backproject_host(np.array([[1e30, np.inf]], dtype=np.float32), (1.0, 1.0, 0.0, 0.0), np.eye(4))
     assert keep.tolist() == [1, 0]
+
+
+def test_one_depth_rule_for_the_host_twins_and_the_normaliser():
+    """float32 or 16 bits (int16 and uint16 carry the same bits), 2-D, a NumPy image made contiguous, a non-contiguous tensor refused:
+    ``backproject_host``, ``carve_host`` and ``_depth_array`` on host tensors accept and refuse the same images."""
+    import torch
+    intr, T = dc.intrinsics(2, 3), dc.camera_pose()
+    store = np.ascontiguousarray(backproject_host(np.full((2, 3), 0.5, dtype=np.float32), intr, T)[0])        # points in front of every pixel
+    ones = np.ones((store.shape[0],), dtype=np.uint8)
+
+    def twins(d, scale=1.0):
+        pts, keep = backproject_host(d, intr, T, depth_scale=scale)
+        return pts, keep, carve_host(store, ones, d, intr, T, 0.05, window=0, depth_scale=scale)
+
+    def norm(d):
+        return _depth_array(torch, torch.from_numpy(d) if isinstance(d, np.ndarray) else d).numpy()
+
+    f32 = dc.depth_image(2, 3, "f32")
+    u16 = np.array([[40000, 1200, 0], [3, 65535, 32768]], dtype=np.uint16)
+    # accepted: float32; uint16 and int16 views of one buffer are the same bits
+    a = twins(f32)
+    assert a[1].any() and not a[1].all() and not a[2].all(), "the float32 frame has holes and carves"
+    _bits_equal(norm(f32), f32, "float32 through the normaliser")
+    b, c = twins(u16, 0.0001), twins(u16.view(np.int16), 0.0001)
+    for x, y, what in zip(b, c, ("points", "keep", "carved mask")):
+        _bits_equal(x, y, f"int16 view: {what}")
+    _bits_equal(b[0], dc.backproject_ref(u16, intr, T, 0.0001)[0], "uint16 above 32767")
+    assert norm(u16.view(np.int16)).dtype == np.int16 and norm(u16.view(np.int16)).tobytes() == u16.tobytes()
+    if hasattr(torch, "uint16"):
+        t = _depth_array(torch, torch.from_numpy(u16.view(np.int16)).view(torch.uint16))
+        assert t.dtype == torch.int16 and t.numpy().tobytes() == u16.tobytes()
+    # a non-contiguous NumPy slice is its contiguous copy
+    wide = np.ascontiguousarray(np.repeat(f32, 2, axis=1))
+    cut = wide[:, ::2]
+    assert not cut.flags["C_CONTIGUOUS"] and np.array_equal(cut, f32, equal_nan=True)
+    for x, y, what in zip(twins(cut), a, ("points", "keep", "carved mask")):
+        _bits_equal(x, y, f"a NumPy slice: {what}")
+    _bits_equal(_depth_array(torch, cut).numpy(), f32, "a NumPy slice through the normaliser")
+    # refused: float64, three dimensions -- by all three; a non-contiguous tensor by the normaliser
+    for bad in (f32.astype(np.float64), np.zeros((2, 3), dtype=np.int32), np.zeros((2, 3, 1), dtype=np.float32), np.zeros((6,), dtype=np.float32)):
+        for call in (lambda: backproject_host(bad, intr, T), lambda: carve_host(store, ones, bad, intr, T, 0.05), lambda: norm(bad),
+                     lambda: _depth_array(torch, bad)):
+            with pytest.raises(ValueError):
+                call()
+    with pytest.raises(ValueError):
+        _depth_array(torch, torch.from_numpy(wide)[:, ::2])
+    with pytest.raises(ValueError):
+        _depth_array(torch, torch.from_numpy(f32).t())
 
 
 def test_numbotics_frame_is_the_permuted_optical_pose():

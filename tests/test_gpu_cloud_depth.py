@@ -14,6 +14,7 @@ from numbotics_amd.scenes import sample_q
 from test_gpu_parity import assert_bitwise, torch_cuda      # noqa: F401  (fixture)
 from cloud_cases import scan, cloud_mask, cloud_closest
 import cloud_depth_cases as dc
+import cloud_fuse_cases as fc
 import long_chain_cases as lc
 
 CUTS = (1, 63, 64, 65, 255, 256, 257)
@@ -315,13 +316,13 @@ def test_update_from_depth_in_one_graph(fresh_world, tmp_path, torch_cuda):
         cloud.update_from_depth(dt, intr, Tt, arm=arm, q=qt0, padding=PAD, ignore_links=[base], frame="numbotics")
         dev.cloud_validity(cloud, qt, PAD, shapes=shapes)
         side.synchronize()
-        stage = cloud._stage["pts"].data_ptr()
+        stage = cloud._stage.pts.data_ptr()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
             cloud.update_from_depth(dt, intr, Tt, arm=arm, q=qt0, padding=PAD, ignore_links=[base], frame="numbotics")
             mask = dev.cloud_validity(cloud, qt, PAD, shapes=shapes)
     torch.cuda.current_stream().wait_stream(side)
-    assert cloud._stage["pts"].data_ptr() == stage, "the captured call reused the staging tensors"
+    assert cloud._stage.pts.data_ptr() == stage, "the captured call reused the staging tensors"
     for k in (1, 2):
         dt.copy_(torch.from_numpy(frames[k][0]).cuda())
         Tt.copy_(torch.from_numpy(cams[k]).cuda())
@@ -330,3 +331,69 @@ def test_update_from_depth_in_one_graph(fresh_world, tmp_path, torch_cuda):
         torch.cuda.synchronize()
         assert np.array_equal(mask.cpu().numpy(), eager[k]), f"replay {k}"
     assert cloud.status() == 0
+
+
+# ---- 7. the stage follows the frame and the arm -----------------------------------------------------------------------------------
+def _small_frame(Hs, Ws, hole):
+    """An (Hs, Ws) float32 frame of six depths with one hole, and its intrinsics."""
+    d = np.linspace(0.5, 1.5, Hs * Ws).astype(np.float32)
+    d[hole] = 0.0
+    return np.ascontiguousarray(d.reshape(Hs, Ws)), dc.intrinsics(Hs, Ws)
+
+
+def test_frame_shape_change_remakes_the_stage(torch_cuda):
+    """A 3x2 host frame, then 2x3 ones -- the same pixel count, another shape -- through one cloud of capacity 6: each call leaves
+    what ``backproject`` gives for that frame alone, and the third call reuses the staging tensors of the second.  The same through
+    ``integrate_depth``, against the restatement of tests/cloud_fuse_cases.py."""
+    from numbotics_amd.physics import PointCloud, backproject
+    T = dc.camera_pose()
+    box = ([-3.0, -3.0, -3.0], [3.0, 3.0, 3.0])
+    frames = [_small_frame(3, 2, 1), _small_frame(2, 3, 4), _small_frame(2, 3, 2)]
+    cloud = PointCloud(np.zeros((0, 3)), RADIUS, bounds=box, capacity=6)
+    ptrs = []
+    for k, (d, intr) in enumerate(frames):
+        gp, gk = cloud.update_from_depth(d, intr, T)
+        bp, bk = backproject(d, intr, T)
+        rp, rk = dc.backproject_ref(d, intr, T)
+        assert rk.sum() == 5, "one hole in six pixels"
+        _bits(bk.cpu().numpy(), rk, f"frame {k}: backproject keep")
+        _bits(gk.cpu().numpy(), bk.cpu().numpy(), f"frame {k}: keep")
+        _bits(gp.cpu().numpy(), bp.cpu().numpy(), f"frame {k}: points")
+        _bits(gp.cpu().numpy(), rp, f"frame {k}: points against the restatement")
+        assert cloud.count() == int(rk.sum()) and cloud.status() == 0 and cloud.n == 6
+        ptrs.append((gp.data_ptr(), gk.data_ptr()))
+    assert ptrs[2] == ptrs[1], "the same shape again: nothing is re-made"
+    fused = PointCloud(np.zeros((0, 3)), RADIUS, bounds=box, capacity=6)
+    store = fc.empty_store(6)
+    for k, (d, intr) in enumerate(frames):
+        store, counts, _, _ = fc.integrate_ref(store, d, intr, T, RADIUS, 0.05, 0, RADIUS)
+        sp, sk = fused.integrate_depth(d, intr, T, carve_margin=0.05, carve_window=0)
+        _bits(sk.cpu().numpy(), store[1], f"fused frame {k}: store mask")
+        _bits(sp.cpu().numpy(), store[0], f"fused frame {k}: store points")
+        mc = fused.map_counts()
+        assert [mc["held"], mc["appended"], mc["dropped"]] == counts.tolist() and fused.count() == mc["held"], (k, mc, counts)
+        ptrs.append(fused._stage.pts.data_ptr())
+    assert ptrs[-1] == ptrs[-2], "the same shape again: nothing is re-made"
+
+
+def test_two_robots_filter_one_cloud(tmp_path, torch_cuda):
+    """One cloud, two arms of 9 and 16 joints, q from the host: the stage's q follows the arm, and each call's mask is the one
+    ``arm.cloud_self_filter`` gives directly."""
+    from numbotics_amd.physics import PointCloud, backproject
+    cloud = PointCloud(np.zeros((0, 3)), RADIUS, bounds=([-2.0, -2.0, -2.0], [2.0, 2.0, 2.0]), capacity=H * W)
+    robots = []
+    for name in ("k9", "k16"):
+        arm, chain, alive = lc.case(name, tmp_path)
+        sm, _ = arm._scene_device()
+        robots.append((name, arm, chain, alive, sm, lc.sample(chain, 4, 5)[2]))
+    assert [r[2].dof for r in robots] == [9, 16]
+    for name, arm, chain, alive, sm, q0 in robots + robots[:1]:
+        depth, intr = _frame(name, sm, q0)
+        bp, bk = backproject(depth, intr, CAM, frame="numbotics")
+        ref = arm.cloud_self_filter(bp, q0, RADIUS, PAD, keep=bk.clone()).cpu().numpy()
+        seen = bk.cpu().numpy()
+        assert 0 < ref.sum() < seen.sum(), f"{name}: the filter removes {seen.sum() - ref.sum()} of {seen.sum()} pixels -- not a mixed case"
+        gp, gk = cloud.update_from_depth(depth, intr, CAM, arm=arm, q=q0, padding=PAD, frame="numbotics")
+        _bits(gk.cpu().numpy(), ref, f"{name}: keep")
+        _bits(gp.cpu().numpy(), bp.cpu().numpy(), f"{name}: points")
+        assert cloud.count() == int(ref.sum()) and not arm.in_collision_with_cloud(q0, cloud, PAD)

@@ -356,8 +356,8 @@ def fuse_part(arm, dev, sm, chain, reps):
     sp, sk = cloud.integrate_depth(frames[k], intr, Ts[k], **kw)
     say(f"    steady state at the last pose: {cloud.map_counts()}")
     say(f"    integrate_depth, the last frame     {fmt(timed(lambda: cloud.integrate_depth(frames[k], intr, Ts[k], **kw), reps))}")
-    st, mp = cloud._stage, cloud._map
-    pts, keep = st["pts"], st["keep"]
+    mp = cloud._map
+    pts, keep = cloud._stage.pts, cloud._stage.keep
     # a step's time is the difference of two prefixes of the sequence: each prefix starts from the back-projection, so that the
     # frame's mask is the one the step sees inside the call (alone, after the call, steps 2 and 5 would find it all zeros)
     def prefix(n):
@@ -371,7 +371,7 @@ def fuse_part(arm, dev, sm, chain, reps):
         if n >= 5:
             cloud.novel(pts, keep, RADIUS, held=sk)
         if n >= 6:
-            append(sp, sk, pts, keep, counts=mp["counts"], workspace=mp["ws"])
+            append(sp, sk, pts, keep, counts=mp.counts, workspace=mp.ws)
         if n >= 7:
             cloud.update(sp, keep=sk)
     before = 0.0
