@@ -585,6 +585,57 @@ int32_t nbk_frame_cloud_append(double *store_pts /* DEVICE [M][3] */, uint8_t *s
                                int64_t workspace_bytes, void *stream);
 
 /*
+ * Rendered frames (additive): depth frames of the device scene, ray-cast.  Replaces World.depth_image (numbotics/physics/world.py:
+ * 363-398: computeViewMatrix, computeProjectionMatrixFOV, getCameraImage and the linearisation of its depth buffer) for the shapes a
+ * descriptor holds, and produces what nbk_frame_cloud_backproject consumes: the same pinhole, the same optical pose, depth along the
+ * view axis.  The scene of frame b is the selected robot shapes at row b of q (shape_bits as nbk_cloud_validity_batch) and, with
+ * draw_world != 0, the world shapes; q and T have B rows or one row that serves every frame (Bq, Bt).  One kernel, no allocation, no
+ * host synchronisation, capturable; q and T are read when the kernel runs.
+ *
+ * The surface is the set the collision predicates call distance 0: a pixel's ray is sphere-traced on the library's exact shape
+ * distance.  The point at depth z on pixel (u, v) is the back-projection's, xc = (((double)u - cx) * z) / fx, ... (depth_scale 1).
+ * With L = sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1) and R = (rho + margin) + (1e-6 |rho + margin| + 1e-7) of a shape's
+ * bounding ball, the ray's candidates are the shapes (planes apart) for which the span below is not empty; z starts at the smallest
+ * z0 and a step takes d, the minimum over the candidates, in the drawn order (selected robot shapes in the descriptor's device
+ * order, then world shapes), of the signed distance from the point to the shape.  d < eps: a hit at this z, labelled with the first
+ * shape that attains the minimum; otherwise z += d / L.  Past the largest z1, a nearer plane hit or z_far: a miss.  max_steps steps
+ * without a decision: unresolved.  A ray that starts inside a shape, or within eps of it, hits at its start (z_near at the least).
+ * Planes are intersected in closed form (h = n . (p(z_near) - c): h < eps hits at z_near; else z_near + h / -(n . w) where the ray
+ * descends, w the ray per unit depth in the world); a plane hit wins only where it is strictly nearer than the march's.
+ *
+ * depth (DEVICE) float32 [B][H][W]: the depth of a hit, `miss` otherwise.  label (DEVICE, optional) int32 [B][H][W]: the robot
+ * shape in the caller's order, n_rshapes + w for world shape w, -1 for a miss, -2 for an unresolved pixel.  counts (DEVICE, optional)
+ * int64 [3], cleared by the call: hit pixels, unresolved pixels, distance evaluations (integer sums: deterministic).  A frame whose q
+ * row or pose is not finite, and every frame while the world status of a movable descriptor is set, is unresolved in every pixel.
+ * Every pixel's result depends on its own ray alone (u - cx, v - cy, the pose, the scene): not on the image size or its tiles.
+ *
+ * nbk_render_ray_spans_host (no GPU needed): the span routine on HOST arrays.  For pixel i = v * W + u and ball s (centres [S][3],
+ * radii [S]: R as given), in float64, every operation rounded once, in this order:
+ *     ax = ((double)u - cx) / fx;  ay = ((double)v - cy) / fy;  A = (ax * ax + ay * ay) + 1
+ *     d[e] = c[e] - T[e][3];  xc = (T[0][0] * d[0] + T[1][0] * d[1]) + T[2][0] * d[2];  yc, zc: columns 1 and 2 (as nbk_frame_cloud_carve)
+ *     B = (ax * xc + ay * yc) + zc;  C = ((xc * xc + yc * yc) + zc * zc) - R * R;  D = B * B - A * C
+ *     hit iff D >= 0 and z0 <= z1 for z0 = max((B - sqrt(D)) / A, z_near), z1 = min((B + sqrt(D)) / A, z_far)
+ * hit[i][s] = 1 and span[i][s] = (z0, z1), or 0 and (0, 0).  NBK_ERR_INVALID for H, W or S < 0, focal lengths not positive, a null T,
+ * z_near < 0, z_far <= z_near, or a null array that would be read or written.
+ *
+ * nbk_render_depth_lds_bytes (no GPU needed): the kernel's LDS for a scene of n_shapes selected robot shapes and no world shape
+ * (each world shape drawn adds 48 bytes), -1 for n_shapes < 0 or when it does not fit 160 KB: the entry answers NBK_ERR_UNSUPPORTED.
+ * NBK_ERR_INVALID -- before any device is looked for -- for a null m, T, depth (or q on a model with joints) with B * H * W > 0,
+ * H, W or B < 0, focal lengths or eps not positive (NaN included), z_near < 0, z_far <= z_near, max_steps outside 1..4096, Bq or Bt
+ * not in {1, B}, B * H * W >= 2^31.  H * W = 0 or B = 0 does nothing.
+ */
+int64_t nbk_render_depth_lds_bytes(int32_t n_shapes);                   /* no GPU */
+int32_t nbk_render_ray_spans_host(int32_t H, int32_t W, double fx, double fy, double cx, double cy, const double *T,
+                                  const double *centres /* [S][3] */, const double *radii /* [S] */, int32_t S, double z_near,
+                                  double z_far, double *span /* [H*W][S][2] */, uint8_t *hit /* [H*W][S] */);   /* no GPU */
+int32_t nbk_render_depth_batch(const nbk_model *m, const double *q /* DEVICE [Bq][n_q], Bq = B or 1 */, int64_t Bq,
+                               const double *T /* DEVICE [Bt][12] optical poses, Bt = B or 1 */, int64_t Bt, int64_t B, int32_t H,
+                               int32_t W, double fx, double fy, double cx, double cy, double z_near, double z_far, double eps,
+                               int32_t max_steps, const uint64_t *shape_bits /* host, NULL = all */, int32_t draw_world, float miss,
+                               float *depth /* DEVICE [B][H][W] */, int32_t *label /* DEVICE [B][H][W] or NULL */,
+                               int64_t *counts /* DEVICE [3] or NULL */, void *stream);
+
+/*
  * Proximity records against a cloud: nbk_cloud_clearance_batch's record with WHERE the contact is and WHICH WAY to move -- what
  * nbk_proximity_jacobian_batch / nbk_pair_records_items give for the scene's pairs.  (Named like its siblings over edges and splines,
  * nbk_<what>_cloud_*: the nbk_cloud_* names are the cloud object's own set.)

@@ -40,6 +40,7 @@ SYMBOLS = [
     "nbk_frame_cloud_set_points", "nbk_frame_cloud_count",
     "nbk_frame_cloud_carve", "nbk_frame_cloud_carve_host", "nbk_frame_cloud_novel", "nbk_frame_cloud_append_workspace_bytes",
     "nbk_frame_cloud_append",
+    "nbk_render_depth_lds_bytes", "nbk_render_ray_spans_host", "nbk_render_depth_batch",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -163,6 +164,11 @@ def load():
     lib.nbk_frame_cloud_append_workspace_bytes.argtypes = [i64, i64]
     lib.nbk_frame_cloud_append_workspace_bytes.restype = i64
     lib.nbk_frame_cloud_append.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp]
+    lib.nbk_render_depth_lds_bytes.argtypes = [i32]
+    lib.nbk_render_depth_lds_bytes.restype = i64
+    lib.nbk_render_ray_spans_host.argtypes = [i32, i32, f64, f64, f64, f64, vp, vp, vp, i32, f64, f64, vp, vp]
+    lib.nbk_render_depth_batch.argtypes = [vp, vp, i64, vp, i64, i64, i32, i32, f64, f64, f64, f64, f64, f64, f64, i32, vp, i32, C.c_float,
+                                           vp, vp, vp, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

@@ -516,6 +516,272 @@ __global__ __launch_bounds__(256) void k_cloud_self_filter(DevModel m, CloudSel 
     }
 }
 
+// ---- rendered frames (nbk_render_depth_batch; DESIGN.md 3, "Rendered frames") ----------------------------------------------------------
+// Depth frames of the device scene -- the selected robot shapes at the frame's q and, when asked for, the world shapes -- ray-cast
+// by sphere tracing on cores_distance: the surface is the set the collision predicates call "distance 0".  One pixel per lane, a wave
+// is an 8x8 tile, a workgroup a 16x16 block of one frame; the grid is blocks x B frames, flat.
+//   preamble   as k_cloud_self_filter: one selected robot shape per lane (stride 256), its frame at the frame's q row, build_core,
+//              the record and the widened radius of its bounding ball into LDS (RenderLds).  World cores are read from m.ws_core.
+//   drawn order  the selected robot shapes in device order, then the world shapes: index i < n_sel is record i, else world i - n_sel.
+//              Candidates are met in this order everywhere, so "ties go to the smaller index" means this order.
+//   tile cull  the lanes test the drawn shapes (stride 64; planes never enter) against a cone around the tile's rays and compact the
+//              survivors, ascending, into the wave's LDS list with one ballot per trip; then, per survivor, every lane takes its OWN
+//              span (depth_ray_sphere_span with the widened ball) and the ballot of the lanes that have one is kept beside it.  The
+//              cone only shortens the second loop: a lane's candidates are the shapes whose span ITS ray has, whatever the tile.
+//   planes     closed form, per lane: h = n.(p(z_near) - c); h < eps: hit at z_near; else with den = n.w (w: the ray per unit depth in
+//              the world) < 0 the hit is z_near + h / -den when that is <= z_far.  The nearest plane competes with the march.
+//   march      z starts at the lane's smallest z0 and ends past its largest z1 (or the plane hit, or z_far).  A step takes d, the
+//              minimum over the lane's candidates in order of cores_distance<false, true>(shape, point core at p(z)); a candidate
+//              whose bounding-ball lower bound |c - p| - R is not below the running minimum is skipped.  d < eps: hit at this z,
+//              labelled with the shape of the minimum (the first that reaches it); else z += d / L.  max_steps steps without a
+//              decision: unresolved.  A march hit at the plane's depth or nearer wins.  The lanes run ahead to their next candidate
+//              and decide side by side under one ballot; the hull support's scalar path only when the ballot shows one candidate.
+// A frame whose q row or pose is not finite, or a set world status (wstatus: the movable descriptor's, else null), is unresolved in
+// every pixel.  counts: hit pixels, unresolved pixels, distance evaluations; integer sums, one atomic add per wave and counter.
+struct RenderArgs {
+    int H, W, bx, by;                 // the image and its 16x16 blocks per row / column
+    DepthCam cam;                     // depth_scale 1; z_min, z_max: z_near, z_far
+    double eps;
+    int max_steps, draw_world, q_one, t_one;
+    float miss;
+};
+
+NBK_DEV void render_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+NBK_DEV unsigned long long render_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+
+// the widened bounding ball of a core (cloud_search_radius' widening: the iterative distances must not lose a shape to their last digits)
+NBK_DEV double render_ball_radius(double rho, double margin) {
+    const double R = rho + margin;
+    return R + (1e-6 * __builtin_fabs(R) + 1e-7);
+}
+
+// the device index of the k-th selected robot shape (record k)
+NBK_DEV int render_record_shape(const CloudSel& s, int k) {
+    if (s.all != 0) return k;
+    for (int w = 0; w < 4; ++w) {
+        const int c = __builtin_popcountll(s.w[w]);
+        if (k < c) {
+            unsigned long long x = s.w[w];
+            for (int j = 0; j < k; ++j) x &= x - 1ull;
+            return 64 * w + __builtin_ctzll(x);
+        }
+        k -= c;
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void k_render_depth(DevModel m, CloudSel sel, int n_sel, const int* __restrict__ rs_user,
+                                                      const int* __restrict__ wstatus, const double* __restrict__ q,
+                                                      const double* __restrict__ Tp, RenderArgs a, float* __restrict__ depth,
+                                                      int* __restrict__ label, unsigned long long* __restrict__ counts) {
+    extern __shared__ double lds[];
+    static_assert(sizeof(Core) == sizeof(double) * RenderLds::CORE_LEN, "RenderLds holds a Core per record");
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n_world = a.draw_world != 0 ? m.n_wshapes : 0;
+    const int n_list = n_sel + n_world;
+    const RenderLds L(n_sel, n_list);
+    double* const rec = L.rec(lds);
+    unsigned long long* const own = L.own(lds) + (size_t)wv * n_list;
+    int* const lst = L.idx(lds) + (size_t)wv * n_list;
+    const int per = a.bx * a.by;
+    const int64_t b = (int64_t)(blockIdx.x / (unsigned)per);
+    const int blk = (int)(blockIdx.x % (unsigned)per);
+    const int tu0 = (blk % a.bx) * 16 + (wv & 1) * 8, tv0 = (blk / a.bx) * 16 + (wv >> 1) * 8;
+    const int u = tu0 + (lane & 7), v = tv0 + (lane >> 3);
+    const bool live = u < a.W && v < a.H;
+    const int64_t pix = (b * a.H + v) * a.W + u;
+    const double* qrow = q + (a.q_one != 0 ? 0 : b * m.n_q);
+    const double* Tg = Tp + (a.t_one != 0 ? 0 : b * 12);
+    double T[12];
+    bool fin = true;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) { T[e] = Tg[e]; fin = fin && (T[e] - T[e] == 0.0); }
+    for (int c = 0; c < m.n_q; ++c) fin = fin && (qrow[c] - qrow[c] == 0.0);
+    if (wstatus != nullptr && *wstatus != 0) fin = false;
+    if (!fin) {                                              // (every thread of the workgroup reads the same values: all leave)
+        if (live) { depth[pix] = a.miss; if (label != nullptr) label[pix] = -2; }
+        const unsigned long long nl = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(live));
+        if (counts != nullptr && lane == 0 && nl != 0ull) atomicAdd(counts + 1, nl);
+        return;
+    }
+    // the records, in device order (k_cloud_self_filter's preamble)
+    for (int s = tid; s < m.n_rshapes; s += 256) {
+        if (!cloud_selected(sel, s)) continue;
+        int k = s;
+        if (sel.all == 0) {
+            k = __builtin_popcountll(sel.w[(s >> 6) & 3] & ((1ull << (s & 63)) - 1ull));
+            for (int w = 0; w < ((s >> 6) & 3); ++w) k += __builtin_popcountll(sel.w[w]);
+        }
+        Xf Ts;
+        cloud_shape_frame(m, s, qrow, Ts);
+        Core A;
+        cloud_core_init(A);
+        build_core(m, s, Ts, A);
+        double* r = rec + (size_t)k * RenderLds::REC_LEN;
+        *reinterpret_cast<Core*>(r) = A;
+        r[RenderLds::RB_AT] = render_ball_radius(A.rho, A.margin);
+    }
+    __syncthreads();
+    // the cone around the tile's rays, in the camera frame: axis n through the tile's middle, half angle to its farthest corner ray
+    // (the rays of a rectangle of pixels lie inside the cone that holds its corners).  Widened: it must never lose a lane's candidate
+    double n[3], cosT = 1.0;
+    {
+        const double mx = (((double)tu0 + 3.5) - a.cam.cx) / a.cam.fx, my = (((double)tv0 + 3.5) - a.cam.cy) / a.cam.fy;
+        const double inv = 1.0 / nbk_sqrt((mx * mx + my * my) + 1.0);
+        n[0] = mx * inv; n[1] = my * inv; n[2] = inv;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double ex = ((double)(tu0 + ((k & 1) ? 7 : 0)) - a.cam.cx) / a.cam.fx, ey = ((double)(tv0 + ((k & 2) ? 7 : 0)) - a.cam.cy) / a.cam.fy;
+            const double c = ((n[0] * ex + n[1] * ey) + n[2]) / nbk_sqrt((ex * ex + ey * ey) + 1.0);
+            cosT = c < cosT ? c : cosT;
+        }
+        cosT -= 1e-9;
+    }
+    const double sinT = nbk_sqrt(1.0 - cosT * cosT > 0.0 ? 1.0 - cosT * cosT : 0.0);
+    int n_c = 0;                                             // the tile's candidates (wave-uniform)
+    for (int i0 = 0; i0 < n_list; i0 += 64) {
+        const int i = i0 + lane;
+        bool keep = false;
+        if (i < n_list) {
+            const bool robot = i < n_sel;
+            const int w = robot ? 0 : i - n_sel;
+            const double* cc = robot ? reinterpret_cast<const Core*>(rec + (size_t)i * RenderLds::REC_LEN)->c : m.ws_core + 18 * (size_t)w;
+            if (robot || m.ws_kind[w] != K_PLANE) {
+                const double R = robot ? rec[(size_t)i * RenderLds::REC_LEN + RenderLds::RB_AT] : render_ball_radius(cc[17], cc[16]);
+                const double d0 = cc[0] - T[3], d1 = cc[1] - T[7], d2 = cc[2] - T[11];
+                const double xc = (T[0] * d0 + T[4] * d1) + T[8] * d2, yc = (T[1] * d0 + T[5] * d1) + T[9] * d2, zc = (T[2] * d0 + T[6] * d1) + T[10] * d2;
+                const double t = (xc * n[0] + yc * n[1]) + zc * n[2], len2 = (xc * xc + yc * yc) + zc * zc;
+                const double perp2 = len2 - t * t;
+                const double perp = nbk_sqrt(perp2 > 0.0 ? perp2 : 0.0);
+                keep = perp * cosT - t * sinT <= R + 1e-9 * (1.0 + nbk_sqrt(len2));
+            }
+        }
+        const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
+        if (keep) lst[n_c + __popcll(km & ((1ull << lane) - 1ull))] = i;
+        n_c += __popcll(km);
+    }
+    render_wave_sync();
+    // every lane's own spans over the tile's candidates; a candidate no lane of the tile has is dropped (the ballot is the wave's)
+    double zs = NBK_INF, ze = -NBK_INF;
+    int n_o = 0;
+    for (int e = 0; e < n_c; ++e) {
+        const int i = lst[e];
+        const bool robot = i < n_sel;
+        const double* cc = robot ? reinterpret_cast<const Core*>(rec + (size_t)i * RenderLds::REC_LEN)->c : m.ws_core + 18 * (size_t)(robot ? 0 : i - n_sel);
+        const double R = robot ? rec[(size_t)i * RenderLds::REC_LEN + RenderLds::RB_AT] : render_ball_radius(cc[17], cc[16]);
+        const double c3[3] = {cc[0], cc[1], cc[2]};
+        double z0 = 0.0, z1 = 0.0;
+        const bool has = live && depth_ray_sphere_span(a.cam, T, u, v, c3, R, a.cam.z_min, a.cam.z_max, &z0, &z1);
+        if (has) { zs = z0 < zs ? z0 : zs; ze = z1 > ze ? z1 : ze; }
+        const unsigned long long hm = __builtin_amdgcn_ballot_w64(has);
+        if (hm != 0ull) {                                    // (n_o <= e, and every lane holds lst[e] already: the ballot needed it)
+            if (lane == 0) { lst[n_o] = i; own[n_o] = hm; }
+            ++n_o;
+        }
+    }
+    render_wave_sync();
+    const double Lr = depth_ray_length(a.cam, u, v);
+    // planes
+    double zp = NBK_INF;
+    int lp = -1;
+    if (live) {
+        double p0[3], wdir[3];
+        depth_ray_point(a.cam, T, u, v, a.cam.z_min, p0);
+        const double ax = ((double)u - a.cam.cx) / a.cam.fx, ay = ((double)v - a.cam.cy) / a.cam.fy;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) wdir[e] = (T[4 * e] * ax + T[4 * e + 1] * ay) + T[4 * e + 2];
+        for (int w = 0; w < n_world; ++w) {
+            if (m.ws_kind[w] != K_PLANE) continue;
+            const double* wc = m.ws_core + 18 * (size_t)w;
+            const double nn[3] = {wc[9], wc[10], wc[11]};
+            const double dd[3] = {p0[0] - wc[0], p0[1] - wc[1], p0[2] - wc[2]};
+            const double h = dot3(dd, nn), den = dot3(wdir, nn);
+            double z = NBK_INF;
+            if (h < a.eps) z = a.cam.z_min;
+            else if (den < 0.0) z = a.cam.z_min + h / -den;
+            if (z <= a.cam.z_max && z < zp) { zp = z; lp = n_sel + w; }
+        }
+    }
+    // the march
+    Core P;
+    cloud_point_core(0.0, P);
+    double z = zs;
+    const double zend = ze < zp ? ze : zp;
+    int state = (live && zs <= zend) ? 0 : 2;                // 0 marching, 1 hit, 2 miss
+    int lab = -1;
+    unsigned long long evals = 0ull;
+    for (int step = 0; step < a.max_steps; ++step) {
+        if (__builtin_amdgcn_ballot_w64(state == 0) == 0ull) break;
+        if (state == 0) depth_ray_point(a.cam, T, u, v, z, P.c);
+        double d = NBK_INF;
+        int arg = -1, e = 0;
+        while (true) {
+            bool cand = false;
+            int ec = 0;
+            while (state == 0 && !cand && e < n_o) {
+                ec = e++;
+                if (((own[ec] >> lane) & 1ull) == 0ull) continue;
+                const int i = lst[ec];
+                const bool robot = i < n_sel;
+                const double* cc = robot ? reinterpret_cast<const Core*>(rec + (size_t)i * RenderLds::REC_LEN)->c : m.ws_core + 18 * (size_t)(robot ? 0 : i - n_sel);
+                const double R = robot ? rec[(size_t)i * RenderLds::REC_LEN + RenderLds::RB_AT] : render_ball_radius(cc[17], cc[16]);
+                const double dc[3] = {cc[0] - P.c[0], cc[1] - P.c[1], cc[2] - P.c[2]};
+                cand = nbk_sqrt(dot3(dc, dc)) - R < d;
+            }
+            const unsigned long long cm = __builtin_amdgcn_ballot_w64(cand);
+            if (cm == 0ull) break;
+            const int e0 = __shfl(ec, __builtin_ctzll(cm));
+            const bool uniform = __builtin_amdgcn_ballot_w64(cand && ec != e0) == 0ull;
+            if (cand) {
+                const int i = lst[ec];
+                Core A;
+                if (i < n_sel) A = *reinterpret_cast<const Core*>(rec + (size_t)i * RenderLds::REC_LEN);
+                else { cloud_core_init(A); load_wcore(m, i - n_sel, A); }
+                if (uniform && A.kind == K_HULL) A.rad = -1.0;
+                double fam = -1.0;
+                const double de = cores_distance<false, true>(A, P, nullptr, &fam);
+                ++evals;
+                if (de < d) { d = de; arg = i; }
+            }
+        }
+        if (state == 0) {
+            if (d < a.eps) { state = 1; lab = arg; }
+            else {
+                z += d / Lr;
+                if (!(z <= zend)) state = 2;
+            }
+        }
+    }
+    const bool unres = live && state == 0;
+    bool hit = state == 1;
+    if (live && !unres && !hit && lp >= 0) { hit = true; z = zp; lab = lp; }
+    if (live) {
+        depth[pix] = hit ? (float)z : a.miss;
+        if (label != nullptr) label[pix] = unres ? -2 : (!hit ? -1 : (lab < n_sel ? rs_user[render_record_shape(sel, lab)] : m.n_rshapes + (lab - n_sel)));
+    }
+    if (counts != nullptr) {
+        const unsigned long long nh = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(live && hit));
+        const unsigned long long nu = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(unres));
+        const unsigned long long ne = render_wave_sum(evals);
+        if (lane == 0) {
+            if (nh != 0ull) atomicAdd(counts, nh);
+            if (nu != 0ull) atomicAdd(counts + 1, nu);
+            if (ne != 0ull) atomicAdd(counts + 2, ne);
+        }
+    }
+}
+
 // ---- sampled edges against the cloud (nbk_edge_cloud_validity_batch) -----------------------------------------------------------
 // valid[e] before the walk: an edge without samples (the degenerate edge) is invalid; accumulating, an entry only ever goes down.
 // An edge of 2^32 samples or more (its sample index no longer fits the packed (edge, sample) word of edge_t) is invalid as well.
@@ -1288,6 +1554,67 @@ int32_t nbk_frame_cloud_self_filter(const nbk_model* m, const double* q0, const 
     const int64_t want = (N + 255) / 256, most = (int64_t)(cus > 0 ? cus : 1) * SELF_FILTER_WGS_PER_CU;
     hipLaunchKernelGGL(k_cloud_self_filter, dim3((unsigned)(want < most ? want : most)), dim3(256), L.bytes(), (hipStream_t)stream, m->d, sel,
                        n_sel, q0, pts, (int)N, radius, padding, keep);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_render_depth_lds_bytes(int32_t n_shapes) {
+    if (n_shapes < 0 || !RenderLds(n_shapes, n_shapes).fits()) return -1;
+    return (int64_t)RenderLds(n_shapes, n_shapes).bytes();
+}
+
+// the camera and range rules the two rendering entries share
+static bool render_cam_ok(int32_t H, int32_t W, double fx, double fy, const double* T, double z_near, double z_far) {
+    return H >= 0 && W >= 0 && fx > 0.0 && fy > 0.0 && T != nullptr && z_near >= 0.0 && z_far > z_near;
+}
+
+int32_t nbk_render_ray_spans_host(int32_t H, int32_t W, double fx, double fy, double cx, double cy, const double* T, const double* centres,
+                                  const double* radii, int32_t S, double z_near, double z_far, double* span, uint8_t* hit) {
+    if (!render_cam_ok(H, W, fx, fy, T, z_near, z_far) || S < 0) return NBK_ERR_INVALID;
+    const int64_t n = (int64_t)H * (int64_t)W;
+    if (n * S > 0 && (centres == nullptr || radii == nullptr || span == nullptr || hit == nullptr)) return NBK_ERR_INVALID;
+    const DepthCam cam{1.0, fx, fy, cx, cy, z_near, z_far};
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t s = 0; s < S; ++s) {
+            double z0 = 0.0, z1 = 0.0;
+            const bool h = depth_ray_sphere_span(cam, T, (int)(i % W), (int)(i / W), centres + 3 * (size_t)s, radii[s], z_near, z_far, &z0, &z1);
+            span[2 * (i * S + s)] = h ? z0 : 0.0;
+            span[2 * (i * S + s) + 1] = h ? z1 : 0.0;
+            hit[i * S + s] = h ? 1 : 0;
+        }
+    return NBK_OK;
+}
+
+int32_t nbk_render_depth_batch(const nbk_model* m, const double* q, int64_t Bq, const double* T, int64_t Bt, int64_t B, int32_t H, int32_t W,
+                               double fx, double fy, double cx, double cy, double z_near, double z_far, double eps, int32_t max_steps,
+                               const uint64_t* shape_bits, int32_t draw_world, float miss, float* depth, int32_t* label, int64_t* counts,
+                               void* stream) {
+    if (m == nullptr || B < 0 || !render_cam_ok(H, W, fx, fy, T, z_near, z_far) || !(eps > 0.0) || max_steps < 1 || max_steps > 4096 ||
+        !(cx - cx == 0.0) || !(cy - cy == 0.0))
+        return NBK_ERR_INVALID;
+    if ((Bq != 1 && Bq != B) || (Bt != 1 && Bt != B)) return NBK_ERR_INVALID;
+    const int64_t hw = (int64_t)H * (int64_t)W;
+    if (hw > 0 && B > (((int64_t)1 << 31) - 1) / hw) return NBK_ERR_INVALID;      // B * H * W >= 2^31
+    if (hw * B > 0 && (depth == nullptr || (q == nullptr && m->d.n_q > 0))) return NBK_ERR_INVALID;
+    CloudSel sel;
+    { const int32_t rc = cloud_model_begin(m, shape_bits, sel); if (rc != NBK_OK) return rc; }
+    const int n_sel = cloud_selected_count(m, sel);
+    const int n_list = n_sel + (draw_world != 0 ? m->d.n_wshapes : 0);
+    const RenderLds L(n_sel, n_list);
+    if (!L.fits()) return NBK_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (counts != nullptr) NBK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st));
+    if (hw * B == 0) return NBK_OK;
+    RenderArgs a;
+    a.H = H; a.W = W; a.bx = (W + 15) / 16; a.by = (H + 15) / 16;
+    a.cam = DepthCam{1.0, fx, fy, cx, cy, z_near, z_far};
+    a.eps = eps; a.max_steps = max_steps; a.draw_world = draw_world != 0 ? 1 : 0;
+    a.q_one = (Bq == 1 && B != 1) ? 1 : 0; a.t_one = (Bt == 1 && B != 1) ? 1 : 0;
+    a.miss = miss;
+    const int64_t blocks = (int64_t)a.bx * a.by * B;         // (< 2^31: a block holds a pixel at least)
+    hipLaunchKernelGGL(k_render_depth, dim3((unsigned)blocks), dim3(256), L.bytes(), st, m->d, sel, n_sel, m->rs_user,
+                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, T, a, depth, label,
+                       reinterpret_cast<unsigned long long*>(counts));
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

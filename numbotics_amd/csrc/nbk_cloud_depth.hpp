@@ -20,6 +20,18 @@
 //     u = floor(((xc * fx) / zc + cx) + 0.5)      v = floor(((yc * fy) / zc + cy) + 0.5)                   (kept as doubles)
 // p is seen through iff zc > z_min, the window u - w .. u + w, v - w .. v + w lies in the image (compared as doubles: NaN and huge
 // values fall out) and every pixel of it is valid by the test above with (z - zc) > margin.  A hole in the window is no evidence.
+//
+// The ray side, for rendered frames (k_render_depth, nbk_render_ray_spans_host; DESIGN.md 3, "Rendered frames").  The point at depth z
+// on pixel (u, v) is depth_backproject_pixel with depth_scale = 1 and no range (depth_ray_point): what a renderer tests at z is the
+// point the back-projection later makes from that depth.  Per unit of depth the ray is L long (T's rotation taken as orthonormal, as
+// above); the depths at which the pixel's ray is inside the ball (c, R), clipped to [z_near, z_far] (depth_ray_sphere_span):
+//     ax = ((double)u - cx) / fx      ay = ((double)v - cy) / fy
+//     A = (ax * ax + ay * ay) + 1     L = sqrt(A)
+//     d[e] = c[e] - T[e][3];  xc, yc, zc = R^T d as for carving
+//     B = (ax * xc + ay * yc) + zc    C = ((xc * xc + yc * yc) + zc * zc) - R * R
+//     D = B * B - A * C               empty unless D >= 0 (a NaN is empty)
+//     s = sqrt(D)     z0 = (B - s) / A     z1 = (B + s) / A
+//     z0 = z0 > z_near ? z0 : z_near       z1 = z1 < z_far ? z1 : z_far       the span is [z0, z1], empty unless z0 <= z1
 #ifndef NBK_CLOUD_DEPTH_HPP
 #define NBK_CLOUD_DEPTH_HPP
 #include <math.h>
@@ -55,6 +67,41 @@ NBK_GRID_FN bool depth_backproject_pixel(const DepthCam& k, const double* T, int
     const double xc = (((double)u - k.cx) * z) / k.fx;
     const double yc = (((double)v - k.cy) * z) / k.fy;
     for (int e = 0; e < 3; ++e) w[e] = ((T[4 * e] * xc + T[4 * e + 1] * yc) + T[4 * e + 2] * z) + T[4 * e + 3];
+    return true;
+}
+
+// the march point of pixel (u, v) at depth z: depth_backproject_pixel's point for depth_scale 1, whatever the range (k: fx, fy, cx, cy)
+NBK_GRID_FN void depth_ray_point(const DepthCam& k, const double* T, int u, int v, double z, double* w) {
+    const double xc = (((double)u - k.cx) * z) / k.fx;
+    const double yc = (((double)v - k.cy) * z) / k.fy;
+    for (int e = 0; e < 3; ++e) w[e] = ((T[4 * e] * xc + T[4 * e + 1] * yc) + T[4 * e + 2] * z) + T[4 * e + 3];
+}
+
+// the length of pixel (u, v)'s ray per unit of depth
+NBK_GRID_FN double depth_ray_length(const DepthCam& k, int u, int v) {
+    const double ax = ((double)u - k.cx) / k.fx, ay = ((double)v - k.cy) / k.fy;
+    return sqrt((ax * ax + ay * ay) + 1.0);
+}
+
+// the depths [z0, z1] within [z_near, z_far] at which pixel (u, v)'s ray is inside the ball (c, R); false (z0, z1 untouched): none
+NBK_GRID_FN bool depth_ray_sphere_span(const DepthCam& k, const double* T, int u, int v, const double* c, double R, double z_near,
+                                       double z_far, double* z0, double* z1) {
+    const double ax = ((double)u - k.cx) / k.fx, ay = ((double)v - k.cy) / k.fy;
+    const double A = (ax * ax + ay * ay) + 1.0;
+    const double d0 = c[0] - T[3], d1 = c[1] - T[7], d2 = c[2] - T[11];
+    const double xc = (T[0] * d0 + T[4] * d1) + T[8] * d2;
+    const double yc = (T[1] * d0 + T[5] * d1) + T[9] * d2;
+    const double zc = (T[2] * d0 + T[6] * d1) + T[10] * d2;
+    const double B = (ax * xc + ay * yc) + zc;
+    const double C = ((xc * xc + yc * yc) + zc * zc) - R * R;
+    const double D = B * B - A * C;
+    if (!(D >= 0.0)) return false;
+    const double s = sqrt(D);
+    double a = (B - s) / A, b = (B + s) / A;
+    a = a > z_near ? a : z_near;
+    b = b < z_far ? b : z_far;
+    if (!(a <= b)) return false;
+    *z0 = a; *z1 = b;
     return true;
 }
 

@@ -118,6 +118,20 @@ struct SelfFilterLds {
     NBK_HD double* rec(double* base) const { return base; }
     NBK_LDS_TOTAL(sizeof(double) * (size_t)rec_len)
 };
+// k_render_depth: one record per selected robot shape, [n_sel][REC_LEN]: the shape's core at the frame's q (CORE_LEN doubles, as above) |
+// the widened radius of its bounding ball; then, for each of the four waves (8x8 pixel tiles) of the workgroup, the tile's candidate
+// list over the n_list shapes drawn (the selected robot shapes, then the world's): own [4][n_list] u64, the lanes whose ray meets
+// the candidate's ball | idx [4][n_list] int, the candidate's place in the drawn order.  World cores stay in global memory.
+struct RenderLds {
+    static constexpr int CORE_LEN = SelfFilterLds::CORE_LEN, REC_LEN = CORE_LEN + 1, RB_AT = CORE_LEN, WAVES = 4;
+    static constexpr int LIST_BYTES = WAVES * 12;      // what one more drawn shape costs beyond its record
+    int rec_len, own_len, idx_len;                     // own: u64, idx: int
+    NBK_HD RenderLds(int n_sel, int n_list) : rec_len(REC_LEN * (n_sel > 0 ? n_sel : 1)), own_len(WAVES * n_list), idx_len(WAVES * n_list) {}
+    NBK_HD double* rec(double* base) const { return base; }
+    NBK_HD unsigned long long* own(double* base) const { return reinterpret_cast<unsigned long long*>(rec(base) + rec_len); }
+    NBK_HD int* idx(double* base) const { return reinterpret_cast<int*>(own(base) + own_len); }
+    NBK_LDS_TOTAL(sizeof(double) * (size_t)rec_len + sizeof(unsigned long long) * (size_t)own_len + sizeof(int) * (size_t)idx_len)
+};
 // k_narrow*: q rows [NARROW_T][n_q] | the scene's hull vertices [hull_blob_n] when they fit HULL_LDS_MAX
 struct NarrowLds {
     int q_len, hull_blob_n;

@@ -584,6 +584,64 @@ class DeviceModel:
             return keep
         return k.cpu().numpy().astype(bool) if ps.numpy else k
 
+    def render_depth(self, q, camera_pose, intrinsics, height, width, near=0.01, far=1000.0, eps=1e-6, max_steps=256, shapes=None,
+                     world=True, miss=0.0, out=None, labels=False, counts=None, frame="optical"):
+        """Depth frames of the device scene, ray-cast on the current stream (nbk_render_depth_batch): the selected robot shapes at
+        ``q`` and, with ``world``, the world shapes, sphere-traced on the exact shape distance -- a surface is where the collision
+        predicates read distance 0.  ``q``: (n_q,) or (B, n_q), ``camera_pose``: one pose or (B, 4, 4) / (B, 3, 4), NumPy or
+        float64 CUDA tensors (read when the kernel runs; ``frame`` as ``backproject``); one row serves every frame of the other's
+        batch.  ``intrinsics``: (fx, fy, cx, cy) or a 3 x 3 matrix.  -> depth, a float32 CUDA tensor (B, height, width): the metric
+        depth along the view axis (what ``backproject`` takes), ``miss`` where the ray meets nothing within [near, far] or stays
+        undecided after ``max_steps`` steps.  ``labels=True``: (depth, label), label int32: the robot shape (``SceneModel`` order),
+        ``n_rshapes + w`` for world shape w, -1 miss, -2 undecided.  ``counts``: an int64 CUDA tensor (3,) that receives (hit
+        pixels, undecided pixels, distance evaluations).  ``out``: the depth tensor (or the (depth, label) pair) to write into.
+        A hit stops within ``eps`` in front of the surface.  No allocation and capturable when everything is a CUDA tensor."""
+        from numbotics_amd.physics.pointcloud import _intrinsics, _device_poses
+        bits = self._shape_bits(shapes)                 # (argument errors come before the device is touched)
+        fx, fy, cx, cy = _intrinsics(intrinsics)
+        H, W = int(height), int(width)
+        if H < 0 or W < 0:
+            raise ValueError(f"height and width must not be negative, got {H} x {W}")
+        if not (fx > 0.0 and fy > 0.0):
+            raise ValueError("focal lengths must be positive")
+        if not (float(near) >= 0.0 and float(far) > float(near)):
+            raise ValueError(f"need 0 <= near < far, got near={near}, far={far}")
+        if not float(eps) > 0.0:
+            raise ValueError(f"eps must be positive, got {eps}")
+        if not 1 <= int(max_steps) <= 4096:
+            raise ValueError(f"max_steps must be in 1..4096, got {max_steps}")
+        if frame not in ("optical", "numbotics"):
+            raise ValueError(f"frame must be 'optical' or 'numbotics', got {frame!r}")
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        T = _device_poses(torch, camera_pose, frame)
+        Bt = int(T.shape[0]) if T.ndim == 3 else 1
+        B = max(qs.B, Bt)
+        if qs.B not in (1, B) or Bt not in (1, B):
+            raise ValueError(f"q has {qs.B} rows and camera_pose {Bt}: each must be one or the batch")
+        if B * H * W >= 1 << 31:
+            raise ValueError("B * height * width must stay below 2^31")
+        depth, label = (out if labels else (out, None)) if out is not None else (None, None)
+        if depth is None:
+            depth = torch.empty((B, H, W), dtype=torch.float32, device=qs.device)
+        elif not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype == torch.float32 and depth.is_contiguous() and depth.numel() == B * H * W):
+            raise ValueError(f"out: depth must be a contiguous float32 CUDA tensor of {B} x {H} x {W} values")
+        if labels:
+            if label is None:
+                label = torch.empty((B, H, W), dtype=torch.int32, device=qs.device)
+            elif not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int32 and label.is_contiguous() and label.numel() == B * H * W):
+                raise ValueError(f"out: label must be a contiguous int32 CUDA tensor of {B} x {H} x {W} values")
+        if counts is not None and not (torch.is_tensor(counts) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous()
+                                       and counts.numel() == 3):
+            raise ValueError("counts must be a contiguous int64 CUDA tensor of 3 values")
+        n = B * H * W
+        _lib.check(self._lib.nbk_render_depth_batch(
+            self._h, qs.t.data_ptr(), qs.B, T.data_ptr(), Bt, B, H, W, fx, fy, cx, cy, float(near), float(far), float(eps), int(max_steps),
+            _host_ptr(bits), 1 if world else 0, float(miss), depth.data_ptr() if n > 0 else None,
+            label.data_ptr() if (label is not None and n > 0) else None, None if counts is None else counts.data_ptr(), self._stream()),
+            "nbk_render_depth_batch")
+        return (depth, label) if labels else depth
+
     def cloud_clearance(self, cloud, q, d_max, shapes=None):
         """Per configuration the smallest signed distance to ``cloud`` over the selected robot shapes when it is below ``d_max``
         -> (distance (B,), robot shape (B,) int32, point index (B,) int32); +inf, -1, -1 where nothing is closer than ``d_max``;

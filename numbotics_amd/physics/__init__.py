@@ -3,6 +3,7 @@ __all__ = [
     "CollisionShape", "PhysicsObject", "Cube", "Cuboid", "Sphere", "Mesh", "Plane", "Capsule", "Cylinder",
     "World", "get_world", "Link", "Chain", "GraphChain", "Constraint", "Joint", "Proximity",
     "PointCloud", "backproject", "carve", "intrinsics_from_fov",
+    "optical_pose", "ray_spans_host",
 ]
 
 from .constraint import Constraint, Joint
@@ -10,4 +11,4 @@ from .collision import Proximity, CollisionShape
 from .world import World, get_world
 from .object import PhysicsObject, Cube, Cuboid, Sphere, Mesh, Plane, Capsule, Cylinder
 from .chain import Link, Chain, GraphChain
-from .pointcloud import PointCloud, backproject, carve, intrinsics_from_fov
+from .pointcloud import PointCloud, backproject, carve, intrinsics_from_fov, optical_pose, ray_spans_host

@@ -158,6 +158,27 @@ def _device_pose(torch, camera_pose, frame, stage=None):
     return T
 
 
+def _device_poses(torch, camera_pose, frame):
+    """One pose by ``_device_pose``, or a batch (B, 4, 4) / (B, 3, 4) as a contiguous float64 (B, 3, 4) CUDA tensor of optical poses
+    (``DeviceModel.render_depth``): a device batch of optical (B, 3, 4) poses as it is, anything else by one copy."""
+    nd = camera_pose.ndim if torch.is_tensor(camera_pose) else np.asarray(camera_pose).ndim
+    if nd != 3:
+        return _device_pose(torch, camera_pose, frame)
+    if not torch.is_tensor(camera_pose):
+        a = np.asarray(camera_pose, dtype=np.float64)
+        host = np.stack([optical_pose(p, frame) for p in a]) if a.shape[0] > 0 else np.zeros((0, 3, 4))
+        return torch.from_numpy(np.ascontiguousarray(host)).to("cuda")
+    T = camera_pose
+    if not T.is_cuda or T.dtype != torch.float64 or tuple(T.shape[1:]) not in ((4, 4), (3, 4)):
+        raise ValueError("camera poses on the device must be a float64 (B, 4, 4) or (B, 3, 4) CUDA tensor")
+    T = T[:, :3, :]
+    if frame == "numbotics":
+        return torch.stack((-T[:, :, 1], -T[:, :, 2], T[:, :, 0], T[:, :, 3]), dim=2).contiguous()
+    if frame != "optical":
+        raise ValueError(f"frame must be 'optical' or 'numbotics', got {frame!r}")
+    return T.contiguous()
+
+
 class _Frame:
     """One depth frame as every nbk_frame_cloud_* image entry takes it, built once per call: ``depth`` by ``_depth_array`` (the one depth
     rule), ``H``, ``W``, ``pose`` (the optical pose) and ``args``, the twelve arguments those entries start with: depth, depth_type
@@ -197,6 +218,24 @@ def backproject_host(depth, intrinsics, camera_pose, depth_scale=1.0, z_min=0.0,
     keep = np.empty((f.H * f.W,), dtype=np.uint8)
     _lib.check(_lib.load().nbk_frame_cloud_backproject_host(*f.args, pts.ctypes.data, keep.ctypes.data), "nbk_frame_cloud_backproject_host")
     return pts, keep
+
+
+def ray_spans_host(height, width, intrinsics, camera_pose, centres, radii, near=0.01, far=1000.0, frame="optical"):
+    """Per pixel and ball the depths at which the pixel's ray is inside the ball, clipped to [near, far], by the routine the renderer
+    takes its candidates with (nbk_render_ray_spans_host; no GPU needed) -> (span (H * W, S, 2) float64, hit (H * W, S) bool); a
+    ray that misses a ball has span (0, 0)."""
+    fx, fy, cx, cy = _intrinsics(intrinsics)
+    T = optical_pose(camera_pose, frame)
+    c = np.ascontiguousarray(np.asarray(centres, dtype=np.float64)).reshape(-1, 3)
+    r = np.ascontiguousarray(np.asarray(radii, dtype=np.float64)).reshape(-1)
+    if r.shape[0] != c.shape[0]:
+        raise ValueError(f"{c.shape[0]} centres but {r.shape[0]} radii")
+    H, W, S = int(height), int(width), int(c.shape[0])
+    span = np.zeros((max(H, 0) * max(W, 0), S, 2), dtype=np.float64)
+    hit = np.zeros((max(H, 0) * max(W, 0), S), dtype=np.uint8)
+    _lib.check(_lib.load().nbk_render_ray_spans_host(H, W, fx, fy, cx, cy, T.ctypes.data, c.ctypes.data, r.ctypes.data, S, float(near),
+                                                     float(far), span.ctypes.data, hit.ctypes.data), "nbk_render_ray_spans_host")
+    return span, hit.astype(bool)
 
 
 def _backproject(torch, f, pts, keep):

@@ -97,6 +97,61 @@ class World:
         """No dynamics here; kept so reference scripts that call ``world.step()`` still run."""
         return None
 
+    def static_scene(self, bullet_margins: bool = True):
+        """Every registered body as it stands -- chains at their ``configuration`` -- as the world shapes of a zero-joint
+        ``SceneModel`` without robot shapes and pairs (the route of physics/proximity.py): what ``depth_image`` draws.  World shape
+        w belongs to ``wshape_obj[w]`` of ``objects()``.  Needs no GPU."""
+        from numbotics_amd.robots.model import HullTable, _shape_records
+        from .proximity import _static_shapes
+        hulls = HullTable()
+        ws, owner = [], []
+        for k, body in enumerate(self.objects()):
+            for _, cs, pose in _static_shapes(body):
+                for t, T, p in _shape_records(cs, pose, hulls, bullet_margins):
+                    ws.append((t, T, p))
+                    owner.append(k)
+        return static_scene_model(ws, hulls, owner)
+
+    def depth_image(self, width: int, height: int, camera_pose, near: float = 0.01, far: float = 1000, fov: float = 60,
+                    bullet_margins: bool = True):
+        """The depth frame a camera at ``camera_pose`` sees of every registered body (reference: numbotics/physics/world.py:363-398,
+        Bullet's ``getCameraImage`` linearised) -> ``(height, width, 1)`` float64, the metric depth along the view axis; ``far``
+        where nothing is seen, the value Bullet's cleared depth buffer linearises to.  The camera stands at ``camera_pose[:3, 3]``
+        and looks along the pose's x axis with z up (the reference's comment); ``fov`` is the vertical field of view
+        in degrees, the aspect ``width / height`` (``intrinsics_from_fov``).  Ray-cast on the device on the shapes and distances the
+        collision checks use (``DeviceModel.render_depth``), boxes, cylinders and hulls rounded by Bullet's margins unless
+        ``bullet_margins=False`` (additive).  Parity with Bullet's rasteriser is unpinned.  A GPU is required."""
+        import numpy as np
+        from numbotics_amd.engine import DeviceModel
+        from .pointcloud import intrinsics_from_fov
+        # (a descriptor per call: a few small uploads against a frame's rays, and no cache to keep right)
+        dev = DeviceModel(self.static_scene(bullet_margins))
+        depth, label = dev.render_depth(np.zeros((1, 1)), np.asarray(camera_pose, dtype=np.float64), intrinsics_from_fov(width, height, fov),
+                                        height, width, near=near, far=far, labels=True, frame="numbotics")
+        d = depth.cpu().numpy().astype(np.float64).reshape(int(height), int(width))
+        d[label.cpu().numpy().reshape(d.shape) < 0] = float(far)
+        return d.reshape(int(height), int(width), 1)
+
+
+def static_scene_model(records, hulls=None, owners=None):
+    """World shape records [(type, 4x4 world pose, params[4])] (robots/model.py: ``_shape_records``) as a zero-joint ``SceneModel``
+    without robot shapes and pairs: a scene that is drawn, never checked.  ``hulls``: the ``HullTable`` the records' hulls name."""
+    import numpy as np
+    from numbotics_amd.robots.model import KinematicModel, SceneModel, HullTable, _T34
+    W = len(records)
+    z = np.zeros
+    kin = KinematicModel(n_q=1, joint_parent=z(0, dtype=np.int32), joint_type=z(0, dtype=np.int32), joint_qidx=z(0, dtype=np.int32),
+                         joint_offset=z((0, 12)), joint_axis=z((0, 3)), joint_rot=z((0, 27)), joint_trans=z((0, 3)), joint_slide=z((0, 3)),
+                         base_pose=_T34(np.eye(4)))
+    hvb, hv, hfb, hp = (hulls if hulls is not None else HullTable()).arrays()
+    return SceneModel(kin=kin, rshape_frame=z(0, dtype=np.int32), rshape_type=z(0, dtype=np.int32), rshape_local=z((0, 12)),
+                      rshape_param=z((0, 4)), rshape_link=z(0, dtype=np.int32), wshape_type=np.array([r[0] for r in records], dtype=np.int32),
+                      wshape_pose=np.array([_T34(r[1]) for r in records], dtype=np.float64).reshape(W, 12),
+                      wshape_param=np.array([r[2] for r in records], dtype=np.float64).reshape(W, 4),
+                      wshape_obj=np.asarray(owners if owners is not None else z(W), dtype=np.int32),
+                      pair_a=z(0, dtype=np.int32), pair_b=z(0, dtype=np.int32),
+                      hull_vert_begin=hvb, hull_verts=hv, hull_face_begin=hfb, hull_planes=hp)
+
 
 def _reset_worlds():
     """Test helper: forget every world."""

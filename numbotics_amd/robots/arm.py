@@ -599,6 +599,48 @@ class Arm(Robot):
             raise ValueError(f"q must have {self.dof} elements")
         return dev.cloud_self_filter(points, q, radius, padding, keep=keep, shapes=shapes)
 
+    def depth_images(self, q, camera_pose, width: int, height: int, fov: float = 60.0, intrinsics=None, near: float = 0.01,
+                     far: float = 1000.0, frame: str = "numbotics", links=None, ignore_links=(), world: bool = True, labels: bool = False,
+                     out=None):
+        """Depth frames of the arm at ``q`` among its world's obstacles, ray-cast on the device (``DeviceModel.render_depth``): what
+        a depth camera at ``camera_pose`` sees of the shapes ``in_collision`` checks, in the shape mode of this arm
+        (``bullet_margins``).  ``q``: ``(dof,)`` or ``(B, dof)``; ``camera_pose``: one (4, 4) pose or ``(B, 4, 4)``; one of either
+        serves the other's batch.  ``frame="numbotics"`` (the default, ``World.depth_image``'s camera: looking along x, z up) or
+        ``"optical"``.  ``fov`` is the vertical field of view in degrees (``intrinsics_from_fov``) unless ``intrinsics`` -- (fx, fy,
+        cx, cy) or a 3 x 3 matrix -- is given.  ``links`` / ``ignore_links``: draw only / all but these links; ``world=False``: the
+        arm alone.  -> the metric depth along the view axis, float32 ``(height, width)`` for one ``q`` and one pose, else ``(B,
+        height, width)``; 0 where nothing is seen within [near, far] -- a hole to ``backproject``.  ``labels=True``: (depth, label)
+        with the shape behind each pixel (``SceneModel`` order; ``n_rshapes + w`` for world shape w, -1 nothing, -2 undecided).
+        NumPy ``q`` gives NumPy, a CUDA ``q`` CUDA tensors, which ``PointCloud.update_from_depth`` / ``integrate_depth`` take as
+        they are.  ``out``: as ``DeviceModel.render_depth``."""
+        from numbotics_amd.physics.pointcloud import intrinsics_from_fov
+        sm, dev = self._scene_device()
+        shapes = self._cloud_shapes(sm, ignore_links)
+        if links is not None:
+            names = {getattr(l, "_name", l) for l in links}
+            known = {l._name for l in sm.links}
+            for n in names:
+                if n not in known:
+                    raise ValueError(f"Link {n} not found in chain")
+            shapes = [s for s in (range(sm.n_rshapes) if shapes is None else shapes) if sm.links[sm.rshape_link[s]]._name in names]
+        is_np = isinstance(q, np.ndarray) or not hasattr(q, "is_cuda")
+        if is_np:
+            q = np.asarray(q, dtype=np.float64)
+        if q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        if not hasattr(camera_pose, "ndim"):
+            camera_pose = np.asarray(camera_pose, dtype=np.float64)
+        one = q.ndim == 1 and camera_pose.ndim == 2
+        k = intrinsics if intrinsics is not None else intrinsics_from_fov(width, height, fov)
+        res = dev.render_depth(q.reshape(-1, self.dof), camera_pose, k, height, width, near=near, far=far, shapes=shapes, world=world,
+                               out=out, labels=labels, frame=frame)
+        parts = res if labels else (res,)
+        if one:
+            parts = tuple(p.reshape(int(height), int(width)) for p in parts)
+        if is_np:
+            parts = tuple(p.cpu().numpy() for p in parts)
+        return parts if labels else parts[0]
+
     def cloud_clearance(self, q, cloud, d_max: float, ignore_links=()):
         """(distance, link name, point index) per configuration: the smallest signed distance between a link shape and a point of
         ``cloud`` when it is below ``d_max`` (else inf, None, -1; NaN, None, -1 for a non-finite configuration).  ``q`` is

@@ -1,6 +1,6 @@
 """Point-cloud obstacles, measured on one GPU (`profiles/cloud_time.log`).
 
-    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records,depth,fuse] [--reps 5]
+    python tools/cloud_time.py [--out profiles/cloud_time.log] [--append] [--only update,validity,clearance,sweep,baseline,edges,certified,splines,records,depth,fuse,render] [--reps 5]
 
 The c2 arm (its cube plays no part: the cloud entries look at the cloud alone) against the "scan" of tests/cloud_cases.py -- half
 the points on a wall x = 0.45, half on a table z = 0.10 -- at N = 1e3 .. 1e6 points of radius 0.01, the base link's shape left out
@@ -50,6 +50,11 @@ microseconds is not timed as one launch), a warm-up per shape, the median of --r
                 state, at least 10 windows each: PointCloud.integrate_depth cycling over the ring; the prefixes 1, 1..2, ... 1..7 of its
                 seven steps on the last frame, a step's time being the difference of two (the steps that write are idempotent there);
                 and update_from_depth of the same frame on a cloud of its own.  (profiles/cloud_fuse_time.log)
+    render      (only when asked for) c2, the arm and its obstacle drawn, from a camera 1.6 m from the arm (vertical field of view 60
+                degrees, defaults otherwise: eps 1e-6, 256 steps): DeviceModel.render_depth of 160x120 and 640x480 frames, B = 1 and
+                B = 16 configurations under one pose, at least 10 windows each: ms per frame, distance evaluations per pixel and
+                the unresolved share (its counts); beside it, for orientation only, backproject + cloud_self_filter of the frame it
+                rendered, windows alternating.  (profiles/cloud_render_time.log)
 """
 import argparse
 import os
@@ -320,6 +325,36 @@ def depth_part(arm, dev, sm, chain, reps):
         say(f"    update(all {n} pixels, no mask)     {fmt(timed(lambda: cloud.update(pts), reps))}")
 
 
+def render_part(arm, dev, sm, chain, reps):
+    from numbotics_amd.physics import backproject, intrinsics_from_fov
+    reps = max(reps, 10)
+    pad = 0.02
+    qs = sample_q(chain, 16, seed=5)
+    cam = np.array([[-1.0, 0.0, 0.0, 1.6], [0.0, -1.0, 0.0, 0.3], [0.0, 0.0, 1.0, 0.6], [0.0, 0.0, 0.0, 1.0]])
+    Tt = torch.from_numpy(cam).cuda()
+    cnt = torch.zeros((3,), dtype=torch.int64, device="cuda")
+    say(f"render: c2 ({sm.n_rshapes} robot shapes, {sm.n_wshapes} world), camera at (1.6, 0.3, 0.6) looking along -x, fov 60, near 0.01, far 1000, "
+        f"eps 1e-6, max_steps 256; >= {reps} windows")
+    for W, H in ((160, 120), (640, 480)):
+        intr = intrinsics_from_fov(W, H, 60.0)
+        for B in (1, 16):
+            qt = torch.from_numpy(np.ascontiguousarray(qs[:B])).cuda()
+            depth = torch.empty((B, H, W), dtype=torch.float32, device="cuda")
+            dev.render_depth(qt, Tt, intr, H, W, out=depth, counts=cnt, frame="numbotics")
+            c = cnt.cpu().numpy()
+            n = B * H * W
+            pts = torch.empty((H * W, 3), dtype=torch.float64, device="cuda")
+            keep = torch.empty((H * W,), dtype=torch.uint8, device="cuda")
+
+            def consume():
+                backproject(depth[0], intr, Tt, frame="numbotics", out=(pts, keep))
+                dev.cloud_self_filter(pts, qt[0], RADIUS, pad, keep=keep)
+            tr, tc = timed_pair(lambda: dev.render_depth(qt, Tt, intr, H, W, out=depth, frame="numbotics"), consume, reps)
+            say(f"  {W}x{H} B = {B:2d}: render {fmt(tr)} = {tr[0] / B:.3f} ms/frame; hit {c[0] / n:.3f}, unresolved {c[1] / n:.5f}, "
+                f"{c[2] / n:.2f} distance evaluations/pixel")
+            say(f"           backproject + self-filter of frame 0 (padding {pad}) {fmt(tc)}")
+
+
 def fuse_part(arm, dev, sm, chain, reps):
     from numbotics_amd.physics import backproject, intrinsics_from_fov
     from numbotics_amd.physics.pointcloud import append, carve
@@ -461,6 +496,8 @@ def main():
         depth_part(arm, dev, sm, chain, a.reps)
     if "fuse" in only:
         fuse_part(arm, dev, sm, chain, a.reps)
+    if "render" in only:
+        render_part(arm, dev, sm, chain, a.reps)
 
 
 if __name__ == "__main__":
