@@ -820,6 +820,64 @@ int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const do
                                             int32_t degree, const double *knots /* host */, double *mu /* [S][n_ctrl-degree][R] */);
 
 /*
+ * Held objects (additive; the reference fixes a body to a link with World.add_constraint, a Bullet dynamics constraint: here it is a
+ * kinematic attachment for collision checks).  A held object is H shapes (1 .. 8; sphere, capsule, box, cylinder) riding on one link
+ * of the descriptor it was made against.  The world pose of held shape h at configuration q is
+ *     F(q) . ((A . G) . L_h)
+ * F(q) the moving frame `frame` of the descriptor (-1: the base), A [12] the link's constant pose in that frame, G the grasp (the
+ * object's pose in the link frame), L_h = shape_local[h] [12] the shape in the object's frame; all 3x4 row-major.  The two constant
+ * products are formed per lane on the device, each entry as xf_mul has it:
+ *     R[i][j] = fma(a[i][2], b[2][j], fma(a[i][1], b[1][j], a[i][0] * b[0][j]))
+ *     t[i]    = fma(a[i][2], tb[2], fma(a[i][1], tb[1], fma(a[i][0], tb[0], ta[i])))
+ * whether G is the stored one or comes with the call.  nbk_held_locals_host (no GPU needed) runs that routine on HOST arrays:
+ * out[h] = (A . G) . L[h].  shape_param[h] [4] and shape_type[h] are a robot shape's (nbk_model_desc.rshape_param / rshape_type).
+ *
+ * The entry points below give the held object's verdict ALONE -- the descriptor's own pairs play no part, and the object's copy among
+ * the world shapes, where the caller registered one, is still what nbk_validity_batch sees (the caller parks or unpairs it):
+ *   held shape h x world shape w for every w of world_shapes (ascending indices of the descriptor's world shapes);
+ *   robot shape s x held shape h for every s of robot_bits (HOST, ceil(S / 64) words in the numbering of nbk_model_create; NULL = none;
+ *   a set needs S <= 256);
+ * each pair by the predicate of nbk_validity_batch -- bit for bit what a descriptor reports that holds the held shapes as robot
+ * shapes S .. S+H-1 of `frame` with local pose out[h] and the pairs (s, S+h) and (S+h, (S+H)+w).
+ *
+ * nbk_held_create: one allocation and one copy; no later call allocates.  NBK_ERR_INVALID for a null pointer, H < 1, a frame outside
+ * -1 .. n_joints-1, a non-finite pose or parameter, an unknown shape type, world indices out of range or not ascending;
+ * NBK_ERR_UNSUPPORTED for H > 8, an NBK_HULL shape, or robot_bits on a descriptor of more than 256 robot shapes.  The descriptor
+ * must outlive the held object, and must be the `m` of every call with it (NBK_ERR_INVALID otherwise, as for a device that is not
+ * current).
+ *
+ * nbk_held_validity_batch: q (device) [B][n_q].  grasp (device) [grasp_rows][16], each row a 4x4 row-major pose whose first three rows
+ * are read when the kernel runs (a replayed graph follows a grasp rewritten in place); grasp_rows = 0 (grasp NULL: the stored G), 1
+ * (one grasp for every row) or B (row b's own: screening grasp candidates).  Bit b = 1 iff some pair above is closer than
+ * `threshold`, or row b of q or its grasp row is not finite, or the world status of a movable descriptor is set.  mask_bits /
+ * mask_bytes as nbk_cloud_validity_batch; accumulate != 0 ORs into them: nbk_validity_batch, then this call on the same mask, is
+ * validity with the object in the hand.  One kernel, one row per lane; asynchronous, no allocation, capturable; LDS holds the q rows only.
+ *
+ * nbk_edge_held_validity_batch: nbk_edge_cloud_validity_batch with the held object's verdict per sample: the same edge rule, end,
+ * n_samples, accumulate (valid is only ever lowered; an entry that is 0 costs nothing) and workspace
+ * (nbk_edge_held_workspace_bytes(E), 40 bytes per edge, 64-byte aligned).  grasp (device, optional) [16]: ONE grasp for the call,
+ * NULL = the stored G; a non-finite grasp or a set world status makes every non-degenerate edge invalid.  Four kernels on `stream`.
+ * Argument errors as nbk_edge_cloud_validity_batch.
+ */
+typedef struct nbk_held nbk_held;
+int32_t nbk_held_locals_host(const double *A /* [12] */, const double *G /* [12] */, const double *L /* [H][12] */, int32_t H,
+                             double *out /* [H][12] */);   /* no GPU */
+int32_t nbk_held_create(const nbk_model *m, int32_t frame, const double *A /* host [12] */, const double *G /* host [12] */, int32_t H,
+                        const int32_t *shape_type /* host [H] */, const double *shape_local /* host [H][12] */,
+                        const double *shape_param /* host [H][4] */, int32_t n_world, const int32_t *world_shapes /* host */,
+                        const uint64_t *robot_bits /* host, optional */, nbk_held **out);
+void nbk_held_destroy(nbk_held *h);
+int32_t nbk_held_validity_batch(const nbk_model *m, const nbk_held *held, const double *q, int64_t B,
+                                const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double threshold,
+                                int32_t accumulate, uint64_t *mask_bits, uint8_t *mask_bytes, void *stream);
+int64_t nbk_edge_held_workspace_bytes(int64_t E);
+int32_t nbk_edge_held_validity_batch(const nbk_model *m, const nbk_held *held, const double *starts, const double *goals,
+                                     const double *dist /* optional */, int64_t E, double resolution, double max_distance,
+                                     int32_t mode, double threshold, const double *grasp /* DEVICE [16] or NULL */,
+                                     int32_t accumulate, uint8_t *valid, double *end /* optional */,
+                                     int32_t *n_samples /* optional */, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -41,6 +41,8 @@ SYMBOLS = [
     "nbk_frame_cloud_carve", "nbk_frame_cloud_carve_host", "nbk_frame_cloud_novel", "nbk_frame_cloud_append_workspace_bytes",
     "nbk_frame_cloud_append",
     "nbk_render_depth_lds_bytes", "nbk_render_ray_spans_host", "nbk_render_depth_batch",
+    "nbk_held_locals_host", "nbk_held_create", "nbk_held_destroy", "nbk_held_validity_batch",
+    "nbk_edge_held_workspace_bytes", "nbk_edge_held_validity_batch",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -169,6 +171,14 @@ def load():
     lib.nbk_render_ray_spans_host.argtypes = [i32, i32, f64, f64, f64, f64, vp, vp, vp, i32, f64, f64, vp, vp]
     lib.nbk_render_depth_batch.argtypes = [vp, vp, i64, vp, i64, i64, i32, i32, f64, f64, f64, f64, f64, f64, f64, i32, vp, i32, C.c_float,
                                            vp, vp, vp, vp]
+    lib.nbk_held_locals_host.argtypes = [vp, vp, vp, i32, vp]
+    lib.nbk_held_create.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(C.c_void_p)]
+    lib.nbk_held_destroy.argtypes = [vp]
+    lib.nbk_held_destroy.restype = None
+    lib.nbk_held_validity_batch.argtypes = [vp, vp, vp, i64, vp, i64, f64, i32, vp, vp, vp]
+    lib.nbk_edge_held_workspace_bytes.argtypes = [i64]
+    lib.nbk_edge_held_workspace_bytes.restype = i64
+    lib.nbk_edge_held_validity_batch.argtypes = [vp, vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, i32, vp, vp, vp, vp, i64, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

@@ -215,6 +215,7 @@ struct nbk_model {
     const int* rs_user = nullptr;             // [S] (device) the caller's index of each robot shape (frame order); h_rs_user: the host copy.  Read by the
                                               // point-cloud entries (nbk_cloud.hpp), which name shapes by the caller's index
     std::vector<int> h_rs_user;
+    std::vector<unsigned> h_frame_mask;       // [J] joints on the path from the base to each moving frame (frame_masks): the held objects' replay (nbk_held.hpp)
     // Everything above is fixed at creation.  What calls change on the host lives in `host`, which a const nbk_model* may write.
     struct Host {
         // Internal scratch of nbk_validity_batch / nbk_edge_validity_batch: ONE SET PER STREAM (created on a stream's first call), so
@@ -4141,7 +4142,7 @@ static HullSlots pack_model(const nbk_model_desc* d, const ModelTables& t, Blob&
     B.bind(&m.bq_static, t.bq_static.data(), P);  B.bind(&M.rs_reach, t.reach.data(), S);
     const int status0[4] = {0, 0, 0, 0};
     B.bind(&M.world_status, status0, 4);
-    B.bind(&M.rs_user, t.order.data(), S);  M.h_rs_user = t.order;
+    B.bind(&M.rs_user, t.order.data(), S);  M.h_rs_user = t.order;  M.h_frame_mask = t.frame_mask;
     B.bind(&m.rs_in, t.rs_in.data(), S);  B.bind(&m.ws_in, t.ws_in.data(), W);
     hs.verts = B.bind(&m.hull_blob, t.hull_blob.data(), t.hull_blob.size());
     hs.planes = B.add(d->hull_planes, sizeof(double) * 4 * (size_t)(H > 0 ? d->hull_face_begin[H] : 0));
@@ -5445,3 +5446,4 @@ int32_t nbk_validity_batch_host(const nbk_model* m, const double* q, int64_t B, 
 }  // extern "C"
 
 #include "nbk_cloud.hpp"             // point-cloud obstacles: their own object, kernels and entry points
+#include "nbk_held.hpp"              // held objects: a body attached to a link, its own object, kernels and entry points

@@ -1,0 +1,418 @@
+// nbk_held.hpp -- held objects: a body of 1..8 primitive shapes riding on one link, checked on the device.  Included by nbk.hip after
+// nbk_cloud.hpp; DESIGN.md 3, "Held objects".
+//
+// The world pose of held shape h at configuration q is  F(q) . ((A . G) . L_h):  F(q) the moving frame of the holding link's joint
+// (the replay of cloud_shape_frame for the frame's joint mask), A the link's constant pose in that frame, G the grasp (the object in
+// the link frame; the stored one, or one per row of the call), L_h the shape in the object's frame.  The two constant products are
+// formed per lane by held_locals, xf_mul's expression; nbk_held_locals_host runs the same routine on the host.
+//
+// A held object is a device object of its own (nbk_held), made against a descriptor like nbk_cloud against nothing: its kernels sit
+// beside the validity pipeline and touch none of it.  Its verdict is the held object's ALONE -- held shape h against the world shapes
+// of its list and the robot shapes of its set, each pair by the scene's own predicate in the operand order of a descriptor that holds
+// the held shapes as robot shapes S .. S+H-1 of the holding frame with the pairs (s, S+h) and (S+h, world w):
+//   world w   tc = (thr + margin_h) + margin_w, rs = (tc + rho_h) + rho_w; free unless rs > 0 and |c_h - c_w|^2 < rs^2; a plane is
+//             always a candidate and decided by plane_collides(held, plane, thr, rho_h)
+//   robot s   tc = (thr + margin_s) + margin_h, rs = (tc + rho_s) + rho_h; free unless rs > 0 and |c_s - c_h|^2 < rs^2
+//   then cores_collide_exact with the cores in canonical order (kind ascending; on a tie the descriptor's first operand first).
+// The world loop is linear in the list: a grid over many world shapes is a later step.
+#pragma once
+
+namespace nbk {
+
+constexpr int HELD_MAX_SHAPES = 8;
+constexpr int HELD_SHAPE_LEN = 18;              // per shape: L_h [12] | h0 h1 h2 rad margin rho
+
+struct HeldDev {                                // what the kernels read (by value)
+    unsigned mask;                              // joints on the path from the base to the holding frame
+    int n_shapes, n_world;
+    const double* tab;                          // A [12] | G [12] | n_shapes x HELD_SHAPE_LEN
+    const int* kind;                            // [n_shapes] core kinds
+    const int* world;                           // [n_world] allowed world shapes, ascending
+    CloudSel robot;                             // allowed robot shapes, device order (all == 0)
+};
+
+// o = a * b for 3x4 poses stored [12] row-major (rows of a 4x4 work as well: only [4 i + j], j < 4, i < 3 is read): xf_mul's
+// expression, term for term
+__host__ __device__ inline void held_mul12(const double* a, const double* b, double* o) {
+    for (int i = 0; i < 3; ++i) {
+        const double a0 = a[4 * i], a1 = a[4 * i + 1], a2 = a[4 * i + 2];
+        for (int j = 0; j < 3; ++j) o[4 * i + j] = NBK_FMA(a2, b[8 + j], NBK_FMA(a1, b[4 + j], a0 * b[j]));
+        o[4 * i + 3] = NBK_FMA(a2, b[11], NBK_FMA(a1, b[7], NBK_FMA(a0, b[3], a[4 * i + 3])));
+    }
+}
+// the local pose of held shape h in the holding frame: (A . G) . L_h
+__host__ __device__ inline void held_locals(const double* AG, const double* L, double* out) { held_mul12(AG, L, out); }
+
+// F(q): the joints of `mask`, base first (cloud_shape_frame for a mask instead of a shape)
+NBK_DEV void held_frame(const DevModel& m, unsigned mask, const double* myq, Xf& T) {
+    xf_from12(m.base_pose, T);
+    for (int k = 0; k < m.n_joints; ++k) {
+        if (((mask >> k) & 1u) == 0u) continue;
+        Xf nxt;
+        joint_apply(m, k, T, myq[m.joint_qidx[k]], nxt);
+        T = nxt;
+    }
+}
+
+// core of held shape h from the holding frame F and A . G: build_core's robot branch with the local pose formed here
+NBK_DEV void held_core(const HeldDev& hd, int h, const Xf& F, const double* AG, Core& o) {
+    const double* rec = hd.tab + 24 + HELD_SHAPE_LEN * h;
+    double loc[12];
+    held_locals(AG, rec, loc);
+    const double* cc = rec + 12;
+    o.kind = hd.kind[h];
+    o.h[0] = cc[0]; o.h[1] = cc[1]; o.h[2] = cc[2]; o.rad = cc[3]; o.margin = cc[4]; o.rho = cc[5];
+    double Rl[9], tl[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { Rl[3 * i] = loc[4 * i]; Rl[3 * i + 1] = loc[4 * i + 1]; Rl[3 * i + 2] = loc[4 * i + 2]; tl[i] = loc[4 * i + 3]; }
+    xf_mul_pos(F, tl, o.c);
+    if (o.kind == K_SEG || o.kind == K_CYL) {
+        xf_mul_col(F, Rl, 2, o.ax[2]);
+    } else if (o.kind == K_BOX) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) xf_mul_col(F, Rl, j, o.ax[j]);
+    }
+}
+
+// o = first ? a : b, member by member (registers stay registers: no core is addressed through a lane-varying pointer)
+NBK_DEV void held_pick(bool first, const Core& a, const Core& b, Core& o) {
+    o.kind = first ? a.kind : b.kind;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        o.c[e] = first ? a.c[e] : b.c[e];
+        o.h[e] = first ? a.h[e] : b.h[e];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o.ax[j][e] = first ? a.ax[j][e] : b.ax[j][e];
+    }
+    o.rad = first ? a.rad : b.rad;
+    o.margin = first ? a.margin : b.margin;
+    o.rho = first ? a.rho : b.rho;
+}
+
+// the pair predicate past the bounding spheres for (P, Q) in the descriptor's operand order, neither a plane
+NBK_DEV bool held_collides(const Core& P, const Core& Q, double tc) {
+    const bool keep = !(P.kind > Q.kind);
+    Core A, Bc;
+    held_pick(keep, P, Q, A);
+    held_pick(keep, Q, P, Bc);
+    return cores_collide_exact(A, Bc, tc);
+}
+
+// The walk: does the held object at the lane's staged row `myq` with the grasp `grasp_row` (12 values of a 3x4, or the first three rows
+// of a 4x4) touch an allowed world or robot shape?  Called by every lane of the wave (`active`: this lane has a row; `hit`: its
+// verdict so far, raised here -- a lane that comes in with a hit, or without a row, only keeps the ballots company).  Two stages per
+// held shape and list, as cloud_row_hits: each lane runs ahead to its next candidate that passes the bounding spheres, then the lanes
+// that hold one decide theirs side by side.
+NBK_DEV void held_row_hits(const DevModel& m, const HeldDev& hd, const double* grasp_row, double thr, const double* myq, bool active,
+                           bool& hit) {
+    if (__builtin_amdgcn_ballot_w64(active && !hit) == 0ull) return;
+    Xf F;
+    double AG[12];
+    if (active && !hit) {
+        held_frame(m, hd.mask, myq, F);
+        double G[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) G[e] = grasp_row[e];
+        held_mul12(hd.tab, G, AG);
+    }
+    Xf T;
+    int cur_frame = -2;                                  // per lane: the frame T holds
+    for (int h = 0; h < hd.n_shapes; ++h) {
+        const bool work = active && !hit;
+        if (__builtin_amdgcn_ballot_w64(work) == 0ull) break;
+        Core Hc;
+        cloud_core_init(Hc);
+        if (work) held_core(hd, h, F, AG, Hc);
+        // ---- the world list
+        int i = 0;
+        while (true) {
+            bool cand = false;
+            int w = 0;
+            double tc = 0.0;
+            while (work && !hit && !cand && i < hd.n_world) {
+                w = hd.world[i++];
+                if (m.ws_kind[w] == K_PLANE) { cand = true; break; }
+                const double* wc = m.ws_core + 18 * (size_t)w;
+                tc = (thr + Hc.margin) + wc[16];
+                const double rs = (tc + Hc.rho) + wc[17];
+                double dl[3];
+                sub3(Hc.c, wc, dl);
+                cand = rs > 0.0 && dot3(dl, dl) < rs * rs;
+            }
+            if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+            if (cand) {
+                Core Wc;
+                cloud_core_init(Wc);
+                load_wcore(m, w, Wc);
+                if (Wc.kind == K_PLANE) { if (plane_collides(Hc, Wc, thr, Hc.rho)) hit = true; }
+                else if (held_collides(Hc, Wc, tc)) hit = true;
+            }
+        }
+        // ---- the robot set (device order)
+        int s = 0;
+        while (true) {
+            bool cand = false;
+            double tc = 0.0;
+            Core A;
+            cloud_core_init(A);
+            while (work && !hit && !cand && s < m.n_rshapes) {
+                const int sc = s++;
+                if (!cloud_selected(hd.robot, sc)) continue;
+                if (m.rs_frame[sc] != cur_frame) { cloud_shape_frame(m, sc, myq, T); cur_frame = m.rs_frame[sc]; }
+                build_core(m, sc, T, A);
+                tc = (thr + A.margin) + Hc.margin;
+                const double rs = (tc + A.rho) + Hc.rho;
+                double dl[3];
+                sub3(A.c, Hc.c, dl);
+                cand = rs > 0.0 && dot3(dl, dl) < rs * rs;
+            }
+            if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+            if (cand && held_collides(A, Hc, tc)) hit = true;
+        }
+    }
+}
+
+// the lane's grasp row: the stored one (rows == 0), the call's one row (1) or row b of B; `fin`: every value read is finite
+NBK_DEV const double* held_grasp_row(const HeldDev& hd, const double* __restrict__ grasp, int grasp_rows, int64_t b, bool& fin) {
+    const double* g = grasp_rows == 0 ? hd.tab + 12 : (grasp_rows == 1 ? grasp : grasp + 16 * b);
+    fin = true;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) fin = fin && (g[e] - g[e] == 0.0);
+    return g;
+}
+
+// verdict of row b = the walk's, or 1 for a non-finite q or grasp row or a set world status (wstatus: the movable descriptor's, else
+// null).  A workgroup owns one mask word, so the word and the bytes have one writer each.
+__global__ __launch_bounds__(64) void k_held_validity(DevModel m, HeldDev hd, const int* __restrict__ wstatus, const double* __restrict__ q,
+                                                      int64_t B, const double* __restrict__ grasp, int grasp_rows, double thr,
+                                                      int accumulate, unsigned long long* __restrict__ mask_bits,
+                                                      uint8_t* __restrict__ mask_bytes) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    double* myq = lds + lane * m.n_q;
+    const bool wbad = wstatus != nullptr && *wstatus != 0;
+    bool hit = false;
+    const double* grow = hd.tab + 12;
+    if (active) {
+        bool gfin = true;
+        grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
+        hit = !cloud_stage_q(q, b, m.n_q, myq) || !gfin || wbad;
+    }
+    if (!wbad) held_row_hits(m, hd, grow, thr, myq, active, hit);
+    const unsigned long long word = __builtin_amdgcn_ballot_w64(active && hit);
+    if (mask_bits != nullptr && lane == 0) {
+        if (accumulate) { if (word != 0ull) mask_bits[blockIdx.x] |= word; }
+        else mask_bits[blockIdx.x] = word;
+    }
+    if (mask_bytes != nullptr && active) {
+        if (!accumulate) mask_bytes[b] = hit ? 1 : 0;
+        else if (hit) mask_bytes[b] = 1;
+    }
+}
+
+// ---- sampled edges with the held object (nbk_edge_held_validity_batch): k_cloud_edges with the held walk in the cloud walk's place.
+// valid[e] before the walk is k_cloud_edges_init's; one grasp per call; a non-finite grasp or a set world status makes every
+// non-degenerate edge invalid.
+__global__ __launch_bounds__(256) void k_held_edges_init(const unsigned long long* __restrict__ cnt, int64_t E, int accumulate,
+                                                         uint8_t* __restrict__ valid) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const bool ok = cnt[e] != 0ull && cnt[e] <= 0xffffffffull;
+    valid[e] = (ok && (!accumulate || valid[e] != 0)) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void k_held_edges(DevModel m, HeldDev hd, const int* __restrict__ wstatus, EdgeSrc es,
+                                                   const unsigned long long* __restrict__ offs, int64_t E,
+                                                   const double* __restrict__ grasp, int grasp_rows, double thr, uint8_t* valid) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    double* myq = lds + lane * m.n_q;
+    const unsigned long long total = offs[E];
+    bool gfin = true;
+    const double* grow = held_grasp_row(hd, grasp, grasp_rows, 0, gfin);
+    const bool bad = !gfin || (wstatus != nullptr && *wstatus != 0);
+    for (unsigned long long base = (unsigned long long)blockIdx.x * WAVE; base < total; base += (unsigned long long)gridDim.x * WAVE) {
+        const unsigned long long f = base + (unsigned long long)lane;
+        int64_t e = 0;
+        bool work = false;
+        if (f < total) {
+            e = cloud_flat_owner(offs, E, f);
+            if (__hip_atomic_load(valid + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+                edge_sample_row(es, ((unsigned long long)e << 32) | (f - offs[e]), m.n_q, myq, 1);
+                work = !row_nonfinite(myq, m.n_q, 1) && !bad;
+                if (!work) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        bool hit = false;
+        if (!bad) held_row_hits(m, hd, grow, thr, myq, work, hit);
+        if (hit) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+}  // namespace nbk
+
+struct nbk_held {
+    nbk::HeldDev d;
+    const nbk_model* model;        // the descriptor it was made against: its calls take no other
+    int device;
+    void* blob;
+};
+
+namespace nbk {
+
+static int32_t held_call_begin(const nbk_model* m, const nbk_held* h) {
+    if (h->model != m) { snprintf(g_err, sizeof(g_err), "the held object was made against another descriptor"); return NBK_ERR_INVALID; }
+    NBK_DEVICE(m);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != h->device) {
+        snprintf(g_err, sizeof(g_err), "held object belongs to device %d, the current device is %d", h->device, dev);
+        return NBK_ERR_INVALID;
+    }
+    return NBK_OK;
+}
+
+static bool held_pose_finite(const double* p) {
+    for (int e = 0; e < 12; ++e) if (!(p[e] - p[e] == 0.0)) return false;
+    return true;
+}
+
+}  // namespace nbk
+
+extern "C" {
+
+int32_t nbk_held_locals_host(const double* A, const double* G, const double* L, int32_t H, double* out) {
+    if (A == nullptr || G == nullptr || H < 0 || (H > 0 && (L == nullptr || out == nullptr))) return NBK_ERR_INVALID;
+    double AG[12];
+    held_mul12(A, G, AG);
+    for (int32_t h = 0; h < H; ++h) held_locals(AG, L + 12 * (size_t)h, out + 12 * (size_t)h);
+    return NBK_OK;
+}
+
+int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, const double* G, int32_t H, const int32_t* shape_type,
+                        const double* shape_local, const double* shape_param, int32_t n_world, const int32_t* world_shapes,
+                        const uint64_t* robot_bits, nbk_held** out) {
+    if (out == nullptr) return NBK_ERR_INVALID;
+    *out = nullptr;
+    if (m == nullptr || A == nullptr || G == nullptr || H < 1 || shape_type == nullptr || shape_local == nullptr || shape_param == nullptr ||
+        n_world < 0 || (n_world > 0 && world_shapes == nullptr))
+        return NBK_ERR_INVALID;
+    if (frame < -1 || frame >= m->n_joints || n_world > m->d.n_wshapes) return NBK_ERR_INVALID;
+    if (!held_pose_finite(A) || !held_pose_finite(G)) return NBK_ERR_INVALID;
+    if (H > HELD_MAX_SHAPES) return NBK_ERR_UNSUPPORTED;
+    for (int32_t h = 0; h < H; ++h) {
+        if (shape_type[h] == NBK_HULL) return NBK_ERR_UNSUPPORTED;
+        if (shape_type[h] != NBK_SPHERE && shape_type[h] != NBK_CAPSULE && shape_type[h] != NBK_BOX && shape_type[h] != NBK_CYLINDER) return NBK_ERR_INVALID;
+        if (!held_pose_finite(shape_local + 12 * (size_t)h)) return NBK_ERR_INVALID;
+        for (int e = 0; e < 4; ++e) if (!(shape_param[4 * h + e] - shape_param[4 * h + e] == 0.0)) return NBK_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_world; ++i) {
+        if (world_shapes[i] < 0 || world_shapes[i] >= m->d.n_wshapes) return NBK_ERR_INVALID;
+        if (i > 0 && world_shapes[i] <= world_shapes[i - 1]) return NBK_ERR_INVALID;
+    }
+    if (robot_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
+    NBK_DEVICE(m);
+    // the tables, then one allocation and one copy
+    std::vector<double> tab(24 + HELD_SHAPE_LEN * (size_t)H, 0.0);
+    std::vector<int> kind(H, 0), world(n_world > 0 ? n_world : 1, 0);
+    memcpy(&tab[0], A, 12 * sizeof(double));
+    memcpy(&tab[12], G, 12 * sizeof(double));
+    for (int32_t h = 0; h < H; ++h) {
+        double* rec = &tab[24 + HELD_SHAPE_LEN * (size_t)h];
+        memcpy(rec, shape_local + 12 * (size_t)h, 12 * sizeof(double));
+        core_params(shape_type[h], shape_param + 4 * (size_t)h, kind[h], rec + 12);
+        rec[17] = host_bound_radius(kind[h], rec + 12);
+    }
+    for (int32_t i = 0; i < n_world; ++i) world[i] = world_shapes[i];
+    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
+    const size_t o_kind = up(sizeof(double) * tab.size());
+    const size_t o_world = up(o_kind + sizeof(int) * kind.size());
+    const size_t bytes = up(o_world + sizeof(int) * world.size());
+    std::vector<char> host(bytes, 0);
+    memcpy(host.data(), tab.data(), sizeof(double) * tab.size());
+    memcpy(host.data() + o_kind, kind.data(), sizeof(int) * kind.size());
+    memcpy(host.data() + o_world, world.data(), sizeof(int) * world.size());
+    std::unique_ptr<nbk_held> hd(new nbk_held());
+    hipError_t e = hipMalloc(&hd->blob, bytes);
+    if (e != hipSuccess) { hip_fail(e, "hipMalloc(held)"); return NBK_ERR_ALLOC; }
+    e = hipMemcpy(hd->blob, host.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(hd->blob); return hip_fail(e, "hipMemcpy(held)"); }
+    const char* base = static_cast<const char*>(hd->blob);
+    hd->d.mask = frame >= 0 ? m->h_frame_mask[frame] : 0u;
+    hd->d.n_shapes = H;
+    hd->d.n_world = n_world;
+    hd->d.tab = reinterpret_cast<const double*>(base);
+    hd->d.kind = reinterpret_cast<const int*>(base + o_kind);
+    hd->d.world = reinterpret_cast<const int*>(base + o_world);
+    hd->d.robot = robot_bits == nullptr ? CloudSel{{0ull, 0ull, 0ull, 0ull}, 0} : cloud_selection(m, robot_bits);
+    hd->model = m;
+    (void)hipGetDevice(&hd->device);
+    *out = hd.release();
+    return NBK_OK;
+}
+
+void nbk_held_destroy(nbk_held* h) {
+    if (h == nullptr) return;
+    if (h->blob) (void)hipFree(h->blob);
+    delete h;
+}
+
+int32_t nbk_held_validity_batch(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const double* grasp,
+                                int64_t grasp_rows, double threshold, int32_t accumulate, uint64_t* mask_bits, uint8_t* mask_bytes,
+                                void* stream) {
+    if (m == nullptr || held == nullptr || B < 0 || threshold != threshold) return NBK_ERR_INVALID;
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    if (B > 0 && (q == nullptr || (mask_bits == nullptr && mask_bytes == nullptr))) return NBK_ERR_INVALID;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    if (B == 0) return NBK_OK;
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
+    hipLaunchKernelGGL(k_held_validity, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d, held->d,
+                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, grasp, rows, threshold, (int)accumulate,
+                       reinterpret_cast<unsigned long long*>(mask_bits), mask_bytes);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_edge_held_workspace_bytes(int64_t E) {
+    if (E < 0 || E > EDGE_CLOUD_MAX_E) return -1;
+    return (int64_t)EdgeCloudLayout(E).bytes;
+}
+
+int32_t nbk_edge_held_validity_batch(const nbk_model* m, const nbk_held* held, const double* starts, const double* goals, const double* dist,
+                                     int64_t E, double resolution, double max_distance, int32_t mode, double threshold,
+                                     const double* grasp, int32_t accumulate, uint8_t* valid, double* end, int32_t* n_samples,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+    // (nothing below dereferences m or held before the argument rules are through: they are answered without a device)
+    if (m == nullptr || held == nullptr || E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
+    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
+        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
+    double* const plan = v.plan;
+    unsigned long long *const cnt = v.cnt, *const offs = v.offs;
+    const unsigned eblocks = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
+                       plan, cnt, end, n_samples);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_held_edges_init, dim3(eblocks), dim3(256), 0, st, cnt, E, (int)accumulate, valid);
+    NBK_HIP(hipGetLastError());
+    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
+    const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
+    hipLaunchKernelGGL(k_held_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
+                       QSlabLds(m->n_q).bytes(), st, m->d, held->d, m->movable ? (const int*)m->world_status : (const int*)nullptr, es,
+                       offs, E, grasp, grasp != nullptr ? 1 : 0, threshold, valid);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+}  // extern "C"

@@ -800,6 +800,81 @@ class DeviceModel:
             self._stream()), "nbk_edge_cloud_validity_batch")
         return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
 
+    # ---- held objects (physics/attachment.py) ------------------------------------------------------------
+    def _grasp(self, torch, pose, B, per_row):
+        """``pose`` of the held calls -> (device tensor or None, rows): None (the stored grasp, 0 rows), (4, 4) (one) or, where
+        ``per_row``, (B, 4, 4).  NumPy is staged; a float64 CUDA tensor is read in place when the kernel runs."""
+        if pose is None:
+            return None, 0
+        if torch.is_tensor(pose):
+            if not (pose.is_cuda and pose.dtype == torch.float64 and pose.is_contiguous()):
+                raise ValueError("a pose on the device must be a contiguous float64 CUDA tensor")
+            t = pose
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(pose, dtype=np.float64))).to("cuda")
+        shape = tuple(t.shape)
+        if shape == (4, 4):
+            return t, 1
+        if per_row and shape == (B, 4, 4):
+            return t, B
+        raise ValueError(f"pose must have shape (4, 4){f' or ({B}, 4, 4)' if per_row else ''}, got {shape}")
+
+    def _held(self, held):
+        if not isinstance(held, DeviceHeld) or held.dev is not self:
+            raise ValueError("held must be a DeviceHeld made against this descriptor")
+        return held._h
+
+    def held_validity(self, held, q, threshold=0.0, packed=False, pose=None, out=None):
+        """In-collision flags of q for the held object ``held`` (a ``DeviceHeld`` of this descriptor) ALONE: its shapes against the
+        world shapes and robot shapes it was resolved against (nbk_held_validity_batch); this descriptor's own pairs play no part,
+        and a copy of the object among the world shapes is still what ``validity`` sees.  ``pose``: the grasp -- the object's pose in
+        the link frame -- (4, 4), or (B, 4, 4) with one grasp per row (screening grasp candidates); default: the stored one.  NumPy
+        or a float64 CUDA tensor, which is read in place when the kernel runs, so a captured graph is re-grasped by rewriting it.  A
+        row whose q or grasp is not finite collides.  ``packed`` / ``out``: as ``cloud_validity`` -- ``validity`` then
+        ``held_validity(..., out=mask)`` is validity with the object in the hand."""
+        torch = _require_gpu()
+        h = self._held(held)
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        want = ((qs.B + 63) // 64,) if packed else (qs.B,)
+        if out is not None:
+            res = self._mask_out(torch, out, want, packed)
+        else:
+            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=qs.device)
+        words, mask = (res, None) if packed else (None, res)
+        _lib.check(self._lib.nbk_held_validity_batch(
+            self._h, h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(threshold),
+            0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
+            self._stream()), "nbk_held_validity_batch")
+        if out is not None:
+            return out
+        return qs.out(words) if packed else qs.out(mask.bool())
+
+    @staticmethod
+    def held_edge_workspace_bytes(E: int) -> int:
+        return int(_lib.load().nbk_edge_held_workspace_bytes(int(E)))
+
+    def held_edge_validity(self, held, starts, goals, resolution, max_distance, mode="connect", threshold=0.0, dist=None, pose=None,
+                           out=None, workspace=None):
+        """``edge_validity``'s edges for the held object ``held`` ALONE: an edge is valid when it is not degenerate and
+        ``held_validity`` clears every one of its samples (nbk_edge_held_validity_batch) -> (valid (E,) bool, end (E, n_q),
+        n_samples (E,) int32), ``end`` and ``n_samples`` bit for bit ``edge_validity``'s.  ``pose``: ONE grasp (4, 4) for the call,
+        as ``held_validity``'s.  ``out`` / ``workspace``: as ``cloud_edge_validity`` (``held_edge_workspace_bytes(E)``)."""
+        torch = _require_gpu()
+        h = self._held(held)
+        s, g, dd = self._stage_edges(starts, goals, dist)
+        gr, _ = self._grasp(torch, pose, s.B, False)
+        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
+        ws = torch.empty((self.held_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device) if workspace is None else workspace
+        _lib.check(self._lib.nbk_edge_held_validity_batch(
+            self._h, h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
+            float(max_distance), _mode_int(mode), float(threshold), None if gr is None else gr.data_ptr(),
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            self._stream()), "nbk_edge_held_validity_batch")
+        return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
+
     def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
         """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
         valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``)."""
@@ -948,6 +1023,55 @@ class DeviceModel:
         if out is not None:
             return valid, t_free, status
         return c.out(valid.bool()), c.out(t_free), c.out(status)
+
+
+def held_locals(A, G, L):
+    """(H, 3, 4) local poses (A . G) . L_h of held shapes in their holding frame, by the routine the held kernels use
+    (nbk_held_locals_host; no GPU needed).  ``A``, ``G``: (4, 4) or (3, 4); ``L``: (H, 4, 4) or (H, 3, 4)."""
+    A = np.ascontiguousarray(np.asarray(A, dtype=np.float64)[:3, :4]).reshape(12)
+    G = np.ascontiguousarray(np.asarray(G, dtype=np.float64)[:3, :4]).reshape(12)
+    L = np.asarray(L, dtype=np.float64)
+    L = np.ascontiguousarray(L.reshape(-1, L.shape[-2], 4)[:, :3, :]).reshape(-1, 12)
+    out = np.empty_like(L)
+    _lib.check(_lib.load().nbk_held_locals_host(A.ctypes.data, G.ctypes.data, L.ctypes.data, L.shape[0], out.ctypes.data),
+               "nbk_held_locals_host")
+    return out.reshape(-1, 3, 4)
+
+
+class DeviceHeld:
+    """A held object on the device (nbk_held): H shapes riding on moving frame ``frame`` of ``dev``'s descriptor, with the world
+    shapes and robot shapes (``SceneModel`` order) its verdict looks at.  ``A``: the link's constant pose in the frame, ``G``: the
+    default grasp, ``shape_local`` (H, 4, 4) / (H, 3, 4): each shape in the object's frame; ``shape_type`` / ``shape_param``: as a
+    robot shape's.  Allocated once; the descriptor is kept alive."""
+
+    def __init__(self, dev, frame, A, G, shape_type, shape_local, shape_param, world_shapes=(), robot_shapes=()):
+        _require_gpu()
+        if dev.scene is None:
+            raise ValueError("a held object needs a descriptor made from a SceneModel")
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64)[:3, :4]).reshape(12)
+        G = np.ascontiguousarray(np.asarray(G, dtype=np.float64)[:3, :4]).reshape(12)
+        st = np.ascontiguousarray(shape_type, dtype=np.int32).reshape(-1)
+        H = int(st.shape[0])
+        L = np.asarray(shape_local, dtype=np.float64)
+        L = np.ascontiguousarray(L.reshape(H, L.shape[-2], 4)[:, :3, :]).reshape(H, 12)
+        sp = np.ascontiguousarray(shape_param, dtype=np.float64).reshape(H, 4)
+        ws = np.ascontiguousarray(sorted(int(w) for w in world_shapes), dtype=np.int32)
+        robot = [int(x) for x in robot_shapes]
+        bits = dev._shape_bits(robot) if robot else None
+        h = C.c_void_p()
+        _lib.check(dev._lib.nbk_held_create(dev._h, int(frame), A.ctypes.data, G.ctypes.data, H, st.ctypes.data, L.ctypes.data,
+                                            sp.ctypes.data, int(ws.shape[0]), ws.ctypes.data if ws.shape[0] else None, _host_ptr(bits),
+                                            C.byref(h)), "nbk_held_create")
+        self._h, self._lib, self.dev, self.n_shapes = h, dev._lib, dev, H
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.nbk_held_destroy(h)
+            except Exception:
+                pass
+            self._h = None
 
 
 def selftest_math(a, b):

@@ -46,6 +46,7 @@ class World:
         self._ids = itertools.count()
         self._vis = None
         self._revision = 0          # bumped whenever the scene changes; device scenes key on it
+        self._attachments = []      # held objects recorded by add_constraint (physics/attachment.py)
         self.gravity = None
 
     @property
@@ -92,6 +93,34 @@ class World:
                     if link.name == name:
                         return link
         return default
+
+    def add_constraint(self, body1, body2, constraint):
+        """The reference's signature (numbotics/physics/world.py:315-360).  A FIXED ``Joint`` between a chain ``Link`` and a
+        ``PhysicsObject``, in either order, records an ``Attachment`` (physics/attachment.py): the object rides on the link at the
+        grasp the joint's ``offset`` / ``parent_pose`` / ``child_pose`` stand for (``constraint_grasp``) and is checked with
+        ``Arm.in_collision_with_attached`` / ``ConnectorParams(attached=...)``; it is returned, and listed by ``attachments()``.
+        Upstream's constraint is a Bullet dynamics constraint, this one a kinematic attachment for collision checks; every other
+        combination raises ``NotImplementedError``, as upstream does for the types it does not support."""
+        from .attachment import Attachment, constraint_grasp
+        from .chain import Link
+        from .constraint import Constraint
+        from .object import PhysicsObject
+        if getattr(constraint, "type", None) != Constraint.FIXED:
+            raise NotImplementedError(f"Only fixed constraints between a link and an object are supported, got {getattr(constraint, 'type', constraint)}")
+        if isinstance(body1, Link) and isinstance(body2, PhysicsObject):
+            link, obj, link_first = body1, body2, True
+        elif isinstance(body1, PhysicsObject) and isinstance(body2, Link):
+            link, obj, link_first = body2, body1, False
+        else:
+            raise NotImplementedError("Only a chain Link and a PhysicsObject can be constrained, got "
+                                      f"{type(body1).__name__} and {type(body2).__name__}")
+        att = Attachment(link, obj, constraint_grasp(constraint, link_first))
+        self._attachments.append(att)
+        return att
+
+    def attachments(self):
+        """The attachments recorded by ``add_constraint``, oldest first."""
+        return list(self._attachments)
 
     def step(self):
         """No dynamics here; kept so reference scripts that call ``world.step()`` still run."""

@@ -9,7 +9,10 @@ and ``connect_batch`` / ``steer_batch`` check E edges per launch (one edge per w
 the device path ANDs ``nbk_edge_cloud_validity_batch`` into the scene's verdict.  Smoothed trajectories see a scan through a per-call
 keyword, ``validate_trajectories(..., cloud=scan)`` on both connectors (``nbk_spline_cloud_validity_batch`` /
 ``nbk_spline_cloud_continuous_batch`` accumulating into the scene's result); a call that names no cloud while the params or the
-connector carry one still refuses ("do not see point clouds yet") instead of ignoring it.  ``ContinuousConnector`` takes its cloud as a constructor argument
+connector carry one still refuses ("do not see point clouds yet") instead of ignoring it.
+``ConnectorParams(attached=...)`` (an ``Attachment``, with an ``arm``) puts an object in the hand: the sampled edges and ``is_valid``
+AND the held object's verdict (``nbk_edge_held_validity_batch`` / ``nbk_held_validity_batch``) into the scene's, after the cloud's
+where both are set; trajectory checks and ``ContinuousConnector`` refuse such params ("do not see held objects yet").  ``ContinuousConnector`` takes its cloud as a constructor argument
 (``ContinuousConnector(params, cloud=...)``: certified straight edges, ``nbk_edge_cloud_continuous_batch``) and still refuses params
 that carry one.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
@@ -44,6 +47,9 @@ class ConnectorParams:
     # (Link objects or names, e.g. the base standing on a scanned table)
     cloud: object = None
     cloud_ignore_links: tuple = ()
+    # additive: an Attachment (Arm.attach / World.add_constraint) -- the object in the hand, which the sampled edges and is_valid
+    # must keep clear as well (at collision_threshold)
+    attached: object = None
 
     def __post_init__(self):
         if self.resolution <= 0:
@@ -58,6 +64,8 @@ class ConnectorParams:
             raise ValueError("Trajectory conversion function must be provided")
         if self.cloud is not None and self.arm is None:
             raise ValueError("A point cloud needs ConnectorParams(arm=...)")
+        if self.attached is not None and self.arm is None:
+            raise ValueError("A held object needs ConnectorParams(arm=...)")
 
 
 def _scene_then_cloud(inputs, scene, cloud):
@@ -77,6 +85,11 @@ def _scene_then_cloud(inputs, scene, cloud):
 def _no_cloud(params, what):
     if params.cloud is not None:
         raise ValueError(f"{what} do not see point clouds yet")
+
+
+def _no_held(params, what):
+    if params.attached is not None:
+        raise ValueError(f"{what} do not see held objects yet")
 
 
 class Connector(ABC):
@@ -140,16 +153,17 @@ class DiscreteConnector(Connector):
         p = self._params
         if p.validity_checker is not None:
             return p.validity_checker(state)
-        if p.cloud is None:
-            return not p.arm.in_collision(state, p.collision_threshold)
-        return not (p.arm.in_collision(state, p.collision_threshold)
-                    or p.arm.in_collision_with_cloud(state, p.cloud, p.collision_threshold, p.cloud_ignore_links))
+        if p.arm.in_collision(state, p.collision_threshold):
+            return False
+        if p.cloud is not None and p.arm.in_collision_with_cloud(state, p.cloud, p.collision_threshold, p.cloud_ignore_links):
+            return False
+        return p.attached is None or not p.arm.in_collision_with_attached(state, p.attached, p.collision_threshold)
 
     def _scalar(self, start, goal, mode, distance):
         """One edge, every sample in one device call (host arrays through the library's pinned staging)."""
         p = self._params
         _, dev = p.arm._scene_device()
-        if p.cloud is None and isinstance(start, np.ndarray) and isinstance(goal, np.ndarray):
+        if p.cloud is None and p.attached is None and isinstance(start, np.ndarray) and isinstance(goal, np.ndarray):
             return dev.edge_validity_scalar(start, goal, p.resolution, p.max_distance, mode=mode,
                                             threshold=p.collision_threshold, dist=float(distance))
         ok, end, ns = self._batch(start[None], goal[None], mode, np.array([distance], dtype=np.float64))
@@ -164,13 +178,19 @@ class DiscreteConnector(Connector):
             raise ValueError("batched edge checks support the default linear trajectory only")
         sm, dev = p.arm._scene_device()
         kw = dict(mode=mode, threshold=p.collision_threshold)
-        if p.cloud is None:
+        if p.cloud is None and p.attached is None:
             return dev.edge_validity(starts, goals, p.resolution, p.max_distance, dist=dist, **kw)
-        # the cloud's verdict is ANDed into the scene's `valid`
+        held = None if p.attached is None else p.attached._device(p.arm)[1]
+
+        # the cloud's verdict, then the held object's, are ANDed into the scene's `valid`
+        def others(s, g, d, res):
+            if p.cloud is not None:
+                dev.cloud_edge_validity(p.cloud, s, g, p.resolution, p.max_distance, dist=d,
+                                        shapes=p.arm._cloud_shapes(sm, p.cloud_ignore_links), out=res[0], **kw)
+            if held is not None:
+                dev.held_edge_validity(held, s, g, p.resolution, p.max_distance, dist=d, out=res[0], **kw)
         return _scene_then_cloud(
-            (starts, goals, dist), lambda s, g, d: dev.edge_validity(s, g, p.resolution, p.max_distance, dist=d, **kw),
-            lambda s, g, d, res: dev.cloud_edge_validity(p.cloud, s, g, p.resolution, p.max_distance, dist=d,
-                                                         shapes=p.arm._cloud_shapes(sm, p.cloud_ignore_links), out=res[0], **kw))
+            (starts, goals, dist), lambda s, g, d: dev.edge_validity(s, g, p.resolution, p.max_distance, dist=d, **kw), others)
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -202,6 +222,7 @@ class DiscreteConnector(Connector):
         ``cloud`` (a ``PointCloud``): the samples are checked against the scan as well (``nbk_spline_cloud_validity_batch``
         accumulating into the scene's result: t_hit is the first sample either of them rejects), without the shapes of
         ``cloud_ignore_links`` (default: the params' own tuple).  A call that names no cloud is refused when the params carry one."""
+        _no_held(self._params, "sampled trajectory checks")
         if cloud is None:
             _no_cloud(self._params, "sampled trajectory checks")
         shape = _shape(control_points)
@@ -211,6 +232,7 @@ class DiscreteConnector(Connector):
     def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None):
         """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit).  ``cloud``,
         ``cloud_ignore_links``: as ``validate_trajectories``."""
+        _no_held(self._params, "sampled trajectory checks")
         if cloud is None:
             _no_cloud(self._params, "sampled trajectory checks")
         c, t, k = _spline_parts(self._params, spline)
@@ -284,6 +306,7 @@ class ContinuousConnector(Connector):
         if not slack >= 0.0:
             raise ValueError("slack must be non-negative")
         _no_cloud(params, "certified continuous checks")
+        _no_held(params, "certified continuous checks")
         if cloud is not None:
             if params.arm is None or params.validity_checker is not None or params.trajectory_func is not _DEFAULT_TRAJ:
                 raise ValueError("a point cloud needs ConnectorParams(arm=...) with the default linear trajectory and no validity_checker")

@@ -578,6 +578,45 @@ class Arm(Robot):
         mask = dev.cloud_validity(cloud, q.reshape(-1, self.dof), threshold, shapes=shapes)
         return mask.reshape(tuple(q.shape[:-1]))
 
+    # ---- held objects ----------------------------------------------------------------------------------------
+    def attach(self, obj, link, pose=None, touch_links=()):
+        """Put ``obj`` (a ``PhysicsObject`` of boxes / spheres / capsules / cylinders, or a list of up to 8 of them) into the hand:
+        -> an ``Attachment`` (numbotics_amd.physics) of ``obj`` riding on ``link`` (a Link of this chain or its name).  ``pose``
+        (4, 4): the grasp, the object's pose in the link frame (for a list: the first object's); default: the object where it
+        stands now, relative to the link at ``arm.configuration``.  ``touch_links``: links (or names) the object may touch, e.g.
+        the fingers.  The held shapes are paired with every world shape of ``scene_model()`` that is not the object's own and with
+        every robot shape whose link is neither ``link``, nor shares its moving frame, nor is a touch link; the attachment is
+        resolved again whenever the scene changes.  Check it with ``in_collision_with_attached`` or ``ConnectorParams(attached=...)``:
+        ``in_collision`` does NOT see the held object, and still sees the object's world copy where it is one of this arm's
+        obstacles -- park it or ``remove_collision_pair`` it."""
+        from numbotics_amd.physics import Attachment
+        from .model import chain_link_poses
+        link = self._resolve(link)
+        if not self._in_chain(link):
+            raise ValueError(f"Link {getattr(link, '_name', link)} not found in chain")
+        objs = list(obj) if isinstance(obj, (list, tuple)) else [obj]
+        if pose is None:
+            if not objs or not isinstance(objs[0], PhysicsObject):
+                raise ValueError("the held object must be a PhysicsObject or a list of them")
+            pose = np.linalg.inv(chain_link_poses(self._chain)[link._name]) @ np.asarray(objs[0].pose, dtype=np.float64)
+        att = Attachment(link, objs, pose, touch_links)
+        att.spec(self)                                          # argument errors now, not at the first query
+        return att
+
+    def in_collision_with_attached(self, q, att, threshold: float = 0.0, pose=None):
+        """Is the held object of ``att`` (``attach`` / ``World.add_constraint``) closer than ``threshold`` to a world shape or a
+        link it is paired with?  ``(dof,)`` -> bool, ``(..., dof)`` -> bool array / tensor, like ``in_collision_with_cloud``.  This
+        is the held object's verdict ONLY: full validity is ``arm.in_collision(q) | arm.in_collision_with_attached(q, att)``, and
+        ``in_collision`` still sees the object's world copy where that is an obstacle of this arm.  ``pose``: another grasp for
+        this call, (4, 4), or one per configuration (B, 4, 4) -- NumPy or a float64 CUDA tensor."""
+        if q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        dev, held = att._device(self)
+        if q.ndim == 1:
+            return bool(dev.held_validity(held, q.reshape(1, -1), threshold, pose=pose)[0])
+        mask = dev.held_validity(held, q.reshape(-1, self.dof), threshold, pose=pose)
+        return mask.reshape(tuple(q.shape[:-1]))
+
     def cloud_self_filter(self, points, q, radius: float, padding: float = 0.0, keep=None, links=None, ignore_links=()):
         """Which of a depth frame's ``points`` (N, 3) are NOT the arm's own image at the configuration ``q`` the frame was taken at:
         ``keep[i]`` goes to 0 iff point i, a sphere of ``radius``, is closer than ``padding`` to a link shape -- the verdict
