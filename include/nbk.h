@@ -858,6 +858,33 @@ int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const do
  * (nbk_edge_held_workspace_bytes(E), 40 bytes per edge, 64-byte aligned).  grasp (device, optional) [16]: ONE grasp for the call,
  * NULL = the stored G; a non-finite grasp or a set world status makes every non-degenerate edge invalid.  Four kernels on `stream`.
  * Argument errors as nbk_edge_cloud_validity_batch.
+ *
+ * Held ITEMS.  The distance and certified entries work on K items (held shape h, other shape), in the order of that descriptor's pair
+ * list: first (s, S+h) for the robot shapes s of robot_bits ascending, then h; then (S+h, world w) for h, then world_shapes ascending.
+ * nbk_held_item_count gives K; nbk_held_items writes K x (held shape, kind: 0 robot / 1 world, index: s in the numbering of
+ * nbk_model_create, or w) to HOST memory.
+ *
+ * nbk_held_distances_batch: out_d (device) [B][K], the signed distance of every item at every row -- bit for bit what
+ * nbk_pair_distances_batch reports for that pair on that descriptor; NaN where row b of q or its grasp row is not finite, or the
+ * world status of a movable descriptor is set.  grasp / grasp_rows as nbk_held_validity_batch.  Planes and hull-shaped WORLD shapes
+ * are served.  One kernel, one (row, item) per lane, item-major; asynchronous, no allocation, capturable.
+ *
+ * nbk_edge_held_continuous_batch / nbk_spline_held_continuous_batch: nbk_edge_continuous_batch / nbk_spline_continuous_batch over
+ * the K items instead of the descriptor's pairs: the same conservative advancement, each item's motion bound the one
+ * nbk_edge_motion_bounds_host / nbk_spline_motion_bounds_host gives for that pair on that descriptor
+ * (nbk_edge_held_motion_bounds_host / nbk_spline_held_motion_bounds_host run the device's routine on the host, no GPU needed:
+ * mu [E][K] / [S][n_ctrl-degree][K]; the held arguments are nbk_held_create's, against the descriptor `d`).  valid / end / t_free /
+ * status as the scene's entries.  accumulate != 0: valid / t_free / status hold the result of a certified call on the same
+ * trajectories (the scene's, or the cloud's after it) and the held object's is folded into it -- the smallest stop point, COLLISION
+ * winning a tie; a trajectory that comes in with a NaN t_free stays 0 / NaN / UNDECIDED.  grasp (device, optional) [16]: ONE grasp
+ * for the call, read when the kernels run; NULL = the stored G.  A non-finite grasp, or a set world status of a movable descriptor,
+ * makes every non-degenerate trajectory 0 / NaN / UNDECIDED.  K = 0 leaves every non-degenerate trajectory FREE at its stop point.
+ * No workspace (the keys live in t_free while the call runs), no allocation, capturable.
+ *
+ * nbk_spline_held_validity_batch: nbk_spline_cloud_validity_batch with the held object's verdict per sample: the same plan, samples,
+ * first-hit rule, accumulate (valid / t_hit / n_samples as there) and workspace (nbk_spline_held_workspace_bytes(S), the layout of
+ * nbk_spline_cloud_workspace_bytes).  grasp as above; a non-finite grasp or a set world status hits every trajectory that has samples
+ * at its first sample.  Argument errors as nbk_spline_cloud_validity_batch.
  */
 typedef struct nbk_held nbk_held;
 int32_t nbk_held_locals_host(const double *A /* [12] */, const double *G /* [12] */, const double *L /* [H][12] */, int32_t H,
@@ -876,6 +903,35 @@ int32_t nbk_edge_held_validity_batch(const nbk_model *m, const nbk_held *held, c
                                      int32_t mode, double threshold, const double *grasp /* DEVICE [16] or NULL */,
                                      int32_t accumulate, uint8_t *valid, double *end /* optional */,
                                      int32_t *n_samples /* optional */, void *workspace, int64_t workspace_bytes, void *stream);
+int32_t nbk_held_item_count(const nbk_held *held);
+int32_t nbk_held_items(const nbk_held *held, int32_t *out /* host [K][3] */);
+int32_t nbk_held_distances_batch(const nbk_model *m, const nbk_held *held, const double *q, int64_t B,
+                                 const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows,
+                                 double *out_d /* [B][K] */, void *stream);
+int32_t nbk_edge_held_continuous_batch(const nbk_model *m, const nbk_held *held, const double *starts, const double *goals,
+                                       const double *dist /* optional */, int64_t E, double max_distance, int32_t mode,
+                                       double threshold, int32_t max_iter, double slack, const double *grasp /* DEVICE [16] or NULL */,
+                                       int32_t accumulate, uint8_t *valid, double *end /* optional */, double *t_free, int32_t *status,
+                                       void *stream);
+int32_t nbk_spline_held_continuous_batch(const nbk_model *m, const nbk_held *held, const double *ctrl, int64_t S, int32_t n_ctrl,
+                                         int32_t degree, const double *knots /* DEVICE */, double threshold, int32_t max_iter,
+                                         double slack, const double *grasp /* DEVICE [16] or NULL */, int32_t accumulate,
+                                         uint8_t *valid, double *t_free, int32_t *status, void *stream);
+int64_t nbk_spline_held_workspace_bytes(int64_t S);
+int32_t nbk_spline_held_validity_batch(const nbk_model *m, const nbk_held *held, const double *ctrl, int64_t S, int32_t n_ctrl,
+                                       int32_t degree, const double *knots /* DEVICE */, double resolution, double threshold,
+                                       const double *grasp /* DEVICE [16] or NULL */, int32_t accumulate, uint8_t *valid,
+                                       double *t_hit /* optional */, int32_t *n_samples /* optional */, void *workspace,
+                                       int64_t workspace_bytes, void *stream);
+int32_t nbk_edge_held_motion_bounds_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                         const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                         int32_t n_world, const int32_t *world_shapes, const uint64_t *robot_bits /* optional */,
+                                         const double *starts, const double *goals, int64_t E, double *mu /* [E][K] */);   /* no GPU */
+int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                           const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                           int32_t n_world, const int32_t *world_shapes, const uint64_t *robot_bits /* optional */,
+                                           const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                           const double *knots /* host */, double *mu /* [S][n_ctrl-degree][K] */);   /* no GPU */
 
 /*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists

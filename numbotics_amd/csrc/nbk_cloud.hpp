@@ -1125,7 +1125,8 @@ constexpr unsigned long long SPC_TOO_MANY = SPC_NONE + 3ull;      // more than 2
 constexpr unsigned long long SPC_MAX_SAMPLES = 0x7fffffffull;
 
 // one wave per trajectory, BEFORE the scan: the starting key.  Knots that break the rules (spline_knots_bad, the rule of
-// k_spline_ca_init) close every trajectory; a set cloud status hits every trajectory that has samples at its first one; accumulating,
+// k_spline_ca_init) close every trajectory; a set status word (hold, nullable: the cloud's status; for the held object's entry the
+// world status of a movable descriptor) hits every trajectory that has samples at its first one; accumulating,
 // an entry that is 0 and has no finite t_hit to lower is closed (t_prev: the caller's t_hit, null when it gave none or does not
 // accumulate).  A trajectory closed as SPC_EMPTY or SPC_TOO_MANY gets the count 0, so the flat sample range holds no sample of it
 // and the sample kernel's run time is bounded by the samples that can be looked at (k_cloud_spline_final reads 0 / -1 off the key).
@@ -1141,7 +1142,7 @@ __global__ __launch_bounds__(64) void k_cloud_spline_init(int n, int k, const do
     unsigned long long key = SPC_NONE;
     if (bad || c == 0ull) key = SPC_EMPTY;
     else if (c > SPC_MAX_SAMPLES) key = SPC_TOO_MANY;
-    else if (*hold != 0) key = 1ull;
+    else if (hold != nullptr && *hold != 0) key = 1ull;
     else if (accumulate && valid[s] == 0 && (t_prev == nullptr || t_prev[s] != t_prev[s])) key = SPC_KEEP;
     if (key == SPC_EMPTY || key == SPC_TOO_MANY) cnt[s] = 0ull;
     first[s] = key;

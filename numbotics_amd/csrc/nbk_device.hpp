@@ -1445,21 +1445,28 @@ __host__ __device__ inline double motion_abs(double x) { return x < 0.0 ? -x : x
 // c_{x,j} of a revolute joint j on shape x's path: joints k below j on that path (joint index ascending), their translation and,
 // for a prismatic k, its largest travel on the trajectory (tr.travel); then the shape's local offset and its bounding radius plus
 // margin.  TR is the trajectory's per-joint speed / travel (EdgeMotion, SplineSpanMotion): a template, not a branch on the caller.
+// A shape is its three table entries (MotionShape): the indexed forms below read them from the tables, a held shape brings its own
+// (nbk_held.hpp).
+struct MotionShape {
+    unsigned mask;               // smask
+    double loc, bnd;             // sloc, sbnd
+};
+
 template <class TR>
-__host__ __device__ inline double motion_reach(const MotionTab& t, int x, int j, const TR& tr) {
-    const unsigned mx = t.smask[x];
+__host__ __device__ inline double motion_reach(const MotionTab& t, const MotionShape& x, int j, const TR& tr) {
+    const unsigned mx = x.mask;
     double c = 0.0;
     for (int k = j + 1; k < t.n_joints; ++k) {
         if (!((mx >> k) & 1u)) continue;
         c = c + t.jtn[k];
         if (t.jtype[k] == NBK_PRISMATIC) c = c + t.jsn[k] * tr.travel(t.jqidx[k]);
     }
-    c = c + t.sloc[x];
-    return c + t.sbnd[x];
+    c = c + x.loc;
+    return c + x.bnd;
 }
 
 template <class TR>
-__host__ __device__ inline double motion_terms(const MotionTab& t, int x, unsigned js, const TR& tr, double mu) {
+__host__ __device__ inline double motion_terms(const MotionTab& t, const MotionShape& x, unsigned js, const TR& tr, double mu) {
     for (int j = 0; j < t.n_joints; ++j) {
         if (!((js >> j) & 1u)) continue;
         const int qj = t.jqidx[j];
@@ -1467,6 +1474,13 @@ __host__ __device__ inline double motion_terms(const MotionTab& t, int x, unsign
         mu = mu + c * tr.speed(qj);
     }
     return mu;
+}
+
+__host__ __device__ inline MotionShape motion_shape(const MotionTab& t, int x) { return MotionShape{t.smask[x], t.sloc[x], t.sbnd[x]}; }
+
+template <class TR>
+__host__ __device__ inline double motion_terms(const MotionTab& t, int x, unsigned js, const TR& tr, double mu) {
+    return motion_terms(t, motion_shape(t, x), js, tr, mu);
 }
 
 // mu of user pair p on the trajectory tr: a's terms first, then b's, each joint index ascending

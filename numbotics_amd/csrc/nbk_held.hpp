@@ -29,7 +29,11 @@ struct HeldDev {                                // what the kernels read (by val
     const int* kind;                            // [n_shapes] core kinds
     const int* world;                           // [n_world] allowed world shapes, ascending
     CloudSel robot;                             // allowed robot shapes, device order (all == 0)
+    int n_items;                                // K: the (held shape, other shape) items of the distance and certified entries
+    const int* items;                           // [K][4] held shape | 0 robot, 1 world | device index of the robot shape, or the world
+                                                // shape | the robot shape's caller's index (MotionTab's order), or the world shape
 };
+constexpr int HELD_ITEM_LEN = 4;
 
 // o = a * b for 3x4 poses stored [12] row-major (rows of a 4x4 work as well: only [4 i + j], j < 4, i < 3 is read): xf_mul's
 // expression, term for term
@@ -251,6 +255,241 @@ __global__ __launch_bounds__(64) void k_held_edges(DevModel m, HeldDev hd, const
     }
 }
 
+// ---- sampled B-spline trajectories with the held object (nbk_spline_held_validity_batch): k_cloud_spline with the held walk in the
+// cloud walk's place -- the same plan, scan, first-hit key (SPC_*) and accumulate rules; k_cloud_spline_init (hold: the world status
+// of a movable descriptor, else null) and k_cloud_spline_final are the cloud's.  One grasp per call; a non-finite one hits every
+// sample that is looked at, so every trajectory that has samples is hit at its first.
+template <int K>
+__global__ __launch_bounds__(64) void k_held_spline(DevModel m, HeldDev hd, const double* __restrict__ ctrl, int n,
+                                                    const double* __restrict__ knots, const double* __restrict__ plan,
+                                                    const unsigned long long* __restrict__ offs, int64_t S,
+                                                    const double* __restrict__ grasp, int grasp_rows, double thr,
+                                                    const double* __restrict__ t_prev, unsigned long long* first) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    double* myq = lds + lane * m.n_q;
+    const unsigned long long total = offs[S];
+    bool gfin = true;
+    const double* grow = held_grasp_row(hd, grasp, grasp_rows, 0, gfin);
+    for (unsigned long long base = (unsigned long long)blockIdx.x * WAVE; base < total; base += (unsigned long long)gridDim.x * WAVE) {
+        const unsigned long long f = base + (unsigned long long)lane;
+        int64_t s = 0;
+        unsigned long long j = 0ull;
+        bool work = false, hit = false;
+        if (f < total) {
+            s = cloud_flat_owner(offs, S, f);
+            j = f - offs[s];
+            const unsigned long long key = __hip_atomic_load(first + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (key <= SPC_NONE && j + 1ull < key) {
+                const double jd = (double)j;
+                const double t = jd < plan[2 * s + 1] ? jd * plan[2 * s] : 1.0;
+                if (t_prev == nullptr || !(t >= t_prev[s])) {
+                    const int ell = spline_span<K>(knots, n, t);
+                    const double* cp = ctrl + ((size_t)s * (size_t)n + (size_t)(ell - K)) * m.n_q;
+                    de_boor<K>(m.n_q, cp, knots, ell, t, [&](int c, double v) { myq[c] = v; });
+                    work = gfin && !row_nonfinite(myq, m.n_q, 1);
+                    hit = !work;                             // a non-finite sample, or grasp, collides
+                }
+            }
+        }
+        if (gfin) held_row_hits(m, hd, grow, thr, myq, work, hit);
+        if (hit) atomicMin(first + s, j + 1ull);
+    }
+}
+
+// ---- held items: one (held shape h, other shape) pair each, in the order of the pair list of a descriptor that holds the held
+// shapes as robot shapes S + h: (s, S + h) for the allowed robot shapes s in the caller's order, then h; then (S + h, world w) for h,
+// then the allowed world shapes.  HeldDev.items holds them (held_item_list, made once by nbk_held_create).
+
+// The signed distance of item `it` at the lane's staged row `myq` with the grasp `grasp_row`: item_distance's statements on the held
+// core and the other shape's, in the descriptor's operand order (robot shape first, held shape second; held shape first, world
+// shape second).  Every lane of the wave calls it; lanes with ok == false replay nothing and get NaN.  The two frames are replayed
+// from the base, each along its own mask: common ancestors give the same bits on either path.
+NBK_DEV double held_item_distance(const DevModel& m, const HeldDev& hd, const double* grasp_row, const double* myq, bool ok, int it) {
+    // the hull support's scalar-cache path (rad < 0) needs every running lane to hold the same hull: only for item-uniform waves
+    const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
+    const int it0 = __shfl(it, okm != 0ull ? __builtin_ctzll(okm) : 0);
+    const bool uniform = __builtin_amdgcn_ballot_w64(ok && it != it0) == 0ull;
+    if (!ok) return __builtin_nan("");
+    const int* rec = hd.items + HELD_ITEM_LEN * it;
+    const int h = rec[0], idx = rec[2];
+    const bool robot = rec[1] == 0;
+    Xf F;
+    held_frame(m, hd.mask, myq, F);
+    double G[12], AG[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) G[e] = grasp_row[e];
+    held_mul12(hd.tab, G, AG);
+    Core Hc, Oc;
+    cloud_core_init(Hc);
+    cloud_core_init(Oc);
+    held_core(hd, h, F, AG, Hc);
+    if (robot) {
+        Xf T;
+        cloud_shape_frame(m, idx, myq, T);
+        build_core(m, idx, T, Oc);
+    } else {
+        load_wcore(m, idx, Oc);
+    }
+    Core A, Bc;
+    held_pick(robot, Oc, Hc, A);
+    held_pick(robot, Hc, Oc, Bc);
+    if (uniform && A.kind == K_HULL) A.rad = -1.0;
+    if (uniform && Bc.kind == K_HULL) Bc.rad = -1.0;
+    double wit[9];
+    double fam = -1.0;
+    double d = cores_distance<true, true>(A, Bc, wit, &fam);
+    if (fam >= 0.0) epa_refine<true>(A, Bc, fam, d, wit);
+    return d;
+}
+
+// one (row, item) per lane, item-major (a wave holds one item unless it straddles two): out_d[b][it], NaN where the q row or the
+// grasp row is not finite or the world status is set
+__global__ __launch_bounds__(64) void k_held_distances(DevModel m, HeldDev hd, const int* __restrict__ wstatus, const double* __restrict__ q,
+                                                       int64_t B, const double* __restrict__ grasp, int grasp_rows,
+                                                       double* __restrict__ out_d) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < B * (int64_t)hd.n_items;
+    const int it = live ? (int)(i / B) : 0;
+    const int64_t b = live ? i - (int64_t)it * B : 0;
+    double* myq = lds + lane * m.n_q;
+    const bool wbad = wstatus != nullptr && *wstatus != 0;
+    bool ok = false;
+    const double* grow = hd.tab + 12;
+    if (live) {
+        bool gfin = true;
+        grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
+        ok = cloud_stage_q(q, b, m.n_q, myq) && gfin && !wbad;
+    }
+    const double d = held_item_distance(m, hd, grow, myq, ok, it);
+    if (live) out_d[b * hd.n_items + it] = d;
+}
+
+// ---- the motion bound of a held item: pair_motion_bound's bits for that pair on a descriptor whose shape tables hold, for S + h,
+// the holding frame's joint mask, the norm of the translation of (A . G) . L_h and rho + margin
+__host__ __device__ inline MotionShape held_motion_shape(unsigned mask, const double* tab, const double* grasp_row, int h) {
+    const double* rec = tab + 24 + HELD_SHAPE_LEN * h;
+    double G[12], AG[12], loc[12];
+    for (int e = 0; e < 12; ++e) G[e] = grasp_row[e];
+    held_mul12(tab, G, AG);
+    held_locals(AG, rec, loc);
+    const double n = __builtin_sqrt(NBK_FMA(loc[11], loc[11], NBK_FMA(loc[7], loc[7], loc[3] * loc[3])));      // (norm3_host's expression)
+    return MotionShape{mask, n, rec[17] + rec[16]};
+}
+
+// mu of the item `rec` on the trajectory tr.  A robot item counts the joints on one path and not on the other, the robot shape's
+// terms first; a world item counts every joint of the holding path.
+template <class TR>
+__host__ __device__ inline double held_item_motion_bound(const MotionTab& t, unsigned mask, const double* tab, const double* grasp_row,
+                                                         const int* rec, const TR& tr) {
+    const MotionShape hs = held_motion_shape(mask, tab, grasp_row, rec[0]);
+    if (rec[1] != 0) return motion_terms(t, hs, hs.mask, tr, 0.0);
+    const int a = rec[3];
+    const unsigned ma = t.smask[a];
+    const double mu = motion_terms(t, a, ma & ~hs.mask, tr, 0.0);
+    return motion_terms(t, hs, hs.mask & ~ma, tr, mu);
+}
+
+// ---- certified continuous checks with the held object (nbk_edge_held_continuous_batch, nbk_spline_held_continuous_batch): ca_walk on
+// one (trajectory, held item) per lane, item-major.  The init kernels are the scene's; k_held_ca_hold, behind them, gives CA_KEEP_KEY
+// to every non-degenerate trajectory when the world status is set or the call's grasp is not finite (device data both), and the
+// walks leave such trajectories alone.
+__global__ __launch_bounds__(256) void k_held_ca_hold(const int* __restrict__ wstatus, const double* __restrict__ grasp, int64_t n,
+                                                      unsigned long long* __restrict__ key) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    bool bad = wstatus != nullptr && *wstatus != 0;
+    if (grasp != nullptr)
+        for (int c = 0; c < 12; ++c) bad = bad || !(grasp[c] - grasp[c] == 0.0);
+    if (bad && key[e] != CA_DEGENERATE_KEY) key[e] = CA_KEEP_KEY;
+}
+
+// the linear edge of EdgeLane for one held item (ca_walk's pu and p are both the item)
+struct HeldEdgeLane {
+    const double* s;
+    const double* g;
+    double Tf;
+    const HeldDev& hd;
+    const double* grow;       // the call's grasp row
+    double* myq;              // the lane's LDS row
+    NBK_DEV double end() const { return Tf; }
+    NBK_DEV double span_end() const { return Tf; }
+    NBK_DEV double enter(const DevModel& m, int it, double) const {
+        return held_item_motion_bound(m.mt, hd.mask, hd.tab, grow, hd.items + HELD_ITEM_LEN * it, EdgeMotion{s, g});
+    }
+    NBK_DEV double distance(const DevModel& m, bool run, int it, int, double t, double*) const {
+        bool ok = false;
+        if (run) {
+            const double omt = 1.0 - t;
+            for (int c = 0; c < m.n_q; ++c) { const double a = omt * s[c]; const double b = t * g[c]; myq[c] = a + b; }
+            ok = !row_nonfinite(myq, m.n_q, 1);      // (a non-finite q(t) is answered NaN without a walk: the item stops UNDECIDED there)
+        }
+        return held_item_distance(m, hd, grow, myq, ok, it);
+    }
+};
+
+__global__ __launch_bounds__(64) void k_held_edge_ca(DevModel m, HeldDev hd, const double* __restrict__ starts, const double* __restrict__ goals,
+                                                     const double* __restrict__ dist, int64_t E, double max_distance, int mode,
+                                                     const double* __restrict__ grasp, double thr, int max_iter, double slack,
+                                                     unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < E * (int64_t)hd.n_items;
+    const int it = live ? (int)(i / E) : 0;
+    const int64_t e = live ? i - (int64_t)it * E : 0;
+    HeldEdgeLane tr{starts + e * m.n_q, goals + e * m.n_q, 0.0, hd, grasp != nullptr ? grasp : hd.tab + 12, lds + lane * m.n_q};
+    double d_edge = 0.0;
+    const bool run = live && edge_span(m.n_q, tr.s, tr.g, dist, e, max_distance, mode, d_edge, tr.Tf) &&
+                     __hip_atomic_load(key + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != CA_KEEP_KEY;
+    ca_walk(m, tr, run, it, it, lane, thr, max_iter, slack, key + e);
+}
+
+// trajectory s of SplineLane<K> for one held item: the trajectory half is SplineLane's
+template <int K>
+struct HeldSplineLane {
+    const double* c;            // control points of the trajectory, [n][nq]
+    const double* knots;
+    double* row;                // LDS [nq]
+    int n, nq, ell;
+    const HeldDev& hd;
+    const double* grow;
+    NBK_DEV double end() const { return 1.0; }
+    NBK_DEV double span_end() const { return knots[ell + 1]; }
+    NBK_DEV double enter(const DevModel& m, int it, double t) {
+        ell = spline_span<K>(knots, n, t);
+        return held_item_motion_bound(m.mt, hd.mask, hd.tab, grow, hd.items + HELD_ITEM_LEN * it,
+                                      SplineSpanMotion{c + (size_t)(ell - K) * nq, knots + (ell - K + 1), nq, K});
+    }
+    NBK_DEV double distance(const DevModel& m, bool run, int it, int, double t, double*) const {
+        bool ok = false;
+        if (run) {
+            double* r = row;
+            de_boor<K>(nq, c + (size_t)(ell - K) * nq, knots, ell, t, [&](int j, double v) { r[j] = v; });
+            ok = !row_nonfinite(row, nq, 1);
+        }
+        return held_item_distance(m, hd, grow, row, ok, it);
+    }
+};
+
+template <int K>
+__global__ __launch_bounds__(64) void k_held_spline_ca(DevModel m, HeldDev hd, const double* __restrict__ ctrl, int64_t S, int n,
+                                                       const double* __restrict__ knots, const double* __restrict__ grasp, double thr,
+                                                       int max_iter, double slack, unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < S * (int64_t)hd.n_items;
+    const int it = live ? (int)(i / S) : 0;
+    const int64_t s = live ? i - (int64_t)it * S : 0;
+    HeldSplineLane<K> tr{ctrl + (size_t)s * (size_t)n * m.n_q, knots, lds + lane * m.n_q, n, m.n_q, K, hd, grasp != nullptr ? grasp : hd.tab + 12};
+    const unsigned long long k0 = __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool run = live && k0 != CA_DEGENERATE_KEY && k0 != CA_KEEP_KEY;
+    ca_walk(m, tr, run, it, it, lane, thr, max_iter, slack, key + s);
+}
+
 }  // namespace nbk
 
 struct nbk_held {
@@ -258,6 +497,7 @@ struct nbk_held {
     const nbk_model* model;        // the descriptor it was made against: its calls take no other
     int device;
     void* blob;
+    std::vector<int> h_items;      // the host copy of d.items
 };
 
 namespace nbk {
@@ -278,6 +518,58 @@ static bool held_pose_finite(const double* p) {
     return true;
 }
 
+// the argument rules of the held shapes, their poses and the world list (nbk_held_create and the host twins of the motion bound)
+static int32_t held_args_check(int32_t frame, int32_t n_joints, int32_t n_wshapes, const double* A, const double* G, int32_t H,
+                               const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
+                               const int32_t* world_shapes) {
+    if (A == nullptr || G == nullptr || H < 1 || shape_type == nullptr || shape_local == nullptr || shape_param == nullptr ||
+        n_world < 0 || (n_world > 0 && world_shapes == nullptr))
+        return NBK_ERR_INVALID;
+    if (frame < -1 || frame >= n_joints || n_world > n_wshapes) return NBK_ERR_INVALID;
+    if (!held_pose_finite(A) || !held_pose_finite(G)) return NBK_ERR_INVALID;
+    if (H > HELD_MAX_SHAPES) return NBK_ERR_UNSUPPORTED;
+    for (int32_t h = 0; h < H; ++h) {
+        if (shape_type[h] == NBK_HULL) return NBK_ERR_UNSUPPORTED;
+        if (shape_type[h] != NBK_SPHERE && shape_type[h] != NBK_CAPSULE && shape_type[h] != NBK_BOX && shape_type[h] != NBK_CYLINDER) return NBK_ERR_INVALID;
+        if (!held_pose_finite(shape_local + 12 * (size_t)h)) return NBK_ERR_INVALID;
+        for (int e = 0; e < 4; ++e) if (!(shape_param[4 * h + e] - shape_param[4 * h + e] == 0.0)) return NBK_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_world; ++i) {
+        if (world_shapes[i] < 0 || world_shapes[i] >= n_wshapes) return NBK_ERR_INVALID;
+        if (i > 0 && world_shapes[i] <= world_shapes[i - 1]) return NBK_ERR_INVALID;
+    }
+    return NBK_OK;
+}
+
+// A | G | the shape records (HeldDev.tab) and the core kinds
+static void held_tab(const double* A, const double* G, int32_t H, const int32_t* shape_type, const double* shape_local,
+                     const double* shape_param, std::vector<double>& tab, std::vector<int>& kind) {
+    tab.assign(24 + HELD_SHAPE_LEN * (size_t)H, 0.0);
+    kind.assign(H, 0);
+    memcpy(&tab[0], A, 12 * sizeof(double));
+    memcpy(&tab[12], G, 12 * sizeof(double));
+    for (int32_t h = 0; h < H; ++h) {
+        double* rec = &tab[24 + HELD_SHAPE_LEN * (size_t)h];
+        memcpy(rec, shape_local + 12 * (size_t)h, 12 * sizeof(double));
+        core_params(shape_type[h], shape_param + 4 * (size_t)h, kind[h], rec + 12);
+        rec[17] = host_bound_radius(kind[h], rec + 12);
+    }
+}
+
+// the items (HeldDev.items): robot_bits in the caller's order over S shapes (null: none); dev_of_user (nullable): the device index
+// of each of the caller's shapes, else the caller's index stands in
+static std::vector<int> held_item_list(int S, const int* dev_of_user, const uint64_t* robot_bits, int H, int n_world, const int32_t* world) {
+    std::vector<int> it;
+    if (robot_bits != nullptr)
+        for (int s = 0; s < S; ++s) {
+            if (((robot_bits[s >> 6] >> (s & 63)) & 1ull) == 0ull) continue;
+            for (int h = 0; h < H; ++h) { it.push_back(h); it.push_back(0); it.push_back(dev_of_user != nullptr ? dev_of_user[s] : s); it.push_back(s); }
+        }
+    for (int h = 0; h < H; ++h)
+        for (int i = 0; i < n_world; ++i) { it.push_back(h); it.push_back(1); it.push_back(world[i]); it.push_back(world[i]); }
+    return it;
+}
+
 }  // namespace nbk
 
 extern "C" {
@@ -295,44 +587,31 @@ int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, cons
                         const uint64_t* robot_bits, nbk_held** out) {
     if (out == nullptr) return NBK_ERR_INVALID;
     *out = nullptr;
-    if (m == nullptr || A == nullptr || G == nullptr || H < 1 || shape_type == nullptr || shape_local == nullptr || shape_param == nullptr ||
-        n_world < 0 || (n_world > 0 && world_shapes == nullptr))
-        return NBK_ERR_INVALID;
-    if (frame < -1 || frame >= m->n_joints || n_world > m->d.n_wshapes) return NBK_ERR_INVALID;
-    if (!held_pose_finite(A) || !held_pose_finite(G)) return NBK_ERR_INVALID;
-    if (H > HELD_MAX_SHAPES) return NBK_ERR_UNSUPPORTED;
-    for (int32_t h = 0; h < H; ++h) {
-        if (shape_type[h] == NBK_HULL) return NBK_ERR_UNSUPPORTED;
-        if (shape_type[h] != NBK_SPHERE && shape_type[h] != NBK_CAPSULE && shape_type[h] != NBK_BOX && shape_type[h] != NBK_CYLINDER) return NBK_ERR_INVALID;
-        if (!held_pose_finite(shape_local + 12 * (size_t)h)) return NBK_ERR_INVALID;
-        for (int e = 0; e < 4; ++e) if (!(shape_param[4 * h + e] - shape_param[4 * h + e] == 0.0)) return NBK_ERR_INVALID;
-    }
-    for (int32_t i = 0; i < n_world; ++i) {
-        if (world_shapes[i] < 0 || world_shapes[i] >= m->d.n_wshapes) return NBK_ERR_INVALID;
-        if (i > 0 && world_shapes[i] <= world_shapes[i - 1]) return NBK_ERR_INVALID;
-    }
+    if (m == nullptr) return NBK_ERR_INVALID;
+    { const int32_t rc = held_args_check(frame, m->n_joints, m->d.n_wshapes, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes);
+      if (rc != NBK_OK) return rc; }
     if (robot_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
     NBK_DEVICE(m);
     // the tables, then one allocation and one copy
-    std::vector<double> tab(24 + HELD_SHAPE_LEN * (size_t)H, 0.0);
-    std::vector<int> kind(H, 0), world(n_world > 0 ? n_world : 1, 0);
-    memcpy(&tab[0], A, 12 * sizeof(double));
-    memcpy(&tab[12], G, 12 * sizeof(double));
-    for (int32_t h = 0; h < H; ++h) {
-        double* rec = &tab[24 + HELD_SHAPE_LEN * (size_t)h];
-        memcpy(rec, shape_local + 12 * (size_t)h, 12 * sizeof(double));
-        core_params(shape_type[h], shape_param + 4 * (size_t)h, kind[h], rec + 12);
-        rec[17] = host_bound_radius(kind[h], rec + 12);
-    }
+    std::vector<double> tab;
+    std::vector<int> kind, world(n_world > 0 ? n_world : 1, 0);
+    held_tab(A, G, H, shape_type, shape_local, shape_param, tab, kind);
     for (int32_t i = 0; i < n_world; ++i) world[i] = world_shapes[i];
+    const int S = m->d.n_rshapes;
+    std::vector<int> dev_of_user(S > 0 ? S : 1, 0);
+    for (int i = 0; i < S; ++i) dev_of_user[m->h_rs_user[i]] = i;
+    std::vector<int> items = held_item_list(S, dev_of_user.data(), robot_bits, H, n_world, world_shapes);
+    const int n_items = (int)(items.size() / HELD_ITEM_LEN);
     auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
     const size_t o_kind = up(sizeof(double) * tab.size());
     const size_t o_world = up(o_kind + sizeof(int) * kind.size());
-    const size_t bytes = up(o_world + sizeof(int) * world.size());
+    const size_t o_items = up(o_world + sizeof(int) * world.size());
+    const size_t bytes = up(o_items + sizeof(int) * (items.size() > 0 ? items.size() : 1));
     std::vector<char> host(bytes, 0);
     memcpy(host.data(), tab.data(), sizeof(double) * tab.size());
     memcpy(host.data() + o_kind, kind.data(), sizeof(int) * kind.size());
     memcpy(host.data() + o_world, world.data(), sizeof(int) * world.size());
+    if (!items.empty()) memcpy(host.data() + o_items, items.data(), sizeof(int) * items.size());
     std::unique_ptr<nbk_held> hd(new nbk_held());
     hipError_t e = hipMalloc(&hd->blob, bytes);
     if (e != hipSuccess) { hip_fail(e, "hipMalloc(held)"); return NBK_ERR_ALLOC; }
@@ -346,6 +625,9 @@ int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, cons
     hd->d.kind = reinterpret_cast<const int*>(base + o_kind);
     hd->d.world = reinterpret_cast<const int*>(base + o_world);
     hd->d.robot = robot_bits == nullptr ? CloudSel{{0ull, 0ull, 0ull, 0ull}, 0} : cloud_selection(m, robot_bits);
+    hd->d.n_items = n_items;
+    hd->d.items = reinterpret_cast<const int*>(base + o_items);
+    hd->h_items = std::move(items);
     hd->model = m;
     (void)hipGetDevice(&hd->device);
     *out = hd.release();
@@ -412,6 +694,211 @@ int32_t nbk_edge_held_validity_batch(const nbk_model* m, const nbk_held* held, c
                        QSlabLds(m->n_q).bytes(), st, m->d, held->d, m->movable ? (const int*)m->world_status : (const int*)nullptr, es,
                        offs, E, grasp, grasp != nullptr ? 1 : 0, threshold, valid);
     NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_held_item_count(const nbk_held* held) { return held == nullptr ? NBK_ERR_INVALID : held->d.n_items; }
+
+int32_t nbk_held_items(const nbk_held* held, int32_t* out) {
+    if (held == nullptr || (held->d.n_items > 0 && out == nullptr)) return NBK_ERR_INVALID;
+    for (int i = 0; i < held->d.n_items; ++i) {
+        const int* rec = &held->h_items[HELD_ITEM_LEN * (size_t)i];
+        out[3 * i] = rec[0]; out[3 * i + 1] = rec[1]; out[3 * i + 2] = rec[3];
+    }
+    return NBK_OK;
+}
+
+int32_t nbk_held_distances_batch(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const double* grasp,
+                                 int64_t grasp_rows, double* out_d, void* stream) {
+    if (m == nullptr || held == nullptr || B < 0) return NBK_ERR_INVALID;
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    const int64_t K = held->d.n_items;
+    if (B > 0 && (q == nullptr || (K > 0 && out_d == nullptr))) return NBK_ERR_INVALID;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    if (B == 0 || K == 0) return NBK_OK;
+    if (B > 0x7fffffffLL || (B * K + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
+    hipLaunchKernelGGL(k_held_distances, dim3((unsigned)((B * K + WAVE - 1) / WAVE)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream,
+                       m->d, held->d, m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, grasp, rows, out_d);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// the hold of the certified held entries, behind the scene's init kernel (k_held_ca_hold): only where something can be held
+static int32_t launch_held_ca_hold(const nbk_model* m, hipStream_t st, const double* grasp, int64_t n, double* t_free) {
+    if (!m->movable && grasp == nullptr) return NBK_OK;
+    hipLaunchKernelGGL(k_held_ca_hold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       m->movable ? (const int*)m->world_status : (const int*)nullptr, grasp, n, ca_keys(t_free));
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_edge_held_continuous_batch(const nbk_model* m, const nbk_held* held, const double* starts, const double* goals, const double* dist,
+                                       int64_t E, double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
+                                       const double* grasp, int32_t accumulate, uint8_t* valid, double* end, double* t_free, int32_t* status,
+                                       void* stream) {
+    // (the argument rules are answered without a device)
+    if (m == nullptr || held == nullptr || E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
+    if (E == 0) return NBK_OK;
+    const int64_t N = E * (int64_t)held->d.n_items;
+    if (E > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, nullptr, accumulate ? status : nullptr, end, t_free);
+      if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_held_ca_hold(m, st, grasp, E, t_free); if (rc != NBK_OK) return rc; }
+    if (N > 0) {
+        hipLaunchKernelGGL(k_held_edge_ca, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, held->d,
+                           starts, goals, dist, E, max_distance, (int)mode, grasp, threshold, (int)max_iter, slack, ca_keys(t_free));
+        NBK_HIP(hipGetLastError());
+    }
+    return launch_ca_final(st, E, valid, t_free, status);
+}
+
+int32_t nbk_spline_held_continuous_batch(const nbk_model* m, const nbk_held* held, const double* ctrl, int64_t S, int32_t n_ctrl,
+                                         int32_t degree, const double* knots, double threshold, int32_t max_iter, double slack,
+                                         const double* grasp, int32_t accumulate, uint8_t* valid, double* t_free, int32_t* status,
+                                         void* stream) {
+    if (m == nullptr || held == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
+    if (S == 0) return NBK_OK;
+    const int64_t N = S * (int64_t)held->d.n_items;
+    if (S > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, nullptr, accumulate ? status : nullptr, t_free);
+      if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_held_ca_hold(m, st, grasp, S, t_free); if (rc != NBK_OK) return rc; }
+    if (N > 0) {
+        const dim3 grid((unsigned)((N + WAVE - 1) / WAVE)), block(WAVE);
+        const size_t lds = QSlabLds(m->n_q).bytes();
+        with_degree(degree, [&](auto K) {
+            hipLaunchKernelGGL(k_held_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, held->d, ctrl, S, (int)n_ctrl, knots, grasp,
+                               threshold, (int)max_iter, slack, ca_keys(t_free));
+        });
+        NBK_HIP(hipGetLastError());
+    }
+    return launch_ca_final(st, S, valid, t_free, status);
+}
+
+int64_t nbk_spline_held_workspace_bytes(int64_t S) {
+    if (S < 0 || S >= SPLINE_MAX_S) return -1;
+    return (int64_t)SplineCloudLayout(S).bytes;
+}
+
+int32_t nbk_spline_held_validity_batch(const nbk_model* m, const nbk_held* held, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                       const double* knots, double resolution, double threshold, const double* grasp,
+                                       int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+    // (as nbk_spline_cloud_validity_batch: the argument rules are answered without a device)
+    if (m == nullptr || held == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
+    if (S > 0 && S < SPLINE_MAX_S &&
+        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
+    if (S == 0) return NBK_OK;
+    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    int cus = 0;
+    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, held->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
+    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
+    NBK_HIP(hipGetLastError());
+    const double* t_prev = accumulate ? t_hit : nullptr;
+    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt,
+                       m->movable ? (const int*)m->world_status : (const int*)nullptr, (int)accumulate, (const uint8_t*)valid, t_prev, v.first);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
+    NBK_HIP(hipGetLastError());
+    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
+    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
+    const size_t lds = QSlabLds(m->n_q).bytes();
+    with_degree(degree, [&](auto K) {
+        hipLaunchKernelGGL(k_held_spline<decltype(K)::value>, grid, block, lds, st, m->d, held->d, ctrl, (int)n_ctrl, knots,
+                           (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp, grasp != nullptr ? 1 : 0, threshold, t_prev,
+                           v.first);
+    });
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
+                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// ---- the host twins of the held motion bound: held_item_motion_bound on the tables motion_tables makes of the descriptor, the
+// items in held_item_list's order (robot_bits in the descriptor's numbering); no GPU
+static int32_t held_motion_host_begin(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                      const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
+                                      const int32_t* world_shapes, const uint64_t* robot_bits, MotionHost& mh, unsigned& mask,
+                                      std::vector<double>& tab, std::vector<int>& items) {
+    if (d == nullptr) return NBK_ERR_INVALID;
+    { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
+    { const int32_t rc = held_args_check(frame, d->n_joints, d->n_wshapes, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes);
+      if (rc != NBK_OK) return rc; }
+    const std::vector<unsigned> fm = frame_masks(d);
+    motion_tables(d, fm, mh);
+    mask = frame >= 0 ? fm[frame] : 0u;
+    std::vector<int> kind;
+    held_tab(A, G, H, shape_type, shape_local, shape_param, tab, kind);
+    items = held_item_list(d->n_rshapes, nullptr, robot_bits, H, n_world, world_shapes);
+    return NBK_OK;
+}
+
+int32_t nbk_edge_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                         const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
+                                         const int32_t* world_shapes, const uint64_t* robot_bits, const double* starts, const double* goals,
+                                         int64_t E, double* mu) {
+    if (E < 0) return NBK_ERR_INVALID;
+    MotionHost mh;
+    unsigned mask = 0u;
+    std::vector<double> tab;
+    std::vector<int> items;
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, mh, mask, tab, items);
+      if (rc != NBK_OK) return rc; }
+    const int64_t K = (int64_t)(items.size() / HELD_ITEM_LEN);
+    if (E == 0 || K == 0) return NBK_OK;
+    if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
+    const MotionTab t = mh.view(d->n_joints, d->n_rshapes);
+    for (int64_t e = 0; e < E; ++e)
+        for (int64_t i = 0; i < K; ++i)
+            mu[e * K + i] = held_item_motion_bound(t, mask, tab.data(), tab.data() + 12, &items[HELD_ITEM_LEN * (size_t)i],
+                                                   EdgeMotion{starts + e * d->n_q, goals + e * d->n_q});
+    return NBK_OK;
+}
+
+int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                           const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                           int32_t n_world, const int32_t* world_shapes, const uint64_t* robot_bits, const double* ctrl,
+                                           int64_t S, int32_t n_ctrl, int32_t degree, const double* knots, double* mu) {
+    if (S < 0 || !spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;
+    MotionHost mh;
+    unsigned mask = 0u;
+    std::vector<double> tab;
+    std::vector<int> items;
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, mh, mask, tab, items);
+      if (rc != NBK_OK) return rc; }
+    const int64_t K = (int64_t)(items.size() / HELD_ITEM_LEN);
+    const int nq = d->n_q, k = degree, L = n_ctrl - degree;
+    if (S == 0 || K == 0) return NBK_OK;
+    if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_args_ok(n_ctrl, degree, knots)) return NBK_ERR_INVALID;
+    const MotionTab t = mh.view(d->n_joints, d->n_rshapes);
+    for (int64_t s = 0; s < S; ++s) {
+        const double* c = ctrl + (size_t)s * (size_t)n_ctrl * nq;
+        for (int ell = k; ell < n_ctrl; ++ell) {
+            double* out = mu + ((size_t)s * L + (size_t)(ell - k)) * K;
+            const bool span = knots[ell] < knots[ell + 1];
+            const SplineSpanMotion tr{c + (size_t)(ell - k) * nq, knots + (ell - k + 1), nq, k};
+            for (int64_t i = 0; i < K; ++i)
+                out[i] = span ? held_item_motion_bound(t, mask, tab.data(), tab.data() + 12, &items[HELD_ITEM_LEN * (size_t)i], tr) : 0.0;
+        }
+    }
     return NBK_OK;
 }
 

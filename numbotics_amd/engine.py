@@ -875,6 +875,87 @@ class DeviceModel:
             self._stream()), "nbk_edge_held_validity_batch")
         return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
 
+    def held_distances(self, held, q, pose=None):
+        """Signed distances of the items of ``held`` at q (nbk_held_distances_batch) -> (B, K): column k is item k of
+        ``held.items()`` -- (held shape, robot shape) for the allowed robot shapes ascending, then (held shape, world shape) -- bit
+        for bit ``pair_distances`` of a descriptor that holds the held shapes as robot shapes.  ``pose``: as ``held_validity``'s, one
+        grasp or one per row.  NaN where the row or its grasp is not finite."""
+        torch = _require_gpu()
+        h = self._held(held)
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        d = torch.empty((qs.B, held.n_items), dtype=torch.float64, device=qs.device)
+        _lib.check(self._lib.nbk_held_distances_batch(
+            self._h, h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, d.data_ptr(), self._stream()),
+            "nbk_held_distances_batch")
+        return qs.out(d)
+
+    def held_edge_continuous(self, held, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None,
+                             pose=None, out=None):
+        """``edge_continuous``'s edges certified for the held object ``held`` ALONE (nbk_edge_held_continuous_batch): one (edge,
+        held item) per lane advances by conservative advancement on the item's distance -> valid (E,) bool, end (E, n_q), t_free
+        (E,), status (E,) int32 (``_lib.CA_*``).  ``pose``: ONE grasp (4, 4) for the call, as ``held_edge_validity``'s; a non-finite
+        one gives 0 / NaN / UNDECIDED.  ``out``: the CUDA tensors (valid, t_free, status) that ``edge_continuous`` -- or
+        ``cloud_edge_continuous(..., out=...)`` after it -- returned for the same edges, mode, max_distance and dist: the held items
+        are reduced INTO them, as ``cloud_edge_continuous`` has it."""
+        torch = _require_gpu()
+        h = self._held(held)
+        s, g, dd = self._stage_edges(starts, goals, dist)
+        gr, _ = self._grasp(torch, pose, s.B, False)
+        valid, t_free, status = self._result_triple(torch, out, s.B, s.device, "(valid, t_free, status)")
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.nbk_edge_held_continuous_batch(
+            self._h, h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
+            _mode_int(mode), float(threshold), int(max_iter), float(slack), None if gr is None else gr.data_ptr(),
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(), status.data_ptr(), self._stream()),
+            "nbk_edge_held_continuous_batch")
+        if out is not None:
+            return valid, s.out(end), t_free, status
+        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
+
+    @staticmethod
+    def held_spline_workspace_bytes(S: int) -> int:
+        return int(_lib.load().nbk_spline_held_workspace_bytes(int(S)))
+
+    def held_spline_validity(self, held, ctrl, knots, degree, resolution, threshold=0.0, pose=None, out=None, workspace=None):
+        """``spline_validity``'s trajectories for the held object ``held`` ALONE (nbk_spline_held_validity_batch): a trajectory is
+        valid when it is not degenerate and ``held_validity`` clears every one of its samples -> (valid (S,) bool, t_hit (S,),
+        n_samples (S,) int32).  Asynchronous on device tensors and capturable.  ``pose``: ONE grasp (4, 4) for the call; a
+        non-finite one hits every trajectory at its first sample.  ``out``: the CUDA tensors (valid, t_hit, n_samples) that
+        ``spline_validity`` -- or ``cloud_spline_validity(..., out=...)`` after it -- returned for the same trajectories and
+        resolution: the held object's verdict is reduced INTO them, as ``cloud_spline_validity`` has it.  ``workspace``: optional
+        torch uint8 CUDA tensor of at least ``held_spline_workspace_bytes(S)`` bytes."""
+        torch = _require_gpu()
+        h = self._held(held)
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        gr, _ = self._grasp(torch, pose, S, False)
+        valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
+        ws = torch.empty((self.held_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device) if workspace is None else workspace
+        _lib.check(self._lib.nbk_spline_held_validity_batch(
+            self._h, h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
+            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
+            ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_held_validity_batch")
+        if out is not None:
+            return valid, t_hit, ns
+        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+
+    def held_spline_continuous(self, held, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6, pose=None, out=None):
+        """``spline_continuous``'s trajectories certified for the held object ``held`` ALONE (nbk_spline_held_continuous_batch) ->
+        valid (S,) bool, t_free (S,), status (S,) int32.  ``pose`` / ``out``: as ``held_edge_continuous``, ``out`` being what
+        ``spline_continuous`` (or ``cloud_spline_continuous(..., out=...)`` after it) returned for the same trajectories."""
+        torch = _require_gpu()
+        h = self._held(held)
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        gr, _ = self._grasp(torch, pose, S, False)
+        valid, t_free, status = self._result_triple(torch, out, S, c.device, "(valid, t_free, status)")
+        _lib.check(self._lib.nbk_spline_held_continuous_batch(
+            self._h, h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
+            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_free.data_ptr(), status.data_ptr(),
+            self._stream()), "nbk_spline_held_continuous_batch")
+        if out is not None:
+            return valid, t_free, status
+        return c.out(valid.bool()), c.out(t_free), c.out(status)
+
     def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
         """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
         valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``)."""
@@ -1038,6 +1119,72 @@ def held_locals(A, G, L):
     return out.reshape(-1, 3, 4)
 
 
+def _held_host_args(model, spec, G):
+    """The held arguments of the host twins of the held motion bound (nbk_held_create's, from a ``HeldSpec``) -> (ctypes arguments,
+    arrays they point into, K)."""
+    S = int(model.n_rshapes)
+    A = np.ascontiguousarray(np.asarray(spec.A, dtype=np.float64)[:3, :4]).reshape(12)
+    G = np.ascontiguousarray(np.asarray(spec.G if G is None else G, dtype=np.float64)[:3, :4]).reshape(12)
+    st = np.ascontiguousarray(spec.shape_type, dtype=np.int32).reshape(-1)
+    H = int(st.shape[0])
+    L = np.asarray(spec.shape_local, dtype=np.float64)
+    L = np.ascontiguousarray(L.reshape(H, L.shape[-2], 4)[:, :3, :]).reshape(H, 12)
+    sp = np.ascontiguousarray(spec.shape_param, dtype=np.float64).reshape(H, 4)
+    ws = np.ascontiguousarray(sorted(int(w) for w in spec.world_shapes), dtype=np.int32)
+    robot = sorted({int(x) for x in spec.robot_shapes})
+    bits = None
+    if robot:
+        bits = np.zeros((max((S + 63) // 64, 1),), dtype=np.uint64)
+        for s in robot:
+            if not 0 <= s < S:
+                raise ValueError(f"robot shape {s} out of range (0..{S - 1})")
+            bits[s >> 6] |= np.uint64(1) << np.uint64(s & 63)
+    args = (int(spec.frame), A.ctypes.data, G.ctypes.data, H, st.ctypes.data, L.ctypes.data, sp.ctypes.data, int(ws.shape[0]),
+            ws.ctypes.data if ws.shape[0] else None, _host_ptr(bits))
+    return args, (A, G, st, L, sp, ws, bits), H * (len(robot) + int(ws.shape[0]))
+
+
+def held_edge_motion_bounds(model, spec, starts, goals, G=None):
+    """Motion bounds mu (E, K) of the linear edges starts -> goals for the K items of the held object ``spec`` (a ``HeldSpec``)
+    on the SceneModel ``model``, in the items' order: the bits ``edge_motion_bounds`` gives for those pairs on a model that holds
+    the held shapes as robot shapes.  The routine nbk_edge_held_continuous_batch advances with, run on the host
+    (nbk_edge_held_motion_bounds_host); no GPU needed.  ``G``: the grasp (default: the spec's)."""
+    n_q = model.kin.n_q
+    s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64)).reshape(-1, n_q)
+    g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64)).reshape(-1, n_q)
+    if s.shape != g.shape:
+        raise ValueError("starts and goals must have the same shape")
+    d, keep = model_desc(model)
+    args, keep2, K = _held_host_args(model, spec, G)
+    mu = np.empty((s.shape[0], K), dtype=np.float64)
+    _lib.check(_lib.load().nbk_edge_held_motion_bounds_host(C.byref(d), *args, s.ctypes.data, g.ctypes.data, s.shape[0], mu.ctypes.data),
+               "nbk_edge_held_motion_bounds_host")
+    del keep, keep2
+    return mu
+
+
+def held_spline_motion_bounds(model, spec, ctrl, knots, degree, G=None):
+    """Motion bounds mu (S, n - degree, K) of S clamped B-splines for the K items of the held object ``spec``, per knot span: the bits
+    ``spline_motion_bounds`` gives for those pairs on a model that holds the held shapes as robot shapes
+    (nbk_spline_held_motion_bounds_host; no GPU needed).  Entries of empty spans are 0."""
+    n_q = model.kin.n_q
+    c = np.ascontiguousarray(np.asarray(ctrl, dtype=np.float64))
+    if c.ndim != 3 or c.shape[2] != n_q:
+        raise ValueError(f"control points must have shape (S, n, {n_q}), got {c.shape}")
+    S, n = c.shape[:2]
+    k = int(degree)
+    if not 1 <= k < n:
+        raise ValueError("degree must be at least 1 and less than the number of control points")
+    kn = _host_f64(knots, n + k + 1)
+    d, keep = model_desc(model)
+    args, keep2, K = _held_host_args(model, spec, G)
+    mu = np.zeros((S, n - k, K), dtype=np.float64)
+    _lib.check(_lib.load().nbk_spline_held_motion_bounds_host(C.byref(d), *args, c.ctypes.data, S, n, k, kn.ctypes.data, mu.ctypes.data),
+               "nbk_spline_held_motion_bounds_host")
+    del keep, keep2
+    return mu
+
+
 class DeviceHeld:
     """A held object on the device (nbk_held): H shapes riding on moving frame ``frame`` of ``dev``'s descriptor, with the world
     shapes and robot shapes (``SceneModel`` order) its verdict looks at.  ``A``: the link's constant pose in the frame, ``G``: the
@@ -1063,6 +1210,14 @@ class DeviceHeld:
                                             sp.ctypes.data, int(ws.shape[0]), ws.ctypes.data if ws.shape[0] else None, _host_ptr(bits),
                                             C.byref(h)), "nbk_held_create")
         self._h, self._lib, self.dev, self.n_shapes = h, dev._lib, dev, H
+        self.n_items = int(dev._lib.nbk_held_item_count(h))
+
+    def items(self):
+        """(K, 3) int32: (held shape, kind -- 0 robot shape, 1 world shape --, index in ``SceneModel`` order) of the items, the
+        columns of ``DeviceModel.held_distances`` (nbk_held_items)."""
+        out = np.zeros((self.n_items, 3), dtype=np.int32)
+        _lib.check(self._lib.nbk_held_items(self._h, out.ctypes.data if self.n_items else None), "nbk_held_items")
+        return out
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -112,6 +112,20 @@ class Attachment:
         self._spec = (key, spec)
         return spec
 
+    def items(self, arm):
+        """[(held shape, name)] of the attachment's items against ``arm.scene_model()``, in the order of the columns of
+        ``DeviceModel.held_distances`` and of ``Arm.attached_clearance``'s item index: each held shape with the link (its name) of
+        every allowed robot shape, robot shapes ascending, then with the object (its name, or its index among the scene's objects)
+        of every allowed world shape, held shapes ascending.  Needs no GPU."""
+        spec = self.spec(arm)
+        sm = arm.scene_model()
+        out = [(h, sm.links[sm.rshape_link[s]]._name) for s in spec.robot_shapes for h in range(spec.n_shapes)]
+        for h in range(spec.n_shapes):
+            for w in spec.world_shapes:
+                o = int(sm.wshape_obj[w])
+                out.append((h, getattr(sm.objects[o], "_name", None) or o))
+        return out
+
     def _device(self, arm):
         """(DeviceModel, DeviceHeld) for the arm's current device scene."""
         from numbotics_amd.engine import DeviceHeld

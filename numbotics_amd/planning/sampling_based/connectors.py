@@ -12,7 +12,11 @@ keyword, ``validate_trajectories(..., cloud=scan)`` on both connectors (``nbk_sp
 connector carry one still refuses ("do not see point clouds yet") instead of ignoring it.
 ``ConnectorParams(attached=...)`` (an ``Attachment``, with an ``arm``) puts an object in the hand: the sampled edges and ``is_valid``
 AND the held object's verdict (``nbk_edge_held_validity_batch`` / ``nbk_held_validity_batch``) into the scene's, after the cloud's
-where both are set; trajectory checks and ``ContinuousConnector`` refuse such params ("do not see held objects yet").  ``ContinuousConnector`` takes its cloud as a constructor argument
+where both are set.  Smoothed trajectories see the held object through a per-call keyword, ``validate_trajectories(..., attached=att)``
+(``nbk_spline_held_validity_batch``, after the scene's and the cloud's); a call that names none while the params carry one still refuses
+("do not see held objects yet"), and ``ContinuousConnector`` refuses such params.  It takes the attachment as a constructor argument,
+``ContinuousConnector(params, attached=att)``: its edges, ``is_valid`` and trajectory methods then certify the held object as well
+(``nbk_edge_held_continuous_batch`` / ``nbk_spline_held_continuous_batch``).  ``ContinuousConnector`` takes its cloud as a constructor argument
 (``ContinuousConnector(params, cloud=...)``: certified straight edges, ``nbk_edge_cloud_continuous_batch``) and still refuses params
 that carry one.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
@@ -90,6 +94,23 @@ def _no_cloud(params, what):
 def _no_held(params, what):
     if params.attached is not None:
         raise ValueError(f"{what} do not see held objects yet")
+
+
+def _attachment(attached):
+    from numbotics_amd.physics import Attachment
+    if not isinstance(attached, Attachment):
+        raise ValueError("attached must be an Attachment (Arm.attach / World.add_constraint)")
+    return attached
+
+
+def _then(*steps):
+    """The accumulating steps of ``_scene_then_cloud`` in order (the cloud's, then the held object's), those that are None left out."""
+    steps = [f for f in steps if f is not None]
+
+    def run(*args):
+        for f in steps:
+            f(*args)
+    return run
 
 
 class Connector(ABC):
@@ -203,40 +224,57 @@ class DiscreteConnector(Connector):
         return ok, end
 
     # ---- smoothed trajectories (additive) ----------------------------------------------------------------
-    def _spline_check(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None):
+    def _spline_check(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None, attached=None):
         p = self._params
         sm, dev = p.arm._scene_device()
         scene = lambda c: dev.spline_validity(c, knots, degree, p.resolution, threshold=p.collision_threshold)      # noqa: E731
-        if cloud is None:
+        if cloud is None and attached is None:
             return scene(ctrl)
-        # only samples before the scene's first hit are looked at
+        # only samples before the first hit so far are looked at: the scene's, then the cloud's, then the held object's
         links = p.cloud_ignore_links if cloud_ignore_links is None else tuple(cloud_ignore_links)
-        return _scene_then_cloud(
-            (ctrl,), scene, lambda c, res: dev.cloud_spline_validity(cloud, c, knots, degree, p.resolution, threshold=p.collision_threshold,
-                                                                     shapes=p.arm._cloud_shapes(sm, links), out=res))
+        held = None if attached is None else attached._device(p.arm)[1]
+        scan = None if cloud is None else (
+            lambda c, res: dev.cloud_spline_validity(cloud, c, knots, degree, p.resolution, threshold=p.collision_threshold,
+                                                     shapes=p.arm._cloud_shapes(sm, links), out=res))
+        hold = None if held is None else (
+            lambda c, res: dev.held_spline_validity(held, c, knots, degree, p.resolution, threshold=p.collision_threshold, out=res))
+        return _scene_then_cloud((ctrl,), scene, _then(scan, hold))
 
-    def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None):
+    def _named_attachment(self, attached):
+        """The attachment a trajectory call names: none while the params carry one is refused, as is another than the params' own."""
+        if attached is None:
+            _no_held(self._params, "sampled trajectory checks")
+            return None
+        _attachment(attached)
+        if self._params.attached is not None and attached is not self._params.attached:
+            raise ValueError("attached must be the attachment of the ConnectorParams")
+        return attached
+
+    def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None, attached=None):
         """S clamped B-splines of ``unit_bspline``'s knots, every one sampled at most ``resolution`` apart in joint space and checked
         on the device (``nbk_spline_validity_batch``): (S, n, dof) -> valid (S,) bool, t_hit (S,) (t of the first colliding
         sample, NaN when valid), n_samples (S,) int32.  NumPy in, NumPy out; device tensors stay on the device.
         ``cloud`` (a ``PointCloud``): the samples are checked against the scan as well (``nbk_spline_cloud_validity_batch``
         accumulating into the scene's result: t_hit is the first sample either of them rejects), without the shapes of
-        ``cloud_ignore_links`` (default: the params' own tuple).  A call that names no cloud is refused when the params carry one."""
-        _no_held(self._params, "sampled trajectory checks")
+        ``cloud_ignore_links`` (default: the params' own tuple).  A call that names no cloud is refused when the params carry one.
+        ``attached`` (an ``Attachment``): the object in the hand is checked at the samples as well, after the scan
+        (``nbk_spline_held_validity_batch`` accumulating into the same result).  A call that names no attachment is refused when
+        the params carry one, and so is one that names another than the params' own."""
+        attached = self._named_attachment(attached)
         if cloud is None:
             _no_cloud(self._params, "sampled trajectory checks")
         shape = _shape(control_points)
         k = _spline_args(self._params, shape, degree)
-        return self._spline_check(control_points, unit_knots(shape[1], k), k, cloud, cloud_ignore_links)
+        return self._spline_check(control_points, unit_knots(shape[1], k), k, cloud, cloud_ignore_links, attached)
 
-    def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None):
+    def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None, attached=None):
         """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_hit).  ``cloud``,
-        ``cloud_ignore_links``: as ``validate_trajectories``."""
-        _no_held(self._params, "sampled trajectory checks")
+        ``cloud_ignore_links``, ``attached``: as ``validate_trajectories``."""
+        attached = self._named_attachment(attached)
         if cloud is None:
             _no_cloud(self._params, "sampled trajectory checks")
         c, t, k = _spline_parts(self._params, spline)
-        valid, t_hit, _ = self._spline_check(c[None], t, k, cloud, cloud_ignore_links)
+        valid, t_hit, _ = self._spline_check(c[None], t, k, cloud, cloud_ignore_links, attached)
         return bool(valid[0]), float(t_hit[0])
 
 
@@ -297,27 +335,39 @@ class ContinuousConnector(Connector):
     THIS constructor because ``ConnectorParams(cloud=...)`` keeps being refused here -- a certificate that ignores an obstacle would
     be worse than none, and callers rely on that refusal; lifting it is a later change.  The trajectory methods take their scan per
     call, ``validate_trajectories(..., cloud=scan)`` (``nbk_spline_cloud_continuous_batch``, with this connector's ``look_ahead``
-    and, by default, its ``cloud_ignore_links``); a call that names no cloud still raises when the connector carries one."""
+    and, by default, its ``cloud_ignore_links``); a call that names no cloud still raises when the connector carries one.
+
+    ``attached`` (an ``Attachment``: the object in the hand): ``certify_batch`` -- and with it ``connect`` / ``steer`` / ``*_batch``
+    -- reduces one (edge, held item) per lane into the same result after the cloud's (``nbk_edge_held_continuous_batch``), ``is_valid``
+    asks ``in_collision_with_attached`` as well, and the trajectory methods certify the held object by default
+    (``nbk_spline_held_continuous_batch``; ``attached=`` names another per call).  It is an argument of this constructor for the
+    cloud's reason, with the cloud's requirements; ``ConnectorParams(attached=...)`` keeps being refused here."""
 
     def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6, cloud=None, cloud_ignore_links=(),
-                 look_ahead: float = CLOUD_LOOK_AHEAD):
+                 look_ahead: float = CLOUD_LOOK_AHEAD, attached=None):
         if int(max_iter) < 1:
             raise ValueError("max_iter must be at least 1")
         if not slack >= 0.0:
             raise ValueError("slack must be non-negative")
         _no_cloud(params, "certified continuous checks")
         _no_held(params, "certified continuous checks")
+        device_edge = params.arm is not None and params.validity_checker is None and params.trajectory_func is _DEFAULT_TRAJ
         if cloud is not None:
-            if params.arm is None or params.validity_checker is not None or params.trajectory_func is not _DEFAULT_TRAJ:
+            if not device_edge:
                 raise ValueError("a point cloud needs ConnectorParams(arm=...) with the default linear trajectory and no validity_checker")
             if not look_ahead > 0.0:
                 raise ValueError("look_ahead must be positive")
+        if attached is not None:
+            if not device_edge:
+                raise ValueError("a held object needs ConnectorParams(arm=...) with the default linear trajectory and no validity_checker")
+            _attachment(attached)
         self._params = params
         self.max_iter = int(max_iter)
         self.slack = float(slack)
         self.cloud = cloud
         self.cloud_ignore_links = tuple(cloud_ignore_links)
         self.look_ahead = float(look_ahead)
+        self.attached = attached
 
     def _device_edge(self):
         p = self._params
@@ -371,10 +421,11 @@ class ContinuousConnector(Connector):
         p = self._params
         if p.validity_checker is not None:
             return p.validity_checker(state) > 0.0
-        if self.cloud is None:
-            return not p.arm.in_collision(state, p.collision_threshold)
-        return not (p.arm.in_collision(state, p.collision_threshold)
-                    or p.arm.in_collision_with_cloud(state, self.cloud, p.collision_threshold, self.cloud_ignore_links))
+        if p.arm.in_collision(state, p.collision_threshold):
+            return False
+        if self.cloud is not None and p.arm.in_collision_with_cloud(state, self.cloud, p.collision_threshold, self.cloud_ignore_links):
+            return False
+        return self.attached is None or not p.arm.in_collision_with_attached(state, self.attached, p.collision_threshold)
 
     # ---- batched ------------------------------------------------------------------------------------------
     def certify_batch(self, starts, goals, mode="connect", dist=None):
@@ -386,14 +437,18 @@ class ContinuousConnector(Connector):
                              "and no validity_checker")
         sm, dev = p.arm._scene_device()
         kw = dict(mode=mode, threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
-        if self.cloud is None:
+        if self.cloud is None and self.attached is None:
             return dev.edge_continuous(starts, goals, p.max_distance, dist=dist, **kw)
-        # items of an edge the scene stopped early stop there; `end` is the scene's
-        return _scene_then_cloud(
-            (starts, goals, dist), lambda s, g, d: dev.edge_continuous(s, g, p.max_distance, dist=d, **kw),
+        held = None if self.attached is None else self.attached._device(p.arm)[1]
+        # items of an edge the scene stopped early stop there; `end` is the scene's.  The cloud's items, then the held object's
+        cloud = None if self.cloud is None else (
             lambda s, g, d, res: dev.cloud_edge_continuous(self.cloud, s, g, p.max_distance, look_ahead=self.look_ahead, dist=d,
                                                            shapes=p.arm._cloud_shapes(sm, self.cloud_ignore_links),
                                                            out=(res[0], res[2], res[3]), **kw))
+        hold = None if held is None else (
+            lambda s, g, d, res: dev.held_edge_continuous(held, s, g, p.max_distance, dist=d, out=(res[0], res[2], res[3]), **kw))
+        return _scene_then_cloud(
+            (starts, goals, dist), lambda s, g, d: dev.edge_continuous(s, g, p.max_distance, dist=d, **kw), _then(cloud, hold))
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -409,19 +464,22 @@ class ContinuousConnector(Connector):
         if self.cloud is not None:
             raise ValueError("certified trajectory checks do not see point clouds yet")
 
-    def _spline_certify(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None):
+    def _spline_certify(self, ctrl, knots, degree, cloud=None, cloud_ignore_links=None, attached=None):
         p = self._params
+        attached = self.attached if attached is None else _attachment(attached)      # (argument errors before the device is touched)
         sm, dev = p.arm._scene_device()
         kw = dict(threshold=p.collision_threshold, max_iter=self.max_iter, slack=self.slack)
-        if cloud is None:
+        if cloud is None and attached is None:
             return dev.spline_continuous(ctrl, knots, degree, **kw)
         links = self.cloud_ignore_links if cloud_ignore_links is None else tuple(cloud_ignore_links)
-        return _scene_then_cloud(
-            (ctrl,), lambda c: dev.spline_continuous(c, knots, degree, **kw),
+        held = None if attached is None else attached._device(p.arm)[1]
+        scan = None if cloud is None else (
             lambda c, res: dev.cloud_spline_continuous(cloud, c, knots, degree, look_ahead=self.look_ahead,
                                                        shapes=p.arm._cloud_shapes(sm, links), out=res, **kw))
+        hold = None if held is None else (lambda c, res: dev.held_spline_continuous(held, c, knots, degree, out=res, **kw))
+        return _scene_then_cloud((ctrl,), lambda c: dev.spline_continuous(c, knots, degree, **kw), _then(scan, hold))
 
-    def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None):
+    def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None, attached=None):
         """S clamped B-splines of ``unit_bspline``'s knots, each certified on the device by conservative advancement across its knot
         spans (``nbk_spline_continuous_batch``): (S, n, dof) -> valid (S,) bool, t_free (S,) (how far along [0, 1] the trajectory
         is certified free; NaN when degenerate), status (S,) int32 (``numbotics_amd._lib.CA_*``).  A trajectory called valid has
@@ -429,18 +487,19 @@ class ContinuousConnector(Connector):
         ``cloud`` (a ``PointCloud``): the trajectories are certified against the scan as well
         (``nbk_spline_cloud_continuous_batch`` accumulating into the scene's result, with this connector's ``look_ahead``), without
         the shapes of ``cloud_ignore_links`` (default: the connector's own tuple).  A call that names no cloud is refused when the
-        connector carries one."""
+        connector carries one.  ``attached`` (an ``Attachment``; default: the connector's own): the object in the hand is certified
+        as well, after the scan (``nbk_spline_held_continuous_batch`` accumulating into the same result)."""
         if cloud is None:
             self._no_cloud_splines()
         shape = _shape(control_points)
         k = _spline_args(self._params, shape, degree)
-        return self._spline_certify(control_points, unit_knots(shape[1], k), k, cloud, cloud_ignore_links)
+        return self._spline_certify(control_points, unit_knots(shape[1], k), k, cloud, cloud_ignore_links, attached)
 
-    def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None):
+    def validate_trajectory(self, spline, cloud=None, cloud_ignore_links=None, attached=None):
         """One ``UnitBSpline`` (``unit_bspline``'s output, or any spline with knots clamped on [0, 1]) -> (valid, t_free).  ``cloud``,
-        ``cloud_ignore_links``: as ``validate_trajectories``."""
+        ``cloud_ignore_links``, ``attached``: as ``validate_trajectories``."""
         if cloud is None:
             self._no_cloud_splines()
         c, t, k = _spline_parts(self._params, spline)
-        valid, t_free, _ = self._spline_certify(c[None], t, k, cloud, cloud_ignore_links)
+        valid, t_free, _ = self._spline_certify(c[None], t, k, cloud, cloud_ignore_links, attached)
         return bool(valid[0]), float(t_free[0])

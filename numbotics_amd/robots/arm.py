@@ -617,6 +617,40 @@ class Arm(Robot):
         mask = dev.held_validity(held, q.reshape(-1, self.dof), threshold, pose=pose)
         return mask.reshape(tuple(q.shape[:-1]))
 
+    def attached_clearance(self, q, att, pose=None):
+        """How close is the held object of ``att`` to what it is paired with?  -> (distance, item): the smallest signed distance
+        over the attachment's items and the item that attains it (the smallest index on a tie; ``att.items(arm)`` names them), or
+        (inf, -1) where the attachment has no item.  ``(dof,)`` -> (float, int); ``(B, dof)`` -> arrays / tensors (B,).  A row
+        that is not finite gives NaN and -1.  ``pose``: as ``in_collision_with_attached``."""
+        if q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        dev, held = att._device(self)
+        d = dev.held_distances(held, q.reshape(-1, self.dof), pose=pose)
+        if isinstance(d, np.ndarray):
+            B = d.shape[0]
+            if d.shape[1] == 0:
+                dist, item = np.full((B,), np.inf), np.full((B,), -1, dtype=np.int64)
+            else:
+                bad = np.isnan(d).any(axis=1)
+                item = np.where(bad, -1, np.argmin(np.where(np.isnan(d), np.inf, d), axis=1))
+                dist = np.where(bad, np.nan, d[np.arange(B), np.maximum(item, 0)])
+        else:
+            import torch
+            B = d.shape[0]
+            if d.shape[1] == 0:
+                dist = torch.full((B,), float("inf"), dtype=torch.float64, device=d.device)
+                item = torch.full((B,), -1, dtype=torch.int64, device=d.device)
+            else:
+                bad = torch.isnan(d).any(dim=1)
+                dmin = d.min(dim=1, keepdim=True).values
+                k = torch.arange(d.shape[1], device=d.device).expand_as(d)
+                first = torch.where(d == dmin, k, d.shape[1]).min(dim=1).values        # the smallest index that attains the minimum
+                item = torch.where(bad, -1, first)
+                dist = torch.where(bad, float("nan"), dmin[:, 0])
+        if q.ndim == 1:
+            return float(dist[0]), int(item[0])
+        return dist, item
+
     def cloud_self_filter(self, points, q, radius: float, padding: float = 0.0, keep=None, links=None, ignore_links=()):
         """Which of a depth frame's ``points`` (N, 3) are NOT the arm's own image at the configuration ``q`` the frame was taken at:
         ``keep[i]`` goes to 0 iff point i, a sphere of ``radius``, is closer than ``padding`` to a link shape -- the verdict

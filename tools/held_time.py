@@ -13,6 +13,11 @@ alternating.
     edges       DeviceModel.held_edge_validity at --edges edges a -> a + U(-0.5, 0.5), resolution 0.05, connect mode; against
                 edge_validity on the box-as-link descriptor minus edge_validity on the plain scene; and the connector's sequence
                 (edge_validity, then the held call ANDed into its result).  The valid flags must agree.
+    trajectories  held_distances at --rows configurations, held_edge_continuous at --edges edges, held_spline_continuous and
+                held_spline_validity at --splines trajectories (6 control points, degree 3, a random walk of step 0.12 from a sampled
+                configuration).  The yardstick is the scene's own entry on the same inputs in the same process (pair_distances,
+                edge_continuous, spline_continuous, spline_validity), per held item against per scene pair.  Each accumulated
+                result must equal the scene's entry on the box-as-link descriptor, bit for bit.
 """
 import argparse
 import dataclasses
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1000000)
     ap.add_argument("--edges", type=int, default=100000)
+    ap.add_argument("--splines", type=int, default=10000)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/held_time.py needs a GPU: nothing is measured without one")
@@ -127,7 +133,65 @@ def main():
             res = dev.edge_validity(st, gt, 0.05, 10.0)
             dev.held_edge_validity(held, st, gt, 0.05, 10.0, out=res[0], workspace=ws)
         say(f"  edge_validity then held(out=)       {fmt(timed(sequence, args.reps))}")
-        del linked, held, dev, qt, st, gt, ws
+        # ---- trajectories: distances, certified edges, certified and sampled splines; the yardstick is the scene's own entry on
+        # the same inputs in the same process (the scene's P pairs against the held object's K items: ms per pair / per item)
+        K, P, S = held.n_items, sm.n_pairs, args.splines
+        d_held = dev.held_distances(held, qt)
+        d_link = linked.pair_distances(qt[:65536])[:, P:]
+        if not torch.equal(d_held[:65536].view(torch.int64), d_link.contiguous().view(torch.int64)):
+            raise SystemExit(f"{name}: held_distances != the held columns of pair_distances(box as link)")
+        del d_held, d_link
+        say(f"trajectories  K = {K} held items, P = {P} scene pairs")
+        t_d, t_pd = timed_pair(lambda: dev.held_distances(held, qt), lambda: dev.pair_distances(qt), args.reps)
+        say(f"  held_distances, B = {B}              {fmt(t_d)}   ({1e3 * t_d[0] / K:.1f} us per item)")
+        say(f"  pair_distances (scene), B = {B}      {fmt(t_pd)}   ({1e3 * t_pd[0] / P:.1f} us per pair; per item / per pair: {t_d[0] * P / (t_pd[0] * K):.2f})")
+        c_own = dev.edge_continuous(st, gt, 10.0)
+        c_held = dev.held_edge_continuous(held, st, gt, 10.0)
+        c_both = linked.edge_continuous(st, gt, 10.0)
+        acc = tuple(x.clone() for x in (c_own[0], c_own[2], c_own[3]))
+        dev.held_edge_continuous(held, st, gt, 10.0, out=acc)
+        if not (torch.equal(acc[2], c_both[3]) and torch.equal(acc[1].view(torch.int64), c_both[2].view(torch.int64))):
+            raise SystemExit(f"{name}: edge_continuous then held_edge_continuous(out=) != edge_continuous(box as link)")
+        say(f"certified edges  E = {E}: results agree; FREE {float((c_held[3] == 0).float().mean()):.3f} (held alone), "
+            f"{float((c_both[3] == 0).float().mean()):.3f} (with the scene)")
+        t_h, t_s = timed_pair(lambda: dev.held_edge_continuous(held, st, gt, 10.0), lambda: dev.edge_continuous(st, gt, 10.0), args.reps)
+        say(f"  held_edge_continuous                {fmt(t_h)}   ({1e3 * t_h[0] / K:.1f} us per item)")
+        say(f"  edge_continuous (scene)             {fmt(t_s)}   ({1e3 * t_s[0] / P:.1f} us per pair; per item / per pair: {t_h[0] * P / (t_s[0] * K):.2f})")
+
+        def certified():
+            r = dev.edge_continuous(st, gt, 10.0)
+            dev.held_edge_continuous(held, st, gt, 10.0, out=(r[0], r[2], r[3]))
+        say(f"  edge_continuous then held(out=)     {fmt(timed(certified, args.reps))}")
+        from numbotics_amd.planning import unit_knots
+        ctrl = qt[:S, None, :] + torch.cumsum(torch.from_numpy(np.random.default_rng(7).uniform(-0.12, 0.12, (S, 6, chain.dof))).cuda(), dim=1)
+        ctrl = ctrl.contiguous()
+        kn = unit_knots(6, 3)
+        knt = torch.from_numpy(kn).cuda()
+        s_held = dev.held_spline_continuous(held, ctrl, knt, 3)
+        s_both = linked.spline_continuous(ctrl, knt, 3)
+        acc = dev.spline_continuous(ctrl, knt, 3)
+        dev.held_spline_continuous(held, ctrl, knt, 3, out=acc)
+        if not (torch.equal(acc[2], s_both[2]) and torch.equal(acc[1].view(torch.int64), s_both[1].view(torch.int64))):
+            raise SystemExit(f"{name}: spline_continuous then held_spline_continuous(out=) != spline_continuous(box as link)")
+        say(f"certified splines  S = {S}, 6 control points, degree 3: results agree; FREE {float((s_held[2] == 0).float().mean()):.3f} "
+            f"(held alone), {float((s_both[2] == 0).float().mean()):.3f} (with the scene)")
+        t_h, t_s = timed_pair(lambda: dev.held_spline_continuous(held, ctrl, knt, 3), lambda: dev.spline_continuous(ctrl, knt, 3), args.reps)
+        say(f"  held_spline_continuous              {fmt(t_h)}   ({1e3 * t_h[0] / K:.1f} us per item)")
+        say(f"  spline_continuous (scene)           {fmt(t_s)}   ({1e3 * t_s[0] / P:.1f} us per pair; per item / per pair: {t_h[0] * P / (t_s[0] * K):.2f})")
+        ws2 = torch.empty((dev.held_spline_workspace_bytes(S),), dtype=torch.uint8, device="cuda")
+        v_held = dev.held_spline_validity(held, ctrl, knt, 3, 0.05, workspace=ws2)
+        v_both = linked.spline_validity(ctrl, kn, 3, 0.05)
+        acc = dev.spline_validity(ctrl, kn, 3, 0.05)
+        dev.held_spline_validity(held, ctrl, knt, 3, 0.05, out=acc, workspace=ws2)
+        if not (torch.equal(acc[0], v_both[0]) and torch.equal(acc[1].view(torch.int64), v_both[1].view(torch.int64))):
+            raise SystemExit(f"{name}: spline_validity then held_spline_validity(out=) != spline_validity(box as link)")
+        say(f"sampled splines  S = {S}, resolution 0.05, {int(v_held[2].sum())} samples: results agree; valid "
+            f"{float(v_held[0].float().mean()):.3f} (held alone), {float(v_both[0].float().mean()):.3f} (with the scene)")
+        t_h, t_s = timed_pair(lambda: dev.held_spline_validity(held, ctrl, knt, 3, 0.05, workspace=ws2),
+                              lambda: dev.spline_validity(ctrl, kn, 3, 0.05), args.reps)
+        say(f"  held_spline_validity                {fmt(t_h)}")
+        say(f"  spline_validity (scene)             {fmt(t_s)}   (held / scene: {t_h[0] / t_s[0]:.2f})")
+        del linked, held, dev, qt, st, gt, ws, ws2, ctrl, acc
     log.close()
 
 
