@@ -934,6 +934,57 @@ int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc *d, int32_t fram
                                            const double *knots /* host */, double *mu /* [S][n_ctrl-degree][K] */);   /* no GPU */
 
 /*
+ * The held object against a point cloud: the held shapes in the robot shapes' place of the cloud's entries.  The verdict of held
+ * shape h (world pose F(q) . ((A . G) . L_h), as above) against a cloud of N points of radius r is the OR over (h, i) of the pair
+ * predicate for (robot shape, sphere world shape of radius r at p_i), in the operand order of nbk_cloud_validity_batch:
+ *     tc = (threshold + margin_h) + r;  rs = (tc + rho_h) + 0;  free unless rs > 0 and |c_h - p_i|^2 < rs^2;  then the exact test,
+ *     the point first
+ * -- bit for bit what a descriptor reports that holds the held shapes as robot shapes S+h of `frame`, the N points as sphere world
+ * shapes and the pairs (S+h, p_i).  This is the held-versus-cloud term ALONE: full validity is scene | arm-versus-cloud |
+ * held-versus-scene | held-versus-cloud, each entry accumulating into the same result.  No world shape and no link takes part: the
+ * world status of a movable descriptor is not read, and world_shapes / robot_bits of nbk_held_create play no part.  A row of q or a
+ * grasp row that is not finite collides; a cloud whose status is set makes every row collide; an empty cloud is free.
+ *
+ * nbk_held_cloud_validity_batch: q, grasp / grasp_rows (0, 1 or B), mask_bits / mask_bytes and accumulate as
+ * nbk_held_validity_batch.  One kernel, one row per lane, the grid walk of nbk_cloud_validity_batch per held shape.
+ *
+ * nbk_held_cloud_clearance_batch: nbk_cloud_clearance_batch over the held shapes: min_dist [B] the smallest signed distance below
+ * d_max, shape [B] (optional) the HELD shape index h, point [B] (optional) the point's index in the last update; +inf, -1, -1 when
+ * nothing is nearer than d_max; NaN, -1, -1 for a non-finite q or grasp row or a set status.  On equal distances the smallest h wins,
+ * then the smallest point index.  d_max must be finite.
+ *
+ * nbk_edge_held_cloud_validity_batch / nbk_spline_held_cloud_validity_batch: nbk_edge_cloud_validity_batch /
+ * nbk_spline_cloud_validity_batch with this verdict per sample: the same plan, samples, end / t_hit / n_samples, accumulate and
+ * workspace (nbk_edge_held_cloud_workspace_bytes(E) / nbk_spline_held_cloud_workspace_bytes(S): the cloud siblings' layouts, no
+ * GPU).  grasp (device, optional) [16]: ONE grasp for the call, NULL = the stored G.  A non-finite grasp or a set cloud status makes
+ * every non-degenerate edge invalid, and hits every trajectory that has samples at its first sample.
+ *
+ * Argument rules are those of the held and cloud siblings, answered before any device is touched: NBK_ERR_INVALID for a null pointer,
+ * grasp_rows outside {0, 1, B}, a grasp pointer that does not go with grasp_rows, a NaN threshold, a non-finite d_max, a workspace
+ * too small or not 64-byte aligned, and a held object made against another descriptor.  Then the held object, the cloud and the
+ * descriptor must be on the current device.  All calls are asynchronous, allocate nothing, and are capturable; LDS holds the q rows only.
+ */
+int32_t nbk_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *q, int64_t B,
+                                      const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double threshold,
+                                      int32_t accumulate, uint64_t *mask_bits, uint8_t *mask_bytes, void *stream);
+int32_t nbk_held_cloud_clearance_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *q, int64_t B,
+                                       const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double d_max,
+                                       double *min_dist, int32_t *shape /* optional */, int32_t *point /* optional */, void *stream);
+int64_t nbk_edge_held_cloud_workspace_bytes(int64_t E);
+int32_t nbk_edge_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *starts,
+                                           const double *goals, const double *dist /* optional */, int64_t E, double resolution,
+                                           double max_distance, int32_t mode, double threshold,
+                                           const double *grasp /* DEVICE [16] or NULL */, int32_t accumulate, uint8_t *valid,
+                                           double *end /* optional */, int32_t *n_samples /* optional */, void *workspace,
+                                           int64_t workspace_bytes, void *stream);
+int64_t nbk_spline_held_cloud_workspace_bytes(int64_t S);
+int32_t nbk_spline_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *ctrl,
+                                             int64_t S, int32_t n_ctrl, int32_t degree, const double *knots /* DEVICE */,
+                                             double resolution, double threshold, const double *grasp /* DEVICE [16] or NULL */,
+                                             int32_t accumulate, uint8_t *valid, double *t_hit /* optional */,
+                                             int32_t *n_samples /* optional */, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -297,6 +297,227 @@ __global__ __launch_bounds__(64) void k_held_spline(DevModel m, HeldDev hd, cons
     }
 }
 
+// ---- the held object against a point cloud (nbk_held_cloud_*): the held shapes in the robot shapes' place of the cloud's kernels.
+// The verdict is the OR over (held shape h, point i) of the pair predicate for (robot shape, sphere world shape of the cloud's radius
+// at p_i) in cloud_row_hits' operand order: tc = (thr + margin_h) + radius, rs = (tc + rho_h) + 0, free unless rs > 0 and
+// |c_h - p|^2 < rs^2, then cloud_collides(P, Hc, tc) with the point core first -- the bits of a descriptor that holds the held shapes
+// as robot shapes S + h of the holding frame and the points as sphere world shapes, with the pairs (S + h, p_i).  This is the
+// held-versus-cloud term ALONE: no world shape and no link takes part, the world status is not read, and the attachment's world
+// list and robot set play no part.
+
+// cloud_collides(P, Hc, tc) for a point core P and a held core Hc.  A held shape is never a hull, so cloud_collides is
+// cores_collide_exact, and for a point core first and a second core that is no hull cores_collide_pre decides EVERY pair -- box
+// cores in its midphase or, like cylinder cores, in its last statement (point_solid), point and segment cores in ps_closest -- and never
+// answers -1: cores_collide_exact returns `pre != 0` there, bit for bit.  Calling the routine that decides keeps the three GJK
+// walks behind it out of these kernels (their scratch arrays and spills with them).  (-1 cannot come; it would read "collides".)
+NBK_DEV bool held_cloud_collides(const Core& P, const Core& Hc, double tc) { return cores_collide_pre(P, Hc, tc) != 0; }
+
+// The walk: cloud_row_hits with held_core in build_core's place (held shapes are never hulls: no scalar-cache path).  Called by
+// every lane of the wave (`active`, `hit` as in held_row_hits); the caller has checked that the cloud holds points and that its
+// status is clear.
+NBK_DEV void held_cloud_row_hits(const DevModel& m, const HeldDev& hd, const CloudDev& cd, const double* grasp_row, double radius,
+                                 double thr, const double* myq, bool active, bool& hit) {
+    if (__builtin_amdgcn_ballot_w64(active && !hit) == 0ull) return;
+    Core P;
+    cloud_point_core(radius, P);
+    Xf F;
+    double AG[12];
+    if (active && !hit) {
+        held_frame(m, hd.mask, myq, F);
+        double G[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) G[e] = grasp_row[e];
+        held_mul12(hd.tab, G, AG);
+    }
+    for (int h = 0; h < hd.n_shapes; ++h) {
+        const bool work = active && !hit;
+        if (__builtin_amdgcn_ballot_w64(work) == 0ull) break;
+        Core Hc;
+        cloud_core_init(Hc);
+        double tc = 0.0, rs = 0.0;
+        if (work) {
+            held_core(hd, h, F, AG, Hc);
+            tc = (thr + Hc.margin) + radius;
+            rs = (tc + Hc.rho) + 0.0;
+        }
+        CloudWalk w;
+        cloud_walk_begin(cd, work, Hc.c, rs, w);
+        const double rs2 = rs * rs;
+        while (true) {
+            // (cloud_row_hits' two stages: run ahead to the next point inside the bounding sphere, decide side by side)
+            bool cand = false;
+            while (!hit && !cand && cloud_walk_next(cd, w)) {
+                const double* p = cd.pts + 3 * (size_t)w.cur;
+                ++w.cur;
+                P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+                double dc[3];
+                sub3(Hc.c, P.c, dc);
+                cand = dot3(dc, dc) < rs2;
+            }
+            if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
+            if (cand && held_cloud_collides(P, Hc, tc)) hit = true;
+        }
+    }
+}
+
+// verdict of row b = the walk's, or 1 for a non-finite q or grasp row or a set cloud status; an empty cloud is free.  k_held_validity's
+// frame: a workgroup owns one mask word, so the word and the bytes have one writer each.
+__global__ __launch_bounds__(64) void k_held_cloud_validity(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ q, int64_t B,
+                                                            const double* __restrict__ grasp, int grasp_rows, double thr, int accumulate,
+                                                            unsigned long long* __restrict__ mask_bits, uint8_t* __restrict__ mask_bytes) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    double* myq = lds + lane * m.n_q;
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool hit = false;
+    const double* grow = hd.tab + 12;
+    if (active) {
+        bool gfin = true;
+        grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
+        hit = !cloud_stage_q(q, b, m.n_q, myq) || !gfin || status != 0;
+    }
+    if (n > 0 && status == 0) held_cloud_row_hits(m, hd, cd, grow, radius, thr, myq, active, hit);
+    const unsigned long long word = __builtin_amdgcn_ballot_w64(active && hit);
+    if (mask_bits != nullptr && lane == 0) {
+        if (accumulate) { if (word != 0ull) mask_bits[blockIdx.x] |= word; }
+        else mask_bits[blockIdx.x] = word;
+    }
+    if (mask_bytes != nullptr && active) {
+        if (!accumulate) mask_bytes[b] = hit ? 1 : 0;
+        else if (hit) mask_bytes[b] = 1;
+    }
+}
+
+// k_cloud_clearance with the held shapes in the robot shapes' place: per row the minimum over (h, i) of the signed distance, reported
+// below d_max with the held shape index and the original point index (ties: the smallest h, then the smallest point); NaN, -1, -1
+// for a non-finite q or grasp row or a set status; +inf, -1, -1 when nothing is nearer than d_max.
+__global__ __launch_bounds__(64) void k_held_cloud_clearance(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ q, int64_t B,
+                                                             const double* __restrict__ grasp, int grasp_rows, double d_max,
+                                                             double* __restrict__ out_d, int32_t* __restrict__ out_s,
+                                                             int32_t* __restrict__ out_p) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    double* myq = lds + lane * m.n_q;
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool ok = false;
+    const double* grow = hd.tab + 12;
+    if (active) {
+        bool gfin = true;
+        grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
+        ok = cloud_stage_q(q, b, m.n_q, myq) && gfin && status == 0;
+    }
+    double best = NBK_INF;
+    int bs = -1, bi = -1;
+    if (n > 0 && status == 0 && __builtin_amdgcn_ballot_w64(ok) != 0ull) {
+        Core P;
+        cloud_point_core(radius, P);
+        Xf F;
+        double AG[12];
+        if (ok) {
+            held_frame(m, hd.mask, myq, F);
+            double G[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) G[e] = grow[e];
+            held_mul12(hd.tab, G, AG);
+        }
+        for (int h = 0; h < hd.n_shapes; ++h) {
+            Core Hc;
+            cloud_core_init(Hc);
+            if (ok) held_core(hd, h, F, AG, Hc);
+            cloud_core_clearance(cd, Hc, P, radius, ok, h, d_max, best, bs, bi);
+        }
+    }
+    if (active) {
+        out_d[b] = ok ? best : __builtin_nan("");
+        if (out_s != nullptr) out_s[b] = ok ? bs : -1;
+        if (out_p != nullptr) out_p[b] = ok ? bi : -1;
+    }
+}
+
+// k_cloud_edges with the held walk against the cloud (nbk_edge_held_cloud_validity_batch): the plan, the scan and k_cloud_edges_init
+// are the cloud's.  One grasp per call; a non-finite grasp or a set cloud status makes every non-degenerate edge invalid.
+__global__ __launch_bounds__(64) void k_held_cloud_edges(DevModel m, HeldDev hd, CloudDev cd, EdgeSrc es,
+                                                         const unsigned long long* __restrict__ offs, int64_t E,
+                                                         const double* __restrict__ grasp, int grasp_rows, double thr, uint8_t* valid) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    double* myq = lds + lane * m.n_q;
+    const unsigned long long total = offs[E];
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool gfin = true;
+    const double* grow = held_grasp_row(hd, grasp, grasp_rows, 0, gfin);
+    const bool bad = !gfin || status != 0;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * WAVE; base < total; base += (unsigned long long)gridDim.x * WAVE) {
+        const unsigned long long f = base + (unsigned long long)lane;
+        int64_t e = 0;
+        bool work = false;
+        if (f < total) {
+            e = cloud_flat_owner(offs, E, f);
+            if (__hip_atomic_load(valid + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+                edge_sample_row(es, ((unsigned long long)e << 32) | (f - offs[e]), m.n_q, myq, 1);
+                work = !row_nonfinite(myq, m.n_q, 1) && !bad;
+                if (!work) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        bool hit = false;
+        if (n > 0 && !bad) held_cloud_row_hits(m, hd, cd, grow, radius, thr, myq, work, hit);
+        if (hit) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// k_cloud_spline with the held walk against the cloud and the call's grasp (nbk_spline_held_cloud_validity_batch): the same plan,
+// scan, first-hit key (SPC_*) and accumulate rules; k_cloud_spline_init (hold: the cloud's status) and k_cloud_spline_final are the
+// cloud's.  A non-finite grasp hits every sample that is looked at, as in k_held_spline.
+template <int K>
+__global__ __launch_bounds__(64) void k_held_cloud_spline(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ ctrl, int n,
+                                                          const double* __restrict__ knots, const double* __restrict__ plan,
+                                                          const unsigned long long* __restrict__ offs, int64_t S,
+                                                          const double* __restrict__ grasp, int grasp_rows, double thr,
+                                                          const double* __restrict__ t_prev, unsigned long long* first) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    double* myq = lds + lane * m.n_q;
+    const unsigned long long total = offs[S];
+    const int ncl = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool gfin = true;
+    const double* grow = held_grasp_row(hd, grasp, grasp_rows, 0, gfin);
+    for (unsigned long long base = (unsigned long long)blockIdx.x * WAVE; base < total; base += (unsigned long long)gridDim.x * WAVE) {
+        const unsigned long long f = base + (unsigned long long)lane;
+        int64_t s = 0;
+        unsigned long long j = 0ull;
+        bool work = false, hit = false;
+        if (f < total) {
+            s = cloud_flat_owner(offs, S, f);
+            j = f - offs[s];
+            const unsigned long long key = __hip_atomic_load(first + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (key <= SPC_NONE && j + 1ull < key) {
+                const double jd = (double)j;
+                const double t = jd < plan[2 * s + 1] ? jd * plan[2 * s] : 1.0;
+                if (t_prev == nullptr || !(t >= t_prev[s])) {
+                    const int ell = spline_span<K>(knots, n, t);
+                    const double* cp = ctrl + ((size_t)s * (size_t)n + (size_t)(ell - K)) * m.n_q;
+                    de_boor<K>(m.n_q, cp, knots, ell, t, [&](int c, double v) { myq[c] = v; });
+                    work = gfin && !row_nonfinite(myq, m.n_q, 1);
+                    hit = !work;                             // a non-finite sample, or grasp, collides
+                }
+            }
+        }
+        if (ncl > 0 && gfin) held_cloud_row_hits(m, hd, cd, grow, radius, thr, myq, work, hit);
+        if (hit) atomicMin(first + s, j + 1ull);
+    }
+}
+
 // ---- held items: one (held shape h, other shape) pair each, in the order of the pair list of a descriptor that holds the held
 // shapes as robot shapes S + h: (s, S + h) for the allowed robot shapes s in the caller's order, then h; then (S + h, world w) for h,
 // then the allowed world shapes.  HeldDev.items holds them (held_item_list, made once by nbk_held_create).
@@ -824,6 +1045,133 @@ int32_t nbk_spline_held_validity_batch(const nbk_model* m, const nbk_held* held,
         hipLaunchKernelGGL(k_held_spline<decltype(K)::value>, grid, block, lds, st, m->d, held->d, ctrl, (int)n_ctrl, knots,
                            (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp, grasp != nullptr ? 1 : 0, threshold, t_prev,
                            v.first);
+    });
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
+                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// ---- the held object against a point cloud.  What every entry answers once its own argument rules are through: the held object's
+// descriptor and device (held_call_begin), then the cloud's device.
+static int32_t held_cloud_call_begin(const nbk_model* m, const nbk_held* held, const nbk_cloud* c) {
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    return cloud_check_device(c);
+}
+
+int32_t nbk_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* q, int64_t B,
+                                      const double* grasp, int64_t grasp_rows, double threshold, int32_t accumulate, uint64_t* mask_bits,
+                                      uint8_t* mask_bytes, void* stream) {
+    if (m == nullptr || held == nullptr || c == nullptr || B < 0 || threshold != threshold) return NBK_ERR_INVALID;
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    if (B > 0 && (q == nullptr || (mask_bits == nullptr && mask_bytes == nullptr))) return NBK_ERR_INVALID;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    if (B == 0) return NBK_OK;
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
+    hipLaunchKernelGGL(k_held_cloud_validity, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d, held->d,
+                       cloud_dev(c), q, B, grasp, rows, threshold, (int)accumulate, reinterpret_cast<unsigned long long*>(mask_bits),
+                       mask_bytes);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_held_cloud_clearance_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* q, int64_t B,
+                                       const double* grasp, int64_t grasp_rows, double d_max, double* min_dist, int32_t* shape,
+                                       int32_t* point, void* stream) {
+    if (m == nullptr || held == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0)) return NBK_ERR_INVALID;
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    if (B > 0 && (q == nullptr || min_dist == nullptr)) return NBK_ERR_INVALID;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    if (B == 0) return NBK_OK;
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
+    hipLaunchKernelGGL(k_held_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
+                       held->d, cloud_dev(c), q, B, grasp, rows, d_max, min_dist, shape, point);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_edge_held_cloud_workspace_bytes(int64_t E) {
+    if (E < 0 || E > EDGE_CLOUD_MAX_E) return -1;
+    return (int64_t)EdgeCloudLayout(E).bytes;
+}
+
+int32_t nbk_edge_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* starts,
+                                           const double* goals, const double* dist, int64_t E, double resolution, double max_distance,
+                                           int32_t mode, double threshold, const double* grasp, int32_t accumulate, uint8_t* valid,
+                                           double* end, int32_t* n_samples, void* workspace, int64_t workspace_bytes, void* stream) {
+    // (nothing below dereferences m, held or c before the argument rules are through: they are answered without a device)
+    if (m == nullptr || held == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
+    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
+        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
+    double* const plan = v.plan;
+    unsigned long long *const cnt = v.cnt, *const offs = v.offs;
+    const unsigned eblocks = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
+                       plan, cnt, end, n_samples);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_edges_init, dim3(eblocks), dim3(256), 0, st, cnt, E, (int)accumulate, valid);
+    NBK_HIP(hipGetLastError());
+    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
+    const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
+    hipLaunchKernelGGL(k_held_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
+                       QSlabLds(m->n_q).bytes(), st, m->d, held->d, cloud_dev(c), es, offs, E, grasp, grasp != nullptr ? 1 : 0, threshold,
+                       valid);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int64_t nbk_spline_held_cloud_workspace_bytes(int64_t S) {
+    if (S < 0 || S >= SPLINE_MAX_S) return -1;
+    return (int64_t)SplineCloudLayout(S).bytes;
+}
+
+int32_t nbk_spline_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* ctrl, int64_t S,
+                                             int32_t n_ctrl, int32_t degree, const double* knots, double resolution, double threshold,
+                                             const double* grasp, int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples,
+                                             void* workspace, int64_t workspace_bytes, void* stream) {
+    // (as nbk_spline_cloud_validity_batch: the argument rules are answered without a device)
+    if (m == nullptr || held == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
+    if (S > 0 && S < SPLINE_MAX_S &&
+        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
+    if (S == 0) return NBK_OK;
+    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    int cus = 0;
+    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
+    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
+    NBK_HIP(hipGetLastError());
+    const double* t_prev = accumulate ? t_hit : nullptr;
+    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt,
+                       (const int*)&c->hdr->status, (int)accumulate, (const uint8_t*)valid, t_prev, v.first);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
+    NBK_HIP(hipGetLastError());
+    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
+    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
+    const size_t lds = QSlabLds(m->n_q).bytes();
+    with_degree(degree, [&](auto K) {
+        hipLaunchKernelGGL(k_held_cloud_spline<decltype(K)::value>, grid, block, lds, st, m->d, held->d, cloud_dev(c), ctrl, (int)n_ctrl,
+                           knots, (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp, grasp != nullptr ? 1 : 0, threshold,
+                           t_prev, v.first);
     });
     NBK_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,

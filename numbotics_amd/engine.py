@@ -956,6 +956,99 @@ class DeviceModel:
             return valid, t_free, status
         return c.out(valid.bool()), c.out(t_free), c.out(status)
 
+    # ---- held objects against point clouds --------------------------------------------------------------
+    def held_cloud_validity(self, held, cloud, q, threshold=0.0, packed=False, pose=None, out=None):
+        """In-collision flags of q for the held object ``held`` against ``cloud`` (a ``PointCloud``) ALONE
+        (nbk_held_cloud_validity_batch): no world shape and no link takes part, and the attachment's world list and robot set play
+        none.  Bit for bit ``cloud_validity`` of a descriptor that holds the held shapes as robot shapes.  ``pose`` / ``packed`` /
+        ``out``: as ``held_validity`` -- ``validity``, ``cloud_validity``, ``held_validity`` and this call on one mask are validity
+        with the object in the hand among what the camera sees.  A row whose q or grasp is not finite collides, every row while
+        the cloud's status is set; an empty cloud is free."""
+        torch = _require_gpu()
+        h = self._held(held)
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        want = ((qs.B + 63) // 64,) if packed else (qs.B,)
+        if out is not None:
+            res = self._mask_out(torch, out, want, packed)
+        else:
+            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=qs.device)
+        words, mask = (res, None) if packed else (None, res)
+        _lib.check(self._lib.nbk_held_cloud_validity_batch(
+            self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(threshold),
+            0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
+            self._stream()), "nbk_held_cloud_validity_batch")
+        if out is not None:
+            return out
+        return qs.out(words) if packed else qs.out(mask.bool())
+
+    def held_cloud_clearance(self, held, cloud, q, d_max, pose=None):
+        """Per configuration the smallest signed distance from the held object to ``cloud`` when it is below ``d_max``
+        (nbk_held_cloud_clearance_batch) -> (distance (B,), held shape (B,) int32, point index (B,) int32); +inf, -1, -1 where
+        nothing is closer than ``d_max``; NaN, -1, -1 for a non-finite configuration or grasp or while the cloud's status is set.
+        Ties: smallest held shape, then smallest point.  ``pose``: as ``held_validity``'s, one grasp or one per row."""
+        torch = _require_gpu()
+        h = self._held(held)
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        d = torch.empty((qs.B,), dtype=torch.float64, device=qs.device)
+        sh = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
+        pt = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
+        _lib.check(self._lib.nbk_held_cloud_clearance_batch(
+            self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(d_max),
+            d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._stream()), "nbk_held_cloud_clearance_batch")
+        return qs.out(d), qs.out(sh), qs.out(pt)
+
+    @staticmethod
+    def held_cloud_edge_workspace_bytes(E: int) -> int:
+        return int(_lib.load().nbk_edge_held_cloud_workspace_bytes(int(E)))
+
+    def held_cloud_edge_validity(self, held, cloud, starts, goals, resolution, max_distance, mode="connect", threshold=0.0, dist=None,
+                                 pose=None, out=None, workspace=None):
+        """``edge_validity``'s edges for the held object against ``cloud`` ALONE: an edge is valid when it is not degenerate and
+        ``held_cloud_validity`` clears every one of its samples (nbk_edge_held_cloud_validity_batch) -> (valid (E,) bool, end
+        (E, n_q), n_samples (E,) int32).  ``pose``: ONE grasp (4, 4) for the call.  ``out`` / ``workspace``: as
+        ``cloud_edge_validity`` (``held_cloud_edge_workspace_bytes(E)``)."""
+        torch = _require_gpu()
+        h = self._held(held)
+        s, g, dd = self._stage_edges(starts, goals, dist)
+        gr, _ = self._grasp(torch, pose, s.B, False)
+        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
+        ws = (torch.empty((self.held_cloud_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device)
+              if workspace is None else workspace)
+        _lib.check(self._lib.nbk_edge_held_cloud_validity_batch(
+            self._h, h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
+            float(max_distance), _mode_int(mode), float(threshold), None if gr is None else gr.data_ptr(),
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            self._stream()), "nbk_edge_held_cloud_validity_batch")
+        return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
+
+    @staticmethod
+    def held_cloud_spline_workspace_bytes(S: int) -> int:
+        return int(_lib.load().nbk_spline_held_cloud_workspace_bytes(int(S)))
+
+    def held_cloud_spline_validity(self, held, cloud, ctrl, knots, degree, resolution, threshold=0.0, pose=None, out=None,
+                                   workspace=None):
+        """``spline_validity``'s trajectories for the held object against ``cloud`` ALONE (nbk_spline_held_cloud_validity_batch) ->
+        (valid (S,) bool, t_hit (S,), n_samples (S,) int32).  ``pose``: ONE grasp (4, 4) for the call.  ``out`` / ``workspace``: as
+        ``held_spline_validity`` (``held_cloud_spline_workspace_bytes(S)``)."""
+        torch = _require_gpu()
+        h = self._held(held)
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        gr, _ = self._grasp(torch, pose, S, False)
+        valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
+        ws = (torch.empty((self.held_cloud_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device)
+              if workspace is None else workspace)
+        _lib.check(self._lib.nbk_spline_held_cloud_validity_batch(
+            self._h, h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
+            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
+            ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_held_cloud_validity_batch")
+        if out is not None:
+            return valid, t_hit, ns
+        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+
     def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
         """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
         valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``)."""

@@ -19,6 +19,12 @@ where both are set.  Smoothed trajectories see the held object through a per-cal
 (``nbk_edge_held_continuous_batch`` / ``nbk_spline_held_continuous_batch``).  ``ContinuousConnector`` takes its cloud as a constructor argument
 (``ContinuousConnector(params, cloud=...)``: certified straight edges, ``nbk_edge_cloud_continuous_batch``) and still refuses params
 that carry one.
+Without ``ConnectorParams(attached_sees_cloud=True)`` the held object does NOT see the scan: with ``cloud=`` and ``attached=`` the
+three steps above run -- the scene's, the arm against the scan, the held object against world shapes and links -- and a box carried
+through a scanned wall is accepted.  With the flag (it needs ``arm``, ``cloud`` and ``attached``) the sampled edges, ``is_valid`` and
+``validate_trajectories(..., cloud=scan, attached=att)`` add a fourth step behind those three, the held object against the scan
+(``nbk_edge_held_cloud_validity_batch`` / ``nbk_held_cloud_validity_batch`` / ``nbk_spline_held_cloud_validity_batch``), accumulating
+into the same result.  ``ContinuousConnector`` refuses the flag: certified held-object checks do not see point clouds yet.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
 certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
 with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.  Its
@@ -54,6 +60,9 @@ class ConnectorParams:
     # additive: an Attachment (Arm.attach / World.add_constraint) -- the object in the hand, which the sampled edges and is_valid
     # must keep clear as well (at collision_threshold)
     attached: object = None
+    # additive: the held object must stay clear of the cloud as well (needs arm, cloud and attached).  Without it the held object
+    # does not see the scan
+    attached_sees_cloud: bool = False
 
     def __post_init__(self):
         if self.resolution <= 0:
@@ -70,6 +79,8 @@ class ConnectorParams:
             raise ValueError("A point cloud needs ConnectorParams(arm=...)")
         if self.attached is not None and self.arm is None:
             raise ValueError("A held object needs ConnectorParams(arm=...)")
+        if self.attached_sees_cloud and (self.arm is None or self.cloud is None or self.attached is None):
+            raise ValueError("attached_sees_cloud needs ConnectorParams(arm=..., cloud=..., attached=...)")
 
 
 def _scene_then_cloud(inputs, scene, cloud):
@@ -104,7 +115,8 @@ def _attachment(attached):
 
 
 def _then(*steps):
-    """The accumulating steps of ``_scene_then_cloud`` in order (the cloud's, then the held object's), those that are None left out."""
+    """The accumulating steps of ``_scene_then_cloud`` in order (the cloud's, then the held object's, then the held object's against
+    the cloud), those that are None left out."""
     steps = [f for f in steps if f is not None]
 
     def run(*args):
@@ -178,7 +190,8 @@ class DiscreteConnector(Connector):
             return False
         if p.cloud is not None and p.arm.in_collision_with_cloud(state, p.cloud, p.collision_threshold, p.cloud_ignore_links):
             return False
-        return p.attached is None or not p.arm.in_collision_with_attached(state, p.attached, p.collision_threshold)
+        return p.attached is None or not p.arm.in_collision_with_attached(
+            state, p.attached, p.collision_threshold, cloud=p.cloud if p.attached_sees_cloud else None)
 
     def _scalar(self, start, goal, mode, distance):
         """One edge, every sample in one device call (host arrays through the library's pinned staging)."""
@@ -203,13 +216,16 @@ class DiscreteConnector(Connector):
             return dev.edge_validity(starts, goals, p.resolution, p.max_distance, dist=dist, **kw)
         held = None if p.attached is None else p.attached._device(p.arm)[1]
 
-        # the cloud's verdict, then the held object's, are ANDed into the scene's `valid`
+        # the cloud's verdict, then the held object's (and, with attached_sees_cloud, the held object's against the cloud), are
+        # ANDed into the scene's `valid`
         def others(s, g, d, res):
             if p.cloud is not None:
                 dev.cloud_edge_validity(p.cloud, s, g, p.resolution, p.max_distance, dist=d,
                                         shapes=p.arm._cloud_shapes(sm, p.cloud_ignore_links), out=res[0], **kw)
             if held is not None:
                 dev.held_edge_validity(held, s, g, p.resolution, p.max_distance, dist=d, out=res[0], **kw)
+            if p.attached_sees_cloud:
+                dev.held_cloud_edge_validity(held, p.cloud, s, g, p.resolution, p.max_distance, dist=d, out=res[0], **kw)
         return _scene_then_cloud(
             (starts, goals, dist), lambda s, g, d: dev.edge_validity(s, g, p.resolution, p.max_distance, dist=d, **kw), others)
 
@@ -238,7 +254,11 @@ class DiscreteConnector(Connector):
                                                      shapes=p.arm._cloud_shapes(sm, links), out=res))
         hold = None if held is None else (
             lambda c, res: dev.held_spline_validity(held, c, knots, degree, p.resolution, threshold=p.collision_threshold, out=res))
-        return _scene_then_cloud((ctrl,), scene, _then(scan, hold))
+        # (attached_sees_cloud: the held object against the scan, where the call names both)
+        hold_scan = None if not (p.attached_sees_cloud and held is not None and cloud is not None) else (
+            lambda c, res: dev.held_cloud_spline_validity(held, cloud, c, knots, degree, p.resolution, threshold=p.collision_threshold,
+                                                          out=res))
+        return _scene_then_cloud((ctrl,), scene, _then(scan, hold, hold_scan))
 
     def _named_attachment(self, attached):
         """The attachment a trajectory call names: none while the params carry one is refused, as is another than the params' own."""
@@ -259,7 +279,9 @@ class DiscreteConnector(Connector):
         ``cloud_ignore_links`` (default: the params' own tuple).  A call that names no cloud is refused when the params carry one.
         ``attached`` (an ``Attachment``): the object in the hand is checked at the samples as well, after the scan
         (``nbk_spline_held_validity_batch`` accumulating into the same result).  A call that names no attachment is refused when
-        the params carry one, and so is one that names another than the params' own."""
+        the params carry one, and so is one that names another than the params' own.  With
+        ``ConnectorParams(attached_sees_cloud=True)`` a call that names both adds the held object against the scan
+        (``nbk_spline_held_cloud_validity_batch``) behind those steps; without the flag the held object does not see the scan."""
         attached = self._named_attachment(attached)
         if cloud is None:
             _no_cloud(self._params, "sampled trajectory checks")
@@ -349,6 +371,8 @@ class ContinuousConnector(Connector):
             raise ValueError("max_iter must be at least 1")
         if not slack >= 0.0:
             raise ValueError("slack must be non-negative")
+        if params.attached_sees_cloud:
+            raise ValueError("certified held-object checks do not see point clouds yet")
         _no_cloud(params, "certified continuous checks")
         _no_held(params, "certified continuous checks")
         device_edge = params.arm is not None and params.validity_checker is None and params.trajectory_func is _DEFAULT_TRAJ

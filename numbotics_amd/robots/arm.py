@@ -603,19 +603,38 @@ class Arm(Robot):
         att.spec(self)                                          # argument errors now, not at the first query
         return att
 
-    def in_collision_with_attached(self, q, att, threshold: float = 0.0, pose=None):
+    def in_collision_with_attached(self, q, att, threshold: float = 0.0, pose=None, cloud=None):
         """Is the held object of ``att`` (``attach`` / ``World.add_constraint``) closer than ``threshold`` to a world shape or a
         link it is paired with?  ``(dof,)`` -> bool, ``(..., dof)`` -> bool array / tensor, like ``in_collision_with_cloud``.  This
         is the held object's verdict ONLY: full validity is ``arm.in_collision(q) | arm.in_collision_with_attached(q, att)``, and
         ``in_collision`` still sees the object's world copy where that is an obstacle of this arm.  ``pose``: another grasp for
-        this call, (4, 4), or one per configuration (B, 4, 4) -- NumPy or a float64 CUDA tensor."""
+        this call, (4, 4), or one per configuration (B, 4, 4) -- NumPy or a float64 CUDA tensor.  ``cloud`` (a ``PointCloud``):
+        the held object's verdict against the scan is ORed in (``DeviceModel.held_cloud_validity``); without it the held object
+        does not see a scan."""
         if q.shape[-1] != self.dof:
             raise ValueError(f"q must have {self.dof} elements")
         dev, held = att._device(self)
+        rows = q.reshape(-1, self.dof)
+        mask = dev.held_validity(held, rows, threshold, pose=pose)
+        if cloud is not None:
+            mask = mask | dev.held_cloud_validity(held, cloud, rows, threshold, pose=pose)
         if q.ndim == 1:
-            return bool(dev.held_validity(held, q.reshape(1, -1), threshold, pose=pose)[0])
-        mask = dev.held_validity(held, q.reshape(-1, self.dof), threshold, pose=pose)
+            return bool(mask[0])
         return mask.reshape(tuple(q.shape[:-1]))
+
+    def attached_cloud_clearance(self, q, att, cloud, d_max: float, pose=None):
+        """How close is the held object of ``att`` to ``cloud``?  -> (distance, held shape index, point index): the smallest signed
+        distance below ``d_max`` with the held shape and the point (its index in the cloud's last update) that attain it, or
+        (inf, -1, -1) where nothing is nearer than ``d_max``; NaN, -1, -1 for a row or grasp that is not finite or while the
+        cloud's status is set.  ``(dof,)`` -> (float, int, int); ``(B, dof)`` -> arrays / tensors (B,).  ``pose``: as
+        ``in_collision_with_attached``."""
+        if q.shape[-1] != self.dof:
+            raise ValueError(f"q must have {self.dof} elements")
+        dev, held = att._device(self)
+        d, sh, pt = dev.held_cloud_clearance(held, cloud, q.reshape(-1, self.dof), d_max, pose=pose)
+        if q.ndim == 1:
+            return float(d[0]), int(sh[0]), int(pt[0])
+        return d, sh, pt
 
     def attached_clearance(self, q, att, pose=None):
         """How close is the held object of ``att`` to what it is paired with?  -> (distance, item): the smallest signed distance
