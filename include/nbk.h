@@ -985,6 +985,54 @@ int32_t nbk_spline_held_cloud_validity_batch(const nbk_model *m, const nbk_held 
                                              int32_t *n_samples /* optional */, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Certified continuous checks of the held object against a point cloud: nbk_edge_cloud_continuous_batch /
+ * nbk_spline_cloud_continuous_batch with the held shapes in the robot shapes' place.  One (trajectory, held shape h) item per lane,
+ * grid (ceil(E / 64), H): a wave holds one held shape.  The item's motion bound is mu_h, the bound of held shape h over EVERY joint
+ * of the holding path (the cloud stands still; nbk_edge_held_shape_motion_bounds_host / nbk_spline_held_shape_motion_bounds_host
+ * run the device's routine on the host with the stored G, no GPU needed: mu [E][H] / [S][n_ctrl-degree][H], 0 on empty spans; the
+ * held arguments are nbk_held_create's without the world list and the robot set).  Its distance at t is the clearance of held shape
+ * h alone against the cloud at q(t), cut at  D = min(D_end, D_cap),  D_end = (threshold + slack) + mu_h (T_f - t)  (a spline:
+ * mu_max (1 - t), mu_max the largest bound over the trajectory's non-empty spans),  D_cap = (threshold + slack) + look_ahead:  the
+ * smallest distance below D where there is one; else +inf when D == D_end -- the item stops FREE at its stop point -- else D_cap, a
+ * lower bound the advance may use.  The result is bit for bit that of nbk_edge_cloud_continuous_batch /
+ * nbk_spline_cloud_continuous_batch on a descriptor that holds the held shapes as robot shapes S+h of `frame`, selected on exactly
+ * those shapes.
+ *
+ * This is the held-versus-cloud term ALONE, as for the four sampled entries above: no world shape and no link takes part, the world
+ * status of a movable descriptor is not read, and world_shapes / robot_bits of nbk_held_create play no part.  valid / end / t_free /
+ * status, max_distance / mode / dist, max_iter / slack and look_ahead as nbk_edge_cloud_continuous_batch.  accumulate != 0: valid /
+ * t_free / status hold the result of a certified call on the same trajectories (the scene's, the cloud's, the held object's) and
+ * this term is folded into it -- the smallest stop point, COLLISION winning a tie; a trajectory that comes in with a NaN t_free
+ * stays 0 / NaN / UNDECIDED.  grasp (device, optional) [16]: ONE grasp for the call, read when the kernels run (a captured graph is
+ * re-grasped by rewriting it); NULL = the stored G.  An empty cloud leaves every non-degenerate trajectory FREE at its stop point; a
+ * set cloud status, or a grasp that is not finite, makes every non-degenerate trajectory 0 / NaN / UNDECIDED.
+ *
+ * Argument rules, answered before any device is touched: NBK_ERR_INVALID for a null m / held / cloud, E < 0 (S < 0), a null starts /
+ * goals / ctrl / knots / valid / t_free / status with trajectories to check, a mode outside {0, 1}, a NaN threshold, max_iter < 1,
+ * slack < 0 or NaN, and look_ahead that is not > 0 (NaN included; +inf is served); E == 0 returns NBK_OK; E > 2^31 - 1 is
+ * NBK_ERR_UNSUPPORTED.  Then the held object must have been made against `m`, and it, the cloud and the descriptor must be on the
+ * current device.  No workspace (the keys live in t_free while the call runs), no allocation, one linear chain of kernels on the
+ * caller's stream, capturable; LDS holds the q rows only.
+ */
+int32_t nbk_edge_held_cloud_continuous_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *starts,
+                                             const double *goals, const double *dist /* optional */, int64_t E, double max_distance,
+                                             int32_t mode, double threshold, int32_t max_iter, double slack, double look_ahead,
+                                             const double *grasp /* DEVICE [16] or NULL */, int32_t accumulate, uint8_t *valid,
+                                             double *end /* optional */, double *t_free, int32_t *status, void *stream);
+int32_t nbk_spline_held_cloud_continuous_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *ctrl,
+                                               int64_t S, int32_t n_ctrl, int32_t degree, const double *knots /* DEVICE */,
+                                               double threshold, int32_t max_iter, double slack, double look_ahead,
+                                               const double *grasp /* DEVICE [16] or NULL */, int32_t accumulate, uint8_t *valid,
+                                               double *t_free, int32_t *status, void *stream);
+int32_t nbk_edge_held_shape_motion_bounds_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                               const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                               const double *starts, const double *goals, int64_t E, double *mu /* [E][H] */);   /* no GPU */
+int32_t nbk_spline_held_shape_motion_bounds_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                                 const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                                 const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                                 const double *knots /* host */, double *mu /* [S][n_ctrl-degree][H] */);   /* no GPU */
+
+/*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists
  * an insert-then-query loop over the reference's flat L2 index yields (numbotics/math/geometry/nearest_neighbors.py:6-85,
  * numbotics/planning/sampling_based/graph.py:165-178; faiss.IndexFlatL2 is a third-party dependency: tie-breaking and

@@ -50,6 +50,8 @@ SYMBOLS = [
     "nbk_held_cloud_validity_batch", "nbk_held_cloud_clearance_batch",
     "nbk_edge_held_cloud_workspace_bytes", "nbk_edge_held_cloud_validity_batch",
     "nbk_spline_held_cloud_workspace_bytes", "nbk_spline_held_cloud_validity_batch",
+    "nbk_edge_held_cloud_continuous_batch", "nbk_spline_held_cloud_continuous_batch",
+    "nbk_edge_held_shape_motion_bounds_host", "nbk_spline_held_shape_motion_bounds_host",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -205,6 +207,12 @@ def load():
     lib.nbk_spline_held_cloud_workspace_bytes.argtypes = [i64]
     lib.nbk_spline_held_cloud_workspace_bytes.restype = i64
     lib.nbk_spline_held_cloud_validity_batch.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, f64, f64, vp, i32, vp, vp, vp, vp, i64, vp]
+    lib.nbk_edge_held_cloud_continuous_batch.argtypes = [vp, vp, vp, vp, vp, vp, i64, f64, i32, f64, i32, f64, f64, vp, i32, vp, vp, vp, vp,
+                                                         vp]
+    lib.nbk_spline_held_cloud_continuous_batch.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, f64, i32, f64, f64, vp, i32, vp, vp, vp, vp]
+    held_shape_args = held_args[:8]                                                     # (no world list, no robot set)
+    lib.nbk_edge_held_shape_motion_bounds_host.argtypes = held_shape_args + [vp, vp, i64, vp]
+    lib.nbk_spline_held_shape_motion_bounds_host.argtypes = held_shape_args + [vp, i64, i32, i32, vp, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

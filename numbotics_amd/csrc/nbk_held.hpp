@@ -711,6 +711,193 @@ __global__ __launch_bounds__(64) void k_held_spline_ca(DevModel m, HeldDev hd, c
     ca_walk(m, tr, run, it, it, lane, thr, max_iter, slack, key + s);
 }
 
+// ---- certified continuous checks of the held object against a point cloud (nbk_edge_held_cloud_continuous_batch,
+// nbk_spline_held_cloud_continuous_batch): ca_walk as it is, on one (trajectory, held shape h) item per lane (ca_walk's pu and p are
+// both h).  The grid is (ceil(E / 64), H) with blockIdx.y = h: a wave holds ONE held shape, so Core.kind is wave-uniform as
+// cloud_core_clearance needs it (a flat item-major index, as in k_held_edge_ca, would straddle shapes).  LDS: [64][n_q] q rows and
+// nothing else.  The init and final kernels are the scene's (hold = the cloud's status, prev when accumulating); k_held_ca_hold,
+// behind the init, gives CA_KEEP_KEY to every non-degenerate trajectory when the call's grasp is not finite -- the world status is
+// not read.  This is the held-versus-cloud term ALONE, as for the sampled kernels above: no world shape and no link takes part.
+//
+// The distance half is CloudEdgeLane's with held_core in build_core's place, the frame and core construction k_held_cloud_clearance's.
+// The item's motion bound is mu_h = motion_terms over every joint of the holding path (the cloud stands still: the world-item branch
+// of held_item_motion_bound, per held shape), and its distance at t the clearance of held shape h ALONE against the cloud at q(t),
+// cut at
+//     D = min(D_end, D_cap),   D_end = (thr + slack) + mu_h (T_f - t),   D_cap = (thr + slack) + look_ahead:
+// the smallest distance below D where there is one; else +inf when D == D_end, else D_cap.  Soundness:
+//   * every point of held shape h moves at most mu_h |t' - t| between q(t) and q(t'), and the points of the cloud stand still;
+//   * so no point within D_end at t means that the distance stays above thr + slack up to T_f: the item may stop FREE at T_f, which
+//     is what ca_walk makes of +inf (gap is infinite, the advance reaches hi = T_f) -- no new branch;
+//   * a distance >= D_cap reported as D_cap is a lower bound of it, and advancing on a lower bound is conservative.
+// look_ahead bounds the ball a step walks, and so the points a lane meets: without it the first step of a long edge walks the whole
+// cloud.  k_edge_ca_init gives CA_KEEP_KEY to the edges whose items do not run and whose result is 0 / UNDECIDED / NaN: every
+// non-degenerate edge while the cloud's status is set, and -- accumulating -- those that come in with a NaN t_free.
+
+// the distance of held shape h from the cloud at the lane's staged row, cut at D (D_end: the cut that reaches the stop point); the
+// frame, A . G and the core are formed here, only where ok, and die here: none of them is carried round ca_walk's loop
+NBK_DEV double held_cloud_cut_distance(const DevModel& m, const HeldDev& hd, const CloudDev& cd, const double* grow, double radius,
+                                       const double* myq, bool ok, int h, double D_end, double d_cap) {
+    Core P;
+    cloud_point_core(radius, P);
+    Core Hc;
+    cloud_core_init(Hc);
+    double D = 0.0;
+    if (ok) {
+        Xf F;
+        held_frame(m, hd.mask, myq, F);
+        double G[12], AG[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) G[e] = grow[e];
+        held_mul12(hd.tab, G, AG);
+        held_core(hd, h, F, AG, Hc);
+        D = D_end < d_cap ? D_end : d_cap;
+    }
+    double best = NBK_INF;
+    int bs = -1, bi = -1;
+    cloud_core_clearance(cd, Hc, P, radius, ok, 0, D, best, bs, bi);
+    if (!ok) return __builtin_nan("");
+    if (best < D) return best;
+    return D == D_end ? NBK_INF : d_cap;
+}
+
+// the linear edge of EdgeLane for one held shape against the cloud
+struct HeldCloudEdgeLane {
+    const double* s;
+    const double* g;
+    double Tf;
+    const HeldDev& hd;
+    const CloudDev& cd;
+    const double* grow;       // the call's grasp row
+    double radius;            // of the cloud's points
+    double* myq;              // the lane's LDS row
+    double d_base, d_cap;     // thr + slack; (thr + slack) + look_ahead
+    double mu;
+    NBK_DEV double end() const { return Tf; }
+    NBK_DEV double span_end() const { return Tf; }
+    NBK_DEV double enter(const DevModel& m, int h, double) {
+        const MotionShape hs = held_motion_shape(hd.mask, hd.tab, grow, h);
+        mu = motion_terms(m.mt, hs, hs.mask, EdgeMotion{s, g}, 0.0);
+        return mu;
+    }
+    NBK_DEV double distance(const DevModel& m, bool run, int h, int, double t, double*) {
+        bool ok = false;
+        if (run) {
+            const double omt = 1.0 - t;
+            for (int c = 0; c < m.n_q; ++c) { const double a = omt * s[c]; const double b = t * g[c]; myq[c] = a + b; }
+            ok = !row_nonfinite(myq, m.n_q, 1);      // (a non-finite q(t) is answered NaN without a walk: the item stops UNDECIDED there)
+        }
+        return held_cloud_cut_distance(m, hd, cd, grow, radius, myq, ok, h, ok ? d_base + mu * (Tf - t) : 0.0, d_cap);
+    }
+};
+
+__global__ __launch_bounds__(64) void k_held_cloud_edge_ca(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ starts,
+                                                           const double* __restrict__ goals, const double* __restrict__ dist, int64_t E,
+                                                           double max_distance, int mode, const double* __restrict__ grasp, double thr,
+                                                           int max_iter, double slack, double look_ahead,
+                                                           unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int h = (int)blockIdx.y;
+    if (h >= hd.n_shapes) return;
+    const int n = cd.hdr->n;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < E;
+    const int64_t e = live ? i : 0;
+    const double base = thr + slack;
+    HeldCloudEdgeLane tr{starts + e * m.n_q, goals + e * m.n_q, 0.0, hd, cd, grasp != nullptr ? grasp : hd.tab + 12, cd.hdr->radius,
+                         lds + lane * m.n_q, base, base + look_ahead, 0.0};
+    double d_edge = 0.0;
+    // (an empty cloud stops every item FREE at T_f, which is where its key stands; the keys of a cloud whose status is set, or of a
+    // grasp that is not finite, are all reserved)
+    const bool run = live && n > 0 && edge_span(m.n_q, tr.s, tr.g, dist, e, max_distance, mode, d_edge, tr.Tf) &&
+                     __hip_atomic_load(key + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != CA_KEEP_KEY;
+    ca_walk(m, tr, run, h, h, lane, thr, max_iter, slack, key + e);
+}
+
+// SplineLane's trajectory with HeldCloudEdgeLane's distance: entering a span gives mu_h on that span, q(t) goes by de_boor into the
+// lane's LDS row, and the distance is the held shape's clearance from the cloud cut at
+//     D = min(D_end, D_cap),   D_end = (thr + slack) + mu_max (1 - t),   D_cap = (thr + slack) + look_ahead,
+// the smallest distance below D where there is one; else +inf when D == D_end; else D_cap.  mu_max is the LARGEST span bound of the
+// trajectory over its non-empty spans, formed once per lane before the walk (bound_all), not the current span's.  Soundness of the
+// +inf, as at CloudSplineLane:
+//   * ca_walk carries an infinite gap across ALL remaining spans without another evaluation (gap - mu (hi - t) stays infinite), so
+//     +inf at t stops the item FREE at 1: it may only be reported when no point can be reached on the whole remainder [t, 1];
+//   * each span's mu bounds the speed of every point of the held shape on that span, so mu_max bounds it on every span, and no point
+//     of the shape travels further than mu_max (1 - t) between q(t) and any q(t'), t' in [t, 1]; the cloud stands still;
+//   * so no point within D_end at t means that the distance stays above thr + slack up to 1;
+//   * D_cap is a lower bound of a distance that is not below it, and advancing on a lower bound is conservative, span by span with
+//     each span's own mu.
+// With n = 2, K = 1 and the knots [0, 0, 1, 1] there is one span, mu_max = mu and T_f = 1: HeldCloudEdgeLane's bits in connect mode.
+template <int K>
+struct HeldCloudSplineLane {
+    const double* c;          // control points of the trajectory, [n][nq]
+    const double* knots;
+    int n, nq, ell;
+    const HeldDev& hd;
+    const CloudDev& cd;
+    const double* grow;       // the call's grasp row
+    double radius;            // of the cloud's points
+    double* myq;              // the lane's LDS row
+    double d_base, d_cap;     // thr + slack; (thr + slack) + look_ahead
+    double mu_max;
+    NBK_DEV double end() const { return 1.0; }
+    NBK_DEV double span_end() const { return knots[ell + 1]; }
+    NBK_DEV double span_bound(const DevModel& m, int h, int span) const {
+        const MotionShape hs = held_motion_shape(hd.mask, hd.tab, grow, h);
+        return motion_terms(m.mt, hs, hs.mask, SplineSpanMotion{c + (size_t)(span - K) * nq, knots + (span - K + 1), nq, K}, 0.0);
+    }
+    NBK_DEV double enter(const DevModel& m, int h, double t) {
+        ell = spline_span<K>(knots, n, t);
+        return span_bound(m, h, ell);
+    }
+    // the largest bound over the non-empty spans: what D_end may use (see above)
+    NBK_DEV void bound_all(const DevModel& m, int h) {
+        mu_max = 0.0;
+        for (int span = K; span < n; ++span) {
+            if (!(knots[span] < knots[span + 1])) continue;
+            const double mu = span_bound(m, h, span);
+            mu_max = mu > mu_max ? mu : mu_max;
+        }
+    }
+    NBK_DEV double distance(const DevModel& m, bool run, int h, int, double t, double*) {
+        bool ok = false;
+        if (run) {
+            double* r = myq;
+            de_boor<K>(nq, c + (size_t)(ell - K) * nq, knots, ell, t, [&](int j, double v) { r[j] = v; });
+            ok = !row_nonfinite(myq, nq, 1);
+        }
+        // mu_max, NOT the current span's mu: +inf frees the item up to 1 across every later span (ca_walk evaluates nothing there),
+        // and a later span may be faster than this one
+        return held_cloud_cut_distance(m, hd, cd, grow, radius, myq, ok, h, ok ? d_base + mu_max * (1.0 - t) : 0.0, d_cap);
+    }
+};
+
+template <int K>
+__global__ __launch_bounds__(64) void k_held_cloud_spline_ca(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ ctrl, int64_t S,
+                                                             int n, const double* __restrict__ knots, const double* __restrict__ grasp,
+                                                             double thr, int max_iter, double slack, double look_ahead,
+                                                             unsigned long long* __restrict__ key) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int h = (int)blockIdx.y;
+    if (h >= hd.n_shapes) return;
+    const int ncl = cd.hdr->n;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const bool live = i < S;
+    const int64_t s = live ? i : 0;
+    const double base = thr + slack;
+    HeldCloudSplineLane<K> tr{ctrl + (size_t)s * (size_t)n * m.n_q, knots, n, m.n_q, K, hd, cd, grasp != nullptr ? grasp : hd.tab + 12,
+                              cd.hdr->radius, lds + lane * m.n_q, base, base + look_ahead, 0.0};
+    // (an empty cloud stops every item FREE at 1, which is where its key stands)
+    bool run = false;
+    if (live && ncl > 0) {
+        const unsigned long long k0 = __hip_atomic_load(key + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        run = k0 != CA_DEGENERATE_KEY && k0 != CA_KEEP_KEY;
+    }
+    if (run) tr.bound_all(m, h);
+    ca_walk(m, tr, run, h, h, lane, thr, max_iter, slack, key + s);
+}
+
 }  // namespace nbk
 
 struct nbk_held {
@@ -1180,6 +1367,66 @@ int32_t nbk_spline_held_cloud_validity_batch(const nbk_model* m, const nbk_held*
     return NBK_OK;
 }
 
+// the hold of the certified held-versus-cloud entries, behind the scene's init kernel: the call's grasp alone (the stored one is
+// finite by nbk_held_create's rules, and the world status is not read)
+static int32_t launch_held_cloud_ca_hold(hipStream_t st, const double* grasp, int64_t n, double* t_free) {
+    if (grasp == nullptr) return NBK_OK;
+    hipLaunchKernelGGL(k_held_ca_hold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int*)nullptr, grasp, n, ca_keys(t_free));
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_edge_held_cloud_continuous_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* starts,
+                                             const double* goals, const double* dist, int64_t E, double max_distance, int32_t mode,
+                                             double threshold, int32_t max_iter, double slack, double look_ahead, const double* grasp,
+                                             int32_t accumulate, uint8_t* valid, double* end, double* t_free, int32_t* status,
+                                             void* stream) {
+    // (the argument rules are answered without a device)
+    if (m == nullptr || held == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
+    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, &c->hdr->status, accumulate ? status : nullptr, end, t_free);
+      if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_held_cloud_ca_hold(st, grasp, E, t_free); if (rc != NBK_OK) return rc; }
+    hipLaunchKernelGGL(k_held_cloud_edge_ca, dim3(blocks_for(E), (unsigned)held->d.n_shapes), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d,
+                       held->d, cloud_dev(c), starts, goals, dist, E, max_distance, (int)mode, grasp, threshold, (int)max_iter, slack,
+                       look_ahead, ca_keys(t_free));
+    NBK_HIP(hipGetLastError());
+    return launch_ca_final(st, E, valid, t_free, status);
+}
+
+int32_t nbk_spline_held_cloud_continuous_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* ctrl, int64_t S,
+                                               int32_t n_ctrl, int32_t degree, const double* knots, double threshold, int32_t max_iter,
+                                               double slack, double look_ahead, const double* grasp, int32_t accumulate, uint8_t* valid,
+                                               double* t_free, int32_t* status, void* stream) {
+    // (the argument rules are answered without a device)
+    if (m == nullptr || held == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
+    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
+    if (S == 0) return NBK_OK;
+    if (S > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, &c->hdr->status, accumulate ? status : nullptr, t_free);
+      if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_held_cloud_ca_hold(st, grasp, S, t_free); if (rc != NBK_OK) return rc; }
+    const dim3 grid(blocks_for(S), (unsigned)held->d.n_shapes), block(WAVE);
+    const size_t lds = QSlabLds(m->n_q).bytes();
+    with_degree(degree, [&](auto K) {
+        hipLaunchKernelGGL(k_held_cloud_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, held->d, cloud_dev(c), ctrl, S,
+                           (int)n_ctrl, knots, grasp, threshold, (int)max_iter, slack, look_ahead, ca_keys(t_free));
+    });
+    NBK_HIP(hipGetLastError());
+    return launch_ca_final(st, S, valid, t_free, status);
+}
+
 // ---- the host twins of the held motion bound: held_item_motion_bound on the tables motion_tables makes of the descriptor, the
 // items in held_item_list's order (robot_bits in the descriptor's numbering); no GPU
 static int32_t held_motion_host_begin(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
@@ -1245,6 +1492,59 @@ int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc* d, int32_t fram
             const SplineSpanMotion tr{c + (size_t)(ell - k) * nq, knots + (ell - k + 1), nq, k};
             for (int64_t i = 0; i < K; ++i)
                 out[i] = span ? held_item_motion_bound(t, mask, tab.data(), tab.data() + 12, &items[HELD_ITEM_LEN * (size_t)i], tr) : 0.0;
+        }
+    }
+    return NBK_OK;
+}
+
+// ---- the host twins of the per-shape bound the held-versus-cloud lanes advance with: motion_terms over the whole holding path for
+// each held shape (HeldCloudEdgeLane::enter, HeldCloudSplineLane::span_bound), with the stored grasp G; no item list, no GPU
+int32_t nbk_edge_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                               const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                               const double* starts, const double* goals, int64_t E, double* mu) {
+    if (E < 0) return NBK_ERR_INVALID;
+    MotionHost mh;
+    unsigned mask = 0u;
+    std::vector<double> tab;
+    std::vector<int> items;
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, 0, nullptr, nullptr, mh, mask, tab, items);
+      if (rc != NBK_OK) return rc; }
+    if (E == 0) return NBK_OK;
+    if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
+    const MotionTab t = mh.view(d->n_joints, d->n_rshapes);
+    for (int64_t e = 0; e < E; ++e)
+        for (int32_t h = 0; h < H; ++h) {
+            const MotionShape hs = held_motion_shape(mask, tab.data(), tab.data() + 12, h);
+            mu[e * H + h] = motion_terms(t, hs, hs.mask, EdgeMotion{starts + e * d->n_q, goals + e * d->n_q}, 0.0);
+        }
+    return NBK_OK;
+}
+
+int32_t nbk_spline_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                                 const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                                 const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
+                                                 double* mu) {
+    if (S < 0 || !spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;
+    MotionHost mh;
+    unsigned mask = 0u;
+    std::vector<double> tab;
+    std::vector<int> items;
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, 0, nullptr, nullptr, mh, mask, tab, items);
+      if (rc != NBK_OK) return rc; }
+    const int nq = d->n_q, k = degree, L = n_ctrl - degree;
+    if (S == 0) return NBK_OK;
+    if (ctrl == nullptr || knots == nullptr || mu == nullptr || !spline_args_ok(n_ctrl, degree, knots)) return NBK_ERR_INVALID;
+    const MotionTab t = mh.view(d->n_joints, d->n_rshapes);
+    for (int64_t s = 0; s < S; ++s) {
+        const double* c = ctrl + (size_t)s * (size_t)n_ctrl * nq;
+        for (int ell = k; ell < n_ctrl; ++ell) {
+            double* out = mu + ((size_t)s * L + (size_t)(ell - k)) * H;
+            const bool span = knots[ell] < knots[ell + 1];
+            const SplineSpanMotion tr{c + (size_t)(ell - k) * nq, knots + (ell - k + 1), nq, k};
+            for (int32_t h = 0; h < H; ++h) {
+                const MotionShape hs = held_motion_shape(mask, tab.data(), tab.data() + 12, h);
+                out[h] = span ? motion_terms(t, hs, hs.mask, tr, 0.0) : 0.0;
+            }
         }
     }
     return NBK_OK;

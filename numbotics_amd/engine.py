@@ -1049,6 +1049,51 @@ class DeviceModel:
             return valid, t_hit, ns
         return c.out(valid.bool()), c.out(t_hit), c.out(ns)
 
+    def held_cloud_edge_continuous(self, held, cloud, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64,
+                                   slack=1e-6, look_ahead=CLOUD_LOOK_AHEAD, dist=None, pose=None, out=None):
+        """``edge_continuous``'s edges certified for the held object ``held`` against ``cloud`` ALONE
+        (nbk_edge_held_cloud_continuous_batch): one (edge, held shape) item per lane advances by conservative advancement on the held
+        shape's clearance from the cloud -> valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``).  No world
+        shape and no link takes part.  Bit for bit ``cloud_edge_continuous`` of a descriptor that holds the held shapes as robot
+        shapes, selected on those shapes.  ``look_ahead``: as ``cloud_edge_continuous``.  ``pose``: ONE grasp (4, 4) for the call, as
+        ``held_edge_continuous``'s; a non-finite one, or a set cloud status, gives 0 / NaN / UNDECIDED; an empty cloud leaves every
+        edge FREE at its stop point.  ``out``: the CUDA tensors (valid, t_free, status) of an earlier certified call on the same
+        edges, mode, max_distance and dist (``edge_continuous``, then ``cloud_edge_continuous(..., out=...)`` and
+        ``held_edge_continuous(..., out=...)``): these items are reduced INTO them."""
+        torch = _require_gpu()
+        h = self._held(held)
+        s, g, dd = self._stage_edges(starts, goals, dist)
+        gr, _ = self._grasp(torch, pose, s.B, False)
+        valid, t_free, status = self._result_triple(torch, out, s.B, s.device, "(valid, t_free, status)")
+        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
+        _lib.check(self._lib.nbk_edge_held_cloud_continuous_batch(
+            self._h, h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
+            _mode_int(mode), float(threshold), int(max_iter), float(slack), float(look_ahead),
+            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
+            status.data_ptr(), self._stream()), "nbk_edge_held_cloud_continuous_batch")
+        if out is not None:
+            return valid, s.out(end), t_free, status
+        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
+
+    def held_cloud_spline_continuous(self, held, cloud, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6,
+                                     look_ahead=CLOUD_LOOK_AHEAD, pose=None, out=None):
+        """``spline_continuous``'s trajectories certified for the held object ``held`` against ``cloud`` ALONE
+        (nbk_spline_held_cloud_continuous_batch) -> valid (S,) bool, t_free (S,), status (S,) int32.  ``look_ahead`` / ``pose`` /
+        ``out``: as ``held_cloud_edge_continuous``, ``out`` being what an earlier certified spline call returned for the same
+        trajectories."""
+        torch = _require_gpu()
+        h = self._held(held)
+        c, kn, S, n = self._stage_splines(ctrl, knots, degree)
+        gr, _ = self._grasp(torch, pose, S, False)
+        valid, t_free, status = self._result_triple(torch, out, S, c.device, "(valid, t_free, status)")
+        _lib.check(self._lib.nbk_spline_held_cloud_continuous_batch(
+            self._h, h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
+            float(look_ahead), None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_free.data_ptr(),
+            status.data_ptr(), self._stream()), "nbk_spline_held_cloud_continuous_batch")
+        if out is not None:
+            return valid, t_free, status
+        return c.out(valid.bool()), c.out(t_free), c.out(status)
+
     def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
         """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
         valid (E,) bool, end (E, n_q), t_free (E,), status (E,) int32 (``_lib.CA_*``)."""
@@ -1274,6 +1319,49 @@ def held_spline_motion_bounds(model, spec, ctrl, knots, degree, G=None):
     mu = np.zeros((S, n - k, K), dtype=np.float64)
     _lib.check(_lib.load().nbk_spline_held_motion_bounds_host(C.byref(d), *args, c.ctypes.data, S, n, k, kn.ctypes.data, mu.ctypes.data),
                "nbk_spline_held_motion_bounds_host")
+    del keep, keep2
+    return mu
+
+
+def held_edge_shape_motion_bounds(model, spec, starts, goals, G=None):
+    """Motion bounds mu (E, H) of the linear edges starts -> goals for the H shapes of the held object ``spec`` (a ``HeldSpec``) on
+    the SceneModel ``model``, every joint of the holding path counting: the bits ``edge_shape_motion_bounds`` gives for robot shapes
+    S .. S+H-1 on a model that holds the held shapes as robot shapes.  The routine nbk_edge_held_cloud_continuous_batch advances
+    with, run on the host (nbk_edge_held_shape_motion_bounds_host); no GPU needed.  ``G``: the grasp (default: the spec's)."""
+    n_q = model.kin.n_q
+    s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64)).reshape(-1, n_q)
+    g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64)).reshape(-1, n_q)
+    if s.shape != g.shape:
+        raise ValueError("starts and goals must have the same shape")
+    d, keep = model_desc(model)
+    args, keep2, _ = _held_host_args(model, spec, G)
+    H = args[3]
+    mu = np.empty((s.shape[0], H), dtype=np.float64)
+    _lib.check(_lib.load().nbk_edge_held_shape_motion_bounds_host(C.byref(d), *args[:7], s.ctypes.data, g.ctypes.data, s.shape[0],
+                                                                  mu.ctypes.data), "nbk_edge_held_shape_motion_bounds_host")
+    del keep, keep2
+    return mu
+
+
+def held_spline_shape_motion_bounds(model, spec, ctrl, knots, degree, G=None):
+    """Motion bounds mu (S, n - degree, H) of S clamped B-splines for the H shapes of the held object ``spec``, per knot span: the
+    bits ``spline_shape_motion_bounds`` gives for robot shapes S .. S+H-1 on a model that holds the held shapes as robot shapes
+    (nbk_spline_held_shape_motion_bounds_host; no GPU needed).  Entries of empty spans are 0."""
+    n_q = model.kin.n_q
+    c = np.ascontiguousarray(np.asarray(ctrl, dtype=np.float64))
+    if c.ndim != 3 or c.shape[2] != n_q:
+        raise ValueError(f"control points must have shape (S, n, {n_q}), got {c.shape}")
+    S, n = c.shape[:2]
+    k = int(degree)
+    if not 1 <= k < n:
+        raise ValueError("degree must be at least 1 and less than the number of control points")
+    kn = _host_f64(knots, n + k + 1)
+    d, keep = model_desc(model)
+    args, keep2, _ = _held_host_args(model, spec, G)
+    H = args[3]
+    mu = np.zeros((S, n - k, H), dtype=np.float64)
+    _lib.check(_lib.load().nbk_spline_held_shape_motion_bounds_host(C.byref(d), *args[:7], c.ctypes.data, S, n, k, kn.ctypes.data,
+                                                                    mu.ctypes.data), "nbk_spline_held_shape_motion_bounds_host")
     del keep, keep2
     return mu
 

@@ -24,7 +24,11 @@ three steps above run -- the scene's, the arm against the scan, the held object 
 through a scanned wall is accepted.  With the flag (it needs ``arm``, ``cloud`` and ``attached``) the sampled edges, ``is_valid`` and
 ``validate_trajectories(..., cloud=scan, attached=att)`` add a fourth step behind those three, the held object against the scan
 (``nbk_edge_held_cloud_validity_batch`` / ``nbk_held_cloud_validity_batch`` / ``nbk_spline_held_cloud_validity_batch``), accumulating
-into the same result.  ``ContinuousConnector`` refuses the flag: certified held-object checks do not see point clouds yet.
+into the same result.  ``ContinuousConnector`` refuses the flag on the params ("certified held-object checks do not see point clouds
+yet") and takes it as a constructor argument, ``ContinuousConnector(params, cloud=scan, attached=att, attached_sees_cloud=True)``:
+its edges then certify the held object against the scan as a fourth step (``nbk_edge_held_cloud_continuous_batch``), ``is_valid`` asks
+for it, and ``validate_trajectories(..., cloud=scan)`` adds ``nbk_spline_held_cloud_continuous_batch``.  Without the constructor flag
+a certified edge still ignores held-versus-scan.
 ``ContinuousConnector`` (connectors.py:108-185) replaces the reference's SciPy SLSQP search per sub-interval with a
 certified check on the device (conservative advancement, ``nbk_edge_continuous_batch``) when the params carry an ``arm``;
 with only a Python ``validity_checker`` (a signed distance) it runs a host SLSQP search of its own.  Its
@@ -363,10 +367,19 @@ class ContinuousConnector(Connector):
     -- reduces one (edge, held item) per lane into the same result after the cloud's (``nbk_edge_held_continuous_batch``), ``is_valid``
     asks ``in_collision_with_attached`` as well, and the trajectory methods certify the held object by default
     (``nbk_spline_held_continuous_batch``; ``attached=`` names another per call).  It is an argument of this constructor for the
-    cloud's reason, with the cloud's requirements; ``ConnectorParams(attached=...)`` keeps being refused here."""
+    cloud's reason, with the cloud's requirements; ``ConnectorParams(attached=...)`` keeps being refused here.
+
+    ``attached_sees_cloud`` (default False; it needs ``cloud`` and ``attached``): the held object is certified against the scan as
+    well.  Without it the certificate covers the scene, the arm against the scan and the held object against the scene, and an edge
+    that carries a box through a scanned wall is called FREE.  With it ``certify_batch`` -- and so ``connect`` / ``steer`` /
+    ``*_batch`` -- appends a fourth step behind those three, one (edge, held shape) item per lane against the scan
+    (``nbk_edge_held_cloud_continuous_batch``, with this connector's ``look_ahead``), ``is_valid`` asks
+    ``in_collision_with_attached(..., cloud=...)``, and the trajectory methods add ``nbk_spline_held_cloud_continuous_batch`` when
+    the call names a cloud and an attachment is in effect, the connector's own or the call's.  The flag is an argument of this
+    constructor for the cloud's reason; ``ConnectorParams(attached_sees_cloud=True)`` keeps being refused here."""
 
     def __init__(self, params: ConnectorParams, max_iter: int = 64, slack: float = 1e-6, cloud=None, cloud_ignore_links=(),
-                 look_ahead: float = CLOUD_LOOK_AHEAD, attached=None):
+                 look_ahead: float = CLOUD_LOOK_AHEAD, attached=None, attached_sees_cloud: bool = False):
         if int(max_iter) < 1:
             raise ValueError("max_iter must be at least 1")
         if not slack >= 0.0:
@@ -375,6 +388,8 @@ class ContinuousConnector(Connector):
             raise ValueError("certified held-object checks do not see point clouds yet")
         _no_cloud(params, "certified continuous checks")
         _no_held(params, "certified continuous checks")
+        if attached_sees_cloud and (cloud is None or attached is None):
+            raise ValueError("attached_sees_cloud needs ContinuousConnector(cloud=..., attached=...)")
         device_edge = params.arm is not None and params.validity_checker is None and params.trajectory_func is _DEFAULT_TRAJ
         if cloud is not None:
             if not device_edge:
@@ -392,6 +407,7 @@ class ContinuousConnector(Connector):
         self.cloud_ignore_links = tuple(cloud_ignore_links)
         self.look_ahead = float(look_ahead)
         self.attached = attached
+        self.attached_sees_cloud = bool(attached_sees_cloud)
 
     def _device_edge(self):
         p = self._params
@@ -449,7 +465,8 @@ class ContinuousConnector(Connector):
             return False
         if self.cloud is not None and p.arm.in_collision_with_cloud(state, self.cloud, p.collision_threshold, self.cloud_ignore_links):
             return False
-        return self.attached is None or not p.arm.in_collision_with_attached(state, self.attached, p.collision_threshold)
+        return self.attached is None or not p.arm.in_collision_with_attached(
+            state, self.attached, p.collision_threshold, cloud=self.cloud if self.attached_sees_cloud else None)
 
     # ---- batched ------------------------------------------------------------------------------------------
     def certify_batch(self, starts, goals, mode="connect", dist=None):
@@ -464,15 +481,20 @@ class ContinuousConnector(Connector):
         if self.cloud is None and self.attached is None:
             return dev.edge_continuous(starts, goals, p.max_distance, dist=dist, **kw)
         held = None if self.attached is None else self.attached._device(p.arm)[1]
-        # items of an edge the scene stopped early stop there; `end` is the scene's.  The cloud's items, then the held object's
+        # items of an edge the scene stopped early stop there; `end` is the scene's.  The cloud's items, then the held object's (and,
+        # with attached_sees_cloud, the held object's against the cloud)
         cloud = None if self.cloud is None else (
             lambda s, g, d, res: dev.cloud_edge_continuous(self.cloud, s, g, p.max_distance, look_ahead=self.look_ahead, dist=d,
                                                            shapes=p.arm._cloud_shapes(sm, self.cloud_ignore_links),
                                                            out=(res[0], res[2], res[3]), **kw))
         hold = None if held is None else (
             lambda s, g, d, res: dev.held_edge_continuous(held, s, g, p.max_distance, dist=d, out=(res[0], res[2], res[3]), **kw))
+        hold_scan = None if not self.attached_sees_cloud else (
+            lambda s, g, d, res: dev.held_cloud_edge_continuous(held, self.cloud, s, g, p.max_distance, look_ahead=self.look_ahead,
+                                                                dist=d, out=(res[0], res[2], res[3]), **kw))
         return _scene_then_cloud(
-            (starts, goals, dist), lambda s, g, d: dev.edge_continuous(s, g, p.max_distance, dist=d, **kw), _then(cloud, hold))
+            (starts, goals, dist), lambda s, g, d: dev.edge_continuous(s, g, p.max_distance, dist=d, **kw),
+            _then(cloud, hold, hold_scan))
 
     def connect_batch(self, starts, goals, dist=None):
         """(E, dof) x (E, dof) -> (E,) bool: True where ``connect`` would return the goal."""
@@ -501,7 +523,10 @@ class ContinuousConnector(Connector):
             lambda c, res: dev.cloud_spline_continuous(cloud, c, knots, degree, look_ahead=self.look_ahead,
                                                        shapes=p.arm._cloud_shapes(sm, links), out=res, **kw))
         hold = None if held is None else (lambda c, res: dev.held_spline_continuous(held, c, knots, degree, out=res, **kw))
-        return _scene_then_cloud((ctrl,), lambda c: dev.spline_continuous(c, knots, degree, **kw), _then(scan, hold))
+        # (attached_sees_cloud: the held object against the scan, where the call names a cloud and an attachment is in effect)
+        hold_scan = None if not (self.attached_sees_cloud and held is not None and cloud is not None) else (
+            lambda c, res: dev.held_cloud_spline_continuous(held, cloud, c, knots, degree, look_ahead=self.look_ahead, out=res, **kw))
+        return _scene_then_cloud((ctrl,), lambda c: dev.spline_continuous(c, knots, degree, **kw), _then(scan, hold, hold_scan))
 
     def validate_trajectories(self, control_points, degree=1, cloud=None, cloud_ignore_links=None, attached=None):
         """S clamped B-splines of ``unit_bspline``'s knots, each certified on the device by conservative advancement across its knot
@@ -512,7 +537,9 @@ class ContinuousConnector(Connector):
         (``nbk_spline_cloud_continuous_batch`` accumulating into the scene's result, with this connector's ``look_ahead``), without
         the shapes of ``cloud_ignore_links`` (default: the connector's own tuple).  A call that names no cloud is refused when the
         connector carries one.  ``attached`` (an ``Attachment``; default: the connector's own): the object in the hand is certified
-        as well, after the scan (``nbk_spline_held_continuous_batch`` accumulating into the same result)."""
+        as well, after the scan (``nbk_spline_held_continuous_batch`` accumulating into the same result).  With the connector's
+        ``attached_sees_cloud`` a call that names a cloud, with an attachment in effect, adds the held object against the scan
+        (``nbk_spline_held_cloud_continuous_batch``) behind those."""
         if cloud is None:
             self._no_cloud_splines()
         shape = _shape(control_points)
