@@ -869,6 +869,22 @@ int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const do
  * world status of a movable descriptor is set.  grasp / grasp_rows as nbk_held_validity_batch.  Planes and hull-shaped WORLD shapes
  * are served.  One kernel, one (row, item) per lane, item-major; asynchronous, no allocation, capturable.
  *
+ * nbk_held_records_batch / nbk_held_records_items: the items' records -- the distance with WHERE the contact is and WHICH WAY to
+ * move, bit for bit what nbk_proximity_jacobian_batch / nbk_pair_records_items report for that pair on that descriptor.  A robot
+ * item is its pair (s, S+h): the subject is the link shape, the target the held shape; a world item is (S+h, w): the subject is the
+ * held shape.  witness [9] = point on the subject, point on the target, unit normal from the target to the subject; jrows [n_q] =
+ * n . Jv_subject(p_subject) - n . Jv_target(p_target), the gradient of the distance, over the joints of the link shape's path and of
+ * the holding frame's (a world target adds nothing).  witness and jrows are optional (NULL).
+ *   nbk_held_records_batch: dist [B][K], witness [B][K][9], jrows [B][K][n_q] (all device); dist is nbk_held_distances_batch's.
+ *   nbk_held_records_items: items (device) [N][2] int32 = (row of q, item index), as nbk_pair_records_items has them; dist [N],
+ *     witness [N][9], jrows [N][n_q].  An entry outside [0, B) x [0, K) reads nothing and gets NaN in every field.  A listed item
+ *     takes the grasp row of its own b.
+ * grasp / grasp_rows as nbk_held_distances_batch.  Every field of an item is NaN where row b of q or its grasp row is not finite,
+ * or the world status of a movable descriptor is set.  NBK_ERR_INVALID for a null m, held, q, items or dist that is needed, B < 0,
+ * N < 0, grasp_rows outside {0, 1, B} or a grasp pointer that does not go with it -- answered before any device is touched.  Each is
+ * one kernel on `stream`, one item per lane; asynchronous, no allocation, capturable.  LDS: the q rows, and [n_joints][6][64] doubles
+ * when jrows is given.
+ *
  * nbk_edge_held_continuous_batch / nbk_spline_held_continuous_batch: nbk_edge_continuous_batch / nbk_spline_continuous_batch over
  * the K items instead of the descriptor's pairs: the same conservative advancement, each item's motion bound the one
  * nbk_edge_motion_bounds_host / nbk_spline_motion_bounds_host gives for that pair on that descriptor
@@ -908,6 +924,15 @@ int32_t nbk_held_items(const nbk_held *held, int32_t *out /* host [K][3] */);
 int32_t nbk_held_distances_batch(const nbk_model *m, const nbk_held *held, const double *q, int64_t B,
                                  const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows,
                                  double *out_d /* [B][K] */, void *stream);
+int32_t nbk_held_records_batch(const nbk_model *m, const nbk_held *held, const double *q, int64_t B,
+                               const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows,
+                               double *dist /* [B][K] */, double *witness /* optional [B][K][9] */,
+                               double *jrows /* optional [B][K][n_q] */, void *stream);
+int32_t nbk_held_records_items(const nbk_model *m, const nbk_held *held, const double *q, int64_t B,
+                               const int32_t *items /* DEVICE [N][2] */, int64_t N,
+                               const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows,
+                               double *dist /* [N] */, double *witness /* optional [N][9] */, double *jrows /* optional [N][n_q] */,
+                               void *stream);
 int32_t nbk_edge_held_continuous_batch(const nbk_model *m, const nbk_held *held, const double *starts, const double *goals,
                                        const double *dist /* optional */, int64_t E, double max_distance, int32_t mode,
                                        double threshold, int32_t max_iter, double slack, const double *grasp /* DEVICE [16] or NULL */,
@@ -953,6 +978,14 @@ int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc *d, int32_t fram
  * nothing is nearer than d_max; NaN, -1, -1 for a non-finite q or grasp row or a set status.  On equal distances the smallest h wins,
  * then the smallest point index.  d_max must be finite.
  *
+ * nbk_held_cloud_records_batch: nbk_records_cloud_batch over the held shapes -- that clearance's record with the witness and the
+ * gradient row.  per_shape == 0: dist [B], shape [B], point [B], witness [B][9], jrows [B][n_q]; dist, shape and point are
+ * nbk_held_cloud_clearance_batch's bits.  per_shape != 0: one record per (row, held shape h), [B][H] ..., each the clearance of
+ * shape h alone.  shape, point, witness and jrows are optional.  witness = point on the held shape, point on the cloud point's
+ * sphere, unit normal from the point to the shape; jrows = n . Jv_held(point on the shape) over the joints of the holding frame's
+ * path.  Nothing nearer than d_max: +inf, -1, -1, a NaN witness and a row of +0.0; a non-finite q or grasp row or a set status: NaN,
+ * -1, -1, NaN, NaN.  One kernel; LDS: the q rows, and [n_joints][6][64] doubles when jrows is given.
+ *
  * nbk_edge_held_cloud_validity_batch / nbk_spline_held_cloud_validity_batch: nbk_edge_cloud_validity_batch /
  * nbk_spline_cloud_validity_batch with this verdict per sample: the same plan, samples, end / t_hit / n_samples, accumulate and
  * workspace (nbk_edge_held_cloud_workspace_bytes(E) / nbk_spline_held_cloud_workspace_bytes(S): the cloud siblings' layouts, no
@@ -970,6 +1003,10 @@ int32_t nbk_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, 
 int32_t nbk_held_cloud_clearance_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *q, int64_t B,
                                        const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double d_max,
                                        double *min_dist, int32_t *shape /* optional */, int32_t *point /* optional */, void *stream);
+int32_t nbk_held_cloud_records_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *q, int64_t B,
+                                     const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double d_max,
+                                     int32_t per_shape, double *dist, int32_t *shape /* optional */, int32_t *point /* optional */,
+                                     double *witness /* optional */, double *jrows /* optional */, void *stream);
 int64_t nbk_edge_held_cloud_workspace_bytes(int64_t E);
 int32_t nbk_edge_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *starts,
                                            const double *goals, const double *dist /* optional */, int64_t E, double resolution,

@@ -43,11 +43,11 @@ SYMBOLS = [
     "nbk_render_depth_lds_bytes", "nbk_render_ray_spans_host", "nbk_render_depth_batch",
     "nbk_held_locals_host", "nbk_held_create", "nbk_held_destroy", "nbk_held_validity_batch",
     "nbk_edge_held_workspace_bytes", "nbk_edge_held_validity_batch",
-    "nbk_held_item_count", "nbk_held_items", "nbk_held_distances_batch",
+    "nbk_held_item_count", "nbk_held_items", "nbk_held_distances_batch", "nbk_held_records_batch", "nbk_held_records_items",
     "nbk_edge_held_continuous_batch", "nbk_spline_held_continuous_batch",
     "nbk_spline_held_workspace_bytes", "nbk_spline_held_validity_batch",
     "nbk_edge_held_motion_bounds_host", "nbk_spline_held_motion_bounds_host",
-    "nbk_held_cloud_validity_batch", "nbk_held_cloud_clearance_batch",
+    "nbk_held_cloud_validity_batch", "nbk_held_cloud_clearance_batch", "nbk_held_cloud_records_batch",
     "nbk_edge_held_cloud_workspace_bytes", "nbk_edge_held_cloud_validity_batch",
     "nbk_spline_held_cloud_workspace_bytes", "nbk_spline_held_cloud_validity_batch",
     "nbk_edge_held_cloud_continuous_batch", "nbk_spline_held_cloud_continuous_batch",
@@ -191,6 +191,8 @@ def load():
     lib.nbk_held_item_count.argtypes = [vp]
     lib.nbk_held_items.argtypes = [vp, vp]
     lib.nbk_held_distances_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
+    lib.nbk_held_records_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.nbk_held_records_items.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.nbk_edge_held_continuous_batch.argtypes = [vp, vp, vp, vp, vp, i64, f64, i32, f64, i32, f64, vp, i32, vp, vp, vp, vp, vp]
     lib.nbk_spline_held_continuous_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, f64, i32, f64, vp, i32, vp, vp, vp, vp]
     lib.nbk_spline_held_workspace_bytes.argtypes = [i64]
@@ -201,6 +203,7 @@ def load():
     lib.nbk_spline_held_motion_bounds_host.argtypes = held_args + [vp, i64, i32, i32, vp, vp]
     lib.nbk_held_cloud_validity_batch.argtypes = [vp, vp, vp, vp, i64, vp, i64, f64, i32, vp, vp, vp]
     lib.nbk_held_cloud_clearance_batch.argtypes = [vp, vp, vp, vp, i64, vp, i64, f64, vp, vp, vp, vp]
+    lib.nbk_held_cloud_records_batch.argtypes = [vp, vp, vp, vp, i64, vp, i64, f64, i32, vp, vp, vp, vp, vp, vp]
     lib.nbk_edge_held_cloud_workspace_bytes.argtypes = [i64]
     lib.nbk_edge_held_cloud_workspace_bytes.restype = i64
     lib.nbk_edge_held_cloud_validity_batch.argtypes = [vp, vp, vp, vp, vp, vp, i64, f64, f64, i32, f64, vp, i32, vp, vp, vp, vp, i64, vp]

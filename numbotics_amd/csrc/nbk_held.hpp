@@ -47,13 +47,15 @@ __host__ __device__ inline void held_mul12(const double* a, const double* b, dou
 // the local pose of held shape h in the holding frame: (A . G) . L_h
 __host__ __device__ inline void held_locals(const double* AG, const double* L, double* out) { held_mul12(AG, L, out); }
 
-// F(q): the joints of `mask`, base first (cloud_shape_frame for a mask instead of a shape)
-NBK_DEV void held_frame(const DevModel& m, unsigned mask, const double* myq, Xf& T) {
+// F(q): the joints of `mask`, base first (cloud_shape_frame for a mask instead of a shape).  rows (optional): the lane's column of the
+// [J][6][64] joint rows, written through joint_frame_rows for every joint of the mask (what prox_row_masks reads)
+NBK_DEV void held_frame(const DevModel& m, unsigned mask, const double* myq, Xf& T, double* rows = nullptr) {
     xf_from12(m.base_pose, T);
     for (int k = 0; k < m.n_joints; ++k) {
         if (((mask >> k) & 1u) == 0u) continue;
         Xf nxt;
         joint_apply(m, k, T, myq[m.joint_qidx[k]], nxt);
+        if (rows != nullptr) joint_frame_rows(m, k, nxt, rows + 6 * k * WAVE);
         T = nxt;
     }
 }
@@ -442,6 +444,95 @@ __global__ __launch_bounds__(64) void k_held_cloud_clearance(DevModel m, HeldDev
     }
 }
 
+// ---- proximity records of the held object against the cloud (nbk_held_cloud_records_batch): k_cloud_records with the held shapes in
+// the robot shapes' place, in its two phases.
+//   1. the winner: k_held_cloud_clearance's loop, cloud_core_clearance keeping the winner's slot in the sorted arrays.  PER_SHAPE =
+//      true has the grid (ceil(B / 64), H) with blockIdx.y = h -- a wave holds ONE held shape, every item starts from a fresh `best`
+//      -- and writes column h of [B][H].
+//   2. the record, for the lanes that hold a winner and only when a witness or a row is asked for: the holding frame once more (the
+//      same joint_apply sequence, so the same frame bits), with joint_frame_rows into the [J][6][64] LDS rows when rows are asked
+//      for; held_core of the winning shape; cores_distance<true, true> and epa_refine<true> on (held core, point core) --
+//      item_distance's statements for a (robot shape, sphere world shape) pair; prox_row_masks with the holding frame's mask and 0.
+//      The distance this phase finds is the one reported where it runs: the bits of phase 1.
+// Nothing nearer than d_max: +inf, -1, -1, NaN witness, a row of +0.0.  A non-finite q or grasp row or a set status: NaN, -1, -1, NaN,
+// NaN.  LDS: PairItemsLds -- [64][n_q] q rows | [J][6][64] joint rows when rows are asked for.
+template <bool PER_SHAPE>
+__global__ __launch_bounds__(64) void k_held_cloud_records(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ q, int64_t B,
+                                                           const double* __restrict__ grasp, int grasp_rows, double d_max,
+                                                           double* __restrict__ out_d, int32_t* __restrict__ out_s,
+                                                           int32_t* __restrict__ out_p, double* __restrict__ out_w,
+                                                           double* __restrict__ out_j) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t b = (int64_t)blockIdx.x * WAVE + lane;
+    const bool active = b < B;
+    const PairItemsLds L(m.n_q);
+    double* myq = L.q(lds) + lane * m.n_q;
+    const int h0 = PER_SHAPE ? (int)blockIdx.y : 0, h1 = PER_SHAPE ? h0 + 1 : hd.n_shapes;
+    if (h0 >= hd.n_shapes) return;
+    const int status = cd.hdr->status;
+    const int n = cd.hdr->n;
+    const double radius = cd.hdr->radius;
+    bool ok = false;
+    const double* grow = hd.tab + 12;
+    if (active) {
+        bool gfin = true;
+        grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
+        ok = cloud_stage_q(q, b, m.n_q, myq) && gfin && status == 0;
+    }
+    double best = NBK_INF;
+    int bs = -1, bi = -1;
+    unsigned slot = 0u;
+    Core P;
+    cloud_point_core(radius, P);
+    double AG[12];
+    if (n > 0 && status == 0 && __builtin_amdgcn_ballot_w64(ok) != 0ull) {
+        Xf F;
+        if (ok) {
+            held_frame(m, hd.mask, myq, F);
+            double G[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) G[e] = grow[e];
+            held_mul12(hd.tab, G, AG);
+        }
+        for (int h = h0; h < h1; ++h) {
+            Core Hc;
+            cloud_core_init(Hc);
+            if (ok) held_core(hd, h, F, AG, Hc);
+            cloud_core_clearance(cd, Hc, P, radius, ok, h, d_max, best, bs, bi, &slot);
+        }
+    }
+    const bool win = ok && bs >= 0;
+    double wit[9];
+    if ((out_w != nullptr || out_j != nullptr) && win) {
+        Xf F;
+        held_frame(m, hd.mask, myq, F, out_j != nullptr ? L.jz(lds) + lane : nullptr);
+        Core Hc;
+        cloud_core_init(Hc);
+        held_core(hd, bs, F, AG, Hc);
+        const double* p = cd.pts + 3 * (size_t)slot;
+        P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
+        double fam = -1.0;
+        double d = cores_distance<true, true>(Hc, P, wit, &fam);
+        if (fam >= 0.0) epa_refine<true>(Hc, P, fam, d, wit);
+        best = d;
+    }
+    if (!active) return;
+    const int64_t o = PER_SHAPE ? b * hd.n_shapes + h0 : b;
+    const double nan = __builtin_nan("");
+    out_d[o] = ok ? best : nan;
+    if (out_s != nullptr) out_s[o] = ok ? bs : -1;
+    if (out_p != nullptr) out_p[o] = ok ? bi : -1;
+    if (out_w != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) out_w[o * 9 + e] = win ? wit[e] : nan;
+    }
+    if (out_j != nullptr) {
+        if (win) prox_row_masks(m, L.jz(lds), lane, hd.mask, 0u, wit, out_j + o * m.n_q);
+        else for (int c = 0; c < m.n_q; ++c) out_j[o * m.n_q + c] = ok ? 0.0 : nan;
+    }
+}
+
 // k_cloud_edges with the held walk against the cloud (nbk_edge_held_cloud_validity_batch): the plan, the scan and k_cloud_edges_init
 // are the cloud's.  One grasp per call; a non-finite grasp or a set cloud status makes every non-degenerate edge invalid.
 __global__ __launch_bounds__(64) void k_held_cloud_edges(DevModel m, HeldDev hd, CloudDev cd, EdgeSrc es,
@@ -522,11 +613,15 @@ __global__ __launch_bounds__(64) void k_held_cloud_spline(DevModel m, HeldDev hd
 // shapes as robot shapes S + h: (s, S + h) for the allowed robot shapes s in the caller's order, then h; then (S + h, world w) for h,
 // then the allowed world shapes.  HeldDev.items holds them (held_item_list, made once by nbk_held_create).
 
-// The signed distance of item `it` at the lane's staged row `myq` with the grasp `grasp_row`: item_distance's statements on the held
-// core and the other shape's, in the descriptor's operand order (robot shape first, held shape second; held shape first, world
-// shape second).  Every lane of the wave calls it; lanes with ok == false replay nothing and get NaN.  The two frames are replayed
-// from the base, each along its own mask: common ancestors give the same bits on either path.
-NBK_DEV double held_item_distance(const DevModel& m, const HeldDev& hd, const double* grasp_row, const double* myq, bool ok, int it) {
+// The record of item `it` at the lane's staged row `myq` with the grasp `grasp_row`: item_distance's statements on the held core and
+// the other shape's, in the descriptor's operand order (robot shape first, held shape second; held shape first, world shape
+// second) -- the signed distance, and in wit[9] the point on the first, the point on the second and the unit normal from the second
+// to the first.  Every lane of the wave calls it; lanes with ok == false replay nothing, get NaN and leave wit alone.  The two
+// frames are replayed from the base, each along its own mask: common ancestors give the same bits on either path.  rows (optional):
+// the lane's column of the [J][6][64] joint rows; every joint of either mask is written (a common ancestor twice, the same bits),
+// which is what prox_row_masks reads for this item.
+NBK_DEV double held_item_record(const DevModel& m, const HeldDev& hd, const double* grasp_row, const double* myq, bool ok, int it,
+                                double* rows, double* wit) {
     // the hull support's scalar-cache path (rad < 0) needs every running lane to hold the same hull: only for item-uniform waves
     const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
     const int it0 = __shfl(it, okm != 0ull ? __builtin_ctzll(okm) : 0);
@@ -536,7 +631,7 @@ NBK_DEV double held_item_distance(const DevModel& m, const HeldDev& hd, const do
     const int h = rec[0], idx = rec[2];
     const bool robot = rec[1] == 0;
     Xf F;
-    held_frame(m, hd.mask, myq, F);
+    held_frame(m, hd.mask, myq, F, rows);
     double G[12], AG[12];
 #pragma unroll
     for (int e = 0; e < 12; ++e) G[e] = grasp_row[e];
@@ -547,7 +642,7 @@ NBK_DEV double held_item_distance(const DevModel& m, const HeldDev& hd, const do
     held_core(hd, h, F, AG, Hc);
     if (robot) {
         Xf T;
-        cloud_shape_frame(m, idx, myq, T);
+        held_frame(m, m.rs_mask[idx], myq, T, rows);      // (cloud_shape_frame's statements)
         build_core(m, idx, T, Oc);
     } else {
         load_wcore(m, idx, Oc);
@@ -557,11 +652,16 @@ NBK_DEV double held_item_distance(const DevModel& m, const HeldDev& hd, const do
     held_pick(robot, Hc, Oc, Bc);
     if (uniform && A.kind == K_HULL) A.rad = -1.0;
     if (uniform && Bc.kind == K_HULL) Bc.rad = -1.0;
-    double wit[9];
     double fam = -1.0;
     double d = cores_distance<true, true>(A, Bc, wit, &fam);
     if (fam >= 0.0) epa_refine<true>(A, Bc, fam, d, wit);
     return d;
+}
+
+// the signed distance alone (k_held_distances, the certified lanes)
+NBK_DEV double held_item_distance(const DevModel& m, const HeldDev& hd, const double* grasp_row, const double* myq, bool ok, int it) {
+    double wit[9];
+    return held_item_record(m, hd, grasp_row, myq, ok, it, nullptr, wit);
 }
 
 // one (row, item) per lane, item-major (a wave holds one item unless it straddles two): out_d[b][it], NaN where the q row or the
@@ -586,6 +686,73 @@ __global__ __launch_bounds__(64) void k_held_distances(DevModel m, HeldDev hd, c
     }
     const double d = held_item_distance(m, hd, grow, myq, ok, it);
     if (live) out_d[b * hd.n_items + it] = d;
+}
+
+// ---- records of held items (nbk_held_records_batch, nbk_held_records_items): the distance of k_held_distances with the witness and
+// the gradient row -- what k_distances<3> / k_pair_items give for the pair of the item on a descriptor that holds the held shapes as
+// robot shapes S + h.  One (row, item) per lane.  LISTED = false: the item-major dense index of k_held_distances, outputs [B][K],
+// [B][K][9], [B][K][n_q].  LISTED = true: items [N][2] = (row of q, item), outputs [N], [N][9], [N][n_q]; an entry outside
+// [0, B) x [0, K) reads nothing and writes NaN to every field.  The row is prox_row_masks over the joint rows the replay leaves in
+// LDS: a robot item (s, S + h) has the link shape as subject (rs_mask[s]) and the held shape as target (hd.mask); a world item
+// (S + h, w) the held shape as subject and no target mask.  Every field is NaN where the q row or the grasp row is not finite or the
+// world status is set.  LDS: PairItemsLds -- [64][n_q] q rows | [J][6][64] joint rows when rows are asked for.
+template <bool LISTED>
+__global__ __launch_bounds__(64) void k_held_records(DevModel m, HeldDev hd, const int* __restrict__ wstatus, const double* __restrict__ q,
+                                                     int64_t B, const int32_t* __restrict__ items, int64_t N,
+                                                     const double* __restrict__ grasp, int grasp_rows, double* __restrict__ out_d,
+                                                     double* __restrict__ out_w, double* __restrict__ out_j) {
+    extern __shared__ double lds[];
+    const int lane = (int)threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
+    const int64_t K = hd.n_items;
+    const bool live = i < (LISTED ? N : B * K);
+    bool in = false;
+    int it = 0;
+    int64_t b = 0;
+    if (live) {
+        if constexpr (LISTED) {
+            const long long bl = items[2 * i];
+            const int il = items[2 * i + 1];
+            in = bl >= 0 && bl < B && il >= 0 && il < K;
+            if (in) { b = bl; it = il; }
+        } else {
+            it = (int)(i / B);
+            b = i - (int64_t)it * B;
+            in = true;
+        }
+    }
+    const PairItemsLds L(m.n_q);
+    double* myq = L.q(lds) + lane * m.n_q;
+    double* rows = out_j != nullptr ? L.jz(lds) + lane : nullptr;
+    const bool wbad = wstatus != nullptr && *wstatus != 0;
+    bool ok = false;
+    const double* grow = hd.tab + 12;
+    if (in) {
+        bool gfin = true;
+        grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
+        ok = cloud_stage_q(q, b, m.n_q, myq) && gfin && !wbad;
+    }
+    double wit[9];
+    const double d = held_item_record(m, hd, grow, myq, ok, it, rows, wit);
+    if (!live) return;
+    const int64_t o = LISTED ? i : b * K + it;
+    if (!ok) {
+        const double nan = __builtin_nan("");
+        out_d[o] = nan;
+        if (out_w != nullptr) for (int e = 0; e < 9; ++e) out_w[o * 9 + e] = nan;
+        if (out_j != nullptr) for (int c = 0; c < m.n_q; ++c) out_j[o * m.n_q + c] = nan;
+        return;
+    }
+    out_d[o] = d;
+    if (out_w != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) out_w[o * 9 + e] = wit[e];
+    }
+    if (out_j != nullptr) {
+        const int* rec = hd.items + HELD_ITEM_LEN * it;
+        const bool robot = rec[1] == 0;
+        prox_row_masks(m, L.jz(lds), lane, robot ? m.rs_mask[rec[2]] : hd.mask, robot ? hd.mask : 0u, wit, out_j + o * m.n_q);
+    }
 }
 
 // ---- the motion bound of a held item: pair_motion_bound's bits for that pair on a descriptor whose shape tables hold, for S + h,
@@ -1133,6 +1300,46 @@ int32_t nbk_held_distances_batch(const nbk_model* m, const nbk_held* held, const
     return NBK_OK;
 }
 
+// the argument rules the two record entries share, answered without a device: the grasp's, as nbk_held_distances_batch has them
+static int32_t held_records_args(const nbk_model* m, const nbk_held* held, int64_t B, const double* grasp, int64_t grasp_rows) {
+    if (m == nullptr || held == nullptr || B < 0) return NBK_ERR_INVALID;
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    return NBK_OK;
+}
+
+int32_t nbk_held_records_batch(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const double* grasp,
+                               int64_t grasp_rows, double* dist, double* witness, double* jrows, void* stream) {
+    { const int32_t rc = held_records_args(m, held, B, grasp, grasp_rows); if (rc != NBK_OK) return rc; }
+    if (B > 0 && (q == nullptr || dist == nullptr)) return NBK_ERR_INVALID;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    const int64_t K = held->d.n_items;
+    if (B == 0 || K == 0) return NBK_OK;
+    if (B > 0x7fffffffLL || (B * K + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
+    hipLaunchKernelGGL(k_held_records<false>, dim3((unsigned)((B * K + WAVE - 1) / WAVE)), dim3(WAVE),
+                       PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes(), (hipStream_t)stream, m->d, held->d,
+                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, (const int32_t*)nullptr, (int64_t)0, grasp, rows,
+                       dist, witness, jrows);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_held_records_items(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const int32_t* items, int64_t N,
+                               const double* grasp, int64_t grasp_rows, double* dist, double* witness, double* jrows, void* stream) {
+    { const int32_t rc = held_records_args(m, held, B, grasp, grasp_rows); if (rc != NBK_OK) return rc; }
+    if (N < 0 || (N > 0 && (items == nullptr || dist == nullptr || (B > 0 && q == nullptr)))) return NBK_ERR_INVALID;
+    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
+    if (N == 0) return NBK_OK;
+    if (B > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
+    hipLaunchKernelGGL(k_held_records<true>, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE),
+                       PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes(), (hipStream_t)stream, m->d, held->d,
+                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, items, N, grasp, rows, dist, witness, jrows);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
 // the hold of the certified held entries, behind the scene's init kernel (k_held_ca_hold): only where something can be held
 static int32_t launch_held_ca_hold(const nbk_model* m, hipStream_t st, const double* grasp, int64_t n, double* t_free) {
     if (!m->movable && grasp == nullptr) return NBK_OK;
@@ -1278,6 +1485,28 @@ int32_t nbk_held_cloud_clearance_batch(const nbk_model* m, const nbk_held* held,
     const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
     hipLaunchKernelGGL(k_held_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
                        held->d, cloud_dev(c), q, B, grasp, rows, d_max, min_dist, shape, point);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+int32_t nbk_held_cloud_records_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* q, int64_t B,
+                                     const double* grasp, int64_t grasp_rows, double d_max, int32_t per_shape, double* dist,
+                                     int32_t* shape, int32_t* point, double* witness, double* jrows, void* stream) {
+    if (m == nullptr || held == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0)) return NBK_ERR_INVALID;
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    if (B > 0 && (q == nullptr || dist == nullptr)) return NBK_ERR_INVALID;
+    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
+    if (B == 0) return NBK_OK;
+    if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
+    const size_t lds = PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes();
+    if (per_shape)
+        hipLaunchKernelGGL(k_held_cloud_records<true>, dim3(blocks_for(B), (unsigned)held->d.n_shapes), dim3(WAVE), lds, (hipStream_t)stream,
+                           m->d, held->d, cloud_dev(c), q, B, grasp, rows, d_max, dist, shape, point, witness, jrows);
+    else
+        hipLaunchKernelGGL(k_held_cloud_records<false>, dim3(blocks_for(B)), dim3(WAVE), lds, (hipStream_t)stream, m->d, held->d,
+                           cloud_dev(c), q, B, grasp, rows, d_max, dist, shape, point, witness, jrows);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

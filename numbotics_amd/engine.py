@@ -890,6 +890,83 @@ class DeviceModel:
             "nbk_held_distances_batch")
         return qs.out(d)
 
+    @staticmethod
+    def _check_items(items):
+        """``items`` of ``held_records``: (N, 2) integers, NumPy or a tensor."""
+        if _torch().is_tensor(items):
+            shape, integer = tuple(items.shape), not (items.is_floating_point() or items.is_complex() or items.dtype == _torch().bool)
+        else:
+            a = np.asarray(items)
+            shape, integer = a.shape, a.size == 0 or (np.issubdtype(a.dtype, np.integer) and a.dtype != np.bool_)
+        if len(shape) != 2 or shape[1] != 2 or not integer:
+            raise ValueError(f"items must be an (N, 2) integer array of (row of q, item index), got shape {shape}")
+
+    def _launch_held_records(self, held, qt, B, g, rows, it, witness, jacobian):
+        """The dense (``it`` None: (B, K) ...) or the listed (``it`` (N, 2) int32 on the device: (N,) ...) record kernel on device
+        tensors -> (dist, witness or None, rows or None)."""
+        torch = _torch()
+        lead = (B, held.n_items) if it is None else (int(it.shape[0]),)
+        d = torch.empty(lead, dtype=torch.float64, device=qt.device)
+        w = torch.empty(lead + (9,), dtype=torch.float64, device=qt.device) if witness else None
+        j = torch.empty(lead + (self.n_q,), dtype=torch.float64, device=qt.device) if jacobian else None
+        gp, wp, jp = None if g is None else g.data_ptr(), None if w is None else w.data_ptr(), None if j is None else j.data_ptr()
+        if d.numel() == 0:
+            return d, w, j
+        if it is None:
+            _lib.check(self._lib.nbk_held_records_batch(self._h, held._h, qt.data_ptr(), B, gp, rows, d.data_ptr(), wp, jp, self._stream()),
+                       "nbk_held_records_batch")
+        else:
+            _lib.check(self._lib.nbk_held_records_items(self._h, held._h, qt.data_ptr(), B, it.data_ptr(), int(it.shape[0]), gp, rows,
+                                                        d.data_ptr(), wp, jp, self._stream()), "nbk_held_records_items")
+        return d, w, j
+
+    def held_records(self, held, q, pose=None, items=None, witness=True, jacobian=True):
+        """``held_distances`` with the contact and the way out of it (nbk_held_records_batch / nbk_held_records_items) -> (dist,
+        witness or None, rows or None).  ``items=None``: every item of every row, (B, K), (B, K, 9), (B, K, n_q), dist bit for bit
+        ``held_distances``'.  ``items`` (N, 2) int = (row of q, item index of ``held.items()``), NumPy or a CUDA tensor: those
+        entries only, (N,), (N, 9), (N, n_q) -- the dense ones at [b, k], NaN for an entry outside [0, B) x [0, K).  Bit for bit
+        ``proximity_jacobian`` / ``pair_records`` of a descriptor that holds the held shapes as robot shapes: for a (held shape,
+        robot shape) item the subject is the LINK's shape and the target the held shape, for a (held shape, world shape) item the
+        subject is the held shape; witness = point on the subject, point on the target, unit normal from the target to the subject;
+        rows = n . Jv_subject - n . Jv_target, the gradient of the distance.  ``pose``: as ``held_distances``'s (a listed item takes
+        the grasp of its own row).  NaN in every field where the row or its grasp is not finite."""
+        self._held(held)                                # (argument errors come before the device is touched)
+        if items is not None:
+            self._check_items(items)
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        it = None if items is None else self._items(items, qs.device)
+        d, w, j = self._launch_held_records(held, qs.t, qs.B, g, rows, it, witness, jacobian)
+        return qs.out(d), None if w is None else qs.out(w), None if j is None else qs.out(j)
+
+    def held_closest_records(self, held, q, pose=None):
+        """``held_distances``, the closest item of every row (the first minimum) and that item's record, with no host round trip in
+        between -> dist (B,), item (B,) int32, witness (B, 9), rows (B, n_q).  A row that is not finite gives NaN, -1, NaN, NaN; a
+        held object without items inf, -1, NaN and rows of zeros."""
+        self._held(held)
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        B, K = qs.B, held.n_items
+        if K == 0:
+            return (qs.out(torch.full((B,), float("inf"), dtype=torch.float64, device=qs.device)),
+                    qs.out(torch.full((B,), -1, dtype=torch.int32, device=qs.device)),
+                    qs.out(torch.full((B, 9), float("nan"), dtype=torch.float64, device=qs.device)),
+                    qs.out(torch.zeros((B, self.n_q), dtype=torch.float64, device=qs.device)))
+        d = torch.empty((B, K), dtype=torch.float64, device=qs.device)
+        _lib.check(self._lib.nbk_held_distances_batch(
+            self._h, held._h, qs.t.data_ptr(), B, None if g is None else g.data_ptr(), rows, d.data_ptr(), self._stream()),
+            "nbk_held_distances_batch")
+        bad = torch.isnan(d).any(dim=1)
+        dmin = d.min(dim=1, keepdim=True).values
+        k = torch.arange(K, dtype=torch.int32, device=qs.device).expand(B, K)
+        first = torch.where(d == dmin, k, K).min(dim=1).values                      # the smallest index that attains the minimum
+        item = torch.where(bad, -1, first).to(torch.int32)                          # (-1: out of range, every field NaN)
+        it = torch.stack((torch.arange(B, dtype=torch.int32, device=qs.device), item), dim=1).contiguous()
+        dist, w, j = self._launch_held_records(held, qs.t, B, g, rows, it, True, True)
+        return qs.out(dist), qs.out(item), qs.out(w), qs.out(j)
+
     def held_edge_continuous(self, held, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None,
                              pose=None, out=None):
         """``edge_continuous``'s edges certified for the held object ``held`` ALONE (nbk_edge_held_continuous_batch): one (edge,
@@ -998,6 +1075,32 @@ class DeviceModel:
             self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(d_max),
             d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._stream()), "nbk_held_cloud_clearance_batch")
         return qs.out(d), qs.out(sh), qs.out(pt)
+
+    def held_cloud_records(self, held, cloud, q, d_max, pose=None, per_shape=False, witness=True, jacobian=True):
+        """``held_cloud_clearance``'s record with the contact and the way out of it (nbk_held_cloud_records_batch) -> (dist, held
+        shape, point, witness or None, rows or None), as ``cloud_records`` with the held shapes in the robot shapes' place.
+        ``per_shape=False``: one record per configuration, (B,), (B,), (B,), (B, 9), (B, n_q); dist, shape and point are
+        ``held_cloud_clearance``'s bits.  ``per_shape=True``: one per (configuration, held shape), (B, H) ..., column h the
+        clearance of held shape h alone.  witness = point on the held shape, point on the cloud point's sphere, unit normal from the
+        point to the shape; rows = n . Jv_held(point on the shape), the gradient of the distance.  Nothing nearer than ``d_max``:
+        inf, -1, -1, NaN witness, a row of zeros; a non-finite configuration or grasp or a set cloud status: NaN, -1, -1, NaN, NaN.
+        ``pose``: as ``held_validity``'s, one grasp or one per row."""
+        h = self._held(held)
+        torch = _require_gpu()
+        qs = _Staged(q, self.n_q)
+        g, rows = self._grasp(torch, pose, qs.B, True)
+        lead = (qs.B, held.n_shapes) if per_shape else (qs.B,)
+        d = torch.empty(lead, dtype=torch.float64, device=qs.device)
+        sh = torch.empty(lead, dtype=torch.int32, device=qs.device)
+        pt = torch.empty(lead, dtype=torch.int32, device=qs.device)
+        w = torch.empty(lead + (9,), dtype=torch.float64, device=qs.device) if witness else None
+        j = torch.empty(lead + (self.n_q,), dtype=torch.float64, device=qs.device) if jacobian else None
+        if d.numel() > 0:
+            _lib.check(self._lib.nbk_held_cloud_records_batch(
+                self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(d_max),
+                1 if per_shape else 0, d.data_ptr(), sh.data_ptr(), pt.data_ptr(), None if w is None else w.data_ptr(),
+                None if j is None else j.data_ptr(), self._stream()), "nbk_held_cloud_records_batch")
+        return qs.out(d), qs.out(sh), qs.out(pt), None if w is None else qs.out(w), None if j is None else qs.out(j)
 
     @staticmethod
     def held_cloud_edge_workspace_bytes(E: int) -> int:

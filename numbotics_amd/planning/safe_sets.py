@@ -161,3 +161,13 @@ def cloud_distance_and_gradient(arm, points, cloud, d_max, link=None, ignore_lin
     _, dev = arm._scene_device()
     dist, _, _, _, rows = dev.cloud_records(cloud, points, d_max, shapes=shapes, witness=False)
     return dist, rows
+
+
+def attached_distance_and_gradient(arm, points, att, pose=None):
+    """``distance_and_gradient`` with an object in the hand: (M, dof) -> the signed distance (M,) of the closest item of the
+    attachment ``att`` (held shape against a link or an obstacle it is paired with; the first minimum) and its gradient rows
+    (M, dof); NaN for a non-finite point, inf and a row of zeros for an attachment without items.  ``pose``: another grasp, as
+    ``Arm.in_collision_with_attached``."""
+    points = np.asarray(points, dtype=np.float64).reshape(-1, arm.dof)
+    dist, _, _, rows = arm.attached_proximity_jacobians(points, att, pose=pose)
+    return dist, rows

@@ -670,6 +670,74 @@ class Arm(Robot):
             return float(dist[0]), int(item[0])
         return dist, item
 
+    # ---- records of the held object's items (additive): where it touches, along which normal, and the gradient of the distance ---
+    def _attached(self, q, att):
+        """The argument rules of the attached record calls, before anything touches the device -> (DeviceModel, DeviceHeld)."""
+        from numbotics_amd.physics import Attachment
+        if not isinstance(att, Attachment):
+            raise ValueError("att must be an Attachment (Arm.attach / World.add_constraint)")
+        self._check_q(q)
+        return att._device(self)
+
+    def attached_proximity_jacobians(self, q, att, pose=None, per_item=False):
+        """``attached_clearance`` with the contact and the gradient, as ``closest_proximity_jacobians`` has it for the arm's own
+        pairs: ``(..., dof)`` (flattened to B rows) -> dist ``(B,)``, item ``(B,)`` int32 (the first minimum; ``att.items(arm)``
+        names them), witness ``(B, 9)``, rows ``(B, dof)``.  For a (held shape, link) item the subject is the LINK and the target
+        the held object, for a (held shape, obstacle) item the subject is the held object: witness = point on the subject, point on
+        the target, unit normal from the target to the subject; rows = n . Jv_subject - n . Jv_target, the gradient of the distance.
+        A row that is not finite gives NaN, -1, NaN, NaN; no items: inf, -1, NaN, rows of zeros.  ``per_item=True``: every item,
+        dist ``(B, K)``, witness ``(B, K, 9)``, rows ``(B, K, dof)`` (``DeviceModel.held_records``).  ``pose``: as
+        ``in_collision_with_attached``.  The closest item and its record are found on the device, with no host round trip."""
+        dev, held = self._attached(q, att)
+        rows = q.reshape(-1, self.dof)
+        if per_item:
+            return dev.held_records(held, rows, pose=pose)
+        return dev.held_closest_records(held, rows, pose=pose)
+
+    def attached_closest_to(self, q, att, pose=None):
+        """``closest_to`` for the held object of ``att``: the ``Proximity`` of its closest item -- subject = the link and target =
+        the held object (``att.objects[0]``) for a (held shape, link) item, subject = the held object and target = the obstacle
+        for a (held shape, obstacle) item -- or None for a ``q`` that is not finite or an attachment without items."""
+        if tuple(q.shape) != (self.dof,):
+            raise ValueError(f"q must be a 1D array with {self.dof} elements")
+        dev, held = self._attached(q, att)
+        qn = q.detach().cpu().numpy() if _is_tensor(q) else np.asarray(q, dtype=np.float64)
+        d, item, w, _ = dev.held_closest_records(held, qn.reshape(1, -1), pose=pose)
+        if item[0] < 0:
+            return None
+        sm = self.scene_model()
+        _, kind, idx = (int(v) for v in held.items()[item[0]])
+        if kind == 0:
+            subj, targ = sm.links[sm.rshape_link[idx]], att.objects[0]
+        else:
+            subj, targ = att.objects[0], sm.objects[sm.wshape_obj[idx]]
+        return Proximity(subject=subj, target=targ, position_on_subject=w[0, 0:3].copy(), position_on_target=w[0, 3:6].copy(),
+                         normal_target_to_subject=w[0, 6:9].copy(), distance=float(d[0]))
+
+    def attached_cloud_proximity_jacobians(self, q, att, cloud, d_max: float, pose=None, per_shape: bool = False):
+        """``attached_cloud_clearance`` with the contact and the gradient, as ``cloud_proximity_jacobians`` has it for the links:
+        (distance, held shape index, point index, witness, rows) per configuration of ``q`` (``(dof,)`` or ``(..., dof)``,
+        flattened to B rows) -- witness ``(B, 9)`` = point on the held shape, point on the cloud point's sphere, unit normal from
+        the point to the shape; rows ``(B, dof)`` = n . Jv_held(point on the shape).  Nothing nearer than ``d_max``: inf, -1, -1,
+        NaN, a row of zeros (a hinge cost's gradient); a row or grasp that is not finite, or a set cloud status: NaN, -1, -1, NaN,
+        NaN.  ``per_shape=True``: one record per (configuration, held shape), ``(B, H)`` ... ``(B, H, dof)``."""
+        dev, held = self._attached(q, att)
+        return dev.held_cloud_records(held, cloud, q.reshape(-1, self.dof), d_max, pose=pose, per_shape=per_shape)
+
+    def attached_cloud_closest_to(self, q, att, cloud, d_max: float, pose=None):
+        """``cloud_closest_to`` for the held object of ``att``: the ``Proximity`` of the closest (held shape, point) when it is
+        nearer than ``d_max`` -- subject = the held object (``att.objects[0]``), target = ``cloud`` -- else None (also for a
+        non-finite ``q``)."""
+        if tuple(q.shape) != (self.dof,):
+            raise ValueError(f"q must be a 1D array with {self.dof} elements")
+        dev, held = self._attached(q, att)
+        qn = q.detach().cpu().numpy() if _is_tensor(q) else np.asarray(q, dtype=np.float64)
+        d, sh, _, w, _ = dev.held_cloud_records(held, cloud, qn.reshape(1, -1), d_max, pose=pose, jacobian=False)
+        if sh[0] < 0:
+            return None
+        return Proximity(subject=att.objects[0], target=cloud, position_on_subject=w[0, 0:3].copy(),
+                         position_on_target=w[0, 3:6].copy(), normal_target_to_subject=w[0, 6:9].copy(), distance=float(d[0]))
+
     def cloud_self_filter(self, points, q, radius: float, padding: float = 0.0, keep=None, links=None, ignore_links=()):
         """Which of a depth frame's ``points`` (N, 3) are NOT the arm's own image at the configuration ``q`` the frame was taken at:
         ``keep[i]`` goes to 0 iff point i, a sphere of ``radius``, is closer than ``padding`` to a link shape -- the verdict

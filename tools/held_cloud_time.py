@@ -1,6 +1,6 @@
 """The held object against point clouds, measured on one GPU (`profiles/held_cloud_time.log`).
 
-    python tools/held_cloud_time.py [--out profiles/held_cloud_time.log] [--reps 5] [--rows 1000000]
+    python tools/held_cloud_time.py [--out profiles/held_cloud_time.log] [--reps 5] [--rows 1000000] [--only records]
 
 Scene c2 with the box of the parity fixtures in the hand (half extents 0.1, 0.1, 0.2, margin 0.04, 0.25 m along the gripper's z;
 H = 1), against the scans of tools/cloud_time.py (scan(N, seed=N), radius 0.01, N = 1e3 and 1e5).  Timing as tools/cloud_time.py:
@@ -15,6 +15,9 @@ The held box is larger than the gripper's and stands elsewhere, so those two cal
 marked "twin" take that out: a held box of the gripper box's own size and margin, grasped so that it stands exactly where the
 gripper box stands -- the same questions, asked through the two walks.  Their masks are compared (the two local poses are formed by
 different products, so single rows may differ in the last bits; the count of differing rows is printed).
+    --only records  (log: profiles/held_cloud_records_time.log) nothing of the above but DeviceModel.held_cloud_records at --rows / 10,
+                d_max 0.05 -- with witness and rows, with the witness alone, with neither -- each beside held_cloud_clearance on the
+                same inputs, whose distance, shape and point it must repeat bit for bit.
 """
 import argparse
 import os
@@ -37,10 +40,13 @@ SH_BOX = 2
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "held_cloud_time.log"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only", choices=("records",), default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1000000)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "held_cloud_records_time.log" if args.only == "records" else "held_cloud_time.log")
     if not torch.cuda.is_available():
         raise SystemExit("tools/held_cloud_time.py needs a GPU: nothing is measured without one")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -93,6 +99,24 @@ def main():
     for N in (10 ** 3, 10 ** 5):
         cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), RADIUS, bounds=BOX)
         say(f"## N = {N}: cell {cloud.cell:.4f}, grid {tuple(int(d) for d in cloud.dims)}")
+        if args.only == "records":
+            d, s, p = dev.held_cloud_clearance(held, cloud, qc[0], 0.05)
+            rd, rs, rp, rw, rj = dev.held_cloud_records(held, cloud, qc[0], 0.05)
+            if not (torch.equal(d.view(torch.int64), rd.view(torch.int64)) and torch.equal(s, rs) and torch.equal(p, rp)):
+                raise SystemExit("held_cloud_records' distance, shape and point != held_cloud_clearance's")
+            win = s >= 0
+            if not (torch.isfinite(rw[win]).all() and torch.isnan(rw[~win]).all() and not rj[~win].any()):
+                raise SystemExit("held_cloud_records: a winner without a witness, or a loser with one or with a row")
+            say(f"records  B = {B // 10}, d_max 0.05: below d_max {float(win.float().mean()):.3f}; distance, shape and point are held_cloud_clearance's")
+            del d, s, p, rd, rs, rp, rw, rj
+            clear = rotating(lambda q: dev.held_cloud_clearance(held, cloud, q, 0.05), qc)
+            for what, kw in (("held_cloud_records (witness, rows)", dict()), ("held_cloud_records (witness)", dict(jacobian=False)),
+                             ("held_cloud_records (neither)", dict(witness=False, jacobian=False))):
+                t_r, t_c = timed_pair(rotating(lambda q, kw=kw: dev.held_cloud_records(held, cloud, q, 0.05, **kw), qc), clear, args.reps)
+                say(f"  {what:<35} {fmt(t_r)}")
+                say(f"  {'held_cloud_clearance beside it':<35} {fmt(t_c)}   (ratio {t_r[0] / t_c[0]:.2f})")
+            del cloud
+            continue
         mine = dev.held_cloud_validity(held, cloud, qs[0], 0.0, packed=True)
         if not torch.equal(mine, dev.held_cloud_validity(held, cloud, qs[0], 0.0, packed=True, pose=Gt)):
             raise SystemExit("the stored grasp and the same grasp given with the call disagree")

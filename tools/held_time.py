@@ -1,6 +1,6 @@
 """Held objects, measured on one GPU (`profiles/held_time.log`).
 
-    python tools/held_time.py [--out profiles/held_time.log] [--reps 5] [--rows 1000000] [--edges 100000]
+    python tools/held_time.py [--out profiles/held_time.log] [--reps 5] [--rows 1000000] [--edges 100000] [--only records]
 
 The c2 and c3 arms with the box of the parity fixtures in the hand (half extents 0.1, 0.1, 0.2, margin 0.04, 0.25 m along the
 gripper's z; H = 1), its world copy parked out of reach.  Timing as tools/cloud_time.py: one HIP event pair around a window of
@@ -18,6 +18,11 @@ alternating.
                 configuration).  The yardstick is the scene's own entry on the same inputs in the same process (pair_distances,
                 edge_continuous, spline_continuous, spline_validity), per held item against per scene pair.  Each accumulated
                 result must equal the scene's entry on the box-as-link descriptor, bit for bit.
+    --only records  (log: profiles/held_records_time.log) nothing of the above but the record entries at --rows configurations:
+                held_records (every item: distance, witness, gradient row), the same without rows and without either, and
+                held_closest_records (held_distances, the argmin on the device, the listed record kernel), each beside
+                held_distances on the same inputs.  Distances, witnesses and rows must equal the held columns of
+                proximity_jacobian on the box-as-link descriptor, bit for bit.
 """
 import argparse
 import dataclasses
@@ -56,14 +61,43 @@ def box_as_link(sm, spec):
         pair_b=np.concatenate((np.where(sm.pair_b >= S, sm.pair_b + H, sm.pair_b), pb)).astype(np.int32))
 
 
+def records(say, name, dev, held, linked, qt, P, reps):
+    """The --only records section for one scene."""
+    B, K, n = int(qt.shape[0]), held.n_items, 16384
+    d, w, j = dev.held_records(held, qt[:n])
+    ref = linked.proximity_jacobian(qt[:n])
+    same = lambda a, b: torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))      # noqa: E731
+    if not (same(d, ref[0][:, P:]) and same(w, ref[1][:, P:]) and same(j, ref[2][:, P:])):
+        raise SystemExit(f"{name}: held_records != the held columns of proximity_jacobian(box as link)")
+    if not same(d, dev.held_distances(held, qt[:n])):
+        raise SystemExit(f"{name}: held_records' distances != held_distances")
+    cd, ci, cw, cj = dev.held_closest_records(held, qt[:n])
+    b = torch.arange(n, device="cuda")
+    if not (same(cd, d.min(dim=1).values) and same(cw, w[b, ci.long()]) and same(cj, j[b, ci.long()])):
+        raise SystemExit(f"{name}: held_closest_records != the dense record at the argmin")
+    say(f"records  B = {B}, K = {K} held items: records agree with proximity_jacobian(box as link) on the first {n} rows")
+    del d, w, j, ref, cd, ci, cw, cj
+    base = lambda: dev.held_distances(held, qt)      # noqa: E731
+    for what, fn in (("held_records (witness, rows)", lambda: dev.held_records(held, qt)),
+                     ("held_records (witness)", lambda: dev.held_records(held, qt, jacobian=False)),
+                     ("held_records (distance alone)", lambda: dev.held_records(held, qt, witness=False, jacobian=False)),
+                     ("held_closest_records", lambda: dev.held_closest_records(held, qt))):
+        t_r, t_d = timed_pair(fn, base, reps)
+        say(f"  {what:<35} {fmt(t_r)}   ({1e3 * t_r[0] / K:.1f} us per item)")
+        say(f"  {'held_distances beside it':<35} {fmt(t_d)}   (ratio {t_r[0] / t_d[0]:.2f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "held_time.log"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only", choices=("records",), default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rows", type=int, default=1000000)
     ap.add_argument("--edges", type=int, default=100000)
     ap.add_argument("--splines", type=int, default=10000)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "held_records_time.log" if args.only == "records" else "held_time.log")
     if not torch.cuda.is_available():
         raise SystemExit("tools/held_time.py needs a GPU: nothing is measured without one")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -90,6 +124,10 @@ def main():
         qt = torch.from_numpy(sample_q(chain, B, seed=3)).cuda()
         say(f"## {name}: {sm.n_rshapes} robot shapes, {sm.n_wshapes} world shapes, {sm.n_pairs} pairs; held pairs: "
             f"{len(spec.world_shapes)} world + {len(spec.robot_shapes)} robot")
+        if args.only == "records":
+            records(say, name, dev, held, linked, qt, sm.n_pairs, args.reps)
+            del linked, held, dev, qt
+            continue
         # ---- validity
         own = dev.validity(qt, 0.0, packed=True)
         both = linked.validity(qt, 0.0, packed=True)
