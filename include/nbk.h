@@ -821,8 +821,8 @@ int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const do
 
 /*
  * Held objects (additive; the reference fixes a body to a link with World.add_constraint, a Bullet dynamics constraint: here it is a
- * kinematic attachment for collision checks).  A held object is H shapes (1 .. 8; sphere, capsule, box, cylinder) riding on one link
- * of the descriptor it was made against.  The world pose of held shape h at configuration q is
+ * kinematic attachment for collision checks).  A held object is H shapes (1 .. 8; sphere, capsule, box, cylinder, and -- made by
+ * nbk_held_create_hulls -- convex hull) riding on one link of the descriptor it was made against.  The world pose of held shape h at configuration q is
  *     F(q) . ((A . G) . L_h)
  * F(q) the moving frame `frame` of the descriptor (-1: the base), A [12] the link's constant pose in that frame, G the grasp (the
  * object's pose in the link frame), L_h = shape_local[h] [12] the shape in the object's frame; all 3x4 row-major.  The two constant
@@ -842,9 +842,19 @@ int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const do
  *
  * nbk_held_create: one allocation and one copy; no later call allocates.  NBK_ERR_INVALID for a null pointer, H < 1, a frame outside
  * -1 .. n_joints-1, a non-finite pose or parameter, an unknown shape type, world indices out of range or not ascending;
- * NBK_ERR_UNSUPPORTED for H > 8, an NBK_HULL shape, or robot_bits on a descriptor of more than 256 robot shapes.  The descriptor
- * must outlive the held object, and must be the `m` of every call with it (NBK_ERR_INVALID otherwise, as for a device that is not
- * current).
+ * NBK_ERR_UNSUPPORTED for H > 8, an NBK_HULL shape (nbk_held_create_hulls takes those), or robot_bits on a descriptor of more than
+ * 256 robot shapes.  The descriptor must outlive the held object, and must be the `m` of every call with it (NBK_ERR_INVALID
+ * otherwise, as for a device that is not current).
+ *
+ * nbk_held_create_hulls: nbk_held_create with the hull tables of the held object behind its arguments -- n_hulls, hull_vert_begin,
+ * hull_verts, hull_face_begin, hull_planes in the layout and with the rules of nbk_model_desc's hull fields (a hull may have no
+ * planes).  A shape of type NBK_HULL names its hull in shape_param[h][0] and its margin in shape_param[h][3], as a robot shape does.
+ * The tables get the checks nbk_model_create gives a descriptor's (unit normals, planes that bound the vertex set, finite values):
+ * NBK_ERR_INVALID, as for a hull index outside 0 .. n_hulls-1, before any device is touched.  Still one allocation and one copy: the
+ * hulls travel in the held object's own blob.  Every entry of this section serves such an object, each result bit for bit what the
+ * descriptor above reports with the held hulls appended to its hull tables; the held-versus-cloud entries below answer
+ * NBK_ERR_UNSUPPORTED for it.  nbk_edge_held_motion_bounds_hulls_host / nbk_spline_held_motion_bounds_hulls_host are the host twins
+ * of the motion bound with the same tables behind the held arguments; the twins without them answer NBK_ERR_UNSUPPORTED for a hull.
  *
  * nbk_held_validity_batch: q (device) [B][n_q].  grasp (device) [grasp_rows][16], each row a 4x4 row-major pose whose first three rows
  * are read when the kernel runs (a replayed graph follows a grasp rewritten in place); grasp_rows = 0 (grasp NULL: the stored G), 1
@@ -909,6 +919,13 @@ int32_t nbk_held_create(const nbk_model *m, int32_t frame, const double *A /* ho
                         const int32_t *shape_type /* host [H] */, const double *shape_local /* host [H][12] */,
                         const double *shape_param /* host [H][4] */, int32_t n_world, const int32_t *world_shapes /* host */,
                         const uint64_t *robot_bits /* host, optional */, nbk_held **out);
+int32_t nbk_held_create_hulls(const nbk_model *m, int32_t frame, const double *A /* host [12] */, const double *G /* host [12] */,
+                              int32_t H, const int32_t *shape_type /* host [H] */, const double *shape_local /* host [H][12] */,
+                              const double *shape_param /* host [H][4] */, int32_t n_world, const int32_t *world_shapes /* host */,
+                              const uint64_t *robot_bits /* host, optional */, int32_t n_hulls,
+                              const int32_t *hull_vert_begin /* host [n_hulls+1] */, const double *hull_verts /* host [NV][3] */,
+                              const int32_t *hull_face_begin /* host [n_hulls+1] */, const double *hull_planes /* host [NF][4] */,
+                              nbk_held **out);
 void nbk_held_destroy(nbk_held *h);
 int32_t nbk_held_validity_batch(const nbk_model *m, const nbk_held *held, const double *q, int64_t B,
                                 const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double threshold,
@@ -957,6 +974,19 @@ int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc *d, int32_t fram
                                            int32_t n_world, const int32_t *world_shapes, const uint64_t *robot_bits /* optional */,
                                            const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                            const double *knots /* host */, double *mu /* [S][n_ctrl-degree][K] */);   /* no GPU */
+int32_t nbk_edge_held_motion_bounds_hulls_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                               const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                               int32_t n_world, const int32_t *world_shapes, const uint64_t *robot_bits /* optional */,
+                                               int32_t n_hulls, const int32_t *hull_vert_begin, const double *hull_verts,
+                                               const int32_t *hull_face_begin, const double *hull_planes, const double *starts,
+                                               const double *goals, int64_t E, double *mu /* [E][K] */);   /* no GPU */
+int32_t nbk_spline_held_motion_bounds_hulls_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                                 const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                                 int32_t n_world, const int32_t *world_shapes, const uint64_t *robot_bits /* optional */,
+                                                 int32_t n_hulls, const int32_t *hull_vert_begin, const double *hull_verts,
+                                                 const int32_t *hull_face_begin, const double *hull_planes, const double *ctrl, int64_t S,
+                                                 int32_t n_ctrl, int32_t degree, const double *knots /* host */,
+                                                 double *mu /* [S][n_ctrl-degree][K] */);   /* no GPU */
 
 /*
  * The held object against a point cloud: the held shapes in the robot shapes' place of the cloud's entries.  The verdict of held
@@ -996,6 +1026,10 @@ int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc *d, int32_t fram
  * grasp_rows outside {0, 1, B}, a grasp pointer that does not go with grasp_rows, a NaN threshold, a non-finite d_max, a workspace
  * too small or not 64-byte aligned, and a held object made against another descriptor.  Then the held object, the cloud and the
  * descriptor must be on the current device.  All calls are asynchronous, allocate nothing, and are capturable; LDS holds the q rows only.
+ *
+ * A held object with an NBK_HULL shape (nbk_held_create_hulls) is not served against a cloud yet: the entries of this section and
+ * the certified ones below answer NBK_ERR_UNSUPPORTED for it once their own argument rules are through, before any device is touched
+ * and without writing anything; the two *_held_shape_motion_bounds_host twins take no hull tables and answer it for a hull shape.
  */
 int32_t nbk_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *q, int64_t B,
                                       const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double threshold,

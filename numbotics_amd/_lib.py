@@ -47,6 +47,7 @@ SYMBOLS = [
     "nbk_edge_held_continuous_batch", "nbk_spline_held_continuous_batch",
     "nbk_spline_held_workspace_bytes", "nbk_spline_held_validity_batch",
     "nbk_edge_held_motion_bounds_host", "nbk_spline_held_motion_bounds_host",
+    "nbk_held_create_hulls", "nbk_edge_held_motion_bounds_hulls_host", "nbk_spline_held_motion_bounds_hulls_host",
     "nbk_held_cloud_validity_batch", "nbk_held_cloud_clearance_batch", "nbk_held_cloud_records_batch",
     "nbk_edge_held_cloud_workspace_bytes", "nbk_edge_held_cloud_validity_batch",
     "nbk_spline_held_cloud_workspace_bytes", "nbk_spline_held_cloud_validity_batch",
@@ -201,6 +202,10 @@ def load():
     held_args = [C.POINTER(ModelDesc), i32, vp, vp, i32, vp, vp, vp, i32, vp, vp]       # the descriptor, then nbk_held_create's
     lib.nbk_edge_held_motion_bounds_host.argtypes = held_args + [vp, vp, i64, vp]
     lib.nbk_spline_held_motion_bounds_host.argtypes = held_args + [vp, i64, i32, i32, vp, vp]
+    hull_args = [i32, vp, vp, vp, vp]                 # n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes
+    lib.nbk_held_create_hulls.argtypes = [vp] + held_args[1:] + hull_args + [C.POINTER(C.c_void_p)]
+    lib.nbk_edge_held_motion_bounds_hulls_host.argtypes = held_args + hull_args + [vp, vp, i64, vp]
+    lib.nbk_spline_held_motion_bounds_hulls_host.argtypes = held_args + hull_args + [vp, i64, i32, i32, vp, vp]
     lib.nbk_held_cloud_validity_batch.argtypes = [vp, vp, vp, vp, i64, vp, i64, f64, i32, vp, vp, vp]
     lib.nbk_held_cloud_clearance_batch.argtypes = [vp, vp, vp, vp, i64, vp, i64, f64, vp, vp, vp, vp]
     lib.nbk_held_cloud_records_batch.argtypes = [vp, vp, vp, vp, i64, vp, i64, f64, i32, vp, vp, vp, vp, vp, vp]

@@ -60,7 +60,10 @@ NBK_DEV void held_frame(const DevModel& m, unsigned mask, const double* myq, Xf&
     }
 }
 
-// core of held shape h from the holding frame F and A . G: build_core's robot branch with the local pose formed here
+// core of held shape h from the holding frame F and A . G: build_core's robot branch with the local pose formed here.  A held hull
+// has its three axes like a box and the HullRef of its tables (in the held blob) in h[].  HULLS = false leaves the hull case out:
+// the held-versus-cloud kernels, which are never given a held hull (their entries refuse one), keep the code they had.
+template <bool HULLS = true>
 NBK_DEV void held_core(const HeldDev& hd, int h, const Xf& F, const double* AG, Core& o) {
     const double* rec = hd.tab + 24 + HELD_SHAPE_LEN * h;
     double loc[12];
@@ -74,7 +77,7 @@ NBK_DEV void held_core(const HeldDev& hd, int h, const Xf& F, const double* AG, 
     xf_mul_pos(F, tl, o.c);
     if (o.kind == K_SEG || o.kind == K_CYL) {
         xf_mul_col(F, Rl, 2, o.ax[2]);
-    } else if (o.kind == K_BOX) {
+    } else if (o.kind == K_BOX || (HULLS && o.kind == K_HULL)) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) xf_mul_col(F, Rl, j, o.ax[j]);
     }
@@ -338,7 +341,7 @@ NBK_DEV void held_cloud_row_hits(const DevModel& m, const HeldDev& hd, const Clo
         cloud_core_init(Hc);
         double tc = 0.0, rs = 0.0;
         if (work) {
-            held_core(hd, h, F, AG, Hc);
+            held_core<false>(hd, h, F, AG, Hc);
             tc = (thr + Hc.margin) + radius;
             rs = (tc + Hc.rho) + 0.0;
         }
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_clearance(DevModel m, HeldDev
         for (int h = 0; h < hd.n_shapes; ++h) {
             Core Hc;
             cloud_core_init(Hc);
-            if (ok) held_core(hd, h, F, AG, Hc);
+            if (ok) held_core<false>(hd, h, F, AG, Hc);
             cloud_core_clearance(cd, Hc, P, radius, ok, h, d_max, best, bs, bi);
         }
     }
@@ -498,7 +501,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_records(DevModel m, HeldDev h
         for (int h = h0; h < h1; ++h) {
             Core Hc;
             cloud_core_init(Hc);
-            if (ok) held_core(hd, h, F, AG, Hc);
+            if (ok) held_core<false>(hd, h, F, AG, Hc);
             cloud_core_clearance(cd, Hc, P, radius, ok, h, d_max, best, bs, bi, &slot);
         }
     }
@@ -509,7 +512,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_records(DevModel m, HeldDev h
         held_frame(m, hd.mask, myq, F, out_j != nullptr ? L.jz(lds) + lane : nullptr);
         Core Hc;
         cloud_core_init(Hc);
-        held_core(hd, bs, F, AG, Hc);
+        held_core<false>(hd, bs, F, AG, Hc);
         const double* p = cd.pts + 3 * (size_t)slot;
         P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
         double fam = -1.0;
@@ -916,7 +919,7 @@ NBK_DEV double held_cloud_cut_distance(const DevModel& m, const HeldDev& hd, con
 #pragma unroll
         for (int e = 0; e < 12; ++e) G[e] = grow[e];
         held_mul12(hd.tab, G, AG);
-        held_core(hd, h, F, AG, Hc);
+        held_core<false>(hd, h, F, AG, Hc);
         D = D_end < d_cap ? D_end : d_cap;
     }
     double best = NBK_INF;
@@ -1073,6 +1076,7 @@ struct nbk_held {
     int device;
     void* blob;
     std::vector<int> h_items;      // the host copy of d.items
+    bool has_hull;                 // a held shape is a hull (nbk_held_create_hulls): the held-versus-cloud entries refuse it
 };
 
 namespace nbk {
@@ -1093,21 +1097,44 @@ static bool held_pose_finite(const double* p) {
     return true;
 }
 
-// the argument rules of the held shapes, their poses and the world list (nbk_held_create and the host twins of the motion bound)
+// the hull tables of a held object, in the layout and with the rules of nbk_model_desc's hull fields (nbk_held_create_hulls and the
+// *_hulls_host twins); the entries without them pass null and refuse a hull shape
+struct HeldHulls {
+    int32_t n;
+    const int32_t* vert_begin;
+    const double* verts;
+    const int32_t* face_begin;
+    const double* planes;
+    int nv(int h) const { return vert_begin[h + 1] - vert_begin[h]; }
+    int nf(int h) const { return face_begin[h + 1] - face_begin[h]; }
+};
+
+// the argument rules of the held shapes, their poses and the world list (the two creators and the host twins of the motion bound).
+// hl == null: a hull shape is NBK_ERR_UNSUPPORTED; else the tables pass desc_check's hull rules (a descriptor of nothing but them)
+// and a hull shape names one of them in param[0]
 static int32_t held_args_check(int32_t frame, int32_t n_joints, int32_t n_wshapes, const double* A, const double* G, int32_t H,
                                const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
-                               const int32_t* world_shapes) {
+                               const int32_t* world_shapes, const HeldHulls* hl = nullptr) {
     if (A == nullptr || G == nullptr || H < 1 || shape_type == nullptr || shape_local == nullptr || shape_param == nullptr ||
         n_world < 0 || (n_world > 0 && world_shapes == nullptr))
         return NBK_ERR_INVALID;
     if (frame < -1 || frame >= n_joints || n_world > n_wshapes) return NBK_ERR_INVALID;
     if (!held_pose_finite(A) || !held_pose_finite(G)) return NBK_ERR_INVALID;
     if (H > HELD_MAX_SHAPES) return NBK_ERR_UNSUPPORTED;
+    if (hl != nullptr) {
+        nbk_model_desc hd{};
+        hd.n_hulls = hl->n; hd.hull_vert_begin = hl->vert_begin; hd.hull_verts = hl->verts;
+        hd.hull_face_begin = hl->face_begin; hd.hull_planes = hl->planes;
+        if (desc_check(&hd, D_HULL_PLANES) != NBK_OK) return NBK_ERR_INVALID;
+    }
     for (int32_t h = 0; h < H; ++h) {
-        if (shape_type[h] == NBK_HULL) return NBK_ERR_UNSUPPORTED;
-        if (shape_type[h] != NBK_SPHERE && shape_type[h] != NBK_CAPSULE && shape_type[h] != NBK_BOX && shape_type[h] != NBK_CYLINDER) return NBK_ERR_INVALID;
+        if (shape_type[h] == NBK_HULL && hl == nullptr) return NBK_ERR_UNSUPPORTED;
+        if (shape_type[h] != NBK_SPHERE && shape_type[h] != NBK_CAPSULE && shape_type[h] != NBK_BOX && shape_type[h] != NBK_CYLINDER &&
+            shape_type[h] != NBK_HULL) return NBK_ERR_INVALID;
         if (!held_pose_finite(shape_local + 12 * (size_t)h)) return NBK_ERR_INVALID;
         for (int e = 0; e < 4; ++e) if (!(shape_param[4 * h + e] - shape_param[4 * h + e] == 0.0)) return NBK_ERR_INVALID;
+        const double idx = shape_param[4 * h];
+        if (shape_type[h] == NBK_HULL && !(idx >= 0.0 && idx < (double)hl->n && idx == (double)(int)idx)) return NBK_ERR_INVALID;
     }
     for (int32_t i = 0; i < n_world; ++i) {
         if (world_shapes[i] < 0 || world_shapes[i] >= n_wshapes) return NBK_ERR_INVALID;
@@ -1117,8 +1144,9 @@ static int32_t held_args_check(int32_t frame, int32_t n_joints, int32_t n_wshape
 }
 
 // A | G | the shape records (HeldDev.tab) and the core kinds
+// (a hull's h0 h1 h2 slot stays zero here: nbk_held_create_hulls patches the HullRef in once the blob's address is known)
 static void held_tab(const double* A, const double* G, int32_t H, const int32_t* shape_type, const double* shape_local,
-                     const double* shape_param, std::vector<double>& tab, std::vector<int>& kind) {
+                     const double* shape_param, std::vector<double>& tab, std::vector<int>& kind, const HeldHulls* hl = nullptr) {
     tab.assign(24 + HELD_SHAPE_LEN * (size_t)H, 0.0);
     kind.assign(H, 0);
     memcpy(&tab[0], A, 12 * sizeof(double));
@@ -1127,6 +1155,10 @@ static void held_tab(const double* A, const double* G, int32_t H, const int32_t*
         double* rec = &tab[24 + HELD_SHAPE_LEN * (size_t)h];
         memcpy(rec, shape_local + 12 * (size_t)h, 12 * sizeof(double));
         core_params(shape_type[h], shape_param + 4 * (size_t)h, kind[h], rec + 12);
+        if (kind[h] == K_HULL) {             // (robot_core_host's statements)
+            const int x = (int)shape_param[4 * (size_t)h];
+            rec[17] = hull_bound_radius(hl->verts + 3 * (size_t)hl->vert_begin[x], hl->nv(x));
+        }
         rec[17] = host_bound_radius(kind[h], rec + 12);
     }
 }
@@ -1157,21 +1189,36 @@ int32_t nbk_held_locals_host(const double* A, const double* G, const double* L, 
     return NBK_OK;
 }
 
-int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, const double* G, int32_t H, const int32_t* shape_type,
-                        const double* shape_local, const double* shape_param, int32_t n_world, const int32_t* world_shapes,
-                        const uint64_t* robot_bits, nbk_held** out) {
+// the body of the two creators (hl: the hull tables of nbk_held_create_hulls, null for nbk_held_create).  The blob: the tables, the
+// kinds, the world list, the items, then -- as the scene's hull_blob -- each hull's [local bounding box (6) | vertices], then every
+// hull's planes; the h0 h1 h2 slot of a hull shape's record holds its HullRef into them (patch_hulls' statements)
+static int32_t held_create(const nbk_model* m, int32_t frame, const double* A, const double* G, int32_t H, const int32_t* shape_type,
+                           const double* shape_local, const double* shape_param, int32_t n_world, const int32_t* world_shapes,
+                           const uint64_t* robot_bits, const HeldHulls* hl, nbk_held** out) {
     if (out == nullptr) return NBK_ERR_INVALID;
     *out = nullptr;
     if (m == nullptr) return NBK_ERR_INVALID;
-    { const int32_t rc = held_args_check(frame, m->n_joints, m->d.n_wshapes, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes);
+    { const int32_t rc = held_args_check(frame, m->n_joints, m->d.n_wshapes, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, hl);
       if (rc != NBK_OK) return rc; }
     if (robot_bits != nullptr && m->d.n_rshapes > 256) return NBK_ERR_UNSUPPORTED;
     NBK_DEVICE(m);
     // the tables, then one allocation and one copy
     std::vector<double> tab;
     std::vector<int> kind, world(n_world > 0 ? n_world : 1, 0);
-    held_tab(A, G, H, shape_type, shape_local, shape_param, tab, kind);
+    held_tab(A, G, H, shape_type, shape_local, shape_param, tab, kind, hl);
     for (int32_t i = 0; i < n_world; ++i) world[i] = world_shapes[i];
+    const int NH = hl != nullptr ? hl->n : 0;
+    std::vector<double> hverts;
+    std::vector<size_t> hoff(NH > 0 ? NH : 1, 0);      // offset (in doubles) of hull x's first vertex inside hverts
+    for (int x = 0; x < NH; ++x) {
+        const double* v = hl->verts + 3 * (size_t)hl->vert_begin[x];
+        double box[6];
+        hull_local_box(v, hl->nv(x), box);
+        hverts.insert(hverts.end(), box, box + 6);
+        hoff[x] = hverts.size();
+        hverts.insert(hverts.end(), v, v + 3 * (size_t)hl->nv(x));
+    }
+    const size_t n_planes = NH > 0 ? 4 * (size_t)hl->face_begin[NH] : 0;
     const int S = m->d.n_rshapes;
     std::vector<int> dev_of_user(S > 0 ? S : 1, 0);
     for (int i = 0; i < S; ++i) dev_of_user[m->h_rs_user[i]] = i;
@@ -1181,15 +1228,32 @@ int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, cons
     const size_t o_kind = up(sizeof(double) * tab.size());
     const size_t o_world = up(o_kind + sizeof(int) * kind.size());
     const size_t o_items = up(o_world + sizeof(int) * world.size());
-    const size_t bytes = up(o_items + sizeof(int) * (items.size() > 0 ? items.size() : 1));
+    const size_t o_verts = up(o_items + sizeof(int) * (items.size() > 0 ? items.size() : 1));
+    const size_t o_planes = up(o_verts + sizeof(double) * hverts.size());
+    const size_t bytes = up(o_planes + sizeof(double) * n_planes);
     std::vector<char> host(bytes, 0);
     memcpy(host.data(), tab.data(), sizeof(double) * tab.size());
     memcpy(host.data() + o_kind, kind.data(), sizeof(int) * kind.size());
     memcpy(host.data() + o_world, world.data(), sizeof(int) * world.size());
     if (!items.empty()) memcpy(host.data() + o_items, items.data(), sizeof(int) * items.size());
+    if (!hverts.empty()) memcpy(host.data() + o_verts, hverts.data(), sizeof(double) * hverts.size());
+    if (n_planes > 0) memcpy(host.data() + o_planes, hl->planes, sizeof(double) * n_planes);
     std::unique_ptr<nbk_held> hd(new nbk_held());
     hipError_t e = hipMalloc(&hd->blob, bytes);
     if (e != hipSuccess) { hip_fail(e, "hipMalloc(held)"); return NBK_ERR_ALLOC; }
+    hd->has_hull = false;
+    for (int32_t h = 0; h < H; ++h) {
+        if (kind[h] != K_HULL) continue;
+        const int x = (int)shape_param[4 * (size_t)h];
+        HullRef r;
+        r.hv = reinterpret_cast<const double*>(static_cast<const char*>(hd->blob) + o_verts) + hoff[x];
+        r.hp = reinterpret_cast<const double*>(static_cast<const char*>(hd->blob) + o_planes) + 4 * (size_t)hl->face_begin[x];
+        r.hn = hl->nv(x);
+        r.hf = hl->nf(x);
+        static_assert(sizeof(HullRef) == 24, "HullRef must overlay h[3]");
+        memcpy(host.data() + sizeof(double) * (24 + HELD_SHAPE_LEN * (size_t)h + 12), &r, sizeof(r));
+        hd->has_hull = true;
+    }
     e = hipMemcpy(hd->blob, host.data(), bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(hd->blob); return hip_fail(e, "hipMemcpy(held)"); }
     const char* base = static_cast<const char*>(hd->blob);
@@ -1207,6 +1271,20 @@ int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, cons
     (void)hipGetDevice(&hd->device);
     *out = hd.release();
     return NBK_OK;
+}
+
+int32_t nbk_held_create(const nbk_model* m, int32_t frame, const double* A, const double* G, int32_t H, const int32_t* shape_type,
+                        const double* shape_local, const double* shape_param, int32_t n_world, const int32_t* world_shapes,
+                        const uint64_t* robot_bits, nbk_held** out) {
+    return held_create(m, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, nullptr, out);
+}
+
+int32_t nbk_held_create_hulls(const nbk_model* m, int32_t frame, const double* A, const double* G, int32_t H, const int32_t* shape_type,
+                              const double* shape_local, const double* shape_param, int32_t n_world, const int32_t* world_shapes,
+                              const uint64_t* robot_bits, int32_t n_hulls, const int32_t* hull_vert_begin, const double* hull_verts,
+                              const int32_t* hull_face_begin, const double* hull_planes, nbk_held** out) {
+    const HeldHulls hl{n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes};
+    return held_create(m, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, &hl, out);
 }
 
 void nbk_held_destroy(nbk_held* h) {
@@ -1450,6 +1528,8 @@ int32_t nbk_spline_held_validity_batch(const nbk_model* m, const nbk_held* held,
 // ---- the held object against a point cloud.  What every entry answers once its own argument rules are through: the held object's
 // descriptor and device (held_call_begin), then the cloud's device.
 static int32_t held_cloud_call_begin(const nbk_model* m, const nbk_held* held, const nbk_cloud* c) {
+    // (held_cloud_collides and the cloud's clearance walk rely on "a held shape is never a hull": refused before a device is touched)
+    if (held->has_hull) { snprintf(g_err, sizeof(g_err), "a held object with a hull is not served against point clouds"); return NBK_ERR_UNSUPPORTED; }
     { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
     return cloud_check_device(c);
 }
@@ -1661,30 +1741,30 @@ int32_t nbk_spline_held_cloud_continuous_batch(const nbk_model* m, const nbk_hel
 static int32_t held_motion_host_begin(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
                                       const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
                                       const int32_t* world_shapes, const uint64_t* robot_bits, MotionHost& mh, unsigned& mask,
-                                      std::vector<double>& tab, std::vector<int>& items) {
+                                      std::vector<double>& tab, std::vector<int>& items, const HeldHulls* hl = nullptr) {
     if (d == nullptr) return NBK_ERR_INVALID;
     { const int32_t rc = desc_check(d, D_MOTION); if (rc != NBK_OK) return rc; }
-    { const int32_t rc = held_args_check(frame, d->n_joints, d->n_wshapes, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes);
+    { const int32_t rc = held_args_check(frame, d->n_joints, d->n_wshapes, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, hl);
       if (rc != NBK_OK) return rc; }
     const std::vector<unsigned> fm = frame_masks(d);
     motion_tables(d, fm, mh);
     mask = frame >= 0 ? fm[frame] : 0u;
     std::vector<int> kind;
-    held_tab(A, G, H, shape_type, shape_local, shape_param, tab, kind);
+    held_tab(A, G, H, shape_type, shape_local, shape_param, tab, kind, hl);
     items = held_item_list(d->n_rshapes, nullptr, robot_bits, H, n_world, world_shapes);
     return NBK_OK;
 }
 
-int32_t nbk_edge_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
-                                         const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
-                                         const int32_t* world_shapes, const uint64_t* robot_bits, const double* starts, const double* goals,
-                                         int64_t E, double* mu) {
+static int32_t edge_held_motion_bounds(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                       const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
+                                       const int32_t* world_shapes, const uint64_t* robot_bits, const HeldHulls* hl, const double* starts,
+                                       const double* goals, int64_t E, double* mu) {
     if (E < 0) return NBK_ERR_INVALID;
     MotionHost mh;
     unsigned mask = 0u;
     std::vector<double> tab;
     std::vector<int> items;
-    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, mh, mask, tab, items);
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, mh, mask, tab, items, hl);
       if (rc != NBK_OK) return rc; }
     const int64_t K = (int64_t)(items.size() / HELD_ITEM_LEN);
     if (E == 0 || K == 0) return NBK_OK;
@@ -1697,16 +1777,34 @@ int32_t nbk_edge_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame,
     return NBK_OK;
 }
 
-int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
-                                           const int32_t* shape_type, const double* shape_local, const double* shape_param,
-                                           int32_t n_world, const int32_t* world_shapes, const uint64_t* robot_bits, const double* ctrl,
-                                           int64_t S, int32_t n_ctrl, int32_t degree, const double* knots, double* mu) {
+int32_t nbk_edge_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                         const int32_t* shape_type, const double* shape_local, const double* shape_param, int32_t n_world,
+                                         const int32_t* world_shapes, const uint64_t* robot_bits, const double* starts, const double* goals,
+                                         int64_t E, double* mu) {
+    return edge_held_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, nullptr, starts,
+                                   goals, E, mu);
+}
+
+int32_t nbk_edge_held_motion_bounds_hulls_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                               const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                               int32_t n_world, const int32_t* world_shapes, const uint64_t* robot_bits, int32_t n_hulls,
+                                               const int32_t* hull_vert_begin, const double* hull_verts, const int32_t* hull_face_begin,
+                                               const double* hull_planes, const double* starts, const double* goals, int64_t E, double* mu) {
+    const HeldHulls hl{n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes};
+    return edge_held_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, &hl, starts,
+                                   goals, E, mu);
+}
+
+static int32_t spline_held_motion_bounds(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                         const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                         int32_t n_world, const int32_t* world_shapes, const uint64_t* robot_bits, const HeldHulls* hl,
+                                         const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots, double* mu) {
     if (S < 0 || !spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;
     MotionHost mh;
     unsigned mask = 0u;
     std::vector<double> tab;
     std::vector<int> items;
-    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, mh, mask, tab, items);
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, mh, mask, tab, items, hl);
       if (rc != NBK_OK) return rc; }
     const int64_t K = (int64_t)(items.size() / HELD_ITEM_LEN);
     const int nq = d->n_q, k = degree, L = n_ctrl - degree;
@@ -1724,6 +1822,25 @@ int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc* d, int32_t fram
         }
     }
     return NBK_OK;
+}
+
+int32_t nbk_spline_held_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                           const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                           int32_t n_world, const int32_t* world_shapes, const uint64_t* robot_bits, const double* ctrl,
+                                           int64_t S, int32_t n_ctrl, int32_t degree, const double* knots, double* mu) {
+    return spline_held_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, nullptr, ctrl,
+                                     S, n_ctrl, degree, knots, mu);
+}
+
+int32_t nbk_spline_held_motion_bounds_hulls_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                                 const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                                 int32_t n_world, const int32_t* world_shapes, const uint64_t* robot_bits, int32_t n_hulls,
+                                                 const int32_t* hull_vert_begin, const double* hull_verts, const int32_t* hull_face_begin,
+                                                 const double* hull_planes, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                                 const double* knots, double* mu) {
+    const HeldHulls hl{n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes};
+    return spline_held_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, &hl, ctrl,
+                                     S, n_ctrl, degree, knots, mu);
 }
 
 // ---- the host twins of the per-shape bound the held-versus-cloud lanes advance with: motion_terms over the whole holding path for

@@ -134,6 +134,15 @@ static double hull_bound_radius(const double* v, int n) {
     return sqrt(best);
 }
 
+// local bounding box of a hull's n vertices (centre, half extents rounded outwards): the six values in front of its vertex list
+// (the scene's hull blob and a held object's)
+static void hull_local_box(const double* v, int n, double* box) {
+    double lo[3] = {v[0], v[1], v[2]}, hi[3] = {v[0], v[1], v[2]};
+    for (int k = 1; k < n; ++k)
+        for (int j = 0; j < 3; ++j) { lo[j] = std::min(lo[j], v[3 * k + j]); hi[j] = std::max(hi[j], v[3 * k + j]); }
+    for (int j = 0; j < 3; ++j) { box[j] = 0.5 * (lo[j] + hi[j]); box[3 + j] = 0.5 * (hi[j] - lo[j]) * (1.0 + 1e-12) + 1e-300; }
+}
+
 static int host_core_rows(int kind) { return kind == K_POINT ? 3 : ((kind == K_BOX || kind == K_HULL) ? 12 : 6); }
 // core parameters of robot shape s as the descriptor stores them: h0 h1 h2 rad margin rho (rho: bounding radius about the centre)
 static void robot_core_host(const nbk_model_desc* d, int s, int& kind, double* cc) {
@@ -488,14 +497,8 @@ static void float_tables(const nbk_model_desc* d, const double* world_radius, Mo
     const int J = d->n_joints, S = d->n_rshapes, W = d->n_wshapes, H = d->n_hulls;
     // local bounding box of every hull (centre, half extents rounded outwards): the hull midphase culls against it
     t.hull_obb.assign(6 * (size_t)(H > 0 ? H : 1), 0.0);
-    for (int h = 0; h < H; ++h) {
-        const double* v = d->hull_verts + 3 * (size_t)d->hull_vert_begin[h];
-        const int n = d->hull_vert_begin[h + 1] - d->hull_vert_begin[h];
-        double lo[3] = {v[0], v[1], v[2]}, hi[3] = {v[0], v[1], v[2]};
-        for (int k = 1; k < n; ++k)
-            for (int j = 0; j < 3; ++j) { lo[j] = std::min(lo[j], v[3 * k + j]); hi[j] = std::max(hi[j], v[3 * k + j]); }
-        for (int j = 0; j < 3; ++j) { t.hull_obb[6 * h + j] = 0.5 * (lo[j] + hi[j]); t.hull_obb[6 * h + 3 + j] = 0.5 * (hi[j] - lo[j]) * (1.0 + 1e-12) + 1e-300; }
-    }
+    for (int h = 0; h < H; ++h)
+        hull_local_box(d->hull_verts + 3 * (size_t)d->hull_vert_begin[h], d->hull_vert_begin[h + 1] - d->hull_vert_begin[h], &t.hull_obb[6 * h]);
     std::vector<float>& ftab = t.ftab;
     double freach = 0.0;
     for (int k = 0; k < J; ++k) for (int e = 0; e < 27; ++e) ftab.push_back((float)d->joint_rot[27 * k + e]);

@@ -824,6 +824,15 @@ class DeviceModel:
             raise ValueError("held must be a DeviceHeld made against this descriptor")
         return held._h
 
+    def _held_scanless(self, held):
+        """``_held`` for the held-versus-cloud calls: their kernels decide with routines that know no held hull, so a held mesh
+        is refused here, before the cloud or a device is touched (nbk.h answers NBK_ERR_UNSUPPORTED for it)."""
+        h = self._held(held)
+        if held.has_hull:
+            raise ValueError("held meshes do not see scans yet: the held-versus-cloud calls serve boxes, spheres, capsules and "
+                             "cylinders only")
+        return h
+
     def held_validity(self, held, q, threshold=0.0, packed=False, pose=None, out=None):
         """In-collision flags of q for the held object ``held`` (a ``DeviceHeld`` of this descriptor) ALONE: its shapes against the
         world shapes and robot shapes it was resolved against (nbk_held_validity_batch); this descriptor's own pairs play no part,
@@ -1042,7 +1051,7 @@ class DeviceModel:
         with the object in the hand among what the camera sees.  A row whose q or grasp is not finite collides, every row while
         the cloud's status is set; an empty cloud is free."""
         torch = _require_gpu()
-        h = self._held(held)
+        h = self._held_scanless(held)
         qs = _Staged(q, self.n_q)
         g, rows = self._grasp(torch, pose, qs.B, True)
         want = ((qs.B + 63) // 64,) if packed else (qs.B,)
@@ -1065,7 +1074,7 @@ class DeviceModel:
         nothing is closer than ``d_max``; NaN, -1, -1 for a non-finite configuration or grasp or while the cloud's status is set.
         Ties: smallest held shape, then smallest point.  ``pose``: as ``held_validity``'s, one grasp or one per row."""
         torch = _require_gpu()
-        h = self._held(held)
+        h = self._held_scanless(held)
         qs = _Staged(q, self.n_q)
         g, rows = self._grasp(torch, pose, qs.B, True)
         d = torch.empty((qs.B,), dtype=torch.float64, device=qs.device)
@@ -1085,7 +1094,7 @@ class DeviceModel:
         point to the shape; rows = n . Jv_held(point on the shape), the gradient of the distance.  Nothing nearer than ``d_max``:
         inf, -1, -1, NaN witness, a row of zeros; a non-finite configuration or grasp or a set cloud status: NaN, -1, -1, NaN, NaN.
         ``pose``: as ``held_validity``'s, one grasp or one per row."""
-        h = self._held(held)
+        h = self._held_scanless(held)
         torch = _require_gpu()
         qs = _Staged(q, self.n_q)
         g, rows = self._grasp(torch, pose, qs.B, True)
@@ -1113,7 +1122,7 @@ class DeviceModel:
         (E, n_q), n_samples (E,) int32).  ``pose``: ONE grasp (4, 4) for the call.  ``out`` / ``workspace``: as
         ``cloud_edge_validity`` (``held_cloud_edge_workspace_bytes(E)``)."""
         torch = _require_gpu()
-        h = self._held(held)
+        h = self._held_scanless(held)
         s, g, dd = self._stage_edges(starts, goals, dist)
         gr, _ = self._grasp(torch, pose, s.B, False)
         valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
@@ -1138,7 +1147,7 @@ class DeviceModel:
         (valid (S,) bool, t_hit (S,), n_samples (S,) int32).  ``pose``: ONE grasp (4, 4) for the call.  ``out`` / ``workspace``: as
         ``held_spline_validity`` (``held_cloud_spline_workspace_bytes(S)``)."""
         torch = _require_gpu()
-        h = self._held(held)
+        h = self._held_scanless(held)
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         gr, _ = self._grasp(torch, pose, S, False)
         valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
@@ -1164,7 +1173,7 @@ class DeviceModel:
         edges, mode, max_distance and dist (``edge_continuous``, then ``cloud_edge_continuous(..., out=...)`` and
         ``held_edge_continuous(..., out=...)``): these items are reduced INTO them."""
         torch = _require_gpu()
-        h = self._held(held)
+        h = self._held_scanless(held)
         s, g, dd = self._stage_edges(starts, goals, dist)
         gr, _ = self._grasp(torch, pose, s.B, False)
         valid, t_free, status = self._result_triple(torch, out, s.B, s.device, "(valid, t_free, status)")
@@ -1185,7 +1194,7 @@ class DeviceModel:
         ``out``: as ``held_cloud_edge_continuous``, ``out`` being what an earlier certified spline call returned for the same
         trajectories."""
         torch = _require_gpu()
-        h = self._held(held)
+        h = self._held_scanless(held)
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         gr, _ = self._grasp(torch, pose, S, False)
         valid, t_free, status = self._result_triple(torch, out, S, c.device, "(valid, t_free, status)")
@@ -1385,6 +1394,20 @@ def _held_host_args(model, spec, G):
     return args, (A, G, st, L, sp, ws, bits), H * (len(robot) + int(ws.shape[0]))
 
 
+def _held_hull_args(hulls):
+    """The hull tables of a held object, (vert_begin, verts, face_begin, planes) as ``HullTable.arrays()`` gives them -> (the five
+    ctypes arguments behind nbk_held_create's, arrays they point into)."""
+    vb = np.ascontiguousarray(hulls[0], dtype=np.int32).reshape(-1)
+    hv = np.ascontiguousarray(hulls[1], dtype=np.float64).reshape(-1, 3)
+    fb = np.ascontiguousarray(hulls[2], dtype=np.int32).reshape(-1)
+    hp = np.ascontiguousarray(hulls[3], dtype=np.float64).reshape(-1, 4)
+    n = int(vb.shape[0]) - 1
+    if n < 0 or fb.shape[0] != n + 1 or (n > 0 and (int(vb[n]) != hv.shape[0] or int(fb[n]) != hp.shape[0])):
+        raise ValueError("held hull tables: vert_begin / face_begin must have n_hulls + 1 entries that end at the table sizes")
+    return (n, vb.ctypes.data, hv.ctypes.data if hv.shape[0] else None, fb.ctypes.data, hp.ctypes.data if hp.shape[0] else None), \
+        (vb, hv, fb, hp)
+
+
 def held_edge_motion_bounds(model, spec, starts, goals, G=None):
     """Motion bounds mu (E, K) of the linear edges starts -> goals for the K items of the held object ``spec`` (a ``HeldSpec``)
     on the SceneModel ``model``, in the items' order: the bits ``edge_motion_bounds`` gives for those pairs on a model that holds
@@ -1398,8 +1421,15 @@ def held_edge_motion_bounds(model, spec, starts, goals, G=None):
     d, keep = model_desc(model)
     args, keep2, K = _held_host_args(model, spec, G)
     mu = np.empty((s.shape[0], K), dtype=np.float64)
-    _lib.check(_lib.load().nbk_edge_held_motion_bounds_host(C.byref(d), *args, s.ctypes.data, g.ctypes.data, s.shape[0], mu.ctypes.data),
-               "nbk_edge_held_motion_bounds_host")
+    hulls = getattr(spec, "hulls", None)
+    if hulls is None:
+        _lib.check(_lib.load().nbk_edge_held_motion_bounds_host(C.byref(d), *args, s.ctypes.data, g.ctypes.data, s.shape[0],
+                                                                mu.ctypes.data), "nbk_edge_held_motion_bounds_host")
+    else:
+        hargs, keep3 = _held_hull_args(hulls)
+        _lib.check(_lib.load().nbk_edge_held_motion_bounds_hulls_host(C.byref(d), *args, *hargs, s.ctypes.data, g.ctypes.data, s.shape[0],
+                                                                      mu.ctypes.data), "nbk_edge_held_motion_bounds_hulls_host")
+        del keep3
     del keep, keep2
     return mu
 
@@ -1420,8 +1450,15 @@ def held_spline_motion_bounds(model, spec, ctrl, knots, degree, G=None):
     d, keep = model_desc(model)
     args, keep2, K = _held_host_args(model, spec, G)
     mu = np.zeros((S, n - k, K), dtype=np.float64)
-    _lib.check(_lib.load().nbk_spline_held_motion_bounds_host(C.byref(d), *args, c.ctypes.data, S, n, k, kn.ctypes.data, mu.ctypes.data),
-               "nbk_spline_held_motion_bounds_host")
+    hulls = getattr(spec, "hulls", None)
+    if hulls is None:
+        _lib.check(_lib.load().nbk_spline_held_motion_bounds_host(C.byref(d), *args, c.ctypes.data, S, n, k, kn.ctypes.data,
+                                                                  mu.ctypes.data), "nbk_spline_held_motion_bounds_host")
+    else:
+        hargs, keep3 = _held_hull_args(hulls)
+        _lib.check(_lib.load().nbk_spline_held_motion_bounds_hulls_host(C.byref(d), *args, *hargs, c.ctypes.data, S, n, k, kn.ctypes.data,
+                                                                        mu.ctypes.data), "nbk_spline_held_motion_bounds_hulls_host")
+        del keep3
     del keep, keep2
     return mu
 
@@ -1473,9 +1510,10 @@ class DeviceHeld:
     """A held object on the device (nbk_held): H shapes riding on moving frame ``frame`` of ``dev``'s descriptor, with the world
     shapes and robot shapes (``SceneModel`` order) its verdict looks at.  ``A``: the link's constant pose in the frame, ``G``: the
     default grasp, ``shape_local`` (H, 4, 4) / (H, 3, 4): each shape in the object's frame; ``shape_type`` / ``shape_param``: as a
-    robot shape's.  Allocated once; the descriptor is kept alive."""
+    robot shape's.  ``hulls``: the hull tables (vert_begin, verts, face_begin, planes) of held SH_HULL shapes -- given, the object is
+    made by nbk_held_create_hulls; without them a hull shape is refused.  Allocated once; the descriptor is kept alive."""
 
-    def __init__(self, dev, frame, A, G, shape_type, shape_local, shape_param, world_shapes=(), robot_shapes=()):
+    def __init__(self, dev, frame, A, G, shape_type, shape_local, shape_param, world_shapes=(), robot_shapes=(), hulls=None):
         _require_gpu()
         if dev.scene is None:
             raise ValueError("a held object needs a descriptor made from a SceneModel")
@@ -1490,10 +1528,16 @@ class DeviceHeld:
         robot = [int(x) for x in robot_shapes]
         bits = dev._shape_bits(robot) if robot else None
         h = C.c_void_p()
-        _lib.check(dev._lib.nbk_held_create(dev._h, int(frame), A.ctypes.data, G.ctypes.data, H, st.ctypes.data, L.ctypes.data,
-                                            sp.ctypes.data, int(ws.shape[0]), ws.ctypes.data if ws.shape[0] else None, _host_ptr(bits),
-                                            C.byref(h)), "nbk_held_create")
+        args = (dev._h, int(frame), A.ctypes.data, G.ctypes.data, H, st.ctypes.data, L.ctypes.data, sp.ctypes.data, int(ws.shape[0]),
+                ws.ctypes.data if ws.shape[0] else None, _host_ptr(bits))
+        if hulls is None:
+            _lib.check(dev._lib.nbk_held_create(*args, C.byref(h)), "nbk_held_create")
+        else:
+            hargs, keep = _held_hull_args(hulls)
+            _lib.check(dev._lib.nbk_held_create_hulls(*args, *hargs, C.byref(h)), "nbk_held_create_hulls")
+            del keep
         self._h, self._lib, self.dev, self.n_shapes = h, dev._lib, dev, H
+        self.has_hull = bool(np.any(st == 5))           # (the held-versus-cloud entries refuse such an object)
         self.n_items = int(dev._lib.nbk_held_item_count(h))
 
     def items(self):

@@ -579,7 +579,7 @@ class Arm(Robot):
         return mask.reshape(tuple(q.shape[:-1]))
 
     # ---- held objects ----------------------------------------------------------------------------------------
-    def attach(self, obj, link, pose=None, touch_links=()):
+    def attach(self, obj, link, pose=None, touch_links=(), meshes=False):
         """Put ``obj`` (a ``PhysicsObject`` of boxes / spheres / capsules / cylinders, or a list of up to 8 of them) into the hand:
         -> an ``Attachment`` (numbotics_amd.physics) of ``obj`` riding on ``link`` (a Link of this chain or its name).  ``pose``
         (4, 4): the grasp, the object's pose in the link frame (for a list: the first object's); default: the object where it
@@ -588,7 +588,9 @@ class Arm(Robot):
         every robot shape whose link is neither ``link``, nor shares its moving frame, nor is a touch link; the attachment is
         resolved again whenever the scene changes.  Check it with ``in_collision_with_attached`` or ``ConnectorParams(attached=...)``:
         ``in_collision`` does NOT see the held object, and still sees the object's world copy where it is one of this arm's
-        obstacles -- park it or ``remove_collision_pair`` it."""
+        obstacles -- park it or ``remove_collision_pair`` it.  ``meshes=True``: a ``Mesh`` may be held too, as its convex hulls -- one,
+        or one per object of its file with ``convex_decomposition=True``, by the routine link meshes go through; the hulls count
+        against the 8 shapes.  Such an attachment does not see scans: every ``cloud`` argument of the attached calls refuses it."""
         from numbotics_amd.physics import Attachment
         from .model import chain_link_poses
         link = self._resolve(link)
@@ -599,7 +601,7 @@ class Arm(Robot):
             if not objs or not isinstance(objs[0], PhysicsObject):
                 raise ValueError("the held object must be a PhysicsObject or a list of them")
             pose = np.linalg.inv(chain_link_poses(self._chain)[link._name]) @ np.asarray(objs[0].pose, dtype=np.float64)
-        att = Attachment(link, objs, pose, touch_links)
+        att = Attachment(link, objs, pose, touch_links, meshes=meshes)
         att.spec(self)                                          # argument errors now, not at the first query
         return att
 
@@ -614,6 +616,8 @@ class Arm(Robot):
         if q.shape[-1] != self.dof:
             raise ValueError(f"q must have {self.dof} elements")
         dev, held = att._device(self)
+        if cloud is not None:
+            dev._held_scanless(held)                              # (a held mesh: refused before anything runs)
         rows = q.reshape(-1, self.dof)
         mask = dev.held_validity(held, rows, threshold, pose=pose)
         if cloud is not None:

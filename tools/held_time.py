@@ -1,6 +1,6 @@
 """Held objects, measured on one GPU (`profiles/held_time.log`).
 
-    python tools/held_time.py [--out profiles/held_time.log] [--reps 5] [--rows 1000000] [--edges 100000] [--only records]
+    python tools/held_time.py [--out profiles/held_time.log] [--reps 5] [--rows 1000000] [--edges 100000] [--only records] [--mesh]
 
 The c2 and c3 arms with the box of the parity fixtures in the hand (half extents 0.1, 0.1, 0.2, margin 0.04, 0.25 m along the
 gripper's z; H = 1), its world copy parked out of reach.  Timing as tools/cloud_time.py: one HIP event pair around a window of
@@ -23,6 +23,12 @@ alternating.
                 held_closest_records (held_distances, the argmin on the device, the listed record kernel), each beside
                 held_distances on the same inputs.  Distances, witnesses and rows must equal the held columns of
                 proximity_jacobian on the box-as-link descriptor, bit for bit.
+    --mesh      (log: profiles/held_mesh_time.log) nothing of the above but what a held hull costs against the same object as a held
+                box: DeviceModel.held_validity at --rows configurations of c2 (packed words) with the package's rock.obj in the
+                gripper (``attach(..., meshes=True)``: one hull of 38 vertices and 72 planes, Bullet's 0.001 margin, 0.22 m along the
+                gripper's z) beside the box of the parity fixtures, the windows of the two alternating; then held_distances of
+                both at 65536 rows.  The hull's mask must equal validity(rock as link) with validity(plain) taken out of it, on
+                a descriptor that carries the hull as a robot shape of the gripper's frame with the hull appended to its tables.
 """
 import argparse
 import dataclasses
@@ -61,6 +67,58 @@ def box_as_link(sm, spec):
         pair_b=np.concatenate((np.where(sm.pair_b >= S, sm.pair_b + H, sm.pair_b), pb)).astype(np.int32))
 
 
+def mesh(say, args):
+    """The --mesh section: the rock in the gripper beside the parity box, on c2."""
+    from numbotics_amd.physics import Mesh
+    from numbotics_amd.scenes import MESH_DIR
+    _reset_worlds()
+    World()
+    arm, chain, obs = build_scene("c2")
+    park = np.array([0.0, 0.0, -6.0])
+    box = Cuboid(0.0, np.array([0.1, 0.1, 0.2]), collision_margin=0.04, position=park.copy())
+    rock = Mesh(0.0, os.path.join(MESH_DIR, "rock.obj"), position=park + np.array([0.0, 1.0, 0.0]))
+    Gb, Gr = np.eye(4), np.eye(4)
+    Gb[2, 3], Gr[2, 3] = 0.25, 0.22
+    att_b = arm.attach(box, "gripper", pose=Gb)
+    att_r = arm.attach(rock, "gripper", pose=Gr, meshes=True)
+    sm, sb, sr = arm.scene_model(), att_b.spec(arm), att_r.spec(arm)
+    dev, held_b = att_b._device(arm)
+    _, held_r = att_r._device(arm)
+    B = args.rows
+    qt = torch.from_numpy(sample_q(chain, B, seed=3)).cuda()
+    say(f"## c2 --mesh: {sm.n_rshapes} robot shapes, {sm.n_wshapes} world shapes; rock.obj: {sr.n_shapes} hull, "
+        f"{int(sr.hull_vert_begin[-1])} vertices, {int(sr.hull_face_begin[-1])} planes, margin {float(sr.shape_param[0][3])}; held pairs "
+        f"of either: {len(sr.world_shapes)} world + {len(sr.robot_shapes)} robot")
+    # the rock as a link shape: the held hull behind the scene's hulls, its index shifted
+    sp = sr.shape_param.copy()
+    sp[:, 0] += sm.n_hulls
+    as_link = box_as_link(sm, dataclasses.replace(sr, shape_param=sp))
+    as_link = dataclasses.replace(
+        as_link, hull_vert_begin=np.concatenate((sm.hull_vert_begin, sm.hull_vert_begin[-1] + sr.hull_vert_begin[1:])).astype(np.int32),
+        hull_verts=np.ascontiguousarray(np.concatenate((sm.hull_verts.reshape(-1, 3), sr.hull_verts))),
+        hull_face_begin=np.concatenate((sm.hull_face_begin, sm.hull_face_begin[-1] + sr.hull_face_begin[1:])).astype(np.int32),
+        hull_planes=np.ascontiguousarray(np.concatenate((sm.hull_planes.reshape(-1, 4), sr.hull_planes))))
+    linked = DeviceModel(as_link)
+    own = dev.validity(qt, 0.0, packed=True)
+    alone = dev.held_validity(held_r, qt, 0.0, packed=True)
+    if not torch.equal(linked.validity(qt, 0.0, packed=True), own | alone):
+        raise SystemExit("validity(rock as link) != validity(plain) | held_validity(rock)")
+    share = lambda w: sum(bin(int(v) & 0xFFFFFFFFFFFFFFFF).count("1") for v in w.cpu().numpy()[:1000]) / 64000.0      # noqa: E731
+    say(f"validity  B = {B}: masks agree; of the first 64000 rows the rock collides in {share(alone):.3f}, the box in "
+        f"{share(dev.held_validity(held_b, qt, 0.0, packed=True)):.3f}")
+    t_r, t_b = timed_pair(lambda: dev.held_validity(held_r, qt, 0.0, packed=True), lambda: dev.held_validity(held_b, qt, 0.0, packed=True), args.reps)
+    say(f"  held_validity, rock.obj (hull)      {fmt(t_r)}")
+    say(f"  held_validity, parity box           {fmt(t_b)}   (hull / box: {t_r[0] / t_b[0]:.2f})")
+    n = 65536
+    d_r = dev.held_distances(held_r, qt[:n])
+    if not torch.equal(d_r.view(torch.int64), linked.pair_distances(qt[:n])[:, sm.n_pairs:].contiguous().view(torch.int64)):
+        raise SystemExit("held_distances(rock) != the held columns of pair_distances(rock as link)")
+    t_r, t_b = timed_pair(lambda: dev.held_distances(held_r, qt[:n]), lambda: dev.held_distances(held_b, qt[:n]), args.reps)
+    say(f"distances  B = {n}, K = {held_r.n_items} items of either: the rock's agree with pair_distances(rock as link)")
+    say(f"  held_distances, rock.obj (hull)     {fmt(t_r)}")
+    say(f"  held_distances, parity box          {fmt(t_b)}   (hull / box: {t_r[0] / t_b[0]:.2f})")
+
+
 def records(say, name, dev, held, linked, qt, P, reps):
     """The --only records section for one scene."""
     B, K, n = int(qt.shape[0]), held.n_items, 16384
@@ -95,9 +153,11 @@ def main():
     ap.add_argument("--rows", type=int, default=1000000)
     ap.add_argument("--edges", type=int, default=100000)
     ap.add_argument("--splines", type=int, default=10000)
+    ap.add_argument("--mesh", action="store_true")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "held_records_time.log" if args.only == "records" else "held_time.log")
+        args.out = os.path.join(ROOT, "profiles", "held_mesh_time.log" if args.mesh else
+                                "held_records_time.log" if args.only == "records" else "held_time.log")
     if not torch.cuda.is_available():
         raise SystemExit("tools/held_time.py needs a GPU: nothing is measured without one")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -109,6 +169,10 @@ def main():
         log.flush()
 
     say(f"# tools/held_time.py  build {source_digest()}  {torch.cuda.get_device_name(0)}  rows {args.rows}  edges {args.edges}  reps {args.reps}")
+    if args.mesh:
+        mesh(say, args)
+        log.close()
+        return
     for name in ("c2", "c3"):
         _reset_worlds()
         World()
