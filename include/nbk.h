@@ -853,7 +853,7 @@ int32_t nbk_spline_shape_motion_bounds_host(const nbk_model_desc *desc, const do
  * NBK_ERR_INVALID, as for a hull index outside 0 .. n_hulls-1, before any device is touched.  Still one allocation and one copy: the
  * hulls travel in the held object's own blob.  Every entry of this section serves such an object, each result bit for bit what the
  * descriptor above reports with the held hulls appended to its hull tables; the held-versus-cloud entries below answer
- * NBK_ERR_UNSUPPORTED for it.  nbk_edge_held_motion_bounds_hulls_host / nbk_spline_held_motion_bounds_hulls_host are the host twins
+ * NBK_ERR_UNSUPPORTED for it unless nbk_held_set_cloud_hulls has opted it in.  nbk_edge_held_motion_bounds_hulls_host / nbk_spline_held_motion_bounds_hulls_host are the host twins
  * of the motion bound with the same tables behind the held arguments; the twins without them answer NBK_ERR_UNSUPPORTED for a hull.
  *
  * nbk_held_validity_batch: q (device) [B][n_q].  grasp (device) [grasp_rows][16], each row a 4x4 row-major pose whose first three rows
@@ -1027,10 +1027,21 @@ int32_t nbk_spline_held_motion_bounds_hulls_host(const nbk_model_desc *d, int32_
  * too small or not 64-byte aligned, and a held object made against another descriptor.  Then the held object, the cloud and the
  * descriptor must be on the current device.  All calls are asynchronous, allocate nothing, and are capturable; LDS holds the q rows only.
  *
- * A held object with an NBK_HULL shape (nbk_held_create_hulls) is not served against a cloud yet: the entries of this section and
- * the certified ones below answer NBK_ERR_UNSUPPORTED for it once their own argument rules are through, before any device is touched
- * and without writing anything; the two *_held_shape_motion_bounds_host twins take no hull tables and answer it for a hull shape.
+ * A held object with an NBK_HULL shape (nbk_held_create_hulls) is served against a cloud only after it has opted in:
+ * nbk_held_set_cloud_hulls(held, on) sets (on != 0) or clears a host-side flag on the object -- no device work, no kernel reads it;
+ * the creators clear it; NBK_ERR_INVALID for a null held; an object without hulls takes the call and nothing changes for it.  Without
+ * the flag the entries of this section and the certified ones below answer NBK_ERR_UNSUPPORTED for such an object once their own
+ * argument rules are through, before any device is touched and without writing anything.  With it all seven serve the object, each
+ * result bit for bit that of the descriptor above with the held hulls appended to its hull tables: the three verdict entries run a
+ * second instance of their kernels (chosen by whether the object holds a hull; the instance of an object without one is unchanged)
+ * in which a hull is decided by the cloud's own predicate -- a hull at tc = (threshold + margin_h) + radius <= 0 goes straight to
+ * the distance iteration, so the hull-box cull's deviation at tc <= 0 does not apply -- and the four distance entries give a hull the
+ * treatment a hull link shape gets.  The two *_held_shape_motion_bounds_host twins take no hull tables and answer
+ * NBK_ERR_UNSUPPORTED for a hull shape; nbk_edge_held_shape_motion_bounds_hulls_host / nbk_spline_held_shape_motion_bounds_hulls_host
+ * take the tables of nbk_held_create_hulls behind the held arguments (checked by nbk_model_desc's hull rules: NBK_ERR_INVALID) and
+ * are otherwise the same routine.
  */
+int32_t nbk_held_set_cloud_hulls(nbk_held *held, int32_t on);
 int32_t nbk_held_cloud_validity_batch(const nbk_model *m, const nbk_held *held, const nbk_cloud *cloud, const double *q, int64_t B,
                                       const double *grasp /* DEVICE [grasp_rows][16] or NULL */, int64_t grasp_rows, double threshold,
                                       int32_t accumulate, uint64_t *mask_bits, uint8_t *mask_bytes, void *stream);
@@ -1102,6 +1113,17 @@ int32_t nbk_spline_held_shape_motion_bounds_host(const nbk_model_desc *d, int32_
                                                  const int32_t *shape_type, const double *shape_local, const double *shape_param,
                                                  const double *ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                                  const double *knots /* host */, double *mu /* [S][n_ctrl-degree][H] */);   /* no GPU */
+int32_t nbk_edge_held_shape_motion_bounds_hulls_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                                     const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                                     int32_t n_hulls, const int32_t *hull_vert_begin, const double *hull_verts,
+                                                     const int32_t *hull_face_begin, const double *hull_planes, const double *starts,
+                                                     const double *goals, int64_t E, double *mu /* [E][H] */);   /* no GPU */
+int32_t nbk_spline_held_shape_motion_bounds_hulls_host(const nbk_model_desc *d, int32_t frame, const double *A, const double *G, int32_t H,
+                                                       const int32_t *shape_type, const double *shape_local, const double *shape_param,
+                                                       int32_t n_hulls, const int32_t *hull_vert_begin, const double *hull_verts,
+                                                       const int32_t *hull_face_begin, const double *hull_planes, const double *ctrl,
+                                                       int64_t S, int32_t n_ctrl, int32_t degree, const double *knots /* host */,
+                                                       double *mu /* [S][n_ctrl-degree][H] */);   /* no GPU */
 
 /*
  * Exact k nearest neighbours of every point among the points inserted before it (itself included): the neighbour lists

@@ -53,6 +53,7 @@ SYMBOLS = [
     "nbk_spline_held_cloud_workspace_bytes", "nbk_spline_held_cloud_validity_batch",
     "nbk_edge_held_cloud_continuous_batch", "nbk_spline_held_cloud_continuous_batch",
     "nbk_edge_held_shape_motion_bounds_host", "nbk_spline_held_shape_motion_bounds_host",
+    "nbk_held_set_cloud_hulls", "nbk_edge_held_shape_motion_bounds_hulls_host", "nbk_spline_held_shape_motion_bounds_hulls_host",
 ]
 MAX_SPLINE_DEGREE = 5       # NBK_MAX_SPLINE_DEGREE
 
@@ -221,6 +222,9 @@ def load():
     held_shape_args = held_args[:8]                                                     # (no world list, no robot set)
     lib.nbk_edge_held_shape_motion_bounds_host.argtypes = held_shape_args + [vp, vp, i64, vp]
     lib.nbk_spline_held_shape_motion_bounds_host.argtypes = held_shape_args + [vp, i64, i32, i32, vp, vp]
+    lib.nbk_held_set_cloud_hulls.argtypes = [vp, i32]
+    lib.nbk_edge_held_shape_motion_bounds_hulls_host.argtypes = held_shape_args + hull_args + [vp, vp, i64, vp]
+    lib.nbk_spline_held_shape_motion_bounds_hulls_host.argtypes = held_shape_args + hull_args + [vp, i64, i32, i32, vp, vp]
     lib.nbk_debug_set_option.argtypes = [C.c_char_p, i64]
     lib.nbk_debug_narrow_variant.argtypes = [vp, f64]
     lib.nbk_debug_last_tiling.argtypes = [vp, C.POINTER(i64)]

@@ -62,7 +62,8 @@ NBK_DEV void held_frame(const DevModel& m, unsigned mask, const double* myq, Xf&
 
 // core of held shape h from the holding frame F and A . G: build_core's robot branch with the local pose formed here.  A held hull
 // has its three axes like a box and the HullRef of its tables (in the held blob) in h[].  HULLS = false leaves the hull case out:
-// the held-versus-cloud kernels, which are never given a held hull (their entries refuse one), keep the code they had.
+// the hull-free instances of the held-versus-cloud verdict kernels, which are never given a held hull (their entries pick the
+// other instance for one), keep the code they had.
 template <bool HULLS = true>
 NBK_DEV void held_core(const HeldDev& hd, int h, const Xf& F, const double* AG, Core& o) {
     const double* rec = hd.tab + 24 + HELD_SHAPE_LEN * h;
@@ -310,16 +311,22 @@ __global__ __launch_bounds__(64) void k_held_spline(DevModel m, HeldDev hd, cons
 // held-versus-cloud term ALONE: no world shape and no link takes part, the world status is not read, and the attachment's world
 // list and robot set play no part.
 
-// cloud_collides(P, Hc, tc) for a point core P and a held core Hc.  A held shape is never a hull, so cloud_collides is
+// cloud_collides(P, Hc, tc) for a point core P and a held core Hc that is NO hull.  There cloud_collides is
 // cores_collide_exact, and for a point core first and a second core that is no hull cores_collide_pre decides EVERY pair -- box
 // cores in its midphase or, like cylinder cores, in its last statement (point_solid), point and segment cores in ps_closest -- and never
 // answers -1: cores_collide_exact returns `pre != 0` there, bit for bit.  Calling the routine that decides keeps the three GJK
 // walks behind it out of these kernels (their scratch arrays and spills with them).  (-1 cannot come; it would read "collides".)
 NBK_DEV bool held_cloud_collides(const Core& P, const Core& Hc, double tc) { return cores_collide_pre(P, Hc, tc) != 0; }
 
-// The walk: cloud_row_hits with held_core in build_core's place (held shapes are never hulls: no scalar-cache path).  Called by
-// every lane of the wave (`active`, `hit` as in held_row_hits); the caller has checked that the cloud holds points and that its
-// status is clear.
+// The walk: cloud_row_hits with held_core in build_core's place.  Called by every lane of the wave (`active`, `hit` as in
+// held_row_hits); the caller has checked that the cloud holds points and that its status is clear.  HULLS = false is the walk of an
+// attachment without a hull, statement for statement what it was before hulls were served: held_cloud_collides decides every
+// pair and no GJK walk is compiled in.  HULLS = true serves an attachment that holds a hull: the loop over h is wave-uniform, so
+// every working lane holds THIS held shape -- a hull core takes the scalar-cache path (rad = -1.0, as in cloud_row_hits) and is
+// decided by cloud_collides (which, for a hull at tc <= 0, goes straight to gjk_collides: hull_box_far's deviation there does not
+// apply), a primitive shape of the same attachment by held_cloud_collides as before; hd.kind[h] is a uniform load, the branch a
+// uniform one.
+template <bool HULLS>
 NBK_DEV void held_cloud_row_hits(const DevModel& m, const HeldDev& hd, const CloudDev& cd, const double* grasp_row, double radius,
                                  double thr, const double* myq, bool active, bool& hit) {
     if (__builtin_amdgcn_ballot_w64(active && !hit) == 0ull) return;
@@ -341,7 +348,8 @@ NBK_DEV void held_cloud_row_hits(const DevModel& m, const HeldDev& hd, const Clo
         cloud_core_init(Hc);
         double tc = 0.0, rs = 0.0;
         if (work) {
-            held_core<false>(hd, h, F, AG, Hc);
+            held_core<HULLS>(hd, h, F, AG, Hc);
+            if (HULLS && Hc.kind == K_HULL) Hc.rad = -1.0;      // every working lane holds this hull: the scalar cache serves its vertices
             tc = (thr + Hc.margin) + radius;
             rs = (tc + Hc.rho) + 0.0;
         }
@@ -360,13 +368,20 @@ NBK_DEV void held_cloud_row_hits(const DevModel& m, const HeldDev& hd, const Clo
                 cand = dot3(dc, dc) < rs2;
             }
             if (__builtin_amdgcn_ballot_w64(cand) == 0ull) break;
-            if (cand && held_cloud_collides(P, Hc, tc)) hit = true;
+            if constexpr (HULLS) {
+                if (hd.kind[h] == K_HULL) { if (cand && cloud_collides(P, Hc, tc)) hit = true; }
+                else if (cand && held_cloud_collides(P, Hc, tc)) hit = true;
+            } else {
+                if (cand && held_cloud_collides(P, Hc, tc)) hit = true;
+            }
         }
     }
 }
 
 // verdict of row b = the walk's, or 1 for a non-finite q or grasp row or a set cloud status; an empty cloud is free.  k_held_validity's
-// frame: a workgroup owns one mask word, so the word and the bytes have one writer each.
+// frame: a workgroup owns one mask word, so the word and the bytes have one writer each.  HULLS: the walk's instance (the entry picks
+// it by nbk_held.has_hull).
+template <bool HULLS>
 __global__ __launch_bounds__(64) void k_held_cloud_validity(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ q, int64_t B,
                                                             const double* __restrict__ grasp, int grasp_rows, double thr, int accumulate,
                                                             unsigned long long* __restrict__ mask_bits, uint8_t* __restrict__ mask_bytes) {
@@ -385,7 +400,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_validity(DevModel m, HeldDev 
         grow = held_grasp_row(hd, grasp, grasp_rows, b, gfin);
         hit = !cloud_stage_q(q, b, m.n_q, myq) || !gfin || status != 0;
     }
-    if (n > 0 && status == 0) held_cloud_row_hits(m, hd, cd, grow, radius, thr, myq, active, hit);
+    if (n > 0 && status == 0) held_cloud_row_hits<HULLS>(m, hd, cd, grow, radius, thr, myq, active, hit);
     const unsigned long long word = __builtin_amdgcn_ballot_w64(active && hit);
     if (mask_bits != nullptr && lane == 0) {
         if (accumulate) { if (word != 0ull) mask_bits[blockIdx.x] |= word; }
@@ -436,7 +451,10 @@ __global__ __launch_bounds__(64) void k_held_cloud_clearance(DevModel m, HeldDev
         for (int h = 0; h < hd.n_shapes; ++h) {
             Core Hc;
             cloud_core_init(Hc);
-            if (ok) held_core<false>(hd, h, F, AG, Hc);
+            if (ok) {
+                held_core(hd, h, F, AG, Hc);
+                if (Hc.kind == K_HULL) Hc.rad = -1.0;      // h is wave-uniform: every working lane holds this hull (k_cloud_clearance's rule)
+            }
             cloud_core_clearance(cd, Hc, P, radius, ok, h, d_max, best, bs, bi);
         }
     }
@@ -454,7 +472,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_clearance(DevModel m, HeldDev
 //      -- and writes column h of [B][H].
 //   2. the record, for the lanes that hold a winner and only when a witness or a row is asked for: the holding frame once more (the
 //      same joint_apply sequence, so the same frame bits), with joint_frame_rows into the [J][6][64] LDS rows when rows are asked
-//      for; held_core of the winning shape; cores_distance<true, true> and epa_refine<true> on (held core, point core) --
+//      for; held_core of the winning shape (a hull through per-lane loads: the lanes' winners may differ); cores_distance<true, true> and epa_refine<true> on (held core, point core) --
 //      item_distance's statements for a (robot shape, sphere world shape) pair; prox_row_masks with the holding frame's mask and 0.
 //      The distance this phase finds is the one reported where it runs: the bits of phase 1.
 // Nothing nearer than d_max: +inf, -1, -1, NaN witness, a row of +0.0.  A non-finite q or grasp row or a set status: NaN, -1, -1, NaN,
@@ -501,7 +519,10 @@ __global__ __launch_bounds__(64) void k_held_cloud_records(DevModel m, HeldDev h
         for (int h = h0; h < h1; ++h) {
             Core Hc;
             cloud_core_init(Hc);
-            if (ok) held_core<false>(hd, h, F, AG, Hc);
+            if (ok) {
+                held_core(hd, h, F, AG, Hc);
+                if (Hc.kind == K_HULL) Hc.rad = -1.0;      // h is wave-uniform here, in the dense loop and with blockIdx.y = h
+            }
             cloud_core_clearance(cd, Hc, P, radius, ok, h, d_max, best, bs, bi, &slot);
         }
     }
@@ -512,7 +533,9 @@ __global__ __launch_bounds__(64) void k_held_cloud_records(DevModel m, HeldDev h
         held_frame(m, hd.mask, myq, F, out_j != nullptr ? L.jz(lds) + lane : nullptr);
         Core Hc;
         cloud_core_init(Hc);
-        held_core<false>(hd, bs, F, AG, Hc);
+        // (each lane builds the core of its OWN winner and the lanes may differ: a hull keeps its per-lane vertex loads here, rad
+        // stays as the tables have it; the comparisons and the vertex are those of the scalar-cache path, so the bits are phase 1's)
+        held_core(hd, bs, F, AG, Hc);
         const double* p = cd.pts + 3 * (size_t)slot;
         P.c[0] = p[0]; P.c[1] = p[1]; P.c[2] = p[2];
         double fam = -1.0;
@@ -538,6 +561,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_records(DevModel m, HeldDev h
 
 // k_cloud_edges with the held walk against the cloud (nbk_edge_held_cloud_validity_batch): the plan, the scan and k_cloud_edges_init
 // are the cloud's.  One grasp per call; a non-finite grasp or a set cloud status makes every non-degenerate edge invalid.
+template <bool HULLS>
 __global__ __launch_bounds__(64) void k_held_cloud_edges(DevModel m, HeldDev hd, CloudDev cd, EdgeSrc es,
                                                          const unsigned long long* __restrict__ offs, int64_t E,
                                                          const double* __restrict__ grasp, int grasp_rows, double thr, uint8_t* valid) {
@@ -564,7 +588,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_edges(DevModel m, HeldDev hd,
             }
         }
         bool hit = false;
-        if (n > 0 && !bad) held_cloud_row_hits(m, hd, cd, grow, radius, thr, myq, work, hit);
+        if (n > 0 && !bad) held_cloud_row_hits<HULLS>(m, hd, cd, grow, radius, thr, myq, work, hit);
         if (hit) __hip_atomic_store(valid + e, (uint8_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -572,7 +596,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_edges(DevModel m, HeldDev hd,
 // k_cloud_spline with the held walk against the cloud and the call's grasp (nbk_spline_held_cloud_validity_batch): the same plan,
 // scan, first-hit key (SPC_*) and accumulate rules; k_cloud_spline_init (hold: the cloud's status) and k_cloud_spline_final are the
 // cloud's.  A non-finite grasp hits every sample that is looked at, as in k_held_spline.
-template <int K>
+template <int K, bool HULLS>
 __global__ __launch_bounds__(64) void k_held_cloud_spline(DevModel m, HeldDev hd, CloudDev cd, const double* __restrict__ ctrl, int n,
                                                           const double* __restrict__ knots, const double* __restrict__ plan,
                                                           const unsigned long long* __restrict__ offs, int64_t S,
@@ -607,7 +631,7 @@ __global__ __launch_bounds__(64) void k_held_cloud_spline(DevModel m, HeldDev hd
                 }
             }
         }
-        if (ncl > 0 && gfin) held_cloud_row_hits(m, hd, cd, grow, radius, thr, myq, work, hit);
+        if (ncl > 0 && gfin) held_cloud_row_hits<HULLS>(m, hd, cd, grow, radius, thr, myq, work, hit);
         if (hit) atomicMin(first + s, j + 1ull);
     }
 }
@@ -919,7 +943,8 @@ NBK_DEV double held_cloud_cut_distance(const DevModel& m, const HeldDev& hd, con
 #pragma unroll
         for (int e = 0; e < 12; ++e) G[e] = grow[e];
         held_mul12(hd.tab, G, AG);
-        held_core<false>(hd, h, F, AG, Hc);
+        held_core(hd, h, F, AG, Hc);
+        if (Hc.kind == K_HULL) Hc.rad = -1.0;      // the certified grids have blockIdx.y = h: every working lane holds this hull
         D = D_end < d_cap ? D_end : d_cap;
     }
     double best = NBK_INF;
@@ -1076,7 +1101,9 @@ struct nbk_held {
     int device;
     void* blob;
     std::vector<int> h_items;      // the host copy of d.items
-    bool has_hull;                 // a held shape is a hull (nbk_held_create_hulls): the held-versus-cloud entries refuse it
+    bool has_hull;                 // a held shape is a hull (nbk_held_create_hulls)
+    bool cloud_hulls;              // nbk_held_set_cloud_hulls: the held-versus-cloud entries serve the hulls (host side only: no kernel
+                                   // reads it); cleared by the creators, and without it those entries refuse an object that has a hull
 };
 
 namespace nbk {
@@ -1163,6 +1190,13 @@ static void held_tab(const double* A, const double* G, int32_t H, const int32_t*
     }
 }
 
+// f(std::true_type / std::false_type) for a run-time flag (with_degree's form): the verdict entries pick their walk's instance
+template <class F>
+static void with_flag(bool on, F&& f) {
+    if (on) f(std::integral_constant<bool, true>{});
+    else f(std::integral_constant<bool, false>{});
+}
+
 // the items (HeldDev.items): robot_bits in the caller's order over S shapes (null: none); dev_of_user (nullable): the device index
 // of each of the caller's shapes, else the caller's index stands in
 static std::vector<int> held_item_list(int S, const int* dev_of_user, const uint64_t* robot_bits, int H, int n_world, const int32_t* world) {
@@ -1242,6 +1276,7 @@ static int32_t held_create(const nbk_model* m, int32_t frame, const double* A, c
     hipError_t e = hipMalloc(&hd->blob, bytes);
     if (e != hipSuccess) { hip_fail(e, "hipMalloc(held)"); return NBK_ERR_ALLOC; }
     hd->has_hull = false;
+    hd->cloud_hulls = false;
     for (int32_t h = 0; h < H; ++h) {
         if (kind[h] != K_HULL) continue;
         const int x = (int)shape_param[4 * (size_t)h];
@@ -1285,6 +1320,12 @@ int32_t nbk_held_create_hulls(const nbk_model* m, int32_t frame, const double* A
                               const int32_t* hull_face_begin, const double* hull_planes, nbk_held** out) {
     const HeldHulls hl{n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes};
     return held_create(m, frame, A, G, H, shape_type, shape_local, shape_param, n_world, world_shapes, robot_bits, &hl, out);
+}
+
+int32_t nbk_held_set_cloud_hulls(nbk_held* held, int32_t on) {
+    if (held == nullptr) return NBK_ERR_INVALID;
+    held->cloud_hulls = on != 0;
+    return NBK_OK;
 }
 
 void nbk_held_destroy(nbk_held* h) {
@@ -1528,8 +1569,8 @@ int32_t nbk_spline_held_validity_batch(const nbk_model* m, const nbk_held* held,
 // ---- the held object against a point cloud.  What every entry answers once its own argument rules are through: the held object's
 // descriptor and device (held_call_begin), then the cloud's device.
 static int32_t held_cloud_call_begin(const nbk_model* m, const nbk_held* held, const nbk_cloud* c) {
-    // (held_cloud_collides and the cloud's clearance walk rely on "a held shape is never a hull": refused before a device is touched)
-    if (held->has_hull) { snprintf(g_err, sizeof(g_err), "a held object with a hull is not served against point clouds"); return NBK_ERR_UNSUPPORTED; }
+    // (hulls against a cloud are opt-in, nbk_held_set_cloud_hulls: without the flag refused before a device is touched)
+    if (held->has_hull && !held->cloud_hulls) { snprintf(g_err, sizeof(g_err), "a held object with a hull is not served against point clouds"); return NBK_ERR_UNSUPPORTED; }
     { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
     return cloud_check_device(c);
 }
@@ -1545,9 +1586,11 @@ int32_t nbk_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, 
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
     const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
-    hipLaunchKernelGGL(k_held_cloud_validity, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d, held->d,
-                       cloud_dev(c), q, B, grasp, rows, threshold, (int)accumulate, reinterpret_cast<unsigned long long*>(mask_bits),
-                       mask_bytes);
+    with_flag(held->has_hull, [&](auto HULLS) {
+        hipLaunchKernelGGL(k_held_cloud_validity<decltype(HULLS)::value>, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(),
+                           (hipStream_t)stream, m->d, held->d, cloud_dev(c), q, B, grasp, rows, threshold, (int)accumulate,
+                           reinterpret_cast<unsigned long long*>(mask_bits), mask_bytes);
+    });
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -1623,9 +1666,11 @@ int32_t nbk_edge_held_cloud_validity_batch(const nbk_model* m, const nbk_held* h
     NBK_HIP(hipGetLastError());
     // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
     const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
-    hipLaunchKernelGGL(k_held_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
-                       QSlabLds(m->n_q).bytes(), st, m->d, held->d, cloud_dev(c), es, offs, E, grasp, grasp != nullptr ? 1 : 0, threshold,
-                       valid);
+    with_flag(held->has_hull, [&](auto HULLS) {
+        hipLaunchKernelGGL(k_held_cloud_edges<decltype(HULLS)::value>, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)),
+                           dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, held->d, cloud_dev(c), es, offs, E, grasp,
+                           grasp != nullptr ? 1 : 0, threshold, valid);
+    });
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
@@ -1665,9 +1710,11 @@ int32_t nbk_spline_held_cloud_validity_batch(const nbk_model* m, const nbk_held*
     const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
     const size_t lds = QSlabLds(m->n_q).bytes();
     with_degree(degree, [&](auto K) {
-        hipLaunchKernelGGL(k_held_cloud_spline<decltype(K)::value>, grid, block, lds, st, m->d, held->d, cloud_dev(c), ctrl, (int)n_ctrl,
-                           knots, (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp, grasp != nullptr ? 1 : 0, threshold,
-                           t_prev, v.first);
+        with_flag(held->has_hull, [&](auto HULLS) {
+            hipLaunchKernelGGL((k_held_cloud_spline<decltype(K)::value, decltype(HULLS)::value>), grid, block, lds, st, m->d, held->d,
+                               cloud_dev(c), ctrl, (int)n_ctrl, knots, (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp,
+                               grasp != nullptr ? 1 : 0, threshold, t_prev, v.first);
+        });
     });
     NBK_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
@@ -1844,16 +1891,18 @@ int32_t nbk_spline_held_motion_bounds_hulls_host(const nbk_model_desc* d, int32_
 }
 
 // ---- the host twins of the per-shape bound the held-versus-cloud lanes advance with: motion_terms over the whole holding path for
-// each held shape (HeldCloudEdgeLane::enter, HeldCloudSplineLane::span_bound), with the stored grasp G; no item list, no GPU
-int32_t nbk_edge_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
-                                               const int32_t* shape_type, const double* shape_local, const double* shape_param,
-                                               const double* starts, const double* goals, int64_t E, double* mu) {
+// each held shape (HeldCloudEdgeLane::enter, HeldCloudSplineLane::span_bound), with the stored grasp G; no item list, no GPU.  One body
+// per trajectory kind: the *_hulls_host names pass the hull tables (held_args_check puts them through desc_check's hull rules),
+// the names without them pass none and refuse a hull shape
+static int32_t edge_held_shape_motion_bounds(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                             const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                             const HeldHulls* hl, const double* starts, const double* goals, int64_t E, double* mu) {
     if (E < 0) return NBK_ERR_INVALID;
     MotionHost mh;
     unsigned mask = 0u;
     std::vector<double> tab;
     std::vector<int> items;
-    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, 0, nullptr, nullptr, mh, mask, tab, items);
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, 0, nullptr, nullptr, mh, mask, tab, items, hl);
       if (rc != NBK_OK) return rc; }
     if (E == 0) return NBK_OK;
     if (starts == nullptr || goals == nullptr || mu == nullptr) return NBK_ERR_INVALID;
@@ -1866,16 +1915,31 @@ int32_t nbk_edge_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t 
     return NBK_OK;
 }
 
-int32_t nbk_spline_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
-                                                 const int32_t* shape_type, const double* shape_local, const double* shape_param,
-                                                 const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
-                                                 double* mu) {
+int32_t nbk_edge_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                               const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                               const double* starts, const double* goals, int64_t E, double* mu) {
+    return edge_held_shape_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, nullptr, starts, goals, E, mu);
+}
+
+int32_t nbk_edge_held_shape_motion_bounds_hulls_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                                     const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                                     int32_t n_hulls, const int32_t* hull_vert_begin, const double* hull_verts,
+                                                     const int32_t* hull_face_begin, const double* hull_planes, const double* starts,
+                                                     const double* goals, int64_t E, double* mu) {
+    const HeldHulls hl{n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes};
+    return edge_held_shape_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, &hl, starts, goals, E, mu);
+}
+
+static int32_t spline_held_shape_motion_bounds(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                               const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                               const HeldHulls* hl, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
+                                               const double* knots, double* mu) {
     if (S < 0 || !spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;
     MotionHost mh;
     unsigned mask = 0u;
     std::vector<double> tab;
     std::vector<int> items;
-    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, 0, nullptr, nullptr, mh, mask, tab, items);
+    { const int32_t rc = held_motion_host_begin(d, frame, A, G, H, shape_type, shape_local, shape_param, 0, nullptr, nullptr, mh, mask, tab, items, hl);
       if (rc != NBK_OK) return rc; }
     const int nq = d->n_q, k = degree, L = n_ctrl - degree;
     if (S == 0) return NBK_OK;
@@ -1894,6 +1958,22 @@ int32_t nbk_spline_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_
         }
     }
     return NBK_OK;
+}
+
+int32_t nbk_spline_held_shape_motion_bounds_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                                 const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                                 const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
+                                                 double* mu) {
+    return spline_held_shape_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, nullptr, ctrl, S, n_ctrl, degree, knots, mu);
+}
+
+int32_t nbk_spline_held_shape_motion_bounds_hulls_host(const nbk_model_desc* d, int32_t frame, const double* A, const double* G, int32_t H,
+                                                       const int32_t* shape_type, const double* shape_local, const double* shape_param,
+                                                       int32_t n_hulls, const int32_t* hull_vert_begin, const double* hull_verts,
+                                                       const int32_t* hull_face_begin, const double* hull_planes, const double* ctrl,
+                                                       int64_t S, int32_t n_ctrl, int32_t degree, const double* knots, double* mu) {
+    const HeldHulls hl{n_hulls, hull_vert_begin, hull_verts, hull_face_begin, hull_planes};
+    return spline_held_shape_motion_bounds(d, frame, A, G, H, shape_type, shape_local, shape_param, &hl, ctrl, S, n_ctrl, degree, knots, mu);
 }
 
 }  // extern "C"

@@ -825,10 +825,11 @@ class DeviceModel:
         return held._h
 
     def _held_scanless(self, held):
-        """``_held`` for the held-versus-cloud calls: their kernels decide with routines that know no held hull, so a held mesh
-        is refused here, before the cloud or a device is touched (nbk.h answers NBK_ERR_UNSUPPORTED for it)."""
+        """``_held`` for the held-versus-cloud calls: a held mesh sees scans only where its ``DeviceHeld`` was made with
+        ``scans=True``; without that it is refused here, before the cloud or a device is touched (nbk.h answers
+        NBK_ERR_UNSUPPORTED for it)."""
         h = self._held(held)
-        if held.has_hull:
+        if held.has_hull and not held.sees_scans:
             raise ValueError("held meshes do not see scans yet: the held-versus-cloud calls serve boxes, spheres, capsules and "
                              "cylinders only")
         return h
@@ -1463,11 +1464,13 @@ def held_spline_motion_bounds(model, spec, ctrl, knots, degree, G=None):
     return mu
 
 
-def held_edge_shape_motion_bounds(model, spec, starts, goals, G=None):
+def held_edge_shape_motion_bounds(model, spec, starts, goals, G=None, hulls=False):
     """Motion bounds mu (E, H) of the linear edges starts -> goals for the H shapes of the held object ``spec`` (a ``HeldSpec``) on
     the SceneModel ``model``, every joint of the holding path counting: the bits ``edge_shape_motion_bounds`` gives for robot shapes
     S .. S+H-1 on a model that holds the held shapes as robot shapes.  The routine nbk_edge_held_cloud_continuous_batch advances
-    with, run on the host (nbk_edge_held_shape_motion_bounds_host); no GPU needed.  ``G``: the grasp (default: the spec's)."""
+    with, run on the host (nbk_edge_held_shape_motion_bounds_host); no GPU needed.  ``G``: the grasp (default: the spec's).
+    ``hulls=True``: the spec's hull tables go along (nbk_edge_held_shape_motion_bounds_hulls_host); without it a spec that holds a
+    hull shape is refused, as the held-versus-cloud entries refuse an object that was not opted in."""
     n_q = model.kin.n_q
     s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64)).reshape(-1, n_q)
     g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64)).reshape(-1, n_q)
@@ -1477,16 +1480,25 @@ def held_edge_shape_motion_bounds(model, spec, starts, goals, G=None):
     args, keep2, _ = _held_host_args(model, spec, G)
     H = args[3]
     mu = np.empty((s.shape[0], H), dtype=np.float64)
-    _lib.check(_lib.load().nbk_edge_held_shape_motion_bounds_host(C.byref(d), *args[:7], s.ctypes.data, g.ctypes.data, s.shape[0],
-                                                                  mu.ctypes.data), "nbk_edge_held_shape_motion_bounds_host")
+    tables = getattr(spec, "hulls", None) if hulls else None
+    if tables is None:
+        _lib.check(_lib.load().nbk_edge_held_shape_motion_bounds_host(C.byref(d), *args[:7], s.ctypes.data, g.ctypes.data, s.shape[0],
+                                                                      mu.ctypes.data), "nbk_edge_held_shape_motion_bounds_host")
+    else:
+        hargs, keep3 = _held_hull_args(tables)
+        _lib.check(_lib.load().nbk_edge_held_shape_motion_bounds_hulls_host(C.byref(d), *args[:7], *hargs, s.ctypes.data, g.ctypes.data,
+                                                                            s.shape[0], mu.ctypes.data),
+                   "nbk_edge_held_shape_motion_bounds_hulls_host")
+        del keep3
     del keep, keep2
     return mu
 
 
-def held_spline_shape_motion_bounds(model, spec, ctrl, knots, degree, G=None):
+def held_spline_shape_motion_bounds(model, spec, ctrl, knots, degree, G=None, hulls=False):
     """Motion bounds mu (S, n - degree, H) of S clamped B-splines for the H shapes of the held object ``spec``, per knot span: the
     bits ``spline_shape_motion_bounds`` gives for robot shapes S .. S+H-1 on a model that holds the held shapes as robot shapes
-    (nbk_spline_held_shape_motion_bounds_host; no GPU needed).  Entries of empty spans are 0."""
+    (nbk_spline_held_shape_motion_bounds_host; no GPU needed).  Entries of empty spans are 0.  ``hulls``: as
+    ``held_edge_shape_motion_bounds`` (nbk_spline_held_shape_motion_bounds_hulls_host)."""
     n_q = model.kin.n_q
     c = np.ascontiguousarray(np.asarray(ctrl, dtype=np.float64))
     if c.ndim != 3 or c.shape[2] != n_q:
@@ -1500,8 +1512,16 @@ def held_spline_shape_motion_bounds(model, spec, ctrl, knots, degree, G=None):
     args, keep2, _ = _held_host_args(model, spec, G)
     H = args[3]
     mu = np.zeros((S, n - k, H), dtype=np.float64)
-    _lib.check(_lib.load().nbk_spline_held_shape_motion_bounds_host(C.byref(d), *args[:7], c.ctypes.data, S, n, k, kn.ctypes.data,
-                                                                    mu.ctypes.data), "nbk_spline_held_shape_motion_bounds_host")
+    tables = getattr(spec, "hulls", None) if hulls else None
+    if tables is None:
+        _lib.check(_lib.load().nbk_spline_held_shape_motion_bounds_host(C.byref(d), *args[:7], c.ctypes.data, S, n, k, kn.ctypes.data,
+                                                                        mu.ctypes.data), "nbk_spline_held_shape_motion_bounds_host")
+    else:
+        hargs, keep3 = _held_hull_args(tables)
+        _lib.check(_lib.load().nbk_spline_held_shape_motion_bounds_hulls_host(C.byref(d), *args[:7], *hargs, c.ctypes.data, S, n, k,
+                                                                              kn.ctypes.data, mu.ctypes.data),
+                   "nbk_spline_held_shape_motion_bounds_hulls_host")
+        del keep3
     del keep, keep2
     return mu
 
@@ -1511,9 +1531,11 @@ class DeviceHeld:
     shapes and robot shapes (``SceneModel`` order) its verdict looks at.  ``A``: the link's constant pose in the frame, ``G``: the
     default grasp, ``shape_local`` (H, 4, 4) / (H, 3, 4): each shape in the object's frame; ``shape_type`` / ``shape_param``: as a
     robot shape's.  ``hulls``: the hull tables (vert_begin, verts, face_begin, planes) of held SH_HULL shapes -- given, the object is
-    made by nbk_held_create_hulls; without them a hull shape is refused.  Allocated once; the descriptor is kept alive."""
+    made by nbk_held_create_hulls; without them a hull shape is refused.  ``scans=True``: the held-versus-cloud calls serve the
+    object's hulls too (nbk_held_set_cloud_hulls, set once here; ``sees_scans``); without it they refuse an object that holds one.
+    Allocated once; the descriptor is kept alive."""
 
-    def __init__(self, dev, frame, A, G, shape_type, shape_local, shape_param, world_shapes=(), robot_shapes=(), hulls=None):
+    def __init__(self, dev, frame, A, G, shape_type, shape_local, shape_param, world_shapes=(), robot_shapes=(), hulls=None, scans=False):
         _require_gpu()
         if dev.scene is None:
             raise ValueError("a held object needs a descriptor made from a SceneModel")
@@ -1537,7 +1559,10 @@ class DeviceHeld:
             _lib.check(dev._lib.nbk_held_create_hulls(*args, *hargs, C.byref(h)), "nbk_held_create_hulls")
             del keep
         self._h, self._lib, self.dev, self.n_shapes = h, dev._lib, dev, H
-        self.has_hull = bool(np.any(st == 5))           # (the held-versus-cloud entries refuse such an object)
+        self.has_hull = bool(np.any(st == 5))           # (the held-versus-cloud entries refuse such an object unless it sees scans)
+        self.sees_scans = bool(scans)
+        if self.sees_scans:
+            _lib.check(dev._lib.nbk_held_set_cloud_hulls(h, 1), "nbk_held_set_cloud_hulls")
         self.n_items = int(dev._lib.nbk_held_item_count(h))
 
     def items(self):

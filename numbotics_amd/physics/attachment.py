@@ -9,7 +9,8 @@ again whenever the arm's scene cache is retired.
 
 A held ``Mesh`` is opt-in (``meshes=True``): it is then held as its convex hulls, by the routine link meshes go through, and the spec
 carries their hull tables (``engine.DeviceHeld(..., hulls=...)``, nbk_held_create_hulls).  Such an attachment is served against the
-scene only: the held-versus-cloud calls refuse it ("Held hulls").
+scene; against point clouds it is served only with ``mesh_scans=True`` as well (``engine.DeviceHeld(..., scans=True)``,
+nbk_held_set_cloud_hulls) -- without that flag the held-versus-cloud calls refuse it ("Held hulls").
 
 Geometry: the world pose of held shape h at q is ``F(q) . ((A . G) . L_h)`` -- F the moving frame of the link's joint, A the link's
 constant pose in it (``kin.frames[link].local``), G the grasp, L_h the shape in the object's frame.
@@ -70,7 +71,7 @@ def _pose44(pose, what="pose"):
 
 class Attachment:
 
-    def __init__(self, link, objects, pose, touch_links=(), meshes=False):
+    def __init__(self, link, objects, pose, touch_links=(), meshes=False, mesh_scans=False):
         from .object import PhysicsObject
         from .chain import Link
         if not isinstance(link, Link):
@@ -83,12 +84,16 @@ class Attachment:
         self.pose = _pose44(pose)
         self.touch_links = tuple(getattr(l, "_name", l) for l in touch_links)
         self.meshes = bool(meshes)  # a held Mesh becomes convex hulls (one, or one per file object with convex_decomposition)
+        if mesh_scans and not meshes:
+            raise ValueError("mesh_scans=True needs meshes=True: it lets the convex hulls of a held mesh see point clouds")
+        self.mesh_scans = bool(mesh_scans)  # the hulls of a held Mesh are served against point clouds too
         self._spec = None           # (arm id, scene key, HeldSpec)
         self._dev = None            # (DeviceModel, HeldSpec, DeviceHeld)
 
     @property
     def has_mesh(self):
-        """A held object is a mesh (held as convex hulls): the held-versus-cloud calls refuse the attachment."""
+        """A held object is a mesh (held as convex hulls): the held-versus-cloud calls refuse the attachment unless it was made
+        with ``mesh_scans=True``."""
         return any(o._collision_shape.shape == Shape.MESH for o in self.objects)
 
     def shape_records(self, bullet_margins=True, hulls=None):
@@ -169,7 +174,7 @@ class Attachment:
         _, dev = arm._scene_device()
         if self._dev is None or self._dev[0] is not dev or self._dev[1] is not spec:
             held = DeviceHeld(dev, spec.frame, spec.A, spec.G, spec.shape_type, spec.shape_local, spec.shape_param,
-                              spec.world_shapes, spec.robot_shapes, hulls=spec.hulls)
+                              spec.world_shapes, spec.robot_shapes, hulls=spec.hulls, scans=self.mesh_scans)
             self._dev = (dev, spec, held)
         return dev, self._dev[2]
 

@@ -85,7 +85,7 @@ class ConnectorParams:
             raise ValueError("A held object needs ConnectorParams(arm=...)")
         if self.attached_sees_cloud and (self.arm is None or self.cloud is None or self.attached is None):
             raise ValueError("attached_sees_cloud needs ConnectorParams(arm=..., cloud=..., attached=...)")
-        if self.attached_sees_cloud and getattr(self.attached, "has_mesh", False):
+        if self.attached_sees_cloud and getattr(self.attached, "has_mesh", False) and not getattr(self.attached, "mesh_scans", False):
             raise ValueError("held meshes do not see scans yet: attached_sees_cloud serves boxes, spheres, capsules and cylinders")
 
 
@@ -392,7 +392,7 @@ class ContinuousConnector(Connector):
         _no_held(params, "certified continuous checks")
         if attached_sees_cloud and (cloud is None or attached is None):
             raise ValueError("attached_sees_cloud needs ContinuousConnector(cloud=..., attached=...)")
-        if attached_sees_cloud and getattr(attached, "has_mesh", False):
+        if attached_sees_cloud and getattr(attached, "has_mesh", False) and not getattr(attached, "mesh_scans", False):
             raise ValueError("held meshes do not see scans yet: attached_sees_cloud serves boxes, spheres, capsules and cylinders")
         device_edge = params.arm is not None and params.validity_checker is None and params.trajectory_func is _DEFAULT_TRAJ
         if cloud is not None:

@@ -579,7 +579,7 @@ class Arm(Robot):
         return mask.reshape(tuple(q.shape[:-1]))
 
     # ---- held objects ----------------------------------------------------------------------------------------
-    def attach(self, obj, link, pose=None, touch_links=(), meshes=False):
+    def attach(self, obj, link, pose=None, touch_links=(), meshes=False, mesh_scans=False):
         """Put ``obj`` (a ``PhysicsObject`` of boxes / spheres / capsules / cylinders, or a list of up to 8 of them) into the hand:
         -> an ``Attachment`` (numbotics_amd.physics) of ``obj`` riding on ``link`` (a Link of this chain or its name).  ``pose``
         (4, 4): the grasp, the object's pose in the link frame (for a list: the first object's); default: the object where it
@@ -590,7 +590,9 @@ class Arm(Robot):
         ``in_collision`` does NOT see the held object, and still sees the object's world copy where it is one of this arm's
         obstacles -- park it or ``remove_collision_pair`` it.  ``meshes=True``: a ``Mesh`` may be held too, as its convex hulls -- one,
         or one per object of its file with ``convex_decomposition=True``, by the routine link meshes go through; the hulls count
-        against the 8 shapes.  Such an attachment does not see scans: every ``cloud`` argument of the attached calls refuses it."""
+        against the 8 shapes.  Such an attachment does not see scans by default: every ``cloud`` argument of the attached calls
+        refuses it.  ``mesh_scans=True`` (with ``meshes=True``) opts in: the hulls are then served against point clouds by every
+        attached call that takes a ``cloud`` and by both connectors' ``attached_sees_cloud``."""
         from numbotics_amd.physics import Attachment
         from .model import chain_link_poses
         link = self._resolve(link)
@@ -601,7 +603,7 @@ class Arm(Robot):
             if not objs or not isinstance(objs[0], PhysicsObject):
                 raise ValueError("the held object must be a PhysicsObject or a list of them")
             pose = np.linalg.inv(chain_link_poses(self._chain)[link._name]) @ np.asarray(objs[0].pose, dtype=np.float64)
-        att = Attachment(link, objs, pose, touch_links, meshes=meshes)
+        att = Attachment(link, objs, pose, touch_links, meshes=meshes, mesh_scans=mesh_scans)
         att.spec(self)                                          # argument errors now, not at the first query
         return att
 

@@ -1,6 +1,6 @@
 """Held objects, measured on one GPU (`profiles/held_time.log`).
 
-    python tools/held_time.py [--out profiles/held_time.log] [--reps 5] [--rows 1000000] [--edges 100000] [--only records] [--mesh]
+    python tools/held_time.py [--out profiles/held_time.log] [--reps 5] [--rows 1000000] [--edges 100000] [--only records] [--mesh] [--mesh-cloud]
 
 The c2 and c3 arms with the box of the parity fixtures in the hand (half extents 0.1, 0.1, 0.2, margin 0.04, 0.25 m along the
 gripper's z; H = 1), its world copy parked out of reach.  Timing as tools/cloud_time.py: one HIP event pair around a window of
@@ -29,6 +29,13 @@ alternating.
                 gripper's z) beside the box of the parity fixtures, the windows of the two alternating; then held_distances of
                 both at 65536 rows.  The hull's mask must equal validity(rock as link) with validity(plain) taken out of it, on
                 a descriptor that carries the hull as a robot shape of the gripper's frame with the hull appended to its tables.
+    --mesh-cloud  (log: profiles/held_mesh_cloud_time.log) nothing of the above but what a held hull costs against a scan: the rock
+                (``attach(..., meshes=True, mesh_scans=True)``) beside the parity box on c2, against the dense scan of
+                tools/cloud_time.py at 1e5 points (scan(N, seed=N), radius 0.01), the windows of the two alternating:
+                DeviceModel.held_cloud_validity at --rows configurations (packed words), held_cloud_clearance at --rows / 10
+                (d_max 0.05), and held_cloud_edge_continuous at --ca-edges edges a -> a + U(-0.5, 0.5) (connect mode, look_ahead
+                0.05).  The rock's verdicts must equal cloud_validity of the rock-as-link descriptor selected on that one shape,
+                and its clearance that descriptor's cloud_clearance, bit for bit.
 """
 import argparse
 import dataclasses
@@ -119,6 +126,76 @@ def mesh(say, args):
     say(f"  held_distances, parity box          {fmt(t_b)}   (hull / box: {t_r[0] / t_b[0]:.2f})")
 
 
+def mesh_cloud(say, args):
+    """The --mesh-cloud section: the rock and the parity box against the dense scan at 1e5 points, on c2."""
+    from cloud_time import scan, RADIUS, BOX
+    from numbotics_amd.physics import Mesh, PointCloud
+    from numbotics_amd.scenes import MESH_DIR
+    _reset_worlds()
+    World()
+    arm, chain, obs = build_scene("c2")
+    park = np.array([0.0, 0.0, -6.0])
+    box = Cuboid(0.0, np.array([0.1, 0.1, 0.2]), collision_margin=0.04, position=park.copy())
+    rock = Mesh(0.0, os.path.join(MESH_DIR, "rock.obj"), position=park + np.array([0.0, 1.0, 0.0]))
+    Gb, Gr = np.eye(4), np.eye(4)
+    Gb[2, 3], Gr[2, 3] = 0.25, 0.22
+    att_b = arm.attach(box, "gripper", pose=Gb)
+    att_r = arm.attach(rock, "gripper", pose=Gr, meshes=True, mesh_scans=True)
+    sm, sr = arm.scene_model(), att_r.spec(arm)
+    dev, held_b = att_b._device(arm)
+    _, held_r = att_r._device(arm)
+    N, B, E = 10 ** 5, args.rows, args.ca_edges
+    cloud = PointCloud(torch.from_numpy(scan(N, seed=N)).cuda(), RADIUS, bounds=BOX)
+    qt = torch.from_numpy(sample_q(chain, B, seed=3)).cuda()
+    qc = qt[:B // 10].contiguous()
+    say(f"## c2 --mesh-cloud: N = {N} points, radius {RADIUS}, cell {cloud.cell:.4f}; rock.obj: {sr.n_shapes} hull, "
+        f"{int(sr.hull_vert_begin[-1])} vertices, {int(sr.hull_face_begin[-1])} planes, margin {float(sr.shape_param[0][3])}, bounding "
+        f"radius {float(np.linalg.norm(sr.hull_verts, axis=1).max()):.3f}; the box: 0.1, 0.1, 0.2, margin 0.04, bounding radius 0.245")
+    # the rock as a link shape of a descriptor with no pairs of its own beyond the scene's: cloud_validity / cloud_clearance selected on it
+    sp = sr.shape_param.copy()
+    sp[:, 0] += sm.n_hulls
+    as_link = box_as_link(sm, dataclasses.replace(sr, shape_param=sp))
+    as_link = dataclasses.replace(
+        as_link, hull_vert_begin=np.concatenate((sm.hull_vert_begin, sm.hull_vert_begin[-1] + sr.hull_vert_begin[1:])).astype(np.int32),
+        hull_verts=np.ascontiguousarray(np.concatenate((sm.hull_verts.reshape(-1, 3), sr.hull_verts))),
+        hull_face_begin=np.concatenate((sm.hull_face_begin, sm.hull_face_begin[-1] + sr.hull_face_begin[1:])).astype(np.int32),
+        hull_planes=np.ascontiguousarray(np.concatenate((sm.hull_planes.reshape(-1, 4), sr.hull_planes))))
+    linked = DeviceModel(as_link)
+    one = [sm.n_rshapes]
+    mine = dev.held_cloud_validity(held_r, cloud, qt, 0.0, packed=True)
+    if not torch.equal(mine, linked.cloud_validity(cloud, qt, 0.0, packed=True, shapes=one)):
+        raise SystemExit("held_cloud_validity(rock) != cloud_validity(rock as link, that shape)")
+    d, _, p = dev.held_cloud_clearance(held_r, cloud, qc, 0.05)
+    dl, _, pl = linked.cloud_clearance(cloud, qc, 0.05, shapes=one)
+    if not (torch.equal(d.view(torch.int64), dl.view(torch.int64)) and torch.equal(p, pl)):
+        raise SystemExit("held_cloud_clearance(rock) != cloud_clearance(rock as link, that shape)")
+    share = lambda w: sum(bin(int(v) & 0xFFFFFFFFFFFFFFFF).count("1") for v in w.cpu().numpy()[:1000]) / 64000.0      # noqa: E731
+    say(f"validity  B = {B}: the rock's mask agrees with cloud_validity(rock as link); of the first 64000 rows the rock collides in "
+        f"{share(mine):.3f}, the box in {share(dev.held_cloud_validity(held_b, cloud, qt, 0.0, packed=True)):.3f}")
+    t_r, t_b = timed_pair(lambda: dev.held_cloud_validity(held_r, cloud, qt, 0.0, packed=True),
+                          lambda: dev.held_cloud_validity(held_b, cloud, qt, 0.0, packed=True), args.reps)
+    say(f"  held_cloud_validity, rock.obj (hull)      {fmt(t_r)}")
+    say(f"  held_cloud_validity, parity box           {fmt(t_b)}   (hull / box: {t_r[0] / t_b[0]:.2f})")
+    db = dev.held_cloud_clearance(held_b, cloud, qc, 0.05)[0]
+    say(f"clearance  B = {B // 10}, d_max 0.05: the rock's agrees with cloud_clearance(rock as link); below d_max: rock "
+        f"{float(torch.isfinite(d).float().mean()):.3f}, box {float(torch.isfinite(db).float().mean()):.3f}")
+    t_r, t_b = timed_pair(lambda: dev.held_cloud_clearance(held_r, cloud, qc, 0.05), lambda: dev.held_cloud_clearance(held_b, cloud, qc, 0.05),
+                          args.reps)
+    say(f"  held_cloud_clearance, rock.obj (hull)     {fmt(t_r)}")
+    say(f"  held_cloud_clearance, parity box          {fmt(t_b)}   (hull / box: {t_r[0] / t_b[0]:.2f})")
+    rng = np.random.default_rng(5)
+    st = qt[:E].contiguous()
+    gt = st + torch.from_numpy(rng.uniform(-0.5, 0.5, (E, chain.dof))).cuda()
+    cr = dev.held_cloud_edge_continuous(held_r, cloud, st, gt, 10.0, look_ahead=0.05)
+    cb = dev.held_cloud_edge_continuous(held_b, cloud, st, gt, 10.0, look_ahead=0.05)
+    shares = lambda c: "/".join(str(int((c[3] == k).sum())) for k in (0, 1, 2))      # noqa: E731
+    say(f"certified edges  E = {E}, connect, look_ahead 0.05, max_iter 64: FREE/COLLISION/UNDECIDED rock {shares(cr)}, box {shares(cb)}")
+    t_r, t_b = timed_pair(lambda: dev.held_cloud_edge_continuous(held_r, cloud, st, gt, 10.0, look_ahead=0.05),
+                          lambda: dev.held_cloud_edge_continuous(held_b, cloud, st, gt, 10.0, look_ahead=0.05), args.reps)
+    say(f"  held_cloud_edge_continuous, rock.obj      {fmt(t_r)}")
+    say(f"  held_cloud_edge_continuous, parity box    {fmt(t_b)}   (hull / box: {t_r[0] / t_b[0]:.2f})")
+
+
 def records(say, name, dev, held, linked, qt, P, reps):
     """The --only records section for one scene."""
     B, K, n = int(qt.shape[0]), held.n_items, 16384
@@ -154,9 +231,11 @@ def main():
     ap.add_argument("--edges", type=int, default=100000)
     ap.add_argument("--splines", type=int, default=10000)
     ap.add_argument("--mesh", action="store_true")
+    ap.add_argument("--mesh-cloud", action="store_true")
+    ap.add_argument("--ca-edges", type=int, default=1000)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "held_mesh_time.log" if args.mesh else
+        args.out = os.path.join(ROOT, "profiles", "held_mesh_cloud_time.log" if args.mesh_cloud else "held_mesh_time.log" if args.mesh else
                                 "held_records_time.log" if args.only == "records" else "held_time.log")
     if not torch.cuda.is_available():
         raise SystemExit("tools/held_time.py needs a GPU: nothing is measured without one")
@@ -169,8 +248,8 @@ def main():
         log.flush()
 
     say(f"# tools/held_time.py  build {source_digest()}  {torch.cuda.get_device_name(0)}  rows {args.rows}  edges {args.edges}  reps {args.reps}")
-    if args.mesh:
-        mesh(say, args)
+    if args.mesh_cloud or args.mesh:
+        (mesh_cloud if args.mesh_cloud else mesh)(say, args)
         log.close()
         return
     for name in ("c2", "c3"):
