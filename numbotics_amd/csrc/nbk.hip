@@ -3572,6 +3572,19 @@ __global__ void k_ca_final(int64_t n, const unsigned long long* __restrict__ key
     t_free[e] = __builtin_bit_cast(double, k >> 2);
 }
 
+// the hold of the certified held-object entries, behind an init kernel: CA_KEEP_KEY to every non-degenerate trajectory when the world
+// status is set or the call's grasp (12 values) is not finite (device data both; either may be null), and the walks leave such
+// trajectories alone
+__global__ __launch_bounds__(256) void k_held_ca_hold(const int* __restrict__ wstatus, const double* __restrict__ grasp, int64_t n,
+                                                      unsigned long long* __restrict__ key) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    bool bad = wstatus != nullptr && *wstatus != 0;
+    if (grasp != nullptr)
+        for (int c = 0; c < 12; ++c) bad = bad || !(grasp[c] - grasp[c] == 0.0);
+    if (bad && key[e] != CA_DEGENERATE_KEY) key[e] = CA_KEEP_KEY;
+}
+
 // exclusive prefix sum of cnt[0..E) into offs[0..E], one workgroup of 1024 threads
 __global__ __launch_bounds__(1024) void k_scan(const unsigned long long* __restrict__ cnt, int64_t E, unsigned long long* __restrict__ offs) {
     __shared__ unsigned long long part[1024];
@@ -4908,6 +4921,15 @@ static int32_t launch_spline_ca_init(const nbk_model* m, hipStream_t st, const d
                                      const double* knots, const int* hold, const int32_t* prev, double* t_free) {
     hipLaunchKernelGGL(k_spline_ca_init, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, hold, prev,
                        ca_keys(t_free));
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// k_held_ca_hold behind the init kernel, only where something can be held: wstatus is the world status of a movable descriptor (the
+// held object's own entries), grasp the call's; the held-versus-cloud entries pass no status, the cloud's own neither
+static int32_t launch_held_ca_hold(hipStream_t st, const int* wstatus, const double* grasp, int64_t n, double* t_free) {
+    if (wstatus == nullptr && grasp == nullptr) return NBK_OK;
+    hipLaunchKernelGGL(k_held_ca_hold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wstatus, grasp, n, ca_keys(t_free));
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }

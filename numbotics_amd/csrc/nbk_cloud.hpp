@@ -1353,6 +1353,8 @@ static int32_t cloud_check_device(const nbk_cloud* c) {
 }
 
 static CloudDev cloud_dev(const nbk_cloud* c) { return CloudDev{c->g, c->hdr, c->pts, c->idx, c->start}; }
+// the status word of the cloud (device memory: an address, not a read), which holds the trajectory calls while it is set
+static const int* cloud_status_word(const nbk_cloud* c) { return &c->hdr->status; }
 
 // the caller's selection (bit s of shape_bits = robot shape s of the descriptor it passed to nbk_model_create) in device order
 static CloudSel cloud_selection(const nbk_model* m, const uint64_t* shape_bits) {
@@ -1395,6 +1397,144 @@ static int32_t cloud_call_begin(const nbk_model* m, const nbk_cloud* c, const ui
 // the caller's workspace of the sampled entries: at least `need` bytes (a layout's) at a 64-byte boundary
 static bool cloud_workspace_ok(const void* workspace, int64_t workspace_bytes, size_t need) {
     return workspace_bytes >= (int64_t)need && (reinterpret_cast<uintptr_t>(workspace) & 63) == 0;
+}
+
+// the workspace sizes of the sampled entries (the cloud's, the held object's, the held object's against a cloud: one layout each)
+static int64_t edge_workspace_bytes(int64_t E) { return E < 0 || E > EDGE_CLOUD_MAX_E ? -1 : (int64_t)EdgeCloudLayout(E).bytes; }
+// (a spline entry takes fewer than SPLINE_MAX_S trajectories)
+static int64_t spline_workspace_bytes(int64_t S) { return S < 0 || S >= SPLINE_MAX_S ? -1 : (int64_t)SplineCloudLayout(S).bytes; }
+
+// ---- One call path per entry kind.  The trajectory entries of the three families -- the cloud's here, the held object's and the held
+// object's against a cloud in nbk_held.hpp -- are, kind by kind, one sequence of statements: the routines below.  An entry checks
+// its handles for null and passes what is its own: begin(), the family's *_call_begin (run once the argument rules, "nothing to do"
+// and the size limit are through: those are answered without a device and before the handles are looked at); hold, the status word
+// that holds the call (the cloud's, or a movable descriptor's world status, or null); launch_walk, which launches the family's walk
+// kernel.  Callables, not std::function: nothing allocates on the call path, and these entries are capturable.
+
+// sampled edges: k_edge_plan -> k_scan -> k_cloud_edges_init -> launch_walk(grid, lds, st, es, offs)
+template <class Begin, class Walk>
+static int32_t sampled_edges_call(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
+                                  double resolution, double max_distance, int32_t mode, double threshold, int32_t accumulate,
+                                  uint8_t* valid, double* end, int32_t* n_samples, void* workspace, int64_t workspace_bytes, void* stream,
+                                  Begin&& begin, Walk&& launch_walk) {
+    if (E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
+    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
+        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = begin(); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
+    const unsigned eblocks = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
+                       v.plan, v.cnt, end, n_samples);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, E, v.offs);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_edges_init, dim3(eblocks), dim3(256), 0, st, v.cnt, E, (int)accumulate, valid);
+    NBK_HIP(hipGetLastError());
+    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
+    const EdgeSrc es{starts, goals, v.plan, nullptr, v.offs + E, 0, nullptr};
+    launch_walk(dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), QSlabLds(m->n_q).bytes(), st, es, v.offs);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// sampled splines: k_spline_plan -> k_cloud_spline_init (hold) -> k_scan -> launch_walk(K, grid, lds, st, v, t_prev) ->
+// k_cloud_spline_final
+template <class Begin, class Walk>
+static int32_t sampled_splines_call(const nbk_model* m, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
+                                    double resolution, double threshold, const int* hold, int32_t accumulate, uint8_t* valid,
+                                    double* t_hit, int32_t* n_samples, void* workspace, int64_t workspace_bytes, void* stream,
+                                    Begin&& begin, Walk&& launch_walk) {
+    if (S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
+    if (S > 0 && S < SPLINE_MAX_S &&
+        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
+    if (S == 0) return NBK_OK;
+    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = begin(); if (rc != NBK_OK) return rc; }
+    int cus = 0;                                    // (begin() has found the descriptor's device to be the current one, and the handles')
+    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+    hipStream_t st = (hipStream_t)stream;
+    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
+    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
+    NBK_HIP(hipGetLastError());
+    const double* t_prev = accumulate ? t_hit : nullptr;
+    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt, hold, (int)accumulate,
+                       (const uint8_t*)valid, t_prev, v.first);
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
+    NBK_HIP(hipGetLastError());
+    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
+    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU));
+    const size_t lds = QSlabLds(m->n_q).bytes();
+    with_degree(degree, [&](auto K) { launch_walk(K, grid, lds, st, v, t_prev); });
+    NBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
+                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
+    NBK_HIP(hipGetLastError());
+    return NBK_OK;
+}
+
+// What the two certified routines take besides: look_ahead, null for the held object's own entries, which have none; *items, the
+// family's items per trajectory, read once begin() is through (the walk is skipped at 0); flat: the family's grid is flat, n x *items
+// lanes, which the size limit then counts -- with *items read BEFORE begin(), as the held object's own entries have it; grasp_status
+// and grasp: launch_held_ca_hold's, both null for the cloud's own entries.
+
+// certified edges: k_edge_ca_init (hold, prev when accumulating) -> the grasp hold -> launch_walk(st) -> k_ca_final
+template <class Begin, class Walk>
+static int32_t certified_edges_call(const nbk_model* m, const double* starts, const double* goals, const double* dist, int64_t E,
+                                    double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
+                                    const double* look_ahead, const int* items, bool flat, const int* hold, const int* grasp_status,
+                                    const double* grasp, int32_t accumulate, uint8_t* valid, double* end, double* t_free,
+                                    int32_t* status, void* stream, Begin&& begin, Walk&& launch_walk) {
+    if (E < 0) return NBK_ERR_INVALID;
+    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
+    if (look_ahead != nullptr && !(*look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
+    if (E == 0) return NBK_OK;
+    if (E > 0x7fffffffLL || (flat && (E * (int64_t)*items + WAVE - 1) / WAVE > 0x7fffffffLL)) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = begin(); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, hold, accumulate ? status : nullptr, end, t_free);
+      if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_held_ca_hold(st, grasp_status, grasp, E, t_free); if (rc != NBK_OK) return rc; }
+    if (*items > 0) {
+        launch_walk(st);
+        NBK_HIP(hipGetLastError());
+    }
+    return launch_ca_final(st, E, valid, t_free, status);
+}
+
+// certified splines: k_spline_ca_init (hold, prev when accumulating) -> the grasp hold -> launch_walk(K, lds, st) -> k_ca_final
+template <class Begin, class Walk>
+static int32_t certified_splines_call(const nbk_model* m, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree, const double* knots,
+                                      double threshold, int32_t max_iter, double slack, const double* look_ahead, const int* items,
+                                      bool flat, const int* hold, const int* grasp_status, const double* grasp, int32_t accumulate,
+                                      uint8_t* valid, double* t_free, int32_t* status, void* stream, Begin&& begin, Walk&& launch_walk) {
+    if (S < 0) return NBK_ERR_INVALID;
+    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
+    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
+    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
+    if (look_ahead != nullptr && !(*look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
+    if (S == 0) return NBK_OK;
+    if (S > 0x7fffffffLL || (flat && (S * (int64_t)*items + WAVE - 1) / WAVE > 0x7fffffffLL)) return NBK_ERR_UNSUPPORTED;
+    { const int32_t rc = begin(); if (rc != NBK_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, hold, accumulate ? status : nullptr, t_free);
+      if (rc != NBK_OK) return rc; }
+    { const int32_t rc = launch_held_ca_hold(st, grasp_status, grasp, S, t_free); if (rc != NBK_OK) return rc; }
+    if (*items > 0) {
+        const size_t lds = QSlabLds(m->n_q).bytes();
+        with_degree(degree, [&](auto K) { launch_walk(K, lds, st); });
+        NBK_HIP(hipGetLastError());
+    }
+    return launch_ca_final(st, S, valid, t_free, status);
 }
 
 }  // namespace nbk
@@ -1743,146 +1883,71 @@ int32_t nbk_records_cloud_batch(const nbk_model* m, const nbk_cloud* c, const do
     return NBK_OK;
 }
 
-int64_t nbk_edge_cloud_workspace_bytes(int64_t E) {
-    if (E < 0 || E > EDGE_CLOUD_MAX_E) return -1;
-    return (int64_t)EdgeCloudLayout(E).bytes;
-}
+int64_t nbk_edge_cloud_workspace_bytes(int64_t E) { return edge_workspace_bytes(E); }
 
 int32_t nbk_edge_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* starts, const double* goals, const double* dist,
                                       int64_t E, double resolution, double max_distance, int32_t mode, double threshold,
                                       const uint64_t* shape_bits, int32_t accumulate, uint8_t* valid, double* end, int32_t* n_samples,
                                       void* workspace, int64_t workspace_bytes, void* stream) {
-    // (nothing below dereferences m or c before the argument rules are through: they are answered without a device)
-    if (m == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
-    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
-    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
-        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
-    if (E == 0) return NBK_OK;
-    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    if (m == nullptr || c == nullptr) return NBK_ERR_INVALID;
     CloudSel sel;
-    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
-    double* const plan = v.plan;
-    unsigned long long *const cnt = v.cnt, *const offs = v.offs;
-    const unsigned eblocks = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
-                       plan, cnt, end, n_samples);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cloud_edges_init, dim3(eblocks), dim3(256), 0, st, cnt, E, (int)accumulate, valid);
-    NBK_HIP(hipGetLastError());
-    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
-    const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
-    hipLaunchKernelGGL(k_cloud_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
-                       QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c), sel, es, offs, E, threshold,
-                       valid);
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return sampled_edges_call(
+        m, starts, goals, dist, E, resolution, max_distance, mode, threshold, accumulate, valid, end, n_samples, workspace, workspace_bytes,
+        stream, [&] { return cloud_call_begin(m, c, shape_bits, sel); },
+        [&](dim3 grid, size_t lds, hipStream_t st, const EdgeSrc& es, const unsigned long long* offs) {
+            hipLaunchKernelGGL(k_cloud_edges, grid, dim3(WAVE), lds, st, m->d, cloud_dev(c), sel, es, offs, E, threshold, valid);
+        });
 }
 
 int32_t nbk_edge_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, const double* starts, const double* goals, const double* dist,
                                         int64_t E, double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
                                         double look_ahead, const uint64_t* shape_bits, int32_t accumulate, uint8_t* valid, double* end,
                                         double* t_free, int32_t* status, void* stream) {
-    // (as nbk_edge_cloud_validity_batch: the argument rules are answered without a device)
-    if (m == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
-    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
-    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
-    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
-    if (E == 0) return NBK_OK;
-    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    if (m == nullptr || c == nullptr) return NBK_ERR_INVALID;
     CloudSel sel;
-    int n_sel = 0;
-    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel, &n_sel); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, &c->hdr->status, accumulate ? status : nullptr, end, t_free);
-      if (rc != NBK_OK) return rc; }
-    if (n_sel > 0) {
-        hipLaunchKernelGGL(k_cloud_edge_ca, dim3(blocks_for(E), (unsigned)n_sel), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c),
-                           sel, m->rs_user, starts, goals, dist, E, max_distance, (int)mode, threshold, (int)max_iter, slack, look_ahead,
-                           ca_keys(t_free));
-        NBK_HIP(hipGetLastError());
-    }
-    return launch_ca_final(st, E, valid, t_free, status);
+    int n_sel = 0;                                  // one row of workgroups per selected shape
+    return certified_edges_call(
+        m, starts, goals, dist, E, max_distance, mode, threshold, max_iter, slack, &look_ahead, &n_sel, false, cloud_status_word(c), nullptr,
+        nullptr, accumulate, valid, end, t_free, status, stream, [&] { return cloud_call_begin(m, c, shape_bits, sel, &n_sel); },
+        [&](hipStream_t st) {
+            hipLaunchKernelGGL(k_cloud_edge_ca, dim3(blocks_for(E), (unsigned)n_sel), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, cloud_dev(c),
+                               sel, m->rs_user, starts, goals, dist, E, max_distance, (int)mode, threshold, (int)max_iter, slack, look_ahead,
+                               ca_keys(t_free));
+        });
 }
 
-int64_t nbk_spline_cloud_workspace_bytes(int64_t S) {
-    if (S < 0 || S >= SPLINE_MAX_S) return -1;              // (the entry takes fewer than SPLINE_MAX_S trajectories)
-    return (int64_t)SplineCloudLayout(S).bytes;
-}
+int64_t nbk_spline_cloud_workspace_bytes(int64_t S) { return spline_workspace_bytes(S); }
 
 int32_t nbk_spline_cloud_validity_batch(const nbk_model* m, const nbk_cloud* c, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                         const double* knots, double resolution, double threshold, const uint64_t* shape_bits,
                                         int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples, void* workspace,
                                         int64_t workspace_bytes, void* stream) {
-    // (as nbk_edge_cloud_validity_batch: the argument rules are answered without a device)
-    if (m == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
-    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
-    if (S > 0 && S < SPLINE_MAX_S &&
-        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
-    if (S == 0) return NBK_OK;
-    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
+    if (m == nullptr || c == nullptr) return NBK_ERR_INVALID;
     CloudSel sel;
-    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel); if (rc != NBK_OK) return rc; }
-    int cus = 0;
-    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    hipStream_t st = (hipStream_t)stream;
-    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
-    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
-    NBK_HIP(hipGetLastError());
-    const double* t_prev = accumulate ? t_hit : nullptr;
-    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt,
-                       (const int*)&c->hdr->status, (int)accumulate, (const uint8_t*)valid, t_prev, v.first);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
-    NBK_HIP(hipGetLastError());
-    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
-    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
-    const size_t lds = QSlabLds(m->n_q).bytes();
-    with_degree(degree, [&](auto K) {
-        hipLaunchKernelGGL(k_cloud_spline<decltype(K)::value>, grid, block, lds, st, m->d, cloud_dev(c), sel, ctrl, (int)n_ctrl, knots,
-                           (const double*)v.plan, (const unsigned long long*)v.offs, S, threshold, t_prev, v.first);
-    });
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
-                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    return sampled_splines_call(
+        m, ctrl, S, n_ctrl, degree, knots, resolution, threshold, cloud_status_word(c), accumulate, valid, t_hit, n_samples, workspace,
+        workspace_bytes, stream, [&] { return cloud_call_begin(m, c, shape_bits, sel); },
+        [&](auto K, dim3 grid, size_t lds, hipStream_t st, const SplineCloudLayout::View& v, const double* t_prev) {
+            hipLaunchKernelGGL(k_cloud_spline<decltype(K)::value>, grid, dim3(WAVE), lds, st, m->d, cloud_dev(c), sel, ctrl, (int)n_ctrl, knots,
+                               (const double*)v.plan, (const unsigned long long*)v.offs, S, threshold, t_prev, v.first);
+        });
 }
 
 int32_t nbk_spline_cloud_continuous_batch(const nbk_model* m, const nbk_cloud* c, const double* ctrl, int64_t S, int32_t n_ctrl,
                                           int32_t degree, const double* knots, double threshold, int32_t max_iter, double slack,
                                           double look_ahead, const uint64_t* shape_bits, int32_t accumulate, uint8_t* valid,
                                           double* t_free, int32_t* status, void* stream) {
-    // (the argument rules are answered without a device)
-    if (m == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
-    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
-    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
-    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
-    if (S == 0) return NBK_OK;
-    if (S > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
+    if (m == nullptr || c == nullptr) return NBK_ERR_INVALID;
     CloudSel sel;
     int n_sel = 0;
-    { const int32_t rc = cloud_call_begin(m, c, shape_bits, sel, &n_sel); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, &c->hdr->status, accumulate ? status : nullptr, t_free);
-      if (rc != NBK_OK) return rc; }
-    if (n_sel > 0) {
-        const dim3 grid(blocks_for(S), (unsigned)n_sel), block(WAVE);
-        const size_t lds = QSlabLds(m->n_q).bytes();
-        with_degree(degree, [&](auto K) {
-            hipLaunchKernelGGL(k_cloud_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, cloud_dev(c), sel, m->rs_user, ctrl, S,
-                               (int)n_ctrl, knots, threshold, (int)max_iter, slack, look_ahead, ca_keys(t_free));
+    return certified_splines_call(
+        m, ctrl, S, n_ctrl, degree, knots, threshold, max_iter, slack, &look_ahead, &n_sel, false, cloud_status_word(c), nullptr, nullptr,
+        accumulate, valid, t_free, status, stream, [&] { return cloud_call_begin(m, c, shape_bits, sel, &n_sel); },
+        [&](auto K, size_t lds, hipStream_t st) {
+            hipLaunchKernelGGL(k_cloud_spline_ca<decltype(K)::value>, dim3(blocks_for(S), (unsigned)n_sel), dim3(WAVE), lds, st, m->d,
+                               cloud_dev(c), sel, m->rs_user, ctrl, S, (int)n_ctrl, knots, threshold, (int)max_iter, slack, look_ahead,
+                               ca_keys(t_free));
         });
-        NBK_HIP(hipGetLastError());
-    }
-    return launch_ca_final(st, S, valid, t_free, status);
 }
 
 }  // extern "C"

@@ -225,14 +225,6 @@ __global__ __launch_bounds__(64) void k_held_validity(DevModel m, HeldDev hd, co
 // ---- sampled edges with the held object (nbk_edge_held_validity_batch): k_cloud_edges with the held walk in the cloud walk's place.
 // valid[e] before the walk is k_cloud_edges_init's; one grasp per call; a non-finite grasp or a set world status makes every
 // non-degenerate edge invalid.
-__global__ __launch_bounds__(256) void k_held_edges_init(const unsigned long long* __restrict__ cnt, int64_t E, int accumulate,
-                                                         uint8_t* __restrict__ valid) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const bool ok = cnt[e] != 0ull && cnt[e] <= 0xffffffffull;
-    valid[e] = (ok && (!accumulate || valid[e] != 0)) ? 1 : 0;
-}
-
 __global__ __launch_bounds__(64) void k_held_edges(DevModel m, HeldDev hd, const int* __restrict__ wstatus, EdgeSrc es,
                                                    const unsigned long long* __restrict__ offs, int64_t E,
                                                    const double* __restrict__ grasp, int grasp_rows, double thr, uint8_t* valid) {
@@ -808,18 +800,9 @@ __host__ __device__ inline double held_item_motion_bound(const MotionTab& t, uns
 }
 
 // ---- certified continuous checks with the held object (nbk_edge_held_continuous_batch, nbk_spline_held_continuous_batch): ca_walk on
-// one (trajectory, held item) per lane, item-major.  The init kernels are the scene's; k_held_ca_hold, behind them, gives CA_KEEP_KEY
-// to every non-degenerate trajectory when the world status is set or the call's grasp is not finite (device data both), and the
-// walks leave such trajectories alone.
-__global__ __launch_bounds__(256) void k_held_ca_hold(const int* __restrict__ wstatus, const double* __restrict__ grasp, int64_t n,
-                                                      unsigned long long* __restrict__ key) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    bool bad = wstatus != nullptr && *wstatus != 0;
-    if (grasp != nullptr)
-        for (int c = 0; c < 12; ++c) bad = bad || !(grasp[c] - grasp[c] == 0.0);
-    if (bad && key[e] != CA_DEGENERATE_KEY) key[e] = CA_KEEP_KEY;
-}
+// one (trajectory, held item) per lane, item-major.  The init kernels are the scene's; k_held_ca_hold (nbk.hip), behind them, gives
+// CA_KEEP_KEY to every non-degenerate trajectory when the world status is set or the call's grasp is not finite (device data both),
+// and the walks leave such trajectories alone.
 
 // the linear edge of EdgeLane for one held item (ca_walk's pu and p are both the item)
 struct HeldEdgeLane {
@@ -1119,6 +1102,18 @@ static int32_t held_call_begin(const nbk_model* m, const nbk_held* h) {
     return NBK_OK;
 }
 
+// the status word that holds a held call: the world status of a movable descriptor, else none
+static const int* world_status_word(const nbk_model* m) { return m->movable ? (const int*)m->world_status : (const int*)nullptr; }
+
+// The grasp rule of the row entries, answered without a device: grasp_rows is 0 (the stored grasp), 1 (the call's one row) or B (a row
+// each), and -- where there are rows of q at all -- a grasp is passed exactly when it has rows -> held_grasp_row's code 0 / 1 / 2, or
+// -1 where the rule is broken
+static int held_grasp_rows(const double* grasp, int64_t grasp_rows, int64_t B) {
+    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return -1;
+    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return -1;
+    return grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
+}
+
 static bool held_pose_finite(const double* p) {
     for (int e = 0; e < 12; ++e) if (!(p[e] - p[e] == 0.0)) return false;
     return true;
@@ -1338,57 +1333,33 @@ int32_t nbk_held_validity_batch(const nbk_model* m, const nbk_held* held, const 
                                 int64_t grasp_rows, double threshold, int32_t accumulate, uint64_t* mask_bits, uint8_t* mask_bytes,
                                 void* stream) {
     if (m == nullptr || held == nullptr || B < 0 || threshold != threshold) return NBK_ERR_INVALID;
-    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
-    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     if (B > 0 && (q == nullptr || (mask_bits == nullptr && mask_bytes == nullptr))) return NBK_ERR_INVALID;
     { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
     hipLaunchKernelGGL(k_held_validity, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d, held->d,
-                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, grasp, rows, threshold, (int)accumulate,
+                       world_status_word(m), q, B, grasp, rows, threshold, (int)accumulate,
                        reinterpret_cast<unsigned long long*>(mask_bits), mask_bytes);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
 
-int64_t nbk_edge_held_workspace_bytes(int64_t E) {
-    if (E < 0 || E > EDGE_CLOUD_MAX_E) return -1;
-    return (int64_t)EdgeCloudLayout(E).bytes;
-}
+int64_t nbk_edge_held_workspace_bytes(int64_t E) { return edge_workspace_bytes(E); }
 
 int32_t nbk_edge_held_validity_batch(const nbk_model* m, const nbk_held* held, const double* starts, const double* goals, const double* dist,
                                      int64_t E, double resolution, double max_distance, int32_t mode, double threshold,
                                      const double* grasp, int32_t accumulate, uint8_t* valid, double* end, int32_t* n_samples,
                                      void* workspace, int64_t workspace_bytes, void* stream) {
-    // (nothing below dereferences m or held before the argument rules are through: they are answered without a device)
-    if (m == nullptr || held == nullptr || E < 0) return NBK_ERR_INVALID;
-    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
-    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
-        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
-    if (E == 0) return NBK_OK;
-    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
-    double* const plan = v.plan;
-    unsigned long long *const cnt = v.cnt, *const offs = v.offs;
-    const unsigned eblocks = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
-                       plan, cnt, end, n_samples);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_held_edges_init, dim3(eblocks), dim3(256), 0, st, cnt, E, (int)accumulate, valid);
-    NBK_HIP(hipGetLastError());
-    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
-    const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
-    hipLaunchKernelGGL(k_held_edges, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)), dim3(WAVE),
-                       QSlabLds(m->n_q).bytes(), st, m->d, held->d, m->movable ? (const int*)m->world_status : (const int*)nullptr, es,
-                       offs, E, grasp, grasp != nullptr ? 1 : 0, threshold, valid);
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    if (m == nullptr || held == nullptr) return NBK_ERR_INVALID;
+    return sampled_edges_call(
+        m, starts, goals, dist, E, resolution, max_distance, mode, threshold, accumulate, valid, end, n_samples, workspace, workspace_bytes,
+        stream, [&] { return held_call_begin(m, held); },
+        [&](dim3 grid, size_t lds, hipStream_t st, const EdgeSrc& es, const unsigned long long* offs) {
+            hipLaunchKernelGGL(k_held_edges, grid, dim3(WAVE), lds, st, m->d, held->d, world_status_word(m), es, offs, E, grasp,
+                               grasp != nullptr ? 1 : 0, threshold, valid);
+        });
 }
 
 int32_t nbk_held_item_count(const nbk_held* held) { return held == nullptr ? NBK_ERR_INVALID : held->d.n_items; }
@@ -1405,165 +1376,99 @@ int32_t nbk_held_items(const nbk_held* held, int32_t* out) {
 int32_t nbk_held_distances_batch(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const double* grasp,
                                  int64_t grasp_rows, double* out_d, void* stream) {
     if (m == nullptr || held == nullptr || B < 0) return NBK_ERR_INVALID;
-    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
-    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     const int64_t K = held->d.n_items;
     if (B > 0 && (q == nullptr || (K > 0 && out_d == nullptr))) return NBK_ERR_INVALID;
     { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
     if (B == 0 || K == 0) return NBK_OK;
     if (B > 0x7fffffffLL || (B * K + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
     hipLaunchKernelGGL(k_held_distances, dim3((unsigned)((B * K + WAVE - 1) / WAVE)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream,
-                       m->d, held->d, m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, grasp, rows, out_d);
+                       m->d, held->d, world_status_word(m), q, B, grasp, rows, out_d);
     NBK_HIP(hipGetLastError());
-    return NBK_OK;
-}
-
-// the argument rules the two record entries share, answered without a device: the grasp's, as nbk_held_distances_batch has them
-static int32_t held_records_args(const nbk_model* m, const nbk_held* held, int64_t B, const double* grasp, int64_t grasp_rows) {
-    if (m == nullptr || held == nullptr || B < 0) return NBK_ERR_INVALID;
-    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
-    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
     return NBK_OK;
 }
 
 int32_t nbk_held_records_batch(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const double* grasp,
                                int64_t grasp_rows, double* dist, double* witness, double* jrows, void* stream) {
-    { const int32_t rc = held_records_args(m, held, B, grasp, grasp_rows); if (rc != NBK_OK) return rc; }
+    if (m == nullptr || held == nullptr || B < 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     if (B > 0 && (q == nullptr || dist == nullptr)) return NBK_ERR_INVALID;
     { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
     const int64_t K = held->d.n_items;
     if (B == 0 || K == 0) return NBK_OK;
     if (B > 0x7fffffffLL || (B * K + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
     hipLaunchKernelGGL(k_held_records<false>, dim3((unsigned)((B * K + WAVE - 1) / WAVE)), dim3(WAVE),
                        PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes(), (hipStream_t)stream, m->d, held->d,
-                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, (const int32_t*)nullptr, (int64_t)0, grasp, rows,
-                       dist, witness, jrows);
+                       world_status_word(m), q, B, (const int32_t*)nullptr, (int64_t)0, grasp, rows, dist, witness, jrows);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
 
 int32_t nbk_held_records_items(const nbk_model* m, const nbk_held* held, const double* q, int64_t B, const int32_t* items, int64_t N,
                                const double* grasp, int64_t grasp_rows, double* dist, double* witness, double* jrows, void* stream) {
-    { const int32_t rc = held_records_args(m, held, B, grasp, grasp_rows); if (rc != NBK_OK) return rc; }
+    if (m == nullptr || held == nullptr || B < 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     if (N < 0 || (N > 0 && (items == nullptr || dist == nullptr || (B > 0 && q == nullptr)))) return NBK_ERR_INVALID;
     { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
     if (N == 0) return NBK_OK;
     if (B > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
     hipLaunchKernelGGL(k_held_records<true>, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE),
                        PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes(), (hipStream_t)stream, m->d, held->d,
-                       m->movable ? (const int*)m->world_status : (const int*)nullptr, q, B, items, N, grasp, rows, dist, witness, jrows);
+                       world_status_word(m), q, B, items, N, grasp, rows, dist, witness, jrows);
     NBK_HIP(hipGetLastError());
     return NBK_OK;
 }
 
-// the hold of the certified held entries, behind the scene's init kernel (k_held_ca_hold): only where something can be held
-static int32_t launch_held_ca_hold(const nbk_model* m, hipStream_t st, const double* grasp, int64_t n, double* t_free) {
-    if (!m->movable && grasp == nullptr) return NBK_OK;
-    hipLaunchKernelGGL(k_held_ca_hold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       m->movable ? (const int*)m->world_status : (const int*)nullptr, grasp, n, ca_keys(t_free));
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
-}
-
+// (the certified entries of the held object alone: a flat grid of n x K lanes, K = the object's items, read for the size limit before
+// the handles are looked at; no status holds the init kernel -- the world status and the call's grasp go through the grasp hold)
 int32_t nbk_edge_held_continuous_batch(const nbk_model* m, const nbk_held* held, const double* starts, const double* goals, const double* dist,
                                        int64_t E, double max_distance, int32_t mode, double threshold, int32_t max_iter, double slack,
                                        const double* grasp, int32_t accumulate, uint8_t* valid, double* end, double* t_free, int32_t* status,
                                        void* stream) {
-    // (the argument rules are answered without a device)
-    if (m == nullptr || held == nullptr || E < 0) return NBK_ERR_INVALID;
-    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
-    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
-    if (E == 0) return NBK_OK;
-    const int64_t N = E * (int64_t)held->d.n_items;
-    if (E > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, nullptr, accumulate ? status : nullptr, end, t_free);
-      if (rc != NBK_OK) return rc; }
-    { const int32_t rc = launch_held_ca_hold(m, st, grasp, E, t_free); if (rc != NBK_OK) return rc; }
-    if (N > 0) {
-        hipLaunchKernelGGL(k_held_edge_ca, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, held->d,
-                           starts, goals, dist, E, max_distance, (int)mode, grasp, threshold, (int)max_iter, slack, ca_keys(t_free));
-        NBK_HIP(hipGetLastError());
-    }
-    return launch_ca_final(st, E, valid, t_free, status);
+    if (m == nullptr || held == nullptr) return NBK_ERR_INVALID;
+    return certified_edges_call(
+        m, starts, goals, dist, E, max_distance, mode, threshold, max_iter, slack, nullptr, &held->d.n_items, true, nullptr,
+        world_status_word(m), grasp, accumulate, valid, end, t_free, status, stream, [&] { return held_call_begin(m, held); },
+        [&](hipStream_t st) {
+            const int64_t N = E * (int64_t)held->d.n_items;
+            hipLaunchKernelGGL(k_held_edge_ca, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, held->d,
+                               starts, goals, dist, E, max_distance, (int)mode, grasp, threshold, (int)max_iter, slack, ca_keys(t_free));
+        });
 }
 
 int32_t nbk_spline_held_continuous_batch(const nbk_model* m, const nbk_held* held, const double* ctrl, int64_t S, int32_t n_ctrl,
                                          int32_t degree, const double* knots, double threshold, int32_t max_iter, double slack,
                                          const double* grasp, int32_t accumulate, uint8_t* valid, double* t_free, int32_t* status,
                                          void* stream) {
-    if (m == nullptr || held == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
-    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
-    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
-    if (S == 0) return NBK_OK;
-    const int64_t N = S * (int64_t)held->d.n_items;
-    if (S > 0x7fffffffLL || (N + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, nullptr, accumulate ? status : nullptr, t_free);
-      if (rc != NBK_OK) return rc; }
-    { const int32_t rc = launch_held_ca_hold(m, st, grasp, S, t_free); if (rc != NBK_OK) return rc; }
-    if (N > 0) {
-        const dim3 grid((unsigned)((N + WAVE - 1) / WAVE)), block(WAVE);
-        const size_t lds = QSlabLds(m->n_q).bytes();
-        with_degree(degree, [&](auto K) {
-            hipLaunchKernelGGL(k_held_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, held->d, ctrl, S, (int)n_ctrl, knots, grasp,
-                               threshold, (int)max_iter, slack, ca_keys(t_free));
+    if (m == nullptr || held == nullptr) return NBK_ERR_INVALID;
+    return certified_splines_call(
+        m, ctrl, S, n_ctrl, degree, knots, threshold, max_iter, slack, nullptr, &held->d.n_items, true, nullptr, world_status_word(m), grasp,
+        accumulate, valid, t_free, status, stream, [&] { return held_call_begin(m, held); },
+        [&](auto K, size_t lds, hipStream_t st) {
+            const int64_t N = S * (int64_t)held->d.n_items;
+            hipLaunchKernelGGL(k_held_spline_ca<decltype(K)::value>, dim3((unsigned)((N + WAVE - 1) / WAVE)), dim3(WAVE), lds, st, m->d,
+                               held->d, ctrl, S, (int)n_ctrl, knots, grasp, threshold, (int)max_iter, slack, ca_keys(t_free));
         });
-        NBK_HIP(hipGetLastError());
-    }
-    return launch_ca_final(st, S, valid, t_free, status);
 }
 
-int64_t nbk_spline_held_workspace_bytes(int64_t S) {
-    if (S < 0 || S >= SPLINE_MAX_S) return -1;
-    return (int64_t)SplineCloudLayout(S).bytes;
-}
+int64_t nbk_spline_held_workspace_bytes(int64_t S) { return spline_workspace_bytes(S); }
 
 int32_t nbk_spline_held_validity_batch(const nbk_model* m, const nbk_held* held, const double* ctrl, int64_t S, int32_t n_ctrl, int32_t degree,
                                        const double* knots, double resolution, double threshold, const double* grasp,
                                        int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples, void* workspace,
                                        int64_t workspace_bytes, void* stream) {
-    // (as nbk_spline_cloud_validity_batch: the argument rules are answered without a device)
-    if (m == nullptr || held == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
-    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
-    if (S > 0 && S < SPLINE_MAX_S &&
-        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
-    if (S == 0) return NBK_OK;
-    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_call_begin(m, held); if (rc != NBK_OK) return rc; }
-    int cus = 0;
-    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, held->device));
-    hipStream_t st = (hipStream_t)stream;
-    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
-    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
-    NBK_HIP(hipGetLastError());
-    const double* t_prev = accumulate ? t_hit : nullptr;
-    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt,
-                       m->movable ? (const int*)m->world_status : (const int*)nullptr, (int)accumulate, (const uint8_t*)valid, t_prev, v.first);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
-    NBK_HIP(hipGetLastError());
-    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
-    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
-    const size_t lds = QSlabLds(m->n_q).bytes();
-    with_degree(degree, [&](auto K) {
-        hipLaunchKernelGGL(k_held_spline<decltype(K)::value>, grid, block, lds, st, m->d, held->d, ctrl, (int)n_ctrl, knots,
-                           (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp, grasp != nullptr ? 1 : 0, threshold, t_prev,
-                           v.first);
-    });
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
-                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    if (m == nullptr || held == nullptr) return NBK_ERR_INVALID;
+    return sampled_splines_call(
+        m, ctrl, S, n_ctrl, degree, knots, resolution, threshold, world_status_word(m), accumulate, valid, t_hit, n_samples, workspace,
+        workspace_bytes, stream, [&] { return held_call_begin(m, held); },
+        [&](auto K, dim3 grid, size_t lds, hipStream_t st, const SplineCloudLayout::View& v, const double* t_prev) {
+            hipLaunchKernelGGL(k_held_spline<decltype(K)::value>, grid, dim3(WAVE), lds, st, m->d, held->d, ctrl, (int)n_ctrl, knots,
+                               (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp, grasp != nullptr ? 1 : 0, threshold, t_prev,
+                               v.first);
+        });
 }
 
 // ---- the held object against a point cloud.  What every entry answers once its own argument rules are through: the held object's
@@ -1579,13 +1484,12 @@ int32_t nbk_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, 
                                       const double* grasp, int64_t grasp_rows, double threshold, int32_t accumulate, uint64_t* mask_bits,
                                       uint8_t* mask_bytes, void* stream) {
     if (m == nullptr || held == nullptr || c == nullptr || B < 0 || threshold != threshold) return NBK_ERR_INVALID;
-    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
-    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     if (B > 0 && (q == nullptr || (mask_bits == nullptr && mask_bytes == nullptr))) return NBK_ERR_INVALID;
     { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);      // (held_grasp_row: stored, one row, a row each)
     with_flag(held->has_hull, [&](auto HULLS) {
         hipLaunchKernelGGL(k_held_cloud_validity<decltype(HULLS)::value>, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(),
                            (hipStream_t)stream, m->d, held->d, cloud_dev(c), q, B, grasp, rows, threshold, (int)accumulate,
@@ -1599,13 +1503,12 @@ int32_t nbk_held_cloud_clearance_batch(const nbk_model* m, const nbk_held* held,
                                        const double* grasp, int64_t grasp_rows, double d_max, double* min_dist, int32_t* shape,
                                        int32_t* point, void* stream) {
     if (m == nullptr || held == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0)) return NBK_ERR_INVALID;
-    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
-    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     if (B > 0 && (q == nullptr || min_dist == nullptr)) return NBK_ERR_INVALID;
     { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
     hipLaunchKernelGGL(k_held_cloud_clearance, dim3(blocks_for(B)), dim3(WAVE), QSlabLds(m->n_q).bytes(), (hipStream_t)stream, m->d,
                        held->d, cloud_dev(c), q, B, grasp, rows, d_max, min_dist, shape, point);
     NBK_HIP(hipGetLastError());
@@ -1616,13 +1519,12 @@ int32_t nbk_held_cloud_records_batch(const nbk_model* m, const nbk_held* held, c
                                      const double* grasp, int64_t grasp_rows, double d_max, int32_t per_shape, double* dist,
                                      int32_t* shape, int32_t* point, double* witness, double* jrows, void* stream) {
     if (m == nullptr || held == nullptr || c == nullptr || B < 0 || !(d_max - d_max == 0.0)) return NBK_ERR_INVALID;
-    if (grasp_rows != 0 && grasp_rows != 1 && grasp_rows != B) return NBK_ERR_INVALID;
-    if ((grasp_rows != 0) != (grasp != nullptr) && B > 0) return NBK_ERR_INVALID;
+    const int rows = held_grasp_rows(grasp, grasp_rows, B);
+    if (rows < 0) return NBK_ERR_INVALID;
     if (B > 0 && (q == nullptr || dist == nullptr)) return NBK_ERR_INVALID;
     { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
     if (B == 0) return NBK_OK;
     if ((B + WAVE - 1) / WAVE > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    const int rows = grasp_rows == 0 ? 0 : (grasp_rows == 1 ? 1 : 2);
     const size_t lds = PairItemsLds(m->n_q, jrows != nullptr ? m->n_joints : 0).bytes();
     if (per_shape)
         hipLaunchKernelGGL(k_held_cloud_records<true>, dim3(blocks_for(B), (unsigned)held->d.n_shapes), dim3(WAVE), lds, (hipStream_t)stream,
@@ -1634,153 +1536,76 @@ int32_t nbk_held_cloud_records_batch(const nbk_model* m, const nbk_held* held, c
     return NBK_OK;
 }
 
-int64_t nbk_edge_held_cloud_workspace_bytes(int64_t E) {
-    if (E < 0 || E > EDGE_CLOUD_MAX_E) return -1;
-    return (int64_t)EdgeCloudLayout(E).bytes;
-}
+int64_t nbk_edge_held_cloud_workspace_bytes(int64_t E) { return edge_workspace_bytes(E); }
 
 int32_t nbk_edge_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* starts,
                                            const double* goals, const double* dist, int64_t E, double resolution, double max_distance,
                                            int32_t mode, double threshold, const double* grasp, int32_t accumulate, uint8_t* valid,
                                            double* end, int32_t* n_samples, void* workspace, int64_t workspace_bytes, void* stream) {
-    // (nothing below dereferences m, held or c before the argument rules are through: they are answered without a device)
-    if (m == nullptr || held == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
-    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!edge_args_ok(RULE_RESOLUTION | RULE_THRESHOLD, resolution, max_distance, mode, threshold)) return NBK_ERR_INVALID;
-    if (E > 0 && E <= EDGE_CLOUD_MAX_E &&
-        !cloud_workspace_ok(workspace, workspace_bytes, EdgeCloudLayout(E).bytes)) return NBK_ERR_INVALID;
-    if (E == 0) return NBK_OK;
-    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    const EdgeCloudLayout::View v = EdgeCloudLayout(E).view(workspace);
-    double* const plan = v.plan;
-    unsigned long long *const cnt = v.cnt, *const offs = v.offs;
-    const unsigned eblocks = (unsigned)((E + 255) / 256);
-    hipLaunchKernelGGL(k_edge_plan, dim3(eblocks), dim3(256), 0, st, m->n_q, starts, goals, dist, E, resolution, max_distance, (int)mode,
-                       plan, cnt, end, n_samples);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, cnt, E, offs);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cloud_edges_init, dim3(eblocks), dim3(256), 0, st, cnt, E, (int)accumulate, valid);
-    NBK_HIP(hipGetLastError());
-    // the grid covers the static bound; what lies beyond it is reached by the kernel's stride
-    const EdgeSrc es{starts, goals, plan, nullptr, offs + E, 0, nullptr};
-    with_flag(held->has_hull, [&](auto HULLS) {
-        hipLaunchKernelGGL(k_held_cloud_edges<decltype(HULLS)::value>, dim3((unsigned)(edge_capacity(E, resolution, max_distance) / WAVE)),
-                           dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d, held->d, cloud_dev(c), es, offs, E, grasp,
-                           grasp != nullptr ? 1 : 0, threshold, valid);
-    });
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
+    if (m == nullptr || held == nullptr || c == nullptr) return NBK_ERR_INVALID;
+    return sampled_edges_call(
+        m, starts, goals, dist, E, resolution, max_distance, mode, threshold, accumulate, valid, end, n_samples, workspace, workspace_bytes,
+        stream, [&] { return held_cloud_call_begin(m, held, c); },
+        [&](dim3 grid, size_t lds, hipStream_t st, const EdgeSrc& es, const unsigned long long* offs) {
+            with_flag(held->has_hull, [&](auto HULLS) {
+                hipLaunchKernelGGL(k_held_cloud_edges<decltype(HULLS)::value>, grid, dim3(WAVE), lds, st, m->d, held->d, cloud_dev(c), es, offs,
+                                   E, grasp, grasp != nullptr ? 1 : 0, threshold, valid);
+            });
+        });
 }
 
-int64_t nbk_spline_held_cloud_workspace_bytes(int64_t S) {
-    if (S < 0 || S >= SPLINE_MAX_S) return -1;
-    return (int64_t)SplineCloudLayout(S).bytes;
-}
+int64_t nbk_spline_held_cloud_workspace_bytes(int64_t S) { return spline_workspace_bytes(S); }
 
 int32_t nbk_spline_held_cloud_validity_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* ctrl, int64_t S,
                                              int32_t n_ctrl, int32_t degree, const double* knots, double resolution, double threshold,
                                              const double* grasp, int32_t accumulate, uint8_t* valid, double* t_hit, int32_t* n_samples,
                                              void* workspace, int64_t workspace_bytes, void* stream) {
-    // (as nbk_spline_cloud_validity_batch: the argument rules are answered without a device)
-    if (m == nullptr || held == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || workspace == nullptr)) return NBK_ERR_INVALID;
-    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
-    if (!(resolution > 0.0 && resolution <= 1.7976931348623157e308) || threshold != threshold) return NBK_ERR_INVALID;
-    if (S > 0 && S < SPLINE_MAX_S &&
-        !cloud_workspace_ok(workspace, workspace_bytes, SplineCloudLayout(S).bytes)) return NBK_ERR_INVALID;
-    if (S == 0) return NBK_OK;
-    if (S >= SPLINE_MAX_S) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
-    int cus = 0;
-    NBK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    hipStream_t st = (hipStream_t)stream;
-    const SplineCloudLayout::View v = SplineCloudLayout(S).view(workspace);
-    hipLaunchKernelGGL(k_spline_plan, dim3((unsigned)S), dim3(WAVE), 0, st, m->n_q, ctrl, (int)n_ctrl, (int)degree, knots, resolution, v.plan, v.cnt);
-    NBK_HIP(hipGetLastError());
-    const double* t_prev = accumulate ? t_hit : nullptr;
-    hipLaunchKernelGGL(k_cloud_spline_init, dim3((unsigned)S), dim3(WAVE), 0, st, (int)n_ctrl, (int)degree, knots, v.cnt,
-                       (const int*)&c->hdr->status, (int)accumulate, (const uint8_t*)valid, t_prev, v.first);
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, v.cnt, S, v.offs);
-    NBK_HIP(hipGetLastError());
-    // a grid of fixed size: the sample total is the device's to know, the kernel strides to it
-    const dim3 grid((unsigned)((cus > 0 ? cus : 1) * SPLINE_CLOUD_WAVES_PER_CU)), block(WAVE);
-    const size_t lds = QSlabLds(m->n_q).bytes();
-    with_degree(degree, [&](auto K) {
-        with_flag(held->has_hull, [&](auto HULLS) {
-            hipLaunchKernelGGL((k_held_cloud_spline<decltype(K)::value, decltype(HULLS)::value>), grid, block, lds, st, m->d, held->d,
-                               cloud_dev(c), ctrl, (int)n_ctrl, knots, (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp,
-                               grasp != nullptr ? 1 : 0, threshold, t_prev, v.first);
+    if (m == nullptr || held == nullptr || c == nullptr) return NBK_ERR_INVALID;
+    return sampled_splines_call(
+        m, ctrl, S, n_ctrl, degree, knots, resolution, threshold, cloud_status_word(c), accumulate, valid, t_hit, n_samples, workspace,
+        workspace_bytes, stream, [&] { return held_cloud_call_begin(m, held, c); },
+        [&](auto K, dim3 grid, size_t lds, hipStream_t st, const SplineCloudLayout::View& v, const double* t_prev) {
+            with_flag(held->has_hull, [&](auto HULLS) {
+                hipLaunchKernelGGL((k_held_cloud_spline<decltype(K)::value, decltype(HULLS)::value>), grid, dim3(WAVE), lds, st, m->d, held->d,
+                                   cloud_dev(c), ctrl, (int)n_ctrl, knots, (const double*)v.plan, (const unsigned long long*)v.offs, S, grasp,
+                                   grasp != nullptr ? 1 : 0, threshold, t_prev, v.first);
+            });
         });
-    });
-    NBK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cloud_spline_final, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, (const double*)v.plan,
-                       (const unsigned long long*)v.cnt, (const unsigned long long*)v.first, (int)accumulate, valid, t_hit, n_samples);
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
 }
 
-// the hold of the certified held-versus-cloud entries, behind the scene's init kernel: the call's grasp alone (the stored one is
-// finite by nbk_held_create's rules, and the world status is not read)
-static int32_t launch_held_cloud_ca_hold(hipStream_t st, const double* grasp, int64_t n, double* t_free) {
-    if (grasp == nullptr) return NBK_OK;
-    hipLaunchKernelGGL(k_held_ca_hold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int*)nullptr, grasp, n, ca_keys(t_free));
-    NBK_HIP(hipGetLastError());
-    return NBK_OK;
-}
-
+// (the certified entries against a cloud: one row of workgroups per held shape -- an object holds at least one --; the cloud's status
+// holds the init kernel, and the grasp hold takes the call's grasp alone: the stored one is finite by nbk_held_create's rules, and
+// the world status is not read)
 int32_t nbk_edge_held_cloud_continuous_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* starts,
                                              const double* goals, const double* dist, int64_t E, double max_distance, int32_t mode,
                                              double threshold, int32_t max_iter, double slack, double look_ahead, const double* grasp,
                                              int32_t accumulate, uint8_t* valid, double* end, double* t_free, int32_t* status,
                                              void* stream) {
-    // (the argument rules are answered without a device)
-    if (m == nullptr || held == nullptr || c == nullptr || E < 0) return NBK_ERR_INVALID;
-    if (E > 0 && (starts == nullptr || goals == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
-    if (!edge_args_ok(RULE_CERTIFIED | RULE_THRESHOLD, 0.0, max_distance, mode, threshold, max_iter, slack)) return NBK_ERR_INVALID;
-    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
-    if (E == 0) return NBK_OK;
-    if (E > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    { const int32_t rc = launch_edge_ca_init(m, st, starts, goals, dist, E, max_distance, mode, &c->hdr->status, accumulate ? status : nullptr, end, t_free);
-      if (rc != NBK_OK) return rc; }
-    { const int32_t rc = launch_held_cloud_ca_hold(st, grasp, E, t_free); if (rc != NBK_OK) return rc; }
-    hipLaunchKernelGGL(k_held_cloud_edge_ca, dim3(blocks_for(E), (unsigned)held->d.n_shapes), dim3(WAVE), QSlabLds(m->n_q).bytes(), st, m->d,
-                       held->d, cloud_dev(c), starts, goals, dist, E, max_distance, (int)mode, grasp, threshold, (int)max_iter, slack,
-                       look_ahead, ca_keys(t_free));
-    NBK_HIP(hipGetLastError());
-    return launch_ca_final(st, E, valid, t_free, status);
+    if (m == nullptr || held == nullptr || c == nullptr) return NBK_ERR_INVALID;
+    return certified_edges_call(
+        m, starts, goals, dist, E, max_distance, mode, threshold, max_iter, slack, &look_ahead, &held->d.n_shapes, false,
+        cloud_status_word(c), nullptr, grasp, accumulate, valid, end, t_free, status, stream,
+        [&] { return held_cloud_call_begin(m, held, c); },
+        [&](hipStream_t st) {
+            hipLaunchKernelGGL(k_held_cloud_edge_ca, dim3(blocks_for(E), (unsigned)held->d.n_shapes), dim3(WAVE), QSlabLds(m->n_q).bytes(), st,
+                               m->d, held->d, cloud_dev(c), starts, goals, dist, E, max_distance, (int)mode, grasp, threshold, (int)max_iter,
+                               slack, look_ahead, ca_keys(t_free));
+        });
 }
 
 int32_t nbk_spline_held_cloud_continuous_batch(const nbk_model* m, const nbk_held* held, const nbk_cloud* c, const double* ctrl, int64_t S,
                                                int32_t n_ctrl, int32_t degree, const double* knots, double threshold, int32_t max_iter,
                                                double slack, double look_ahead, const double* grasp, int32_t accumulate, uint8_t* valid,
                                                double* t_free, int32_t* status, void* stream) {
-    // (the argument rules are answered without a device)
-    if (m == nullptr || held == nullptr || c == nullptr || S < 0) return NBK_ERR_INVALID;
-    if (S > 0 && (ctrl == nullptr || knots == nullptr || valid == nullptr || t_free == nullptr || status == nullptr)) return NBK_ERR_INVALID;
-    if (!spline_args_ok(n_ctrl, degree, nullptr)) return NBK_ERR_INVALID;      // (the knots are on the device)
-    if (max_iter < 1 || !(slack >= 0.0) || threshold != threshold) return NBK_ERR_INVALID;
-    if (!(look_ahead > 0.0)) return NBK_ERR_INVALID;                  // NaN included; +inf is served
-    if (S == 0) return NBK_OK;
-    if (S > 0x7fffffffLL) return NBK_ERR_UNSUPPORTED;
-    { const int32_t rc = held_cloud_call_begin(m, held, c); if (rc != NBK_OK) return rc; }
-    hipStream_t st = (hipStream_t)stream;
-    { const int32_t rc = launch_spline_ca_init(m, st, ctrl, S, n_ctrl, degree, knots, &c->hdr->status, accumulate ? status : nullptr, t_free);
-      if (rc != NBK_OK) return rc; }
-    { const int32_t rc = launch_held_cloud_ca_hold(st, grasp, S, t_free); if (rc != NBK_OK) return rc; }
-    const dim3 grid(blocks_for(S), (unsigned)held->d.n_shapes), block(WAVE);
-    const size_t lds = QSlabLds(m->n_q).bytes();
-    with_degree(degree, [&](auto K) {
-        hipLaunchKernelGGL(k_held_cloud_spline_ca<decltype(K)::value>, grid, block, lds, st, m->d, held->d, cloud_dev(c), ctrl, S,
-                           (int)n_ctrl, knots, grasp, threshold, (int)max_iter, slack, look_ahead, ca_keys(t_free));
-    });
-    NBK_HIP(hipGetLastError());
-    return launch_ca_final(st, S, valid, t_free, status);
+    if (m == nullptr || held == nullptr || c == nullptr) return NBK_ERR_INVALID;
+    return certified_splines_call(
+        m, ctrl, S, n_ctrl, degree, knots, threshold, max_iter, slack, &look_ahead, &held->d.n_shapes, false, cloud_status_word(c), nullptr,
+        grasp, accumulate, valid, t_free, status, stream, [&] { return held_cloud_call_begin(m, held, c); },
+        [&](auto K, size_t lds, hipStream_t st) {
+            hipLaunchKernelGGL(k_held_cloud_spline_ca<decltype(K)::value>, dim3(blocks_for(S), (unsigned)held->d.n_shapes), dim3(WAVE), lds,
+                               st, m->d, held->d, cloud_dev(c), ctrl, S, (int)n_ctrl, knots, grasp, threshold, (int)max_iter, slack,
+                               look_ahead, ca_keys(t_free));
+        });
 }
 
 // ---- the host twins of the held motion bound: held_item_motion_bound on the tables motion_tables makes of the descriptor, the

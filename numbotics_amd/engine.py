@@ -534,6 +534,42 @@ class DeviceModel:
             raise ValueError(f"out must be a contiguous CUDA tensor of shape {want} ({'int64' if packed else 'uint8 / bool'})")
         return out
 
+    @staticmethod
+    def _ptr(t):
+        """``data_ptr()`` of an optional device tensor; None stays None (a null pointer)."""
+        return None if t is None else t.data_ptr()
+
+    def _mask_result(self, torch, out, B, packed, device):
+        """The row mask of the verdict calls -- the caller's ``out`` (``_mask_out``) or a fresh one of ``validity``'s form for this
+        ``packed`` -> (mask, pointer to it as packed words or None, pointer to it as bytes or None)."""
+        want = ((B + 63) // 64,) if packed else (B,)
+        if out is not None:
+            res = self._mask_out(torch, out, want, packed)
+        else:
+            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=device)
+        return (res, res.data_ptr(), None) if packed else (res, None, res.data_ptr())
+
+    def _edge_result(self, torch, out, s):
+        """(valid, end, n_samples) of the sampled edge calls that AND into ``out``: valid is the caller's ``out`` (``_mask_out``) or
+        fresh, end and n_samples are fresh."""
+        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
+        return (valid, torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device),
+                torch.empty((s.B,), dtype=torch.int32, device=s.device))
+
+    @staticmethod
+    def _workspace(torch, workspace, size, n, device):
+        """The caller's ``workspace``, or by default ``size(n)`` bytes from torch's caching allocator -> (tensor, its bytes)."""
+        ws = torch.empty((size(n),), dtype=torch.uint8, device=device) if workspace is None else workspace
+        return ws, ws.numel() * ws.element_size()
+
+    @staticmethod
+    def _views(st, out, valid, *rest):
+        """The ending of the calls that reduce into ``out``: the caller's tensors as they are, else ``st.out()`` views of the fresh
+        ones with the verdict as bool."""
+        if out is not None:
+            return (valid,) + rest
+        return (st.out(valid.bool()),) + tuple(st.out(x) for x in rest)
+
     def cloud_validity(self, cloud, q, threshold=0.0, packed=False, shapes=None, out=None):
         """In-collision flags of q against ``cloud`` ALONE (a ``PointCloud``): this descriptor's own pairs and world shapes play no
         part.  Bit for bit the verdict of a descriptor that holds the cloud's points as sphere world shapes paired with the selected
@@ -543,19 +579,11 @@ class DeviceModel:
         torch = _require_gpu()
         qs = _Staged(q, self.n_q)
         bits = self._shape_bits(shapes)
-        want = ((qs.B + 63) // 64,) if packed else (qs.B,)
-        if out is not None:
-            res = self._mask_out(torch, out, want, packed)
-        else:
-            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=qs.device)
-        words, mask = (res, None) if packed else (None, res)
+        res, words, mask = self._mask_result(torch, out, qs.B, packed, qs.device)
         _lib.check(self._lib.nbk_cloud_validity_batch(
             self._h, cloud._h, qs.t.data_ptr(), qs.B, float(threshold), _host_ptr(bits),
-            0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
-            self._stream()), "nbk_cloud_validity_batch")
-        if out is not None:
-            return out
-        return qs.out(words) if packed else qs.out(mask.bool())
+            0 if out is None else 1, words, mask, self._stream()), "nbk_cloud_validity_batch")
+        return out if out is not None else qs.out(res if packed else res.bool())
 
     def cloud_self_filter(self, points, q0, radius, padding=0.0, keep=None, shapes=None):
         """Take the robot's own image out of a frame's points (nbk_frame_cloud_self_filter): ``keep[i]`` goes to 0 iff point i, as a
@@ -681,8 +709,8 @@ class DeviceModel:
         if d.numel() > 0:
             _lib.check(self._lib.nbk_records_cloud_batch(
                 self._h, cloud._h, qs.t.data_ptr(), qs.B, float(d_max), _host_ptr(bits), 1 if per_shape else 0,
-                d.data_ptr(), sh.data_ptr(), pt.data_ptr(), None if w is None else w.data_ptr(),
-                None if j is None else j.data_ptr(), self._stream()), "nbk_records_cloud_batch")
+                d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._ptr(w),
+                self._ptr(j), self._stream()), "nbk_records_cloud_batch")
         return qs.out(d), qs.out(sh), qs.out(pt), None if w is None else qs.out(w), None if j is None else qs.out(j)
 
     def pair_distances(self, q, witness=False):
@@ -691,7 +719,7 @@ class DeviceModel:
         d = torch.empty((qs.B, self.n_pairs), dtype=torch.float64, device=qs.device)
         w = torch.empty((qs.B, self.n_pairs, 9), dtype=torch.float64, device=qs.device) if witness else None
         _lib.check(self._lib.nbk_pair_distances_batch(self._h, qs.t.data_ptr(), qs.B, d.data_ptr(),
-                                                      None if w is None else w.data_ptr(), self._stream()),
+                                                      self._ptr(w), self._stream()),
                    "nbk_pair_distances_batch")
         return (qs.out(d), qs.out(w)) if witness else qs.out(d)
 
@@ -721,7 +749,7 @@ class DeviceModel:
         w = torch.empty((N, 9), dtype=torch.float64, device=qt.device) if witness else None
         j = torch.empty((N, self.n_q), dtype=torch.float64, device=qt.device) if jacobian else None
         _lib.check(self._lib.nbk_pair_records_items(self._h, qt.data_ptr(), B, it.data_ptr(), N, d.data_ptr(),
-                                                    None if w is None else w.data_ptr(), None if j is None else j.data_ptr(),
+                                                    self._ptr(w), self._ptr(j),
                                                     self._stream()), "nbk_pair_records_items")
         return d, w, j
 
@@ -789,16 +817,14 @@ class DeviceModel:
         torch = _require_gpu()
         s, g, dd = self._stage_edges(starts, goals, dist)
         bits = self._shape_bits(shapes)
-        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
-        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
-        ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
-        ws = torch.empty((self.cloud_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device) if workspace is None else workspace
+        valid, end, ns = self._edge_result(torch, out, s)
+        ws, ws_bytes = self._workspace(torch, workspace, self.cloud_edge_workspace_bytes, s.B, s.device)
         _lib.check(self._lib.nbk_edge_cloud_validity_batch(
             self._h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
             float(max_distance), _mode_int(mode), float(threshold), _host_ptr(bits),
-            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws_bytes,
             self._stream()), "nbk_edge_cloud_validity_batch")
-        return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
+        return self._views(s, out, valid)[0], s.out(end), s.out(ns)
 
     # ---- held objects (physics/attachment.py) ------------------------------------------------------------
     def _grasp(self, torch, pose, B, per_row):
@@ -846,19 +872,11 @@ class DeviceModel:
         h = self._held(held)
         qs = _Staged(q, self.n_q)
         g, rows = self._grasp(torch, pose, qs.B, True)
-        want = ((qs.B + 63) // 64,) if packed else (qs.B,)
-        if out is not None:
-            res = self._mask_out(torch, out, want, packed)
-        else:
-            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=qs.device)
-        words, mask = (res, None) if packed else (None, res)
+        res, words, mask = self._mask_result(torch, out, qs.B, packed, qs.device)
         _lib.check(self._lib.nbk_held_validity_batch(
-            self._h, h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(threshold),
-            0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
-            self._stream()), "nbk_held_validity_batch")
-        if out is not None:
-            return out
-        return qs.out(words) if packed else qs.out(mask.bool())
+            self._h, h, qs.t.data_ptr(), qs.B, self._ptr(g), rows, float(threshold),
+            0 if out is None else 1, words, mask, self._stream()), "nbk_held_validity_batch")
+        return out if out is not None else qs.out(res if packed else res.bool())
 
     @staticmethod
     def held_edge_workspace_bytes(E: int) -> int:
@@ -874,16 +892,14 @@ class DeviceModel:
         h = self._held(held)
         s, g, dd = self._stage_edges(starts, goals, dist)
         gr, _ = self._grasp(torch, pose, s.B, False)
-        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
-        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
-        ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
-        ws = torch.empty((self.held_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device) if workspace is None else workspace
+        valid, end, ns = self._edge_result(torch, out, s)
+        ws, ws_bytes = self._workspace(torch, workspace, self.held_edge_workspace_bytes, s.B, s.device)
         _lib.check(self._lib.nbk_edge_held_validity_batch(
             self._h, h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
-            float(max_distance), _mode_int(mode), float(threshold), None if gr is None else gr.data_ptr(),
-            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            float(max_distance), _mode_int(mode), float(threshold), self._ptr(gr),
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws_bytes,
             self._stream()), "nbk_edge_held_validity_batch")
-        return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
+        return self._views(s, out, valid)[0], s.out(end), s.out(ns)
 
     def held_distances(self, held, q, pose=None):
         """Signed distances of the items of ``held`` at q (nbk_held_distances_batch) -> (B, K): column k is item k of
@@ -896,7 +912,7 @@ class DeviceModel:
         g, rows = self._grasp(torch, pose, qs.B, True)
         d = torch.empty((qs.B, held.n_items), dtype=torch.float64, device=qs.device)
         _lib.check(self._lib.nbk_held_distances_batch(
-            self._h, h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, d.data_ptr(), self._stream()),
+            self._h, h, qs.t.data_ptr(), qs.B, self._ptr(g), rows, d.data_ptr(), self._stream()),
             "nbk_held_distances_batch")
         return qs.out(d)
 
@@ -919,7 +935,7 @@ class DeviceModel:
         d = torch.empty(lead, dtype=torch.float64, device=qt.device)
         w = torch.empty(lead + (9,), dtype=torch.float64, device=qt.device) if witness else None
         j = torch.empty(lead + (self.n_q,), dtype=torch.float64, device=qt.device) if jacobian else None
-        gp, wp, jp = None if g is None else g.data_ptr(), None if w is None else w.data_ptr(), None if j is None else j.data_ptr()
+        gp, wp, jp = self._ptr(g), self._ptr(w), self._ptr(j)
         if d.numel() == 0:
             return d, w, j
         if it is None:
@@ -966,7 +982,7 @@ class DeviceModel:
                     qs.out(torch.zeros((B, self.n_q), dtype=torch.float64, device=qs.device)))
         d = torch.empty((B, K), dtype=torch.float64, device=qs.device)
         _lib.check(self._lib.nbk_held_distances_batch(
-            self._h, held._h, qs.t.data_ptr(), B, None if g is None else g.data_ptr(), rows, d.data_ptr(), self._stream()),
+            self._h, held._h, qs.t.data_ptr(), B, self._ptr(g), rows, d.data_ptr(), self._stream()),
             "nbk_held_distances_batch")
         bad = torch.isnan(d).any(dim=1)
         dmin = d.min(dim=1, keepdim=True).values
@@ -993,12 +1009,11 @@ class DeviceModel:
         end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
         _lib.check(self._lib.nbk_edge_held_continuous_batch(
             self._h, h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
-            _mode_int(mode), float(threshold), int(max_iter), float(slack), None if gr is None else gr.data_ptr(),
+            _mode_int(mode), float(threshold), int(max_iter), float(slack), self._ptr(gr),
             0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(), status.data_ptr(), self._stream()),
             "nbk_edge_held_continuous_batch")
-        if out is not None:
-            return valid, s.out(end), t_free, status
-        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
+        valid, t_free, status = self._views(s, out, valid, t_free, status)
+        return valid, s.out(end), t_free, status
 
     @staticmethod
     def held_spline_workspace_bytes(S: int) -> int:
@@ -1017,14 +1032,12 @@ class DeviceModel:
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         gr, _ = self._grasp(torch, pose, S, False)
         valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
-        ws = torch.empty((self.held_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device) if workspace is None else workspace
+        ws, ws_bytes = self._workspace(torch, workspace, self.held_spline_workspace_bytes, S, c.device)
         _lib.check(self._lib.nbk_spline_held_validity_batch(
             self._h, h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
-            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
-            ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_held_validity_batch")
-        if out is not None:
-            return valid, t_hit, ns
-        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+            self._ptr(gr), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
+            ws.data_ptr(), ws_bytes, self._stream()), "nbk_spline_held_validity_batch")
+        return self._views(c, out, valid, t_hit, ns)
 
     def held_spline_continuous(self, held, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6, pose=None, out=None):
         """``spline_continuous``'s trajectories certified for the held object ``held`` ALONE (nbk_spline_held_continuous_batch) ->
@@ -1037,11 +1050,9 @@ class DeviceModel:
         valid, t_free, status = self._result_triple(torch, out, S, c.device, "(valid, t_free, status)")
         _lib.check(self._lib.nbk_spline_held_continuous_batch(
             self._h, h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
-            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_free.data_ptr(), status.data_ptr(),
+            self._ptr(gr), 0 if out is None else 1, valid.data_ptr(), t_free.data_ptr(), status.data_ptr(),
             self._stream()), "nbk_spline_held_continuous_batch")
-        if out is not None:
-            return valid, t_free, status
-        return c.out(valid.bool()), c.out(t_free), c.out(status)
+        return self._views(c, out, valid, t_free, status)
 
     # ---- held objects against point clouds --------------------------------------------------------------
     def held_cloud_validity(self, held, cloud, q, threshold=0.0, packed=False, pose=None, out=None):
@@ -1055,19 +1066,11 @@ class DeviceModel:
         h = self._held_scanless(held)
         qs = _Staged(q, self.n_q)
         g, rows = self._grasp(torch, pose, qs.B, True)
-        want = ((qs.B + 63) // 64,) if packed else (qs.B,)
-        if out is not None:
-            res = self._mask_out(torch, out, want, packed)
-        else:
-            res = torch.empty(want, dtype=torch.int64 if packed else torch.uint8, device=qs.device)
-        words, mask = (res, None) if packed else (None, res)
+        res, words, mask = self._mask_result(torch, out, qs.B, packed, qs.device)
         _lib.check(self._lib.nbk_held_cloud_validity_batch(
-            self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(threshold),
-            0 if out is None else 1, None if words is None else words.data_ptr(), None if mask is None else mask.data_ptr(),
-            self._stream()), "nbk_held_cloud_validity_batch")
-        if out is not None:
-            return out
-        return qs.out(words) if packed else qs.out(mask.bool())
+            self._h, h, cloud._h, qs.t.data_ptr(), qs.B, self._ptr(g), rows, float(threshold),
+            0 if out is None else 1, words, mask, self._stream()), "nbk_held_cloud_validity_batch")
+        return out if out is not None else qs.out(res if packed else res.bool())
 
     def held_cloud_clearance(self, held, cloud, q, d_max, pose=None):
         """Per configuration the smallest signed distance from the held object to ``cloud`` when it is below ``d_max``
@@ -1082,7 +1085,7 @@ class DeviceModel:
         sh = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
         pt = torch.empty((qs.B,), dtype=torch.int32, device=qs.device)
         _lib.check(self._lib.nbk_held_cloud_clearance_batch(
-            self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(d_max),
+            self._h, h, cloud._h, qs.t.data_ptr(), qs.B, self._ptr(g), rows, float(d_max),
             d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._stream()), "nbk_held_cloud_clearance_batch")
         return qs.out(d), qs.out(sh), qs.out(pt)
 
@@ -1107,9 +1110,9 @@ class DeviceModel:
         j = torch.empty(lead + (self.n_q,), dtype=torch.float64, device=qs.device) if jacobian else None
         if d.numel() > 0:
             _lib.check(self._lib.nbk_held_cloud_records_batch(
-                self._h, h, cloud._h, qs.t.data_ptr(), qs.B, None if g is None else g.data_ptr(), rows, float(d_max),
-                1 if per_shape else 0, d.data_ptr(), sh.data_ptr(), pt.data_ptr(), None if w is None else w.data_ptr(),
-                None if j is None else j.data_ptr(), self._stream()), "nbk_held_cloud_records_batch")
+                self._h, h, cloud._h, qs.t.data_ptr(), qs.B, self._ptr(g), rows, float(d_max),
+                1 if per_shape else 0, d.data_ptr(), sh.data_ptr(), pt.data_ptr(), self._ptr(w),
+                self._ptr(j), self._stream()), "nbk_held_cloud_records_batch")
         return qs.out(d), qs.out(sh), qs.out(pt), None if w is None else qs.out(w), None if j is None else qs.out(j)
 
     @staticmethod
@@ -1126,17 +1129,14 @@ class DeviceModel:
         h = self._held_scanless(held)
         s, g, dd = self._stage_edges(starts, goals, dist)
         gr, _ = self._grasp(torch, pose, s.B, False)
-        valid = torch.empty((s.B,), dtype=torch.uint8, device=s.device) if out is None else self._mask_out(torch, out, (s.B,))
-        end = torch.empty((s.B, self.n_q), dtype=torch.float64, device=s.device)
-        ns = torch.empty((s.B,), dtype=torch.int32, device=s.device)
-        ws = (torch.empty((self.held_cloud_edge_workspace_bytes(s.B),), dtype=torch.uint8, device=s.device)
-              if workspace is None else workspace)
+        valid, end, ns = self._edge_result(torch, out, s)
+        ws, ws_bytes = self._workspace(torch, workspace, self.held_cloud_edge_workspace_bytes, s.B, s.device)
         _lib.check(self._lib.nbk_edge_held_cloud_validity_batch(
             self._h, h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(resolution),
-            float(max_distance), _mode_int(mode), float(threshold), None if gr is None else gr.data_ptr(),
-            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            float(max_distance), _mode_int(mode), float(threshold), self._ptr(gr),
+            0 if out is None else 1, valid.data_ptr(), end.data_ptr(), ns.data_ptr(), ws.data_ptr(), ws_bytes,
             self._stream()), "nbk_edge_held_cloud_validity_batch")
-        return (out if out is not None else s.out(valid.bool())), s.out(end), s.out(ns)
+        return self._views(s, out, valid)[0], s.out(end), s.out(ns)
 
     @staticmethod
     def held_cloud_spline_workspace_bytes(S: int) -> int:
@@ -1152,15 +1152,12 @@ class DeviceModel:
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         gr, _ = self._grasp(torch, pose, S, False)
         valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
-        ws = (torch.empty((self.held_cloud_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device)
-              if workspace is None else workspace)
+        ws, ws_bytes = self._workspace(torch, workspace, self.held_cloud_spline_workspace_bytes, S, c.device)
         _lib.check(self._lib.nbk_spline_held_cloud_validity_batch(
             self._h, h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
-            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
-            ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_held_cloud_validity_batch")
-        if out is not None:
-            return valid, t_hit, ns
-        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+            self._ptr(gr), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
+            ws.data_ptr(), ws_bytes, self._stream()), "nbk_spline_held_cloud_validity_batch")
+        return self._views(c, out, valid, t_hit, ns)
 
     def held_cloud_edge_continuous(self, held, cloud, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64,
                                    slack=1e-6, look_ahead=CLOUD_LOOK_AHEAD, dist=None, pose=None, out=None):
@@ -1182,11 +1179,10 @@ class DeviceModel:
         _lib.check(self._lib.nbk_edge_held_cloud_continuous_batch(
             self._h, h, cloud._h, s.t.data_ptr(), g.t.data_ptr(), None if dd is None else dd.t.data_ptr(), s.B, float(max_distance),
             _mode_int(mode), float(threshold), int(max_iter), float(slack), float(look_ahead),
-            None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
+            self._ptr(gr), 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
             status.data_ptr(), self._stream()), "nbk_edge_held_cloud_continuous_batch")
-        if out is not None:
-            return valid, s.out(end), t_free, status
-        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
+        valid, t_free, status = self._views(s, out, valid, t_free, status)
+        return valid, s.out(end), t_free, status
 
     def held_cloud_spline_continuous(self, held, cloud, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6,
                                      look_ahead=CLOUD_LOOK_AHEAD, pose=None, out=None):
@@ -1201,11 +1197,9 @@ class DeviceModel:
         valid, t_free, status = self._result_triple(torch, out, S, c.device, "(valid, t_free, status)")
         _lib.check(self._lib.nbk_spline_held_cloud_continuous_batch(
             self._h, h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
-            float(look_ahead), None if gr is None else gr.data_ptr(), 0 if out is None else 1, valid.data_ptr(), t_free.data_ptr(),
+            float(look_ahead), self._ptr(gr), 0 if out is None else 1, valid.data_ptr(), t_free.data_ptr(),
             status.data_ptr(), self._stream()), "nbk_spline_held_cloud_continuous_batch")
-        if out is not None:
-            return valid, t_free, status
-        return c.out(valid.bool()), c.out(t_free), c.out(status)
+        return self._views(c, out, valid, t_free, status)
 
     def edge_continuous(self, starts, goals, max_distance, mode="connect", threshold=0.0, max_iter=64, slack=1e-6, dist=None):
         """Certified continuous check of the linear edges starts -> goals (nbk_edge_continuous_batch) ->
@@ -1241,9 +1235,8 @@ class DeviceModel:
             _mode_int(mode), float(threshold), int(max_iter), float(slack), float(look_ahead),
             _host_ptr(bits), 0 if out is None else 1, valid.data_ptr(), end.data_ptr(), t_free.data_ptr(),
             status.data_ptr(), self._stream()), "nbk_edge_cloud_continuous_batch")
-        if out is not None:
-            return valid, s.out(end), t_free, status
-        return s.out(valid.bool()), s.out(end), s.out(t_free), s.out(status)
+        valid, t_free, status = self._views(s, out, valid, t_free, status)
+        return valid, s.out(end), t_free, status
 
     def spline_validity(self, ctrl, knots, degree, resolution, threshold=0.0):
         """Sampled check of S clamped B-splines sharing one knot vector (nbk_spline_validity_batch): ctrl (S, n, n_q), knots
@@ -1327,14 +1320,12 @@ class DeviceModel:
         c, kn, S, n = self._stage_splines(ctrl, knots, degree)
         bits = self._shape_bits(shapes)
         valid, t_hit, ns = self._result_triple(torch, out, S, c.device, "(valid, t_hit, n_samples)")
-        ws = torch.empty((self.cloud_spline_workspace_bytes(S),), dtype=torch.uint8, device=c.device) if workspace is None else workspace
+        ws, ws_bytes = self._workspace(torch, workspace, self.cloud_spline_workspace_bytes, S, c.device)
         _lib.check(self._lib.nbk_spline_cloud_validity_batch(
             self._h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(resolution), float(threshold),
             _host_ptr(bits), 0 if out is None else 1, valid.data_ptr(), t_hit.data_ptr(), ns.data_ptr(),
-            ws.data_ptr(), ws.numel() * ws.element_size(), self._stream()), "nbk_spline_cloud_validity_batch")
-        if out is not None:
-            return valid, t_hit, ns
-        return c.out(valid.bool()), c.out(t_hit), c.out(ns)
+            ws.data_ptr(), ws_bytes, self._stream()), "nbk_spline_cloud_validity_batch")
+        return self._views(c, out, valid, t_hit, ns)
 
     def cloud_spline_continuous(self, cloud, ctrl, knots, degree, threshold=0.0, max_iter=64, slack=1e-6, look_ahead=CLOUD_LOOK_AHEAD,
                                 shapes=None, out=None):
@@ -1352,9 +1343,7 @@ class DeviceModel:
             self._h, cloud._h, c.t.data_ptr(), S, n, int(degree), kn.data_ptr(), float(threshold), int(max_iter), float(slack),
             float(look_ahead), _host_ptr(bits), 0 if out is None else 1, valid.data_ptr(),
             t_free.data_ptr(), status.data_ptr(), self._stream()), "nbk_spline_cloud_continuous_batch")
-        if out is not None:
-            return valid, t_free, status
-        return c.out(valid.bool()), c.out(t_free), c.out(status)
+        return self._views(c, out, valid, t_free, status)
 
 
 def held_locals(A, G, L):
